@@ -1,6 +1,10 @@
 """bench.py -- the driver's benchmark contract for the WaveRNN mel->wav hot path.
 
-    python bench.py --gpus N --steps K --warmup W [--config {1,2,4,3}]
+    python bench.py --gpus N --steps K --warmup W [--config {1,2,4,3}] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step if --dump-outputs is given, and
+prints the result line; everything else it can measure (the extra legs, the CPU baselines, the measured HBM peaks) runs
+only with --full.
 
 `python bench.py --gpus N` launches its own N ranks (re-exec under torch.distributed.run, one rank per GPU, RCCL);
 started under torch.distributed.run it uses the ranks it is given (`--gpus` then defaults to WORLD_SIZE).
@@ -20,15 +24,20 @@ One "step" = one pass of the hot path over one batch of synthetic input resident
 metric = audio ksamples/s (all loop steps of all rows counted, like the reference's own "Gen Rate" meter,
 fatchord_version.py:267-271), whole job over all N GPUs; weak scaling (the per-GPU batch is fixed).
 
-The headline fields are the selected config's.  The default run (config 1, N=1) additionally times configs[2] and [4] for a
+The headline fields are the selected config's.  A --full run (config 1, N=1) additionally times configs[2] and [4] for a
 few steps and attaches them as `extra_configs` {"2": {...}, "4": {...}} to the same JSON line (~10 s), plus "fold_auto": ONE 5 s utterance
 in the reference's fold mode with target='auto' (the latency-optimal fold count: single-utterance latency), "fold_hp_defaults" (the
 reference's own target 11000 / overlap 550) and "fold_per_xcd" (one fold per XCD team: rounds 4-5's 'auto'), "dm": the secondary
 dual-softmax model (deepmind_version.py:75-165; 50 000 samples) and "train_step": the training step of the loop
-layers (`wrnn_train_step`) at the reference's training shape (~1 s each).  A run on N > 1
+layers (`wrnn_train_step`) at the reference's training shape (~1 s each).  A --full run on N > 1
 GPUs (config 1) attaches `extra_configs` {"3": {...}}: BASELINE configs[3] (64 clips per GPU, scatter / gather over RCCL) at that N.
 
-Extra objects on the JSON line:
+--dump-outputs DIR (rank 0): what the last timed step computed, as DIR/<name>.npy -- `wave` (float64, the waveform generate() returns,
+one row per utterance; for --config 3 the waveforms gathered from every rank), `samples` (float32, the loop's output rows; not for
+--config 3) and `rows` (float64, the utterance indices of the rows written).  Above 64 MB in all, a fixed seeded subset of the rows is
+written.  Inputs (weights, mels, sampling seeds) are seeded, so the same arguments give the same inputs in every run.
+
+Extra objects on the JSON line (`peak_measured*` of roofline, cpu_baseline, cpu_port and cpu_reference with --full only):
   roofline      -- ALGORITHMIC bytes (weights once per step for the whole batch + 836 B conditioning/sample, SURVEY.md
                    8d) or FLOPs (8 668 160 per sample RAW) x steps per launch / the loop kernel's average launch duration
                    (HIP events recorded by the library on the launch stream), against the bound SURVEY 8d names for the
@@ -371,8 +380,26 @@ def self_launch(args) -> int:
     return subprocess.call(cmd, env=env)
 
 
+DUMP_LIMIT = 64_000_000   # bytes: --dump-outputs writes a fixed, seeded subset of the rows above this
+
+
+def write_outputs(out_dir: str, arrays: dict) -> None:
+    """`arrays`: name -> (rows, ...) float32 / float64 arrays with the same rows.  Writes out_dir/<name>.npy and out_dir/rows.npy (the row
+    indices kept); when all of it would exceed DUMP_LIMIT, a seeded subset of the rows (the same for every name) is kept."""
+    n = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(a[0].nbytes for a in arrays.values()) + 8
+    keep = max(1, min(n, DUMP_LIMIT // row_bytes))
+    idx = np.arange(n) if keep == n else np.sort(np.random.Generator(np.random.PCG64(0)).choice(n, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, f'{name}.npy'), np.ascontiguousarray(a[idx]))
+    np.save(os.path.join(out_dir, 'rows.npy'), idx.astype(np.float64))
+
+
 def run_config(cfg_id: int, *, world: int, rank: int, dev, dry: bool, steps: int, warmup: int, frames: int, batch: int,
-               kernel_name: str, copy_peak: dict | None, dump: str | None = None, phase_profile: bool = False) -> dict | None:
+               kernel_name: str, copy_peak: dict | None, dump: str | None = None, phase_profile: bool = False,
+               dump_outputs: str | None = None) -> dict | None:
     """Time `steps` passes of config `cfg_id` (after `warmup` untimed ones) and return the fields of its JSON line (rank 0;
     None elsewhere)."""
     import torch
@@ -469,6 +496,11 @@ def run_config(cfg_id: int, *, world: int, rank: int, dev, dry: bool, steps: int
         np.savez(dump, wave=torch.stack(gathered).cpu().numpy() if gathered is not None else wave.cpu().numpy()[None],
                  labels=labels.cpu().numpy(), samples=samples.cpu().numpy(),   # rank 0's own rows
                  seed=np.asarray([seed_of(steps - 1)], np.uint64), frames=T, batch=B, world=world, mel_seed=1000)
+    if dump_outputs:
+        if gathered is not None:
+            write_outputs(dump_outputs, {'wave': torch.stack(gathered).reshape(world * rows, wave_len).cpu().numpy()})
+        else:
+            write_outputs(dump_outputs, {'wave': wave.cpu().numpy(), 'samples': samples.cpu().numpy()})
     total_samples = world * steps * rows * L
     value = total_samples / dt / 1000.0
     audio_s = (T - 1) * HOP / SAMPLE_RATE
@@ -558,10 +590,17 @@ def main() -> int:
     ap.add_argument('--no-extra-configs', action='store_true', help='skip the configs[2] / configs[4] legs of the default run')
     ap.add_argument('--phase-profile', action='store_true', help='run the instrumented loop kernel (wrnn_phase_profile) and attach cycles per phase')
     ap.add_argument('--dump', default=None, help='rank 0: save the waveforms of the last timed step (npz) -- used by tests/test_gpu_config3.py')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='rank 0: write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beyond the headline: the extra legs (configs[2] / [4], fold, dm, train step; configs[3] at N > 1), '
+                         'the CPU baselines and the measured HBM peaks')
     ap.add_argument('--cpu-dry-run', action='store_true',
                     help='exercise the launcher / rendezvous / collectives / timing / JSON scaffolding on CPU (gloo) with a stand-in for the '
                          'device calls: tests only, the line it prints is not a measurement')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     under_launcher = 'RANK' in os.environ
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -603,15 +642,16 @@ def main() -> int:
             os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
             dist.init_process_group('nccl', device_id=dev)
 
-    copy_peak = None if dry or rank != 0 else measure_hbm_peaks(dev)
+    copy_peak = None if dry or rank != 0 or not args.full else measure_hbm_peaks(dev)
     out = run_config(args.config, world=world, rank=rank, dev=dev, dry=dry, steps=args.steps, warmup=args.warmup, frames=args.frames,
-                     batch=args.batch, kernel_name=args.kernel, copy_peak=copy_peak, dump=args.dump, phase_profile=args.phase_profile)
-    default_run = (args.config == 1 and world == 1 and not dry and not args.no_extra_configs and args.frames == T_FRAMES
+                     batch=args.batch, kernel_name=args.kernel, copy_peak=copy_peak, dump=args.dump, phase_profile=args.phase_profile,
+                     dump_outputs=args.dump_outputs)
+    default_run = (args.full and args.config == 1 and world == 1 and not dry and not args.no_extra_configs and args.frames == T_FRAMES
                    and args.batch == 0 and args.kernel == 'auto')
     # the driver's SCALE command (`--gpus N`, config 1 by default) also reports BASELINE configs[3] at that N: 64 clips per GPU scattered
     # from / gathered on rank 0 over RCCL -- one line carries the weak B=1-per-GPU number and the throughput-mode number
     scale_extra = None
-    if args.config == 1 and world > 1 and not args.no_extra_configs and args.batch == 0 and args.kernel == 'auto':
+    if args.full and args.config == 1 and world > 1 and not args.no_extra_configs and args.batch == 0 and args.kernel == 'auto':
         # The headline is measured; this leg must not be able to take it down.  Its scatter / gather over RCCL has run on one rank (GPU box)
         # and on 2 / 8 gloo ranks (CPU) -- never on 8 real GPUs -- so a watchdog stands behind it: if the leg is not back within
         # SCALE_LEG_TIMEOUT seconds, rank 0 prints the headline line with the leg marked as timed out and every rank leaves.
@@ -672,7 +712,7 @@ def main() -> int:
             except Exception as ex:
                 extra['train_step'] = {'error': repr(ex)}
             out['extra_configs'] = extra
-        if world == 1 and not args.no_cpu_baseline and not dry:
+        if args.full and world == 1 and not args.no_cpu_baseline and not dry:
             # cpu_baseline = the reference's own op sequence on torch-CPU on THIS box (the closest obtainable thing to "the reference CPU
             # wavernn_gen.py on the host cores of the same box": /root/reference does not exist here); cpu_port = the C restatement
             print('bench.py: cpu_baseline leg (torch CPU reference ops)', file=sys.stderr, flush=True)

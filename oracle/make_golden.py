@@ -2,7 +2,7 @@
 
 Run in the build container only (needs /root/reference):
 
-    PYTHONDONTWRITEBYTECODE=1 python -m oracle.make_golden [long | forward | train | dm]
+    PYTHONDONTWRITEBYTECODE=1 python -m oracle.make_golden [long | forward | train | dm | module]
 
 Every fixture stores only seeds + the reference's outputs: weights, mels and
 the sampling noise are rebuilt from the seeds on whatever box replays them
@@ -102,6 +102,89 @@ def mint_train():
 
 
 
+# `python -m oracle.make_golden module`: what the tests that compare with the reference MODULE itself (not only with its outputs on
+# the generate path) need, recorded so that they run without the reference tree
+MODULE_TRAIN_CASE = 'train_mol_default_b4_t5'
+MODULE_GRAD_SAMPLES = 2048
+MODULE_INIT_ARGS = (512, 512, 10, 2, (5, 5, 11), 80, 128, 128, 10, 275, 22050, 'RAW')
+MODULE_INIT_SEED = 3
+
+
+def module_grad_sample_idx(size: int) -> np.ndarray:
+    """Flat indices of the gradient entries a module fixture keeps: all of them up to MODULE_GRAD_SAMPLES, else a seeded sorted subset."""
+    if size <= MODULE_GRAD_SAMPLES:
+        return np.arange(size, dtype=np.int64)
+    return np.sort(np.random.Generator(np.random.PCG64(size)).choice(size, MODULE_GRAD_SAMPLES, replace=False)).astype(np.int64)
+
+
+def tensor_sha256(a) -> str:
+    import hashlib
+    a = np.ascontiguousarray(np.asarray(a))
+    return hashlib.sha256(str(a.dtype).encode() + str(a.shape).encode() + a.tobytes()).hexdigest()
+
+
+def mint_module():
+    """(1) module_<train case>.npz: one training iteration of the unmodified module in float64 (loss, the whole fc3 output, and per parameter
+    the largest |gradient|, its flat index and value and the entries at module_grad_sample_idx);  (2) module_default_init.npz:
+    sha256 of every state_dict tensor of fatchord_version.WaveRNN(*MODULE_INIT_ARGS) after torch.manual_seed(MODULE_INIT_SEED);
+    (3) option_b_reference_class.json: what INTEGRATION.md option B's `_cfg_of` / `_descs_of` give on the reference class."""
+    import contextlib
+    import io
+    import json
+    import torch
+    from oracle import ref_harness as rh
+    from tacotronv2_wavernn_chinese_amd.synth import DEFAULT_DIMS
+    c = {t['name']: t for t in TRAIN_CASES}[MODULE_TRAIN_CASE]
+    sd = make_state_dict(WEIGHT_SEED, mode=c['mode'], variant=c['variant'], bits=c['bits'])
+    x, mels, y = train_inputs(c)
+    # the module in float64: its up-layer FIR gradients in float32 depend on the host's summation order (oracle/torch_ref.training_step)
+    f64 = lambda a: np.asarray(a, np.float64) if np.asarray(a).dtype.kind == 'f' else a
+    torch.set_default_dtype(torch.float64)   # the tensors forward() creates itself (h0, :141-142)
+    try:
+        out = rh.reference_train_step(rh.build_reference_model(sd, mode=c['mode'], bits=c['bits']).double(), f64(x), f64(mels), f64(y))
+    finally:
+        torch.set_default_dtype(torch.float32)
+    fix = dict(loss=np.float64(out['loss']), logits=out['logits'].astype(np.float32), keys=np.array(sorted(out['grads'])))
+    for k, g in out['grads'].items():
+        flat = np.asarray(g, np.float32).reshape(-1)
+        am = int(np.argmax(np.abs(flat)))
+        fix['amax_idx/' + k], fix['amax_val/' + k] = np.int64(am), flat[am]
+        fix['val/' + k] = flat[module_grad_sample_idx(flat.size)]
+    path = os.path.join(GOLDEN_DIR, f'module_{MODULE_TRAIN_CASE}.npz')
+    np.savez_compressed(path, **fix)
+    print(f'{path}: {len(out["grads"])} gradients -> {os.path.getsize(path) / 1024:.0f} KiB')
+    ref = rh.load_reference()
+    torch.manual_seed(MODULE_INIT_SEED)
+    with contextlib.redirect_stdout(io.StringIO()):
+        m = ref.fv.WaveRNN(*MODULE_INIT_ARGS)
+    msd = m.state_dict()
+    path = os.path.join(GOLDEN_DIR, 'module_default_init.npz')
+    np.savez_compressed(path, keys=np.array(list(msd)), sha256=np.array([tensor_sha256(v.numpy()) for v in msd.values()]))
+    print(f'{path}: {len(msd)} tensors')
+    md = open(os.path.join(os.path.dirname(GOLDEN_DIR), '..', 'INTEGRATION.md')).read()
+    import re
+    ns = {}
+    exec(compile(re.search(r'```python\n(.*?)```', md[md.index('## Option B'):], re.S).group(1), 'INTEGRATION.md:option-B', 'exec'), ns)
+    rec = {}
+    for mode, bits in (('RAW', 10), ('MOL', 9)):
+        model = rh.build_reference_model(make_state_dict(0, mode=mode, variant='default', bits=bits), mode=mode, bits=bits)
+        cfg = ns['_cfg_of'](model, 3)
+        _, descs = ns['_descs_of'](model)
+        rec[mode] = dict(module=type(model).__module__ + '.' + type(model).__name__,
+                         cfg={f: (list(getattr(cfg, f)) if f == 'upsample_factors' else getattr(cfg, f)) for f, _ in cfg._fields_},
+                         descs=[[d.name.decode(), d.dtype, list(d.shape[:d.ndim]),
+                                 tensor_sha256(np.ctypeslib.as_array(ctypes_floats(d.data), shape=(int(np.prod(d.shape[:d.ndim])),)))] for d in descs])
+    path = os.path.join(GOLDEN_DIR, 'option_b_reference_class.json')
+    with open(path, 'w') as f:
+        json.dump(rec, f, indent=1)
+    print(f'{path}: {sum(len(r["descs"]) for r in rec.values())} descriptors')
+
+
+def ctypes_floats(ptr):
+    import ctypes as C
+    return C.cast(ptr, C.POINTER(C.c_float))
+
+
 def mint_forward():
     from oracle import ref_harness as rh
     for c in FORWARD_CASES:
@@ -160,6 +243,9 @@ def main() -> int:
         return 0
     if len(sys.argv) > 1 and sys.argv[1] == 'train':
         mint_train()
+        return 0
+    if len(sys.argv) > 1 and sys.argv[1] == 'module':
+        mint_module()
         return 0
     cases = LONG_CASES if (len(sys.argv) > 1 and sys.argv[1] == 'long') else CASES
     for c in cases:

@@ -126,19 +126,26 @@ def loss_of(mode: str, y_hat: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
 
 
 def training_step(state_dict: Dict[str, np.ndarray], mode: str, x: np.ndarray, mels: np.ndarray, y: np.ndarray, dtype=torch.float32,
-                  device='cpu', training=True) -> dict:
+                  device='cpu', training=True, upsample_dtype=None) -> dict:
     """loss + gradients of every floating-point parameter for one (x, mels, y) batch, as `loss.backward()` on the reference
-    module in train() mode gives them.  Returns dict(loss, logits, grads {key: ndarray}, d_mels_up, d_aux)."""
+    module in train() mode gives them.  Returns dict(loss, logits, grads {key: ndarray}, d_mels_up, d_aux).
+    upsample_dtype (default: dtype): the upsample network's parameters, input and autograd in that precision, its outputs cast
+    to dtype for the loop layers.  The three up-layer FIR gradients are sums over all B x L x 80 upsampled positions with heavy
+    cancellation: in float32 their value depends on the summation order torch's CPU kernels pick for the host (thread count,
+    blocking) by up to several per cent, so a host-independent float32 restatement runs this part in float64."""
+    up_dtype = upsample_dtype or dtype
     sd = {}
     for k, v in state_dict.items():
         t = torch.as_tensor(np.asarray(v))
         if t.is_floating_point():
-            t = t.to(device=device, dtype=dtype).clone().requires_grad_(not k.endswith(('running_mean', 'running_var')))
+            t = t.to(device=device, dtype=up_dtype if k.startswith('upsample.') else dtype).clone()
+            t.requires_grad_(not k.endswith(('running_mean', 'running_var')))
         sd[k] = t
     xt = torch.as_tensor(x).to(device=device, dtype=dtype)
-    mt = torch.as_tensor(mels).to(device=device, dtype=dtype)
+    mt = torch.as_tensor(mels).to(device=device, dtype=up_dtype)
     yt = torch.as_tensor(y).to(device=device)
     mels_up, aux = upsample(sd, mt, training=training)
+    mels_up, aux = mels_up.to(dtype), aux.to(dtype)
     mels_up.retain_grad()
     aux.retain_grad()
     y_hat = loop_forward(sd, xt, mels_up, aux)

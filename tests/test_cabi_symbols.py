@@ -31,8 +31,8 @@ def test_create_rejects_bad_config_without_gpu():
         _cabi.NativeVocoder(rnn_dims=512, fc_dims=512, bits=10, pad=2, upsample_factors=(5, 5, 11), feat_dims=80,
                             compute_dims=128, res_out_dims=128, res_blocks=10, hop_length=275, sample_rate=22050,
                             mode='XYZ', device=0)
-    with pytest.raises(_cabi.WrnnError):  # unsupported dims are refused loudly, not silently mis-computed
-        _cabi.NativeVocoder(rnn_dims=256, fc_dims=512, bits=10, pad=2, upsample_factors=(5, 5, 11), feat_dims=80,
+    with pytest.raises(_cabi.WrnnError, match='unsupported dims'):  # unsupported dims are refused loudly, not silently mis-computed
+        _cabi.NativeVocoder(rnn_dims=2048, fc_dims=512, bits=10, pad=2, upsample_factors=(5, 5, 11), feat_dims=80,
                             compute_dims=128, res_out_dims=128, res_blocks=10, hop_length=275, sample_rate=22050,
                             mode='RAW', device=0)
 

@@ -64,7 +64,7 @@ def _report(tag, st):
     bound_near_ties(tag, st['compared'], st['near_ties'])
 
 
-def test_config1_b1_t401_injected_noise_vs_reference_and_oracle():
+def test_config1_b1_t401_injected_noise_vs_reference_and_oracle(tmp_path):
     """configs[1]: the benchmarked clip, free-running over all 110 275 steps with the reference's own noise stream
     (452 MB of Exp(1) draws on the device), default segmentation (14 launches), against the labels of the unmodified
     reference and against the oracle driven along the GPU's own trajectory (every step compared)."""
@@ -83,7 +83,7 @@ def test_config1_b1_t401_injected_noise_vs_reference_and_oracle():
     if not st['near_ties']:
         # identical to the oracle's free run over the whole clip => must equal what the reference itself produced
         np.testing.assert_array_equal(got, fx['labels'].astype(np.int32))
-        wav = m.generate(fx['mels'], '/tmp/wrnn_c1.wav', False, 11000, 550, True, noise_mode=_cabi.NOISE_INJECTED,
+        wav = m.generate(fx['mels'], str(tmp_path / 'c1.wav'), False, 11000, 550, True, noise_mode=_cabi.NOISE_INJECTED,
                          noise1=fx['noise']['expo'])
         assert wav.dtype == np.float64 and wav.shape == (400 * 275,)
         np.testing.assert_array_equal(wav.astype(np.float32), fx['wav'])

@@ -243,24 +243,24 @@ def test_per_xcd_target_makes_one_fold_per_xcd(tmp_path):
     assert wav.shape == ((T - 1) * 275,)
 
 
-def test_quirks():
+def test_quirks(tmp_path):
     fx = load_case('raw_peaky_b1_t24')
     m = _model(fx)
     from tacotronv2_wavernn_chinese_amd import _cabi
     from tacotronv2_wavernn_chinese_amd.synth import make_mels
     # T < 21: the reference dies in the fade-out broadcast (fatchord_version.py:256-258)
     with pytest.raises(ValueError):
-        m.generate(make_mels(1, 1, 20), '/tmp/wrnn_q.wav', False, 11000, 550, True)
+        m.generate(make_mels(1, 1, 20), str(tmp_path / 'q.wav'), False, 11000, 550, True)
     # batched needs a single utterance (fold_with_overlap, :338)
     with pytest.raises(_cabi.WrnnError):
-        m.generate(make_mels(1, 2, 30), '/tmp/wrnn_q.wav', True, 2000, 200, True)
+        m.generate(make_mels(1, 2, 30), str(tmp_path / 'q.wav'), True, 2000, 200, True)
     # philox mode: reproducible under torch.manual_seed, different across seeds
     torch.manual_seed(5)
-    a = m.generate(make_mels(2, 1, 21), '/tmp/wrnn_q.wav', False, 11000, 550, True)
+    a = m.generate(make_mels(2, 1, 21), str(tmp_path / 'q.wav'), False, 11000, 550, True)
     torch.manual_seed(5)
-    b = m.generate(make_mels(2, 1, 21), '/tmp/wrnn_q.wav', False, 11000, 550, True)
+    b = m.generate(make_mels(2, 1, 21), str(tmp_path / 'q.wav'), False, 11000, 550, True)
     torch.manual_seed(6)
-    c = m.generate(make_mels(2, 1, 21), '/tmp/wrnn_q.wav', False, 11000, 550, True)
+    c = m.generate(make_mels(2, 1, 21), str(tmp_path / 'q.wav'), False, 11000, 550, True)
     np.testing.assert_array_equal(a, b)
     assert not np.array_equal(a, c)
 

@@ -54,37 +54,41 @@ def test_option_b_structs_match_the_header(tmp_path):
 @pytest.mark.parametrize('mode,bits', [('RAW', 10), ('MOL', 9)])
 def test_option_b_config_and_descriptors_from_the_real_reference_class(mode, bits):
     """The stub reads attributes of the class it is pasted into (self.rnn_dims, self.fc1.out_features, self.pad, self.upsample..., :93-129).
-    The GPU test binds it onto this package's own WaveRNN (the GPU box has no reference tree); HERE, where /root/reference exists, the stub's
-    ``_cfg_of`` / ``_descs_of`` are run on the REAL ``wavernn.models.fatchord_version.WaveRNN`` and must give the wrnn_config and the
-    tensor table the package's binding builds for the same weights."""
-    if not os.path.isdir('/root/reference/wavernn'):
-        pytest.skip('needs the reference tree (build container only)')
+    What its ``_cfg_of`` / ``_descs_of`` gave on the REAL ``wavernn.models.fatchord_version.WaveRNN`` (loaded with the same seeded weights)
+    is recorded in tests/golden/option_b_reference_class.json (`python -m oracle.make_golden module`): it must be the wrnn_config and the
+    tensor table the package's binding builds for the same weights, and the stub must give the same on this package's WaveRNN (what the
+    GPU test binds it onto)."""
+    import json
     import torch
-    from oracle import ref_harness as rh
+    from oracle import make_golden as mg
     from tacotronv2_wavernn_chinese_amd import _cabi
     from tacotronv2_wavernn_chinese_amd.synth import DEFAULT_DIMS, make_state_dict
     from tacotronv2_wavernn_chinese_amd.vocoder import WaveRNN
     ns, _ = _stub_namespace()
+    with open(os.path.join(ROOT, 'tests', 'golden', 'option_b_reference_class.json')) as f:
+        rec = json.load(f)[mode]
+    assert rec['module'] == 'wavernn.models.fatchord_version.WaveRNN'
     sd = make_state_dict(0, mode=mode, variant='default', bits=bits)
-    ref_model = rh.build_reference_model(sd, mode=mode, bits=bits)
-    assert type(ref_model).__module__ == 'wavernn.models.fatchord_version'
-    cfg = ns['_cfg_of'](ref_model, 3)
     dims = dict(DEFAULT_DIMS, bits=bits)
     want = dict(rnn_dims=dims['rnn_dims'], fc_dims=dims['fc_dims'], bits=bits, pad=dims['pad'], n_upsample=len(dims['upsample_factors']),
                 feat_dims=dims['feat_dims'], compute_dims=dims['compute_dims'], res_out_dims=dims['res_out_dims'], res_blocks=dims['res_blocks'],
                 hop_length=dims['hop_length'], sample_rate=dims['sample_rate'], mode=_cabi.MODE_RAW if mode == 'RAW' else _cabi.MODE_MOL, device=3)
     for k, v in want.items():
-        assert getattr(cfg, k) == v, k
-    assert list(cfg.upsample_factors)[:cfg.n_upsample] == list(dims['upsample_factors'])
-    keep, descs = ns['_descs_of'](ref_model)
+        assert rec['cfg'][k] == v, k
+    assert rec['cfg']['upsample_factors'][:rec['cfg']['n_upsample']] == list(dims['upsample_factors'])
     ours = WaveRNN(**dims, mode=mode)
     ours.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in sd.items()})
+    cfg = ns['_cfg_of'](ours, 3)
+    assert {f: (list(getattr(cfg, f)) if f == 'upsample_factors' else getattr(cfg, f)) for f, _ in cfg._fields_} == rec['cfg']
     ours_sd = {k: v.numpy() for k, v in ours.state_dict().items() if v.dtype == torch.float32}
-    got = {d.name.decode(): (d.dtype, tuple(d.shape[:d.ndim])) for d in descs}
-    assert got == {k: (_cabi.DTYPE_F32, a.shape) for k, a in ours_sd.items()}
-    for d in descs:   # the data pointers carry the reference module's own weights
+    assert {name: (dt, tuple(shape)) for name, dt, shape, _ in rec['descs']} == {k: (_cabi.DTYPE_F32, a.shape) for k, a in ours_sd.items()}
+    for name, _, _, sha in rec['descs']:   # the reference module's data pointers carried these weights
+        assert sha == mg.tensor_sha256(ours_sd[name].reshape(-1)), name
+    keep, descs = ns['_descs_of'](ours)
+    assert [[d.name.decode(), d.dtype, list(d.shape[:d.ndim])] for d in descs] == [r[:3] for r in rec['descs']]
+    for d, r in zip(descs, rec['descs']):
         a = np.ctypeslib.as_array(C.cast(d.data, C.POINTER(C.c_float)), shape=(int(np.prod(d.shape[:d.ndim])),))
-        np.testing.assert_array_equal(a, ours_sd[d.name.decode()].reshape(-1))
+        assert mg.tensor_sha256(a) == r[3], r[0]
 
 
 @pytest.mark.gpu

@@ -119,7 +119,7 @@ def test_bench_distributed_scaffolding_dry_run(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     for cfg in ('3', '1'):
         r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--cpu-dry-run', '--config', cfg, '--steps', '2',
-                            '--warmup', '1', '--frames', '21', '--batch', '3' if cfg == '3' else '0'],
+                            '--warmup', '1', '--frames', '21', '--batch', '3' if cfg == '3' else '0', '--full'],
                            capture_output=True, text=True, timeout=600, env=env, cwd=tmp_path)
         assert r.returncode == 0, r.stderr[-3000:]
         lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -157,7 +157,7 @@ def test_bench_scaffolding_at_the_real_rank_count(tmp_path):
 
 
 def test_the_scale_leg_cannot_take_the_headline_down(tmp_path):
-    """`bench.py --gpus 2` (config 1) attaches configs[3]; if that leg hangs -- its RCCL scatter / gather has never run on 8 real GPUs --
+    """`bench.py --gpus 2 --full` (config 1) attaches configs[3]; if that leg hangs -- its RCCL scatter / gather has never run on 8 real GPUs --
     a watchdog prints the headline line without it and every rank leaves.  Here the watchdog is made to fire at once."""
     import json
     import os
@@ -167,9 +167,50 @@ def test_the_scale_leg_cannot_take_the_headline_down(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env['WRNN_BENCH_SCALE_LEG_TIMEOUT'] = '0.001'
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--cpu-dry-run', '--config', '1', '--steps', '2', '--warmup', '1',
-                        '--frames', '21'], capture_output=True, text=True, timeout=600, env=env, cwd=tmp_path)
+                        '--frames', '21', '--full'], capture_output=True, text=True, timeout=600, env=env, cwd=tmp_path)
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, (r.stdout[-1000:], r.stderr[-2000:])
     d = json.loads(lines[0])
     assert d['n_gpus'] == 2 and d['value'] > 0
     assert 'watchdog' in d['extra_configs']['3']['error']
+
+
+def test_plain_bench_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline line without the extra legs; --dump-outputs writes what the last timed step
+    computed (CPU dry run: the stand-in waveforms), the same in two runs with the same arguments, and --steps sets the timed steps."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    outs = []
+    for run in ('a', 'b'):
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--cpu-dry-run', '--config', '3', '--steps', '3',
+                            '--warmup', '1', '--frames', '21', '--batch', '3', '--dump-outputs', str(tmp_path / run)],
+                           capture_output=True, text=True, timeout=600, env=env, cwd=tmp_path)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d['steps'] == 3 and d['ms_per_step'] > 0 and d['higher_is_better'] is True and d['dtype'] == 'f32'
+        assert not any(k in d for k in ('extra_configs', 'cpu_baseline', 'cpu_port', 'cpu_reference'))
+        assert 'peak_measured' not in d['roofline']
+        wave, rows = np.load(tmp_path / run / 'wave.npy'), np.load(tmp_path / run / 'rows.npy')
+        assert wave.dtype == np.float64 and wave.shape == (3, 20 * 275) and rows.tolist() == [0.0, 1.0, 2.0]
+        outs.append(wave)
+    np.testing.assert_array_equal(outs[0], outs[1])
+
+
+def test_dump_outputs_keeps_a_seeded_row_subset_under_the_limit(tmp_path, monkeypatch):
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_LIMIT', 10 * (4 * 8 + 2 * 4 + 8))
+    w = np.arange(64 * 4, dtype=np.float64).reshape(64, 4)
+    s = np.arange(64 * 2, dtype=np.float32).reshape(64, 2)
+    for d in ('a', 'b'):
+        bench.write_outputs(str(tmp_path / d), {'wave': w, 'samples': s})
+    rows = np.load(tmp_path / 'a' / 'rows.npy')
+    assert rows.shape == (10,) and np.all(np.diff(rows) > 0)
+    np.testing.assert_array_equal(rows, np.load(tmp_path / 'b' / 'rows.npy'))
+    np.testing.assert_array_equal(np.load(tmp_path / 'a' / 'wave.npy'), w[rows.astype(int)])
+    np.testing.assert_array_equal(np.load(tmp_path / 'a' / 'samples.npy'), s[rows.astype(int)])
