@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define WRNN_ABI_VERSION 6
+#define WRNN_ABI_VERSION 7
 
 /* mode: fatchord_version.py:98-103 */
 #define WRNN_MODE_RAW 0 /* softmax over 2**bits classes */
@@ -297,6 +297,51 @@ int32_t wrnn_team_info(const wrnn_handle *h, int32_t *n_teams_out, const char **
 /* Test hook: on != 0 makes this handle behave as if the residency check of wrnn_create had failed (AUTO -> SIMPLE, an explicit team kernel
  * -> WRNN_ERR_INVALID), so that the slow-path warning can be exercised on a healthy device. */
 int wrnn_debug_force_no_teams(wrnn_handle *h, int32_t on);
+
+/* ---- streaming generation (ABI 7) -------------------------------------------------------------------------------------------
+ * Mel frames arrive a few at a time (Tacotron's decoder); audio leaves as soon as the frames it depends on are in.  A stream
+ * fed the frames of mels (B, feat, T) in ANY partition into pushes and then ended produces exactly -- bit for bit -- the labels
+ * and samples of wrnn_generate(mels, B, T, batched = 0, ...) with the same seed, noise mode and kernel: conditioning is local
+ * in time (sample step t of frame i = t / hop reads mel frames i - pad .. i + pad only), the recurrent state crosses pushes
+ * through device memory owned by the stream, and the Philox noise is keyed by (seed, absolute step, row, class).
+ *
+ * Planning rule (wrnn_stream_ready_steps): before the last push, (frames_in - pad) * hop steps are ready, rounded DOWN to a
+ * multiple of 32 -- the TEAM2 kernel draws its Philox noise in 32-step blocks, so every resume point lies on a block boundary;
+ * the last push releases all frames_in * hop steps (the frames after the end are the zero padding of generate(), :183-185).
+ *
+ * The stream owns its recurrent state, the conditioning tables of the frames in flight (a window of the newly ready frames
+ * plus a `pad`-frame halo, recomputed from a bounded mel history: the workspace is bounded by the largest push, not by the
+ * stream's length), its row table and its device error word; the handle lends only the team-kernel mailboxes inside the
+ * per-device team gate.  Several streams and offline calls may be interleaved on one handle.  A stream is not thread-safe,
+ * its pushes must be ordered on the device (one HIP stream), and it must be closed before its handle is destroyed. */
+typedef struct wrnn_stream wrnn_stream;
+
+/* B rows pushed in lock-step.  opts: struct_size as for wrnn_generate; noise_mode WRNN_NOISE_PHILOX (seed) or WRNN_NOISE_ARGMAX
+ * (RAW); kernel WRNN_KERNEL_AUTO (TEAM2 where the team kernels can run, else SIMPLE), WRNN_KERNEL_TEAM2 or WRNN_KERNEL_SIMPLE.
+ * WRNN_NOISE_INJECTED, the BATCH kernels, mels_padded, and every pointer / tuning field of opts set are WRNN_ERR_INVALID. */
+int wrnn_stream_open(wrnn_handle *h, int32_t B, const wrnn_sample_opts *opts, wrnn_stream **out);
+
+/* mels_dev (B, feat, n_frames) device, the next n_frames >= 0 frames of every row (may be NULL when n_frames == 0); last != 0
+ * ends the utterance.  Enqueues every step that has become ready on `stream` and writes them to labels_out_dev (may be NULL)
+ * and samples_out_dev as (B, *steps_out) row-major; out_capacity = elements each output array holds (>= B * *steps_out,
+ * WRNN_ERR_INVALID otherwise; wrnn_stream_ready_steps tells the caller the size beforehand).  *steps_out is known on the host
+ * at return, nothing waits.  mels_dev must stay valid until the push's work has run.  After the last push, or once the stream
+ * is poisoned (see wrnn_stream_sync), a push is WRNN_ERR_STATE. */
+int wrnn_stream_push(wrnn_stream *st, const float *mels_dev, int32_t n_frames, int32_t last, int32_t *labels_out_dev,
+                     float *samples_out_dev, int64_t out_capacity, int64_t *steps_out, void *stream);
+
+/* Waits for `stream`, then reports a device-side error of the pushes so far (WRNN_ERR_BUSY: a team kernel could not get its
+ * workgroups resident; WRNN_ERR_TIMEOUT).  After either the stream is poisoned: later pushes return WRNN_ERR_STATE. */
+int wrnn_stream_sync(wrnn_stream *st, void *stream);
+
+/* frames pushed, steps enqueued, device bytes the stream owns (any pointer may be NULL) */
+int wrnn_stream_info(const wrnn_stream *st, int64_t *frames_in, int64_t *steps_done, int64_t *workspace_bytes);
+
+/* Host-only (no device): the planning rule above -- steps ready after frames_in frames; -1 for frames_in < 0, hop < 1, pad < 0. */
+int64_t wrnn_stream_ready_steps(int64_t frames_in, int32_t hop, int32_t pad, int32_t last);
+
+/* Waits for the device, then frees the stream's device memory.  NULL is a no-op. */
+void wrnn_stream_close(wrnn_stream *st);
 
 const char *wrnn_last_error(const wrnn_handle *h);
 int32_t wrnn_abi_version(void);

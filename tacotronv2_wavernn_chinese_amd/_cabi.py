@@ -25,7 +25,7 @@ DTYPE_F32, DTYPE_I64 = 0, 1
 ERR_NAMES = {0: 'WRNN_OK', -1: 'WRNN_ERR_INVALID', -2: 'WRNN_ERR_HIP', -3: 'WRNN_ERR_STATE',
              -4: 'WRNN_ERR_MISSING_KEY', -5: 'WRNN_ERR_TIMEOUT', -6: 'WRNN_ERR_BUSY'}
 ERR_INVALID, ERR_TIMEOUT, ERR_BUSY = -1, -5, -6
-ABI_VERSION = 6   # WRNN_ABI_VERSION of the include/wavernn_amd.h this binding was written against
+ABI_VERSION = 7   # WRNN_ABI_VERSION of the include/wavernn_amd.h this binding was written against
 
 # every symbol include/wavernn_amd.h declares (checked by tests/test_cabi_symbols.py)
 EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wrnn_plan', 'wrnn_generate',
@@ -33,7 +33,9 @@ EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wr
                     'wrnn_abi_version', 'wrnn_destroy', 'wrnn_epilogue', 'wrnn_epilogue_rows', 'wrnn_epilogue_tables', 'wrnn_loss',
                     'wrnn_phase_profile', 'wrnn_phase_cycles', 'wrnn_train_step', 'wrnn_train_forward', 'wrnn_train_backward', 'wrnn_sync_status', 'wrnn_train_force_step_kernels',
                     'wrnn_dm_create', 'wrnn_dm_load_weights', 'wrnn_dm_generate', 'wrnn_dm_last_error', 'wrnn_dm_destroy',
-                    'wrnn_dm_set_kernel', 'wrnn_dm_sync_status', 'wrnn_team_info', 'wrnn_debug_force_no_teams')
+                    'wrnn_dm_set_kernel', 'wrnn_dm_sync_status', 'wrnn_team_info', 'wrnn_debug_force_no_teams',
+                    'wrnn_stream_open', 'wrnn_stream_push', 'wrnn_stream_sync', 'wrnn_stream_info', 'wrnn_stream_ready_steps',
+                    'wrnn_stream_close')
 
 
 def epilogue_tables(n_classes: int, overlap: int, hop: int):
@@ -183,6 +185,18 @@ def load_library() -> C.CDLL:
     lib.wrnn_team_info.restype = C.c_int32
     lib.wrnn_debug_force_no_teams.argtypes = [vp, C.c_int32]
     lib.wrnn_debug_force_no_teams.restype = C.c_int
+    lib.wrnn_stream_open.argtypes = [vp, C.c_int32, C.POINTER(SampleOpts), C.POINTER(vp)]
+    lib.wrnn_stream_open.restype = C.c_int
+    lib.wrnn_stream_push.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int64, C.POINTER(C.c_int64), vp]
+    lib.wrnn_stream_push.restype = C.c_int
+    lib.wrnn_stream_sync.argtypes = [vp, vp]
+    lib.wrnn_stream_sync.restype = C.c_int
+    lib.wrnn_stream_info.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.wrnn_stream_info.restype = C.c_int
+    lib.wrnn_stream_ready_steps.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32]
+    lib.wrnn_stream_ready_steps.restype = C.c_int64
+    lib.wrnn_stream_close.argtypes = [vp]
+    lib.wrnn_stream_close.restype = None
     lib.wrnn_dm_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
     lib.wrnn_dm_create.restype = C.c_int
     lib.wrnn_dm_load_weights.argtypes = [vp, C.POINTER(TensorDesc), C.c_int32]
@@ -367,6 +381,50 @@ class NativeVocoder:
         self._check(self.lib.wrnn_last_timing(self._h, C.byref(t)))
         return dict(prologue_ms=t.prologue_ms, loop_ms=t.loop_ms, kernel=t.kernel, rows=t.rows, steps=t.steps,
                     launches=t.launches)
+
+
+def stream_ready_steps(frames_in: int, hop: int, pad: int, last: bool) -> int:
+    """Host-only ``wrnn_stream_ready_steps``: loop steps a stream can run after ``frames_in`` mel frames (-1 for bad arguments)."""
+    return int(load_library().wrnn_stream_ready_steps(int(frames_in), int(hop), int(pad), int(bool(last))))
+
+
+class NativeStream:
+    """Owner of one ``wrnn_stream`` opened on a :class:`NativeVocoder`'s handle (which it keeps alive)."""
+
+    def __init__(self, nat: NativeVocoder, B: int, *, noise_mode: int = NOISE_PHILOX, seed: int = 0, kernel: int = KERNEL_AUTO):
+        self.nat, self.lib = nat, nat.lib
+        o = SampleOpts()
+        o.struct_size = C.sizeof(SampleOpts)
+        o.noise_mode, o.kernel, o.seed = int(noise_mode), int(kernel), int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._s = C.c_void_p()
+        nat._check(self.lib.wrnn_stream_open(nat._h, int(B), C.byref(o), C.byref(self._s)))
+
+    def push(self, mels_ptr: int, n_frames: int, last: bool, labels_ptr: int, samples_ptr: int, capacity: int, stream: int) -> int:
+        """Enqueues the steps that became ready; returns their count (known without waiting)."""
+        n = C.c_int64()
+        self.nat._check(self.lib.wrnn_stream_push(self._s, mels_ptr or None, int(n_frames), int(bool(last)), labels_ptr or None,
+                                                  samples_ptr or None, int(capacity), C.byref(n), stream or None))
+        return int(n.value)
+
+    def sync(self, stream: int):
+        """Waits for ``stream``; raises WrnnError for a device-side error of the pushes so far (the stream is then unusable)."""
+        self.nat._check(self.lib.wrnn_stream_sync(self._s, stream or None))
+
+    def info(self) -> dict:
+        f, s, w = C.c_int64(), C.c_int64(), C.c_int64()
+        self.nat._check(self.lib.wrnn_stream_info(self._s, C.byref(f), C.byref(s), C.byref(w)))
+        return dict(frames_in=int(f.value), steps_done=int(s.value), workspace_bytes=int(w.value))
+
+    def close(self):
+        if getattr(self, '_s', None):
+            self.lib.wrnn_stream_close(self._s)
+            self._s = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _tensor_descs(state_dict: Dict[str, np.ndarray]):

@@ -89,6 +89,8 @@ const char *loop_team_obstacle(const wrnn_handle *h) {
 
 }  // namespace
 
+const char *wrnn_loop_team_obstacle(const wrnn_handle *h) { return loop_team_obstacle(h); }
+
 hipError_t wrnn_team_gate_enter(int device, hipStream_t s) {
     TeamGate &g = g_team_gate[(unsigned)device % 64u];
     g.mu.lock();

@@ -75,12 +75,15 @@ __global__ void __launch_bounds__(SIMPLE_THREADS) loop_simple_kernel(WrnnLoopArg
     const float *ktab = w + a.off.ktab;
     const int lane = tid & 63, wave = tid >> 6;
 
-    // h1 = h2 = 0, x = x_init or 0   (:194-196)
-    for (int j = tid; j < H; j += SIMPLE_THREADS) { s_h1[j] = 0.0f; s_h2[j] = 0.0f; }
-    if (tid == 0) *s_xfeed = a.x_init ? a.x_init[row] : 0.0f;
+    // h1 = h2 = 0, x = x_init or 0   (:194-196); a stream's later pushes (seg0 > 0) resume from the state the previous one left
+    float *st = a.state ? a.state + (size_t)row * wrnn_simple_state_floats(d) : nullptr;
+    const bool resume = st && a.seg0 > 0;
+    for (int j = tid; j < H; j += SIMPLE_THREADS) { s_h1[j] = resume ? st[j] : 0.0f; s_h2[j] = resume ? st[H + j] : 0.0f; }
+    if (tid == 0) *s_xfeed = resume ? st[2 * H] : (a.x_init ? a.x_init[row] : 0.0f);
     __syncthreads();
 
-    for (int64_t t = 0; t < rw.steps; ++t) {   // the row's own length (ragged batch) or the call's
+    // steps [seg0, seg0 + rw.steps): the row's own length (ragged batch) or the call's; a stream push runs its ready steps
+    for (int64_t t = a.seg0; t < a.seg0 + rw.steps; ++t) {
         // ---- conditioning row for this step: m_t, a_t  (:203-206) ----------
         const int64_t pos = rw.start + t;
         const bool live = pos < a.total_len;  // fold padding 'after' is zeros (:327-330)
@@ -252,6 +255,10 @@ __global__ void __launch_bounds__(SIMPLE_THREADS) loop_simple_kernel(WrnnLoopArg
             }
         }
         __syncthreads();
+    }
+    if (st) {   // hand the recurrent state to the stream's next push
+        for (int j = tid; j < H; j += SIMPLE_THREADS) { st[j] = s_h1[j]; st[H + j] = s_h2[j]; }
+        if (tid == 0) st[2 * H] = *s_xfeed;
     }
 }
 

@@ -142,7 +142,13 @@ struct WrnnLoopArgs {
     int32_t *labels_out;      // (rows, L) or null
     float *samples_out;       // (rows, L)
     unsigned *err;
+    // streams (stream.hip): row r runs steps [seg0, seg0 + rows[r].steps) (Philox keyed by the absolute step, outputs at
+    // [row * steps + t]) and, when state != null, starts from / leaves its recurrent state in
+    // state[row * wrnn_simple_state_floats]: [h1 H | h2 H | x 1 | pad].  Offline calls: 0, null.
+    int64_t seg0;
+    float *state;
 };
+__host__ __device__ inline int wrnn_simple_state_floats(const WrnnDims &d) { return 2 * d.H + 4; }
 
 // Team kernel (loop_team.hip): mailbox size per team in 8-byte granules:
 // x3, fc1, fc2, race winners (2 x 512 each), gh1 (2 x 1536)
@@ -278,6 +284,8 @@ hipError_t wrnn_team2_occupancy(int mode, bool prof, int *blocks_per_cu, size_t 
 // kernel launched on `device` by any handle / stream and takes the device's launch lock, leave() records the new tail and
 // releases the lock.  Nothing blocks on the GPU's progress; only the launching threads are serialised.
 hipError_t wrnn_team_gate_enter(int device, hipStream_t s);
+// why the XCD-team kernels cannot run for this handle, or nullptr (api.hip; what AUTO and wrnn_team_info decide on)
+const char *wrnn_loop_team_obstacle(const wrnn_handle *h);
 hipError_t wrnn_team_gate_leave(int device, hipStream_t s);
 hipError_t wrnn_launch_loss(int mode, const float *y_hat, const void *y, int NC, long n_rows, double *partial, int *bad, float *out,
                             hipStream_t s);

@@ -7,7 +7,7 @@ handed to ``model.generate``; the output file name pattern is the reference's (:
 
 Deliberate differences: the reference hard-overrides ``batched = False`` and
 ``device = cpu`` after parsing its flags (:76-77, :93); here ``--batched`` is honoured and the model
-runs on the MI355X.  Extensions: ``--target auto|per_xcd``, ``--noise reference [--seed N]``
+runs on the MI355X.  Extensions: ``--target auto|per_xcd``, ``--noise reference [--seed N]``, ``--stream-frames N`` (streaming generation)
 (the reference's own noise stream: ``vocoder.reference_noise``).  The reference's ``.wav`` input branch is broken (undefined ``file_name``, :18-20)
 and needs librosa feature extraction, which is out of scope: it raises ``ValueError`` here.
 """
@@ -15,15 +15,17 @@ from __future__ import annotations
 
 import argparse
 import os
+import time
 
 import numpy as np
 import torch
 
+from .dsp import save_wav
 from .hparams import hparams as hp
 from .vocoder import WaveRNN
 
 
-def gen_from_file(model: WaveRNN, load_path, save_path, batched, target, overlap, **generate_opts):
+def gen_from_file(model: WaveRNN, load_path, save_path, batched, target, overlap, stream_frames=None, **generate_opts):
     k = model.get_step() // 1000
     load_path = str(load_path)
     if ".npy" in load_path:
@@ -39,10 +41,42 @@ def gen_from_file(model: WaveRNN, load_path, save_path, batched, target, overlap
         raise ValueError(f"Expected an extension of .wav or .npy, but got {os.path.splitext(load_path)[1]}!")
 
     mel = torch.tensor(mel).unsqueeze(0)
+    if stream_frames:
+        return _gen_streamed(model, mel, load_path, save_path, int(stream_frames), generate_opts.get('noise_mode', 'philox'))
     batch_str = f'gen_batched_target{target}_overlap{overlap}' if batched else 'gen_NOT_BATCHED'
     idx = load_path.split('/')[-1].strip().split('.')[0]
     save_str = os.path.join(str(save_path), idx + '_' + batch_str + '_' + 'step={}k'.format(k) + '.wav')
     _ = model.generate(mel, save_str, batched, target, overlap, hp.mu_law, **generate_opts)
+    print('\n\nstep = {}'.format(k * 1000))
+    return save_str
+
+
+def _gen_streamed(model: WaveRNN, mel, load_path, save_path, n, noise_mode):
+    """--stream-frames N: the mel fed to ``model.stream`` in pushes of N frames, as a TTS front end would hand them over.  The wav is the
+    one the unbatched path writes (same seed draw, same audio bit for bit); prints the time to first audio and the real-time factor."""
+    if n < 1:
+        raise ValueError(f'--stream-frames must be >= 1, got {n}')
+    k = model.get_step() // 1000
+    idx = load_path.split('/')[-1].strip().split('.')[0]
+    save_str = os.path.join(str(save_path), idx + '_gen_NOT_BATCHED_step={}k'.format(k) + '.wav')
+    T = mel.size(-1)
+    parts, first = [], None
+    start = time.perf_counter()
+    with model.stream(mu_law=hp.mu_law, noise_mode=noise_mode) as st:
+        for f in range(0, T, n):
+            parts.append(st.push(mel[0, :, f:f + n]))
+            if first is None and parts[-1].size:
+                first = time.perf_counter() - start
+        parts.append(st.finish())
+    wall = time.perf_counter() - start
+    if first is None:
+        first = wall
+    out = np.concatenate(parts)
+    save_wav(out, save_str, model.sample_rate)
+    model.train()   # what generate() leaves behind (:262)
+    secs = out.size / model.sample_rate
+    print(f'\nstreamed {T} frames in pushes of {n}: first audio after {first * 1e3:.1f} ms, {wall * 1e3:.1f} ms for {secs:.3f} s of audio '
+          f'(real-time factor {wall / max(secs, 1e-9):.4f})')
     print('\n\nstep = {}'.format(k * 1000))
     return save_str
 
@@ -80,6 +114,9 @@ def main(argv=None):
                         help="extension: 'reference' replays the reference's own draws from the torch CPU generator (with --seed: the wav the "
                              "reference script produces after torch.manual_seed(seed)); 'philox' (default) = the device counter RNG")
     parser.add_argument('--seed', type=int, default=None, help='extension: torch.manual_seed(SEED) before generating')
+    parser.add_argument('--stream-frames', type=int, default=None, metavar='N',
+                        help='extension: feed the mel to a streaming generator in pushes of N frames (unbatched; the same wav as '
+                             '--unbatched) and print the time to first audio and the real-time factor')
     parser.add_argument('--hp_file', metavar='FILE', default=DEFAULT_HPARAMS,
                         help='The file to use for the hyperparameters')
     parser.set_defaults(batched=None)
@@ -117,7 +154,10 @@ def main(argv=None):
         os.makedirs(out_dir, exist_ok=True)
         if args.seed is not None:
             torch.manual_seed(args.seed)
-        gen_from_file(model, args.file, out_dir, args.batched, args.target, args.overlap, noise_mode=args.noise)
+        if args.stream_frames is not None and args.noise != 'philox':
+            raise ValueError('--stream-frames draws its noise on the device: --noise reference needs the whole clip')
+        gen_from_file(model, args.file, out_dir, args.batched, args.target, args.overlap, stream_frames=args.stream_frames,
+                      noise_mode=args.noise)
     print('\n\nExiting...\n')
 
 

@@ -644,6 +644,32 @@ class WaveRNN(nn.Module):
         self.train()
         return outs
 
+    def stream(self, batch=1, mu_law=True, seed=None, noise_mode='philox', kernel=None, tail='reference', raw=False,
+               batched=False) -> 'VocoderStream':
+        """Streaming generation (extension): a :class:`VocoderStream` that takes mel frames as they arrive (``push``) and returns
+        the audio they make final.  Fed the frames of a mel (B, n_mels, T) in any partition into pushes and then ``finish()``-ed,
+        its labels / samples are bit-identical to ``generate_raw(mels, False, ..., noise_mode, seed, kernel)`` and, with
+        ``tail='reference'``, its float64 audio (concatenated) to what ``generate(mels[0:1], path, False, ..., mu_law)`` returns
+        after the same ``torch.manual_seed``: ``seed=None`` draws the Philox seed from the global torch generator exactly as
+        ``generate`` does.  ``tail='reference'`` holds the last 21 hops back until ``finish()`` (the trim to (T - 1) * hop and the
+        20-hop fade-out need the end); ``tail='none'`` returns every decoded sample as soon as it exists, all T * hop of them,
+        untrimmed and unfaded (lowest latency).  ``raw=True``: push / finish return dict(labels, samples) device tensors (B, n).
+        noise_mode: 'philox' or 'argmax' (RAW).  The reference's own noise ('reference', 'injected') needs the whole clip's draws,
+        and batched (fold) mode needs the whole clip to cut it into folds: both raise ``ValueError``.  kernel: None (the
+        model's ``kernel``, AUTO: TEAM2 where the team kernels can run, else SIMPLE -- with a warning), 'team2' / 'simple' or a
+        WRNN_KERNEL_* id.  A busy GPU (WRNN_ERR_BUSY) is raised, not retried on another kernel."""
+        if batched:
+            raise ValueError('batched (fold) generation needs the whole clip to cut it into folds: a stream is unbatched')
+        return VocoderStream(self, batch=batch, mu_law=mu_law, seed=seed, noise_mode=noise_mode, kernel=kernel, tail=tail, raw=raw)
+
+    def generate_stream(self, mel_chunks, **kw):
+        """Generator over ``stream(**kw)``: yields ``push(chunk)`` for every chunk of ``mel_chunks`` ((n_mels, k) or
+        (B, n_mels, k) each), then ``finish()``."""
+        with self.stream(**kw) as st:
+            for chunk in mel_chunks:
+                yield st.push(chunk)
+            yield st.finish()
+
     def gen_display(self, i, seq_len, b_size, start):
         """The reference's own ksamples/s meter (:267-271)."""
         gen_rate = (i + 1) / (time.time() - start) * b_size / 1000
@@ -768,3 +794,147 @@ class _LoopForwardFn(torch.autograd.Function):
             if model.check_device_errors is True:
                 nat.sync_status(st)
         return (None, None, d_m, d_a) + tuple(grads)
+
+
+def stream_release(frames_in: int, steps_done: int, last: bool, hop: int, tail: str = 'reference') -> int:
+    """Audio samples of a stream that are final after ``frames_in`` frames and ``steps_done`` generated steps.  tail='none': every
+    generated sample.  tail='reference': sample m once it cannot lie in the last 21 hops -- the trim to (T - 1) * hop and the
+    20-hop fade-out of generate() (:255-258) -- i.e. m < (frames_in - 21) * hop; at the end (``last``) all (T - 1) * hop."""
+    if tail == 'none':
+        return int(steps_done)
+    if last:
+        return (int(frames_in) - 1) * int(hop)
+    return min(max((int(frames_in) - 21) * int(hop), 0), int(steps_done))
+
+
+class VocoderStream:
+    """One utterance (or B in lock-step) generated while its mel frames arrive: see :meth:`WaveRNN.stream`.
+
+    ``push(mels)`` takes the next frames, (n_mels, k) or (B, n_mels, k) (numpy or torch, k >= 0), runs every loop step that has
+    become ready (``wrnn_stream_ready_steps``: (frames_in - pad) * hop rounded down to 32 steps before the end), waits for them
+    and returns the newly final float64 audio, (n,) for ``batch=1`` else (B, n); ``finish()`` ends the utterance and returns the
+    rest.  A device-side error raises ``WrnnError`` and leaves the stream unusable; a push after ``finish()`` raises
+    ``WrnnError`` (WRNN_ERR_STATE).  ``close()`` (or leaving the ``with`` block) frees the native stream."""
+
+    def __init__(self, model: 'WaveRNN', *, batch, mu_law, seed, noise_mode, kernel, tail, raw):
+        if tail not in ('reference', 'none'):
+            raise ValueError(f"tail must be 'reference' or 'none', got {tail!r}")
+        if isinstance(noise_mode, str):
+            if noise_mode not in _NOISE_MODES:
+                raise ValueError(f'noise_mode must be one of {sorted(_NOISE_MODES)} or a WRNN_NOISE_* id, got {noise_mode!r}')
+            noise_mode = _NOISE_MODES[noise_mode]
+        if noise_mode not in (_cabi.NOISE_PHILOX, _cabi.NOISE_ARGMAX):
+            raise ValueError("a stream draws its noise on the device (noise_mode 'philox' or 'argmax'): 'reference' / 'injected' "
+                             "noise needs the draws of the whole clip up front")
+        if noise_mode == _cabi.NOISE_ARGMAX and model.mode != 'RAW':
+            raise ValueError("noise_mode='argmax' is RAW-only")
+        if int(batch) < 1:
+            raise ValueError(f'batch must be >= 1, got {batch}')
+        if isinstance(kernel, str):
+            if kernel not in ('auto', 'team2', 'simple'):
+                raise ValueError(f"a stream runs kernel 'auto', 'team2' or 'simple', got {kernel!r}")
+            kernel = _cabi.KERNEL_IDS[kernel]
+        kernel = model.kernel if kernel is None else int(kernel)
+        if seed is None:
+            # what generate() does (its native_opts['seed']): one draw from the global torch generator, philox only
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if noise_mode == _cabi.NOISE_PHILOX else 0
+        self.model, self.B, self.tail, self.raw = model, int(batch), tail, bool(raw)
+        self.mu_law = bool(mu_law) if model.mode == 'RAW' else False   # MOL forces mu_law=False (:174)
+        self.hop, self.pad, self.seed = model.hop_length, model.pad, int(seed)
+        self._nat = model.native()
+        self._dev = torch.device('cuda', self._nat.device)
+        if kernel == _cabi.KERNEL_AUTO:
+            ok, _, why = self._nat.team_info()
+            if not ok:
+                model._warn_slow_path(why or 'the team kernels cannot run on this device', 0)
+        with torch.cuda.device(self._dev):
+            self._ns = _cabi.NativeStream(self._nat, self.B, noise_mode=noise_mode, seed=self.seed, kernel=kernel)
+        self.frames_in = 0        # mel frames pushed
+        self.steps = 0            # loop steps generated (per row)
+        self.released = 0         # audio samples returned (per row)
+        self._pending = np.zeros((self.B, 0), np.float64)   # decoded samples [released, steps) held back (tail='reference')
+        self._ended = False
+
+    # ------------------------------------------------------------------ api
+    def push(self, mels):
+        return self._push(mels, last=False)
+
+    def finish(self):
+        return self._push(None, last=True)
+
+    def info(self) -> dict:
+        """frames_in, steps_done, workspace_bytes (device memory the native stream owns)."""
+        return self._ns.info()
+
+    def close(self):
+        if self._ns is not None:
+            self._ns.close()
+            self._ns = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ------------------------------------------------------------ internals
+    def _mels(self, mels):
+        t = torch.as_tensor(mels)
+        if t.dim() == 2:
+            t = t.unsqueeze(0)
+        if t.dim() != 3 or t.size(0) != self.B or t.size(1) != self.model.feat_dims:
+            raise ValueError(f'expected mels shaped ({self.model.feat_dims}, k) or ({self.B}, {self.model.feat_dims}, k), got {tuple(torch.as_tensor(mels).shape)}')
+        return t
+
+    def _push(self, mels, last):
+        if self._ns is None:
+            raise _cabi.WrnnError(-3, 'the stream is closed')
+        t = self._mels(mels) if mels is not None else None
+        k = 0 if t is None else int(t.size(-1))
+        hop = self.hop
+        if last and self.tail == 'reference' and self.frames_in + k < 21 and not self._ended:
+            wave_len = (self.frames_in + k - 1) * hop   # the fade-out broadcast error of generate() (:256-258)
+            raise ValueError(f'operands could not be broadcast together with shapes ({max(wave_len, 0)},) '
+                             f'({20 * hop},) ({max(wave_len, 0)},)')
+        n = max(_cabi.stream_ready_steps(self.frames_in + k, hop, self.pad, last) - self.steps, 0)
+        with torch.cuda.device(self._dev):
+            mels_d = t.to(device=self._dev, dtype=torch.float32).contiguous() if k else None
+            labels = torch.empty((self.B, max(n, 1)), dtype=torch.int32, device=self._dev)
+            samples = torch.empty((self.B, max(n, 1)), dtype=torch.float32, device=self._dev)
+            st = torch.cuda.current_stream(self._dev).cuda_stream
+            got = self._ns.push(mels_d.data_ptr() if k else 0, k, last, labels.data_ptr(), samples.data_ptr(), labels.numel(), st)
+            self._ns.sync(st)   # waits; raises WrnnError for a device-side error (busy GPU, timeout)
+            del mels_d
+        if got != n:
+            raise RuntimeError(f'internal: the native stream ran {got} steps, the host planned {n}')
+        self.frames_in += k
+        self.steps += got
+        self._ended = self._ended or last
+        labels, samples = labels[:, :got], samples[:, :got]
+        if self.raw:
+            return dict(labels=labels, samples=samples)
+        audio = samples.cpu().numpy().astype(np.float64)   # :243-245
+        if self.mu_law:
+            audio = decode_mu_law(audio, self.model.n_classes, False)
+        if self.tail == 'none':
+            return self._shape(audio)
+        self._pending = np.concatenate([self._pending, audio], axis=1)
+        upto = stream_release(self.frames_in, self.steps, last, hop, self.tail)
+        out = self._pending[:, :upto - self.released]
+        self._pending = self._pending[:, upto - self.released:]
+        if last:
+            fade_from = upto - 20 * hop - self.released   # >= 0: nothing past (T - 21) * hop was released before
+            out[:, fade_from:] *= np.linspace(1, 0, 20 * hop)
+            self._pending = np.zeros((self.B, 0), np.float64)
+        self.released = upto
+        return self._shape(out)
+
+    def _shape(self, a):
+        return a[0] if self.B == 1 else a
