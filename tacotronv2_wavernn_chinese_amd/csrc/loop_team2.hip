@@ -10,14 +10,14 @@
 // (W_hh1.h1, W_hh2.h2, conditioning and noise of the next step, the gh1 gather) plus 256 v_accvgpr_read for
 // weights parked in AGPRs.  So: 8 waves per workgroup, two per SIMD, and the two waves of a SIMD get different jobs:
 //   waves 0-3 "C" (critical): W_ih2 (96) + fc1 (32) + fc2 (32) weights in VGPRs, fc3 slice in LDS;
-//                             phases B, C, D, E; each C wave reduces a quarter of the race winners;
+//                             phases B, C, D, E; each C wave publishes ONE race candidate, wave 0 reduces the team's 128;
 //   waves 4-7 "S" (shadow):   W_hh1 (96) + W_hh2 gates r,z (64) in VGPRs, W_hh2 gate n (32) in LDS;
 //                             window 2: gh1 = W_hh1.h1 (published), window 3: sampling noise of step t+1 (16 lanes of a
 //                             quarter-wave evaluate 16 different Philox blocks -> one evaluation per lane per 32 steps),
 //                             window 4: conditioning of step t+1 (LDS <- registers <- HBM stream, prefetched two steps
 //                             ahead), window 5: gh1 gather, gh2 = W_hh2.h2, per-frame constants.
-// All 512 threads share phase A (unit j = tid), the exchange polls (granule tid) and the final 4-way merge of the
-// race.  No AGPR parking: 2 waves/SIMD x 256 registers hold 160 weights + the working set.  S hands its results to C
+// All 512 threads share phase A (unit j = tid) and the exchange polls (granule tid); behind B5 the race costs one LDS read
+// ({sample value, class}: the value comes from a per-class table built once, not from a division).  No AGPR parking: 2 waves/SIMD x 256 registers hold 160 weights + the working set.  S hands its results to C
 // through small LDS slots between the same 5 barriers.  The phase-A conditioning {cI, v_r, v_z, v_n}[512] of every step
 // is precomputed by cond_stream_kernel (prologue.hip) into an 8 KB/step HBM stream instead of being rebuilt from
 // per-frame records in LDS: 57 KB of LDS and ~70 instructions per step saved for 1.6 GB/s of HBM traffic.
@@ -166,6 +166,34 @@ __device__ __forceinline__ float wave_max(float v) {   // max over 64 lanes, val
     return v;
 }
 
+__device__ __forceinline__ float rows_max(float v) {   // max over the 4 DPP rows of a wave whose rows are uniform, valid in lane 63
+    asm volatile(
+        "s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
+        "s_nop 1"
+        : "+v"(v));
+    return v;
+}
+
+// ---- the race exchange (exchange 4): 128 candidates {value, (epoch << 10) | class}, one per C wave of the team, granule 4 g + wl
+// (monotone in class index).  Wave 0 of every workgroup reads all of them: lane l takes granules 2l, 2l + 1 with ONE 16-byte sc1 load
+// (each 8-byte half was written by one store and carries its own tag).  Load and wait are one asm statement: the compiler never sees a
+// register with a load pending on it.
+typedef unsigned u4 __attribute__((ext_vector_type(4)));
+#ifndef T2_RACE_SLEEP
+#define T2_RACE_SLEEP 3   // s_sleep units between the publish and the look (a look that arrives before the data costs a second round trip)
+#endif
+__device__ __forceinline__ u4 race_load(const u64 *base, unsigned off) {
+    u4 g;
+    asm volatile("global_load_dwordx4 %0, %1, %2 sc1\n\t"
+                 "s_waitcnt vmcnt(0)"
+                 : "=&v"(g) : "v"(off), "s"(base) : "memory");
+    return g;
+}
+__device__ __forceinline__ bool race_ok(const u4 &g, unsigned tag) { return (g.y >> 10) == tag && (g.w >> 10) == tag; }
+
 // activation vectors in LDS: element j -> plane p=(j>>2)&7, slot q=j>>5 (8 conflict-free ds_read_b128 per lane).  A plane
 // is 64 floats + 4 of padding: the ds_write_b32 of 32 consecutive elements then touches 32 distinct banks (with 64-float
 // planes the 8 planes of a 32-lane group alias onto 4 banks: 8-way conflict, 27 % of the LDS-active cycles in round 1).
@@ -251,7 +279,8 @@ constexpr int L_XB = L_MISC + 64;              // 6 activation vectors x XB_VEC 
 constexpr int XB_H1 = 0, XB_X2 = 1, XB_X3 = 2, XB_H2 = 3, XB_F1 = 4, XB_F2 = 5;
 constexpr int L_SW = L_XB + 6 * XB_VEC;           // [8 planes][256 S-threads][4]: the n-gate row of W_hh2 (32 weights / S thread)
 constexpr int L_FC3 = L_SW + 8 * 256 * 4;      // [4 C-waves][2 rows][8 planes][64 lanes][4]
-constexpr int L_TOTAL = L_FC3 + 16384;
+constexpr int L_XTAB = L_FC3 + 16384;         // [1024] RAW: the sample value of every class, 2 k / (n_classes - 1) - 1
+constexpr int L_TOTAL = L_XTAB + 1024;
 static_assert(L_TOTAL * 4 <= 163840, "LDS budget");
 constexpr int M_XF = 9, M_DEAD = 10;  // misc slots: fed-back sample, bail-out flag
 
@@ -350,6 +379,10 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
         const float4 *f3 = (const float4 *)(a.team_fc3 + (size_t)g * 16384);
         float4 *dst = (float4 *)(lds + L_FC3);
         for (int i = tid; i < 4096; i += T2_THREADS) dst[i] = f3[i];
+        // RAW: sample = 2 * k / (n_classes - 1.) - 1. (:235) for every class the 10-bit tag can name, evaluated once: the step loop
+        // looks its candidate up instead of dividing on the serial chain
+        if (MODE == WRNN_MODE_RAW)
+            for (int k = tid; k < 1024; k += T2_THREADS) lds[L_XTAB + k] = 2.0f * (float)k / ((float)NC - 1.0f) - 1.0f;
         // per-unit phase-A constants, unit j = tid
         ((float4 *)(lds + L_CSTA))[tid] = make_float4(a.wI0[tid], a.u1[tid], a.u1[512 + tid], a.u1[1024 + tid]);
         if (!isC && q == 0) {
@@ -635,26 +668,40 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
                     const float v0 = has_fc3 ? lg0 + hand[4 + 2 * par] : -INFINITY;
                     const float v1 = (c3row0 + 1 < NC) ? lg1 + hand[5 + 2 * par] : -INFINITY;
                     const bool p1 = v1 > v0;
-                    if (q == 0) st_granule(mail, G_PR + par * 512 + 16 * g + qslot,
-                                           (epoch << 10) | (unsigned)(p1 ? c3row0 + 1 : c3row0), __float_as_uint(p1 ? v1 : v0));
+                    // the wave's four quarters (uniform rows) -> one candidate, in registers; ties -> lowest row = lowest class
+                    const float bq = p1 ? v1 : v0;
+                    const int kq = p1 ? c3row0 + 1 : c3row0;
+                    const float mw = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rows_max(bq)), 63));
+                    const u64 bw = __ballot(bq == mw);
+                    const int kw = __builtin_amdgcn_readlane(kq, (int)__builtin_ctzll(bw ? bw : 1ull));
+                    if (lane == 0) st_granule(mail, G_PR + par * 512 + 4 * g + wl, (epoch << 10) | (unsigned)kw, __float_as_uint(mw));
                     P2(13);
-                    {
-                        // ---- exchange 4: 512 {value,index} granules, 2 per lane over the 4 C waves; each wave leaves its
-                        // winner in LDS, every thread merges the four after B5 (no serial tail on one wave) ----
-                        __builtin_amdgcn_s_sleep(3);
-                        u64 gq[2];
-                        peek_n<2>(mail, G_PR + par * 512 + wl * 128 + lane * 2, 1, gq);
-                        finish_n<2, 42>(mail, G_PR + par * 512 + wl * 128 + lane * 2, 1, epoch & 0x3fffffu, gq, dead, a.err, 14u);
+                    if (wave == 0) {
+                        // ---- exchange 4: wave 0 reduces the team's 128 candidates and leaves {sample value, class} in LDS for everyone.  The
+                        // shadow waves reach B5 later than this wave does (instrumented build: their gh1 gather queues behind the HBM prefetch),
+                        // so nothing here delays the barrier, and behind it the step needs one LDS read: no merge, no division ----
+                        if (T2_RACE_SLEEP) __builtin_amdgcn_s_sleep(T2_RACE_SLEEP);
+                        const unsigned roff = (G_PR + par * 512 + 2u * (unsigned)lane) * 8u;
+                        const unsigned rtag = epoch & 0x3fffffu;
+                        u4 gq = race_load(mail, roff);
+                        for (unsigned spins = 0; !dead && !__all(race_ok(gq, rtag));) {
+                            if (++spins > T2_SPIN_MAX) { dead = true; if (lane == 0) atomicExch(a.err, 14u); break; }
+                            gq = race_load(mail, roff);
+                        }
                         P2(14);
-                        const float va = __uint_as_float((unsigned)gq[0]), vb = __uint_as_float((unsigned)gq[1]);
+                        const float va = __uint_as_float(gq.x), vb = __uint_as_float(gq.z);
                         const bool pb_ = vb > va;
                         const float best = pb_ ? vb : va;
-                        const int besti = (int)(((pb_ ? gq[1] : gq[0]) >> 32) & 1023u);
+                        const int besti = (int)((pb_ ? gq.w : gq.y) & 1023u);
+                        // sample = 2 * k / (n_classes - 1.) - 1.   (:235): every lane looks up its own candidate's while the maximum is reduced
+                        const float bestx = lds[L_XTAB + besti];
                         const float mx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_max(best)), 63));
                         const u64 ball = __ballot(best == mx);
-                        const int src = (int)__builtin_ctzll(ball ? ball : 1ull);
-                        const int k = __builtin_amdgcn_readlane(besti, src);
-                        if (lane == 0) { misc_f[16 + 2 * wl] = mx; misc_i[17 + 2 * wl] = k; }
+                        const int src = (int)__builtin_ctzll(ball ? ball : 1ull);   // ties -> lowest granule = lowest class
+                        if (lane == 0) {
+                            misc_i[16] = __builtin_amdgcn_readlane(__float_as_int(bestx), src);
+                            misc_i[17] = __builtin_amdgcn_readlane(besti, src);
+                        }
                     }
                 } else {
                     // MOL (distribution.py:87-123): the 30 fc3 outputs are exchanged, wave 0 of every WG samples
@@ -717,18 +764,16 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
                     if (q == 0) { hand[0] = sr; hand[1] = sz; hand[2] = sn; }
                 }
             }
+            // PROF slots of the tail: 13 = race compute + 4 -> 1 + publish (C) | gh1 gather (S); 14 = exchange-4 wait (wave 0); 11 = 128 -> 1 and
+            // the sample value -> LDS (wave 0) | gh2 (S) | nothing (waves 1-3); 12 = B5; 15 = what is left of the merge: one LDS read
             P2(11);
             __syncthreads();  // B5
             P2(12);
             if (MODE == WRNN_MODE_RAW) {
-                // merge the four per-wave race winners (ties -> lower wave = lower class index range)
-                const float4 m0 = *(const float4 *)(misc_f + 16), m1 = *(const float4 *)(misc_f + 20);
-                float bv = m0.x; int bk = __float_as_int(m0.y);
-                if (m0.z > bv) { bv = m0.z; bk = __float_as_int(m0.w); }
-                if (m1.x > bv) { bv = m1.x; bk = __float_as_int(m1.y); }
-                if (m1.z > bv) { bv = m1.z; bk = __float_as_int(m1.w); }
-                // sample = 2 * k / (n_classes - 1.) - 1.   (:235)
-                const float x_new = 2.0f * (float)bk / ((float)NC - 1.0f) - 1.0f;
+                const float2 win = *(const float2 *)(misc_f + 16);   // {sample value, class} of the race winner
+                const float x_new = win.x;
+                const int bk = __float_as_int(win.y);
+                P2(15);
                 // (:237) The teacher-forced value is waited for INSIDE its branch: with `cond ? load : x_new` the compiler cannot know at
                 // the top of the next step whether a load into xfeed is pending and opens EVERY step with `s_waitcnt vmcnt(0)` -- which also
                 // waits for workgroup 0's output stores just below and for the S waves' conditioning prefetch of step t + 2 (round 4,

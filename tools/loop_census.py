@@ -1,6 +1,12 @@
 """Static census of the step loops of loop_batch_cs_kernel's generated ISA (no GPU needed).
 
     python tools/loop_census.py [-DCS_KNOB=1 ...] > profiles/rNN_static_census_batch_cs.txt
+    python tools/loop_census.py --team2 [-DT2_KNOB=1 ...]      # the latency kernel: loop_team2_kernel<RAW> per barrier window
+
+--team2: the step loop of the shipped loop_team2_kernel instantiation split at its workgroup barriers (window 0 = phase A in front of B1,
+window 5 = behind B5), per window the instruction mix and the spill traffic (`scratch_*`, `v_readlane / v_writelane`), and for every scratch
+instruction the wave role whose code it sits in: critical (C), shadow (S) or shared, taken from the line table (-gline-tables-only) against the
+`if (isC) {...} else {...}` blocks and the S-only lambdas of the source.
 
 For every non-instrumented instantiation: hipcc's resource remarks, and for each ROLE's step loop (the C waves' and the S waves' loops are separate
 code: the innermost loops that contain workgroup barriers and MFMAs) the static instruction mix -- above all the spill traffic that sits on a step:
@@ -84,7 +90,104 @@ def fmt(c):
     return ', '.join(f'{k} {c[k]}' for k in ['instr'] + [k for k, _ in CLASSES] if c.get(k))
 
 
+def team2_roles(src_lines):
+    """source line (1-based) -> 'C' / 'S' for the role blocks of the step loop and the S-only lambdas; every other line is absent (shared)."""
+    role, stack, depth, lam = {}, [], 0, None
+    for n, l in enumerate(src_lines, 1):
+        t = l.strip()
+        if lam is None and re.match(r'auto s_\w+ = \[&\]', t):
+            lam = depth
+        if stack and t.startswith('} else {') and depth - 1 == stack[-1][0]:
+            stack[-1][1] = 'S'
+        elif re.match(r'if \(isC\) \{$', t):
+            stack.append([depth, 'C'])
+        if lam is not None:
+            role[n] = 'S'
+        elif stack:
+            role[n] = stack[-1][1]
+        depth += l.count('{') - l.count('}')
+        if stack and depth <= stack[-1][0]:
+            stack.pop()
+        if lam is not None and depth <= lam:
+            lam = None
+    return role
+
+
+def team2_main(extra) -> int:
+    flags = [f for f in FLAGS if f not in ('-mllvm', '-amdgpu-mfma-vgpr-form')]
+    with tempfile.TemporaryDirectory() as td:
+        asm = os.path.join(td, 't2.s')
+        r = subprocess.run([HIPCC, *flags, *extra, '-gline-tables-only', '--cuda-device-only', '-S', 'loop_team2.hip', '-o', asm, '-Rpass-analysis=kernel-resource-usage'],
+                           capture_output=True, text=True, cwd=CSRC)
+        if r.returncode:
+            sys.stderr.write(r.stderr)
+            return 1
+        txt = open(asm).read()
+        # the resource remarks from a compile without the line table (same code; the spill statistic counts debug instructions otherwise)
+        r = subprocess.run([HIPCC, *flags, *extra, '--cuda-device-only', '-S', 'loop_team2.hip', '-o', asm, '-Rpass-analysis=kernel-resource-usage'],
+                           capture_output=True, text=True, cwd=CSRC)
+        plain = [l.split(';')[0].strip() for l in open(asm).read().split('\n')]
+        code = lambda ls: [l for l in ls if l and l[0] != '.' and not l.endswith(':')]
+        assert code(plain) == code([x.split(';')[0].strip() for x in txt.split('\n')]), \
+            'the line table changed the generated code'
+    fn = '_Z17loop_team2_kernelILi0ELb0ELb0EEv12WrnnTeamArgs'
+    res = re.findall(r'remark:\s+((?:TotalSGPRs|VGPRs|ScratchSize|SGPRs Spill|VGPRs Spill).*?)\s*\[-Rpass', r.stderr.split('Function Name: ' + fn)[1].split('Function Name:')[0])
+    m = re.search(r'\n' + fn + r':[^\n]*\n(.*?)\n\s*s_endpgm', txt, re.S)
+    lines = m.group(1).split('\n')
+    roles = team2_roles(open(os.path.join(CSRC, 'loop_team2.hip')).read().split('\n'))
+    # (instruction, role) with the role of the latest line-table entry that names a line of a role block; code inlined from helpers keeps its caller's
+    tagged, cur = [], 'shared'
+    for l in lines:
+        mm = re.match(r'\s*\.loc\s+\d+\s+(\d+)', l)
+        if mm:
+            n = int(mm.group(1))
+            if n in roles:
+                cur = roles[n]
+            elif n >= STEP_LOOP_FIRST_LINE[0]:
+                cur = 'shared'
+            continue
+        tagged.append((l, cur))
+    lab = {mm.group(1): i for i, (l, _) in enumerate(tagged) if (mm := re.match(r'^(\.LBB\d+_\d+):', l))}
+    loops = []
+    for i, (l, _) in enumerate(tagged):
+        mm = re.search(r'\b(?:s_cbranch_\w+|s_branch)\s+(\.LBB\d+_\d+)', l)
+        if mm and mm.group(1) in lab and lab[mm.group(1)] < i:
+            loops.append((lab[mm.group(1)], i))
+    nbar = lambda a, b: sum(l.strip().startswith('s_barrier') for l, _ in tagged[a:b + 1])
+    a, b = min(((b - a, a, b) for a, b in loops if nbar(a, b) >= 5))[1:]
+    body = tagged[a:b + 1]
+    print(f'# tools/loop_census.py --team2 {" ".join(extra)}: loop_team2_kernel<RAW, false, false> as in the tree (hipcc -O3 --offload-arch=gfx950)')
+    print('== ' + ' | '.join(x.strip() for x in res))
+    print(f'   step loop (per-step path, the every-64-steps bail-out block aside): {fmt(census([l for l, _ in body]))}')
+    cuts = [i for i, (l, _) in enumerate(body) if l.strip().startswith('s_barrier')]
+    lo = 0
+    for wi, c in enumerate(cuts + [len(body)]):
+        part = body[lo:c]
+        lo = c + 1
+        wc = census([l for l, _ in part])
+        name = 'phase A, in front of B1' if wi == 0 else f'B{wi} .. ' + (f'B{wi + 1}' if wi < len(cuts) else 'end of the step')
+        print(f'   window {wi} ({name}): {fmt(wc)}')
+        for l, role in part:
+            t = l.strip().split(';')[0].strip()
+            if t.startswith('scratch_'):
+                print(f'      {t:48s} <- {role} waves\' code')
+        by = {}
+        for l, role in part:
+            if l.strip().startswith(('v_readlane_b32', 'v_writelane_b32')):
+                by[role] = by.get(role, 0) + 1
+        if by:
+            print('      v_readlane / v_writelane by role: ' + ', '.join(f'{k} {v}' for k, v in sorted(by.items())))
+    return 0
+
+
+STEP_LOOP_FIRST_LINE = [0]
+
+
 def main() -> int:
+    if '--team2' in sys.argv[1:]:
+        src = open(os.path.join(CSRC, 'loop_team2.hip')).read().split('\n')
+        STEP_LOOP_FIRST_LINE[0] = next(n for n, l in enumerate(src, 1) if 'for (int64_t t = a.seg0; t < seg_end; ++t)' in l)
+        return team2_main([a for a in sys.argv[1:] if a.startswith('-') and a != '--team2'])
     want_windows = '--windows' in sys.argv[1:]
     extra = [a for a in sys.argv[1:] if a.startswith('-') and a != '--windows']
     with tempfile.TemporaryDirectory() as td:
