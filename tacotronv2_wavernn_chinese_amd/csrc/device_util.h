@@ -38,6 +38,16 @@ __host__ __device__ inline float wrnn_uniform(uint64_t seed, uint64_t t, uint32_
     return u01_from_bits(bits);
 }
 
+// MOL sampling noise: the draw above mapped into the reference's uniform_(1e-5, 1 - 1e-5) (distribution.py:106,118),
+// k < 10 the mixture pick, k == 10 the logistic draw.  ONE fused multiply-add, spelled out: left as `1e-5f + w * c` the
+// contraction is the compiler's choice per call site, and the two roundings differ on 27 % of the 2^23 inputs (the
+// logistic noise by up to 4e-5) -- every MOL kernel must feed its logf the same u for the same (seed, t, row), and
+// tests/philox_ref.py replays exactly this form.  Range: [1.0059e-5, 0.99998993], inside the reference's.
+__host__ __device__ inline float wrnn_mol_from_u01(float w) { return fmaf(w, 1.0f - 2e-5f, 1e-5f); }
+__host__ __device__ inline float wrnn_uniform_mol(uint64_t seed, uint64_t t, uint32_t row, uint32_t k) {
+    return wrnn_mol_from_u01(wrnn_uniform(seed, t, row, k));
+}
+
 // RAW sampling noise: the uniform behind q_k of (step t, row, class k).  One Philox block serves classes
 // (2j, 2j+1) for steps (2s, 2s+1): block counter (t>>1, row, k>>1), element ((t&1)<<1)|(k&1) -- a kernel that
 // owns a class pair evaluates the block every other step.

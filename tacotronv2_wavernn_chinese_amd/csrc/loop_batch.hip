@@ -610,7 +610,7 @@ __global__ void __launch_bounds__(TB_THREADS) loop_batch_kernel(WrnnBatchArgs a)
                         if (a.noise_mode == WRNN_NOISE_INJECTED)
                             u = lane < nr ? a.noise1[((size_t)t * a.n_rows + rrow) * nr + lane] : a.noise2[(size_t)t * a.n_rows + rrow];
                         else
-                            u = 1e-5f + wrnn_uniform(a.seed, (uint64_t)t, (uint32_t)rrow, (uint32_t)lane) * (1.0f - 2e-5f);
+                            u = wrnn_uniform_mol(a.seed, (uint64_t)t, (uint32_t)rrow, (uint32_t)lane);
                         nzv = lane < nr ? -logf(-logf(u)) : logf(u) - logf(1.0f - u);
                     }
                     float mylg = 0.0f;

@@ -235,7 +235,7 @@ __global__ void __launch_bounds__(SIMPLE_THREADS) loop_simple_kernel(WrnnLoopArg
                 if (lane < nr) {
                     float u1;
                     if (a.noise_mode == WRNN_NOISE_INJECTED) u1 = a.noise1[((size_t)t * a.n_rows + row) * nr + lane];
-                    else u1 = 1e-5f + wrnn_uniform(a.seed, (uint64_t)t, (uint32_t)row, (uint32_t)lane) * (1.0f - 2e-5f);
+                    else u1 = wrnn_uniform_mol(a.seed, (uint64_t)t, (uint32_t)row, (uint32_t)lane);
                     v = s_logits[lane] - logf(-logf(u1));   // :107
                     k = lane;
                 }
@@ -243,7 +243,7 @@ __global__ void __launch_bounds__(SIMPLE_THREADS) loop_simple_kernel(WrnnLoopArg
                 if (lane == 0) {
                     float u2;
                     if (a.noise_mode == WRNN_NOISE_INJECTED) u2 = a.noise2[(size_t)t * a.n_rows + row];
-                    else u2 = 1e-5f + wrnn_uniform(a.seed, (uint64_t)t, (uint32_t)row, 10u) * (1.0f - 2e-5f);
+                    else u2 = wrnn_uniform_mol(a.seed, (uint64_t)t, (uint32_t)row, 10u);
                     const float mean = s_logits[nr + k];                       // :113
                     const float ls = fmaxf(s_logits[2 * nr + k], -32.23619130191664f);  // log(1e-14) :114-115
                     float xs = mean + expf(ls) * (logf(u2) - logf(1.0f - u2));  // :119

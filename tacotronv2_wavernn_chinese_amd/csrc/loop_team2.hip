@@ -471,7 +471,7 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
                 if (a.noise_mode == WRNN_NOISE_INJECTED)
                     u = lane < nr ? a.noise1[((size_t)ts * a.n_rows + row) * nr + lane] : a.noise2[(size_t)ts * a.n_rows + row];
                 else
-                    u = 1e-5f + wrnn_uniform(a.seed, (uint64_t)ts, (uint32_t)row, (uint32_t)lane) * (1.0f - 2e-5f);
+                    u = wrnn_uniform_mol(a.seed, (uint64_t)ts, (uint32_t)row, (uint32_t)lane);
                 misc_f[32 + 16 * (ep_of_ts & 1u) + lane] = lane < nr ? -logf(-logf(u)) : logf(u) - logf(1.0f - u);
             }
             if (MODE == WRNN_MODE_RAW && has_fc3) {
