@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define WRNN_ABI_VERSION 7
+#define WRNN_ABI_VERSION 8
 
 /* mode: fatchord_version.py:98-103 */
 #define WRNN_MODE_RAW 0 /* softmax over 2**bits classes */
@@ -274,7 +274,8 @@ int wrnn_sync_status(wrnn_handle *h, void *stream);
 int wrnn_train_force_step_kernels(wrnn_handle *h, int32_t on);
 
 /* Blocks until the last wrnn_generate on this handle finished, then reports
- * HIP-event timings and any device-side error (WRNN_ERR_TIMEOUT). */
+ * HIP-event timings and any device-side error (WRNN_ERR_TIMEOUT, WRNN_ERR_BUSY; WRNN_ERR_INVALID when the fold count a
+ * folded call computed on the device differs from its rows_total). */
 int wrnn_last_timing(wrnn_handle *h, wrnn_timing *out);
 
 /* Developer instrumentation (replaces the WRNN_TEAM_PROF environment variable of ABI 3): enable != 0 makes the following
@@ -342,6 +343,44 @@ int64_t wrnn_stream_ready_steps(int64_t frames_in, int32_t hop, int32_t pad, int
 
 /* Waits for the device, then frees the stream's device memory.  NULL is a no-op. */
 void wrnn_stream_close(wrnn_stream *st);
+
+/* ---- fold mode for SEVERAL utterances in one call (ABI 8) --------------------------------------------------------------------
+ * The reference folds one utterance (fold_with_overlap :293-340 indexes a batch-1 tensor).  A serving loop with several clips
+ * queued folds ALL of them with one common fold length: every fold of every clip is one loop row of target + 2*overlap steps,
+ * so the call fills the 8 x 8 rows of the batch kernel even when no single clip could.  Utterance b is cut exactly as a call
+ * on that clip alone cuts it -- n_b folds by the rule of the plan entry above, fold i from position i * (target + overlap), zero
+ * conditioning past the clip's OWN end frames[b] * hop (:327-330) -- and its folds are the consecutive rows
+ * fold0[b] .. fold0[b + 1] - 1 of the outputs.
+ *
+ * Host only, no handle: fold0_out[b] = first row of utterance b, fold0_out[B] = rows in all (B + 1 entries); *steps_out =
+ * target + 2*overlap (may be NULL).  total_b = frames_host[b] * hop samples.  WRNN_ERR_INVALID: bad arguments, frames_host[b] < 1, an
+ * utterance that yields no fold (shorter than `overlap`), or more than INT32_MAX rows. */
+int wrnn_plan_folded(const int32_t *frames_host, int32_t B, int32_t hop, int32_t target, int32_t overlap, int32_t *fold0_out,
+                     int64_t *steps_out);
+
+/* Prologue + loop of such a call.  mels_dev (B, feat, T), every clip right-zero-padded to T frames; frames_dev: B int32 on the
+ * device, 1 <= frames_dev[b] <= T; rows_total = fold0_out[B] of the plan above for the same frames / target / overlap.
+ *   labels_out_dev / samples_out_dev (rows_total, target + 2*overlap), as the generate entry writes them.
+ * The row table is built on the device from frames_dev (nothing is staged on the host, the call never waits); when the
+ * device's fold count differs from rows_total no row outside [0, rows_total) is touched and the timing entry reports
+ * WRNN_ERR_INVALID.  Kernel choice, opts->batch_rows, opts->team2_segment, segmentation and the per-device team gate work as
+ * for rows_total rows of one folded utterance; wrnn_timing.rows = rows_total.  Noise: WRNN_NOISE_INJECTED arrays are
+ * (steps, rows_total, .); the WRNN_NOISE_PHILOX row key is the GLOBAL row index fold0[b] + i, so a clip's draws depend on
+ * its position in the call (per-request keys are not provided).  opts->frames_dev, mels_padded, x_forced_dev, x_init_dev and
+ * logits_out_dev must be 0 / NULL (WRNN_ERR_INVALID). */
+int wrnn_generate_folded(wrnn_handle *h, const float *mels_dev, int32_t B, int32_t T, const int32_t *frames_dev, int32_t rows_total,
+                         int32_t target, int32_t overlap, const wrnn_sample_opts *opts, int32_t *labels_out_dev,
+                         float *samples_out_dev, void *stream);
+
+/* The float64 tail of every utterance of the last folded call on this handle, one launch: utterance b's rows are decoded,
+ * crossfaded and unfolded with the arithmetic of the single-utterance tail (:342-405), trimmed to wave_len_b =
+ * (frames_dev[b] - 1) * hop, faded out over the last 20 hops (:255-258) and written to wave_out_dev[b * out_stride + n];
+ * entries [wave_len_b, out_stride) are set to 0, a clip shorter than the fade-out is all zeros (the host side rejects those).
+ * Reads the fold offsets that call left on the handle: WRNN_ERR_STATE when there was none or its B, target, overlap or
+ * rows_total differ.  steps must be target + 2*overlap. */
+int wrnn_epilogue_folded(wrnn_handle *h, const float *samples_dev, const int32_t *labels_dev, int32_t B, int32_t rows_total,
+                         int64_t steps, int32_t target, int32_t overlap, int32_t mu_law, const int32_t *frames_dev,
+                         double *wave_out_dev, int64_t out_stride, void *stream);
 
 const char *wrnn_last_error(const wrnn_handle *h);
 int32_t wrnn_abi_version(void);

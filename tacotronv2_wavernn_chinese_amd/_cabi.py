@@ -24,8 +24,8 @@ KERNEL_IDS = {v: k for k, v in KERNEL_NAMES.items()}
 DTYPE_F32, DTYPE_I64 = 0, 1
 ERR_NAMES = {0: 'WRNN_OK', -1: 'WRNN_ERR_INVALID', -2: 'WRNN_ERR_HIP', -3: 'WRNN_ERR_STATE',
              -4: 'WRNN_ERR_MISSING_KEY', -5: 'WRNN_ERR_TIMEOUT', -6: 'WRNN_ERR_BUSY'}
-ERR_INVALID, ERR_TIMEOUT, ERR_BUSY = -1, -5, -6
-ABI_VERSION = 7   # WRNN_ABI_VERSION of the include/wavernn_amd.h this binding was written against
+ERR_INVALID, ERR_STATE, ERR_TIMEOUT, ERR_BUSY = -1, -3, -5, -6
+ABI_VERSION = 8   # WRNN_ABI_VERSION of the include/wavernn_amd.h this binding was written against
 
 # every symbol include/wavernn_amd.h declares (checked by tests/test_cabi_symbols.py)
 EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wrnn_plan', 'wrnn_generate',
@@ -35,7 +35,7 @@ EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wr
                     'wrnn_dm_create', 'wrnn_dm_load_weights', 'wrnn_dm_generate', 'wrnn_dm_last_error', 'wrnn_dm_destroy',
                     'wrnn_dm_set_kernel', 'wrnn_dm_sync_status', 'wrnn_team_info', 'wrnn_debug_force_no_teams',
                     'wrnn_stream_open', 'wrnn_stream_push', 'wrnn_stream_sync', 'wrnn_stream_info', 'wrnn_stream_ready_steps',
-                    'wrnn_stream_close')
+                    'wrnn_stream_close', 'wrnn_plan_folded', 'wrnn_generate_folded', 'wrnn_epilogue_folded')
 
 
 def epilogue_tables(n_classes: int, overlap: int, hop: int):
@@ -197,6 +197,12 @@ def load_library() -> C.CDLL:
     lib.wrnn_stream_ready_steps.restype = C.c_int64
     lib.wrnn_stream_close.argtypes = [vp]
     lib.wrnn_stream_close.restype = None
+    lib.wrnn_plan_folded.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.POINTER(C.c_int64)]
+    lib.wrnn_plan_folded.restype = C.c_int
+    lib.wrnn_generate_folded.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SampleOpts), vp, vp, vp]
+    lib.wrnn_generate_folded.restype = C.c_int
+    lib.wrnn_epilogue_folded.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_int64, vp]
+    lib.wrnn_epilogue_folded.restype = C.c_int
     lib.wrnn_dm_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
     lib.wrnn_dm_create.restype = C.c_int
     lib.wrnn_dm_load_weights.argtypes = [vp, C.POINTER(TensorDesc), C.c_int32]
@@ -313,6 +319,24 @@ class NativeVocoder:
         self._check(self.lib.wrnn_generate(self._h, mels_ptr, B, T, int(bool(batched)), int(target), int(overlap),
                                            C.byref(o), labels_ptr or None, samples_ptr, stream or None))
 
+    def generate_folded(self, mels_ptr: int, B: int, T: int, frames_ptr: int, rows_total: int, target: int, overlap: int, *,
+                        labels_ptr: int, samples_ptr: int, stream: int, noise_mode: int = NOISE_PHILOX, seed: int = 0,
+                        noise1_ptr: int = 0, noise2_ptr: int = 0, kernel: int = KERNEL_AUTO, batch_rows: int = 0, team2_segment: int = 0):
+        """``wrnn_generate_folded``: the folds of all B utterances as the rows of one call (rows_total from :func:`plan_folded`)."""
+        o = SampleOpts()
+        o.struct_size = C.sizeof(SampleOpts)
+        o.batch_rows, o.team2_segment = int(batch_rows), int(team2_segment)
+        o.noise_mode, o.kernel, o.seed = noise_mode, kernel, seed & 0xFFFFFFFFFFFFFFFF
+        o.noise1_dev, o.noise2_dev = noise1_ptr or None, noise2_ptr or None
+        self._check(self.lib.wrnn_generate_folded(self._h, mels_ptr, B, T, frames_ptr or None, int(rows_total), int(target), int(overlap),
+                                                  C.byref(o), labels_ptr or None, samples_ptr, stream or None))
+
+    def epilogue_folded(self, samples_ptr: int, labels_ptr: int, B: int, rows_total: int, steps: int, target: int, overlap: int,
+                        mu_law: bool, frames_ptr: int, out_ptr: int, out_stride: int, stream: int):
+        """Every utterance of the last ``generate_folded`` call crossfaded, unfolded, trimmed and faded out, one launch."""
+        self._check(self.lib.wrnn_epilogue_folded(self._h, samples_ptr, labels_ptr or None, int(B), int(rows_total), int(steps), int(target),
+                                                  int(overlap), int(bool(mu_law)), frames_ptr or None, out_ptr, int(out_stride), stream or None))
+
     def epilogue(self, samples_ptr: int, labels_ptr: int, rows: int, steps: int, batched: bool, target: int,
                  overlap: int, mu_law: bool, wave_len: int, out_ptr: int, stream: int):
         self._check(self.lib.wrnn_epilogue(self._h, samples_ptr, labels_ptr or None, rows, steps, int(bool(batched)),
@@ -381,6 +405,19 @@ class NativeVocoder:
         self._check(self.lib.wrnn_last_timing(self._h, C.byref(t)))
         return dict(prologue_ms=t.prologue_ms, loop_ms=t.loop_ms, kernel=t.kernel, rows=t.rows, steps=t.steps,
                     launches=t.launches)
+
+
+def plan_folded(frames, hop: int, target: int, overlap: int) -> Tuple[np.ndarray, int]:
+    """Host-only ``wrnn_plan_folded``: (fold0 (B + 1,) int32 -- first row of every utterance, fold0[B] = rows in all --, steps per row) for
+    a call that folds utterances of ``frames[b]`` mel frames with one ``target``.  ``WrnnError`` (WRNN_ERR_INVALID) for an utterance that
+    yields no fold or bad arguments."""
+    fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+    fold0 = np.zeros(fr.size + 1, np.int32)
+    steps = C.c_int64()
+    rc = load_library().wrnn_plan_folded(fr.ctypes.data, int(fr.size), int(hop), int(target), int(overlap), fold0.ctypes.data, C.byref(steps))
+    if rc != 0:
+        raise WrnnError(rc, f'wrnn_plan_folded: no fold plan for frames {fr.tolist()[:8]}{"..." if fr.size > 8 else ""}, hop {hop}, target {target}, overlap {overlap}')
+    return fold0, int(steps.value)
 
 
 def stream_ready_steps(frames_in: int, hop: int, pad: int, last: bool) -> int:

@@ -2,6 +2,7 @@
 // Host-side work here is limited to: validating the configuration, repacking
 // the reference state_dict into the device layouts the kernels want, and
 // enqueueing kernels on the caller's stream.
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -196,6 +197,7 @@ void wrnn_destroy(wrnn_handle *h) {
     if (h->rows_dev) (void)hipFree(h->rows_dev);
     if (h->order_dev) (void)hipFree(h->order_dev);
     if (h->sched_dev) (void)hipFree(h->sched_dev);
+    if (h->fold0_dev) (void)hipFree(h->fold0_dev);
     if (h->prof) (void)hipFree(h->prof);
     if (h->err_dev) (void)hipFree(h->err_dev);
     if (h->team_w) (void)hipFree(h->team_w);
@@ -510,8 +512,13 @@ int wrnn_plan(wrnn_handle *h, int32_t B, int32_t T, int32_t batched, int32_t tar
     return WRNN_OK;
 }
 
-int wrnn_generate(wrnn_handle *h, const float *mels_dev, int32_t B, int32_t T, int32_t batched, int32_t target, int32_t overlap,
-                  const wrnn_sample_opts *opts, int32_t *labels_out_dev, float *samples_out_dev, void *stream) {
+}  // extern "C"
+
+// Body of wrnn_generate and wrnn_generate_folded.  fold_frames != null: the rows are the folds of ALL B utterances (rows_total of them,
+// see rows_folded_kernel), every per-frame table entry past an utterance's own end is its zero-input entry T.
+static int generate_impl(wrnn_handle *h, const float *mels_dev, int32_t B, int32_t T, int32_t batched, int32_t target, int32_t overlap,
+                         const wrnn_sample_opts *opts, int32_t *labels_out_dev, float *samples_out_dev, void *stream,
+                         const int32_t *fold_frames, int32_t rows_total) {
     if (!h || !mels_dev || !opts || !samples_out_dev) return fail(h, WRNN_ERR_INVALID, "wrnn_generate: bad arguments");
     if (opts->struct_size != sizeof(wrnn_sample_opts))
         return fail(h, WRNN_ERR_INVALID, "wrnn_sample_opts.struct_size is %u, this library (ABI %d) expects %zu: caller built against another revision of wavernn_amd.h",
@@ -523,7 +530,11 @@ int wrnn_generate(wrnn_handle *h, const float *mels_dev, int32_t B, int32_t T, i
     const WrnnDims &d = h->d;
     int32_t rows = 0;
     int64_t steps = 0;
-    if (int rc = wrnn_plan(h, B, T, batched, target, overlap, &rows, &steps)) return rc;
+    if (fold_frames) {
+        if (B < 1 || T < 1 || rows_total < 1 || target < 1 || overlap < 0) return fail(h, WRNN_ERR_INVALID, "wrnn_generate_folded: bad arguments");
+        rows = rows_total;
+        steps = (int64_t)target + 2LL * overlap;
+    } else if (int rc = wrnn_plan(h, B, T, batched, target, overlap, &rows, &steps)) return rc;
     if (opts->noise_mode == WRNN_NOISE_INJECTED && (!opts->noise1_dev || (d.mode == WRNN_MODE_MOL && !opts->noise2_dev)))
         return fail(h, WRNN_ERR_INVALID, "WRNN_NOISE_INJECTED needs noise pointers");
     if (opts->noise_mode == WRNN_NOISE_ARGMAX && d.mode != WRNN_MODE_RAW)
@@ -546,12 +557,25 @@ int wrnn_generate(wrnn_handle *h, const float *mels_dev, int32_t B, int32_t T, i
     }
     const int sched_teams = h->n_teams < 1 ? 1 : h->n_teams;
     const int n_slots = (rows + sched_teams - 1) / sched_teams * sched_teams;
-    HIP_TRY(h, wrnn_launch_rows(h->rows_dev, h->order_dev, h->sched_dev, rows, sched_teams, batched, (long)target + overlap, (long)steps,
-                                opts->frames_dev, T, d.HOP, s));
+    HIP_TRY(h, hipMemsetAsync(h->err_dev, 0, 64, s));
+    if (fold_frames) {
+        h->fold_B = 0;   // the fold offsets on the handle are valid once the kernel that writes them is enqueued
+        if ((size_t)B + 1 > h->fold0_cap) {
+            if (h->fold0_dev) (void)hipFree(h->fold0_dev);
+            h->fold0_dev = nullptr; h->fold0_cap = 0;
+            HIP_TRY(h, hipMalloc(&h->fold0_dev, ((size_t)B + 1) * sizeof(int32_t)));
+            h->fold0_cap = (size_t)B + 1;
+        }
+        HIP_TRY(h, wrnn_launch_rows_folded(h->rows_dev, h->order_dev, h->sched_dev, h->fold0_dev, h->err_dev, fold_frames, B, rows, sched_teams,
+                                           (long)target, (long)overlap, d.HOP, T, s));
+        h->fold_B = B; h->fold_target = target; h->fold_overlap = overlap; h->fold_rows = rows;
+    } else {
+        HIP_TRY(h, wrnn_launch_rows(h->rows_dev, h->order_dev, h->sched_dev, rows, sched_teams, batched, (long)target + overlap, (long)steps,
+                                    opts->frames_dev, T, d.HOP, s));
+    }
     const int snake = opts->frames_dev ? 1 : 0;
     unsigned long long *const prof = h->prof_on ? h->prof : nullptr;
     if (int rc = ensure_aux(h, B, T)) return rc;
-    HIP_TRY(h, hipMemsetAsync(h->err_dev, 0, 64, s));
 
     HIP_TRY(h, hipEventRecord(h->ev[0], s));
     const int mel_T = opts->mels_padded ? T + 2 * d.P : T, mel_off = opts->mels_padded ? d.P : 0;
@@ -563,7 +587,7 @@ int wrnn_generate(wrnn_handle *h, const float *mels_dev, int32_t B, int32_t T, i
     a.n_rows = rows; a.T = T; a.total_len = (int64_t)T * d.HOP; a.steps = steps;
     a.noise_mode = opts->noise_mode; a.seed = opts->seed; a.noise1 = opts->noise1_dev; a.noise2 = opts->noise2_dev;
     a.x_forced = opts->x_forced_dev; a.x_init = opts->x_init_dev; a.logits_out = opts->logits_out_dev; a.labels_out = labels_out_dev;
-    a.samples_out = samples_out_dev; a.err = h->err_dev;
+    a.samples_out = samples_out_dev; a.err = h->err_dev; a.frames = fold_frames;
     int kernel = opts->kernel;
     int launches = 1;
     // what the team kernels (TEAM2, BATCH) need: co-residency (checked in wrnn_create), the 5-frame upsampling support
@@ -609,7 +633,7 @@ int wrnn_generate(wrnn_handle *h, const float *mels_dev, int32_t B, int32_t T, i
         if (batch_family) {
             // R = 4 * nq rows per XCD team in lock-step on the matrix cores (loop_batch.hip); the rows are spread evenly over
             // the teams first (rpb rows per batch), a team runs ceil(batches / n_teams) batches one after the other
-            HIP_TRY(h, wrnn_launch_pack_records32(tCM, tCA, tVM, tVA, tC2, tC3, tC4, tREC, B, T, P, s));
+            HIP_TRY(h, wrnn_launch_pack_records32(tCM, tCA, tVM, tVA, tC2, tC3, tC4, tREC, B, T, P, fold_frames, s));
             int rpb = (rows + h->n_teams - 1) / h->n_teams;
             if (rpb > WRNN_BATCH_MAX_ROWS) rpb = WRNN_BATCH_MAX_ROWS;
             if (opts->batch_rows > 0) rpb = opts->batch_rows;
@@ -635,7 +659,8 @@ int wrnn_generate(wrnn_handle *h, const float *mels_dev, int32_t B, int32_t T, i
             HIP_TRY(h, ge);
             h->prof_div = (double)steps * ((((rows + rpb - 1) / rpb) + h->n_teams - 1) / h->n_teams);
         } else {
-        HIP_TRY(h, wrnn_launch_pack_records(tCM, tCA, tVM, tVA, tREC, B, T, P, s));
+        HIP_TRY(h, wrnn_launch_pack_records(tCM, tCA, tVM, tVA, tREC, B, T, P, fold_frames, s));
+        if (fold_frames) HIP_TRY(h, wrnn_launch_mask_frame_tables(tC2, tC3, tC4, fold_frames, B, T, s));
         WrnnTeamArgs ta{};
         ta.w = w; ta.off = o; ta.d = d; ta.team_w = h->team_w; ta.team_fc3 = h->team_fc3; ta.wI0 = h->wI0; ta.u1 = h->u1;
         ta.tabREC = tREC; ta.tabCOND = nullptr; ta.tabC2 = tC2; ta.tabC3 = tC3; ta.tabC4 = tC4;
@@ -698,6 +723,45 @@ int wrnn_generate(wrnn_handle *h, const float *mels_dev, int32_t B, int32_t T, i
     return WRNN_OK;
 }
 
+extern "C" {
+
+int wrnn_generate(wrnn_handle *h, const float *mels_dev, int32_t B, int32_t T, int32_t batched, int32_t target, int32_t overlap,
+                  const wrnn_sample_opts *opts, int32_t *labels_out_dev, float *samples_out_dev, void *stream) {
+    return generate_impl(h, mels_dev, B, T, batched, target, overlap, opts, labels_out_dev, samples_out_dev, stream, nullptr, 0);
+}
+
+int wrnn_plan_folded(const int32_t *frames_host, int32_t B, int32_t hop, int32_t target, int32_t overlap, int32_t *fold0_out,
+                     int64_t *steps_out) {
+    if (!frames_host || !fold0_out || B < 1 || hop < 1 || target < 1 || overlap < 0) return WRNN_ERR_INVALID;
+    const int64_t stride = (int64_t)target + overlap;
+    int64_t acc = 0;
+    fold0_out[0] = 0;
+    for (int32_t b = 0; b < B; ++b) {
+        if (frames_host[b] < 1) return WRNN_ERR_INVALID;
+        // Python floor division like fatchord_version.py:319-325 (see wrnn_plan)
+        const int64_t total = (int64_t)frames_host[b] * hop, num = total - overlap;
+        int64_t n = num / stride;
+        if (num % stride != 0 && num < 0) --n;
+        if (total - (n * stride + overlap) != 0) ++n;
+        if (n < 1) return WRNN_ERR_INVALID;   // shorter than one fold
+        acc += n;
+        if (acc > INT32_MAX) return WRNN_ERR_INVALID;
+        fold0_out[b + 1] = (int32_t)acc;
+    }
+    if (steps_out) *steps_out = (int64_t)target + 2LL * overlap;
+    return WRNN_OK;
+}
+
+int wrnn_generate_folded(wrnn_handle *h, const float *mels_dev, int32_t B, int32_t T, const int32_t *frames_dev, int32_t rows_total,
+                         int32_t target, int32_t overlap, const wrnn_sample_opts *opts, int32_t *labels_out_dev,
+                         float *samples_out_dev, void *stream) {
+    if (!h || !frames_dev) return fail(h, WRNN_ERR_INVALID, "wrnn_generate_folded: bad arguments");
+    if (opts && opts->struct_size == sizeof(wrnn_sample_opts) &&
+        (opts->frames_dev || opts->mels_padded || opts->x_forced_dev || opts->x_init_dev || opts->logits_out_dev))
+        return fail(h, WRNN_ERR_INVALID, "wrnn_generate_folded: opts.frames_dev, mels_padded, x_forced_dev, x_init_dev and logits_out_dev must be unset");
+    return generate_impl(h, mels_dev, B, T, 1, target, overlap, opts, labels_out_dev, samples_out_dev, stream, frames_dev, rows_total);
+}
+
 int wrnn_loss(wrnn_handle *h, const float *y_hat_dev, const void *y_dev, int64_t n_rows, float *loss_out_dev, void *stream) {
     if (!h || !y_hat_dev || !y_dev || !loss_out_dev || n_rows < 1) return fail(h, WRNN_ERR_INVALID, "wrnn_loss: bad arguments");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
@@ -725,6 +789,9 @@ int wrnn_last_timing(wrnn_handle *h, wrnn_timing *out) {
     unsigned errw = 0;
     HIP_TRY(h, hipMemcpy(&errw, h->err_dev, sizeof(errw), hipMemcpyDeviceToHost));
     if (out) *out = h->last;
+    if (errw == WRNN_DEVERR_ROWS)
+        return fail(h, WRNN_ERR_INVALID, "wrnn_generate_folded: rows_total differs from the fold count of frames_dev on the device "
+                                         "(wrnn_plan_folded gives it for the same frames, target and overlap)");
     if (errw == WRNN_DEVERR_BUSY)
         return fail(h, WRNN_ERR_BUSY, "the team kernel's workgroups did not all become resident within its start-up wait: the GPU is shared with another "
                                       "kernel (another process?).  Retry, or use WRNN_KERNEL_SIMPLE");

@@ -66,6 +66,39 @@ epilogue_rows_kernel(const float *__restrict__ samples, const int32_t *__restric
     out[(size_t)r * (size_t)out_stride + (size_t)n] = v;
 }
 
+// wrnn_epilogue_folded: utterance b = rows fold0[b] .. fold0[b + 1] - 1, finished with the arithmetic of epilogue_kernel's batched
+// branch (at most two fold contributions added in fold order, :397-403), trimmed to its own (frames[b] - 1) * hop, faded out,
+// zero from there to out_stride.  grid (ceil(out_stride / 256), B)
+__global__ void __launch_bounds__(256)
+epilogue_folded_rows_kernel(const float *__restrict__ samples, const int32_t *__restrict__ labels, const double *__restrict__ dec,
+                            const double *__restrict__ fade_in, const double *__restrict__ fade_out, const double *__restrict__ tail,
+                            const int32_t *__restrict__ fold0, long steps, long target, long overlap, long tail_len,
+                            const int32_t *__restrict__ frames, int hop, double *__restrict__ out, long out_stride) {
+    const long n = (long)blockIdx.x * 256 + threadIdx.x;
+    const int b = blockIdx.y;
+    if (n >= out_stride) return;
+    const long r0 = fold0[b], rows = fold0[b + 1] - r0;
+    const long st = target + overlap;
+    long wl = ((long)frames[b] - 1) * hop;
+    if (wl > rows * st + overlap) wl = rows * st + overlap;   // never past the unfolded length of the rows this utterance has
+    auto val = [&](long r, long p) -> double {
+        const size_t i = (size_t)(r0 + r) * (size_t)steps + (size_t)p;
+        return dec ? dec[labels[i]] : (double)samples[i];   // (:243-248)
+    };
+    double v = 0.0;
+    if (wl >= tail_len && n < wl) {
+        const long i = n / st, p = n - i * st;
+        if (i >= 1 && p < overlap) v = __dadd_rn(v, __dmul_rn(val(i - 1, p + st), fade_out[p]));
+        if (i < rows) {
+            double a = val(i, p);
+            if (p < overlap) a = __dmul_rn(a, fade_in[p]);
+            v = __dadd_rn(v, a);
+        }
+        if (n >= wl - tail_len) v = __dmul_rn(v, tail[n - (wl - tail_len)]);   // (:255-258)
+    }
+    out[(size_t)b * (size_t)out_stride + (size_t)n] = v;
+}
+
 // np.linspace(start, stop, num) in float64: arange(num) * step + start, last element = stop
 #pragma clang fp contract(off)
 void np_linspace(double start, double stop, long num, double *y) {
@@ -179,5 +212,32 @@ extern "C" int wrnn_epilogue(wrnn_handle *h, const float *samples_dev, const int
                        decode ? dec : nullptr, fin, fout, tail, (int)rows, (long)steps, (int)(batched != 0), (long)target, (long)overlap,
                        (long)wave_len, tail_len, wave_out_dev);
     if (hipGetLastError() != hipSuccess) return fail(WRNN_ERR_HIP, "wrnn_epilogue: launch failed");
+    return WRNN_OK;
+}
+
+extern "C" int wrnn_epilogue_folded(wrnn_handle *h, const float *samples_dev, const int32_t *labels_dev, int32_t B, int32_t rows_total,
+                                    int64_t steps, int32_t target, int32_t overlap, int32_t mu_law, const int32_t *frames_dev,
+                                    double *wave_out_dev, int64_t out_stride, void *stream) {
+    if (!h) return WRNN_ERR_INVALID;
+    auto fail = [&](int code, const char *msg) { h->err = msg; return code; };
+    if (!samples_dev || !wave_out_dev || !frames_dev || B < 1 || rows_total < 1 || out_stride < 1)
+        return fail(WRNN_ERR_INVALID, "wrnn_epilogue_folded: null buffer or empty input");
+    if (overlap < 0 || target < 1 || steps != (int64_t)target + 2 * (int64_t)overlap)
+        return fail(WRNN_ERR_INVALID, "wrnn_epilogue_folded: folds must be target + 2*overlap samples long");
+    if (h->fold_B < 1 || !h->fold0_dev) return fail(WRNN_ERR_STATE, "wrnn_epilogue_folded: no wrnn_generate_folded call on this handle");
+    if (h->fold_B != B || h->fold_target != target || h->fold_overlap != overlap || h->fold_rows != rows_total)
+        return fail(WRNN_ERR_STATE, "wrnn_epilogue_folded: B, target, overlap or rows_total differ from the handle's last wrnn_generate_folded call");
+    const WrnnDims &d = h->d;
+    const bool decode = mu_law && d.mode == WRNN_MODE_RAW;   // MOL forces mu_law off (:174)
+    if (decode && !labels_dev) return fail(WRNN_ERR_INVALID, "wrnn_epilogue_folded: mu-law decode needs the labels of the RAW loop");
+    if (hipSetDevice(h->cfg.device) != hipSuccess) return fail(WRNN_ERR_HIP, "wrnn_epilogue_folded: hipSetDevice failed");
+    const long ov = overlap;
+    if (const char *e = epilogue_tables_on_device(h, ov)) return fail(WRNN_ERR_HIP, e);
+    const double *dec = h->epi_tab, *fin = dec + d.NC, *fout = fin + ov, *tail = fout + ov;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(epilogue_folded_rows_kernel, dim3((unsigned)((out_stride + 255) / 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream,
+                       samples_dev, labels_dev, decode ? dec : nullptr, fin, fout, tail, h->fold0_dev, (long)steps, (long)target, (long)overlap,
+                       20L * d.HOP, frames_dev, d.HOP, wave_out_dev, (long)out_stride);
+    if (hipGetLastError() != hipSuccess) return fail(WRNN_ERR_HIP, "wrnn_epilogue_folded: launch failed");
     return WRNN_OK;
 }

@@ -86,7 +86,8 @@ __global__ void __launch_bounds__(SIMPLE_THREADS) loop_simple_kernel(WrnnLoopArg
     for (int64_t t = a.seg0; t < a.seg0 + rw.steps; ++t) {
         // ---- conditioning row for this step: m_t, a_t  (:203-206) ----------
         const int64_t pos = rw.start + t;
-        const bool live = pos < a.total_len;  // fold padding 'after' is zeros (:327-330)
+        // fold padding 'after' is zeros (:327-330); folds of several utterances: past the row's OWN utterance
+        const bool live = a.frames ? pos < (int64_t)a.frames[rw.utt] * HOP && pos < a.total_len : pos < a.total_len;
         const int i = live ? (int)(pos / HOP) : 0;
         const int r = live ? (int)(pos - (int64_t)i * HOP) : 0;
         for (int j = tid; j < F + R; j += SIMPLE_THREADS) {

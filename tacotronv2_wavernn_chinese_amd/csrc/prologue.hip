@@ -233,6 +233,15 @@ hipError_t wrnn_launch_frame_linear(int mode, const float *src, size_t src_bstri
     return hipGetLastError();
 }
 
+// Table index of frame fi of utterance b: fi itself, or T (the zero-input entry) past the utterance's own frames[b] when the
+// call folds several utterances (frames != null; clamped like rows_folded_kernel clamps it)
+__device__ __forceinline__ int own_frame(const int32_t *frames, int b, int fi, int T) {
+    if (!frames) return fi;
+    int nf = frames[b];
+    nf = nf < 1 ? 1 : (nf > T ? T : nf);
+    return fi < nf ? fi : T;
+}
+
 // Team kernel conditioning records: REC[b][fi][j][28], fi in [0, T] (fi == T: zero conditioning, used for
 // fold padding), j = hidden unit.  One record holds everything phase A of unit j needs during frame fi:
 //   [0] CA[fi][j]   [1..3] VA[fi][r,z,n][j]   [4..8] CM[fi+dd][j], dd<5   [9+3dd+g] VM[fi+dd][g][j]   [24..27] pad
@@ -240,12 +249,14 @@ hipError_t wrnn_launch_frame_linear(int mode, const float *src, size_t src_bstri
 // stored 5x redundantly in HBM so that the per-frame LDS refill is one straight 56 KB copy.
 __global__ void __launch_bounds__(256)
 pack_records_kernel(const float *__restrict__ CM, const float *__restrict__ CA, const float *__restrict__ VM,
-                    const float *__restrict__ VA, float *__restrict__ rec, int T, int P) {
-    const int fi = blockIdx.x, b = blockIdx.y;
+                    const float *__restrict__ VA, float *__restrict__ rec, int T, int P, const int32_t *__restrict__ frames) {
+    const int b = blockIdx.y;
     const int TP = T + 2 * P, T1 = T + 1;
     const float *cm = CM + (size_t)b * TP * 512, *ca = CA + (size_t)b * T1 * 512;
     const float *vm = VM + (size_t)b * TP * 1536, *va = VA + (size_t)b * T1 * 1536;
-    float *out = rec + ((size_t)b * T1 + fi) * 512 * 28;
+    float *out = rec + ((size_t)b * T1 + blockIdx.x) * 512 * 28;
+    // folds of several utterances: a frame past this utterance's own end is packed from entry T, i.e. as the zero-input record
+    const int fi = own_frame(frames, b, blockIdx.x, T);
     const bool live = fi < T;
     for (int i = threadIdx.x; i < 512 * 28; i += blockDim.x) {
         const int j = i / 28, f = i - j * 28;
@@ -259,9 +270,9 @@ pack_records_kernel(const float *__restrict__ CM, const float *__restrict__ CA, 
 }
 
 hipError_t wrnn_launch_pack_records(const float *CM, const float *CA, const float *VM, const float *VA, float *rec, int B,
-                                    int T, int P, hipStream_t s) {
+                                    int T, int P, const int32_t *frames, hipStream_t s) {
     (void)hipGetLastError();  // the runtime is shared with PyTorch: drop any stale sticky error of this thread
-    hipLaunchKernelGGL(pack_records_kernel, dim3(T + 1, B), dim3(256), 0, s, CM, CA, VM, VA, rec, T, P);
+    hipLaunchKernelGGL(pack_records_kernel, dim3(T + 1, B), dim3(256), 0, s, CM, CA, VM, VA, rec, T, P, frames);
     return hipGetLastError();
 }
 
@@ -318,13 +329,14 @@ hipError_t wrnn_launch_cond_stream(const float *rec, const float *ktab, const Wr
 __global__ void __launch_bounds__(256)
 pack_records32_kernel(const float *__restrict__ CM, const float *__restrict__ CA, const float *__restrict__ VM,
                       const float *__restrict__ VA, const float *__restrict__ C2, const float *__restrict__ C3,
-                      const float *__restrict__ C4, float *__restrict__ rec, int T, int P) {
-    const int fi = blockIdx.x, b = blockIdx.y;
+                      const float *__restrict__ C4, float *__restrict__ rec, int T, int P, const int32_t *__restrict__ frames) {
+    const int b = blockIdx.y;
     const int TP = T + 2 * P, T1 = T + 1;
     const float *cm = CM + (size_t)b * TP * 512, *ca = CA + (size_t)b * T1 * 512;
     const float *vm = VM + (size_t)b * TP * 1536, *va = VA + (size_t)b * T1 * 1536;
     const float *c2 = C2 + (size_t)b * T1 * 1536, *c3 = C3 + (size_t)b * T1 * 512, *c4 = C4 + (size_t)b * T1 * 512;
-    float *out = rec + ((size_t)b * T1 + fi) * 512 * 32;
+    float *out = rec + ((size_t)b * T1 + blockIdx.x) * 512 * 32;
+    const int fi = own_frame(frames, b, blockIdx.x, T);   // see pack_records_kernel
     const bool live = fi < T;
     for (int i = threadIdx.x; i < 512 * 32; i += blockDim.x) {
         const int j = i >> 5, f = i & 31;
@@ -341,9 +353,32 @@ pack_records32_kernel(const float *__restrict__ CM, const float *__restrict__ CA
 }
 
 hipError_t wrnn_launch_pack_records32(const float *CM, const float *CA, const float *VM, const float *VA, const float *C2,
-                                      const float *C3, const float *C4, float *rec, int B, int T, int P, hipStream_t s) {
+                                      const float *C3, const float *C4, float *rec, int B, int T, int P, const int32_t *frames,
+                                      hipStream_t s) {
     (void)hipGetLastError();
-    hipLaunchKernelGGL(pack_records32_kernel, dim3(T + 1, B), dim3(256), 0, s, CM, CA, VM, VA, C2, C3, C4, rec, T, P);
+    hipLaunchKernelGGL(pack_records32_kernel, dim3(T + 1, B), dim3(256), 0, s, CM, CA, VM, VA, C2, C3, C4, rec, T, P, frames);
+    return hipGetLastError();
+}
+
+// WRNN_KERNEL_TEAM2 reads C2 / C3 / C4 by frame index straight from the tables (its records hold phase A only): for a call that
+// folds several utterances, entries frames[b] <= f < T of utterance b are overwritten with entry T (zero aux in: the bias), so that
+// the kernel's call-wide limit `frame < T` yields zero conditioning from each utterance's own end on.  grid (T, B), block 256.
+__global__ void __launch_bounds__(256)
+mask_frame_tables_kernel(float *__restrict__ C2, float *__restrict__ C3, float *__restrict__ C4, const int32_t *__restrict__ frames, int T) {
+    const int f = blockIdx.x, b = blockIdx.y;
+    if (own_frame(frames, b, f, T) == f) return;
+    const size_t T1 = (size_t)T + 1;
+    float *c2 = C2 + (size_t)b * T1 * 1536, *c3 = C3 + (size_t)b * T1 * 512, *c4 = C4 + (size_t)b * T1 * 512;
+    for (int i = threadIdx.x; i < 1536; i += blockDim.x) c2[(size_t)f * 1536 + i] = c2[(size_t)T * 1536 + i];
+    for (int i = threadIdx.x; i < 512; i += blockDim.x) {
+        c3[(size_t)f * 512 + i] = c3[(size_t)T * 512 + i];
+        c4[(size_t)f * 512 + i] = c4[(size_t)T * 512 + i];
+    }
+}
+
+hipError_t wrnn_launch_mask_frame_tables(float *C2, float *C3, float *C4, const int32_t *frames, int B, int T, hipStream_t s) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(mask_frame_tables_kernel, dim3(T, B), dim3(256), 0, s, C2, C3, C4, frames, T);
     return hipGetLastError();
 }
 
@@ -403,5 +438,76 @@ hipError_t wrnn_launch_rows(WrnnRow *rows, int32_t *order, int32_t *sched, int n
     const int n_slots = (n_rows + n_teams - 1) / n_teams * n_teams;
     hipLaunchKernelGGL(rows_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, s, rows, order, sched, n_rows, n_teams, batched, stride, steps,
                        frames, T, hop);
+    return hipGetLastError();
+}
+
+// Row table of a call that folds SEVERAL utterances with one fold length (wrnn_generate_folded): utterance b is cut like a call
+// on that clip alone cuts it (fold_with_overlap :319-338: n_b folds by the floor-division rule of wrnn_plan, fold i from position
+// i * (target + overlap)) and its folds are rows fold0[b] .. fold0[b + 1] - 1.  One workgroup: fold counts in parallel, a serial
+// prefix over B (a few hundred utterances at most), then one row per thread in a strided loop.  rows_total is the HOST's sum
+// (wrnn_plan_folded; the outputs are sized by it): whatever frames[] holds, only rows [0, rows_total) are written, each with a
+// valid (utt, start) -- a disagreement repeats the last valid row and raises WRNN_DEVERR_ROWS -- and fold0[] is clamped to
+// rows_total, so the epilogue stays inside the outputs too.  order / sched: identity, -1 in the empty slots, as rows_kernel
+// writes them for a uniform batch.
+__global__ void __launch_bounds__(256)
+rows_folded_kernel(WrnnRow *__restrict__ rows, int32_t *__restrict__ order, int32_t *__restrict__ sched, int32_t *fold0,
+                   unsigned *__restrict__ err, const int32_t *__restrict__ frames, int B, int rows_total, int n_teams, long target,
+                   long overlap, int hop, int T) {
+    __shared__ long s_sum;
+    const long stride = target + overlap;
+    for (int b = threadIdx.x; b < B; b += blockDim.x) {
+        int f = frames[b];
+        f = f < 1 ? 1 : (f > T ? T : f);
+        const long total = (long)f * hop;
+        // Python floor division, as wrnn_plan (fatchord_version.py:319-325)
+        const long num = total - overlap;
+        long n = num / stride;
+        if (num % stride != 0 && num < 0) --n;
+        if (total - (n * stride + overlap) != 0) ++n;
+        if (n < 0) n = 0;
+        if (n > rows_total) n = (long)rows_total + 1;   // keeps the prefix far from overflow; still a mismatch
+        fold0[b + 1] = (int32_t)n;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long acc = 0;
+        fold0[0] = 0;
+        for (int b = 0; b < B; ++b) {
+            acc += fold0[b + 1];
+            fold0[b + 1] = (int32_t)(acc < rows_total ? acc : rows_total);
+        }
+        s_sum = acc;
+        if (acc != rows_total) atomicCAS(err, 0u, WRNN_DEVERR_ROWS);
+    }
+    __syncthreads();
+    const long sum = s_sum;
+    const int n_valid = (int)(sum < rows_total ? sum : rows_total);
+    const int n_slots = (rows_total + n_teams - 1) / n_teams * n_teams;
+    for (int r = threadIdx.x; r < n_slots; r += blockDim.x) {
+        if (r >= rows_total) { sched[r] = -1; continue; }
+        WrnnRow w;
+        w.utt = 0; w.steps = (int32_t)(target + 2 * overlap); w.start = 0;
+        if (n_valid > 0) {
+            const int rr = r < n_valid ? r : n_valid - 1;
+            int lo = 0, hi = B - 1;                      // smallest b with fold0[b + 1] > rr
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (fold0[mid + 1] > rr) hi = mid; else lo = mid + 1;
+            }
+            w.utt = lo;
+            w.start = (int64_t)(rr - fold0[lo]) * stride;
+        }
+        rows[r] = w;
+        order[r] = r;
+        sched[r] = r;
+    }
+}
+
+hipError_t wrnn_launch_rows_folded(WrnnRow *rows, int32_t *order, int32_t *sched, int32_t *fold0, unsigned *err, const int32_t *frames,
+                                   int B, int rows_total, int n_teams, long target, long overlap, int hop, int T, hipStream_t s) {
+    (void)hipGetLastError();
+    if (n_teams < 1) n_teams = 1;
+    hipLaunchKernelGGL(rows_folded_kernel, dim3(1), dim3(256), 0, s, rows, order, sched, fold0, err, frames, B, rows_total, n_teams,
+                       target, overlap, hop, T);
     return hipGetLastError();
 }

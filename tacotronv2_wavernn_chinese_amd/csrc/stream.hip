@@ -220,7 +220,7 @@ int wrnn_stream_push(wrnn_stream *st, const float *mels_dev, int32_t n_frames, i
             S_TRY(h, wrnn_launch_frame_linear(0, aux + A, (size_t)Tw * R, R, Tw, w + o.r2_wih_t + (size_t)H * 3 * H, 3 * H, w + o.r2_bih, tC2, (size_t)T1 * 3 * H, T1, A, 3 * H, B, Tw, P, s));
             S_TRY(h, wrnn_launch_frame_linear(0, aux + 2 * A, (size_t)Tw * R, R, Tw, w + o.fc1_t + (size_t)H * FC, FC, w + o.fc1_b, tC3, (size_t)T1 * FC, T1, A, FC, B, Tw, P, s));
             S_TRY(h, wrnn_launch_frame_linear(0, aux + 3 * A, (size_t)Tw * R, R, Tw, w + o.fc2_t + (size_t)FC * FC, FC, w + o.fc2_b, tC4, (size_t)T1 * FC, T1, A, FC, B, Tw, P, s));
-            S_TRY(h, wrnn_launch_pack_records(tCM, tCA, tVM, tVA, tREC, B, Tw, P, s));
+            S_TRY(h, wrnn_launch_pack_records(tCM, tCA, tVM, tVA, tREC, B, Tw, P, nullptr, s));
             // segments as wrnn_generate sizes them (the conditioning chunk of all rows ~64 MB, multiples of 32 steps); every segment
             // start s0 + k * seg lies on a 32-step boundary because s0 does
             int64_t seg = ((int64_t)(64u << 20) / ((int64_t)B * H * 4 * (int64_t)sizeof(float))) & ~(int64_t)31;

@@ -66,6 +66,8 @@ struct WrnnRow {
 // Device error word codes (first come, first kept): 3 = a team kernel's workgroups did not all become resident (WRNN_ERR_BUSY),
 // everything else = a bounded exchange spin gave up (WRNN_ERR_TIMEOUT)
 #define WRNN_DEVERR_BUSY 3u
+// rows_folded_kernel: the fold count computed on the device differs from the call's rows_total (WRNN_ERR_INVALID)
+#define WRNN_DEVERR_ROWS 4u
 // polls a workgroup waits at the start of a team kernel for the other 31 of its XCD (~1.5 ms; a resident launch needs ~10 us)
 #define WRNN_ARRIVE_POLLS 200000u
 
@@ -86,6 +88,11 @@ struct wrnn_handle {
     int32_t *order_dev = nullptr; // [rows] rows by length, longest first, in a ragged batch; identity otherwise (BATCH kernel)
     int32_t *sched_dev = nullptr; // [rows rounded up to n_teams] per-team row lists of the TEAM2 kernel (see WrnnTeamArgs)
     size_t rows_cap = 0;
+    // wrnn_generate_folded: first row of every utterance, [B + 1], written by rows_folded_kernel and read by wrnn_epilogue_folded;
+    // fold_B > 0 once such a call ran: its B, target, overlap, rows_total
+    int32_t *fold0_dev = nullptr;
+    size_t fold0_cap = 0;
+    int32_t fold_B = 0, fold_target = 0, fold_overlap = 0, fold_rows = 0;
     unsigned *err_dev = nullptr;  // device error word (bounded spins)
     // team kernel state
     float *team_w = nullptr, *team_fc3 = nullptr, *wI0 = nullptr, *u1 = nullptr;
@@ -147,6 +154,8 @@ struct WrnnLoopArgs {
     // state[row * wrnn_simple_state_floats]: [h1 H | h2 H | x 1 | pad].  Offline calls: 0, null.
     int64_t seg0;
     float *state;
+    // folds of several utterances (wrnn_generate_folded), B int32 or null: utterance u ends at frames[u] * HOP instead of total_len
+    const int32_t *frames;
 };
 __host__ __device__ inline int wrnn_simple_state_floats(const WrnnDims &d) { return 2 * d.H + 4; }
 
@@ -293,13 +302,21 @@ hipError_t wrnn_launch_loss(int mode, const float *y_hat, const void *y, int NC,
 // sched[] (n_rows rounded up to n_teams entries) = the same order dealt to n_teams teams in snake order, -1 where empty
 hipError_t wrnn_launch_rows(WrnnRow *rows, int32_t *order, int32_t *sched, int n_rows, int n_teams, int batched, long stride, long steps,
                             const int32_t *frames, int T, int hop, hipStream_t s);
+// frames (B int32, device) or null: records fi >= frames[b] of utterance b are written as copies of record T (zero conditioning)
 hipError_t wrnn_launch_pack_records32(const float *CM, const float *CA, const float *VM, const float *VA, const float *C2,
-                                      const float *C3, const float *C4, float *rec, int B, int T, int P, hipStream_t s);
+                                      const float *C3, const float *C4, float *rec, int B, int T, int P, const int32_t *frames,
+                                      hipStream_t s);
+// folds of several utterances: rows[fold0[b] + i] = {b, steps, i * stride}, identity order / sched, fold0[B + 1] (clamped to
+// rows_total); a fold count that differs from rows_total sets *err = WRNN_DEVERR_ROWS and touches no row outside [0, rows_total)
+hipError_t wrnn_launch_rows_folded(WrnnRow *rows, int32_t *order, int32_t *sched, int32_t *fold0, unsigned *err, const int32_t *frames,
+                                   int B, int rows_total, int n_teams, long target, long overlap, int hop, int T, hipStream_t s);
+// TEAM2 reads C2 / C3 / C4 (B, T + 1, .) by frame: entries frames[b] <= f < T of utterance b become copies of entry T
+hipError_t wrnn_launch_mask_frame_tables(float *C2, float *C3, float *C4, const int32_t *frames, int B, int T, hipStream_t s);
 hipError_t wrnn_launch_loop_team2(const WrnnTeamArgs &a, hipStream_t s);
 hipError_t wrnn_launch_cond_stream(const float *rec, const float *ktab, const WrnnRow *rows, float *cond, int n_rows, int T,
                                    int HOP, long total_len, long seg0, long seg_len, hipStream_t s);
 hipError_t wrnn_launch_pack_records(const float *CM, const float *CA, const float *VM, const float *VA, float *rec, int B,
-                                    int T, int P, hipStream_t s);
+                                    int T, int P, const int32_t *frames, hipStream_t s);
 // out[b][f][n] = bias[n] + sum_k in(b,f,k) * Wt[k*ldw + n]; mode 0: row-major src (rows >= valid read as 0),
 // mode 1: src = mels (B,F,T) read as zero-padded frames melpad[f] = mel[:, f - P]
 hipError_t wrnn_launch_frame_linear(int mode, const float *src, size_t src_bstride, int ld, int valid, const float *Wt,

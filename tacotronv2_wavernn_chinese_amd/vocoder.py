@@ -120,6 +120,31 @@ def fold_plan(total_len: int, overlap: int, n_teams: int = 8, mode: str = 'RAW',
     return best
 
 
+def fold_plan_many(total_lens, overlap: int, n_teams: int = 8, mode: str = 'RAW', min_target: int = 0):
+    """``fold_plan`` for a call that folds SEVERAL utterances with one common ``target`` (``generate_many(batched=True, target='auto')``):
+    minimises ``predicted_loop_us(sum_b fold_count(len_b, target, overlap), target + 2 x overlap, ...)`` over the candidates
+    ``fold_target(len_b, overlap, n)`` of every utterance b and every n <= 2 x 8 x teams -- the targets at which some utterance's fold count
+    changes.  Ties go to the larger target (fewer crossfades).  ``min_target`` as in ``fold_plan``; the plan that leaves every utterance in
+    one fold is always admissible.  Returns (target, rows, predicted_us); for one utterance this is ``fold_plan``'s result."""
+    lens = [int(t) for t in total_lens]
+    if not lens:
+        raise ValueError('fold_plan_many needs at least one utterance')
+    teams = max(int(n_teams), 1)
+    one_fold = fold_target(max(lens), overlap, 1)
+    cands = {fold_target(t, overlap, n) for t in lens for n in range(1, 2 * ROWS_PER_TEAM_MAX * teams + 1)}
+    best = None
+    for target in sorted(cands, reverse=True):
+        counts = [fold_count(t, target, overlap) for t in lens]
+        if min(counts) < 1 or (target < min_target and target != one_fold):
+            continue
+        cost = predicted_loop_us(sum(counts), target + 2 * overlap, teams, mode)
+        if best is None or cost < best[2] * (1.0 - 1e-9):
+            best = (target, sum(counts), cost)
+    if best is None:
+        raise ValueError(f'no fold plan for {lens} samples with overlap {overlap}')
+    return best
+
+
 _CU_COUNT = {}   # torch.cuda.get_device_properties costs ~0.1 s on its first call (amdsmi): asked once per device
 
 
@@ -473,26 +498,86 @@ class WaveRNN(nn.Module):
                              kernel=k, x_init_ptr=xi, mels_padded=mels_padded,
                              frames_ptr=fr, batch_rows=batch_rows, team2_segment=team2_segment)
                 return nat.last_timing()  # synchronises; surfaces device-side errors
-            try:
-                self.last_timing = launch(want_kernel)
-            except _cabi.WrnnError as e:
-                # WRNN_ERR_BUSY: a team kernel's 32 workgroups per XCD did not all become resident (another process holds CUs).  An explicit
-                # kernel request fails as it is; AUTO retries once after a moment, then runs the any-shape kernel -- loudly.
-                if e.code != _cabi.ERR_BUSY or want_kernel != _cabi.KERNEL_AUTO:
-                    raise
-                time.sleep(self.busy_retry_seconds)
-                try:
-                    self.last_timing = launch(_cabi.KERNEL_AUTO)
-                except _cabi.WrnnError as e2:
-                    if e2.code != _cabi.ERR_BUSY:
-                        raise
-                    self._warn_slow_path(f'the GPU is shared with another kernel ({e2})', steps)
-                    self.last_timing = launch(_cabi.KERNEL_SIMPLE)
-            if want_kernel == _cabi.KERNEL_AUTO and self.last_timing['kernel'] == _cabi.KERNEL_SIMPLE and not getattr(self, '_slow_warned', False):
-                self._warn_slow_path(nat.team_info()[2] or 'the team kernels cannot run on this device', steps)
+            self._launch_with_busy_retry(nat, launch, want_kernel, steps)
             frames_dev = keep[0] if ragged else None
             del keep
         return dict(samples=samples, labels=labels, logits=logits, rows=rows, steps=steps, frames=frames_dev)
+
+    def _launch_with_busy_retry(self, nat, launch, want_kernel, steps):
+        """``self.last_timing = launch(kernel)`` with the policy for a busy GPU."""
+        try:
+            self.last_timing = launch(want_kernel)
+        except _cabi.WrnnError as e:
+            # WRNN_ERR_BUSY: a team kernel's 32 workgroups per XCD did not all become resident (another process holds CUs).  An explicit
+            # kernel request fails as it is; AUTO retries once after a moment, then runs the any-shape kernel -- loudly.
+            if e.code != _cabi.ERR_BUSY or want_kernel != _cabi.KERNEL_AUTO:
+                raise
+            time.sleep(self.busy_retry_seconds)
+            try:
+                self.last_timing = launch(_cabi.KERNEL_AUTO)
+            except _cabi.WrnnError as e2:
+                if e2.code != _cabi.ERR_BUSY:
+                    raise
+                self._warn_slow_path(f'the GPU is shared with another kernel ({e2})', steps)
+                self.last_timing = launch(_cabi.KERNEL_SIMPLE)
+        if want_kernel == _cabi.KERNEL_AUTO and self.last_timing['kernel'] == _cabi.KERNEL_SIMPLE and not getattr(self, '_slow_warned', False):
+            self._warn_slow_path(nat.team_info()[2] or 'the team kernels cannot run on this device', steps)
+
+    def generate_raw_folded(self, mels, frames, target, overlap, *, noise_mode=_cabi.NOISE_PHILOX, seed=0, noise1=None, noise2=None,
+                            kernel=None, batch_rows=0, team2_segment=0, rows_total=None):
+        """Device part of ``generate_many(batched=True)``: ONE ``wrnn_generate_folded`` call whose rows are the folds of ALL utterances.
+        mels (B, n_mels, T), every clip right-zero-padded to T frames; frames (B,) the clips' own frame counts.  Utterance b is cut as
+        ``generate_raw(mels[b:b+1, :, :frames[b]], True, target, overlap)`` cuts it and owns rows fold0[b] .. fold0[b + 1] - 1.  Returns
+        dict(samples, labels (rows, steps) cuda tensors, fold0 (B + 1,) int32 numpy, rows, steps, frames (cuda int32), B, target, overlap).
+        noise1 / noise2 (injected): (steps, rows, .) over ALL rows; the Philox draws of a row are keyed by its GLOBAL row index
+        fold0[b] + i, so a clip's audio depends on its position in the call.  rows_total: test hook, overrides the planned row count."""
+        if isinstance(noise_mode, str):
+            if noise_mode not in _NOISE_MODES:
+                raise ValueError(f'noise_mode must be one of {sorted(_NOISE_MODES)} or a WRNN_NOISE_* id, got {noise_mode!r}')
+            noise_mode = _NOISE_MODES[noise_mode]
+        if noise_mode == _NOISE_REFERENCE:
+            raise ValueError("noise_mode='reference' replays the reference's own generate(): it has no call that folds several utterances")
+        fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+        nat = self.native()
+        dev = torch.device('cuda', nat.device)
+        with torch.cuda.device(dev):
+            mels_t = torch.as_tensor(mels).to(device=dev, dtype=torch.float32).contiguous()
+            if mels_t.dim() != 3 or mels_t.size(1) != self.feat_dims:
+                raise ValueError(f'expected mels shaped (B, {self.feat_dims}, T), got {tuple(mels_t.shape)}')
+            B, _, T = mels_t.shape
+            if fr.shape != (B,) or fr.min() < 1 or fr.max() > T:
+                raise ValueError(f'frames must be ({B},) integers in [1, {T}], got {fr.tolist()}')
+            fold0, steps = _cabi.plan_folded(fr, self.hop_length, target, overlap)
+            rows = int(fold0[-1]) if rows_total is None else int(rows_total)
+            samples = torch.empty((rows, steps), dtype=torch.float32, device=dev)
+            labels = torch.empty((rows, steps), dtype=torch.int32, device=dev)
+            fr_t = torch.from_numpy(fr).to(dev)
+            keep = []
+
+            def to_dev(a, shape):
+                if a is None:
+                    return 0
+                t = torch.as_tensor(a).to(device=dev, dtype=torch.float32).contiguous()
+                if tuple(t.shape) != shape:
+                    raise ValueError(f'expected shape {shape}, got {tuple(t.shape)}')
+                keep.append(t)
+                return t.data_ptr()
+            nmix = self.n_classes if self.mode == 'RAW' else self.n_classes // 3
+            n1 = to_dev(noise1, (steps, rows, nmix))
+            n2 = to_dev(noise2, (steps, rows))
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            want_kernel = self.kernel if kernel is None else kernel
+            if isinstance(want_kernel, str):
+                want_kernel = _cabi.KERNEL_IDS[want_kernel]
+
+            def launch(k):
+                nat.generate_folded(mels_t.data_ptr(), B, T, fr_t.data_ptr(), rows, target, overlap, labels_ptr=labels.data_ptr(),
+                                    samples_ptr=samples.data_ptr(), stream=stream, noise_mode=noise_mode, seed=int(seed), noise1_ptr=n1,
+                                    noise2_ptr=n2, kernel=k, batch_rows=batch_rows, team2_segment=team2_segment)
+                return nat.last_timing()  # synchronises; surfaces device-side errors
+            self._launch_with_busy_retry(nat, launch, want_kernel, steps)
+            del keep
+        return dict(samples=samples, labels=labels, fold0=fold0, rows=rows, steps=steps, frames=fr_t, B=B, target=int(target), overlap=int(overlap))
 
     def _warn_slow_path(self, why: str, steps: int):
         """Once per model: AUTO is running ``WRNN_KERNEL_SIMPLE`` (one workgroup per row, weights streamed every step, ~1 ms per step:
@@ -585,7 +670,7 @@ class WaveRNN(nn.Module):
         self.train()
         return output
 
-    def generate_many(self, mels_list, save_paths=None, mu_law=True, epilogue='host', **native_opts):
+    def generate_many(self, mels_list, save_paths=None, mu_law=True, epilogue='host', batched=False, target='auto', overlap=550, **native_opts):
         """Extension for serving loops: several independent utterances of different lengths in ONE device call, so that all
         8 XCD teams of the GPU work (a single unbatched utterance keeps one team = 1/8 of the chip busy; up to 8 utterances
         run on the latency kernel one per team, more on the batch kernel).  ``mels_list``: sequence of (n_mels, T_i) arrays.
@@ -595,7 +680,19 @@ class WaveRNN(nn.Module):
         the longest one's.  The first T_i * hop samples of row i are what a single ``generate`` call on clip i computes for the
         same noise.  Returns a list of float64 arrays, each what ``generate(mels_i[None], path_i, False, ...)`` returns
         ((T_i - 1) * hop samples, mu-law decoded, 20-hop fade-out); writes the wavs when ``save_paths`` is given.
-        ``epilogue='device'``: decode / trim / fade-out of all rows in one ``wrnn_epilogue_rows`` launch."""
+        ``epilogue='device'``: decode / trim / fade-out of all rows in one ``wrnn_epilogue_rows`` launch.
+
+        ``batched=True``: the reference's fold mode (:293-405) for ALL clips in one ``wrnn_generate_folded`` call -- every clip is cut into
+        folds of one common ``target`` (an int, or ``'auto'``: ``fold_plan_many``, the target with the lowest predicted loop time for the
+        whole queue) and every fold of every clip is one row of the batch kernel, so that short clips fill the chip together.  Element i
+        is what ``generate(mels_i[None], path_i, True, target, overlap, mu_law)`` returns in shape, dtype and length; the noise of a fold is
+        keyed by its row index in the call, so the audio of a clip depends on its position in ``mels_list`` (for one clip: bit-equal to
+        ``generate`` with the same seed).  ``epilogue='device'``: crossfade / unfold / trim / fade-out of all clips in one
+        ``wrnn_epilogue_folded`` launch.  ``noise_mode='reference'`` raises ``ValueError``: the reference has no such call."""
+        if batched and native_opts.get('noise_mode') in ('reference', _NOISE_REFERENCE):
+            raise ValueError("noise_mode='reference' replays the reference's own generate(): it has no call that folds several utterances")
+        if batched and epilogue not in ('host', 'device'):
+            raise ValueError(f"epilogue must be 'host' or 'device', got {epilogue!r}")
         self.eval()
         mu_law = mu_law if self.mode == 'RAW' else False
         arrs = [np.asarray(torch.as_tensor(m).detach().cpu().numpy(), dtype=np.float32) for m in mels_list]
@@ -613,6 +710,13 @@ class WaveRNN(nn.Module):
         if 'seed' not in native_opts and native_opts.get('noise_mode', _cabi.NOISE_PHILOX) in (_cabi.NOISE_PHILOX, 'philox'):
             native_opts['seed'] = int(torch.randint(0, 2 ** 62, (1,)).item())
         ragged = len(set(lens)) > 1
+        if batched:
+            outs = self._generate_many_folded(batch, lens, mu_law, epilogue, target, overlap, native_opts)
+            if save_paths is not None:
+                for out, path in zip(outs, save_paths):
+                    save_wav(out, path, self.sample_rate)
+            self.train()
+            return outs
         res = self.generate_raw(batch, False, 11000, 550, frames=np.asarray(lens, np.int32) if ragged else None, **native_opts)
         if epilogue == 'device':
             nat = self.native()
@@ -642,6 +746,38 @@ class WaveRNN(nn.Module):
             for out, path in zip(outs, save_paths):
                 save_wav(out, path, self.sample_rate)
         self.train()
+        return outs
+
+    def _generate_many_folded(self, batch, lens, mu_law, epilogue, target, overlap, native_opts):
+        """``generate_many(batched=True)`` behind the argument checks: batch (B, n_mels, max T) zero-padded, lens the clips' frames."""
+        hop = self.hop_length
+        if isinstance(target, str):
+            if target != 'auto':
+                raise ValueError(f"target must be an int or 'auto', got {target!r}")
+            target = fold_plan_many([t * hop for t in lens], int(overlap), _device_teams(next(self.parameters()).device), self.mode,
+                                    int(self.fold_min_target))[0]
+        res = self.generate_raw_folded(batch, lens, int(target), int(overlap), **native_opts)
+        fold0 = res['fold0']
+        if epilogue == 'device':
+            nat = self.native()
+            dev = res['samples'].device
+            wl_max = (max(lens) - 1) * hop
+            with torch.cuda.device(dev):
+                waves = torch.empty((len(lens), wl_max), dtype=torch.float64, device=dev)
+                nat.epilogue_folded(res['samples'].data_ptr(), res['labels'].data_ptr(), len(lens), res['rows'], res['steps'], res['target'],
+                                    res['overlap'], mu_law, res['frames'].data_ptr(), waves.data_ptr(), wl_max,
+                                    torch.cuda.current_stream(dev).cuda_stream)
+            waves = waves.cpu().numpy()
+            return [waves[i, :(t_i - 1) * hop].copy() for i, t_i in enumerate(lens)]
+        samples = res['samples'].cpu().numpy().astype(np.float64)   # (rows, steps)   :243-245
+        outs = []
+        for i, t_i in enumerate(lens):
+            out = samples[fold0[i]:fold0[i + 1]]
+            if mu_law:
+                out = decode_mu_law(out, self.n_classes, False)
+            out = self.xfade_and_unfold(np.ascontiguousarray(out), res['target'], res['overlap'])[:(t_i - 1) * hop]
+            out[-20 * hop:] *= np.linspace(1, 0, 20 * hop)
+            outs.append(out)
         return outs
 
     def stream(self, batch=1, mu_law=True, seed=None, noise_mode='philox', kernel=None, tail='reference', raw=False,
