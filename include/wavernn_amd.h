@@ -390,7 +390,8 @@ void wrnn_destroy(wrnn_handle *h);
  * reference script imports it).  Entry points mirror WaveRNN(hidden_size, quantisation) :9-31, load_state_dict and
  * generate(seq_len) :75-165.  noise_dev (WRNN_NOISE_INJECTED): Exp(1) draws (seq_len, 2, quantisation), [t][0] for the
  * coarse Categorical.sample() (:131), [t][1] for the fine one (:151).  Outputs: int32 (seq_len,) each; the signal is
- * coarse * 256 + fine - 2**15 (wavernn/utils/dsp.py:33-34), combined on the host side of the binding. */
+ * coarse * 256 + fine - 2**15 (wavernn/utils/dsp.py:33-34), combined on the host side of the binding.  seq_len == 0 is
+ * a successful no-op whose buffer pointers may be null. */
 typedef struct wrnn_dm_handle wrnn_dm_handle;
 int wrnn_dm_create(int32_t hidden_size, int32_t quantisation, int32_t device, wrnn_dm_handle **out);
 int wrnn_dm_load_weights(wrnn_dm_handle *h, const wrnn_tensor_desc *tensors, int32_t n);

@@ -2,7 +2,10 @@
 
 Run in the build container only (needs /root/reference):
 
-    PYTHONDONTWRITEBYTECODE=1 python -m oracle.make_golden [long | forward | train | dm | module]
+    PYTHONDONTWRITEBYTECODE=1 python -m oracle.make_golden [short | long | forward | train | dm | module] [NAME ...]
+
+Names after the kind (short, long and dm only) restrict the run to those cases, so that adding a case
+leaves the committed fixtures of the others byte for byte as they are (an .npz carries the time it was written).
 
 Every fixture stores only seeds + the reference's outputs: weights, mels and
 the sampling noise are rebuilt from the seeds on whatever box replays them
@@ -28,6 +31,8 @@ CASES = [
     dict(name='raw_default_b1_t24', mode='RAW', bits=10, variant='default', B=1, T=24, batched=False),
     dict(name='raw_peaky_b1_t24', mode='RAW', bits=10, variant='peaky', B=1, T=24, batched=False),
     dict(name='raw_peaky_b3_t21', mode='RAW', bits=10, variant='peaky', B=3, T=21, batched=False),
+    # 8-bit mu-law, 256 classes: on the team kernels only workgroups 0..7 own classes
+    dict(name='raw_peaky8_b2_t21', mode='RAW', bits=8, variant='peaky', B=2, T=21, batched=False),
     dict(name='raw_peaky_fold_t30', mode='RAW', bits=10, variant='peaky', B=1, T=30, batched=True,
          target=2000, overlap=200),
     dict(name='mol_default_b1_t24', mode='MOL', bits=9, variant='default', B=1, T=24, batched=False),
@@ -55,7 +60,10 @@ TRAIN_CASES = [
     dict(name='train_mol_default_b4_t5', mode='MOL', bits=9, variant='default', B=4, T=5),
 ]
 # The secondary dual-softmax model (`python -m oracle.make_golden dm`): SURVEY.md 8a A12, deepmind_version.py:75-165
-DM_CASES = [dict(name='dm_h896_s2000', hidden=896, steps=2000)]
+# A fixture without `hidden` / `quant` entries (the first one) is hidden 896, quantisation 256.
+DM_CASES = [dict(name='dm_h896_s2000', hidden=896, quant=256, steps=2000),
+            dict(name='dm_h512_s1000', hidden=512, quant=256, steps=1000),
+            dict(name='dm_h640_q128_s1000', hidden=640, quant=128, steps=1000)]   # the reference's generate() runs at any quantisation
 TRAIN_GRAD_SAMPLES = 257
 WEIGHT_SEED, MEL_SEED, NOISE_SEED = 0, 1234, 42
 
@@ -214,7 +222,7 @@ def mint_forward():
         print(f"{c['name']}: logits {out['logits'].shape} loss {out['loss']:.6f} loss_sub {loss_sub:.6f} -> {os.path.getsize(path) / 1024:.0f} KiB")
 
 
-def mint_dm():
+def mint_dm(only=()):
     """deepmind_version.WaveRNN.generate(seq_len) of the unmodified reference on seeded weights: the 16-bit output and the
     coarse / fine class indices of every step.  Stored with the seeds only; tests/test_deepmind.py replays the Exp(1) draws
     (oracle.noise.dm_noise_from_seed) and checks them against the checksum kept here."""
@@ -222,11 +230,13 @@ def mint_dm():
     from oracle.noise import dm_noise_from_seed
     from tacotronv2_wavernn_chinese_amd.synth import make_dm_state_dict
     for c in DM_CASES:
-        sd = make_dm_state_dict(WEIGHT_SEED, hidden_size=c['hidden'])
+        if only and c['name'] not in only:
+            continue
+        sd = make_dm_state_dict(WEIGHT_SEED, hidden_size=c['hidden'], quantisation=c['quant'])
         out = rh.reference_dm_generate(sd, c['steps'], NOISE_SEED)
-        q = dm_noise_from_seed(NOISE_SEED, c['steps'])
+        q = dm_noise_from_seed(NOISE_SEED, c['steps'], c['quant'])
         path = os.path.join(GOLDEN_DIR, c['name'] + '.npz')
-        np.savez_compressed(path, weight_seed=WEIGHT_SEED, noise_seed=NOISE_SEED, steps=c['steps'],
+        np.savez_compressed(path, weight_seed=WEIGHT_SEED, noise_seed=NOISE_SEED, steps=c['steps'], hidden=c['hidden'], quant=c['quant'],
                             coarse=out['coarse'].astype(np.int16), fine=out['fine'].astype(np.int16), output=out['output'].astype(np.int32),
                             noise_checksum=noise_checksum({'q': q}))
         print(f"{c['name']}: {c['steps']} steps -> {os.path.getsize(path) / 1024:.0f} KiB")
@@ -235,8 +245,9 @@ def mint_dm():
 def main() -> int:
     from oracle import ref_harness as rh
     os.makedirs(GOLDEN_DIR, exist_ok=True)
+    only = set(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == 'dm':
-        mint_dm()
+        mint_dm(only)
         return 0
     if len(sys.argv) > 1 and sys.argv[1] == 'forward':
         mint_forward()
@@ -249,6 +260,8 @@ def main() -> int:
         return 0
     cases = LONG_CASES if (len(sys.argv) > 1 and sys.argv[1] == 'long') else CASES
     for c in cases:
+        if only and c['name'] not in only:
+            continue
         sd = make_state_dict(WEIGHT_SEED, mode=c['mode'], variant=c['variant'], bits=c['bits'])
         model = rh.build_reference_model(sd, mode=c['mode'], bits=c['bits'])
         mels = make_mels(MEL_SEED, c['B'], c['T'])
@@ -257,7 +270,7 @@ def main() -> int:
                                     overlap=overlap, mu_law=True)
         key = 'labels' if c['mode'] == 'RAW' else 'samples'
         L, rows = out[key].shape
-        noise = rh.replay_noise(NOISE_SEED, c['mode'], L, rows, n_classes=1024)
+        noise = rh.replay_noise(NOISE_SEED, c['mode'], L, rows, n_classes=2 ** c['bits'])   # RAW: one draw per class; MOL ignores it
         up, aux = rh.reference_upsample(model, mels)
         fix = dict(
             mode=c['mode'], bits=c['bits'], variant=c['variant'], B=c['B'], T=c['T'],

@@ -276,11 +276,12 @@ int wrnn_dm_set_kernel(wrnn_dm_handle *h, int32_t kernel) {
 
 int wrnn_dm_generate(wrnn_dm_handle *h, int64_t seq_len, int32_t noise_mode, uint64_t seed, const float *noise_dev,
                      int32_t *coarse_out_dev, int32_t *fine_out_dev, void *stream) {
-    if (!h || seq_len < 0 || !coarse_out_dev || !fine_out_dev) return dm_fail(h, WRNN_ERR_INVALID, "wrnn_dm_generate: bad arguments");
+    if (!h || seq_len < 0) return dm_fail(h, WRNN_ERR_INVALID, "wrnn_dm_generate: bad arguments");
     if (!h->loaded) return dm_fail(h, WRNN_ERR_STATE, "weights not loaded");
-    if (noise_mode == WRNN_NOISE_INJECTED && !noise_dev) return dm_fail(h, WRNN_ERR_INVALID, "WRNN_NOISE_INJECTED needs a noise pointer");
     if (noise_mode < 0 || noise_mode > 2) return dm_fail(h, WRNN_ERR_INVALID, "bad noise_mode");
-    if (seq_len == 0) return WRNN_OK;
+    if (seq_len == 0) return WRNN_OK;   // nothing to write or to draw: an allocator hands out null for the empty buffers of such a call
+    if (!coarse_out_dev || !fine_out_dev) return dm_fail(h, WRNN_ERR_INVALID, "wrnn_dm_generate: bad arguments");
+    if (noise_mode == WRNN_NOISE_INJECTED && !noise_dev) return dm_fail(h, WRNN_ERR_INVALID, "WRNN_NOISE_INJECTED needs a noise pointer");
     DM_TRY(h, hipSetDevice(h->device));
     WrnnDmArgs a = h->args;
     a.w = h->wdev; a.H = h->H; a.Q = h->Q; a.seq_len = seq_len; a.noise_mode = noise_mode; a.seed = seed; a.noise = noise_dev;

@@ -30,7 +30,7 @@ def load_case(name: str) -> dict:
     fx['mels'] = make_mels(int(fx['mel_seed']), int(fx['B']), int(fx['T']))
     key = 'labels' if fx['mode'] == 'RAW' else 'samples'
     L, rows = fx[key].shape
-    noise = noise_from_seed(int(fx['noise_seed']), fx['mode'], L, rows)
+    noise = noise_from_seed(int(fx['noise_seed']), fx['mode'], L, rows, n_classes=2 ** int(fx['bits']))   # RAW: a draw per class
     if not np.allclose(noise_checksum(noise), fx['noise_checksum'], rtol=0, atol=0):
         pytest.skip('torch CPU RNG stream differs from the one the goldens were minted with')
     fx['noise'] = noise

@@ -8,20 +8,32 @@ from oracle import oracle as orc
 from oracle.noise import dm_noise_from_seed, noise_checksum
 from tacotronv2_wavernn_chinese_amd.synth import make_dm_state_dict
 
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'dm_h896_s2000.npz')
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+DM_GOLDENS = sorted(f[:-4] for f in os.listdir(GOLDEN_DIR) if f.startswith('dm_') and f.endswith('.npz'))
 
 
-def _golden():
-    z = np.load(GOLD)
+def _golden(name='dm_h896_s2000'):
+    z = np.load(os.path.join(GOLDEN_DIR, name + '.npz'))
     steps = int(z['steps'])
-    q = dm_noise_from_seed(int(z['noise_seed']), steps)
+    # the first fixture carries no sizes: hidden 896, quantisation 256 (oracle/make_golden.py DM_CASES)
+    hidden, quant = (int(z['hidden']), int(z['quant'])) if 'hidden' in z.files else (896, 256)
+    q = dm_noise_from_seed(int(z['noise_seed']), steps, quant)
     if not np.array_equal(noise_checksum({'q': q}), z['noise_checksum']):
         pytest.skip('torch CPU RNG stream differs from the one the goldens were minted with')
-    return z, steps, q, make_dm_state_dict(int(z['weight_seed']))
+    return z, steps, q, make_dm_state_dict(int(z['weight_seed']), hidden_size=hidden, quantisation=quant)
 
 
-def test_oracle_matches_reference_golden():
-    z, steps, q, sd = _golden()
+def test_dm_goldens_cover_a_second_hidden_size_and_a_smaller_quantisation():
+    assert {'dm_h896_s2000', 'dm_h512_s1000', 'dm_h640_q128_s1000'} <= set(DM_GOLDENS)
+
+
+@pytest.mark.parametrize('name', DM_GOLDENS)
+def test_oracle_matches_reference_golden(name):
+    """The C restatement against generate() of the unmodified reference, which runs at any quantisation: hidden 896 and 512
+    at 256 classes, hidden 640 (the odd plane count of the team kernel) at 128.  Every other size of the GPU size sweep
+    (tests/test_gpu_dm_sizes.py) rests on the oracle alone: the same code with other loop bounds."""
+    z, steps, q, sd = _golden(name)
+    assert q.shape == (steps, 2, sd['O2.weight'].shape[0])
     r = orc.DeepmindOracle(sd).generate(steps, q)
     np.testing.assert_array_equal(r['coarse'], z['coarse'].astype(np.int32))
     np.testing.assert_array_equal(r['fine'], z['fine'].astype(np.int32))

@@ -366,6 +366,46 @@ def test_raw_9bit_has_no_phantom_classes(kernel):
     assert label_stats(got, ref['labels'], first)['max_abs'] <= 1
 
 
+@pytest.mark.parametrize('kernel', ['team2', 'batch', 'batch_cs', 'simple'])
+@pytest.mark.parametrize('bits', [8, 5, 1])
+def test_raw_small_class_counts_match_oracle_at_every_step(bits, kernel):
+    """RAW at 256, 32 and 2 classes: on the team kernels workgroups 8..31, workgroups 1..31, and all but one quarter-wave
+    own no class (at 2 classes the second class slot `cls0 + 4` of the batch kernels is never valid).  Teacher-forced on
+    the oracle's own samples and free-running, the labels equal the oracle's at EVERY step: the fixtures keep the oracle's
+    race margin >= 1e-4 over the run (tests/size_fixtures.py, asserted by tests/test_size_fixtures_host.py), so there is no
+    near-tie to allow for.  Two rows on team2 / simple; five on the batch kernels, so that a row quad is partly filled."""
+    from tacotronv2_wavernn_chinese_amd import _cabi
+    from tests.size_fixtures import raw_fixture, raw_rows
+    B = raw_rows(kernel)
+    fx = raw_fixture(bits, B)
+    NC, free, forced = fx['n_classes'], fx['free'], fx['forced']
+    m = _model(fx['state_dict'], bits=bits, kernel=kernel)
+    assert m.n_classes == NC
+    noise = dict(noise_mode=_cabi.NOISE_INJECTED, noise1=np.array(fx['q']))
+    # teacher-forced on the oracle's samples, with logits
+    res = m.generate_raw(fx['mels'], False, 11000, 550, x_forced=np.array(free['samples']), want_logits=True, **noise)
+    got, smp, lg = res['labels'].cpu().numpy().T, res['samples'].cpu().numpy().T, res['logits'].cpu().numpy()
+    scale = max(1.0, float(np.abs(forced['logits']).max()))
+    err = float(np.abs(lg - forced['logits']).max()) if lg.shape == forced['logits'].shape else float('nan')
+    parity_report(f'RAW {NC} classes {kernel} teacher-forced: {got.size} steps compared, label mismatches '
+                  f'{int(np.count_nonzero(got != forced["labels"]))}, max label {int(got.max())}, max logit error {err:.3e} '
+                  f'(bound {2e-5 * scale:.3e}), oracle min margin {fx["min_margin"]:.2e}')
+    assert got.shape == (fx['L'], B) and lg.shape == (fx['L'], B, NC)
+    assert got.min() >= 0 and got.max() < NC
+    np.testing.assert_array_equal(got, forced['labels'])
+    assert err <= 2e-5 * scale
+    np.testing.assert_array_equal(smp, 2.0 * got.astype(np.float32) / np.float32(NC - 1.0) - np.float32(1.0))
+    # free-running
+    res = m.generate_raw(fx['mels'], False, 11000, 550, **noise)
+    got, smp = res['labels'].cpu().numpy().T, res['samples'].cpu().numpy().T
+    bad = np.argwhere(got != free['labels'])
+    parity_report(f'RAW {NC} classes {kernel} free-running: {got.size} steps compared, label mismatches {len(bad)} '
+                  f'(first at {bad[0].tolist() if len(bad) else None}), oracle min margin {fx["min_margin"]:.2e}')
+    assert got.min() >= 0 and got.max() < NC
+    np.testing.assert_array_equal(got, free['labels'])
+    np.testing.assert_array_equal(smp, 2.0 * got.astype(np.float32) / np.float32(NC - 1.0) - np.float32(1.0))
+
+
 def test_generate_many_fills_the_teams_with_ragged_utterances(tmp_path):
     """Serving extension: 5 utterances of different lengths in one device call (one per XCD team on the latency kernel).
     Row i, trimmed to its own length, must be what a single generate() call on clip i gives for the same noise."""

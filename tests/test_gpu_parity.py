@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 KERNELS = ['team2', 'batch', 'batch_cs', 'simple']
 # The straightforward one-workgroup kernel runs ~1 ms/step: it is exercised on the B=3 case (3 rows in
 # parallel) and on the fold case only; the team kernel (the shipped path) runs every case.
-SIMPLE_CASES = {'raw_peaky_b3_t21', 'raw_peaky_fold_t30', 'mol_default_b2_t21'}
+SIMPLE_CASES = {'raw_peaky_b3_t21', 'raw_peaky_fold_t30', 'mol_default_b2_t21', 'raw_peaky8_b2_t21'}
 
 
 def _skip_slow(name, kernel):
@@ -125,7 +125,7 @@ def test_raw_free_running_matches_reference_labels(name, kernel):
     first = check_free_run_raw(got, ref)
     # samples are the label mapped to [-1, 1] exactly like fatchord_version.py:235
     smp = res['samples'].cpu().numpy().T
-    np.testing.assert_array_equal(smp, (2.0 * got.astype(np.float32) / np.float32(1023.0) - np.float32(1.0)))
+    np.testing.assert_array_equal(smp, (2.0 * got.astype(np.float32) / np.float32(m.n_classes - 1.0) - np.float32(1.0)))
     if all(f is None for f in first):
         np.testing.assert_array_equal(got, fx['labels'].astype(np.int32))
 

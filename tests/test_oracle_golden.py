@@ -39,7 +39,7 @@ def test_loop_and_epilogue_match_reference(name):
     if fx['mode'] == 'RAW':
         # bit-exact class indices over the whole free-running sequence
         np.testing.assert_array_equal(r['labels'], fx['labels'].astype(np.int32))
-        ncls, mu = 1024, True
+        ncls, mu = 2 ** int(fx['bits']), True
     else:
         np.testing.assert_allclose(r['samples'], fx['samples'], rtol=0, atol=2e-6)
         ncls, mu = 30, False
