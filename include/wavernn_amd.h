@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define WRNN_ABI_VERSION 8
+#define WRNN_ABI_VERSION 9
 
 /* mode: fatchord_version.py:98-103 */
 #define WRNN_MODE_RAW 0 /* softmax over 2**bits classes */
@@ -49,7 +49,7 @@ extern "C" {
 
 /* where the sampler's randomness comes from (fatchord_version.py:225-237,
  * wavernn/utils/distribution.py:87-123) */
-#define WRNN_NOISE_PHILOX 0   /* device counter RNG keyed by (seed, step, row, class) */
+#define WRNN_NOISE_PHILOX 0   /* device counter RNG keyed by (seed, step, row, class); utt_seeds_dev: per-utterance keys */
 #define WRNN_NOISE_INJECTED 1 /* caller-supplied draws: parity protocol with the reference */
 #define WRNN_NOISE_ARGMAX 2   /* RAW only: greedy (q == 1) */
 
@@ -136,8 +136,9 @@ typedef struct wrnn_sample_opts {
     /* Ragged batch (unbatched mode only), device pointer to B int32 or NULL: utterance b has frames_dev[b] valid mel
      * frames (1 <= frames_dev[b] <= T; mels_dev stays (B, feat, T), zero beyond an utterance's own frames -- the padding
      * generate() itself applies, :183).  Row b then runs frames_dev[b] * hop steps instead of T * hop: its first
-     * frames_dev[b] * hop outputs are exactly what a call on that clip alone produces (rows are independent, :194-196;
-     * the noise is keyed by (row, step)), the rest of the row is left unwritten.  The library orders the rows by length
+     * frames_dev[b] * hop outputs are exactly what a call on that clip alone produces under injected noise (rows are
+     * independent, :194-196); under WRNN_NOISE_PHILOX the draws are keyed by (seed, step, row b), i.e. by the clip's place
+     * in the batch, unless utt_seeds_dev gives every clip its own key.  The rest of the row is left unwritten.  The library orders the rows by length
      * on the device (longest first), fills team batches with rows of similar length and deals the batches to the teams
      * in snake order, so that no team idles behind a long clip. */
     const int32_t *frames_dev;
@@ -146,6 +147,16 @@ typedef struct wrnn_sample_opts {
      * segments so that the conditioning stream of one segment stays cache resident; rounded down to a multiple of 32). */
     int32_t batch_rows;
     int32_t team2_segment;
+    /* ABI 9.  Per-utterance seeds (WRNN_NOISE_PHILOX only), device pointer to B uint64 or NULL.  Every draw of utterance b is
+     * keyed as a call on that clip ALONE with seed = utt_seeds_dev[b] keys it: key = all 64 bits of utt_seeds_dev[b], row word =
+     * the row's index inside its utterance (fold i in wrnn_generate_folded, 0 in an unbatched wrnn_generate), step and class
+     * words unchanged; `seed` is not read.  What a clip sounds like then does not depend on which clips share the call, on its
+     * place among them, or on how a queue was dealt over devices: its rows are bit-equal to those of the solo call on the same
+     * kernel with the same batch_rows / team2_segment.  The per-row keys are built on the device next to the row table (nothing
+     * is staged on the host, the call never waits); the array must stay valid until that kernel has run.  NULL: the call-wide
+     * `seed` and the row's index in the call, as before ABI 9.  WRNN_ERR_INVALID: with batched != 0 in wrnn_generate (one
+     * utterance: `seed` already is its key), with any noise_mode other than WRNN_NOISE_PHILOX, and in wrnn_stream_open. */
+    const uint64_t *utt_seeds_dev;
 } wrnn_sample_opts;
 
 typedef struct wrnn_timing {
@@ -365,8 +376,11 @@ int wrnn_plan_folded(const int32_t *frames_host, int32_t B, int32_t hop, int32_t
  * device's fold count differs from rows_total no row outside [0, rows_total) is touched and the timing entry reports
  * WRNN_ERR_INVALID.  Kernel choice, opts->batch_rows, opts->team2_segment, segmentation and the per-device team gate work as
  * for rows_total rows of one folded utterance; wrnn_timing.rows = rows_total.  Noise: WRNN_NOISE_INJECTED arrays are
- * (steps, rows_total, .); the WRNN_NOISE_PHILOX row key is the GLOBAL row index fold0[b] + i, so a clip's draws depend on
- * its position in the call (per-request keys are not provided).  opts->frames_dev, mels_padded, x_forced_dev, x_init_dev and
+ * (steps, rows_total, .); WRNN_NOISE_PHILOX keys fold i of utterance b by (opts->utt_seeds_dev[b], step, i) -- the draws of
+ * wrnn_generate(clip b, batched = 1) with that seed, wherever the clip stands in the call -- or, when utt_seeds_dev is NULL, by
+ * (opts->seed, step, GLOBAL row index fold0[b] + i): then a clip's draws depend on its position in the call.  The CUT of a
+ * clip depends on `target` alone; a caller that derives target from the whole queue makes the audio depend on the queue
+ * through the cut, whatever the seeds.  opts->frames_dev, mels_padded, x_forced_dev, x_init_dev and
  * logits_out_dev must be 0 / NULL (WRNN_ERR_INVALID). */
 int wrnn_generate_folded(wrnn_handle *h, const float *mels_dev, int32_t B, int32_t T, const int32_t *frames_dev, int32_t rows_total,
                          int32_t target, int32_t overlap, const wrnn_sample_opts *opts, int32_t *labels_out_dev,

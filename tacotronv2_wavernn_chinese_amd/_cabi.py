@@ -25,7 +25,7 @@ DTYPE_F32, DTYPE_I64 = 0, 1
 ERR_NAMES = {0: 'WRNN_OK', -1: 'WRNN_ERR_INVALID', -2: 'WRNN_ERR_HIP', -3: 'WRNN_ERR_STATE',
              -4: 'WRNN_ERR_MISSING_KEY', -5: 'WRNN_ERR_TIMEOUT', -6: 'WRNN_ERR_BUSY'}
 ERR_INVALID, ERR_STATE, ERR_TIMEOUT, ERR_BUSY = -1, -3, -5, -6
-ABI_VERSION = 8   # WRNN_ABI_VERSION of the include/wavernn_amd.h this binding was written against
+ABI_VERSION = 9   # WRNN_ABI_VERSION of the include/wavernn_amd.h this binding was written against
 
 # every symbol include/wavernn_amd.h declares (checked by tests/test_cabi_symbols.py)
 EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wrnn_plan', 'wrnn_generate',
@@ -74,7 +74,7 @@ class SampleOpts(C.Structure):
     _fields_ = [('struct_size', C.c_uint32), ('noise_mode', C.c_int32), ('kernel', C.c_int32), ('mels_padded', C.c_int32),
                 ('seed', C.c_uint64), ('noise1_dev', C.c_void_p), ('noise2_dev', C.c_void_p), ('x_forced_dev', C.c_void_p),
                 ('logits_out_dev', C.c_void_p), ('x_init_dev', C.c_void_p), ('frames_dev', C.c_void_p),
-                ('batch_rows', C.c_int32), ('team2_segment', C.c_int32)]
+                ('batch_rows', C.c_int32), ('team2_segment', C.c_int32), ('utt_seeds_dev', C.c_void_p)]
 
 
 LOOP_PARAM_FIELDS = ('I_w', 'I_b', 'rnn1_w_ih', 'rnn1_w_hh', 'rnn1_b_ih', 'rnn1_b_hh', 'rnn2_w_ih', 'rnn2_w_hh', 'rnn2_b_ih',
@@ -306,10 +306,11 @@ class NativeVocoder:
                  labels_ptr: int, samples_ptr: int, stream: int, noise_mode: int = NOISE_PHILOX, seed: int = 0,
                  noise1_ptr: int = 0, noise2_ptr: int = 0, x_forced_ptr: int = 0, logits_ptr: int = 0,
                  kernel: int = KERNEL_AUTO, x_init_ptr: int = 0, mels_padded: bool = False, frames_ptr: int = 0,
-                 batch_rows: int = 0, team2_segment: int = 0):
+                 batch_rows: int = 0, team2_segment: int = 0, utt_seeds_ptr: int = 0):
         o = SampleOpts()
         o.struct_size = C.sizeof(SampleOpts)
         o.frames_dev = frames_ptr or None
+        o.utt_seeds_dev = utt_seeds_ptr or None   # B device uint64: per-utterance Philox keys (unbatched calls)
         o.batch_rows, o.team2_segment = int(batch_rows), int(team2_segment)
         o.noise_mode, o.kernel, o.seed = noise_mode, kernel, seed & 0xFFFFFFFFFFFFFFFF
         o.noise1_dev, o.noise2_dev = noise1_ptr or None, noise2_ptr or None
@@ -321,13 +322,15 @@ class NativeVocoder:
 
     def generate_folded(self, mels_ptr: int, B: int, T: int, frames_ptr: int, rows_total: int, target: int, overlap: int, *,
                         labels_ptr: int, samples_ptr: int, stream: int, noise_mode: int = NOISE_PHILOX, seed: int = 0,
-                        noise1_ptr: int = 0, noise2_ptr: int = 0, kernel: int = KERNEL_AUTO, batch_rows: int = 0, team2_segment: int = 0):
+                        noise1_ptr: int = 0, noise2_ptr: int = 0, kernel: int = KERNEL_AUTO, batch_rows: int = 0, team2_segment: int = 0,
+                        utt_seeds_ptr: int = 0):
         """``wrnn_generate_folded``: the folds of all B utterances as the rows of one call (rows_total from :func:`plan_folded`)."""
         o = SampleOpts()
         o.struct_size = C.sizeof(SampleOpts)
         o.batch_rows, o.team2_segment = int(batch_rows), int(team2_segment)
         o.noise_mode, o.kernel, o.seed = noise_mode, kernel, seed & 0xFFFFFFFFFFFFFFFF
         o.noise1_dev, o.noise2_dev = noise1_ptr or None, noise2_ptr or None
+        o.utt_seeds_dev = utt_seeds_ptr or None
         self._check(self.lib.wrnn_generate_folded(self._h, mels_ptr, B, T, frames_ptr or None, int(rows_total), int(target), int(overlap),
                                                   C.byref(o), labels_ptr or None, samples_ptr, stream or None))
 

@@ -197,6 +197,7 @@ void wrnn_destroy(wrnn_handle *h) {
     if (h->rows_dev) (void)hipFree(h->rows_dev);
     if (h->order_dev) (void)hipFree(h->order_dev);
     if (h->sched_dev) (void)hipFree(h->sched_dev);
+    if (h->keys_dev) (void)hipFree(h->keys_dev);
     if (h->fold0_dev) (void)hipFree(h->fold0_dev);
     if (h->prof) (void)hipFree(h->prof);
     if (h->err_dev) (void)hipFree(h->err_dev);
@@ -540,6 +541,10 @@ static int generate_impl(wrnn_handle *h, const float *mels_dev, int32_t B, int32
     if (opts->noise_mode == WRNN_NOISE_ARGMAX && d.mode != WRNN_MODE_RAW)
         return fail(h, WRNN_ERR_INVALID, "WRNN_NOISE_ARGMAX is RAW-only");
     if (opts->noise_mode < 0 || opts->noise_mode > 2) return fail(h, WRNN_ERR_INVALID, "bad noise_mode");
+    if (opts->utt_seeds_dev && opts->noise_mode != WRNN_NOISE_PHILOX)
+        return fail(h, WRNN_ERR_INVALID, "utt_seeds_dev (per-utterance seeds) needs noise_mode WRNN_NOISE_PHILOX");
+    if (opts->utt_seeds_dev && batched && !fold_frames)
+        return fail(h, WRNN_ERR_INVALID, "utt_seeds_dev is for unbatched calls and wrnn_generate_folded: a batched wrnn_generate has one utterance, `seed` is its key");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
 
@@ -549,10 +554,13 @@ static int generate_impl(wrnn_handle *h, const float *mels_dev, int32_t B, int32
         h->rows_dev = nullptr; h->rows_cap = 0;
         if (h->order_dev) (void)hipFree(h->order_dev);
         if (h->sched_dev) (void)hipFree(h->sched_dev);
+        if (h->keys_dev) (void)hipFree(h->keys_dev);
         h->order_dev = h->sched_dev = nullptr;
+        h->keys_dev = nullptr;
         HIP_TRY(h, hipMalloc(&h->rows_dev, (size_t)rows * sizeof(WrnnRow)));
         HIP_TRY(h, hipMalloc(&h->order_dev, (size_t)rows * sizeof(int32_t)));
         HIP_TRY(h, hipMalloc(&h->sched_dev, ((size_t)rows + 64) * sizeof(int32_t)));
+        HIP_TRY(h, hipMalloc(&h->keys_dev, (size_t)rows * sizeof(WrnnRowKey)));
         h->rows_cap = rows;
     }
     const int sched_teams = h->n_teams < 1 ? 1 : h->n_teams;
@@ -567,11 +575,11 @@ static int generate_impl(wrnn_handle *h, const float *mels_dev, int32_t B, int32
             h->fold0_cap = (size_t)B + 1;
         }
         HIP_TRY(h, wrnn_launch_rows_folded(h->rows_dev, h->order_dev, h->sched_dev, h->fold0_dev, h->err_dev, fold_frames, B, rows, sched_teams,
-                                           (long)target, (long)overlap, d.HOP, T, s));
+                                           (long)target, (long)overlap, d.HOP, T, h->keys_dev, opts->utt_seeds_dev, s));
         h->fold_B = B; h->fold_target = target; h->fold_overlap = overlap; h->fold_rows = rows;
     } else {
         HIP_TRY(h, wrnn_launch_rows(h->rows_dev, h->order_dev, h->sched_dev, rows, sched_teams, batched, (long)target + overlap, (long)steps,
-                                    opts->frames_dev, T, d.HOP, s));
+                                    opts->frames_dev, T, d.HOP, h->keys_dev, opts->utt_seeds_dev, s));
     }
     const int snake = opts->frames_dev ? 1 : 0;
     unsigned long long *const prof = h->prof_on ? h->prof : nullptr;
@@ -585,7 +593,7 @@ static int generate_impl(wrnn_handle *h, const float *mels_dev, int32_t B, int32
     WrnnLoopArgs a{};
     a.w = h->wdev; a.off = h->off; a.d = d; a.mels = mels_dev; a.mel_T = mel_T; a.mel_off = mel_off; a.aux_frames = h->aux_frames; a.rows = h->rows_dev;
     a.n_rows = rows; a.T = T; a.total_len = (int64_t)T * d.HOP; a.steps = steps;
-    a.noise_mode = opts->noise_mode; a.seed = opts->seed; a.noise1 = opts->noise1_dev; a.noise2 = opts->noise2_dev;
+    a.noise_mode = opts->noise_mode; a.seed = opts->seed; a.keys = opts->utt_seeds_dev ? h->keys_dev : nullptr; a.noise1 = opts->noise1_dev; a.noise2 = opts->noise2_dev;
     a.x_forced = opts->x_forced_dev; a.x_init = opts->x_init_dev; a.logits_out = opts->logits_out_dev; a.labels_out = labels_out_dev;
     a.samples_out = samples_out_dev; a.err = h->err_dev; a.frames = fold_frames;
     int kernel = opts->kernel;
@@ -643,7 +651,7 @@ static int generate_impl(wrnn_handle *h, const float *mels_dev, int32_t B, int32
             ba.w = w; ba.off = o; ba.d = d; ba.batch_w = h->batch_w; ba.batch_fc3 = h->batch_fc3; ba.batch_wn = h->batch_wn; ba.wI0 = h->wI0; ba.u1 = h->u1;
             ba.tabREC32 = tREC; ba.rows = h->rows_dev; ba.order = h->order_dev; ba.snake = snake; ba.n_rows = rows; ba.n_teams = h->n_teams; ba.nq = rpb <= 4 ? 1 : 2; ba.rpb = rpb;
             ba.T = T; ba.total_len = a.total_len; ba.steps = steps;
-            ba.noise_mode = a.noise_mode; ba.seed = a.seed; ba.noise1 = a.noise1; ba.noise2 = a.noise2; ba.x_forced = a.x_forced; ba.x_init = a.x_init;
+            ba.noise_mode = a.noise_mode; ba.seed = a.seed; ba.keys = a.keys; ba.noise1 = a.noise1; ba.noise2 = a.noise2; ba.x_forced = a.x_forced; ba.x_init = a.x_init;
             ba.logits_out = a.logits_out; ba.labels_out = a.labels_out; ba.samples_out = a.samples_out;
             ba.mail = h->mail; ba.ctl = h->ctl; ba.err = h->err_dev; ba.prof = prof;
             if (prof) HIP_TRY(h, hipMemsetAsync(h->prof, 0, 8 * WRNN_PROF_SLOTS * sizeof(unsigned long long), s));
@@ -666,7 +674,7 @@ static int generate_impl(wrnn_handle *h, const float *mels_dev, int32_t B, int32
         ta.tabREC = tREC; ta.tabCOND = nullptr; ta.tabC2 = tC2; ta.tabC3 = tC3; ta.tabC4 = tC4;
         ta.rows = h->rows_dev; ta.sched = h->sched_dev; ta.n_slots = n_slots; ta.ragged = snake; ta.n_rows = rows; ta.n_teams = h->n_teams; ta.T = T; ta.total_len = a.total_len; ta.steps = steps;
         ta.seg0 = 0; ta.seg_len = steps; ta.state = nullptr;
-        ta.noise_mode = a.noise_mode; ta.seed = a.seed; ta.noise1 = a.noise1; ta.noise2 = a.noise2; ta.x_forced = a.x_forced; ta.x_init = a.x_init;
+        ta.noise_mode = a.noise_mode; ta.seed = a.seed; ta.keys = a.keys; ta.noise1 = a.noise1; ta.noise2 = a.noise2; ta.x_forced = a.x_forced; ta.x_init = a.x_init;
         ta.logits_out = a.logits_out; ta.labels_out = a.labels_out; ta.samples_out = a.samples_out;
         ta.mail = h->mail; ta.ctl = h->ctl; ta.err = h->err_dev; ta.prof = prof;
         {

@@ -106,8 +106,10 @@ struct Lay {
     static constexpr int L_MISC = L_XN + 16;       // [16]
     static constexpr int L_PROF = L_MISC + 16;     // [4 waves][24] phase-cycle accumulators of the instrumented build (in LDS, not in
                                                    // registers: the kernel has none to spare)
-    static constexpr int L_TOTAL = L_PROF + 96;
+    static constexpr int L_KEY = L_PROF + 96;      // [R][4] RAW: Philox key {seed lo, seed hi, row word, -} of every batch row (see key_fill)
+    static constexpr int L_TOTAL = L_KEY + 4 * R;
     static_assert(L_TOTAL * 4 <= 163840, "LDS budget");
+    static_assert((L_KEY % 4) == 0, "keys are read as 16-byte vectors");
     // mailbox regions per team (granules); every region is double-buffered by step parity
     static constexpr unsigned RG = (unsigned)VEC;
     static constexpr unsigned G_X2 = 0, G_H1 = 2 * RG, G_X3 = 4 * RG, G_F1 = 6 * RG, G_F2 = 8 * RG, G_PR = 10 * RG;
@@ -119,6 +121,20 @@ struct Lay {
 // slots of L_CST
 constexpr int C_A0 = 0, C_A1 = 1, C_A2 = 2, C_A3 = 3, C_B30 = 4, C_B31 = 5, C_H1R = 6, C_H1Z = 7, C_H1N = 8, C_H2R = 9, C_H2Z = 10, C_H2N = 11;
 constexpr int M_DEAD = 0, M_TEAM = 1, M_RANK = 2;
+
+// RAW sampler keys of a team batch (both batch kernels).  A thread draws for its OWN batch row rb = lane-dependent, so the key cannot
+// sit in scalar registers, and as three more VGPRs (plus the ten round keys the compiler then hoists out of the step loop) it pushed
+// every RAW instantiation into new scratch spills.  So: thread `brow` < R resolves the key of batch row `brow` ONCE per batch -- slot ->
+// row through a.order[], then the call's (seed, row) or the row's own entry of a.keys (opts.utt_seeds_dev) -- into this LDS table, and
+// a step reads its 16 bytes where it evaluates the Philox block (every other step, off the serial chain).
+typedef const unsigned __attribute__((address_space(3))) *lds_cup;
+__device__ __forceinline__ void key_fill(const WrnnBatchArgs &a, float *keyt, int batch, int brow) {
+    const int s0 = batch * a.rpb + brow;
+    const int r = a.order[(brow < a.rpb && s0 < a.n_rows) ? s0 : a.n_rows - 1];
+    u4v k = {(unsigned)a.seed, (unsigned)(a.seed >> 32), (unsigned)r, 0u};
+    if (a.keys) { const WrnnRowKey rk = a.keys[r]; k.x = (unsigned)rk.seed; k.y = (unsigned)(rk.seed >> 32); k.z = rk.row; }
+    ((u4v *)keyt)[brow] = k;
+}
 
 // All-gather of NV published vectors (R x 512 granules each, mailbox order [rq][wl][S][iu][j][e]; slice m = (rq, wl) holds
 // what wave wl of EVERY workgroup published for row quad rq).  Every load of every vector is in flight at once -- one L2

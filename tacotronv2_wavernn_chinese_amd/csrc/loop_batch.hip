@@ -180,6 +180,18 @@ __global__ void __launch_bounds__(TB_THREADS) loop_batch_kernel(WrnnBatchArgs a)
             frow[bi] = a.order[rok ? s0 : a.n_rows - 1];
             fsteps[bi] = rok ? a.rows[frow[bi]].steps : 0;   // 0 = masked
         }
+        // Philox keys: the call's (seed, row), or the row's own when the call carries per-utterance seeds (opts.utt_seeds_dev; indexed by
+        // the row, not by its slot).  Resolved once per batch: MOL draws for the rows this wave finishes (wave-uniform: scalar
+        // registers), RAW for the thread's own row (the LDS table of key_fill, batch_common.h).
+        uint64_t fseed[NQ];
+        uint32_t fkrow[NQ];
+#pragma unroll
+        for (int bi = 0; bi < NQ; ++bi) { fseed[bi] = a.seed; fkrow[bi] = (uint32_t)frow[bi]; }
+        if (MODE != WRNN_MODE_RAW && a.keys) {
+#pragma unroll
+            for (int bi = 0; bi < NQ; ++bi) { const WrnnRowKey k = a.keys[frow[bi]]; fseed[bi] = k.seed; fkrow[bi] = k.row; }
+        }
+        if (MODE == WRNN_MODE_RAW && tid < R) key_fill(a, lds + L::L_KEY, batch, tid);
 
         // conditioning {cI, v_r, v_z, v_n} of step ts for (unit, row): record + 5-tap upsampling (prologue.hip)
         // The loads are issued one step ahead: the record (24 floats) stays in registers and is re-read only when the frame
@@ -240,7 +252,8 @@ __global__ void __launch_bounds__(TB_THREADS) loop_batch_kernel(WrnnBatchArgs a)
                 const bool upper = lane >= 32;
                 unsigned ba, bb;
                 if ((ts & 1) == 0) {
-                    const Philox4 pb = wrnn_raw_block(a.seed, (uint64_t)ts, (uint32_t)row, (uint32_t)(upper ? cls0 + 4 : cls0));
+                    const lds_cup kp = (lds_cup)(size_t)(smem_base + (unsigned)L::L_KEY * 4u) + 4 * rb;
+                    const Philox4 pb = wrnn_raw_block(((uint64_t)kp[1] << 32) | kp[0], (uint64_t)ts, kp[2], (uint32_t)(upper ? cls0 + 4 : cls0));
                     ba = pb.x; bb = pb.y;
                     pz0 = __uint_as_float(pb.z); pz1 = __uint_as_float(pb.w);
                 } else { ba = __float_as_uint(pz0); bb = __float_as_uint(pz1); }
@@ -610,7 +623,7 @@ __global__ void __launch_bounds__(TB_THREADS) loop_batch_kernel(WrnnBatchArgs a)
                         if (a.noise_mode == WRNN_NOISE_INJECTED)
                             u = lane < nr ? a.noise1[((size_t)t * a.n_rows + rrow) * nr + lane] : a.noise2[(size_t)t * a.n_rows + rrow];
                         else
-                            u = wrnn_uniform_mol(a.seed, (uint64_t)t, (uint32_t)rrow, (uint32_t)lane);
+                            u = wrnn_uniform_mol(fseed[bi], (uint64_t)t, fkrow[bi], (uint32_t)lane);
                         nzv = lane < nr ? -logf(-logf(u)) : logf(u) - logf(1.0f - u);
                     }
                     float mylg = 0.0f;

@@ -127,8 +127,10 @@ struct LayCS {
     static constexpr int L_LG = L_H1;               // [R][32] MOL: the 30 fc3 outputs of every batch row, in window 5 (H1 is dead from B4 to the next h1' gather)
     static constexpr int L_MISC = L_XN + 16;
     static constexpr int L_PROF = L_MISC + 16;      // [2 roles][24]: phase cycles of wave 0 (C) and wave 4 (S), instrumented build only
-    static constexpr int L_TOTAL = L_PROF + 48;
+    static constexpr int L_KEY = L_PROF + 48;       // [R][4] RAW: Philox key of every batch row (key_fill, batch_common.h)
+    static constexpr int L_TOTAL = L_KEY + 4 * R;
     static_assert(L_TOTAL * 4 <= 163840, "LDS budget");
+    static_assert((L_KEY % 4) == 0, "keys are read as 16-byte vectors");
     static_assert((L_P % 4) == 0, "B operands are read as 16-byte vectors");
 };
 // hand-over slots
@@ -804,6 +806,18 @@ __global__ void __launch_bounds__(CS_THREADS) loop_batch_cs_kernel(WrnnBatchArgs
                 frowS[bi] = a.order[rok ? s0 : a.n_rows - 1];
                 fstepsS[bi] = rok ? a.rows[frowS[bi]].steps : 0;
             }
+            // Philox keys: the call's (seed, row), or the row's own when the call carries per-utterance seeds (opts.utt_seeds_dev; indexed by
+            // the row, not by its slot).  Resolved once per batch: MOL draws for the rows frowS[] whose sampler the C wave of this SIMD runs
+            // (wave-uniform: scalar registers), RAW for the thread's own row -- at R = 8 both quads' rows, whichever wave finishes them --
+            // through the LDS table of key_fill (batch_common.h).
+            uint64_t fseed[NQ];
+            uint32_t fkrow[NQ];
+#pragma unroll
+            for (int bi = 0; bi < NQ; ++bi) { fseed[bi] = a.seed; fkrow[bi] = (uint32_t)frowS[bi]; }
+            if (MODE != WRNN_MODE_RAW && a.keys) {
+#pragma unroll
+                for (int bi = 0; bi < NQ; ++bi) { const WrnnRowKey k = a.keys[frowS[bi]]; fseed[bi] = k.seed; fkrow[bi] = k.row; }
+            }
             auto noise_step = [&](int64_t ts, unsigned np) {
                 if (MODE != WRNN_MODE_RAW) {
                     // sample_from_discretized_mix_logistic (distribution.py:106-121): 10 Gumbel draws (mixture pick) + 1 logistic draw per row
@@ -816,7 +830,7 @@ __global__ void __launch_bounds__(CS_THREADS) loop_batch_cs_kernel(WrnnBatchArgs
                             if (a.noise_mode == WRNN_NOISE_INJECTED)
                                 u = lane < nr ? a.noise1[((size_t)ts * a.n_rows + rrow) * nr + lane] : a.noise2[(size_t)ts * a.n_rows + rrow];
                             else
-                                u = wrnn_uniform_mol(a.seed, (uint64_t)ts, (uint32_t)rrow, (uint32_t)lane);
+                                u = wrnn_uniform_mol(fseed[bi], (uint64_t)ts, fkrow[bi], (uint32_t)lane);
                             molnz[((int)np * R + brow) * 16 + lane] = lane < nr ? -logf(-logf(u)) : logf(u) - logf(1.0f - u);
                         }
                     }
@@ -831,7 +845,8 @@ __global__ void __launch_bounds__(CS_THREADS) loop_batch_cs_kernel(WrnnBatchArgs
                     const bool upper = lane >= 32;
                     unsigned ba, bb;
                     if ((ts & 1) == 0) {
-                        const Philox4 pb = wrnn_raw_block(a.seed, (uint64_t)ts, (uint32_t)row, (uint32_t)(upper ? cls0 + 4 : cls0));
+                        const lds_cup kp = (lds_cup)(size_t)(smem_base + (unsigned)L::L_KEY * 4u) + 4 * rb;
+                        const Philox4 pb = wrnn_raw_block(((uint64_t)kp[1] << 32) | kp[0], (uint64_t)ts, kp[2], (uint32_t)(upper ? cls0 + 4 : cls0));
                         ba = pb.x; bb = pb.y;
                         pz0 = __uint_as_float(pb.z); pz1 = __uint_as_float(pb.w);
                     } else { ba = __float_as_uint(pz0); bb = __float_as_uint(pz1); }
@@ -848,6 +863,7 @@ __global__ void __launch_bounds__(CS_THREADS) loop_batch_cs_kernel(WrnnBatchArgs
                 hand[H_GH1R * SL] = cst[C_H1R * SL]; hand[H_GH1Z * SL] = cst[C_H1Z * SL]; hand[H_GH1N * SL] = cst[C_H1N * SL];
                 hand[H_GH2R * SL] = cst[C_H2R * SL]; hand[H_GH2Z * SL] = cst[C_H2Z * SL]; hand[H_GH2N * SL] = cst[C_H2N * SL];
             }
+            if (MODE == WRNN_MODE_RAW && tl < R) key_fill(a, lds + L::L_KEY, batch, tl);   // read behind the barrier in front of step 0
             cond_step(0);
             frame_flush();
             __syncthreads();

@@ -74,6 +74,10 @@ __global__ void __launch_bounds__(SIMPLE_THREADS) loop_simple_kernel(WrnnLoopArg
     const float *aux_b = a.aux_frames + (size_t)rw.utt * a.T * R;
     const float *ktab = w + a.off.ktab;
     const int lane = tid & 63, wave = tid >> 6;
+    // Philox key of the row: the call's (seed, row), or the row's own when the call carries per-utterance seeds (opts.utt_seeds_dev)
+    uint64_t kseed = a.seed;
+    uint32_t krow = (uint32_t)row;
+    if (a.keys) { const WrnnRowKey k = a.keys[row]; kseed = k.seed; krow = k.row; }
 
     // h1 = h2 = 0, x = x_init or 0   (:194-196); a stream's later pushes (seg0 > 0) resume from the state the previous one left
     float *st = a.state ? a.state + (size_t)row * wrnn_simple_state_floats(d) : nullptr;
@@ -208,7 +212,7 @@ __global__ void __launch_bounds__(SIMPLE_THREADS) loop_simple_kernel(WrnnLoopArg
                 if (a.noise_mode == WRNN_NOISE_INJECTED) {
                     v -= logf(a.noise1[((size_t)t * a.n_rows + row) * NC + c]);
                 } else if (a.noise_mode == WRNN_NOISE_PHILOX) {
-                    const float u = wrnn_uniform_raw(a.seed, (uint64_t)t, (uint32_t)row, (uint32_t)c);
+                    const float u = wrnn_uniform_raw(kseed, (uint64_t)t, krow, (uint32_t)c);
                     v -= logf(-logf(u));
                 }
                 if (v > bv) { bv = v; bi = c; }
@@ -236,7 +240,7 @@ __global__ void __launch_bounds__(SIMPLE_THREADS) loop_simple_kernel(WrnnLoopArg
                 if (lane < nr) {
                     float u1;
                     if (a.noise_mode == WRNN_NOISE_INJECTED) u1 = a.noise1[((size_t)t * a.n_rows + row) * nr + lane];
-                    else u1 = wrnn_uniform_mol(a.seed, (uint64_t)t, (uint32_t)row, (uint32_t)lane);
+                    else u1 = wrnn_uniform_mol(kseed, (uint64_t)t, krow, (uint32_t)lane);
                     v = s_logits[lane] - logf(-logf(u1));   // :107
                     k = lane;
                 }
@@ -244,7 +248,7 @@ __global__ void __launch_bounds__(SIMPLE_THREADS) loop_simple_kernel(WrnnLoopArg
                 if (lane == 0) {
                     float u2;
                     if (a.noise_mode == WRNN_NOISE_INJECTED) u2 = a.noise2[(size_t)t * a.n_rows + row];
-                    else u2 = wrnn_uniform_mol(a.seed, (uint64_t)t, (uint32_t)row, 10u);
+                    else u2 = wrnn_uniform_mol(kseed, (uint64_t)t, krow, 10u);
                     const float mean = s_logits[nr + k];                       // :113
                     const float ls = fmaxf(s_logits[2 * nr + k], -32.23619130191664f);  // log(1e-14) :114-115
                     float xs = mean + expf(ls) * (logf(u2) - logf(1.0f - u2));  // :119

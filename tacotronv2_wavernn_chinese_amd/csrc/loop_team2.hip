@@ -415,6 +415,11 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
             if (row < 0) continue;
         }
         const WrnnRow rw = a.rows[row];
+        // Philox key of the row: the call's (seed, row), or the row's own when the call carries per-utterance seeds (opts.utt_seeds_dev).
+        // Resolved once per row; the row is uniform in the workgroup, so the key stays in scalar registers.
+        uint64_t kseed = a.seed;
+        uint32_t krow = (uint32_t)row;
+        if (a.keys) { const WrnnRowKey k = a.keys[row]; kseed = k.seed; krow = k.row; }
         int64_t seg_end = a.seg0 + a.seg_len;   // this launch runs steps [seg0, seg_end) of the row
         if constexpr (RAGGED) {
             if (a.seg0 >= rw.steps) continue;   // a shorter row: finished in an earlier segment
@@ -471,7 +476,7 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
                 if (a.noise_mode == WRNN_NOISE_INJECTED)
                     u = lane < nr ? a.noise1[((size_t)ts * a.n_rows + row) * nr + lane] : a.noise2[(size_t)ts * a.n_rows + row];
                 else
-                    u = wrnn_uniform_mol(a.seed, (uint64_t)ts, (uint32_t)row, (uint32_t)lane);
+                    u = wrnn_uniform_mol(kseed, (uint64_t)ts, krow, (uint32_t)lane);
                 misc_f[32 + 16 * (ep_of_ts & 1u) + lane] = lane < nr ? -logf(-logf(u)) : logf(u) - logf(1.0f - u);
             }
             if (MODE == WRNN_MODE_RAW && has_fc3) {
@@ -485,7 +490,7 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
                     // evaluate 16 DIFFERENT blocks (the next 32 steps) at once instead of the same one 16 times: one
                     // Philox evaluation per lane every 32 steps; the lane that owns step ts hands its draw over.
                     if ((ts & 31) == 0) {
-                        const Philox4 pz = wrnn_raw_block(a.seed, (uint64_t)ts + 2u * (unsigned)q, (uint32_t)row, (uint32_t)c3row0);
+                        const Philox4 pz = wrnn_raw_block(kseed, (uint64_t)ts + 2u * (unsigned)q, krow, (uint32_t)c3row0);
                         // -log q = -log(-log u): the inner log exactly (q is tiny for u -> 1, where v_log_f32 is not accurate
                         // relative to the result -- and such a draw tends to win the race), the outer one fast
                         nzE0 = -__logf(-logf(u01_from_bits(pz.x)));

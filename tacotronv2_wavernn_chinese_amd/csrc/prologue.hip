@@ -384,9 +384,10 @@ hipError_t wrnn_launch_mask_frame_tables(float *C2, float *C3, float *C4, const 
 
 // The loop's row table, built on the device (no host staging buffer, no synchronisation in wrnn_generate):
 // unbatched: row r = utterance r from position 0; batched (fold_with_overlap :332-338): row r = utterance 0 from
-// position r * (target + overlap).
+// position r * (target + overlap).  seeds != null (unbatched calls with per-utterance seeds): keys[r] = {seeds[r], 0}, the
+// Philox key of a call on utterance r alone.
 __global__ void rows_kernel(WrnnRow *rows, int32_t *order, int32_t *sched, int n_rows, int n_teams, int batched, long stride, long steps,
-                            const int32_t *frames, int T, int hop) {
+                            const int32_t *frames, int T, int hop, WrnnRowKey *keys, const uint64_t *seeds) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     const int n_slots = (n_rows + n_teams - 1) / n_teams * n_teams;
     if (r >= n_rows) {
@@ -410,6 +411,7 @@ __global__ void rows_kernel(WrnnRow *rows, int32_t *order, int32_t *sched, int n
     w.steps = (int32_t)mine;
     w.start = batched ? (int64_t)r * stride : 0;
     rows[r] = w;
+    if (seeds) keys[r] = WrnnRowKey{seeds[r], 0u, 0u};
     // schedule order: longest first, ties by index (a rank scan: n_rows is at most a few thousand utterances)
     int rank = r;
     if (frames) {
@@ -432,12 +434,12 @@ __global__ void rows_kernel(WrnnRow *rows, int32_t *order, int32_t *sched, int n
 }
 
 hipError_t wrnn_launch_rows(WrnnRow *rows, int32_t *order, int32_t *sched, int n_rows, int n_teams, int batched, long stride, long steps,
-                            const int32_t *frames, int T, int hop, hipStream_t s) {
+                            const int32_t *frames, int T, int hop, WrnnRowKey *keys, const uint64_t *seeds, hipStream_t s) {
     (void)hipGetLastError();
     if (n_teams < 1) n_teams = 1;
     const int n_slots = (n_rows + n_teams - 1) / n_teams * n_teams;
     hipLaunchKernelGGL(rows_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, s, rows, order, sched, n_rows, n_teams, batched, stride, steps,
-                       frames, T, hop);
+                       frames, T, hop, keys, seeds);
     return hipGetLastError();
 }
 
@@ -448,11 +450,12 @@ hipError_t wrnn_launch_rows(WrnnRow *rows, int32_t *order, int32_t *sched, int n
 // (wrnn_plan_folded; the outputs are sized by it): whatever frames[] holds, only rows [0, rows_total) are written, each with a
 // valid (utt, start) -- a disagreement repeats the last valid row and raises WRNN_DEVERR_ROWS -- and fold0[] is clamped to
 // rows_total, so the epilogue stays inside the outputs too.  order / sched: identity, -1 in the empty slots, as rows_kernel
-// writes them for a uniform batch.
+// writes them for a uniform batch.  seeds != null: keys[r] = {seeds[utt], fold index inside the utterance}, the Philox key of that
+// fold in a call on the utterance alone.
 __global__ void __launch_bounds__(256)
 rows_folded_kernel(WrnnRow *__restrict__ rows, int32_t *__restrict__ order, int32_t *__restrict__ sched, int32_t *fold0,
                    unsigned *__restrict__ err, const int32_t *__restrict__ frames, int B, int rows_total, int n_teams, long target,
-                   long overlap, int hop, int T) {
+                   long overlap, int hop, int T, WrnnRowKey *__restrict__ keys, const uint64_t *__restrict__ seeds) {
     __shared__ long s_sum;
     const long stride = target + overlap;
     for (int b = threadIdx.x; b < B; b += blockDim.x) {
@@ -487,6 +490,7 @@ rows_folded_kernel(WrnnRow *__restrict__ rows, int32_t *__restrict__ order, int3
         if (r >= rows_total) { sched[r] = -1; continue; }
         WrnnRow w;
         w.utt = 0; w.steps = (int32_t)(target + 2 * overlap); w.start = 0;
+        uint32_t fold = 0;
         if (n_valid > 0) {
             const int rr = r < n_valid ? r : n_valid - 1;
             int lo = 0, hi = B - 1;                      // smallest b with fold0[b + 1] > rr
@@ -495,19 +499,22 @@ rows_folded_kernel(WrnnRow *__restrict__ rows, int32_t *__restrict__ order, int3
                 if (fold0[mid + 1] > rr) hi = mid; else lo = mid + 1;
             }
             w.utt = lo;
-            w.start = (int64_t)(rr - fold0[lo]) * stride;
+            fold = (uint32_t)(rr - fold0[lo]);
+            w.start = (int64_t)fold * stride;
         }
         rows[r] = w;
+        if (seeds) keys[r] = WrnnRowKey{seeds[w.utt], fold, 0u};
         order[r] = r;
         sched[r] = r;
     }
 }
 
 hipError_t wrnn_launch_rows_folded(WrnnRow *rows, int32_t *order, int32_t *sched, int32_t *fold0, unsigned *err, const int32_t *frames,
-                                   int B, int rows_total, int n_teams, long target, long overlap, int hop, int T, hipStream_t s) {
+                                   int B, int rows_total, int n_teams, long target, long overlap, int hop, int T, WrnnRowKey *keys,
+                                   const uint64_t *seeds, hipStream_t s) {
     (void)hipGetLastError();
     if (n_teams < 1) n_teams = 1;
     hipLaunchKernelGGL(rows_folded_kernel, dim3(1), dim3(256), 0, s, rows, order, sched, fold0, err, frames, B, rows_total, n_teams,
-                       target, overlap, hop, T);
+                       target, overlap, hop, T, keys, seeds);
     return hipGetLastError();
 }

@@ -128,8 +128,8 @@ int wrnn_stream_open(wrnn_handle *h, int32_t B, const wrnn_sample_opts *opts, wr
         return sfail(h, WRNN_ERR_INVALID, "a stream draws its noise on the device: noise_mode must be WRNN_NOISE_PHILOX or WRNN_NOISE_ARGMAX");
     if (opts->noise_mode == WRNN_NOISE_ARGMAX && h->d.mode != WRNN_MODE_RAW) return sfail(h, WRNN_ERR_INVALID, "WRNN_NOISE_ARGMAX is RAW-only");
     if (opts->mels_padded || opts->noise1_dev || opts->noise2_dev || opts->x_forced_dev || opts->logits_out_dev || opts->x_init_dev ||
-        opts->frames_dev || opts->batch_rows || opts->team2_segment)
-        return sfail(h, WRNN_ERR_INVALID, "a stream takes noise_mode, kernel and seed only: mels_padded, the pointers and the tuning fields must be 0");
+        opts->frames_dev || opts->batch_rows || opts->team2_segment || opts->utt_seeds_dev)
+        return sfail(h, WRNN_ERR_INVALID, "a stream takes noise_mode, kernel and seed only: mels_padded, the pointers (utt_seeds_dev included) and the tuning fields must be 0");
     const char *team_no = wrnn_loop_team_obstacle(h);
     int kernel = opts->kernel;
     if (kernel == WRNN_KERNEL_AUTO) kernel = team_no ? WRNN_KERNEL_SIMPLE : WRNN_KERNEL_TEAM2;

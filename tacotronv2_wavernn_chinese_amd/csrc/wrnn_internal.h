@@ -63,6 +63,14 @@ struct WrnnRow {
     int32_t steps;    // loop steps of this row: the call's `steps`, or frames[utt] * hop in a ragged batch (opts.frames_dev)
     int64_t start;    // first upsampled position of this row
 };
+// Philox key of one loop row when the call carries per-utterance seeds (opts.utt_seeds_dev): every draw of the row is keyed
+// (seed, step, row, class) with the row's utterance seed and the row's index INSIDE its utterance (fold i of a folded call,
+// 0 of an unbatched one) -- what a call on that utterance alone with that seed draws.  Indexed by the row, not by a schedule slot.
+struct WrnnRowKey {
+    uint64_t seed;
+    uint32_t row;
+    uint32_t pad;
+};
 // Device error word codes (first come, first kept): 3 = a team kernel's workgroups did not all become resident (WRNN_ERR_BUSY),
 // everything else = a bounded exchange spin gave up (WRNN_ERR_TIMEOUT)
 #define WRNN_DEVERR_BUSY 3u
@@ -87,6 +95,7 @@ struct wrnn_handle {
     WrnnRow *rows_dev = nullptr;
     int32_t *order_dev = nullptr; // [rows] rows by length, longest first, in a ragged batch; identity otherwise (BATCH kernel)
     int32_t *sched_dev = nullptr; // [rows rounded up to n_teams] per-team row lists of the TEAM2 kernel (see WrnnTeamArgs)
+    WrnnRowKey *keys_dev = nullptr;   // [rows] Philox keys of a call with opts.utt_seeds_dev (written next to the row table)
     size_t rows_cap = 0;
     // wrnn_generate_folded: first row of every utterance, [B + 1], written by rows_folded_kernel and read by wrnn_epilogue_folded;
     // fold_B > 0 once such a call ran: its B, target, overlap, rows_total
@@ -141,6 +150,7 @@ struct WrnnLoopArgs {
     int64_t steps;            // loop length per row (the longest row's in a ragged batch; row r runs rows[r].steps)
     int32_t noise_mode;
     uint64_t seed;
+    const WrnnRowKey *keys;   // [n_rows] per-row Philox keys replacing (seed, row), or null (no opts.utt_seeds_dev; streams)
     const float *noise1;      // RAW (L, rows, NC) | MOL (L, rows, 10)
     const float *noise2;      // MOL (L, rows)
     const float *x_forced;    // (L, rows) or null
@@ -199,6 +209,7 @@ struct WrnnTeamArgs {
     float *state;
     int32_t noise_mode;
     uint64_t seed;
+    const WrnnRowKey *keys;   // as in WrnnLoopArgs
     const float *noise1;
     const float *noise2;
     const float *x_forced;
@@ -241,6 +252,7 @@ struct WrnnBatchArgs {
     int64_t steps;
     int32_t noise_mode;
     uint64_t seed;
+    const WrnnRowKey *keys;   // as in WrnnLoopArgs; indexed by the row a.order[] maps a slot to
     const float *noise1;
     const float *noise2;
     const float *x_forced;
@@ -299,17 +311,20 @@ hipError_t wrnn_team_gate_leave(int device, hipStream_t s);
 hipError_t wrnn_launch_loss(int mode, const float *y_hat, const void *y, int NC, long n_rows, double *partial, int *bad, float *out,
                             hipStream_t s);
 // rows[r] = {utt, steps, start}; order[] = rows sorted by steps, longest first (stable), when frames != null, else identity;
-// sched[] (n_rows rounded up to n_teams entries) = the same order dealt to n_teams teams in snake order, -1 where empty
+// sched[] (n_rows rounded up to n_teams entries) = the same order dealt to n_teams teams in snake order, -1 where empty;
+// seeds (n_rows uint64, device; unbatched calls) != null: keys[r] = {seeds[r], 0}
 hipError_t wrnn_launch_rows(WrnnRow *rows, int32_t *order, int32_t *sched, int n_rows, int n_teams, int batched, long stride, long steps,
-                            const int32_t *frames, int T, int hop, hipStream_t s);
+                            const int32_t *frames, int T, int hop, WrnnRowKey *keys, const uint64_t *seeds, hipStream_t s);
 // frames (B int32, device) or null: records fi >= frames[b] of utterance b are written as copies of record T (zero conditioning)
 hipError_t wrnn_launch_pack_records32(const float *CM, const float *CA, const float *VM, const float *VA, const float *C2,
                                       const float *C3, const float *C4, float *rec, int B, int T, int P, const int32_t *frames,
                                       hipStream_t s);
 // folds of several utterances: rows[fold0[b] + i] = {b, steps, i * stride}, identity order / sched, fold0[B + 1] (clamped to
-// rows_total); a fold count that differs from rows_total sets *err = WRNN_DEVERR_ROWS and touches no row outside [0, rows_total)
+// rows_total); a fold count that differs from rows_total sets *err = WRNN_DEVERR_ROWS and touches no row outside [0, rows_total);
+// seeds (B uint64, device) != null: keys[fold0[b] + i] = {seeds[b], i}
 hipError_t wrnn_launch_rows_folded(WrnnRow *rows, int32_t *order, int32_t *sched, int32_t *fold0, unsigned *err, const int32_t *frames,
-                                   int B, int rows_total, int n_teams, long target, long overlap, int hop, int T, hipStream_t s);
+                                   int B, int rows_total, int n_teams, long target, long overlap, int hop, int T, WrnnRowKey *keys,
+                                   const uint64_t *seeds, hipStream_t s);
 // TEAM2 reads C2 / C3 / C4 (B, T + 1, .) by frame: entries frames[b] <= f < T of utterance b become copies of entry T
 hipError_t wrnn_launch_mask_frame_tables(float *C2, float *C3, float *C4, const int32_t *frames, int B, int T, hipStream_t s);
 hipError_t wrnn_launch_loop_team2(const WrnnTeamArgs &a, hipStream_t s);

@@ -148,6 +148,21 @@ def fold_plan_many(total_lens, overlap: int, n_teams: int = 8, mode: str = 'RAW'
 _CU_COUNT = {}   # torch.cuda.get_device_properties costs ~0.1 s on its first call (amdsmi): asked once per device
 
 
+def request_seeds(seeds, n_utterances, noise_mode=_cabi.NOISE_PHILOX, seed=None) -> np.ndarray:
+    """Host check of ``seeds=`` (``wrnn_sample_opts.utt_seeds_dev``): a sequence of ``n_utterances`` Python ints, one Philox key per
+    utterance, returned as uint64 (taken mod 2**64).  ``ValueError`` -- raised by the callers before any device work -- when a call-wide
+    ``seed`` is given as well, when the length is wrong, or when the noise does not come from the device RNG (injected / argmax /
+    reference)."""
+    if seed is not None:
+        raise ValueError('seeds (one per utterance) and seed (one for the call) are exclusive: give one of them')
+    if noise_mode not in (_cabi.NOISE_PHILOX, 'philox'):
+        raise ValueError(f"seeds key the device RNG: noise_mode must be 'philox', got {noise_mode!r}")
+    vals = [int(s) for s in seeds]
+    if len(vals) != int(n_utterances):
+        raise ValueError(f'seeds must hold one seed per utterance: expected {int(n_utterances)}, got {len(vals)}')
+    return np.array([v & 0xFFFFFFFFFFFFFFFF for v in vals], dtype=np.uint64)
+
+
 def _device_teams(dev) -> int:
     dev = torch.device(dev)
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
@@ -424,9 +439,9 @@ class WaveRNN(nn.Module):
             self._native.sync_status(torch.cuda.current_stream(dev).cuda_stream)
 
     # ---------------------------------------------------------------- generate
-    def generate_raw(self, mels, batched, target, overlap, *, noise_mode=_cabi.NOISE_PHILOX, seed=0,
+    def generate_raw(self, mels, batched, target, overlap, *, noise_mode=_cabi.NOISE_PHILOX, seed=None,
                      noise1=None, noise2=None, x_forced=None, want_logits=False, kernel=None, x_init=None,
-                     mels_padded=False, frames=None, batch_rows=0, team2_segment=0):
+                     mels_padded=False, frames=None, batch_rows=0, team2_segment=0, seeds=None):
         """Device part of generate() (:183-241).  Returns dict(samples (rows, L) float32 cuda tensor,
         labels (rows, L) int32 cuda tensor, logits or None, rows, steps).
 
@@ -439,11 +454,21 @@ class WaveRNN(nn.Module):
         frames: optional (B,) valid frames per utterance of a ragged, right-zero-padded batch (``wrnn_sample_opts.frames_dev``):
         row b runs frames[b] * hop steps, the rest of its output row is left unwritten (here: zero).
         batch_rows / team2_segment: tuning knobs of the BATCH / TEAM2 kernels (0 = the library's choice).
+        seed (default 0) keys the Philox draws of the whole call by (seed, step, row): a row's draws depend on its place in the batch.
+        seeds (unbatched calls only): B ints instead, one per utterance -- row b draws exactly what a call on utterance b alone with
+        ``seed=seeds[b]`` draws (same kernel), whatever else is in the batch and wherever it stands (``request_seeds``).
         """
         if isinstance(noise_mode, str):
             if noise_mode not in _NOISE_MODES:
                 raise ValueError(f'noise_mode must be one of {sorted(_NOISE_MODES)} or a WRNN_NOISE_* id, got {noise_mode!r}')
             noise_mode = _NOISE_MODES[noise_mode]
+        seeds_np = None
+        if seeds is not None:
+            if batched:
+                raise ValueError('seeds is for unbatched calls (one seed per utterance); a batched call has one utterance: use seed')
+            shape = mels.shape if hasattr(mels, 'shape') else np.shape(mels)
+            seeds_np = request_seeds(seeds, shape[0] if len(shape) else 0, noise_mode, seed)
+        seed = 0 if seed is None else seed
         nat = self.native()
         dev = torch.device('cuda', nat.device)
         with torch.cuda.device(dev):
@@ -467,6 +492,11 @@ class WaveRNN(nn.Module):
                     raise ValueError(f'frames must have shape ({B},), got {tuple(fr_t.shape)}')
                 keep.append(fr_t)
                 fr = fr_t.data_ptr()
+            us = 0
+            if seeds_np is not None:
+                us_t = torch.from_numpy(seeds_np.view(np.int64)).to(dev)   # the bits of the uint64 keys
+                keep.append(us_t)
+                us = us_t.data_ptr()
 
             def to_dev(a, shape):
                 if a is None:
@@ -496,7 +526,7 @@ class WaveRNN(nn.Module):
                              noise_mode=noise_mode, seed=int(seed), noise1_ptr=n1, noise2_ptr=n2, x_forced_ptr=xf,
                              logits_ptr=logits.data_ptr() if logits is not None else 0,
                              kernel=k, x_init_ptr=xi, mels_padded=mels_padded,
-                             frames_ptr=fr, batch_rows=batch_rows, team2_segment=team2_segment)
+                             frames_ptr=fr, batch_rows=batch_rows, team2_segment=team2_segment, utt_seeds_ptr=us)
                 return nat.last_timing()  # synchronises; surfaces device-side errors
             self._launch_with_busy_retry(nat, launch, want_kernel, steps)
             frames_dev = keep[0] if ragged else None
@@ -523,14 +553,17 @@ class WaveRNN(nn.Module):
         if want_kernel == _cabi.KERNEL_AUTO and self.last_timing['kernel'] == _cabi.KERNEL_SIMPLE and not getattr(self, '_slow_warned', False):
             self._warn_slow_path(nat.team_info()[2] or 'the team kernels cannot run on this device', steps)
 
-    def generate_raw_folded(self, mels, frames, target, overlap, *, noise_mode=_cabi.NOISE_PHILOX, seed=0, noise1=None, noise2=None,
-                            kernel=None, batch_rows=0, team2_segment=0, rows_total=None):
+    def generate_raw_folded(self, mels, frames, target, overlap, *, noise_mode=_cabi.NOISE_PHILOX, seed=None, noise1=None, noise2=None,
+                            kernel=None, batch_rows=0, team2_segment=0, rows_total=None, seeds=None):
         """Device part of ``generate_many(batched=True)``: ONE ``wrnn_generate_folded`` call whose rows are the folds of ALL utterances.
         mels (B, n_mels, T), every clip right-zero-padded to T frames; frames (B,) the clips' own frame counts.  Utterance b is cut as
         ``generate_raw(mels[b:b+1, :, :frames[b]], True, target, overlap)`` cuts it and owns rows fold0[b] .. fold0[b + 1] - 1.  Returns
         dict(samples, labels (rows, steps) cuda tensors, fold0 (B + 1,) int32 numpy, rows, steps, frames (cuda int32), B, target, overlap).
-        noise1 / noise2 (injected): (steps, rows, .) over ALL rows; the Philox draws of a row are keyed by its GLOBAL row index
-        fold0[b] + i, so a clip's audio depends on its position in the call.  rows_total: test hook, overrides the planned row count."""
+        noise1 / noise2 (injected): (steps, rows, .) over ALL rows.  Philox: ``seeds`` (B ints, one per utterance) keys fold i of
+        utterance b by (seeds[b], step, i) -- its rows are bit-equal to ``generate_raw(clip b, True, target, overlap, seed=seeds[b])`` on the
+        same kernel and batch_rows, whatever else is in the call; with the call-wide ``seed`` (default 0) a row is keyed by its GLOBAL row
+        index fold0[b] + i, so a clip's audio depends on its position in the call.  rows_total: test hook, overrides the planned row
+        count."""
         if isinstance(noise_mode, str):
             if noise_mode not in _NOISE_MODES:
                 raise ValueError(f'noise_mode must be one of {sorted(_NOISE_MODES)} or a WRNN_NOISE_* id, got {noise_mode!r}')
@@ -538,6 +571,8 @@ class WaveRNN(nn.Module):
         if noise_mode == _NOISE_REFERENCE:
             raise ValueError("noise_mode='reference' replays the reference's own generate(): it has no call that folds several utterances")
         fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+        seeds_np = None if seeds is None else request_seeds(seeds, fr.size, noise_mode, seed)
+        seed = 0 if seed is None else seed
         nat = self.native()
         dev = torch.device('cuda', nat.device)
         with torch.cuda.device(dev):
@@ -553,6 +588,11 @@ class WaveRNN(nn.Module):
             labels = torch.empty((rows, steps), dtype=torch.int32, device=dev)
             fr_t = torch.from_numpy(fr).to(dev)
             keep = []
+            us = 0
+            if seeds_np is not None:
+                us_t = torch.from_numpy(seeds_np.view(np.int64)).to(dev)   # the bits of the uint64 keys
+                keep.append(us_t)
+                us = us_t.data_ptr()
 
             def to_dev(a, shape):
                 if a is None:
@@ -573,7 +613,7 @@ class WaveRNN(nn.Module):
             def launch(k):
                 nat.generate_folded(mels_t.data_ptr(), B, T, fr_t.data_ptr(), rows, target, overlap, labels_ptr=labels.data_ptr(),
                                     samples_ptr=samples.data_ptr(), stream=stream, noise_mode=noise_mode, seed=int(seed), noise1_ptr=n1,
-                                    noise2_ptr=n2, kernel=k, batch_rows=batch_rows, team2_segment=team2_segment)
+                                    noise2_ptr=n2, kernel=k, batch_rows=batch_rows, team2_segment=team2_segment, utt_seeds_ptr=us)
                 return nat.last_timing()  # synchronises; surfaces device-side errors
             self._launch_with_busy_retry(nat, launch, want_kernel, steps)
             del keep
@@ -670,7 +710,8 @@ class WaveRNN(nn.Module):
         self.train()
         return output
 
-    def generate_many(self, mels_list, save_paths=None, mu_law=True, epilogue='host', batched=False, target='auto', overlap=550, **native_opts):
+    def generate_many(self, mels_list, save_paths=None, mu_law=True, epilogue='host', batched=False, target='auto', overlap=550, seeds=None,
+                      **native_opts):
         """Extension for serving loops: several independent utterances of different lengths in ONE device call, so that all
         8 XCD teams of the GPU work (a single unbatched utterance keeps one team = 1/8 of the chip busy; up to 8 utterances
         run on the latency kernel one per team, more on the batch kernel).  ``mels_list``: sequence of (n_mels, T_i) arrays.
@@ -685,10 +726,21 @@ class WaveRNN(nn.Module):
         ``batched=True``: the reference's fold mode (:293-405) for ALL clips in one ``wrnn_generate_folded`` call -- every clip is cut into
         folds of one common ``target`` (an int, or ``'auto'``: ``fold_plan_many``, the target with the lowest predicted loop time for the
         whole queue) and every fold of every clip is one row of the batch kernel, so that short clips fill the chip together.  Element i
-        is what ``generate(mels_i[None], path_i, True, target, overlap, mu_law)`` returns in shape, dtype and length; the noise of a fold is
-        keyed by its row index in the call, so the audio of a clip depends on its position in ``mels_list`` (for one clip: bit-equal to
-        ``generate`` with the same seed).  ``epilogue='device'``: crossfade / unfold / trim / fade-out of all clips in one
-        ``wrnn_epilogue_folded`` launch.  ``noise_mode='reference'`` raises ``ValueError``: the reference has no such call."""
+        is what ``generate(mels_i[None], path_i, True, target, overlap, mu_law)`` returns in shape, dtype and length.
+        ``epilogue='device'``: crossfade / unfold / trim / fade-out of all clips in one ``wrnn_epilogue_folded`` launch.
+        ``noise_mode='reference'`` raises ``ValueError``: the reference has no such call.
+
+        Noise.  ``seeds=None``: ONE call seed (``seed=``, or a draw from the global torch generator) and rows keyed by their index in the
+        call -- the audio of a clip then depends on the other clips of the queue and on its position in ``mels_list``.  ``seeds``: one int
+        per clip (mod 2**64) -- clip i draws what a call on clip i ALONE with ``seed=seeds[i]`` draws, in both modes: a request can be
+        replayed, reordered, queued with others or dealt to another number of GPUs (``generate_sharded`` with
+        ``lambda idx, ms: model.generate_many(ms, seeds=[S[i] for i in idx])``) and sounds the same.  Not covered: ``target='auto'``
+        picks the common fold length from the WHOLE queue, so a folded clip's cut -- and with it its audio -- still depends on the queue
+        unless ``target`` is fixed; and bit-equality to a solo call holds on the same kernel (eight or fewer rows run TEAM2, more run
+        the batch kernel) -- across kernels it is the usual parity up to near-ties of the sampler.  ``ValueError`` before any device work:
+        ``seeds`` with ``seed``, a wrong length, or a ``noise_mode`` other than ``'philox'``."""
+        if seeds is not None:
+            native_opts['seeds'] = request_seeds(seeds, len(mels_list), native_opts.get('noise_mode', _cabi.NOISE_PHILOX), native_opts.get('seed'))
         if batched and native_opts.get('noise_mode') in ('reference', _NOISE_REFERENCE):
             raise ValueError("noise_mode='reference' replays the reference's own generate(): it has no call that folds several utterances")
         if batched and epilogue not in ('host', 'device'):
@@ -707,7 +759,7 @@ class WaveRNN(nn.Module):
         batch = np.zeros((len(arrs), self.feat_dims, tmax), np.float32)
         for i, a in enumerate(arrs):
             batch[i, :, :lens[i]] = a
-        if 'seed' not in native_opts and native_opts.get('noise_mode', _cabi.NOISE_PHILOX) in (_cabi.NOISE_PHILOX, 'philox'):
+        if seeds is None and 'seed' not in native_opts and native_opts.get('noise_mode', _cabi.NOISE_PHILOX) in (_cabi.NOISE_PHILOX, 'philox'):
             native_opts['seed'] = int(torch.randint(0, 2 ** 62, (1,)).item())
         ragged = len(set(lens)) > 1
         if batched:
