@@ -74,6 +74,7 @@ extern "C" {
 #define WRNN_ERR_MISSING_KEY -4 /* state_dict key absent (strict load) */
 #define WRNN_ERR_TIMEOUT -5     /* a bounded device spin gave up */
 #define WRNN_ERR_BUSY -6        /* a team kernel could not get all its workgroups resident (GPU shared with another process) */
+#define WRNN_ERR_UNSUPPORTED -7 /* a valid configuration this build has no kernel for (the mel front end: n_fft != 2048) */
 
 typedef struct wrnn_handle wrnn_handle;
 
@@ -418,6 +419,46 @@ int wrnn_dm_set_kernel(wrnn_dm_handle *h, int32_t kernel);
 int wrnn_dm_sync_status(wrnn_dm_handle *h, void *stream);
 const char *wrnn_dm_last_error(const wrnn_dm_handle *h);
 void wrnn_dm_destroy(wrnn_dm_handle *h);
+
+/* ---- mel front end (added to ABI 9: new entry points only, no existing entry or struct changes, so the number stays): wav -> mel, the input side of wavernn_gen.py's `.wav` branch (:17-20) ----------------------------
+ * melspectrogram(y) = normalize(amp_to_db(mel_basis @ |stft(y)|)) of wavernn/utils/dsp.py:41-43, 50-51, 58-59, 72-81 with the librosa
+ * semantics of the reference's era: center=True with reflect padding of n_fft/2, a periodic Hann window of win_length centred in
+ * n_fft, 1 + n / hop frames, n_fft/2 + 1 bins, the Slaney filterbank (htk=False, fmax = sample_rate/2, rows scaled by
+ * 2 / (f[i+2] - f[i])), 20 log10(max(1e-5, .)) and clip((S - min_level_db) / -min_level_db, 0, 1); ref_level_db is NOT subtracted
+ * (only spectrogram() does that, :66-69).  A front end of its own, not tied to a model handle: it needs no weights.
+ * Supported: n_fft == 2048 (anything else: WRNN_ERR_UNSUPPORTED), 1 <= win_length <= n_fft, hop_length >= 1, 1 <= n_mels <= 128,
+ * 0 <= fmin < sample_rate/2, min_level_db < 0 (else WRNN_ERR_INVALID).  The window, the twiddles and the sparse filterbank are built in
+ * the create entry on the host in float64 and rounded to float32 once; that entry touches no device (a handle can be made and asked for
+ * frame counts and tables on a machine without a GPU), the tables are uploaded by the first launch (one blocking copy; later calls are
+ * asynchronous like the rest of the header). */
+typedef struct wrnn_mel_handle wrnn_mel_handle;
+typedef struct wrnn_mel_config {
+    int32_t sample_rate;  /* 22050 */
+    int32_t n_fft;        /* 2048  */
+    int32_t hop_length;   /* 275   */
+    int32_t win_length;   /* 1100  */
+    int32_t n_mels;       /* 80    */
+    float fmin;           /* 95    */
+    float min_level_db;   /* -100  */
+    int32_t device;       /* HIP device ordinal */
+} wrnn_mel_config;
+int wrnn_mel_create(const wrnn_mel_config *cfg, wrnn_mel_handle **out);
+/* Host only: frames of a clip of n_samples, 1 + n_samples / hop_length; WRNN_ERR_INVALID (< 0) for a clip shorter than n_fft/2 + 1
+ * samples, which cannot be reflect-padded (numpy refuses it too). */
+int64_t wrnn_mel_frames(const wrnn_mel_handle *h, int64_t n_samples);
+/* wav_dev: B float32 clips in one buffer, row stride n_max samples; n_samples_dev: B int32 on the device, the clips' own lengths
+ * (ragged; a value above n_max is read as n_max); mel_out_dev (B, n_mels, T_max) float32 contiguous, the layout the generate entry
+ * consumes.  Frames at or past a clip's own frame count are written as 0 -- the zero conditioning of a right-padded ragged batch --
+ * and so is every frame of a clip too short to pad: the lengths live on the device and the call never waits, so the HOST side checks
+ * them with the frames entry before the launch.  One launch, grid (T_max, B), asynchronous on `stream`. */
+int wrnn_melspectrogram(wrnn_mel_handle *h, const float *wav_dev, int64_t n_max, const int32_t *n_samples_dev, int32_t B, int32_t T_max,
+                        float *mel_out_dev, void *stream);
+/* Host only (tests): copies of the float32 tables the kernel reads.  window[win_length]; twiddle[2 * n_fft] = (cos, -sin) of
+ * 2 pi k / n_fft; rows[3 * n_mels] = (first_bin, n_bins, offset into weights) per filterbank row; weights[*n_weights] = the rows'
+ * non-zero spans, packed.  Any pointer may be NULL (call once for *n_weights, then with buffers). */
+int wrnn_mel_tables(const wrnn_mel_handle *h, float *window, float *twiddle, int32_t *rows, float *weights, int32_t *n_weights);
+const char *wrnn_mel_last_error(const wrnn_mel_handle *h);
+void wrnn_mel_destroy(wrnn_mel_handle *h);
 
 #ifdef __cplusplus
 }

@@ -23,8 +23,8 @@ KERNEL_NAMES = {KERNEL_AUTO: 'auto', KERNEL_SIMPLE: 'simple', KERNEL_TEAM2: 'tea
 KERNEL_IDS = {v: k for k, v in KERNEL_NAMES.items()}
 DTYPE_F32, DTYPE_I64 = 0, 1
 ERR_NAMES = {0: 'WRNN_OK', -1: 'WRNN_ERR_INVALID', -2: 'WRNN_ERR_HIP', -3: 'WRNN_ERR_STATE',
-             -4: 'WRNN_ERR_MISSING_KEY', -5: 'WRNN_ERR_TIMEOUT', -6: 'WRNN_ERR_BUSY'}
-ERR_INVALID, ERR_STATE, ERR_TIMEOUT, ERR_BUSY = -1, -3, -5, -6
+             -4: 'WRNN_ERR_MISSING_KEY', -5: 'WRNN_ERR_TIMEOUT', -6: 'WRNN_ERR_BUSY', -7: 'WRNN_ERR_UNSUPPORTED'}
+ERR_INVALID, ERR_STATE, ERR_TIMEOUT, ERR_BUSY, ERR_UNSUPPORTED = -1, -3, -5, -6, -7
 ABI_VERSION = 9   # WRNN_ABI_VERSION of the include/wavernn_amd.h this binding was written against
 
 # every symbol include/wavernn_amd.h declares (checked by tests/test_cabi_symbols.py)
@@ -35,7 +35,8 @@ EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wr
                     'wrnn_dm_create', 'wrnn_dm_load_weights', 'wrnn_dm_generate', 'wrnn_dm_last_error', 'wrnn_dm_destroy',
                     'wrnn_dm_set_kernel', 'wrnn_dm_sync_status', 'wrnn_team_info', 'wrnn_debug_force_no_teams',
                     'wrnn_stream_open', 'wrnn_stream_push', 'wrnn_stream_sync', 'wrnn_stream_info', 'wrnn_stream_ready_steps',
-                    'wrnn_stream_close', 'wrnn_plan_folded', 'wrnn_generate_folded', 'wrnn_epilogue_folded')
+                    'wrnn_stream_close', 'wrnn_plan_folded', 'wrnn_generate_folded', 'wrnn_epilogue_folded',
+                    'wrnn_mel_create', 'wrnn_mel_frames', 'wrnn_melspectrogram', 'wrnn_mel_tables', 'wrnn_mel_last_error', 'wrnn_mel_destroy')
 
 
 def epilogue_tables(n_classes: int, overlap: int, hop: int):
@@ -94,6 +95,11 @@ class Timing(C.Structure):
                 ('steps', C.c_int64), ('launches', C.c_int32), ('reserved_', C.c_int32)]
 
 
+class MelConfig(C.Structure):
+    _fields_ = [('sample_rate', C.c_int32), ('n_fft', C.c_int32), ('hop_length', C.c_int32), ('win_length', C.c_int32),
+                ('n_mels', C.c_int32), ('fmin', C.c_float), ('min_level_db', C.c_float), ('device', C.c_int32)]
+
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -133,6 +139,9 @@ def load_library() -> C.CDLL:
     got = int(lib.wrnn_abi_version())
     if got != ABI_VERSION:   # the .so is a git-ignored build artefact: a stale one would read the structs at shifted offsets
         raise RuntimeError(f'{LIB_PATH} implements ABI {got}, this binding needs ABI {ABI_VERSION}: rebuild it '
+                           '(`python -c "import __graft_entry__ as g; g.build()"`)')
+    if not hasattr(lib, 'wrnn_melspectrogram'):   # the mel entry points joined ABI 9 without a new number: a build from before them reports 9 too
+        raise RuntimeError(f'{LIB_PATH} implements ABI {got} without the wrnn_mel_* entry points: rebuild it '
                            '(`python -c "import __graft_entry__ as g; g.build()"`)')
     vp = C.c_void_p
     lib.wrnn_create.argtypes = [C.POINTER(Config), C.POINTER(vp)]
@@ -203,6 +212,18 @@ def load_library() -> C.CDLL:
     lib.wrnn_generate_folded.restype = C.c_int
     lib.wrnn_epilogue_folded.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_int64, vp]
     lib.wrnn_epilogue_folded.restype = C.c_int
+    lib.wrnn_mel_create.argtypes = [C.POINTER(MelConfig), C.POINTER(vp)]
+    lib.wrnn_mel_create.restype = C.c_int
+    lib.wrnn_mel_frames.argtypes = [vp, C.c_int64]
+    lib.wrnn_mel_frames.restype = C.c_int64
+    lib.wrnn_melspectrogram.argtypes = [vp, vp, C.c_int64, vp, C.c_int32, C.c_int32, vp, vp]
+    lib.wrnn_melspectrogram.restype = C.c_int
+    lib.wrnn_mel_tables.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_int32)]
+    lib.wrnn_mel_tables.restype = C.c_int
+    lib.wrnn_mel_last_error.argtypes = [vp]
+    lib.wrnn_mel_last_error.restype = C.c_char_p
+    lib.wrnn_mel_destroy.argtypes = [vp]
+    lib.wrnn_mel_destroy.restype = None
     lib.wrnn_dm_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
     lib.wrnn_dm_create.restype = C.c_int
     lib.wrnn_dm_load_weights.argtypes = [vp, C.POINTER(TensorDesc), C.c_int32]
@@ -524,3 +545,57 @@ class NativeDeepmind:
 
     def set_kernel(self, kernel: int):
         self._check(self.lib.wrnn_dm_set_kernel(self._h, int(kernel)))
+
+
+class NativeMel:
+    """Owner of one ``wrnn_mel_handle`` (the wav -> mel front end; no weights).  Creating it touches no device; a configuration the
+    library refuses raises ``ValueError`` (n_fft other than 2048: WRNN_ERR_UNSUPPORTED; the rest: WRNN_ERR_INVALID)."""
+
+    def __init__(self, *, sample_rate, n_fft, hop_length, win_length, n_mels, fmin, min_level_db, device: int = 0):
+        self.lib = load_library()
+        cfg = MelConfig(int(sample_rate), int(n_fft), int(hop_length), int(win_length), int(n_mels), float(fmin), float(min_level_db), int(device))
+        self.cfg = cfg
+        self.device = int(device)
+        self._h = C.c_void_p()
+        rc = self.lib.wrnn_mel_create(C.byref(cfg), C.byref(self._h))
+        if rc != 0:
+            msg = self.lib.wrnn_mel_last_error(self._h).decode() if self._h else 'wrnn_mel_create failed'
+            self.close()
+            raise ValueError(f'{ERR_NAMES.get(rc, rc)}: {msg}')
+
+    def _check(self, rc: int):
+        if rc != 0:
+            raise WrnnError(rc, self.lib.wrnn_mel_last_error(self._h).decode())
+
+    def frames(self, n_samples: int) -> int:
+        """Host-only ``wrnn_mel_frames``: 1 + n // hop; ``ValueError`` for a clip too short to reflect-pad."""
+        t = int(self.lib.wrnn_mel_frames(self._h, int(n_samples)))
+        if t < 0:
+            raise ValueError(f'a clip of {int(n_samples)} samples cannot be reflect-padded by n_fft/2 = {self.cfg.n_fft // 2}: '
+                             f'at least {self.cfg.n_fft // 2 + 1} samples are needed')
+        return t
+
+    def tables(self) -> dict:
+        """The float32 tables the kernel reads (``wrnn_mel_tables``): window, twiddle (n_fft, 2), rows (n_mels, 3), weights."""
+        nw = C.c_int32()
+        self._check(self.lib.wrnn_mel_tables(self._h, None, None, None, None, C.byref(nw)))
+        window = np.empty(self.cfg.win_length, np.float32)
+        twiddle = np.empty((self.cfg.n_fft, 2), np.float32)
+        rows = np.empty((self.cfg.n_mels, 3), np.int32)
+        weights = np.empty(nw.value, np.float32)
+        self._check(self.lib.wrnn_mel_tables(self._h, window.ctypes.data, twiddle.ctypes.data, rows.ctypes.data, weights.ctypes.data, None))
+        return dict(window=window, twiddle=twiddle, rows=rows, weights=weights)
+
+    def melspectrogram(self, wav_ptr: int, n_max: int, n_samples_ptr: int, B: int, T_max: int, out_ptr: int, stream: int):
+        self._check(self.lib.wrnn_melspectrogram(self._h, wav_ptr, int(n_max), n_samples_ptr, int(B), int(T_max), out_ptr, stream or None))
+
+    def close(self):
+        if getattr(self, '_h', None):
+            self.lib.wrnn_mel_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

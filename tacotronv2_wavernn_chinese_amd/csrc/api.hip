@@ -11,6 +11,7 @@
 #include <map>
 #include <mutex>
 
+#include "mel_internal.h"
 #include "wrnn_internal.h"
 
 namespace {
@@ -838,6 +839,116 @@ int wrnn_phase_cycles(wrnn_handle *h, double *out) {
     const double n = h->prof_div > 0 ? h->prof_div : 1.0;   // steps x rows (or batches) team 0 ran
     for (int i = 0; i < 8 * WRNN_PROF_SLOTS; ++i) out[i] = (double)pr[i] / n;
     return WRNN_OK;
+}
+
+}  // extern "C"
+
+// ---- mel front end: a handle of its own, no weights ---------------------------------------------------------------
+
+struct wrnn_mel_handle {
+    wrnn_mel_config cfg{};
+    WrnnMelTables tab;
+    void *dev = nullptr;          // one allocation: window | twiddle | rows | weights, made by the first wrnn_melspectrogram
+    size_t o_tw = 0, o_rows = 0, o_w = 0;
+    std::string err;
+};
+
+namespace {
+int mel_fail(wrnn_mel_handle *h, int code, const char *fmt, ...) {
+    char buf[400];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    if (h) h->err = buf;
+    return code;
+}
+#define MEL_TRY(h, expr)                                                                                   \
+    do {                                                                                                   \
+        hipError_t e__ = (expr);                                                                           \
+        if (e__ != hipSuccess) return mel_fail((h), WRNN_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e__)); \
+    } while (0)
+}  // namespace
+
+extern "C" {
+
+int wrnn_mel_create(const wrnn_mel_config *cfg, wrnn_mel_handle **out) {
+    if (!cfg || !out) return WRNN_ERR_INVALID;
+    wrnn_mel_handle *h = new wrnn_mel_handle();
+    *out = h;
+    h->cfg = *cfg;
+    if (cfg->n_fft != WRNN_MEL_NFFT) return mel_fail(h, WRNN_ERR_UNSUPPORTED, "n_fft = %d: the front end is built for n_fft = %d only", cfg->n_fft, WRNN_MEL_NFFT);
+    if (cfg->hop_length < 1 || !(cfg->min_level_db < 0.0f) || cfg->device < 0)
+        return mel_fail(h, WRNN_ERR_INVALID, "bad configuration: hop_length >= 1, min_level_db < 0, device >= 0");
+    if (!wrnn_mel_build_tables(cfg->sample_rate, cfg->win_length, cfg->n_mels, (double)cfg->fmin, &h->tab))
+        return mel_fail(h, WRNN_ERR_INVALID, "bad configuration: 1 <= win_length <= n_fft, 1 <= n_mels <= %d, 0 <= fmin < sample_rate / 2", WRNN_MEL_MAX_MELS);
+    return WRNN_OK;
+}
+
+int64_t wrnn_mel_frames(const wrnn_mel_handle *h, int64_t n_samples) {
+    if (!h || h->tab.window.empty() || n_samples < h->cfg.n_fft / 2 + 1) return WRNN_ERR_INVALID;
+    return 1 + n_samples / h->cfg.hop_length;
+}
+
+int wrnn_mel_tables(const wrnn_mel_handle *h, float *window, float *twiddle, int32_t *rows, float *weights, int32_t *n_weights) {
+    if (!h || h->tab.window.empty()) return WRNN_ERR_INVALID;
+    const WrnnMelTables &t = h->tab;
+    if (window) std::copy(t.window.begin(), t.window.end(), window);
+    if (twiddle) std::copy(t.twiddle.begin(), t.twiddle.end(), twiddle);
+    if (rows) std::copy(t.rows.begin(), t.rows.end(), rows);
+    if (weights) std::copy(t.weights.begin(), t.weights.end(), weights);
+    if (n_weights) *n_weights = (int32_t)t.weights.size();
+    return WRNN_OK;
+}
+
+int wrnn_melspectrogram(wrnn_mel_handle *h, const float *wav_dev, int64_t n_max, const int32_t *n_samples_dev, int32_t B, int32_t T_max,
+                        float *mel_out_dev, void *stream) {
+    if (!h) return WRNN_ERR_INVALID;
+    if (h->tab.window.empty()) return mel_fail(h, WRNN_ERR_STATE, "the handle's configuration was refused by wrnn_mel_create");
+    if (!wav_dev || !n_samples_dev || !mel_out_dev || n_max < 1 || B < 1 || B > 65535 || T_max < 1)
+        return mel_fail(h, WRNN_ERR_INVALID, "bad arguments: device pointers, n_max >= 1, 1 <= B <= 65535, T_max >= 1");
+    MEL_TRY(h, hipSetDevice(h->cfg.device));
+    const WrnnMelTables &t = h->tab;
+    if (!h->dev) {
+        auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        h->o_tw = up(t.window.size() * 4);
+        h->o_rows = h->o_tw + up(t.twiddle.size() * 4);
+        h->o_w = h->o_rows + up(t.rows.size() * 4);
+        const size_t total = h->o_w + up(t.weights.size() * 4);
+        std::vector<char> img(total, 0);
+        memcpy(img.data(), t.window.data(), t.window.size() * 4);
+        memcpy(img.data() + h->o_tw, t.twiddle.data(), t.twiddle.size() * 4);
+        memcpy(img.data() + h->o_rows, t.rows.data(), t.rows.size() * 4);
+        memcpy(img.data() + h->o_w, t.weights.data(), t.weights.size() * 4);
+        void *d = nullptr;
+        MEL_TRY(h, hipMalloc(&d, total));
+        hipError_t e = hipMemcpy(d, img.data(), total, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            return mel_fail(h, WRNN_ERR_HIP, "uploading the front-end tables: %s", hipGetErrorString(e));
+        }
+        h->dev = d;
+    }
+    WrnnMelArgs a{};
+    const char *d = (const char *)h->dev;
+    a.wav = wav_dev; a.n_samples = n_samples_dev; a.out = mel_out_dev;
+    a.window = (const float *)d; a.twiddle = (const float2 *)(d + h->o_tw);
+    a.rows = (const int32_t *)(d + h->o_rows); a.weights = (const float *)(d + h->o_w);
+    a.n_max = n_max; a.T_max = T_max; a.n_mels = h->cfg.n_mels; a.hop = h->cfg.hop_length; a.win_length = h->cfg.win_length;
+    a.min_level_db = h->cfg.min_level_db;
+    MEL_TRY(h, wrnn_launch_melspec(a, B, (hipStream_t)stream));
+    return WRNN_OK;
+}
+
+const char *wrnn_mel_last_error(const wrnn_mel_handle *h) { return h ? h->err.c_str() : "null handle"; }
+
+void wrnn_mel_destroy(wrnn_mel_handle *h) {
+    if (!h) return;
+    if (h->dev) {
+        (void)hipSetDevice(h->cfg.device);
+        (void)hipFree(h->dev);
+    }
+    delete h;
 }
 
 }  // extern "C"

@@ -1,0 +1,180 @@
+// The mel front end: melspectrogram(y) = normalize(amp_to_db(mel_basis @ |stft(y)|)) of wavernn/utils/dsp.py:72-81 with the
+// librosa semantics of the reference's era (center=True reflect padding, periodic Hann of win_length centred in n_fft, Slaney
+// filterbank).  One workgroup of 256 threads per frame, grid (T_max, B): the frame's non-zero taps are gathered straight from the
+// clip with the reflect index, the 2048 real points run as a 1024-point complex radix-4 transform in LDS plus the split pass,
+// the magnitudes stay in LDS and the sparse filterbank, dB and normalisation finish the column.  Nothing crosses workgroups.
+#include <cmath>
+
+#include "mel_internal.h"
+
+namespace {
+
+constexpr int NC = WRNN_MEL_NFFT / 2;   // complex points
+
+__device__ inline float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+
+// base-4 digit reversal of a 10-bit index: bit reversal, then the two bits of every digit swapped back
+__device__ inline int rev4(int k) {
+    const unsigned r = __brev((unsigned)k) >> 22;
+    return (int)(((r & 0x2AAu) >> 1) | ((r & 0x155u) << 1));
+}
+
+__global__ void __launch_bounds__(WRNN_MEL_THREADS) melspec_kernel(WrnnMelArgs a) {
+    __shared__ float2 z[NC];          // 8 KiB: the transform, in place
+    __shared__ float mag[NC + 1];     // 4 KiB + 4 B: |X[k]|, k = 0 .. n_fft/2
+    const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    long n = a.n_samples[b];
+    if (n > a.n_max) n = a.n_max;
+    // a clip that cannot be reflect-padded has no frames (the host side refuses it before the launch)
+    const long T_b = n >= NC + 1 ? 1 + n / a.hop : 0;
+    float *out = a.out + (long)b * a.n_mels * a.T_max + t;
+    if (t >= T_b) {                   // workgroup-uniform: past the clip's own end, the zero conditioning of a ragged batch
+        for (int m = tid; m < a.n_mels; m += WRNN_MEL_THREADS) out[(long)m * a.T_max] = 0.0f;
+        return;
+    }
+    const float *x = a.wav + (long)b * a.n_max;
+    const int off = (WRNN_MEL_NFFT - a.win_length) / 2;
+    const long j0 = (long)t * a.hop - NC;          // clip index of frame sample 0
+    // z[k] = x[2k] + i x[2k + 1] of the windowed frame, stored digit-reversed for the in-place decimation-in-time passes
+    for (int k = tid; k < NC; k += WRNN_MEL_THREADS) {
+        float v[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int i = 2 * k + e - off;         // window tap
+            v[e] = 0.0f;
+            if (i >= 0 && i < a.win_length) {
+                long j = j0 + 2 * k + e;
+                if (j < 0) j = -j;
+                else if (j >= n) j = 2 * (n - 1) - j;
+                v[e] = x[j] * a.window[i];
+            }
+        }
+        z[rev4(k)] = make_float2(v[0], v[1]);
+    }
+    // five radix-4 passes, one butterfly per thread and pass; W_4 = -i
+#pragma unroll
+    for (int s = 0; s < 5; ++s) {
+        __syncthreads();
+        const int q = 1 << (2 * s);
+        const int pos = tid & (q - 1), base = ((tid >> (2 * s)) << (2 * s + 2)) + pos;
+        float2 a0 = z[base], a1 = z[base + q], a2 = z[base + 2 * q], a3 = z[base + 3 * q];
+        if (s > 0) {
+            const int ts = pos * (512 >> (2 * s));   // W_L^pos as an index into the n_fft-point table, L = 4 q
+            a1 = cmul(a1, a.twiddle[ts]);
+            a2 = cmul(a2, a.twiddle[2 * ts]);
+            a3 = cmul(a3, a.twiddle[3 * ts]);
+        }
+        const float2 s02 = make_float2(a0.x + a2.x, a0.y + a2.y), d02 = make_float2(a0.x - a2.x, a0.y - a2.y);
+        const float2 s13 = make_float2(a1.x + a3.x, a1.y + a3.y), d13 = make_float2(a1.x - a3.x, a1.y - a3.y);
+        z[base] = make_float2(s02.x + s13.x, s02.y + s13.y);
+        z[base + q] = make_float2(d02.x + d13.y, d02.y - d13.x);       // d02 - i d13
+        z[base + 2 * q] = make_float2(s02.x - s13.x, s02.y - s13.y);
+        z[base + 3 * q] = make_float2(d02.x - d13.y, d02.y + d13.x);   // d02 + i d13
+    }
+    __syncthreads();
+    // split pass: X[k] = E[k] + W^k O[k], X[NC - k] = conj(E[k] - W^k O[k]); only the magnitudes are kept
+    for (int k = tid; k <= NC / 2; k += WRNN_MEL_THREADS) {
+        if (k == 0) {
+            const float2 z0 = z[0];
+            mag[0] = fabsf(z0.x + z0.y);
+            mag[NC] = fabsf(z0.x - z0.y);
+        } else {
+            const float2 zk = z[k], zn = z[NC - k];
+            const float2 E = make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y));
+            const float2 O = make_float2(0.5f * (zk.y + zn.y), -0.5f * (zk.x - zn.x));
+            const float2 WO = cmul(a.twiddle[k], O);
+            const float pr = E.x + WO.x, pi = E.y + WO.y, mr = E.x - WO.x, mi = E.y - WO.y;
+            mag[k] = sqrtf(pr * pr + pi * pi);
+            mag[NC - k] = sqrtf(mr * mr + mi * mi);
+        }
+    }
+    __syncthreads();
+    // sparse filterbank: four lanes per mel row, then amp_to_db and normalize
+    for (int m0 = 0; m0 < a.n_mels; m0 += WRNN_MEL_THREADS / 4) {
+        const int m = m0 + (tid >> 2), sub = tid & 3;
+        float acc = 0.0f;
+        if (m < a.n_mels) {
+            const int first = a.rows[3 * m], nb = a.rows[3 * m + 1];
+            const float *w = a.weights + a.rows[3 * m + 2];
+            for (int i = sub; i < nb; i += 4) acc += w[i] * mag[first + i];
+        }
+        acc += __shfl_xor(acc, 1);
+        acc += __shfl_xor(acc, 2);
+        if (m < a.n_mels && sub == 0) {
+            // 20 log10(1e-5) is -100 exactly; log10f of the float nearest to 1e-5 need not round to -5
+            const float S = acc > 1e-5f ? 20.0f * log10f(acc) : -100.0f;
+            const float v = (S - a.min_level_db) / -a.min_level_db;
+            out[(long)m * a.T_max] = fminf(fmaxf(v, 0.0f), 1.0f);
+        }
+    }
+}
+
+// np.linspace(start, stop, num): arange * step + start, last point set to stop
+std::vector<double> linspace(double start, double stop, int num) {
+    std::vector<double> y(num);
+    const double step = (stop - start) / (double)(num - 1);
+    for (int i = 0; i < num; ++i) y[i] = (double)i * step + start;
+    y[num - 1] = stop;
+    return y;
+}
+
+// Slaney mel scale (librosa htk=False): linear below 1 kHz, 200/3 Hz per mel; log above, 27 mels per factor 6.4
+const double F_SP = 200.0 / 3.0, MIN_LOG_HZ = 1000.0;
+double hz_to_mel(double f) {
+    const double min_log_mel = MIN_LOG_HZ / F_SP, logstep = std::log(6.4) / 27.0;
+    return f >= MIN_LOG_HZ ? min_log_mel + std::log(f / MIN_LOG_HZ) / logstep : f / F_SP;
+}
+double mel_to_hz(double m) {
+    const double min_log_mel = MIN_LOG_HZ / F_SP, logstep = std::log(6.4) / 27.0;
+    return m >= min_log_mel ? MIN_LOG_HZ * std::exp(logstep * (m - min_log_mel)) : F_SP * m;
+}
+
+}  // namespace
+
+bool wrnn_mel_build_tables(int sample_rate, int win_length, int n_mels, double fmin, WrnnMelTables *out) {
+    const int N = WRNN_MEL_NFFT;
+    const double fmax = 0.5 * (double)sample_rate;
+    if (sample_rate < 1 || win_length < 1 || win_length > N || n_mels < 1 || n_mels > WRNN_MEL_MAX_MELS || !(fmin >= 0.0) || !(fmin < fmax))
+        return false;
+    // scipy.signal.get_window('hann', win_length, fftbins=True): the symmetric window of win_length + 1 points without its last one
+    out->window.resize(win_length);
+    const double pi = 3.141592653589793;
+    const double wstep = (pi - (-pi)) / (double)win_length;
+    for (int i = 0; i < win_length; ++i) out->window[i] = (float)(0.5 + 0.5 * std::cos((double)i * wstep + (-pi)));
+    out->twiddle.resize(2 * (size_t)N);
+    for (int k = 0; k < N; ++k) {
+        const double ang = 2.0 * pi * (double)k / (double)N;
+        out->twiddle[2 * k] = (float)std::cos(ang);
+        out->twiddle[2 * k + 1] = (float)-std::sin(ang);
+    }
+    // librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax = sr / 2, htk=False, norm=1)
+    const std::vector<double> fftfreqs = linspace(0.0, fmax, 1 + N / 2);
+    std::vector<double> mel_f = linspace(hz_to_mel(fmin), hz_to_mel(fmax), n_mels + 2);
+    for (double &m : mel_f) m = mel_to_hz(m);
+    out->rows.assign(3 * (size_t)n_mels, 0);
+    out->weights.clear();
+    for (int i = 0; i < n_mels; ++i) {
+        const double fd0 = mel_f[i + 1] - mel_f[i], fd1 = mel_f[i + 2] - mel_f[i + 1], enorm = 2.0 / (mel_f[i + 2] - mel_f[i]);
+        int first = -1, last = -1;
+        std::vector<float> row(1 + N / 2, 0.0f);
+        for (int k = 0; k <= N / 2; ++k) {
+            const double lower = -(mel_f[i] - fftfreqs[k]) / fd0, upper = (mel_f[i + 2] - fftfreqs[k]) / fd1;
+            const double w = std::fmax(0.0, std::fmin(lower, upper)) * enorm;
+            row[k] = (float)w;
+            if (row[k] != 0.0f) {
+                if (first < 0) first = k;
+                last = k;
+            }
+        }
+        out->rows[3 * i] = first < 0 ? 0 : first;
+        out->rows[3 * i + 1] = first < 0 ? 0 : last - first + 1;
+        out->rows[3 * i + 2] = (int32_t)out->weights.size();
+        if (first >= 0) out->weights.insert(out->weights.end(), row.begin() + first, row.begin() + last + 1);
+    }
+    return true;
+}
+
+hipError_t wrnn_launch_melspec(const WrnnMelArgs &a, int B, hipStream_t s) {
+    hipLaunchKernelGGL(melspec_kernel, dim3((unsigned)a.T_max, (unsigned)B), dim3(WRNN_MEL_THREADS), 0, s, a);
+    return hipGetLastError();
+}

@@ -4,6 +4,11 @@ sample_rate = 22050
 num_mels = 80
 hop_length = 275
 bits = 10
+# the wav -> mel front end (wavernn_hparams.py:19-25)
+n_fft = 2048
+win_length = 1100
+fmin = 95
+min_level_db = -100
 mu_law = True
 
 voc_model_id = 'wavernn'

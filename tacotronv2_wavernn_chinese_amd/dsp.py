@@ -2,7 +2,8 @@
 
 Mirror of the subset of ``wavernn/utils/dsp.py`` the mel->wav path touches:
 ``label_2_float`` (:8-9), ``save_wav`` (:22-23), ``decode_mu_law`` (:98-103).
-Feature extraction (mel/STFT/Griffin-Lim) is out of scope.
+``load_wav`` (:18-19) and ``melspectrogram`` (:72-81) live in ``frontend.py``: the mel is built on the device (``csrc/melspec.hip``).
+``spectrogram``, pre-emphasis and Griffin-Lim are not mirrored.
 """
 from __future__ import annotations
 

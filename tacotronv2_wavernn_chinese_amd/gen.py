@@ -8,8 +8,12 @@ handed to ``model.generate``; the output file name pattern is the reference's (:
 Deliberate differences: the reference hard-overrides ``batched = False`` and
 ``device = cpu`` after parsing its flags (:76-77, :93); here ``--batched`` is honoured and the model
 runs on the MI355X.  Extensions: ``--target auto|per_xcd``, ``--noise reference [--seed N]``, ``--stream-frames N`` (streaming generation)
-(the reference's own noise stream: ``vocoder.reference_noise``).  The reference's ``.wav`` input branch is broken (undefined ``file_name``, :18-20)
-and needs librosa feature extraction, which is out of scope: it raises ``ValueError`` here.
+(the reference's own noise stream: ``vocoder.reference_noise``).
+
+The ``.wav`` branch (:17-20) does what the reference's intends: ``load_wav``, the input saved as ``__{idx}__{k}k_steps_target.wav`` (the
+reference names an undefined ``file_name`` there; ``idx`` is the stem it computes at :38), then the mel of the clip -- built on the device by
+``frontend.MelFrontEnd`` (``csrc/melspec.hip``) instead of librosa -- takes the same path as a ``.npy`` mel, ``--stream-frames`` included.  A file
+at another sample rate raises ``ValueError`` (no resampler is built in).
 """
 from __future__ import annotations
 
@@ -21,6 +25,7 @@ import numpy as np
 import torch
 
 from .dsp import save_wav
+from .frontend import load_wav
 from .hparams import hparams as hp
 from .vocoder import WaveRNN
 
@@ -35,12 +40,17 @@ def gen_from_file(model: WaveRNN, load_path, save_path, batched, target, overlap
         _max, _min = np.max(mel), np.min(mel)
         if _max >= 1.01 or _min <= -0.01:
             raise ValueError(f'Expected spectrogram range in [0,1] but was instead [{_min}, {_max}]')
+        mel = torch.tensor(mel).unsqueeze(0)
     elif ".wav" in load_path:
-        raise ValueError('wav -> mel feature extraction is outside the mel->wav path; pass a (T, n_mels) .npy mel')
+        if not os.path.isfile(load_path):   # an input check like the ones above, not an OSError from inside the wav reader
+            raise ValueError(f'{load_path}: no such wav file')
+        wav = load_wav(load_path, hp.sample_rate)
+        idx = load_path.split('/')[-1].strip().split('.')[0]
+        save_wav(wav, os.path.join(str(save_path), f'__{idx}__{k}k_steps_target.wav'), hp.sample_rate)
+        mel = model.mel_front_end().melspectrogram(wav, device=torch.device('cuda', model._device_index()))   # (1, n_mels, T) on the device
     else:
         raise ValueError(f"Expected an extension of .wav or .npy, but got {os.path.splitext(load_path)[1]}!")
 
-    mel = torch.tensor(mel).unsqueeze(0)
     if stream_frames:
         return _gen_streamed(model, mel, load_path, save_path, int(stream_frames), generate_opts.get('noise_mode', 'philox'))
     batch_str = f'gen_batched_target{target}_overlap{overlap}' if batched else 'gen_NOT_BATCHED'
@@ -105,7 +115,7 @@ def main(argv=None):
                         help="[int] number of samples in each batch index ('auto': the fold length with the lowest predicted latency on this GPU; "
                              "'per_xcd': one fold per XCD)")
     parser.add_argument('--overlap', '-o', type=int, help='[int] number of crossover samples')
-    parser.add_argument('--file', '-f', type=str, help='[string/path] (T, n_mels) .npy mel to vocode')
+    parser.add_argument('--file', '-f', type=str, help='[string/path] (T, n_mels) .npy mel, or a .wav at the model sample rate, to vocode')
     parser.add_argument('--voc_weights', '-w', type=str, help='[string/path] Load in different WaveRNN weights')
     parser.add_argument('--gta', '-g', dest='gta', action='store_true', help='Generate from GTA testset')
     parser.add_argument('--force_cpu', '-c', action='store_true',

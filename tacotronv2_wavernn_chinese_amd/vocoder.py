@@ -710,8 +710,32 @@ class WaveRNN(nn.Module):
         self.train()
         return output
 
-    def generate_many(self, mels_list, save_paths=None, mu_law=True, epilogue='host', batched=False, target='auto', overlap=550, seeds=None,
-                      **native_opts):
+    def mel_front_end(self, front_end=None):
+        """The wav -> mel front end of this model (``frontend.MelFrontEnd``): the model's own ``sample_rate``, ``hop_length`` and
+        ``feat_dims``, the remaining parameters (``n_fft``, ``win_length``, ``fmin``, ``min_level_db``) from the configured hparams where they
+        set them, else the reference's defaults.  ``front_end``: use this one instead (its mel must have ``feat_dims`` channels)."""
+        from .frontend import MelFrontEnd
+        if front_end is None:
+            front_end = getattr(self, '_mel_front_end', None)
+            if front_end is None:
+                from .hparams import hparams as hp
+                front_end = MelFrontEnd(hp, sample_rate=self.sample_rate, hop_length=self.hop_length, n_mels=self.feat_dims)
+                self._mel_front_end = front_end
+        if front_end.n_mels != self.feat_dims or front_end.hop_length != self.hop_length:
+            raise ValueError(f'the front end makes {front_end.n_mels} mel channels at hop {front_end.hop_length}, the model needs '
+                             f'{self.feat_dims} at hop {self.hop_length}')
+        return front_end
+
+    def generate_from_wav(self, wav, save_path: Union[str, Path], batched, target, overlap, mu_law, front_end=None, **generate_opts):
+        """Copy-synthesis, the ``.wav`` branch of ``wavernn_gen.py:17-20``: the mel of ``wav`` (1-D samples in [-1, 1] at the model's sample
+        rate) is built on the device (``mel_front_end``) and handed to ``generate`` as a device tensor, without a host round trip.  Returns
+        what ``generate`` returns for that mel: ``(T - 1) * hop`` samples, ``T = 1 + len(wav) // hop``."""
+        fe = self.mel_front_end(front_end)
+        mel = fe.melspectrogram(wav, device=torch.device('cuda', self._device_index()))
+        return self.generate(mel, save_path, batched, target, overlap, mu_law, **generate_opts)
+
+    def generate_many(self, mels_list=None, save_paths=None, mu_law=True, epilogue='host', batched=False, target='auto', overlap=550, seeds=None,
+                      wavs=None, front_end=None, **native_opts):
         """Extension for serving loops: several independent utterances of different lengths in ONE device call, so that all
         8 XCD teams of the GPU work (a single unbatched utterance keeps one team = 1/8 of the chip busy; up to 8 utterances
         run on the latency kernel one per team, more on the batch kernel).  ``mels_list``: sequence of (n_mels, T_i) arrays.
@@ -738,27 +762,44 @@ class WaveRNN(nn.Module):
         picks the common fold length from the WHOLE queue, so a folded clip's cut -- and with it its audio -- still depends on the queue
         unless ``target`` is fixed; and bit-equality to a solo call holds on the same kernel (eight or fewer rows run TEAM2, more run
         the batch kernel) -- across kernels it is the usual parity up to near-ties of the sampler.  ``ValueError`` before any device work:
-        ``seeds`` with ``seed``, a wrong length, or a ``noise_mode`` other than ``'philox'``."""
+        ``seeds`` with ``seed``, a wrong length, or a ``noise_mode`` other than ``'philox'``.
+
+        ``wavs=`` in place of ``mels_list``: a list of 1-D sample arrays; their mels are built by ONE ragged launch of the device front end
+        (``mel_front_end``; clip i has ``1 + len(wavs[i]) // hop`` frames) and stay on the device.  Everything else is as for the same
+        mels given as ``mels_list``."""
+        if (mels_list is None) == (wavs is None):
+            raise ValueError('give either mels_list or wavs')
+        n_req = len(mels_list) if wavs is None else len(wavs)
         if seeds is not None:
-            native_opts['seeds'] = request_seeds(seeds, len(mels_list), native_opts.get('noise_mode', _cabi.NOISE_PHILOX), native_opts.get('seed'))
+            native_opts['seeds'] = request_seeds(seeds, n_req, native_opts.get('noise_mode', _cabi.NOISE_PHILOX), native_opts.get('seed'))
         if batched and native_opts.get('noise_mode') in ('reference', _NOISE_REFERENCE):
             raise ValueError("noise_mode='reference' replays the reference's own generate(): it has no call that folds several utterances")
         if batched and epilogue not in ('host', 'device'):
             raise ValueError(f"epilogue must be 'host' or 'device', got {epilogue!r}")
         self.eval()
         mu_law = mu_law if self.mode == 'RAW' else False
-        arrs = [np.asarray(torch.as_tensor(m).detach().cpu().numpy(), dtype=np.float32) for m in mels_list]
-        if not arrs or any(a.ndim != 2 or a.shape[0] != self.feat_dims for a in arrs):
-            raise ValueError(f'expected a non-empty sequence of (n_mels={self.feat_dims}, T_i) arrays')
-        lens = [a.shape[1] for a in arrs]
+        if wavs is not None:
+            fe = self.mel_front_end(front_end)
+            if not len(wavs):
+                raise ValueError('expected a non-empty sequence of clips')
+            lens = [fe.frames(int(np.shape(w)[0])) for w in wavs]
+            arrs = lens   # one entry per clip; the mels themselves are made on the device below
+        else:
+            arrs = [np.asarray(torch.as_tensor(m).detach().cpu().numpy(), dtype=np.float32) for m in mels_list]
+            if not arrs or any(a.ndim != 2 or a.shape[0] != self.feat_dims for a in arrs):
+                raise ValueError(f'expected a non-empty sequence of (n_mels={self.feat_dims}, T_i) arrays')
+            lens = [a.shape[1] for a in arrs]
         if min(lens) < 21:   # the fade-out broadcast error of :258, raised before any device work
             t_bad = min(lens)
             raise ValueError(f'operands could not be broadcast together with shapes ({max((t_bad - 1) * self.hop_length, 0)},) '
                              f'({20 * self.hop_length},) ({max((t_bad - 1) * self.hop_length, 0)},)')
         tmax = max(lens)
-        batch = np.zeros((len(arrs), self.feat_dims, tmax), np.float32)
-        for i, a in enumerate(arrs):
-            batch[i, :, :lens[i]] = a
+        if wavs is not None:
+            batch = fe.melspectrogram(list(wavs), device=torch.device('cuda', self._device_index()))   # (B, n_mels, tmax) on the device, zero past each clip
+        else:
+            batch = np.zeros((len(arrs), self.feat_dims, tmax), np.float32)
+            for i, a in enumerate(arrs):
+                batch[i, :, :lens[i]] = a
         if seeds is None and 'seed' not in native_opts and native_opts.get('noise_mode', _cabi.NOISE_PHILOX) in (_cabi.NOISE_PHILOX, 'philox'):
             native_opts['seed'] = int(torch.randint(0, 2 ** 62, (1,)).item())
         ragged = len(set(lens)) > 1
