@@ -16,22 +16,6 @@
 
 namespace {
 
-int fail(wrnn_handle *h, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (h) h->err = buf;
-    return code;
-}
-
-#define HIP_TRY(h, expr)                                                                           \
-    do {                                                                                           \
-        hipError_t e__ = (expr);                                                                   \
-        if (e__ != hipSuccess) return fail((h), WRNN_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e__)); \
-    } while (0)
-
 // Composite taps of the stretch+conv chain (UpsampleNetwork, fatchord_version.py:73-88),
 // computed in fp64 by pushing one impulse frame through the exact chain.
 std::vector<float> build_ktab(const WrnnDims &d, const int *scales, int n_up, const std::vector<std::vector<double>> &taps) {
@@ -139,21 +123,21 @@ int wrnn_create(const wrnn_config *cfg, wrnn_handle **out) {
     // Any constructor dims (fatchord_version.py:93-129) run on the SIMPLE kernel as long as its activation vectors fit a
     // CU's LDS; the team kernels (TEAM2, BATCH) are built for the reference hparams (wavernn_hparams.py:18-57).
     if (d.H < 1 || d.FC < 1 || d.F < 1 || d.C < 1 || d.R < 4 || d.NBLK < 0 || d.P < 0 || cfg->bits < 1 || cfg->bits > 16)
-        return fail(h, WRNN_ERR_INVALID, "bad dims");
-    if (cfg->res_out_dims % 4 != 0) return fail(h, WRNN_ERR_INVALID, "res_out_dims must be a multiple of 4 (aux split, :109)");
+        return wrnn_fail(h, WRNN_ERR_INVALID, "bad dims");
+    if (cfg->res_out_dims % 4 != 0) return wrnn_fail(h, WRNN_ERR_INVALID, "res_out_dims must be a multiple of 4 (aux split, :109)");
     if (d.H > 1024 || d.C > 1024 || d.R > 1024)
-        return fail(h, WRNN_ERR_INVALID, "unsupported dims: rnn_dims, compute_dims, res_out_dims up to 1024");
+        return wrnn_fail(h, WRNN_ERR_INVALID, "unsupported dims: rnn_dims, compute_dims, res_out_dims up to 1024");
     h->team_dims = d.H == 512 && d.FC == 512 && d.F == 80 && d.R == 128 && d.C == 128 && d.A == 32;
-    if (hop != cfg->hop_length) return fail(h, WRNN_ERR_INVALID, "prod(upsample_factors)=%d != hop_length=%d", hop, cfg->hop_length);
+    if (hop != cfg->hop_length) return wrnn_fail(h, WRNN_ERR_INVALID, "prod(upsample_factors)=%d != hop_length=%d", hop, cfg->hop_length);
     if (reach > cfg->pad * hop || d.ND > WRNN_KTAB_MAXD)
-        return fail(h, WRNN_ERR_INVALID, "upsample edge reach %d exceeds indent %d: composite FIR not shift-invariant", reach, cfg->pad * hop);
+        return wrnn_fail(h, WRNN_ERR_INVALID, "upsample edge reach %d exceeds indent %d: composite FIR not shift-invariant", reach, cfg->pad * hop);
     if (wrnn_simple_lds_bytes(d) > 160u * 1024u || ((size_t)(8 + d.KS - 1) * d.F + 16u * d.C) * sizeof(float) > 160u * 1024u)
-        return fail(h, WRNN_ERR_INVALID, "dims too large: the activation vectors of one row (%zu bytes) must fit 160 KB of LDS", wrnn_simple_lds_bytes(d));
-    HIP_TRY(h, hipSetDevice(cfg->device));
+        return wrnn_fail(h, WRNN_ERR_INVALID, "dims too large: the activation vectors of one row (%zu bytes) must fit 160 KB of LDS", wrnn_simple_lds_bytes(d));
+    WRNN_HIP_TRY(h, hipSetDevice(cfg->device));
     {
         // team kernels: one team per XCD = 32 CUs (SPX: 256 CUs = 8 teams; a CPX/DPX partition exposes fewer)
         hipDeviceProp_t prop;
-        HIP_TRY(h, hipGetDeviceProperties(&prop, cfg->device));
+        WRNN_HIP_TRY(h, hipGetDeviceProperties(&prop, cfg->device));
         h->n_teams = prop.multiProcessorCount / 32;
         if (h->n_teams > 8) h->n_teams = 8;
     }
@@ -184,9 +168,9 @@ int wrnn_create(const wrnn_config *cfg, wrnn_handle **out) {
         }
         (void)hipGetLastError();
     }
-    for (int i = 0; i < 3; ++i) HIP_TRY(h, hipEventCreate(&h->ev[i]));
-    HIP_TRY(h, hipMalloc(&h->err_dev, 64));
-    HIP_TRY(h, hipMemset(h->err_dev, 0, 64));
+    for (int i = 0; i < 3; ++i) WRNN_HIP_TRY(h, hipEventCreate(&h->ev[i]));
+    WRNN_HIP_TRY(h, hipMalloc(&h->err_dev, 64));
+    WRNN_HIP_TRY(h, hipMemset(h->err_dev, 0, 64));
     return WRNN_OK;
 }
 
@@ -248,13 +232,13 @@ int wrnn_load_weights(wrnn_handle *h, const wrnn_tensor_desc *tensors, int32_t n
         if (tensors[i].name && tensors[i].data) tv[tensors[i].name] = TensorView{&tensors[i]};
     auto need = [&](const std::string &name, std::initializer_list<int64_t> shape, const float **out) -> int {
         auto it = tv.find(name);
-        if (it == tv.end()) return fail(h, WRNN_ERR_MISSING_KEY, "state_dict key missing: %s", name.c_str());
+        if (it == tv.end()) return wrnn_fail(h, WRNN_ERR_MISSING_KEY, "state_dict key missing: %s", name.c_str());
         const wrnn_tensor_desc *t = it->second.t;
-        if (t->dtype != WRNN_DTYPE_F32) return fail(h, WRNN_ERR_INVALID, "%s: expected float32", name.c_str());
-        if ((size_t)t->ndim != shape.size()) return fail(h, WRNN_ERR_INVALID, "%s: expected %d dimensions, got %d", name.c_str(), (int)shape.size(), (int)t->ndim);
+        if (t->dtype != WRNN_DTYPE_F32) return wrnn_fail(h, WRNN_ERR_INVALID, "%s: expected float32", name.c_str());
+        if ((size_t)t->ndim != shape.size()) return wrnn_fail(h, WRNN_ERR_INVALID, "%s: expected %d dimensions, got %d", name.c_str(), (int)shape.size(), (int)t->ndim);
         int di = 0;
         for (auto s : shape) {
-            if (t->shape[di] != s) return fail(h, WRNN_ERR_INVALID, "%s: dimension %d is %lld, expected %lld", name.c_str(), di, (long long)t->shape[di], (long long)s);
+            if (t->shape[di] != s) return wrnn_fail(h, WRNN_ERR_INVALID, "%s: dimension %d is %lld, expected %lld", name.c_str(), di, (long long)t->shape[di], (long long)s);
             ++di;
         }
         *out = it->second.f();
@@ -445,53 +429,44 @@ int wrnn_load_weights(wrnn_handle *h, const wrnn_tensor_desc *tensors, int32_t n
                     }
                 }
     }
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    WRNN_HIP_TRY(h, hipSetDevice(h->cfg.device));
     auto upload = [&](float *&dst, const std::vector<float> &src) -> int {
         if (dst) { (void)hipFree(dst); dst = nullptr; }
-        HIP_TRY(h, hipMalloc(&dst, src.size() * sizeof(float)));
-        HIP_TRY(h, hipMemcpy(dst, src.data(), src.size() * sizeof(float), hipMemcpyHostToDevice));
+        WRNN_HIP_TRY(h, hipMalloc(&dst, src.size() * sizeof(float)));
+        WRNN_HIP_TRY(h, hipMemcpy(dst, src.data(), src.size() * sizeof(float), hipMemcpyHostToDevice));
         return WRNN_OK;
     };
     if ((rc = upload(h->team_w, tw)) || (rc = upload(h->team_fc3, tf3)) || (rc = upload(h->wI0, vwI0)) || (rc = upload(h->u1, vu1)) ||
         (rc = upload(h->batch_w, bw)) || (rc = upload(h->batch_fc3, bf3)) || (rc = upload(h->batch_wn, bwn))) return rc;
     }
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    WRNN_HIP_TRY(h, hipSetDevice(h->cfg.device));
     if (!h->mail) {
-        HIP_TRY(h, hipMalloc(&h->mail, (size_t)8 * WRNN_MAIL_GRANULES_MAX * sizeof(unsigned long long)));
-        HIP_TRY(h, hipMalloc(&h->ctl, 128));
+        WRNN_HIP_TRY(h, hipMalloc(&h->mail, WRNN_MAIL_BYTES));
+        WRNN_HIP_TRY(h, hipMalloc(&h->ctl, 128));
     }
     if (h->wdev) { (void)hipFree(h->wdev); h->wdev = nullptr; }
-    HIP_TRY(h, hipMalloc(&h->wdev, o.total * sizeof(float)));
-    HIP_TRY(h, hipMemcpy(h->wdev, pk.data(), o.total * sizeof(float), hipMemcpyHostToDevice));
+    WRNN_HIP_TRY(h, hipMalloc(&h->wdev, o.total * sizeof(float)));
+    WRNN_HIP_TRY(h, hipMemcpy(h->wdev, pk.data(), o.total * sizeof(float), hipMemcpyHostToDevice));
     h->loaded = true;
     return WRNN_OK;
 }
 
-static int ensure_aux(wrnn_handle *h, int B, int T) {
-    const size_t need = (size_t)B * T * h->d.R;
-    if (need > h->aux_cap) {
-        if (h->aux_frames) (void)hipFree(h->aux_frames);
-        h->aux_frames = nullptr; h->aux_cap = 0;
-        HIP_TRY(h, hipMalloc(&h->aux_frames, need * sizeof(float)));
-        h->aux_cap = need;
-    }
-    return WRNN_OK;
-}
+static int ensure_aux(wrnn_handle *h, int B, int T) { return wrnn_grow(h, h->aux_frames, h->aux_cap, (size_t)B * T * h->d.R); }
 
 int wrnn_conditioning(wrnn_handle *h, const float *mels_dev, int32_t B, int32_t T, int32_t mels_padded, float *up_dev, float *aux_dev, void *stream) {
-    if (!h || !mels_dev || B < 1 || T < 1) return fail(h, WRNN_ERR_INVALID, "wrnn_conditioning: bad arguments");
-    if (!h->loaded) return fail(h, WRNN_ERR_STATE, "weights not loaded");
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (!h || !mels_dev || B < 1 || T < 1) return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_conditioning: bad arguments");
+    if (!h->loaded) return wrnn_fail(h, WRNN_ERR_STATE, "weights not loaded");
+    WRNN_HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     if (int rc = ensure_aux(h, B, T)) return rc;
     const int mel_T = mels_padded ? T + 2 * h->d.P : T, mel_off = mels_padded ? h->d.P : 0;
-    HIP_TRY(h, wrnn_launch_resnet(h, mels_dev, B, T, mel_T, mel_off, h->aux_frames, s));
-    if (up_dev || aux_dev) HIP_TRY(h, wrnn_launch_materialize(h, mels_dev, h->aux_frames, B, T, mel_T, mel_off, up_dev, aux_dev, s));
+    WRNN_HIP_TRY(h, wrnn_launch_resnet(h, mels_dev, B, T, mel_T, mel_off, h->aux_frames, s));
+    if (up_dev || aux_dev) WRNN_HIP_TRY(h, wrnn_launch_materialize(h, mels_dev, h->aux_frames, B, T, mel_T, mel_off, up_dev, aux_dev, s));
     return WRNN_OK;
 }
 
 int wrnn_plan(wrnn_handle *h, int32_t B, int32_t T, int32_t batched, int32_t target, int32_t overlap, int32_t *rows_out, int64_t *steps_out) {
-    if (!h || B < 1 || T < 1) return fail(h, WRNN_ERR_INVALID, "wrnn_plan: bad arguments");
+    if (!h || B < 1 || T < 1) return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_plan: bad arguments");
     const int64_t total = (int64_t)T * h->d.HOP;
     if (!batched) {
         if (rows_out) *rows_out = B;
@@ -500,15 +475,15 @@ int wrnn_plan(wrnn_handle *h, int32_t B, int32_t T, int32_t batched, int32_t tar
     }
     // fold_with_overlap (fatchord_version.py:293-340) indexes folded[i] = x[:, start:end, :] with a
     // batch-1 x; any other batch size raises in the reference.
-    if (B != 1) return fail(h, WRNN_ERR_INVALID, "batched generation requires a single utterance (fold_with_overlap)");
-    if (target < 1 || overlap < 0) return fail(h, WRNN_ERR_INVALID, "bad target/overlap");
+    if (B != 1) return wrnn_fail(h, WRNN_ERR_INVALID, "batched generation requires a single utterance (fold_with_overlap)");
+    if (target < 1 || overlap < 0) return wrnn_fail(h, WRNN_ERR_INVALID, "bad target/overlap");
     // Python floor division like fatchord_version.py:319 (a clip shorter than `overlap` gives -1 -> 0 folds -> error)
     const int64_t fold_den = (int64_t)target + overlap, fold_num = total - overlap;
     int64_t num_folds = fold_num / fold_den;
     if (fold_num % fold_den != 0 && fold_num < 0) --num_folds;
     const int64_t extended = num_folds * ((int64_t)overlap + target) + overlap;
     if (total - extended != 0) num_folds += 1;
-    if (num_folds < 1) return fail(h, WRNN_ERR_INVALID, "sequence shorter than one fold");
+    if (num_folds < 1) return wrnn_fail(h, WRNN_ERR_INVALID, "sequence shorter than one fold");
     if (rows_out) *rows_out = (int32_t)num_folds;
     if (steps_out) *steps_out = (int64_t)target + 2LL * overlap;
     return WRNN_OK;
@@ -516,80 +491,122 @@ int wrnn_plan(wrnn_handle *h, int32_t B, int32_t T, int32_t batched, int32_t tar
 
 }  // extern "C"
 
+// Row table of a call (rows, order, sched, keys under the one capacity rows_cap), built on the device: nothing is staged on the host,
+// the call never waits for the stream.
+static int build_row_table(wrnn_handle *h, int32_t B, int32_t T, int32_t batched, int32_t target, int32_t overlap, const wrnn_sample_opts *opts,
+                           const int32_t *fold_frames, int32_t rows, int64_t steps, int sched_teams, hipStream_t s) {
+    if ((size_t)rows > h->rows_cap) {
+        size_t cap[4] = {0, 0, 0, 0};   // rows_cap stays 0 until all four buffers are there
+        h->rows_cap = 0;
+        int rc;
+        if ((rc = wrnn_grow(h, h->rows_dev, cap[0], (size_t)rows)) || (rc = wrnn_grow(h, h->order_dev, cap[1], (size_t)rows)) ||
+            (rc = wrnn_grow(h, h->sched_dev, cap[2], (size_t)rows + 64)) || (rc = wrnn_grow(h, h->keys_dev, cap[3], (size_t)rows)))
+            return rc;
+        h->rows_cap = rows;
+    }
+    WRNN_HIP_TRY(h, hipMemsetAsync(h->err_dev, 0, 64, s));
+    if (!fold_frames) {
+        WRNN_HIP_TRY(h, wrnn_launch_rows(h->rows_dev, h->order_dev, h->sched_dev, rows, sched_teams, batched, (long)target + overlap, (long)steps,
+                                         opts->frames_dev, T, h->d.HOP, h->keys_dev, opts->utt_seeds_dev, s));
+        return WRNN_OK;
+    }
+    h->fold_B = 0;   // the fold offsets on the handle are valid once the kernel that writes them is enqueued
+    if (int rc = wrnn_grow(h, h->fold0_dev, h->fold0_cap, (size_t)B + 1)) return rc;
+    WRNN_HIP_TRY(h, wrnn_launch_rows_folded(h->rows_dev, h->order_dev, h->sched_dev, h->fold0_dev, h->err_dev, fold_frames, B, rows, sched_teams,
+                                            (long)target, (long)overlap, h->d.HOP, T, h->keys_dev, opts->utt_seeds_dev, s));
+    h->fold_B = B; h->fold_target = target; h->fold_overlap = overlap; h->fold_rows = rows;
+    return WRNN_OK;
+}
+
+// The batch kernels: R = 4 * nq rows per XCD team in lock-step on the matrix cores (loop_batch.hip); the rows are spread evenly over
+// the teams first (rpb rows per batch), a team runs ceil(batches / n_teams) batches one after the other.  a: the call's loop arguments.
+static int run_batch(wrnn_handle *h, const WrnnLoopArgs &a, const WrnnFrameTables &t, int B, bool cs, int batch_rows, int snake, hipStream_t s) {
+    const int rows = a.n_rows;
+    WRNN_HIP_TRY(h, wrnn_launch_pack_records32(t.CM, t.CA, t.VM, t.VA, t.C2, t.C3, t.C4, t.REC, B, a.T, a.d.P, a.frames, s));
+    int rpb = (rows + h->n_teams - 1) / h->n_teams;
+    if (rpb > WRNN_BATCH_MAX_ROWS) rpb = WRNN_BATCH_MAX_ROWS;
+    if (batch_rows > 0) rpb = batch_rows;
+    if (cs && rpb > 4 * wrnn_batch_cs_max_nq(a.d.mode)) rpb = 4 * wrnn_batch_cs_max_nq(a.d.mode);   // critical / shadow wave roles (loop_batch_cs.hip)
+    WrnnBatchArgs ba{};
+    ba.w = a.w; ba.off = a.off; ba.d = a.d; ba.batch_w = h->batch_w; ba.batch_fc3 = h->batch_fc3; ba.batch_wn = h->batch_wn; ba.wI0 = h->wI0; ba.u1 = h->u1;
+    ba.tabREC32 = t.REC; ba.rows = a.rows; ba.order = h->order_dev; ba.snake = snake; ba.n_rows = rows; ba.n_teams = h->n_teams; ba.nq = rpb <= 4 ? 1 : 2; ba.rpb = rpb;
+    ba.T = a.T; ba.total_len = a.total_len; ba.steps = a.steps;
+    wrnn_copy_sampling(ba, a);
+    ba.mail = h->mail; ba.ctl = h->ctl; ba.err = a.err; ba.prof = h->prof_on ? h->prof : nullptr;
+    if (ba.prof) WRNN_HIP_TRY(h, hipMemsetAsync(h->prof, 0, 8 * WRNN_PROF_SLOTS * sizeof(unsigned long long), s));
+    WRNN_HIP_TRY(h, hipEventRecord(h->ev[1], s));  // tables and records are prologue work
+    WRNN_HIP_TRY(h, wrnn_gated_launch(h->cfg.device, s, h->mail, WRNN_MAIL_BYTES, h->ctl, 128,
+                                      [&] { return cs ? wrnn_launch_loop_batch_cs(ba, s) : wrnn_launch_loop_batch(ba, s); }));
+    h->prof_div = (double)a.steps * ((((rows + rpb - 1) / rpb) + h->n_teams - 1) / h->n_teams);
+    return WRNN_OK;
+}
+
+// The latency kernel: one row per XCD team at a time, in segments (launch.hip)
+static int run_team2(wrnn_handle *h, const WrnnLoopArgs &a, const WrnnFrameTables &t, int B, int team2_segment, int snake, int n_slots, int *launches,
+                     hipStream_t s) {
+    const int rows = a.n_rows;
+    WRNN_HIP_TRY(h, wrnn_launch_pack_records(t.CM, t.CA, t.VM, t.VA, t.REC, B, a.T, a.d.P, a.frames, s));
+    if (a.frames) WRNN_HIP_TRY(h, wrnn_launch_mask_frame_tables(t.C2, t.C3, t.C4, a.frames, B, a.T, s));
+    const int64_t seg = wrnn_team2_segment_len(rows, a.d.H, a.steps, team2_segment);
+    int rc;
+    if ((rc = wrnn_grow(h, h->cond, h->cond_cap, (size_t)rows * (size_t)seg * a.d.H * 4)) ||
+        (rc = wrnn_grow(h, h->team_state, h->team_state_cap, (size_t)rows * WRNN_TEAM_STATE_FLOATS)))
+        return rc;
+    WrnnTeamArgs ta{};
+    ta.w = a.w; ta.off = a.off; ta.d = a.d; ta.team_w = h->team_w; ta.team_fc3 = h->team_fc3; ta.wI0 = h->wI0; ta.u1 = h->u1;
+    ta.tabREC = t.REC; ta.tabC2 = t.C2; ta.tabC3 = t.C3; ta.tabC4 = t.C4;
+    ta.rows = a.rows; ta.sched = h->sched_dev; ta.n_slots = n_slots; ta.ragged = snake; ta.n_rows = rows; ta.n_teams = h->n_teams; ta.T = a.T; ta.total_len = a.total_len; ta.steps = a.steps;
+    ta.state = h->team_state;
+    wrnn_copy_sampling(ta, a);
+    ta.mail = h->mail; ta.ctl = h->ctl; ta.err = a.err; ta.prof = h->prof_on ? h->prof : nullptr;
+    WRNN_HIP_TRY(h, hipEventRecord(h->ev[1], s));  // the tables are prologue work; the stream chunks are timed with the loop
+    if (ta.prof) WRNN_HIP_TRY(h, hipMemsetAsync(h->prof, 0, 8 * WRNN_PROF_SLOTS * sizeof(unsigned long long), s));
+    h->prof_div = (double)a.steps * ((rows + h->n_teams - 1) / h->n_teams);
+    return wrnn_run_team2_segments(h, ta, h->cond, 0, a.steps, seg, launches, s);
+}
+
 // Body of wrnn_generate and wrnn_generate_folded.  fold_frames != null: the rows are the folds of ALL B utterances (rows_total of them,
 // see rows_folded_kernel), every per-frame table entry past an utterance's own end is its zero-input entry T.
 static int generate_impl(wrnn_handle *h, const float *mels_dev, int32_t B, int32_t T, int32_t batched, int32_t target, int32_t overlap,
                          const wrnn_sample_opts *opts, int32_t *labels_out_dev, float *samples_out_dev, void *stream,
                          const int32_t *fold_frames, int32_t rows_total) {
-    if (!h || !mels_dev || !opts || !samples_out_dev) return fail(h, WRNN_ERR_INVALID, "wrnn_generate: bad arguments");
+    if (!h || !mels_dev || !opts || !samples_out_dev) return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_generate: bad arguments");
     if (opts->struct_size != sizeof(wrnn_sample_opts))
-        return fail(h, WRNN_ERR_INVALID, "wrnn_sample_opts.struct_size is %u, this library (ABI %d) expects %zu: caller built against another revision of wavernn_amd.h",
+        return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_sample_opts.struct_size is %u, this library (ABI %d) expects %zu: caller built against another revision of wavernn_amd.h",
                     opts->struct_size, WRNN_ABI_VERSION, sizeof(wrnn_sample_opts));
-    if (!h->loaded) return fail(h, WRNN_ERR_STATE, "weights not loaded");
-    if (opts->frames_dev && batched) return fail(h, WRNN_ERR_INVALID, "frames_dev (ragged batch) is for unbatched calls: folds of one utterance have one length");
-    if (opts->batch_rows < 0 || opts->batch_rows > WRNN_BATCH_MAX_ROWS) return fail(h, WRNN_ERR_INVALID, "batch_rows must be 0 (default) or 1..%d", WRNN_BATCH_MAX_ROWS);
-    if (opts->team2_segment < 0) return fail(h, WRNN_ERR_INVALID, "team2_segment must be >= 0");
+    if (!h->loaded) return wrnn_fail(h, WRNN_ERR_STATE, "weights not loaded");
+    if (opts->frames_dev && batched) return wrnn_fail(h, WRNN_ERR_INVALID, "frames_dev (ragged batch) is for unbatched calls: folds of one utterance have one length");
+    if (opts->batch_rows < 0 || opts->batch_rows > WRNN_BATCH_MAX_ROWS) return wrnn_fail(h, WRNN_ERR_INVALID, "batch_rows must be 0 (default) or 1..%d", WRNN_BATCH_MAX_ROWS);
+    if (opts->team2_segment < 0) return wrnn_fail(h, WRNN_ERR_INVALID, "team2_segment must be >= 0");
     const WrnnDims &d = h->d;
     int32_t rows = 0;
     int64_t steps = 0;
     if (fold_frames) {
-        if (B < 1 || T < 1 || rows_total < 1 || target < 1 || overlap < 0) return fail(h, WRNN_ERR_INVALID, "wrnn_generate_folded: bad arguments");
+        if (B < 1 || T < 1 || rows_total < 1 || target < 1 || overlap < 0) return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_generate_folded: bad arguments");
         rows = rows_total;
         steps = (int64_t)target + 2LL * overlap;
     } else if (int rc = wrnn_plan(h, B, T, batched, target, overlap, &rows, &steps)) return rc;
     if (opts->noise_mode == WRNN_NOISE_INJECTED && (!opts->noise1_dev || (d.mode == WRNN_MODE_MOL && !opts->noise2_dev)))
-        return fail(h, WRNN_ERR_INVALID, "WRNN_NOISE_INJECTED needs noise pointers");
+        return wrnn_fail(h, WRNN_ERR_INVALID, "WRNN_NOISE_INJECTED needs noise pointers");
     if (opts->noise_mode == WRNN_NOISE_ARGMAX && d.mode != WRNN_MODE_RAW)
-        return fail(h, WRNN_ERR_INVALID, "WRNN_NOISE_ARGMAX is RAW-only");
-    if (opts->noise_mode < 0 || opts->noise_mode > 2) return fail(h, WRNN_ERR_INVALID, "bad noise_mode");
+        return wrnn_fail(h, WRNN_ERR_INVALID, "WRNN_NOISE_ARGMAX is RAW-only");
+    if (opts->noise_mode < 0 || opts->noise_mode > 2) return wrnn_fail(h, WRNN_ERR_INVALID, "bad noise_mode");
     if (opts->utt_seeds_dev && opts->noise_mode != WRNN_NOISE_PHILOX)
-        return fail(h, WRNN_ERR_INVALID, "utt_seeds_dev (per-utterance seeds) needs noise_mode WRNN_NOISE_PHILOX");
+        return wrnn_fail(h, WRNN_ERR_INVALID, "utt_seeds_dev (per-utterance seeds) needs noise_mode WRNN_NOISE_PHILOX");
     if (opts->utt_seeds_dev && batched && !fold_frames)
-        return fail(h, WRNN_ERR_INVALID, "utt_seeds_dev is for unbatched calls and wrnn_generate_folded: a batched wrnn_generate has one utterance, `seed` is its key");
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
+        return wrnn_fail(h, WRNN_ERR_INVALID, "utt_seeds_dev is for unbatched calls and wrnn_generate_folded: a batched wrnn_generate has one utterance, `seed` is its key");
+    WRNN_HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
 
-    // rows table, built on the device: nothing is staged on the host, the call never waits for the stream
-    if ((size_t)rows > h->rows_cap) {
-        if (h->rows_dev) (void)hipFree(h->rows_dev);
-        h->rows_dev = nullptr; h->rows_cap = 0;
-        if (h->order_dev) (void)hipFree(h->order_dev);
-        if (h->sched_dev) (void)hipFree(h->sched_dev);
-        if (h->keys_dev) (void)hipFree(h->keys_dev);
-        h->order_dev = h->sched_dev = nullptr;
-        h->keys_dev = nullptr;
-        HIP_TRY(h, hipMalloc(&h->rows_dev, (size_t)rows * sizeof(WrnnRow)));
-        HIP_TRY(h, hipMalloc(&h->order_dev, (size_t)rows * sizeof(int32_t)));
-        HIP_TRY(h, hipMalloc(&h->sched_dev, ((size_t)rows + 64) * sizeof(int32_t)));
-        HIP_TRY(h, hipMalloc(&h->keys_dev, (size_t)rows * sizeof(WrnnRowKey)));
-        h->rows_cap = rows;
-    }
     const int sched_teams = h->n_teams < 1 ? 1 : h->n_teams;
-    const int n_slots = (rows + sched_teams - 1) / sched_teams * sched_teams;
-    HIP_TRY(h, hipMemsetAsync(h->err_dev, 0, 64, s));
-    if (fold_frames) {
-        h->fold_B = 0;   // the fold offsets on the handle are valid once the kernel that writes them is enqueued
-        if ((size_t)B + 1 > h->fold0_cap) {
-            if (h->fold0_dev) (void)hipFree(h->fold0_dev);
-            h->fold0_dev = nullptr; h->fold0_cap = 0;
-            HIP_TRY(h, hipMalloc(&h->fold0_dev, ((size_t)B + 1) * sizeof(int32_t)));
-            h->fold0_cap = (size_t)B + 1;
-        }
-        HIP_TRY(h, wrnn_launch_rows_folded(h->rows_dev, h->order_dev, h->sched_dev, h->fold0_dev, h->err_dev, fold_frames, B, rows, sched_teams,
-                                           (long)target, (long)overlap, d.HOP, T, h->keys_dev, opts->utt_seeds_dev, s));
-        h->fold_B = B; h->fold_target = target; h->fold_overlap = overlap; h->fold_rows = rows;
-    } else {
-        HIP_TRY(h, wrnn_launch_rows(h->rows_dev, h->order_dev, h->sched_dev, rows, sched_teams, batched, (long)target + overlap, (long)steps,
-                                    opts->frames_dev, T, d.HOP, h->keys_dev, opts->utt_seeds_dev, s));
-    }
+    if (int rc = build_row_table(h, B, T, batched, target, overlap, opts, fold_frames, rows, steps, sched_teams, s)) return rc;
     const int snake = opts->frames_dev ? 1 : 0;
-    unsigned long long *const prof = h->prof_on ? h->prof : nullptr;
     if (int rc = ensure_aux(h, B, T)) return rc;
 
-    HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    WRNN_HIP_TRY(h, hipEventRecord(h->ev[0], s));
     const int mel_T = opts->mels_padded ? T + 2 * d.P : T, mel_off = opts->mels_padded ? d.P : 0;
-    HIP_TRY(h, wrnn_launch_resnet(h, mels_dev, B, T, mel_T, mel_off, h->aux_frames, s));
-    HIP_TRY(h, hipEventRecord(h->ev[1], s));
+    WRNN_HIP_TRY(h, wrnn_launch_resnet(h, mels_dev, B, T, mel_T, mel_off, h->aux_frames, s));
+    WRNN_HIP_TRY(h, hipEventRecord(h->ev[1], s));
 
     WrnnLoopArgs a{};
     a.w = h->wdev; a.off = h->off; a.d = d; a.mels = mels_dev; a.mel_T = mel_T; a.mel_off = mel_off; a.aux_frames = h->aux_frames; a.rows = h->rows_dev;
@@ -611,122 +628,19 @@ static int generate_impl(wrnn_handle *h, const float *mels_dev, int32_t B, int32
     }
     if (kernel == WRNN_KERNEL_BATCH_CS && !team_no && !h->cs_ok) team_no = "loop_batch_cs_kernel cannot be resident (LDS/registers); WRNN_KERNEL_BATCH can";
     if (kernel == WRNN_KERNEL_SIMPLE) {
-        HIP_TRY(h, wrnn_launch_loop_simple(a, s));
+        WRNN_HIP_TRY(h, wrnn_launch_loop_simple(a, s));
     } else if (kernel == WRNN_KERNEL_TEAM2 || kernel == WRNN_KERNEL_BATCH || kernel == WRNN_KERNEL_BATCH_CS) {
         const bool batch_family = kernel != WRNN_KERNEL_TEAM2;
-        if (team_no) return fail(h, WRNN_ERR_INVALID, "%s", team_no);
-        // conditioning pushed through the linear layers it feeds (once per call)
-        const int H = d.H, FC = d.FC, F = d.F, A = d.A, R = d.R, P = d.P;
-        const int TP = T + 2 * P, T1 = T + 1;
-        const size_t nCM = (size_t)B * TP * H, nCA = (size_t)B * T1 * H, nVM = (size_t)B * TP * 3 * H, nVA = (size_t)B * T1 * 3 * H;
-        const size_t nC2 = (size_t)B * T1 * 3 * H, nC3 = (size_t)B * T1 * FC, nC4 = (size_t)B * T1 * FC;
-        const size_t nREC = (size_t)B * T1 * H * (batch_family ? 32 : 28);
-        const size_t need = nCM + nCA + nVM + nVA + nC2 + nC3 + nC4 + nREC;
-        if (need > h->tab_cap) {
-            if (h->tab) (void)hipFree(h->tab);
-            h->tab = nullptr; h->tab_cap = 0;
-            HIP_TRY(h, hipMalloc(&h->tab, need * sizeof(float)));
-            h->tab_cap = need;
-        }
-        float *tCM = h->tab, *tCA = tCM + nCM, *tVM = tCA + nCA, *tVA = tVM + nVM, *tC2 = tVA + nVA, *tC3 = tC2 + nC2, *tC4 = tC3 + nC3, *tREC = tC4 + nC4;
-        const float *w = h->wdev;
-        const WrnnPacked &o = h->off;
-        HIP_TRY(h, wrnn_launch_frame_linear(1, mels_dev, (size_t)F * mel_T, 0, 0, w + o.I_t + (size_t)1 * H, H, nullptr, tCM, (size_t)TP * H, TP, F, H, B, mel_T, P - mel_off, s));
-        HIP_TRY(h, wrnn_launch_frame_linear(0, h->aux_frames, (size_t)T * R, R, T, w + o.I_t + (size_t)(1 + F) * H, H, w + o.I_b, tCA, (size_t)T1 * H, T1, A, H, B, T, P, s));
-        HIP_TRY(h, wrnn_launch_frame_linear(0, tCM, (size_t)TP * H, H, TP, w + o.r1_wih_t, 3 * H, nullptr, tVM, (size_t)TP * 3 * H, TP, H, 3 * H, B, T, P, s));
-        HIP_TRY(h, wrnn_launch_frame_linear(0, tCA, (size_t)T1 * H, H, T1, w + o.r1_wih_t, 3 * H, w + o.r1_bih, tVA, (size_t)T1 * 3 * H, T1, H, 3 * H, B, T, P, s));
-        HIP_TRY(h, wrnn_launch_frame_linear(0, h->aux_frames + A, (size_t)T * R, R, T, w + o.r2_wih_t + (size_t)H * 3 * H, 3 * H, w + o.r2_bih, tC2, (size_t)T1 * 3 * H, T1, A, 3 * H, B, T, P, s));
-        HIP_TRY(h, wrnn_launch_frame_linear(0, h->aux_frames + 2 * A, (size_t)T * R, R, T, w + o.fc1_t + (size_t)H * FC, FC, w + o.fc1_b, tC3, (size_t)T1 * FC, T1, A, FC, B, T, P, s));
-        HIP_TRY(h, wrnn_launch_frame_linear(0, h->aux_frames + 3 * A, (size_t)T * R, R, T, w + o.fc2_t + (size_t)FC * FC, FC, w + o.fc2_b, tC4, (size_t)T1 * FC, T1, A, FC, B, T, P, s));
-        const size_t mail_bytes = (size_t)8 * WRNN_MAIL_GRANULES_MAX * sizeof(unsigned long long);
-        if (batch_family) {
-            // R = 4 * nq rows per XCD team in lock-step on the matrix cores (loop_batch.hip); the rows are spread evenly over
-            // the teams first (rpb rows per batch), a team runs ceil(batches / n_teams) batches one after the other
-            HIP_TRY(h, wrnn_launch_pack_records32(tCM, tCA, tVM, tVA, tC2, tC3, tC4, tREC, B, T, P, fold_frames, s));
-            int rpb = (rows + h->n_teams - 1) / h->n_teams;
-            if (rpb > WRNN_BATCH_MAX_ROWS) rpb = WRNN_BATCH_MAX_ROWS;
-            if (opts->batch_rows > 0) rpb = opts->batch_rows;
-            const bool cs = kernel == WRNN_KERNEL_BATCH_CS;   // critical / shadow wave roles (loop_batch_cs.hip)
-            if (cs && rpb > 4 * wrnn_batch_cs_max_nq(d.mode)) rpb = 4 * wrnn_batch_cs_max_nq(d.mode);
-            WrnnBatchArgs ba{};
-            ba.w = w; ba.off = o; ba.d = d; ba.batch_w = h->batch_w; ba.batch_fc3 = h->batch_fc3; ba.batch_wn = h->batch_wn; ba.wI0 = h->wI0; ba.u1 = h->u1;
-            ba.tabREC32 = tREC; ba.rows = h->rows_dev; ba.order = h->order_dev; ba.snake = snake; ba.n_rows = rows; ba.n_teams = h->n_teams; ba.nq = rpb <= 4 ? 1 : 2; ba.rpb = rpb;
-            ba.T = T; ba.total_len = a.total_len; ba.steps = steps;
-            ba.noise_mode = a.noise_mode; ba.seed = a.seed; ba.keys = a.keys; ba.noise1 = a.noise1; ba.noise2 = a.noise2; ba.x_forced = a.x_forced; ba.x_init = a.x_init;
-            ba.logits_out = a.logits_out; ba.labels_out = a.labels_out; ba.samples_out = a.samples_out;
-            ba.mail = h->mail; ba.ctl = h->ctl; ba.err = h->err_dev; ba.prof = prof;
-            if (prof) HIP_TRY(h, hipMemsetAsync(h->prof, 0, 8 * WRNN_PROF_SLOTS * sizeof(unsigned long long), s));
-            HIP_TRY(h, hipEventRecord(h->ev[1], s));  // tables and records are prologue work
-            // team kernels of one device run one after the other, whatever handle / stream launches them (wavernn_amd.h); the
-            // mailbox reset belongs inside the gate: the handle's previous team kernel may still be reading it
-            HIP_TRY(h, wrnn_team_gate_enter(h->cfg.device, s));
-            hipError_t le = hipMemsetAsync(h->mail, 0, mail_bytes, s);
-            if (le == hipSuccess) le = hipMemsetAsync(h->ctl, 0, 128, s);
-            if (le == hipSuccess) le = cs ? wrnn_launch_loop_batch_cs(ba, s) : wrnn_launch_loop_batch(ba, s);
-            const hipError_t ge = wrnn_team_gate_leave(h->cfg.device, s);
-            HIP_TRY(h, le);
-            HIP_TRY(h, ge);
-            h->prof_div = (double)steps * ((((rows + rpb - 1) / rpb) + h->n_teams - 1) / h->n_teams);
-        } else {
-        HIP_TRY(h, wrnn_launch_pack_records(tCM, tCA, tVM, tVA, tREC, B, T, P, fold_frames, s));
-        if (fold_frames) HIP_TRY(h, wrnn_launch_mask_frame_tables(tC2, tC3, tC4, fold_frames, B, T, s));
-        WrnnTeamArgs ta{};
-        ta.w = w; ta.off = o; ta.d = d; ta.team_w = h->team_w; ta.team_fc3 = h->team_fc3; ta.wI0 = h->wI0; ta.u1 = h->u1;
-        ta.tabREC = tREC; ta.tabCOND = nullptr; ta.tabC2 = tC2; ta.tabC3 = tC3; ta.tabC4 = tC4;
-        ta.rows = h->rows_dev; ta.sched = h->sched_dev; ta.n_slots = n_slots; ta.ragged = snake; ta.n_rows = rows; ta.n_teams = h->n_teams; ta.T = T; ta.total_len = a.total_len; ta.steps = steps;
-        ta.seg0 = 0; ta.seg_len = steps; ta.state = nullptr;
-        ta.noise_mode = a.noise_mode; ta.seed = a.seed; ta.keys = a.keys; ta.noise1 = a.noise1; ta.noise2 = a.noise2; ta.x_forced = a.x_forced; ta.x_init = a.x_init;
-        ta.logits_out = a.logits_out; ta.labels_out = a.labels_out; ta.samples_out = a.samples_out;
-        ta.mail = h->mail; ta.ctl = h->ctl; ta.err = h->err_dev; ta.prof = prof;
-        {
-            // The phase-A conditioning is streamed from HBM (8 KB per row and step).  A row is generated in segments,
-            // one stream chunk + one loop launch each, sized so that the chunk (~64 MB over all rows) is still resident
-            // in the memory-side cache when the loop reads it: against a stream written once for the whole clip
-            // (903 MB for 5 s of audio, read back from DRAM) this is 6.5 % faster at B=1, bounds the scratch to
-            // rows x seg x 8 KB, and costs one relaunch (~40 us) per segment.  Segment lengths are multiples of 32
-            // steps (the shadow waves regenerate their Philox state on those boundaries).
-            int64_t seg = ((int64_t)(64u << 20) / ((int64_t)rows * H * 4 * (int64_t)sizeof(float))) & ~(int64_t)31;
-            if (seg > 16384) seg = 16384;
-            if (seg < 2048) seg = 2048;
-            if (opts->team2_segment > 0) { seg = (int64_t)opts->team2_segment & ~(int64_t)31; if (seg < 32) seg = 32; }
-            if (seg > steps) seg = steps;
-            const size_t nCOND = (size_t)rows * (size_t)seg * H * 4;
-            if (nCOND > h->cond_cap) {
-                if (h->cond) (void)hipFree(h->cond);
-                h->cond = nullptr; h->cond_cap = 0;
-                HIP_TRY(h, hipMalloc(&h->cond, nCOND * sizeof(float)));
-                h->cond_cap = nCOND;
-            }
-            const size_t nST = (size_t)rows * WRNN_TEAM_STATE_FLOATS;
-            if (nST > h->team_state_cap) {
-                if (h->team_state) (void)hipFree(h->team_state);
-                h->team_state = nullptr; h->team_state_cap = 0;
-                HIP_TRY(h, hipMalloc(&h->team_state, nST * sizeof(float)));
-                h->team_state_cap = nST;
-            }
-            HIP_TRY(h, hipEventRecord(h->ev[1], s));  // the tables are prologue work; the stream chunks are timed with the loop
-            if (prof) HIP_TRY(h, hipMemsetAsync(h->prof, 0, 8 * WRNN_PROF_SLOTS * sizeof(unsigned long long), s));
-            ta.team_w = h->team_w; ta.tabCOND = h->cond; ta.state = h->team_state;
-            h->prof_div = (double)steps * ((rows + h->n_teams - 1) / h->n_teams);
-            for (int64_t t0 = 0; t0 < steps; t0 += seg) {
-                const int64_t len = steps - t0 < seg ? steps - t0 : seg;
-                HIP_TRY(h, wrnn_launch_cond_stream(tREC, w + o.ktab, h->rows_dev, h->cond, rows, T, d.HOP, a.total_len, t0, len, s));
-                ta.seg0 = t0; ta.seg_len = len;
-                HIP_TRY(h, wrnn_team_gate_enter(h->cfg.device, s));   // see the BATCH branch
-                hipError_t le = hipMemsetAsync(h->mail, 0, mail_bytes, s);
-                if (le == hipSuccess) le = hipMemsetAsync(h->ctl, 0, 128, s);
-                if (le == hipSuccess) le = wrnn_launch_loop_team2(ta, s);
-                const hipError_t ge = wrnn_team_gate_leave(h->cfg.device, s);
-                HIP_TRY(h, le);
-                HIP_TRY(h, ge);
-                launches = (int)(t0 / seg) + 1;
-            }
-        }
-        }
+        if (team_no) return wrnn_fail(h, WRNN_ERR_INVALID, "%s", team_no);
+        WrnnFrameTables t;
+        if (int rc = wrnn_build_frame_tables(h, h->tab, h->tab_cap, mels_dev, mel_T, d.P - mel_off, h->aux_frames, B, T, batch_family ? 32 : 28, t, s)) return rc;
+        if (int rc = batch_family ? run_batch(h, a, t, B, kernel == WRNN_KERNEL_BATCH_CS, opts->batch_rows, snake, s)
+                                  : run_team2(h, a, t, B, opts->team2_segment, snake, (rows + sched_teams - 1) / sched_teams * sched_teams, &launches, s))
+            return rc;
     } else {
-        return fail(h, WRNN_ERR_INVALID, "kernel %d not available", kernel);
+        return wrnn_fail(h, WRNN_ERR_INVALID, "kernel %d not available", kernel);
     }
-    HIP_TRY(h, hipEventRecord(h->ev[2], s));
+    WRNN_HIP_TRY(h, hipEventRecord(h->ev[2], s));
     h->timing_valid = true;
     h->last.kernel = kernel; h->last.rows = rows; h->last.steps = steps; h->last.launches = launches;
     return WRNN_OK;
@@ -764,53 +678,48 @@ int wrnn_plan_folded(const int32_t *frames_host, int32_t B, int32_t hop, int32_t
 int wrnn_generate_folded(wrnn_handle *h, const float *mels_dev, int32_t B, int32_t T, const int32_t *frames_dev, int32_t rows_total,
                          int32_t target, int32_t overlap, const wrnn_sample_opts *opts, int32_t *labels_out_dev,
                          float *samples_out_dev, void *stream) {
-    if (!h || !frames_dev) return fail(h, WRNN_ERR_INVALID, "wrnn_generate_folded: bad arguments");
+    if (!h || !frames_dev) return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_generate_folded: bad arguments");
     if (opts && opts->struct_size == sizeof(wrnn_sample_opts) &&
         (opts->frames_dev || opts->mels_padded || opts->x_forced_dev || opts->x_init_dev || opts->logits_out_dev))
-        return fail(h, WRNN_ERR_INVALID, "wrnn_generate_folded: opts.frames_dev, mels_padded, x_forced_dev, x_init_dev and logits_out_dev must be unset");
+        return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_generate_folded: opts.frames_dev, mels_padded, x_forced_dev, x_init_dev and logits_out_dev must be unset");
     return generate_impl(h, mels_dev, B, T, 1, target, overlap, opts, labels_out_dev, samples_out_dev, stream, frames_dev, rows_total);
 }
 
 int wrnn_loss(wrnn_handle *h, const float *y_hat_dev, const void *y_dev, int64_t n_rows, float *loss_out_dev, void *stream) {
-    if (!h || !y_hat_dev || !y_dev || !loss_out_dev || n_rows < 1) return fail(h, WRNN_ERR_INVALID, "wrnn_loss: bad arguments");
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (!h || !y_hat_dev || !y_dev || !loss_out_dev || n_rows < 1) return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_loss: bad arguments");
+    WRNN_HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     const size_t nblk = (size_t)(h->d.mode == WRNN_MODE_RAW ? (n_rows + 3) / 4 : (n_rows + 255) / 256);
-    if (nblk + 1 > h->loss_cap) {
-        if (h->loss_partial) (void)hipFree(h->loss_partial);
-        h->loss_partial = nullptr; h->loss_cap = 0;
-        HIP_TRY(h, hipMalloc(&h->loss_partial, (nblk + 1) * sizeof(double)));
-        h->loss_cap = nblk + 1;
-    }
+    if (int rc = wrnn_grow(h, h->loss_partial, h->loss_cap, nblk + 1)) return rc;
     int *bad = (int *)(h->loss_partial + nblk);
-    HIP_TRY(h, hipMemsetAsync(bad, 0, sizeof(double), s));
-    HIP_TRY(h, wrnn_launch_loss(h->d.mode, y_hat_dev, y_dev, h->d.NC, (long)n_rows, h->loss_partial, bad, loss_out_dev, s));
+    WRNN_HIP_TRY(h, hipMemsetAsync(bad, 0, sizeof(double), s));
+    WRNN_HIP_TRY(h, wrnn_launch_loss(h->d.mode, y_hat_dev, y_dev, h->d.NC, (long)n_rows, h->loss_partial, bad, loss_out_dev, s));
     return WRNN_OK;
 }
 
 int wrnn_last_timing(wrnn_handle *h, wrnn_timing *out) {
     if (!h) return WRNN_ERR_INVALID;
-    if (!h->timing_valid) return fail(h, WRNN_ERR_STATE, "no generate call to time");
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    HIP_TRY(h, hipEventSynchronize(h->ev[2]));
-    HIP_TRY(h, hipEventElapsedTime(&h->last.prologue_ms, h->ev[0], h->ev[1]));
-    HIP_TRY(h, hipEventElapsedTime(&h->last.loop_ms, h->ev[1], h->ev[2]));
+    if (!h->timing_valid) return wrnn_fail(h, WRNN_ERR_STATE, "no generate call to time");
+    WRNN_HIP_TRY(h, hipSetDevice(h->cfg.device));
+    WRNN_HIP_TRY(h, hipEventSynchronize(h->ev[2]));
+    WRNN_HIP_TRY(h, hipEventElapsedTime(&h->last.prologue_ms, h->ev[0], h->ev[1]));
+    WRNN_HIP_TRY(h, hipEventElapsedTime(&h->last.loop_ms, h->ev[1], h->ev[2]));
     unsigned errw = 0;
-    HIP_TRY(h, hipMemcpy(&errw, h->err_dev, sizeof(errw), hipMemcpyDeviceToHost));
+    WRNN_HIP_TRY(h, hipMemcpy(&errw, h->err_dev, sizeof(errw), hipMemcpyDeviceToHost));
     if (out) *out = h->last;
     if (errw == WRNN_DEVERR_ROWS)
-        return fail(h, WRNN_ERR_INVALID, "wrnn_generate_folded: rows_total differs from the fold count of frames_dev on the device "
+        return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_generate_folded: rows_total differs from the fold count of frames_dev on the device "
                                          "(wrnn_plan_folded gives it for the same frames, target and overlap)");
     if (errw == WRNN_DEVERR_BUSY)
-        return fail(h, WRNN_ERR_BUSY, "the team kernel's workgroups did not all become resident within its start-up wait: the GPU is shared with another "
+        return wrnn_fail(h, WRNN_ERR_BUSY, "the team kernel's workgroups did not all become resident within its start-up wait: the GPU is shared with another "
                                       "kernel (another process?).  Retry, or use WRNN_KERNEL_SIMPLE");
-    if (errw) return fail(h, WRNN_ERR_TIMEOUT, "device-side bounded spin gave up (code %u)", errw);
+    if (errw) return wrnn_fail(h, WRNN_ERR_TIMEOUT, "device-side bounded spin gave up (code %u)", errw);
     return WRNN_OK;
 }
 
 int wrnn_phase_profile(wrnn_handle *h, int32_t enable) {
     if (!h) return WRNN_ERR_INVALID;
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    WRNN_HIP_TRY(h, hipSetDevice(h->cfg.device));
     if (enable) {
         // the instrumented instantiations have their own register / LDS footprint: check their residency like wrnn_create does
         int blocks = 0;
@@ -820,10 +729,10 @@ int wrnn_phase_profile(wrnn_handle *h, int32_t enable) {
             for (int nq = 1; nq <= 2 && e == hipSuccess && blocks >= 1; ++nq) e = wrnn_batch_occupancy(h->cfg.mode, nq, true, &blocks, &lds);
             for (int nq = 1; nq <= wrnn_batch_cs_max_nq(h->cfg.mode) && e == hipSuccess && blocks >= 1; ++nq) e = wrnn_batch_cs_occupancy(h->cfg.mode, nq, true, &blocks, &lds);
             (void)hipGetLastError();
-            if (e != hipSuccess || blocks < 1) return fail(h, WRNN_ERR_INVALID, "the instrumented team kernels cannot be resident on this device");
+            if (e != hipSuccess || blocks < 1) return wrnn_fail(h, WRNN_ERR_INVALID, "the instrumented team kernels cannot be resident on this device");
         }
-        if (!h->prof) HIP_TRY(h, hipMalloc(&h->prof, 8 * WRNN_PROF_SLOTS * sizeof(unsigned long long)));
-        HIP_TRY(h, hipMemset(h->prof, 0, 8 * WRNN_PROF_SLOTS * sizeof(unsigned long long)));
+        if (!h->prof) WRNN_HIP_TRY(h, hipMalloc(&h->prof, 8 * WRNN_PROF_SLOTS * sizeof(unsigned long long)));
+        WRNN_HIP_TRY(h, hipMemset(h->prof, 0, 8 * WRNN_PROF_SLOTS * sizeof(unsigned long long)));
     }
     h->prof_on = enable != 0;
     return WRNN_OK;
@@ -831,11 +740,11 @@ int wrnn_phase_profile(wrnn_handle *h, int32_t enable) {
 
 int wrnn_phase_cycles(wrnn_handle *h, double *out) {
     if (!h || !out) return WRNN_ERR_INVALID;
-    if (!h->prof_on || !h->prof || !h->timing_valid) return fail(h, WRNN_ERR_STATE, "no instrumented call to report (wrnn_phase_profile(h, 1), then a TEAM2 / BATCH call)");
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
-    HIP_TRY(h, hipEventSynchronize(h->ev[2]));
+    if (!h->prof_on || !h->prof || !h->timing_valid) return wrnn_fail(h, WRNN_ERR_STATE, "no instrumented call to report (wrnn_phase_profile(h, 1), then a TEAM2 / BATCH call)");
+    WRNN_HIP_TRY(h, hipSetDevice(h->cfg.device));
+    WRNN_HIP_TRY(h, hipEventSynchronize(h->ev[2]));
     unsigned long long pr[8 * WRNN_PROF_SLOTS];
-    HIP_TRY(h, hipMemcpy(pr, h->prof, sizeof(pr), hipMemcpyDeviceToHost));
+    WRNN_HIP_TRY(h, hipMemcpy(pr, h->prof, sizeof(pr), hipMemcpyDeviceToHost));
     const double n = h->prof_div > 0 ? h->prof_div : 1.0;   // steps x rows (or batches) team 0 ran
     for (int i = 0; i < 8 * WRNN_PROF_SLOTS; ++i) out[i] = (double)pr[i] / n;
     return WRNN_OK;

@@ -9,8 +9,6 @@
 // frame index they derive from (start + absolute step) is window-relative, while the Philox noise stays keyed by the
 // absolute step.  The recurrent state crosses pushes through the stream's `state` like TEAM2 segments cross launches.
 #include <climits>
-#include <cstdarg>
-#include <cstdio>
 
 #include "wrnn_internal.h"
 
@@ -36,32 +34,6 @@ struct wrnn_stream {
 };
 
 namespace {
-
-int sfail(wrnn_handle *h, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (h) h->err = buf;
-    return code;
-}
-
-#define S_TRY(h, expr)                                                                                   \
-    do {                                                                                                 \
-        hipError_t e__ = (expr);                                                                         \
-        if (e__ != hipSuccess) return sfail((h), WRNN_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e__)); \
-    } while (0)
-
-// grow-only device scratch (the stream's workspace stays at its high-water mark)
-int ensure(wrnn_handle *h, float *&p, size_t &cap, size_t need) {
-    if (need <= cap) return WRNN_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    S_TRY(h, hipMalloc(&p, need * sizeof(float)));
-    cap = need;
-    return WRNN_OK;
-}
 
 // out[b][f][k] = frame o0 + k of row b: 0 outside [0, limit), else from the history (frames [h0, h0 + hn)) or the pushed mels
 // (frames [p0, p0 + pn)).  Every frame the host asks for lies in one of the three ranges.
@@ -118,25 +90,25 @@ int64_t wrnn_stream_ready_steps(int64_t frames_in, int32_t hop, int32_t pad, int
 }
 
 int wrnn_stream_open(wrnn_handle *h, int32_t B, const wrnn_sample_opts *opts, wrnn_stream **out) {
-    if (!h || !opts || !out || B < 1) return sfail(h, WRNN_ERR_INVALID, "wrnn_stream_open: bad arguments");
+    if (!h || !opts || !out || B < 1) return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_stream_open: bad arguments");
     *out = nullptr;
     if (opts->struct_size != sizeof(wrnn_sample_opts))
-        return sfail(h, WRNN_ERR_INVALID, "wrnn_sample_opts.struct_size is %u, this library (ABI %d) expects %zu", opts->struct_size,
+        return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_sample_opts.struct_size is %u, this library (ABI %d) expects %zu", opts->struct_size,
                      WRNN_ABI_VERSION, sizeof(wrnn_sample_opts));
-    if (!h->loaded) return sfail(h, WRNN_ERR_STATE, "weights not loaded");
+    if (!h->loaded) return wrnn_fail(h, WRNN_ERR_STATE, "weights not loaded");
     if (opts->noise_mode != WRNN_NOISE_PHILOX && opts->noise_mode != WRNN_NOISE_ARGMAX)
-        return sfail(h, WRNN_ERR_INVALID, "a stream draws its noise on the device: noise_mode must be WRNN_NOISE_PHILOX or WRNN_NOISE_ARGMAX");
-    if (opts->noise_mode == WRNN_NOISE_ARGMAX && h->d.mode != WRNN_MODE_RAW) return sfail(h, WRNN_ERR_INVALID, "WRNN_NOISE_ARGMAX is RAW-only");
+        return wrnn_fail(h, WRNN_ERR_INVALID, "a stream draws its noise on the device: noise_mode must be WRNN_NOISE_PHILOX or WRNN_NOISE_ARGMAX");
+    if (opts->noise_mode == WRNN_NOISE_ARGMAX && h->d.mode != WRNN_MODE_RAW) return wrnn_fail(h, WRNN_ERR_INVALID, "WRNN_NOISE_ARGMAX is RAW-only");
     if (opts->mels_padded || opts->noise1_dev || opts->noise2_dev || opts->x_forced_dev || opts->logits_out_dev || opts->x_init_dev ||
         opts->frames_dev || opts->batch_rows || opts->team2_segment || opts->utt_seeds_dev)
-        return sfail(h, WRNN_ERR_INVALID, "a stream takes noise_mode, kernel and seed only: mels_padded, the pointers (utt_seeds_dev included) and the tuning fields must be 0");
+        return wrnn_fail(h, WRNN_ERR_INVALID, "a stream takes noise_mode, kernel and seed only: mels_padded, the pointers (utt_seeds_dev included) and the tuning fields must be 0");
     const char *team_no = wrnn_loop_team_obstacle(h);
     int kernel = opts->kernel;
     if (kernel == WRNN_KERNEL_AUTO) kernel = team_no ? WRNN_KERNEL_SIMPLE : WRNN_KERNEL_TEAM2;
-    if (kernel == WRNN_KERNEL_TEAM2 && team_no) return sfail(h, WRNN_ERR_INVALID, "%s", team_no);
+    if (kernel == WRNN_KERNEL_TEAM2 && team_no) return wrnn_fail(h, WRNN_ERR_INVALID, "%s", team_no);
     if (kernel != WRNN_KERNEL_TEAM2 && kernel != WRNN_KERNEL_SIMPLE)
-        return sfail(h, WRNN_ERR_INVALID, "a stream runs WRNN_KERNEL_AUTO, TEAM2 or SIMPLE (kernel %d)", opts->kernel);
-    S_TRY(h, hipSetDevice(h->cfg.device));
+        return wrnn_fail(h, WRNN_ERR_INVALID, "a stream runs WRNN_KERNEL_AUTO, TEAM2 or SIMPLE (kernel %d)", opts->kernel);
+    WRNN_HIP_TRY(h, hipSetDevice(h->cfg.device));
     wrnn_stream *st = new wrnn_stream();
     st->h = h; st->device = h->cfg.device; st->B = B; st->kernel = kernel; st->noise_mode = opts->noise_mode; st->seed = opts->seed;
     const int teams = h->n_teams < 1 ? 1 : h->n_teams;
@@ -151,7 +123,7 @@ int wrnn_stream_open(wrnn_handle *h, int32_t B, const wrnn_sample_opts *opts, wr
     }
     if (e != hipSuccess) {
         wrnn_stream_close(st);
-        return sfail(h, WRNN_ERR_HIP, "wrnn_stream_open: %s", hipGetErrorString(e));
+        return wrnn_fail(h, WRNN_ERR_HIP, "wrnn_stream_open: %s", hipGetErrorString(e));
     }
     *out = st;
     return WRNN_OK;
@@ -162,10 +134,10 @@ int wrnn_stream_push(wrnn_stream *st, const float *mels_dev, int32_t n_frames, i
     if (!st) return WRNN_ERR_INVALID;
     wrnn_handle *h = st->h;
     if (steps_out) *steps_out = 0;
-    if (st->poisoned) return sfail(h, WRNN_ERR_STATE, "the stream reported a device-side error (wrnn_stream_sync): it cannot continue");
-    if (st->ended) return sfail(h, WRNN_ERR_STATE, "push after the stream's last push");
-    if (n_frames < 0 || (n_frames > 0 && !mels_dev) || !steps_out) return sfail(h, WRNN_ERR_INVALID, "wrnn_stream_push: bad arguments");
-    if (!h->loaded) return sfail(h, WRNN_ERR_STATE, "weights not loaded");
+    if (st->poisoned) return wrnn_fail(h, WRNN_ERR_STATE, "the stream reported a device-side error (wrnn_stream_sync): it cannot continue");
+    if (st->ended) return wrnn_fail(h, WRNN_ERR_STATE, "push after the stream's last push");
+    if (n_frames < 0 || (n_frames > 0 && !mels_dev) || !steps_out) return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_stream_push: bad arguments");
+    if (!h->loaded) return wrnn_fail(h, WRNN_ERR_STATE, "weights not loaded");
     const WrnnDims &d = h->d;
     const int B = st->B, F = d.F, P = d.P, HOP = d.HOP;
     const int64_t fin = st->frames_in + n_frames;
@@ -173,10 +145,10 @@ int wrnn_stream_push(wrnn_stream *st, const float *mels_dev, int32_t n_frames, i
     const int64_t s0 = st->steps_done, s1 = ready > s0 ? ready : s0;
     const int64_t n = s1 - s0;
     if (n > 0 && (!samples_out_dev || out_capacity < (int64_t)B * n))
-        return sfail(h, WRNN_ERR_INVALID, "wrnn_stream_push: %lld steps are ready, the outputs must hold B * steps = %lld elements (capacity %lld)",
+        return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_stream_push: %lld steps are ready, the outputs must hold B * steps = %lld elements (capacity %lld)",
                      (long long)n, (long long)B * n, (long long)out_capacity);
-    if (n > INT32_MAX / 2) return sfail(h, WRNN_ERR_INVALID, "wrnn_stream_push: push too long");
-    S_TRY(h, hipSetDevice(h->cfg.device));
+    if (n > INT32_MAX / 2) return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_stream_push: push too long");
+    WRNN_HIP_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     const int hn = (int)(st->frames_in - st->hist0);
     const float *hist = st->hist[st->cur];
@@ -185,73 +157,43 @@ int wrnn_stream_push(wrnn_stream *st, const float *mels_dev, int32_t n_frames, i
         // window: frames [f0, f1) own the ready steps, their conditioning reads mel frames [f0 - P, f1 + P)
         const int64_t f0 = s0 / HOP, f1 = (s1 + HOP - 1) / HOP;
         const int Tw = (int)(f1 - f0), nW = Tw + 2 * P;
-        if (f0 - P >= 0 && f0 - P < st->hist0) return sfail(h, WRNN_ERR_STATE, "internal: mel history lost frame %lld", (long long)(f0 - P));
-        if (int rc = ensure(h, st->win, st->win_cap, (size_t)B * F * nW)) return rc;
-        S_TRY(h, launch_gather(hist, st->hist0, hn, mels_dev, st->frames_in, n_frames, st->win, f0 - P, nW, B, F, fin, s));
-        if (int rc = ensure(h, st->aux, st->aux_cap, (size_t)B * Tw * d.R)) return rc;
-        S_TRY(h, wrnn_launch_resnet(h, st->win, B, Tw, nW, P, st->aux, s));
+        if (f0 - P >= 0 && f0 - P < st->hist0) return wrnn_fail(h, WRNN_ERR_STATE, "internal: mel history lost frame %lld", (long long)(f0 - P));
+        if (int rc = wrnn_grow(h, st->win, st->win_cap, (size_t)B * F * nW)) return rc;
+        WRNN_HIP_TRY(h, launch_gather(hist, st->hist0, hn, mels_dev, st->frames_in, n_frames, st->win, f0 - P, nW, B, F, fin, s));
+        if (int rc = wrnn_grow(h, st->aux, st->aux_cap, (size_t)B * Tw * d.R)) return rc;
+        WRNN_HIP_TRY(h, wrnn_launch_resnet(h, st->win, B, Tw, nW, P, st->aux, s));
         const int32_t row_steps = st->kernel == WRNN_KERNEL_SIMPLE ? (int32_t)n : INT32_MAX;
         hipLaunchKernelGGL(stream_rows_kernel, dim3((st->n_slots + 255) / 256), dim3(256), 0, s, st->rows, st->sched, B, st->n_slots,
                            row_steps, -f0 * (int64_t)HOP);
-        S_TRY(h, hipGetLastError());
+        WRNN_HIP_TRY(h, hipGetLastError());
+        // the loop arguments of the push; TEAM2 takes its sampling fields from them
+        WrnnLoopArgs a{};
+        a.w = h->wdev; a.off = h->off; a.d = d; a.mels = st->win; a.mel_T = nW; a.mel_off = P; a.aux_frames = st->aux; a.rows = st->rows;
+        a.n_rows = B; a.T = Tw; a.total_len = (int64_t)Tw * HOP; a.steps = n;
+        a.noise_mode = st->noise_mode; a.seed = st->seed;
+        a.labels_out = labels_out_dev ? labels_out_dev - s0 : nullptr; a.samples_out = samples_out_dev - s0; a.err = st->err;
+        a.seg0 = s0; a.state = st->state;
         if (st->kernel == WRNN_KERNEL_SIMPLE) {
-            WrnnLoopArgs a{};
-            a.w = h->wdev; a.off = h->off; a.d = d; a.mels = st->win; a.mel_T = nW; a.mel_off = P; a.aux_frames = st->aux; a.rows = st->rows;
-            a.n_rows = B; a.T = Tw; a.total_len = (int64_t)Tw * HOP; a.steps = n;
-            a.noise_mode = st->noise_mode; a.seed = st->seed;
-            a.labels_out = labels_out_dev ? labels_out_dev - s0 : nullptr; a.samples_out = samples_out_dev - s0; a.err = st->err;
-            a.seg0 = s0; a.state = st->state;
-            S_TRY(h, wrnn_launch_loop_simple(a, s));
+            WRNN_HIP_TRY(h, wrnn_launch_loop_simple(a, s));
         } else {
-            // the offline TEAM2 prologue (api.hip, wrnn_generate) on the window: T = Tw, mels (B, F, Tw + 2P) padded by P
-            const int H = d.H, FC = d.FC, A = d.A, R = d.R;
-            const int TP = Tw + 2 * P, T1 = Tw + 1;
-            const size_t nCM = (size_t)B * TP * H, nCA = (size_t)B * T1 * H, nVM = (size_t)B * TP * 3 * H, nVA = (size_t)B * T1 * 3 * H;
-            const size_t nC2 = (size_t)B * T1 * 3 * H, nC3 = (size_t)B * T1 * FC, nC4 = (size_t)B * T1 * FC, nREC = (size_t)B * T1 * H * 28;
-            if (int rc = ensure(h, st->tab, st->tab_cap, nCM + nCA + nVM + nVA + nC2 + nC3 + nC4 + nREC)) return rc;
-            float *tCM = st->tab, *tCA = tCM + nCM, *tVM = tCA + nCA, *tVA = tVM + nVM, *tC2 = tVA + nVA, *tC3 = tC2 + nC2, *tC4 = tC3 + nC3,
-                  *tREC = tC4 + nC4;
-            const float *w = h->wdev, *aux = st->aux;
-            const WrnnPacked &o = h->off;
-            S_TRY(h, wrnn_launch_frame_linear(1, st->win, (size_t)F * nW, 0, 0, w + o.I_t + (size_t)1 * H, H, nullptr, tCM, (size_t)TP * H, TP, F, H, B, nW, 0, s));
-            S_TRY(h, wrnn_launch_frame_linear(0, aux, (size_t)Tw * R, R, Tw, w + o.I_t + (size_t)(1 + F) * H, H, w + o.I_b, tCA, (size_t)T1 * H, T1, A, H, B, Tw, P, s));
-            S_TRY(h, wrnn_launch_frame_linear(0, tCM, (size_t)TP * H, H, TP, w + o.r1_wih_t, 3 * H, nullptr, tVM, (size_t)TP * 3 * H, TP, H, 3 * H, B, Tw, P, s));
-            S_TRY(h, wrnn_launch_frame_linear(0, tCA, (size_t)T1 * H, H, T1, w + o.r1_wih_t, 3 * H, w + o.r1_bih, tVA, (size_t)T1 * 3 * H, T1, H, 3 * H, B, Tw, P, s));
-            S_TRY(h, wrnn_launch_frame_linear(0, aux + A, (size_t)Tw * R, R, Tw, w + o.r2_wih_t + (size_t)H * 3 * H, 3 * H, w + o.r2_bih, tC2, (size_t)T1 * 3 * H, T1, A, 3 * H, B, Tw, P, s));
-            S_TRY(h, wrnn_launch_frame_linear(0, aux + 2 * A, (size_t)Tw * R, R, Tw, w + o.fc1_t + (size_t)H * FC, FC, w + o.fc1_b, tC3, (size_t)T1 * FC, T1, A, FC, B, Tw, P, s));
-            S_TRY(h, wrnn_launch_frame_linear(0, aux + 3 * A, (size_t)Tw * R, R, Tw, w + o.fc2_t + (size_t)FC * FC, FC, w + o.fc2_b, tC4, (size_t)T1 * FC, T1, A, FC, B, Tw, P, s));
-            S_TRY(h, wrnn_launch_pack_records(tCM, tCA, tVM, tVA, tREC, B, Tw, P, nullptr, s));
-            // segments as wrnn_generate sizes them (the conditioning chunk of all rows ~64 MB, multiples of 32 steps); every segment
-            // start s0 + k * seg lies on a 32-step boundary because s0 does
-            int64_t seg = ((int64_t)(64u << 20) / ((int64_t)B * H * 4 * (int64_t)sizeof(float))) & ~(int64_t)31;
-            if (seg > 16384) seg = 16384;
-            if (seg < 2048) seg = 2048;
-            if (seg > n) seg = n;
-            if (int rc = ensure(h, st->cond, st->cond_cap, (size_t)B * (size_t)seg * H * 4)) return rc;
+            // the offline TEAM2 prologue and segment loop (launch.hip) on the window: T = Tw, mels (B, F, Tw + 2P) padded by P
+            WrnnFrameTables t;
+            if (int rc = wrnn_build_frame_tables(h, st->tab, st->tab_cap, st->win, nW, 0, st->aux, B, Tw, 28, t, s)) return rc;
+            WRNN_HIP_TRY(h, wrnn_launch_pack_records(t.CM, t.CA, t.VM, t.VA, t.REC, B, Tw, P, nullptr, s));
+            // every segment start s0 + k * seg lies on a 32-step boundary because s0 does
+            const int64_t seg = wrnn_team2_segment_len(B, d.H, n, 0);
+            if (int rc = wrnn_grow(h, st->cond, st->cond_cap, (size_t)B * (size_t)seg * d.H * 4)) return rc;
             WrnnTeamArgs ta{};
-            ta.w = w; ta.off = o; ta.d = d; ta.team_w = h->team_w; ta.team_fc3 = h->team_fc3; ta.wI0 = h->wI0; ta.u1 = h->u1;
-            ta.tabREC = tREC; ta.tabCOND = st->cond; ta.tabC2 = tC2; ta.tabC3 = tC3; ta.tabC4 = tC4;
+            ta.w = a.w; ta.off = a.off; ta.d = d; ta.team_w = h->team_w; ta.team_fc3 = h->team_fc3; ta.wI0 = h->wI0; ta.u1 = h->u1;
+            ta.tabREC = t.REC; ta.tabC2 = t.C2; ta.tabC3 = t.C3; ta.tabC4 = t.C4;
             // B == 1: the uniform instantiation offline calls run, its outputs at [t] whatever a.steps is (a.steps past every step:
             // the state is always handed on); B > 1: the ragged one, whose rows end at rows[r].steps (never) and write at [r * n + t]
             ta.rows = st->rows; ta.sched = st->sched; ta.n_slots = st->n_slots; ta.ragged = B > 1; ta.n_rows = B; ta.n_teams = h->n_teams;
-            ta.T = Tw; ta.total_len = (int64_t)Tw * HOP; ta.steps = B > 1 ? n : (int64_t)1 << 62;
+            ta.T = Tw; ta.total_len = a.total_len; ta.steps = B > 1 ? n : (int64_t)1 << 62;
             ta.state = st->state;
-            ta.noise_mode = st->noise_mode; ta.seed = st->seed;
-            ta.labels_out = labels_out_dev ? labels_out_dev - s0 : nullptr; ta.samples_out = samples_out_dev - s0;
+            wrnn_copy_sampling(ta, a);
             ta.mail = h->mail; ta.ctl = h->ctl; ta.err = st->err; ta.prof = nullptr;
-            const size_t mail_bytes = (size_t)8 * WRNN_MAIL_GRANULES_MAX * sizeof(unsigned long long);
-            for (int64_t t0 = s0; t0 < s1; t0 += seg) {
-                const int64_t len = s1 - t0 < seg ? s1 - t0 : seg;
-                S_TRY(h, wrnn_launch_cond_stream(tREC, w + o.ktab, st->rows, st->cond, B, Tw, HOP, ta.total_len, t0, len, s));
-                ta.seg0 = t0; ta.seg_len = len;
-                S_TRY(h, wrnn_team_gate_enter(h->cfg.device, s));   // see wrnn_generate: mailbox reset and launch inside the gate
-                hipError_t le = hipMemsetAsync(h->mail, 0, mail_bytes, s);
-                if (le == hipSuccess) le = hipMemsetAsync(h->ctl, 0, 128, s);
-                if (le == hipSuccess) le = wrnn_launch_loop_team2(ta, s);
-                const hipError_t ge = wrnn_team_gate_leave(h->cfg.device, s);
-                S_TRY(h, le);
-                S_TRY(h, ge);
-            }
+            if (int rc = wrnn_run_team2_segments(h, ta, st->cond, s0, s1, seg, nullptr, s)) return rc;
         }
     }
     // mel history for the next push: frames [keep0, fin), keep0 = the first frame the next window can reach
@@ -261,8 +203,8 @@ int wrnn_stream_push(wrnn_stream *st, const float *mels_dev, int32_t n_frames, i
         if (keep0 > fin) keep0 = fin;
         const int nk = (int)(fin - keep0);
         const int nxt = 1 - st->cur;
-        if (int rc = ensure(h, st->hist[nxt], st->hist_cap[nxt], (size_t)B * F * (nk > 0 ? nk : 1))) return rc;
-        S_TRY(h, launch_gather(hist, st->hist0, hn, mels_dev, st->frames_in, n_frames, st->hist[nxt], keep0, nk, B, F, fin, s));
+        if (int rc = wrnn_grow(h, st->hist[nxt], st->hist_cap[nxt], (size_t)B * F * (nk > 0 ? nk : 1))) return rc;
+        WRNN_HIP_TRY(h, launch_gather(hist, st->hist0, hn, mels_dev, st->frames_in, n_frames, st->hist[nxt], keep0, nk, B, F, fin, s));
         st->cur = nxt;
         st->hist0 = keep0;
     }
@@ -276,16 +218,16 @@ int wrnn_stream_push(wrnn_stream *st, const float *mels_dev, int32_t n_frames, i
 int wrnn_stream_sync(wrnn_stream *st, void *stream) {
     if (!st) return WRNN_ERR_INVALID;
     wrnn_handle *h = st->h;
-    S_TRY(h, hipSetDevice(h->cfg.device));
-    S_TRY(h, hipStreamSynchronize((hipStream_t)stream));
+    WRNN_HIP_TRY(h, hipSetDevice(h->cfg.device));
+    WRNN_HIP_TRY(h, hipStreamSynchronize((hipStream_t)stream));
     unsigned errw = 0;
-    S_TRY(h, hipMemcpy(&errw, st->err, sizeof(errw), hipMemcpyDeviceToHost));
+    WRNN_HIP_TRY(h, hipMemcpy(&errw, st->err, sizeof(errw), hipMemcpyDeviceToHost));
     if (!errw) return WRNN_OK;
     st->poisoned = true;
     if (errw == WRNN_DEVERR_BUSY)
-        return sfail(h, WRNN_ERR_BUSY, "the stream's team kernel could not get its workgroups resident (the GPU is shared with another kernel): "
+        return wrnn_fail(h, WRNN_ERR_BUSY, "the stream's team kernel could not get its workgroups resident (the GPU is shared with another kernel): "
                                        "the stream cannot continue; open a new one (WRNN_KERNEL_SIMPLE runs anywhere)");
-    return sfail(h, WRNN_ERR_TIMEOUT, "device-side bounded spin gave up in a stream push (code %u)", errw);
+    return wrnn_fail(h, WRNN_ERR_TIMEOUT, "device-side bounded spin gave up in a stream push (code %u)", errw);
 }
 
 int wrnn_stream_info(const wrnn_stream *st, int64_t *frames_in, int64_t *steps_done, int64_t *workspace_bytes) {

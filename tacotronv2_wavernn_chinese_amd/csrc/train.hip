@@ -746,12 +746,8 @@ static int train_impl(wrnn_handle *h, int phase, const wrnn_loop_params *w, cons
         ta.img = img; ta.bhh = bhh[i]; ta.GI = q.GI; ta.Hs = q.H; ta.HP = q.HP; ta.Rs = q.R; ta.Zs = q.Z; ta.Ns = q.N; ta.GHN = q.GHN;
         ta.dHext = dHext; ta.dGI = q.dGI; ta.dGH = q.dGH; ta.B = B; ta.L = L; ta.n_teams = h->n_teams; ta.rpb = rpb;
         ta.mail = st->mail; ta.ctl = st->ctl; ta.err = h->err_dev;
-        if ((e = wrnn_team_gate_enter(h->cfg.device, s)) != hipSuccess) return e;   // team kernels of a device run one after the other
-        e = hipMemsetAsync(st->mail, 0, (size_t)h->n_teams * wrnn_gru_team_mail_granules(nq, bwd) * sizeof(unsigned long long), s);
-        if (e == hipSuccess) e = hipMemsetAsync(st->ctl, 0, 256, s);
-        if (e == hipSuccess) e = wrnn_gru_team_launch(ta, nq, bwd, s);
-        const hipError_t ge = wrnn_team_gate_leave(h->cfg.device, s);
-        return e != hipSuccess ? e : ge;
+        return wrnn_gated_launch(h->cfg.device, s, st->mail, (size_t)h->n_teams * wrnn_gru_team_mail_granules(nq, bwd) * sizeof(unsigned long long),
+                                 st->ctl, 256, [&] { return wrnn_gru_team_launch(ta, nq, bwd, s); });
     };
     const float *a1 = aux_dev, *a2 = aux_dev + A, *a3 = aux_dev + 2 * A, *a4 = aux_dev + 3 * A;   // aux channel split (:198-199)
 

@@ -169,7 +169,7 @@ struct WrnnLoopArgs {
 };
 __host__ __device__ inline int wrnn_simple_state_floats(const WrnnDims &d) { return 2 * d.H + 4; }
 
-// Team kernel (loop_team.hip): mailbox size per team in 8-byte granules:
+// Team kernel (loop_team2.hip): mailbox size per team in 8-byte granules:
 // x3, fc1, fc2, race winners (2 x 512 each), gh1 (2 x 1536)
 #define WRNN_TEAM_MAIL_GRANULES (8 * 512 + 2 * 1536)
 #define WRNN_TEAM_NWREG 352
@@ -228,6 +228,7 @@ struct WrnnTeamArgs {
 #define WRNN_BATCH_MAIL_GRANULES (10 * 8 * 512 + 2 * 8 * 128)
 #define WRNN_BATCH_MAX_ROWS 8
 #define WRNN_MAIL_GRANULES_MAX (WRNN_BATCH_MAIL_GRANULES > WRNN_TEAM_MAIL_GRANULES ? WRNN_BATCH_MAIL_GRANULES : WRNN_TEAM_MAIL_GRANULES)
+#define WRNN_MAIL_BYTES ((size_t)8 * WRNN_MAIL_GRANULES_MAX * sizeof(unsigned long long))   // wrnn_handle::mail, 8 teams
 
 struct WrnnBatchArgs {
     const float *w;           // packed weights (biases, ktab)
@@ -305,9 +306,9 @@ hipError_t wrnn_team2_occupancy(int mode, bool prof, int *blocks_per_cu, size_t 
 // kernel launched on `device` by any handle / stream and takes the device's launch lock, leave() records the new tail and
 // releases the lock.  Nothing blocks on the GPU's progress; only the launching threads are serialised.
 hipError_t wrnn_team_gate_enter(int device, hipStream_t s);
+hipError_t wrnn_team_gate_leave(int device, hipStream_t s);
 // why the XCD-team kernels cannot run for this handle, or nullptr (api.hip; what AUTO and wrnn_team_info decide on)
 const char *wrnn_loop_team_obstacle(const wrnn_handle *h);
-hipError_t wrnn_team_gate_leave(int device, hipStream_t s);
 hipError_t wrnn_launch_loss(int mode, const float *y_hat, const void *y, int NC, long n_rows, double *partial, int *bad, float *out,
                             hipStream_t s);
 // rows[r] = {utt, steps, start}; order[] = rows sorted by steps, longest first (stable), when frames != null, else identity;
@@ -337,3 +338,62 @@ hipError_t wrnn_launch_pack_records(const float *CM, const float *CA, const floa
 hipError_t wrnn_launch_frame_linear(int mode, const float *src, size_t src_bstride, int ld, int valid, const float *Wt,
                                     int ldw, const float *bias, float *out, size_t out_bstride, int frames, int K,
                                     int N, int B, int T, int P, hipStream_t s);
+
+// ---- host launch path of the team kernels, shared by the offline calls (api.hip), the streams (stream.hip) and training (train.hip) ----
+
+// h->err = the formatted message (h may be null); returns `code` (launch.hip)
+int wrnn_fail(wrnn_handle *h, int code, const char *fmt, ...);
+#define WRNN_HIP_TRY(h, expr)                                                                                \
+    do {                                                                                                     \
+        hipError_t e__ = (expr);                                                                             \
+        if (e__ != hipSuccess) return wrnn_fail((h), WRNN_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e__)); \
+    } while (0)
+
+// Grow-only device scratch of `need` elements: kept while it is large enough, so a buffer stays at its high-water mark.  A failed
+// allocation leaves p null and cap 0.
+template <typename T>
+int wrnn_grow(wrnn_handle *h, T *&p, size_t &cap, size_t need) {
+    if (need <= cap) return WRNN_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+    WRNN_HIP_TRY(h, hipMalloc(&p, need * sizeof(T)));
+    cap = need;
+    return WRNN_OK;
+}
+
+// One team-kernel launch inside the device's gate.  Team kernels of one device run one after the other, whatever handle / stream
+// launches them (wavernn_amd.h); the mailbox and arrival-counter resets belong inside the gate: the previous team kernel on these
+// buffers may still be reading them.  The gate is left on every path; the first error wins.
+template <typename Launch>
+hipError_t wrnn_gated_launch(int device, hipStream_t s, void *mail, size_t mail_bytes, void *ctl, size_t ctl_bytes, Launch launch) {
+    hipError_t e = wrnn_team_gate_enter(device, s);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(mail, 0, mail_bytes, s);
+    if (e == hipSuccess) e = hipMemsetAsync(ctl, 0, ctl_bytes, s);
+    if (e == hipSuccess) e = launch();
+    const hipError_t ge = wrnn_team_gate_leave(device, s);
+    return e != hipSuccess ? e : ge;
+}
+
+// the ten sampling fields WrnnBatchArgs and WrnnTeamArgs share with the WrnnLoopArgs of the same call
+template <typename Dst>
+void wrnn_copy_sampling(Dst &dst, const WrnnLoopArgs &a) {
+    dst.noise_mode = a.noise_mode; dst.seed = a.seed; dst.keys = a.keys; dst.noise1 = a.noise1; dst.noise2 = a.noise2;
+    dst.x_forced = a.x_forced; dst.x_init = a.x_init; dst.logits_out = a.logits_out; dst.labels_out = a.labels_out; dst.samples_out = a.samples_out;
+}
+
+// Per-frame tables of the team kernels (see WrnnTeamArgs): the conditioning pushed through the linear layers it feeds, once per call
+// or stream window.  CM | CA | VM | VA | C2 | C3 | C4 | REC in one allocation; REC (B, T+1, H, rec_floats) is left to the caller's
+// wrnn_launch_pack_records (28 floats, TEAM2) / wrnn_launch_pack_records32 (32, the batch kernels).
+struct WrnnFrameTables {
+    float *CM, *CA, *VM, *VA, *C2, *C3, *C4, *REC;
+};
+// `mels` (B, F, mel_T) with frame 0 at index P - mel_shift (wrnn_launch_resnet's mel_off), aux (B, T, R); buf / cap grow on demand
+int wrnn_build_frame_tables(wrnn_handle *h, float *&buf, size_t &cap, const float *mels, int mel_T, int mel_shift, const float *aux, int B,
+                            int T, int rec_floats, WrnnFrameTables &t, hipStream_t s);
+// TEAM2 runs steps [t_begin, t_end) of every row in segments of `seg` steps, one conditioning chunk + one gated launch each (the
+// reasons are at wrnn_team2_segment_len, launch.hip); seg_override: wrnn_sample_opts.team2_segment, 0 = the library's choice
+int64_t wrnn_team2_segment_len(int rows, int H, int64_t steps, int seg_override);
+// ta complete but for seg0 / seg_len / tabCOND; cond holds n_rows * seg * H * 4 floats; *launches (may be null) = segments run
+int wrnn_run_team2_segments(wrnn_handle *h, WrnnTeamArgs &ta, float *cond, int64_t t_begin, int64_t t_end, int64_t seg, int *launches,
+                            hipStream_t s);

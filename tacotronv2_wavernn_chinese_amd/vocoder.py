@@ -163,6 +163,18 @@ def request_seeds(seeds, n_utterances, noise_mode=_cabi.NOISE_PHILOX, seed=None)
     return np.array([v & 0xFFFFFFFFFFFFFFFF for v in vals], dtype=np.uint64)
 
 
+def _draw_call_seed(native_opts):
+    """The Philox seed of a call that was given none: one draw from the global torch generator, so that ``torch.manual_seed`` makes the
+    call reproducible like it does for the reference."""
+    if 'seed' not in native_opts and native_opts.get('noise_mode', _cabi.NOISE_PHILOX) in (_cabi.NOISE_PHILOX, 'philox'):
+        native_opts['seed'] = int(torch.randint(0, 2 ** 62, (1,)).item())
+
+
+def _fade_broadcast_error(wave_len, hop):
+    """The ``ValueError`` the reference's 20-hop fade-out raises for a clip of fewer than 21 frames (:256-258)."""
+    return ValueError(f'operands could not be broadcast together with shapes ({max(wave_len, 0)},) ({20 * hop},) ({max(wave_len, 0)},)')
+
+
 def _device_teams(dev) -> int:
     dev = torch.device(dev)
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
@@ -215,6 +227,15 @@ def reference_noise(mode: str, rows: int, steps: int, n_classes: int, rnn_dims: 
 
 _NOISE_REFERENCE = -1   # host-side mode: resolved to NOISE_INJECTED with the reference's own draws before the C-ABI call
 _NOISE_MODES = {'philox': _cabi.NOISE_PHILOX, 'injected': _cabi.NOISE_INJECTED, 'argmax': _cabi.NOISE_ARGMAX, 'reference': _NOISE_REFERENCE}
+
+
+def _noise_mode_id(noise_mode):
+    """A ``noise_mode`` argument as its id: names are looked up (``ValueError`` for an unknown one), ids pass."""
+    if not isinstance(noise_mode, str):
+        return noise_mode
+    if noise_mode not in _NOISE_MODES:
+        raise ValueError(f'noise_mode must be one of {sorted(_NOISE_MODES)} or a WRNN_NOISE_* id, got {noise_mode!r}')
+    return _NOISE_MODES[noise_mode]
 
 
 class WaveRNN(nn.Module):
@@ -458,10 +479,7 @@ class WaveRNN(nn.Module):
         seeds (unbatched calls only): B ints instead, one per utterance -- row b draws exactly what a call on utterance b alone with
         ``seed=seeds[b]`` draws (same kernel), whatever else is in the batch and wherever it stands (``request_seeds``).
         """
-        if isinstance(noise_mode, str):
-            if noise_mode not in _NOISE_MODES:
-                raise ValueError(f'noise_mode must be one of {sorted(_NOISE_MODES)} or a WRNN_NOISE_* id, got {noise_mode!r}')
-            noise_mode = _NOISE_MODES[noise_mode]
+        noise_mode = _noise_mode_id(noise_mode)
         seeds_np = None
         if seeds is not None:
             if batched:
@@ -484,57 +502,62 @@ class WaveRNN(nn.Module):
             ragged = frames is not None
             samples = (torch.zeros if ragged else torch.empty)((rows, steps), dtype=torch.float32, device=dev)
             labels = (torch.zeros if ragged else torch.empty)((rows, steps), dtype=torch.int32, device=dev)
-            keep = []
-            fr = 0
+            fr_t = None
             if ragged:
                 fr_t = torch.as_tensor(frames).to(device=dev, dtype=torch.int32).contiguous()
                 if tuple(fr_t.shape) != (B,):
                     raise ValueError(f'frames must have shape ({B},), got {tuple(fr_t.shape)}')
-                keep.append(fr_t)
-                fr = fr_t.data_ptr()
-            us = 0
-            if seeds_np is not None:
-                us_t = torch.from_numpy(seeds_np.view(np.int64)).to(dev)   # the bits of the uint64 keys
-                keep.append(us_t)
-                us = us_t.data_ptr()
-
-            def to_dev(a, shape):
-                if a is None:
-                    return 0
-                t = torch.as_tensor(a).to(device=dev, dtype=torch.float32).contiguous()
-                if tuple(t.shape) != shape:
-                    raise ValueError(f'expected shape {shape}, got {tuple(t.shape)}')
-                keep.append(t)
-                return t.data_ptr()
-            nmix = self.n_classes if self.mode == 'RAW' else self.n_classes // 3
             if noise_mode == _NOISE_REFERENCE:
                 if noise1 is not None or noise2 is not None:
                     raise ValueError("noise_mode='reference' draws its own noise: noise1 / noise2 must be None")
                 noise1, noise2 = reference_noise(self.mode, rows, steps, self.n_classes, self.rnn_dims, self.aux_dims, dev)
                 noise_mode = _cabi.NOISE_INJECTED
-            n1 = to_dev(noise1, (steps, rows, nmix))
-            n2 = to_dev(noise2, (steps, rows))
-            xf = to_dev(x_forced, (steps, rows))
-            xi = to_dev(x_init, (rows,))
             logits = torch.empty((steps, rows, self.n_classes), dtype=torch.float32, device=dev) if want_logits else None
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            want_kernel = self.kernel if kernel is None else kernel
 
-            def launch(k):
-                nat.generate(mels_t.data_ptr(), B, T, batched, target, overlap,
-                             labels_ptr=labels.data_ptr(), samples_ptr=samples.data_ptr(), stream=stream,
-                             noise_mode=noise_mode, seed=int(seed), noise1_ptr=n1, noise2_ptr=n2, x_forced_ptr=xf,
-                             logits_ptr=logits.data_ptr() if logits is not None else 0,
-                             kernel=k, x_init_ptr=xi, mels_padded=mels_padded,
-                             frames_ptr=fr, batch_rows=batch_rows, team2_segment=team2_segment, utt_seeds_ptr=us)
-                return nat.last_timing()  # synchronises; surfaces device-side errors
-            self._launch_with_busy_retry(nat, launch, want_kernel, steps)
-            frames_dev = keep[0] if ragged else None
-            del keep
-        return dict(samples=samples, labels=labels, logits=logits, rows=rows, steps=steps, frames=frames_dev)
+            def call(**staged):
+                nat.generate(mels_t.data_ptr(), B, T, batched, target, overlap, labels_ptr=labels.data_ptr(), samples_ptr=samples.data_ptr(),
+                             logits_ptr=logits.data_ptr() if logits is not None else 0, mels_padded=mels_padded,
+                             frames_ptr=fr_t.data_ptr() if ragged else 0, batch_rows=batch_rows, team2_segment=team2_segment, **staged)
+            self._stage_and_launch(nat, dev, call, rows, steps, noise_mode, seed, seeds_np, noise1, noise2, kernel,
+                                   x_forced_ptr=(x_forced, (steps, rows)), x_init_ptr=(x_init, (rows,)))
+        return dict(samples=samples, labels=labels, logits=logits, rows=rows, steps=steps, frames=fr_t)
+
+    def _stage_and_launch(self, nat, dev, call, rows, steps, noise_mode, seed, seeds_np, noise1, noise2, kernel, **extra):
+        """What ``generate_raw`` and ``generate_raw_folded`` do alike once rows and steps are known: upload the per-utterance seeds, the
+        injected noise and the ``extra`` float32 arrays (keyword of the native call = (array-like or None, required shape); None becomes
+        a null pointer), resolve the kernel (None: the model's; a name or a WRNN_KERNEL_* id) and run ``call(kernel=, noise_mode=,
+        seed=, utt_seeds_ptr=, stream=, noise1_ptr=, noise2_ptr=, **extra pointers)`` under the busy-GPU policy.  The uploads live
+        until the call has synchronised (``last_timing``)."""
+        keep = []
+        us = 0
+        if seeds_np is not None:
+            keep.append(torch.from_numpy(seeds_np.view(np.int64)).to(dev))   # the bits of the uint64 keys
+            us = keep[-1].data_ptr()
+
+        def to_dev(a, shape):
+            if a is None:
+                return 0
+            t = torch.as_tensor(a).to(device=dev, dtype=torch.float32).contiguous()
+            if tuple(t.shape) != shape:
+                raise ValueError(f'expected shape {shape}, got {tuple(t.shape)}')
+            keep.append(t)
+            return t.data_ptr()
+        nmix = self.n_classes if self.mode == 'RAW' else self.n_classes // 3
+        ptrs = dict(noise1_ptr=to_dev(noise1, (steps, rows, nmix)), noise2_ptr=to_dev(noise2, (steps, rows)))
+        ptrs.update((name, to_dev(a, shape)) for name, (a, shape) in extra.items())
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        want_kernel = self.kernel if kernel is None else kernel
+        if isinstance(want_kernel, str):
+            want_kernel = _cabi.KERNEL_IDS[want_kernel]
+
+        def launch(k):
+            call(kernel=k, noise_mode=noise_mode, seed=int(seed), utt_seeds_ptr=us, stream=stream, **ptrs)
+            return nat.last_timing()  # synchronises; surfaces device-side errors
+        self._launch_with_busy_retry(nat, launch, want_kernel, steps)
 
     def _launch_with_busy_retry(self, nat, launch, want_kernel, steps):
-        """``self.last_timing = launch(kernel)`` with the policy for a busy GPU."""
+        """``self.last_timing = launch(kernel)`` with the policy for a busy GPU.  Called by ``_stage_and_launch``: the slow-path warning is
+        attributed to ITS caller (``generate_raw`` / ``generate_raw_folded``), four frames up."""
         try:
             self.last_timing = launch(want_kernel)
         except _cabi.WrnnError as e:
@@ -548,10 +571,10 @@ class WaveRNN(nn.Module):
             except _cabi.WrnnError as e2:
                 if e2.code != _cabi.ERR_BUSY:
                     raise
-                self._warn_slow_path(f'the GPU is shared with another kernel ({e2})', steps)
+                self._warn_slow_path(f'the GPU is shared with another kernel ({e2})', steps, stacklevel=4)
                 self.last_timing = launch(_cabi.KERNEL_SIMPLE)
         if want_kernel == _cabi.KERNEL_AUTO and self.last_timing['kernel'] == _cabi.KERNEL_SIMPLE and not getattr(self, '_slow_warned', False):
-            self._warn_slow_path(nat.team_info()[2] or 'the team kernels cannot run on this device', steps)
+            self._warn_slow_path(nat.team_info()[2] or 'the team kernels cannot run on this device', steps, stacklevel=4)
 
     def generate_raw_folded(self, mels, frames, target, overlap, *, noise_mode=_cabi.NOISE_PHILOX, seed=None, noise1=None, noise2=None,
                             kernel=None, batch_rows=0, team2_segment=0, rows_total=None, seeds=None):
@@ -564,10 +587,7 @@ class WaveRNN(nn.Module):
         same kernel and batch_rows, whatever else is in the call; with the call-wide ``seed`` (default 0) a row is keyed by its GLOBAL row
         index fold0[b] + i, so a clip's audio depends on its position in the call.  rows_total: test hook, overrides the planned row
         count."""
-        if isinstance(noise_mode, str):
-            if noise_mode not in _NOISE_MODES:
-                raise ValueError(f'noise_mode must be one of {sorted(_NOISE_MODES)} or a WRNN_NOISE_* id, got {noise_mode!r}')
-            noise_mode = _NOISE_MODES[noise_mode]
+        noise_mode = _noise_mode_id(noise_mode)
         if noise_mode == _NOISE_REFERENCE:
             raise ValueError("noise_mode='reference' replays the reference's own generate(): it has no call that folds several utterances")
         fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
@@ -587,46 +607,21 @@ class WaveRNN(nn.Module):
             samples = torch.empty((rows, steps), dtype=torch.float32, device=dev)
             labels = torch.empty((rows, steps), dtype=torch.int32, device=dev)
             fr_t = torch.from_numpy(fr).to(dev)
-            keep = []
-            us = 0
-            if seeds_np is not None:
-                us_t = torch.from_numpy(seeds_np.view(np.int64)).to(dev)   # the bits of the uint64 keys
-                keep.append(us_t)
-                us = us_t.data_ptr()
 
-            def to_dev(a, shape):
-                if a is None:
-                    return 0
-                t = torch.as_tensor(a).to(device=dev, dtype=torch.float32).contiguous()
-                if tuple(t.shape) != shape:
-                    raise ValueError(f'expected shape {shape}, got {tuple(t.shape)}')
-                keep.append(t)
-                return t.data_ptr()
-            nmix = self.n_classes if self.mode == 'RAW' else self.n_classes // 3
-            n1 = to_dev(noise1, (steps, rows, nmix))
-            n2 = to_dev(noise2, (steps, rows))
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            want_kernel = self.kernel if kernel is None else kernel
-            if isinstance(want_kernel, str):
-                want_kernel = _cabi.KERNEL_IDS[want_kernel]
-
-            def launch(k):
+            def call(**staged):
                 nat.generate_folded(mels_t.data_ptr(), B, T, fr_t.data_ptr(), rows, target, overlap, labels_ptr=labels.data_ptr(),
-                                    samples_ptr=samples.data_ptr(), stream=stream, noise_mode=noise_mode, seed=int(seed), noise1_ptr=n1,
-                                    noise2_ptr=n2, kernel=k, batch_rows=batch_rows, team2_segment=team2_segment, utt_seeds_ptr=us)
-                return nat.last_timing()  # synchronises; surfaces device-side errors
-            self._launch_with_busy_retry(nat, launch, want_kernel, steps)
-            del keep
+                                    samples_ptr=samples.data_ptr(), batch_rows=batch_rows, team2_segment=team2_segment, **staged)
+            self._stage_and_launch(nat, dev, call, rows, steps, noise_mode, seed, seeds_np, noise1, noise2, kernel)
         return dict(samples=samples, labels=labels, fold0=fold0, rows=rows, steps=steps, frames=fr_t, B=B, target=int(target), overlap=int(overlap))
 
-    def _warn_slow_path(self, why: str, steps: int):
+    def _warn_slow_path(self, why: str, steps: int, stacklevel: int = 3):
         """Once per model: AUTO is running ``WRNN_KERNEL_SIMPLE`` (one workgroup per row, weights streamed every step, ~1 ms per step:
         ~300x slower than the team kernels and slower than the reference on a few CPU cores)."""
         if getattr(self, '_slow_warned', False):
             return
         self._slow_warned = True
         warnings.warn(f'WaveRNN: generating on the any-shape fallback kernel (WRNN_KERNEL_SIMPLE), ~1 ms per sample step -- about 300x slower '
-                      f'than the XCD-team kernels ({steps} steps: ~{steps * 1e-3:.0f} s per row).  Reason: {why}.', RuntimeWarning, stacklevel=3)
+                      f'than the XCD-team kernels ({steps} steps: ~{steps * 1e-3:.0f} s per row).  Reason: {why}.', RuntimeWarning, stacklevel=stacklevel)
 
     def epilogue_device(self, res, batched, target, overlap, mu_law, wave_len):
         """float64 tail of generate() (:243-258) on the GPU (``wrnn_epilogue``): (wave_len,) float64 cuda tensor."""
@@ -677,35 +672,20 @@ class WaveRNN(nn.Module):
         wave_len = (mels_t.size(-1) - 1) * self.hop_length
         if isinstance(target, str):
             target = self.fold_target_for_device(mels_t.size(-1), overlap, policy=target)
-        if 'seed' not in native_opts and native_opts.get('noise_mode', _cabi.NOISE_PHILOX) in (_cabi.NOISE_PHILOX, 'philox'):
-            native_opts['seed'] = int(torch.randint(0, 2 ** 62, (1,)).item())
+        _draw_call_seed(native_opts)
         res = self.generate_raw(mels_t, batched, target, overlap, **native_opts)
         if self.verbose:
             self.gen_display(res['steps'] - 1, res['steps'], res['rows'], start)
         if epilogue == 'device':
-            if wave_len < 20 * self.hop_length:   # the broadcast error of :258
-                raise ValueError(f'operands could not be broadcast together with shapes ({max(wave_len, 0)},) '
-                                 f'({20 * self.hop_length},) ({max(wave_len, 0)},)')
+            if wave_len < 20 * self.hop_length:
+                raise _fade_broadcast_error(wave_len, self.hop_length)
             output = self.epilogue_device(res, batched, target, overlap, mu_law, wave_len).cpu().numpy()
             save_wav(output, save_path, self.sample_rate)
             self.train()
             return output
         if epilogue != 'host':
             raise ValueError(f"epilogue must be 'host' or 'device', got {epilogue!r}")
-        output = res['samples'].cpu().numpy().astype(np.float64)  # (rows, L)   :243-245
-
-        if mu_law:
-            output = decode_mu_law(output, self.n_classes, False)
-        if batched:
-            output = self.xfade_and_unfold(output, target, overlap)
-        else:
-            output = output[0]
-
-        # Fade-out at the end to avoid signal cutting out suddenly   (:255-258)
-        fade_out = np.linspace(1, 0, 20 * self.hop_length)
-        output = output[:wave_len]
-        output[-20 * self.hop_length:] *= fade_out
-
+        output = self._finish_host(res['samples'].cpu().numpy().astype(np.float64), mu_law, batched, target, overlap, wave_len)
         save_wav(output, save_path, self.sample_rate)
         self.train()
         return output
@@ -789,10 +769,8 @@ class WaveRNN(nn.Module):
             if not arrs or any(a.ndim != 2 or a.shape[0] != self.feat_dims for a in arrs):
                 raise ValueError(f'expected a non-empty sequence of (n_mels={self.feat_dims}, T_i) arrays')
             lens = [a.shape[1] for a in arrs]
-        if min(lens) < 21:   # the fade-out broadcast error of :258, raised before any device work
-            t_bad = min(lens)
-            raise ValueError(f'operands could not be broadcast together with shapes ({max((t_bad - 1) * self.hop_length, 0)},) '
-                             f'({20 * self.hop_length},) ({max((t_bad - 1) * self.hop_length, 0)},)')
+        if min(lens) < 21:   # raised before any device work
+            raise _fade_broadcast_error((min(lens) - 1) * self.hop_length, self.hop_length)
         tmax = max(lens)
         if wavs is not None:
             batch = fe.melspectrogram(list(wavs), device=torch.device('cuda', self._device_index()))   # (B, n_mels, tmax) on the device, zero past each clip
@@ -800,8 +778,8 @@ class WaveRNN(nn.Module):
             batch = np.zeros((len(arrs), self.feat_dims, tmax), np.float32)
             for i, a in enumerate(arrs):
                 batch[i, :, :lens[i]] = a
-        if seeds is None and 'seed' not in native_opts and native_opts.get('noise_mode', _cabi.NOISE_PHILOX) in (_cabi.NOISE_PHILOX, 'philox'):
-            native_opts['seed'] = int(torch.randint(0, 2 ** 62, (1,)).item())
+        if seeds is None:
+            _draw_call_seed(native_opts)
         ragged = len(set(lens)) > 1
         if batched:
             outs = self._generate_many_folded(batch, lens, mu_law, epilogue, target, overlap, native_opts)
@@ -812,27 +790,13 @@ class WaveRNN(nn.Module):
             return outs
         res = self.generate_raw(batch, False, 11000, 550, frames=np.asarray(lens, np.int32) if ragged else None, **native_opts)
         if epilogue == 'device':
-            nat = self.native()
-            dev = res['samples'].device
-            wl_max = (tmax - 1) * self.hop_length
-            with torch.cuda.device(dev):
-                waves = torch.empty((len(arrs), wl_max), dtype=torch.float64, device=dev)
-                nat.epilogue_rows(res['samples'].data_ptr(), res['labels'].data_ptr(), res['rows'], res['steps'], mu_law, wl_max,
-                                  res['frames'].data_ptr() if ragged else 0, waves.data_ptr(), wl_max,
-                                  torch.cuda.current_stream(dev).cuda_stream)
-            waves = waves.cpu().numpy()
-            outs = [waves[i, :(t_i - 1) * self.hop_length].copy() for i, t_i in enumerate(lens)]
+            outs = self._finish_device(res, lens, lambda nat, waves, wl_max, st: nat.epilogue_rows(
+                res['samples'].data_ptr(), res['labels'].data_ptr(), res['rows'], res['steps'], mu_law, wl_max,
+                res['frames'].data_ptr() if ragged else 0, waves, wl_max, st))
         elif epilogue == 'host':
             samples = res['samples'].cpu().numpy().astype(np.float64)
-            outs = []
-            for i, t_i in enumerate(lens):
-                wave_len = (t_i - 1) * self.hop_length
-                out = samples[i, :t_i * self.hop_length]
-                if mu_law:
-                    out = decode_mu_law(out, self.n_classes, False)
-                out = out[:wave_len]
-                out[-20 * self.hop_length:] *= np.linspace(1, 0, 20 * self.hop_length)
-                outs.append(out)
+            outs = [self._finish_host(samples[i:i + 1, :t_i * self.hop_length], mu_law, False, 0, 0, (t_i - 1) * self.hop_length)
+                    for i, t_i in enumerate(lens)]
         else:
             raise ValueError(f"epilogue must be 'host' or 'device', got {epilogue!r}")
         if save_paths is not None:
@@ -852,26 +816,34 @@ class WaveRNN(nn.Module):
         res = self.generate_raw_folded(batch, lens, int(target), int(overlap), **native_opts)
         fold0 = res['fold0']
         if epilogue == 'device':
-            nat = self.native()
-            dev = res['samples'].device
-            wl_max = (max(lens) - 1) * hop
-            with torch.cuda.device(dev):
-                waves = torch.empty((len(lens), wl_max), dtype=torch.float64, device=dev)
-                nat.epilogue_folded(res['samples'].data_ptr(), res['labels'].data_ptr(), len(lens), res['rows'], res['steps'], res['target'],
-                                    res['overlap'], mu_law, res['frames'].data_ptr(), waves.data_ptr(), wl_max,
-                                    torch.cuda.current_stream(dev).cuda_stream)
-            waves = waves.cpu().numpy()
-            return [waves[i, :(t_i - 1) * hop].copy() for i, t_i in enumerate(lens)]
+            return self._finish_device(res, lens, lambda nat, waves, wl_max, st: nat.epilogue_folded(
+                res['samples'].data_ptr(), res['labels'].data_ptr(), len(lens), res['rows'], res['steps'], res['target'], res['overlap'], mu_law,
+                res['frames'].data_ptr(), waves, wl_max, st))
         samples = res['samples'].cpu().numpy().astype(np.float64)   # (rows, steps)   :243-245
-        outs = []
-        for i, t_i in enumerate(lens):
-            out = samples[fold0[i]:fold0[i + 1]]
-            if mu_law:
-                out = decode_mu_law(out, self.n_classes, False)
-            out = self.xfade_and_unfold(np.ascontiguousarray(out), res['target'], res['overlap'])[:(t_i - 1) * hop]
-            out[-20 * hop:] *= np.linspace(1, 0, 20 * hop)
-            outs.append(out)
-        return outs
+        return [self._finish_host(samples[fold0[i]:fold0[i + 1]], mu_law, True, res['target'], res['overlap'], (t_i - 1) * hop)
+                for i, t_i in enumerate(lens)]
+
+    def _finish_host(self, rows_f64, mu_law, batched, target, overlap, wave_len):
+        """float64 host tail of the reference's generate() (:243-258) for one clip: rows_f64 (rows, L) are its loop outputs -- its folds
+        when batched, else row 0 is the clip.  Decode mu-law, crossfade and unfold, trim to wave_len = (T - 1) * hop, fade the last
+        20 hops out (a shorter clip raises the reference's broadcast ``ValueError`` here).  May write into rows_f64."""
+        out = decode_mu_law(rows_f64, self.n_classes, False) if mu_law else rows_f64
+        out = self.xfade_and_unfold(out, target, overlap) if batched else out[0]
+        out = out[:wave_len]
+        out[-20 * self.hop_length:] *= np.linspace(1, 0, 20 * self.hop_length)
+        return out
+
+    def _finish_device(self, res, lens, epilogue):
+        """Device tail of ``generate_many``: ``epilogue(nat, waves_ptr, wl_max, stream)`` -- one ``nat.epilogue_*`` launch -- fills a
+        (clips, wl_max) float64 buffer, wl_max = the longest clip's (T - 1) * hop; returns clip i's first (T_i - 1) * hop samples."""
+        nat = self.native()
+        dev = res['samples'].device
+        wl_max = (max(lens) - 1) * self.hop_length
+        with torch.cuda.device(dev):
+            waves = torch.empty((len(lens), wl_max), dtype=torch.float64, device=dev)
+            epilogue(nat, waves.data_ptr(), wl_max, torch.cuda.current_stream(dev).cuda_stream)
+        waves = waves.cpu().numpy()
+        return [waves[i, :(t_i - 1) * self.hop_length].copy() for i, t_i in enumerate(lens)]
 
     def stream(self, batch=1, mu_law=True, seed=None, noise_mode='philox', kernel=None, tail='reference', raw=False,
                batched=False) -> 'VocoderStream':
@@ -1048,10 +1020,7 @@ class VocoderStream:
     def __init__(self, model: 'WaveRNN', *, batch, mu_law, seed, noise_mode, kernel, tail, raw):
         if tail not in ('reference', 'none'):
             raise ValueError(f"tail must be 'reference' or 'none', got {tail!r}")
-        if isinstance(noise_mode, str):
-            if noise_mode not in _NOISE_MODES:
-                raise ValueError(f'noise_mode must be one of {sorted(_NOISE_MODES)} or a WRNN_NOISE_* id, got {noise_mode!r}')
-            noise_mode = _NOISE_MODES[noise_mode]
+        noise_mode = _noise_mode_id(noise_mode)
         if noise_mode not in (_cabi.NOISE_PHILOX, _cabi.NOISE_ARGMAX):
             raise ValueError("a stream draws its noise on the device (noise_mode 'philox' or 'argmax'): 'reference' / 'injected' "
                              "noise needs the draws of the whole clip up front")

@@ -89,6 +89,28 @@ def test_epilogue_pieces_match_the_oracle_restatement():
     np.testing.assert_allclose(decode_mu_law(lab, 1024, True), orc.decode_mu_law(f, 1024), rtol=0, atol=1e-15)
 
 
+def test_finish_host_is_the_inline_tail_it_replaced():
+    """``_finish_host`` against the sequence generate(), generate_many() and the folded call each spelled out before they shared it:
+    decode_mu_law -> xfade_and_unfold -> [:wave_len] -> last 20 hops times linspace(1, 0, 20 * hop), bit for bit in float64.  hop = 5,
+    so that the three folds of the batched case (2 050 samples unfolded) are longer than the 20-hop fade."""
+    from tacotronv2_wavernn_chinese_amd.dsp import decode_mu_law
+    from tacotronv2_wavernn_chinese_amd.vocoder import WaveRNN
+    m = WaveRNN(rnn_dims=16, fc_dims=16, bits=10, pad=2, upsample_factors=(5,), feat_dims=8, compute_dims=8, res_out_dims=8, res_blocks=1,
+                hop_length=5, sample_rate=22050, mode='RAW')
+    hop, target, overlap = m.hop_length, 550, 100
+    rng = np.random.default_rng(7)
+    for batched, shape, wave_len in ((False, (1, 21 * hop), 20 * hop), (True, (3, target + 2 * overlap), 3 * (target + overlap) + overlap - hop)):
+        rows = rng.integers(-2, 3, shape).astype(np.float64)   # integer-valued and small: finite under the mu-law expansion
+        for mu_law in (True, False):
+            want = decode_mu_law(rows.copy(), m.n_classes, False) if mu_law else rows.copy()
+            want = m.xfade_and_unfold(want, target, overlap) if batched else want[0]
+            want = want[:wave_len]
+            want[-20 * hop:] *= np.linspace(1, 0, 20 * hop)
+            got = m._finish_host(rows.copy(), mu_law, batched, target, overlap, wave_len)
+            assert got.dtype == np.float64 and got.shape == (wave_len,) and np.all(np.isfinite(got)) and np.any(got != 0)
+            assert np.array_equal(got, want), (batched, mu_law)
+
+
 def test_save_wav_is_a_float32_wav_at_the_sample_rate(tmp_path):
     from scipy.io import wavfile
     from tacotronv2_wavernn_chinese_amd.dsp import save_wav
