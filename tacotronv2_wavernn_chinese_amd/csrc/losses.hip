@@ -3,8 +3,8 @@
 //   MOL: discretized_mix_logistic_loss(y_hat, y)  (wavernn/utils/distribution.py:16-84, num_classes = 65536,
 //        log_scale_min = log(1e-14), reduce = True)  -- mean over B*L of -logsumexp_k(log_prob_k + log_softmax(logit)_k)
 // Forward values only (the path here is inference; the numbers are what a training log would print).
-// Both are HBM-read-bound row reductions: one wave per row (RAW, 4 KB per row) / one thread per row (MOL, 120 B per row),
-// per-block partial sums in double, summed in a fixed order by a second kernel (deterministic, no atomics).
+// Both are HBM-read-bound row reductions: one wave per row (RAW, 4 KB per row) / one thread per row (MOL, 120 B per row, the arm
+// values in double), per-block partial sums in double, summed in a fixed order by a second kernel (deterministic, no atomics).
 #include "wrnn_internal.h"
 
 namespace {
@@ -44,52 +44,67 @@ __global__ void __launch_bounds__(256) ce_rows_kernel(const float *__restrict__ 
     if (threadIdx.x == 0) partial[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
 }
 
-__device__ __forceinline__ float softplus_f(float x) { return x > 20.0f ? x : log1pf(expf(x)); }   // F.softplus (beta 1, threshold 20)
 __device__ __forceinline__ float sigmoid_ref(float x) { return 1.0f / (1.0f + expf(-x)); }
+__device__ __forceinline__ double softplus_d(double x) { return x > 30.0 ? x : log1p(exp(x)); }   // F.softplus; past 30 log1p(exp(x)) == x in double
+__device__ __forceinline__ double sigmoid_d(double x) { return 1.0 / (1.0 + exp(-x)); }
 
-// grid ceil(rows / 256), block 256: one thread per (b, t) row of y_hat (rows, 3 * nr_mix)
+// grid ceil(rows / 256), block 256: one thread per (b, t) row of y_hat (rows, 3 * nr_mix).
+// WHICH arm a (row, component) takes is decided as the reference's float32 arithmetic decides it: y against +-0.999f, and the float32
+// difference of float32 sigmoids against 1e-5f (the same expression `mol_grad_kernel` uses, so loss and gradient are on one arm).  The
+// VALUE of the arm and everything after it is evaluated in double and rounded to float32 once, at the end (`mean_kernel`): in float32 the
+// row value itself is a few ulp off, and against a float64 restatement that is up to 18x what the reference's own float32 result loses
+// on rows where that result happens to round well (edge rows, 1000 of them: 1.26e-7 against 6.8e-9).  The reference's blends
+// `c * arm_a + (1 - c) * arm_b` multiply the arm not taken by 0: written as a selection here.  30 doubles per row, B*L rows: next to the
+// GEMMs of a training step this costs nothing.
 __global__ void __launch_bounds__(256) mol_rows_kernel(const float *__restrict__ y_hat, const float *__restrict__ yv, int nr_mix,
-                                                       long n_rows, float num_classes, float log_scale_min,
+                                                       long n_rows, float num_classes, double log_scale_min,
                                                        double *__restrict__ partial) {
     __shared__ double part[4];
     const long row = (long)blockIdx.x * 256 + threadIdx.x;
     double loss = 0.0;
     if (row < n_rows) {
         const float *p = y_hat + (size_t)row * 3 * nr_mix;
-        const float y = yv[row];
+        const float yf = yv[row];
+        const double y = (double)yf;
         // log_softmax(logit_probs)                                   (:77)
-        float lm = -INFINITY;
-        for (int k = 0; k < nr_mix; ++k) lm = fmaxf(lm, p[k]);
-        float ls = 0.0f;
-        for (int k = 0; k < nr_mix; ++k) ls += expf(p[k] - lm);
-        const float lse_logit = lm + logf(ls);
-        const float half_bin = 1.0f / (num_classes - 1.0f);
-        const float log_half = logf((num_classes - 1.0f) / 2.0f);
-        float lp[16];
-        float mx = -INFINITY;
+        double lm = -INFINITY;
+        for (int k = 0; k < nr_mix; ++k) lm = fmax(lm, (double)p[k]);
+        double ls = 0.0;
+        for (int k = 0; k < nr_mix; ++k) ls += exp((double)p[k] - lm);
+        const double lse_logit = lm + log(ls);
+        const double half_bin = 1.0 / ((double)num_classes - 1.0);
+        const double log_half = log(((double)num_classes - 1.0) / 2.0);
+        const float half_bin_f = 1.0f / (num_classes - 1.0f), ls_min_f = (float)log_scale_min;
+        double lp[16];
+        double mx = -INFINITY;
         for (int k = 0; k < nr_mix; ++k) {
-            const float mean = p[nr_mix + k];
-            const float lsc = fmaxf(p[2 * nr_mix + k], log_scale_min);          // :31
-            const float cy = y - mean;                                          // :36
-            const float inv = expf(-lsc);                                       // :37
-            const float plus_in = inv * (cy + half_bin), min_in = inv * (cy - half_bin);
-            const float cdf_delta = sigmoid_ref(plus_in) - sigmoid_ref(min_in); // :39-54
-            const float log_cdf_plus = plus_in - softplus_f(plus_in);           // :45
-            const float log_one_minus_cdf_min = -softplus_f(min_in);            // :49
-            const float mid_in = inv * cy;
-            const float log_pdf_mid = mid_in - lsc - 2.0f * softplus_f(mid_in); // :57
-            const float c2 = cdf_delta > 1e-5f ? 1.0f : 0.0f;                   // :68-72, evaluated as the same blend of both arms
-            const float inner_inner = c2 * logf(fmaxf(cdf_delta, 1e-12f)) + (1.0f - c2) * (log_pdf_mid - log_half);
-            const float c1 = y > 0.999f ? 1.0f : 0.0f;
-            const float inner = c1 * log_one_minus_cdf_min + (1.0f - c1) * inner_inner;
-            const float c0 = y < -0.999f ? 1.0f : 0.0f;
-            const float v = (c0 * log_cdf_plus + (1.0f - c0) * inner) + (p[k] - lse_logit);   // :75-77
+            const double mean = (double)p[nr_mix + k];
+            const double lsc = fmax((double)p[2 * nr_mix + k], log_scale_min);  // :31
+            const double cy = y - mean;                                         // :36
+            const double inv = exp(-lsc);                                       // :37
+            // the float32 cdf_delta the reference compares with 1e-5          (:39-54, :69)
+            const float inv_f = expf(-fmaxf(p[2 * nr_mix + k], ls_min_f)), cy_f = yf - p[nr_mix + k];
+            const float cdf_f = sigmoid_ref(inv_f * (cy_f + half_bin_f)) - sigmoid_ref(inv_f * (cy_f - half_bin_f));
+            double v;
+            if (yf < -0.999f) {                                                 // :76  log_cdf_plus :45
+                const double plus_in = inv * (cy + half_bin);
+                v = plus_in - softplus_d(plus_in);
+            } else if (yf > 0.999f) {                                           // :74  log_one_minus_cdf_min :49
+                v = -softplus_d(inv * (cy - half_bin));
+            } else if (cdf_f > 1e-5f) {                                         // :69-72
+                const double cdf_delta = sigmoid_d(inv * (cy + half_bin)) - sigmoid_d(inv * (cy - half_bin));
+                v = log(fmax(cdf_delta, 1e-12));
+            } else {                                                            // log_pdf_mid :57
+                const double mid_in = inv * cy;
+                v = mid_in - lsc - 2.0 * softplus_d(mid_in) - log_half;
+            }
+            v += (double)p[k] - lse_logit;                                      // :75-77
             lp[k] = v;
-            mx = fmaxf(mx, v);
+            mx = fmax(mx, v);
         }
-        float s = 0.0f;
-        for (int k = 0; k < nr_mix; ++k) s += expf(lp[k] - mx);                 // log_sum_exp :6-12
-        loss = -(double)(mx + logf(s));
+        double s = 0.0;
+        for (int k = 0; k < nr_mix; ++k) s += exp(lp[k] - mx);                  // log_sum_exp :6-12
+        loss = -(mx + log(s));
     }
     // block sum in a fixed order
     for (int off = 32; off >= 1; off >>= 1) loss += __shfl_xor(loss, off, 64);
@@ -124,7 +139,7 @@ hipError_t wrnn_launch_loss(int mode, const float *y_hat, const void *y, int NC,
     } else {
         nblk = (n_rows + 255) / 256;
         hipLaunchKernelGGL(mol_rows_kernel, dim3((unsigned)nblk), dim3(256), 0, s, y_hat, (const float *)y, NC / 3, n_rows, 65536.0f,
-                           -32.23619130191664f, partial);
+                           -32.23619130191664, partial);
     }
     hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, s, partial, nblk, 1.0 / (double)n_rows, bad, out);
     return hipGetLastError();
