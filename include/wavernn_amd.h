@@ -460,6 +460,40 @@ int wrnn_mel_tables(const wrnn_mel_handle *h, float *window, float *twiddle, int
 const char *wrnn_mel_last_error(const wrnn_mel_handle *h);
 void wrnn_mel_destroy(wrnn_mel_handle *h);
 
+/* ---- training data on the device (added to ABI 9 like the mel front end: two new functions, no struct and no existing entry changes,
+ * so the number stays; a binding can tell a build from before them only by the missing symbols).  What wavernn_preprocess.py and
+ * collate_vocoder (wavernn/utils/dataset.py:107-133) do on the host.  Neither entry takes a handle: there is no state and no error
+ * text, only the status.  Both run on the device `stream` belongs to (the current device for the NULL stream), are asynchronous, and
+ * check their arguments before any device call (WRNN_ERR_INVALID comes back on a machine without a GPU too).
+ *
+ * wrnn_quantise: labels_dev[i] = the class of sample wav_dev[i], 0 <= i < n, evaluated in float64 in the reference's operation order.
+ * mu_law != 0: encode_mu_law(x, 2**bits) (wavernn/utils/dsp.py:92-95), floor((sign(x) log(1 + mu |x|) / log(1 + mu) + 1) / 2 * mu +
+ * 0.5) with mu = 2**bits - 1; mu_law == 0: float_2_label(x, bits) (:12-15), (x + 1) * mu / 2, truncated like the collate's
+ * .astype(int64).  Labels are clipped to [0, mu].  The reference asserts |x| <= 1; here every sample with |x| > 1 (or NaN) is ADDED to
+ * *n_clipped_dev when that pointer is not NULL (the caller zeroes it and decides what the count means).  bits: 1 .. 16.  n == 0 is a
+ * successful no-op whose pointers may be NULL; WRNN_ERR_INVALID for bits out of range, n < 0, or a NULL buffer with n > 0. */
+int wrnn_quantise(const float *wav_dev, int64_t n, int32_t bits, int32_t mu_law, int32_t *labels_dev, int64_t *n_clipped_dev, void *stream);
+
+/* One training batch cut from a corpus that lives on the device, one launch.  The corpus: labels_dev, the int32 labels of all
+ * utterances, utterance u from element label_off_dev[u], at least (frames_dev[u] - 1) * hop of them (a wav of n samples has 1 + n / hop
+ * frames); mels_dev, their mels, utterance u FRAMES-MAJOR (frames_dev[u], n_mels) float32 from element mel_off_dev[u] (the layout of the
+ * reference's mel .npy files; a window is one contiguous run).  Row b of the batch takes utterance utt_dev[b] at mel frame
+ * win_off_dev[b], as collate_vocoder does: with win = seq_len / hop + 2 * pad,
+ *   mels_out[b] (n_mels, win) = frames win_off[b] .. win_off[b] + win, transposed;
+ *   l = labels of the utterance from sample (win_off[b] + pad) * hop, seq_len + 1 of them;
+ *   x_out[b, i] = label_2_float(l[i], sig_bits) = 2 * l[i] / (2**sig_bits - 1) - 1, every operation rounded to float32 (the divide
+ *   correctly rounded): bit-equal to torch's float32 arithmetic;
+ *   y_out[b, i] = l[i + 1] as int64 (y_float == 0, the RAW target), or label_2_float(l[i + 1], sig_bits) as float32 (the MOL target).
+ * x_out, y_out (B, seq_len), mels_out (B, n_mels, win), contiguous.  The tables are on the device, so the caller validates utt and
+ * win_off on the host before the call: 0 <= win_off[b] < frames[utt[b]] - 2 - (win + 2 * pad), the range collate_vocoder draws from
+ * (:109-110).  The kernel re-checks that range against frames_dev and writes zeros for a row that fails; it never reads outside
+ * an utterance of a valid table.  WRNN_ERR_INVALID: seq_len % hop != 0, B < 1 or > 65535, n_mels / hop / seq_len < 1, pad < 0,
+ * sig_bits outside 1 .. 16, any NULL pointer. */
+int wrnn_collate_windows(const int32_t *labels_dev, const float *mels_dev, const int64_t *label_off_dev, const int64_t *mel_off_dev,
+                         const int32_t *frames_dev, const int32_t *utt_dev, const int32_t *win_off_dev, int32_t B, int32_t n_mels,
+                         int32_t hop, int32_t pad, int32_t seq_len, int32_t sig_bits, int32_t y_float, float *x_out, void *y_out,
+                         float *mels_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

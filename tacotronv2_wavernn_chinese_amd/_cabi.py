@@ -36,7 +36,8 @@ EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wr
                     'wrnn_dm_set_kernel', 'wrnn_dm_sync_status', 'wrnn_team_info', 'wrnn_debug_force_no_teams',
                     'wrnn_stream_open', 'wrnn_stream_push', 'wrnn_stream_sync', 'wrnn_stream_info', 'wrnn_stream_ready_steps',
                     'wrnn_stream_close', 'wrnn_plan_folded', 'wrnn_generate_folded', 'wrnn_epilogue_folded',
-                    'wrnn_mel_create', 'wrnn_mel_frames', 'wrnn_melspectrogram', 'wrnn_mel_tables', 'wrnn_mel_last_error', 'wrnn_mel_destroy')
+                    'wrnn_mel_create', 'wrnn_mel_frames', 'wrnn_melspectrogram', 'wrnn_mel_tables', 'wrnn_mel_last_error', 'wrnn_mel_destroy',
+                    'wrnn_quantise', 'wrnn_collate_windows')
 
 
 def epilogue_tables(n_classes: int, overlap: int, hop: int):
@@ -140,8 +141,10 @@ def load_library() -> C.CDLL:
     if got != ABI_VERSION:   # the .so is a git-ignored build artefact: a stale one would read the structs at shifted offsets
         raise RuntimeError(f'{LIB_PATH} implements ABI {got}, this binding needs ABI {ABI_VERSION}: rebuild it '
                            '(`python -c "import __graft_entry__ as g; g.build()"`)')
-    if not hasattr(lib, 'wrnn_melspectrogram'):   # the mel entry points joined ABI 9 without a new number: a build from before them reports 9 too
-        raise RuntimeError(f'{LIB_PATH} implements ABI {got} without the wrnn_mel_* entry points: rebuild it '
+    # entry points have joined ABI 9 without a new number (the mel front end, the dataset kernels): a build from before them reports 9 too
+    missing = [s for s in EXPORTED_SYMBOLS if not hasattr(lib, s)]
+    if missing:
+        raise RuntimeError(f'{LIB_PATH} implements ABI {got} without {", ".join(missing)}: it was built from older sources, rebuild it '
                            '(`python -c "import __graft_entry__ as g; g.build()"`)')
     vp = C.c_void_p
     lib.wrnn_create.argtypes = [C.POINTER(Config), C.POINTER(vp)]
@@ -224,6 +227,11 @@ def load_library() -> C.CDLL:
     lib.wrnn_mel_last_error.restype = C.c_char_p
     lib.wrnn_mel_destroy.argtypes = [vp]
     lib.wrnn_mel_destroy.restype = None
+    lib.wrnn_quantise.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp]
+    lib.wrnn_quantise.restype = C.c_int
+    lib.wrnn_collate_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         vp, vp, vp, vp]
+    lib.wrnn_collate_windows.restype = C.c_int
     lib.wrnn_dm_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
     lib.wrnn_dm_create.restype = C.c_int
     lib.wrnn_dm_load_weights.argtypes = [vp, C.POINTER(TensorDesc), C.c_int32]
@@ -447,6 +455,26 @@ def plan_folded(frames, hop: int, target: int, overlap: int) -> Tuple[np.ndarray
 def stream_ready_steps(frames_in: int, hop: int, pad: int, last: bool) -> int:
     """Host-only ``wrnn_stream_ready_steps``: loop steps a stream can run after ``frames_in`` mel frames (-1 for bad arguments)."""
     return int(load_library().wrnn_stream_ready_steps(int(frames_in), int(hop), int(pad), int(bool(last))))
+
+
+def quantise(wav_ptr: int, n: int, bits: int, mu_law: bool, labels_ptr: int, n_clipped_ptr: int, stream: int):
+    """``wrnn_quantise``: n float32 samples -> int32 class labels on the device; samples with ``|x| > 1`` are added to the int64 at
+    ``n_clipped_ptr`` (0: not counted).  ``WrnnError`` for a refused call (bad arguments are refused before any device call)."""
+    rc = load_library().wrnn_quantise(wav_ptr or None, int(n), int(bits), int(bool(mu_law)), labels_ptr or None, n_clipped_ptr or None, stream or None)
+    if rc != 0:
+        raise WrnnError(rc, f'wrnn_quantise(n={int(n)}, bits={int(bits)})')
+
+
+def collate_windows(labels_ptr: int, mels_ptr: int, label_off_ptr: int, mel_off_ptr: int, frames_ptr: int, utt_ptr: int, win_off_ptr: int,
+                    B: int, n_mels: int, hop: int, pad: int, seq_len: int, sig_bits: int, y_float: bool, x_ptr: int, y_ptr: int,
+                    mels_out_ptr: int, stream: int):
+    """``wrnn_collate_windows``: one training batch cut from the device-resident corpus, one launch."""
+    rc = load_library().wrnn_collate_windows(labels_ptr or None, mels_ptr or None, label_off_ptr or None, mel_off_ptr or None, frames_ptr or None,
+                                             utt_ptr or None, win_off_ptr or None, int(B), int(n_mels), int(hop), int(pad), int(seq_len),
+                                             int(sig_bits), int(bool(y_float)), x_ptr or None, y_ptr or None, mels_out_ptr or None, stream or None)
+    if rc != 0:
+        raise WrnnError(rc, f'wrnn_collate_windows(B={int(B)}, n_mels={int(n_mels)}, hop={int(hop)}, pad={int(pad)}, seq_len={int(seq_len)}, '
+                            f'sig_bits={int(sig_bits)})')
 
 
 class NativeStream:

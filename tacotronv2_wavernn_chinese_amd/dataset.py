@@ -1,0 +1,302 @@
+"""The training data on the device: a folder of wavs -> a corpus resident in HBM -> ``(x, y, mels)`` window batches.
+
+What the reference spreads over ``wavernn_preprocess.py`` (quantise the wav, write ``quant/*.npy``, ``mel/*.npy`` and the list file),
+``get_vocoder_datasets`` and ``collate_vocoder`` (``wavernn/utils/dataset.py:62-133``).  Here the mel comes from the device front end
+(``csrc/melspec.hip``), the labels from ``wrnn_quantise`` and every batch from one ``wrnn_collate_windows`` launch over a corpus that
+stays where the trainer is (``csrc/dataset.hip``): ten hours of 22.05 kHz audio are about 4 GB of int32 labels and 80-band mels.
+
+``DeviceCorpus`` keeps two device allocations -- all labels back to back, and all mels back to back with every utterance
+frames-major, ``(frames, n_mels)``, the layout of the reference's mel files, so that a training window is one contiguous run -- and
+the per-utterance offset tables, on the host and on the device.  ``DeviceWindowLoader`` is ``train.WindowLoader`` over such a corpus:
+the same draws from the same generator (``train.draw_window_offsets``), hence the same batches bit for bit, already on the device.
+"""
+from __future__ import annotations
+
+import random
+from pathlib import Path
+from typing import List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import _cabi
+from .train import draw_window_offsets
+
+LIST_NAME = 'wavernn_training_data.txt'
+
+
+def signal_bits(hp) -> Tuple[int, bool]:
+    """(bits, mu_law) of the training labels for an hparams-like object: MOL trains on a 16-bit linear signal (dataset.py:126), RAW
+    on ``hp.bits`` classes, mu-law when ``hp.mu_law`` says so."""
+    if getattr(hp, 'voc_mode', 'RAW') == 'MOL':
+        return 16, False
+    return int(hp.bits), bool(getattr(hp, 'mu_law', True))
+
+
+def min_frames(*, hop_length: int, pad: int, seq_len: int) -> int:
+    """Utterances with fewer mel frames are dropped by ``get_vocoder_datasets`` (dataset.py:73-75)."""
+    return seq_len // hop_length + 2 * pad + 2 * pad + 2
+
+
+def _device(device) -> torch.device:
+    dev = torch.device(device if device is not None else 'cuda')
+    if dev.type != 'cuda':
+        raise ValueError(f'a DeviceCorpus lives on the GPU, got device {dev}')
+    return torch.device('cuda', dev.index if dev.index is not None else torch.cuda.current_device())
+
+
+class DeviceCorpus:
+    """Utterances as ``labels`` (int32, all utterances back to back) and ``mels`` (float32, utterance u as ``(frames[u], n_mels)``
+    from element ``mel_off[u]``) on one device.  ``label_off / label_len / mel_off / frames`` are host arrays with one entry per
+    utterance; ``stems`` names the utterances (file names of ``save``).  Make one with ``from_wavs``, ``from_pairs`` or ``load``."""
+
+    def __init__(self, labels: torch.Tensor, mels: torch.Tensor, label_off, label_len, mel_off, frames, n_mels: int, stems: Sequence[str],
+                 *, hop_length: int, sample_rate: Optional[int] = None, bits: Optional[int] = None, mu_law: Optional[bool] = None,
+                 n_clipped: int = 0):
+        self.labels, self.mels = labels, mels
+        self.label_off, self.label_len = np.asarray(label_off, np.int64), np.asarray(label_len, np.int64)
+        self.mel_off, self.frames = np.asarray(mel_off, np.int64), np.asarray(frames, np.int32)
+        self.n_mels, self.stems, self.hop_length = int(n_mels), list(stems), int(hop_length)
+        self.sample_rate, self.bits, self.mu_law, self.n_clipped = sample_rate, bits, mu_law, int(n_clipped)
+        if not (len(self.label_off) == len(self.label_len) == len(self.mel_off) == len(self.frames) == len(self.stems)):
+            raise ValueError('the offset tables and the names differ in length')
+        # what wrnn_collate_windows relies on: every window the collate can draw lies inside the utterance's own labels and mel
+        short = np.flatnonzero(self.label_len < (self.frames.astype(np.int64) - 1) * self.hop_length)
+        if short.size:
+            u = int(short[0])
+            raise ValueError(f'utterance {self.stems[u]!r}: {int(self.label_len[u])} labels for {int(self.frames[u])} frames of hop '
+                             f'{self.hop_length}, at least {(int(self.frames[u]) - 1) * self.hop_length} are needed')
+        if len(self) and (int((self.label_off + self.label_len).max()) > labels.numel()
+                          or int((self.mel_off + self.frames.astype(np.int64) * self.n_mels).max()) > mels.numel()
+                          or int(self.label_off.min()) < 0 or int(self.mel_off.min()) < 0):
+            raise ValueError('an offset table points outside the device buffers')
+        self._tables = None
+
+    # ------------------------------------------------------------------ what the loader and the callers read
+    def __len__(self):
+        return len(self.frames)
+
+    @property
+    def device(self) -> torch.device:
+        return self.labels.device
+
+    @property
+    def hours(self) -> float:
+        return float(self.label_len.sum()) / float(self.sample_rate or 22050) / 3600.0
+
+    def device_tables(self):
+        """(label_off int64, mel_off int64, frames int32) on the device, uploaded once."""
+        if self._tables is None:
+            dev = self.device
+            self._tables = (torch.from_numpy(self.label_off).to(dev), torch.from_numpy(self.mel_off).to(dev), torch.from_numpy(self.frames).to(dev))
+        return self._tables
+
+    def pairs(self) -> List[Tuple[np.ndarray, np.ndarray]]:
+        """Host ``(mel (n_mels, frames), labels)`` arrays, one pair per utterance: what ``train.WindowLoader`` takes."""
+        out = []
+        for lo, ln, mo, t in zip(self.label_off, self.label_len, self.mel_off, self.frames):
+            mel = self.mels[int(mo):int(mo) + int(t) * self.n_mels].cpu().numpy().reshape(int(t), self.n_mels)
+            out.append((mel.T, self.labels[int(lo):int(lo) + int(ln)].cpu().numpy()))
+        return out
+
+    def subset(self, ids: Sequence[int]) -> 'DeviceCorpus':
+        """The utterances ``ids`` as a corpus of their own that shares the device buffers (nothing is copied)."""
+        ids = np.asarray(list(ids), np.int64)
+        return DeviceCorpus(self.labels, self.mels, self.label_off[ids], self.label_len[ids], self.mel_off[ids], self.frames[ids], self.n_mels,
+                            [self.stems[i] for i in ids], hop_length=self.hop_length, sample_rate=self.sample_rate, bits=self.bits,
+                            mu_law=self.mu_law, n_clipped=self.n_clipped)
+
+    def split(self, test_samples: int) -> Tuple['DeviceCorpus', 'DeviceCorpus']:
+        """(train, test) the way ``read_feature_list`` / ``get_vocoder_datasets`` (dataset.py:79-85) split: ids shuffled with seed
+        1234, the last ``test_samples`` set aside."""
+        ids = list(range(len(self)))
+        random.Random(1234).shuffle(ids)
+        if test_samples:
+            return self.subset(ids[:-test_samples]), self.subset(ids[-test_samples:])
+        return self.subset(ids), self.subset([])
+
+    # ------------------------------------------------------------------ constructors
+    @classmethod
+    def from_pairs(cls, pairs, device=None, *, hop_length: int, stems: Optional[Sequence[str]] = None, **meta) -> 'DeviceCorpus':
+        """From host ``(mel (n_mels, frames), labels)`` arrays (what ``pairs()`` returns, what ``WindowLoader`` takes)."""
+        dev = _device(device)
+        pairs = list(pairs)
+        if not pairs:
+            raise ValueError('expected at least one utterance')
+        n_mels = int(pairs[0][0].shape[0])
+        frames = [int(m.shape[1]) for m, _ in pairs]
+        lens = [int(np.shape(w)[0]) for _, w in pairs]
+        if any(m.ndim != 2 or m.shape[0] != n_mels for m, _ in pairs):
+            raise ValueError(f'expected (n_mels = {n_mels}, frames) mels')
+        label_off = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+        mel_off = np.concatenate([[0], np.cumsum(frames)[:-1]]).astype(np.int64) * n_mels
+        labels = np.concatenate([np.asarray(w).astype(np.int32) for _, w in pairs])
+        mels = np.concatenate([np.ascontiguousarray(np.asarray(m, np.float32).T).reshape(-1) for m, _ in pairs])
+        names = list(stems) if stems is not None else [f'utt{i:05d}' for i in range(len(pairs))]
+        return cls(torch.from_numpy(labels).to(dev), torch.from_numpy(mels).to(dev), label_off, lens, mel_off, frames, n_mels, names,
+                   hop_length=hop_length, **meta)
+
+    @classmethod
+    def from_wavs(cls, paths_or_arrays, hp, device=None, batch_clips: int = 16) -> 'DeviceCorpus':
+        """Wav files (``frontend.load_wav``) or float arrays in [-1, 1] -> corpus.  The clips go to the device in ragged groups of
+        ``batch_clips`` (grouped by length, so that little of a group's buffer is padding); each group's buffer is read by one launch of
+        the mel front end and one of ``wrnn_quantise``.  Bits and companding follow ``hp`` (``signal_bits``); utterances too short for
+        ``hp.voc_seq_len`` / ``hp.voc_pad`` are dropped like ``get_vocoder_datasets`` does.  ``n_clipped`` counts samples with
+        ``|x| > 1``: their labels are clipped, where the reference asserts."""
+        from .frontend import MelFrontEnd, load_wav
+        dev = _device(device)
+        fe = MelFrontEnd(hp, device=dev)
+        hop, n_mels = fe.hop_length, fe.n_mels
+        bits, mu_law = signal_bits(hp)
+        least = min_frames(hop_length=hop, pad=int(hp.voc_pad), seq_len=int(hp.voc_seq_len))
+        clips, stems = [], []
+        for i, item in enumerate(paths_or_arrays):
+            if isinstance(item, (str, Path)):
+                wav, stem = load_wav(item, fe.sample_rate), Path(item).stem
+            else:
+                wav = item.detach().cpu().numpy() if isinstance(item, torch.Tensor) else np.asarray(item)
+                wav, stem = np.ascontiguousarray(wav, dtype=np.float32), f'utt{i:05d}'
+            if wav.ndim != 1:
+                raise ValueError(f'expected 1-D clips of samples, got shape {wav.shape}')
+            if 1 + wav.shape[0] // hop < least:
+                continue
+            clips.append(wav)
+            stems.append(stem)
+        if not clips:
+            raise ValueError(f'no utterance has the {least} mel frames one training window needs')
+        lens = np.array([c.shape[0] for c in clips], np.int64)
+        frames = np.array([fe.frames(int(n)) for n in lens], np.int64)
+        label_off = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+        mel_off = np.concatenate([[0], np.cumsum(frames)[:-1]]).astype(np.int64) * n_mels
+        by_len = np.argsort(lens, kind='stable')
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            labels = torch.empty(int(lens.sum()), dtype=torch.int32, device=dev)
+            mels = torch.empty(int(frames.sum()) * n_mels, dtype=torch.float32, device=dev)
+            clipped = torch.zeros(1, dtype=torch.int64, device=dev)
+            for g in range(0, len(by_len), max(1, int(batch_clips))):
+                ids = by_len[g:g + max(1, int(batch_clips))]
+                n_max = int(lens[ids].max())
+                host = np.zeros((len(ids), n_max), np.float32)
+                for r, u in enumerate(ids):
+                    host[r, :lens[u]] = clips[u]
+                wav = torch.from_numpy(host).to(dev)
+                mel = fe.melspectrogram_padded(wav, lens[ids])                      # (B, n_mels, T_max)
+                lab = torch.empty((len(ids), n_max), dtype=torch.int32, device=dev)
+                _cabi.quantise(wav.data_ptr(), wav.numel(), bits, mu_law, lab.data_ptr(), clipped.data_ptr(), stream)   # the padding is 0: never clipped
+                for r, u in enumerate(ids):
+                    n, t = int(lens[u]), int(frames[u])
+                    labels[int(label_off[u]):int(label_off[u]) + n] = lab[r, :n]
+                    mels[int(mel_off[u]):int(mel_off[u]) + t * n_mels].view(t, n_mels).copy_(mel[r, :, :t].t())
+            n_clipped = int(clipped.item())
+        return cls(labels, mels, label_off, lens, mel_off, frames, n_mels, stems, hop_length=hop, sample_rate=fe.sample_rate, bits=bits,
+                   mu_law=mu_law, n_clipped=n_clipped)
+
+    # ------------------------------------------------------------------ files
+    def save(self, out_dir: Union[str, Path]) -> Path:
+        """``quant/<stem>.npy`` (int32 labels), ``mel/<stem>.npy`` (``(frames, n_mels)`` float32, the reference's file layout) and
+        ``wavernn_training_data.txt`` with one ``quant|mel|mel|stem`` line per utterance: fields 0 and 2 are what
+        ``train.read_feature_list`` and the reference's ``get_vocoder_datasets`` read.  Returns the list file's path."""
+        out = Path(out_dir).expanduser().resolve()
+        (out / 'quant').mkdir(parents=True, exist_ok=True)
+        (out / 'mel').mkdir(parents=True, exist_ok=True)
+        if len(set(self.stems)) != len(self.stems):
+            raise ValueError('two utterances share a name: their files would overwrite each other')
+        lines = []
+        for (mel, lab), stem in zip(self.pairs(), self.stems):
+            q, m = out / 'quant' / f'{stem}.npy', out / 'mel' / f'{stem}.npy'
+            np.save(q, lab.astype(np.int32), allow_pickle=False)
+            np.save(m, np.ascontiguousarray(mel.T, dtype=np.float32), allow_pickle=False)
+            lines.append(f'{q}|{m}|{m}|{stem}\n')
+        listing = out / LIST_NAME
+        listing.write_text(''.join(lines), encoding='utf-8')
+        return listing
+
+    @classmethod
+    def load(cls, list_file_or_pairs, device=None, *, hop_length: int, **meta) -> 'DeviceCorpus':
+        """A saved corpus back on the device without recomputing anything: ``list_file_or_pairs`` is the list file ``save`` wrote
+        (every line is taken, in order) or ``(quantised wav path, mel path)`` pairs such as ``train.read_feature_list`` returns."""
+        if isinstance(list_file_or_pairs, (str, Path)):
+            items = []
+            with open(list_file_or_pairs, 'r', encoding='utf-8') as f:
+                for line in f:
+                    parts = [p.strip() for p in line.strip().split('|')]
+                    if len(parts) >= 3:
+                        items.append((parts[0], parts[2], parts[3] if len(parts) > 3 and parts[3] else Path(parts[0]).stem))
+        else:
+            items = [(str(q), str(m), Path(q).stem) for q, m in list_file_or_pairs]
+        if not items:
+            raise ValueError('the list names no utterance')
+        pairs = [(np.load(m).T, np.load(q)) for q, m, _ in items]
+        return cls.from_pairs(pairs, device, hop_length=hop_length, stems=[s for _, _, s in items], **meta)
+
+
+class DeviceWindowLoader:
+    """``train.WindowLoader`` over a :class:`DeviceCorpus`: a sized iterable, shuffled per epoch, a fresh random window per utterance,
+    a last short batch kept -- and every batch ``(x, y, mels)`` built on the device by one ``wrnn_collate_windows`` launch after one
+    small host-to-device copy of the batch's ``(utterance, offset)`` pairs.  The permutation and the offsets are drawn on the host from
+    ``np.random.Generator(PCG64(seed))`` in ``WindowLoader``'s order, so batch k equals batch k of
+    ``WindowLoader(corpus.pairs(), ...)`` with the same seed bit for bit.  ``corpus`` needs ``len()`` and ``frames`` for ``draws()``;
+    iterating needs a real ``DeviceCorpus``."""
+
+    def __init__(self, corpus, batch_size: int, *, mode: str, bits: int, hop_length: int, pad: int, seq_len: int, seed: int = 0):
+        self.corpus, self.batch_size, self.mode = corpus, int(batch_size), mode
+        self.sig_bits = 16 if mode == 'MOL' else int(bits)
+        self.kw = dict(hop_length=int(hop_length), pad=int(pad), seq_len=int(seq_len))
+        self.rng = np.random.Generator(np.random.PCG64(seed))
+
+    def __len__(self):
+        return (len(self.corpus) + self.batch_size - 1) // self.batch_size
+
+    def draws(self):
+        """One epoch of ``(utterance indices, window offsets)`` int32 array pairs, one per batch: host only.  Raises the
+        ``ValueError``s of ``collate_windows`` (``seq_len`` against the hop, an utterance too short)."""
+        frames = np.asarray(self.corpus.frames)
+        order = self.rng.permutation(len(frames))
+        for i in range(0, len(order), self.batch_size):
+            utt = order[i:i + self.batch_size]
+            yield utt.astype(np.int32), np.asarray(draw_window_offsets(frames[utt], rng=self.rng, **self.kw), np.int32)
+
+    def __iter__(self):
+        c, kw = self.corpus, self.kw
+        if kw['hop_length'] != c.hop_length:
+            raise ValueError(f'the corpus was made with hop {c.hop_length}, the loader asks for {kw["hop_length"]}')
+        for utt, off in self.draws():      # validated on the host: utt is a permutation's slice, off inside the collate's range
+            dev, B, win = c.device, len(utt), kw['seq_len'] // kw['hop_length'] + 2 * kw['pad']
+            with torch.cuda.device(dev):
+                label_off, mel_off, frames = c.device_tables()
+                uo = torch.from_numpy(np.stack([utt, off])).to(dev)
+                x = torch.empty((B, kw['seq_len']), dtype=torch.float32, device=dev)
+                y = torch.empty((B, kw['seq_len']), dtype=torch.float32 if self.mode == 'MOL' else torch.int64, device=dev)
+                mels = torch.empty((B, c.n_mels, win), dtype=torch.float32, device=dev)
+                _cabi.collate_windows(c.labels.data_ptr(), c.mels.data_ptr(), label_off.data_ptr(), mel_off.data_ptr(), frames.data_ptr(),
+                                      uo[0].data_ptr(), uo[1].data_ptr(), B, c.n_mels, kw['hop_length'], kw['pad'], kw['seq_len'], self.sig_bits,
+                                      self.mode == 'MOL', x.data_ptr(), y.data_ptr(), mels.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            yield x, y, mels
+
+
+def main(argv=None):
+    """``python wavernn_preprocess.py --wav_dir DIR --out_dir DIR``: every ``*.wav`` of the folder -> ``quant/``, ``mel/`` and the
+    training list ``wavernn_train.py`` reads (``hp.feature_path``)."""
+    import argparse
+    from .hparams import DEFAULT_HPARAMS, hparams as hp
+    parser = argparse.ArgumentParser(description='Preprocess a folder of wavs for WaveRNN vocoder training')
+    parser.add_argument('--wav_dir', required=True, metavar='DIR', help='folder of wav files at hp.sample_rate')
+    parser.add_argument('--out_dir', required=True, metavar='DIR', help='where quant/, mel/ and the list file go')
+    parser.add_argument('--hp_file', metavar='FILE', default=DEFAULT_HPARAMS, help='The file to use for the hyperparameters')
+    parser.add_argument('--batch_clips', type=int, default=16, help='clips per launch of the front end')
+    args = parser.parse_args(argv)
+    hp.configure(args.hp_file)
+    if not torch.cuda.is_available():
+        raise RuntimeError('the preprocessing runs on an MI355X only (no CPU path)')
+    wavs = sorted(Path(args.wav_dir).expanduser().glob('*.wav'))
+    if not wavs:
+        raise FileNotFoundError(f'no *.wav files in {args.wav_dir}')
+    corpus = DeviceCorpus.from_wavs(wavs, hp, 'cuda', batch_clips=args.batch_clips)
+    listing = corpus.save(args.out_dir)
+    print(f'{len(corpus)} utterances of {len(wavs)} files | {corpus.hours:.3f} hours | {corpus.n_clipped} clipped samples | '
+          f'{corpus.bits} bits {"mu-law" if corpus.mu_law else "linear"} | {listing}')
+
+
+if __name__ == "__main__":
+    main()

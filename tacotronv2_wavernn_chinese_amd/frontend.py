@@ -72,8 +72,7 @@ class MelFrontEnd:
             raise ValueError(f'the front end runs on the GPU only, got device {dev}')
         index = dev.index if dev.index is not None else torch.cuda.current_device()
         dev = torch.device('cuda', index)
-        nat = self._native(index)
-        n_max, t_max, B = max(lens), max(frames), len(clips)
+        n_max, B = max(lens), len(clips)
         with torch.cuda.device(dev):
             if B == 1:
                 wav = torch.as_tensor(clips[0]).to(device=dev, dtype=torch.float32).contiguous().view(1, -1)
@@ -86,9 +85,24 @@ class MelFrontEnd:
                 for i, c in enumerate(clips):
                     host[i, :lens[i]] = c.detach().cpu().numpy() if isinstance(c, torch.Tensor) else np.asarray(c)
                 wav = torch.from_numpy(host).to(dev)
+        return self.melspectrogram_padded(wav, lens)
+
+    def melspectrogram_padded(self, wav: torch.Tensor, lens) -> torch.Tensor:
+        """The launch behind :meth:`melspectrogram` for clips that already lie on the device: ``wav`` a contiguous float32 ``(B, n_max)`` tensor
+        with clip b in ``wav[b, :lens[b]]`` -> ``(B, n_mels, T_max)``.  The caller keeps ``wav`` (``DeviceCorpus`` quantises the same buffer)."""
+        if not (isinstance(wav, torch.Tensor) and wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 2 and wav.is_contiguous()):
+            raise ValueError('expected a contiguous float32 (B, n_max) tensor on the GPU')
+        lens = [int(n) for n in lens]
+        B, n_max = wav.shape
+        if len(lens) != B or not lens or max(lens) > n_max:
+            raise ValueError(f'{len(lens)} lengths (max {max(lens, default=0)}) for a buffer of shape {tuple(wav.shape)}')
+        frames = [self.frames(n) for n in lens]   # refuses a short clip before anything is launched
+        dev, t_max = wav.device, max(frames)
+        with torch.cuda.device(dev):
             n_dev = torch.tensor(lens, dtype=torch.int32).to(dev)
             out = torch.empty((B, self.n_mels, t_max), dtype=torch.float32, device=dev)
-            nat.melspectrogram(wav.data_ptr(), n_max, n_dev.data_ptr(), B, t_max, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+            self._native(dev.index).melspectrogram(wav.data_ptr(), n_max, n_dev.data_ptr(), B, t_max, out.data_ptr(),
+                                                   torch.cuda.current_stream(dev).cuda_stream)
         self.last_frames = frames
         return out
 

@@ -6,9 +6,10 @@ files per checkpoint (``*_weights.pyt`` = ``model.state_dict()``, ``*_optim.pyt`
 places (``logs_wavernn/checkpoints/latest_*.pyt`` + ``wave_step{k}K_*.pyt``, ``wavernn/utils/paths.py:11-17``), so a run can be
 resumed by either code base and ``wavernn_gen.py`` finds the weights where it looks for them.
 
-Out of scope here (data formats either side of the path only): the dataset reader.  ``train_set`` is any sized
-iterable of ``(x, y, mels)``; ``collate_windows`` below builds such batches from in-memory ``(mel, quantised wav)`` pairs the
-way the reference's collate cuts its windows, and is what the tests and ``--synthetic`` use.
+``train_set`` is any sized iterable of ``(x, y, mels)``; ``collate_windows`` below builds such batches on the host from ``(mel,
+quantised wav)`` pairs the way the reference's collate cuts its windows (``.npy`` files of a training list, or in-memory arrays as the
+tests and ``--synthetic`` use them).  ``dataset.py`` makes the list from a folder of wavs and serves the same batches from a corpus
+resident on the device (``--wav_dir``, ``--resident``).
 
 The iteration itself is ``WaveRNN.training_loss`` (one ``wrnn_train_step``: forward, loss and backward of the loop layers on
 the MI355X) unless a ``loss_func`` is given, in which case the loop body is the reference's own
@@ -79,21 +80,33 @@ def label_2_float(x, bits: int):
     return 2.0 * x / (2 ** bits - 1.0) - 1.0
 
 
+def draw_window_offsets(frames: Sequence[int], *, hop_length: int, pad: int, seq_len: int, rng: np.random.Generator):
+    """The random part of one batch (dataset.py:108-110): for utterances of ``frames`` mel frames, in order, the first mel frame of
+    each one's window, one ``rng.integers(0, room)`` per utterance.  The one place the draws are made: ``collate_windows`` and
+    ``dataset.DeviceWindowLoader`` both call it, so with the same generator they cut the same windows.  ``ValueError`` for a
+    ``seq_len`` that is no multiple of the hop and for an utterance too short for a window."""
+    if seq_len % hop_length:
+        raise ValueError('seq_len must be a multiple of hop_length')
+    win = seq_len // hop_length + 2 * pad
+    offs = []
+    for n in frames:
+        room = int(n) - 2 - (win + 2 * pad)
+        if room <= 0:
+            raise ValueError(f'an utterance of {int(n)} frames is too short for a window of {win} (+{2 * pad + 2})')
+        offs.append(int(rng.integers(0, room)))
+    return offs
+
+
 def collate_windows(batch: Sequence[Tuple[np.ndarray, np.ndarray]], *, mode: str, bits: int, hop_length: int, pad: int,
                     seq_len: int, rng: np.random.Generator):
     """One training batch from ``(mel (n_mels, frames), quantised wav (frames * hop,) of class indices)`` pairs: a random window of
     ``seq_len`` samples + the ``pad`` context frames either side per pair (dataset.py:107-133).  Returns (x, y, mels) as the loop
     wants them: x (B, seq_len) floats in [-1, 1], y (B, seq_len) the next-sample targets (int64 classes for RAW, floats of a
     16-bit signal for MOL), mels (B, n_mels, seq_len / hop + 2 * pad)."""
-    if seq_len % hop_length:
-        raise ValueError('seq_len must be a multiple of hop_length')
+    offs = draw_window_offsets([mel.shape[-1] for mel, _ in batch], hop_length=hop_length, pad=pad, seq_len=seq_len, rng=rng)
     win = seq_len // hop_length + 2 * pad
     mels, labels = [], []
-    for mel, wav in batch:
-        room = mel.shape[-1] - 2 - (win + 2 * pad)
-        if room <= 0:
-            raise ValueError(f'an utterance of {mel.shape[-1]} frames is too short for a window of {win} (+{2 * pad + 2})')
-        off = int(rng.integers(0, room))
+    for (mel, wav), off in zip(batch, offs):
         s0 = (off + pad) * hop_length
         mels.append(mel[:, off:off + win])
         labels.append(wav[s0:s0 + seq_len + 1])
@@ -252,6 +265,10 @@ def main(argv=None):
     parser.add_argument('--gta', '-g', action='store_true', help='accepted for compatibility: the list file names the mels to train on')
     parser.add_argument('--hp_file', metavar='FILE', default=DEFAULT_HPARAMS, help='The file to use for the hyperparameters')
     parser.add_argument('--synthetic', type=int, metavar='N', default=0, help='train on N synthetic utterances instead of hp.feature_path')
+    parser.add_argument('--wav_dir', metavar='DIR', help='train on the wav files of a folder: mels and labels are made on the device and stay '
+                                                         'there (dataset.DeviceCorpus), every batch is cut by one kernel launch')
+    parser.add_argument('--resident', action='store_true', help='load the corpus of hp.feature_path onto the device once instead of reading '
+                                                                '.npy files every iteration')
     parser.add_argument('--total_steps', type=int, help='override hp.voc_total_steps')
     parser.add_argument('--reference_body', action='store_true',
                         help="run the reference's loop body (model(x, m) + torch loss) instead of the fused training_loss")
@@ -269,9 +286,26 @@ def main(argv=None):
     if args.synthetic:
         sig_bits = 16 if hp.voc_mode == 'MOL' else hp.bits
         train, test = synthetic_pairs(args.synthetic, 40, bits=sig_bits, n_mels=hp.num_mels, hop_length=hp.hop_length), []
+    elif args.wav_dir:
+        from .dataset import DeviceCorpus
+        wavs = sorted(Path(args.wav_dir).expanduser().glob('*.wav'))
+        if not wavs:
+            raise FileNotFoundError(f'no *.wav files in {args.wav_dir}')
+        corpus = DeviceCorpus.from_wavs(wavs, hp, 'cuda')
+        print(f'{len(corpus)} utterances of {len(wavs)} files | {corpus.hours:.3f} hours | {corpus.n_clipped} clipped samples')
+        train, held_out = corpus.split(hp.voc_test_samples)
+        test = held_out.pairs()
     else:
         train, test = read_feature_list(hp.feature_path, seq_len=hp.voc_seq_len, hop_length=hp.hop_length, pad=hp.voc_pad,
                                         test_samples=hp.voc_test_samples)
+        if args.resident:
+            from .dataset import DeviceCorpus
+            train = DeviceCorpus.load(train, 'cuda', hop_length=hp.hop_length)
+    if isinstance(train, list):
+        loader = WindowLoader(train, hp.voc_batch_size, **kw)
+    else:
+        from .dataset import DeviceWindowLoader
+        loader = DeviceWindowLoader(train, hp.voc_batch_size, **kw)
     total = args.total_steps if args.total_steps is not None else hp.voc_total_steps
     print(f'Remaining {total - model.get_step()} steps | batch {hp.voc_batch_size} | lr {hp.voc_lr} | seq_len {hp.voc_seq_len} | '
           f'{len(train)} training utterances')
@@ -285,16 +319,17 @@ def main(argv=None):
         from .dsp import decode_mu_law, label_2_float, save_wav
         k = step // 1000
         batch_str = f'gen_batched_target{hp.voc_target}_overlap{hp.voc_overlap}' if hp.voc_gen_batched else 'gen_NOT_BATCHED'
-        for i, (wav, mel) in enumerate(test_set[:hp.voc_gen_at_checkpoint], 1):
-            x = np.load(wav)                          # the quantised target (:28-37): decoded and kept next to the generated file, as the reference does
+        for i, pair in enumerate(test_set[:hp.voc_gen_at_checkpoint], 1):
+            mel, x = WindowLoader._arrays(pair)       # (wav path, mel path) of .npy files, or in-memory (mel (n_mels, frames), labels)
+            # the quantised target (:28-37): decoded and kept next to the generated file, as the reference does
             bits = 16 if hp.voc_mode == 'MOL' else hp.bits
             x = decode_mu_law(x, 2 ** bits, from_labels=True) if (hp.mu_law and hp.voc_mode != 'MOL') else label_2_float(x.astype(np.float64), bits)
             save_wav(x, paths.voc_output / f'{k}k_steps_{i}_target.wav')
-            m = torch.from_numpy(np.load(mel).T.astype(np.float32)).unsqueeze(0)
+            m = torch.from_numpy(np.ascontiguousarray(mel, dtype=np.float32)).unsqueeze(0)
             mod.generate(m, str(paths.voc_output / f'{k}k_steps_{i}_{batch_str}.wav'), hp.voc_gen_batched, hp.voc_target,
                          hp.voc_overlap, hp.mu_law)
 
-    voc_train_loop(paths, model, loss_func, optimizer, WindowLoader(train, hp.voc_batch_size, **kw), test, hp.voc_lr, total,
+    voc_train_loop(paths, model, loss_func, optimizer, loader, test, hp.voc_lr, total,
                    clip_grad_norm=hp.voc_clip_grad_norm, checkpoint_every=hp.voc_checkpoint_every, at_checkpoint=at_checkpoint,
                    report=lambda s: print('\r' + s, end='', flush=True))
     print('\nTraining Complete.')
