@@ -494,6 +494,36 @@ int wrnn_collate_windows(const int32_t *labels_dev, const float *mels_dev, const
                          int32_t hop, int32_t pad, int32_t seq_len, int32_t sig_bits, int32_t y_float, float *x_out, void *y_out,
                          float *mels_out, void *stream);
 
+/* ---- resampler (added to ABI 9 like the mel front end: new entry points only, so the number stays): wav at any integer sample rate ->
+ * wav at the model's, what librosa.load(path, sr=hp.sample_rate) does in wavernn/utils/dsp.py:18-19 for a file at another rate.  For
+ * src_rate -> dst_rate with g = gcd, p = dst / g, q = src / g, scale = min(1, p / q), half = ceil(64 / scale):
+ *   y[t] = sum_{j = -half + 1 .. half} h(j - r / p) x[n + j],  n = (t q) / p,  r = (t q) % p  (64-bit integers; x is 0 outside the clip),
+ *   h(u) = scale rolloff sinc(rolloff v) I0(beta sqrt(1 - (v / 64)^2)) / I0(beta) for v = scale |u| < 64, else 0,
+ * rolloff = 0.9475937167399596, beta = 14.769656459379492: the Kaiser-windowed sinc with 64 zero crossings of the `kaiser_best` family
+ * (the parameters of the reference's default resampler as far as we can tell; neither librosa nor resampy is available to compare with).
+ * h is evaluated exactly at the p x 2 half tap positions in float64 and rounded to float32 once by the create entry (no table lookup, no
+ * interpolation between table entries, no running float time register).  A clip of n samples gives ceil(n p / q) samples; librosa 0.7.2
+ * computes int(n ratio) and pads to the ceiling, so the two differ in at most the last sample.
+ * The create entry touches no device (WRNN_ERR_INVALID: a rate <= 0 or device < 0; WRNN_ERR_UNSUPPORTED: dst / src < 1/32, which bounds the
+ * kernel's LDS span, or a bank of more than 2^24 entries); a refused handle is still returned, for its error text and the destroy entry.
+ * The bank is uploaded by the first launch (one blocking copy; later calls are asynchronous). */
+typedef struct wrnn_resample_handle wrnn_resample_handle;
+int wrnn_resample_create(int32_t src_rate, int32_t dst_rate, int32_t device, wrnn_resample_handle **out);
+/* Host only: ceil(n_in p / q); WRNN_ERR_INVALID (< 0) for n_in < 0 or >= 2^31, or a refused handle. */
+int64_t wrnn_resample_out_len(const wrnn_resample_handle *h, int64_t n_in);
+/* Host only (tests): the float32 bank, bank[r * taps + k] = h(k - half + 1 - r / p), p * taps entries with taps = 2 half; any pointer may
+ * be NULL (call once for the sizes, then with a buffer). */
+int wrnn_resample_bank(const wrnn_resample_handle *h, float *bank, int32_t *p, int32_t *q, int32_t *taps);
+/* in_dev: B float32 clips in one buffer, row stride n_in_max samples; n_in_dev: B int32 on the device, the clips' own lengths (ragged; a
+ * value above n_in_max is read as n_in_max).  Whatever the buffer holds past a clip's own length is never read.  out_dev (B, n_out_max)
+ * float32: row b holds the ceil(n_in[b] p / q) samples of clip b (those below n_out_max) and ZEROS from there to n_out_max, the padding
+ * the mel and quantise entries rely on; a row equals the call on that clip alone bit for bit.  One launch, grid (ceil(n_out_max / 256), B),
+ * asynchronous on `stream`.  Equal rates: WRNN_ERR_INVALID (there is nothing to do, and the low-pass must not run at ratio 1). */
+int wrnn_resample(wrnn_resample_handle *h, const float *in_dev, int64_t n_in_max, const int32_t *n_in_dev, int32_t B, int64_t n_out_max,
+                  float *out_dev, void *stream);
+const char *wrnn_resample_last_error(const wrnn_resample_handle *h);
+void wrnn_resample_destroy(wrnn_resample_handle *h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,7 +37,9 @@ EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wr
                     'wrnn_stream_open', 'wrnn_stream_push', 'wrnn_stream_sync', 'wrnn_stream_info', 'wrnn_stream_ready_steps',
                     'wrnn_stream_close', 'wrnn_plan_folded', 'wrnn_generate_folded', 'wrnn_epilogue_folded',
                     'wrnn_mel_create', 'wrnn_mel_frames', 'wrnn_melspectrogram', 'wrnn_mel_tables', 'wrnn_mel_last_error', 'wrnn_mel_destroy',
-                    'wrnn_quantise', 'wrnn_collate_windows')
+                    'wrnn_quantise', 'wrnn_collate_windows',
+                    'wrnn_resample_create', 'wrnn_resample_out_len', 'wrnn_resample_bank', 'wrnn_resample', 'wrnn_resample_last_error',
+                    'wrnn_resample_destroy')
 
 
 def epilogue_tables(n_classes: int, overlap: int, hop: int):
@@ -141,7 +143,7 @@ def load_library() -> C.CDLL:
     if got != ABI_VERSION:   # the .so is a git-ignored build artefact: a stale one would read the structs at shifted offsets
         raise RuntimeError(f'{LIB_PATH} implements ABI {got}, this binding needs ABI {ABI_VERSION}: rebuild it '
                            '(`python -c "import __graft_entry__ as g; g.build()"`)')
-    # entry points have joined ABI 9 without a new number (the mel front end, the dataset kernels): a build from before them reports 9 too
+    # entry points have joined ABI 9 without a new number (the mel front end, the dataset kernels, the resampler): a build from before them reports 9 too
     missing = [s for s in EXPORTED_SYMBOLS if not hasattr(lib, s)]
     if missing:
         raise RuntimeError(f'{LIB_PATH} implements ABI {got} without {", ".join(missing)}: it was built from older sources, rebuild it '
@@ -227,6 +229,18 @@ def load_library() -> C.CDLL:
     lib.wrnn_mel_last_error.restype = C.c_char_p
     lib.wrnn_mel_destroy.argtypes = [vp]
     lib.wrnn_mel_destroy.restype = None
+    lib.wrnn_resample_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
+    lib.wrnn_resample_create.restype = C.c_int
+    lib.wrnn_resample_out_len.argtypes = [vp, C.c_int64]
+    lib.wrnn_resample_out_len.restype = C.c_int64
+    lib.wrnn_resample_bank.argtypes = [vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.wrnn_resample_bank.restype = C.c_int
+    lib.wrnn_resample.argtypes = [vp, vp, C.c_int64, vp, C.c_int32, C.c_int64, vp, vp]
+    lib.wrnn_resample.restype = C.c_int
+    lib.wrnn_resample_last_error.argtypes = [vp]
+    lib.wrnn_resample_last_error.restype = C.c_char_p
+    lib.wrnn_resample_destroy.argtypes = [vp]
+    lib.wrnn_resample_destroy.restype = None
     lib.wrnn_quantise.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp]
     lib.wrnn_quantise.restype = C.c_int
     lib.wrnn_collate_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -620,6 +634,57 @@ class NativeMel:
     def close(self):
         if getattr(self, '_h', None):
             self.lib.wrnn_mel_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NativeResampler:
+    """Owner of one ``wrnn_resample_handle`` (``src_rate -> dst_rate``).  Creating it touches no device; rates the library refuses raise
+    ``ValueError`` (a rate <= 0: WRNN_ERR_INVALID; a ratio below 1/32 or an oversized filter bank: WRNN_ERR_UNSUPPORTED)."""
+
+    def __init__(self, src_rate: int, dst_rate: int, device: int = 0):
+        self.lib = load_library()
+        self.src_rate, self.dst_rate, self.device = int(src_rate), int(dst_rate), int(device)
+        if not (-2 ** 31 <= self.src_rate < 2 ** 31 and -2 ** 31 <= self.dst_rate < 2 ** 31):
+            raise ValueError(f'WRNN_ERR_INVALID: sample rates {src_rate} -> {dst_rate} do not fit 32 bits')
+        self._h = C.c_void_p()
+        rc = self.lib.wrnn_resample_create(self.src_rate, self.dst_rate, self.device, C.byref(self._h))
+        if rc != 0:
+            msg = self.lib.wrnn_resample_last_error(self._h).decode() if self._h else 'wrnn_resample_create failed'
+            self.close()
+            raise ValueError(f'{ERR_NAMES.get(rc, rc)}: {msg}')
+        p, q, taps = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(self.lib.wrnn_resample_bank(self._h, None, C.byref(p), C.byref(q), C.byref(taps)))
+        self.p, self.q, self.taps = p.value, q.value, taps.value
+
+    def _check(self, rc: int):
+        if rc != 0:
+            raise WrnnError(rc, self.lib.wrnn_resample_last_error(self._h).decode())
+
+    def out_len(self, n_in: int) -> int:
+        """Host-only ``wrnn_resample_out_len``: ceil(n p / q)."""
+        n = int(self.lib.wrnn_resample_out_len(self._h, int(n_in))) if 0 <= int(n_in) < 2 ** 31 else -1
+        if n < 0:
+            raise ValueError(f'a clip length of {int(n_in)} samples is outside 0 .. 2**31 - 1')
+        return n
+
+    def bank(self) -> np.ndarray:
+        """The float32 filter bank (``wrnn_resample_bank``), ``(p, taps)``: row r holds ``h(k - taps / 2 + 1 - r / p)``."""
+        bank = np.empty((self.p, self.taps), np.float32)
+        self._check(self.lib.wrnn_resample_bank(self._h, bank.ctypes.data, None, None, None))
+        return bank
+
+    def resample(self, in_ptr: int, n_in_max: int, n_in_ptr: int, B: int, n_out_max: int, out_ptr: int, stream: int):
+        self._check(self.lib.wrnn_resample(self._h, in_ptr, int(n_in_max), n_in_ptr, int(B), int(n_out_max), out_ptr, stream or None))
+
+    def close(self):
+        if getattr(self, '_h', None):
+            self.lib.wrnn_resample_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -12,6 +12,7 @@
 #include <mutex>
 
 #include "mel_internal.h"
+#include "resample_internal.h"
 #include "wrnn_internal.h"
 
 namespace {
@@ -856,6 +857,105 @@ void wrnn_mel_destroy(wrnn_mel_handle *h) {
     if (h->dev) {
         (void)hipSetDevice(h->cfg.device);
         (void)hipFree(h->dev);
+    }
+    delete h;
+}
+
+}  // extern "C"
+
+// ---- resampler: a handle of its own, like the mel front end ------------------------------------------------------------
+
+struct wrnn_resample_handle {
+    int32_t src_rate = 0, dst_rate = 0, device = 0;
+    WrnnResamplePlan plan;
+    float *bank_dev = nullptr;    // wrnn_resample_device_bank, uploaded by the first wrnn_resample
+    std::string err;
+};
+
+namespace {
+int rs_fail(wrnn_resample_handle *h, int code, const char *fmt, ...) {
+    char buf[400];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    if (h) h->err = buf;
+    return code;
+}
+#define RS_TRY(h, expr)                                                                                   \
+    do {                                                                                                  \
+        hipError_t e__ = (expr);                                                                          \
+        if (e__ != hipSuccess) return rs_fail((h), WRNN_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e__)); \
+    } while (0)
+}  // namespace
+
+extern "C" {
+
+int wrnn_resample_create(int32_t src_rate, int32_t dst_rate, int32_t device, wrnn_resample_handle **out) {
+    if (!out) return WRNN_ERR_INVALID;
+    wrnn_resample_handle *h = new wrnn_resample_handle();
+    *out = h;
+    h->src_rate = src_rate; h->dst_rate = dst_rate; h->device = device;
+    if (device < 0) return rs_fail(h, WRNN_ERR_INVALID, "bad configuration: device >= 0");
+    const int rc = wrnn_resample_build_plan(src_rate, dst_rate, &h->plan);
+    if (rc == WRNN_ERR_INVALID) return rs_fail(h, rc, "bad configuration: %d Hz -> %d Hz, both rates must be positive", src_rate, dst_rate);
+    if (rc != WRNN_OK)
+        return rs_fail(h, rc, "%d Hz -> %d Hz is outside what the resampler is built for: a ratio of at least 1/%d and a filter bank of at most "
+                              "%d entries (the bank has one phase per output position of the reduced ratio)",
+                       src_rate, dst_rate, WRNN_RS_MIN_SCALE_INV, WRNN_RS_MAX_BANK);
+    return WRNN_OK;
+}
+
+int64_t wrnn_resample_out_len(const wrnn_resample_handle *h, int64_t n_in) {
+    if (!h || h->plan.bank.empty() || n_in < 0 || n_in > INT32_MAX) return WRNN_ERR_INVALID;
+    return (n_in * h->plan.p + h->plan.q - 1) / h->plan.q;
+}
+
+int wrnn_resample_bank(const wrnn_resample_handle *h, float *bank, int32_t *p, int32_t *q, int32_t *taps) {
+    if (!h || h->plan.bank.empty()) return WRNN_ERR_INVALID;
+    if (bank) std::copy(h->plan.bank.begin(), h->plan.bank.end(), bank);
+    if (p) *p = h->plan.p;
+    if (q) *q = h->plan.q;
+    if (taps) *taps = h->plan.taps;
+    return WRNN_OK;
+}
+
+int wrnn_resample(wrnn_resample_handle *h, const float *in_dev, int64_t n_in_max, const int32_t *n_in_dev, int32_t B, int64_t n_out_max,
+                  float *out_dev, void *stream) {
+    if (!h) return WRNN_ERR_INVALID;
+    const WrnnResamplePlan &pl = h->plan;
+    if (pl.bank.empty()) return rs_fail(h, WRNN_ERR_STATE, "the handle's rates were refused by wrnn_resample_create");
+    if (pl.p == pl.q) return rs_fail(h, WRNN_ERR_INVALID, "equal rates: there is nothing to resample, and the filter is a low-pass that must not run at ratio 1");
+    if (!in_dev || !n_in_dev || !out_dev || n_in_max < 1 || n_in_max > INT32_MAX || B < 1 || B > 65535 || n_out_max < 1 ||
+        n_out_max > (int64_t)INT32_MAX * WRNN_RS_TILE)
+        return rs_fail(h, WRNN_ERR_INVALID, "bad arguments: device pointers, 1 <= n_in_max < 2^31, 1 <= B <= 65535, n_out_max >= 1");
+    RS_TRY(h, hipSetDevice(h->device));
+    if (!h->bank_dev) {
+        const std::vector<float> bt = wrnn_resample_device_bank(pl);
+        void *d = nullptr;
+        RS_TRY(h, hipMalloc(&d, bt.size() * sizeof(float)));
+        hipError_t e = hipMemcpy(d, bt.data(), bt.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            return rs_fail(h, WRNN_ERR_HIP, "uploading the filter bank: %s", hipGetErrorString(e));
+        }
+        h->bank_dev = (float *)d;
+    }
+    WrnnResampleArgs a{};
+    a.in = in_dev; a.n_in = n_in_dev; a.out = out_dev; a.bank = h->bank_dev;
+    a.n_in_max = n_in_max; a.n_out_max = n_out_max;
+    a.p = pl.p; a.q = pl.q; a.half = pl.half; a.taps = pl.taps;
+    RS_TRY(h, wrnn_launch_resample(a, B, pl.span_max, (hipStream_t)stream));
+    return WRNN_OK;
+}
+
+const char *wrnn_resample_last_error(const wrnn_resample_handle *h) { return h ? h->err.c_str() : "null handle"; }
+
+void wrnn_resample_destroy(wrnn_resample_handle *h) {
+    if (!h) return;
+    if (h->bank_dev) {
+        (void)hipSetDevice(h->device);
+        (void)hipFree(h->bank_dev);
     }
     delete h;
 }

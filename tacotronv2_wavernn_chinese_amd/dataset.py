@@ -137,50 +137,80 @@ class DeviceCorpus:
                    hop_length=hop_length, **meta)
 
     @classmethod
-    def from_wavs(cls, paths_or_arrays, hp, device=None, batch_clips: int = 16) -> 'DeviceCorpus':
+    def from_wavs(cls, paths_or_arrays, hp, device=None, batch_clips: int = 16, resample: bool = False) -> 'DeviceCorpus':
         """Wav files (``frontend.load_wav``) or float arrays in [-1, 1] -> corpus.  The clips go to the device in ragged groups of
         ``batch_clips`` (grouped by length, so that little of a group's buffer is padding); each group's buffer is read by one launch of
         the mel front end and one of ``wrnn_quantise``.  Bits and companding follow ``hp`` (``signal_bits``); utterances too short for
         ``hp.voc_seq_len`` / ``hp.voc_pad`` are dropped like ``get_vocoder_datasets`` does.  ``n_clipped`` counts samples with
-        ``|x| > 1``: their labels are clipped, where the reference asserts."""
-        from .frontend import MelFrontEnd, load_wav
+        ``|x| > 1``: their labels are clipped, where the reference asserts.
+
+        An array item may be an ``(array, rate)`` pair.  A file or a pair at another rate than ``hp.sample_rate`` raises ``ValueError``
+        unless ``resample=True``: then the groups are formed per source rate, a group at another rate is uploaded at its own rate and one
+        launch of ``frontend.Resampler`` writes the zero-padded buffer the two launches above read -- no host round trip is added.  Lengths,
+        frame counts and the short-utterance filter use the resampled length.  Resampled peaks may exceed 1 (``n_clipped`` counts them)."""
+        from .frontend import MelFrontEnd, Resampler, load_wav, read_wav
         dev = _device(device)
         fe = MelFrontEnd(hp, device=dev)
         hop, n_mels = fe.hop_length, fe.n_mels
         bits, mu_law = signal_bits(hp)
         least = min_frames(hop_length=hop, pad=int(hp.voc_pad), seq_len=int(hp.voc_seq_len))
-        clips, stems = [], []
+        clips, stems, rates, out_lens, resamplers = [], [], [], [], {}
         for i, item in enumerate(paths_or_arrays):
+            rate = fe.sample_rate
             if isinstance(item, (str, Path)):
-                wav, stem = load_wav(item, fe.sample_rate), Path(item).stem
+                stem = Path(item).stem
+                if resample:
+                    wav, rate = read_wav(item)
+                else:
+                    wav = load_wav(item, fe.sample_rate)
             else:
+                if isinstance(item, tuple) and len(item) == 2 and np.ndim(item[1]) == 0 and np.ndim(item[0]) == 1:
+                    item, rate = item[0], int(item[1])
                 wav = item.detach().cpu().numpy() if isinstance(item, torch.Tensor) else np.asarray(item)
                 wav, stem = np.ascontiguousarray(wav, dtype=np.float32), f'utt{i:05d}'
             if wav.ndim != 1:
                 raise ValueError(f'expected 1-D clips of samples, got shape {wav.shape}')
-            if 1 + wav.shape[0] // hop < least:
+            n = int(wav.shape[0])
+            if rate != fe.sample_rate:
+                if not resample:
+                    raise ValueError(f'clip {stem!r} is sampled at {rate} Hz, the model needs {fe.sample_rate} Hz: pass resample=True '
+                                     f'for the resampler on the device')
+                if rate not in resamplers:
+                    resamplers[rate] = Resampler(rate, fe.sample_rate, device=dev)
+                n = resamplers[rate].out_len(n)
+            if 1 + n // hop < least or wav.shape[0] < 1:
                 continue
             clips.append(wav)
             stems.append(stem)
+            rates.append(rate)
+            out_lens.append(n)
         if not clips:
             raise ValueError(f'no utterance has the {least} mel frames one training window needs')
-        lens = np.array([c.shape[0] for c in clips], np.int64)
+        lens = np.array(out_lens, np.int64)                       # at the model's rate
+        src_lens = np.array([c.shape[0] for c in clips], np.int64)
         frames = np.array([fe.frames(int(n)) for n in lens], np.int64)
         label_off = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
         mel_off = np.concatenate([[0], np.cumsum(frames)[:-1]]).astype(np.int64) * n_mels
         by_len = np.argsort(lens, kind='stable')
+        rates = np.array(rates, np.int64)
+        step = max(1, int(batch_clips))
+        groups = []                                               # the model's own rate first, then the others as they first appear
+        for rate in [fe.sample_rate] + list(resamplers):
+            ids = by_len[rates[by_len] == rate]
+            groups += [(rate, ids[g:g + step]) for g in range(0, len(ids), step)]
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             labels = torch.empty(int(lens.sum()), dtype=torch.int32, device=dev)
             mels = torch.empty(int(frames.sum()) * n_mels, dtype=torch.float32, device=dev)
             clipped = torch.zeros(1, dtype=torch.int64, device=dev)
-            for g in range(0, len(by_len), max(1, int(batch_clips))):
-                ids = by_len[g:g + max(1, int(batch_clips))]
-                n_max = int(lens[ids].max())
-                host = np.zeros((len(ids), n_max), np.float32)
+            for rate, ids in groups:
+                host = np.zeros((len(ids), int(src_lens[ids].max())), np.float32)
                 for r, u in enumerate(ids):
-                    host[r, :lens[u]] = clips[u]
+                    host[r, :src_lens[u]] = clips[u]
                 wav = torch.from_numpy(host).to(dev)
+                if rate != fe.sample_rate:
+                    wav = resamplers[rate].resample_padded(wav, src_lens[ids])      # (B, max lens[ids]), zero past each clip
+                n_max = int(wav.shape[1])
                 mel = fe.melspectrogram_padded(wav, lens[ids])                      # (B, n_mels, T_max)
                 lab = torch.empty((len(ids), n_max), dtype=torch.int32, device=dev)
                 _cabi.quantise(wav.data_ptr(), wav.numel(), bits, mu_law, lab.data_ptr(), clipped.data_ptr(), stream)   # the padding is 0: never clipped
@@ -281,10 +311,12 @@ def main(argv=None):
     import argparse
     from .hparams import DEFAULT_HPARAMS, hparams as hp
     parser = argparse.ArgumentParser(description='Preprocess a folder of wavs for WaveRNN vocoder training')
-    parser.add_argument('--wav_dir', required=True, metavar='DIR', help='folder of wav files at hp.sample_rate')
+    parser.add_argument('--wav_dir', required=True, metavar='DIR', help='folder of wav files at hp.sample_rate (any rate with --resample)')
     parser.add_argument('--out_dir', required=True, metavar='DIR', help='where quant/, mel/ and the list file go')
     parser.add_argument('--hp_file', metavar='FILE', default=DEFAULT_HPARAMS, help='The file to use for the hyperparameters')
     parser.add_argument('--batch_clips', type=int, default=16, help='clips per launch of the front end')
+    parser.add_argument('--resample', action='store_true', help='resample files at another rate to hp.sample_rate on the device '
+                                                                '(default: such a file is an error)')
     args = parser.parse_args(argv)
     hp.configure(args.hp_file)
     if not torch.cuda.is_available():
@@ -292,7 +324,7 @@ def main(argv=None):
     wavs = sorted(Path(args.wav_dir).expanduser().glob('*.wav'))
     if not wavs:
         raise FileNotFoundError(f'no *.wav files in {args.wav_dir}')
-    corpus = DeviceCorpus.from_wavs(wavs, hp, 'cuda', batch_clips=args.batch_clips)
+    corpus = DeviceCorpus.from_wavs(wavs, hp, 'cuda', batch_clips=args.batch_clips, resample=args.resample)
     listing = corpus.save(args.out_dir)
     print(f'{len(corpus)} utterances of {len(wavs)} files | {corpus.hours:.3f} hours | {corpus.n_clipped} clipped samples | '
           f'{corpus.bits} bits {"mu-law" if corpus.mu_law else "linear"} | {listing}')

@@ -13,7 +13,8 @@ runs on the MI355X.  Extensions: ``--target auto|per_xcd``, ``--noise reference 
 The ``.wav`` branch (:17-20) does what the reference's intends: ``load_wav``, the input saved as ``__{idx}__{k}k_steps_target.wav`` (the
 reference names an undefined ``file_name`` there; ``idx`` is the stem it computes at :38), then the mel of the clip -- built on the device by
 ``frontend.MelFrontEnd`` (``csrc/melspec.hip``) instead of librosa -- takes the same path as a ``.npy`` mel, ``--stream-frames`` included.  A file
-at another sample rate raises ``ValueError`` (no resampler is built in).
+at another sample rate raises ``ValueError`` unless ``resample=True`` / ``--resample``: then it is resampled on the device
+(``frontend.Resampler``, ``csrc/resample.hip``) and the saved target file is the resampled clip at the model's rate, as the reference's is.
 """
 from __future__ import annotations
 
@@ -30,7 +31,7 @@ from .hparams import hparams as hp
 from .vocoder import WaveRNN
 
 
-def gen_from_file(model: WaveRNN, load_path, save_path, batched, target, overlap, stream_frames=None, **generate_opts):
+def gen_from_file(model: WaveRNN, load_path, save_path, batched, target, overlap, stream_frames=None, resample=False, **generate_opts):
     k = model.get_step() // 1000
     load_path = str(load_path)
     if ".npy" in load_path:
@@ -44,7 +45,7 @@ def gen_from_file(model: WaveRNN, load_path, save_path, batched, target, overlap
     elif ".wav" in load_path:
         if not os.path.isfile(load_path):   # an input check like the ones above, not an OSError from inside the wav reader
             raise ValueError(f'{load_path}: no such wav file')
-        wav = load_wav(load_path, hp.sample_rate)
+        wav = load_wav(load_path, hp.sample_rate, resample=resample, device=torch.device('cuda', model._device_index()) if resample else None)
         idx = load_path.split('/')[-1].strip().split('.')[0]
         save_wav(wav, os.path.join(str(save_path), f'__{idx}__{k}k_steps_target.wav'), hp.sample_rate)
         mel = model.mel_front_end().melspectrogram(wav, device=torch.device('cuda', model._device_index()))   # (1, n_mels, T) on the device
@@ -115,7 +116,9 @@ def main(argv=None):
                         help="[int] number of samples in each batch index ('auto': the fold length with the lowest predicted latency on this GPU; "
                              "'per_xcd': one fold per XCD)")
     parser.add_argument('--overlap', '-o', type=int, help='[int] number of crossover samples')
-    parser.add_argument('--file', '-f', type=str, help='[string/path] (T, n_mels) .npy mel, or a .wav at the model sample rate, to vocode')
+    parser.add_argument('--file', '-f', type=str, help='[string/path] (T, n_mels) .npy mel, or a .wav at the model sample rate (any rate with --resample), to vocode')
+    parser.add_argument('--resample', action='store_true',
+                        help='extension: resample a --file .wav at another rate to the model sample rate on the device (default: an error)')
     parser.add_argument('--voc_weights', '-w', type=str, help='[string/path] Load in different WaveRNN weights')
     parser.add_argument('--gta', '-g', dest='gta', action='store_true', help='Generate from GTA testset')
     parser.add_argument('--force_cpu', '-c', action='store_true',
@@ -167,7 +170,7 @@ def main(argv=None):
         if args.stream_frames is not None and args.noise != 'philox':
             raise ValueError('--stream-frames draws its noise on the device: --noise reference needs the whole clip')
         gen_from_file(model, args.file, out_dir, args.batched, args.target, args.overlap, stream_frames=args.stream_frames,
-                      noise_mode=args.noise)
+                      noise_mode=args.noise, resample=args.resample)
     print('\n\nExiting...\n')
 
 

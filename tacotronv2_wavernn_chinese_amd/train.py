@@ -267,6 +267,8 @@ def main(argv=None):
     parser.add_argument('--synthetic', type=int, metavar='N', default=0, help='train on N synthetic utterances instead of hp.feature_path')
     parser.add_argument('--wav_dir', metavar='DIR', help='train on the wav files of a folder: mels and labels are made on the device and stay '
                                                          'there (dataset.DeviceCorpus), every batch is cut by one kernel launch')
+    parser.add_argument('--resample', action='store_true', help='with --wav_dir: resample files at another rate to hp.sample_rate on the '
+                                                                'device (default: such a file is an error)')
     parser.add_argument('--resident', action='store_true', help='load the corpus of hp.feature_path onto the device once instead of reading '
                                                                 '.npy files every iteration')
     parser.add_argument('--total_steps', type=int, help='override hp.voc_total_steps')
@@ -291,7 +293,7 @@ def main(argv=None):
         wavs = sorted(Path(args.wav_dir).expanduser().glob('*.wav'))
         if not wavs:
             raise FileNotFoundError(f'no *.wav files in {args.wav_dir}')
-        corpus = DeviceCorpus.from_wavs(wavs, hp, 'cuda')
+        corpus = DeviceCorpus.from_wavs(wavs, hp, 'cuda', resample=args.resample)
         print(f'{len(corpus)} utterances of {len(wavs)} files | {corpus.hours:.3f} hours | {corpus.n_clipped} clipped samples')
         train, held_out = corpus.split(hp.voc_test_samples)
         test = held_out.pairs()

@@ -706,16 +706,48 @@ class WaveRNN(nn.Module):
                              f'{self.feat_dims} at hop {self.hop_length}')
         return front_end
 
-    def generate_from_wav(self, wav, save_path: Union[str, Path], batched, target, overlap, mu_law, front_end=None, **generate_opts):
+    def resampler(self, wav_rate):
+        """The ``frontend.Resampler`` from ``wav_rate`` to this model's ``sample_rate`` (one per source rate, kept)."""
+        from .frontend import Resampler
+        cache = self.__dict__.setdefault('_resamplers', {})
+        if int(wav_rate) not in cache:
+            cache[int(wav_rate)] = Resampler(int(wav_rate), self.sample_rate)
+        return cache[int(wav_rate)]
+
+    def generate_from_wav(self, wav, save_path: Union[str, Path], batched, target, overlap, mu_law, front_end=None, wav_rate=None,
+                          **generate_opts):
         """Copy-synthesis, the ``.wav`` branch of ``wavernn_gen.py:17-20``: the mel of ``wav`` (1-D samples in [-1, 1] at the model's sample
         rate) is built on the device (``mel_front_end``) and handed to ``generate`` as a device tensor, without a host round trip.  Returns
-        what ``generate`` returns for that mel: ``(T - 1) * hop`` samples, ``T = 1 + len(wav) // hop``."""
+        what ``generate`` returns for that mel: ``(T - 1) * hop`` samples, ``T = 1 + len(wav) // hop``.  ``wav_rate``: the clip's own sample
+        rate; one that differs from the model's is resampled on the device first (``frontend.Resampler``), and ``len(wav)`` above is then
+        the resampled length ``ceil(len * sample_rate / wav_rate)``."""
         fe = self.mel_front_end(front_end)
-        mel = fe.melspectrogram(wav, device=torch.device('cuda', self._device_index()))
+        dev = torch.device('cuda', self._device_index())
+        if wav_rate is not None and int(wav_rate) != self.sample_rate:
+            wav = self.resampler(wav_rate).resample(wav, device=dev)   # (1, n) on the device
+        mel = fe.melspectrogram(wav, device=dev)
         return self.generate(mel, save_path, batched, target, overlap, mu_law, **generate_opts)
 
+    def _resample_clips(self, wavs, wav_rates, dev):
+        """``wavs`` with every clip at another rate than the model's replaced by its resampled version on the device: one launch per
+        source rate.  When anything was resampled the remaining clips go to the device too, so that the front end's ragged launch reads
+        device clips only."""
+        rates = [int(wav_rates)] * len(wavs) if np.ndim(wav_rates) == 0 else [int(r) for r in wav_rates]
+        if len(rates) != len(wavs):
+            raise ValueError(f'{len(rates)} wav_rates for {len(wavs)} clips')
+        if all(r == self.sample_rate for r in rates):
+            return list(wavs)
+        out = [w if r != self.sample_rate else torch.as_tensor(w).to(device=dev, dtype=torch.float32) for w, r in zip(wavs, rates)]
+        for rate in sorted(set(rates) - {self.sample_rate}):
+            ids = [i for i, r in enumerate(rates) if r == rate]
+            rs = self.resampler(rate)
+            rows = rs.resample([wavs[i] for i in ids], device=dev)
+            for row, n, i in zip(rows, rs.last_lens, ids):
+                out[i] = row[:n]
+        return out
+
     def generate_many(self, mels_list=None, save_paths=None, mu_law=True, epilogue='host', batched=False, target='auto', overlap=550, seeds=None,
-                      wavs=None, front_end=None, **native_opts):
+                      wavs=None, front_end=None, wav_rates=None, **native_opts):
         """Extension for serving loops: several independent utterances of different lengths in ONE device call, so that all
         8 XCD teams of the GPU work (a single unbatched utterance keeps one team = 1/8 of the chip busy; up to 8 utterances
         run on the latency kernel one per team, more on the batch kernel).  ``mels_list``: sequence of (n_mels, T_i) arrays.
@@ -746,7 +778,8 @@ class WaveRNN(nn.Module):
 
         ``wavs=`` in place of ``mels_list``: a list of 1-D sample arrays; their mels are built by ONE ragged launch of the device front end
         (``mel_front_end``; clip i has ``1 + len(wavs[i]) // hop`` frames) and stay on the device.  Everything else is as for the same
-        mels given as ``mels_list``."""
+        mels given as ``mels_list``.  ``wav_rates``: the clips' own sample rates, one int for all or one per clip; clips at another rate
+        than the model's are resampled on the device first (``frontend.Resampler``, one launch per source rate)."""
         if (mels_list is None) == (wavs is None):
             raise ValueError('give either mels_list or wavs')
         n_req = len(mels_list) if wavs is None else len(wavs)
@@ -762,6 +795,8 @@ class WaveRNN(nn.Module):
             fe = self.mel_front_end(front_end)
             if not len(wavs):
                 raise ValueError('expected a non-empty sequence of clips')
+            if wav_rates is not None:
+                wavs = self._resample_clips(wavs, wav_rates, torch.device('cuda', self._device_index()))
             lens = [fe.frames(int(np.shape(w)[0])) for w in wavs]
             arrs = lens   # one entry per clip; the mels themselves are made on the device below
         else:
