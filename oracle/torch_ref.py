@@ -65,8 +65,9 @@ def _gru(x, w_ih, w_hh, b_ih, b_hh):
     return torch.stack(out, dim=1)
 
 
-def loop_forward(sd: Dict[str, torch.Tensor], x: torch.Tensor, mels_up: torch.Tensor, aux: torch.Tensor):
-    """forward() from the upsampled conditioning on (:145-167): fc3 outputs (B, L, n_classes)."""
+def loop_forward(sd: Dict[str, torch.Tensor], x: torch.Tensor, mels_up: torch.Tensor, aux: torch.Tensor, return_pre: bool = False):
+    """forward() from the upsampled conditioning on (:145-167): fc3 outputs (B, L, n_classes).  return_pre: also the fc1 / fc2
+    pre-activations (B, L, fc_dims) each -- what the two ReLUs see (tests/train_steer.py)."""
     A = aux.shape[2] // 4
     a1, a2, a3, a4 = (aux[:, :, i * A:(i + 1) * A] for i in range(4))
     h = torch.cat([x.unsqueeze(-1), mels_up, a1], dim=2) @ sd['I.weight'].t() + sd['I.bias']
@@ -74,9 +75,10 @@ def loop_forward(sd: Dict[str, torch.Tensor], x: torch.Tensor, mels_up: torch.Te
     h = _gru(h, sd['rnn1.weight_ih_l0'], sd['rnn1.weight_hh_l0'], sd['rnn1.bias_ih_l0'], sd['rnn1.bias_hh_l0']) + res
     res = h
     h = _gru(torch.cat([h, a2], dim=2), sd['rnn2.weight_ih_l0'], sd['rnn2.weight_hh_l0'], sd['rnn2.bias_ih_l0'], sd['rnn2.bias_hh_l0']) + res
-    h = F.relu(torch.cat([h, a3], dim=2) @ sd['fc1.weight'].t() + sd['fc1.bias'])
-    h = F.relu(torch.cat([h, a4], dim=2) @ sd['fc2.weight'].t() + sd['fc2.bias'])
-    return h @ sd['fc3.weight'].t() + sd['fc3.bias']
+    p1 = torch.cat([h, a3], dim=2) @ sd['fc1.weight'].t() + sd['fc1.bias']
+    p2 = torch.cat([F.relu(p1), a4], dim=2) @ sd['fc2.weight'].t() + sd['fc2.bias']
+    y = F.relu(p2) @ sd['fc3.weight'].t() + sd['fc3.bias']
+    return (y, p1, p2) if return_pre else y
 
 
 def _log_sum_exp(x):                                                            # distribution.py:6-12
