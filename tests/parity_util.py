@@ -169,3 +169,21 @@ def label_stats(got, ref_labels, first):
             t = int(first[r])
             near.append(int(abs(int(got[t, r]) - int(ref_labels[t, r]))))
     return dict(compared=compared, mismatches=mism, max_abs=max_abs, near_tie_abs=near)
+
+
+def stream_raw(m, mels, sizes, **kw):
+    """Push mels (B, n_mels, T) through ``m.stream(raw=True, **kw)`` in chunks of `sizes` frames, then finish: the raw outputs
+    concatenated, (labels, samples) numpy (B, T * hop)."""
+    B = mels.shape[0]
+    labs, smps = [], []
+    with m.stream(batch=B, raw=True, **kw) as st:
+        f = 0
+        for k in sizes:
+            r = st.push(mels[:, :, f:f + k] if B > 1 else mels[0, :, f:f + k])
+            f += k
+            labs.append(r['labels'].cpu().numpy())
+            smps.append(r['samples'].cpu().numpy())
+        r = st.finish()
+        labs.append(r['labels'].cpu().numpy())
+        smps.append(r['samples'].cpu().numpy())
+    return np.concatenate(labs, axis=1), np.concatenate(smps, axis=1)

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.parity_util import stream_raw as _stream_raw
+
 pytestmark = pytest.mark.gpu
 
 HOP = 275
@@ -38,23 +40,6 @@ def _partition(kind, T, seed=0):
         sizes.append(int(min(rng.integers(0, 7), T - sum(sizes))))   # zero-frame pushes included
     sizes.insert(1, 0)
     return sizes
-
-
-def _stream_raw(m, mels, sizes, **kw):
-    """Push mels (B, n_mels, T) in chunks of `sizes` frames, raw outputs concatenated: (labels, samples) numpy (B, T * hop)."""
-    B = mels.shape[0]
-    labs, smps = [], []
-    with m.stream(batch=B, raw=True, **kw) as st:
-        f = 0
-        for k in sizes:
-            r = st.push(mels[:, :, f:f + k] if B > 1 else mels[0, :, f:f + k])
-            f += k
-            labs.append(r['labels'].cpu().numpy())
-            smps.append(r['samples'].cpu().numpy())
-        r = st.finish()
-        labs.append(r['labels'].cpu().numpy())
-        smps.append(r['samples'].cpu().numpy())
-    return np.concatenate(labs, axis=1), np.concatenate(smps, axis=1)
 
 
 @pytest.mark.parametrize('B', [1, 3])
