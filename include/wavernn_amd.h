@@ -524,6 +524,36 @@ int wrnn_resample(wrnn_resample_handle *h, const float *in_dev, int64_t n_in_max
 const char *wrnn_resample_last_error(const wrnn_resample_handle *h);
 void wrnn_resample_destroy(wrnn_resample_handle *h);
 
+/* ---- wav conditioning (new entry points in ABI 9 again): the two steps the reference applies to every training wav between loading
+ * it and the mel (tacotron/datasets/preprocessor.py:62-72): trim leading and trailing silence (audio.trim_silence =
+ * librosa.effects.trim(wav, top_db, frame_length, hop)[0]), then wav / abs(wav).max() * rescaling_max.  For a clip x of n samples:
+ *   p = x reflect-padded by frame_length / 2 on both sides (numpy mode='reflect'; needs n >= frame_length / 2 + 1),
+ *   e[f] = mean(p[f hop : f hop + frame_length] ** 2) for the F = 1 + n / hop frames, summed in float64,
+ *   frame f is non-silent when max(1e-10, e[f]) > 10 ** (-top_db / 10) * max(1e-10, max_f e), decided in float64
+ *   (10 log10 of both sides is librosa's power_to_db(e, ref=np.max) > -top_db; librosa itself computes in float32),
+ *   start = first_non_silent * hop, end = min(n, (last_non_silent + 1) * hop); digital silence is kept whole,
+ *   peak = max |x[start : end]|,  y[i] = x[start + i] / peak * target: a correctly rounded float32 divide, then one float32 multiply;
+ *   peak == 0 leaves the clip unscaled.
+ * Non-finite samples promise nothing about values, only that nothing outside the clip is read and 0 <= start <= end <= n.
+ * No handle, like wrnn_quantise: asynchronous on `stream`, nothing waits on the host, arguments are checked before any device call. */
+/* Host only: the F = 1 + n / hop frames of a clip of n samples; WRNN_ERR_INVALID (< 0) for n < frame_length / 2 + 1 or a window
+ * wrnn_condition refuses. */
+int64_t wrnn_condition_frames(int64_t n, int32_t frame_length, int32_t hop);
+/* wav_dev: B float32 clips in one buffer, row stride n_max; n_dev: B int32 on the device, the clips' own lengths (a value above n_max is
+ * read as n_max, a negative one as 0; what lies past a clip is never read).  trim == 0: whole-clip bounds; peak_target == 0: no scaling;
+ * both: WRNN_ERR_INVALID, there is nothing to do.  energy_ws_dev: caller-allocated workspace of B * F_max + B float64; the first
+ * (B, F_max) are the frame energies (zeros at and past a clip's own F; frames past F_max are ignored, so F_max should be
+ * wrnn_condition_frames of the longest clip; untouched when trim == 0), the last B are one 8-byte record per clip that the decision
+ * launch leaves for the gather.  out_dev (B, n_out_max) float32 with n_out_max >= n_max: row b holds the end - start conditioned samples
+ * from column 0 and ZEROS from there to n_out_max, the padding the mel and quantise entries rely on; it must not overlap wav_dev.
+ * n_out_dev[b] = end - start, ready to be wrnn_melspectrogram's n_samples_dev.  bounds_dev (B, 2) int32 (start, end) and peak_dev (B)
+ * float32 may be NULL.  A row equals the call on that clip alone bit for bit, energies included.  WRNN_ERR_INVALID: top_db <= 0 or
+ * non-finite, frame_length outside 2 .. 8192, hop outside 1 .. frame_length, peak_target < 0 or non-finite, B outside 1 .. 65535,
+ * n_max < 1, n_out_max < n_max or >= 2^31, F_max < 1, a NULL required pointer. */
+int wrnn_condition(const float *wav_dev, int64_t n_max, const int32_t *n_dev, int32_t B, int32_t trim, double top_db, int32_t frame_length,
+                   int32_t hop, float peak_target, double *energy_ws_dev, int32_t F_max, float *out_dev, int64_t n_out_max,
+                   int32_t *n_out_dev, int32_t *bounds_dev, float *peak_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,7 +39,7 @@ EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wr
                     'wrnn_mel_create', 'wrnn_mel_frames', 'wrnn_melspectrogram', 'wrnn_mel_tables', 'wrnn_mel_last_error', 'wrnn_mel_destroy',
                     'wrnn_quantise', 'wrnn_collate_windows',
                     'wrnn_resample_create', 'wrnn_resample_out_len', 'wrnn_resample_bank', 'wrnn_resample', 'wrnn_resample_last_error',
-                    'wrnn_resample_destroy')
+                    'wrnn_resample_destroy', 'wrnn_condition_frames', 'wrnn_condition')
 
 
 def epilogue_tables(n_classes: int, overlap: int, hop: int):
@@ -143,7 +143,8 @@ def load_library() -> C.CDLL:
     if got != ABI_VERSION:   # the .so is a git-ignored build artefact: a stale one would read the structs at shifted offsets
         raise RuntimeError(f'{LIB_PATH} implements ABI {got}, this binding needs ABI {ABI_VERSION}: rebuild it '
                            '(`python -c "import __graft_entry__ as g; g.build()"`)')
-    # entry points have joined ABI 9 without a new number (the mel front end, the dataset kernels, the resampler): a build from before them reports 9 too
+    # entry points have joined ABI 9 without a new number (the mel front end, the dataset kernels, the resampler, the wav conditioning): a
+    # build from before them reports 9 too
     missing = [s for s in EXPORTED_SYMBOLS if not hasattr(lib, s)]
     if missing:
         raise RuntimeError(f'{LIB_PATH} implements ABI {got} without {", ".join(missing)}: it was built from older sources, rebuild it '
@@ -241,6 +242,11 @@ def load_library() -> C.CDLL:
     lib.wrnn_resample_last_error.restype = C.c_char_p
     lib.wrnn_resample_destroy.argtypes = [vp]
     lib.wrnn_resample_destroy.restype = None
+    lib.wrnn_condition_frames.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+    lib.wrnn_condition_frames.restype = C.c_int64
+    lib.wrnn_condition.argtypes = [vp, C.c_int64, vp, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_float, vp, C.c_int32, vp,
+                                   C.c_int64, vp, vp, vp, vp]
+    lib.wrnn_condition.restype = C.c_int
     lib.wrnn_quantise.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp]
     lib.wrnn_quantise.restype = C.c_int
     lib.wrnn_collate_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -489,6 +495,29 @@ def collate_windows(labels_ptr: int, mels_ptr: int, label_off_ptr: int, mel_off_
     if rc != 0:
         raise WrnnError(rc, f'wrnn_collate_windows(B={int(B)}, n_mels={int(n_mels)}, hop={int(hop)}, pad={int(pad)}, seq_len={int(seq_len)}, '
                             f'sig_bits={int(sig_bits)})')
+
+
+def condition_frames(n: int, frame_length: int, hop: int) -> int:
+    """Host-only ``wrnn_condition_frames``: the ``1 + n // hop`` energy frames of a clip of ``n`` samples; ``ValueError`` for a window the
+    library refuses (``frame_length`` outside 2 .. 8192, ``hop`` outside 1 .. ``frame_length``) or a clip too short to reflect-pad."""
+    fits = all(-2 ** 31 <= int(v) < 2 ** 31 for v in (frame_length, hop)) and -2 ** 63 <= int(n) < 2 ** 63
+    f = int(load_library().wrnn_condition_frames(int(n), int(frame_length), int(hop))) if fits else -1
+    if f < 0:
+        raise ValueError(f'no energy frames for a clip of {int(n)} samples with frame_length {int(frame_length)}, hop {int(hop)}: the window '
+                         f'must be 2 .. 8192 samples, the hop 1 .. frame_length, and the clip at least frame_length // 2 + 1 samples')
+    return f
+
+
+def condition(wav_ptr: int, n_max: int, n_ptr: int, B: int, trim: bool, top_db: float, frame_length: int, hop: int, peak_target: float,
+              energy_ws_ptr: int, F_max: int, out_ptr: int, n_out_max: int, n_out_ptr: int, bounds_ptr: int, peak_ptr: int, stream: int):
+    """``wrnn_condition``: silence trimming and peak normalisation of B ragged clips, three launches, nothing waits.  ``energy_ws_ptr``:
+    ``B * F_max + B`` float64.  ``WrnnError`` for a refused call (bad arguments are refused before any device call)."""
+    rc = load_library().wrnn_condition(wav_ptr or None, int(n_max), n_ptr or None, int(B), int(bool(trim)), float(top_db), int(frame_length),
+                                       int(hop), float(peak_target), energy_ws_ptr or None, int(F_max), out_ptr or None, int(n_out_max),
+                                       n_out_ptr or None, bounds_ptr or None, peak_ptr or None, stream or None)
+    if rc != 0:
+        raise WrnnError(rc, f'wrnn_condition(B={int(B)}, n_max={int(n_max)}, trim={bool(trim)}, top_db={float(top_db)}, frame_length={int(frame_length)}, '
+                            f'hop={int(hop)}, peak_target={float(peak_target)}, F_max={int(F_max)}, n_out_max={int(n_out_max)})')
 
 
 class NativeStream:

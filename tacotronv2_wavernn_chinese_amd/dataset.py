@@ -52,8 +52,9 @@ class DeviceCorpus:
 
     def __init__(self, labels: torch.Tensor, mels: torch.Tensor, label_off, label_len, mel_off, frames, n_mels: int, stems: Sequence[str],
                  *, hop_length: int, sample_rate: Optional[int] = None, bits: Optional[int] = None, mu_law: Optional[bool] = None,
-                 n_clipped: int = 0):
+                 n_clipped: int = 0, trim_top_db: Optional[float] = None, peak_norm: Optional[float] = None):
         self.labels, self.mels = labels, mels
+        self.trim_top_db, self.peak_norm = trim_top_db, peak_norm   # how from_wavs conditioned the clips (None: it did not)
         self.label_off, self.label_len = np.asarray(label_off, np.int64), np.asarray(label_len, np.int64)
         self.mel_off, self.frames = np.asarray(mel_off, np.int64), np.asarray(frames, np.int32)
         self.n_mels, self.stems, self.hop_length = int(n_mels), list(stems), int(hop_length)
@@ -104,7 +105,7 @@ class DeviceCorpus:
         ids = np.asarray(list(ids), np.int64)
         return DeviceCorpus(self.labels, self.mels, self.label_off[ids], self.label_len[ids], self.mel_off[ids], self.frames[ids], self.n_mels,
                             [self.stems[i] for i in ids], hop_length=self.hop_length, sample_rate=self.sample_rate, bits=self.bits,
-                            mu_law=self.mu_law, n_clipped=self.n_clipped)
+                            mu_law=self.mu_law, n_clipped=self.n_clipped, trim_top_db=self.trim_top_db, peak_norm=self.peak_norm)
 
     def split(self, test_samples: int) -> Tuple['DeviceCorpus', 'DeviceCorpus']:
         """(train, test) the way ``read_feature_list`` / ``get_vocoder_datasets`` (dataset.py:79-85) split: ids shuffled with seed
@@ -137,7 +138,8 @@ class DeviceCorpus:
                    hop_length=hop_length, **meta)
 
     @classmethod
-    def from_wavs(cls, paths_or_arrays, hp, device=None, batch_clips: int = 16, resample: bool = False) -> 'DeviceCorpus':
+    def from_wavs(cls, paths_or_arrays, hp, device=None, batch_clips: int = 16, resample: bool = False, trim_top_db=None,
+                  peak_norm=None) -> 'DeviceCorpus':
         """Wav files (``frontend.load_wav``) or float arrays in [-1, 1] -> corpus.  The clips go to the device in ragged groups of
         ``batch_clips`` (grouped by length, so that little of a group's buffer is padding); each group's buffer is read by one launch of
         the mel front end and one of ``wrnn_quantise``.  Bits and companding follow ``hp`` (``signal_bits``); utterances too short for
@@ -147,8 +149,19 @@ class DeviceCorpus:
         An array item may be an ``(array, rate)`` pair.  A file or a pair at another rate than ``hp.sample_rate`` raises ``ValueError``
         unless ``resample=True``: then the groups are formed per source rate, a group at another rate is uploaded at its own rate and one
         launch of ``frontend.Resampler`` writes the zero-padded buffer the two launches above read -- no host round trip is added.  Lengths,
-        frame counts and the short-utterance filter use the resampled length.  Resampled peaks may exceed 1 (``n_clipped`` counts them)."""
-        from .frontend import MelFrontEnd, Resampler, load_wav, read_wav
+        frame counts and the short-utterance filter use the resampled length.  Resampled peaks may exceed 1 (``n_clipped`` counts them)
+        unless ``peak_norm`` is on.
+
+        ``trim_top_db`` / ``peak_norm`` (both off by default; ``hp.peak_norm`` is not consulted, the reference reads it nowhere either):
+        every group is conditioned on the device by ``frontend.WavConditioner`` between the resampler and the two launches above --
+        leading and trailing silence trimmed like ``librosa.effects.trim(wav, top_db=trim_top_db, frame_length=2048, hop_length=512)``,
+        then ``wav / abs(wav).max() * 0.999`` (``peak_norm=True``; a number is the target), the reference's
+        ``tacotron/datasets/preprocessor.py:62-72``.  One host wait per group is added, for the trimmed lengths that size the corpus
+        tables; lengths, frame counts and the short-utterance filter use the trimmed length.  The corpus keeps the two settings as
+        ``trim_top_db`` and ``peak_norm`` (the target, or ``None``)."""
+        from .frontend import MelFrontEnd, Resampler, WavConditioner, condition_settings, load_wav, read_wav
+        trim_top_db, peak_target = condition_settings(trim_top_db, peak_norm)
+        cond = WavConditioner(trim_top_db, peak_target) if trim_top_db is not None or peak_target is not None else None
         dev = _device(device)
         fe = MelFrontEnd(hp, device=dev)
         hop, n_mels = fe.hop_length, fe.n_mels
@@ -180,6 +193,8 @@ class DeviceCorpus:
                 n = resamplers[rate].out_len(n)
             if 1 + n // hop < least or wav.shape[0] < 1:
                 continue
+            if trim_top_db is not None:
+                cond.frames(n)   # ValueError for a clip too short for the trim window, before any device work
             clips.append(wav)
             stems.append(stem)
             rates.append(rate)
@@ -198,6 +213,8 @@ class DeviceCorpus:
         for rate in [fe.sample_rate] + list(resamplers):
             ids = by_len[rates[by_len] == rate]
             groups += [(rate, ids[g:g + step]) for g in range(0, len(ids), step)]
+        if cond is not None:
+            return cls._from_wavs_conditioned(clips, stems, groups, src_lens, lens, resamplers, fe, cond, dev, bits, mu_law, least)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             labels = torch.empty(int(lens.sum()), dtype=torch.int32, device=dev)
@@ -221,6 +238,55 @@ class DeviceCorpus:
             n_clipped = int(clipped.item())
         return cls(labels, mels, label_off, lens, mel_off, frames, n_mels, stems, hop_length=hop, sample_rate=fe.sample_rate, bits=bits,
                    mu_law=mu_law, n_clipped=n_clipped)
+
+    @classmethod
+    def _from_wavs_conditioned(cls, clips, stems, groups, src_lens, lens, resamplers, fe, cond, dev, bits, mu_law, least) -> 'DeviceCorpus':
+        """``from_wavs`` behind its first pass when trimming or peak normalisation is on.  Per group: upload -> resample (a group at
+        another rate) -> condition -> mel and quantise, all reading device buffers; the trimmed lengths are read once per group, they decide
+        which clips stay and size the tables.  The utterances keep the order they were given in."""
+        hop, n_mels = fe.hop_length, fe.n_mels
+        kept = {}                                                 # utterance -> (labels, mel frames-major, samples, frames), its own tensors
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            clipped = torch.zeros(1, dtype=torch.int64, device=dev)
+            for rate, ids in groups:
+                host = np.zeros((len(ids), int(src_lens[ids].max())), np.float32)
+                for r, u in enumerate(ids):
+                    host[r, :src_lens[u]] = clips[u]
+                wav = torch.from_numpy(host).to(dev)
+                if rate != fe.sample_rate:
+                    wav = resamplers[rate].resample_padded(wav, src_lens[ids])
+                wav, n_out = cond.condition_padded(wav, lens[ids])                  # (B, max lens[ids]), zero past each trimmed clip
+                new = n_out.cpu().numpy().astype(np.int64)                          # the group's one host wait
+                rows = [r for r in range(len(ids)) if 1 + int(new[r]) // hop >= least]
+                if not rows:
+                    continue
+                if len(rows) < len(ids):
+                    wav = wav[torch.tensor(rows, device=dev)].contiguous()
+                ids, new = ids[rows], new[rows]
+                mel = fe.melspectrogram_padded(wav, new)
+                lab = torch.empty(tuple(wav.shape), dtype=torch.int32, device=dev)
+                _cabi.quantise(wav.data_ptr(), wav.numel(), bits, mu_law, lab.data_ptr(), clipped.data_ptr(), stream)
+                for r, u in enumerate(ids):
+                    n, t = int(new[r]), int(fe.last_frames[r])
+                    kept[int(u)] = (lab[r, :n].clone(), mel[r, :, :t].t().contiguous().view(-1), n, t)
+            if not kept:
+                raise ValueError(f'no utterance has the {least} mel frames one training window needs after trimming')
+            order = sorted(kept)
+            new_lens = np.array([kept[u][2] for u in order], np.int64)
+            frames = np.array([kept[u][3] for u in order], np.int64)
+            label_off = np.concatenate([[0], np.cumsum(new_lens)[:-1]]).astype(np.int64)
+            mel_off = np.concatenate([[0], np.cumsum(frames)[:-1]]).astype(np.int64) * n_mels
+            labels = torch.empty(int(new_lens.sum()), dtype=torch.int32, device=dev)
+            mels = torch.empty(int(frames.sum()) * n_mels, dtype=torch.float32, device=dev)
+            for k, u in enumerate(order):
+                lab, mel, n, t = kept.pop(u)
+                labels[int(label_off[k]):int(label_off[k]) + n] = lab
+                mels[int(mel_off[k]):int(mel_off[k]) + t * n_mels] = mel
+            n_clipped = int(clipped.item())
+        return cls(labels, mels, label_off, new_lens, mel_off, frames, n_mels, [stems[u] for u in order], hop_length=hop,
+                   sample_rate=fe.sample_rate, bits=bits, mu_law=mu_law, n_clipped=n_clipped, trim_top_db=cond.trim_top_db,
+                   peak_norm=cond.peak_target)
 
     # ------------------------------------------------------------------ files
     def save(self, out_dir: Union[str, Path]) -> Path:
@@ -317,14 +383,17 @@ def main(argv=None):
     parser.add_argument('--batch_clips', type=int, default=16, help='clips per launch of the front end')
     parser.add_argument('--resample', action='store_true', help='resample files at another rate to hp.sample_rate on the device '
                                                                 '(default: such a file is an error)')
+    from .frontend import add_condition_arguments, condition_arguments
+    add_condition_arguments(parser, 'the files')
     args = parser.parse_args(argv)
+    conditioning = condition_arguments(args)
     hp.configure(args.hp_file)
     if not torch.cuda.is_available():
         raise RuntimeError('the preprocessing runs on an MI355X only (no CPU path)')
     wavs = sorted(Path(args.wav_dir).expanduser().glob('*.wav'))
     if not wavs:
         raise FileNotFoundError(f'no *.wav files in {args.wav_dir}')
-    corpus = DeviceCorpus.from_wavs(wavs, hp, 'cuda', batch_clips=args.batch_clips, resample=args.resample)
+    corpus = DeviceCorpus.from_wavs(wavs, hp, 'cuda', batch_clips=args.batch_clips, resample=args.resample, **conditioning)
     listing = corpus.save(args.out_dir)
     print(f'{len(corpus)} utterances of {len(wavs)} files | {corpus.hours:.3f} hours | {corpus.n_clipped} clipped samples | '
           f'{corpus.bits} bits {"mu-law" if corpus.mu_law else "linear"} | {listing}')

@@ -3,7 +3,8 @@
 ``MelFrontEnd.melspectrogram`` is ``melspectrogram`` of ``wavernn/utils/dsp.py:72-81`` (``normalize(amp_to_db(mel_basis @ |stft(y)|))``,
 librosa semantics of the reference's era) as one launch of the kernel in ``csrc/melspec.hip``; ``load_wav`` is ``dsp.py:18-19``, and with
 ``resample=True`` a file at another rate goes through ``Resampler`` (``csrc/resample.hip``), a Kaiser-windowed sinc on the device.
-Pre-emphasis, ``spectrogram``, Griffin-Lim and the Tacotron-side recipe of ``tacotron/datasets/audio.py`` are not here.
+``WavConditioner`` (``csrc/condition.hip``) is the silence trimming and peak rescaling of ``tacotron/datasets/preprocessor.py:62-72``,
+opt-in everywhere.  Pre-emphasis, ``spectrogram``, Griffin-Lim and the Tacotron-side mel of ``tacotron/datasets/audio.py`` are not here.
 """
 from __future__ import annotations
 
@@ -73,20 +74,7 @@ class MelFrontEnd:
             raise ValueError(f'the front end runs on the GPU only, got device {dev}')
         index = dev.index if dev.index is not None else torch.cuda.current_device()
         dev = torch.device('cuda', index)
-        n_max, B = max(lens), len(clips)
-        with torch.cuda.device(dev):
-            if B == 1:
-                wav = torch.as_tensor(clips[0]).to(device=dev, dtype=torch.float32).contiguous().view(1, -1)
-            elif all(isinstance(c, torch.Tensor) and c.is_cuda for c in clips):
-                wav = torch.zeros((B, n_max), dtype=torch.float32, device=dev)
-                for i, c in enumerate(clips):
-                    wav[i, :lens[i]] = c
-            else:
-                host = np.zeros((B, n_max), np.float32)
-                for i, c in enumerate(clips):
-                    host[i, :lens[i]] = c.detach().cpu().numpy() if isinstance(c, torch.Tensor) else np.asarray(c)
-                wav = torch.from_numpy(host).to(dev)
-        return self.melspectrogram_padded(wav, lens)
+        return self.melspectrogram_padded(_padded_rows(clips, lens, dev), lens)
 
     def melspectrogram_padded(self, wav: torch.Tensor, lens) -> torch.Tensor:
         """The launch behind :meth:`melspectrogram` for clips that already lie on the device: ``wav`` a contiguous float32 ``(B, n_max)`` tensor
@@ -106,6 +94,24 @@ class MelFrontEnd:
                                                    torch.cuda.current_stream(dev).cuda_stream)
         self.last_frames = frames
         return out
+
+
+def _padded_rows(clips, lens, dev) -> torch.Tensor:
+    """Clips of different lengths, on the host or the device -> one zero-padded float32 ``(B, max(lens))`` tensor on ``dev``: a single clip
+    as it is, device clips copied on the device, host clips through one padded host buffer and one upload."""
+    n_max, B = max(lens), len(clips)
+    with torch.cuda.device(dev):
+        if B == 1:
+            return torch.as_tensor(clips[0]).to(device=dev, dtype=torch.float32).contiguous().view(1, -1)
+        if all(isinstance(c, torch.Tensor) and c.is_cuda for c in clips):
+            wav = torch.zeros((B, n_max), dtype=torch.float32, device=dev)
+            for i, c in enumerate(clips):
+                wav[i, :lens[i]] = c
+            return wav
+        host = np.zeros((B, n_max), np.float32)
+        for i, c in enumerate(clips):
+            host[i, :lens[i]] = c.detach().cpu().numpy() if isinstance(c, torch.Tensor) else np.asarray(c)
+        return torch.from_numpy(host).to(dev)
 
 
 def _clip_list(wavs):
@@ -133,7 +139,8 @@ class Resampler:
     ratio ``p / q``; a clip of ``n`` samples gives ``ceil(n p / q)`` (librosa 0.7.2 computes ``int(n ratio)`` samples and pads to the
     ceiling: at most the last sample differs).  Bit parity with librosa / resampy is not claimed.  Equal rates launch nothing and return
     the input object as it is (the filter is a low-pass).  ``ValueError`` for rates the library refuses (a rate <= 0, ``dst / src < 1/32``,
-    a bank of more than 2**24 entries).  Resampled peaks may exceed the input's: a full-scale clip can leave [-1, 1]."""
+    a bank of more than 2**24 entries).  Resampled peaks may exceed the input's: a full-scale clip can leave [-1, 1]; ``peak_norm``
+    (``WavConditioner``, applied after the resampler) brings it back."""
 
     def __init__(self, src_rate, dst_rate, device=None):
         self.src_rate, self.dst_rate = int(src_rate), int(dst_rate)
@@ -170,20 +177,7 @@ class Resampler:
         if dev.type != 'cuda':
             raise ValueError(f'the resampler runs on the GPU only, got device {dev}')
         dev = torch.device('cuda', dev.index if dev.index is not None else torch.cuda.current_device())
-        n_max, B = max(lens), len(clips)
-        with torch.cuda.device(dev):
-            if B == 1:
-                wav = torch.as_tensor(clips[0]).to(device=dev, dtype=torch.float32).contiguous().view(1, -1)
-            elif all(isinstance(c, torch.Tensor) and c.is_cuda for c in clips):
-                wav = torch.zeros((B, n_max), dtype=torch.float32, device=dev)
-                for i, c in enumerate(clips):
-                    wav[i, :lens[i]] = c
-            else:
-                host = np.zeros((B, n_max), np.float32)
-                for i, c in enumerate(clips):
-                    host[i, :lens[i]] = c.detach().cpu().numpy() if isinstance(c, torch.Tensor) else np.asarray(c)
-                wav = torch.from_numpy(host).to(dev)
-        return self.resample_padded(wav, lens)
+        return self.resample_padded(_padded_rows(clips, lens, dev), lens)
 
     __call__ = resample
 
@@ -211,6 +205,152 @@ class Resampler:
         return out
 
 
+RESCALING_MAX = 0.999   # tacotron_hparams.py:69 rescaling_max, what peak_norm=True scales the peak to
+TRIM_TOP_DB, TRIM_FRAME_LENGTH, TRIM_HOP_LENGTH = 25.0, 2048, 512   # tacotron_hparams.py:91-93
+
+
+def condition_settings(trim_top_db=None, peak_norm=None):
+    """The two conditioning switches as the library takes them: ``(trim_top_db or None, peak target or None)``.  ``trim_top_db``: ``None``
+    (off) or a finite number of dB above 0.  ``peak_norm``: ``None`` / ``False`` (off), ``True`` (0.999, the reference's
+    ``rescaling_max``) or a finite target above 0.  ``ValueError`` for anything else."""
+    if trim_top_db is not None:
+        if isinstance(trim_top_db, bool) or not isinstance(trim_top_db, (int, float, np.integer, np.floating)):
+            raise ValueError(f'trim_top_db must be None or a number of dB, got {trim_top_db!r}')
+        trim_top_db = float(trim_top_db)
+        if not (np.isfinite(trim_top_db) and trim_top_db > 0):
+            raise ValueError(f'trim_top_db must be finite and above 0, got {trim_top_db!r}')
+    if peak_norm is None or peak_norm is False:
+        target = None
+    elif peak_norm is True:
+        target = RESCALING_MAX
+    elif isinstance(peak_norm, (int, float, np.integer, np.floating)):
+        target = float(peak_norm)
+        if not (np.isfinite(target) and 0 < target <= float(np.finfo(np.float32).max)):
+            raise ValueError(f'peak_norm must be True or a finite float32 target above 0, got {peak_norm!r}')
+    else:
+        raise ValueError(f'peak_norm must be None, a bool or a target, got {peak_norm!r}')
+    return trim_top_db, target
+
+
+def add_condition_arguments(parser, what='the wavs'):
+    """``--trim_silence``, ``--trim_top_db DB`` and ``--peak_norm [TARGET]`` for a command-line parser (``condition_arguments`` reads them)."""
+    parser.add_argument('--trim_silence', action='store_true',
+                        help=f'extension: trim leading and trailing silence of {what} on the device, like librosa.effects.trim with a '
+                             f'{TRIM_FRAME_LENGTH} / {TRIM_HOP_LENGTH} window (default: off)')
+    parser.add_argument('--trim_top_db', type=float, default=TRIM_TOP_DB, metavar='DB',
+                        help='with --trim_silence: frames more than DB below the loudest frame are silence (default: %(default)s)')
+    parser.add_argument('--peak_norm', type=float, nargs='?', const=RESCALING_MAX, default=None, metavar='TARGET',
+                        help=f'extension: rescale {what} to a peak of TARGET on the device, after trimming (TARGET left out: '
+                             f'{RESCALING_MAX}; default: off)')
+
+
+def condition_arguments(args) -> dict:
+    """The ``trim_top_db=`` / ``peak_norm=`` keywords for the flags of ``add_condition_arguments`` (checked: ``ValueError``)."""
+    trim_top_db, target = condition_settings(args.trim_top_db if args.trim_silence else None, args.peak_norm)
+    return dict(trim_top_db=trim_top_db, peak_norm=target)
+
+
+class WavConditioner:
+    """``WavConditioner(trim_top_db=25, peak_norm=True)``: the two steps the reference applies to every training wav between loading it
+    and the mel (``tacotron/datasets/preprocessor.py:62-72``), on the device (``csrc/condition.hip``), for a whole ragged list at once.
+
+    ``trim_top_db``: trim leading and trailing silence like ``librosa.effects.trim(wav, top_db, frame_length, hop_length)[0]``: frames
+    of the reflect-padded clip whose mean square lies more than ``top_db`` dB below the loudest frame's are silent, and the clip is cut
+    to ``[first_non_silent * hop, min(n, (last_non_silent + 1) * hop))``.  Energies and the decision are float64 (librosa's are
+    float32); digital silence is kept whole.  ``peak_norm``: then ``wav / abs(wav).max() * target`` in float32 (``True``: 0.999); an
+    all-zero clip is left as it is.  At least one of the two must be on; both are off by default everywhere else in the package, and
+    nothing reads ``hp.peak_norm`` (``wavernn_hparams.py:29`` declares it, the reference reads it nowhere).  A clip needs
+    ``frame_length // 2 + 1`` samples to be trimmed."""
+
+    def __init__(self, trim_top_db=None, peak_norm=None, frame_length=TRIM_FRAME_LENGTH, hop_length=TRIM_HOP_LENGTH, device=None):
+        self.trim_top_db, self.peak_target = condition_settings(trim_top_db, peak_norm)
+        if self.trim_top_db is None and self.peak_target is None:
+            raise ValueError('a WavConditioner with neither trim_top_db nor peak_norm has nothing to do')
+        self.frame_length, self.hop_length = int(frame_length), int(hop_length)
+        _cabi.condition_frames(2 ** 20, self.frame_length, self.hop_length)   # the window is checked here, without a device
+        self._device = device
+        self.last_lens = self.last_bounds = self.last_peaks = None
+
+    def frames(self, n: int) -> int:
+        """``1 + n // hop_length`` energy frames; ``ValueError`` for a clip shorter than ``frame_length // 2 + 1`` samples."""
+        return _cabi.condition_frames(int(n), self.frame_length, self.hop_length)
+
+    def condition(self, wavs, device=None) -> torch.Tensor:
+        """One 1-D array / tensor, or a list of them of different lengths, on the host or the device -> ``(B, n_max)`` float32 tensor on
+        the device, conditioned clip b in ``[b, :last_lens[b]]`` and zeros from there on.  A row equals the call on that clip alone bit
+        for bit.  Sets ``last_lens``, ``last_bounds`` (``(B, 2)`` start and end in the input clip) and ``last_peaks`` (``max |x|`` over
+        the kept span, before scaling); reading them is the one host wait of the call."""
+        clips, lens = _clip_list(wavs)
+        if min(lens) < 1:
+            raise ValueError('expected clips of at least one sample')
+        dev = torch.device(device if device is not None else self._device if self._device is not None else 'cuda')
+        if dev.type != 'cuda':
+            raise ValueError(f'the conditioning runs on the GPU only, got device {dev}')
+        if self.trim_top_db is not None:
+            for n in lens:
+                self.frames(n)   # refuses a short clip before anything is launched
+        dev = torch.device('cuda', dev.index if dev.index is not None else torch.cuda.current_device())
+        wav = _padded_rows(clips, lens, dev)
+        with torch.cuda.device(dev):
+            bounds = torch.empty((len(clips), 2), dtype=torch.int32, device=dev)
+            peaks = torch.empty(len(clips), dtype=torch.float32, device=dev)
+        out, n_out = self.condition_padded(wav, lens, bounds=bounds, peaks=peaks)
+        self.last_lens = [int(n) for n in n_out.cpu().numpy()]
+        self.last_bounds, self.last_peaks = bounds.cpu().numpy(), peaks.cpu().numpy()
+        return out
+
+    __call__ = condition
+
+    def condition_padded(self, wav: torch.Tensor, lens, bounds=None, peaks=None, energies=None):
+        """The launches behind :meth:`condition` for clips that already lie on the device: ``wav`` a contiguous float32 ``(B, n_max)``
+        tensor with clip b in ``wav[b, :lens[b]]`` (what lies past a clip is never read); ``lens`` a list, or an int32 ``(B,)`` device
+        tensor such as the one this method returns.  Returns ``(out, n_out)``: ``out`` ``(B, n_max)`` float32, zero past each clip's own
+        new length, the buffer ``MelFrontEnd.melspectrogram_padded`` and ``wrnn_quantise`` read, and ``n_out`` the int32 ``(B,)`` device
+        tensor of the new lengths.  Nothing waits for the device.  ``bounds`` (int32 ``(B, 2)``), ``peaks`` (float32 ``(B,)``) and
+        ``energies`` (float64 ``(B, frames(n_max))``, the frame energies; trimming only) are optional device tensors to fill.  Lengths
+        given as a list are checked here; device lengths are the caller's to keep at ``frame_length // 2 + 1`` or more."""
+        if not (isinstance(wav, torch.Tensor) and wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 2 and wav.is_contiguous()):
+            raise ValueError('expected a contiguous float32 (B, n_max) tensor on the GPU')
+        B, n_max = wav.shape
+        dev = wav.device
+        trim = self.trim_top_db is not None
+        if isinstance(lens, torch.Tensor) and lens.is_cuda:
+            if not (lens.dtype == torch.int32 and lens.dim() == 1 and lens.shape[0] == B and lens.is_contiguous() and lens.device == dev):
+                raise ValueError(f'expected {B} int32 lengths on {dev}')
+            n_dev = lens
+        else:
+            lens = [int(n) for n in lens]
+            if len(lens) != B or not lens or max(lens) > n_max or min(lens) < 1:
+                raise ValueError(f'{len(lens)} lengths ({min(lens, default=0)} .. {max(lens, default=0)}) for a buffer of shape {tuple(wav.shape)}')
+            if trim:
+                for n in lens:
+                    self.frames(n)
+            n_dev = None
+        if B < 1 or n_max < 1:
+            raise ValueError(f'an empty buffer of shape {tuple(wav.shape)}')
+        F_max = 1 + n_max // self.hop_length
+        if energies is not None and not trim:
+            raise ValueError('frame energies are computed for trimming only')
+        for name, t, dtype, shape in (('bounds', bounds, torch.int32, (B, 2)), ('peaks', peaks, torch.float32, (B,)),
+                                      ('energies', energies, torch.float64, (B, F_max))):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape
+                                      and t.is_contiguous()):
+                raise ValueError(f'{name}: expected a contiguous {dtype} tensor of shape {shape} on {dev}')
+        with torch.cuda.device(dev):
+            if n_dev is None:
+                n_dev = torch.tensor(lens, dtype=torch.int32).to(dev)
+            ws = torch.empty(B * F_max + B, dtype=torch.float64, device=dev)
+            out = torch.empty((B, n_max), dtype=torch.float32, device=dev)
+            n_out = torch.empty(B, dtype=torch.int32, device=dev)
+            _cabi.condition(wav.data_ptr(), n_max, n_dev.data_ptr(), B, trim, self.trim_top_db if trim else TRIM_TOP_DB, self.frame_length,
+                            self.hop_length, self.peak_target or 0.0, ws.data_ptr(), F_max, out.data_ptr(), n_max, n_out.data_ptr(),
+                            bounds.data_ptr() if bounds is not None else 0, peaks.data_ptr() if peaks is not None else 0,
+                            torch.cuda.current_stream(dev).cuda_stream)
+            if energies is not None:
+                energies.copy_(ws[:B * F_max].view(B, F_max))
+        return out, n_out
+
+
 def _decode(path, data) -> np.ndarray:
     if data.dtype == np.int16:
         y = data.astype(np.float32) / np.float32(32768.0)
@@ -235,20 +375,29 @@ def read_wav(path):
     return _decode(path, data), int(sr)
 
 
-def load_wav(path, sample_rate, resample=False, device=None):
+def load_wav(path, sample_rate, resample=False, device=None, trim_top_db=None, peak_norm=None):
     """``librosa.load(path, sr=sample_rate)[0]`` (``dsp.py:18-19``): float32 mono (``read_wav``).  A file at another rate raises
     ``ValueError`` unless ``resample=True``: then it is resampled on the device (``Resampler``) and comes back as a host array of
-    ``ceil(n sample_rate / rate)`` samples."""
+    ``ceil(n sample_rate / rate)`` samples.  ``trim_top_db`` / ``peak_norm`` (both off by default): the clip is then conditioned on the
+    device after the resampler (``WavConditioner``) and the trimmed, rescaled clip comes back."""
     from scipy.io import wavfile
+    trim_top_db, target = condition_settings(trim_top_db, peak_norm)
     sr, data = wavfile.read(str(path))
     if int(sr) != int(sample_rate) and not resample:
         raise ValueError(f'{path} is sampled at {int(sr)} Hz, the model needs {int(sample_rate)} Hz: resample the file first, or pass '
                          f'resample=True (--resample) for the resampler on the device')
     y = _decode(path, data)
-    if int(sr) == int(sample_rate):
+    conditioned = trim_top_db is not None or target is not None
+    if int(sr) == int(sample_rate) and not conditioned:
         return y
     if y.shape[0] < 1:
         raise ValueError(f'{path} holds no samples')
-    rs = Resampler(int(sr), sample_rate, device=device)
-    out = rs.resample(y)
-    return np.ascontiguousarray(out[0, :rs.last_lens[0]].cpu().numpy())
+    if int(sr) != int(sample_rate):
+        rs = Resampler(int(sr), sample_rate, device=device)
+        y = rs.resample(y, device=device)
+        y = y[0, :rs.last_lens[0]]
+    if conditioned:
+        cond = WavConditioner(trim_top_db, target, device=device)
+        y = cond.condition(y, device=device)
+        y = y[0, :cond.last_lens[0]]
+    return np.ascontiguousarray(y.cpu().numpy())

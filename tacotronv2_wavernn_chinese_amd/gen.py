@@ -15,6 +15,9 @@ reference names an undefined ``file_name`` there; ``idx`` is the stem it compute
 ``frontend.MelFrontEnd`` (``csrc/melspec.hip``) instead of librosa -- takes the same path as a ``.npy`` mel, ``--stream-frames`` included.  A file
 at another sample rate raises ``ValueError`` unless ``resample=True`` / ``--resample``: then it is resampled on the device
 (``frontend.Resampler``, ``csrc/resample.hip``) and the saved target file is the resampled clip at the model's rate, as the reference's is.
+``trim_top_db=`` / ``peak_norm=`` (``--trim_silence [--trim_top_db DB]``, ``--peak_norm [TARGET]``; off by default): the clip is conditioned
+on the device like the training wavs of a corpus made with the same settings (``frontend.WavConditioner``, ``csrc/condition.hip``), and the
+saved target file is the conditioned clip.
 """
 from __future__ import annotations
 
@@ -26,12 +29,13 @@ import numpy as np
 import torch
 
 from .dsp import save_wav
-from .frontend import load_wav
+from .frontend import add_condition_arguments, condition_arguments, load_wav
 from .hparams import hparams as hp
 from .vocoder import WaveRNN
 
 
-def gen_from_file(model: WaveRNN, load_path, save_path, batched, target, overlap, stream_frames=None, resample=False, **generate_opts):
+def gen_from_file(model: WaveRNN, load_path, save_path, batched, target, overlap, stream_frames=None, resample=False, trim_top_db=None,
+                  peak_norm=None, **generate_opts):
     k = model.get_step() // 1000
     load_path = str(load_path)
     if ".npy" in load_path:
@@ -45,7 +49,9 @@ def gen_from_file(model: WaveRNN, load_path, save_path, batched, target, overlap
     elif ".wav" in load_path:
         if not os.path.isfile(load_path):   # an input check like the ones above, not an OSError from inside the wav reader
             raise ValueError(f'{load_path}: no such wav file')
-        wav = load_wav(load_path, hp.sample_rate, resample=resample, device=torch.device('cuda', model._device_index()) if resample else None)
+        on_device = resample or trim_top_db is not None or (peak_norm is not None and peak_norm is not False)
+        wav = load_wav(load_path, hp.sample_rate, resample=resample, device=torch.device('cuda', model._device_index()) if on_device else None,
+                       trim_top_db=trim_top_db, peak_norm=peak_norm)
         idx = load_path.split('/')[-1].strip().split('.')[0]
         save_wav(wav, os.path.join(str(save_path), f'__{idx}__{k}k_steps_target.wav'), hp.sample_rate)
         mel = model.mel_front_end().melspectrogram(wav, device=torch.device('cuda', model._device_index()))   # (1, n_mels, T) on the device
@@ -119,6 +125,7 @@ def main(argv=None):
     parser.add_argument('--file', '-f', type=str, help='[string/path] (T, n_mels) .npy mel, or a .wav at the model sample rate (any rate with --resample), to vocode')
     parser.add_argument('--resample', action='store_true',
                         help='extension: resample a --file .wav at another rate to the model sample rate on the device (default: an error)')
+    add_condition_arguments(parser, 'a --file .wav')
     parser.add_argument('--voc_weights', '-w', type=str, help='[string/path] Load in different WaveRNN weights')
     parser.add_argument('--gta', '-g', dest='gta', action='store_true', help='Generate from GTA testset')
     parser.add_argument('--force_cpu', '-c', action='store_true',
@@ -135,6 +142,7 @@ def main(argv=None):
     parser.set_defaults(batched=None)
     args = parser.parse_args(argv)
 
+    conditioning = condition_arguments(args)
     hp.configure(args.hp_file)
     if args.target is None:
         args.target = hp.voc_target
@@ -170,7 +178,7 @@ def main(argv=None):
         if args.stream_frames is not None and args.noise != 'philox':
             raise ValueError('--stream-frames draws its noise on the device: --noise reference needs the whole clip')
         gen_from_file(model, args.file, out_dir, args.batched, args.target, args.overlap, stream_frames=args.stream_frames,
-                      noise_mode=args.noise, resample=args.resample)
+                      noise_mode=args.noise, resample=args.resample, **conditioning)
     print('\n\nExiting...\n')
 
 

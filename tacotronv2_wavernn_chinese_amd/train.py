@@ -269,12 +269,15 @@ def main(argv=None):
                                                          'there (dataset.DeviceCorpus), every batch is cut by one kernel launch')
     parser.add_argument('--resample', action='store_true', help='with --wav_dir: resample files at another rate to hp.sample_rate on the '
                                                                 'device (default: such a file is an error)')
+    from .frontend import add_condition_arguments, condition_arguments
+    add_condition_arguments(parser, 'the --wav_dir files')
     parser.add_argument('--resident', action='store_true', help='load the corpus of hp.feature_path onto the device once instead of reading '
                                                                 '.npy files every iteration')
     parser.add_argument('--total_steps', type=int, help='override hp.voc_total_steps')
     parser.add_argument('--reference_body', action='store_true',
                         help="run the reference's loop body (model(x, m) + torch loss) instead of the fused training_loss")
     args = parser.parse_args(argv)
+    conditioning = condition_arguments(args)
     hp.configure(args.hp_file)
     if not torch.cuda.is_available():
         raise RuntimeError('this vocoder trains on an MI355X only (no CPU path)')
@@ -293,7 +296,7 @@ def main(argv=None):
         wavs = sorted(Path(args.wav_dir).expanduser().glob('*.wav'))
         if not wavs:
             raise FileNotFoundError(f'no *.wav files in {args.wav_dir}')
-        corpus = DeviceCorpus.from_wavs(wavs, hp, 'cuda', resample=args.resample)
+        corpus = DeviceCorpus.from_wavs(wavs, hp, 'cuda', resample=args.resample, **conditioning)
         print(f'{len(corpus)} utterances of {len(wavs)} files | {corpus.hours:.3f} hours | {corpus.n_clipped} clipped samples')
         train, held_out = corpus.split(hp.voc_test_samples)
         test = held_out.pairs()

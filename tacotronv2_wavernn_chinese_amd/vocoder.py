@@ -715,16 +715,22 @@ class WaveRNN(nn.Module):
         return cache[int(wav_rate)]
 
     def generate_from_wav(self, wav, save_path: Union[str, Path], batched, target, overlap, mu_law, front_end=None, wav_rate=None,
-                          **generate_opts):
+                          trim_top_db=None, peak_norm=None, **generate_opts):
         """Copy-synthesis, the ``.wav`` branch of ``wavernn_gen.py:17-20``: the mel of ``wav`` (1-D samples in [-1, 1] at the model's sample
         rate) is built on the device (``mel_front_end``) and handed to ``generate`` as a device tensor, without a host round trip.  Returns
         what ``generate`` returns for that mel: ``(T - 1) * hop`` samples, ``T = 1 + len(wav) // hop``.  ``wav_rate``: the clip's own sample
         rate; one that differs from the model's is resampled on the device first (``frontend.Resampler``), and ``len(wav)`` above is then
-        the resampled length ``ceil(len * sample_rate / wav_rate)``."""
+        the resampled length ``ceil(len * sample_rate / wav_rate)``.  ``trim_top_db`` / ``peak_norm`` (off by default): the clip is
+        conditioned on the device after the resampler, as ``DeviceCorpus.from_wavs`` conditions training wavs with the same settings
+        (``frontend.WavConditioner``: silence trimmed, then rescaled to the peak), and ``len(wav)`` is the trimmed length."""
+        from .frontend import condition_settings
+        trim_top_db, peak_norm = condition_settings(trim_top_db, peak_norm)
         fe = self.mel_front_end(front_end)
         dev = torch.device('cuda', self._device_index())
         if wav_rate is not None and int(wav_rate) != self.sample_rate:
             wav = self.resampler(wav_rate).resample(wav, device=dev)   # (1, n) on the device
+        if trim_top_db is not None or peak_norm is not None:
+            wav = self._condition_clips(wav, trim_top_db, peak_norm, dev)[0]
         mel = fe.melspectrogram(wav, device=dev)
         return self.generate(mel, save_path, batched, target, overlap, mu_law, **generate_opts)
 
@@ -746,8 +752,16 @@ class WaveRNN(nn.Module):
                 out[i] = row[:n]
         return out
 
+    def _condition_clips(self, wavs, trim_top_db, peak_norm, dev):
+        """``wavs`` (a list of clips, or the ``(B, n)`` rows of the resampler) conditioned on the device by one ``frontend.WavConditioner``
+        call: a list of 1-D device tensors, clip i cut to its trimmed length."""
+        from .frontend import WavConditioner
+        cond = WavConditioner(trim_top_db, peak_norm)
+        rows = cond.condition(wavs, device=dev)
+        return [row[:n] for row, n in zip(rows, cond.last_lens)]
+
     def generate_many(self, mels_list=None, save_paths=None, mu_law=True, epilogue='host', batched=False, target='auto', overlap=550, seeds=None,
-                      wavs=None, front_end=None, wav_rates=None, **native_opts):
+                      wavs=None, front_end=None, wav_rates=None, trim_top_db=None, peak_norm=None, **native_opts):
         """Extension for serving loops: several independent utterances of different lengths in ONE device call, so that all
         8 XCD teams of the GPU work (a single unbatched utterance keeps one team = 1/8 of the chip busy; up to 8 utterances
         run on the latency kernel one per team, more on the batch kernel).  ``mels_list``: sequence of (n_mels, T_i) arrays.
@@ -779,9 +793,15 @@ class WaveRNN(nn.Module):
         ``wavs=`` in place of ``mels_list``: a list of 1-D sample arrays; their mels are built by ONE ragged launch of the device front end
         (``mel_front_end``; clip i has ``1 + len(wavs[i]) // hop`` frames) and stay on the device.  Everything else is as for the same
         mels given as ``mels_list``.  ``wav_rates``: the clips' own sample rates, one int for all or one per clip; clips at another rate
-        than the model's are resampled on the device first (``frontend.Resampler``, one launch per source rate)."""
+        than the model's are resampled on the device first (``frontend.Resampler``, one launch per source rate).  ``trim_top_db`` /
+        ``peak_norm`` (with ``wavs=`` only; off by default): all clips are then conditioned by one ``frontend.WavConditioner`` call, and
+        the frame counts follow the trimmed lengths."""
+        from .frontend import condition_settings
+        trim_top_db, peak_norm = condition_settings(trim_top_db, peak_norm)
         if (mels_list is None) == (wavs is None):
             raise ValueError('give either mels_list or wavs')
+        if wavs is None and (trim_top_db is not None or peak_norm is not None):
+            raise ValueError('trim_top_db and peak_norm condition wavs: give wavs=, not mels_list')
         n_req = len(mels_list) if wavs is None else len(wavs)
         if seeds is not None:
             native_opts['seeds'] = request_seeds(seeds, n_req, native_opts.get('noise_mode', _cabi.NOISE_PHILOX), native_opts.get('seed'))
@@ -797,6 +817,8 @@ class WaveRNN(nn.Module):
                 raise ValueError('expected a non-empty sequence of clips')
             if wav_rates is not None:
                 wavs = self._resample_clips(wavs, wav_rates, torch.device('cuda', self._device_index()))
+            if trim_top_db is not None or peak_norm is not None:
+                wavs = self._condition_clips(list(wavs), trim_top_db, peak_norm, torch.device('cuda', self._device_index()))
             lens = [fe.frames(int(np.shape(w)[0])) for w in wavs]
             arrs = lens   # one entry per clip; the mels themselves are made on the device below
         else:
