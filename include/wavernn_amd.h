@@ -62,6 +62,8 @@ extern "C" {
 #define WRNN_KERNEL_BATCH 4  /* one team per 4 or 8 rows in lock-step on the matrix cores (v_mfma_f32_4x4x1) */
 #define WRNN_KERNEL_BATCH_CS 5 /* ABI 5: the same batch step with two waves per SIMD -- critical / shadow wave roles, the shadow
                                 * matrix products, noise and conditioning run beside the serial chain instead of inside it */
+#define WRNN_KERNEL_TEAMG 6  /* added to ABI 9: one XCD team per row for ANY model dims -- layer shapes are run-time arguments, a workgroup
+                              * keeps what fits of its weight slice in LDS and streams the rest; opt-in, AUTO never picks it */
 
 /* tensor dtypes accepted by wrnn_load_weights */
 #define WRNN_DTYPE_F32 0
@@ -310,6 +312,50 @@ int32_t wrnn_team_info(const wrnn_handle *h, int32_t *n_teams_out, const char **
 /* Test hook: on != 0 makes this handle behave as if the residency check of wrnn_create had failed (AUTO -> SIMPLE, an explicit team kernel
  * -> WRNN_ERR_INVALID), so that the slow-path warning can be exercised on a healthy device. */
 int wrnn_debug_force_no_teams(wrnn_handle *h, int32_t on);
+
+/* ---- the team kernel for any dims (added to ABI 9: new entry points only, no existing entry or struct changes, so the number stays) ----
+ * WRNN_KERNEL_TEAMG splits every loop layer by output rows over the 32 workgroups of an XCD team.  Layer order below = the order in
+ * which layers are given LDS residency (shortest rows first): */
+#define WRNN_TEAMG_FC3 0   /* fc3:  n_classes rows of fc_dims */
+#define WRNN_TEAMG_FC2 1   /* fc2:  fc_dims rows of fc_dims + aux_dims */
+#define WRNN_TEAMG_FC1 2   /* fc1:  fc_dims rows of rnn_dims + aux_dims */
+#define WRNN_TEAMG_RNN2 3  /* rnn2: 3 rnn_dims gate rows of [W_ih2 (rnn_dims + aux_dims) | W_hh2 (rnn_dims)] */
+#define WRNN_TEAMG_RNN1 4  /* rnn1: 3 rnn_dims gate rows of [W_ih1 (rnn_dims) | W_hh1 (rnn_dims)] */
+#define WRNN_TEAMG_COND 5  /* I:    rnn_dims rows of feat_dims + aux_dims (the conditioning's share; the sample's column is a vector) */
+#define WRNN_TEAMG_LAYERS 6
+typedef struct wrnn_teamg_layer_info {
+    int32_t units;           /* units owned as a whole: hidden units (rnn1, rnn2: the three gate rows of a unit stay together) or rows */
+    int32_t rows_per_unit;   /* 3 (rnn1, rnn2) or 1 */
+    int32_t k;               /* floats per row */
+    int32_t k_padded;        /* as laid out for the kernel: every operand segment rounded up to 64 floats */
+    int32_t own_first[32];   /* workgroup g owns units [own_first[g], own_first[g] + own_count[g]) */
+    int32_t own_count[32];
+    int32_t rows_min, rows_max;      /* output rows owned by a workgroup, over the 32 */
+    int32_t resident_units;          /* the first resident_units of every workgroup's slice live in LDS, the rest is streamed */
+    int32_t reserved_;
+    int64_t weight_bytes;            /* units * rows_per_unit * k * 4 */
+    int64_t resident_bytes_wg;       /* weight bytes resident in the fullest workgroup */
+    int64_t resident_bytes_team;     /* ... summed over the 32 workgroups */
+    int64_t streamed_bytes_step;     /* weight bytes the team reads from L2 / Infinity Cache every step;
+                                      * resident_bytes_team + streamed_bytes_step == weight_bytes */
+    int64_t lds_bytes;               /* LDS the resident part takes in every workgroup (padded rows) */
+} wrnn_teamg_layer_info;
+typedef struct wrnn_teamg_plan_info {
+    wrnn_teamg_layer_info layer[WRNN_TEAMG_LAYERS];
+    int64_t lds_budget_bytes;        /* the budget the placement was made for */
+    int64_t activation_bytes;        /* LDS of the activation vectors */
+    int64_t lds_bytes;               /* activation_bytes + sum of layer[].lds_bytes: the kernel's dynamic LDS, <= 160 KiB */
+    int64_t streamed_bytes_step;     /* sum over the layers */
+    int64_t mail_granules;           /* 8-byte {tag, value} granules of one team's mailbox */
+} wrnn_teamg_plan_info;
+/* Host only, no device: ownership and placement for the model `cfg` describes (device, sample_rate are not read).  lds_budget_bytes:
+ * LDS a workgroup may spend on resident weights, < 0 = the default (160 KiB minus the activation vectors); a larger value is clamped to
+ * the default.  WRNN_ERR_INVALID: bad arguments or dims wrnn_create refuses; WRNN_ERR_UNSUPPORTED: the activation vectors alone exceed
+ * 160 KiB or the mailbox a team needs exceeds the library's (fc_dims far above 1024). */
+int wrnn_teamg_plan(const wrnn_config *cfg, int64_t lds_budget_bytes, wrnn_teamg_plan_info *out);
+/* Test hook in the style of wrnn_debug_force_no_teams: the following WRNN_KERNEL_TEAMG calls of this handle place their weights with
+ * this LDS budget (< 0: back to the default), so that small models exercise the streamed and the mixed placement. */
+int wrnn_debug_teamg_lds_budget(wrnn_handle *h, int64_t bytes);
 
 /* ---- streaming generation (ABI 7) -------------------------------------------------------------------------------------------
  * Mel frames arrive a few at a time (Tacotron's decoder); audio leaves as soon as the frames it depends on are in.  A stream

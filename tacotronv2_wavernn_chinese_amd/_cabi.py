@@ -18,8 +18,9 @@ LIB_PATH = os.path.join(_HERE, 'csrc', 'libwavernn_amd.so')
 
 MODE_RAW, MODE_MOL = 0, 1
 NOISE_PHILOX, NOISE_INJECTED, NOISE_ARGMAX = 0, 1, 2
-KERNEL_AUTO, KERNEL_SIMPLE, KERNEL_TEAM2, KERNEL_BATCH, KERNEL_BATCH_CS = 0, 1, 3, 4, 5
-KERNEL_NAMES = {KERNEL_AUTO: 'auto', KERNEL_SIMPLE: 'simple', KERNEL_TEAM2: 'team2', KERNEL_BATCH: 'batch', KERNEL_BATCH_CS: 'batch_cs'}
+KERNEL_AUTO, KERNEL_SIMPLE, KERNEL_TEAM2, KERNEL_BATCH, KERNEL_BATCH_CS, KERNEL_TEAMG = 0, 1, 3, 4, 5, 6
+KERNEL_NAMES = {KERNEL_AUTO: 'auto', KERNEL_SIMPLE: 'simple', KERNEL_TEAM2: 'team2', KERNEL_BATCH: 'batch', KERNEL_BATCH_CS: 'batch_cs',
+                KERNEL_TEAMG: 'teamg'}
 KERNEL_IDS = {v: k for k, v in KERNEL_NAMES.items()}
 DTYPE_F32, DTYPE_I64 = 0, 1
 ERR_NAMES = {0: 'WRNN_OK', -1: 'WRNN_ERR_INVALID', -2: 'WRNN_ERR_HIP', -3: 'WRNN_ERR_STATE',
@@ -39,7 +40,7 @@ EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wr
                     'wrnn_mel_create', 'wrnn_mel_frames', 'wrnn_melspectrogram', 'wrnn_mel_tables', 'wrnn_mel_last_error', 'wrnn_mel_destroy',
                     'wrnn_quantise', 'wrnn_collate_windows',
                     'wrnn_resample_create', 'wrnn_resample_out_len', 'wrnn_resample_bank', 'wrnn_resample', 'wrnn_resample_last_error',
-                    'wrnn_resample_destroy', 'wrnn_condition_frames', 'wrnn_condition')
+                    'wrnn_resample_destroy', 'wrnn_condition_frames', 'wrnn_condition', 'wrnn_teamg_plan', 'wrnn_debug_teamg_lds_budget')
 
 
 def epilogue_tables(n_classes: int, overlap: int, hop: int):
@@ -101,6 +102,47 @@ class Timing(C.Structure):
 class MelConfig(C.Structure):
     _fields_ = [('sample_rate', C.c_int32), ('n_fft', C.c_int32), ('hop_length', C.c_int32), ('win_length', C.c_int32),
                 ('n_mels', C.c_int32), ('fmin', C.c_float), ('min_level_db', C.c_float), ('device', C.c_int32)]
+
+
+TEAMG_LAYER_NAMES = ('fc3', 'fc2', 'fc1', 'rnn2', 'rnn1', 'cond')   # WRNN_TEAMG_*: the order in which layers are given LDS residency
+
+
+class TeamgLayerInfo(C.Structure):
+    _fields_ = [('units', C.c_int32), ('rows_per_unit', C.c_int32), ('k', C.c_int32), ('k_padded', C.c_int32),
+                ('own_first', C.c_int32 * 32), ('own_count', C.c_int32 * 32), ('rows_min', C.c_int32), ('rows_max', C.c_int32),
+                ('resident_units', C.c_int32), ('reserved_', C.c_int32), ('weight_bytes', C.c_int64), ('resident_bytes_wg', C.c_int64),
+                ('resident_bytes_team', C.c_int64), ('streamed_bytes_step', C.c_int64), ('lds_bytes', C.c_int64)]
+
+
+class TeamgPlanInfo(C.Structure):
+    _fields_ = [('layer', TeamgLayerInfo * 6), ('lds_budget_bytes', C.c_int64), ('activation_bytes', C.c_int64), ('lds_bytes', C.c_int64),
+                ('streamed_bytes_step', C.c_int64), ('mail_granules', C.c_int64)]
+
+
+def teamg_plan(lds_budget_bytes: int = -1, *, rnn_dims, fc_dims, bits, pad, upsample_factors, feat_dims, compute_dims, res_out_dims,
+               res_blocks, hop_length, sample_rate=22050, mode='RAW') -> dict:
+    """Host-only ``wrnn_teamg_plan``: how WRNN_KERNEL_TEAMG splits a model of these constructor dims over the 32 workgroups of a team and
+    what it keeps in LDS with ``lds_budget_bytes`` for resident weights (< 0: the default, 160 KiB minus the activation vectors).
+    ``layers``: name -> dict of the ``wrnn_teamg_layer_info`` fields (``own_first`` / ``own_count`` as lists of 32)."""
+    cfg = Config()
+    cfg.rnn_dims, cfg.fc_dims, cfg.bits, cfg.pad = rnn_dims, fc_dims, bits, pad
+    cfg.n_upsample = len(upsample_factors)
+    for i, s in enumerate(upsample_factors):
+        cfg.upsample_factors[i] = int(s)
+    cfg.feat_dims, cfg.compute_dims, cfg.res_out_dims = feat_dims, compute_dims, res_out_dims
+    cfg.res_blocks, cfg.hop_length, cfg.sample_rate = res_blocks, hop_length, sample_rate
+    cfg.mode = MODE_RAW if mode == 'RAW' else MODE_MOL
+    info = TeamgPlanInfo()
+    rc = load_library().wrnn_teamg_plan(C.byref(cfg), int(lds_budget_bytes), C.byref(info))
+    if rc != 0:
+        raise WrnnError(rc, f'wrnn_teamg_plan: no plan for rnn_dims {rnn_dims}, fc_dims {fc_dims}, feat_dims {feat_dims}, res_out_dims {res_out_dims}, '
+                            f'bits {bits}, mode {mode}')
+    layers = {}
+    for name, li in zip(TEAMG_LAYER_NAMES, info.layer):
+        layers[name] = {f: (list(getattr(li, f)) if f.startswith('own_') else int(getattr(li, f))) for f, _ in TeamgLayerInfo._fields_ if f != 'reserved_'}
+    out = {f: int(getattr(info, f)) for f, _ in TeamgPlanInfo._fields_ if f != 'layer'}
+    out['layers'] = layers
+    return out
 
 
 _lib: Optional[C.CDLL] = None
@@ -200,6 +242,10 @@ def load_library() -> C.CDLL:
     lib.wrnn_team_info.restype = C.c_int32
     lib.wrnn_debug_force_no_teams.argtypes = [vp, C.c_int32]
     lib.wrnn_debug_force_no_teams.restype = C.c_int
+    lib.wrnn_teamg_plan.argtypes = [C.POINTER(Config), C.c_int64, C.POINTER(TeamgPlanInfo)]
+    lib.wrnn_teamg_plan.restype = C.c_int
+    lib.wrnn_debug_teamg_lds_budget.argtypes = [vp, C.c_int64]
+    lib.wrnn_debug_teamg_lds_budget.restype = C.c_int
     lib.wrnn_stream_open.argtypes = [vp, C.c_int32, C.POINTER(SampleOpts), C.POINTER(vp)]
     lib.wrnn_stream_open.restype = C.c_int
     lib.wrnn_stream_push.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int64, C.POINTER(C.c_int64), vp]
@@ -289,6 +335,9 @@ class NativeVocoder:
         cfg.device = int(device)
         self.device = int(device)
         self.hop = int(hop_length)
+        self._dims = dict(rnn_dims=rnn_dims, fc_dims=fc_dims, bits=bits, pad=pad, upsample_factors=tuple(upsample_factors), feat_dims=feat_dims,
+                          compute_dims=compute_dims, res_out_dims=res_out_dims, res_blocks=res_blocks, hop_length=hop_length,
+                          sample_rate=sample_rate, mode=mode)
         self._h = C.c_void_p()
         rc = self.lib.wrnn_create(C.byref(cfg), C.byref(self._h))
         if rc != 0:
@@ -451,6 +500,14 @@ class NativeVocoder:
     def debug_force_no_teams(self, on: bool):
         """Test hook: AUTO behaves as if the team kernels' residency check had failed."""
         self._check(self.lib.wrnn_debug_force_no_teams(self._h, int(bool(on))))
+
+    def teamg_plan(self, lds_budget_bytes: int = -1) -> dict:
+        """Ownership and weight placement of WRNN_KERNEL_TEAMG for this model (:func:`teamg_plan`; host only)."""
+        return teamg_plan(lds_budget_bytes, **self._dims)
+
+    def debug_teamg_lds_budget(self, lds_budget_bytes: int):
+        """Test hook: the following WRNN_KERNEL_TEAMG calls place their weights with this LDS budget (< 0: the default)."""
+        self._check(self.lib.wrnn_debug_teamg_lds_budget(self._h, int(lds_budget_bytes)))
 
     def last_timing(self) -> dict:
         t = Timing()

@@ -189,6 +189,7 @@ void wrnn_destroy(wrnn_handle *h) {
     if (h->err_dev) (void)hipFree(h->err_dev);
     if (h->team_w) (void)hipFree(h->team_w);
     if (h->team_fc3) (void)hipFree(h->team_fc3);
+    if (h->teamg_img) (void)hipFree(h->teamg_img);
     if (h->batch_w) (void)hipFree(h->batch_w);
     if (h->batch_fc3) (void)hipFree(h->batch_fc3);
     if (h->batch_wn) (void)hipFree(h->batch_wn);
@@ -220,6 +221,11 @@ int32_t wrnn_team_info(const wrnn_handle *h, int32_t *n_teams_out, const char **
 int wrnn_debug_force_no_teams(wrnn_handle *h, int32_t on) {
     if (!h) return WRNN_ERR_INVALID;
     h->force_no_teams = on != 0;
+    return WRNN_OK;
+}
+int wrnn_debug_teamg_lds_budget(wrnn_handle *h, int64_t bytes) {
+    if (!h) return WRNN_ERR_INVALID;
+    h->teamg_budget = bytes < 0 ? -1 : bytes;
     return WRNN_OK;
 }
 int32_t wrnn_n_classes(const wrnn_handle *h) { return h ? h->d.NC : 0; }
@@ -448,6 +454,7 @@ int wrnn_load_weights(wrnn_handle *h, const wrnn_tensor_desc *tensors, int32_t n
     if (h->wdev) { (void)hipFree(h->wdev); h->wdev = nullptr; }
     WRNN_HIP_TRY(h, hipMalloc(&h->wdev, o.total * sizeof(float)));
     WRNN_HIP_TRY(h, hipMemcpy(h->wdev, pk.data(), o.total * sizeof(float), hipMemcpyHostToDevice));
+    h->teamg_img_ok = false;   // the TEAMG image is packed from wdev by the next TEAMG call
     h->loaded = true;
     return WRNN_OK;
 }
@@ -566,6 +573,33 @@ static int run_team2(wrnn_handle *h, const WrnnLoopArgs &a, const WrnnFrameTable
     return wrnn_run_team2_segments(h, ta, h->cond, 0, a.steps, seg, launches, s);
 }
 
+// The team kernel for any dims (loop_teamg.hip): one row per XCD team at a time, one launch.  Placement and residency are settled here,
+// before the launch; whatever keeps the kernel from running is an error with its reason, never another kernel.
+static int run_teamg(wrnn_handle *h, const WrnnLoopArgs &a, int snake, int n_slots, hipStream_t s) {
+    if (h->force_no_teams) return wrnn_fail(h, WRNN_ERR_INVALID, "team kernels disabled by wrnn_debug_force_no_teams (test hook)");
+    if (h->n_teams < 1) return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "WRNN_KERNEL_TEAMG: fewer than 32 CUs visible (one team = the 32 CUs of an XCD)");
+    WrnnTeamGArgs ga{};
+    if (const char *why = wrnn_teamg_make_plan(a.d, h->teamg_budget, ga.plan)) return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "%s", why);
+    int blocks = 0;
+    const hipError_t oe = wrnn_teamg_occupancy(ga.plan, &blocks);
+    (void)hipGetLastError();
+    if (oe != hipSuccess || blocks < 1)
+        return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "WRNN_KERNEL_TEAMG: loop_teamg_kernel cannot be resident on a CU with %zu bytes of LDS (%s)",
+                         ((size_t)ga.plan.act_floats + ga.plan.res_floats) * sizeof(float), oe != hipSuccess ? hipGetErrorString(oe) : "occupancy 0");
+    if (!h->teamg_img_ok) {
+        if (h->teamg_img) { (void)hipFree(h->teamg_img); h->teamg_img = nullptr; }
+        WRNN_HIP_TRY(h, hipMalloc(&h->teamg_img, (size_t)32 * ga.plan.img_floats_wg * sizeof(float)));
+        WRNN_HIP_TRY(h, wrnn_teamg_pack(h, ga.plan, h->teamg_img, s));
+        h->teamg_img_ok = true;
+        WRNN_HIP_TRY(h, hipEventRecord(h->ev[1], s));   // the one-time image is not loop time
+    }
+    ga.a = a; ga.img = h->teamg_img; ga.sched = h->sched_dev; ga.n_slots = n_slots; ga.ragged = snake; ga.n_teams = h->n_teams;
+    ga.mail = h->mail; ga.ctl = h->ctl;
+    const size_t mail_bytes = (size_t)h->n_teams * ga.plan.mail_granules * sizeof(unsigned long long);   // sized from the dims; <= WRNN_MAIL_BYTES
+    WRNN_HIP_TRY(h, wrnn_gated_launch(h->cfg.device, s, h->mail, mail_bytes, h->ctl, 128, [&] { return wrnn_launch_loop_teamg(ga, s); }));
+    return WRNN_OK;
+}
+
 // Body of wrnn_generate and wrnn_generate_folded.  fold_frames != null: the rows are the folds of ALL B utterances (rows_total of them,
 // see rows_folded_kernel), every per-frame table entry past an utterance's own end is its zero-input entry T.
 static int generate_impl(wrnn_handle *h, const float *mels_dev, int32_t B, int32_t T, int32_t batched, int32_t target, int32_t overlap,
@@ -638,6 +672,8 @@ static int generate_impl(wrnn_handle *h, const float *mels_dev, int32_t B, int32
         if (int rc = batch_family ? run_batch(h, a, t, B, kernel == WRNN_KERNEL_BATCH_CS, opts->batch_rows, snake, s)
                                   : run_team2(h, a, t, B, opts->team2_segment, snake, (rows + sched_teams - 1) / sched_teams * sched_teams, &launches, s))
             return rc;
+    } else if (kernel == WRNN_KERNEL_TEAMG) {
+        if (int rc = run_teamg(h, a, snake, (rows + sched_teams - 1) / sched_teams * sched_teams, s)) return rc;
     } else {
         return wrnn_fail(h, WRNN_ERR_INVALID, "kernel %d not available", kernel);
     }

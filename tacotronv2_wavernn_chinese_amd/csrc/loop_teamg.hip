@@ -1,0 +1,573 @@
+// WRNN_KERNEL_TEAMG: the per-sample loop of WaveRNN.generate (wavernn/models/fatchord_version.py:194-241) for ANY constructor
+// dims, one row per XCD team.  The machinery is loop_dm_team.hip's: one team = the 32 workgroups of one XCD (formed by
+// HW_REG_XCC_ID, co-residency checked with WRNN_ARRIVE_POLLS), 8-byte {tag, value} granules exchanged through the XCD's L2,
+// double-buffered by step parity, every spin bounded (device error word, `dead`: all waves run to the end).  What is new is that
+// nothing is a compile-time shape: the layer sizes arrive in WrnnTeamGPlan.
+//
+// Ownership.  Every layer is a list of units -- a hidden unit with its three gate rows (rnn1, rnn2) or one output row (I, fc1, fc2,
+// fc3).  Workgroup g owns units [g U, min(N, (g + 1) U)) of a layer of N units, U = ceil(N / 32): possibly none (rnn 100: U = 4, the
+// last seven workgroups own no hidden unit), and it still takes part in every exchange.  A 16-lane group (one DPP row) evaluates one
+// unit: a row is K floats padded to a multiple of 64, lane q reads float4 q, q + 16, ... of the row and of the activation vector,
+// the 16 partial sums are added with dmt_row_sum's DPP steps.  Where a workgroup owns 16 or fewer hidden units a group takes one gate
+// row of a unit instead (gru_phase).
+//
+// Placement.  A workgroup's slice of the weights is one contiguous image in device memory (wrnn_teamg_pack); the first `nres` units
+// of every layer are copied to LDS at the start of a launch and stay there, the rest is read every step from L2 / Infinity Cache with
+// the same 16-byte loads.  Weights are read-only during a launch: plain loads.  wrnn_teamg_make_plan decides nres.
+//
+// One step = five exchanges on the serial chain plus one beside it:
+//   [xc]  the conditioning's share of I, W_I[:, 1:] . [m_t | a1_t] + b_I, for step t + 1 -- published under exchange 2 of step t
+//   x = xc + W_I[:, 0] x_{t-1}                                                             :208-209 (every workgroup, all H)
+//   1. h1' of the own units from [W_ih1 | W_hh1] . [x | h1]          -> [h1']  x2 = x + h1'  :210-212
+//   2. h2' from [W_ih2 | W_hh2] . [x2 | a2_t | h2]                   -> [h2']  x3 = x2 + h2' :213-216
+//   3. relu(fc1 . [x3 | a3_t])                                       -> [fc1]                :217-218
+//   4. relu(fc2 . [fc1 | a4_t])                                      -> [fc2]                :220-221
+//   5. fc3 rows of the own classes; RAW: + noise, race inside the workgroup, -> [32 candidates (value, class)], every workgroup
+//      picks the winner; MOL: -> [30 outputs], every workgroup runs the sampler                :223-237
+#include "device_util.h"
+#include "wrnn_internal.h"
+
+#define TG_THREADS WRNN_TEAMG_THREADS
+#define TG_SPIN_MAX 300000u
+#define TG_WGS 32
+#define TG_LDS_MAX (160 * 1024)
+
+typedef unsigned long long u64;
+
+namespace {
+
+__host__ __device__ inline int tg_r64(int n) { return (n + 63) & ~63; }
+
+// LDS carve-up of the activation vectors (floats); every vector is padded with zeros to the padded row length of the layer it feeds
+struct TgLay {
+    int HP, XAP, FAP, FCP, CK, CB;
+    int xh1, xh2, f1, f2, f3, cb, gs, misc, total;
+    __host__ __device__ TgLay(const WrnnDims &d) {
+        HP = tg_r64(d.H); XAP = tg_r64(d.H + d.A); FAP = tg_r64(d.FC + d.A); FCP = tg_r64(d.FC); CK = tg_r64(d.F + d.A);
+        CB = tg_r64(d.F + d.R) > CK ? tg_r64(d.F + d.R) : CK;
+        int o = 0;
+        xh1 = o; o += 2 * (HP + HP);     // [parity][x (HP) | h1 (HP)]            input of rnn1
+        xh2 = o; o += 2 * (XAP + HP);    // [parity][x2 | a2_t (XAP) | h2 (HP)]   input of rnn2
+        f1 = o; o += XAP;                // [x3 | a3_t]                           input of fc1
+        f2 = o; o += FAP;                // [relu(fc1) | a4_t]                    input of fc2
+        f3 = o; o += FCP;                // relu(fc2)                             input of fc3
+        cb = o; o += 2 * CB;             // [parity][m_t (F) | a_t (R)]           conditioning of a step; its head is the input of I
+        gs = o; o += 128;                // [16 units][3 gates][segment A sum, segment B sum] of a GRU layer split by gate rows
+        misc = o; o += 128;              // 0-2 team / rank / bail-out, 8 x_{t-1}, 32-63 race values, 64-95 race classes
+        total = o;
+    }
+};
+
+__device__ __forceinline__ unsigned tg_xcc_id() {
+    unsigned v;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
+    return v & 0xf;
+}
+__device__ __forceinline__ void tg_st(u64 *base, unsigned idx, unsigned tag, float payload) {
+    const u64 v = ((u64)tag << 32) | __float_as_uint(payload);
+    const unsigned off = idx * 8u;
+    asm volatile("global_store_dwordx2 %0, %1, %2" ::"v"(off), "v"(v), "s"(base) : "memory");
+}
+__device__ __forceinline__ u64 tg_peek(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// one granule per lane; wave-uniform completion; two staggered first looks (see loop_team2.hip)
+__device__ __forceinline__ float tg_take(const u64 *base, unsigned idx, unsigned tag, bool &dead, unsigned *err, unsigned code) {
+    u64 ga = tg_peek(base + idx);
+    __builtin_amdgcn_s_sleep(3);
+    u64 gb = tg_peek(base + idx);
+    if (__all((unsigned)(ga >> 32) == tag)) return __uint_as_float((unsigned)ga);
+    unsigned spins = 0;
+    while (!dead && !__all((unsigned)(gb >> 32) == tag)) {
+        if (++spins > TG_SPIN_MAX) { dead = true; if ((threadIdx.x & 63) == 0) atomicExch(err, code); break; }
+        gb = tg_peek(base + idx);
+    }
+    return __uint_as_float((unsigned)gb);
+}
+template <int CTRL>
+__device__ __forceinline__ float tg_dpp(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float tg_row_sum(float v) {   // sum over the 16 lanes of a DPP row, in every lane
+    v += tg_dpp<0xB1>(v);
+    v += tg_dpp<0x4E>(v);
+    v += tg_dpp<0x141>(v);
+    v += tg_dpp<0x140>(v);
+    return v;
+}
+
+// G rows of one unit against one activation vector: wp = the unit's first row + lane q (float4), rows kp4 float4 apart; xp = the
+// vector + q.  Segment A = float4 steps [0, nA), segment B = [nA, nK): sa / sb are their sums (the n gate of a GRU needs them apart)
+template <int G>
+__device__ __forceinline__ void tg_dot(const float4 *__restrict__ wp, int kp4, const float4 *xp, int nA, int nK, float (&sa)[G], float (&sb)[G]) {
+    float a0[G], a1[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) a0[g] = a1[g] = 0.0f;
+#pragma unroll 4
+    for (int k = 0; k < nA; ++k) {
+        const float4 x = xp[k * 16];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const float4 w = wp[(size_t)g * kp4 + k * 16];
+            a0[g] = fmaf(w.x, x.x, a0[g]); a1[g] = fmaf(w.y, x.y, a1[g]);
+            a0[g] = fmaf(w.z, x.z, a0[g]); a1[g] = fmaf(w.w, x.w, a1[g]);
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) { sa[g] = tg_row_sum(a0[g] + a1[g]); a0[g] = a1[g] = 0.0f; }
+#pragma unroll 4
+    for (int k = nA; k < nK; ++k) {
+        const float4 x = xp[k * 16];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const float4 w = wp[(size_t)g * kp4 + k * 16];
+            a0[g] = fmaf(w.x, x.x, a0[g]); a1[g] = fmaf(w.y, x.y, a1[g]);
+            a0[g] = fmaf(w.z, x.z, a0[g]); a1[g] = fmaf(w.w, x.w, a1[g]);
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) sb[g] = tg_row_sum(a0[g] + a1[g]);
+}
+
+__global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta) {
+    extern __shared__ __attribute__((aligned(16))) char smem_tg[];
+    float *lds = (float *)smem_tg;
+    const WrnnLoopArgs &a = ta.a;
+    const WrnnDims d = a.d;
+    const TgLay ly(d);
+    const int H = d.H, FC = d.FC, F = d.F, A = d.A, R = d.R, NC = d.NC, HOP = d.HOP, ND = d.ND, P = d.P;
+    const int HP = ly.HP, XAP = ly.XAP, FCP = ly.FCP;
+    float *misc = lds + ly.misc;
+    int *misc_i = (int *)misc;
+    float *f1 = lds + ly.f1, *f2 = lds + ly.f2, *f3 = lds + ly.f3;
+    float *wres = lds + ly.total;   // resident weights
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int qw = tid >> 4, q = tid & 15;
+
+    // ---- team formation (as loop_team2.hip): teams are numbered in order of first arrival of their XCD ----
+    if (tid == 0) {
+        const unsigned x = tg_xcc_id();
+        misc_i[2] = 0;   // bail-out flag
+        const unsigned rank = atomicAdd(&ta.ctl[x], 1u);
+        unsigned slot1 = 0, arrived = 0;
+        if (rank == 0) {
+            slot1 = atomicAdd(&ta.ctl[8], 1u) + 1u;
+            __hip_atomic_store(&ta.ctl[16 + x], slot1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        // co-residency checked, not assumed: the 32 workgroups of this XCD spin on each other for the whole launch
+        for (unsigned spins = 0; spins < WRNN_ARRIVE_POLLS; ++spins) {
+            slot1 = __hip_atomic_load(&ta.ctl[16 + x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            arrived = __hip_atomic_load(&ta.ctl[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (slot1 && arrived >= TG_WGS) break;
+        }
+        if (arrived < TG_WGS) { slot1 = 0; if (rank < TG_WGS) atomicCAS(a.err, 0u, WRNN_DEVERR_BUSY); }
+        misc_i[0] = slot1 ? (int)slot1 - 1 : 1 << 20;
+        misc_i[1] = (int)rank;
+    }
+    __syncthreads();
+    const int team = __builtin_amdgcn_readfirstlane(misc_i[0]);
+    const int g = __builtin_amdgcn_readfirstlane(misc_i[1]);
+    __syncthreads();
+    if (g >= TG_WGS || team >= ta.n_teams || team >= a.n_rows) return;
+    u64 *mail = ta.mail + (size_t)team * ta.plan.mail_granules;
+    // mailbox regions (granules), two parities each
+    const unsigned M_XC = 0, M_H1 = 2 * HP, M_H2 = 4 * HP, M_F1 = 6 * HP, M_F2 = 6 * HP + 2 * FCP, M_CAND = 6 * HP + 4 * FCP;
+    const float *w = a.w;
+    const float *img = ta.img + (size_t)g * ta.plan.img_floats_wg;
+
+    // ---- resident weights, zeroed activations ----
+    for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) {
+        const WrnnTeamGLayer &L = ta.plan.L[l];
+        const int n4 = L.nres * L.G * (L.KP / 4);
+        const float4 *src = (const float4 *)(img + L.img_off);
+        float4 *dst = (float4 *)(wres + L.lds_off);
+        for (int i = tid; i < n4; i += TG_THREADS) dst[i] = src[i];
+    }
+    for (int i = tid; i < ly.misc; i += TG_THREADS) lds[i] = 0.0f;
+    __syncthreads();
+
+    // units of layer l this workgroup owns
+    auto owned = [&](const WrnnTeamGLayer &L) -> int {
+        int n = L.N - g * L.U;
+        return n < 0 ? 0 : (n > L.U ? L.U : n);
+    };
+    // m_t, a_t of step t of the row (:203-206), as loop_simple.hip: zero conditioning past the row's own utterance (:327-330)
+    auto cond_fill = [&](const WrnnRow &rw, int64_t t, float *dst) {
+        const float *mel_b = a.mels + (size_t)rw.utt * F * a.mel_T;
+        const float *aux_b = a.aux_frames + (size_t)rw.utt * a.T * R;
+        const float *ktab = w + a.off.ktab;
+        const int64_t pos = rw.start + t;
+        const bool live = a.frames ? pos < (int64_t)a.frames[rw.utt] * HOP && pos < a.total_len : pos < a.total_len;
+        const int i = live ? (int)(pos / HOP) : 0;
+        const int r = live ? (int)(pos - (int64_t)i * HOP) : 0;
+        for (int j = tid; j < F + R; j += TG_THREADS) {
+            float v = 0.0f;
+            if (live) {
+                if (j < F) {
+                    for (int k = 0; k < ND; ++k) {
+                        const int fr = i + k - P + a.mel_off;
+                        const float mv = (fr >= 0 && fr < a.mel_T) ? mel_b[(size_t)j * a.mel_T + fr] : 0.0f;
+                        v = fmaf(ktab[r * ND + k], mv, v);
+                    }
+                } else {
+                    v = aux_b[(size_t)i * R + (j - F)];
+                }
+            }
+            dst[j] = v;
+        }
+    };
+    // the own rows of W_I[:, 1:] . [m | a1] + b_I for the step whose conditioning is in cbuf -> mailbox, tagged `tag`
+    auto xc_publish = [&](const float *cbuf, unsigned tag) {
+        const WrnnTeamGLayer &L = ta.plan.L[WRNN_TEAMG_COND];
+        const int nown = owned(L), kp4 = L.KP / 4, nK = L.KP / 64;
+        for (int ul = qw; ul < nown; ul += 32) {
+            float sa[1], sb[1];
+            if (ul < L.nres) tg_dot<1>((const float4 *)(wres + L.lds_off + (size_t)ul * L.KP) + q, kp4, (const float4 *)cbuf + q, nK, nK, sa, sb);
+            else tg_dot<1>((const float4 *)(img + L.img_off + (size_t)ul * L.KP) + q, kp4, (const float4 *)cbuf + q, nK, nK, sa, sb);
+            const int j = g * L.U + ul;
+            if (q == 0) tg_st(mail, M_XC + (tag & 1u) * HP + j, tag, sa[0] + w[a.off.I_b + j]);
+        }
+    };
+    // one GRU layer (get_gru_cell :273-279, gate rows [r; z; n]): h' of the own units -> mailbox.  xin = [input (KAP) | h (HP)]
+    // With 16 or fewer units per workgroup (rnn_dims <= 512) a unit per 16-lane group would leave half the groups, and their loads in
+    // flight, idle: then a group takes one gate ROW, the sums meet in LDS and one lane per unit finishes the cell.  Same sums either way.
+    auto gru_phase = [&](const WrnnTeamGLayer &L, const float *xin, size_t obih, size_t obhh, unsigned region, unsigned epoch) {
+        const int nown = owned(L), kp4 = L.KP / 4, nA = L.KAP / 64, nK = L.KP / 64;
+        const bool by_row = L.U <= 16;
+        if (by_row) {
+            float *gs = lds + ly.gs;
+            for (int task = qw; task < 3 * nown; task += 32) {
+                const int ul = task / 3;
+                float sa[1], sb[1];
+                if (ul < L.nres) tg_dot<1>((const float4 *)(wres + L.lds_off + (size_t)task * L.KP) + q, kp4, (const float4 *)xin + q, nA, nK, sa, sb);
+                else tg_dot<1>((const float4 *)(img + L.img_off + (size_t)task * L.KP) + q, kp4, (const float4 *)xin + q, nA, nK, sa, sb);
+                if (q == 0) { gs[2 * task] = sa[0]; gs[2 * task + 1] = sb[0]; }
+            }
+            __syncthreads();
+        }
+        for (int ul = by_row ? tid : qw; ul < nown; ul += by_row ? TG_THREADS : 32) {
+            float gi[3], gh[3];
+            if (by_row) {
+                const float *gs = lds + ly.gs + 6 * ul;
+                gi[0] = gs[0]; gh[0] = gs[1]; gi[1] = gs[2]; gh[1] = gs[3]; gi[2] = gs[4]; gh[2] = gs[5];
+            } else if (ul < L.nres) tg_dot<3>((const float4 *)(wres + L.lds_off + (size_t)ul * 3 * L.KP) + q, kp4, (const float4 *)xin + q, nA, nK, gi, gh);
+            else tg_dot<3>((const float4 *)(img + L.img_off + (size_t)ul * 3 * L.KP) + q, kp4, (const float4 *)xin + q, nA, nK, gi, gh);
+            const int j = g * L.U + ul;
+            const float *bi = w + obih, *bh = w + obhh;
+            const float rg = 1.0f / (1.0f + expf(-((gi[0] + bi[j]) + (gh[0] + bh[j]))));
+            const float zg = 1.0f / (1.0f + expf(-((gi[1] + bi[H + j]) + (gh[1] + bh[H + j]))));
+            const float ng = tanhf((gi[2] + bi[2 * H + j]) + rg * (gh[2] + bh[2 * H + j]));
+            const float hn = (1.0f - zg) * ng + zg * xin[L.KAP + j];
+            if (by_row || q == 0) tg_st(mail, region + (epoch & 1u) * HP + j, epoch, hn);
+        }
+    };
+    // relu(W . x + b) of the own rows -> mailbox
+    auto fc_phase = [&](const WrnnTeamGLayer &L, const float *xin, size_t ob, unsigned region, unsigned epoch) {
+        const int nown = owned(L), kp4 = L.KP / 4, nK = L.KP / 64;
+        for (int ul = qw; ul < nown; ul += 32) {
+            float sa[1], sb[1];
+            if (ul < L.nres) tg_dot<1>((const float4 *)(wres + L.lds_off + (size_t)ul * L.KP) + q, kp4, (const float4 *)xin + q, nK, nK, sa, sb);
+            else tg_dot<1>((const float4 *)(img + L.img_off + (size_t)ul * L.KP) + q, kp4, (const float4 *)xin + q, nK, nK, sa, sb);
+            const int j = g * L.U + ul;
+            if (q == 0) tg_st(mail, region + (epoch & 1u) * FCP + j, epoch, fmaxf(sa[0] + w[ob + j], 0.0f));
+        }
+    };
+    // all N values of an exchanged vector, element j to thread j (+ 512, ...); whole waves take part, lanes past N re-read granule N - 1
+    auto gather = [&](unsigned region, int N, unsigned epoch, bool &dead, unsigned code, auto &&put) {
+        for (int j0 = wave * 64; j0 < N; j0 += TG_THREADS) {
+            const int j = j0 + lane;
+            const float v = tg_take(mail, region + (unsigned)(j < N ? j : N - 1), epoch, dead, a.err, code);
+            if (j < N) put(j, v);
+        }
+    };
+
+    bool dead = false;
+    unsigned epoch = 0;
+    for (int it = team; it < (ta.ragged ? ta.n_slots : a.n_rows); it += ta.n_teams) {
+        int row = it;
+        if (ta.ragged) {
+            row = ta.sched[it];
+            if (row < 0 || row >= a.n_rows) continue;
+        }
+        const WrnnRow rw = a.rows[row];
+        if (rw.steps < 1) continue;
+        uint64_t kseed = a.seed;
+        uint32_t krow = (uint32_t)row;
+        if (a.keys) { const WrnnRowKey k = a.keys[row]; kseed = k.seed; krow = k.row; }
+
+        // h1 = h2 = 0, x = x_init or 0 (:194-196); conditioning and xc of the row's first step
+        for (int j = tid; j < HP; j += TG_THREADS) {
+            lds[ly.xh1 + HP + j] = 0.0f; lds[ly.xh1 + 3 * HP + j] = 0.0f;
+            lds[ly.xh2 + XAP + j] = 0.0f; lds[ly.xh2 + 2 * XAP + HP + j] = 0.0f;
+        }
+        if (tid == 0) misc[8] = a.x_init ? a.x_init[row] : 0.0f;
+        cond_fill(rw, a.seg0, lds + ly.cb + ((epoch + 1u) & 1u) * ly.CB);
+        __syncthreads();
+        xc_publish(lds + ly.cb + ((epoch + 1u) & 1u) * ly.CB, epoch + 1u);
+
+        for (int64_t t = a.seg0; t < a.seg0 + rw.steps; ++t) {
+            ++epoch;
+            const unsigned par = epoch & 1u;
+            float *xh1 = lds + ly.xh1 + par * 2 * HP, *xh1n = lds + ly.xh1 + (par ^ 1u) * 2 * HP;
+            float *xh2 = lds + ly.xh2 + par * (XAP + HP), *xh2n = lds + ly.xh2 + (par ^ 1u) * (XAP + HP);
+            float *cbp = lds + ly.cb + par * ly.CB, *cbn = lds + ly.cb + (par ^ 1u) * ly.CB;
+            const bool more = t + 1 < a.seg0 + rw.steps;
+
+            // ---- conditioning: a2 / a3 / a4 of this step into the layer inputs ----
+            for (int j = tid; j < A; j += TG_THREADS) {
+                xh2[H + j] = cbp[F + A + j];        // a2_t :213
+                f1[H + j] = cbp[F + 2 * A + j];     // a3_t :217
+                f2[FC + j] = cbp[F + 3 * A + j];    // a4_t :220
+            }
+            // ---- x = I(cat[x_{t-1}, m_t, a1_t]) :208-209: the exchanged conditioning share + the sample's column ----
+            {
+                const float xprev = misc[8];
+                const float *wI0 = w + a.off.I_t;   // row 0 of the [in][out] layout = W_I[:, 0]
+                gather(M_XC + par * HP, H, epoch, dead, 10u, [&](int j, float v) { xh1[j] = fmaf(wI0[j], xprev, v); });
+            }
+            __syncthreads();
+            // ---- 1. h1 = rnn1(x, h1); x = x + h1 :210-212 ----
+            gru_phase(ta.plan.L[WRNN_TEAMG_RNN1], xh1, a.off.r1_bih, a.off.r1_bhh, M_H1, epoch);
+            if (more) cond_fill(rw, t + 1, cbn);     // m, a of the next step, under the round trip of exchange 1
+            gather(M_H1 + par * HP, H, epoch, dead, 11u, [&](int j, float v) { xh1n[HP + j] = v; xh2[j] = xh1[j] + v; });
+            __syncthreads();
+            // ---- 2. h2 = rnn2(cat[x, a2_t], h2); x = x + h2 :213-216 ----
+            gru_phase(ta.plan.L[WRNN_TEAMG_RNN2], xh2, a.off.r2_bih, a.off.r2_bhh, M_H2, epoch);
+            if (more) xc_publish(cbn, epoch + 1u);   // beside the chain, under exchange 2: read at the start of the next step
+            gather(M_H2 + par * HP, H, epoch, dead, 12u, [&](int j, float v) { xh2n[XAP + j] = v; f1[j] = xh2[j] + v; });
+            __syncthreads();
+            // ---- 3. / 4. x = relu(fc1(cat[x, a3_t])); x = relu(fc2(cat[x, a4_t])) :217-221 ----
+            fc_phase(ta.plan.L[WRNN_TEAMG_FC1], f1, a.off.fc1_b, M_F1, epoch);
+            gather(M_F1 + par * FCP, FC, epoch, dead, 13u, [&](int j, float v) { f2[j] = v; });
+            __syncthreads();
+            fc_phase(ta.plan.L[WRNN_TEAMG_FC2], f2, a.off.fc2_b, M_F2, epoch);
+            gather(M_F2 + par * FCP, FC, epoch, dead, 14u, [&](int j, float v) { f3[j] = v; });
+            __syncthreads();
+            // ---- 5. logits = fc3(x) :223 of the own classes, and the sampler :225-237 ----
+            {
+                const WrnnTeamGLayer &L = ta.plan.L[WRNN_TEAMG_FC3];
+                const int nown = owned(L), kp4 = L.KP / 4, nK = L.KP / 64;
+                float bv = -INFINITY;
+                int bi = 0x7fffffff;
+                for (int ul = qw; ul < nown; ul += 32) {
+                    float sa[1], sb[1];
+                    if (ul < L.nres) tg_dot<1>((const float4 *)(wres + L.lds_off + (size_t)ul * L.KP) + q, kp4, (const float4 *)f3 + q, nK, nK, sa, sb);
+                    else tg_dot<1>((const float4 *)(img + L.img_off + (size_t)ul * L.KP) + q, kp4, (const float4 *)f3 + q, nK, nK, sa, sb);
+                    const int c = g * L.U + ul;
+                    const float lg = sa[0] + w[a.off.fc3_b + c];
+                    if (a.logits_out && q == 0) a.logits_out[((size_t)t * a.n_rows + row) * NC + c] = lg;
+                    if (d.mode == WRNN_MODE_RAW) {
+                        // Categorical(softmax(logits)).sample() == argmax_k logit_k - log q_k, q ~ Exp(1) (loop_simple.hip)
+                        float v = lg;
+                        if (a.noise_mode == WRNN_NOISE_INJECTED) v -= logf(a.noise1[((size_t)t * a.n_rows + row) * NC + c]);
+                        else if (a.noise_mode == WRNN_NOISE_PHILOX) v -= logf(-logf(wrnn_uniform_raw(kseed, (uint64_t)t, krow, (uint32_t)c)));
+                        if (v > bv) { bv = v; bi = c; }   // classes ascend: ties keep the lowest
+                    } else if (q == 0) {
+                        tg_st(mail, M_CAND + par * 64 + c, epoch, lg);
+                    }
+                }
+                if (d.mode == WRNN_MODE_RAW) {
+                    if (q == 0) { misc[32 + qw] = bv; misc_i[64 + qw] = bi; }
+                    __syncthreads();
+                    if (wave == 0) {
+                        float v = lane < 32 ? misc[32 + lane] : -INFINITY;
+                        int k = lane < 32 ? misc_i[64 + lane] : 0x7fffffff;
+                        wave_argmax(v, k);
+                        if (lane == 0) {   // the workgroup's candidate: granule g = value, 32 + g = class
+                            tg_st(mail, M_CAND + par * 64 + g, epoch, v);
+                            tg_st(mail, M_CAND + par * 64 + 32 + g, epoch, __int_as_float(k));
+                        }
+                        const float pv = tg_take(mail, M_CAND + par * 64 + lane, epoch, dead, a.err, 15u);
+                        const int ck = __shfl(__float_as_int(pv), (lane + 32) & 63, 64);
+                        v = lane < 32 ? pv : -INFINITY;
+                        k = lane < 32 ? ck : 0x7fffffff;
+                        wave_argmax(v, k);
+                        if (lane == 0) {
+                            const float smp = 2.0f * (float)k / ((float)NC - 1.0f) - 1.0f;   // :235
+                            if (g == 0) {
+                                if (a.labels_out) a.labels_out[(size_t)row * a.steps + t] = k;
+                                a.samples_out[(size_t)row * a.steps + t] = smp;
+                            }
+                            misc[8] = a.x_forced ? a.x_forced[(size_t)t * a.n_rows + row] : smp;
+                        }
+                    }
+                } else if (wave == 0) {
+                    // sample_from_discretized_mix_logistic (wavernn/utils/distribution.py:87-123) on the 3 * nr exchanged outputs, in every workgroup
+                    const int nr = NC / 3;
+                    const float lg = tg_take(mail, M_CAND + par * 64 + (lane < NC ? lane : NC - 1), epoch, dead, a.err, 15u);
+                    float v = -INFINITY;
+                    int k = 0x7fffffff;
+                    if (lane < nr) {
+                        float u1;
+                        if (a.noise_mode == WRNN_NOISE_INJECTED) u1 = a.noise1[((size_t)t * a.n_rows + row) * nr + lane];
+                        else u1 = wrnn_uniform_mol(kseed, (uint64_t)t, krow, (uint32_t)lane);
+                        v = lg - logf(-logf(u1));   // :107
+                        k = lane;
+                    }
+                    wave_argmax(v, k);
+                    k = k < nr ? k : 0;   // only after a timed-out exchange
+                    const float mean = __shfl(lg, nr + k, 64);                                  // :113
+                    const float ls = fmaxf(__shfl(lg, 2 * nr + k, 64), -32.23619130191664f);   // log(1e-14) :114-115
+                    if (lane == 0) {
+                        float u2;
+                        if (a.noise_mode == WRNN_NOISE_INJECTED) u2 = a.noise2[(size_t)t * a.n_rows + row];
+                        else u2 = wrnn_uniform_mol(kseed, (uint64_t)t, krow, 10u);
+                        float xs = mean + expf(ls) * (logf(u2) - logf(1.0f - u2));  // :119
+                        xs = fminf(fmaxf(xs, -1.0f), 1.0f);                         // :121
+                        if (g == 0) {
+                            if (a.labels_out) a.labels_out[(size_t)row * a.steps + t] = k;
+                            a.samples_out[(size_t)row * a.steps + t] = xs;
+                        }
+                        misc[8] = a.x_forced ? a.x_forced[(size_t)t * a.n_rows + row] : xs;
+                    }
+                }
+            }
+            if ((epoch & 63u) == 0u && dead && lane == 0) misc_i[2] = 1;   // bounded-spin bail-out, checked workgroup-wide every 64 samples
+            __syncthreads();
+            if ((epoch & 63u) == 0u && misc_i[2]) return;
+        }
+    }
+}
+
+// dst(g, ul, gate, kdst + k) = src_t[(k0 + k) * ld + row0 + g * U + ul] for the units that exist; the image was zeroed
+__global__ void __launch_bounds__(256) teamg_pack_kernel(const float *__restrict__ src_t, int ld, int row0, int k0, int K, float *__restrict__ img,
+                                                         size_t wg_stride, size_t layer_off, int N, int U, int G, int gate, int KP, int kdst) {
+    const int unit = blockIdx.x;   // < N
+    const int g = unit / U, ul = unit - g * U;
+    float *dst = img + (size_t)g * wg_stride + layer_off + ((size_t)ul * G + gate) * KP + kdst;
+    for (int k = threadIdx.x; k < K; k += 256) dst[k] = src_t[(size_t)(k0 + k) * ld + row0 + unit];
+}
+
+}  // namespace
+
+const char *wrnn_teamg_make_plan(const WrnnDims &d, int64_t budget, WrnnTeamGPlan &p) {
+    const TgLay ly(d);
+    p = WrnnTeamGPlan{};
+    auto set = [&](int l, int N, int G, int KA, int KB) {
+        WrnnTeamGLayer &L = p.L[l];
+        L.N = N; L.G = G; L.KA = KA; L.KB = KB; L.KAP = tg_r64(KA); L.KP = L.KAP + (KB ? tg_r64(KB) : 0); L.U = (N + TG_WGS - 1) / TG_WGS;
+    };
+    set(WRNN_TEAMG_FC3, d.NC, 1, d.FC, 0);
+    set(WRNN_TEAMG_FC2, d.FC, 1, d.FC + d.A, 0);
+    set(WRNN_TEAMG_FC1, d.FC, 1, d.H + d.A, 0);
+    set(WRNN_TEAMG_RNN2, d.H, 3, d.H + d.A, d.H);
+    set(WRNN_TEAMG_RNN1, d.H, 3, d.H, d.H);
+    set(WRNN_TEAMG_COND, d.H, 1, d.F + d.A, 0);
+    p.act_floats = ly.total;
+    const int64_t act_bytes = (int64_t)ly.total * 4;
+    const int64_t granules = 2LL * (3 * ly.HP + 2 * ly.FCP + 64);
+    p.mail_granules = (int32_t)granules;
+    if (act_bytes > TG_LDS_MAX) return "WRNN_KERNEL_TEAMG: the activation vectors of one row exceed 160 KiB of LDS";
+    if (granules > WRNN_MAIL_GRANULES_MAX) return "WRNN_KERNEL_TEAMG: fc_dims too large for the team mailbox";
+    if (d.mode == WRNN_MODE_MOL && d.NC > 64) return "WRNN_KERNEL_TEAMG: more than 64 mixture outputs";
+    const int64_t dflt = TG_LDS_MAX - act_bytes;
+    if (budget < 0 || budget > dflt) budget = dflt;
+    // Residency in layer order (shortest rows first): whole units, as many as still fit; the first layer that does not fit whole is the
+    // last to get any (so a layer's resident share never shrinks when the budget grows).  Every workgroup gets the same count.
+    int64_t left = budget / 4, img = 0, res = 0;
+    for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) {
+        WrnnTeamGLayer &L = p.L[l];
+        const int64_t unit = (int64_t)L.G * L.KP;
+        int64_t n = left / unit;
+        if (n > L.U) n = L.U;
+        L.nres = (int32_t)n;
+        L.lds_off = (int32_t)res;
+        L.img_off = img;
+        res += n * unit; left -= n * unit;
+        if (n < L.U) left = 0;
+        img += (int64_t)L.U * unit;
+    }
+    p.img_floats_wg = img;
+    p.res_floats = (int32_t)res;
+    return nullptr;
+}
+
+hipError_t wrnn_teamg_pack(const wrnn_handle *h, const WrnnTeamGPlan &p, float *img, hipStream_t s) {
+    const WrnnDims &d = h->d;
+    const WrnnPacked &o = h->off;
+    const float *w = h->wdev;
+    hipError_t e = hipMemsetAsync(img, 0, (size_t)TG_WGS * p.img_floats_wg * sizeof(float), s);
+    if (e != hipSuccess) return e;
+    (void)hipGetLastError();
+    auto put = [&](int l, const float *src_t, int ld, int row0, int k0, int K, int gate, int kdst) {
+        const WrnnTeamGLayer &L = p.L[l];
+        hipLaunchKernelGGL(teamg_pack_kernel, dim3(L.N), dim3(256), 0, s, src_t, ld, row0, k0, K, img, (size_t)p.img_floats_wg, (size_t)L.img_off, L.N, L.U,
+                           L.G, gate, L.KP, kdst);
+    };
+    const int H = d.H, A = d.A, FC = d.FC;
+    put(WRNN_TEAMG_FC3, w + o.fc3_t, d.NC, 0, 0, FC, 0, 0);
+    put(WRNN_TEAMG_FC2, w + o.fc2_t, FC, 0, 0, FC + A, 0, 0);
+    put(WRNN_TEAMG_FC1, w + o.fc1_t, FC, 0, 0, H + A, 0, 0);
+    for (int gate = 0; gate < 3; ++gate) {
+        put(WRNN_TEAMG_RNN2, w + o.r2_wih_t, 3 * H, gate * H, 0, H + A, gate, 0);
+        put(WRNN_TEAMG_RNN2, w + o.r2_whh_t, 3 * H, gate * H, 0, H, gate, p.L[WRNN_TEAMG_RNN2].KAP);
+        put(WRNN_TEAMG_RNN1, w + o.r1_wih_t, 3 * H, gate * H, 0, H, gate, 0);
+        put(WRNN_TEAMG_RNN1, w + o.r1_whh_t, 3 * H, gate * H, 0, H, gate, p.L[WRNN_TEAMG_RNN1].KAP);
+    }
+    put(WRNN_TEAMG_COND, w + o.I_t, H, 0, 1, d.F + A, 0, 0);   // column 0 (the fed-back sample) stays a vector
+    return hipGetLastError();
+}
+
+static size_t teamg_lds_bytes(const WrnnTeamGPlan &p) { return ((size_t)p.act_floats + (size_t)p.res_floats) * sizeof(float); }
+
+hipError_t wrnn_teamg_occupancy(const WrnnTeamGPlan &p, int *blocks_per_cu) {
+    const size_t lds = teamg_lds_bytes(p);
+    hipError_t e = hipFuncSetAttribute((const void *)loop_teamg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, (const void *)loop_teamg_kernel, TG_THREADS, lds);
+}
+
+hipError_t wrnn_launch_loop_teamg(const WrnnTeamGArgs &a, hipStream_t s) {
+    (void)hipGetLastError();
+    const size_t lds = teamg_lds_bytes(a.plan);
+    hipError_t e = hipFuncSetAttribute((const void *)loop_teamg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(loop_teamg_kernel, dim3(a.n_teams * TG_WGS), dim3(TG_THREADS), lds, s, a);
+    return hipGetLastError();
+}
+
+// ---- C ABI: the plan, host only ----
+
+extern "C" int wrnn_teamg_plan(const wrnn_config *cfg, int64_t lds_budget_bytes, wrnn_teamg_plan_info *out) {
+    if (!cfg || !out) return WRNN_ERR_INVALID;
+    // the dims as wrnn_create derives and bounds them (api.hip)
+    WrnnDims d{};
+    d.H = cfg->rnn_dims; d.FC = cfg->fc_dims; d.F = cfg->feat_dims; d.C = cfg->compute_dims; d.R = cfg->res_out_dims; d.A = cfg->res_out_dims / 4;
+    d.NBLK = cfg->res_blocks; d.P = cfg->pad; d.KS = 2 * cfg->pad + 1; d.ND = d.KS; d.mode = cfg->mode; d.HOP = cfg->hop_length;
+    if (cfg->mode == WRNN_MODE_RAW) {
+        if (cfg->bits < 1 || cfg->bits > 16) return WRNN_ERR_INVALID;
+        d.NC = 1 << cfg->bits;
+    } else if (cfg->mode == WRNN_MODE_MOL) d.NC = 30;
+    else return WRNN_ERR_INVALID;
+    if (d.H < 1 || d.FC < 1 || d.F < 1 || d.R < 4 || d.R % 4 != 0 || d.H > 1024 || d.R > 1024 || d.FC > (1 << 20) || d.F > (1 << 20)) return WRNN_ERR_INVALID;
+    WrnnTeamGPlan p;
+    if (wrnn_teamg_make_plan(d, lds_budget_bytes, p)) return WRNN_ERR_UNSUPPORTED;
+    *out = wrnn_teamg_plan_info{};
+    for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) {
+        const WrnnTeamGLayer &L = p.L[l];
+        wrnn_teamg_layer_info &o = out->layer[l];
+        const int K = L.KA + L.KB;
+        o.units = L.N; o.rows_per_unit = L.G; o.k = K; o.k_padded = L.KP; o.resident_units = L.nres;
+        o.weight_bytes = 4LL * L.N * L.G * K;
+        o.rows_min = INT32_MAX;
+        for (int g = 0; g < TG_WGS; ++g) {
+            int n = L.N - g * L.U;
+            n = n < 0 ? 0 : (n > L.U ? L.U : n);
+            o.own_first[g] = n ? g * L.U : L.N;
+            o.own_count[g] = n;
+            const int rows = n * L.G, res = (n < L.nres ? n : L.nres);
+            if (rows < o.rows_min) o.rows_min = rows;
+            if (rows > o.rows_max) o.rows_max = rows;
+            const int64_t rb = 4LL * res * L.G * K;
+            if (rb > o.resident_bytes_wg) o.resident_bytes_wg = rb;
+            o.resident_bytes_team += rb;
+        }
+        o.streamed_bytes_step = o.weight_bytes - o.resident_bytes_team;
+        o.lds_bytes = 4LL * L.nres * L.G * L.KP;
+        out->streamed_bytes_step += o.streamed_bytes_step;
+    }
+    out->activation_bytes = 4LL * p.act_floats;
+    out->lds_bytes = 4LL * ((int64_t)p.act_floats + p.res_floats);
+    out->lds_budget_bytes = (lds_budget_bytes < 0 || lds_budget_bytes > TG_LDS_MAX - out->activation_bytes) ? TG_LDS_MAX - out->activation_bytes : lds_budget_bytes;
+    out->mail_granules = p.mail_granules;
+    return WRNN_OK;
+}

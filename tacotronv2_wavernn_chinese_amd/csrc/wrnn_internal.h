@@ -109,6 +109,9 @@ struct wrnn_handle {
     bool team_dims = false;       // the constructor dims are the reference hparams the team kernels are built for
     bool team_ok = false;         // the 32-workgroup team kernels can be co-resident on this device (checked at create)
     std::string team_why;         // why not, when team_ok is false
+    float *teamg_img = nullptr;   // TEAMG weight image [32 WGs][WrnnTeamGPlan::img_floats_wg], packed on the device by the first TEAMG call after a load
+    bool teamg_img_ok = false;
+    int64_t teamg_budget = -1;    // wrnn_debug_teamg_lds_budget: LDS bytes for resident weights, < 0 = the default
     bool force_no_teams = false;  // wrnn_debug_force_no_teams: AUTO behaves as if residency had failed (tests of the slow-path warning)
     bool cs_ok = false;           // ... and loop_batch_cs_kernel in particular (AUTO falls back to WRNN_KERNEL_BATCH without it)
     float *tab = nullptr;         // CM|CA|VM|VA|C2|C3|C4 for the current batch
@@ -266,6 +269,41 @@ struct WrnnBatchArgs {
     unsigned *err;
     unsigned long long *prof;
 };
+
+// Team kernel for any dims (loop_teamg.hip).  Every layer is a set of `N` units of `G` rows (3 gate rows of a hidden unit, or one
+// row); a row is [segment A: KA weights, padded to KAP | segment B: KB weights, padded] = KP floats, both paddings multiples of 64
+// (16 lanes x float4).  Workgroup g owns units [g * U, min(N, (g + 1) * U)); its slice of the image is U * G rows of KP floats at
+// img_off, of which the first nres units are copied to LDS (at lds_off floats behind the activation vectors) at the start of a launch.
+struct WrnnTeamGLayer {
+    int32_t N, G, KA, KB, KAP, KP, U, nres;
+    int64_t img_off;    // floats, inside a workgroup's image
+    int32_t lds_off;    // floats, inside the resident-weight area
+    int32_t pad_;
+};
+struct WrnnTeamGPlan {
+    WrnnTeamGLayer L[WRNN_TEAMG_LAYERS];
+    int64_t img_floats_wg;     // image floats per workgroup (every workgroup the same)
+    int32_t act_floats;        // LDS floats of the activation vectors (TgLay, loop_teamg.hip)
+    int32_t res_floats;        // LDS floats of the resident weights
+    int32_t mail_granules;     // per team
+    int32_t pad_;
+};
+#define WRNN_TEAMG_THREADS 512
+struct WrnnTeamGArgs {
+    WrnnLoopArgs a;            // the call's loop arguments (weights, conditioning inputs, rows, sampling)
+    WrnnTeamGPlan plan;
+    const float *img;          // [32][plan.img_floats_wg]
+    const int32_t *sched;      // as WrnnTeamArgs
+    int32_t n_slots, ragged, n_teams, pad_;
+    unsigned long long *mail;  // [n_teams][plan.mail_granules]
+    unsigned *ctl;
+};
+// pure host: ownership and placement for dims d with `budget` LDS bytes for resident weights (< 0 or too large: 160 KiB minus the
+// activation vectors); nullptr, or why the kernel cannot serve these dims
+const char *wrnn_teamg_make_plan(const WrnnDims &d, int64_t budget, WrnnTeamGPlan &p);
+hipError_t wrnn_teamg_pack(const wrnn_handle *h, const WrnnTeamGPlan &p, float *img, hipStream_t s);
+hipError_t wrnn_teamg_occupancy(const WrnnTeamGPlan &p, int *blocks_per_cu);
+hipError_t wrnn_launch_loop_teamg(const WrnnTeamGArgs &a, hipStream_t s);
 
 // Persistent team kernels of the two GRU recurrences of wrnn_train_step (train_team.hip)
 struct WrnnGruTeamArgs {

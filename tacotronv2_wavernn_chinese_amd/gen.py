@@ -7,7 +7,7 @@ handed to ``model.generate``; the output file name pattern is the reference's (:
 
 Deliberate differences: the reference hard-overrides ``batched = False`` and
 ``device = cpu`` after parsing its flags (:76-77, :93); here ``--batched`` is honoured and the model
-runs on the MI355X.  Extensions: ``--target auto|per_xcd``, ``--noise reference [--seed N]``, ``--stream-frames N`` (streaming generation)
+runs on the MI355X.  Extensions: ``--kernel NAME``, ``--target auto|per_xcd``, ``--noise reference [--seed N]``, ``--stream-frames N`` (streaming generation)
 (the reference's own noise stream: ``vocoder.reference_noise``).
 
 The ``.wav`` branch (:17-20) does what the reference's intends: ``load_wav``, the input saved as ``__{idx}__{k}k_steps_target.wav`` (the
@@ -112,7 +112,10 @@ def build_model_from_hparams() -> WaveRNN:
                    mode=hp.voc_mode)
 
 
-def main(argv=None):
+KERNEL_CHOICES = ('auto', 'simple', 'team2', 'batch', 'batch_cs', 'teamg')
+
+
+def build_parser() -> argparse.ArgumentParser:
     from .hparams import DEFAULT_HPARAMS
     parser = argparse.ArgumentParser(description='Generate WaveRNN Samples')
     parser.add_argument('--batched', '-b', dest='batched', action='store_true', help='Fast Batched Generation')
@@ -139,8 +142,15 @@ def main(argv=None):
                              '--unbatched) and print the time to first audio and the real-time factor')
     parser.add_argument('--hp_file', metavar='FILE', default=DEFAULT_HPARAMS,
                         help='The file to use for the hyperparameters')
+    parser.add_argument('--kernel', choices=KERNEL_CHOICES, default='auto',
+                        help="extension: the device loop kernel ('auto': the library's choice; 'teamg': the XCD-team kernel for any model "
+                             "dims, the fast path of a model whose dims are not the reference hparams)")
     parser.set_defaults(batched=None)
-    args = parser.parse_args(argv)
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
 
     conditioning = condition_arguments(args)
     hp.configure(args.hp_file)
@@ -159,6 +169,8 @@ def main(argv=None):
     print('Using device:', device)
     print('\nInitialising Model...\n')
     model = build_model_from_hparams().to(device)
+    from . import _cabi
+    model.kernel = _cabi.KERNEL_IDS[args.kernel]
     # wavernn_gen.py:112-117: `--voc_weights`, else the latest checkpoint of the training run
     # (Paths.voc_latest_weights = <base>/logs_wavernn/checkpoints/latest_weights.pyt, wavernn/utils/paths.py:11-12; <base> is
     # the directory the script is started from here).  The reference then dies in torch.load when that file is absent; no

@@ -621,7 +621,8 @@ class WaveRNN(nn.Module):
             return
         self._slow_warned = True
         warnings.warn(f'WaveRNN: generating on the any-shape fallback kernel (WRNN_KERNEL_SIMPLE), ~1 ms per sample step -- about 300x slower '
-                      f'than the XCD-team kernels ({steps} steps: ~{steps * 1e-3:.0f} s per row).  Reason: {why}.', RuntimeWarning, stacklevel=stacklevel)
+                      f'than the XCD-team kernels ({steps} steps: ~{steps * 1e-3:.0f} s per row).  Reason: {why}.  A model of other dims runs an '
+                      f"XCD-team kernel with kernel='teamg' (generate_raw(..., kernel='teamg') or model.kernel = 'teamg').", RuntimeWarning, stacklevel=stacklevel)
 
     def epilogue_device(self, res, batched, target, overlap, mu_law, wave_len):
         """float64 tail of generate() (:243-258) on the GPU (``wrnn_epilogue``): (wave_len,) float64 cuda tensor."""
