@@ -13,7 +13,7 @@
 
 #include "mel_internal.h"
 #include "resample_internal.h"
-#include "wrnn_internal.h"
+#include "team_common.h"
 
 namespace {
 
@@ -95,6 +95,20 @@ hipError_t wrnn_team_gate_leave(int device, hipStream_t s) {
     return e;
 }
 
+const char *wrnn_dims_from_config(const wrnn_config *cfg, WrnnDims &d) {
+    d = WrnnDims{};
+    d.H = cfg->rnn_dims; d.FC = cfg->fc_dims; d.F = cfg->feat_dims; d.C = cfg->compute_dims;
+    d.R = cfg->res_out_dims; d.A = cfg->res_out_dims / 4; d.NBLK = cfg->res_blocks; d.P = cfg->pad;
+    d.KS = 2 * cfg->pad + 1; d.ND = d.KS; d.mode = cfg->mode; d.HOP = cfg->hop_length;
+    if (cfg->mode == WRNN_MODE_RAW) d.NC = 1 << cfg->bits;       // fatchord_version.py:98-99
+    else if (cfg->mode == WRNN_MODE_MOL) d.NC = 30;             // :100-101
+    else return "mode must be WRNN_MODE_RAW or WRNN_MODE_MOL";
+    if (d.H < 1 || d.FC < 1 || d.F < 1 || d.C < 1 || d.R < 4 || d.NBLK < 0 || d.P < 0 || cfg->bits < 1 || cfg->bits > 16) return "bad dims";
+    if (cfg->res_out_dims % 4 != 0) return "res_out_dims must be a multiple of 4 (aux split, :109)";
+    if (d.H > 1024 || d.C > 1024 || d.R > 1024) return "unsupported dims: rnn_dims, compute_dims, res_out_dims up to 1024";
+    return nullptr;
+}
+
 extern "C" {
 
 int32_t wrnn_abi_version(void) { return WRNN_ABI_VERSION; }
@@ -105,9 +119,6 @@ int wrnn_create(const wrnn_config *cfg, wrnn_handle **out) {
     wrnn_handle *h = new wrnn_handle();
     h->cfg = *cfg;
     WrnnDims &d = h->d;
-    d.H = cfg->rnn_dims; d.FC = cfg->fc_dims; d.F = cfg->feat_dims; d.C = cfg->compute_dims;
-    d.R = cfg->res_out_dims; d.A = cfg->res_out_dims / 4; d.NBLK = cfg->res_blocks; d.P = cfg->pad;
-    d.KS = 2 * cfg->pad + 1; d.mode = cfg->mode;
     int hop = 1, reach = 0;
     if (cfg->n_upsample < 1 || cfg->n_upsample > WRNN_MAX_UP) { delete h; return WRNN_ERR_INVALID; }
     for (int i = 0; i < cfg->n_upsample; ++i) hop *= cfg->upsample_factors[i];
@@ -115,19 +126,11 @@ int wrnn_create(const wrnn_config *cfg, wrnn_handle **out) {
         int later = hop;
         for (int i = 0; i < cfg->n_upsample; ++i) { later /= cfg->upsample_factors[i]; reach += cfg->upsample_factors[i] * later; }
     }
-    d.HOP = hop;
-    d.ND = 2 * cfg->pad + 1;
-    if (cfg->mode == WRNN_MODE_RAW) d.NC = 1 << cfg->bits;       // fatchord_version.py:98-99
-    else if (cfg->mode == WRNN_MODE_MOL) d.NC = 30;             // :100-101
-    else { delete h; return WRNN_ERR_INVALID; }
+    if (cfg->mode != WRNN_MODE_RAW && cfg->mode != WRNN_MODE_MOL) { delete h; return WRNN_ERR_INVALID; }
     *out = h;  // from here on errors are reported through the handle
     // Any constructor dims (fatchord_version.py:93-129) run on the SIMPLE kernel as long as its activation vectors fit a
     // CU's LDS; the team kernels (TEAM2, BATCH) are built for the reference hparams (wavernn_hparams.py:18-57).
-    if (d.H < 1 || d.FC < 1 || d.F < 1 || d.C < 1 || d.R < 4 || d.NBLK < 0 || d.P < 0 || cfg->bits < 1 || cfg->bits > 16)
-        return wrnn_fail(h, WRNN_ERR_INVALID, "bad dims");
-    if (cfg->res_out_dims % 4 != 0) return wrnn_fail(h, WRNN_ERR_INVALID, "res_out_dims must be a multiple of 4 (aux split, :109)");
-    if (d.H > 1024 || d.C > 1024 || d.R > 1024)
-        return wrnn_fail(h, WRNN_ERR_INVALID, "unsupported dims: rnn_dims, compute_dims, res_out_dims up to 1024");
+    if (const char *why = wrnn_dims_from_config(cfg, d)) return wrnn_fail(h, WRNN_ERR_INVALID, "%s", why);
     h->team_dims = d.H == 512 && d.FC == 512 && d.F == 80 && d.R == 128 && d.C == 128 && d.A == 32;
     if (hop != cfg->hop_length) return wrnn_fail(h, WRNN_ERR_INVALID, "prod(upsample_factors)=%d != hop_length=%d", hop, cfg->hop_length);
     if (reach > cfg->pad * hop || d.ND > WRNN_KTAB_MAXD)
@@ -449,7 +452,7 @@ int wrnn_load_weights(wrnn_handle *h, const wrnn_tensor_desc *tensors, int32_t n
     WRNN_HIP_TRY(h, hipSetDevice(h->cfg.device));
     if (!h->mail) {
         WRNN_HIP_TRY(h, hipMalloc(&h->mail, WRNN_MAIL_BYTES));
-        WRNN_HIP_TRY(h, hipMalloc(&h->ctl, 128));
+        WRNN_HIP_TRY(h, hipMalloc(&h->ctl, TEAM_CTL_WORDS * sizeof(unsigned)));
     }
     if (h->wdev) { (void)hipFree(h->wdev); h->wdev = nullptr; }
     WRNN_HIP_TRY(h, hipMalloc(&h->wdev, o.total * sizeof(float)));
@@ -543,7 +546,7 @@ static int run_batch(wrnn_handle *h, const WrnnLoopArgs &a, const WrnnFrameTable
     ba.mail = h->mail; ba.ctl = h->ctl; ba.err = a.err; ba.prof = h->prof_on ? h->prof : nullptr;
     if (ba.prof) WRNN_HIP_TRY(h, hipMemsetAsync(h->prof, 0, 8 * WRNN_PROF_SLOTS * sizeof(unsigned long long), s));
     WRNN_HIP_TRY(h, hipEventRecord(h->ev[1], s));  // tables and records are prologue work
-    WRNN_HIP_TRY(h, wrnn_gated_launch(h->cfg.device, s, h->mail, WRNN_MAIL_BYTES, h->ctl, 128,
+    WRNN_HIP_TRY(h, wrnn_gated_launch(h->cfg.device, s, h->mail, WRNN_MAIL_BYTES, h->ctl, TEAM_CTL_WORDS * sizeof(unsigned),
                                       [&] { return cs ? wrnn_launch_loop_batch_cs(ba, s) : wrnn_launch_loop_batch(ba, s); }));
     h->prof_div = (double)a.steps * ((((rows + rpb - 1) / rpb) + h->n_teams - 1) / h->n_teams);
     return WRNN_OK;
@@ -596,7 +599,7 @@ static int run_teamg(wrnn_handle *h, const WrnnLoopArgs &a, int snake, int n_slo
     ga.a = a; ga.img = h->teamg_img; ga.sched = h->sched_dev; ga.n_slots = n_slots; ga.ragged = snake; ga.n_teams = h->n_teams;
     ga.mail = h->mail; ga.ctl = h->ctl;
     const size_t mail_bytes = (size_t)h->n_teams * ga.plan.mail_granules * sizeof(unsigned long long);   // sized from the dims; <= WRNN_MAIL_BYTES
-    WRNN_HIP_TRY(h, wrnn_gated_launch(h->cfg.device, s, h->mail, mail_bytes, h->ctl, 128, [&] { return wrnn_launch_loop_teamg(ga, s); }));
+    WRNN_HIP_TRY(h, wrnn_gated_launch(h->cfg.device, s, h->mail, mail_bytes, h->ctl, TEAM_CTL_WORDS * sizeof(unsigned), [&] { return wrnn_launch_loop_teamg(ga, s); }));
     return WRNN_OK;
 }
 

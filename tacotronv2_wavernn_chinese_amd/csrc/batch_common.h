@@ -1,15 +1,12 @@
-// Building blocks of the batch kernel (loop_batch.hip): team / mailbox primitives, the
+// Building blocks of the batch kernel (loop_batch.hip): the 16-byte gather on top of the team protocol (team_common.h), the
 // v_mfma_f32_4x4x1 loops with hand-made software pipelining, the K-phase fold, the LDS carve-up.  See loop_batch.hip for the
 // mapping these pieces implement.
 #pragma once
-#include "device_util.h"
-#include "wrnn_internal.h"
+#include "team_common.h"
 
-#define TB_WGS 32
 #define TB_THREADS 256
 #define TB_SPIN_MAX 400000u
 
-typedef unsigned long long u64;
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef unsigned u4v __attribute__((ext_vector_type(4)));
 typedef unsigned u2v __attribute__((ext_vector_type(2)));
@@ -25,16 +22,6 @@ __device__ __forceinline__ unsigned launder(unsigned v) { asm volatile("" : "+v"
 
 namespace {
 
-__device__ __forceinline__ unsigned xcc_idb() {
-    unsigned v;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
-    return v & 0xf;
-}
-__device__ __forceinline__ void st_granule(u64 *base, unsigned idx, unsigned tag, unsigned payload) {
-    const u64 v = ((u64)tag << 32) | payload;
-    const unsigned off = idx * 8u;
-    asm volatile("global_store_dwordx2 %0, %1, %2" ::"v"(off), "v"(v), "s"(base) : "memory");
-}
 // 16-byte sc1 load (L1 bypass) of two adjacent granules; compiler-tracked (s_waitcnt vmcnt inserted by hipcc).  The per-thread
 // part of the address (tid * 16) is the VGPR offset, everything wave-uniform (region, parity, slice) goes into the SGPR offset:
 // the instruction's immediate offset has 12 bits, so slice offsets folded into the VGPR cost one register per slice.
@@ -53,10 +40,6 @@ __device__ __forceinline__ float aget(const float &a) { return a; }
 template <bool AG>
 __device__ __forceinline__ float wget(const float &w) { return AG ? aget(w) : w; }
 
-template <int CTRL>
-__device__ __forceinline__ float dppf(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
 // fold the 16 K phases: in d[i] lane (kp, j) = partial of unit i, batch row j; out: lane (rho = lane>>4, *, j) = full sum
 // of unit {0, 2, 1, 3}[rho] for batch row j, replicated over the 4 lanes-of-four of the row
 __device__ __forceinline__ float fold_kp(f4 d) {
@@ -70,26 +53,6 @@ __device__ __forceinline__ float fold_kp(f4 d) {
     t += dppf<0x128>(t);   // row_ror:8
     return t;
 }
-__device__ __forceinline__ float wave_max_b(float v) {   // max over 64 lanes, valid in lane 63 (see loop_team2.hip)
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-        "s_nop 1"
-        : "+v"(v));
-    return v;
-}
-__device__ __forceinline__ float sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float tanh_fast(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * x) + 1.0f); }
 
 // ---- LDS carve-up (floats) -----------------------------------------------------------------------------------------
 template <int NQ>
@@ -120,7 +83,6 @@ struct Lay {
 };
 // slots of L_CST
 constexpr int C_A0 = 0, C_A1 = 1, C_A2 = 2, C_A3 = 3, C_B30 = 4, C_B31 = 5, C_H1R = 6, C_H1Z = 7, C_H1N = 8, C_H2R = 9, C_H2Z = 10, C_H2N = 11;
-constexpr int M_DEAD = 0, M_TEAM = 1, M_RANK = 2;
 
 // RAW sampler keys of a team batch (both batch kernels).  A thread draws for its OWN batch row rb = lane-dependent, so the key cannot
 // sit in scalar registers, and as three more VGPRs (plus the ten round keys the compiler then hoists out of the step loop) it pushed

@@ -22,7 +22,7 @@ struct WrnnDmTeamArgs {
     const float *team_w;          // [32 WGs][3 * H/16 registers][512 threads]   R rows of the thread's hidden unit
     const float *team_lds;        // [32 WGs][O1 U*S | O3 U*S | O2 QW*S | O4 QW*S]  LDS images (quarter-wave row, plane, lane)
     unsigned long long *mail;     // [WRNN_DM_MAIL_GRANULES]
-    unsigned *ctl;                // [32] team formation counters
+    unsigned *ctl;                // [TEAM_CTL_WORDS] team formation (team_common.h)
     unsigned *err;                // device error word
 };
 bool wrnn_dm_team_supported(int H, int Q);

@@ -3,7 +3,7 @@
 #include <cstdarg>
 #include <cstdio>
 
-#include "wrnn_internal.h"
+#include "team_common.h"
 
 int wrnn_fail(wrnn_handle *h, int code, const char *fmt, ...) {
     char buf[512];
@@ -57,7 +57,7 @@ int wrnn_run_team2_segments(wrnn_handle *h, WrnnTeamArgs &ta, float *cond, int64
         const int64_t len = t_end - t0 < seg ? t_end - t0 : seg;
         WRNN_HIP_TRY(h, wrnn_launch_cond_stream(ta.tabREC, ta.w + ta.off.ktab, ta.rows, cond, ta.n_rows, ta.T, ta.d.HOP, ta.total_len, t0, len, s));
         ta.seg0 = t0; ta.seg_len = len;
-        WRNN_HIP_TRY(h, wrnn_gated_launch(h->cfg.device, s, h->mail, WRNN_MAIL_BYTES, h->ctl, 128, [&] { return wrnn_launch_loop_team2(ta, s); }));
+        WRNN_HIP_TRY(h, wrnn_gated_launch(h->cfg.device, s, h->mail, WRNN_MAIL_BYTES, h->ctl, TEAM_CTL_WORDS * sizeof(unsigned), [&] { return wrnn_launch_loop_team2(ta, s); }));
     }
     if (launches) *launches = n;
     return WRNN_OK;

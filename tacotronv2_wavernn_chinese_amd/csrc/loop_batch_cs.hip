@@ -283,39 +283,10 @@ __global__ void __launch_bounds__(CS_THREADS) loop_batch_cs_kernel(WrnnBatchArgs
     const WrnnDims d = a.d;
     const int NC = d.NC, HOP = d.HOP, T = a.T;
 
-    // ---- team formation (loop_batch.hip) ------------
-    if (tid == 0) {
-        const unsigned x = xcc_idb();
-        misc_i[M_DEAD] = 0;
-        const unsigned rank = atomicAdd(&a.ctl[x], 1u);
-        unsigned slot1 = 0;
-        if (rank == 0) {
-            slot1 = atomicAdd(&a.ctl[8], 1u) + 1u;
-            __hip_atomic_store(&a.ctl[16 + x], slot1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            for (unsigned spins = 0; spins < 4000000u; ++spins) {
-                slot1 = __hip_atomic_load(&a.ctl[16 + x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (slot1) break;
-            }
-        }
-        if (slot1 && rank < TB_WGS) {
-            unsigned arrived = 0;
-            for (unsigned spins = 0; spins < WRNN_ARRIVE_POLLS; ++spins) {
-                arrived = __hip_atomic_load(&a.ctl[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (arrived >= TB_WGS) break;
-                __builtin_amdgcn_s_sleep(8);
-            }
-            if (arrived < TB_WGS) { atomicCAS(a.err, 0u, WRNN_DEVERR_BUSY); slot1 = 0; }
-        }
-        misc_i[M_TEAM] = slot1 ? (int)slot1 - 1 : 1 << 20;
-        misc_i[M_RANK] = (int)rank;
-    }
-    __syncthreads();
-    const int team = __builtin_amdgcn_readfirstlane(misc_i[M_TEAM]);
-    const int g = __builtin_amdgcn_readfirstlane(misc_i[M_RANK]);
-    __syncthreads();
+    // ---- team formation (team_common.h; why this kernel keeps the two-loop form is said there) ------------
+    JOIN_TEAM_TWO_LOOP(a, misc_i, tid, team, g);
     const int n_batches = (a.n_rows + a.rpb - 1) / a.rpb;
-    if (g >= TB_WGS || team >= a.n_teams || team >= n_batches) return;
+    if (g >= TEAM_WGS || team >= a.n_teams || team >= n_batches) return;
     u64 *mail = a.mail + (size_t)team * WRNN_BATCH_MAIL_GRANULES;
     const __amdgpu_buffer_rsrc_t mrs = __builtin_amdgcn_make_buffer_rsrc((void *)mail, 0, (int)(WRNN_BATCH_MAIL_GRANULES * 8u), 0x00020000);
 
@@ -712,7 +683,7 @@ __global__ void __launch_bounds__(CS_THREADS) loop_batch_cs_kernel(WrnnBatchArgs
                         const bool pb = vb > va;
                         const float best = pb ? vb : va;
                         const int besti = (int)((pb ? gq.w : gq.y) & 1023u);
-                        const float mx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_max_b(best)), 63));
+                        const float mx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_max(best)), 63));
                         const u64 ball = __ballot(best == mx);
                         const int src = (int)__builtin_ctzll(ball ? ball : 1ull);
                         lab = __builtin_amdgcn_readlane(besti, src);
@@ -724,7 +695,7 @@ __global__ void __launch_bounds__(CS_THREADS) loop_batch_cs_kernel(WrnnBatchArgs
                         const float nzv = lane <= nr ? molnz[((int)par * R + brow) * 16 + lane] : 0.0f;
                         const float mylg = lgt[brow * 32 + (lane < NC ? lane : 0)];
                         const float v = lane < nr ? mylg + nzv : -INFINITY;
-                        const float mx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_max_b(v)), 63));
+                        const float mx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_max(v)), 63));
                         const u64 ball = __ballot(v == mx);
                         const int km = (int)__builtin_ctzll(ball ? ball : 1ull);
                         const float mean = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mylg), nr + km));
@@ -1013,7 +984,7 @@ __global__ void __launch_bounds__(CS_THREADS) loop_batch_cs_kernel(WrnnBatchArgs
                     const bool pb = vb > va;   // equal scores: the lower slot = the lower class range wins
                     const float best = pb ? vb : va;
                     const int besti = (int)((pb ? gq.w : gq.y) & 1023u);
-                    const float mx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_max_b(best)), 63));
+                    const float mx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_max(best)), 63));
                     const u64 ball = __ballot(best == mx);
                     const int src = (int)__builtin_ctzll(ball ? ball : 1ull);
                     const int lab = __builtin_amdgcn_readlane(besti, src);
@@ -1049,11 +1020,11 @@ static hipError_t launch_cs(const WrnnBatchArgs &a, hipStream_t s) {
     if (a.prof) {
         e = hipFuncSetAttribute((const void *)loop_batch_cs_kernel<MODE, NQ, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((loop_batch_cs_kernel<MODE, NQ, true>), dim3(a.n_teams * TB_WGS), dim3(CS_THREADS), lds, s, a);
+        hipLaunchKernelGGL((loop_batch_cs_kernel<MODE, NQ, true>), dim3(a.n_teams * TEAM_WGS), dim3(CS_THREADS), lds, s, a);
     } else {
         e = hipFuncSetAttribute((const void *)loop_batch_cs_kernel<MODE, NQ, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((loop_batch_cs_kernel<MODE, NQ, false>), dim3(a.n_teams * TB_WGS), dim3(CS_THREADS), lds, s, a);
+        hipLaunchKernelGGL((loop_batch_cs_kernel<MODE, NQ, false>), dim3(a.n_teams * TEAM_WGS), dim3(CS_THREADS), lds, s, a);
     }
     return hipGetLastError();
 }

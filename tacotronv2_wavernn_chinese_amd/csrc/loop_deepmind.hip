@@ -2,8 +2,7 @@
 // wavernn/models/deepmind_version.py, generate(seq_len) :75-165.  No reference script ever imports that model, so
 // this is a straightforward, reference-ordered kernel (one persistent workgroup, weights streamed [in][out] from
 // L2 each step) with the same sampler as the main path: Categorical(softmax(l)).sample() == argmax_k l_k - log q_k.
-#include "device_util.h"
-#include "wrnn_internal.h"
+#include "team_common.h"
 
 #define DM_THREADS 1024
 
@@ -122,7 +121,7 @@ struct wrnn_dm_handle {
     int kernel = 0;               // 0 auto (team kernel when the sizes allow), 1 single-workgroup kernel, 2 team kernel
     float *team_w = nullptr, *team_lds = nullptr;
     unsigned long long *mail = nullptr;
-    unsigned *ctl = nullptr;      // [32] team counters + [32] error word
+    unsigned *ctl = nullptr;      // [TEAM_CTL_WORDS] team formation + [TEAM_CTL_WORDS] of which the first is the error word
     std::string err;
 };
 
@@ -258,7 +257,7 @@ int wrnn_dm_load_weights(wrnn_dm_handle *h, const wrnn_tensor_desc *tensors, int
         if ((rc = upload(h->team_w, tw)) || (rc = upload(h->team_lds, tl))) return rc;
         if (!h->mail) {
             DM_TRY(h, hipMalloc(&h->mail, (size_t)WRNN_DM_MAIL_GRANULES * sizeof(unsigned long long)));
-            DM_TRY(h, hipMalloc(&h->ctl, 256));
+            DM_TRY(h, hipMalloc(&h->ctl, 2 * TEAM_CTL_WORDS * sizeof(unsigned)));
         }
     }
     h->loaded = true;
@@ -290,9 +289,9 @@ int wrnn_dm_generate(wrnn_dm_handle *h, int64_t seq_len, int32_t noise_mode, uin
     if (team) {
         hipStream_t s = (hipStream_t)stream;
         DM_TRY(h, hipMemsetAsync(h->mail, 0, (size_t)WRNN_DM_MAIL_GRANULES * sizeof(unsigned long long), s));
-        DM_TRY(h, hipMemsetAsync(h->ctl, 0, 256, s));
+        DM_TRY(h, hipMemsetAsync(h->ctl, 0, 2 * TEAM_CTL_WORDS * sizeof(unsigned), s));
         WrnnDmTeamArgs ta{};
-        ta.base = a; ta.team_w = h->team_w; ta.team_lds = h->team_lds; ta.mail = h->mail; ta.ctl = h->ctl; ta.err = h->ctl + 32;
+        ta.base = a; ta.team_w = h->team_w; ta.team_lds = h->team_lds; ta.mail = h->mail; ta.ctl = h->ctl; ta.err = h->ctl + TEAM_CTL_WORDS;
         // team kernels of one device are ordered behind each other, whatever handle / stream launches them (wavernn_amd.h)
         DM_TRY(h, wrnn_team_gate_enter(h->device, s));
         const hipError_t le = wrnn_launch_dm_team(ta, s);
@@ -314,7 +313,7 @@ int wrnn_dm_sync_status(wrnn_dm_handle *h, void *stream) {
     DM_TRY(h, hipStreamSynchronize((hipStream_t)stream));
     if (!h->ctl) return WRNN_OK;
     unsigned errw = 0;
-    DM_TRY(h, hipMemcpy(&errw, h->ctl + 32, sizeof(errw), hipMemcpyDeviceToHost));
+    DM_TRY(h, hipMemcpy(&errw, h->ctl + TEAM_CTL_WORDS, sizeof(errw), hipMemcpyDeviceToHost));
     if (errw == WRNN_DEVERR_BUSY)
         return dm_fail(h, WRNN_ERR_BUSY, "the team kernel's 32 workgroups did not all become resident: the GPU is shared with another kernel (retry, or wrnn_dm_set_kernel(h, 1))");
     if (errw) return dm_fail(h, WRNN_ERR_TIMEOUT, "device-side bounded spin gave up (code %u)", errw);

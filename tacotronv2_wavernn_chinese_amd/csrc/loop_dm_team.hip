@@ -1,5 +1,5 @@
 // Team kernel for the dual-softmax (coarse/fine) WaveRNN of wavernn/models/deepmind_version.py, generate() :75-165
-// (SURVEY.md section 8a row A12).  Same machinery as loop_team2.hip: one team = the 32 workgroups of one XCD, fp32
+// (SURVEY.md section 8a row A12).  The team protocol is team_common.h's: one team = the 32 workgroups of one XCD, fp32
 // weights resident on chip, 8-byte {tag,value} granules exchanged through the XCD's L2, double-buffered by sample
 // parity.  One sample = 6 exchanges:
 //
@@ -12,73 +12,12 @@
 // H/16 per lane) live in VGPRs; the O slices live in LDS.  R(hidden) is evaluated once per sample with the hidden
 // state of the previous sample, for both halves (:116-119), so the fine rows wait in registers until coarse is known.
 // Sampling: Categorical(softmax(l)).sample() == argmax_k l_k - log q_k, q ~ Exp(1)  (as on the main path).
-#include "device_util.h"
 #include "dm_internal.h"
-#include "wrnn_internal.h"
+#include "team_common.h"
 
 #define DMT_THREADS 512
-#define DMT_SPIN_MAX 300000u
-
-typedef unsigned long long u64;
 
 namespace {
-
-__device__ __forceinline__ unsigned dmt_xcc_id() {
-    unsigned v;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
-    return v & 0xf;
-}
-__device__ __forceinline__ void dmt_st(u64 *base, unsigned idx, unsigned tag, float payload) {
-    const u64 v = ((u64)tag << 32) | __float_as_uint(payload);
-    const unsigned off = idx * 8u;
-    asm volatile("global_store_dwordx2 %0, %1, %2" ::"v"(off), "v"(v), "s"(base) : "memory");
-}
-__device__ __forceinline__ u64 dmt_peek(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// one granule per lane; wave-uniform completion; two staggered first looks (see loop_team2.hip)
-__device__ __forceinline__ float dmt_take(const u64 *base, unsigned idx, unsigned tag, bool &dead, unsigned *err, unsigned code) {
-    u64 ga = dmt_peek(base + idx);
-    __builtin_amdgcn_s_sleep(3);
-    u64 gb = dmt_peek(base + idx);
-    if (__all((unsigned)(ga >> 32) == tag)) return __uint_as_float((unsigned)ga);
-    unsigned spins = 0;
-    while (!dead && !__all((unsigned)(gb >> 32) == tag)) {
-        if (++spins > DMT_SPIN_MAX) { dead = true; if ((threadIdx.x & 63) == 0) atomicExch(err, code); break; }
-        gb = dmt_peek(base + idx);
-    }
-    return __uint_as_float((unsigned)gb);
-}
-template <int CTRL>
-__device__ __forceinline__ float dmt_dpp(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float dmt_row_sum(float v) {   // sum over the 16 lanes of a DPP row, in every lane
-    v += dmt_dpp<0xB1>(v);
-    v += dmt_dpp<0x4E>(v);
-    v += dmt_dpp<0x141>(v);
-    v += dmt_dpp<0x140>(v);
-    return v;
-}
-__device__ __forceinline__ float dmt_wave_max(float v) {   // max over 64 lanes, valid in lane 63
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-        "s_nop 1"
-        : "+v"(v));
-    return v;
-}
-
-__device__ __forceinline__ float dmt_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float dmt_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * x) + 1.0f); }
 
 constexpr unsigned G_HC = 0, G_T1C = 1024, G_HF = 2048, G_T1F = 3072, G_C = 4096, G_F = 4608;   // x2 parities each
 
@@ -101,46 +40,16 @@ __global__ void __launch_bounds__(DMT_THREADS, 2) dm_team_kernel(WrnnDmTeamArgs 
     float *hcS = hR + 2 * H;          // [S] new coarse half in S-chunk order (input of O1)
     float *hfS = hcS + S;             // [S] new fine half (input of O3)
     float *t1 = hfS + S;              // [S] relu(O1 / O3 output) (input of O2 / O4)
-    float *misc = t1 + S;             // [128]: 0-2 team/rank/bail-out, 16-23 race partials, 32-95 sampling noise [parity][coarse 16 | fine 16]
+    float *misc = t1 + S;             // [128]: 0-2 team/rank/bail-out (team_common.h), 16-23 race partials, 32-95 sampling noise [parity][coarse 16 | fine 16]
     int *misc_i = (int *)misc;
     float *imgO1 = misc + 128, *imgO3 = imgO1 + U * S, *imgO2 = imgO3 + U * S, *imgO4 = imgO2 + QW * S;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int qw = tid >> 4, q = tid & 15;
 
-    // ---- team formation (as loop_team2.hip): the first XCD to arrive is the team ----
-    if (tid == 0) {
-        const unsigned x = dmt_xcc_id();
-        const unsigned rank = atomicAdd(&ta.ctl[x], 1u);
-        unsigned slot1 = 0;
-        if (rank == 0) {
-            slot1 = atomicAdd(&ta.ctl[8], 1u) + 1u;
-            __hip_atomic_store(&ta.ctl[16 + x], slot1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            for (unsigned spins = 0; spins < 4000000u; ++spins) {
-                slot1 = __hip_atomic_load(&ta.ctl[16 + x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (slot1) break;
-            }
-        }
-        // co-residency checked, not assumed (see loop_team2.hip): the 32 workgroups of the team's XCD must all have arrived
-        if (slot1 == 1u && rank < 32u) {
-            unsigned arrived = 0;
-            for (unsigned spins = 0; spins < WRNN_ARRIVE_POLLS; ++spins) {
-                arrived = __hip_atomic_load(&ta.ctl[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (arrived >= 32u) break;
-                __builtin_amdgcn_s_sleep(8);
-            }
-            if (arrived < 32u) { atomicCAS(ta.err, 0u, WRNN_DEVERR_BUSY); slot1 = 0; }
-        }
-        misc_i[0] = slot1 ? (int)slot1 - 1 : 1 << 20;
-        misc_i[1] = (int)rank;
-        misc_i[2] = 0;   // bail-out flag
-    }
-    __syncthreads();
-    const int team = __builtin_amdgcn_readfirstlane(misc_i[0]);
-    const int g = __builtin_amdgcn_readfirstlane(misc_i[1]);
-    __syncthreads();
-    if (team != 0 || g >= 32) return;
+    // ---- team formation (team_common.h): the grid covers every XCD, the first XCD to arrive is the team, the others leave at once ----
+    int team, g;
+    if (!join_team<true>(ta.ctl, ta.err, misc_i, 1, team, g) || team != 0) return;
     u64 *mail = ta.mail;
     const float *w = a.w;
 
@@ -205,13 +114,13 @@ __global__ void __launch_bounds__(DMT_THREADS, 2) dm_team_kernel(WrnnDmTeamArgs 
             s0 = fmaf(ww.x, xx.x, s0); s1 = fmaf(ww.y, xx.y, s1);
             s0 = fmaf(ww.z, xx.z, s0); s1 = fmaf(ww.w, xx.w, s1);
         }
-        return dmt_row_sum(s0 + s1);
+        return row_sum(s0 + s1);
     };
     // argmax over the Q published class values (one granule per thread of the first Q/64 waves), ties -> lowest index
     auto race = [&](unsigned region, unsigned par, unsigned epoch, bool &dead) -> int {
         if (wave < Q / 64) {
-            const float v = dmt_take(mail, region + par * 256 + tid, epoch, dead, ta.err, 21u);
-            const float mx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dmt_wave_max(v)), 63));
+            const float v = take_staggered(mail, region + par * 256 + tid, epoch, dead, ta.err, 21u);
+            const float mx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_max(v)), 63));
             const u64 ball = __ballot(v == mx);
             const int src = (int)__builtin_ctzll(ball ? ball : 1ull);
             if (lane == 0) { misc[16 + 2 * wave] = mx; misc_i[17 + 2 * wave] = wave * 64 + src; }
@@ -242,7 +151,7 @@ __global__ void __launch_bounds__(DMT_THREADS, 2) dm_team_kernel(WrnnDmTeamArgs 
             b0 = fmaf(wR[CPL * 4 + 4 * k + 2], x.z, b0); b1 = fmaf(wR[CPL * 4 + 4 * k + 3], x.w, b1);
             c0 = fmaf(wR[CPL * 8 + 4 * k + 2], x.z, c0); c1 = fmaf(wR[CPL * 8 + 4 * k + 3], x.w, c1);
         }
-        ru = dmt_row_sum(a0 + a1); rr = dmt_row_sum(b0 + b1); re = dmt_row_sum(c0 + c1);
+        ru = row_sum(a0 + a1); rr = row_sum(b0 + b1); re = row_sum(c0 + c1);
     };
 
     bool dead = false;
@@ -259,15 +168,15 @@ __global__ void __launch_bounds__(DMT_THREADS, 2) dm_team_kernel(WrnnDmTeamArgs 
         // ---- coarse gates :111-125 ----
         if (isCq) {
             const float Iu = iw[0] * pc + iw[1] * pf, Ir = iw[3] * pc + iw[4] * pf, Ie = iw[6] * pc + iw[7] * pf;
-            const float u = dmt_sigmoid(ru + Iu + bu);
-            const float r = dmt_sigmoid(rr + Ir + br);
-            const float e = dmt_tanh(r * re + Ie + be);
+            const float u = sigmoid_fast(ru + Iu + bu);
+            const float r = sigmoid_fast(rr + Ir + br);
+            const float e = tanh_fast(r * re + Ie + be);
             hown = u * hown + (1.0f - u) * e;
-            if (q == 0) dmt_st(mail, G_HC + par * 512 + hi, epoch, hown);
+            if (q == 0) st_granule(mail, G_HC + par * 512 + hi, epoch, __float_as_uint(hown));
         }
         // ---- exchange 1: new coarse half ----
         if (wave < S / 64) {
-            const float v = dmt_take(mail, G_HC + par * 512 + tid, epoch, dead, ta.err, 11u);
+            const float v = take_staggered(mail, G_HC + par * 512 + tid, epoch, dead, ta.err, 11u);
             hout[chunk_idx<CPL>(tid)] = v;
             hcS[chunk_idx<PS>(tid)] = v;
         }
@@ -275,13 +184,13 @@ __global__ void __launch_bounds__(DMT_THREADS, 2) dm_team_kernel(WrnnDmTeamArgs 
         // ---- out_coarse = O2(relu(O1(hidden_coarse))) :128 ----
         if (isCq) {
             const float s = dotS(imgO1, qw, hcS) + bO1;
-            if (q == 0) dmt_st(mail, G_T1C + par * 512 + orow, epoch, fmaxf(s, 0.0f));
+            if (q == 0) st_granule(mail, G_T1C + par * 512 + orow, epoch, __float_as_uint(fmaxf(s, 0.0f)));
         }
-        if (wave < S / 64) t1[chunk_idx<PS>(tid)] = dmt_take(mail, G_T1C + par * 512 + tid, epoch, dead, ta.err, 12u);
+        if (wave < S / 64) t1[chunk_idx<PS>(tid)] = take_staggered(mail, G_T1C + par * 512 + tid, epoch, dead, ta.err, 12u);
         __syncthreads();
         if (qw < QW) {
             const float s = dotS(imgO2, qw, t1) + bO2 + misc[32 + 32 * par + qw];
-            if (q == 0) dmt_st(mail, G_C + par * 256 + cls, epoch, s);
+            if (q == 0) st_granule(mail, G_C + par * 256 + cls, epoch, __float_as_uint(s));
         }
         oc = race(G_C, par, epoch, dead);                                   // Categorical(...).sample() :130-131
         if (g == 0 && tid == 0) a.coarse[t] = oc;
@@ -291,14 +200,14 @@ __global__ void __launch_bounds__(DMT_THREADS, 2) dm_team_kernel(WrnnDmTeamArgs 
             const float Iu = iw[0] * pc + iw[1] * pf + iw[2] * cp;
             const float Ir = iw[3] * pc + iw[4] * pf + iw[5] * cp;
             const float Ie = iw[6] * pc + iw[7] * pf + iw[8] * cp;
-            const float u = dmt_sigmoid(ru + Iu + bu);
-            const float r = dmt_sigmoid(rr + Ir + br);
-            const float e = dmt_tanh(r * re + Ie + be);
+            const float u = sigmoid_fast(ru + Iu + bu);
+            const float r = sigmoid_fast(rr + Ir + br);
+            const float e = tanh_fast(r * re + Ie + be);
             hown = u * hown + (1.0f - u) * e;
-            if (q == 0) dmt_st(mail, G_HF + par * 512 + (hi - S), epoch, hown);
+            if (q == 0) st_granule(mail, G_HF + par * 512 + (hi - S), epoch, __float_as_uint(hown));
         }
         if (wave < S / 64) {
-            const float v = dmt_take(mail, G_HF + par * 512 + tid, epoch, dead, ta.err, 13u);
+            const float v = take_staggered(mail, G_HF + par * 512 + tid, epoch, dead, ta.err, 13u);
             hout[chunk_idx<CPL>(S + tid)] = v;
             hfS[chunk_idx<PS>(tid)] = v;
         }
@@ -307,21 +216,21 @@ __global__ void __launch_bounds__(DMT_THREADS, 2) dm_team_kernel(WrnnDmTeamArgs 
         // ---- out_fine = O4(relu(O3(hidden_fine))) :148 ----
         if (isCq) {
             const float s = dotS(imgO3, qw, hfS) + bO3;
-            if (q == 0) dmt_st(mail, G_T1F + par * 512 + orow, epoch, fmaxf(s, 0.0f));
+            if (q == 0) st_granule(mail, G_T1F + par * 512 + orow, epoch, __float_as_uint(fmaxf(s, 0.0f)));
             r_rows(hout);         // under the t1 exchange
         }
-        if (wave < S / 64) t1[chunk_idx<PS>(tid)] = dmt_take(mail, G_T1F + par * 512 + tid, epoch, dead, ta.err, 14u);
+        if (wave < S / 64) t1[chunk_idx<PS>(tid)] = take_staggered(mail, G_T1F + par * 512 + tid, epoch, dead, ta.err, 14u);
         __syncthreads();
         if (qw < QW) {
             const float s = dotS(imgO4, qw, t1) + bO4 + misc[32 + 32 * par + 16 + qw];
-            if (q == 0) dmt_st(mail, G_F + par * 256 + cls, epoch, s);
+            if (q == 0) st_granule(mail, G_F + par * 256 + cls, epoch, __float_as_uint(s));
         }
         of = race(G_F, par, epoch, dead);                                   // :150-151
         if (g == 0 && tid == 0) a.fine[t] = of;
         if ((t & 63) == 63) {   // bounded-spin bail-out, checked workgroup-wide every 64 samples
-            if (dead && lane == 0) misc_i[2] = 1;
+            if (dead && lane == 0) misc_i[M_DEAD] = 1;
             __syncthreads();
-            if (misc_i[2]) return;
+            if (misc_i[M_DEAD]) return;
         }
     }
 }

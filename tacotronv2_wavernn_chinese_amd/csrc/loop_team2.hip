@@ -1,6 +1,6 @@
 // WRNN_KERNEL_TEAM2: the per-sample loop (fatchord_version.py:194-241) with WAVE SPECIALISATION.
 //
-// Team structure and exchange protocol (one team = the 32 workgroups of one XCD,
+// Team structure and exchange protocol are team_common.h's (one team = the 32 workgroups of one XCD,
 // fp32 weights resident on chip, 8-byte {tag,value} granules through the XCD's L2, 4 exchanges on the critical
 // path + 1 off it, 5 workgroup barriers per step).  What changes is who does what inside a workgroup.
 //
@@ -24,29 +24,12 @@
 //
 // Thread map inside a role (wl = wave & 3, lane l: quarter r4 = l>>4, q = l&15): quarter-wave (wl, r4) owns hidden
 // unit / fc row u = 16 g + 4 wl + r4 and columns 32q..32q+31 of every row it owns.
-#include "device_util.h"
-#include "wrnn_internal.h"
+#include "team_common.h"
 
-#define T2_WGS 32
 #define T2_THREADS 512
-#define T2_SPIN_MAX 300000u
-
-typedef unsigned long long u64;
 
 namespace {
 
-__device__ __forceinline__ unsigned xcc_id2() {
-    unsigned v;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
-    return v & 0xf;
-}
-
-// 8-byte granule {tag (hi), payload (lo)}: plain store (-> the XCD's L2), sc1 load (bypasses L1).  Same-XCD only.
-__device__ __forceinline__ void st_granule(u64 *base, unsigned idx, unsigned tag, unsigned payload) {
-    const u64 v = ((u64)tag << 32) | payload;
-    const unsigned off = idx * 8u;
-    asm volatile("global_store_dwordx2 %0, %1, %2" ::"v"(off), "v"(v), "s"(base) : "memory");
-}
 template <int N>
 __device__ __forceinline__ void peek_n(const u64 *base, unsigned idx, unsigned stride, u64 (&g)[N]) {
 #pragma unroll
@@ -65,7 +48,7 @@ __device__ __forceinline__ void finish_n(const u64 *base, unsigned idx, unsigned
                                          unsigned *err, unsigned code) {
     unsigned spins = 0;
     while (!dead && !__all(tags_ok<N, SHIFT>(g, tag))) {
-        if (++spins > T2_SPIN_MAX) { dead = true; if ((threadIdx.x & 63) == 0) atomicExch(err, code); break; }
+        if (++spins > TEAM_SPIN_MAX) { dead = true; if ((threadIdx.x & 63) == 0) atomicExch(err, code); break; }
         peek_n<N>(base, idx, stride, g);
     }
 }
@@ -132,38 +115,6 @@ __device__ __forceinline__ void retire_look(u64 (&gb)[1]) {
 #if T2_LATE_B
     asm volatile("" ::"v"(gb[0]));
 #endif
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_get(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float row_sum(float v) {   // sum over the 16 lanes of a DPP row, result in every lane
-    v += dpp_get<0xB1>(v);
-    v += dpp_get<0x4E>(v);
-    v += dpp_get<0x141>(v);
-    v += dpp_get<0x140>(v);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {   // max over 64 lanes, valid in lane 63
-    // One v_max_f32_dpp per step (the compiler's fmaxf + update_dpp form costs 4 VALU per step: copy, DPP move, two
-    // canonicalising maxes).  s_nop 1 = the two wait states a DPP read of a just-written VGPR needs.
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-        "s_nop 1"
-        : "+v"(v));
-    return v;
 }
 
 __device__ __forceinline__ float rows_max(float v) {   // max over the 4 DPP rows of a wave whose rows are uniform, valid in lane 63
@@ -265,8 +216,6 @@ __device__ __forceinline__ float dot32(const float *w, const float *vec, int q) 
     }
     return (s0.x + s0.y) + (s1.x + s1.y);
 }
-__device__ __forceinline__ float sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float tanh_fast(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * x) + 1.0f); }
 
 // ---- LDS carve-up (floats); per-thread-base + constant families first (16-bit DS offsets) ---------------
 constexpr int L_COND = 0;                      // [512][4]  {cI, v_r, v_z, v_n} of the coming step (HBM stream -> everyone)
@@ -282,7 +231,7 @@ constexpr int L_FC3 = L_SW + 8 * 256 * 4;      // [4 C-waves][2 rows][8 planes][
 constexpr int L_XTAB = L_FC3 + 16384;         // [1024] RAW: the sample value of every class, 2 k / (n_classes - 1) - 1
 constexpr int L_TOTAL = L_XTAB + 1024;
 static_assert(L_TOTAL * 4 <= 163840, "LDS budget");
-constexpr int M_XF = 9, M_DEAD = 10;  // misc slots: fed-back sample, bail-out flag
+constexpr int M_XF = 9;  // misc slot of the fed-back sample (0-2: team_common.h)
 
 constexpr unsigned G_X3 = 0, G_F1 = 1024, G_F2 = 2048, G_PR = 3072, G_GH = 4096;  // mailbox regions (granules)
 
@@ -318,37 +267,9 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
     const int NC = d.NC, HOP = d.HOP, T = a.T;
     const float4 *swl = (const float4 *)(lds + L_SW) + (tid - 256);   // S threads only
 
-    // ---- team formation: by the XCD this workgroup actually runs on ------------
-    if (tid == 0) {
-        // ctl[0..7]: arrivals per physical XCC id; ctl[8]: team slots handed out; ctl[16 + xcc]: slot + 1 of that XCC.
-        // Teams are numbered in order of first arrival, so any set of XCC ids (SPX, or a partition exposing a
-        // subset of the XCDs) maps onto team slots 0..n_teams-1.
-        const unsigned x = xcc_id2();
-        misc_i[M_DEAD] = 0;
-        const unsigned rank = atomicAdd(&a.ctl[x], 1u);
-        unsigned slot1 = 0, arrived = 0;
-        if (rank == 0) {
-            slot1 = atomicAdd(&a.ctl[8], 1u) + 1u;
-            __hip_atomic_store(&a.ctl[16 + x], slot1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        // Co-residency, checked instead of assumed: the 32 workgroups of this XCD spin on each other for the whole launch, so
-        // all of them must be running NOW.  One bounded wait (~0.1 s) for the team slot AND the arrival counter; if the counter
-        // does not fill -- the GPU is shared with another process's kernel -- report WRNN_ERR_BUSY and leave instead of timing
-        // out inside the loop.
-        for (unsigned spins = 0; spins < WRNN_ARRIVE_POLLS; ++spins) {
-            slot1 = __hip_atomic_load(&a.ctl[16 + x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            arrived = __hip_atomic_load(&a.ctl[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (slot1 && arrived >= T2_WGS) break;
-        }
-        if (arrived < T2_WGS) { slot1 = 0; if (rank < T2_WGS) atomicCAS(a.err, 0u, WRNN_DEVERR_BUSY); }
-        misc_i[0] = slot1 ? (int)slot1 - 1 : 1 << 20;   // no slot seen: treated as "not in a team" below
-        misc_i[1] = (int)rank;
-    }
-    __syncthreads();
-    const int team = __builtin_amdgcn_readfirstlane(misc_i[0]);
-    const int g = __builtin_amdgcn_readfirstlane(misc_i[1]);
-    __syncthreads();
-    if (g >= T2_WGS || team >= a.n_teams || team >= a.n_rows) return;
+    // ---- team formation: by the XCD this workgroup actually runs on (team_common.h) ------------
+    int team, g;
+    if (!join_team(a.ctl, a.err, misc_i, a.n_teams, team, g) || team >= a.n_rows) return;
     u64 *mail = a.mail + (size_t)team * WRNN_TEAM_MAIL_GRANULES;
 
     const int unit = 16 * g + 4 * wl + r4;          // hidden unit / fc1 / fc2 row of this quarter-wave
@@ -690,7 +611,7 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
                         const unsigned rtag = epoch & 0x3fffffu;
                         u4 gq = race_load(mail, roff);
                         for (unsigned spins = 0; !dead && !__all(race_ok(gq, rtag));) {
-                            if (++spins > T2_SPIN_MAX) { dead = true; if (lane == 0) atomicExch(a.err, 14u); break; }
+                            if (++spins > TEAM_SPIN_MAX) { dead = true; if (lane == 0) atomicExch(a.err, 14u); break; }
                             gq = race_load(mail, roff);
                         }
                         P2(14);
@@ -722,7 +643,7 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
                             peek_n<1>(mail, G_PR + par * 512 + lane, 1, gq);
                             unsigned spins = 0;
                             while (!dead && (unsigned)(gq[0] >> 32) != epoch) {
-                                if (++spins > T2_SPIN_MAX) { dead = true; atomicExch(a.err, 16u); break; }
+                                if (++spins > TEAM_SPIN_MAX) { dead = true; atomicExch(a.err, 16u); break; }
                                 peek_n<1>(mail, G_PR + par * 512 + lane, 1, gq);
                             }
                             mylg = __uint_as_float((unsigned)gq[0]);

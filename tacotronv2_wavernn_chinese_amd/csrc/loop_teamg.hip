@@ -1,6 +1,6 @@
 // WRNN_KERNEL_TEAMG: the per-sample loop of WaveRNN.generate (wavernn/models/fatchord_version.py:194-241) for ANY constructor
-// dims, one row per XCD team.  The machinery is loop_dm_team.hip's: one team = the 32 workgroups of one XCD (formed by
-// HW_REG_XCC_ID, co-residency checked with WRNN_ARRIVE_POLLS), 8-byte {tag, value} granules exchanged through the XCD's L2,
+// dims, one row per XCD team.  The team protocol is team_common.h's: one team = the 32 workgroups of one XCD (formed by
+// HW_REG_XCC_ID, co-residency checked at the start), 8-byte {tag, value} granules exchanged through the XCD's L2,
 // double-buffered by step parity, every spin bounded (device error word, `dead`: all waves run to the end).  What is new is that
 // nothing is a compile-time shape: the layer sizes arrive in WrnnTeamGPlan.
 //
@@ -8,7 +8,7 @@
 // fc3).  Workgroup g owns units [g U, min(N, (g + 1) U)) of a layer of N units, U = ceil(N / 32): possibly none (rnn 100: U = 4, the
 // last seven workgroups own no hidden unit), and it still takes part in every exchange.  A 16-lane group (one DPP row) evaluates one
 // unit: a row is K floats padded to a multiple of 64, lane q reads float4 q, q + 16, ... of the row and of the activation vector,
-// the 16 partial sums are added with dmt_row_sum's DPP steps.  Where a workgroup owns 16 or fewer hidden units a group takes one gate
+// the 16 partial sums are added with row_sum's DPP steps.  Where a workgroup owns 16 or fewer hidden units a group takes one gate
 // row of a unit instead (gru_phase).
 //
 // Placement.  A workgroup's slice of the weights is one contiguous image in device memory (wrnn_teamg_pack); the first `nres` units
@@ -24,15 +24,10 @@
 //   4. relu(fc2 . [fc1 | a4_t])                                      -> [fc2]                :220-221
 //   5. fc3 rows of the own classes; RAW: + noise, race inside the workgroup, -> [32 candidates (value, class)], every workgroup
 //      picks the winner; MOL: -> [30 outputs], every workgroup runs the sampler                :223-237
-#include "device_util.h"
-#include "wrnn_internal.h"
+#include "team_common.h"
 
 #define TG_THREADS WRNN_TEAMG_THREADS
-#define TG_SPIN_MAX 300000u
-#define TG_WGS 32
 #define TG_LDS_MAX (160 * 1024)
-
-typedef unsigned long long u64;
 
 namespace {
 
@@ -53,46 +48,10 @@ struct TgLay {
         f3 = o; o += FCP;                // relu(fc2)                             input of fc3
         cb = o; o += 2 * CB;             // [parity][m_t (F) | a_t (R)]           conditioning of a step; its head is the input of I
         gs = o; o += 128;                // [16 units][3 gates][segment A sum, segment B sum] of a GRU layer split by gate rows
-        misc = o; o += 128;              // 0-2 team / rank / bail-out, 8 x_{t-1}, 32-63 race values, 64-95 race classes
+        misc = o; o += 128;              // 0-2 team / rank / bail-out (team_common.h), 8 x_{t-1}, 32-63 race values, 64-95 race classes
         total = o;
     }
 };
-
-__device__ __forceinline__ unsigned tg_xcc_id() {
-    unsigned v;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
-    return v & 0xf;
-}
-__device__ __forceinline__ void tg_st(u64 *base, unsigned idx, unsigned tag, float payload) {
-    const u64 v = ((u64)tag << 32) | __float_as_uint(payload);
-    const unsigned off = idx * 8u;
-    asm volatile("global_store_dwordx2 %0, %1, %2" ::"v"(off), "v"(v), "s"(base) : "memory");
-}
-__device__ __forceinline__ u64 tg_peek(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// one granule per lane; wave-uniform completion; two staggered first looks (see loop_team2.hip)
-__device__ __forceinline__ float tg_take(const u64 *base, unsigned idx, unsigned tag, bool &dead, unsigned *err, unsigned code) {
-    u64 ga = tg_peek(base + idx);
-    __builtin_amdgcn_s_sleep(3);
-    u64 gb = tg_peek(base + idx);
-    if (__all((unsigned)(ga >> 32) == tag)) return __uint_as_float((unsigned)ga);
-    unsigned spins = 0;
-    while (!dead && !__all((unsigned)(gb >> 32) == tag)) {
-        if (++spins > TG_SPIN_MAX) { dead = true; if ((threadIdx.x & 63) == 0) atomicExch(err, code); break; }
-        gb = tg_peek(base + idx);
-    }
-    return __uint_as_float((unsigned)gb);
-}
-template <int CTRL>
-__device__ __forceinline__ float tg_dpp(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float tg_row_sum(float v) {   // sum over the 16 lanes of a DPP row, in every lane
-    v += tg_dpp<0xB1>(v);
-    v += tg_dpp<0x4E>(v);
-    v += tg_dpp<0x141>(v);
-    v += tg_dpp<0x140>(v);
-    return v;
-}
 
 // G rows of one unit against one activation vector: wp = the unit's first row + lane q (float4), rows kp4 float4 apart; xp = the
 // vector + q.  Segment A = float4 steps [0, nA), segment B = [nA, nK): sa / sb are their sums (the n gate of a GRU needs them apart)
@@ -112,7 +71,7 @@ __device__ __forceinline__ void tg_dot(const float4 *__restrict__ wp, int kp4, c
         }
     }
 #pragma unroll
-    for (int g = 0; g < G; ++g) { sa[g] = tg_row_sum(a0[g] + a1[g]); a0[g] = a1[g] = 0.0f; }
+    for (int g = 0; g < G; ++g) { sa[g] = row_sum(a0[g] + a1[g]); a0[g] = a1[g] = 0.0f; }
 #pragma unroll 4
     for (int k = nA; k < nK; ++k) {
         const float4 x = xp[k * 16];
@@ -124,7 +83,7 @@ __device__ __forceinline__ void tg_dot(const float4 *__restrict__ wp, int kp4, c
         }
     }
 #pragma unroll
-    for (int g = 0; g < G; ++g) sb[g] = tg_row_sum(a0[g] + a1[g]);
+    for (int g = 0; g < G; ++g) sb[g] = row_sum(a0[g] + a1[g]);
 }
 
 __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta) {
@@ -143,31 +102,9 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int qw = tid >> 4, q = tid & 15;
 
-    // ---- team formation (as loop_team2.hip): teams are numbered in order of first arrival of their XCD ----
-    if (tid == 0) {
-        const unsigned x = tg_xcc_id();
-        misc_i[2] = 0;   // bail-out flag
-        const unsigned rank = atomicAdd(&ta.ctl[x], 1u);
-        unsigned slot1 = 0, arrived = 0;
-        if (rank == 0) {
-            slot1 = atomicAdd(&ta.ctl[8], 1u) + 1u;
-            __hip_atomic_store(&ta.ctl[16 + x], slot1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        // co-residency checked, not assumed: the 32 workgroups of this XCD spin on each other for the whole launch
-        for (unsigned spins = 0; spins < WRNN_ARRIVE_POLLS; ++spins) {
-            slot1 = __hip_atomic_load(&ta.ctl[16 + x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            arrived = __hip_atomic_load(&ta.ctl[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (slot1 && arrived >= TG_WGS) break;
-        }
-        if (arrived < TG_WGS) { slot1 = 0; if (rank < TG_WGS) atomicCAS(a.err, 0u, WRNN_DEVERR_BUSY); }
-        misc_i[0] = slot1 ? (int)slot1 - 1 : 1 << 20;
-        misc_i[1] = (int)rank;
-    }
-    __syncthreads();
-    const int team = __builtin_amdgcn_readfirstlane(misc_i[0]);
-    const int g = __builtin_amdgcn_readfirstlane(misc_i[1]);
-    __syncthreads();
-    if (g >= TG_WGS || team >= ta.n_teams || team >= a.n_rows) return;
+    // ---- team formation (team_common.h) ----
+    int team, g;
+    if (!join_team(ta.ctl, a.err, misc_i, ta.n_teams, team, g) || team >= a.n_rows) return;
     u64 *mail = ta.mail + (size_t)team * ta.plan.mail_granules;
     // mailbox regions (granules), two parities each
     const unsigned M_XC = 0, M_H1 = 2 * HP, M_H2 = 4 * HP, M_F1 = 6 * HP, M_F2 = 6 * HP + 2 * FCP, M_CAND = 6 * HP + 4 * FCP;
@@ -224,7 +161,7 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
             if (ul < L.nres) tg_dot<1>((const float4 *)(wres + L.lds_off + (size_t)ul * L.KP) + q, kp4, (const float4 *)cbuf + q, nK, nK, sa, sb);
             else tg_dot<1>((const float4 *)(img + L.img_off + (size_t)ul * L.KP) + q, kp4, (const float4 *)cbuf + q, nK, nK, sa, sb);
             const int j = g * L.U + ul;
-            if (q == 0) tg_st(mail, M_XC + (tag & 1u) * HP + j, tag, sa[0] + w[a.off.I_b + j]);
+            if (q == 0) st_granule(mail, M_XC + (tag & 1u) * HP + j, tag, __float_as_uint(sa[0] + w[a.off.I_b + j]));
         }
     };
     // one GRU layer (get_gru_cell :273-279, gate rows [r; z; n]): h' of the own units -> mailbox.  xin = [input (KAP) | h (HP)]
@@ -257,7 +194,7 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
             const float zg = 1.0f / (1.0f + expf(-((gi[1] + bi[H + j]) + (gh[1] + bh[H + j]))));
             const float ng = tanhf((gi[2] + bi[2 * H + j]) + rg * (gh[2] + bh[2 * H + j]));
             const float hn = (1.0f - zg) * ng + zg * xin[L.KAP + j];
-            if (by_row || q == 0) tg_st(mail, region + (epoch & 1u) * HP + j, epoch, hn);
+            if (by_row || q == 0) st_granule(mail, region + (epoch & 1u) * HP + j, epoch, __float_as_uint(hn));
         }
     };
     // relu(W . x + b) of the own rows -> mailbox
@@ -268,14 +205,14 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
             if (ul < L.nres) tg_dot<1>((const float4 *)(wres + L.lds_off + (size_t)ul * L.KP) + q, kp4, (const float4 *)xin + q, nK, nK, sa, sb);
             else tg_dot<1>((const float4 *)(img + L.img_off + (size_t)ul * L.KP) + q, kp4, (const float4 *)xin + q, nK, nK, sa, sb);
             const int j = g * L.U + ul;
-            if (q == 0) tg_st(mail, region + (epoch & 1u) * FCP + j, epoch, fmaxf(sa[0] + w[ob + j], 0.0f));
+            if (q == 0) st_granule(mail, region + (epoch & 1u) * FCP + j, epoch, __float_as_uint(fmaxf(sa[0] + w[ob + j], 0.0f)));
         }
     };
     // all N values of an exchanged vector, element j to thread j (+ 512, ...); whole waves take part, lanes past N re-read granule N - 1
     auto gather = [&](unsigned region, int N, unsigned epoch, bool &dead, unsigned code, auto &&put) {
         for (int j0 = wave * 64; j0 < N; j0 += TG_THREADS) {
             const int j = j0 + lane;
-            const float v = tg_take(mail, region + (unsigned)(j < N ? j : N - 1), epoch, dead, a.err, code);
+            const float v = take_staggered(mail, region + (unsigned)(j < N ? j : N - 1), epoch, dead, a.err, code);
             if (j < N) put(j, v);
         }
     };
@@ -362,7 +299,7 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
                         else if (a.noise_mode == WRNN_NOISE_PHILOX) v -= logf(-logf(wrnn_uniform_raw(kseed, (uint64_t)t, krow, (uint32_t)c)));
                         if (v > bv) { bv = v; bi = c; }   // classes ascend: ties keep the lowest
                     } else if (q == 0) {
-                        tg_st(mail, M_CAND + par * 64 + c, epoch, lg);
+                        st_granule(mail, M_CAND + par * 64 + c, epoch, __float_as_uint(lg));
                     }
                 }
                 if (d.mode == WRNN_MODE_RAW) {
@@ -373,10 +310,10 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
                         int k = lane < 32 ? misc_i[64 + lane] : 0x7fffffff;
                         wave_argmax(v, k);
                         if (lane == 0) {   // the workgroup's candidate: granule g = value, 32 + g = class
-                            tg_st(mail, M_CAND + par * 64 + g, epoch, v);
-                            tg_st(mail, M_CAND + par * 64 + 32 + g, epoch, __int_as_float(k));
+                            st_granule(mail, M_CAND + par * 64 + g, epoch, __float_as_uint(v));
+                            st_granule(mail, M_CAND + par * 64 + 32 + g, epoch, (unsigned)k);
                         }
-                        const float pv = tg_take(mail, M_CAND + par * 64 + lane, epoch, dead, a.err, 15u);
+                        const float pv = take_staggered(mail, M_CAND + par * 64 + lane, epoch, dead, a.err, 15u);
                         const int ck = __shfl(__float_as_int(pv), (lane + 32) & 63, 64);
                         v = lane < 32 ? pv : -INFINITY;
                         k = lane < 32 ? ck : 0x7fffffff;
@@ -393,7 +330,7 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
                 } else if (wave == 0) {
                     // sample_from_discretized_mix_logistic (wavernn/utils/distribution.py:87-123) on the 3 * nr exchanged outputs, in every workgroup
                     const int nr = NC / 3;
-                    const float lg = tg_take(mail, M_CAND + par * 64 + (lane < NC ? lane : NC - 1), epoch, dead, a.err, 15u);
+                    const float lg = take_staggered(mail, M_CAND + par * 64 + (lane < NC ? lane : NC - 1), epoch, dead, a.err, 15u);
                     float v = -INFINITY;
                     int k = 0x7fffffff;
                     if (lane < nr) {
@@ -421,9 +358,9 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
                     }
                 }
             }
-            if ((epoch & 63u) == 0u && dead && lane == 0) misc_i[2] = 1;   // bounded-spin bail-out, checked workgroup-wide every 64 samples
+            if ((epoch & 63u) == 0u && dead && lane == 0) misc_i[M_DEAD] = 1;   // bounded-spin bail-out, checked workgroup-wide every 64 samples
             __syncthreads();
-            if ((epoch & 63u) == 0u && misc_i[2]) return;
+            if ((epoch & 63u) == 0u && misc_i[M_DEAD]) return;
         }
     }
 }
@@ -444,7 +381,7 @@ const char *wrnn_teamg_make_plan(const WrnnDims &d, int64_t budget, WrnnTeamGPla
     p = WrnnTeamGPlan{};
     auto set = [&](int l, int N, int G, int KA, int KB) {
         WrnnTeamGLayer &L = p.L[l];
-        L.N = N; L.G = G; L.KA = KA; L.KB = KB; L.KAP = tg_r64(KA); L.KP = L.KAP + (KB ? tg_r64(KB) : 0); L.U = (N + TG_WGS - 1) / TG_WGS;
+        L.N = N; L.G = G; L.KA = KA; L.KB = KB; L.KAP = tg_r64(KA); L.KP = L.KAP + (KB ? tg_r64(KB) : 0); L.U = (N + TEAM_WGS - 1) / TEAM_WGS;
     };
     set(WRNN_TEAMG_FC3, d.NC, 1, d.FC, 0);
     set(WRNN_TEAMG_FC2, d.FC, 1, d.FC + d.A, 0);
@@ -485,7 +422,7 @@ hipError_t wrnn_teamg_pack(const wrnn_handle *h, const WrnnTeamGPlan &p, float *
     const WrnnDims &d = h->d;
     const WrnnPacked &o = h->off;
     const float *w = h->wdev;
-    hipError_t e = hipMemsetAsync(img, 0, (size_t)TG_WGS * p.img_floats_wg * sizeof(float), s);
+    hipError_t e = hipMemsetAsync(img, 0, (size_t)TEAM_WGS * p.img_floats_wg * sizeof(float), s);
     if (e != hipSuccess) return e;
     (void)hipGetLastError();
     auto put = [&](int l, const float *src_t, int ld, int row0, int k0, int K, int gate, int kdst) {
@@ -521,7 +458,7 @@ hipError_t wrnn_launch_loop_teamg(const WrnnTeamGArgs &a, hipStream_t s) {
     const size_t lds = teamg_lds_bytes(a.plan);
     hipError_t e = hipFuncSetAttribute((const void *)loop_teamg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(loop_teamg_kernel, dim3(a.n_teams * TG_WGS), dim3(TG_THREADS), lds, s, a);
+    hipLaunchKernelGGL(loop_teamg_kernel, dim3(a.n_teams * TEAM_WGS), dim3(TG_THREADS), lds, s, a);
     return hipGetLastError();
 }
 
@@ -529,16 +466,8 @@ hipError_t wrnn_launch_loop_teamg(const WrnnTeamGArgs &a, hipStream_t s) {
 
 extern "C" int wrnn_teamg_plan(const wrnn_config *cfg, int64_t lds_budget_bytes, wrnn_teamg_plan_info *out) {
     if (!cfg || !out) return WRNN_ERR_INVALID;
-    // the dims as wrnn_create derives and bounds them (api.hip)
-    WrnnDims d{};
-    d.H = cfg->rnn_dims; d.FC = cfg->fc_dims; d.F = cfg->feat_dims; d.C = cfg->compute_dims; d.R = cfg->res_out_dims; d.A = cfg->res_out_dims / 4;
-    d.NBLK = cfg->res_blocks; d.P = cfg->pad; d.KS = 2 * cfg->pad + 1; d.ND = d.KS; d.mode = cfg->mode; d.HOP = cfg->hop_length;
-    if (cfg->mode == WRNN_MODE_RAW) {
-        if (cfg->bits < 1 || cfg->bits > 16) return WRNN_ERR_INVALID;
-        d.NC = 1 << cfg->bits;
-    } else if (cfg->mode == WRNN_MODE_MOL) d.NC = 30;
-    else return WRNN_ERR_INVALID;
-    if (d.H < 1 || d.FC < 1 || d.F < 1 || d.R < 4 || d.R % 4 != 0 || d.H > 1024 || d.R > 1024 || d.FC > (1 << 20) || d.F > (1 << 20)) return WRNN_ERR_INVALID;
+    WrnnDims d;
+    if (wrnn_dims_from_config(cfg, d) || d.FC > (1 << 20) || d.F > (1 << 20)) return WRNN_ERR_INVALID;
     WrnnTeamGPlan p;
     if (wrnn_teamg_make_plan(d, lds_budget_bytes, p)) return WRNN_ERR_UNSUPPORTED;
     *out = wrnn_teamg_plan_info{};
@@ -549,7 +478,7 @@ extern "C" int wrnn_teamg_plan(const wrnn_config *cfg, int64_t lds_budget_bytes,
         o.units = L.N; o.rows_per_unit = L.G; o.k = K; o.k_padded = L.KP; o.resident_units = L.nres;
         o.weight_bytes = 4LL * L.N * L.G * K;
         o.rows_min = INT32_MAX;
-        for (int g = 0; g < TG_WGS; ++g) {
+        for (int g = 0; g < TEAM_WGS; ++g) {
             int n = L.N - g * L.U;
             n = n < 0 ? 0 : (n > L.U ? L.U : n);
             o.own_first[g] = n ? g * L.U : L.N;

@@ -28,7 +28,7 @@
 #include <cstdarg>
 #include <cstdio>
 
-#include "wrnn_internal.h"
+#include "team_common.h"
 
 namespace {
 
@@ -727,7 +727,7 @@ static int train_impl(wrnn_handle *h, int phase, const wrnn_loop_params *w, cons
             (void)hipGetLastError();
             if (ok) {
                 const size_t mg = (size_t)h->n_teams * wrnn_gru_team_mail_granules(2, true);
-                ok = hipMalloc(&st->mail, mg * sizeof(unsigned long long)) == hipSuccess && hipMalloc(&st->ctl, 256) == hipSuccess;
+                ok = hipMalloc(&st->mail, mg * sizeof(unsigned long long)) == hipSuccess && hipMalloc(&st->ctl, 2 * TEAM_CTL_WORDS * sizeof(unsigned)) == hipSuccess;
             }
             if (ok) st->team_checked = 1;
         }
@@ -747,7 +747,7 @@ static int train_impl(wrnn_handle *h, int phase, const wrnn_loop_params *w, cons
         ta.dHext = dHext; ta.dGI = q.dGI; ta.dGH = q.dGH; ta.B = B; ta.L = L; ta.n_teams = h->n_teams; ta.rpb = rpb;
         ta.mail = st->mail; ta.ctl = st->ctl; ta.err = h->err_dev;
         return wrnn_gated_launch(h->cfg.device, s, st->mail, (size_t)h->n_teams * wrnn_gru_team_mail_granules(nq, bwd) * sizeof(unsigned long long),
-                                 st->ctl, 256, [&] { return wrnn_gru_team_launch(ta, nq, bwd, s); });
+                                 st->ctl, 2 * TEAM_CTL_WORDS * sizeof(unsigned), [&] { return wrnn_gru_team_launch(ta, nq, bwd, s); });
     };
     const float *a1 = aux_dev, *a2 = aux_dev + A, *a3 = aux_dev + 2 * A, *a4 = aux_dev + 3 * A;   // aux channel split (:198-199)
 

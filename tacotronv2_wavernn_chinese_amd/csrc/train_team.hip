@@ -1,7 +1,7 @@
 // The two GRU recurrences of wrnn_train_step (train.hip) as PERSISTENT team kernels: one launch per recurrence instead of one per
 // time step.  A step kernel starts with cold caches (the previous step wrote its results back at its end) and costs 6.6 us (forward) /
 // 13.9 us (backward) for ~1 us of arithmetic; here the recurrent weights stay in LDS for the whole sequence and the state travels
-// through the XCD's L2 with the team kernels' protocol (loop_batch.hip): team = the 32 workgroups of one XCD (HW_REG_XCC_ID), 8-byte
+// through the XCD's L2 with the team kernels' protocol (team_common.h): team = the 32 workgroups of one XCD (HW_REG_XCC_ID), 8-byte
 // {tag, value} granules, plain store + sc1 load, the data is the flag, parity double-buffering, bounded spins, arrival check.
 //
 // Work split (rnn_dims = 512 only; other dims use the step kernels): a team runs R = 4 or 8 batch rows, workgroup g owns hidden units
@@ -39,33 +39,6 @@
 namespace {
 
 constexpr int TT_H = 512;
-
-// team formation + co-residency check, shared by both kernels (see loop_team2.hip); returns false when this workgroup is not in a team
-__device__ __forceinline__ bool join_team(unsigned *ctl, unsigned *err, int *misc_i, int n_teams, int &team, int &g) {
-    if (threadIdx.x == 0) {
-        const unsigned x = xcc_idb();
-        misc_i[M_DEAD] = 0;
-        const unsigned rank = atomicAdd(&ctl[x], 1u);
-        unsigned slot1 = 0, arrived = 0;
-        if (rank == 0) {
-            slot1 = atomicAdd(&ctl[8], 1u) + 1u;
-            __hip_atomic_store(&ctl[16 + x], slot1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        for (unsigned spins = 0; spins < WRNN_ARRIVE_POLLS; ++spins) {
-            slot1 = __hip_atomic_load(&ctl[16 + x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            arrived = __hip_atomic_load(&ctl[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (slot1 && arrived >= TB_WGS) break;
-        }
-        if (arrived < TB_WGS) { slot1 = 0; if (rank < TB_WGS) atomicCAS(err, 0u, WRNN_DEVERR_BUSY); }
-        misc_i[M_TEAM] = slot1 ? (int)slot1 - 1 : 1 << 20;
-        misc_i[M_RANK] = (int)rank;
-    }
-    __syncthreads();
-    team = __builtin_amdgcn_readfirstlane(misc_i[M_TEAM]);
-    g = __builtin_amdgcn_readfirstlane(misc_i[M_RANK]);
-    __syncthreads();
-    return g < TB_WGS && team < n_teams;
-}
 
 // ---------------------------------------------------------------------------------------------------------------- forward
 // LDS (floats): weight image [4 waves][3 gates][8 S][64 lanes][4 e] (96 KB) | h vector [rq][S][kp][j][e] (R x 512) | misc
@@ -446,7 +419,7 @@ template <class K>
 static hipError_t launch_team(K kern, size_t lds, const WrnnGruTeamArgs &a, hipStream_t s) {
     hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(a.n_teams * TB_WGS), dim3(TB_THREADS), lds, s, a);
+    hipLaunchKernelGGL(kern, dim3(a.n_teams * TEAM_WGS), dim3(TB_THREADS), lds, s, a);
     return hipGetLastError();
 }
 

@@ -31,6 +31,9 @@ struct WrnnDims {
     int mode;     // WRNN_MODE_*
     int ND;       // frames of support of the composite upsampling FIR
 };
+// d from cfg, as WaveRNN.__init__ derives the dims, bounded to what every kernel relies on (HOP = cfg->hop_length: whether the
+// upsample factors multiply to it is wrnn_create's check); nullptr, or why cfg is refused (api.hip)
+const char *wrnn_dims_from_config(const wrnn_config *cfg, WrnnDims &d);
 
 // Offsets (in floats) into the single packed device allocation.
 struct WrnnPacked {
@@ -76,8 +79,6 @@ struct WrnnRowKey {
 #define WRNN_DEVERR_BUSY 3u
 // rows_folded_kernel: the fold count computed on the device differs from the call's rows_total (WRNN_ERR_INVALID)
 #define WRNN_DEVERR_ROWS 4u
-// polls a workgroup waits at the start of a team kernel for the other 31 of its XCD (~1.5 ms; a resident launch needs ~10 us)
-#define WRNN_ARRIVE_POLLS 200000u
 
 struct WrnnTrainState;   // train.hip: workspace + captured step graphs of wrnn_train_step
 void wrnn_train_state_free(WrnnTrainState *st);
@@ -221,7 +222,7 @@ struct WrnnTeamArgs {
     int32_t *labels_out;
     float *samples_out;
     unsigned long long *mail;  // [n_teams][WRNN_TEAM_MAIL_GRANULES]
-    unsigned *ctl;             // [16] per-XCD arrival counters
+    unsigned *ctl;             // [TEAM_CTL_WORDS] team formation (team_common.h)
     unsigned *err;
     unsigned long long *prof;  // [8][WRNN_PROF_SLOTS] phase cycle counters (developer instrumentation) or null
 };
