@@ -64,6 +64,9 @@ extern "C" {
                                 * matrix products, noise and conditioning run beside the serial chain instead of inside it */
 #define WRNN_KERNEL_TEAMG 6  /* added to ABI 9: one XCD team per row for ANY model dims -- layer shapes are run-time arguments, a workgroup
                               * keeps what fits of its weight slice in LDS and streams the rest; opt-in, AUTO never picks it */
+#define WRNN_KERNEL_TEAMG_BATCH 7 /* added to ABI 9: the same kernel with 2..8 rows per team in lock-step (opts.batch_rows, 0 = the library's
+                                   * choice) -- every weight load and every exchange serves all of them; each row is bit-equal to
+                                   * WRNN_KERNEL_TEAMG's.  Opt-in; one row per team runs WRNN_KERNEL_TEAMG itself and reports 6 */
 
 /* tensor dtypes accepted by wrnn_load_weights */
 #define WRNN_DTYPE_F32 0
@@ -356,6 +359,15 @@ int wrnn_teamg_plan(const wrnn_config *cfg, int64_t lds_budget_bytes, wrnn_teamg
 /* Test hook in the style of wrnn_debug_force_no_teams: the following WRNN_KERNEL_TEAMG calls of this handle place their weights with
  * this LDS budget (< 0: back to the default), so that small models exercise the streamed and the mixed placement. */
 int wrnn_debug_teamg_lds_budget(wrnn_handle *h, int64_t bytes);
+/* WRNN_KERNEL_TEAMG_BATCH (added to ABI 9 like the above: new entry points and one kernel id, nothing existing changes).  The plan of
+ * rows_per_team rows in lock-step: 1 = wrnn_teamg_plan itself; 2, 4, 8 = the kernel's instantiations (a batch of 3 rows runs on 4 with a
+ * slot idle).  Ownership and the weight image are those of wrnn_teamg_plan; activation_bytes and mail_granules are for rows_per_team
+ * rows, and the resident weights get what LDS the activation vectors leave.  WRNN_ERR_INVALID: also rows_per_team outside 1..8;
+ * WRNN_ERR_UNSUPPORTED: the rows' activation vectors exceed 160 KiB, or their mailbox regions the library's mailbox.
+ * wrnn_debug_teamg_lds_budget applies to both kernels. */
+int wrnn_teamg_batch_plan(const wrnn_config *cfg, int32_t rows_per_team, int64_t lds_budget_bytes, wrnn_teamg_plan_info *out);
+/* Rows per team batch of the last generate call's loop kernel (the batch kernels); 1 for the one-row kernels and before any call. */
+int32_t wrnn_last_batch_rows(const wrnn_handle *h);
 
 /* ---- streaming generation (ABI 7) -------------------------------------------------------------------------------------------
  * Mel frames arrive a few at a time (Tacotron's decoder); audio leaves as soon as the frames it depends on are in.  A stream

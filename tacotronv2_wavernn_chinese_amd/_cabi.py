@@ -18,9 +18,9 @@ LIB_PATH = os.path.join(_HERE, 'csrc', 'libwavernn_amd.so')
 
 MODE_RAW, MODE_MOL = 0, 1
 NOISE_PHILOX, NOISE_INJECTED, NOISE_ARGMAX = 0, 1, 2
-KERNEL_AUTO, KERNEL_SIMPLE, KERNEL_TEAM2, KERNEL_BATCH, KERNEL_BATCH_CS, KERNEL_TEAMG = 0, 1, 3, 4, 5, 6
+KERNEL_AUTO, KERNEL_SIMPLE, KERNEL_TEAM2, KERNEL_BATCH, KERNEL_BATCH_CS, KERNEL_TEAMG, KERNEL_TEAMG_BATCH = 0, 1, 3, 4, 5, 6, 7
 KERNEL_NAMES = {KERNEL_AUTO: 'auto', KERNEL_SIMPLE: 'simple', KERNEL_TEAM2: 'team2', KERNEL_BATCH: 'batch', KERNEL_BATCH_CS: 'batch_cs',
-                KERNEL_TEAMG: 'teamg'}
+                KERNEL_TEAMG: 'teamg', KERNEL_TEAMG_BATCH: 'teamg_batch'}
 KERNEL_IDS = {v: k for k, v in KERNEL_NAMES.items()}
 DTYPE_F32, DTYPE_I64 = 0, 1
 ERR_NAMES = {0: 'WRNN_OK', -1: 'WRNN_ERR_INVALID', -2: 'WRNN_ERR_HIP', -3: 'WRNN_ERR_STATE',
@@ -40,7 +40,8 @@ EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wr
                     'wrnn_mel_create', 'wrnn_mel_frames', 'wrnn_melspectrogram', 'wrnn_mel_tables', 'wrnn_mel_last_error', 'wrnn_mel_destroy',
                     'wrnn_quantise', 'wrnn_collate_windows',
                     'wrnn_resample_create', 'wrnn_resample_out_len', 'wrnn_resample_bank', 'wrnn_resample', 'wrnn_resample_last_error',
-                    'wrnn_resample_destroy', 'wrnn_condition_frames', 'wrnn_condition', 'wrnn_teamg_plan', 'wrnn_debug_teamg_lds_budget')
+                    'wrnn_resample_destroy', 'wrnn_condition_frames', 'wrnn_condition', 'wrnn_teamg_plan', 'wrnn_debug_teamg_lds_budget',
+                    'wrnn_teamg_batch_plan', 'wrnn_last_batch_rows')
 
 
 def epilogue_tables(n_classes: int, overlap: int, hop: int):
@@ -120,10 +121,11 @@ class TeamgPlanInfo(C.Structure):
 
 
 def teamg_plan(lds_budget_bytes: int = -1, *, rnn_dims, fc_dims, bits, pad, upsample_factors, feat_dims, compute_dims, res_out_dims,
-               res_blocks, hop_length, sample_rate=22050, mode='RAW') -> dict:
+               res_blocks, hop_length, sample_rate=22050, mode='RAW', rows_per_team=None) -> dict:
     """Host-only ``wrnn_teamg_plan``: how WRNN_KERNEL_TEAMG splits a model of these constructor dims over the 32 workgroups of a team and
     what it keeps in LDS with ``lds_budget_bytes`` for resident weights (< 0: the default, 160 KiB minus the activation vectors).
-    ``layers``: name -> dict of the ``wrnn_teamg_layer_info`` fields (``own_first`` / ``own_count`` as lists of 32)."""
+    ``layers``: name -> dict of the ``wrnn_teamg_layer_info`` fields (``own_first`` / ``own_count`` as lists of 32).
+    ``rows_per_team``: ``wrnn_teamg_batch_plan`` instead (see :func:`teamg_batch_plan`)."""
     cfg = Config()
     cfg.rnn_dims, cfg.fc_dims, cfg.bits, cfg.pad = rnn_dims, fc_dims, bits, pad
     cfg.n_upsample = len(upsample_factors)
@@ -133,9 +135,13 @@ def teamg_plan(lds_budget_bytes: int = -1, *, rnn_dims, fc_dims, bits, pad, upsa
     cfg.res_blocks, cfg.hop_length, cfg.sample_rate = res_blocks, hop_length, sample_rate
     cfg.mode = MODE_RAW if mode == 'RAW' else MODE_MOL
     info = TeamgPlanInfo()
-    rc = load_library().wrnn_teamg_plan(C.byref(cfg), int(lds_budget_bytes), C.byref(info))
+    if rows_per_team is None:
+        rc, what = load_library().wrnn_teamg_plan(C.byref(cfg), int(lds_budget_bytes), C.byref(info)), 'wrnn_teamg_plan'
+    else:
+        rc = load_library().wrnn_teamg_batch_plan(C.byref(cfg), int(rows_per_team), int(lds_budget_bytes), C.byref(info))
+        what = f'wrnn_teamg_batch_plan({rows_per_team} rows per team)'
     if rc != 0:
-        raise WrnnError(rc, f'wrnn_teamg_plan: no plan for rnn_dims {rnn_dims}, fc_dims {fc_dims}, feat_dims {feat_dims}, res_out_dims {res_out_dims}, '
+        raise WrnnError(rc, f'{what}: no plan for rnn_dims {rnn_dims}, fc_dims {fc_dims}, feat_dims {feat_dims}, res_out_dims {res_out_dims}, '
                             f'bits {bits}, mode {mode}')
     layers = {}
     for name, li in zip(TEAMG_LAYER_NAMES, info.layer):
@@ -143,6 +149,13 @@ def teamg_plan(lds_budget_bytes: int = -1, *, rnn_dims, fc_dims, bits, pad, upsa
     out = {f: int(getattr(info, f)) for f, _ in TeamgPlanInfo._fields_ if f != 'layer'}
     out['layers'] = layers
     return out
+
+
+def teamg_batch_plan(rows_per_team: int, lds_budget_bytes: int = -1, **dims) -> dict:
+    """Host-only ``wrnn_teamg_batch_plan``: the plan of WRNN_KERNEL_TEAMG_BATCH with ``rows_per_team`` rows in lock-step (1: ``teamg_plan``'s;
+    2, 4, 8: the kernel's instantiations).  Same dict as :func:`teamg_plan`; ``activation_bytes`` and ``mail_granules`` are for that many
+    rows.  ``WrnnError``: WRNN_ERR_INVALID outside 1..8, WRNN_ERR_UNSUPPORTED when the rows' vectors or mailbox regions do not fit."""
+    return teamg_plan(lds_budget_bytes, rows_per_team=int(rows_per_team), **dims)
 
 
 _lib: Optional[C.CDLL] = None
@@ -246,6 +259,10 @@ def load_library() -> C.CDLL:
     lib.wrnn_teamg_plan.restype = C.c_int
     lib.wrnn_debug_teamg_lds_budget.argtypes = [vp, C.c_int64]
     lib.wrnn_debug_teamg_lds_budget.restype = C.c_int
+    lib.wrnn_teamg_batch_plan.argtypes = [C.POINTER(Config), C.c_int32, C.c_int64, C.POINTER(TeamgPlanInfo)]
+    lib.wrnn_teamg_batch_plan.restype = C.c_int
+    lib.wrnn_last_batch_rows.argtypes = [vp]
+    lib.wrnn_last_batch_rows.restype = C.c_int32
     lib.wrnn_stream_open.argtypes = [vp, C.c_int32, C.POINTER(SampleOpts), C.POINTER(vp)]
     lib.wrnn_stream_open.restype = C.c_int
     lib.wrnn_stream_push.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int64, C.POINTER(C.c_int64), vp]
@@ -505,15 +522,19 @@ class NativeVocoder:
         """Ownership and weight placement of WRNN_KERNEL_TEAMG for this model (:func:`teamg_plan`; host only)."""
         return teamg_plan(lds_budget_bytes, **self._dims)
 
+    def teamg_batch_plan(self, rows_per_team: int, lds_budget_bytes: int = -1) -> dict:
+        """The plan of WRNN_KERNEL_TEAMG_BATCH for this model with ``rows_per_team`` rows in lock-step (:func:`teamg_batch_plan`; host only)."""
+        return teamg_batch_plan(rows_per_team, lds_budget_bytes, **self._dims)
+
     def debug_teamg_lds_budget(self, lds_budget_bytes: int):
-        """Test hook: the following WRNN_KERNEL_TEAMG calls place their weights with this LDS budget (< 0: the default)."""
+        """Test hook: the following WRNN_KERNEL_TEAMG / WRNN_KERNEL_TEAMG_BATCH calls place their weights with this LDS budget (< 0: the default)."""
         self._check(self.lib.wrnn_debug_teamg_lds_budget(self._h, int(lds_budget_bytes)))
 
     def last_timing(self) -> dict:
         t = Timing()
         self._check(self.lib.wrnn_last_timing(self._h, C.byref(t)))
         return dict(prologue_ms=t.prologue_ms, loop_ms=t.loop_ms, kernel=t.kernel, rows=t.rows, steps=t.steps,
-                    launches=t.launches)
+                    launches=t.launches, batch_rows=int(self.lib.wrnn_last_batch_rows(self._h)))
 
 
 def plan_folded(frames, hop: int, target: int, overlap: int) -> Tuple[np.ndarray, int]:

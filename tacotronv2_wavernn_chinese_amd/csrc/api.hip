@@ -226,6 +226,8 @@ int wrnn_debug_force_no_teams(wrnn_handle *h, int32_t on) {
     h->force_no_teams = on != 0;
     return WRNN_OK;
 }
+int32_t wrnn_last_batch_rows(const wrnn_handle *h) { return h ? h->last_batch_rows : 1; }
+
 int wrnn_debug_teamg_lds_budget(wrnn_handle *h, int64_t bytes) {
     if (!h) return WRNN_ERR_INVALID;
     h->teamg_budget = bytes < 0 ? -1 : bytes;
@@ -531,7 +533,7 @@ static int build_row_table(wrnn_handle *h, int32_t B, int32_t T, int32_t batched
 
 // The batch kernels: R = 4 * nq rows per XCD team in lock-step on the matrix cores (loop_batch.hip); the rows are spread evenly over
 // the teams first (rpb rows per batch), a team runs ceil(batches / n_teams) batches one after the other.  a: the call's loop arguments.
-static int run_batch(wrnn_handle *h, const WrnnLoopArgs &a, const WrnnFrameTables &t, int B, bool cs, int batch_rows, int snake, hipStream_t s) {
+static int run_batch(wrnn_handle *h, const WrnnLoopArgs &a, const WrnnFrameTables &t, int B, bool cs, int batch_rows, int snake, int *rpb_out, hipStream_t s) {
     const int rows = a.n_rows;
     WRNN_HIP_TRY(h, wrnn_launch_pack_records32(t.CM, t.CA, t.VM, t.VA, t.C2, t.C3, t.C4, t.REC, B, a.T, a.d.P, a.frames, s));
     int rpb = (rows + h->n_teams - 1) / h->n_teams;
@@ -549,6 +551,7 @@ static int run_batch(wrnn_handle *h, const WrnnLoopArgs &a, const WrnnFrameTable
     WRNN_HIP_TRY(h, wrnn_gated_launch(h->cfg.device, s, h->mail, WRNN_MAIL_BYTES, h->ctl, TEAM_CTL_WORDS * sizeof(unsigned),
                                       [&] { return cs ? wrnn_launch_loop_batch_cs(ba, s) : wrnn_launch_loop_batch(ba, s); }));
     h->prof_div = (double)a.steps * ((((rows + rpb - 1) / rpb) + h->n_teams - 1) / h->n_teams);
+    *rpb_out = rpb;
     return WRNN_OK;
 }
 
@@ -603,6 +606,34 @@ static int run_teamg(wrnn_handle *h, const WrnnLoopArgs &a, int snake, int n_slo
     return WRNN_OK;
 }
 
+// The same kernel with rpb > 1 rows per team in lock-step (loop_teamg_batch.hip) on its instantiation rb = 2, 4 or 8; the refusals of
+// run_teamg, the weight image of run_teamg.
+static int run_teamg_batch(wrnn_handle *h, const WrnnLoopArgs &a, int snake, int rpb, hipStream_t s) {
+    if (h->force_no_teams) return wrnn_fail(h, WRNN_ERR_INVALID, "team kernels disabled by wrnn_debug_force_no_teams (test hook)");
+    if (h->n_teams < 1) return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "WRNN_KERNEL_TEAMG_BATCH: fewer than 32 CUs visible (one team = the 32 CUs of an XCD)");
+    const int rb = wrnn_teamg_batch_inst(rpb);
+    WrnnTeamGBatchArgs ga{};
+    if (const char *why = wrnn_teamg_make_plan(a.d, h->teamg_budget, ga.plan, rb)) return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "%s (batch_rows %d runs as %d)", why, rpb, rb);
+    int blocks = 0;
+    const hipError_t oe = wrnn_teamg_batch_occupancy(ga.plan, rb, &blocks);
+    (void)hipGetLastError();
+    if (oe != hipSuccess || blocks < 1)
+        return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "WRNN_KERNEL_TEAMG_BATCH: loop_teamg_batch_kernel<%d> cannot be resident on a CU with %zu bytes of LDS (%s)", rb,
+                         ((size_t)ga.plan.act_floats + ga.plan.res_floats) * sizeof(float), oe != hipSuccess ? hipGetErrorString(oe) : "occupancy 0");
+    if (!h->teamg_img_ok) {
+        if (h->teamg_img) { (void)hipFree(h->teamg_img); h->teamg_img = nullptr; }
+        WRNN_HIP_TRY(h, hipMalloc(&h->teamg_img, (size_t)32 * ga.plan.img_floats_wg * sizeof(float)));
+        WRNN_HIP_TRY(h, wrnn_teamg_pack(h, ga.plan, h->teamg_img, s));
+        h->teamg_img_ok = true;
+        WRNN_HIP_TRY(h, hipEventRecord(h->ev[1], s));   // the one-time image is not loop time
+    }
+    ga.a = a; ga.img = h->teamg_img; ga.order = h->order_dev; ga.rpb = rpb; ga.snake = snake; ga.n_teams = h->n_teams;
+    ga.mail = h->mail; ga.ctl = h->ctl;
+    const size_t mail_bytes = (size_t)h->n_teams * ga.plan.mail_granules * sizeof(unsigned long long);   // <= WRNN_MAIL_BYTES: the plan refuses more
+    WRNN_HIP_TRY(h, wrnn_gated_launch(h->cfg.device, s, h->mail, mail_bytes, h->ctl, TEAM_CTL_WORDS * sizeof(unsigned), [&] { return wrnn_launch_loop_teamg_batch(ga, rb, s); }));
+    return WRNN_OK;
+}
+
 // Body of wrnn_generate and wrnn_generate_folded.  fold_frames != null: the rows are the folds of ALL B utterances (rows_total of them,
 // see rows_folded_kernel), every per-frame table entry past an utterance's own end is its zero-input entry T.
 static int generate_impl(wrnn_handle *h, const float *mels_dev, int32_t B, int32_t T, int32_t batched, int32_t target, int32_t overlap,
@@ -653,7 +684,7 @@ static int generate_impl(wrnn_handle *h, const float *mels_dev, int32_t B, int32
     a.x_forced = opts->x_forced_dev; a.x_init = opts->x_init_dev; a.logits_out = opts->logits_out_dev; a.labels_out = labels_out_dev;
     a.samples_out = samples_out_dev; a.err = h->err_dev; a.frames = fold_frames;
     int kernel = opts->kernel;
-    int launches = 1;
+    int launches = 1, batch_rows_run = 1;
     // what the team kernels (TEAM2, BATCH) need: co-residency (checked in wrnn_create), the 5-frame upsampling support
     // of pad = 2, hop <= 275, and 1024 or fewer classes.  AUTO falls back to the any-shape kernel otherwise;
     // an explicit request for a team kernel that cannot run is an error.
@@ -672,17 +703,33 @@ static int generate_impl(wrnn_handle *h, const float *mels_dev, int32_t B, int32
         if (team_no) return wrnn_fail(h, WRNN_ERR_INVALID, "%s", team_no);
         WrnnFrameTables t;
         if (int rc = wrnn_build_frame_tables(h, h->tab, h->tab_cap, mels_dev, mel_T, d.P - mel_off, h->aux_frames, B, T, batch_family ? 32 : 28, t, s)) return rc;
-        if (int rc = batch_family ? run_batch(h, a, t, B, kernel == WRNN_KERNEL_BATCH_CS, opts->batch_rows, snake, s)
+        if (int rc = batch_family ? run_batch(h, a, t, B, kernel == WRNN_KERNEL_BATCH_CS, opts->batch_rows, snake, &batch_rows_run, s)
                                   : run_team2(h, a, t, B, opts->team2_segment, snake, (rows + sched_teams - 1) / sched_teams * sched_teams, &launches, s))
             return rc;
     } else if (kernel == WRNN_KERNEL_TEAMG) {
         if (int rc = run_teamg(h, a, snake, (rows + sched_teams - 1) / sched_teams * sched_teams, s)) return rc;
+    } else if (kernel == WRNN_KERNEL_TEAMG_BATCH) {
+        // rows per team as run_batch spreads them; left to the library (batch_rows 0) it is lowered to the largest instantiation whose
+        // activation vectors and mailbox regions the plan admits for these dims.  One row per team is WRNN_KERNEL_TEAMG itself.
+        int rpb = (rows + sched_teams - 1) / sched_teams;
+        if (rpb > WRNN_TEAMG_BATCH_MAX_ROWS) rpb = WRNN_TEAMG_BATCH_MAX_ROWS;
+        if (opts->batch_rows > 0) rpb = opts->batch_rows;
+        else {
+            WrnnTeamGPlan probe;
+            while (rpb > 1 && wrnn_teamg_make_plan(d, h->teamg_budget, probe, wrnn_teamg_batch_inst(rpb))) rpb = wrnn_teamg_batch_inst(rpb) / 2;
+        }
+        if (rpb == 1) {
+            kernel = WRNN_KERNEL_TEAMG;
+            if (int rc = run_teamg(h, a, snake, (rows + sched_teams - 1) / sched_teams * sched_teams, s)) return rc;
+        } else if (int rc = run_teamg_batch(h, a, snake, rpb, s)) return rc;
+        batch_rows_run = rpb;
     } else {
         return wrnn_fail(h, WRNN_ERR_INVALID, "kernel %d not available", kernel);
     }
     WRNN_HIP_TRY(h, hipEventRecord(h->ev[2], s));
     h->timing_valid = true;
     h->last.kernel = kernel; h->last.rows = rows; h->last.steps = steps; h->last.launches = launches;
+    h->last_batch_rows = batch_rows_run;
     return WRNN_OK;
 }
 

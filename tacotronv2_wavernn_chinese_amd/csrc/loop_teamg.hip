@@ -25,33 +25,9 @@
 //   5. fc3 rows of the own classes; RAW: + noise, race inside the workgroup, -> [32 candidates (value, class)], every workgroup
 //      picks the winner; MOL: -> [30 outputs], every workgroup runs the sampler                :223-237
 #include "team_common.h"
-
-#define TG_THREADS WRNN_TEAMG_THREADS
-#define TG_LDS_MAX (160 * 1024)
+#include "teamg_layout.h"
 
 namespace {
-
-__host__ __device__ inline int tg_r64(int n) { return (n + 63) & ~63; }
-
-// LDS carve-up of the activation vectors (floats); every vector is padded with zeros to the padded row length of the layer it feeds
-struct TgLay {
-    int HP, XAP, FAP, FCP, CK, CB;
-    int xh1, xh2, f1, f2, f3, cb, gs, misc, total;
-    __host__ __device__ TgLay(const WrnnDims &d) {
-        HP = tg_r64(d.H); XAP = tg_r64(d.H + d.A); FAP = tg_r64(d.FC + d.A); FCP = tg_r64(d.FC); CK = tg_r64(d.F + d.A);
-        CB = tg_r64(d.F + d.R) > CK ? tg_r64(d.F + d.R) : CK;
-        int o = 0;
-        xh1 = o; o += 2 * (HP + HP);     // [parity][x (HP) | h1 (HP)]            input of rnn1
-        xh2 = o; o += 2 * (XAP + HP);    // [parity][x2 | a2_t (XAP) | h2 (HP)]   input of rnn2
-        f1 = o; o += XAP;                // [x3 | a3_t]                           input of fc1
-        f2 = o; o += FAP;                // [relu(fc1) | a4_t]                    input of fc2
-        f3 = o; o += FCP;                // relu(fc2)                             input of fc3
-        cb = o; o += 2 * CB;             // [parity][m_t (F) | a_t (R)]           conditioning of a step; its head is the input of I
-        gs = o; o += 128;                // [16 units][3 gates][segment A sum, segment B sum] of a GRU layer split by gate rows
-        misc = o; o += 128;              // 0-2 team / rank / bail-out (team_common.h), 8 x_{t-1}, 32-63 race values, 64-95 race classes
-        total = o;
-    }
-};
 
 // G rows of one unit against one activation vector: wp = the unit's first row + lane q (float4), rows kp4 float4 apart; xp = the
 // vector + q.  Segment A = float4 steps [0, nA), segment B = [nA, nK): sa / sb are their sums (the n gate of a GRU needs them apart)
@@ -376,8 +352,9 @@ __global__ void __launch_bounds__(256) teamg_pack_kernel(const float *__restrict
 
 }  // namespace
 
-const char *wrnn_teamg_make_plan(const WrnnDims &d, int64_t budget, WrnnTeamGPlan &p) {
+const char *wrnn_teamg_make_plan(const WrnnDims &d, int64_t budget, WrnnTeamGPlan &p, int rows_per_team) {
     const TgLay ly(d);
+    const int RB = rows_per_team;
     p = WrnnTeamGPlan{};
     auto set = [&](int l, int N, int G, int KA, int KB) {
         WrnnTeamGLayer &L = p.L[l];
@@ -389,12 +366,18 @@ const char *wrnn_teamg_make_plan(const WrnnDims &d, int64_t budget, WrnnTeamGPla
     set(WRNN_TEAMG_RNN2, d.H, 3, d.H + d.A, d.H);
     set(WRNN_TEAMG_RNN1, d.H, 3, d.H, d.H);
     set(WRNN_TEAMG_COND, d.H, 1, d.F + d.A, 0);
-    p.act_floats = ly.total;
-    const int64_t act_bytes = (int64_t)ly.total * 4;
-    const int64_t granules = 2LL * (3 * ly.HP + 2 * ly.FCP + 64);
+    // one row: TgLay as ever; RB rows in lock-step: TgbLay, and every mailbox region once per row
+    const int64_t act_floats = RB == 1 ? ly.total : TgbLay(d, RB).total;
+    const int64_t act_bytes = act_floats * 4;
+    const int64_t granules = (int64_t)RB * 2LL * (3 * ly.HP + 2 * ly.FCP + 64);
+    if (act_bytes > TG_LDS_MAX)
+        return RB == 1 ? "WRNN_KERNEL_TEAMG: the activation vectors of one row exceed 160 KiB of LDS"
+                       : "WRNN_KERNEL_TEAMG_BATCH: the activation vectors of this many rows per team exceed 160 KiB of LDS";
+    if (granules > WRNN_MAIL_GRANULES_MAX)
+        return RB == 1 ? "WRNN_KERNEL_TEAMG: fc_dims too large for the team mailbox"
+                       : "WRNN_KERNEL_TEAMG_BATCH: the exchanges of this many rows per team exceed the team mailbox";
+    p.act_floats = (int32_t)act_floats;
     p.mail_granules = (int32_t)granules;
-    if (act_bytes > TG_LDS_MAX) return "WRNN_KERNEL_TEAMG: the activation vectors of one row exceed 160 KiB of LDS";
-    if (granules > WRNN_MAIL_GRANULES_MAX) return "WRNN_KERNEL_TEAMG: fc_dims too large for the team mailbox";
     if (d.mode == WRNN_MODE_MOL && d.NC > 64) return "WRNN_KERNEL_TEAMG: more than 64 mixture outputs";
     const int64_t dflt = TG_LDS_MAX - act_bytes;
     if (budget < 0 || budget > dflt) budget = dflt;
@@ -464,12 +447,12 @@ hipError_t wrnn_launch_loop_teamg(const WrnnTeamGArgs &a, hipStream_t s) {
 
 // ---- C ABI: the plan, host only ----
 
-extern "C" int wrnn_teamg_plan(const wrnn_config *cfg, int64_t lds_budget_bytes, wrnn_teamg_plan_info *out) {
-    if (!cfg || !out) return WRNN_ERR_INVALID;
+static int teamg_plan_info(const wrnn_config *cfg, int rows_per_team, int64_t lds_budget_bytes, wrnn_teamg_plan_info *out) {
+    if (!cfg || !out || rows_per_team < 1 || rows_per_team > WRNN_TEAMG_BATCH_MAX_ROWS) return WRNN_ERR_INVALID;
     WrnnDims d;
     if (wrnn_dims_from_config(cfg, d) || d.FC > (1 << 20) || d.F > (1 << 20)) return WRNN_ERR_INVALID;
     WrnnTeamGPlan p;
-    if (wrnn_teamg_make_plan(d, lds_budget_bytes, p)) return WRNN_ERR_UNSUPPORTED;
+    if (wrnn_teamg_make_plan(d, lds_budget_bytes, p, rows_per_team)) return WRNN_ERR_UNSUPPORTED;
     *out = wrnn_teamg_plan_info{};
     for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) {
         const WrnnTeamGLayer &L = p.L[l];
@@ -499,4 +482,12 @@ extern "C" int wrnn_teamg_plan(const wrnn_config *cfg, int64_t lds_budget_bytes,
     out->lds_budget_bytes = (lds_budget_bytes < 0 || lds_budget_bytes > TG_LDS_MAX - out->activation_bytes) ? TG_LDS_MAX - out->activation_bytes : lds_budget_bytes;
     out->mail_granules = p.mail_granules;
     return WRNN_OK;
+}
+
+extern "C" int wrnn_teamg_plan(const wrnn_config *cfg, int64_t lds_budget_bytes, wrnn_teamg_plan_info *out) {
+    return teamg_plan_info(cfg, 1, lds_budget_bytes, out);
+}
+
+extern "C" int wrnn_teamg_batch_plan(const wrnn_config *cfg, int32_t rows_per_team, int64_t lds_budget_bytes, wrnn_teamg_plan_info *out) {
+    return teamg_plan_info(cfg, rows_per_team, lds_budget_bytes, out);
 }

@@ -113,6 +113,7 @@ struct wrnn_handle {
     float *teamg_img = nullptr;   // TEAMG weight image [32 WGs][WrnnTeamGPlan::img_floats_wg], packed on the device by the first TEAMG call after a load
     bool teamg_img_ok = false;
     int64_t teamg_budget = -1;    // wrnn_debug_teamg_lds_budget: LDS bytes for resident weights, < 0 = the default
+    int last_batch_rows = 1;      // rows per team batch of the last generate call's loop kernel (wrnn_last_batch_rows)
     bool force_no_teams = false;  // wrnn_debug_force_no_teams: AUTO behaves as if residency had failed (tests of the slow-path warning)
     bool cs_ok = false;           // ... and loop_batch_cs_kernel in particular (AUTO falls back to WRNN_KERNEL_BATCH without it)
     float *tab = nullptr;         // CM|CA|VM|VA|C2|C3|C4 for the current batch
@@ -300,11 +301,30 @@ struct WrnnTeamGArgs {
     unsigned *ctl;
 };
 // pure host: ownership and placement for dims d with `budget` LDS bytes for resident weights (< 0 or too large: 160 KiB minus the
-// activation vectors); nullptr, or why the kernel cannot serve these dims
-const char *wrnn_teamg_make_plan(const WrnnDims &d, int64_t budget, WrnnTeamGPlan &p);
+// activation vectors); nullptr, or why the kernel cannot serve these dims.  rows_per_team = 1: loop_teamg.hip; 2, 4, 8: the lock-step
+// rows of loop_teamg_batch.hip, whose activation vectors (TgbLay, teamg_layout.h) and mailbox regions are counted that many times --
+// ownership and the weight image do not depend on it.
+const char *wrnn_teamg_make_plan(const WrnnDims &d, int64_t budget, WrnnTeamGPlan &p, int rows_per_team = 1);
 hipError_t wrnn_teamg_pack(const wrnn_handle *h, const WrnnTeamGPlan &p, float *img, hipStream_t s);
 hipError_t wrnn_teamg_occupancy(const WrnnTeamGPlan &p, int *blocks_per_cu);
 hipError_t wrnn_launch_loop_teamg(const WrnnTeamGArgs &a, hipStream_t s);
+
+// The same team kernel with RB = 2, 4 or 8 rows per team in lock-step (loop_teamg_batch.hip).  plan = wrnn_teamg_make_plan(.., RB).
+#define WRNN_TEAMG_BATCH_MAX_ROWS 8
+struct WrnnTeamGBatchArgs {
+    WrnnLoopArgs a;
+    WrnnTeamGPlan plan;
+    const float *img;          // the image of WRNN_KERNEL_TEAMG, shared
+    const int32_t *order;      // schedule slot -> row, as WrnnBatchArgs
+    int32_t rpb;               // rows placed in one batch (<= RB): batch b = slots [b * rpb, (b + 1) * rpb), it runs for the steps of its longest row
+    int32_t snake;             // != 0: batches are dealt to the teams in snake order (ragged batch), else round-robin
+    int32_t n_teams, pad_;
+    unsigned long long *mail;  // [n_teams][plan.mail_granules], row r of a team's batch at r * (plan.mail_granules / RB)
+    unsigned *ctl;
+};
+inline int wrnn_teamg_batch_inst(int rpb) { return rpb <= 2 ? 2 : (rpb <= 4 ? 4 : 8); }   // the instantiation that runs rpb rows
+hipError_t wrnn_teamg_batch_occupancy(const WrnnTeamGPlan &p, int rb, int *blocks_per_cu);
+hipError_t wrnn_launch_loop_teamg_batch(const WrnnTeamGBatchArgs &a, int rb, hipStream_t s);
 
 // Persistent team kernels of the two GRU recurrences of wrnn_train_step (train_team.hip)
 struct WrnnGruTeamArgs {

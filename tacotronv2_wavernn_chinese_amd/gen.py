@@ -112,7 +112,7 @@ def build_model_from_hparams() -> WaveRNN:
                    mode=hp.voc_mode)
 
 
-KERNEL_CHOICES = ('auto', 'simple', 'team2', 'batch', 'batch_cs', 'teamg')
+KERNEL_CHOICES = ('auto', 'simple', 'team2', 'batch', 'batch_cs', 'teamg', 'teamg_batch')
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -144,7 +144,8 @@ def build_parser() -> argparse.ArgumentParser:
                         help='The file to use for the hyperparameters')
     parser.add_argument('--kernel', choices=KERNEL_CHOICES, default='auto',
                         help="extension: the device loop kernel ('auto': the library's choice; 'teamg': the XCD-team kernel for any model "
-                             "dims, the fast path of a model whose dims are not the reference hparams)")
+                             "dims, the fast path of a model whose dims are not the reference hparams; 'teamg_batch': the same kernel with "
+                             "several rows per team in lock-step, for batched (fold) mode and other many-row calls of such a model)")
     parser.set_defaults(batched=None)
     return parser
 

@@ -105,7 +105,9 @@ def fold_plan(total_len: int, overlap: int, n_teams: int = 8, mode: str = 'RAW',
     a 5 s clip lands at 64 folds (8 per team, 2 265 steps, ~17 ms) against 47 ms for one fold per team.  Returns
     (target, folds, predicted_us); ties go to the smaller fold count (fewer crossfades).  ``min_target`` bounds the crossfade DENSITY
     from below (the latency optimum of a 5 s clip is a 550-sample crossfade every 1 715 samples: a third of the audio lies inside one;
-    ``min_target=5500`` gives 18 folds / 35 ms instead of 64 / 17 ms); a one-fold plan is always admissible."""
+    ``min_target=5500`` gives 18 folds / 35 ms instead of 64 / 17 ms); a one-fold plan is always admissible.
+    The step times are those of the 512 / 512 kernels (``STEP_US``) whatever the model: ``target='auto'`` uses them for a model on
+    ``kernel='teamg'`` / ``'teamg_batch'`` too -- a cost model for other dims is a follow-up."""
     best = None
     for n in range(1, 2 * ROWS_PER_TEAM_MAX * max(n_teams, 1) + 1):
         target = fold_target(total_len, overlap, n)
@@ -474,7 +476,9 @@ class WaveRNN(nn.Module):
         RAW noise1 (L, rows, n_classes) Exp(1) draws; MOL noise1 (L, rows, 10), noise2 (L, rows).
         frames: optional (B,) valid frames per utterance of a ragged, right-zero-padded batch (``wrnn_sample_opts.frames_dev``):
         row b runs frames[b] * hop steps, the rest of its output row is left unwritten (here: zero).
-        batch_rows / team2_segment: tuning knobs of the BATCH / TEAM2 kernels (0 = the library's choice).
+        batch_rows / team2_segment: tuning knobs of the BATCH, TEAMG_BATCH / TEAM2 kernels (0 = the library's choice).
+        kernel: None (the model's ``kernel``), a name of ``_cabi.KERNEL_IDS`` or a WRNN_KERNEL_* id; ``'teamg'`` / ``'teamg_batch'`` are
+        the XCD-team kernels for any model dims with one / several rows per team (``last_timing['batch_rows']`` says how many ran).
         seed (default 0) keys the Philox draws of the whole call by (seed, step, row): a row's draws depend on its place in the batch.
         seeds (unbatched calls only): B ints instead, one per utterance -- row b draws exactly what a call on utterance b alone with
         ``seed=seeds[b]`` draws (same kernel), whatever else is in the batch and wherever it stands (``request_seeds``).
@@ -622,7 +626,8 @@ class WaveRNN(nn.Module):
         self._slow_warned = True
         warnings.warn(f'WaveRNN: generating on the any-shape fallback kernel (WRNN_KERNEL_SIMPLE), ~1 ms per sample step -- about 300x slower '
                       f'than the XCD-team kernels ({steps} steps: ~{steps * 1e-3:.0f} s per row).  Reason: {why}.  A model of other dims runs an '
-                      f"XCD-team kernel with kernel='teamg' (generate_raw(..., kernel='teamg') or model.kernel = 'teamg').", RuntimeWarning, stacklevel=stacklevel)
+                      f"XCD-team kernel with kernel='teamg' (generate_raw(..., kernel='teamg') or model.kernel = 'teamg'), many rows at once -- folds, "
+                      f"generate_many -- with kernel='teamg_batch'.", RuntimeWarning, stacklevel=stacklevel)
 
     def epilogue_device(self, res, batched, target, overlap, mu_law, wave_len):
         """float64 tail of generate() (:243-258) on the GPU (``wrnn_epilogue``): (wave_len,) float64 cuda tensor."""
