@@ -368,6 +368,22 @@ int wrnn_debug_teamg_lds_budget(wrnn_handle *h, int64_t bytes);
 int wrnn_teamg_batch_plan(const wrnn_config *cfg, int32_t rows_per_team, int64_t lds_budget_bytes, wrnn_teamg_plan_info *out);
 /* Rows per team batch of the last generate call's loop kernel (the batch kernels); 1 for the one-row kernels and before any call. */
 int32_t wrnn_last_batch_rows(const wrnn_handle *h);
+/* Half-precision weight image for WRNN_KERNEL_TEAMG and WRNN_KERNEL_TEAMG_BATCH (added to ABI 9 like the above: new entry points only).
+ * WRNN_WEIGHTS_F16 stores the six matrices of the image as IEEE binary16, rounded to nearest even on the device with subnormals kept;
+ * activations, accumulators, biases, the sample's column of I, cells and samplers stay fp32.  An fp16 weight converts to fp32 exactly and
+ * the kernels multiply and add in the same order, so the outputs are bit-equal to the fp32 kernel's on a model whose matrices were
+ * rounded to fp16 beforehand.  The format is a property of the handle, for both kernels; the default is WRNN_WEIGHTS_F32 and no other
+ * kernel reads it.  Changing it drops the packed image, the next TEAMG / TEAMG_BATCH call packs again.  WRNN_ERR_INVALID: any other value.
+ * A weight that does not round to a finite fp16 (|w| >= 65520) is found by the pack: the generate call that packs waits once for that
+ * check and fails with WRNN_ERR_UNSUPPORTED, naming the layer; nothing is ever clamped, and the handle still generates in fp32. */
+#define WRNN_WEIGHTS_F32 0
+#define WRNN_WEIGHTS_F16 1
+int wrnn_teamg_set_weight_format(wrnn_handle *h, int32_t fmt);
+int32_t wrnn_teamg_weight_format(const wrnn_handle *h);
+/* wrnn_teamg_batch_plan for a weight format.  WRNN_WEIGHTS_F32: that function byte for byte.  WRNN_WEIGHTS_F16: ownership, k and k_padded
+ * (elements) are unchanged, every byte figure -- weight_bytes, resident_bytes_*, lds_bytes, streamed_bytes_step -- counts 2-byte
+ * weights, and more units fit the same budget.  activation_bytes and mail_granules do not depend on the format. */
+int wrnn_teamg_plan_fmt(const wrnn_config *cfg, int32_t rows_per_team, int32_t weight_format, int64_t lds_budget_bytes, wrnn_teamg_plan_info *out);
 
 /* ---- streaming generation (ABI 7) -------------------------------------------------------------------------------------------
  * Mel frames arrive a few at a time (Tacotron's decoder); audio leaves as soon as the frames it depends on are in.  A stream

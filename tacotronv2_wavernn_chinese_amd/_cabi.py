@@ -41,7 +41,8 @@ EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wr
                     'wrnn_quantise', 'wrnn_collate_windows',
                     'wrnn_resample_create', 'wrnn_resample_out_len', 'wrnn_resample_bank', 'wrnn_resample', 'wrnn_resample_last_error',
                     'wrnn_resample_destroy', 'wrnn_condition_frames', 'wrnn_condition', 'wrnn_teamg_plan', 'wrnn_debug_teamg_lds_budget',
-                    'wrnn_teamg_batch_plan', 'wrnn_last_batch_rows')
+                    'wrnn_teamg_batch_plan', 'wrnn_last_batch_rows', 'wrnn_teamg_set_weight_format', 'wrnn_teamg_weight_format',
+                    'wrnn_teamg_plan_fmt')
 
 
 def epilogue_tables(n_classes: int, overlap: int, hop: int):
@@ -105,6 +106,8 @@ class MelConfig(C.Structure):
                 ('n_mels', C.c_int32), ('fmin', C.c_float), ('min_level_db', C.c_float), ('device', C.c_int32)]
 
 
+WEIGHT_FORMATS = {'f32': 0, 'f16': 1}   # WRNN_WEIGHTS_*: the element type of the TEAMG / TEAMG_BATCH weight image
+WEIGHT_FORMAT_NAMES = {v: k for k, v in WEIGHT_FORMATS.items()}
 TEAMG_LAYER_NAMES = ('fc3', 'fc2', 'fc1', 'rnn2', 'rnn1', 'cond')   # WRNN_TEAMG_*: the order in which layers are given LDS residency
 
 
@@ -121,11 +124,12 @@ class TeamgPlanInfo(C.Structure):
 
 
 def teamg_plan(lds_budget_bytes: int = -1, *, rnn_dims, fc_dims, bits, pad, upsample_factors, feat_dims, compute_dims, res_out_dims,
-               res_blocks, hop_length, sample_rate=22050, mode='RAW', rows_per_team=None) -> dict:
+               res_blocks, hop_length, sample_rate=22050, mode='RAW', rows_per_team=None, weights=None) -> dict:
     """Host-only ``wrnn_teamg_plan``: how WRNN_KERNEL_TEAMG splits a model of these constructor dims over the 32 workgroups of a team and
     what it keeps in LDS with ``lds_budget_bytes`` for resident weights (< 0: the default, 160 KiB minus the activation vectors).
     ``layers``: name -> dict of the ``wrnn_teamg_layer_info`` fields (``own_first`` / ``own_count`` as lists of 32).
-    ``rows_per_team``: ``wrnn_teamg_batch_plan`` instead (see :func:`teamg_batch_plan`)."""
+    ``rows_per_team``: ``wrnn_teamg_batch_plan`` instead (see :func:`teamg_batch_plan`); ``weights``: ``wrnn_teamg_plan_fmt`` instead (see
+    :func:`teamg_plan_fmt`)."""
     cfg = Config()
     cfg.rnn_dims, cfg.fc_dims, cfg.bits, cfg.pad = rnn_dims, fc_dims, bits, pad
     cfg.n_upsample = len(upsample_factors)
@@ -135,7 +139,13 @@ def teamg_plan(lds_budget_bytes: int = -1, *, rnn_dims, fc_dims, bits, pad, upsa
     cfg.res_blocks, cfg.hop_length, cfg.sample_rate = res_blocks, hop_length, sample_rate
     cfg.mode = MODE_RAW if mode == 'RAW' else MODE_MOL
     info = TeamgPlanInfo()
-    if rows_per_team is None:
+    if weights is not None:
+        if weights not in WEIGHT_FORMATS:
+            raise ValueError(f'weights must be one of {sorted(WEIGHT_FORMATS)}, not {weights!r}')
+        rows = 1 if rows_per_team is None else int(rows_per_team)
+        rc = load_library().wrnn_teamg_plan_fmt(C.byref(cfg), rows, WEIGHT_FORMATS[weights], int(lds_budget_bytes), C.byref(info))
+        what = f'wrnn_teamg_plan_fmt({rows} rows per team, {weights} weights)'
+    elif rows_per_team is None:
         rc, what = load_library().wrnn_teamg_plan(C.byref(cfg), int(lds_budget_bytes), C.byref(info)), 'wrnn_teamg_plan'
     else:
         rc = load_library().wrnn_teamg_batch_plan(C.byref(cfg), int(rows_per_team), int(lds_budget_bytes), C.byref(info))
@@ -156,6 +166,12 @@ def teamg_batch_plan(rows_per_team: int, lds_budget_bytes: int = -1, **dims) -> 
     2, 4, 8: the kernel's instantiations).  Same dict as :func:`teamg_plan`; ``activation_bytes`` and ``mail_granules`` are for that many
     rows.  ``WrnnError``: WRNN_ERR_INVALID outside 1..8, WRNN_ERR_UNSUPPORTED when the rows' vectors or mailbox regions do not fit."""
     return teamg_plan(lds_budget_bytes, rows_per_team=int(rows_per_team), **dims)
+
+
+def teamg_plan_fmt(rows_per_team: int, weights: str, lds_budget_bytes: int = -1, **dims) -> dict:
+    """Host-only ``wrnn_teamg_plan_fmt``: :func:`teamg_batch_plan` for the weight image format ``weights`` ('f32' or 'f16').  Same dict; with
+    'f16' every byte figure counts 2-byte weights and more units fit the same LDS budget, ownership and ``k_padded`` are unchanged."""
+    return teamg_plan(lds_budget_bytes, rows_per_team=int(rows_per_team), weights=weights, **dims)
 
 
 _lib: Optional[C.CDLL] = None
@@ -261,6 +277,12 @@ def load_library() -> C.CDLL:
     lib.wrnn_debug_teamg_lds_budget.restype = C.c_int
     lib.wrnn_teamg_batch_plan.argtypes = [C.POINTER(Config), C.c_int32, C.c_int64, C.POINTER(TeamgPlanInfo)]
     lib.wrnn_teamg_batch_plan.restype = C.c_int
+    lib.wrnn_teamg_plan_fmt.argtypes = [C.POINTER(Config), C.c_int32, C.c_int32, C.c_int64, C.POINTER(TeamgPlanInfo)]
+    lib.wrnn_teamg_plan_fmt.restype = C.c_int
+    lib.wrnn_teamg_set_weight_format.argtypes = [vp, C.c_int32]
+    lib.wrnn_teamg_set_weight_format.restype = C.c_int
+    lib.wrnn_teamg_weight_format.argtypes = [vp]
+    lib.wrnn_teamg_weight_format.restype = C.c_int32
     lib.wrnn_last_batch_rows.argtypes = [vp]
     lib.wrnn_last_batch_rows.restype = C.c_int32
     lib.wrnn_stream_open.argtypes = [vp, C.c_int32, C.POINTER(SampleOpts), C.POINTER(vp)]
@@ -530,11 +552,22 @@ class NativeVocoder:
         """Test hook: the following WRNN_KERNEL_TEAMG / WRNN_KERNEL_TEAMG_BATCH calls place their weights with this LDS budget (< 0: the default)."""
         self._check(self.lib.wrnn_debug_teamg_lds_budget(self._h, int(lds_budget_bytes)))
 
+    def set_teamg_weights(self, fmt: str):
+        """The element type of the TEAMG / TEAMG_BATCH weight image, 'f32' or 'f16' (``wrnn_teamg_set_weight_format``); a change makes the next
+        call of either kernel pack the image again.  No other kernel reads it."""
+        if fmt not in WEIGHT_FORMATS:
+            raise ValueError(f'teamg weights must be one of {sorted(WEIGHT_FORMATS)}, not {fmt!r}')
+        self._check(self.lib.wrnn_teamg_set_weight_format(self._h, WEIGHT_FORMATS[fmt]))
+
+    @property
+    def teamg_weights(self) -> str:
+        return WEIGHT_FORMAT_NAMES[int(self.lib.wrnn_teamg_weight_format(self._h))]
+
     def last_timing(self) -> dict:
         t = Timing()
         self._check(self.lib.wrnn_last_timing(self._h, C.byref(t)))
         return dict(prologue_ms=t.prologue_ms, loop_ms=t.loop_ms, kernel=t.kernel, rows=t.rows, steps=t.steps,
-                    launches=t.launches, batch_rows=int(self.lib.wrnn_last_batch_rows(self._h)))
+                    launches=t.launches, batch_rows=int(self.lib.wrnn_last_batch_rows(self._h)), teamg_weights=self.teamg_weights)
 
 
 def plan_folded(frames, hop: int, target: int, overlap: int) -> Tuple[np.ndarray, int]:

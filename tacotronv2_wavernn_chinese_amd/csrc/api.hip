@@ -233,6 +233,14 @@ int wrnn_debug_teamg_lds_budget(wrnn_handle *h, int64_t bytes) {
     h->teamg_budget = bytes < 0 ? -1 : bytes;
     return WRNN_OK;
 }
+int wrnn_teamg_set_weight_format(wrnn_handle *h, int32_t fmt) {
+    if (!h) return WRNN_ERR_INVALID;
+    if (fmt != WRNN_WEIGHTS_F32 && fmt != WRNN_WEIGHTS_F16) return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_teamg_set_weight_format: %d is neither WRNN_WEIGHTS_F32 nor WRNN_WEIGHTS_F16", fmt);
+    if (fmt != h->teamg_fmt) h->teamg_img_ok = false;   // the next TEAMG / TEAMG_BATCH call packs the image in the new element type
+    h->teamg_fmt = fmt;
+    return WRNN_OK;
+}
+int32_t wrnn_teamg_weight_format(const wrnn_handle *h) { return h ? h->teamg_fmt : WRNN_WEIGHTS_F32; }
 int32_t wrnn_n_classes(const wrnn_handle *h) { return h ? h->d.NC : 0; }
 int64_t wrnn_loop_weight_bytes(const wrnn_handle *h) { return h ? h->loop_weight_bytes : 0; }
 
@@ -579,26 +587,37 @@ static int run_team2(wrnn_handle *h, const WrnnLoopArgs &a, const WrnnFrameTable
     return wrnn_run_team2_segments(h, ta, h->cond, 0, a.steps, seg, launches, s);
 }
 
+// The weight image of both kernels for any dims, in the handle's format: packed by the first call after a load or a format change.  The
+// fp16 pack waits once for its range check; a weight with no finite fp16 fails the call and leaves no image.
+static int teamg_image(wrnn_handle *h, const WrnnTeamGPlan &plan, hipStream_t s) {
+    if (h->teamg_img_ok) return WRNN_OK;
+    if (h->teamg_img) { (void)hipFree(h->teamg_img); h->teamg_img = nullptr; }
+    WRNN_HIP_TRY(h, hipMalloc(&h->teamg_img, wrnn_teamg_img_bytes(plan)));
+    int bad = -1;
+    WRNN_HIP_TRY(h, wrnn_teamg_pack(h, plan, h->teamg_img, s, &bad));
+    if (bad >= 0)
+        return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "WRNN_WEIGHTS_F16: a weight of layer %s does not round to a finite fp16 (|w| >= 65520); use WRNN_WEIGHTS_F32 for this model",
+                         wrnn_teamg_layer_names[bad]);
+    h->teamg_img_ok = true;
+    WRNN_HIP_TRY(h, hipEventRecord(h->ev[1], s));   // the one-time image is not loop time
+    return WRNN_OK;
+}
+static int teamg_esz(const wrnn_handle *h) { return h->teamg_fmt == WRNN_WEIGHTS_F16 ? 2 : 4; }
+
 // The team kernel for any dims (loop_teamg.hip): one row per XCD team at a time, one launch.  Placement and residency are settled here,
 // before the launch; whatever keeps the kernel from running is an error with its reason, never another kernel.
 static int run_teamg(wrnn_handle *h, const WrnnLoopArgs &a, int snake, int n_slots, hipStream_t s) {
     if (h->force_no_teams) return wrnn_fail(h, WRNN_ERR_INVALID, "team kernels disabled by wrnn_debug_force_no_teams (test hook)");
     if (h->n_teams < 1) return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "WRNN_KERNEL_TEAMG: fewer than 32 CUs visible (one team = the 32 CUs of an XCD)");
     WrnnTeamGArgs ga{};
-    if (const char *why = wrnn_teamg_make_plan(a.d, h->teamg_budget, ga.plan)) return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "%s", why);
+    if (const char *why = wrnn_teamg_make_plan(a.d, h->teamg_budget, ga.plan, 1, teamg_esz(h))) return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "%s", why);
     int blocks = 0;
     const hipError_t oe = wrnn_teamg_occupancy(ga.plan, &blocks);
     (void)hipGetLastError();
     if (oe != hipSuccess || blocks < 1)
         return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "WRNN_KERNEL_TEAMG: loop_teamg_kernel cannot be resident on a CU with %zu bytes of LDS (%s)",
-                         ((size_t)ga.plan.act_floats + ga.plan.res_floats) * sizeof(float), oe != hipSuccess ? hipGetErrorString(oe) : "occupancy 0");
-    if (!h->teamg_img_ok) {
-        if (h->teamg_img) { (void)hipFree(h->teamg_img); h->teamg_img = nullptr; }
-        WRNN_HIP_TRY(h, hipMalloc(&h->teamg_img, (size_t)32 * ga.plan.img_floats_wg * sizeof(float)));
-        WRNN_HIP_TRY(h, wrnn_teamg_pack(h, ga.plan, h->teamg_img, s));
-        h->teamg_img_ok = true;
-        WRNN_HIP_TRY(h, hipEventRecord(h->ev[1], s));   // the one-time image is not loop time
-    }
+                         wrnn_teamg_lds_bytes(ga.plan), oe != hipSuccess ? hipGetErrorString(oe) : "occupancy 0");
+    if (int rc = teamg_image(h, ga.plan, s)) return rc;
     ga.a = a; ga.img = h->teamg_img; ga.sched = h->sched_dev; ga.n_slots = n_slots; ga.ragged = snake; ga.n_teams = h->n_teams;
     ga.mail = h->mail; ga.ctl = h->ctl;
     const size_t mail_bytes = (size_t)h->n_teams * ga.plan.mail_granules * sizeof(unsigned long long);   // sized from the dims; <= WRNN_MAIL_BYTES
@@ -613,20 +632,14 @@ static int run_teamg_batch(wrnn_handle *h, const WrnnLoopArgs &a, int snake, int
     if (h->n_teams < 1) return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "WRNN_KERNEL_TEAMG_BATCH: fewer than 32 CUs visible (one team = the 32 CUs of an XCD)");
     const int rb = wrnn_teamg_batch_inst(rpb);
     WrnnTeamGBatchArgs ga{};
-    if (const char *why = wrnn_teamg_make_plan(a.d, h->teamg_budget, ga.plan, rb)) return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "%s (batch_rows %d runs as %d)", why, rpb, rb);
+    if (const char *why = wrnn_teamg_make_plan(a.d, h->teamg_budget, ga.plan, rb, teamg_esz(h))) return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "%s (batch_rows %d runs as %d)", why, rpb, rb);
     int blocks = 0;
     const hipError_t oe = wrnn_teamg_batch_occupancy(ga.plan, rb, &blocks);
     (void)hipGetLastError();
     if (oe != hipSuccess || blocks < 1)
         return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "WRNN_KERNEL_TEAMG_BATCH: loop_teamg_batch_kernel<%d> cannot be resident on a CU with %zu bytes of LDS (%s)", rb,
-                         ((size_t)ga.plan.act_floats + ga.plan.res_floats) * sizeof(float), oe != hipSuccess ? hipGetErrorString(oe) : "occupancy 0");
-    if (!h->teamg_img_ok) {
-        if (h->teamg_img) { (void)hipFree(h->teamg_img); h->teamg_img = nullptr; }
-        WRNN_HIP_TRY(h, hipMalloc(&h->teamg_img, (size_t)32 * ga.plan.img_floats_wg * sizeof(float)));
-        WRNN_HIP_TRY(h, wrnn_teamg_pack(h, ga.plan, h->teamg_img, s));
-        h->teamg_img_ok = true;
-        WRNN_HIP_TRY(h, hipEventRecord(h->ev[1], s));   // the one-time image is not loop time
-    }
+                         wrnn_teamg_lds_bytes(ga.plan), oe != hipSuccess ? hipGetErrorString(oe) : "occupancy 0");
+    if (int rc = teamg_image(h, ga.plan, s)) return rc;
     ga.a = a; ga.img = h->teamg_img; ga.order = h->order_dev; ga.rpb = rpb; ga.snake = snake; ga.n_teams = h->n_teams;
     ga.mail = h->mail; ga.ctl = h->ctl;
     const size_t mail_bytes = (size_t)h->n_teams * ga.plan.mail_granules * sizeof(unsigned long long);   // <= WRNN_MAIL_BYTES: the plan refuses more
@@ -716,7 +729,7 @@ static int generate_impl(wrnn_handle *h, const float *mels_dev, int32_t B, int32
         if (opts->batch_rows > 0) rpb = opts->batch_rows;
         else {
             WrnnTeamGPlan probe;
-            while (rpb > 1 && wrnn_teamg_make_plan(d, h->teamg_budget, probe, wrnn_teamg_batch_inst(rpb))) rpb = wrnn_teamg_batch_inst(rpb) / 2;
+            while (rpb > 1 && wrnn_teamg_make_plan(d, h->teamg_budget, probe, wrnn_teamg_batch_inst(rpb), teamg_esz(h))) rpb = wrnn_teamg_batch_inst(rpb) / 2;
         }
         if (rpb == 1) {
             kernel = WRNN_KERNEL_TEAMG;

@@ -15,6 +15,12 @@
 // of every layer are copied to LDS at the start of a launch and stay there, the rest is read every step from L2 / Infinity Cache with
 // the same 16-byte loads.  Weights are read-only during a launch: plain loads.  wrnn_teamg_make_plan decides nres.
 //
+// Element type.  The kernel is templated on the type of the image's elements: float, or _Float16 (WRNN_WEIGHTS_F16) --
+// half the bytes streamed, twice the units resident, rows permuted at pack time so that a lane's 16-byte load brings the weights of two
+// steps (teamg_layout.h).  Only the six matrices change type; activations, sums, biases, W_I[:, 0], cells and samplers are fp32, and
+// since a binary16 widens exactly and the multiply-adds keep their order, the outputs are those of the fp32 instantiation on the model
+// with its matrices rounded to fp16.
+//
 // One step = five exchanges on the serial chain plus one beside it:
 //   [xc]  the conditioning's share of I, W_I[:, 1:] . [m_t | a1_t] + b_I, for step t + 1 -- published under exchange 2 of step t
 //   x = xc + W_I[:, 0] x_{t-1}                                                             :208-209 (every workgroup, all H)
@@ -24,6 +30,8 @@
 //   4. relu(fc2 . [fc1 | a4_t])                                      -> [fc2]                :220-221
 //   5. fc3 rows of the own classes; RAW: + noise, race inside the workgroup, -> [32 candidates (value, class)], every workgroup
 //      picks the winner; MOL: -> [30 outputs], every workgroup runs the sampler                :223-237
+#include <type_traits>
+
 #include "team_common.h"
 #include "teamg_layout.h"
 
@@ -62,6 +70,70 @@ __device__ __forceinline__ void tg_dot(const float4 *__restrict__ wp, int kp4, c
     for (int g = 0; g < G; ++g) sb[g] = row_sum(a0[g] + a1[g]);
 }
 
+// tg_dot on the fp16 image (teamg_layout.h): rp = the unit's first row, rows kp8 16-byte pieces apart, row0 its index in the slice.  One
+// 16-byte load per row and PAIR of steps, four pairs issued together -- tg_dot's bytes in flight --, an 8-byte load for the unpaired last step
+// of a segment; per step the same four weights, widened exactly, into the same a0 / a1 chains in the same order.
+template <int G>
+__device__ __forceinline__ void tg_dot16(const TgHalf8 *__restrict__ rp, int kp8, int row0, int q, const float4 *xp, int nA, int nK, float (&sa)[G],
+                                         float (&sb)[G]) {
+    const TgHalf8 *wp[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) wp[g] = rp + (size_t)g * kp8 + (q ^ tg16_swz(row0 + g, kp8 * 8));
+    float a0[G], a1[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) a0[g] = a1[g] = 0.0f;
+    auto mac = [&](int g, const float4 &w, const float4 &x) {
+        a0[g] = fmaf(w.x, x.x, a0[g]); a1[g] = fmaf(w.y, x.y, a1[g]);
+        a0[g] = fmaf(w.z, x.z, a0[g]); a1[g] = fmaf(w.w, x.w, a1[g]);
+    };
+    // NP pairs of steps from step k: their weight loads are issued together
+    auto block = [&](auto np, int k) {
+        constexpr int NP = decltype(np)::value;
+        TgHalf8 w[NP][G];
+#pragma unroll
+        for (int u = 0; u < NP; ++u)
+#pragma unroll
+            for (int g = 0; g < G; ++g) w[u][g] = wp[g][(k + 2 * u) * 8];
+#pragma unroll
+        for (int u = 0; u < NP; ++u) {
+            const float4 x0 = xp[(k + 2 * u) * 16], x1 = xp[(k + 2 * u + 1) * 16];
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                mac(g, tg_lo4(w[u][g]), x0);
+                mac(g, tg_hi4(w[u][g]), x1);
+            }
+        }
+    };
+    // four pairs at a time, then what is left as one block of two and one of one: a short segment (4 steps at rnn_dims 256) still has
+    // all its loads in flight at once, as tg_dot's unrolled loop has them
+    auto segment = [&](int k0, int k1) {
+        int k = k0;
+#pragma unroll 1
+        for (; k + 8 <= k1; k += 8) block(std::integral_constant<int, 4>{}, k);
+        if (k + 4 <= k1) { block(std::integral_constant<int, 2>{}, k); k += 4; }
+        if (k + 2 <= k1) { block(std::integral_constant<int, 1>{}, k); k += 2; }
+        if (k < k1) {
+            const float4 x = xp[k * 16];
+#pragma unroll
+            for (int g = 0; g < G; ++g) mac(g, tg_w4(((const TgHalf4 *)(rp + (size_t)g * kp8))[k * 16 + q]), x);
+        }
+    };
+    segment(0, nA);
+#pragma unroll
+    for (int g = 0; g < G; ++g) { sa[g] = row_sum(a0[g] + a1[g]); a0[g] = a1[g] = 0.0f; }
+    segment(nA, nK);
+#pragma unroll
+    for (int g = 0; g < G; ++g) sb[g] = row_sum(a0[g] + a1[g]);
+}
+
+// G rows from row `row0` of a layer's slice at `base` (LDS or device memory), KP elements each, in the image's element type
+template <int G, typename WT>
+__device__ __forceinline__ void tg_rows(const WT *base, int row0, int KP, int q, const float4 *xp, int nA, int nK, float (&sa)[G], float (&sb)[G]) {
+    if constexpr (sizeof(WT) == 4) tg_dot<G>((const float4 *)(base + (size_t)row0 * KP) + q, KP / 4, xp, nA, nK, sa, sb);
+    else tg_dot16<G>((const TgHalf8 *)(base + (size_t)row0 * KP), KP / 8, row0, q, xp, nA, nK, sa, sb);
+}
+
+template <typename WT>
 __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta) {
     extern __shared__ __attribute__((aligned(16))) char smem_tg[];
     float *lds = (float *)smem_tg;
@@ -73,7 +145,7 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
     float *misc = lds + ly.misc;
     int *misc_i = (int *)misc;
     float *f1 = lds + ly.f1, *f2 = lds + ly.f2, *f3 = lds + ly.f3;
-    float *wres = lds + ly.total;   // resident weights
+    WT *wres = (WT *)(lds + ly.total);   // resident weights, in the image's element type
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int qw = tid >> 4, q = tid & 15;
@@ -85,12 +157,12 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
     // mailbox regions (granules), two parities each
     const unsigned M_XC = 0, M_H1 = 2 * HP, M_H2 = 4 * HP, M_F1 = 6 * HP, M_F2 = 6 * HP + 2 * FCP, M_CAND = 6 * HP + 4 * FCP;
     const float *w = a.w;
-    const float *img = ta.img + (size_t)g * ta.plan.img_floats_wg;
+    const WT *img = (const WT *)ta.img + (size_t)g * ta.plan.img_elems_wg;
 
     // ---- resident weights, zeroed activations ----
     for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) {
         const WrnnTeamGLayer &L = ta.plan.L[l];
-        const int n4 = L.nres * L.G * (L.KP / 4);
+        const int n4 = L.nres * L.G * (L.KP / 4) / (int)(sizeof(float) / sizeof(WT));   // 16-byte pieces: KP is a multiple of 64 elements
         const float4 *src = (const float4 *)(img + L.img_off);
         float4 *dst = (float4 *)(wres + L.lds_off);
         for (int i = tid; i < n4; i += TG_THREADS) dst[i] = src[i];
@@ -131,11 +203,11 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
     // the own rows of W_I[:, 1:] . [m | a1] + b_I for the step whose conditioning is in cbuf -> mailbox, tagged `tag`
     auto xc_publish = [&](const float *cbuf, unsigned tag) {
         const WrnnTeamGLayer &L = ta.plan.L[WRNN_TEAMG_COND];
-        const int nown = owned(L), kp4 = L.KP / 4, nK = L.KP / 64;
+        const int nown = owned(L), nK = L.KP / 64;
         for (int ul = qw; ul < nown; ul += 32) {
             float sa[1], sb[1];
-            if (ul < L.nres) tg_dot<1>((const float4 *)(wres + L.lds_off + (size_t)ul * L.KP) + q, kp4, (const float4 *)cbuf + q, nK, nK, sa, sb);
-            else tg_dot<1>((const float4 *)(img + L.img_off + (size_t)ul * L.KP) + q, kp4, (const float4 *)cbuf + q, nK, nK, sa, sb);
+            if (ul < L.nres) tg_rows<1>(wres + L.lds_off, ul, L.KP, q, (const float4 *)cbuf + q, nK, nK, sa, sb);
+            else tg_rows<1>(img + L.img_off, ul, L.KP, q, (const float4 *)cbuf + q, nK, nK, sa, sb);
             const int j = g * L.U + ul;
             if (q == 0) st_granule(mail, M_XC + (tag & 1u) * HP + j, tag, __float_as_uint(sa[0] + w[a.off.I_b + j]));
         }
@@ -144,15 +216,15 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
     // With 16 or fewer units per workgroup (rnn_dims <= 512) a unit per 16-lane group would leave half the groups, and their loads in
     // flight, idle: then a group takes one gate ROW, the sums meet in LDS and one lane per unit finishes the cell.  Same sums either way.
     auto gru_phase = [&](const WrnnTeamGLayer &L, const float *xin, size_t obih, size_t obhh, unsigned region, unsigned epoch) {
-        const int nown = owned(L), kp4 = L.KP / 4, nA = L.KAP / 64, nK = L.KP / 64;
+        const int nown = owned(L), nA = L.KAP / 64, nK = L.KP / 64;
         const bool by_row = L.U <= 16;
         if (by_row) {
             float *gs = lds + ly.gs;
             for (int task = qw; task < 3 * nown; task += 32) {
                 const int ul = task / 3;
                 float sa[1], sb[1];
-                if (ul < L.nres) tg_dot<1>((const float4 *)(wres + L.lds_off + (size_t)task * L.KP) + q, kp4, (const float4 *)xin + q, nA, nK, sa, sb);
-                else tg_dot<1>((const float4 *)(img + L.img_off + (size_t)task * L.KP) + q, kp4, (const float4 *)xin + q, nA, nK, sa, sb);
+                if (ul < L.nres) tg_rows<1>(wres + L.lds_off, task, L.KP, q, (const float4 *)xin + q, nA, nK, sa, sb);
+                else tg_rows<1>(img + L.img_off, task, L.KP, q, (const float4 *)xin + q, nA, nK, sa, sb);
                 if (q == 0) { gs[2 * task] = sa[0]; gs[2 * task + 1] = sb[0]; }
             }
             __syncthreads();
@@ -162,8 +234,8 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
             if (by_row) {
                 const float *gs = lds + ly.gs + 6 * ul;
                 gi[0] = gs[0]; gh[0] = gs[1]; gi[1] = gs[2]; gh[1] = gs[3]; gi[2] = gs[4]; gh[2] = gs[5];
-            } else if (ul < L.nres) tg_dot<3>((const float4 *)(wres + L.lds_off + (size_t)ul * 3 * L.KP) + q, kp4, (const float4 *)xin + q, nA, nK, gi, gh);
-            else tg_dot<3>((const float4 *)(img + L.img_off + (size_t)ul * 3 * L.KP) + q, kp4, (const float4 *)xin + q, nA, nK, gi, gh);
+            } else if (ul < L.nres) tg_rows<3>(wres + L.lds_off, ul * 3, L.KP, q, (const float4 *)xin + q, nA, nK, gi, gh);
+            else tg_rows<3>(img + L.img_off, ul * 3, L.KP, q, (const float4 *)xin + q, nA, nK, gi, gh);
             const int j = g * L.U + ul;
             const float *bi = w + obih, *bh = w + obhh;
             const float rg = 1.0f / (1.0f + expf(-((gi[0] + bi[j]) + (gh[0] + bh[j]))));
@@ -175,11 +247,11 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
     };
     // relu(W . x + b) of the own rows -> mailbox
     auto fc_phase = [&](const WrnnTeamGLayer &L, const float *xin, size_t ob, unsigned region, unsigned epoch) {
-        const int nown = owned(L), kp4 = L.KP / 4, nK = L.KP / 64;
+        const int nown = owned(L), nK = L.KP / 64;
         for (int ul = qw; ul < nown; ul += 32) {
             float sa[1], sb[1];
-            if (ul < L.nres) tg_dot<1>((const float4 *)(wres + L.lds_off + (size_t)ul * L.KP) + q, kp4, (const float4 *)xin + q, nK, nK, sa, sb);
-            else tg_dot<1>((const float4 *)(img + L.img_off + (size_t)ul * L.KP) + q, kp4, (const float4 *)xin + q, nK, nK, sa, sb);
+            if (ul < L.nres) tg_rows<1>(wres + L.lds_off, ul, L.KP, q, (const float4 *)xin + q, nK, nK, sa, sb);
+            else tg_rows<1>(img + L.img_off, ul, L.KP, q, (const float4 *)xin + q, nK, nK, sa, sb);
             const int j = g * L.U + ul;
             if (q == 0) st_granule(mail, region + (epoch & 1u) * FCP + j, epoch, __float_as_uint(fmaxf(sa[0] + w[ob + j], 0.0f)));
         }
@@ -258,13 +330,13 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
             // ---- 5. logits = fc3(x) :223 of the own classes, and the sampler :225-237 ----
             {
                 const WrnnTeamGLayer &L = ta.plan.L[WRNN_TEAMG_FC3];
-                const int nown = owned(L), kp4 = L.KP / 4, nK = L.KP / 64;
+                const int nown = owned(L), nK = L.KP / 64;
                 float bv = -INFINITY;
                 int bi = 0x7fffffff;
                 for (int ul = qw; ul < nown; ul += 32) {
                     float sa[1], sb[1];
-                    if (ul < L.nres) tg_dot<1>((const float4 *)(wres + L.lds_off + (size_t)ul * L.KP) + q, kp4, (const float4 *)f3 + q, nK, nK, sa, sb);
-                    else tg_dot<1>((const float4 *)(img + L.img_off + (size_t)ul * L.KP) + q, kp4, (const float4 *)f3 + q, nK, nK, sa, sb);
+                    if (ul < L.nres) tg_rows<1>(wres + L.lds_off, ul, L.KP, q, (const float4 *)f3 + q, nK, nK, sa, sb);
+                    else tg_rows<1>(img + L.img_off, ul, L.KP, q, (const float4 *)f3 + q, nK, nK, sa, sb);
                     const int c = g * L.U + ul;
                     const float lg = sa[0] + w[a.off.fc3_b + c];
                     if (a.logits_out && q == 0) a.logits_out[((size_t)t * a.n_rows + row) * NC + c] = lg;
@@ -341,21 +413,37 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
     }
 }
 
-// dst(g, ul, gate, kdst + k) = src_t[(k0 + k) * ld + row0 + g * U + ul] for the units that exist; the image was zeroed
-__global__ void __launch_bounds__(256) teamg_pack_kernel(const float *__restrict__ src_t, int ld, int row0, int k0, int K, float *__restrict__ img,
-                                                         size_t wg_stride, size_t layer_off, int N, int U, int G, int gate, int KP, int kdst) {
+// dst(g, ul, gate, kdst + k) = src_t[(k0 + k) * ld + row0 + g * U + ul] for the units that exist; the image was zeroed.
+// WT = _Float16: element kdst + k of the row goes where teamg_layout.h's paired layout puts it (tg16_pos), rounded to nearest even with
+// subnormals kept (the conversion instruction in the kernel's default modes); a result that is not finite -- |w| >= 65520, or a weight
+// that was not finite -- sets *bad and is never clamped.
+template <typename WT>
+__global__ void __launch_bounds__(256) teamg_pack_kernel(const float *__restrict__ src_t, int ld, int row0, int k0, int K, WT *__restrict__ img,
+                                                         size_t wg_stride, size_t layer_off, int N, int U, int G, int gate, int KAP, int KP, int kdst, int32_t *bad) {
     const int unit = blockIdx.x;   // < N
     const int g = unit / U, ul = unit - g * U;
-    float *dst = img + (size_t)g * wg_stride + layer_off + ((size_t)ul * G + gate) * KP + kdst;
-    for (int k = threadIdx.x; k < K; k += 256) dst[k] = src_t[(size_t)(k0 + k) * ld + row0 + unit];
+    const int row = ul * G + gate;
+    WT *dst = img + (size_t)g * wg_stride + layer_off + (size_t)row * KP;
+    for (int k = threadIdx.x; k < K; k += 256) {
+        const WT v = (WT)src_t[(size_t)(k0 + k) * ld + row0 + unit];
+        if constexpr (sizeof(WT) == 2) {
+            if (!(fabsf((float)v) <= 65504.0f)) *bad = 1;
+            dst[tg16_pos(kdst + k, row, KAP, KP)] = v;
+        } else {
+            dst[kdst + k] = v;
+        }
+    }
 }
 
 }  // namespace
 
-const char *wrnn_teamg_make_plan(const WrnnDims &d, int64_t budget, WrnnTeamGPlan &p, int rows_per_team) {
+const char *const wrnn_teamg_layer_names[WRNN_TEAMG_LAYERS] = {"fc3", "fc2", "fc1", "rnn2", "rnn1", "I"};
+
+const char *wrnn_teamg_make_plan(const WrnnDims &d, int64_t budget, WrnnTeamGPlan &p, int rows_per_team, int esz) {
     const TgLay ly(d);
     const int RB = rows_per_team;
     p = WrnnTeamGPlan{};
+    p.esz = esz;
     auto set = [&](int l, int N, int G, int KA, int KB) {
         WrnnTeamGLayer &L = p.L[l];
         L.N = N; L.G = G; L.KA = KA; L.KB = KB; L.KAP = tg_r64(KA); L.KP = L.KAP + (KB ? tg_r64(KB) : 0); L.U = (N + TEAM_WGS - 1) / TEAM_WGS;
@@ -383,7 +471,8 @@ const char *wrnn_teamg_make_plan(const WrnnDims &d, int64_t budget, WrnnTeamGPla
     if (budget < 0 || budget > dflt) budget = dflt;
     // Residency in layer order (shortest rows first): whole units, as many as still fit; the first layer that does not fit whole is the
     // last to get any (so a layer's resident share never shrinks when the budget grows).  Every workgroup gets the same count.
-    int64_t left = budget / 4, img = 0, res = 0;
+    // Counted in elements of esz bytes; a unit is a multiple of 64 elements, so every offset is a multiple of 16 bytes in either format.
+    int64_t left = budget / esz, img = 0, res = 0;
     for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) {
         WrnnTeamGLayer &L = p.L[l];
         const int64_t unit = (int64_t)L.G * L.KP;
@@ -396,22 +485,28 @@ const char *wrnn_teamg_make_plan(const WrnnDims &d, int64_t budget, WrnnTeamGPla
         if (n < L.U) left = 0;
         img += (int64_t)L.U * unit;
     }
-    p.img_floats_wg = img;
-    p.res_floats = (int32_t)res;
+    p.img_elems_wg = img;
+    p.res_elems = (int32_t)res;
     return nullptr;
 }
 
-hipError_t wrnn_teamg_pack(const wrnn_handle *h, const WrnnTeamGPlan &p, float *img, hipStream_t s) {
+hipError_t wrnn_teamg_pack(const wrnn_handle *h, const WrnnTeamGPlan &p, void *img, hipStream_t s, int *bad_layer) {
     const WrnnDims &d = h->d;
     const WrnnPacked &o = h->off;
     const float *w = h->wdev;
-    hipError_t e = hipMemsetAsync(img, 0, (size_t)TEAM_WGS * p.img_floats_wg * sizeof(float), s);
+    *bad_layer = -1;
+    hipError_t e = hipMemsetAsync(img, 0, wrnn_teamg_img_bytes(p), s);   // padding elements and the range flags
     if (e != hipSuccess) return e;
     (void)hipGetLastError();
+    int32_t *flags = (int32_t *)((char *)img + (size_t)TEAM_WGS * p.img_elems_wg * p.esz);   // one word per layer behind the slices
     auto put = [&](int l, const float *src_t, int ld, int row0, int k0, int K, int gate, int kdst) {
         const WrnnTeamGLayer &L = p.L[l];
-        hipLaunchKernelGGL(teamg_pack_kernel, dim3(L.N), dim3(256), 0, s, src_t, ld, row0, k0, K, img, (size_t)p.img_floats_wg, (size_t)L.img_off, L.N, L.U,
-                           L.G, gate, L.KP, kdst);
+        if (p.esz == 4)
+            hipLaunchKernelGGL(teamg_pack_kernel<float>, dim3(L.N), dim3(256), 0, s, src_t, ld, row0, k0, K, (float *)img, (size_t)p.img_elems_wg, (size_t)L.img_off,
+                               L.N, L.U, L.G, gate, L.KAP, L.KP, kdst, flags + l);
+        else
+            hipLaunchKernelGGL(teamg_pack_kernel<_Float16>, dim3(L.N), dim3(256), 0, s, src_t, ld, row0, k0, K, (_Float16 *)img, (size_t)p.img_elems_wg,
+                               (size_t)L.img_off, L.N, L.U, L.G, gate, L.KAP, L.KP, kdst, flags + l);
     };
     const int H = d.H, A = d.A, FC = d.FC;
     put(WRNN_TEAMG_FC3, w + o.fc3_t, d.NC, 0, 0, FC, 0, 0);
@@ -424,42 +519,56 @@ hipError_t wrnn_teamg_pack(const wrnn_handle *h, const WrnnTeamGPlan &p, float *
         put(WRNN_TEAMG_RNN1, w + o.r1_whh_t, 3 * H, gate * H, 0, H, gate, p.L[WRNN_TEAMG_RNN1].KAP);
     }
     put(WRNN_TEAMG_COND, w + o.I_t, H, 0, 1, d.F + A, 0, 0);   // column 0 (the fed-back sample) stays a vector
-    return hipGetLastError();
+    e = hipGetLastError();
+    if (e != hipSuccess || p.esz == 4) return e;
+    // the range check of the fp16 image: once per pack, the only wait
+    int32_t bad[WRNN_TEAMG_LAYERS];
+    e = hipMemcpyAsync(bad, flags, sizeof(bad), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return e;
+    for (int l = WRNN_TEAMG_LAYERS - 1; l >= 0; --l)
+        if (bad[l]) *bad_layer = l;
+    return hipSuccess;
 }
 
-static size_t teamg_lds_bytes(const WrnnTeamGPlan &p) { return ((size_t)p.act_floats + (size_t)p.res_floats) * sizeof(float); }
+static const void *teamg_kernel_fn(const WrnnTeamGPlan &p) {
+    return p.esz == 4 ? (const void *)loop_teamg_kernel<float> : (const void *)loop_teamg_kernel<_Float16>;
+}
 
 hipError_t wrnn_teamg_occupancy(const WrnnTeamGPlan &p, int *blocks_per_cu) {
-    const size_t lds = teamg_lds_bytes(p);
-    hipError_t e = hipFuncSetAttribute((const void *)loop_teamg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const size_t lds = wrnn_teamg_lds_bytes(p);
+    hipError_t e = hipFuncSetAttribute(teamg_kernel_fn(p), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, (const void *)loop_teamg_kernel, TG_THREADS, lds);
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, teamg_kernel_fn(p), TG_THREADS, lds);
 }
 
 hipError_t wrnn_launch_loop_teamg(const WrnnTeamGArgs &a, hipStream_t s) {
     (void)hipGetLastError();
-    const size_t lds = teamg_lds_bytes(a.plan);
-    hipError_t e = hipFuncSetAttribute((const void *)loop_teamg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const size_t lds = wrnn_teamg_lds_bytes(a.plan);
+    hipError_t e = hipFuncSetAttribute(teamg_kernel_fn(a.plan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(loop_teamg_kernel, dim3(a.n_teams * TEAM_WGS), dim3(TG_THREADS), lds, s, a);
+    if (a.plan.esz == 4) hipLaunchKernelGGL(loop_teamg_kernel<float>, dim3(a.n_teams * TEAM_WGS), dim3(TG_THREADS), lds, s, a);
+    else hipLaunchKernelGGL(loop_teamg_kernel<_Float16>, dim3(a.n_teams * TEAM_WGS), dim3(TG_THREADS), lds, s, a);
     return hipGetLastError();
 }
 
 // ---- C ABI: the plan, host only ----
 
-static int teamg_plan_info(const wrnn_config *cfg, int rows_per_team, int64_t lds_budget_bytes, wrnn_teamg_plan_info *out) {
+static int teamg_plan_info(const wrnn_config *cfg, int rows_per_team, int fmt, int64_t lds_budget_bytes, wrnn_teamg_plan_info *out) {
     if (!cfg || !out || rows_per_team < 1 || rows_per_team > WRNN_TEAMG_BATCH_MAX_ROWS) return WRNN_ERR_INVALID;
+    if (fmt != WRNN_WEIGHTS_F32 && fmt != WRNN_WEIGHTS_F16) return WRNN_ERR_INVALID;
+    const int64_t esz = fmt == WRNN_WEIGHTS_F16 ? 2 : 4;
     WrnnDims d;
     if (wrnn_dims_from_config(cfg, d) || d.FC > (1 << 20) || d.F > (1 << 20)) return WRNN_ERR_INVALID;
     WrnnTeamGPlan p;
-    if (wrnn_teamg_make_plan(d, lds_budget_bytes, p, rows_per_team)) return WRNN_ERR_UNSUPPORTED;
+    if (wrnn_teamg_make_plan(d, lds_budget_bytes, p, rows_per_team, (int)esz)) return WRNN_ERR_UNSUPPORTED;
     *out = wrnn_teamg_plan_info{};
     for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) {
         const WrnnTeamGLayer &L = p.L[l];
         wrnn_teamg_layer_info &o = out->layer[l];
         const int K = L.KA + L.KB;
         o.units = L.N; o.rows_per_unit = L.G; o.k = K; o.k_padded = L.KP; o.resident_units = L.nres;
-        o.weight_bytes = 4LL * L.N * L.G * K;
+        o.weight_bytes = esz * L.N * L.G * K;
         o.rows_min = INT32_MAX;
         for (int g = 0; g < TEAM_WGS; ++g) {
             int n = L.N - g * L.U;
@@ -469,25 +578,29 @@ static int teamg_plan_info(const wrnn_config *cfg, int rows_per_team, int64_t ld
             const int rows = n * L.G, res = (n < L.nres ? n : L.nres);
             if (rows < o.rows_min) o.rows_min = rows;
             if (rows > o.rows_max) o.rows_max = rows;
-            const int64_t rb = 4LL * res * L.G * K;
+            const int64_t rb = esz * res * L.G * K;
             if (rb > o.resident_bytes_wg) o.resident_bytes_wg = rb;
             o.resident_bytes_team += rb;
         }
         o.streamed_bytes_step = o.weight_bytes - o.resident_bytes_team;
-        o.lds_bytes = 4LL * L.nres * L.G * L.KP;
+        o.lds_bytes = esz * L.nres * L.G * L.KP;
         out->streamed_bytes_step += o.streamed_bytes_step;
     }
     out->activation_bytes = 4LL * p.act_floats;
-    out->lds_bytes = 4LL * ((int64_t)p.act_floats + p.res_floats);
+    out->lds_bytes = (int64_t)wrnn_teamg_lds_bytes(p);
     out->lds_budget_bytes = (lds_budget_bytes < 0 || lds_budget_bytes > TG_LDS_MAX - out->activation_bytes) ? TG_LDS_MAX - out->activation_bytes : lds_budget_bytes;
     out->mail_granules = p.mail_granules;
     return WRNN_OK;
 }
 
 extern "C" int wrnn_teamg_plan(const wrnn_config *cfg, int64_t lds_budget_bytes, wrnn_teamg_plan_info *out) {
-    return teamg_plan_info(cfg, 1, lds_budget_bytes, out);
+    return teamg_plan_info(cfg, 1, WRNN_WEIGHTS_F32, lds_budget_bytes, out);
 }
 
 extern "C" int wrnn_teamg_batch_plan(const wrnn_config *cfg, int32_t rows_per_team, int64_t lds_budget_bytes, wrnn_teamg_plan_info *out) {
-    return teamg_plan_info(cfg, rows_per_team, lds_budget_bytes, out);
+    return teamg_plan_info(cfg, rows_per_team, WRNN_WEIGHTS_F32, lds_budget_bytes, out);
+}
+
+extern "C" int wrnn_teamg_plan_fmt(const wrnn_config *cfg, int32_t rows_per_team, int32_t weight_format, int64_t lds_budget_bytes, wrnn_teamg_plan_info *out) {
+    return teamg_plan_info(cfg, rows_per_team, weight_format, lds_budget_bytes, out);
 }

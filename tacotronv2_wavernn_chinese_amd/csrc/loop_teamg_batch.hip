@@ -8,6 +8,8 @@
 // Per (row, output) the arithmetic is loop_teamg.hip's operand for operand -- tgb_dot keeps tg_dot's k order, its a0 / a1 split and
 // row_sum, the cells use the same libm calls, Philox is keyed (seed or row key, step, row, class), the race keeps the lowest class of
 // a tie -- so a row's labels, samples and logits are bit-equal to WRNN_KERNEL_TEAMG's whatever batch the row lands in.
+// The kernel is templated on the element type of the image as loop_teamg.hip is (float, or _Float16 for WRNN_WEIGHTS_F16): the fp16
+// instantiations are bit-equal to the fp16 instantiation of that kernel, and to the fp32 ones on the model rounded to fp16.
 //
 // Rows.  Batch b = schedule slots [b rpb, (b + 1) rpb) of `order` (longest first in a ragged call, identity otherwise), dealt to the
 // teams round-robin, in snake order when ragged, as loop_batch_cs.hip deals them.  A batch runs for the steps of its longest row; a
@@ -20,6 +22,8 @@
 // gate row where it owns fewer (G = 1, more loads in flight) -- loop_teamg.hip's rule, the sums are the same either way.  After a
 // dot product lane r of the group finishes row r: bias, cell or relu, noise, its granule.  The race of row r and the MOL sampler of
 // row r run in wave r.
+#include <type_traits>
+
 #include "team_common.h"
 #include "teamg_layout.h"
 
@@ -95,7 +99,102 @@ __device__ __forceinline__ void tgb_dot(const float4 *__restrict__ wp, int kp4, 
         }
 }
 
-template <int RB>
+// tgb_dot on the fp16 image (teamg_layout.h), as tg_dot16 is tg_dot's: rp = the unit's first row, rows kp8 16-byte pieces apart, row0 its
+// index in the slice.  One 16-byte load per row and PAIR of steps, UNP pairs issued together (tgb_dot's weight bytes in flight; with 8
+// rows half of them, there are no registers for more), an 8-byte load for the unpaired last step of a segment.  Each step's weights are
+// widened exactly right before its multiply-adds; per (row, lane) the chains are tgb_dot's.
+template <int G, int RB>
+__device__ __forceinline__ void tgb_dot16(const TgHalf8 *__restrict__ rp, int kp8, int row0, const float4 *lds4, int xi, int xs4, int nA, int nK, int q, float (&sa)[G],
+                                          float (&sb)[G]) {
+    constexpr int UNP = (G == 1 ? 4 : 2) / (RB <= 4 ? 1 : 2);
+    asm volatile("" : "+v"(xi));
+    const float4 *xp = lds4 + xi;
+    const TgHalf8 *wp[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) wp[g] = rp + (size_t)g * kp8 + (q ^ tg16_swz(row0 + g, kp8 * 8));
+    float a0[RB][G], a1[RB][G];
+#pragma unroll
+    for (int r = 0; r < RB; ++r)
+#pragma unroll
+        for (int g = 0; g < G; ++g) a0[r][g] = a1[r][g] = 0.0f;
+    auto mac = [&](const float4 (&w)[G], int k) {
+#pragma unroll
+        for (int r = 0; r < RB; ++r) {
+            const float4 x = xp[r * xs4 + k * 16];
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                a0[r][g] = fmaf(w[g].x, x.x, a0[r][g]); a1[r][g] = fmaf(w[g].y, x.y, a1[r][g]);
+                a0[r][g] = fmaf(w[g].z, x.z, a0[r][g]); a1[r][g] = fmaf(w[g].w, x.w, a1[r][g]);
+            }
+        }
+    };
+    auto pair = [&](const TgHalf8 (&wv)[G], int k) {
+        float4 w[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) w[g] = tg_lo4(wv[g]);
+        mac(w, k);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int g = 0; g < G; ++g) w[g] = tg_hi4(wv[g]);
+        mac(w, k + 1);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // NP pairs of steps from step k: their weight loads are issued together
+    auto block = [&](auto np, int k) {
+        constexpr int NP = decltype(np)::value;
+        TgHalf8 wv[NP][G];
+#pragma unroll
+        for (int u = 0; u < NP; ++u)
+#pragma unroll
+            for (int g = 0; g < G; ++g) wv[u][g] = wp[g][(k + 2 * u) * 8];
+#pragma unroll
+        for (int u = 0; u < NP; ++u) pair(wv[u], k + 2 * u);
+    };
+    // UNP pairs at a time, then what is left in halving blocks: a short segment still has all its loads in flight at once
+    auto segment = [&](int k0, int k1) {
+        int k = k0;
+#pragma unroll 1
+        for (; k + 2 * UNP <= k1; k += 2 * UNP) block(std::integral_constant<int, UNP>{}, k);
+        if constexpr (UNP > 2) {
+            if (k + 4 <= k1) { block(std::integral_constant<int, 2>{}, k); k += 4; }
+        }
+        if constexpr (UNP > 1) {
+            if (k + 2 <= k1) { block(std::integral_constant<int, 1>{}, k); k += 2; }
+        }
+        if (k < k1) {
+            float4 w[G];
+#pragma unroll
+            for (int g = 0; g < G; ++g) w[g] = tg_w4(((const TgHalf4 *)(rp + (size_t)g * kp8))[k * 16 + q]);
+            mac(w, k);
+        }
+    };
+    segment(0, nA);
+#pragma unroll
+    for (int r = 0; r < RB; ++r)
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const float v = row_sum(a0[r][g] + a1[r][g]);
+            sa[g] = (r == 0 || q == r) ? v : sa[g];
+            a0[r][g] = a1[r][g] = 0.0f;
+        }
+    segment(nA, nK);
+#pragma unroll
+    for (int r = 0; r < RB; ++r)
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const float v = row_sum(a0[r][g] + a1[r][g]);
+            sb[g] = (r == 0 || q == r) ? v : sb[g];
+        }
+}
+
+// G rows from row `row0` of a layer's slice at `base` (LDS or device memory), KP elements each, in the image's element type
+template <int G, int RB, typename WT>
+__device__ __forceinline__ void tgb_rows(const WT *base, int row0, int KP, const float4 *lds4, int xi, int xs4, int nA, int nK, int q, float (&sa)[G], float (&sb)[G]) {
+    if constexpr (sizeof(WT) == 4) tgb_dot<G, RB>((const float4 *)(base + (size_t)row0 * KP) + q, KP / 4, lds4, xi, xs4, nA, nK, q, sa, sb);
+    else tgb_dot16<G, RB>((const TgHalf8 *)(base + (size_t)row0 * KP), KP / 8, row0, lds4, xi, xs4, nA, nK, q, sa, sb);
+}
+
+template <int RB, typename WT>
 __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGBatchArgs ta) {
     extern __shared__ __attribute__((aligned(16))) char smem_tgb[];
     float *lds = (float *)smem_tgb;
@@ -109,7 +208,7 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
     int *misc_i = (int *)misc;
     float *gsum = lds + ly.gs, *race = lds + ly.race;
     int *race_i = (int *)race;
-    float *wres = lds + ly.total;   // resident weights
+    WT *wres = (WT *)(lds + ly.total);   // resident weights, in the image's element type
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int qw = tid >> 4, q = tid & 15;   // not const: see the top of the step loop
@@ -123,12 +222,12 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
     // mailbox regions of a row (granules), two parities each
     const unsigned M_XC = 0, M_H1 = 2 * HP, M_H2 = 4 * HP, M_F1 = 6 * HP, M_F2 = 6 * HP + 2 * FCP, M_CAND = 6 * HP + 4 * FCP;
     const float *w = a.w;
-    const float *img = ta.img + (size_t)g * ta.plan.img_floats_wg;
+    const WT *img = (const WT *)ta.img + (size_t)g * ta.plan.img_elems_wg;
 
     // ---- resident weights, zeroed activations ----
     for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) {
         const WrnnTeamGLayer &L = ta.plan.L[l];
-        const int n4 = L.nres * L.G * (L.KP / 4);
+        const int n4 = L.nres * L.G * (L.KP / 4) / (int)(sizeof(float) / sizeof(WT));   // 16-byte pieces: KP is a multiple of 64 elements
         const float4 *src = (const float4 *)(img + L.img_off);
         float4 *dst = (float4 *)(wres + L.lds_off);
         for (int i = tid; i < n4; i += TG_THREADS) dst[i] = src[i];
@@ -175,12 +274,12 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
     // the own rows of W_I[:, 1:] . [m | a1] + b_I for the step whose conditioning is in parity `par` -> every row's mailbox, tagged `tag`
     auto xc_publish = [&](unsigned par, unsigned tag) {
         const WrnnTeamGLayer &L = ta.plan.L[WRNN_TEAMG_COND];
-        const int nown = owned(L), kp4 = L.KP / 4, nK = L.KP / 64;
+        const int nown = owned(L), nK = L.KP / 64;
         const int xi = (ly.v.cb + par * CB) / 4 + q;
         for (int ul = qw; ul < nown; ul += 32) {
             float sa[1], sb[1];
-            if (ul < L.nres) tgb_dot<1, RB>((const float4 *)(wres + L.lds_off + (size_t)ul * L.KP) + q, kp4, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
-            else tgb_dot<1, RB>((const float4 *)(img + L.img_off + (size_t)ul * L.KP) + q, kp4, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
+            if (ul < L.nres) tgb_rows<1, RB>(wres + L.lds_off, ul, L.KP, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
+            else tgb_rows<1, RB>(img + L.img_off, ul, L.KP, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
             const int j = g * L.U + ul;
             if (q < RB) st_granule(mail, q * G1 + M_XC + (tag & 1u) * HP + j, tag, __float_as_uint(sa[0] + w[a.off.I_b + j]));
         }
@@ -188,7 +287,7 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
     // one GRU layer (get_gru_cell :273-279, gate rows [r; z; n]): h' of the own units of every row -> mailbox.  A row's input is
     // [input (KAP) | h (HP)] at xoff of its vectors.  By gate row or by unit as in loop_teamg.hip.
     auto gru_phase = [&](const WrnnTeamGLayer &L, int xoff, size_t obih, size_t obhh, unsigned region, unsigned epoch) {
-        const int nown = owned(L), kp4 = L.KP / 4, nA = L.KAP / 64, nK = L.KP / 64;
+        const int nown = owned(L), nA = L.KAP / 64, nK = L.KP / 64;
         const int xi = xoff / 4 + q;
         const float *bi = w + obih, *bh = w + obhh;
         auto cell = [&](int r, int j, const float (&gi)[3], const float (&gh)[3]) {
@@ -202,8 +301,8 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
             for (int task = qw; task < 3 * nown; task += 32) {
                 const int ul = task / 3;
                 float sa[1], sb[1];
-                if (ul < L.nres) tgb_dot<1, RB>((const float4 *)(wres + L.lds_off + (size_t)task * L.KP) + q, kp4, (const float4 *)lds, xi, xs4, nA, nK, q, sa, sb);
-                else tgb_dot<1, RB>((const float4 *)(img + L.img_off + (size_t)task * L.KP) + q, kp4, (const float4 *)lds, xi, xs4, nA, nK, q, sa, sb);
+                if (ul < L.nres) tgb_rows<1, RB>(wres + L.lds_off, task, L.KP, (const float4 *)lds, xi, xs4, nA, nK, q, sa, sb);
+                else tgb_rows<1, RB>(img + L.img_off, task, L.KP, (const float4 *)lds, xi, xs4, nA, nK, q, sa, sb);
                 if (q < RB) { gsum[q * 128 + 2 * task] = sa[0]; gsum[q * 128 + 2 * task + 1] = sb[0]; }
             }
             __syncthreads();
@@ -217,15 +316,15 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
             for (int ul = qw; ul < nown; ul += 32) {
                 float gi[3] = {0.0f, 0.0f, 0.0f}, gh[3] = {0.0f, 0.0f, 0.0f};
                 if constexpr (RB <= 4) {
-                    if (ul < L.nres) tgb_dot<3, RB>((const float4 *)(wres + L.lds_off + (size_t)ul * 3 * L.KP) + q, kp4, (const float4 *)lds, xi, xs4, nA, nK, q, gi, gh);
-                    else tgb_dot<3, RB>((const float4 *)(img + L.img_off + (size_t)ul * 3 * L.KP) + q, kp4, (const float4 *)lds, xi, xs4, nA, nK, q, gi, gh);
+                    if (ul < L.nres) tgb_rows<3, RB>(wres + L.lds_off, ul * 3, L.KP, (const float4 *)lds, xi, xs4, nA, nK, q, gi, gh);
+                    else tgb_rows<3, RB>(img + L.img_off, ul * 3, L.KP, (const float4 *)lds, xi, xs4, nA, nK, q, gi, gh);
                 } else {
                     // 8 rows x 3 gates x (a0, a1) would not leave room for the loads in flight: gate by gate, the same sums
 #pragma unroll 1
                     for (int gt = 0; gt < 3; ++gt) {
                         float sa[1], sb[1];
-                        if (ul < L.nres) tgb_dot<1, RB>((const float4 *)(wres + L.lds_off + ((size_t)ul * 3 + gt) * L.KP) + q, kp4, (const float4 *)lds, xi, xs4, nA, nK, q, sa, sb);
-                        else tgb_dot<1, RB>((const float4 *)(img + L.img_off + ((size_t)ul * 3 + gt) * L.KP) + q, kp4, (const float4 *)lds, xi, xs4, nA, nK, q, sa, sb);
+                        if (ul < L.nres) tgb_rows<1, RB>(wres + L.lds_off, ul * 3 + gt, L.KP, (const float4 *)lds, xi, xs4, nA, nK, q, sa, sb);
+                        else tgb_rows<1, RB>(img + L.img_off, ul * 3 + gt, L.KP, (const float4 *)lds, xi, xs4, nA, nK, q, sa, sb);
                         gi[0] = gt == 0 ? sa[0] : gi[0]; gi[1] = gt == 1 ? sa[0] : gi[1]; gi[2] = gt == 2 ? sa[0] : gi[2];
                         gh[0] = gt == 0 ? sb[0] : gh[0]; gh[1] = gt == 1 ? sb[0] : gh[1]; gh[2] = gt == 2 ? sb[0] : gh[2];
                     }
@@ -236,12 +335,12 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
     };
     // relu(W . x + b) of the own rows, every row -> mailbox
     auto fc_phase = [&](const WrnnTeamGLayer &L, int xoff, size_t ob, unsigned region, unsigned epoch) {
-        const int nown = owned(L), kp4 = L.KP / 4, nK = L.KP / 64;
+        const int nown = owned(L), nK = L.KP / 64;
         const int xi = xoff / 4 + q;
         for (int ul = qw; ul < nown; ul += 32) {
             float sa[1], sb[1];
-            if (ul < L.nres) tgb_dot<1, RB>((const float4 *)(wres + L.lds_off + (size_t)ul * L.KP) + q, kp4, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
-            else tgb_dot<1, RB>((const float4 *)(img + L.img_off + (size_t)ul * L.KP) + q, kp4, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
+            if (ul < L.nres) tgb_rows<1, RB>(wres + L.lds_off, ul, L.KP, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
+            else tgb_rows<1, RB>(img + L.img_off, ul, L.KP, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
             const int j = g * L.U + ul;
             if (q < RB) st_granule(mail, q * G1 + region + (epoch & 1u) * FCP + j, epoch, __float_as_uint(fmaxf(sa[0] + w[ob + j], 0.0f)));
         }
@@ -351,7 +450,7 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
             // ---- 5. logits = fc3(x) :223 of the own classes, and the sampler :225-237.  Lane r of a group: row r ----
             {
                 const WrnnTeamGLayer &L = ta.plan.L[WRNN_TEAMG_FC3];
-                const int nown = owned(L), kp4 = L.KP / 4, nK = L.KP / 64;
+                const int nown = owned(L), nK = L.KP / 64;
                 const int xi = f3 / 4 + q;
                 const int qr = q < RB ? q : 0;
                 const int row = q < RB ? misc_i[MB_ROW + qr] : -1;
@@ -362,8 +461,8 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
                 int bi = 0x7fffffff;
                 for (int ul = qw; ul < nown; ul += 32) {
                     float sa[1], sb[1];
-                    if (ul < L.nres) tgb_dot<1, RB>((const float4 *)(wres + L.lds_off + (size_t)ul * L.KP) + q, kp4, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
-                    else tgb_dot<1, RB>((const float4 *)(img + L.img_off + (size_t)ul * L.KP) + q, kp4, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
+                    if (ul < L.nres) tgb_rows<1, RB>(wres + L.lds_off, ul, L.KP, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
+                    else tgb_rows<1, RB>(img + L.img_off, ul, L.KP, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
                     if (q < RB) {
                         const int c = g * L.U + ul;
                         const float lg = sa[0] + w[a.off.fc3_b + c];
@@ -453,30 +552,41 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
 }
 
 template <int RB>
-hipError_t tgb_prepare(size_t lds) {
-    return hipFuncSetAttribute((const void *)loop_teamg_batch_kernel<RB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+const void *tgb_fn(int esz) {
+    return esz == 4 ? (const void *)loop_teamg_batch_kernel<RB, float> : (const void *)loop_teamg_batch_kernel<RB, _Float16>;
 }
+const void *tgb_kernel_fn(int rb, int esz) { return rb == 2 ? tgb_fn<2>(esz) : rb == 4 ? tgb_fn<4>(esz) : rb == 8 ? tgb_fn<8>(esz) : nullptr; }
 
-size_t tgb_lds_bytes(const WrnnTeamGPlan &p) { return ((size_t)p.act_floats + (size_t)p.res_floats) * sizeof(float); }
+template <int RB, typename WT>
+void tgb_launch(const WrnnTeamGBatchArgs &a, size_t lds, hipStream_t s) {
+    hipLaunchKernelGGL((loop_teamg_batch_kernel<RB, WT>), dim3(a.n_teams * TEAM_WGS), dim3(TG_THREADS), lds, s, a);
+}
+template <int RB>
+void tgb_launch_fmt(const WrnnTeamGBatchArgs &a, size_t lds, hipStream_t s) {
+    if (a.plan.esz == 4) tgb_launch<RB, float>(a, lds, s);
+    else tgb_launch<RB, _Float16>(a, lds, s);
+}
 
 }  // namespace
 
 hipError_t wrnn_teamg_batch_occupancy(const WrnnTeamGPlan &p, int rb, int *blocks_per_cu) {
-    const size_t lds = tgb_lds_bytes(p);
-    const void *fn = rb == 2 ? (const void *)loop_teamg_batch_kernel<2> : rb == 4 ? (const void *)loop_teamg_batch_kernel<4> : (const void *)loop_teamg_batch_kernel<8>;
-    hipError_t e = rb == 2 ? tgb_prepare<2>(lds) : rb == 4 ? tgb_prepare<4>(lds) : rb == 8 ? tgb_prepare<8>(lds) : hipErrorInvalidValue;
+    const size_t lds = wrnn_teamg_lds_bytes(p);
+    const void *fn = tgb_kernel_fn(rb, p.esz);
+    if (!fn) return hipErrorInvalidValue;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, fn, TG_THREADS, lds);
 }
 
 hipError_t wrnn_launch_loop_teamg_batch(const WrnnTeamGBatchArgs &a, int rb, hipStream_t s) {
     (void)hipGetLastError();
-    const size_t lds = tgb_lds_bytes(a.plan);
-    hipError_t e = rb == 2 ? tgb_prepare<2>(lds) : rb == 4 ? tgb_prepare<4>(lds) : rb == 8 ? tgb_prepare<8>(lds) : hipErrorInvalidValue;
+    const size_t lds = wrnn_teamg_lds_bytes(a.plan);
+    const void *fn = tgb_kernel_fn(rb, a.plan.esz);
+    if (!fn) return hipErrorInvalidValue;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    const dim3 grid(a.n_teams * TEAM_WGS), block(TG_THREADS);
-    if (rb == 2) hipLaunchKernelGGL(loop_teamg_batch_kernel<2>, grid, block, lds, s, a);
-    else if (rb == 4) hipLaunchKernelGGL(loop_teamg_batch_kernel<4>, grid, block, lds, s, a);
-    else hipLaunchKernelGGL(loop_teamg_batch_kernel<8>, grid, block, lds, s, a);
+    if (rb == 2) tgb_launch_fmt<2>(a, lds, s);
+    else if (rb == 4) tgb_launch_fmt<4>(a, lds, s);
+    else tgb_launch_fmt<8>(a, lds, s);
     return hipGetLastError();
 }

@@ -1,5 +1,6 @@
 // LDS carve-up of the two team kernels for any dims: TgLay (loop_teamg.hip, one row per team) and TgbLay (loop_teamg_batch.hip, RB rows
-// per team in lock-step).  wrnn_teamg_make_plan sizes the resident weights by what these leave of 160 KiB.
+// per team in lock-step).  wrnn_teamg_make_plan sizes the resident weights by what these leave of 160 KiB.  The vectors are fp32 whatever
+// the element type of the weight image.
 #pragma once
 #include "wrnn_internal.h"
 
@@ -50,6 +51,40 @@ struct TgbLay {
         total = o;
     }
 };
+// The fp16 image.  A row of the fp32 image is KP floats in order: at step k of a dot product lane q of a 16-lane group loads elements
+// 4 (q + 16 k) .. + 3, one float4.  The fp16 image holds the same elements as IEEE binary16, permuted inside the row so that ONE 16-byte
+// load covers the lane's elements of TWO consecutive steps -- the bytes in flight per load, and the width of an LDS read, stay those of
+// the fp32 kernel:
+//   * a row is two segments of steps, [0, nA) and [nA, nK) (the operands a GRU's n gate needs apart; nA = nK for the other layers), and
+//     steps pair up inside a segment: pair j of the segment that starts at step k0 is steps k0 + 2 j and k0 + 2 j + 1.  It takes the 256
+//     bytes from byte 128 (k0 + 2 j) of the row; lane q's 16 bytes are piece q ^ s of those 16 pieces: 4 halves of the first step, then 4
+//     of the second;
+//   * a segment with an odd number of steps ends in one unpaired step, stored as in the fp32 image: lane q's 4 halves at halves
+//     64 k + 4 q .. + 3 (an 8-byte load);
+//   * s = 8 for an odd row (counted inside the workgroup's slice of the layer) of a layer whose KP / 64 is odd, else 0.  Rows are
+//     KP * 2 bytes apart, so consecutive rows of such a layer start 128 bytes apart modulo the 256 bytes the 64 LDS banks span, and the
+//     16-lane groups that one ds_read_b128 serves together -- lanes 0-3 and 12-15 of one row with lanes 4-11 of the next -- would meet
+//     on the same banks.  Swapping the two 128-byte halves of every pair in the odd rows puts them back on disjoint banks: every
+//     resident row is read conflict-free, as in the fp32 kernel, whose rows are a multiple of 256 bytes apart.
+// The permutation only moves bytes (tg16_pos below is what wrnn_teamg_pack writes by and the dot products read by): each lane still gets
+// the elements 4 (q + 16 k) .. + 3 at step k, k ascending, and widens them exactly -- every binary16 value, subnormals included, is an
+// fp32 value -- so its multiply-adds see the operands they would see with the rounded matrix stored as fp32.
+typedef _Float16 TgHalf4 __attribute__((ext_vector_type(4)));
+typedef _Float16 TgHalf8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ float4 tg_w4(const TgHalf4 &w) { return make_float4((float)w.x, (float)w.y, (float)w.z, (float)w.w); }
+__device__ __forceinline__ float4 tg_lo4(const TgHalf8 &w) { return make_float4((float)w[0], (float)w[1], (float)w[2], (float)w[3]); }
+__device__ __forceinline__ float4 tg_hi4(const TgHalf8 &w) { return make_float4((float)w[4], (float)w[5], (float)w[6], (float)w[7]); }
+// 8 for the rows whose pairs are stored with their halves swapped
+__host__ __device__ inline int tg16_swz(int row, int KP) { return (row & (KP >> 6) & 1) << 3; }
+// where element p of row `row` (KAP = elements of segment A, KP = of the row; both multiples of 64) lives in the row of the fp16 image
+__host__ __device__ inline int tg16_pos(int p, int row, int KAP, int KP) {
+    const int k = p >> 6, q = (p >> 2) & 15, c = p & 3;
+    const int k0 = p < KAP ? 0 : KAP >> 6, k1 = p < KAP ? KAP >> 6 : KP >> 6;
+    const int rel = k - k0;
+    if (((k1 - k0) & 1) && rel == k1 - k0 - 1) return p;   // the unpaired last step of a segment
+    return 64 * (k - (rel & 1)) + 8 * (q ^ tg16_swz(row, KP)) + 4 * (rel & 1) + c;
+}
+
 constexpr int MB_X = 8, MB_ROW = 16, MB_STEPS = 24, MB_UTT = 32, MB_START = 40, MB_SEED = 56, MB_KROW = 72;
 
 }  // namespace

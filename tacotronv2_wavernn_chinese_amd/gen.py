@@ -7,7 +7,7 @@ handed to ``model.generate``; the output file name pattern is the reference's (:
 
 Deliberate differences: the reference hard-overrides ``batched = False`` and
 ``device = cpu`` after parsing its flags (:76-77, :93); here ``--batched`` is honoured and the model
-runs on the MI355X.  Extensions: ``--kernel NAME``, ``--target auto|per_xcd``, ``--noise reference [--seed N]``, ``--stream-frames N`` (streaming generation)
+runs on the MI355X.  Extensions: ``--kernel NAME``, ``--teamg-weights f32|f16``, ``--target auto|per_xcd``, ``--noise reference [--seed N]``, ``--stream-frames N`` (streaming generation)
 (the reference's own noise stream: ``vocoder.reference_noise``).
 
 The ``.wav`` branch (:17-20) does what the reference's intends: ``load_wav``, the input saved as ``__{idx}__{k}k_steps_target.wav`` (the
@@ -146,6 +146,9 @@ def build_parser() -> argparse.ArgumentParser:
                         help="extension: the device loop kernel ('auto': the library's choice; 'teamg': the XCD-team kernel for any model "
                              "dims, the fast path of a model whose dims are not the reference hparams; 'teamg_batch': the same kernel with "
                              "several rows per team in lock-step, for batched (fold) mode and other many-row calls of such a model)")
+    parser.add_argument('--teamg-weights', choices=('f32', 'f16'), default='f32',
+                        help="extension: element type of the weight image of --kernel teamg / teamg_batch ('f16': the loop matrices as IEEE "
+                             "binary16, half the bytes streamed per step; activations and accumulators stay fp32); ignored by the other kernels")
     parser.set_defaults(batched=None)
     return parser
 
@@ -172,6 +175,7 @@ def main(argv=None):
     model = build_model_from_hparams().to(device)
     from . import _cabi
     model.kernel = _cabi.KERNEL_IDS[args.kernel]
+    model.teamg_weights = args.teamg_weights
     # wavernn_gen.py:112-117: `--voc_weights`, else the latest checkpoint of the training run
     # (Paths.voc_latest_weights = <base>/logs_wavernn/checkpoints/latest_weights.pyt, wavernn/utils/paths.py:11-12; <base> is
     # the directory the script is started from here).  The reference then dies in torch.load when that file is absent; no

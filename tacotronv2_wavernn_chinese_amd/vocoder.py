@@ -282,6 +282,7 @@ class WaveRNN(nn.Module):
         self._native_key = None
         # knobs that are not part of the reference signature
         self.kernel = _cabi.KERNEL_AUTO
+        self._teamg_weights = 'f32'       # see the property teamg_weights
         # True: every training call (training_loss, forward / backward in train() mode) waits for its kernels and raises on a device-side
         # error (a busy GPU, a timed-out team kernel) -- safe, but the host cannot queue the rest of the iteration (the upsample network's
         # backward, clipping, Adam: ~150 small launches) under the running step.  'deferred': no wait; the caller asks once per iteration
@@ -317,6 +318,24 @@ class WaveRNN(nn.Module):
             objs.extend(b for n, b in m._buffers.items() if n != 'step' and n != 'num_batches_tracked')
         return (dev,) + tuple((id(p), p._version, p.data_ptr()) for p in objs if p is not None)
 
+    @property
+    def teamg_weights(self) -> str:
+        """Element type of the weight image of ``kernel='teamg'`` / ``'teamg_batch'``: ``'f32'`` (default) or ``'f16'``.  With ``'f16'`` the six
+        loop matrices are stored as IEEE binary16 (rounded to nearest even; activations, accumulators, biases and samplers stay fp32), which
+        halves the bytes a team streams per step and doubles what fits in LDS.  The outputs are bit-equal to the fp32 kernel's on a model
+        whose matrices were rounded to fp16 beforehand.  The setting belongs to the model: it survives ``load_state_dict`` and ``.to()``,
+        the image is packed again by the next call, and no other kernel reads it (``last_timing['teamg_weights']`` says what ran).  A
+        weight that has no finite fp16 makes that call raise ``WrnnError`` (WRNN_ERR_UNSUPPORTED) naming the layer."""
+        return self._teamg_weights
+
+    @teamg_weights.setter
+    def teamg_weights(self, fmt: str):
+        if fmt not in _cabi.WEIGHT_FORMATS:
+            raise ValueError(f"teamg_weights must be 'f32' or 'f16', not {fmt!r}")
+        self._teamg_weights = fmt
+        if self._native is not None:
+            self._native.set_teamg_weights(fmt)
+
     def invalidate_native(self):
         """Force the next ``generate`` to repack the weights into the native handle."""
         self._native_key = None
@@ -329,6 +348,7 @@ class WaveRNN(nn.Module):
             if self._native is not None:
                 self._native.close()
             self._native = _cabi.NativeVocoder(device=dev, **self._ctor)
+            self._native.set_teamg_weights(self._teamg_weights)
             self._native_key = None
         return self._native
 
@@ -340,6 +360,7 @@ class WaveRNN(nn.Module):
             if self._native is not None:
                 self._native.close()
             self._native = _cabi.NativeVocoder(device=dev, **self._ctor)
+            self._native.set_teamg_weights(self._teamg_weights)
             self._native_key = None
         if self._native_key != key:
             sd = {k: v.detach().cpu().numpy() for k, v in self.state_dict().items()}

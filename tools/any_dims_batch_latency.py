@@ -10,7 +10,12 @@ around the loop kernel of one call; warm-up calls first, then `--reps` timed cal
 listed.  us/step/row = median loop time / (steps x rows): the time the call spends per row and step, all teams busy.  Next to each the bytes
 a team streams per step and row (`wrnn_teamg_batch_plan`).  The last lines state, per dim set, whether the default rows per team
 (batch_rows 0) beats TEAMG per row by more than the larger min-to-max spread of the two, and whether a smaller admitted count beats the
-default by more than that."""
+default by more than that.
+
+    python tools/any_dims_batch_latency.py --weights f16 [--out FILE]
+
+times WRNN_KERNEL_TEAMG_BATCH with the fp32 weight image against the fp16 image (`teamg_weights='f16'`) at every rows-per-team count both
+plans admit: two handles of one model, the formats alternating call by call."""
 import argparse
 import os
 import sys
@@ -24,12 +29,76 @@ sys.path.insert(0, ROOT)
 FRAMES = {'A': 2, 'C': 42, 'D': 1}      # 256, 252 and 275 steps
 
 
+def weights_session(args):
+    """fp32 image against fp16 image, WRNN_KERNEL_TEAMG_BATCH at every admitted rows-per-team count, 8 x n_teams rows."""
+    from tacotronv2_wavernn_chinese_amd import _cabi
+    from tacotronv2_wavernn_chinese_amd.synth import make_mels, make_state_dict
+    from tacotronv2_wavernn_chinese_amd.vocoder import WaveRNN
+    from tests.teamg_cases import DIM_SETS
+    lines = [f'fp16 weight image, many rows on other dims, {torch.cuda.get_device_name(0)}, torch {torch.__version__}', '',
+             f'loop_ms of one call (HIP events around the loop kernel), {args.warmup} warm-up + {args.reps} timed calls per format, alternating; RAW, Philox noise',
+             'us/step/row = median loop time / (steps x rows); spread = (max - min) of the timed calls in the same unit; streamed = weight bytes a team reads per step', '']
+    verdicts = []
+    for name in args.sets:
+        dims = DIM_SETS[name]
+        sd = make_state_dict(7, 'RAW', 'peaky', **dims)
+        models = {}
+        for w in ('f32', 'f16'):
+            m = WaveRNN(**dims, mode='RAW')
+            m.verbose = False
+            m.teamg_weights = w
+            m.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in sd.items()})
+            m.to('cuda:0')
+            models[w] = m
+        teams = models['f32'].native().team_info()[1]
+        B, T = 8 * teams, FRAMES[name]
+        steps = T * dims['hop_length']
+        plans = {}
+        for R in (2, 4, 8):
+            try:
+                plans[R] = {w: _cabi.teamg_plan_fmt(R, w, -1, mode='RAW', **dims) for w in ('f32', 'f16')}
+            except _cabi.WrnnError:
+                pass
+        lines.append(f'set {name}: rnn {dims["rnn_dims"]}, fc {dims["fc_dims"]}, hop {dims["hop_length"]}; {B} rows x {steps} steps on {teams} teams; rows per team admitted: {sorted(plans)}')
+        mels = torch.from_numpy(make_mels(5, B, T, feat_dims=dims['feat_dims'])).cuda()
+        ms = {(R, w): [] for R in plans for w in ('f32', 'f16')}
+        for rep in range(args.warmup + args.reps):
+            for R, w in ms:
+                m = models[w]
+                m.generate_raw(mels, False, 11000, 550, noise_mode='philox', seed=99, kernel='teamg_batch', batch_rows=R)
+                lt = m.last_timing
+                assert lt['kernel'] == _cabi.KERNEL_TEAMG_BATCH and lt['steps'] == steps and lt['rows'] == B and lt['batch_rows'] == R and lt['teamg_weights'] == w
+                if rep >= args.warmup:
+                    ms[(R, w)].append(float(lt['loop_ms']))
+        us = {k: float(np.median(v)) * 1e3 / (steps * B) for k, v in ms.items()}
+        spread = {k: (max(v) - min(v)) * 1e3 / (steps * B) for k, v in ms.items()}
+        for R in sorted(plans):
+            for w in ('f32', 'f16'):
+                p = plans[R][w]
+                lines.append(f'  R={R} {w}  {us[(R, w)]:8.3f} us/step/row  {1e3 / us[(R, w)]:9.2f} ksamples/s in all  spread {spread[(R, w)]:.3f}   streamed {p["streamed_bytes_step"] / 1e6:6.2f} MB '
+                             f'per step, LDS {p["lds_bytes"]}   calls (ms): ' + ' '.join(f'{v:.3f}' for v in ms[(R, w)]))
+            margin = max(spread[(R, 'f32')], spread[(R, 'f16')])
+            verdicts.append(f'set {name} R={R}: f16 / f32 time {us[(R, "f16")] / us[(R, "f32")]:.3f} (streamed bytes f16 / f32 '
+                            f'{plans[R]["f16"]["streamed_bytes_step"] / max(plans[R]["f32"]["streamed_bytes_step"], 1):.3f}), margin {margin:.3f} -> '
+                            f'{"f16 SLOWER than f32 beyond the spread" if us[(R, "f16")] - us[(R, "f32")] > margin else "f16 not slower than f32"}')
+        lines.append('')
+        del models
+        torch.cuda.empty_cache()
+    lines += verdicts
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--sets', default='ACD')
     ap.add_argument('--out', default=None)
+    ap.add_argument('--weights', choices=('f32', 'f16'), default='f32', help="f16: time the fp32 image against the fp16 image of TEAMG_BATCH instead")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise RuntimeError('any_dims_batch_latency.py measures on an MI355X: no GPU, no figures')
@@ -39,6 +108,8 @@ def main():
     from tacotronv2_wavernn_chinese_amd.synth import make_mels, make_state_dict
     from tacotronv2_wavernn_chinese_amd.vocoder import WaveRNN
     from tests.teamg_cases import DIM_SETS
+    if args.weights == 'f16':
+        return weights_session(args)
     lines = [f'many rows on other dims, {torch.cuda.get_device_name(0)}, torch {torch.__version__}', '',
              f'loop_ms of one call (HIP events around the loop kernel), {args.warmup} warm-up + {args.reps} timed calls per kernel, alternating; RAW, Philox noise',
              'us/step/row = median loop time / (steps x rows); streamed = weight bytes a team reads per step, per row of its batch (wrnn_teamg_batch_plan)', '']

@@ -6,7 +6,14 @@
 Dim sets A (256 / 384), C (1024 / 1024) and D (the reference hparams, TEAMG forced) of tests/teamg_cases.py at B = 1 and B = 8 rows, the
 same mels and the same Philox seed for both kernels, about 250 steps per row.  Timed: `wrnn_timing.loop_ms`, the HIP events around the
 loop kernel of one call; warm-up calls first, then `--reps` timed calls per kernel, the two kernels alternating; every call is listed, the
-median is what the ratio is made of.  Next to it the bytes TEAMG streams per step (`wrnn_teamg_plan`) and what that is per second and XCD."""
+median is what the ratio is made of.  Next to it the bytes TEAMG streams per step (`wrnn_teamg_plan`) and what that is per second and XCD.
+
+    python tools/any_dims_latency.py --weights f16 [--out profiles/any_dims_f16.txt]
+
+times WRNN_KERNEL_TEAMG with the fp32 weight image against the same kernel with the fp16 image (`teamg_weights='f16'`) instead: two
+handles of one model, the two formats alternating call by call, the same shapes, mels and seed; per shape the median, the min-to-max
+spread of either, the bytes streamed per step in either format (`wrnn_teamg_plan_fmt`) and whether f16 is slower than f32 by more than the
+larger spread."""
 import argparse
 import os
 import sys
@@ -20,11 +27,71 @@ sys.path.insert(0, ROOT)
 FRAMES = {'A': 2, 'C': 42, 'D': 1}      # 256, 252 and 275 steps
 
 
+def weights_session(args):
+    """fp32 image against fp16 image, WRNN_KERNEL_TEAMG, B = 1 and B = 8 rows."""
+    from tacotronv2_wavernn_chinese_amd import _cabi
+    from tacotronv2_wavernn_chinese_amd.synth import make_mels, make_state_dict
+    from tacotronv2_wavernn_chinese_amd.vocoder import WaveRNN
+    from tests.teamg_cases import DIM_SETS
+    lines = [f'fp16 weight image of the any-dims team kernel, {torch.cuda.get_device_name(0)}, torch {torch.__version__}', '',
+             f'loop_ms of one call (HIP events around the loop kernel), {args.warmup} warm-up + {args.reps} timed calls per format, alternating; RAW, Philox noise',
+             'us/step = median loop time / steps per row; spread = (max - min) of the timed calls per step; GB/s per XCD = bytes streamed per step / us per step', '']
+    verdicts = []
+    for name in ('A', 'C', 'D'):
+        dims = DIM_SETS[name]
+        sd = make_state_dict(7, 'RAW', 'peaky', **dims)
+        models, plans = {}, {}
+        for w in ('f32', 'f16'):
+            m = WaveRNN(**dims, mode='RAW')
+            m.verbose = False
+            m.teamg_weights = w
+            m.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in sd.items()})
+            m.to('cuda:0')
+            models[w] = m
+            plans[w] = _cabi.teamg_plan_fmt(1, w, -1, mode='RAW', **dims)
+        lines.append(f'set {name}: rnn {dims["rnn_dims"]}, fc {dims["fc_dims"]}, feat {dims["feat_dims"]}, res_out {dims["res_out_dims"]}, bits {dims["bits"]}, hop {dims["hop_length"]}; '
+                     + '; '.join(f'{w}: weights {sum(L["weight_bytes"] for L in plans[w]["layers"].values()) / 1e6:.2f} MB, streamed {plans[w]["streamed_bytes_step"] / 1e6:.2f} MB '
+                                 f'per step and team, LDS {plans[w]["lds_bytes"]}' for w in ('f32', 'f16')))
+        for B in (1, 8):
+            T = FRAMES[name]
+            steps = T * dims['hop_length']
+            mels = torch.from_numpy(make_mels(5, B, T, feat_dims=dims['feat_dims'])).cuda()
+            ms = {'f32': [], 'f16': []}
+            for rep in range(args.warmup + args.reps):
+                for w in ('f32', 'f16'):
+                    m = models[w]
+                    m.generate_raw(mels, False, 11000, 550, noise_mode='philox', seed=99, kernel='teamg')
+                    lt = m.last_timing
+                    assert lt['kernel'] == _cabi.KERNEL_TEAMG and lt['steps'] == steps and lt['teamg_weights'] == w
+                    if rep >= args.warmup:
+                        ms[w].append(float(lt['loop_ms']))
+            us = {w: float(np.median(v)) * 1e3 / steps for w, v in ms.items()}
+            spread = {w: (max(v) - min(v)) * 1e3 / steps for w, v in ms.items()}
+            for w in ('f32', 'f16'):
+                lines.append(f'  B={B} {steps} steps  {w}  {us[w]:8.2f} us/step  spread {spread[w]:.2f}  {1e3 / us[w]:7.2f} ksamples/s per row  '
+                             f'{plans[w]["streamed_bytes_step"] / us[w] / 1e3:7.1f} GB/s per XCD   calls (ms): ' + ' '.join(f'{v:.3f}' for v in ms[w]))
+            margin = max(spread.values())
+            ratio_b = plans['f16']['streamed_bytes_step'] / max(plans['f32']['streamed_bytes_step'], 1)
+            verdicts.append(f'set {name} B={B}: f16 / f32 time per step {us["f16"] / us["f32"]:.3f} (streamed bytes f16 / f32 {ratio_b:.3f}), margin {margin:.2f} us -> '
+                            f'{"f16 SLOWER than f32 beyond the spread" if us["f16"] - us["f32"] > margin else "f16 not slower than f32"}; '
+                            f'f16 {1e3 / us["f16"]:.2f} ksamples/s per row ({"above" if 1e3 / us["f16"] > 22.05 else "below"} 22.05)')
+        lines.append('')
+        del models
+        torch.cuda.empty_cache()
+    lines += verdicts
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--weights', choices=('f32', 'f16'), default='f32', help="f16: time the fp32 image against the fp16 image of TEAMG instead")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise RuntimeError('any_dims_latency.py measures on an MI355X: no GPU, no figures')
@@ -34,6 +101,8 @@ def main():
     from tacotronv2_wavernn_chinese_amd.synth import make_mels, make_state_dict
     from tacotronv2_wavernn_chinese_amd.vocoder import WaveRNN
     from tests.teamg_cases import DIM_SETS
+    if args.weights == 'f16':
+        return weights_session(args)
     lines = [f'generate loop on other dims, {torch.cuda.get_device_name(0)}, torch {torch.__version__}', '',
              f'loop_ms of one call (HIP events around the loop kernel), {args.warmup} warm-up + {args.reps} timed calls per kernel, alternating; RAW, Philox noise',
              'us/step = median loop time / steps per row; GB/s per XCD = the bytes TEAMG streams per step (wrnn_teamg_plan) / its us per step', '']
