@@ -534,6 +534,47 @@ int wrnn_mel_tables(const wrnn_mel_handle *h, float *window, float *twiddle, int
 const char *wrnn_mel_last_error(const wrnn_mel_handle *h);
 void wrnn_mel_destroy(wrnn_mel_handle *h);
 
+/* Feature profiles of the mel front end (added to ABI 9 like the front end itself: one new struct and one new entry point, nothing
+ * existing changes).  The features above are those of wavernn/utils/dsp.py.  The mels the reference's WaveRNN is trained on, and that
+ * Tacotron hands it at synthesis time, come from another chain: tacotron/datasets/preprocessor.py:52-121, tacotron/datasets/audio.py:
+ * 95-102, 203-207, 250-295, and the map to [0, 1] of wavernn_preprocess.py:149-159.  Every stage in which the two differ is a field
+ * here, usable on its own.  For one clip x of n >= 1 samples:
+ *   1. preemphasis k (0.97; 0 = off):        p[0] = x[0], p[i] = x[i] - k x[i-1]; p exists on [0, n) only.
+ *   2. preemph_rescale r (0.999; 0 = off):   p <- p / max|p| * r; a clip with max|p| == 0 stays as it is.
+ *   3. pad_mode:                              frame t reads p at t hop - n_fft/2 + i; outside [0, n) it is the reflection
+ *                                             (WRNN_MEL_PAD_REFLECT, as above) or 0 (WRNN_MEL_PAD_ZERO, librosa pad_mode='constant').
+ *                                             With zero padding a clip of any n >= 1 has 1 + n / hop frames.
+ *   4. magnitude_power (2; 1 = as above):    the filterbank sees |X| or |X|^2 = re^2 + im^2.
+ *   5. fmax (7600; 0 = sample_rate / 2):     the upper edge of the Slaney filterbank.
+ *   6. ref_level_db (20; 0 = as above):      S = 20 log10(max(10^(min_level_db / 20), mel)) - ref_level_db.
+ *   7. max_abs_value A (4; 0 = as above):    sym = clip(2 A ((S - min_level_db) / -min_level_db) - A, -A, A), the value Tacotron's
+ *                                             preprocessing stores, then out = clip((sym + A) / (2 A), 0, 1).  A == 0: the direct
+ *                                             clip((S - min_level_db) / -min_level_db, 0, 1).
+ * The values in parentheses are the reference's (tacotron_hparams.py); the struct itself has no defaults.  All fields zero apart from
+ * pad_mode = WRNN_MEL_PAD_REFLECT and magnitude_power = 1 is the profile of the plain create entry, and a handle made with it runs the
+ * same kernel and gives the same bits (fmax changes the filterbank table only, and keeps that kernel too).  Any other profile runs a
+ * second instantiation of that kernel, whose profile fields are run-time, workgroup-uniform switches; steps 1 to 3 are fused into its
+ * tap gather (no pre-emphasised copy of a clip is written), and with preemph_rescale != 0 one reduction launch in front of it computes
+ * the clips' pre-emphasised peaks into a workspace the handle owns (65535 floats, allocated with the tables), so calls on ONE handle
+ * must be ordered by the caller (one stream at a time).  The call still never waits on the host.
+ * WRNN_ERR_INVALID: struct_size other than sizeof(wrnn_mel_features), an unknown pad_mode, magnitude_power outside {1, 2}, fmax != 0
+ * outside (fmin, sample_rate / 2], a negative (or NaN) preemphasis, preemph_rescale or max_abs_value, a ref_level_db that is not finite,
+ * and whatever the plain create entry refuses.  n_fft != 2048 stays WRNN_ERR_UNSUPPORTED.  The frames, tables and launch entries above work
+ * on either kind of handle; the frames entry refuses n < n_fft/2 + 1 under reflect padding and n < 1 under zero padding. */
+#define WRNN_MEL_PAD_REFLECT 0
+#define WRNN_MEL_PAD_ZERO 1
+typedef struct wrnn_mel_features {
+    uint32_t struct_size;    /* sizeof(wrnn_mel_features) */
+    int32_t pad_mode;        /* WRNN_MEL_PAD_* */
+    int32_t magnitude_power; /* 1 or 2 */
+    float fmax;              /* Hz; 0 = sample_rate / 2 */
+    float ref_level_db;
+    float preemphasis;
+    float preemph_rescale;
+    float max_abs_value;
+} wrnn_mel_features;
+int wrnn_mel_create_features(const wrnn_mel_config *cfg, const wrnn_mel_features *features, wrnn_mel_handle **out);
+
 /* ---- training data on the device (added to ABI 9 like the mel front end: two new functions, no struct and no existing entry changes,
  * so the number stays; a binding can tell a build from before them only by the missing symbols).  What wavernn_preprocess.py and
  * collate_vocoder (wavernn/utils/dataset.py:107-133) do on the host.  Neither entry takes a handle: there is no state and no error

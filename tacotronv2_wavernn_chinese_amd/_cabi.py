@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wr
                     'wrnn_stream_open', 'wrnn_stream_push', 'wrnn_stream_sync', 'wrnn_stream_info', 'wrnn_stream_ready_steps',
                     'wrnn_stream_close', 'wrnn_plan_folded', 'wrnn_generate_folded', 'wrnn_epilogue_folded',
                     'wrnn_mel_create', 'wrnn_mel_frames', 'wrnn_melspectrogram', 'wrnn_mel_tables', 'wrnn_mel_last_error', 'wrnn_mel_destroy',
+                    'wrnn_mel_create_features',
                     'wrnn_quantise', 'wrnn_collate_windows',
                     'wrnn_resample_create', 'wrnn_resample_out_len', 'wrnn_resample_bank', 'wrnn_resample', 'wrnn_resample_last_error',
                     'wrnn_resample_destroy', 'wrnn_condition_frames', 'wrnn_condition', 'wrnn_teamg_plan', 'wrnn_debug_teamg_lds_budget',
@@ -104,6 +105,19 @@ class Timing(C.Structure):
 class MelConfig(C.Structure):
     _fields_ = [('sample_rate', C.c_int32), ('n_fft', C.c_int32), ('hop_length', C.c_int32), ('win_length', C.c_int32),
                 ('n_mels', C.c_int32), ('fmin', C.c_float), ('min_level_db', C.c_float), ('device', C.c_int32)]
+
+
+MEL_PAD_MODES = {'reflect': 0, 'zero': 1}   # WRNN_MEL_PAD_*
+
+
+class MelFeatures(C.Structure):
+    """``wrnn_mel_features``; the values a fresh one holds are the default profile (``wrnn_mel_create``'s)."""
+    _fields_ = [('struct_size', C.c_uint32), ('pad_mode', C.c_int32), ('magnitude_power', C.c_int32), ('fmax', C.c_float),
+                ('ref_level_db', C.c_float), ('preemphasis', C.c_float), ('preemph_rescale', C.c_float), ('max_abs_value', C.c_float)]
+
+    def __init__(self, pad_mode=0, magnitude_power=1, fmax=0.0, ref_level_db=0.0, preemphasis=0.0, preemph_rescale=0.0, max_abs_value=0.0):
+        super().__init__(C.sizeof(MelFeatures), int(pad_mode), int(magnitude_power), float(fmax), float(ref_level_db), float(preemphasis),
+                         float(preemph_rescale), float(max_abs_value))
 
 
 WEIGHT_FORMATS = {'f32': 0, 'f16': 1}   # WRNN_WEIGHTS_*: the element type of the TEAMG / TEAMG_BATCH weight image
@@ -305,6 +319,8 @@ def load_library() -> C.CDLL:
     lib.wrnn_epilogue_folded.restype = C.c_int
     lib.wrnn_mel_create.argtypes = [C.POINTER(MelConfig), C.POINTER(vp)]
     lib.wrnn_mel_create.restype = C.c_int
+    lib.wrnn_mel_create_features.argtypes = [C.POINTER(MelConfig), C.POINTER(MelFeatures), C.POINTER(vp)]
+    lib.wrnn_mel_create_features.restype = C.c_int
     lib.wrnn_mel_frames.argtypes = [vp, C.c_int64]
     lib.wrnn_mel_frames.restype = C.c_int64
     lib.wrnn_melspectrogram.argtypes = [vp, vp, C.c_int64, vp, C.c_int32, C.c_int32, vp, vp]
@@ -731,15 +747,20 @@ class NativeDeepmind:
 
 class NativeMel:
     """Owner of one ``wrnn_mel_handle`` (the wav -> mel front end; no weights).  Creating it touches no device; a configuration the
-    library refuses raises ``ValueError`` (n_fft other than 2048: WRNN_ERR_UNSUPPORTED; the rest: WRNN_ERR_INVALID)."""
+    library refuses raises ``ValueError`` (n_fft other than 2048: WRNN_ERR_UNSUPPORTED; the rest: WRNN_ERR_INVALID).  ``features``: a
+    ``MelFeatures`` (``wrnn_mel_create_features``); ``None`` is the default profile through ``wrnn_mel_create``."""
 
-    def __init__(self, *, sample_rate, n_fft, hop_length, win_length, n_mels, fmin, min_level_db, device: int = 0):
+    def __init__(self, *, sample_rate, n_fft, hop_length, win_length, n_mels, fmin, min_level_db, device: int = 0, features=None):
         self.lib = load_library()
         cfg = MelConfig(int(sample_rate), int(n_fft), int(hop_length), int(win_length), int(n_mels), float(fmin), float(min_level_db), int(device))
         self.cfg = cfg
+        self.features = features
         self.device = int(device)
         self._h = C.c_void_p()
-        rc = self.lib.wrnn_mel_create(C.byref(cfg), C.byref(self._h))
+        if features is None:
+            rc = self.lib.wrnn_mel_create(C.byref(cfg), C.byref(self._h))
+        else:
+            rc = self.lib.wrnn_mel_create_features(C.byref(cfg), C.byref(features), C.byref(self._h))
         if rc != 0:
             msg = self.lib.wrnn_mel_last_error(self._h).decode() if self._h else 'wrnn_mel_create failed'
             self.close()
@@ -750,8 +771,11 @@ class NativeMel:
             raise WrnnError(rc, self.lib.wrnn_mel_last_error(self._h).decode())
 
     def frames(self, n_samples: int) -> int:
-        """Host-only ``wrnn_mel_frames``: 1 + n // hop; ``ValueError`` for a clip too short to reflect-pad."""
+        """Host-only ``wrnn_mel_frames``: 1 + n // hop; ``ValueError`` for a clip too short to reflect-pad (an empty one under zero
+        padding)."""
         t = int(self.lib.wrnn_mel_frames(self._h, int(n_samples)))
+        if t < 0 and self.features is not None and self.features.pad_mode == MEL_PAD_MODES['zero']:
+            raise ValueError(f'a clip of {int(n_samples)} samples has no frames: at least 1 sample is needed')
         if t < 0:
             raise ValueError(f'a clip of {int(n_samples)} samples cannot be reflect-padded by n_fft/2 = {self.cfg.n_fft // 2}: '
                              f'at least {self.cfg.n_fft // 2 + 1} samples are needed')

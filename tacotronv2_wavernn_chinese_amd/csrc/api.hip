@@ -856,9 +856,11 @@ int wrnn_phase_cycles(wrnn_handle *h, double *out) {
 
 struct wrnn_mel_handle {
     wrnn_mel_config cfg{};
+    wrnn_mel_features feat{};
+    bool profile = false;         // feat differs from the default profile: the kernel's profile instantiation runs
     WrnnMelTables tab;
-    void *dev = nullptr;          // one allocation: window | twiddle | rows | weights, made by the first wrnn_melspectrogram
-    size_t o_tw = 0, o_rows = 0, o_w = 0;
+    void *dev = nullptr;          // one allocation: window | twiddle | rows | weights | peak workspace, made by the first wrnn_melspectrogram
+    size_t o_tw = 0, o_rows = 0, o_w = 0, o_peak = 0;
     std::string err;
 };
 
@@ -881,21 +883,40 @@ int mel_fail(wrnn_mel_handle *h, int code, const char *fmt, ...) {
 
 extern "C" {
 
-int wrnn_mel_create(const wrnn_mel_config *cfg, wrnn_mel_handle **out) {
-    if (!cfg || !out) return WRNN_ERR_INVALID;
+static const wrnn_mel_features MEL_DEFAULT_FEATURES = {(uint32_t)sizeof(wrnn_mel_features), WRNN_MEL_PAD_REFLECT, 1, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+static const int MEL_MAX_B = 65535;   // grid.y; also the size of the handle's peak workspace
+
+int wrnn_mel_create(const wrnn_mel_config *cfg, wrnn_mel_handle **out) { return wrnn_mel_create_features(cfg, &MEL_DEFAULT_FEATURES, out); }
+
+int wrnn_mel_create_features(const wrnn_mel_config *cfg, const wrnn_mel_features *f, wrnn_mel_handle **out) {
+    if (!cfg || !f || !out) return WRNN_ERR_INVALID;
     wrnn_mel_handle *h = new wrnn_mel_handle();
     *out = h;
     h->cfg = *cfg;
+    if (f->struct_size != sizeof(wrnn_mel_features))
+        return mel_fail(h, WRNN_ERR_INVALID, "features.struct_size = %u, this library's wrnn_mel_features has %zu bytes", f->struct_size, sizeof(wrnn_mel_features));
+    h->feat = *f;
     if (cfg->n_fft != WRNN_MEL_NFFT) return mel_fail(h, WRNN_ERR_UNSUPPORTED, "n_fft = %d: the front end is built for n_fft = %d only", cfg->n_fft, WRNN_MEL_NFFT);
     if (cfg->hop_length < 1 || !(cfg->min_level_db < 0.0f) || cfg->device < 0)
         return mel_fail(h, WRNN_ERR_INVALID, "bad configuration: hop_length >= 1, min_level_db < 0, device >= 0");
-    if (!wrnn_mel_build_tables(cfg->sample_rate, cfg->win_length, cfg->n_mels, (double)cfg->fmin, &h->tab))
+    if ((f->pad_mode != WRNN_MEL_PAD_REFLECT && f->pad_mode != WRNN_MEL_PAD_ZERO) || (f->magnitude_power != 1 && f->magnitude_power != 2))
+        return mel_fail(h, WRNN_ERR_INVALID, "bad features: pad_mode is WRNN_MEL_PAD_REFLECT or WRNN_MEL_PAD_ZERO, magnitude_power 1 or 2");
+    if (!(f->preemphasis >= 0.0f) || !(f->preemph_rescale >= 0.0f) || !(f->max_abs_value >= 0.0f) || !std::isfinite(f->preemphasis) ||
+        !std::isfinite(f->preemph_rescale) || !std::isfinite(f->max_abs_value) || !std::isfinite(f->ref_level_db))
+        return mel_fail(h, WRNN_ERR_INVALID, "bad features: preemphasis, preemph_rescale and max_abs_value are finite and >= 0, ref_level_db is finite");
+    if (f->fmax != 0.0f && !((double)f->fmax > (double)cfg->fmin && (double)f->fmax <= 0.5 * (double)cfg->sample_rate))
+        return mel_fail(h, WRNN_ERR_INVALID, "bad features: fmax = %g is not in (fmin, sample_rate / 2] (0 stands for sample_rate / 2)", (double)f->fmax);
+    if (!wrnn_mel_build_tables(cfg->sample_rate, cfg->win_length, cfg->n_mels, (double)cfg->fmin, (double)f->fmax, &h->tab))
         return mel_fail(h, WRNN_ERR_INVALID, "bad configuration: 1 <= win_length <= n_fft, 1 <= n_mels <= %d, 0 <= fmin < sample_rate / 2", WRNN_MEL_MAX_MELS);
+    // fmax lives in the filterbank table alone, so it needs no arm of the kernel
+    h->profile = f->pad_mode != WRNN_MEL_PAD_REFLECT || f->magnitude_power != 1 || f->ref_level_db != 0.0f || f->preemphasis != 0.0f ||
+                 f->preemph_rescale != 0.0f || f->max_abs_value != 0.0f;
     return WRNN_OK;
 }
 
 int64_t wrnn_mel_frames(const wrnn_mel_handle *h, int64_t n_samples) {
-    if (!h || h->tab.window.empty() || n_samples < h->cfg.n_fft / 2 + 1) return WRNN_ERR_INVALID;
+    if (!h || h->tab.window.empty()) return WRNN_ERR_INVALID;
+    if (n_samples < (h->feat.pad_mode == WRNN_MEL_PAD_ZERO ? 1 : h->cfg.n_fft / 2 + 1)) return WRNN_ERR_INVALID;
     return 1 + n_samples / h->cfg.hop_length;
 }
 
@@ -914,7 +935,7 @@ int wrnn_melspectrogram(wrnn_mel_handle *h, const float *wav_dev, int64_t n_max,
                         float *mel_out_dev, void *stream) {
     if (!h) return WRNN_ERR_INVALID;
     if (h->tab.window.empty()) return mel_fail(h, WRNN_ERR_STATE, "the handle's configuration was refused by wrnn_mel_create");
-    if (!wav_dev || !n_samples_dev || !mel_out_dev || n_max < 1 || B < 1 || B > 65535 || T_max < 1)
+    if (!wav_dev || !n_samples_dev || !mel_out_dev || n_max < 1 || B < 1 || B > MEL_MAX_B || T_max < 1)
         return mel_fail(h, WRNN_ERR_INVALID, "bad arguments: device pointers, n_max >= 1, 1 <= B <= 65535, T_max >= 1");
     MEL_TRY(h, hipSetDevice(h->cfg.device));
     const WrnnMelTables &t = h->tab;
@@ -923,7 +944,8 @@ int wrnn_melspectrogram(wrnn_mel_handle *h, const float *wav_dev, int64_t n_max,
         h->o_tw = up(t.window.size() * 4);
         h->o_rows = h->o_tw + up(t.twiddle.size() * 4);
         h->o_w = h->o_rows + up(t.rows.size() * 4);
-        const size_t total = h->o_w + up(t.weights.size() * 4);
+        h->o_peak = h->o_w + up(t.weights.size() * 4);
+        const size_t total = h->o_peak + (h->feat.preemph_rescale > 0.0f ? up((size_t)MEL_MAX_B * 4) : 0);
         std::vector<char> img(total, 0);
         memcpy(img.data(), t.window.data(), t.window.size() * 4);
         memcpy(img.data() + h->o_tw, t.twiddle.data(), t.twiddle.size() * 4);
@@ -945,7 +967,18 @@ int wrnn_melspectrogram(wrnn_mel_handle *h, const float *wav_dev, int64_t n_max,
     a.rows = (const int32_t *)(d + h->o_rows); a.weights = (const float *)(d + h->o_w);
     a.n_max = n_max; a.T_max = T_max; a.n_mels = h->cfg.n_mels; a.hop = h->cfg.hop_length; a.win_length = h->cfg.win_length;
     a.min_level_db = h->cfg.min_level_db;
-    MEL_TRY(h, wrnn_launch_melspec(a, B, (hipStream_t)stream));
+    if (h->profile) {
+        const wrnn_mel_features &f = h->feat;
+        a.pad_zero = f.pad_mode == WRNN_MEL_PAD_ZERO; a.power2 = f.magnitude_power == 2;
+        a.preemph = f.preemphasis; a.rescale = f.preemph_rescale; a.ref_level_db = f.ref_level_db; a.max_abs = f.max_abs_value;
+        a.floor_amp = (float)std::pow(10.0, (double)h->cfg.min_level_db / 20.0);
+        if (f.preemph_rescale > 0.0f) {
+            float *peak = (float *)((char *)h->dev + h->o_peak);
+            a.peak = peak;
+            MEL_TRY(h, wrnn_launch_mel_peak(wav_dev, n_max, n_samples_dev, B, f.preemphasis, peak, (hipStream_t)stream));
+        }
+    }
+    MEL_TRY(h, wrnn_launch_melspec(a, B, h->profile, (hipStream_t)stream));
     return WRNN_OK;
 }
 

@@ -29,8 +29,19 @@ struct WrnnMelArgs {
     int64_t n_max;
     int32_t T_max, n_mels, hop, win_length;
     float min_level_db;
+    // the feature profile (wrnn_mel_features); read by the profile instantiation of the kernel only
+    const float *peak;            // [B] max |pre-emphasised clip|, written by the peak launch; NULL when preemph_rescale == 0
+    int32_t pad_zero, power2;     // zero padding instead of reflection; |X|^2 instead of |X|
+    float preemph, rescale;       // k of x[i] - k x[i-1]; the peak the pre-emphasised clip is scaled to (0: unscaled)
+    float floor_amp;              // 10^(min_level_db / 20), rounded to float32
+    float ref_level_db, max_abs;
 };
 
 // Host only.  Returns false for a configuration outside the supported set (n_mels, win_length, fmin); n_fft is the caller's check.
-bool wrnn_mel_build_tables(int sample_rate, int win_length, int n_mels, double fmin, WrnnMelTables *out);
-hipError_t wrnn_launch_melspec(const WrnnMelArgs &a, int B, hipStream_t s);
+// fmax == 0: sample_rate / 2.
+bool wrnn_mel_build_tables(int sample_rate, int win_length, int n_mels, double fmin, double fmax, WrnnMelTables *out);
+// profile == false: the kernel of the default features (reflect padding, |X|, no pre-emphasis, direct normalisation), which reads none
+// of the profile fields.  profile == true: every profile field is a run-time, workgroup-uniform switch.
+hipError_t wrnn_launch_melspec(const WrnnMelArgs &a, int B, bool profile, hipStream_t s);
+// peak[b] = max over i < min(n_samples[b], n_max) of |x[i] - preemph * x[i-1]| (x[-1] = 0): a memset and one launch, asynchronous.
+hipError_t wrnn_launch_mel_peak(const float *wav, int64_t n_max, const int32_t *n_samples, int B, float preemph, float *peak, hipStream_t s);

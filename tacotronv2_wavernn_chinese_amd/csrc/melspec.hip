@@ -3,6 +3,11 @@
 // filterbank).  One workgroup of 256 threads per frame, grid (T_max, B): the frame's non-zero taps are gathered straight from the
 // clip with the reflect index, the 2048 real points run as a 1024-point complex radix-4 transform in LDS plus the split pass,
 // the magnitudes stay in LDS and the sparse filterbank, dB and normalisation finish the column.  Nothing crosses workgroups.
+//
+// The kernel is a template on PROFILE.  <false> is the kernel above and nothing else.  <true> carries the feature profile of
+// wrnn_mel_features (the Tacotron-side mel of tacotron/datasets/audio.py:95-102, 203-207, 250-295) as run-time, workgroup-uniform
+// arms of the same stages: pre-emphasis and the rescale to the pre-emphasised peak fused into the tap gather, zero padding, the power
+// spectrum, ref_level_db and the symmetric normalisation.  The peak comes from melspec_peak_kernel, one launch in front.
 #include <cmath>
 
 #include "mel_internal.h"
@@ -19,14 +24,46 @@ __device__ inline int rev4(int k) {
     return (int)(((r & 0x2AAu) >> 1) | ((r & 0x155u) << 1));
 }
 
+// sample j of the pre-emphasised clip, 0 <= j < n: x[j] - k x[j-1] with x[-1] = 0.  The peak launch and the tap gather share it.
+__device__ inline float preemph_at(const float *x, long j, float k) { return x[j] - k * (j > 0 ? x[j - 1] : 0.0f); }
+
+constexpr int PEAK_THREADS = 256, PEAK_PER_THREAD = 16, PEAK_CHUNK = PEAK_THREADS * PEAK_PER_THREAD;
+
+// grid (ceil(n_max / PEAK_CHUNK), B): the maximum of one chunk of one clip, then one atomic per workgroup.  The values are
+// non-negative floats, whose order is the order of their bit patterns, so the atomic is an unsigned integer maximum and the result does
+// not depend on the order the workgroups arrive in.  peak[] is zeroed in front of the launch.
+__global__ void __launch_bounds__(PEAK_THREADS) melspec_peak_kernel(const float *wav, long n_max, const int32_t *n_samples, float k, float *peak) {
+    __shared__ float part[PEAK_THREADS / 64];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    long n = n_samples[b];
+    if (n > n_max) n = n_max;
+    const long lo = (long)blockIdx.x * PEAK_CHUNK;
+    if (lo >= n) return;              // workgroup-uniform: the chunk lies past this clip's own end
+    const float *x = wav + (long)b * n_max;
+    float m = 0.0f;
+#pragma unroll 4
+    for (int i = 0; i < PEAK_PER_THREAD; ++i) {
+        const long j = lo + tid + (long)i * PEAK_THREADS;
+        if (j < n) m = fmaxf(m, fabsf(preemph_at(x, j, k)));
+    }
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if ((tid & 63) == 0) part[tid >> 6] = m;
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < PEAK_THREADS / 64; ++w) m = fmaxf(m, part[w]);
+        atomicMax((unsigned int *)(peak + b), __float_as_uint(m));
+    }
+}
+
+template <bool PROFILE>
 __global__ void __launch_bounds__(WRNN_MEL_THREADS) melspec_kernel(WrnnMelArgs a) {
     __shared__ float2 z[NC];          // 8 KiB: the transform, in place
-    __shared__ float mag[NC + 1];     // 4 KiB + 4 B: |X[k]|, k = 0 .. n_fft/2
+    __shared__ float mag[NC + 1];     // 4 KiB + 4 B: |X[k]| (or |X[k]|^2), k = 0 .. n_fft/2
     const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     long n = a.n_samples[b];
     if (n > a.n_max) n = a.n_max;
-    // a clip that cannot be reflect-padded has no frames (the host side refuses it before the launch)
-    const long T_b = n >= NC + 1 ? 1 + n / a.hop : 0;
+    // a clip that cannot be reflect-padded has no frames (the host side refuses it before the launch); zero padding needs one sample
+    const long T_b = n >= (PROFILE && a.pad_zero ? 1 : NC + 1) ? 1 + n / a.hop : 0;
     float *out = a.out + (long)b * a.n_mels * a.T_max + t;
     if (t >= T_b) {                   // workgroup-uniform: past the clip's own end, the zero conditioning of a ragged batch
         for (int m = tid; m < a.n_mels; m += WRNN_MEL_THREADS) out[(long)m * a.T_max] = 0.0f;
@@ -36,6 +73,12 @@ __global__ void __launch_bounds__(WRNN_MEL_THREADS) melspec_kernel(WrnnMelArgs a
     const int off = (WRNN_MEL_NFFT - a.win_length) / 2;
     const long j0 = (long)t * a.hop - NC;          // clip index of frame sample 0
     // z[k] = x[2k] + i x[2k + 1] of the windowed frame, stored digit-reversed for the in-place decimation-in-time passes
+    // profile: the clip is pre-emphasised and scaled to the peak `rescale` on the fly; an all-zero clip (peak 0) stays as it is
+    float scale = 1.0f;
+    if (PROFILE && a.rescale > 0.0f) {
+        const float peak = a.peak[b];
+        if (peak > 0.0f) scale = a.rescale / peak;
+    }
     for (int k = tid; k < NC; k += WRNN_MEL_THREADS) {
         float v[2];
 #pragma unroll
@@ -44,9 +87,15 @@ __global__ void __launch_bounds__(WRNN_MEL_THREADS) melspec_kernel(WrnnMelArgs a
             v[e] = 0.0f;
             if (i >= 0 && i < a.win_length) {
                 long j = j0 + 2 * k + e;
-                if (j < 0) j = -j;
-                else if (j >= n) j = 2 * (n - 1) - j;
-                v[e] = x[j] * a.window[i];
+                if constexpr (PROFILE) {
+                    const bool outside = j < 0 || j >= n;
+                    if (outside && !a.pad_zero) j = j < 0 ? -j : 2 * (n - 1) - j;
+                    if (!outside || !a.pad_zero) v[e] = preemph_at(x, j, a.preemph) * scale * a.window[i];
+                } else {
+                    if (j < 0) j = -j;
+                    else if (j >= n) j = 2 * (n - 1) - j;
+                    v[e] = x[j] * a.window[i];
+                }
             }
         }
         z[rev4(k)] = make_float2(v[0], v[1]);
@@ -76,16 +125,24 @@ __global__ void __launch_bounds__(WRNN_MEL_THREADS) melspec_kernel(WrnnMelArgs a
     for (int k = tid; k <= NC / 2; k += WRNN_MEL_THREADS) {
         if (k == 0) {
             const float2 z0 = z[0];
-            mag[0] = fabsf(z0.x + z0.y);
-            mag[NC] = fabsf(z0.x - z0.y);
+            const float dc = z0.x + z0.y, ny = z0.x - z0.y;
+            const bool p2 = PROFILE && a.power2;
+            mag[0] = p2 ? dc * dc : fabsf(dc);
+            mag[NC] = p2 ? ny * ny : fabsf(ny);
         } else {
             const float2 zk = z[k], zn = z[NC - k];
             const float2 E = make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y));
             const float2 O = make_float2(0.5f * (zk.y + zn.y), -0.5f * (zk.x - zn.x));
             const float2 WO = cmul(a.twiddle[k], O);
             const float pr = E.x + WO.x, pi = E.y + WO.y, mr = E.x - WO.x, mi = E.y - WO.y;
-            mag[k] = sqrtf(pr * pr + pi * pi);
-            mag[NC - k] = sqrtf(mr * mr + mi * mi);
+            const float pp = pr * pr + pi * pi, mm = mr * mr + mi * mi;
+            if (PROFILE && a.power2) {
+                mag[k] = pp;
+                mag[NC - k] = mm;
+            } else {
+                mag[k] = sqrtf(pp);
+                mag[NC - k] = sqrtf(mm);
+            }
         }
     }
     __syncthreads();
@@ -101,10 +158,22 @@ __global__ void __launch_bounds__(WRNN_MEL_THREADS) melspec_kernel(WrnnMelArgs a
         acc += __shfl_xor(acc, 1);
         acc += __shfl_xor(acc, 2);
         if (m < a.n_mels && sub == 0) {
-            // 20 log10(1e-5) is -100 exactly; log10f of the float nearest to 1e-5 need not round to -5
-            const float S = acc > 1e-5f ? 20.0f * log10f(acc) : -100.0f;
-            const float v = (S - a.min_level_db) / -a.min_level_db;
-            out[(long)m * a.T_max] = fminf(fmaxf(v, 0.0f), 1.0f);
+            if constexpr (PROFILE) {
+                // the floor 10^(min_level_db / 20) is min_level_db exactly, as below; whatever lies under it is clipped to 0 anyway
+                const float S = (acc > a.floor_amp ? 20.0f * log10f(acc) : a.min_level_db) - a.ref_level_db;
+                float v = (S - a.min_level_db) / -a.min_level_db;
+                if (a.max_abs > 0.0f) {
+                    // the [-A, A] value Tacotron's preprocessing stores, then wavernn_preprocess.py's map to [0, 1]
+                    const float A = a.max_abs, sym = fminf(fmaxf(2.0f * A * v - A, -A), A);
+                    v = (sym + A) / (2.0f * A);
+                }
+                out[(long)m * a.T_max] = fminf(fmaxf(v, 0.0f), 1.0f);
+            } else {
+                // 20 log10(1e-5) is -100 exactly; log10f of the float nearest to 1e-5 need not round to -5
+                const float S = acc > 1e-5f ? 20.0f * log10f(acc) : -100.0f;
+                const float v = (S - a.min_level_db) / -a.min_level_db;
+                out[(long)m * a.T_max] = fminf(fmaxf(v, 0.0f), 1.0f);
+            }
         }
     }
 }
@@ -131,10 +200,11 @@ double mel_to_hz(double m) {
 
 }  // namespace
 
-bool wrnn_mel_build_tables(int sample_rate, int win_length, int n_mels, double fmin, WrnnMelTables *out) {
+bool wrnn_mel_build_tables(int sample_rate, int win_length, int n_mels, double fmin, double fmax_arg, WrnnMelTables *out) {
     const int N = WRNN_MEL_NFFT;
-    const double fmax = 0.5 * (double)sample_rate;
-    if (sample_rate < 1 || win_length < 1 || win_length > N || n_mels < 1 || n_mels > WRNN_MEL_MAX_MELS || !(fmin >= 0.0) || !(fmin < fmax))
+    const double nyquist = 0.5 * (double)sample_rate, fmax = fmax_arg == 0.0 ? nyquist : fmax_arg;
+    if (sample_rate < 1 || win_length < 1 || win_length > N || n_mels < 1 || n_mels > WRNN_MEL_MAX_MELS || !(fmin >= 0.0) || !(fmin < fmax) ||
+        !(fmax <= nyquist))
         return false;
     // scipy.signal.get_window('hann', win_length, fftbins=True): the symmetric window of win_length + 1 points without its last one
     out->window.resize(win_length);
@@ -147,8 +217,8 @@ bool wrnn_mel_build_tables(int sample_rate, int win_length, int n_mels, double f
         out->twiddle[2 * k] = (float)std::cos(ang);
         out->twiddle[2 * k + 1] = (float)-std::sin(ang);
     }
-    // librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax = sr / 2, htk=False, norm=1)
-    const std::vector<double> fftfreqs = linspace(0.0, fmax, 1 + N / 2);
+    // librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax, htk=False, norm=1); the bin frequencies run to sr / 2 whatever fmax is
+    const std::vector<double> fftfreqs = linspace(0.0, nyquist, 1 + N / 2);
     std::vector<double> mel_f = linspace(hz_to_mel(fmin), hz_to_mel(fmax), n_mels + 2);
     for (double &m : mel_f) m = mel_to_hz(m);
     out->rows.assign(3 * (size_t)n_mels, 0);
@@ -174,7 +244,17 @@ bool wrnn_mel_build_tables(int sample_rate, int win_length, int n_mels, double f
     return true;
 }
 
-hipError_t wrnn_launch_melspec(const WrnnMelArgs &a, int B, hipStream_t s) {
-    hipLaunchKernelGGL(melspec_kernel, dim3((unsigned)a.T_max, (unsigned)B), dim3(WRNN_MEL_THREADS), 0, s, a);
+hipError_t wrnn_launch_melspec(const WrnnMelArgs &a, int B, bool profile, hipStream_t s) {
+    const dim3 grid((unsigned)a.T_max, (unsigned)B), block(WRNN_MEL_THREADS);
+    if (profile) hipLaunchKernelGGL(melspec_kernel<true>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(melspec_kernel<false>, grid, block, 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t wrnn_launch_mel_peak(const float *wav, int64_t n_max, const int32_t *n_samples, int B, float preemph, float *peak, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(peak, 0, (size_t)B * sizeof(float), s);
+    if (e != hipSuccess) return e;
+    const dim3 grid((unsigned)((n_max + PEAK_CHUNK - 1) / PEAK_CHUNK), (unsigned)B);
+    hipLaunchKernelGGL(melspec_peak_kernel, grid, dim3(PEAK_THREADS), 0, s, wav, (long)n_max, n_samples, preemph, peak);
     return hipGetLastError();
 }

@@ -23,6 +23,22 @@ from . import _cabi
 from .train import draw_window_offsets
 
 LIST_NAME = 'wavernn_training_data.txt'
+FEATURES_NAME = 'wavernn_training_features.txt'   # next to the list file: the feature profile of the saved mels, one word
+
+
+def saved_features(list_file: Union[str, Path]) -> str:
+    """The feature profile ``DeviceCorpus.save`` recorded next to ``list_file``; ``'vocoder'`` where nothing is recorded (a corpus saved
+    before the profiles, or the reference's own files)."""
+    note = Path(list_file).expanduser().parent / FEATURES_NAME
+    return note.read_text(encoding='utf-8').strip() if note.is_file() else 'vocoder'
+
+
+def check_saved_features(list_file: Union[str, Path], features: str) -> None:
+    """``ValueError`` when the corpus saved at ``list_file`` holds other features than the requested ones."""
+    have = saved_features(list_file)
+    if have != features:
+        raise ValueError(f'{list_file} holds {have!r} mel features, {features!r} were asked for: a vocoder trained on one kind cannot be '
+                         f'driven with the other.  Pass --features {have}, or preprocess the wavs again with --features {features}')
 
 
 def signal_bits(hp) -> Tuple[int, bool]:
@@ -52,8 +68,9 @@ class DeviceCorpus:
 
     def __init__(self, labels: torch.Tensor, mels: torch.Tensor, label_off, label_len, mel_off, frames, n_mels: int, stems: Sequence[str],
                  *, hop_length: int, sample_rate: Optional[int] = None, bits: Optional[int] = None, mu_law: Optional[bool] = None,
-                 n_clipped: int = 0, trim_top_db: Optional[float] = None, peak_norm: Optional[float] = None):
+                 n_clipped: int = 0, trim_top_db: Optional[float] = None, peak_norm: Optional[float] = None, features: str = 'vocoder'):
         self.labels, self.mels = labels, mels
+        self.features = features   # the feature profile of the mels (frontend.FEATURE_PROFILES)
         self.trim_top_db, self.peak_norm = trim_top_db, peak_norm   # how from_wavs conditioned the clips (None: it did not)
         self.label_off, self.label_len = np.asarray(label_off, np.int64), np.asarray(label_len, np.int64)
         self.mel_off, self.frames = np.asarray(mel_off, np.int64), np.asarray(frames, np.int32)
@@ -105,7 +122,8 @@ class DeviceCorpus:
         ids = np.asarray(list(ids), np.int64)
         return DeviceCorpus(self.labels, self.mels, self.label_off[ids], self.label_len[ids], self.mel_off[ids], self.frames[ids], self.n_mels,
                             [self.stems[i] for i in ids], hop_length=self.hop_length, sample_rate=self.sample_rate, bits=self.bits,
-                            mu_law=self.mu_law, n_clipped=self.n_clipped, trim_top_db=self.trim_top_db, peak_norm=self.peak_norm)
+                            mu_law=self.mu_law, n_clipped=self.n_clipped, trim_top_db=self.trim_top_db, peak_norm=self.peak_norm,
+                            features=self.features)
 
     def split(self, test_samples: int) -> Tuple['DeviceCorpus', 'DeviceCorpus']:
         """(train, test) the way ``read_feature_list`` / ``get_vocoder_datasets`` (dataset.py:79-85) split: ids shuffled with seed
@@ -139,7 +157,7 @@ class DeviceCorpus:
 
     @classmethod
     def from_wavs(cls, paths_or_arrays, hp, device=None, batch_clips: int = 16, resample: bool = False, trim_top_db=None,
-                  peak_norm=None) -> 'DeviceCorpus':
+                  peak_norm=None, features: str = 'vocoder') -> 'DeviceCorpus':
         """Wav files (``frontend.load_wav``) or float arrays in [-1, 1] -> corpus.  The clips go to the device in ragged groups of
         ``batch_clips`` (grouped by length, so that little of a group's buffer is padding); each group's buffer is read by one launch of
         the mel front end and one of ``wrnn_quantise``.  Bits and companding follow ``hp`` (``signal_bits``); utterances too short for
@@ -158,12 +176,19 @@ class DeviceCorpus:
         then ``wav / abs(wav).max() * 0.999`` (``peak_norm=True``; a number is the target), the reference's
         ``tacotron/datasets/preprocessor.py:62-72``.  One host wait per group is added, for the trimmed lengths that size the corpus
         tables; lengths, frame counts and the short-utterance filter use the trimmed length.  The corpus keeps the two settings as
-        ``trim_top_db`` and ``peak_norm`` (the target, or ``None``)."""
+        ``trim_top_db`` and ``peak_norm`` (the target, or ``None``).
+
+        ``features``: the feature profile of the mels (``frontend.FEATURE_PROFILES``), kept as ``self.features``.  Under ``'tacotron'``
+        the mel is Tacotron's (of the pre-emphasised clip; the pre-emphasis happens inside the mel kernel) and the audio target is what
+        ``tacotron/datasets/preprocessor.py:100-112`` stores: the conditioned, NOT pre-emphasised clip zero-padded on the right to
+        ``frames * hop`` samples, so an utterance has ``frames * hop`` labels whose tail is the label of 0.0.  With ``trim_top_db=25,
+        peak_norm=True`` that is the reference's whole recipe."""
         from .frontend import MelFrontEnd, Resampler, WavConditioner, condition_settings, load_wav, read_wav
         trim_top_db, peak_target = condition_settings(trim_top_db, peak_norm)
         cond = WavConditioner(trim_top_db, peak_target) if trim_top_db is not None or peak_target is not None else None
         dev = _device(device)
-        fe = MelFrontEnd(hp, device=dev)
+        fe = MelFrontEnd(hp, device=dev, features=features)
+        padded = features == 'tacotron'                           # labels cover frames * hop samples, the tail being zeros
         hop, n_mels = fe.hop_length, fe.n_mels
         bits, mu_law = signal_bits(hp)
         least = min_frames(hop_length=hop, pad=int(hp.voc_pad), seq_len=int(hp.voc_seq_len))
@@ -204,7 +229,8 @@ class DeviceCorpus:
         lens = np.array(out_lens, np.int64)                       # at the model's rate
         src_lens = np.array([c.shape[0] for c in clips], np.int64)
         frames = np.array([fe.frames(int(n)) for n in lens], np.int64)
-        label_off = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+        label_len = frames * hop if padded else lens
+        label_off = np.concatenate([[0], np.cumsum(label_len)[:-1]]).astype(np.int64)
         mel_off = np.concatenate([[0], np.cumsum(frames)[:-1]]).astype(np.int64) * n_mels
         by_len = np.argsort(lens, kind='stable')
         rates = np.array(rates, np.int64)
@@ -214,43 +240,47 @@ class DeviceCorpus:
             ids = by_len[rates[by_len] == rate]
             groups += [(rate, ids[g:g + step]) for g in range(0, len(ids), step)]
         if cond is not None:
-            return cls._from_wavs_conditioned(clips, stems, groups, src_lens, lens, resamplers, fe, cond, dev, bits, mu_law, least)
+            return cls._from_wavs_conditioned(clips, stems, groups, src_lens, lens, resamplers, fe, cond, dev, bits, mu_law, least, padded)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            labels = torch.empty(int(lens.sum()), dtype=torch.int32, device=dev)
+            labels = torch.empty(int(label_len.sum()), dtype=torch.int32, device=dev)
             mels = torch.empty(int(frames.sum()) * n_mels, dtype=torch.float32, device=dev)
             clipped = torch.zeros(1, dtype=torch.int64, device=dev)
             for rate, ids in groups:
-                host = np.zeros((len(ids), int(src_lens[ids].max())), np.float32)
+                host = np.zeros((len(ids), int(src_lens[ids].max()) + (hop if padded and rate == fe.sample_rate else 0)), np.float32)
                 for r, u in enumerate(ids):
                     host[r, :src_lens[u]] = clips[u]
                 wav = torch.from_numpy(host).to(dev)
                 if rate != fe.sample_rate:
                     wav = resamplers[rate].resample_padded(wav, src_lens[ids])      # (B, max lens[ids]), zero past each clip
+                if padded:
+                    wav = _widened(wav, int(label_len[ids].max()))
                 n_max = int(wav.shape[1])
                 mel = fe.melspectrogram_padded(wav, lens[ids])                      # (B, n_mels, T_max)
                 lab = torch.empty((len(ids), n_max), dtype=torch.int32, device=dev)
                 _cabi.quantise(wav.data_ptr(), wav.numel(), bits, mu_law, lab.data_ptr(), clipped.data_ptr(), stream)   # the padding is 0: never clipped
                 for r, u in enumerate(ids):
-                    n, t = int(lens[u]), int(frames[u])
+                    n, t = int(label_len[u]), int(frames[u])
                     labels[int(label_off[u]):int(label_off[u]) + n] = lab[r, :n]
                     mels[int(mel_off[u]):int(mel_off[u]) + t * n_mels].view(t, n_mels).copy_(mel[r, :, :t].t())
             n_clipped = int(clipped.item())
-        return cls(labels, mels, label_off, lens, mel_off, frames, n_mels, stems, hop_length=hop, sample_rate=fe.sample_rate, bits=bits,
-                   mu_law=mu_law, n_clipped=n_clipped)
+        return cls(labels, mels, label_off, label_len, mel_off, frames, n_mels, stems, hop_length=hop, sample_rate=fe.sample_rate, bits=bits,
+                   mu_law=mu_law, n_clipped=n_clipped, features=features)
 
     @classmethod
-    def _from_wavs_conditioned(cls, clips, stems, groups, src_lens, lens, resamplers, fe, cond, dev, bits, mu_law, least) -> 'DeviceCorpus':
+    def _from_wavs_conditioned(cls, clips, stems, groups, src_lens, lens, resamplers, fe, cond, dev, bits, mu_law, least,
+                               padded=False) -> 'DeviceCorpus':
         """``from_wavs`` behind its first pass when trimming or peak normalisation is on.  Per group: upload -> resample (a group at
         another rate) -> condition -> mel and quantise, all reading device buffers; the trimmed lengths are read once per group, they decide
-        which clips stay and size the tables.  The utterances keep the order they were given in."""
+        which clips stay and size the tables.  The utterances keep the order they were given in.  ``padded``: an utterance's labels
+        cover ``frames * hop`` samples of its zero-padded row, not the clip alone."""
         hop, n_mels = fe.hop_length, fe.n_mels
         kept = {}                                                 # utterance -> (labels, mel frames-major, samples, frames), its own tensors
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             clipped = torch.zeros(1, dtype=torch.int64, device=dev)
             for rate, ids in groups:
-                host = np.zeros((len(ids), int(src_lens[ids].max())), np.float32)
+                host = np.zeros((len(ids), int(src_lens[ids].max()) + (hop if padded and rate == fe.sample_rate else 0)), np.float32)
                 for r, u in enumerate(ids):
                     host[r, :src_lens[u]] = clips[u]
                 wav = torch.from_numpy(host).to(dev)
@@ -264,11 +294,14 @@ class DeviceCorpus:
                 if len(rows) < len(ids):
                     wav = wav[torch.tensor(rows, device=dev)].contiguous()
                 ids, new = ids[rows], new[rows]
+                if padded:
+                    wav = _widened(wav, (1 + int(new.max()) // hop) * hop)
                 mel = fe.melspectrogram_padded(wav, new)
                 lab = torch.empty(tuple(wav.shape), dtype=torch.int32, device=dev)
                 _cabi.quantise(wav.data_ptr(), wav.numel(), bits, mu_law, lab.data_ptr(), clipped.data_ptr(), stream)
                 for r, u in enumerate(ids):
-                    n, t = int(new[r]), int(fe.last_frames[r])
+                    t = int(fe.last_frames[r])
+                    n = t * hop if padded else int(new[r])
                     kept[int(u)] = (lab[r, :n].clone(), mel[r, :, :t].t().contiguous().view(-1), n, t)
             if not kept:
                 raise ValueError(f'no utterance has the {least} mel frames one training window needs after trimming')
@@ -286,13 +319,14 @@ class DeviceCorpus:
             n_clipped = int(clipped.item())
         return cls(labels, mels, label_off, new_lens, mel_off, frames, n_mels, [stems[u] for u in order], hop_length=hop,
                    sample_rate=fe.sample_rate, bits=bits, mu_law=mu_law, n_clipped=n_clipped, trim_top_db=cond.trim_top_db,
-                   peak_norm=cond.peak_target)
+                   peak_norm=cond.peak_target, features=fe.features)
 
     # ------------------------------------------------------------------ files
     def save(self, out_dir: Union[str, Path]) -> Path:
         """``quant/<stem>.npy`` (int32 labels), ``mel/<stem>.npy`` (``(frames, n_mels)`` float32, the reference's file layout) and
         ``wavernn_training_data.txt`` with one ``quant|mel|mel|stem`` line per utterance: fields 0 and 2 are what
-        ``train.read_feature_list`` and the reference's ``get_vocoder_datasets`` read.  Returns the list file's path."""
+        ``train.read_feature_list`` and the reference's ``get_vocoder_datasets`` read.  The feature profile of the mels goes into
+        ``wavernn_training_features.txt`` next to it (``saved_features`` reads it back).  Returns the list file's path."""
         out = Path(out_dir).expanduser().resolve()
         (out / 'quant').mkdir(parents=True, exist_ok=True)
         (out / 'mel').mkdir(parents=True, exist_ok=True)
@@ -306,13 +340,16 @@ class DeviceCorpus:
             lines.append(f'{q}|{m}|{m}|{stem}\n')
         listing = out / LIST_NAME
         listing.write_text(''.join(lines), encoding='utf-8')
+        (out / FEATURES_NAME).write_text(self.features + '\n', encoding='utf-8')
         return listing
 
     @classmethod
     def load(cls, list_file_or_pairs, device=None, *, hop_length: int, **meta) -> 'DeviceCorpus':
         """A saved corpus back on the device without recomputing anything: ``list_file_or_pairs`` is the list file ``save`` wrote
-        (every line is taken, in order) or ``(quantised wav path, mel path)`` pairs such as ``train.read_feature_list`` returns."""
+        (every line is taken, in order) or ``(quantised wav path, mel path)`` pairs such as ``train.read_feature_list`` returns.  A list
+        file brings the features ``save`` recorded next to it; for pairs say ``features=`` (default ``'vocoder'``)."""
         if isinstance(list_file_or_pairs, (str, Path)):
+            meta.setdefault('features', saved_features(list_file_or_pairs))
             items = []
             with open(list_file_or_pairs, 'r', encoding='utf-8') as f:
                 for line in f:
@@ -325,6 +362,11 @@ class DeviceCorpus:
             raise ValueError('the list names no utterance')
         pairs = [(np.load(m).T, np.load(q)) for q, m, _ in items]
         return cls.from_pairs(pairs, device, hop_length=hop_length, stems=[s for _, _, s in items], **meta)
+
+
+def _widened(wav: torch.Tensor, width: int) -> torch.Tensor:
+    """``wav`` (B, n) as it is when ``n >= width``, else a copy zero-padded on the right to ``width`` columns."""
+    return wav if wav.shape[1] >= width else torch.nn.functional.pad(wav, (0, width - wav.shape[1]))
 
 
 class DeviceWindowLoader:
@@ -371,11 +413,9 @@ class DeviceWindowLoader:
             yield x, y, mels
 
 
-def main(argv=None):
-    """``python wavernn_preprocess.py --wav_dir DIR --out_dir DIR``: every ``*.wav`` of the folder -> ``quant/``, ``mel/`` and the
-    training list ``wavernn_train.py`` reads (``hp.feature_path``)."""
+def build_parser():
     import argparse
-    from .hparams import DEFAULT_HPARAMS, hparams as hp
+    from .hparams import DEFAULT_HPARAMS
     parser = argparse.ArgumentParser(description='Preprocess a folder of wavs for WaveRNN vocoder training')
     parser.add_argument('--wav_dir', required=True, metavar='DIR', help='folder of wav files at hp.sample_rate (any rate with --resample)')
     parser.add_argument('--out_dir', required=True, metavar='DIR', help='where quant/, mel/ and the list file go')
@@ -383,9 +423,18 @@ def main(argv=None):
     parser.add_argument('--batch_clips', type=int, default=16, help='clips per launch of the front end')
     parser.add_argument('--resample', action='store_true', help='resample files at another rate to hp.sample_rate on the device '
                                                                 '(default: such a file is an error)')
-    from .frontend import add_condition_arguments, condition_arguments
+    from .frontend import add_condition_arguments, add_features_argument
     add_condition_arguments(parser, 'the files')
-    args = parser.parse_args(argv)
+    add_features_argument(parser, 'the files')
+    return parser
+
+
+def main(argv=None):
+    """``python wavernn_preprocess.py --wav_dir DIR --out_dir DIR``: every ``*.wav`` of the folder -> ``quant/``, ``mel/`` and the
+    training list ``wavernn_train.py`` reads (``hp.feature_path``)."""
+    from .frontend import condition_arguments
+    from .hparams import hparams as hp
+    args = build_parser().parse_args(argv)
     conditioning = condition_arguments(args)
     hp.configure(args.hp_file)
     if not torch.cuda.is_available():
@@ -393,10 +442,11 @@ def main(argv=None):
     wavs = sorted(Path(args.wav_dir).expanduser().glob('*.wav'))
     if not wavs:
         raise FileNotFoundError(f'no *.wav files in {args.wav_dir}')
-    corpus = DeviceCorpus.from_wavs(wavs, hp, 'cuda', batch_clips=args.batch_clips, resample=args.resample, **conditioning)
+    corpus = DeviceCorpus.from_wavs(wavs, hp, 'cuda', batch_clips=args.batch_clips, resample=args.resample, features=args.features,
+                                    **conditioning)
     listing = corpus.save(args.out_dir)
     print(f'{len(corpus)} utterances of {len(wavs)} files | {corpus.hours:.3f} hours | {corpus.n_clipped} clipped samples | '
-          f'{corpus.bits} bits {"mu-law" if corpus.mu_law else "linear"} | {listing}')
+          f'{corpus.bits} bits {"mu-law" if corpus.mu_law else "linear"} | {corpus.features} features | {listing}')
 
 
 if __name__ == "__main__":

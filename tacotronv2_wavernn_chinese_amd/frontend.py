@@ -4,7 +4,8 @@
 librosa semantics of the reference's era) as one launch of the kernel in ``csrc/melspec.hip``; ``load_wav`` is ``dsp.py:18-19``, and with
 ``resample=True`` a file at another rate goes through ``Resampler`` (``csrc/resample.hip``), a Kaiser-windowed sinc on the device.
 ``WavConditioner`` (``csrc/condition.hip``) is the silence trimming and peak rescaling of ``tacotron/datasets/preprocessor.py:62-72``,
-opt-in everywhere.  Pre-emphasis, ``spectrogram``, Griffin-Lim and the Tacotron-side mel of ``tacotron/datasets/audio.py`` are not here.
+opt-in everywhere.  ``MelFrontEnd(features='tacotron')`` is the Tacotron-side mel of ``tacotron/datasets/audio.py`` (pre-emphasis fused
+into the kernel's tap gather), the features the reference's vocoder is trained on.  ``spectrogram`` and Griffin-Lim are not here.
 """
 from __future__ import annotations
 
@@ -17,14 +18,54 @@ from . import _cabi
 MEL_DEFAULTS = dict(sample_rate=22050, n_fft=2048, hop_length=275, win_length=1100, num_mels=80, fmin=95, min_level_db=-100)
 
 
+# The feature profiles (``wrnn_mel_features``).  'vocoder': ``melspectrogram`` of ``wavernn/utils/dsp.py``, what this package has always
+# made.  'tacotron': the mel the reference's WaveRNN is trained on and Tacotron hands it, ``tacotron/datasets/audio.py:95-102, 203-207,
+# 250-295`` with ``tacotron_hparams.py``'s values, mapped to [0, 1] like ``wavernn_preprocess.py:149-159``.
+FEATURE_PROFILES = {
+    'vocoder': dict(pad_mode='reflect', magnitude_power=1, fmax=0.0, ref_level_db=0.0, preemphasis=0.0, preemph_rescale=0.0, max_abs_value=0.0),
+    'tacotron': dict(pad_mode='zero', magnitude_power=2, fmax=7600.0, ref_level_db=20.0, preemphasis=0.97, preemph_rescale=0.999,
+                     max_abs_value=4.0),
+}
+FEATURES_HELP = ("extension: the mel features of {what}: 'vocoder' (default) = melspectrogram of wavernn/utils/dsp.py; 'tacotron' = the mel "
+                 "Tacotron's preprocessing makes and the reference's WaveRNN is trained on (pre-emphasis, zero padding, power spectrum, "
+                 "fmax 7600, ref_level_db 20, [-4, 4] mapped to [0, 1]).  The reference's whole recipe: --features tacotron --trim_silence "
+                 "--peak_norm")
+
+
+def feature_settings(features='vocoder', **overrides) -> dict:
+    """The profile ``features`` with ``overrides`` applied, checked: ``ValueError`` for an unknown profile name or ``pad_mode``,
+    ``TypeError`` for an unknown field."""
+    if features not in FEATURE_PROFILES:
+        raise ValueError(f'features must be one of {sorted(FEATURE_PROFILES)}, got {features!r}')
+    unknown = set(overrides) - set(FEATURE_PROFILES['vocoder'])
+    if unknown:
+        raise TypeError(f'unknown feature fields {sorted(unknown)}')
+    out = dict(FEATURE_PROFILES[features], **overrides)
+    if out['pad_mode'] not in _cabi.MEL_PAD_MODES:
+        raise ValueError(f"pad_mode must be one of {sorted(_cabi.MEL_PAD_MODES)}, got {out['pad_mode']!r}")
+    return out
+
+
+def add_features_argument(parser, what='the wavs'):
+    """``--features {vocoder,tacotron}`` for a command-line parser."""
+    parser.add_argument('--features', choices=sorted(FEATURE_PROFILES), default='vocoder', help=FEATURES_HELP.format(what=what))
+
+
 class MelFrontEnd:
     """``MelFrontEnd(hp)`` reads ``sample_rate, n_fft, hop_length, win_length, num_mels, fmin, min_level_db`` from an hparams-like object
     (a name it lacks takes the reference's default); keywords override (``n_mels`` is accepted for ``num_mels``).  ``ValueError`` for a
-    configuration the library has no kernel for (``n_fft`` other than 2048) or refuses."""
+    configuration the library has no kernel for (``n_fft`` other than 2048) or refuses.
 
-    def __init__(self, hp=None, device=None, **kw):
+    ``features``: the feature profile, ``'vocoder'`` (default: what the class has always made) or ``'tacotron'`` (``FEATURE_PROFILES``);
+    the keywords ``fmax, ref_level_db, preemphasis, preemph_rescale, magnitude_power, pad_mode, max_abs_value`` move single fields of it
+    (``pad_mode``: ``'reflect'`` or ``'zero'``).  The profile's fields are not read from ``hp``.  ``self.features`` keeps the name,
+    ``self.feature_config`` the fields."""
+
+    def __init__(self, hp=None, device=None, features='vocoder', **kw):
         if 'n_mels' in kw:
             kw['num_mels'] = kw.pop('n_mels')
+        self.feature_config = feature_settings(features, **{k: kw.pop(k) for k in list(kw) if k in FEATURE_PROFILES['vocoder']})
+        self.features = features
         unknown = set(kw) - set(MEL_DEFAULTS)
         if unknown:
             raise TypeError(f'unknown front-end parameters {sorted(unknown)}')
@@ -38,13 +79,16 @@ class MelFrontEnd:
 
     def _native(self, index: int) -> _cabi.NativeMel:
         if index not in self._nat:
-            c = self.config
+            c, f = self.config, self.feature_config
+            # the default profile goes through wrnn_mel_create itself, as before the profiles
+            feat = None if f == FEATURE_PROFILES['vocoder'] else _cabi.MelFeatures(**dict(f, pad_mode=_cabi.MEL_PAD_MODES[f['pad_mode']]))
             self._nat[index] = _cabi.NativeMel(sample_rate=c['sample_rate'], n_fft=c['n_fft'], hop_length=c['hop_length'], win_length=c['win_length'],
-                                               n_mels=c['num_mels'], fmin=c['fmin'], min_level_db=c['min_level_db'], device=index)
+                                               n_mels=c['num_mels'], fmin=c['fmin'], min_level_db=c['min_level_db'], device=index, features=feat)
         return self._nat[index]
 
     def frames(self, n_samples: int) -> int:
-        """``1 + n // hop``; ``ValueError`` for a clip shorter than ``n_fft // 2 + 1`` samples (it cannot be reflect-padded)."""
+        """``1 + n // hop``; ``ValueError`` for a clip shorter than ``n_fft // 2 + 1`` samples (it cannot be reflect-padded); under
+        ``pad_mode='zero'`` for an empty clip only."""
         return next(iter(self._nat.values())).frames(n_samples)
 
     def tables(self) -> dict:
@@ -375,12 +419,15 @@ def read_wav(path):
     return _decode(path, data), int(sr)
 
 
-def load_wav(path, sample_rate, resample=False, device=None, trim_top_db=None, peak_norm=None):
+def load_wav(path, sample_rate, resample=False, device=None, trim_top_db=None, peak_norm=None, features='vocoder'):
     """``librosa.load(path, sr=sample_rate)[0]`` (``dsp.py:18-19``): float32 mono (``read_wav``).  A file at another rate raises
     ``ValueError`` unless ``resample=True``: then it is resampled on the device (``Resampler``) and comes back as a host array of
     ``ceil(n sample_rate / rate)`` samples.  ``trim_top_db`` / ``peak_norm`` (both off by default): the clip is then conditioned on the
-    device after the resampler (``WavConditioner``) and the trimmed, rescaled clip comes back."""
+    device after the resampler (``WavConditioner``) and the trimmed, rescaled clip comes back.  ``features`` is checked and changes
+    nothing here: under every profile the clip that comes back is the vocoder's target, never pre-emphasised (the ``'tacotron'``
+    profile pre-emphasises inside the mel kernel)."""
     from scipy.io import wavfile
+    feature_settings(features)
     trim_top_db, target = condition_settings(trim_top_db, peak_norm)
     sr, data = wavfile.read(str(path))
     if int(sr) != int(sample_rate) and not resample:

@@ -17,7 +17,9 @@ at another sample rate raises ``ValueError`` unless ``resample=True`` / ``--resa
 (``frontend.Resampler``, ``csrc/resample.hip``) and the saved target file is the resampled clip at the model's rate, as the reference's is.
 ``trim_top_db=`` / ``peak_norm=`` (``--trim_silence [--trim_top_db DB]``, ``--peak_norm [TARGET]``; off by default): the clip is conditioned
 on the device like the training wavs of a corpus made with the same settings (``frontend.WavConditioner``, ``csrc/condition.hip``), and the
-saved target file is the conditioned clip.
+saved target file is the conditioned clip.  ``features=`` (``--features {vocoder,tacotron}``): the feature profile of the mel;
+``'tacotron'`` is the mel Tacotron's preprocessing makes, for a checkpoint trained the reference's way (``frontend.FEATURE_PROFILES``).
+The saved target file is the same under both: the pre-emphasis happens inside the mel kernel.
 """
 from __future__ import annotations
 
@@ -29,13 +31,13 @@ import numpy as np
 import torch
 
 from .dsp import save_wav
-from .frontend import add_condition_arguments, condition_arguments, load_wav
+from .frontend import add_condition_arguments, add_features_argument, condition_arguments, load_wav
 from .hparams import hparams as hp
 from .vocoder import WaveRNN
 
 
 def gen_from_file(model: WaveRNN, load_path, save_path, batched, target, overlap, stream_frames=None, resample=False, trim_top_db=None,
-                  peak_norm=None, **generate_opts):
+                  peak_norm=None, features='vocoder', **generate_opts):
     k = model.get_step() // 1000
     load_path = str(load_path)
     if ".npy" in load_path:
@@ -51,10 +53,11 @@ def gen_from_file(model: WaveRNN, load_path, save_path, batched, target, overlap
             raise ValueError(f'{load_path}: no such wav file')
         on_device = resample or trim_top_db is not None or (peak_norm is not None and peak_norm is not False)
         wav = load_wav(load_path, hp.sample_rate, resample=resample, device=torch.device('cuda', model._device_index()) if on_device else None,
-                       trim_top_db=trim_top_db, peak_norm=peak_norm)
+                       trim_top_db=trim_top_db, peak_norm=peak_norm, features=features)
         idx = load_path.split('/')[-1].strip().split('.')[0]
         save_wav(wav, os.path.join(str(save_path), f'__{idx}__{k}k_steps_target.wav'), hp.sample_rate)
-        mel = model.mel_front_end().melspectrogram(wav, device=torch.device('cuda', model._device_index()))   # (1, n_mels, T) on the device
+        fe = model.mel_front_end() if features == 'vocoder' else model.mel_front_end(features=features)   # a model-like object need not know profiles
+        mel = fe.melspectrogram(wav, device=torch.device('cuda', model._device_index()))   # (1, n_mels, T) on the device
     else:
         raise ValueError(f"Expected an extension of .wav or .npy, but got {os.path.splitext(load_path)[1]}!")
 
@@ -129,6 +132,7 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--resample', action='store_true',
                         help='extension: resample a --file .wav at another rate to the model sample rate on the device (default: an error)')
     add_condition_arguments(parser, 'a --file .wav')
+    add_features_argument(parser, 'a --file .wav')
     parser.add_argument('--voc_weights', '-w', type=str, help='[string/path] Load in different WaveRNN weights')
     parser.add_argument('--gta', '-g', dest='gta', action='store_true', help='Generate from GTA testset')
     parser.add_argument('--force_cpu', '-c', action='store_true',
@@ -195,7 +199,7 @@ def main(argv=None):
         if args.stream_frames is not None and args.noise != 'philox':
             raise ValueError('--stream-frames draws its noise on the device: --noise reference needs the whole clip')
         gen_from_file(model, args.file, out_dir, args.batched, args.target, args.overlap, stream_frames=args.stream_frames,
-                      noise_mode=args.noise, resample=args.resample, **conditioning)
+                      noise_mode=args.noise, resample=args.resample, features=args.features, **conditioning)
     print('\n\nExiting...\n')
 
 

@@ -255,12 +255,9 @@ def synthetic_pairs(n: int, frames: int, *, bits: int, n_mels: int, hop_length: 
     return out
 
 
-def main(argv=None):
-    """``python wavernn_train.py`` (wavernn_train.py:20-86) on the MI355X."""
+def build_parser():
     import argparse
-    import torch.nn.functional as F
-    from .gen import build_model_from_hparams
-    from .hparams import DEFAULT_HPARAMS, hparams as hp
+    from .hparams import DEFAULT_HPARAMS
     parser = argparse.ArgumentParser(description='Train WaveRNN Vocoder')
     parser.add_argument('--gta', '-g', action='store_true', help='accepted for compatibility: the list file names the mels to train on')
     parser.add_argument('--hp_file', metavar='FILE', default=DEFAULT_HPARAMS, help='The file to use for the hyperparameters')
@@ -269,16 +266,29 @@ def main(argv=None):
                                                          'there (dataset.DeviceCorpus), every batch is cut by one kernel launch')
     parser.add_argument('--resample', action='store_true', help='with --wav_dir: resample files at another rate to hp.sample_rate on the '
                                                                 'device (default: such a file is an error)')
-    from .frontend import add_condition_arguments, condition_arguments
+    from .frontend import add_condition_arguments, add_features_argument
     add_condition_arguments(parser, 'the --wav_dir files')
+    add_features_argument(parser, 'the --wav_dir files; a saved corpus (hp.feature_path) must hold the same ones')
     parser.add_argument('--resident', action='store_true', help='load the corpus of hp.feature_path onto the device once instead of reading '
                                                                 '.npy files every iteration')
     parser.add_argument('--total_steps', type=int, help='override hp.voc_total_steps')
     parser.add_argument('--reference_body', action='store_true',
                         help="run the reference's loop body (model(x, m) + torch loss) instead of the fused training_loss")
-    args = parser.parse_args(argv)
+    return parser
+
+
+def main(argv=None):
+    """``python wavernn_train.py`` (wavernn_train.py:20-86) on the MI355X."""
+    import torch.nn.functional as F
+    from .frontend import condition_arguments
+    from .gen import build_model_from_hparams
+    from .hparams import hparams as hp
+    args = build_parser().parse_args(argv)
     conditioning = condition_arguments(args)
     hp.configure(args.hp_file)
+    if not args.synthetic and not args.wav_dir:
+        from .dataset import check_saved_features
+        check_saved_features(hp.feature_path, args.features)   # ValueError: the saved mels are of another kind than the ones asked for
     if not torch.cuda.is_available():
         raise RuntimeError('this vocoder trains on an MI355X only (no CPU path)')
     if int(np.prod(hp.voc_upsample_factors)) != hp.hop_length:
@@ -296,7 +306,7 @@ def main(argv=None):
         wavs = sorted(Path(args.wav_dir).expanduser().glob('*.wav'))
         if not wavs:
             raise FileNotFoundError(f'no *.wav files in {args.wav_dir}')
-        corpus = DeviceCorpus.from_wavs(wavs, hp, 'cuda', resample=args.resample, **conditioning)
+        corpus = DeviceCorpus.from_wavs(wavs, hp, 'cuda', resample=args.resample, features=args.features, **conditioning)
         print(f'{len(corpus)} utterances of {len(wavs)} files | {corpus.hours:.3f} hours | {corpus.n_clipped} clipped samples')
         train, held_out = corpus.split(hp.voc_test_samples)
         test = held_out.pairs()
@@ -305,7 +315,7 @@ def main(argv=None):
                                         test_samples=hp.voc_test_samples)
         if args.resident:
             from .dataset import DeviceCorpus
-            train = DeviceCorpus.load(train, 'cuda', hop_length=hp.hop_length)
+            train = DeviceCorpus.load(train, 'cuda', hop_length=hp.hop_length, features=args.features)
     if isinstance(train, list):
         loader = WindowLoader(train, hp.voc_batch_size, **kw)
     else:

@@ -717,17 +717,19 @@ class WaveRNN(nn.Module):
         self.train()
         return output
 
-    def mel_front_end(self, front_end=None):
+    def mel_front_end(self, front_end=None, features='vocoder'):
         """The wav -> mel front end of this model (``frontend.MelFrontEnd``): the model's own ``sample_rate``, ``hop_length`` and
         ``feat_dims``, the remaining parameters (``n_fft``, ``win_length``, ``fmin``, ``min_level_db``) from the configured hparams where they
-        set them, else the reference's defaults.  ``front_end``: use this one instead (its mel must have ``feat_dims`` channels)."""
+        set them, else the reference's defaults.  ``features``: the feature profile (``frontend.FEATURE_PROFILES``; one front end per
+        profile is kept).  ``front_end``: use this one instead (its mel must have ``feat_dims`` channels; the features are then its own)."""
         from .frontend import MelFrontEnd
         if front_end is None:
-            front_end = getattr(self, '_mel_front_end', None)
-            if front_end is None:
+            cache = self.__dict__.setdefault('_mel_front_ends', {})
+            if features not in cache:
                 from .hparams import hparams as hp
-                front_end = MelFrontEnd(hp, sample_rate=self.sample_rate, hop_length=self.hop_length, n_mels=self.feat_dims)
-                self._mel_front_end = front_end
+                cache[features] = MelFrontEnd(hp, sample_rate=self.sample_rate, hop_length=self.hop_length, n_mels=self.feat_dims,
+                                              features=features)
+            front_end = cache[features]
         if front_end.n_mels != self.feat_dims or front_end.hop_length != self.hop_length:
             raise ValueError(f'the front end makes {front_end.n_mels} mel channels at hop {front_end.hop_length}, the model needs '
                              f'{self.feat_dims} at hop {self.hop_length}')
@@ -742,17 +744,18 @@ class WaveRNN(nn.Module):
         return cache[int(wav_rate)]
 
     def generate_from_wav(self, wav, save_path: Union[str, Path], batched, target, overlap, mu_law, front_end=None, wav_rate=None,
-                          trim_top_db=None, peak_norm=None, **generate_opts):
+                          trim_top_db=None, peak_norm=None, features='vocoder', **generate_opts):
         """Copy-synthesis, the ``.wav`` branch of ``wavernn_gen.py:17-20``: the mel of ``wav`` (1-D samples in [-1, 1] at the model's sample
         rate) is built on the device (``mel_front_end``) and handed to ``generate`` as a device tensor, without a host round trip.  Returns
         what ``generate`` returns for that mel: ``(T - 1) * hop`` samples, ``T = 1 + len(wav) // hop``.  ``wav_rate``: the clip's own sample
         rate; one that differs from the model's is resampled on the device first (``frontend.Resampler``), and ``len(wav)`` above is then
         the resampled length ``ceil(len * sample_rate / wav_rate)``.  ``trim_top_db`` / ``peak_norm`` (off by default): the clip is
         conditioned on the device after the resampler, as ``DeviceCorpus.from_wavs`` conditions training wavs with the same settings
-        (``frontend.WavConditioner``: silence trimmed, then rescaled to the peak), and ``len(wav)`` is the trimmed length."""
+        (``frontend.WavConditioner``: silence trimmed, then rescaled to the peak), and ``len(wav)`` is the trimmed length.  ``features``:
+        the feature profile of the mel (``mel_front_end``); ``'tacotron'`` for a model trained on Tacotron's mels."""
         from .frontend import condition_settings
         trim_top_db, peak_norm = condition_settings(trim_top_db, peak_norm)
-        fe = self.mel_front_end(front_end)
+        fe = self.mel_front_end(front_end, features)
         dev = torch.device('cuda', self._device_index())
         if wav_rate is not None and int(wav_rate) != self.sample_rate:
             wav = self.resampler(wav_rate).resample(wav, device=dev)   # (1, n) on the device
@@ -788,7 +791,7 @@ class WaveRNN(nn.Module):
         return [row[:n] for row, n in zip(rows, cond.last_lens)]
 
     def generate_many(self, mels_list=None, save_paths=None, mu_law=True, epilogue='host', batched=False, target='auto', overlap=550, seeds=None,
-                      wavs=None, front_end=None, wav_rates=None, trim_top_db=None, peak_norm=None, **native_opts):
+                      wavs=None, front_end=None, wav_rates=None, trim_top_db=None, peak_norm=None, features='vocoder', **native_opts):
         """Extension for serving loops: several independent utterances of different lengths in ONE device call, so that all
         8 XCD teams of the GPU work (a single unbatched utterance keeps one team = 1/8 of the chip busy; up to 8 utterances
         run on the latency kernel one per team, more on the batch kernel).  ``mels_list``: sequence of (n_mels, T_i) arrays.
@@ -822,13 +825,15 @@ class WaveRNN(nn.Module):
         mels given as ``mels_list``.  ``wav_rates``: the clips' own sample rates, one int for all or one per clip; clips at another rate
         than the model's are resampled on the device first (``frontend.Resampler``, one launch per source rate).  ``trim_top_db`` /
         ``peak_norm`` (with ``wavs=`` only; off by default): all clips are then conditioned by one ``frontend.WavConditioner`` call, and
-        the frame counts follow the trimmed lengths."""
+        the frame counts follow the trimmed lengths.  ``features`` (with ``wavs=`` only): the feature profile of the mels."""
         from .frontend import condition_settings
         trim_top_db, peak_norm = condition_settings(trim_top_db, peak_norm)
         if (mels_list is None) == (wavs is None):
             raise ValueError('give either mels_list or wavs')
         if wavs is None and (trim_top_db is not None or peak_norm is not None):
             raise ValueError('trim_top_db and peak_norm condition wavs: give wavs=, not mels_list')
+        if wavs is None and features != 'vocoder':
+            raise ValueError('features names the mels made from wavs: give wavs=, not mels_list')
         n_req = len(mels_list) if wavs is None else len(wavs)
         if seeds is not None:
             native_opts['seeds'] = request_seeds(seeds, n_req, native_opts.get('noise_mode', _cabi.NOISE_PHILOX), native_opts.get('seed'))
@@ -839,7 +844,7 @@ class WaveRNN(nn.Module):
         self.eval()
         mu_law = mu_law if self.mode == 'RAW' else False
         if wavs is not None:
-            fe = self.mel_front_end(front_end)
+            fe = self.mel_front_end(front_end, features)
             if not len(wavs):
                 raise ValueError('expected a non-empty sequence of clips')
             if wav_rates is not None:
