@@ -24,6 +24,9 @@
 //
 // Thread map inside a role (wl = wave & 3, lane l: quarter r4 = l>>4, q = l&15): quarter-wave (wl, r4) owns hidden
 // unit / fc row u = 16 g + 4 wl + r4 and columns 32q..32q+31 of every row it owns.
+//
+// Developer knobs (all -D, see where each is defined): T2_HOIST_LDS (shipped 1), T2_STRAIGHT_POLL (shipped 7), T2_PRESLEEP, T2_DEFER_OUT, T2_RACE_SLEEP
+// work as before or are new; T2_LATE_B and T2_STAGGER (the two-look polls of rounds 1-3, measured slower in round 4) were removed with their dead paths.
 #include "team_common.h"
 
 #define T2_THREADS 512
@@ -53,17 +56,16 @@ __device__ __forceinline__ void finish_n(const u64 *base, unsigned idx, unsigned
     }
 }
 
-// One exchange, one granule per thread.  Shipped (round 4): ONE look right behind the publish, then the bounded re-read loop.
-// Rounds 1-3 issued two staggered looks (A at once, B `T2_STAGGER` sleeps later) and meant to examine B only if A came back
-// incomplete -- but written as `return all_ok(A) ? A : finish(B)` the compiler merged the two results with a v_cndmask behind
-// `s_waitcnt vmcnt(0)`, so every exchange waited for look B as well; and because B could still be in flight on the way out, every
-// later reuse of its registers (among them the first instruction of the step loop) got a conservative vmcnt(0).  Measured in one
-// session (profiles/r04_team2_experiments.txt, ksamples/s at B = 1): round-3 code 300.5; two looks with B really examined late
-// (T2_LATE_B 1: every path's result pinned to its own load, B retired behind the exchange's barrier) 296 - 297 with T2_STAGGER 3,
-// 293 with 2, 303 with 5; one look (T2_LATE_B 2) 303; one look behind an s_sleep (T2_PRESLEEP 1 / 2 / 4) 304 / 303 / 295.  The
-// staggered second look buys nothing: a look that arrives before the data costs one more round trip whichever way it is issued.
-#ifndef T2_STAGGER
-#define T2_STAGGER 3
+// ---- A/B knobs of the two chain changes measured in profiles/team2_chain_lds.txt (tools/build_variant.sh NAME loop_team2 -DT2_...=N) ----
+#ifndef T2_HOIST_LDS
+#define T2_HOIST_LDS 1      // shipped ON (+3.3 .. +4.1 % in five sessions): the per-quarter constants and hand-over slots are read ahead of the dot product they follow
+#endif
+#ifndef T2_STRAIGHT_POLL
+// shipped 7.  Bits: the poll has ONE load site, so a look with every tag current leaves by the loop exit without register copies, in
+// 1 = take_granule (exchanges 1-3), 2 = wave 0's race look, 4 = the S gather.  Neutral in time (-0.1 % +- the session's 0.5 % on top of the
+// hoists); a first look rarely finds its data, what the chain sees of a poll is the re-read.  An earlier form with load + wait in one asm
+// and the retry out of line LOST 2.5 % and is not in the tree (profiles/team2_chain_lds.txt).
+#define T2_STRAIGHT_POLL 7
 #endif
 #ifndef T2_DEFER_OUT
 #define T2_DEFER_OUT 0   // developer knob, see the merge at the end of the step
@@ -71,51 +73,53 @@ __device__ __forceinline__ void finish_n(const u64 *base, unsigned idx, unsigned
 #ifndef T2_PRESLEEP
 #define T2_PRESLEEP 0   // developer knob: s_sleep units in front of the first look
 #endif
-#ifndef T2_LATE_B
-#define T2_LATE_B 2   // 2 = one look + re-read loop (shipped); 1 = two staggered looks, B examined only when A is stale; 0 = the round-3 code
+
+// T2_HOIST_LDS: every consumer of a hoisted value sits in `if (q == 0)` behind the DPP row sums, and the compiler sinks a plain read into
+// that branch, where it is a dependent LDS round trip with its own s_waitcnt between the last FMA and the publish.  `hoist_fence` between
+// the read and the dot product keeps the ds_read in front of the dot product's ds_read_b128 batch; `pin` behind the dot product makes the
+// value one the compiler cannot re-load where it is used.  All 16 lanes of a quarter read the same address (a broadcast).
+__device__ __forceinline__ void hoist_fence() {
+#if T2_HOIST_LDS
+    __builtin_amdgcn_sched_barrier(0);
 #endif
-__device__ __forceinline__ unsigned take_granule(const u64 *base, unsigned idx, unsigned tag, bool &dead, unsigned *err, unsigned code, u64 (&gb)[1]) {
+}
+__device__ __forceinline__ void pin(float &v) {
+#if T2_HOIST_LDS
+    asm volatile("" : "+v"(v));
+#endif
+}
+
+// One exchange, one granule per thread: ONE look right behind the publish, then the bounded re-read loop.  (Rounds 1-3 issued two
+// staggered looks; measured in profiles/r04_team2_experiments.txt, the second look buys nothing: a look that arrives before the data
+// costs one more round trip whichever way it is issued.  The staggered forms and their knobs T2_LATE_B / T2_STAGGER are gone.)
+#if T2_STRAIGHT_POLL & 1
+// ONE load site: the first look is the first trip of the loop.  With a look in front of the loop and a re-read inside it the granule is a phi
+// of two loads, and a wave whose tags are all current runs through the loop's copies (v_mov_b64) and four taken branches before it may
+// write LDS.  Here a current look leaves by the loop exit with the value in the register it was loaded into; the retry, the spin bound,
+// `dead` and the error word are behind that exit.  Same sequence of looks and the same bound as finish_n.
+__device__ __forceinline__ unsigned take_granule(const u64 *base, unsigned idx, unsigned tag, bool &dead, unsigned *err, unsigned code) {
+#if T2_PRESLEEP
+    __builtin_amdgcn_s_sleep(T2_PRESLEEP);
+#endif
+    u64 g;
+    for (unsigned spins = 0;;) {
+        g = __hip_atomic_load(base + idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (__all((unsigned)(g >> 32) == tag) || dead) break;
+        if (++spins > TEAM_SPIN_MAX) { dead = true; if ((threadIdx.x & 63) == 0) atomicExch(err, code); break; }
+    }
+    return (unsigned)g;
+}
+#else
+__device__ __forceinline__ unsigned take_granule(const u64 *base, unsigned idx, unsigned tag, bool &dead, unsigned *err, unsigned code) {
     u64 ga[1];
 #if T2_PRESLEEP
     __builtin_amdgcn_s_sleep(T2_PRESLEEP);
 #endif
     peek_n<1>(base, idx, 1, ga);
-#if T2_LATE_B == 2   // one look, then the re-read loop
     finish_n<1, 32>(base, idx, 1, tag, ga, dead, err, code);
     return (unsigned)ga[0];
-#else
-    __builtin_amdgcn_s_sleep(T2_STAGGER);
-    peek_n<1>(base, idx, 1, gb);
-    if (__all(tags_ok<1, 32>(ga, tag))) {
-        unsigned r = (unsigned)ga[0];
-#if T2_LATE_B
-        asm volatile("" : "+v"(r));
-#endif
-        return r;
-    }
-#if T2_LATE_B
-    // `gb` keeps its single definition (the load above): re-reads go into their own registers -- a variable that is loaded on one
-    // path and re-loaded on another becomes a phi, and the copy into the phi's register is a wait for the load on EVERY path
-    if (__all(tags_ok<1, 32>(gb, tag))) { unsigned r = (unsigned)gb[0]; asm volatile("" : "+v"(r)); return r; }
-    u64 gc[1];
-    peek_n<1>(base, idx, 1, gc);
-    finish_n<1, 32>(base, idx, 1, tag, gc, dead, err, code);
-    unsigned r = (unsigned)gc[0];
-    asm volatile("" : "+v"(r));   // every path hands over a value that is waited for on that path
-    return r;
-#else
-    finish_n<1, 32>(base, idx, 1, tag, gb, dead, err, code);
-    return (unsigned)gb[0];
-#endif
-#endif
 }
-// look B has returned by the time the gathered value is in LDS and the workgroup barrier is passed: waiting for it HERE costs nothing and
-// leaves no load pending whose registers the compiler would have to guard with a vmcnt(0) somewhere on the serial chain
-__device__ __forceinline__ void retire_look(u64 (&gb)[1]) {
-#if T2_LATE_B
-    asm volatile("" ::"v"(gb[0]));
 #endif
-}
 
 __device__ __forceinline__ float rows_max(float v) {   // max over the 4 DPP rows of a wave whose rows are uniform, valid in lane 63
     asm volatile(
@@ -383,8 +387,10 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
         // before a stretch of ALU work so that no exchange poll queues behind these ~1 us loads.
         auto s_prefetch = [&](int64_t ts) {
             if (ts < seg_end) {
-                cnext0 = CONDg[(size_t)ts * 512 + sidx];
-                cnext1 = CONDg[(size_t)ts * 512 + sidx + 256];
+                const float4 *cp = CONDg + (size_t)ts * 512;
+                const unsigned so = (unsigned)sidx & 255u;
+                cnext0 = cp[so];
+                cnext1 = cp[256 + so];
             }
         };
         // S: sampling noise of step ts for the paired C quarter -> hand[4 + 2*parity(ts) ...]
@@ -437,7 +443,7 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
                     cstQ[11] = C3g[(size_t)fi * 512 + unit];
                     cstQ[12] = C4g[(size_t)fi * 512 + unit];
                 }
-                cst_frame = pend_frame;
+                cst_frame = __builtin_amdgcn_readfirstlane(pend_frame);
             }
         };
         if (!isC) {
@@ -456,7 +462,6 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
 
         int out_k = 0;
         float out_x = 0.0f;
-        u64 lookb[1] = {0};   // the second look of an exchange (take_granule), retired behind the exchange's barrier
         for (int64_t t = a.seg0; t < seg_end; ++t) {
             ++epoch;
             const unsigned par = epoch & 1u;
@@ -484,12 +489,14 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
 
             if (isC) {
                 // ---- phase B: GRU2 unit `unit` (:213-216); rows r,z,n of W_ih2[:, :512] . x2 ----
-                const float h2o = xb[XB_H2 * XB_VEC + pu];
-                const float x2u = xb[XB_X2 * XB_VEC + pu];
-                const float g2r = hand[0], g2z = hand[1], g2n = hand[2];
-                const float c2r = cstQ[8], c2z = cstQ[9], c2n = cstQ[10];
+                float h2o = xb[XB_H2 * XB_VEC + pu];
+                float x2u = xb[XB_X2 * XB_VEC + pu];
+                float g2r = hand[0], g2z = hand[1], g2n = hand[2];
+                float c2r = cstQ[8], c2z = cstQ[9], c2n = cstQ[10];
+                hoist_fence();
                 float gr, gz, gn;
                 dot32x3(wv, xb + XB_X2 * XB_VEC, q, gr, gz, gn);
+                pin(h2o); pin(x2u); pin(g2r); pin(g2z); pin(g2n); pin(c2r); pin(c2z); pin(c2n);
                 gr = row_sum(gr) + c2r; gz = row_sum(gz) + c2z; gn = row_sum(gn) + c2n;
                 const float rg = sigmoid_fast(gr + g2r);
                 const float zg = sigmoid_fast(gz + g2z);
@@ -504,8 +511,11 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
                 // ---- S: gh1 for the next step = W_hh1 . h1' + b_hh1, published for everyone ----
                 float sr, sz, sn;
                 __builtin_amdgcn_s_sleep(2);   // let the critical waves' x2 reads go first
+                float b1r = cstQ[0], b1z = cstQ[1], b1n = cstQ[2];
+                hoist_fence();
                 dot32x3(wv, xb + XB_H1 * XB_VEC, q, sr, sz, sn);
-                sr = row_sum(sr) + cstQ[0]; sz = row_sum(sz) + cstQ[1]; sn = row_sum(sn) + cstQ[2];
+                pin(b1r); pin(b1z); pin(b1n);
+                sr = row_sum(sr) + b1r; sz = row_sum(sz) + b1z; sn = row_sum(sn) + b1n;
                 if (q == 0) {
                     st_granule(mail, G_GH + par * 1536 + unit, epoch, __float_as_uint(sr));
                     st_granule(mail, G_GH + par * 1536 + 512 + unit, epoch, __float_as_uint(sz));
@@ -515,18 +525,21 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
             P2(2);
             // ---- exchange 1 (all threads, granule tid): x3 = x + h2 ; h2' = x3 - x2 ----
             {
-                const float x3 = __uint_as_float(take_granule(mail, G_X3 + par * 512 + tid, epoch, dead, a.err, 11u, lookb));
+                const float x3 = __uint_as_float(take_granule(mail, G_X3 + par * 512 + tid, epoch, dead, a.err, 11u));
                 xb[XB_X3 * XB_VEC + pj] = x3;
                 xb[XB_H2 * XB_VEC + pj] = x3 - x2_j;
             }
             P2(3);
             __syncthreads();  // B2
-            retire_look(lookb);
             P2(4);
 
             if (isC) {
                 // ---- phase C: fc1 row `unit` (:217-218) ----
-                const float s = row_sum(dot32(wv + 128, xb + XB_X3 * XB_VEC, q)) + cstQ[11];
+                float c3u = cstQ[11];
+                hoist_fence();
+                const float d = dot32(wv + 128, xb + XB_X3 * XB_VEC, q);
+                pin(c3u);
+                const float s = row_sum(d) + c3u;
                 if (q == 0) st_granule(mail, G_F1 + par * 512 + unit, epoch, __float_as_uint(fmaxf(s, 0.0f)));
             } else {
                 // ---- S: sampling noise of step t+1 (C reads the other parity slot this step) ----
@@ -535,16 +548,19 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
             P2(5);
             // ---- exchange 2: fc1 outputs ----
             {
-                xb[XB_F1 * XB_VEC + pj] = __uint_as_float(take_granule(mail, G_F1 + par * 512 + tid, epoch, dead, a.err, 12u, lookb));
+                xb[XB_F1 * XB_VEC + pj] = __uint_as_float(take_granule(mail, G_F1 + par * 512 + tid, epoch, dead, a.err, 12u));
             }
             P2(6);
             __syncthreads();  // B3
-            retire_look(lookb);
             P2(7);
 
             if (isC) {
                 // ---- phase D: fc2 row `unit` (:220-221) ----
-                const float s = row_sum(dot32(wv + 96, xb + XB_F1 * XB_VEC, q)) + cstQ[12];
+                float c4u = cstQ[12];
+                hoist_fence();
+                const float d = dot32(wv + 96, xb + XB_F1 * XB_VEC, q);
+                pin(c4u);
+                const float s = row_sum(d) + c4u;
                 if (q == 0) st_granule(mail, G_F2 + par * 512 + unit, epoch, __float_as_uint(fmaxf(s, 0.0f)));
             } else {
                 // ---- S: conditioning + noise of step t+1 ----
@@ -553,16 +569,22 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
             P2(8);
             // ---- exchange 3: fc2 outputs ----
             {
-                xb[XB_F2 * XB_VEC + pj] = __uint_as_float(take_granule(mail, G_F2 + par * 512 + tid, epoch, dead, a.err, 13u, lookb));
+                xb[XB_F2 * XB_VEC + pj] = __uint_as_float(take_granule(mail, G_F2 + par * 512 + tid, epoch, dead, a.err, 13u));
             }
             P2(9);
             __syncthreads();  // B4
-            retire_look(lookb);
             P2(10);
 
             if (isC) {
                 // ---- phase E: fc3 rows + race (:223, :231-235) ----
                 float lg0, lg1;
+#if T2_HOIST_LDS
+                // the fc3 biases and (RAW) both noise slots of this step's parity: one 8-byte read each, issued ahead of the fc3 reads
+                float b3a = cstQ[6], b3b = cstQ[7];
+                float2 nz = make_float2(0.f, 0.f);
+                if (MODE == WRNN_MODE_RAW) nz = *(const float2 *)(hand + 4 + 2 * par);
+                hoist_fence();
+#endif
                 {
                     const float4 *xp = (const float4 *)(xb + XB_F2 * XB_VEC) + q;
                     const float4 *wp = (const float4 *)(lds + L_FC3) + (size_t)(wl * 2) * 8 * 64 + lane;
@@ -579,20 +601,36 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
                             pa = pkfma(mk2(wa[k].z, wa[k].w), xh, pa); pb = pkfma(mk2(wb[k].z, wb[k].w), xh, pb);
                         }
                     }
+#if T2_HOIST_LDS
+                    pin(b3a); pin(b3b); pin(nz.x); pin(nz.y);
+                    lg0 = row_sum(pa.x + pa.y) + b3a;
+                    lg1 = row_sum(pb.x + pb.y) + b3b;
+#else
                     lg0 = row_sum(pa.x + pa.y) + cstQ[6];
                     lg1 = row_sum(pb.x + pb.y) + cstQ[7];
+#endif
                 }
                 if (a.logits_out && q == 0 && has_fc3) {
-                    float *lo = a.logits_out + ((size_t)t * a.n_rows + row) * NC + c3row0;
+                    // the row offset is made opaque HERE: otherwise the compiler keeps `logits_out + c3row0` as a 64-bit per-lane address for the
+                    // whole launch -- a spill slot, in a kernel at its register limit, for a branch that free-running generation never takes
+                    int c3o = c3row0;
+                    asm volatile("" : "+v"(c3o));
+                    float *lo = a.logits_out + ((size_t)t * a.n_rows + row) * NC + c3o;
                     lo[0] = lg0;
                     if (c3row0 + 1 < NC) lo[1] = lg1;
                 }
                 if (MODE == WRNN_MODE_RAW) {
                     // winner of this quarter-wave's 2 classes: argmax logit_k - log q_k
-                    // quarters beyond n_classes (bits < 10) own no class: they enter the race with -inf (and never read their
-                    // noise slot, which the shadow wave leaves unwritten for them)
+                    // quarters beyond n_classes (bits < 10) own no class: they enter the race with -inf.  The shadow wave leaves their
+                    // noise slot unwritten: T2_HOIST_LDS reads it all the same (no branch on the chain) and the SELECT discards whatever
+                    // it held, NaN included; the older form never reads it
+#if T2_HOIST_LDS
+                    const float v0 = has_fc3 ? lg0 + nz.x : -INFINITY;
+                    const float v1 = (c3row0 + 1 < NC) ? lg1 + nz.y : -INFINITY;
+#else
                     const float v0 = has_fc3 ? lg0 + hand[4 + 2 * par] : -INFINITY;
                     const float v1 = (c3row0 + 1 < NC) ? lg1 + hand[5 + 2 * par] : -INFINITY;
+#endif
                     const bool p1 = v1 > v0;
                     // the wave's four quarters (uniform rows) -> one candidate, in registers; ties -> lowest row = lowest class
                     const float bq = p1 ? v1 : v0;
@@ -609,11 +647,20 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
                         if (T2_RACE_SLEEP) __builtin_amdgcn_s_sleep(T2_RACE_SLEEP);
                         const unsigned roff = (G_PR + par * 512 + 2u * (unsigned)lane) * 8u;
                         const unsigned rtag = epoch & 0x3fffffu;
+#if T2_STRAIGHT_POLL & 2
+                        u4 gq;
+                        for (unsigned spins = 0;;) {   // one load site, see take_granule
+                            gq = race_load(mail, roff);
+                            if (__all(race_ok(gq, rtag)) || dead) break;
+                            if (++spins > TEAM_SPIN_MAX) { dead = true; if (lane == 0) atomicExch(a.err, 14u); break; }
+                        }
+#else
                         u4 gq = race_load(mail, roff);
                         for (unsigned spins = 0; !dead && !__all(race_ok(gq, rtag));) {
                             if (++spins > TEAM_SPIN_MAX) { dead = true; if (lane == 0) atomicExch(a.err, 14u); break; }
                             gq = race_load(mail, roff);
                         }
+#endif
                         P2(14);
                         const float va = __uint_as_float(gq.x), vb = __uint_as_float(gq.z);
                         const bool pb_ = vb > va;
@@ -675,9 +722,18 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
                 // exchange (measured: 3.40 vs 3.45 us/step against "gh2 first") ----
                 s_frame_consts();
                 s_prefetch(t + 2);
+#if T2_STRAIGHT_POLL & 4
+                u64 gq[6];
+                for (unsigned spins = 0;;) {   // one load site, see take_granule
+                    peek_n<6>(mail, G_GH + par * 1536 + sidx, 256, gq);
+                    if (__all(tags_ok<6, 32>(gq, epoch)) || dead) break;
+                    if (++spins > TEAM_SPIN_MAX) { dead = true; if (lane == 0) atomicExch(a.err, 15u); break; }
+                }
+#else
                 u64 gq[6];
                 peek_n<6>(mail, G_GH + par * 1536 + sidx, 256, gq);
                 finish_n<6, 32>(mail, G_GH + par * 1536 + sidx, 256, epoch, gq, dead, a.err, 15u);
+#endif
 #pragma unroll
                 for (int m = 0; m < 6; ++m) gh1s[sidx + m * 256] = __uint_as_float((unsigned)gq[m]);
                 P2(13);
@@ -685,8 +741,11 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
                     // gh2 for the next step = W_hh2 . h2' + b_hh2 -> hand-off slot of the paired C quarter (C read the
                     // old value back in phase B, three barriers ago)
                     float sr, sz, sn;
+                    float b2r = cstQ[3], b2z = cstQ[4], b2n = cstQ[5];
+                    hoist_fence();
                     dot32x3_mixed(wv + 96, swl, xb + XB_H2 * XB_VEC, q, sr, sz, sn);
-                    sr = row_sum(sr) + cstQ[3]; sz = row_sum(sz) + cstQ[4]; sn = row_sum(sn) + cstQ[5];
+                    pin(b2r); pin(b2z); pin(b2n);
+                    sr = row_sum(sr) + b2r; sz = row_sum(sz) + b2z; sn = row_sum(sn) + b2n;
                     if (q == 0) { hand[0] = sr; hand[1] = sz; hand[2] = sn; }
                 }
             }

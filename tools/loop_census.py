@@ -6,7 +6,9 @@
 --team2: the step loop of the shipped loop_team2_kernel instantiation split at its workgroup barriers (window 0 = phase A in front of B1,
 window 5 = behind B5), per window the instruction mix and the spill traffic (`scratch_*`, `v_readlane / v_writelane`), and for every scratch
 instruction the wave role whose code it sits in: critical (C), shadow (S) or shared, taken from the line table (-gline-tables-only) against the
-`if (isC) {...} else {...}` blocks and the S-only lambdas of the source.
+`if (isC) {...} else {...}` blocks and the S-only lambdas of the source.  Per window and role also what the generated code puts on the serial
+chain behind the source's back: the `ds_read*` that sit between the last `v_pk_fma_f32` of a dot product and the publish that consumes it (a read
+sunk behind the row sums is a dependent LDS round trip), and the instruction count from the wait of an exchange's first `sc1` look to its LDS landing.
 
 For every non-instrumented instantiation: hipcc's resource remarks, and for each ROLE's step loop (the C waves' and the S waves' loops are separate
 code: the innermost loops that contain workgroup barriers and MFMAs) the static instruction mix -- above all the spill traffic that sits on a step:
@@ -113,6 +115,35 @@ def team2_roles(src_lines):
     return role
 
 
+def chain_report(part):
+    """part: [(asm line, role)] of one barrier window.  Lines for (1) every granule publish (`global_store_dwordx2`) and LDS hand-over (`ds_write*`
+    directly behind a dot product's row sums): the ds_read* between it and the nearest v_pk_fma_f32 in front of it; (2) every exchange: the
+    instructions from the wait of the first sc1 look to the landing (the first ds_write behind it), straight-line count and the copies among them."""
+    ins = [(l.strip().split(';')[0].strip(), role) for l, role in part]
+    ins = [(t, r) for t, r in ins if t and t[0] != '.' or re.match(r'^\.LBB\d+_\d+:', t)]
+    out = []
+    for i, (t, role) in enumerate(ins):
+        if not t.startswith('global_store_dwordx2'):
+            continue
+        fma = max((j for j in range(i) if ins[j][0].startswith('v_pk_fma_f32')), default=None)
+        if fma is None:
+            continue
+        reads = [x for x, _ in ins[fma + 1:i] if x.startswith('ds_read')]
+        out.append(f'publish ({role}) {i - fma - 1} instr behind the last v_pk_fma_f32, ds_read between: {len(reads)}' + (': ' + ' ; '.join(reads) if reads else ''))
+    looks = [i for i, (t, _) in enumerate(ins) if re.search(r'\bsc1\b', t) and t.startswith('global_load')]
+    seen = set()
+    for i in looks:
+        w = next((j for j in range(i, len(ins)) if ins[j][0].startswith('s_waitcnt') and 'vmcnt' in ins[j][0]), None)
+        land = next((j for j in range(i, len(ins)) if ins[j][0].startswith('ds_write')), None)
+        if w is None or land is None or land in seen:
+            continue
+        seen.add(land)
+        span = [x for x, _ in ins[w + 1:land] if not x.endswith(':')]
+        out.append(f'poll ({ins[i][1]}): {len(span)} instr laid out between the first look\'s wait and the landing `{ins[land][0].split()[0]}`, '
+                   f'v_mov_b64 {sum(x.startswith("v_mov_b64") for x in span)}, branches {sum(x.startswith(("s_cbranch", "s_branch")) for x in span)}')
+    return out
+
+
 def team2_main(extra) -> int:
     flags = [f for f in FLAGS if f not in ('-mllvm', '-amdgpu-mfma-vgpr-form')]
     with tempfile.TemporaryDirectory() as td:
@@ -154,7 +185,9 @@ def team2_main(extra) -> int:
         if mm and mm.group(1) in lab and lab[mm.group(1)] < i:
             loops.append((lab[mm.group(1)], i))
     nbar = lambda a, b: sum(l.strip().startswith('s_barrier') for l, _ in tagged[a:b + 1])
-    a, b = min(((b - a, a, b) for a, b in loops if nbar(a, b) >= 5))[1:]
+    # a poll's retry block laid out behind the loop branches back into it: such a span holds barriers too but crosses the nest, it is no loop of it
+    crosses = lambda a, b: any(a2 < a < b2 < b for a2, b2 in loops)
+    a, b = min(((b - a, a, b) for a, b in loops if nbar(a, b) >= 5 and not crosses(a, b)))[1:]
     body = tagged[a:b + 1]
     print(f'# tools/loop_census.py --team2 {" ".join(extra)}: loop_team2_kernel<RAW, false, false> as in the tree (hipcc -O3 --offload-arch=gfx950)')
     print('== ' + ' | '.join(x.strip() for x in res))
@@ -177,6 +210,8 @@ def team2_main(extra) -> int:
                 by[role] = by.get(role, 0) + 1
         if by:
             print('      v_readlane / v_writelane by role: ' + ', '.join(f'{k} {v}' for k, v in sorted(by.items())))
+        for line in chain_report(part):
+            print('      ' + line)
     return 0
 
 
