@@ -289,6 +289,18 @@ int wrnn_sync_status(wrnn_handle *h, void *stream);
 /* The two GRU recurrences of wrnn_train_step run as one persistent XCD-team kernel each where rnn_dims is 512 and the device has
  * 32-CU teams, else as one kernel per time step replayed from a hipGraph.  on != 0 forces the per-step kernels (tests compare the two). */
 int wrnn_train_force_step_kernels(wrnn_handle *h, int32_t on);
+/* Added to ABI 9 (new entry points only).  What the two GRU recurrences of the last training call on h ran, and with how many rows per
+ * team batch (0 for the step kernels); WRNN_ERR_STATE before any training call.  Either pointer may be NULL. */
+#define WRNN_TRAIN_RAN_STEPS 0
+#define WRNN_TRAIN_RAN_TEAM512 1
+int wrnn_train_last_recurrence(const wrnn_handle *h, int32_t *kernel, int32_t *rows_per_team);
+/* Host only, no device: the layout persistent team recurrences would have for a run-time rnn_dims at `rows` rows per team (1..4: a
+ * 4-row instantiation, 5..8: an 8-row one), with the work split of the 512 kernels: units per workgroup = ceil(rnn_dims / 32), the
+ * dynamic LDS of a forward and a backward kernel in bytes, and the 8-byte granules of one team's mailbox.  This build has no such
+ * kernels yet; the plan says which rnn_dims they could take.  WRNN_ERR_INVALID: rnn_dims < 16 or no multiple of 16, rows outside 1..8
+ * (nothing written).  WRNN_ERR_UNSUPPORTED: either kernel would need more than 160 KiB of LDS for its slice of W_hh (the figures are
+ * written all the same); W_hh is not streamed from L2, such dims stay on the step kernels.  Any out pointer may be NULL. */
+int wrnn_train_teamg_plan(int32_t rnn_dims, int32_t rows, int32_t *units_per_wg, int64_t *lds_fwd, int64_t *lds_bwd, int64_t *mail_granules);
 
 /* Blocks until the last wrnn_generate on this handle finished, then reports
  * HIP-event timings and any device-side error (WRNN_ERR_TIMEOUT, WRNN_ERR_BUSY; WRNN_ERR_INVALID when the fold count a

@@ -43,7 +43,7 @@ EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wr
                     'wrnn_resample_create', 'wrnn_resample_out_len', 'wrnn_resample_bank', 'wrnn_resample', 'wrnn_resample_last_error',
                     'wrnn_resample_destroy', 'wrnn_condition_frames', 'wrnn_condition', 'wrnn_teamg_plan', 'wrnn_debug_teamg_lds_budget',
                     'wrnn_teamg_batch_plan', 'wrnn_last_batch_rows', 'wrnn_teamg_set_weight_format', 'wrnn_teamg_weight_format',
-                    'wrnn_teamg_plan_fmt')
+                    'wrnn_teamg_plan_fmt', 'wrnn_train_last_recurrence', 'wrnn_train_teamg_plan')
 
 
 def epilogue_tables(n_classes: int, overlap: int, hop: int):
@@ -182,6 +182,20 @@ def teamg_batch_plan(rows_per_team: int, lds_budget_bytes: int = -1, **dims) -> 
     return teamg_plan(lds_budget_bytes, rows_per_team=int(rows_per_team), **dims)
 
 
+# wrnn_train_last_recurrence: what the two GRU recurrences of the last training call ran
+TRAIN_RAN_NAMES = {0: 'steps', 1: 'team512'}
+
+
+def train_teamg_plan(rnn_dims: int, rows: int) -> dict:
+    """Host-only ``wrnn_train_teamg_plan``: the layout persistent team recurrences of training would have for ``rnn_dims`` at ``rows`` rows
+    per team.  Returns ``dict(status, units_per_wg, lds_fwd, lds_bwd, mail_granules)``; ``status`` is ``WRNN_OK`` (0) where a workgroup's
+    slice of W_hh fits LDS, ``WRNN_ERR_UNSUPPORTED`` (-7) where it exceeds 160 KiB (the figures are still filled in) and
+    ``WRNN_ERR_INVALID`` (-1) for an rnn_dims that is no multiple of 16 or rows outside 1..8 (figures 0).  Never raises."""
+    u, lf, lb, mg = C.c_int32(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    rc = load_library().wrnn_train_teamg_plan(int(rnn_dims), int(rows), C.byref(u), C.byref(lf), C.byref(lb), C.byref(mg))
+    return dict(status=int(rc), units_per_wg=int(u.value), lds_fwd=int(lf.value), lds_bwd=int(lb.value), mail_granules=int(mg.value))
+
+
 def teamg_plan_fmt(rows_per_team: int, weights: str, lds_budget_bytes: int = -1, **dims) -> dict:
     """Host-only ``wrnn_teamg_plan_fmt``: :func:`teamg_batch_plan` for the weight image format ``weights`` ('f32' or 'f16').  Same dict; with
     'f16' every byte figure counts 2-byte weights and more units fit the same LDS budget, ownership and ``k_padded`` are unchanged."""
@@ -297,6 +311,10 @@ def load_library() -> C.CDLL:
     lib.wrnn_teamg_set_weight_format.restype = C.c_int
     lib.wrnn_teamg_weight_format.argtypes = [vp]
     lib.wrnn_teamg_weight_format.restype = C.c_int32
+    lib.wrnn_train_last_recurrence.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.wrnn_train_last_recurrence.restype = C.c_int
+    lib.wrnn_train_teamg_plan.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.wrnn_train_teamg_plan.restype = C.c_int
     lib.wrnn_last_batch_rows.argtypes = [vp]
     lib.wrnn_last_batch_rows.restype = C.c_int32
     lib.wrnn_stream_open.argtypes = [vp, C.c_int32, C.POINTER(SampleOpts), C.POINTER(vp)]
@@ -542,6 +560,12 @@ class NativeVocoder:
 
     def train_force_step_kernels(self, on: bool):
         self._check(self.lib.wrnn_train_force_step_kernels(self._h, int(bool(on))))
+
+    def train_last_recurrence(self) -> Tuple[str, int]:
+        """('steps' | 'team512', rows per team batch) of the last training call on this handle (``wrnn_train_last_recurrence``)."""
+        k, r = C.c_int32(), C.c_int32()
+        self._check(self.lib.wrnn_train_last_recurrence(self._h, C.byref(k), C.byref(r)))
+        return TRAIN_RAN_NAMES[int(k.value)], int(r.value)
 
     def loss(self, y_hat_ptr: int, y_ptr: int, n_rows: int, out_ptr: int, stream: int):
         self._check(self.lib.wrnn_loss(self._h, y_hat_ptr, y_ptr, int(n_rows), out_ptr, stream or None))

@@ -29,6 +29,7 @@
 #include <cstdio>
 
 #include "team_common.h"
+#include "train_teamg_plan.h"
 
 namespace {
 
@@ -733,6 +734,8 @@ static int train_impl(wrnn_handle *h, int phase, const wrnn_loop_params *w, cons
         }
     }
     const bool use_team = st->team_checked == 1 && H == TEAM_H && !h->train_force_steps;
+    h->train_last_kernel = use_team ? WRNN_TRAIN_RAN_TEAM512 : WRNN_TRAIN_RAN_STEPS;   // wrnn_train_last_recurrence
+    h->train_last_rows = use_team ? rpb : 0;
     if (!use_team) {   // the per-step kernels' LDS sizes: only where they run (the attribute is per device: set per call, a host-side table write)
         T_TRY(hipFuncSetAttribute((const void *)fwd_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));
         T_TRY(hipFuncSetAttribute((const void *)bwd_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));
@@ -917,4 +920,25 @@ extern "C" int wrnn_train_force_step_kernels(wrnn_handle *h, int32_t on) {
     if (!h) return WRNN_ERR_INVALID;
     h->train_force_steps = on != 0;
     return WRNN_OK;
+}
+
+// what the recurrences of the last training call on h ran (WRNN_TRAIN_RAN_*), and with how many rows per team batch
+extern "C" int wrnn_train_last_recurrence(const wrnn_handle *h, int32_t *kernel, int32_t *rows_per_team) {
+    if (!h) return WRNN_ERR_INVALID;
+    if (h->train_last_kernel < 0) return WRNN_ERR_STATE;
+    if (kernel) *kernel = h->train_last_kernel;
+    if (rows_per_team) *rows_per_team = h->train_last_rows;
+    return WRNN_OK;
+}
+
+// the layout a persistent team recurrence for run-time rnn_dims would have (train_teamg_plan.h): pure host code, no device
+extern "C" int wrnn_train_teamg_plan(int32_t rnn_dims, int32_t rows, int32_t *units_per_wg, int64_t *lds_fwd, int64_t *lds_bwd, int64_t *mail_granules) {
+    if (rnn_dims < 16 || rnn_dims % 16 != 0 || rows < 1 || rows > 8) return WRNN_ERR_INVALID;
+    const WrnnTrainTeamGPlan p = wrnn_train_teamg_layout(rnn_dims, rows);
+    if (units_per_wg) *units_per_wg = p.U;
+    if (lds_fwd) *lds_fwd = p.lds_fwd;
+    if (lds_bwd) *lds_bwd = p.lds_bwd;
+    if (mail_granules) *mail_granules = p.mail_bwd > p.mail_fwd ? p.mail_bwd : p.mail_fwd;
+    // above the limit there is no streaming of W_hh from L2: such dims stay on the step kernels
+    return (p.lds_fwd > WRNN_TTG_LDS_LIMIT || p.lds_bwd > WRNN_TTG_LDS_LIMIT || !p.structural_ok) ? WRNN_ERR_UNSUPPORTED : WRNN_OK;
 }

@@ -136,6 +136,7 @@ struct wrnn_handle {
     size_t loss_cap = 0;
     WrnnTrainState *train = nullptr;
     bool train_force_steps = false;   // wrnn_train_force_step_kernels
+    int32_t train_last_kernel = -1, train_last_rows = 0;   // what the recurrences of the last training call ran (wrnn_train_last_recurrence); -1 = none yet
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     bool timing_valid = false;
     wrnn_timing last{};
