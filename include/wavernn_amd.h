@@ -302,6 +302,29 @@ int wrnn_train_last_recurrence(const wrnn_handle *h, int32_t *kernel, int32_t *r
  * written all the same); W_hh is not streamed from L2, such dims stay on the step kernels.  Any out pointer may be NULL. */
 int wrnn_train_teamg_plan(int32_t rnn_dims, int32_t rows, int32_t *units_per_wg, int64_t *lds_fwd, int64_t *lds_bwd, int64_t *mail_granules);
 
+/* Mixed-precision training, added to ABI 9 (new entry points only).  The precision belongs to the handle; the default is
+ * WRNN_TRAIN_F32.  With WRNN_TRAIN_BF16 the batched GEMMs of the training calls -- forward, input gradients, weight gradients, the
+ * d_aux / d_mels_up products -- round each operand element once to bfloat16 (nearest even) on its way to the matrix cores and
+ * accumulate in fp32; memory stays fp32.  Not rounded: the two GEMMs that read x_dev (the sample input's column of I, forward and
+ * gradient: they stay on the fp32 kernel), the recurrences and their W_hh, biases, bias gradients, losses and loss gradients.
+ * bfloat16 keeps fp32's exponent range, so no loss scaling is involved.  WRNN_ERR_INVALID: fmt is neither value. */
+#define WRNN_TRAIN_F32 0
+#define WRNN_TRAIN_BF16 1
+int wrnn_train_set_precision(wrnn_handle *h, int32_t fmt);
+int wrnn_train_precision(const wrnn_handle *h, int32_t *fmt);
+/* How many GEMMs the last training call on h launched on the fp32 and on the bf16 kernel (host-side counts; a split-K product counts
+ * once).  WRNN_ERR_STATE before any training call.  Either pointer may be NULL. */
+int wrnn_train_last_gemms(const wrnn_handle *h, int32_t *n_f32, int32_t *n_bf16);
+/* Developer / test entry: one product C (M x N) = (beta) C + A.B (+ bias[N]) (relu) on the caller's device buffers through the GEMM
+ * dispatcher and split-K wrapper of the training calls.  A(m,k) = ta ? A[k*lda + m] : A[m*lda + k], B(k,n) = tb ? B[n*ldb + k] :
+ * B[k*ldb + n]; operands need 4-byte alignment only.  precision is taken literally.  slices: 1 = no split, 0 = the wrapper's own choice,
+ * 2..64 = that many slices of K (slices past the end of K contribute zeros), summed in slice order from a temporary of this call's own --
+ * a split product takes no bias and no relu, and the call then waits for the stream.  WRNN_ERR_UNSUPPORTED: ta and tb with
+ * WRNN_TRAIN_BF16 (that kernel has the NT, NN and TN forms). */
+int wrnn_debug_train_gemm(wrnn_handle *h, int32_t precision, int32_t ta, int32_t tb, const float *A, int64_t lda, const float *B,
+                          int64_t ldb, float *C, int64_t ldc, int32_t M, int32_t N, int32_t K, int32_t beta, const float *bias,
+                          int32_t relu, int32_t slices, void *stream);
+
 /* Blocks until the last wrnn_generate on this handle finished, then reports
  * HIP-event timings and any device-side error (WRNN_ERR_TIMEOUT, WRNN_ERR_BUSY; WRNN_ERR_INVALID when the fold count a
  * folded call computed on the device differs from its rows_total). */

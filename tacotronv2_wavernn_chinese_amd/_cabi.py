@@ -43,7 +43,8 @@ EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wr
                     'wrnn_resample_create', 'wrnn_resample_out_len', 'wrnn_resample_bank', 'wrnn_resample', 'wrnn_resample_last_error',
                     'wrnn_resample_destroy', 'wrnn_condition_frames', 'wrnn_condition', 'wrnn_teamg_plan', 'wrnn_debug_teamg_lds_budget',
                     'wrnn_teamg_batch_plan', 'wrnn_last_batch_rows', 'wrnn_teamg_set_weight_format', 'wrnn_teamg_weight_format',
-                    'wrnn_teamg_plan_fmt', 'wrnn_train_last_recurrence', 'wrnn_train_teamg_plan')
+                    'wrnn_teamg_plan_fmt', 'wrnn_train_last_recurrence', 'wrnn_train_teamg_plan',
+                    'wrnn_train_set_precision', 'wrnn_train_precision', 'wrnn_train_last_gemms', 'wrnn_debug_train_gemm')
 
 
 def epilogue_tables(n_classes: int, overlap: int, hop: int):
@@ -184,6 +185,29 @@ def teamg_batch_plan(rows_per_team: int, lds_budget_bytes: int = -1, **dims) -> 
 
 # wrnn_train_last_recurrence: what the two GRU recurrences of the last training call ran
 TRAIN_RAN_NAMES = {0: 'steps', 1: 'team512'}
+TRAIN_PRECISIONS = {'f32': 0, 'bf16': 1}   # WRNN_TRAIN_*: the kernel the batched GEMMs of the training calls run on
+TRAIN_PRECISION_NAMES = {v: k for k, v in TRAIN_PRECISIONS.items()}
+
+
+def _train_precision_id(precision: str) -> int:
+    if precision not in TRAIN_PRECISIONS:
+        raise ValueError(f'train precision must be one of {sorted(TRAIN_PRECISIONS)}, not {precision!r}')
+    return TRAIN_PRECISIONS[precision]
+
+
+def check_train_gemm_args(precision: str, ta: bool, tb: bool, lda: int, ldb: int, ldc: int, M: int, N: int, K: int, bias_ptr: int, relu: bool,
+                          slices: int) -> int:
+    """The argument checks of :meth:`NativeVocoder.debug_train_gemm` that need no device (``ValueError``); returns the precision id."""
+    prec = _train_precision_id(precision)
+    if M < 1 or N < 1 or K < 0:
+        raise ValueError(f'debug_train_gemm: bad shape M={M}, N={N}, K={K}')
+    if not 0 <= slices <= 64:
+        raise ValueError(f'debug_train_gemm: slices must be 0 (the wrapper chooses), 1 (no split) or 2..64, not {slices}')
+    if lda < (M if ta else max(K, 1)) or ldb < (max(K, 1) if tb else N) or ldc < N:
+        raise ValueError(f'debug_train_gemm: a leading dimension is shorter than its row (lda={lda}, ldb={ldb}, ldc={ldc})')
+    if slices != 1 and (bias_ptr or relu):
+        raise ValueError('debug_train_gemm: a split product takes no bias and no relu')
+    return prec
 
 
 def train_teamg_plan(rnn_dims: int, rows: int) -> dict:
@@ -315,6 +339,15 @@ def load_library() -> C.CDLL:
     lib.wrnn_train_last_recurrence.restype = C.c_int
     lib.wrnn_train_teamg_plan.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.wrnn_train_teamg_plan.restype = C.c_int
+    lib.wrnn_train_set_precision.argtypes = [vp, C.c_int32]
+    lib.wrnn_train_set_precision.restype = C.c_int
+    lib.wrnn_train_precision.argtypes = [vp, C.POINTER(C.c_int32)]
+    lib.wrnn_train_precision.restype = C.c_int
+    lib.wrnn_train_last_gemms.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.wrnn_train_last_gemms.restype = C.c_int
+    lib.wrnn_debug_train_gemm.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp]
+    lib.wrnn_debug_train_gemm.restype = C.c_int
     lib.wrnn_last_batch_rows.argtypes = [vp]
     lib.wrnn_last_batch_rows.restype = C.c_int32
     lib.wrnn_stream_open.argtypes = [vp, C.c_int32, C.POINTER(SampleOpts), C.POINTER(vp)]
@@ -566,6 +599,37 @@ class NativeVocoder:
         k, r = C.c_int32(), C.c_int32()
         self._check(self.lib.wrnn_train_last_recurrence(self._h, C.byref(k), C.byref(r)))
         return TRAIN_RAN_NAMES[int(k.value)], int(r.value)
+
+    def set_train_precision(self, precision: str):
+        """'f32' (default) or 'bf16': the kernel the batched GEMMs of the following training calls run on (``wrnn_train_set_precision``).
+        The two GEMMs on the sample input ``x`` and the recurrences stay fp32 either way."""
+        self._check(self.lib.wrnn_train_set_precision(self._h, _train_precision_id(precision)))
+
+    @property
+    def train_precision(self) -> str:
+        fmt = C.c_int32()
+        self._check(self.lib.wrnn_train_precision(self._h, C.byref(fmt)))
+        return TRAIN_PRECISION_NAMES[int(fmt.value)]
+
+    def train_last_gemms(self) -> Tuple[int, int]:
+        """(GEMMs on the fp32 kernel, GEMMs on the bf16 kernel) of the last training call on this handle (``wrnn_train_last_gemms``);
+        ``WrnnError`` (WRNN_ERR_STATE) before any."""
+        a, b = C.c_int32(), C.c_int32()
+        self._check(self.lib.wrnn_train_last_gemms(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def debug_train_gemm(self, precision: str, ta: bool, tb: bool, a_ptr: int, lda: int, b_ptr: int, ldb: int, c_ptr: int, ldc: int, M: int,
+                         N: int, K: int, *, beta: bool = False, bias_ptr: int = 0, relu: bool = False, slices: int = 1, stream: int = 0):
+        """``wrnn_debug_train_gemm``: C (M, N) = (beta) C + A.B (+ bias) (relu) on device float32 buffers through the training calls' GEMM
+        dispatcher and split-K wrapper, ``precision`` ('f32' / 'bf16') taken literally.  ``ValueError`` for arguments that are wrong on
+        their face (:func:`check_train_gemm_args`), ``WrnnError`` (WRNN_ERR_UNSUPPORTED) for ta and tb in bf16."""
+        prec = check_train_gemm_args(precision, bool(ta), bool(tb), int(lda), int(ldb), int(ldc), int(M), int(N), int(K), int(bias_ptr or 0),
+                                     bool(relu), int(slices))
+        if not (a_ptr and b_ptr and c_ptr):
+            raise ValueError('debug_train_gemm: A, B and C are device pointers')
+        self._check(self.lib.wrnn_debug_train_gemm(self._h, prec, int(bool(ta)), int(bool(tb)), a_ptr, int(lda), b_ptr, int(ldb), c_ptr, int(ldc),
+                                                   int(M), int(N), int(K), int(bool(beta)), bias_ptr or None, int(bool(relu)), int(slices),
+                                                   stream or None))
 
     def loss(self, y_hat_ptr: int, y_ptr: int, n_rows: int, out_ptr: int, stream: int):
         self._check(self.lib.wrnn_loss(self._h, y_hat_ptr, y_ptr, int(n_rows), out_ptr, stream or None))

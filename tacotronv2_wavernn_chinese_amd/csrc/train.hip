@@ -16,6 +16,8 @@
 //                         operands staged through LDS k-major (conflict-free operand reads), register double-buffered global loads,
 //                         optional split-K over blockIdx.z (weight gradients).  fp32 in, fp32 accumulate: the bound is the fp32
 //                         matrix peak (157 TFLOP/s); measured 111 TFLOP/s (forward / input gradients), 65 (weight gradients).
+//   gemm_bf16_kernel      train_gemm_bf16.hip: the same contract with operands rounded to bf16 on their way into LDS and bf16 MFMAs; runs
+//                         every GEMM but the two on x_dev when the handle's precision is WRNN_TRAIN_BF16 (opt-in)
 //   the recurrences       train_team.hip: one persistent XCD-team kernel per recurrence and direction (rnn_dims 512).  Fallback here:
 //   gru_fwd_step_kernel   one launch per time step: gh = h_{t-1} . W_hh^T for 4 hidden units x 32 batch rows per workgroup
 //                         (weights + h_{t-1} through LDS, v_mfma_f32_16x16x4f32), gates, h_t; saves r, z, n, gh_n, h for the backward.
@@ -146,9 +148,23 @@ __global__ void __launch_bounds__(256) sgemm_kernel(const float *__restrict__ A,
         }
 }
 
-hipError_t gemm(hipStream_t s, bool ta, bool tb, const float *A, long lda, const float *B, long ldb, float *C, long ldc, int M, int N, int K,
+// Where the GEMMs of one call go, and how many were launched on which kernel (wrnn_train_last_gemms)
+struct GemmRun {
+    hipStream_t s;
+    int32_t *n_f32, *n_bf16;
+};
+
+// prec = WRNN_TRAIN_F32: sgemm_kernel; WRNN_TRAIN_BF16: gemm_bf16_kernel (train_gemm_bf16.hip), hipErrorNotSupported for its TT form
+hipError_t gemm(GemmRun &r, int prec, bool ta, bool tb, const float *A, long lda, const float *B, long ldb, float *C, long ldc, int M, int N, int K,
                 int beta = 0, const float *bias = nullptr, int relu = 0, int slices = 1, int kper = 0, long cslice = 0) {
     if (M <= 0 || N <= 0) return hipSuccess;
+    hipStream_t s = r.s;
+    if (prec == WRNN_TRAIN_BF16) {
+        const hipError_t e = wrnn_gemm_bf16_launch(s, ta, tb, A, lda, B, ldb, C, ldc, M, N, K, beta, bias, relu, slices, kper, cslice);
+        if (e == hipSuccess) ++*r.n_bf16;
+        return e;
+    }
+    ++*r.n_f32;
     dim3 grid((N + GT_N - 1) / GT_N, (M + GT_M - 1) / GT_M, slices);
     if (ta && tb) hipLaunchKernelGGL((sgemm_kernel<true, true>), grid, dim3(256), 0, s, A, lda, B, ldb, C, ldc, M, N, K, beta, bias, relu, kper, cslice);
     else if (ta) hipLaunchKernelGGL((sgemm_kernel<true, false>), grid, dim3(256), 0, s, A, lda, B, ldb, C, ldc, M, N, K, beta, bias, relu, kper, cslice);
@@ -209,6 +225,32 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(const float *__restr
     for (int sl = 0; sl < S; ++sl) acc += P[(size_t)sl * MN + i];
     const long m = i / N, n = i - m * N;
     C[m * ldc + n] = beta ? C[m * ldc + n] + acc : acc;
+}
+
+// Split-K wrapper.  The weight gradients dW = dOut^T . In contract over all B*L rows with a small output: K is split over slices so that
+// the launch fills the chip, and the partial products are summed in slice order (deterministic).
+// The wrapper's own choice of slices for an Mo x No output with room for sk_floats floats of partial products:
+int splitk_slices(int Mo, int No, size_t sk_floats) {
+    const int tiles = ((Mo + GT_M - 1) / GT_M) * ((No + GT_N - 1) / GT_N);
+    // slices x tiles <= TN_WG_TARGET workgroups, all co-resident (with ceil() 48 tiles x 6 slices = 288 workgroups ran as one full pass
+    // over 256 CUs + a 12 % second one)
+    int S = tiles >= TN_WG_TARGET / 2 ? 1 : TN_WG_TARGET / tiles;
+    if (S > 64) S = 64;
+    while (S > 1 && (size_t)S * Mo * No > sk_floats) --S;
+    return S;
+}
+// C (Mo x No) = (beta) C + A . B over K in S slices; S <= 1: one plain GEMM.  sk_part: S * Mo * No floats.  Either kernel (prec).
+hipError_t gemm_splitk(GemmRun &r, int prec, bool ta, bool tb, const float *Am, long lda, const float *Bm, long ldb, float *Cm, long ldc, int Mo,
+                       int No, long K, int beta, int S, float *sk_part) {
+    if (S <= 1) return gemm(r, prec, ta, tb, Am, lda, Bm, ldb, Cm, ldc, Mo, No, (int)K, beta);
+    if (Mo <= 0 || No <= 0) return hipSuccess;
+    const int kt = prec == WRNN_TRAIN_BF16 ? WRNN_GEMM_BF16_KTILE : GT_K;   // a slice is whole k tiles of the kernel that runs
+    const long per = ((K + S - 1) / S + kt - 1) / kt * kt;
+    // one launch, blockIdx.z = slice (slices past the end of K write zeros)
+    hipError_t e = gemm(r, prec, ta, tb, Am, lda, Bm, ldb, sk_part, No, Mo, No, (int)K, 0, nullptr, 0, S, (int)per, (long)Mo * No);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((long)Mo * No + 255) / 256)), dim3(256), 0, r.s, sk_part, S, (long)Mo * No, No, Cm, ldc, beta);
+    return hipGetLastError();
 }
 
 __device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
@@ -753,14 +795,20 @@ static int train_impl(wrnn_handle *h, int phase, const wrnn_loop_params *w, cons
                                  st->ctl, 2 * TEAM_CTL_WORDS * sizeof(unsigned), [&] { return wrnn_gru_team_launch(ta, nq, bwd, s); });
     };
     const float *a1 = aux_dev, *a2 = aux_dev + A, *a3 = aux_dev + 2 * A, *a4 = aux_dev + 3 * A;   // aux channel split (:198-199)
+    // The handle's precision (wrnn_train_set_precision) for every GEMM below but the two that read x_dev -- the forward rank-1 term of I and
+    // the gradient of I.weight[:, 0] -- which stay on the fp32 kernel: x is a 10-bit (RAW) or continuous (MOL) sample value, and 8
+    // significand bits would coarsen the network's own input near +-1; the two are 1/113 of I's work.  The recurrences keep fp32 W_hh.
+    const int P = h->train_precision;
+    h->train_n_f32 = h->train_n_bf16 = 0;
+    GemmRun gx{s, &h->train_n_f32, &h->train_n_bf16};
 
     // ================= forward (:146-167) =================
     if (do_fwd) {
     st->fwd_valid = false;
-    // x = I(cat[x, mels, a1])
-    T_TRY(gemm(s, false, true, x_dev, 1, w->I_w, IN_I, XI, H, M, H, 1, 0, w->I_b));
-    T_TRY(gemm(s, false, true, mels_up_dev, F, w->I_w + 1, IN_I, XI, H, M, H, F, 1));
-    T_TRY(gemm(s, false, true, a1, R, w->I_w + 1 + F, IN_I, XI, H, M, H, A, 1));
+    // x = I(cat[x, mels, a1]); the rank-1 term of the sample input stays on the fp32 kernel (see P above)
+    T_TRY(gemm(gx, WRNN_TRAIN_F32, false, true, x_dev, 1, w->I_w, IN_I, XI, H, M, H, 1, 0, w->I_b));
+    T_TRY(gemm(gx, P, false, true, mels_up_dev, F, w->I_w + 1, IN_I, XI, H, M, H, F, 1));
+    T_TRY(gemm(gx, P, false, true, a1, R, w->I_w + 1 + F, IN_I, XI, H, M, H, A, 1));
     auto recur_fwd = [&](int i) -> hipError_t {
         const Gru &q = gr[i];
         hipError_t e = hipMemsetAsync(q.HP, 0, nH * sizeof(float), s);   // h_{-1} = 0 (:141-142); rows t > 0 are overwritten
@@ -772,20 +820,20 @@ static int train_impl(wrnn_handle *h, int phase, const wrnn_loop_params *w, cons
         });
     };
     // rnn1 (:152-153)
-    T_TRY(gemm(s, false, true, XI, H, w->rnn1_w_ih, H, gr[0].GI, G, M, G, H, 0, w->rnn1_b_ih));
+    T_TRY(gemm(gx, P, false, true, XI, H, w->rnn1_w_ih, H, gr[0].GI, G, M, G, H, 0, w->rnn1_b_ih));
     T_TRY(recur_fwd(0));
     hipLaunchKernelGGL(add_kernel, dim3((unsigned)((nH + 255) / 256)), dim3(256), 0, s, XI, gr[0].H, X2, (long)nH);
     // rnn2 over cat[x, a2] (:155-158)
-    T_TRY(gemm(s, false, true, X2, H, w->rnn2_w_ih, H + A, gr[1].GI, G, M, G, H, 0, w->rnn2_b_ih));
-    T_TRY(gemm(s, false, true, a2, R, w->rnn2_w_ih + H, H + A, gr[1].GI, G, M, G, A, 1));
+    T_TRY(gemm(gx, P, false, true, X2, H, w->rnn2_w_ih, H + A, gr[1].GI, G, M, G, H, 0, w->rnn2_b_ih));
+    T_TRY(gemm(gx, P, false, true, a2, R, w->rnn2_w_ih + H, H + A, gr[1].GI, G, M, G, A, 1));
     T_TRY(recur_fwd(1));
     hipLaunchKernelGGL(add_kernel, dim3((unsigned)((nH + 255) / 256)), dim3(256), 0, s, X2, gr[1].H, X3, (long)nH);
     // fc1, fc2 (relu), fc3 (:160-166)
-    T_TRY(gemm(s, false, true, X3, H, w->fc1_w, H + A, F1, FC, M, FC, H, 0, w->fc1_b));
-    T_TRY(gemm(s, false, true, a3, R, w->fc1_w + H, H + A, F1, FC, M, FC, A, 1, nullptr, 1));
-    T_TRY(gemm(s, false, true, F1, FC, w->fc2_w, FC + A, F2, FC, M, FC, FC, 0, w->fc2_b));
-    T_TRY(gemm(s, false, true, a4, R, w->fc2_w + FC, FC + A, F2, FC, M, FC, A, 1, nullptr, 1));
-    T_TRY(gemm(s, false, true, F2, FC, w->fc3_w, FC, Y, NC, M, NC, FC, 0, w->fc3_b));
+    T_TRY(gemm(gx, P, false, true, X3, H, w->fc1_w, H + A, F1, FC, M, FC, H, 0, w->fc1_b));
+    T_TRY(gemm(gx, P, false, true, a3, R, w->fc1_w + H, H + A, F1, FC, M, FC, A, 1, nullptr, 1));
+    T_TRY(gemm(gx, P, false, true, F1, FC, w->fc2_w, FC + A, F2, FC, M, FC, FC, 0, w->fc2_b));
+    T_TRY(gemm(gx, P, false, true, a4, R, w->fc2_w + FC, FC + A, F2, FC, M, FC, A, 1, nullptr, 1));
+    T_TRY(gemm(gx, P, false, true, F2, FC, w->fc3_w, FC, Y, NC, M, NC, FC, 0, w->fc3_b));
     if (y_dev && loss_out_dev)
         if (int rc = wrnn_loss(h, Y, y_dev, M, loss_out_dev, stream)) return rc;
     st->fwd_valid = true;
@@ -807,42 +855,29 @@ static int train_impl(wrnn_handle *h, int phase, const wrnn_loop_params *w, cons
         hipLaunchKernelGGL(col_sum_part_kernel, dim3((N + 63) / 64, CS_CHUNKS), dim3(256), 0, s, Am, lda, M, N, cs_part);
         hipLaunchKernelGGL(col_sum_final_kernel, dim3((N + 255) / 256), dim3(256), 0, s, cs_part, N, out);
     };
-    // weight gradients dW = dOut^T . In contract over all B*L rows with a small output: split K over slices so that the launch fills
-    // the chip, partial products summed in slice order (deterministic)
-    auto gemm_tn = [&](const float *Am, long lda, const float *Bm, long ldb, float *Cm, long ldc, int Mo, int No) -> hipError_t {
-        const int tiles = ((Mo + GT_M - 1) / GT_M) * ((No + GT_N - 1) / GT_N);
-        // slices x tiles <= TN_WG_TARGET workgroups, all co-resident (with ceil() 48 tiles x 6 slices = 288 workgroups ran as one full pass
-        // over 256 CUs + a 12 % second one)
-        int S = tiles >= TN_WG_TARGET / 2 ? 1 : TN_WG_TARGET / tiles;
-        if (S > 64) S = 64;
-        while (S > 1 && (size_t)S * Mo * No > sk_floats) --S;
-        if (S <= 1) return gemm(s, true, false, Am, lda, Bm, ldb, Cm, ldc, Mo, No, (int)M);
-        const long per = ((M + S - 1) / S + GT_K - 1) / GT_K * GT_K;
-        // one launch, blockIdx.z = slice (slices past the end of K write zeros)
-        hipError_t e = gemm(s, true, false, Am, lda, Bm, ldb, sk_part, No, Mo, No, (int)M, 0, nullptr, 0, S, (int)per, (long)Mo * No);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((long)Mo * No + 255) / 256)), dim3(256), 0, s, sk_part, S, (long)Mo * No, No, Cm, ldc, 0);
-        return hipGetLastError();
+    // weight gradients dW = dOut^T . In: the split-K wrapper (gemm_splitk), on the kernel `prec` names
+    auto gemm_tn = [&](int prec, const float *Am, long lda, const float *Bm, long ldb, float *Cm, long ldc, int Mo, int No) -> hipError_t {
+        return gemm_splitk(gx, prec, true, false, Am, lda, Bm, ldb, Cm, ldc, Mo, No, M, 0, splitk_slices(Mo, No, sk_floats), sk_part);
     };
     const unsigned eb_f = (unsigned)((nF + 255) / 256);
     // fc3
-    T_TRY(gemm_tn(dY, NC, F2, FC, g->fc3_w, FC, NC, FC));
+    T_TRY(gemm_tn(P, dY, NC, F2, FC, g->fc3_w, FC, NC, FC));
     colsum(dY, NC, NC, g->fc3_b);
-    T_TRY(gemm(s, false, false, dY, NC, w->fc3_w, FC, dF2, FC, M, FC, NC));
+    T_TRY(gemm(gx, P, false, false, dY, NC, w->fc3_w, FC, dF2, FC, M, FC, NC));
     hipLaunchKernelGGL(relu_bwd_kernel, dim3(eb_f), dim3(256), 0, s, dF2, F2, (long)nF);
     // fc2 over cat[F1, a4]
-    T_TRY(gemm_tn(dF2, FC, F1, FC, g->fc2_w, FC + A, FC, FC));
-    T_TRY(gemm_tn(dF2, FC, a4, R, g->fc2_w + FC, FC + A, FC, A));
+    T_TRY(gemm_tn(P, dF2, FC, F1, FC, g->fc2_w, FC + A, FC, FC));
+    T_TRY(gemm_tn(P, dF2, FC, a4, R, g->fc2_w + FC, FC + A, FC, A));
     colsum(dF2, FC, FC, g->fc2_b);
-    T_TRY(gemm(s, false, false, dF2, FC, w->fc2_w, FC + A, dF1, FC, M, FC, FC));
-    if (d_aux_dev) T_TRY(gemm(s, false, false, dF2, FC, w->fc2_w + FC, FC + A, d_aux_dev + 3 * A, R, M, A, FC));
+    T_TRY(gemm(gx, P, false, false, dF2, FC, w->fc2_w, FC + A, dF1, FC, M, FC, FC));
+    if (d_aux_dev) T_TRY(gemm(gx, P, false, false, dF2, FC, w->fc2_w + FC, FC + A, d_aux_dev + 3 * A, R, M, A, FC));
     hipLaunchKernelGGL(relu_bwd_kernel, dim3(eb_f), dim3(256), 0, s, dF1, F1, (long)nF);
     // fc1 over cat[X3, a3]
-    T_TRY(gemm_tn(dF1, FC, X3, H, g->fc1_w, H + A, FC, H));
-    T_TRY(gemm_tn(dF1, FC, a3, R, g->fc1_w + H, H + A, FC, A));
+    T_TRY(gemm_tn(P, dF1, FC, X3, H, g->fc1_w, H + A, FC, H));
+    T_TRY(gemm_tn(P, dF1, FC, a3, R, g->fc1_w + H, H + A, FC, A));
     colsum(dF1, FC, FC, g->fc1_b);
-    T_TRY(gemm(s, false, false, dF1, FC, w->fc1_w, H + A, dX3, H, M, H, FC));
-    if (d_aux_dev) T_TRY(gemm(s, false, false, dF1, FC, w->fc1_w + H, H + A, d_aux_dev + 2 * A, R, M, A, FC));
+    T_TRY(gemm(gx, P, false, false, dF1, FC, w->fc1_w, H + A, dX3, H, M, H, FC));
+    if (d_aux_dev) T_TRY(gemm(gx, P, false, false, dF1, FC, w->fc1_w + H, H + A, d_aux_dev + 2 * A, R, M, A, FC));
     auto recur_bwd = [&](int i, const float *dHext) -> hipError_t {
         const Gru &q = gr[i];
         if (use_team) return recur_team(i, true, dHext);
@@ -855,29 +890,29 @@ static int train_impl(wrnn_handle *h, int phase, const wrnn_loop_params *w, cons
     };
     // rnn2: h2 enters x3 = x2 + h2, so dH2(ext) = dX3
     T_TRY(recur_bwd(1, dX3));
-    T_TRY(gemm_tn(gr[1].dGI, G, X2, H, g->rnn2_w_ih, H + A, G, H));
-    T_TRY(gemm_tn(gr[1].dGI, G, a2, R, g->rnn2_w_ih + H, H + A, G, A));
-    T_TRY(gemm_tn(gr[1].dGH, G, gr[1].HP, H, g->rnn2_w_hh, H, G, H));
+    T_TRY(gemm_tn(P, gr[1].dGI, G, X2, H, g->rnn2_w_ih, H + A, G, H));
+    T_TRY(gemm_tn(P, gr[1].dGI, G, a2, R, g->rnn2_w_ih + H, H + A, G, A));
+    T_TRY(gemm_tn(P, gr[1].dGH, G, gr[1].HP, H, g->rnn2_w_hh, H, G, H));
     colsum(gr[1].dGI, G, G, g->rnn2_b_ih);
     colsum(gr[1].dGH, G, G, g->rnn2_b_hh);
     T_TRY(hipMemcpyAsync(dX2, dX3, nH * sizeof(float), hipMemcpyDeviceToDevice, s));        // residual x3 = x2 + h2
-    T_TRY(gemm(s, false, false, gr[1].dGI, G, w->rnn2_w_ih, H + A, dX2, H, M, H, G, 1));
-    if (d_aux_dev) T_TRY(gemm(s, false, false, gr[1].dGI, G, w->rnn2_w_ih + H, H + A, d_aux_dev + A, R, M, A, G));
+    T_TRY(gemm(gx, P, false, false, gr[1].dGI, G, w->rnn2_w_ih, H + A, dX2, H, M, H, G, 1));
+    if (d_aux_dev) T_TRY(gemm(gx, P, false, false, gr[1].dGI, G, w->rnn2_w_ih + H, H + A, d_aux_dev + A, R, M, A, G));
     // rnn1
     T_TRY(recur_bwd(0, dX2));
-    T_TRY(gemm_tn(gr[0].dGI, G, XI, H, g->rnn1_w_ih, H, G, H));
-    T_TRY(gemm_tn(gr[0].dGH, G, gr[0].HP, H, g->rnn1_w_hh, H, G, H));
+    T_TRY(gemm_tn(P, gr[0].dGI, G, XI, H, g->rnn1_w_ih, H, G, H));
+    T_TRY(gemm_tn(P, gr[0].dGH, G, gr[0].HP, H, g->rnn1_w_hh, H, G, H));
     colsum(gr[0].dGI, G, G, g->rnn1_b_ih);
     colsum(gr[0].dGH, G, G, g->rnn1_b_hh);
     T_TRY(hipMemcpyAsync(dXI, dX2, nH * sizeof(float), hipMemcpyDeviceToDevice, s));        // residual x2 = xI + h1
-    T_TRY(gemm(s, false, false, gr[0].dGI, G, w->rnn1_w_ih, H, dXI, H, M, H, G, 1));
+    T_TRY(gemm(gx, P, false, false, gr[0].dGI, G, w->rnn1_w_ih, H, dXI, H, M, H, G, 1));
     // I over cat[x, mels, a1]
-    T_TRY(gemm_tn(dXI, H, x_dev, 1, g->I_w, IN_I, H, 1));
-    T_TRY(gemm_tn(dXI, H, mels_up_dev, F, g->I_w + 1, IN_I, H, F));
-    T_TRY(gemm_tn(dXI, H, a1, R, g->I_w + 1 + F, IN_I, H, A));
+    T_TRY(gemm_tn(WRNN_TRAIN_F32, dXI, H, x_dev, 1, g->I_w, IN_I, H, 1));   // the gradient of I.weight[:, 0]: fp32, like the forward term
+    T_TRY(gemm_tn(P, dXI, H, mels_up_dev, F, g->I_w + 1, IN_I, H, F));
+    T_TRY(gemm_tn(P, dXI, H, a1, R, g->I_w + 1 + F, IN_I, H, A));
     colsum(dXI, H, H, g->I_b);
-    if (d_mels_up_dev) T_TRY(gemm(s, false, false, dXI, H, w->I_w + 1, IN_I, d_mels_up_dev, F, M, F, H));
-    if (d_aux_dev) T_TRY(gemm(s, false, false, dXI, H, w->I_w + 1 + F, IN_I, d_aux_dev, R, M, A, H));
+    if (d_mels_up_dev) T_TRY(gemm(gx, P, false, false, dXI, H, w->I_w + 1, IN_I, d_mels_up_dev, F, M, F, H));
+    if (d_aux_dev) T_TRY(gemm(gx, P, false, false, dXI, H, w->I_w + 1 + F, IN_I, d_aux_dev, R, M, A, H));
     T_TRY(hipGetLastError());
     return WRNN_OK;
 }
@@ -928,6 +963,62 @@ extern "C" int wrnn_train_last_recurrence(const wrnn_handle *h, int32_t *kernel,
     if (h->train_last_kernel < 0) return WRNN_ERR_STATE;
     if (kernel) *kernel = h->train_last_kernel;
     if (rows_per_team) *rows_per_team = h->train_last_rows;
+    return WRNN_OK;
+}
+
+// which kernel the batched GEMMs of the following training calls on h run on (the two GEMMs on x_dev and the recurrences stay fp32)
+extern "C" int wrnn_train_set_precision(wrnn_handle *h, int32_t fmt) {
+    if (!h) return WRNN_ERR_INVALID;
+    if (fmt != WRNN_TRAIN_F32 && fmt != WRNN_TRAIN_BF16)
+        return tfail(h, WRNN_ERR_INVALID, "wrnn_train_set_precision: %d is neither WRNN_TRAIN_F32 nor WRNN_TRAIN_BF16", fmt);
+    h->train_precision = fmt;
+    return WRNN_OK;
+}
+
+extern "C" int wrnn_train_precision(const wrnn_handle *h, int32_t *fmt) {
+    if (!h || !fmt) return WRNN_ERR_INVALID;
+    *fmt = h->train_precision;
+    return WRNN_OK;
+}
+
+// GEMM launches of the last training call on h, by kernel (host-side counts; a split-K product is one launch)
+extern "C" int wrnn_train_last_gemms(const wrnn_handle *h, int32_t *n_f32, int32_t *n_bf16) {
+    if (!h) return WRNN_ERR_INVALID;
+    if (h->train_n_f32 < 0) return WRNN_ERR_STATE;
+    if (n_f32) *n_f32 = h->train_n_f32;
+    if (n_bf16) *n_bf16 = h->train_n_bf16;
+    return WRNN_OK;
+}
+
+// developer / test entry: one product through gemm() and gemm_splitk() -- the dispatcher and the split-K wrapper train_impl uses -- on the
+// caller's device buffers, with `precision` taken literally (no x_dev rule).  slices: 1 = no split, 0 = the wrapper's own choice,
+// 2..64 = that many; a split product has no bias / relu (as in train_impl) and sums its partials from a temporary of its own, which
+// this call frees after waiting for the stream.
+extern "C" int wrnn_debug_train_gemm(wrnn_handle *h, int32_t precision, int32_t ta, int32_t tb, const float *A, int64_t lda, const float *B,
+                                     int64_t ldb, float *C, int64_t ldc, int32_t M, int32_t N, int32_t K, int32_t beta, const float *bias,
+                                     int32_t relu, int32_t slices, void *stream) {
+    if (!h) return WRNN_ERR_INVALID;
+    if (precision != WRNN_TRAIN_F32 && precision != WRNN_TRAIN_BF16) return tfail(h, WRNN_ERR_INVALID, "wrnn_debug_train_gemm: bad precision %d", precision);
+    if (!A || !B || !C || M < 1 || N < 1 || K < 0 || lda < 1 || ldb < 1 || ldc < N || slices < 0 || slices > 64)
+        return tfail(h, WRNN_ERR_INVALID, "wrnn_debug_train_gemm: bad arguments");
+    if ((ta ? lda < M : lda < K) || (tb ? ldb < K : ldb < N)) return tfail(h, WRNN_ERR_INVALID, "wrnn_debug_train_gemm: a leading dimension is shorter than its row");
+    if (slices != 1 && (bias || relu)) return tfail(h, WRNN_ERR_INVALID, "wrnn_debug_train_gemm: a split product takes no bias and no relu");
+    if (precision == WRNN_TRAIN_BF16 && ta && tb) return tfail(h, WRNN_ERR_UNSUPPORTED, "wrnn_debug_train_gemm: the bf16 kernel has no TT form");
+    T_TRY(hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    int32_t n32 = 0, n16 = 0;
+    GemmRun gx{s, &n32, &n16};
+    if (slices == 1) {
+        T_TRY(gemm(gx, precision, ta != 0, tb != 0, A, lda, B, ldb, C, ldc, M, N, K, beta != 0, bias, relu != 0));
+        return WRNN_OK;
+    }
+    const int S = slices ? slices : splitk_slices(M, N, (size_t)64 * M * N);
+    float *part = nullptr;
+    if (S > 1) T_TRY(hipMalloc(&part, (size_t)S * M * N * sizeof(float)));
+    hipError_t e = gemm_splitk(gx, precision, ta != 0, tb != 0, A, lda, B, ldb, C, ldc, M, N, K, beta != 0, S, part);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (part) (void)hipFree(part);
+    T_TRY(e);
     return WRNN_OK;
 }
 

@@ -137,6 +137,8 @@ struct wrnn_handle {
     WrnnTrainState *train = nullptr;
     bool train_force_steps = false;   // wrnn_train_force_step_kernels
     int32_t train_last_kernel = -1, train_last_rows = 0;   // what the recurrences of the last training call ran (wrnn_train_last_recurrence); -1 = none yet
+    int32_t train_precision = 0;      // WRNN_TRAIN_F32 / WRNN_TRAIN_BF16 (wrnn_train_set_precision): which kernel the GEMMs of training run on
+    int32_t train_n_f32 = -1, train_n_bf16 = -1;   // GEMM launches of the last training call by kernel (wrnn_train_last_gemms); -1 = none yet
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     bool timing_valid = false;
     wrnn_timing last{};
@@ -354,6 +356,12 @@ size_t wrnn_gru_team_mail_granules(int nq, bool bwd);
 hipError_t wrnn_gru_team_pack(const float *Whh, float *img, bool bwd, hipStream_t s);
 hipError_t wrnn_gru_team_launch(const WrnnGruTeamArgs &a, int nq, bool bwd, hipStream_t s);
 hipError_t wrnn_gru_team_occupancy(int nq, bool bwd, int *blocks_per_cu);
+
+// The batched GEMM of wrnn_train_step with operands rounded to bfloat16 on their way into LDS (train_gemm_bf16.hip): sgemm_kernel's
+// arguments (train.hip), NT / NN / TN; hipErrorNotSupported for TT.  A split-K slice is a multiple of WRNN_GEMM_BF16_KTILE.
+#define WRNN_GEMM_BF16_KTILE 32
+hipError_t wrnn_gemm_bf16_launch(hipStream_t s, bool ta, bool tb, const float *A, long lda, const float *B, long ldb, float *C, long ldc, int M,
+                                 int N, int K, int beta, const float *bias, int relu, int slices, int kper, long cslice);
 
 // kernels / launchers (defined in the .hip files)
 // mel_T = frames per row of `mels`, mel_off = index of frame 0 in it: (T, 0) for generate()'s unpadded mels (zero

@@ -271,6 +271,9 @@ def build_parser():
     add_features_argument(parser, 'the --wav_dir files; a saved corpus (hp.feature_path) must hold the same ones')
     parser.add_argument('--resident', action='store_true', help='load the corpus of hp.feature_path onto the device once instead of reading '
                                                                 '.npy files every iteration')
+    parser.add_argument('--train-precision', dest='train_precision', choices=('f32', 'bf16'), default='f32',
+                        help="precision of the loop layers' batched GEMMs: f32 (default), or bf16 operands on the matrix cores with fp32 "
+                             'accumulators (WaveRNN.train_precision; parameters, recurrences and losses stay fp32)')
     parser.add_argument('--total_steps', type=int, help='override hp.voc_total_steps')
     parser.add_argument('--reference_body', action='store_true',
                         help="run the reference's loop body (model(x, m) + torch loss) instead of the fused training_loss")
@@ -295,6 +298,7 @@ def main(argv=None):
         raise ValueError('voc_upsample_factors must factorise hop_length')
     paths = VocPaths('.')
     model = build_model_from_hparams().to(torch.device('cuda'))
+    model.train_precision = args.train_precision
     optimizer = torch.optim.Adam(model.parameters())
     restore_checkpoint(paths, model, optimizer, create_if_missing=True)
     kw = dict(mode=hp.voc_mode, bits=hp.bits, hop_length=hp.hop_length, pad=hp.voc_pad, seq_len=hp.voc_seq_len)
@@ -323,7 +327,7 @@ def main(argv=None):
         loader = DeviceWindowLoader(train, hp.voc_batch_size, **kw)
     total = args.total_steps if args.total_steps is not None else hp.voc_total_steps
     print(f'Remaining {total - model.get_step()} steps | batch {hp.voc_batch_size} | lr {hp.voc_lr} | seq_len {hp.voc_seq_len} | '
-          f'{len(train)} training utterances')
+          f'{len(train)} training utterances | GEMMs in {model.train_precision}')
     loss_func = None
     if args.reference_body:
         if hp.voc_mode != 'RAW':

@@ -283,6 +283,7 @@ class WaveRNN(nn.Module):
         # knobs that are not part of the reference signature
         self.kernel = _cabi.KERNEL_AUTO
         self._teamg_weights = 'f32'       # see the property teamg_weights
+        self._train_precision = 'f32'     # see the property train_precision
         # True: every training call (training_loss, forward / backward in train() mode) waits for its kernels and raises on a device-side
         # error (a busy GPU, a timed-out team kernel) -- safe, but the host cannot queue the rest of the iteration (the upsample network's
         # backward, clipping, Adam: ~150 small launches) under the running step.  'deferred': no wait; the caller asks once per iteration
@@ -336,6 +337,24 @@ class WaveRNN(nn.Module):
         if self._native is not None:
             self._native.set_teamg_weights(fmt)
 
+    @property
+    def train_precision(self) -> str:
+        """Precision of the batched GEMMs of training (``forward`` in ``train()`` mode, ``training_loss``, both autograd functions):
+        ``'f32'`` (default) or ``'bf16'``.  With ``'bf16'`` every operand of those GEMMs -- forward, input gradients, weight gradients --
+        is rounded once to bfloat16 (nearest even) on its way to the matrix cores; accumulators, parameters, activations in memory,
+        biases, losses, the sample input's column of ``I`` and both recurrences stay fp32, and bfloat16's fp32 exponent range needs no
+        loss scaling.  The setting belongs to the model like ``teamg_weights``: it survives ``invalidate_native`` and ``.to()`` and is
+        applied when the native handle is made.  ``training_status()`` reports it."""
+        return self._train_precision
+
+    @train_precision.setter
+    def train_precision(self, precision: str):
+        if precision not in _cabi.TRAIN_PRECISIONS:
+            raise ValueError(f"train_precision must be 'f32' or 'bf16', not {precision!r}")
+        self._train_precision = precision
+        if self._native is not None:
+            self._native.set_train_precision(precision)
+
     def invalidate_native(self):
         """Force the next ``generate`` to repack the weights into the native handle."""
         self._native_key = None
@@ -349,6 +368,7 @@ class WaveRNN(nn.Module):
                 self._native.close()
             self._native = _cabi.NativeVocoder(device=dev, **self._ctor)
             self._native.set_teamg_weights(self._teamg_weights)
+            self._native.set_train_precision(self._train_precision)
             self._native_key = None
         return self._native
 
@@ -361,6 +381,7 @@ class WaveRNN(nn.Module):
                 self._native.close()
             self._native = _cabi.NativeVocoder(device=dev, **self._ctor)
             self._native.set_teamg_weights(self._teamg_weights)
+            self._native.set_train_precision(self._train_precision)
             self._native_key = None
         if self._native_key != key:
             sd = {k: v.detach().cpu().numpy() for k, v in self.state_dict().items()}
@@ -475,12 +496,19 @@ class WaveRNN(nn.Module):
     def training_status(self):
         """Waits for the model's stream and raises ``WrnnError`` if a training kernel launched since the last forward pass reported a
         device-side error (``wrnn_sync_status``).  For ``check_device_errors = 'deferred'``: call it once per iteration, before the weights
-        of that iteration are trusted (written to a checkpoint)."""
+        of that iteration are trusted (written to a checkpoint).  Returns ``dict(train_precision=..., gemms=...)``: the precision the
+        training GEMMs run in (the handle's, where there is one) and ``(on the fp32 kernel, on the bf16 kernel)`` of the last training
+        call, ``None`` before any."""
         dev = next(self.parameters()).device
         if dev.type != 'cuda' or self._native is None:
-            return
+            return dict(train_precision=self._train_precision, gemms=None)
         with torch.cuda.device(dev):
             self._native.sync_status(torch.cuda.current_stream(dev).cuda_stream)
+        try:
+            gemms = self._native.train_last_gemms()
+        except _cabi.WrnnError:
+            gemms = None
+        return dict(train_precision=self._native.train_precision, gemms=gemms)
 
     # ---------------------------------------------------------------- generate
     def generate_raw(self, mels, batched, target, overlap, *, noise_mode=_cabi.NOISE_PHILOX, seed=None,
