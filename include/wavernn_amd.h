@@ -704,6 +704,70 @@ int wrnn_condition(const float *wav_dev, int64_t n_max, const int32_t *n_dev, in
                    int32_t hop, float peak_target, double *energy_ws_dev, int32_t F_max, float *out_dev, int64_t n_out_max,
                    int32_t *n_out_dev, int32_t *bounds_dev, float *peak_dev, void *stream);
 
+/* ---- Griffin-Lim (new entry points in ABI 9 again, and one new struct; nothing existing changes): [0, 1] mel -> wav with no trained
+ * model, the inverse of the mel front end in either feature profile.  The chain is inv_mel_spectrogram of tacotron/datasets/audio.py:
+ * 122-137, 176-186, 203-210, 256-260 (wavernn/utils/dsp.py:105-116 has a variant).  With the fields of wrnn_mel_config and
+ * wrnn_mel_features above, for one mel column m of a clip of T frames:
+ *   a. undo steps 7, 6 and 4 of the profile:  A = max_abs_value > 0: sym = clip(2 A m - A, -A, A),
+ *                                               S_db = (sym + A) (-min_level_db) / (2 A) + min_level_db;
+ *                                             A == 0: S_db = clip(m, 0, 1) (-min_level_db) + min_level_db;
+ *                                             a = 10^((S_db + ref_level_db) / 20), then a^(1 / magnitude_power);
+ *      lin = max(1e-10, P a), S = lin^power, with P the (n_fft/2 + 1) x n_mels pseudo-inverse of the profile's filterbank,
+ *      P = B^T (B B^T)^-1 by a Cholesky factorisation of the Gram matrix, built in the create entry in float64 and kept in float64.
+ *   b. first round: Z = S exp(2 pi i r), r per (frame, bin) zero, injected, or drawn on the device (below); y = istft(Z).
+ *   c. n_iter rounds: X = stft(y), u = X / |X| (1 where |X| == 0), y = istft(S u).
+ *   d. de-emphasis with k = preemphasis: out[i] = y[i] + k out[i-1] (k == 0: none).
+ * stft is the profile's own (the window of win_length centred in n_fft, hop_length, frame t reads y at t hop - n_fft/2 + i, zeros or the
+ * reflection outside the clip by pad_mode; the reflection repeats for a clip shorter than the pad, like numpy's).  istft is
+ * librosa.istft with center=True: the inverse transforms times the window, overlap-added in ascending frame order, divided by the
+ * window-sum-square where that exceeds FLT_MIN, and cut to the hop (T - 1) samples behind the first n_fft/2.  A clip of one frame is empty.
+ * irfft reads the real parts of bins 0 and n_fft/2 only, as numpy's does.  The mel, the injected phases and the wav are float32;
+ * everything between them is float64 (P, the window, the twiddles, S, the transforms, the frames and the wave between rounds, the
+ * de-emphasis), rounded to float32 once per output sample: the rounds amplify rounding where a bin of the wave's spectrum passes near
+ * zero, and a float32 chain drifts from the float64 one by far more than its one-round error.  Sums are gathers in a fixed order: two calls give the same bits, and a clip of a
+ * ragged batch equals the call on it alone bit for bit.
+ * The create entry touches no device.  It refuses what wrnn_mel_create_features refuses, a struct_size other than
+ * sizeof(wrnn_griffin_config), power <= 0 and n_iter_default < 0 (WRNN_ERR_INVALID); n_fft != 2048, a filterbank with an empty row or
+ * without full row rank (its Gram matrix does not factorise) are WRNN_ERR_UNSUPPORTED.  A refused handle is still returned, for its
+ * error text and the destroy entry. */
+#define WRNN_GRIFFIN_PHASE_ZERO 0      /* r = 0 */
+#define WRNN_GRIFFIN_PHASE_PHILOX 1    /* r = the counter RNG's uniform in (0, 1) keyed (seed; frame, clip, bin): step = frame, row = clip,
+                                        * element = bin of the generate entries' Philox4x32-10 stream */
+#define WRNN_GRIFFIN_PHASE_INJECTED 2  /* r = phases_dev (B, T_max, n_fft/2 + 1) */
+typedef struct wrnn_griffin_handle wrnn_griffin_handle;
+typedef struct wrnn_griffin_config {
+    uint32_t struct_size;    /* sizeof(wrnn_griffin_config) */
+    float power;             /* 1.5: the exponent on the linear magnitudes (tacotron_hparams.py `power`) */
+    int32_t n_iter_default;  /* 60: the rounds of a call with n_iter < 0 */
+} wrnn_griffin_config;
+int wrnn_griffin_create(const wrnn_mel_config *cfg, const wrnn_mel_features *features, const wrnn_griffin_config *griffin,
+                        wrnn_griffin_handle **out);
+/* Host only: hop_length (frames - 1), the samples of a clip of `frames` >= 1 mel frames; WRNN_ERR_INVALID (< 0) otherwise. */
+int64_t wrnn_griffin_samples(const wrnn_griffin_handle *h, int64_t frames);
+/* Host only (tests): pinv[(n_fft/2 + 1) * n_mels] = P row-major, window[win_length], and window_sumsquare[n_fft + hop (frames - 1)] =
+ * the sum of the squared window over the frames that cover each position of the padded signal, summed as the overlap-add launch sums
+ * it; all three are the float64 tables the kernels read, rounded to float32 here.  Any pointer may be NULL; `frames` is read for
+ * window_sumsquare only. */
+int wrnn_griffin_tables(const wrnn_griffin_handle *h, float *pinv, float *window, int32_t frames, float *window_sumsquare);
+/* mel_dev (B, n_mels, T_max) float32 in [0, 1], the layout wrnn_melspectrogram writes and wrnn_generate reads; frames_dev: B int32 on the
+ * device, the clips' own frame counts (ragged; read as clamped to 0 .. T_max).  n_iter < 0: the handle's n_iter_default.  phases_dev goes
+ * with WRNN_GRIFFIN_PHASE_INJECTED and is NULL otherwise.  wav_out_dev (B, n_out_max) float32, n_out_max >= max(1, hop (T_max - 1)):
+ * row b holds the hop (frames[b] - 1) samples of clip b and ZEROS from there on.  magnitude_out_dev: NULL, or (B, T_max, n_fft/2 + 1)
+ * for S of step a (zero rows past a clip's own frames).  1 + 2 (1 + n_iter) + 1 launches (the last is the de-emphasis), asynchronous
+ * on `stream`; nothing waits on the host and nothing is captured.  The handle owns the workspaces (S, the windowed frames, the wave)
+ * and grows them when a call needs more -- the one case in which a call waits for `stream` -- so calls on ONE handle must be ordered by
+ * the caller, as for a profile mel handle.  The tables are uploaded by the first call (one blocking copy). */
+int wrnn_griffin_lim(wrnn_griffin_handle *h, const float *mel_dev, const int32_t *frames_dev, int32_t B, int32_t T_max, int32_t n_iter,
+                     int32_t phase_mode, uint64_t seed, const float *phases_dev, float *wav_out_dev, int64_t n_out_max,
+                     float *magnitude_out_dev, void *stream);
+/* inv_preemphasis on its own, no handle (like wrnn_condition): out[b, i] = wav[b, i] + k out[b, i-1] for i < n_dev[b] (a value above
+ * n_max is read as n_max, a negative one as 0), zeros from there to n_max; both buffers (B, n_max) float32, in place allowed.  The
+ * recurrence runs in float64 as a blocked scan and is rounded to float32 once per sample.  One launch, one workgroup per clip.
+ * WRNN_ERR_INVALID: |k| >= 1 or not finite, B outside 1 .. 65535, n_max < 1, a NULL pointer. */
+int wrnn_deemphasis(const float *wav_dev, int64_t n_max, const int32_t *n_dev, int32_t B, double k, float *out_dev, void *stream);
+const char *wrnn_griffin_last_error(const wrnn_griffin_handle *h);
+void wrnn_griffin_destroy(wrnn_griffin_handle *h);
+
 #ifdef __cplusplus
 }
 #endif

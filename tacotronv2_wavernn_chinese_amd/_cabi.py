@@ -44,7 +44,9 @@ EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wr
                     'wrnn_resample_destroy', 'wrnn_condition_frames', 'wrnn_condition', 'wrnn_teamg_plan', 'wrnn_debug_teamg_lds_budget',
                     'wrnn_teamg_batch_plan', 'wrnn_last_batch_rows', 'wrnn_teamg_set_weight_format', 'wrnn_teamg_weight_format',
                     'wrnn_teamg_plan_fmt', 'wrnn_train_last_recurrence', 'wrnn_train_teamg_plan',
-                    'wrnn_train_set_precision', 'wrnn_train_precision', 'wrnn_train_last_gemms', 'wrnn_debug_train_gemm')
+                    'wrnn_train_set_precision', 'wrnn_train_precision', 'wrnn_train_last_gemms', 'wrnn_debug_train_gemm',
+                    'wrnn_griffin_create', 'wrnn_griffin_samples', 'wrnn_griffin_tables', 'wrnn_griffin_lim', 'wrnn_deemphasis',
+                    'wrnn_griffin_last_error', 'wrnn_griffin_destroy')
 
 
 def epilogue_tables(n_classes: int, overlap: int, hop: int):
@@ -119,6 +121,17 @@ class MelFeatures(C.Structure):
     def __init__(self, pad_mode=0, magnitude_power=1, fmax=0.0, ref_level_db=0.0, preemphasis=0.0, preemph_rescale=0.0, max_abs_value=0.0):
         super().__init__(C.sizeof(MelFeatures), int(pad_mode), int(magnitude_power), float(fmax), float(ref_level_db), float(preemphasis),
                          float(preemph_rescale), float(max_abs_value))
+
+
+GRIFFIN_PHASE_ZERO, GRIFFIN_PHASE_PHILOX, GRIFFIN_PHASE_INJECTED = 0, 1, 2   # WRNN_GRIFFIN_PHASE_*
+
+
+class GriffinConfig(C.Structure):
+    """``wrnn_griffin_config``."""
+    _fields_ = [('struct_size', C.c_uint32), ('power', C.c_float), ('n_iter_default', C.c_int32)]
+
+    def __init__(self, power=1.5, n_iter_default=60):
+        super().__init__(C.sizeof(GriffinConfig), float(power), int(n_iter_default))
 
 
 WEIGHT_FORMATS = {'f32': 0, 'f16': 1}   # WRNN_WEIGHTS_*: the element type of the TEAMG / TEAMG_BATCH weight image
@@ -399,6 +412,20 @@ def load_library() -> C.CDLL:
     lib.wrnn_condition.argtypes = [vp, C.c_int64, vp, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_float, vp, C.c_int32, vp,
                                    C.c_int64, vp, vp, vp, vp]
     lib.wrnn_condition.restype = C.c_int
+    lib.wrnn_griffin_create.argtypes = [C.POINTER(MelConfig), C.POINTER(MelFeatures), C.POINTER(GriffinConfig), C.POINTER(vp)]
+    lib.wrnn_griffin_create.restype = C.c_int
+    lib.wrnn_griffin_samples.argtypes = [vp, C.c_int64]
+    lib.wrnn_griffin_samples.restype = C.c_int64
+    lib.wrnn_griffin_tables.argtypes = [vp, vp, vp, C.c_int32, vp]
+    lib.wrnn_griffin_tables.restype = C.c_int
+    lib.wrnn_griffin_lim.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, vp, vp, C.c_int64, vp, vp]
+    lib.wrnn_griffin_lim.restype = C.c_int
+    lib.wrnn_deemphasis.argtypes = [vp, C.c_int64, vp, C.c_int32, C.c_double, vp, vp]
+    lib.wrnn_deemphasis.restype = C.c_int
+    lib.wrnn_griffin_last_error.argtypes = [vp]
+    lib.wrnn_griffin_last_error.restype = C.c_char_p
+    lib.wrnn_griffin_destroy.argtypes = [vp]
+    lib.wrnn_griffin_destroy.restype = None
     lib.wrnn_quantise.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp]
     lib.wrnn_quantise.restype = C.c_int
     lib.wrnn_collate_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -893,6 +920,70 @@ class NativeMel:
             self.close()
         except Exception:
             pass
+
+
+class NativeGriffinLim:
+    """Owner of one ``wrnn_griffin_handle`` (mel -> wav by Griffin-Lim; no weights).  Creating it touches no device; a configuration the
+    library refuses raises ``ValueError`` (n_fft other than 2048 or a filterbank that cannot be inverted: WRNN_ERR_UNSUPPORTED; the rest:
+    WRNN_ERR_INVALID).  ``features``: a ``MelFeatures``; ``griffin``: a ``GriffinConfig``."""
+
+    def __init__(self, *, sample_rate, n_fft, hop_length, win_length, n_mels, fmin, min_level_db, device: int = 0, features=None, griffin=None):
+        self.lib = load_library()
+        cfg = MelConfig(int(sample_rate), int(n_fft), int(hop_length), int(win_length), int(n_mels), float(fmin), float(min_level_db), int(device))
+        self.cfg = cfg
+        self.features = features if features is not None else MelFeatures()
+        self.griffin = griffin if griffin is not None else GriffinConfig()
+        self.device = int(device)
+        self._h = C.c_void_p()
+        rc = self.lib.wrnn_griffin_create(C.byref(cfg), C.byref(self.features), C.byref(self.griffin), C.byref(self._h))
+        if rc != 0:
+            msg = self.lib.wrnn_griffin_last_error(self._h).decode() if self._h else 'wrnn_griffin_create failed'
+            self.close()
+            raise ValueError(f'{ERR_NAMES.get(rc, rc)}: {msg}')
+
+    def _check(self, rc: int):
+        if rc != 0:
+            raise WrnnError(rc, self.lib.wrnn_griffin_last_error(self._h).decode())
+
+    def samples(self, frames: int) -> int:
+        """Host-only ``wrnn_griffin_samples``: ``hop (frames - 1)``; ``ValueError`` for ``frames < 1``."""
+        n = int(self.lib.wrnn_griffin_samples(self._h, int(frames))) if 1 <= int(frames) < 2 ** 31 else -1
+        if n < 0:
+            raise ValueError(f'a mel of {int(frames)} frames has no wav: at least 1 frame is needed')
+        return n
+
+    def tables(self, frames: int = 1) -> dict:
+        """``wrnn_griffin_tables``: pinv (n_fft/2 + 1, n_mels), window, and the window-sum-square of a clip of ``frames`` frames over
+        the ``n_fft + hop (frames - 1)`` positions of the padded signal, all float32."""
+        pinv = np.empty((self.cfg.n_fft // 2 + 1, self.cfg.n_mels), np.float32)
+        window = np.empty(self.cfg.win_length, np.float32)
+        wss = np.empty(self.cfg.n_fft + self.cfg.hop_length * (int(frames) - 1), np.float32)
+        self._check(self.lib.wrnn_griffin_tables(self._h, pinv.ctypes.data, window.ctypes.data, int(frames), wss.ctypes.data))
+        return dict(pinv=pinv, window=window, window_sumsquare=wss)
+
+    def griffin_lim(self, mel_ptr: int, frames_ptr: int, B: int, T_max: int, n_iter: int, phase_mode: int, seed: int, phases_ptr: int,
+                    out_ptr: int, n_out_max: int, magnitude_ptr: int, stream: int):
+        self._check(self.lib.wrnn_griffin_lim(self._h, mel_ptr or None, frames_ptr or None, int(B), int(T_max), int(n_iter), int(phase_mode),
+                                              int(seed) & (2 ** 64 - 1), phases_ptr or None, out_ptr or None, int(n_out_max),
+                                              magnitude_ptr or None, stream or None))
+
+    def close(self):
+        if getattr(self, '_h', None):
+            self.lib.wrnn_griffin_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def deemphasis(wav_ptr: int, n_max: int, n_ptr: int, B: int, k: float, out_ptr: int, stream: int):
+    """``wrnn_deemphasis``: ``out[b, i] = wav[b, i] + k out[b, i-1]`` over B ragged clips, one launch, nothing waits."""
+    rc = load_library().wrnn_deemphasis(wav_ptr or None, int(n_max), n_ptr or None, int(B), float(k), out_ptr or None, stream or None)
+    if rc != 0:
+        raise WrnnError(rc, f'wrnn_deemphasis(B={int(B)}, n_max={int(n_max)}, k={float(k)}) refused its arguments')
 
 
 class NativeResampler:

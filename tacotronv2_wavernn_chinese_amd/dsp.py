@@ -5,7 +5,8 @@ Mirror of the subset of ``wavernn/utils/dsp.py`` the mel->wav path touches:
 with, ``float_2_label`` (:12-15) and ``encode_mu_law`` (:92-95): float64 NumPy, for small inputs and the tests -- a corpus is quantised
 on the device (``csrc/dataset.hip``, ``dataset.DeviceCorpus``).
 ``load_wav`` (:18-19) and ``melspectrogram`` (:72-81) live in ``frontend.py``: the mel is built on the device (``csrc/melspec.hip``).
-``spectrogram``, pre-emphasis and Griffin-Lim are not mirrored.
+Pre-emphasis is fused into the mel kernel, and Griffin-Lim with its de-emphasis is ``frontend.GriffinLim`` (``csrc/griffin_lim.hip``);
+``spectrogram`` is not mirrored.
 """
 from __future__ import annotations
 

@@ -5,7 +5,8 @@ librosa semantics of the reference's era) as one launch of the kernel in ``csrc/
 ``resample=True`` a file at another rate goes through ``Resampler`` (``csrc/resample.hip``), a Kaiser-windowed sinc on the device.
 ``WavConditioner`` (``csrc/condition.hip``) is the silence trimming and peak rescaling of ``tacotron/datasets/preprocessor.py:62-72``,
 opt-in everywhere.  ``MelFrontEnd(features='tacotron')`` is the Tacotron-side mel of ``tacotron/datasets/audio.py`` (pre-emphasis fused
-into the kernel's tap gather), the features the reference's vocoder is trained on.  ``spectrogram`` and Griffin-Lim are not here.
+into the kernel's tap gather), the features the reference's vocoder is trained on.  ``GriffinLim`` (``csrc/griffin_lim.hip``) is the way back with no trained model:
+``inv_mel_spectrogram`` of ``tacotron/datasets/audio.py:122-137`` in either profile.  Linear ``spectrogram`` files and LWS are not here.
 """
 from __future__ import annotations
 
@@ -138,6 +139,141 @@ class MelFrontEnd:
                                                    torch.cuda.current_stream(dev).cuda_stream)
         self.last_frames = frames
         return out
+
+
+class GriffinLim:
+    """``GriffinLim(hp, features='tacotron', power=1.5, n_iter=60)``: [0, 1] mels -> wavs on the device with no trained model, the
+    reference's ``inv_mel_spectrogram`` (``tacotron/datasets/audio.py:122-137, 176-186``) on the kernels of ``csrc/griffin_lim.hip``:
+    the profile's normalisation, dB and magnitude power undone, the pseudo-inverse of its filterbank, ``** power``, ``n_iter`` rounds of
+    stft / istft that keep the magnitudes and take the wave's phases, and the de-emphasis with the profile's ``preemphasis``.  It is the
+    inverse of ``MelFrontEnd(hp, features=features)`` and reads the same configuration (``hp``, the ``MEL_DEFAULTS`` names and the
+    profile's fields as keywords); ``power`` and ``n_iter`` are arguments of this class only.  ``ValueError`` for a configuration the
+    library refuses (``n_fft`` other than 2048, ``power <= 0``, a filterbank with an empty row)."""
+
+    def __init__(self, hp=None, device=None, features='tacotron', power=1.5, n_iter=60, **kw):
+        if 'n_mels' in kw:
+            kw['num_mels'] = kw.pop('n_mels')
+        self.feature_config = feature_settings(features, **{k: kw.pop(k) for k in list(kw) if k in FEATURE_PROFILES['vocoder']})
+        self.features = features
+        unknown = set(kw) - set(MEL_DEFAULTS)
+        if unknown:
+            raise TypeError(f'unknown Griffin-Lim parameters {sorted(unknown)}')
+        self.config = {k: kw[k] if k in kw else getattr(hp, k, v) if hp is not None else v for k, v in MEL_DEFAULTS.items()}
+        self.power, self.n_iter = float(power), int(n_iter)
+        if self.n_iter < 0:
+            raise ValueError(f'n_iter must be >= 0, got {n_iter!r}')
+        self._device = device
+        self._index = torch.device(device).index if device is not None and torch.device(device).index is not None else None
+        self.n_mels, self.hop_length, self.sample_rate = int(self.config['num_mels']), int(self.config['hop_length']), int(self.config['sample_rate'])
+        self.n_bins = int(self.config['n_fft']) // 2 + 1
+        self._nat = {}
+        self._native(self._index or 0, True)   # the configuration is checked here, without a device
+        self.last_samples = self.last_seed = None
+
+    def _native(self, index: int, deemphasis: bool) -> _cabi.NativeGriffinLim:
+        """One handle per device and per de-emphasis switch: the library de-emphasises with the handle's ``preemphasis``."""
+        key = (index, bool(deemphasis))
+        if key not in self._nat:
+            c, f = self.config, dict(self.feature_config)
+            if not deemphasis:
+                f['preemphasis'] = 0.0
+            feat = _cabi.MelFeatures(**dict(f, pad_mode=_cabi.MEL_PAD_MODES[f['pad_mode']]))
+            self._nat[key] = _cabi.NativeGriffinLim(sample_rate=c['sample_rate'], n_fft=c['n_fft'], hop_length=c['hop_length'],
+                                                    win_length=c['win_length'], n_mels=c['num_mels'], fmin=c['fmin'],
+                                                    min_level_db=c['min_level_db'], device=index, features=feat,
+                                                    griffin=_cabi.GriffinConfig(self.power, self.n_iter))
+        return self._nat[key]
+
+    def samples(self, frames: int) -> int:
+        """``hop_length * (frames - 1)``: the samples a mel of ``frames`` frames gives; ``ValueError`` for ``frames < 1``."""
+        return next(iter(self._nat.values())).samples(frames)
+
+    def tables(self, frames: int = 1) -> dict:
+        """``pinv`` (n_fft/2 + 1, n_mels), ``window`` and the ``window_sumsquare`` of a clip of ``frames`` frames, as the kernels read them."""
+        return next(iter(self._nat.values())).tables(frames)
+
+    def reconstruct(self, mels, lens=None, *, n_iter=None, seed=None, phases=None, deemphasis=True, magnitude=False, device=None):
+        """One ``(n_mels, T)`` mel, a list of them with different ``T``, or a ``(B, n_mels, T_max)`` batch with the clips' frame counts
+        ``lens`` (the tensor ``MelFrontEnd.melspectrogram`` returns, with its ``last_frames``) -> ``(B, max samples)`` float32 tensor on
+        the device, clip b in ``[b, :last_samples[b]]`` and zeros from there on; a row equals the call on that clip alone bit for bit.
+        The first round's phases ``exp(2 pi i r)``: ``phases`` given: r injected, ``(B, T_max, n_fft/2 + 1)``; else ``seed`` given: r
+        drawn on the device by the counter RNG, the same wav for the same seed; neither: a fresh seed from torch's generator
+        (``self.last_seed`` keeps it).  ``phases='zero'``: r = 0.  ``deemphasis=False`` returns the pre-emphasised wave.
+        ``magnitude=True``: returns ``(wav, S)`` with S ``(B, T_max, n_fft/2 + 1)``, the linear magnitudes the rounds aim at.  Nothing
+        waits for the device."""
+        dev = torch.device(device if device is not None else self._device if self._device is not None else 'cuda')
+        if dev.type != 'cuda':
+            raise ValueError(f'Griffin-Lim runs on the GPU only, got device {dev}')
+        if isinstance(mels, torch.Tensor) and mels.is_cuda and device is None:
+            dev = mels.device
+        dev = torch.device('cuda', dev.index if dev.index is not None else torch.cuda.current_device())
+        if isinstance(mels, (list, tuple)):
+            clips = [torch.as_tensor(np.asarray(m) if not isinstance(m, torch.Tensor) else m) for m in mels]
+        else:
+            m = torch.as_tensor(np.asarray(mels) if not isinstance(mels, torch.Tensor) else mels)
+            clips = [m] if m.dim() == 2 else None
+        n_iter = self.n_iter if n_iter is None else int(n_iter)
+        if n_iter < 0:
+            raise ValueError(f'n_iter must be >= 0, got {n_iter}')
+        with torch.cuda.device(dev):
+            if clips is not None:
+                if lens is not None:
+                    raise ValueError('lens goes with a (B, n_mels, T_max) batch only')
+                if not clips or any(c.dim() != 2 or c.shape[0] != self.n_mels or c.shape[1] < 1 for c in clips):
+                    raise ValueError(f'expected mels shaped ({self.n_mels}, T >= 1)')
+                frames = [int(c.shape[1]) for c in clips]
+                if len(clips) == 1:
+                    batch = clips[0].to(device=dev, dtype=torch.float32).contiguous().unsqueeze(0)
+                else:
+                    batch = torch.zeros((len(clips), self.n_mels, max(frames)), dtype=torch.float32, device=dev)
+                    for i, c in enumerate(clips):
+                        batch[i, :, :frames[i]] = c.to(device=dev, dtype=torch.float32)
+            else:
+                if m.dim() != 3 or m.shape[1] != self.n_mels or m.shape[2] < 1 or lens is None:
+                    raise ValueError(f'expected one ({self.n_mels}, T) mel, a list of them, or a (B, {self.n_mels}, T_max) batch with lens')
+                frames = [int(t) for t in lens]
+                if len(frames) != m.shape[0] or min(frames) < 1 or max(frames) > m.shape[2]:
+                    raise ValueError(f'{len(frames)} frame counts ({min(frames, default=0)} .. {max(frames, default=0)}) for a batch shaped {tuple(m.shape)}')
+                batch = m.to(device=dev, dtype=torch.float32).contiguous()
+            B, _, T_max = batch.shape
+            nat = self._native(dev.index, deemphasis)
+            n_out = max(1, nat.samples(T_max))
+            if isinstance(phases, str):
+                if phases != 'zero':
+                    raise ValueError(f"phases must be an array, 'zero' or None, got {phases!r}")
+                mode, r, seed_used = _cabi.GRIFFIN_PHASE_ZERO, None, 0
+            elif phases is not None:
+                r = torch.as_tensor(np.asarray(phases) if not isinstance(phases, torch.Tensor) else phases).to(device=dev, dtype=torch.float32).contiguous()
+                if tuple(r.shape) != (B, T_max, self.n_bins):
+                    raise ValueError(f'phases: expected shape {(B, T_max, self.n_bins)}, got {tuple(r.shape)}')
+                mode, seed_used = _cabi.GRIFFIN_PHASE_INJECTED, 0
+            else:
+                seed_used = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
+                mode, r = _cabi.GRIFFIN_PHASE_PHILOX, None
+                self.last_seed = seed_used
+            frames_dev = torch.tensor(frames, dtype=torch.int32).to(dev)
+            out = torch.empty((B, n_out), dtype=torch.float32, device=dev)
+            S = torch.empty((B, T_max, self.n_bins), dtype=torch.float32, device=dev) if magnitude else None
+            nat.griffin_lim(batch.data_ptr(), frames_dev.data_ptr(), B, T_max, n_iter, mode, seed_used, r.data_ptr() if r is not None else 0,
+                            out.data_ptr(), n_out, S.data_ptr() if S is not None else 0, torch.cuda.current_stream(dev).cuda_stream)
+        self.last_samples = [nat.samples(t) for t in frames]
+        return (out, S) if magnitude else out
+
+
+def deemphasis(wav: torch.Tensor, lens, k: float) -> torch.Tensor:
+    """``inv_preemphasis`` on the device (``wrnn_deemphasis``): ``wav`` a contiguous float32 ``(B, n_max)`` tensor on the GPU with clip b
+    in ``wav[b, :lens[b]]`` -> ``out[b, i] = wav[b, i] + k out[b, i-1]``, zeros past each clip's own length."""
+    if not (isinstance(wav, torch.Tensor) and wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 2 and wav.is_contiguous()):
+        raise ValueError('expected a contiguous float32 (B, n_max) tensor on the GPU')
+    lens = [int(n) for n in lens]
+    B, n_max = wav.shape
+    if len(lens) != B or not lens or max(lens) > n_max or min(lens) < 0 or n_max < 1:
+        raise ValueError(f'{len(lens)} lengths ({min(lens, default=0)} .. {max(lens, default=0)}) for a buffer of shape {tuple(wav.shape)}')
+    with torch.cuda.device(wav.device):
+        n_dev = torch.tensor(lens, dtype=torch.int32).to(wav.device)
+        out = torch.empty_like(wav)
+        _cabi.deemphasis(wav.data_ptr(), n_max, n_dev.data_ptr(), B, float(k), out.data_ptr(), torch.cuda.current_stream(wav.device).cuda_stream)
+    return out
 
 
 def _padded_rows(clips, lens, dev) -> torch.Tensor:

@@ -101,6 +101,45 @@ def _gen_streamed(model: WaveRNN, mel, load_path, save_path, n, noise_mode):
     return save_str
 
 
+def griffin_lim_from_file(load_path, save_path, n_iter=60, features='vocoder', seed=None, resample=False, trim_top_db=None, peak_norm=None,
+                          device=None):
+    """``--griffin_lim``: the mel of ``gen_from_file`` -- a ``(T, n_mels)`` ``.npy`` in [0, 1], or the mel of a ``.wav`` through the front end
+    -- vocoded by Griffin-Lim on the device (``frontend.GriffinLim``) instead of a model: no checkpoint, no weights.  ``features`` names the
+    profile the mel is in.  Writes ``<stem>_griffin_lim.wav`` through ``save_wav`` and returns its path.  The de-emphasis has a gain of
+    1 / (1 - k) = 33 at DC, so a wave may leave [-1, 1]: only then is it rescaled, to a peak of 0.999, with one line on stderr."""
+    import sys
+    from .frontend import GriffinLim, MelFrontEnd
+    load_path = str(load_path)
+    device = torch.device('cuda') if device is None else torch.device(device)
+    if ".npy" in load_path:
+        mel = np.load(load_path).T
+        if mel.ndim != 2 or mel.shape[0] != hp.num_mels:
+            raise ValueError(f'Expected a numpy array shaped (n_mels, n_hops), but got {mel.shape}!')
+        _max, _min = np.max(mel), np.min(mel)
+        if _max >= 1.01 or _min <= -0.01:
+            raise ValueError(f'Expected spectrogram range in [0,1] but was instead [{_min}, {_max}]')
+        mel = torch.tensor(mel)
+    elif ".wav" in load_path:
+        if not os.path.isfile(load_path):
+            raise ValueError(f'{load_path}: no such wav file')
+        wav = load_wav(load_path, hp.sample_rate, resample=resample, device=device, trim_top_db=trim_top_db, peak_norm=peak_norm, features=features)
+        mel = MelFrontEnd(hp, features=features).melspectrogram(wav, device=device)[0]
+    else:
+        raise ValueError(f"Expected an extension of .wav or .npy, but got {os.path.splitext(load_path)[1]}!")
+    gl = GriffinLim(hp, features=features, n_iter=int(n_iter))
+    out = gl.reconstruct(mel, seed=seed, device=device)
+    wav = out[0, :gl.last_samples[0]].cpu().numpy()
+    peak = float(np.abs(wav).max()) if wav.size else 0.0
+    if peak > 1.0:
+        print(f'griffin_lim: peak {peak:.4g} exceeds 1, rescaled to 0.999', file=sys.stderr)
+        wav = wav * np.float32(0.999 / peak)
+    idx = load_path.split('/')[-1].strip().split('.')[0]
+    save_str = os.path.join(str(save_path), idx + '_griffin_lim.wav')
+    save_wav(wav, save_str, hp.sample_rate)
+    print(f'\n{n_iter} Griffin-Lim iterations, seed {gl.last_seed}: {wav.size} samples -> {save_str}')
+    return save_str
+
+
 def default_weights_path(base: str = '.') -> str:
     """``Paths(hp.voc_model_id).voc_latest_weights`` of the reference (``wavernn/utils/paths.py:8-12``)."""
     return os.path.join(os.path.abspath(base), 'logs_wavernn', 'checkpoints', 'latest_weights.pyt')
@@ -141,6 +180,10 @@ def build_parser() -> argparse.ArgumentParser:
                         help="extension: 'reference' replays the reference's own draws from the torch CPU generator (with --seed: the wav the "
                              "reference script produces after torch.manual_seed(seed)); 'philox' (default) = the device counter RNG")
     parser.add_argument('--seed', type=int, default=None, help='extension: torch.manual_seed(SEED) before generating')
+    parser.add_argument('--griffin_lim', type=int, nargs='?', const=60, default=None, metavar='N_ITER',
+                        help='extension: vocode --file by N_ITER Griffin-Lim iterations on the device (N_ITER left out: 60) instead of the '
+                             'model: no checkpoint is loaded; --features names the profile of the mel, --seed the first phases; writes '
+                             '<stem>_griffin_lim.wav (default: off)')
     parser.add_argument('--stream-frames', type=int, default=None, metavar='N',
                         help='extension: feed the mel to a streaming generator in pushes of N frames (unbatched; the same wav as '
                              '--unbatched) and print the time to first audio and the real-time factor')
@@ -175,6 +218,17 @@ def main(argv=None):
 
     device = torch.device('cuda')
     print('Using device:', device)
+    if args.griffin_lim is not None:
+        if not args.file:
+            raise ValueError('--griffin_lim vocodes a --file')
+        if args.griffin_lim < 0:
+            raise ValueError(f'--griffin_lim takes a number of iterations >= 0, got {args.griffin_lim}')
+        out_dir = './wavernn_inference_output'
+        os.makedirs(out_dir, exist_ok=True)
+        griffin_lim_from_file(args.file, out_dir, n_iter=args.griffin_lim, features=args.features, seed=args.seed, resample=args.resample,
+                              device=device, **conditioning)
+        print('\n\nExiting...\n')
+        return
     print('\nInitialising Model...\n')
     model = build_model_from_hparams().to(device)
     from . import _cabi
