@@ -711,7 +711,8 @@ static int train_impl(wrnn_handle *h, int phase, const wrnn_loop_params *w, cons
         oG[i][6] = take(nH); oG[i][7] = take(nG); oG[i][8] = take(nG); oG[i][9] = take((size_t)B * H); oG[i][10] = take((size_t)H * G);
     }
     const size_t odY = take(nY), odF2 = take(nF), odF1 = take(nF), odX3 = take(nH), odX2 = take(nH), odXI = take(nH);
-    const int maxN = G > NC ? G : NC;
+    int maxN = G > NC ? G : NC;                                              // the widest colsum() below: 3H, n_classes ...
+    if (FC > maxN) maxN = FC;                                                // ... or fc_dims columns (the fc1 / fc2 bias gradients)
     const size_t sk_floats = (size_t)16 * G * (H + A);                      // split-K partial products (<= 16 slices of the largest dW)
     const size_t oCS = take((size_t)2 * CS_CHUNKS * maxN), oSK = take(sk_floats);
     const size_t oIMG = take((size_t)786432);                                // weight image of the recurrence at hand (team kernels)

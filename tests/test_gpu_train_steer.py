@@ -12,6 +12,21 @@ the kernels branch.  n = the number of 32-CU teams (`team_info`, 8 on the MI355X
     MOL             (4 n + 1, 7), (5, 1), (16 n + 2, 3): the 30-wide fc3 tile, `gemm_tn` with Mo = 30, `mol_grad_kernel`
     generic `<0>`   rnn 256 / fc 384 / 40 mels / aux 24, RAW and MOL at (33, 3), (35, 7), (1, 1)
     split pass      train_forward, then train_backward from the float64 reference's d_logits (rounded to float32), at (4 n + 1, 3)
+    branches of `<0>`  six models (tests/train_steer.py BRANCH_DIMS, tiny upsampler), RAW at (1, 1) -- only the `have == false` step --,
+                    (2, 2) -- one carry step -- and (33, 3) -- a second row block holding one real row, two carries --; MOL at (33, 3)
+                    for h48 and h272; the split pass at h272 (33, 3); each asserts train_last_recurrence() == ('steps', 0).
+                    G = 3 rnn columns of dGH staged in chunks of 768, nblk = rnn / 4 workgroups remapped by `xcd_tile` iff nblk % 8 == 0:
+                      h16   rnn 16 / fc 8 / 32 classes / 3 mels / aux 4: kq = 4 (one MFMA step per wave), one 48-column chunk, nblk = 4
+                            (identity map), fewer classes than lanes in `ce_grad_kernel`, A = 1
+                      h48   rnn 48 / fc 200 / 128 / 13 / 20: one partial chunk of 144, nblk = 12 (identity), A = 5 (aux slices only 4-byte
+                            aligned, R = 20), fc > max(3 rnn, classes): the widest `colsum` is fc's (the `cs_part` sizing)
+                      h272  rnn 272 / fc 72 / 256 / 40 / 96: G = 768 + 48, the shortest tail chunk; nblk = 68 (identity)
+                      h320  rnn 320 / fc 96 / 256 / 40 / 96: G = 768 + 192; nblk = 80, the remapped arm with a tail chunk
+                      h528  rnn 528 / fc 64 / 64 / 20 / 32: G = 2 x 768 + 48, three chunks, the first size above the 512 kernels
+                      h880  rnn 880 / fc 64 / 64 / 20 / 32: the largest `train_impl` admits (forward LDS 163 776 of 163 840 B),
+                            G = 3 x 768 + 336
+    refusals        rnn_dims 24 ("multiple of 16") and 896 ("too large for the step kernels' LDS tiles"): WrnnError, every NaN-prefilled
+                    output untouched, no recurrence on record, `sync_status` clean
 
 Every default-dims case runs on the team kernels and, after train_force_step_kernels(True), on `gru_*_step_kernel<512>`; twice each,
 so the second call replays (the captured step graphs on the step path).  One handle per (mode, dims) for the whole module: the shapes
@@ -20,7 +35,8 @@ a timed-out exchange of the team kernels fails the test.
 
 Bounds.  TOL = 2e-5 of the tensor's largest float64 entry on every entry of the 16 gradients, d_mels_up, d_aux and the logits, and
 relative on the loss: the bound of test_loop_gradients_from_float64_conditioning for this same comparison, ~25x the float32 noise of
-the reference itself on these inputs (torch float32 vs float64: 9.4e-7 at most, test_train_steer_host.py) and >= 50x below what one
+the reference itself on these inputs (torch float32 vs float64: 9.4e-7 at most, test_train_steer_host.py; 1.31e-6 on the sets of the
+`<0>` branches, h880 (1, 1): 15x) and >= 50x below what one
 omitted (row, step) pair of at most 8 450 moves.  ROW_TOL = 1.3e-4 on every batch row of d_mels_up / d_aux against that row's OWN
 largest entry, so that a wrong row with small gradients cannot hide behind a large one: torch's float32 restatement on the same RAW
 inputs is off by up to 3.26e-5 per row (B = 130, L = 1; 3.6e-6 at most in the other cases), times 4 for the different summation
@@ -32,6 +48,12 @@ Measured on the MI355X (n = 8; every case and path in profiles/train_steer.txt),
 agree with float64 alike.  Sensitivity, tried once against deliberately wrong builds: a backward team kernel that skips the refill of
 step 0's inputs fails every team case with L >= 3 (I.weight 0.08 ... 0.39 off), a forward team kernel that hands the second row quad
 the first quad's products fails every team case with rpb >= 5 and L >= 2 (1.2e-2 ... 1.7e-2).
+
+The branches of `<0>`, measured alike over their 18 RAW / 2 MOL runs and the h272 split pass: loss 9.0e-8 / 3.4e-8, logits 3.6e-7 /
+5.3e-7, gradients 1.36e-6 (d_mels_up, h880 (1, 1): torch's float32 is 1.31e-6 off there) / 2.4e-6 (d_mels_up, MOL h272), per row
+1.6e-6 (h48 (33, 3)) / 3.6e-6 (MOL h48); the figures of the cases above did not move by a digit.  Sensitivity, tried once: a
+`gru_bwd_step_kernel<0>` that skips its partial last chunk (`if (cw < GB_KC) continue;`) fails all 14 of these runs with L >= 2 and the
+h272 split pass (I.weight 1.3e-2 ... 5.2e-2 off) while every earlier case, generic `<0>` at rnn 256 included, still passes.
 """
 import numpy as np
 import pytest
@@ -143,6 +165,8 @@ def test_train_step_equals_float64_on_steered_inputs(run, handle_of):
             nat.sync_status(c.stream)
         nat.train_step(c.ptrs(c.ps), None, c.x.data_ptr(), c.mu.data_ptr(), c.au.data_ptr(), c.y.data_ptr(), B, L, c.loss2.data_ptr(), 0, 0, 0, c.stream)
         nat.sync_status(c.stream)
+        if dims_name in ts.BRANCH_DIMS:
+            assert nat.train_last_recurrence() == ('steps', 0)
     finally:
         nat.train_force_step_kernels(False)
     loss, loss2 = float(c.loss), float(c.loss2)
@@ -156,12 +180,7 @@ def test_train_step_equals_float64_on_steered_inputs(run, handle_of):
     assert e_log <= TOL, tag
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize('path', PATHS)
-def test_split_pass_from_the_float64_loss_gradient(path, handle_of):
-    """train_forward, then train_backward fed d_logits of the float64 reference (rounded to float32): the device loss gradient
-    (`ce_grad_kernel`) takes no part, the gradients are held to the same bounds."""
-    case = ts.SPLIT_CASE
+def _split_pass(case, path, handle_of):
     mode, dims_name, spec, L = case
     dev = torch.device('cuda:0')
     nat, n, why_not = handle_of(mode, dims_name)
@@ -185,3 +204,50 @@ def test_split_pass_from_the_float64_loss_gradient(path, handle_of):
     tag = f'[steer split {ts.case_id(case)} {path}] B={B}: logits {e_log:.2e},'
     _check_grads(tag, c.got(), ref, L)
     assert e_log <= TOL, tag
+    return nat
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('path', PATHS)
+def test_split_pass_from_the_float64_loss_gradient(path, handle_of):
+    """train_forward, then train_backward fed d_logits of the float64 reference (rounded to float32): the device loss gradient
+    (`ce_grad_kernel`) takes no part, the gradients are held to the same bounds."""
+    _split_pass(ts.SPLIT_CASE, path, handle_of)
+
+
+@pytest.mark.gpu
+def test_split_pass_on_a_tail_chunk_of_the_generic_step_kernels(handle_of):
+    """The same split pass at rnn 272 (G = 768 + 48), where `gru_bwd_step_kernel<0>` stages a second, 48-column chunk."""
+    nat = _split_pass(ts.BRANCH_SPLIT_CASE, 'steps', handle_of)
+    assert nat.train_last_recurrence() == ('steps', 0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('rnn_dims,why', [(24, 'multiple of 16'), (896, "too large for the step kernels' LDS tiles")])
+def test_train_step_refuses_the_rnn_dims_the_step_kernels_cannot_run(rnn_dims, why):
+    """rnn_dims that is no multiple of 16, and the first multiple of 16 whose forward tile is over the 160 KiB of LDS (880 is the largest
+    admitted: RAW-h880-* above): WrnnError that says which, nothing launched -- every output still as prefilled, no recurrence on record."""
+    from tacotronv2_wavernn_chinese_amd import _cabi
+    from tacotronv2_wavernn_chinese_amd.synth import make_state_dict
+    dev = torch.device('cuda:0')
+    dims = dict(ts.dims_of('h16'), rnn_dims=rnn_dims)
+    sd = make_state_dict(0, mode='RAW', variant='default', **dims)
+    rng = np.random.Generator(np.random.PCG64(rnn_dims))
+    A, nc = dims['res_out_dims'] // 4, 2 ** dims['bits']
+    st = dict(sd={k: np.array(sd[k], np.float32) for k in ts.GRAD_KEYS}, x=rng.uniform(-1, 1, (1, 1)).astype(np.float32),
+              mels_up=rng.random((1, 1, dims['feat_dims']), dtype=np.float32), aux=rng.standard_normal((1, 1, 4 * A)).astype(np.float32),
+              y=rng.integers(0, nc, size=(1, 1)).astype(np.int64))
+    assert st['sd']['rnn1.weight_hh_l0'].shape == (3 * rnn_dims, rnn_dims) and st['sd']['fc3.weight'].shape[0] == nc
+    c = _Call(st, 'RAW', dev)
+    nat = _cabi.NativeVocoder(**dims, mode='RAW', device=0)
+    try:
+        with pytest.raises(_cabi.WrnnError) as ei:
+            nat.train_step(c.ptrs(c.ps), c.ptrs(c.gs), c.x.data_ptr(), c.mu.data_ptr(), c.au.data_ptr(), c.y.data_ptr(), 1, 1, c.loss.data_ptr(),
+                           c.logits.data_ptr(), c.dm.data_ptr(), c.da.data_ptr(), c.stream)
+        assert why in str(ei.value), str(ei.value)
+        assert nat.lib.wrnn_train_last_recurrence(nat._h, None, None) == -3          # WRNN_ERR_STATE: no training call ran
+        nat.sync_status(c.stream)
+        for t in c.gs + [c.dm, c.da, c.loss, c.logits]:
+            assert bool(torch.isnan(t).all())
+    finally:
+        nat.close()

@@ -9,6 +9,9 @@ Measured (float32 vs float64, worst tensor, of its largest entry): default dims 
 (9.4e-7 at B = 5, L = 64, which only the GPU file runs), generic dims 7.9e-7 ... 8.6e-7 (B = 1, L = 1: d_aux); c1 = 1.24 ... 1.95,
 c2 = 1.80 ... 3.39; on-fraction exactly 0.5.  Per batch row of d_mels_up / d_aux, against the row's OWN largest entry, the same
 float32 evaluation is off by up to 3.3e-5 (B = 130, L = 1; 3.6e-6 at most elsewhere): the source of ROW_TOL in the GPU file.
+The six sets of the `<0>` branches (BRANCH_DIMS: rnn 16 ... 880), 18 RAW cases at (1, 1), (2, 2), (33, 3): 3.1e-7 ... 8.5e-7, but
+1.31e-6 at h880 (1, 1) (d_mels_up), the worst of this file; per row 1.31e-6 at most (the same case; 1.03e-6 elsewhere);
+c1 = 0.88 ... 2.12, c2 = 1.01 ... 2.93; on-fraction exactly 0.5, the MOL cases (h48, h272) included.
 """
 import numpy as np
 import pytest
@@ -32,6 +35,25 @@ def test_the_case_list_covers_what_it_says():
     assert {(ts.batch_of(c[2], n), c[3]) for c in ts.LENGTH_SWEEP} == {(B, L) for B in (5, 33, 130) for L in (1, 2, 3, 64, 65)}
     assert ts.SPLIT_CASE in ts.ALL_CASES and len(set(ts.ALL_CASES)) == len(ts.ALL_CASES)
     assert max(ts.batch_of(c[2], n) * c[3] for c in ts.ALL_CASES) == 8450
+    # the branches of `gru_*_step_kernel<0>` (csrc/train.hip): what each set of BRANCH_DIMS is there for, as arithmetic on its dims
+    bd = ts.BRANCH_DIMS
+    assert list(bd) == ['h16', 'h48', 'h272', 'h320', 'h528', 'h880'] and all(bd[k]['rnn_dims'] == int(k[1:]) for k in bd)
+    assert all(d['rnn_dims'] % 16 == 0 and d['rnn_dims'] != 512 and d['res_out_dims'] % 4 == 0 and d['fc_dims'] % 2 == 0 for d in bd.values())
+    G = {k: 3 * d['rnn_dims'] for k, d in bd.items()}
+    assert {k: (g // 768, g % 768) for k, g in G.items()} == \
+        {'h16': (0, 48), 'h48': (0, 144), 'h272': (1, 48), 'h320': (1, 192), 'h528': (2, 48), 'h880': (3, 336)}   # full chunks, tail chunk
+    assert 3 * ts.GENERIC_DIMS['rnn_dims'] == 768                      # the generic set: exactly one full chunk, no tail
+    assert [k for k, d in bd.items() if (d['rnn_dims'] // 4) % 8 == 0] == ['h320']        # `xcd_tile` remaps; identity for the others
+    assert bd['h16']['rnn_dims'] // 4 == 4 and 2 ** bd['h16']['bits'] == 32 < 64 and bd['h16']['res_out_dims'] // 4 == 1
+    assert bd['h48']['res_out_dims'] // 4 == 5 and bd['h48']['res_out_dims'] % 8 != 0
+    assert [k for k, d in bd.items() if d['fc_dims'] > max(3 * d['rnn_dims'], 2 ** d['bits'])] == ['h48']   # the column-sum scratch
+    assert 44 * (880 + 4) * 4 + 8192 <= 160 * 1024 < 44 * (896 + 4) * 4 + 8192          # h880: the largest `train_impl` admits
+    assert (32 * (768 + 4) + 4 * (3 * 896 + 4) + 512) * 4 <= 160 * 1024                 # the forward tile is what binds, not the backward
+    assert ts.BRANCH_CASES == ts.ALL_CASES[-20:] and ts.BRANCH_SPLIT_CASE in ts.BRANCH_CASES
+    assert {(c[0], c[2][1], c[3]) for c in ts.BRANCH_CASES if c[1] == 'h272'} == {('RAW', 1, 1), ('RAW', 2, 2), ('RAW', 33, 3), ('MOL', 33, 3)}
+    assert all(sum(c[1] == k for c in ts.BRANCH_CASES) == (4 if k in ('h48', 'h272') else 3) for k in bd)
+    assert all(c in HOST_CASES for c in ts.BRANCH_CASES)
+    assert [ts.case_seed(c) for c in (ts.ALL_CASES[0], ts.GENERIC_CASES[-1], ts.BRANCH_CASES[0])] == [7, 34007, 35007]   # old seeds kept
 
 
 @pytest.mark.parametrize('case', HOST_CASES, ids=ts.case_id)

@@ -31,6 +31,23 @@ GRAD_KEYS = ('I.weight', 'I.bias', 'rnn1.weight_ih_l0', 'rnn1.weight_hh_l0', 'rn
 # rnn 256 / fc 384 / 40 mels / aux 24: the dims of test_train_step_on_non_default_dims_and_ragged_batch_sizes (`gru_*_step_kernel<0>`)
 GENERIC_DIMS = dict(rnn_dims=256, fc_dims=384, bits=8, pad=2, upsample_factors=(4, 4, 8), feat_dims=40, compute_dims=64,
                     res_out_dims=96, res_blocks=2, hop_length=128, sample_rate=16000)
+# The sizes at which `gru_*_step_kernel<0>` branches (G = 3 rnn: the backward kernel stages dGH in chunks of 768 columns; nblk = rnn / 4
+# workgroups, remapped by `xcd_tile` only when nblk % 8 == 0; A = res_out / 4).  The loop kernels never see the upsampler: it is tiny.
+#   h16   kq = 4: one MFMA step per wave; one 48-column chunk; nblk = 4, identity map; 32 classes < one wave; A = 1
+#   h48   one partial chunk of 144; nblk = 12, identity; A = 5 (odd: the aux slices are 4-byte aligned, R = 20); fc > max(G, classes)
+#   h272  G = 816 = 768 + 48, the shortest tail chunk there is; nblk = 68, identity
+#   h320  G = 960 = 768 + 192; nblk = 80: the remapped arm with a tail chunk
+#   h528  G = 1584 = 2 x 768 + 48: three chunks, the first size above the 512 kernels
+#   h880  the largest rnn_dims `train_impl` admits (forward LDS 163 776 B of 163 840); G = 2640 = 3 x 768 + 336
+_TINY_UPSAMPLER = dict(pad=2, upsample_factors=(2, 3), hop_length=6, compute_dims=16, res_blocks=1, sample_rate=16000)
+BRANCH_DIMS = {
+    'h16': dict(rnn_dims=16, fc_dims=8, bits=5, feat_dims=3, res_out_dims=4, **_TINY_UPSAMPLER),
+    'h48': dict(rnn_dims=48, fc_dims=200, bits=7, feat_dims=13, res_out_dims=20, **_TINY_UPSAMPLER),
+    'h272': dict(rnn_dims=272, fc_dims=72, bits=8, feat_dims=40, res_out_dims=96, **_TINY_UPSAMPLER),
+    'h320': dict(rnn_dims=320, fc_dims=96, bits=8, feat_dims=40, res_out_dims=96, **_TINY_UPSAMPLER),
+    'h528': dict(rnn_dims=528, fc_dims=64, bits=6, feat_dims=20, res_out_dims=32, **_TINY_UPSAMPLER),
+    'h880': dict(rnn_dims=880, fc_dims=64, bits=6, feat_dims=20, res_out_dims=32, **_TINY_UPSAMPLER),
+}
 
 
 def batch_of(spec, n):
@@ -49,7 +66,13 @@ LENGTH_SWEEP = [('RAW', 'default', s, L) for s in ((0, 5), (4, 1), (16, 2)) for 
 MOL_CASES = [('MOL', 'default', (4, 1), 7), ('MOL', 'default', (0, 5), 1), ('MOL', 'default', (16, 2), 3)]
 GENERIC_CASES = [(m, 'generic', (0, B), L) for m in ('RAW', 'MOL') for B, L in ((33, 3), (35, 7), (1, 1))]
 SPLIT_CASE = ('RAW', 'default', (4, 1), 3)
-ALL_CASES = ROWS_SWEEP + LENGTH_SWEEP + MOL_CASES + GENERIC_CASES
+# The branches of `<0>` (BRANCH_DIMS), appended so that the cases before them keep their seeds.  (1, 1): only the `have == false` step;
+# (2, 2): one carry step; (33, 3): a second row block that holds one real row, two carries
+BRANCH_SHAPES = ((1, 1), (2, 2), (33, 3))
+BRANCH_CASES = [('RAW', name, (0, B), L) for name in BRANCH_DIMS for B, L in BRANCH_SHAPES] + \
+               [('MOL', name, (0, 33), 3) for name in ('h48', 'h272')]
+BRANCH_SPLIT_CASE = ('RAW', 'h272', (0, 33), 3)
+ALL_CASES = ROWS_SWEEP + LENGTH_SWEEP + MOL_CASES + GENERIC_CASES + BRANCH_CASES
 
 
 def case_id(c):
@@ -62,7 +85,7 @@ def case_seed(c):
 
 
 def dims_of(name):
-    return dict(DEFAULT_DIMS) if name == 'default' else dict(GENERIC_DIMS)
+    return dict(DEFAULT_DIMS) if name == 'default' else dict(GENERIC_DIMS) if name == 'generic' else dict(BRANCH_DIMS[name])
 
 
 def _signs(rng, B, L):
