@@ -768,6 +768,74 @@ int wrnn_deemphasis(const float *wav_dev, int64_t n_max, const int32_t *n_dev, i
 const char *wrnn_griffin_last_error(const wrnn_griffin_handle *h);
 void wrnn_griffin_destroy(wrnn_griffin_handle *h);
 
+/* ---- spectral scores (new entry points in ABI 9 again, and one new struct; nothing existing changes): how far a TEST clip b is from a
+ * TARGET clip a, both float32, compared over the n samples the caller passes for the pair (the shorter clip's length).
+ * Mel scores.  Both clips go through the mel front end above, in either feature profile: Ma, Mb in [0, 1], (n_mels, T), T = 1 + n / hop_length.
+ *   D = (Ma - Mb) (-min_level_db)                      dB, clipped at the floor as the front end clips
+ *   lsd_t = sqrt(mean_m D[m, t]^2)                     the frame's log-mel distance in dB
+ *   mcd_t = (10 / ln 10) sqrt(2 sum_{k = 1 .. K} c[k, t]^2),  c = C (D ln 10 / 20),  C[k, m] = sqrt(2 / n_mels) cos(pi k (m + 1/2) / n_mels)
+ *                                                      (orthonormal DCT-II without c0), K = mcd_order; no time alignment
+ * STFT scores, for every resolution r = (n_fft, hop, win): center=True with reflect padding of n_fft / 2, a periodic Hann window of win
+ * centred in n_fft ((n_fft - win) / 2 zeros on its left), 1 + n / hop frames, n_fft / 2 + 1 bins; A = sqrt(max(re^2 + im^2, mag_floor))
+ * of the target, B of the test:
+ *   num_t = sum_k (B - A)^2,  den_t = sum_k A^2,  lm_t = sum_k |ln A - ln B|
+ * The transform runs in float64 up to re^2 + im^2, which is rounded to float32 once per bin; the floor, the square root and the logarithm
+ * are float32, and a frame's bin sums are carried in float64 and rounded once (|ln A - ln B| divides the transform's error by the bin's
+ * magnitude, and a float32 transform does not keep the smallest bins of a noisy frame).
+ * Per-frame values are float32.  The summaries are float64 sums of those float32 values, taken by a second launch in a fixed order (no
+ * floating-point atomics: two calls give the same bits, and a clip of a ragged batch equals the call on it alone bit for bit):
+ *   mel_lsd_db = mean_t lsd_t,  mcd_db = mean_t mcd_t,
+ *   sc[r] = sqrt(sum_t num_t) / sqrt(sum_t den_t)      spectral convergence
+ *   logmag[r] = sum_t lm_t / (frames bins)             log-magnitude distance
+ *   mr_sc, mr_logmag = the means of sc[r], logmag[r] over the handle's resolutions.
+ * Both clips of a frame run through the same instructions, so identical clips score exactly 0 everywhere, and so do two silences (both
+ * sides sit at the floor; den_t is bins * mag_floor there, not 0).
+ * The create entry touches no device.  `features` may be NULL: the default profile.  It refuses what the profile create entry of the
+ * front end refuses (with that entry's status), and with WRNN_ERR_INVALID a struct_size other than the struct's own size, n_res outside
+ * 1 .. 4, n_fft outside {256, 512, 1024, 2048}, win outside 1 .. n_fft, hop < 1, a mag_floor that is not finite and > 0, and mcd_order
+ * outside 1 .. n_mels - 1.  A refused handle is still returned, for its error text and the destroy entry.
+ * A clip needs max over the resolutions of n_fft / 2 + 1 samples (and the front end's own 1025 under reflect padding). */
+#define WRNN_SCORE_MAX_RES 4
+#define WRNN_SCORE_FIELDS 12       /* doubles per clip in summary_dev, in this order: */
+#define WRNN_SCORE_MEL_LSD_DB 0
+#define WRNN_SCORE_MCD_DB 1
+#define WRNN_SCORE_MR_SC 2
+#define WRNN_SCORE_MR_LOGMAG 3
+#define WRNN_SCORE_SC0 4           /* sc[r] at 4 + r, 0 for r >= n_res */
+#define WRNN_SCORE_LOGMAG0 8       /* logmag[r] at 8 + r, 0 for r >= n_res */
+typedef struct wrnn_score_handle wrnn_score_handle;
+typedef struct wrnn_score_config {
+    uint32_t struct_size;    /* the size of this struct */
+    int32_t n_res;           /* 1 .. WRNN_SCORE_MAX_RES */
+    int32_t n_fft[4];        /* (512, 1024, 2048) */
+    int32_t hop[4];          /* (50, 120, 240) */
+    int32_t win[4];          /* (240, 600, 1200) */
+    float mag_floor;         /* 1e-7: the floor under re^2 + im^2 */
+    int32_t mcd_order;       /* 13 */
+} wrnn_score_config;
+int wrnn_score_create(const wrnn_mel_config *cfg, const wrnn_mel_features *features, const wrnn_score_config *score, wrnn_score_handle **out);
+/* Host only: the frames of a clip of n samples at resolution r, 1 + n / hop[r]; r = -1: the mel's, 1 + n / hop_length.
+ * WRNN_ERR_INVALID (< 0) for a clip shorter than the handle's shortest legal clip, r outside -1 .. n_res - 1, or a refused handle. */
+int64_t wrnn_score_frames(const wrnn_score_handle *h, int32_t r, int64_t n);
+/* target_dev, test_dev: B float32 clips each, row stride n_max; n_dev: B int32 on the device, the pairs' own lengths (ragged; a value
+ * above n_max is read as n_max; a clip shorter than the shortest legal one has no frames and all-zero results: the lengths live on the
+ * device and the call never waits, so the HOST side checks them with the frames entry).  summary_dev (B, WRNN_SCORE_FIELDS) float64.
+ * frames_dev: NULL (the per-frame values go to the handle's scratch), or (B, frames_stride) float32.  A row holds, with F(r) the frames
+ * entry's value for n_max samples: lsd[F(-1)] | mcd[F(-1)] | then for r = 0 .. n_res - 1: num[F(r)] | den[F(r)] | lm[F(r)]; frames_stride
+ * is at least the sum of those.  Entries at or past a clip's own frame count are written as 0.  2 (+ 2 peak launches under a profile with
+ * preemph_rescale) mel launches, 1 + n_res + 2 launches of this section, asynchronous on `stream`.  The handle owns the scratch (the two
+ * mels, the sums, the per-frame values) and grows it when a call needs more -- the one case in which a call waits for `stream` -- so
+ * calls on ONE handle must be ordered by the caller.  The tables are uploaded by the first call (one blocking copy). */
+int wrnn_score(wrnn_score_handle *h, const float *target_dev, const float *test_dev, int64_t n_max, const int32_t *n_dev, int32_t B,
+               double *summary_dev, float *frames_dev, int64_t frames_stride, void *stream);
+/* Host only (tests): the tables the kernels read, as float32.  window[win[r]] and twiddle[2 * n_fft[r]] = (cos, -sin) of
+ * 2 pi k / n_fft[r] of resolution r: the transform kernel reads these two in float64, they are rounded to float32 here;
+ * dct[mcd_order * n_mels] = C rows 1 .. mcd_order, row-major, built in float64 and rounded once (the device copy is its transpose).
+ * Any pointer may be NULL. */
+int wrnn_score_tables(const wrnn_score_handle *h, int32_t r, float *window, float *twiddle, float *dct);
+const char *wrnn_score_last_error(const wrnn_score_handle *h);
+void wrnn_score_destroy(wrnn_score_handle *h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,7 +46,9 @@ EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wr
                     'wrnn_teamg_plan_fmt', 'wrnn_train_last_recurrence', 'wrnn_train_teamg_plan',
                     'wrnn_train_set_precision', 'wrnn_train_precision', 'wrnn_train_last_gemms', 'wrnn_debug_train_gemm',
                     'wrnn_griffin_create', 'wrnn_griffin_samples', 'wrnn_griffin_tables', 'wrnn_griffin_lim', 'wrnn_deemphasis',
-                    'wrnn_griffin_last_error', 'wrnn_griffin_destroy')
+                    'wrnn_griffin_last_error', 'wrnn_griffin_destroy',
+                    'wrnn_score_create', 'wrnn_score_frames', 'wrnn_score', 'wrnn_score_tables', 'wrnn_score_last_error',
+                    'wrnn_score_destroy')
 
 
 def epilogue_tables(n_classes: int, overlap: int, hop: int):
@@ -132,6 +134,29 @@ class GriffinConfig(C.Structure):
 
     def __init__(self, power=1.5, n_iter_default=60):
         super().__init__(C.sizeof(GriffinConfig), float(power), int(n_iter_default))
+
+
+SCORE_MAX_RES, SCORE_FIELDS = 4, 12   # WRNN_SCORE_MAX_RES, WRNN_SCORE_FIELDS
+# the order of the doubles in wrnn_score's summary: WRNN_SCORE_MEL_LSD_DB .. WRNN_SCORE_LOGMAG0 + 3
+SCORE_FIELD_NAMES = ('mel_lsd_db', 'mcd_db', 'mr_sc', 'mr_logmag', 'sc0', 'sc1', 'sc2', 'sc3', 'logmag0', 'logmag1', 'logmag2', 'logmag3')
+SCORE_DEFAULT_RESOLUTIONS = ((512, 50, 240), (1024, 120, 600), (2048, 240, 1200))   # (n_fft, hop, win)
+
+
+class ScoreConfig(C.Structure):
+    """``wrnn_score_config``; ``resolutions``: up to four ``(n_fft, hop, win)``."""
+    _fields_ = [('struct_size', C.c_uint32), ('n_res', C.c_int32), ('n_fft', C.c_int32 * 4), ('hop', C.c_int32 * 4), ('win', C.c_int32 * 4),
+                ('mag_floor', C.c_float), ('mcd_order', C.c_int32)]
+
+    def __init__(self, resolutions=SCORE_DEFAULT_RESOLUTIONS, mag_floor=1e-7, mcd_order=13):
+        res = [tuple(int(v) for v in r) for r in resolutions]
+        if any(len(r) != 3 for r in res):
+            raise ValueError(f'a resolution is (n_fft, hop, win), got {resolutions!r}')
+        if len(res) > SCORE_MAX_RES:
+            raise ValueError(f'a handle holds at most {SCORE_MAX_RES} resolutions, got {len(res)}')
+        pad = [(0, 0, 0)] * (SCORE_MAX_RES - len(res))
+        cols = list(zip(*(res + pad)))
+        super().__init__(C.sizeof(ScoreConfig), len(res), (C.c_int32 * 4)(*cols[0]), (C.c_int32 * 4)(*cols[1]), (C.c_int32 * 4)(*cols[2]),
+                         float(mag_floor), int(mcd_order))
 
 
 WEIGHT_FORMATS = {'f32': 0, 'f16': 1}   # WRNN_WEIGHTS_*: the element type of the TEAMG / TEAMG_BATCH weight image
@@ -426,6 +451,18 @@ def load_library() -> C.CDLL:
     lib.wrnn_griffin_last_error.restype = C.c_char_p
     lib.wrnn_griffin_destroy.argtypes = [vp]
     lib.wrnn_griffin_destroy.restype = None
+    lib.wrnn_score_create.argtypes = [C.POINTER(MelConfig), C.POINTER(MelFeatures), C.POINTER(ScoreConfig), C.POINTER(vp)]
+    lib.wrnn_score_create.restype = C.c_int
+    lib.wrnn_score_frames.argtypes = [vp, C.c_int32, C.c_int64]
+    lib.wrnn_score_frames.restype = C.c_int64
+    lib.wrnn_score.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int32, vp, vp, C.c_int64, vp]
+    lib.wrnn_score.restype = C.c_int
+    lib.wrnn_score_tables.argtypes = [vp, C.c_int32, vp, vp, vp]
+    lib.wrnn_score_tables.restype = C.c_int
+    lib.wrnn_score_last_error.argtypes = [vp]
+    lib.wrnn_score_last_error.restype = C.c_char_p
+    lib.wrnn_score_destroy.argtypes = [vp]
+    lib.wrnn_score_destroy.restype = None
     lib.wrnn_quantise.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp]
     lib.wrnn_quantise.restype = C.c_int
     lib.wrnn_collate_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -970,6 +1007,81 @@ class NativeGriffinLim:
     def close(self):
         if getattr(self, '_h', None):
             self.lib.wrnn_griffin_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NativeScore:
+    """Owner of one ``wrnn_score_handle`` (spectral scores of a test clip against a target; no weights).  Creating it touches no device;
+    a configuration the library refuses raises ``ValueError``.  ``features``: a ``MelFeatures`` or ``None`` (the default profile);
+    ``score``: a ``ScoreConfig``."""
+
+    def __init__(self, *, sample_rate, n_fft, hop_length, win_length, n_mels, fmin, min_level_db, device: int = 0, features=None, score=None):
+        self.lib = load_library()
+        cfg = MelConfig(int(sample_rate), int(n_fft), int(hop_length), int(win_length), int(n_mels), float(fmin), float(min_level_db), int(device))
+        self.cfg = cfg
+        self.features = features
+        self.score_config = score if score is not None else ScoreConfig()
+        self.device = int(device)
+        self._h = C.c_void_p()
+        rc = self.lib.wrnn_score_create(C.byref(cfg), C.byref(features) if features is not None else None, C.byref(self.score_config),
+                                        C.byref(self._h))
+        if rc != 0:
+            msg = self.lib.wrnn_score_last_error(self._h).decode() if self._h else 'wrnn_score_create failed'
+            self.close()
+            raise ValueError(f'{ERR_NAMES.get(rc, rc)}: {msg}')
+        self.n_res = int(self.score_config.n_res)
+        self.resolutions = [(int(self.score_config.n_fft[r]), int(self.score_config.hop[r]), int(self.score_config.win[r])) for r in range(self.n_res)]
+        reflect = features is None or features.pad_mode == MEL_PAD_MODES['reflect']
+        self.min_samples = max([n // 2 + 1 for n, _, _ in self.resolutions] + ([cfg.n_fft // 2 + 1] if reflect else [1]))
+
+    def _check(self, rc: int):
+        if rc != 0:
+            raise WrnnError(rc, self.lib.wrnn_score_last_error(self._h).decode())
+
+    def frames(self, r: int, n: int) -> int:
+        """Host-only ``wrnn_score_frames``: the frames of ``n`` samples at resolution ``r`` (``-1``: the mel); ``ValueError`` for a clip
+        shorter than ``min_samples`` (it cannot be reflect-padded at every resolution) or an unknown ``r``."""
+        if not -1 <= int(r) < self.n_res:
+            raise ValueError(f'resolution {int(r)} is outside -1 .. {self.n_res - 1}')
+        t = int(self.lib.wrnn_score_frames(self._h, int(r), int(n))) if 0 <= int(n) < 2 ** 31 else -1
+        if t < 0:
+            raise ValueError(f'a clip of {int(n)} samples cannot be scored: at least {self.min_samples} samples are needed')
+        return t
+
+    def layout(self, n_max: int):
+        """The per-frame row of a call with ``n_max``: ``[(name, r, offset, frames)]`` in buffer order and the row's length."""
+        segs, at = [], 0
+        for name, r in [('lsd', -1), ('mcd', -1)] + [(q, r) for r in range(self.n_res) for q in ('num', 'den', 'lm')]:
+            t = self.frames(r, n_max)
+            segs.append((name, r, at, t))
+            at += t
+        return segs, at
+
+    def tables(self) -> dict:
+        """``wrnn_score_tables``: ``windows`` and ``twiddles`` (n_fft, 2) per resolution, and ``dct`` (mcd_order, n_mels), all float32."""
+        K = int(self.score_config.mcd_order)
+        dct = np.empty((K, self.cfg.n_mels), np.float32)
+        windows, twiddles = [], []
+        for r, (n_fft, _, win) in enumerate(self.resolutions):
+            w, tw = np.empty(win, np.float32), np.empty((n_fft, 2), np.float32)
+            self._check(self.lib.wrnn_score_tables(self._h, r, w.ctypes.data, tw.ctypes.data, dct.ctypes.data))
+            windows.append(w)
+            twiddles.append(tw)
+        return dict(windows=windows, twiddles=twiddles, dct=dct)
+
+    def score(self, target_ptr: int, test_ptr: int, n_max: int, n_ptr: int, B: int, summary_ptr: int, frames_ptr: int, frames_stride: int, stream: int):
+        self._check(self.lib.wrnn_score(self._h, target_ptr or None, test_ptr or None, int(n_max), n_ptr or None, int(B), summary_ptr or None,
+                                        frames_ptr or None, int(frames_stride), stream or None))
+
+    def close(self):
+        if getattr(self, '_h', None):
+            self.lib.wrnn_score_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -6,7 +6,9 @@ librosa semantics of the reference's era) as one launch of the kernel in ``csrc/
 ``WavConditioner`` (``csrc/condition.hip``) is the silence trimming and peak rescaling of ``tacotron/datasets/preprocessor.py:62-72``,
 opt-in everywhere.  ``MelFrontEnd(features='tacotron')`` is the Tacotron-side mel of ``tacotron/datasets/audio.py`` (pre-emphasis fused
 into the kernel's tap gather), the features the reference's vocoder is trained on.  ``GriffinLim`` (``csrc/griffin_lim.hip``) is the way back with no trained model:
-``inv_mel_spectrogram`` of ``tacotron/datasets/audio.py:122-137`` in either profile.  Linear ``spectrogram`` files and LWS are not here.
+``inv_mel_spectrogram`` of ``tacotron/datasets/audio.py:122-137`` in either profile.  ``SpectralScore`` (``csrc/score.hip``) rates a test clip
+against its target: log-mel distance and mel-cepstral distortion over this front end's mel, spectral convergence and log-magnitude distance at
+several STFT resolutions (the reference compares its ``*_target.wav`` files with nothing).  Linear ``spectrogram`` files and LWS are not here.
 """
 from __future__ import annotations
 
@@ -529,6 +531,95 @@ class WavConditioner:
             if energies is not None:
                 energies.copy_(ws[:B * F_max].view(B, F_max))
         return out, n_out
+
+
+class SpectralScore:
+    """``SpectralScore(hp, features='vocoder', resolutions=..., mcd_order=13, mag_floor=1e-7)``: how far test clips are from their
+    targets, on the device (``csrc/score.hip``): the per-frame log-mel distance and mel-cepstral distortion over the mel of
+    ``MelFrontEnd(hp, features=features)`` (the same configuration: ``hp``, the ``MEL_DEFAULTS`` names and the profile's fields as
+    keywords), and spectral convergence and log-magnitude distance at every ``(n_fft, hop, win)`` of ``resolutions`` (at most four,
+    ``n_fft`` one of 256, 512, 1024, 2048).  The definitions are in ``include/wavernn_amd.h``.  No time alignment: the clips are compared
+    sample for sample.  ``ValueError`` for a configuration the library refuses, without a device."""
+
+    def __init__(self, hp=None, device=None, features='vocoder', resolutions=_cabi.SCORE_DEFAULT_RESOLUTIONS, mcd_order=13, mag_floor=1e-7, **kw):
+        if 'n_mels' in kw:
+            kw['num_mels'] = kw.pop('n_mels')
+        self.feature_config = feature_settings(features, **{k: kw.pop(k) for k in list(kw) if k in FEATURE_PROFILES['vocoder']})
+        self.features = features
+        unknown = set(kw) - set(MEL_DEFAULTS)
+        if unknown:
+            raise TypeError(f'unknown score parameters {sorted(unknown)}')
+        self.config = {k: kw[k] if k in kw else getattr(hp, k, v) if hp is not None else v for k, v in MEL_DEFAULTS.items()}
+        self.mcd_order, self.mag_floor = int(mcd_order), float(mag_floor)
+        self._score_config = _cabi.ScoreConfig(resolutions, self.mag_floor, self.mcd_order)   # ValueError: malformed or too many resolutions
+        self._device = device
+        self._index = torch.device(device).index if device is not None and torch.device(device).index is not None else None
+        self.n_mels, self.hop_length, self.sample_rate = int(self.config['num_mels']), int(self.config['hop_length']), int(self.config['sample_rate'])
+        self._nat = {}
+        nat = self._native(self._index or 0)   # the configuration is checked here, without a device
+        self.resolutions, self.min_samples = nat.resolutions, nat.min_samples
+
+    def _native(self, index: int) -> _cabi.NativeScore:
+        if index not in self._nat:
+            c, f = self.config, self.feature_config
+            feat = None if f == FEATURE_PROFILES['vocoder'] else _cabi.MelFeatures(**dict(f, pad_mode=_cabi.MEL_PAD_MODES[f['pad_mode']]))
+            self._nat[index] = _cabi.NativeScore(sample_rate=c['sample_rate'], n_fft=c['n_fft'], hop_length=c['hop_length'], win_length=c['win_length'],
+                                                 n_mels=c['num_mels'], fmin=c['fmin'], min_level_db=c['min_level_db'], device=index, features=feat,
+                                                 score=self._score_config)
+        return self._nat[index]
+
+    def frames(self, r: int, n: int) -> int:
+        """The frames of a clip of ``n`` samples at resolution ``r`` (``-1``: the mel); ``ValueError`` for a clip shorter than ``min_samples``."""
+        return next(iter(self._nat.values())).frames(r, n)
+
+    def tables(self) -> dict:
+        """``windows``, ``twiddles`` (per resolution) and ``dct`` (mcd_order, n_mels) as the kernels read them."""
+        return next(iter(self._nat.values())).tables()
+
+    def score(self, targets, tests, device=None, per_frame=False):
+        """``targets`` and ``tests``: what ``MelFrontEnd.melspectrogram`` accepts (one 1-D array / tensor, a 2-D one, or a list of clips of
+        different lengths, on the host or the device), pair by pair; every pair is cut to its shorter clip.  One library call for the
+        whole list.  Returns a list of dicts, one per pair: ``mel_lsd_db``, ``mcd_db``, ``mr_sc``, ``mr_logmag``, ``stft`` (a list of
+        ``{n_fft, hop, win, sc, logmag, frames}``) and ``n``; with ``per_frame=True`` also ``lsd``, ``mcd`` (float32 arrays over the mel's
+        frames) and ``num``, ``den``, ``lm`` in every entry of ``stft``.  ``ValueError`` before any device work for a pair shorter than
+        ``min_samples``.  Reading the results back is the one host wait."""
+        (ca, la), (cb, lb) = _clip_list(targets), _clip_list(tests)
+        if len(ca) != len(cb):
+            raise ValueError(f'{len(ca)} targets for {len(cb)} tests')
+        lens = [min(a, b) for a, b in zip(la, lb)]
+        for n in lens:
+            self.frames(-1, n)                 # refuses a short pair before anything is launched
+        dev = torch.device(device if device is not None else self._device if self._device is not None else 'cuda')
+        if dev.type != 'cuda':
+            raise ValueError(f'the scores run on the GPU only, got device {dev}')
+        dev = torch.device('cuda', dev.index if dev.index is not None else torch.cuda.current_device())
+        B, n_max = len(lens), max(lens)
+        wa = _padded_rows([c[:n] for c, n in zip(ca, lens)], lens, dev)
+        wb = _padded_rows([c[:n] for c, n in zip(cb, lens)], lens, dev)
+        nat = self._native(dev.index)
+        segs, stride = nat.layout(n_max)
+        with torch.cuda.device(dev):
+            n_dev = torch.tensor(lens, dtype=torch.int32).to(dev)
+            summary = torch.empty((B, _cabi.SCORE_FIELDS), dtype=torch.float64, device=dev)
+            frames = torch.empty((B, stride), dtype=torch.float32, device=dev) if per_frame else None
+            nat.score(wa.data_ptr(), wb.data_ptr(), n_max, n_dev.data_ptr(), B, summary.data_ptr(), frames.data_ptr() if per_frame else 0,
+                      stride, torch.cuda.current_stream(dev).cuda_stream)
+            summary = summary.cpu().numpy()
+            frames = frames.cpu().numpy() if per_frame else None
+        # the raw per-frame rows as the library wrote them (zeros past a clip's own frames) and their segments (name, r, offset, frames)
+        self.last_frames_buffer, self.last_layout = frames, segs
+        out = []
+        for b, n in enumerate(lens):
+            s = dict(zip(_cabi.SCORE_FIELD_NAMES, (float(v) for v in summary[b])))
+            d = dict(n=n, mel_lsd_db=s['mel_lsd_db'], mcd_db=s['mcd_db'], mr_sc=s['mr_sc'], mr_logmag=s['mr_logmag'], stft=[])
+            for r, (n_fft, hop, win) in enumerate(self.resolutions):
+                d['stft'].append(dict(n_fft=n_fft, hop=hop, win=win, sc=s[f'sc{r}'], logmag=s[f'logmag{r}'], frames=nat.frames(r, n)))
+            if per_frame:
+                for name, r, off, _ in segs:
+                    t = nat.frames(r, n)
+                    (d if r < 0 else d['stft'][r])[name] = frames[b, off:off + t].copy()
+            out.append(d)
+        return out
 
 
 def _decode(path, data) -> np.ndarray:

@@ -255,6 +255,33 @@ def synthetic_pairs(n: int, frames: int, *, bits: int, n_mels: int, hop_length: 
     return out
 
 
+def checkpoint_generator(hp, paths: VocPaths, scorer=None):
+    """The ``at_checkpoint`` of the command line: ``gen_testset`` (dataset.py:18-43), vocode a few held-out mels next to the checkpoint.
+    ``scorer``: a ``frontend.SpectralScore``; every generated clip is then scored against its decoded target (both are in memory) and
+    ``step, clip, mel_lsd_db, mcd_db, mr_sc, mr_logmag`` is appended to ``checkpoints/scores.txt``.  ``None``: nothing else is written."""
+    def at_checkpoint(mod, test_set, step):
+        from .dsp import decode_mu_law, label_2_float, save_wav
+        k = step // 1000
+        batch_str = f'gen_batched_target{hp.voc_target}_overlap{hp.voc_overlap}' if hp.voc_gen_batched else 'gen_NOT_BATCHED'
+        rows = []
+        for i, pair in enumerate(test_set[:hp.voc_gen_at_checkpoint], 1):
+            mel, x = WindowLoader._arrays(pair)       # (wav path, mel path) of .npy files, or in-memory (mel (n_mels, frames), labels)
+            # the quantised target (:28-37): decoded and kept next to the generated file, as the reference does
+            bits = 16 if hp.voc_mode == 'MOL' else hp.bits
+            x = decode_mu_law(x, 2 ** bits, from_labels=True) if (hp.mu_law and hp.voc_mode != 'MOL') else label_2_float(x.astype(np.float64), bits)
+            save_wav(x, paths.voc_output / f'{k}k_steps_{i}_target.wav', hp.sample_rate)
+            m = torch.from_numpy(np.ascontiguousarray(mel, dtype=np.float32)).unsqueeze(0)
+            wav = mod.generate(m, str(paths.voc_output / f'{k}k_steps_{i}_{batch_str}.wav'), hp.voc_gen_batched, hp.voc_target,
+                               hp.voc_overlap, hp.mu_law)
+            if scorer is not None:
+                s = scorer.score(np.asarray(x, np.float32), np.asarray(wav, np.float32), device=next(mod.parameters()).device)[0]
+                rows.append(f"{step} {i} {s['mel_lsd_db']:.6f} {s['mcd_db']:.6f} {s['mr_sc']:.6f} {s['mr_logmag']:.6f}\n")
+        if rows:
+            with open(paths.voc_checkpoints / 'scores.txt', 'a') as fh:
+                fh.writelines(rows)
+    return at_checkpoint
+
+
 def build_parser():
     import argparse
     from .hparams import DEFAULT_HPARAMS
@@ -275,6 +302,11 @@ def build_parser():
                         help="precision of the loop layers' batched GEMMs: f32 (default), or bf16 operands on the matrix cores with fp32 "
                              'accumulators (WaveRNN.train_precision; parameters, recurrences and losses stay fp32)')
     parser.add_argument('--total_steps', type=int, help='override hp.voc_total_steps')
+    parser.add_argument('--score_at_checkpoint', action='store_true',
+                        help='extension: at every checkpoint, score each generated held-out clip against its target on the device '
+                             '(frontend.SpectralScore) and append "step clip mel_lsd_db mcd_db mr_sc mr_logmag" to '
+                             'logs_wavernn/checkpoints/scores.txt (default: off; with --synthetic, hp.voc_gen_at_checkpoint more synthetic '
+                             'utterances are held out for it)')
     parser.add_argument('--reference_body', action='store_true',
                         help="run the reference's loop body (model(x, m) + torch loss) instead of the fused training_loss")
     return parser
@@ -305,6 +337,8 @@ def main(argv=None):
     if args.synthetic:
         sig_bits = 16 if hp.voc_mode == 'MOL' else hp.bits
         train, test = synthetic_pairs(args.synthetic, 40, bits=sig_bits, n_mels=hp.num_mels, hop_length=hp.hop_length), []
+        if args.score_at_checkpoint:   # the synthetic run holds nothing out: utterances of another seed stand in, the training set stays
+            test = synthetic_pairs(hp.voc_gen_at_checkpoint, 40, bits=sig_bits, n_mels=hp.num_mels, hop_length=hp.hop_length, seed=1)
     elif args.wav_dir:
         from .dataset import DeviceCorpus
         wavs = sorted(Path(args.wav_dir).expanduser().glob('*.wav'))
@@ -334,19 +368,11 @@ def main(argv=None):
             raise ValueError('--reference_body: pass your own MOL loss to voc_train_loop; the CLI only carries F.cross_entropy')
         loss_func = F.cross_entropy
 
-    def at_checkpoint(mod, test_set, step):       # gen_testset (dataset.py:18-43): vocode a few held-out mels next to the checkpoint
-        from .dsp import decode_mu_law, label_2_float, save_wav
-        k = step // 1000
-        batch_str = f'gen_batched_target{hp.voc_target}_overlap{hp.voc_overlap}' if hp.voc_gen_batched else 'gen_NOT_BATCHED'
-        for i, pair in enumerate(test_set[:hp.voc_gen_at_checkpoint], 1):
-            mel, x = WindowLoader._arrays(pair)       # (wav path, mel path) of .npy files, or in-memory (mel (n_mels, frames), labels)
-            # the quantised target (:28-37): decoded and kept next to the generated file, as the reference does
-            bits = 16 if hp.voc_mode == 'MOL' else hp.bits
-            x = decode_mu_law(x, 2 ** bits, from_labels=True) if (hp.mu_law and hp.voc_mode != 'MOL') else label_2_float(x.astype(np.float64), bits)
-            save_wav(x, paths.voc_output / f'{k}k_steps_{i}_target.wav')
-            m = torch.from_numpy(np.ascontiguousarray(mel, dtype=np.float32)).unsqueeze(0)
-            mod.generate(m, str(paths.voc_output / f'{k}k_steps_{i}_{batch_str}.wav'), hp.voc_gen_batched, hp.voc_target,
-                         hp.voc_overlap, hp.mu_law)
+    scorer = None
+    if args.score_at_checkpoint:
+        from .frontend import SpectralScore
+        scorer = SpectralScore(hp, features=args.features)
+    at_checkpoint = checkpoint_generator(hp, paths, scorer)
 
     voc_train_loop(paths, model, loss_func, optimizer, loader, test, hp.voc_lr, total,
                    clip_grad_norm=hp.voc_clip_grad_norm, checkpoint_every=hp.voc_checkpoint_every, at_checkpoint=at_checkpoint,
