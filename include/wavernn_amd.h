@@ -419,6 +419,22 @@ int32_t wrnn_teamg_weight_format(const wrnn_handle *h);
  * (elements) are unchanged, every byte figure -- weight_bytes, resident_bytes_*, lds_bytes, streamed_bytes_step -- counts 2-byte
  * weights, and more units fit the same budget.  activation_bytes and mail_granules do not depend on the format. */
 int wrnn_teamg_plan_fmt(const wrnn_config *cfg, int32_t rows_per_team, int32_t weight_format, int64_t lds_budget_bytes, wrnn_teamg_plan_info *out);
+/* 8-bit weight image for the same two kernels (added to ABI 9: one new entry point, one new value).  WRNN_WEIGHTS_E4M3 stores the six
+ * matrices as OCP e4m3fn bytes with ONE power-of-two scale per image layer (fc3, fc2, fc1, rnn2, rnn1, I[:, 1:]; a GRU layer is weight_ih
+ * and weight_hh together, all three gates): s = 2^e, e the smallest integer with max|w| / 2^e <= 448, clamped to e >= -126 so that s
+ * is a normal float; s = 1 for an all-zero layer.  A stored byte is RNE(w / s), subnormals kept; nothing can saturate.  The kernels
+ * widen a byte exactly, multiply and add in the fp32 kernels' order and multiply a row's sums by s once; a power of two commutes with
+ * every rounding, so the outputs are bit-equal to the fp32 kernels' on the dequantised model (byte * s), as long as no product of that
+ * run is subnormal.  Weights below max|w| 2^-15 of their layer fall into e4m3's subnormals and lose relative precision; below
+ * max|w| 2^-19 they become zero.  Everything else stays fp32 as with WRNN_WEIGHTS_F16.  The pack finds the six maxima on the device and
+ * waits once for them; a weight that is not finite fails the generate call with WRNN_ERR_UNSUPPORTED, naming the layer, and the handle
+ * still generates after WRNN_WEIGHTS_F32 is set.  A finite weight of any size is accepted: the scale absorbs it.
+ * Value 2 is reserved and stays WRNN_ERR_INVALID in wrnn_teamg_set_weight_format and wrnn_teamg_plan_fmt.  With WRNN_WEIGHTS_E4M3
+ * wrnn_teamg_plan_fmt counts 1-byte weights. */
+#define WRNN_WEIGHTS_E4M3 3
+/* The six scales of the image last packed on h, in the order fc3, fc2, fc1, rnn2, rnn1, I; 1.0 each for an fp32 or fp16 image, after a
+ * refused pack and before any pack. */
+int wrnn_teamg_weight_scales(const wrnn_handle *h, float out[6]);
 
 /* ---- streaming generation (ABI 7) -------------------------------------------------------------------------------------------
  * Mel frames arrive a few at a time (Tacotron's decoder); audio leaves as soon as the frames it depends on are in.  A stream

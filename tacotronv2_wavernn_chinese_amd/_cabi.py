@@ -43,7 +43,7 @@ EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wr
                     'wrnn_resample_create', 'wrnn_resample_out_len', 'wrnn_resample_bank', 'wrnn_resample', 'wrnn_resample_last_error',
                     'wrnn_resample_destroy', 'wrnn_condition_frames', 'wrnn_condition', 'wrnn_teamg_plan', 'wrnn_debug_teamg_lds_budget',
                     'wrnn_teamg_batch_plan', 'wrnn_last_batch_rows', 'wrnn_teamg_set_weight_format', 'wrnn_teamg_weight_format',
-                    'wrnn_teamg_plan_fmt', 'wrnn_train_last_recurrence', 'wrnn_train_teamg_plan',
+                    'wrnn_teamg_plan_fmt', 'wrnn_teamg_weight_scales', 'wrnn_train_last_recurrence', 'wrnn_train_teamg_plan',
                     'wrnn_train_set_precision', 'wrnn_train_precision', 'wrnn_train_last_gemms', 'wrnn_debug_train_gemm',
                     'wrnn_griffin_create', 'wrnn_griffin_samples', 'wrnn_griffin_tables', 'wrnn_griffin_lim', 'wrnn_deemphasis',
                     'wrnn_griffin_last_error', 'wrnn_griffin_destroy',
@@ -161,6 +161,9 @@ class ScoreConfig(C.Structure):
 
 WEIGHT_FORMATS = {'f32': 0, 'f16': 1}   # WRNN_WEIGHTS_*: the element type of the TEAMG / TEAMG_BATCH weight image
 WEIGHT_FORMAT_NAMES = {v: k for k, v in WEIGHT_FORMATS.items()}
+# every format of that image, WRNN_WEIGHTS_E4M3 included (code 2 is reserved): what the setters and teamg_plan_fmt validate against
+TEAMG_WEIGHT_FORMATS = {**WEIGHT_FORMATS, 'e4m3': 3}
+TEAMG_WEIGHT_FORMAT_NAMES = {v: k for k, v in TEAMG_WEIGHT_FORMATS.items()}
 TEAMG_LAYER_NAMES = ('fc3', 'fc2', 'fc1', 'rnn2', 'rnn1', 'cond')   # WRNN_TEAMG_*: the order in which layers are given LDS residency
 
 
@@ -193,10 +196,10 @@ def teamg_plan(lds_budget_bytes: int = -1, *, rnn_dims, fc_dims, bits, pad, upsa
     cfg.mode = MODE_RAW if mode == 'RAW' else MODE_MOL
     info = TeamgPlanInfo()
     if weights is not None:
-        if weights not in WEIGHT_FORMATS:
-            raise ValueError(f'weights must be one of {sorted(WEIGHT_FORMATS)}, not {weights!r}')
+        if not isinstance(weights, str) or weights not in TEAMG_WEIGHT_FORMATS:
+            raise ValueError(f'weights must be one of {sorted(TEAMG_WEIGHT_FORMATS)}, not {weights!r}')
         rows = 1 if rows_per_team is None else int(rows_per_team)
-        rc = load_library().wrnn_teamg_plan_fmt(C.byref(cfg), rows, WEIGHT_FORMATS[weights], int(lds_budget_bytes), C.byref(info))
+        rc = load_library().wrnn_teamg_plan_fmt(C.byref(cfg), rows, TEAMG_WEIGHT_FORMATS[weights], int(lds_budget_bytes), C.byref(info))
         what = f'wrnn_teamg_plan_fmt({rows} rows per team, {weights} weights)'
     elif rows_per_team is None:
         rc, what = load_library().wrnn_teamg_plan(C.byref(cfg), int(lds_budget_bytes), C.byref(info)), 'wrnn_teamg_plan'
@@ -259,8 +262,9 @@ def train_teamg_plan(rnn_dims: int, rows: int) -> dict:
 
 
 def teamg_plan_fmt(rows_per_team: int, weights: str, lds_budget_bytes: int = -1, **dims) -> dict:
-    """Host-only ``wrnn_teamg_plan_fmt``: :func:`teamg_batch_plan` for the weight image format ``weights`` ('f32' or 'f16').  Same dict; with
-    'f16' every byte figure counts 2-byte weights and more units fit the same LDS budget, ownership and ``k_padded`` are unchanged."""
+    """Host-only ``wrnn_teamg_plan_fmt``: :func:`teamg_batch_plan` for the weight image format ``weights`` (a key of ``TEAMG_WEIGHT_FORMATS``).  Same dict;
+    with 'f16' every byte figure counts 2-byte weights, with 'e4m3' 1-byte weights, and more units fit the same LDS budget; ownership and
+    ``k_padded`` are unchanged."""
     return teamg_plan(lds_budget_bytes, rows_per_team=int(rows_per_team), weights=weights, **dims)
 
 
@@ -373,6 +377,8 @@ def load_library() -> C.CDLL:
     lib.wrnn_teamg_set_weight_format.restype = C.c_int
     lib.wrnn_teamg_weight_format.argtypes = [vp]
     lib.wrnn_teamg_weight_format.restype = C.c_int32
+    lib.wrnn_teamg_weight_scales.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.wrnn_teamg_weight_scales.restype = C.c_int
     lib.wrnn_train_last_recurrence.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.wrnn_train_last_recurrence.restype = C.c_int
     lib.wrnn_train_teamg_plan.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -721,15 +727,22 @@ class NativeVocoder:
         self._check(self.lib.wrnn_debug_teamg_lds_budget(self._h, int(lds_budget_bytes)))
 
     def set_teamg_weights(self, fmt: str):
-        """The element type of the TEAMG / TEAMG_BATCH weight image, 'f32' or 'f16' (``wrnn_teamg_set_weight_format``); a change makes the next
-        call of either kernel pack the image again.  No other kernel reads it."""
-        if fmt not in WEIGHT_FORMATS:
-            raise ValueError(f'teamg weights must be one of {sorted(WEIGHT_FORMATS)}, not {fmt!r}')
-        self._check(self.lib.wrnn_teamg_set_weight_format(self._h, WEIGHT_FORMATS[fmt]))
+        """The element type of the TEAMG / TEAMG_BATCH weight image, 'f32', 'f16' or 'e4m3' (``wrnn_teamg_set_weight_format``); a change makes
+        the next call of either kernel pack the image again.  No other kernel reads it."""
+        if not isinstance(fmt, str) or fmt not in TEAMG_WEIGHT_FORMATS:
+            raise ValueError(f'teamg weights must be one of {sorted(TEAMG_WEIGHT_FORMATS)}, not {fmt!r}')
+        self._check(self.lib.wrnn_teamg_set_weight_format(self._h, TEAMG_WEIGHT_FORMATS[fmt]))
 
     @property
     def teamg_weights(self) -> str:
-        return WEIGHT_FORMAT_NAMES[int(self.lib.wrnn_teamg_weight_format(self._h))]
+        return TEAMG_WEIGHT_FORMAT_NAMES[int(self.lib.wrnn_teamg_weight_format(self._h))]
+
+    def teamg_weight_scales(self) -> np.ndarray:
+        """The six per-layer scales of the image last packed (``wrnn_teamg_weight_scales``), in the order fc3, fc2, fc1, rnn2, rnn1, I;
+        ones unless that image was 'e4m3'."""
+        out = (C.c_float * 6)()
+        self._check(self.lib.wrnn_teamg_weight_scales(self._h, out))
+        return np.array(out[:], np.float32)
 
     def last_timing(self) -> dict:
         t = Timing()

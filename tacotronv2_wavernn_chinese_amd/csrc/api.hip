@@ -235,12 +235,18 @@ int wrnn_debug_teamg_lds_budget(wrnn_handle *h, int64_t bytes) {
 }
 int wrnn_teamg_set_weight_format(wrnn_handle *h, int32_t fmt) {
     if (!h) return WRNN_ERR_INVALID;
-    if (fmt != WRNN_WEIGHTS_F32 && fmt != WRNN_WEIGHTS_F16) return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_teamg_set_weight_format: %d is neither WRNN_WEIGHTS_F32 nor WRNN_WEIGHTS_F16", fmt);
+    if (fmt != WRNN_WEIGHTS_F32 && fmt != WRNN_WEIGHTS_F16 && fmt != WRNN_WEIGHTS_E4M3)   // 2 is reserved
+        return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_teamg_set_weight_format: %d is none of WRNN_WEIGHTS_F32, WRNN_WEIGHTS_F16, WRNN_WEIGHTS_E4M3", fmt);
     if (fmt != h->teamg_fmt) h->teamg_img_ok = false;   // the next TEAMG / TEAMG_BATCH call packs the image in the new element type
     h->teamg_fmt = fmt;
     return WRNN_OK;
 }
 int32_t wrnn_teamg_weight_format(const wrnn_handle *h) { return h ? h->teamg_fmt : WRNN_WEIGHTS_F32; }
+int wrnn_teamg_weight_scales(const wrnn_handle *h, float out[6]) {
+    if (!h || !out) return WRNN_ERR_INVALID;
+    for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) out[l] = h->teamg_scale[l];
+    return WRNN_OK;
+}
 int32_t wrnn_n_classes(const wrnn_handle *h) { return h ? h->d.NC : 0; }
 int64_t wrnn_loop_weight_bytes(const wrnn_handle *h) { return h ? h->loop_weight_bytes : 0; }
 
@@ -594,7 +600,12 @@ static int teamg_image(wrnn_handle *h, const WrnnTeamGPlan &plan, hipStream_t s)
     if (h->teamg_img) { (void)hipFree(h->teamg_img); h->teamg_img = nullptr; }
     WRNN_HIP_TRY(h, hipMalloc(&h->teamg_img, wrnn_teamg_img_bytes(plan)));
     int bad = -1;
-    WRNN_HIP_TRY(h, wrnn_teamg_pack(h, plan, h->teamg_img, s, &bad));
+    WRNN_HIP_TRY(h, wrnn_teamg_pack(h, plan, h->teamg_img, s, &bad, h->teamg_scale));
+    if (bad >= 0 && plan.esz == 1) {
+        for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) h->teamg_scale[l] = 1.0f;
+        return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "WRNN_WEIGHTS_E4M3: a weight of layer %s is not finite, the layer has no scale; the fp32 image runs whatever the weights",
+                         wrnn_teamg_layer_names[bad]);
+    }
     if (bad >= 0)
         return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "WRNN_WEIGHTS_F16: a weight of layer %s does not round to a finite fp16 (|w| >= 65520); use WRNN_WEIGHTS_F32 for this model",
                          wrnn_teamg_layer_names[bad]);
@@ -602,7 +613,11 @@ static int teamg_image(wrnn_handle *h, const WrnnTeamGPlan &plan, hipStream_t s)
     WRNN_HIP_TRY(h, hipEventRecord(h->ev[1], s));   // the one-time image is not loop time
     return WRNN_OK;
 }
-static int teamg_esz(const wrnn_handle *h) { return h->teamg_fmt == WRNN_WEIGHTS_F16 ? 2 : 4; }
+static int teamg_esz(const wrnn_handle *h) { return h->teamg_fmt == WRNN_WEIGHTS_E4M3 ? 1 : h->teamg_fmt == WRNN_WEIGHTS_F16 ? 2 : 4; }
+// the scales of the packed image into a plan made for this call (wrnn_teamg_make_plan leaves them 1)
+static void teamg_plan_scales(const wrnn_handle *h, WrnnTeamGPlan &p) {
+    for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) p.L[l].scale = h->teamg_scale[l];
+}
 
 // The team kernel for any dims (loop_teamg.hip): one row per XCD team at a time, one launch.  Placement and residency are settled here,
 // before the launch; whatever keeps the kernel from running is an error with its reason, never another kernel.
@@ -618,6 +633,7 @@ static int run_teamg(wrnn_handle *h, const WrnnLoopArgs &a, int snake, int n_slo
         return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "WRNN_KERNEL_TEAMG: loop_teamg_kernel cannot be resident on a CU with %zu bytes of LDS (%s)",
                          wrnn_teamg_lds_bytes(ga.plan), oe != hipSuccess ? hipGetErrorString(oe) : "occupancy 0");
     if (int rc = teamg_image(h, ga.plan, s)) return rc;
+    teamg_plan_scales(h, ga.plan);
     ga.a = a; ga.img = h->teamg_img; ga.sched = h->sched_dev; ga.n_slots = n_slots; ga.ragged = snake; ga.n_teams = h->n_teams;
     ga.mail = h->mail; ga.ctl = h->ctl;
     const size_t mail_bytes = (size_t)h->n_teams * ga.plan.mail_granules * sizeof(unsigned long long);   // sized from the dims; <= WRNN_MAIL_BYTES
@@ -640,6 +656,7 @@ static int run_teamg_batch(wrnn_handle *h, const WrnnLoopArgs &a, int snake, int
         return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "WRNN_KERNEL_TEAMG_BATCH: loop_teamg_batch_kernel<%d> cannot be resident on a CU with %zu bytes of LDS (%s)", rb,
                          wrnn_teamg_lds_bytes(ga.plan), oe != hipSuccess ? hipGetErrorString(oe) : "occupancy 0");
     if (int rc = teamg_image(h, ga.plan, s)) return rc;
+    teamg_plan_scales(h, ga.plan);
     ga.a = a; ga.img = h->teamg_img; ga.order = h->order_dev; ga.rpb = rpb; ga.snake = snake; ga.n_teams = h->n_teams;
     ga.mail = h->mail; ga.ctl = h->ctl;
     const size_t mail_bytes = (size_t)h->n_teams * ga.plan.mail_granules * sizeof(unsigned long long);   // <= WRNN_MAIL_BYTES: the plan refuses more

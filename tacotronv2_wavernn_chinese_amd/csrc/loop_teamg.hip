@@ -19,7 +19,9 @@
 // half the bytes streamed, twice the units resident, rows permuted at pack time so that a lane's 16-byte load brings the weights of two
 // steps (teamg_layout.h).  Only the six matrices change type; activations, sums, biases, W_I[:, 0], cells and samplers are fp32, and
 // since a binary16 widens exactly and the multiply-adds keep their order, the outputs are those of the fp32 instantiation on the model
-// with its matrices rounded to fp16.
+// with its matrices rounded to fp16.  TgE4m3 (WRNN_WEIGHTS_E4M3): OCP e4m3fn bytes with one power-of-two scale per layer,
+// a quarter of the bytes, rows permuted so that a 16-byte load brings the weights of four steps; a row's segment sums are multiplied by
+// the layer's scale, which commutes with every rounding: the outputs are the fp32 instantiation's on the dequantised model.
 //
 // One step = five exchanges on the serial chain plus one beside it:
 //   [xc]  the conditioning's share of I, W_I[:, 1:] . [m_t | a1_t] + b_I, for step t + 1 -- published under exchange 2 of step t
@@ -30,6 +32,7 @@
 //   4. relu(fc2 . [fc1 | a4_t])                                      -> [fc2]                :220-221
 //   5. fc3 rows of the own classes; RAW: + noise, race inside the workgroup, -> [32 candidates (value, class)], every workgroup
 //      picks the winner; MOL: -> [30 outputs], every workgroup runs the sampler                :223-237
+#include <cstring>
 #include <type_traits>
 
 #include "team_common.h"
@@ -126,11 +129,103 @@ __device__ __forceinline__ void tg_dot16(const TgHalf8 *__restrict__ rp, int kp8
     for (int g = 0; g < G; ++g) sb[g] = row_sum(a0[g] + a1[g]);
 }
 
-// G rows from row `row0` of a layer's slice at `base` (LDS or device memory), KP elements each, in the image's element type
+// tg_dot on the e4m3 image (teamg_layout.h): rp = the unit's first row, rows KP bytes apart, row0 its index in the slice.  One 16-byte load
+// per row and QUAD of steps, a block of four quads issued together -- tg_dot's bytes in flight; two for a unit of three rows --; what is left
+// of a segment (less than a block: quads, an
+// 8-byte pair, a 4-byte single step) is loaded together before any of it is used, so a short segment has all its loads in flight at once.
+// Per step the same four weights, widened exactly (two v_cvt_pk_f32_fp8), into the same a0 / a1 chains in the same order.  The sums are
+// those of the stored bytes: the caller applies the layer's scale.
+template <int G>
+__device__ __forceinline__ void tg_dot8(const unsigned char *__restrict__ rp, int KP, int row0, int q, const float4 *xp, int nA, int nK, float (&sa)[G],
+                                        float (&sb)[G]) {
+    constexpr int NB = G == 1 ? 4 : 2;   // quads of a block: 64 bytes per lane in flight for a row, 2 x 3 x 16 for a unit (the registers' limit)
+    const uint4 *wq[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) wq[g] = (const uint4 *)(rp + (size_t)g * KP) + ((q + tg8_rot(row0 + g, KP)) & 15);
+    float a0[G], a1[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) a0[g] = a1[g] = 0.0f;
+    auto mac = [&](int g, const float4 &w, const float4 &x) {
+        a0[g] = fmaf(w.x, x.x, a0[g]); a1[g] = fmaf(w.y, x.y, a1[g]);
+        a0[g] = fmaf(w.z, x.z, a0[g]); a1[g] = fmaf(w.w, x.w, a1[g]);
+    };
+    // the four steps of a quad from step k
+    auto quad = [&](const uint4 (&w)[G], int k) {
+        // two steps at a time, as tg_dot16 has them: the activation reads and the widened weights of a whole block, scheduled early,
+        // would not fit the registers
+        const float4 x0 = xp[k * 16], x1 = xp[(k + 1) * 16];
+#pragma unroll
+        for (int g = 0; g < G; ++g) { mac(g, tg8_w4(w[g].x), x0); mac(g, tg8_w4(w[g].y), x1); }
+        __builtin_amdgcn_sched_barrier(0);
+        const float4 x2 = xp[(k + 2) * 16], x3 = xp[(k + 3) * 16];
+#pragma unroll
+        for (int g = 0; g < G; ++g) { mac(g, tg8_w4(w[g].z), x2); mac(g, tg8_w4(w[g].w), x3); }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto segment = [&](int k0, int k1) {
+        int k = k0;
+#pragma unroll 1
+        for (; k + 4 * NB <= k1; k += 4 * NB) {
+            uint4 w[NB][G];
+#pragma unroll
+            for (int u = 0; u < NB; ++u)
+#pragma unroll
+                for (int g = 0; g < G; ++g) w[u][g] = wq[g][(k + 4 * u) * 4];
+#pragma unroll
+            for (int u = 0; u < NB; ++u) quad(w[u], k + 4 * u);
+        }
+        // less than a block left: every load of it first
+        const int rem = k1 - k, nq = rem >> 2, kp = k + 4 * nq, ks = kp + (rem & 2);
+        uint4 w[NB - 1][G];
+        uint2 wp[G];
+        unsigned ws[G];
+#pragma unroll
+        for (int u = 0; u < NB - 1; ++u)
+            if (u < nq) {
+#pragma unroll
+                for (int g = 0; g < G; ++g) w[u][g] = wq[g][(k + 4 * u) * 4];
+            }
+        if (rem & 2) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) wp[g] = ((const uint2 *)(rp + (size_t)g * KP + 64 * kp))[q];
+        }
+        if (rem & 1) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) ws[g] = ((const unsigned *)(rp + (size_t)g * KP + 64 * ks))[q];
+        }
+#pragma unroll
+        for (int u = 0; u < NB - 1; ++u)
+            if (u < nq) quad(w[u], k + 4 * u);
+        if (rem & 2) {
+            const float4 x0 = xp[kp * 16], x1 = xp[(kp + 1) * 16];
+#pragma unroll
+            for (int g = 0; g < G; ++g) { mac(g, tg8_w4(wp[g].x), x0); mac(g, tg8_w4(wp[g].y), x1); }
+        }
+        if (rem & 1) {
+            const float4 x = xp[ks * 16];
+#pragma unroll
+            for (int g = 0; g < G; ++g) mac(g, tg8_w4(ws[g]), x);
+        }
+    };
+    segment(0, nA);
+#pragma unroll
+    for (int g = 0; g < G; ++g) { sa[g] = row_sum(a0[g] + a1[g]); a0[g] = a1[g] = 0.0f; }
+    segment(nA, nK);
+#pragma unroll
+    for (int g = 0; g < G; ++g) sb[g] = row_sum(a0[g] + a1[g]);
+}
+
+// G rows from row `row0` of a layer's slice at `base` (LDS or device memory), KP elements each, in the image's element type; `scale` is the
+// layer's (e4m3 only: a power of two, so scaling the two sums equals scaling every weight)
 template <int G, typename WT>
-__device__ __forceinline__ void tg_rows(const WT *base, int row0, int KP, int q, const float4 *xp, int nA, int nK, float (&sa)[G], float (&sb)[G]) {
+__device__ __forceinline__ void tg_rows(const WT *base, int row0, int KP, float scale, int q, const float4 *xp, int nA, int nK, float (&sa)[G], float (&sb)[G]) {
     if constexpr (sizeof(WT) == 4) tg_dot<G>((const float4 *)(base + (size_t)row0 * KP) + q, KP / 4, xp, nA, nK, sa, sb);
-    else tg_dot16<G>((const TgHalf8 *)(base + (size_t)row0 * KP), KP / 8, row0, q, xp, nA, nK, sa, sb);
+    else if constexpr (sizeof(WT) == 2) tg_dot16<G>((const TgHalf8 *)(base + (size_t)row0 * KP), KP / 8, row0, q, xp, nA, nK, sa, sb);
+    else {
+        tg_dot8<G>((const unsigned char *)(base + (size_t)row0 * KP), KP, row0, q, xp, nA, nK, sa, sb);
+#pragma unroll
+        for (int g = 0; g < G; ++g) { sa[g] *= scale; sb[g] *= scale; }
+    }
 }
 
 template <typename WT>
@@ -206,10 +301,10 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
         const int nown = owned(L), nK = L.KP / 64;
         for (int ul = qw; ul < nown; ul += 32) {
             float sa[1], sb[1];
-            if (ul < L.nres) tg_rows<1>(wres + L.lds_off, ul, L.KP, q, (const float4 *)cbuf + q, nK, nK, sa, sb);
-            else tg_rows<1>(img + L.img_off, ul, L.KP, q, (const float4 *)cbuf + q, nK, nK, sa, sb);
+            if (ul < L.nres) tg_rows<1>(wres + L.lds_off, ul, L.KP, L.scale, q, (const float4 *)cbuf + q, nK, nK, sa, sb);
+            else tg_rows<1>(img + L.img_off, ul, L.KP, L.scale, q, (const float4 *)cbuf + q, nK, nK, sa, sb);
             const int j = g * L.U + ul;
-            if (q == 0) st_granule(mail, M_XC + (tag & 1u) * HP + j, tag, __float_as_uint(sa[0] + w[a.off.I_b + j]));
+            if (q == 0) tg_st_granule<WT>(mail, M_XC + (tag & 1u) * HP + j, tag, __float_as_uint(sa[0] + w[a.off.I_b + j]));
         }
     };
     // one GRU layer (get_gru_cell :273-279, gate rows [r; z; n]): h' of the own units -> mailbox.  xin = [input (KAP) | h (HP)]
@@ -223,8 +318,8 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
             for (int task = qw; task < 3 * nown; task += 32) {
                 const int ul = task / 3;
                 float sa[1], sb[1];
-                if (ul < L.nres) tg_rows<1>(wres + L.lds_off, task, L.KP, q, (const float4 *)xin + q, nA, nK, sa, sb);
-                else tg_rows<1>(img + L.img_off, task, L.KP, q, (const float4 *)xin + q, nA, nK, sa, sb);
+                if (ul < L.nres) tg_rows<1>(wres + L.lds_off, task, L.KP, L.scale, q, (const float4 *)xin + q, nA, nK, sa, sb);
+                else tg_rows<1>(img + L.img_off, task, L.KP, L.scale, q, (const float4 *)xin + q, nA, nK, sa, sb);
                 if (q == 0) { gs[2 * task] = sa[0]; gs[2 * task + 1] = sb[0]; }
             }
             __syncthreads();
@@ -234,15 +329,15 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
             if (by_row) {
                 const float *gs = lds + ly.gs + 6 * ul;
                 gi[0] = gs[0]; gh[0] = gs[1]; gi[1] = gs[2]; gh[1] = gs[3]; gi[2] = gs[4]; gh[2] = gs[5];
-            } else if (ul < L.nres) tg_rows<3>(wres + L.lds_off, ul * 3, L.KP, q, (const float4 *)xin + q, nA, nK, gi, gh);
-            else tg_rows<3>(img + L.img_off, ul * 3, L.KP, q, (const float4 *)xin + q, nA, nK, gi, gh);
+            } else if (ul < L.nres) tg_rows<3>(wres + L.lds_off, ul * 3, L.KP, L.scale, q, (const float4 *)xin + q, nA, nK, gi, gh);
+            else tg_rows<3>(img + L.img_off, ul * 3, L.KP, L.scale, q, (const float4 *)xin + q, nA, nK, gi, gh);
             const int j = g * L.U + ul;
             const float *bi = w + obih, *bh = w + obhh;
             const float rg = 1.0f / (1.0f + expf(-((gi[0] + bi[j]) + (gh[0] + bh[j]))));
             const float zg = 1.0f / (1.0f + expf(-((gi[1] + bi[H + j]) + (gh[1] + bh[H + j]))));
             const float ng = tanhf((gi[2] + bi[2 * H + j]) + rg * (gh[2] + bh[2 * H + j]));
             const float hn = (1.0f - zg) * ng + zg * xin[L.KAP + j];
-            if (by_row || q == 0) st_granule(mail, region + (epoch & 1u) * HP + j, epoch, __float_as_uint(hn));
+            if (by_row || q == 0) tg_st_granule<WT>(mail, region + (epoch & 1u) * HP + j, epoch, __float_as_uint(hn));
         }
     };
     // relu(W . x + b) of the own rows -> mailbox
@@ -250,10 +345,10 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
         const int nown = owned(L), nK = L.KP / 64;
         for (int ul = qw; ul < nown; ul += 32) {
             float sa[1], sb[1];
-            if (ul < L.nres) tg_rows<1>(wres + L.lds_off, ul, L.KP, q, (const float4 *)xin + q, nK, nK, sa, sb);
-            else tg_rows<1>(img + L.img_off, ul, L.KP, q, (const float4 *)xin + q, nK, nK, sa, sb);
+            if (ul < L.nres) tg_rows<1>(wres + L.lds_off, ul, L.KP, L.scale, q, (const float4 *)xin + q, nK, nK, sa, sb);
+            else tg_rows<1>(img + L.img_off, ul, L.KP, L.scale, q, (const float4 *)xin + q, nK, nK, sa, sb);
             const int j = g * L.U + ul;
-            if (q == 0) st_granule(mail, region + (epoch & 1u) * FCP + j, epoch, __float_as_uint(fmaxf(sa[0] + w[ob + j], 0.0f)));
+            if (q == 0) tg_st_granule<WT>(mail, region + (epoch & 1u) * FCP + j, epoch, __float_as_uint(fmaxf(sa[0] + w[ob + j], 0.0f)));
         }
     };
     // all N values of an exchanged vector, element j to thread j (+ 512, ...); whole waves take part, lanes past N re-read granule N - 1
@@ -335,8 +430,8 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
                 int bi = 0x7fffffff;
                 for (int ul = qw; ul < nown; ul += 32) {
                     float sa[1], sb[1];
-                    if (ul < L.nres) tg_rows<1>(wres + L.lds_off, ul, L.KP, q, (const float4 *)f3 + q, nK, nK, sa, sb);
-                    else tg_rows<1>(img + L.img_off, ul, L.KP, q, (const float4 *)f3 + q, nK, nK, sa, sb);
+                    if (ul < L.nres) tg_rows<1>(wres + L.lds_off, ul, L.KP, L.scale, q, (const float4 *)f3 + q, nK, nK, sa, sb);
+                    else tg_rows<1>(img + L.img_off, ul, L.KP, L.scale, q, (const float4 *)f3 + q, nK, nK, sa, sb);
                     const int c = g * L.U + ul;
                     const float lg = sa[0] + w[a.off.fc3_b + c];
                     if (a.logits_out && q == 0) a.logits_out[((size_t)t * a.n_rows + row) * NC + c] = lg;
@@ -347,7 +442,7 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
                         else if (a.noise_mode == WRNN_NOISE_PHILOX) v -= logf(-logf(wrnn_uniform_raw(kseed, (uint64_t)t, krow, (uint32_t)c)));
                         if (v > bv) { bv = v; bi = c; }   // classes ascend: ties keep the lowest
                     } else if (q == 0) {
-                        st_granule(mail, M_CAND + par * 64 + c, epoch, __float_as_uint(lg));
+                        tg_st_granule<WT>(mail, M_CAND + par * 64 + c, epoch, __float_as_uint(lg));
                     }
                 }
                 if (d.mode == WRNN_MODE_RAW) {
@@ -358,8 +453,8 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
                         int k = lane < 32 ? misc_i[64 + lane] : 0x7fffffff;
                         wave_argmax(v, k);
                         if (lane == 0) {   // the workgroup's candidate: granule g = value, 32 + g = class
-                            st_granule(mail, M_CAND + par * 64 + g, epoch, __float_as_uint(v));
-                            st_granule(mail, M_CAND + par * 64 + 32 + g, epoch, (unsigned)k);
+                            tg_st_granule<WT>(mail, M_CAND + par * 64 + g, epoch, __float_as_uint(v));
+                            tg_st_granule<WT>(mail, M_CAND + par * 64 + 32 + g, epoch, (unsigned)k);
                         }
                         const float pv = take_staggered(mail, M_CAND + par * 64 + lane, epoch, dead, a.err, 15u);
                         const int ck = __shfl(__float_as_int(pv), (lane + 32) & 63, 64);
@@ -435,7 +530,42 @@ __global__ void __launch_bounds__(256) teamg_pack_kernel(const float *__restrict
     }
 }
 
+// The e4m3 pack: the same element as RNE(w * inv) in OCP e4m3fn (v_cvt_pk_fp8_f32 in the default rounding mode, subnormals kept), where
+// inv = 1 / the layer's scale, a power of two: |w| * inv <= 448, nothing saturates.  tg8_pos places the byte.
+__global__ void __launch_bounds__(256) teamg_pack8_kernel(const float *__restrict__ src_t, int ld, int row0, int k0, int K, unsigned char *__restrict__ img,
+                                                          size_t wg_stride, size_t layer_off, int N, int U, int G, int gate, int KAP, int KP, int kdst, float inv) {
+    const int unit = blockIdx.x;   // < N
+    const int g = unit / U, ul = unit - g * U;
+    const int row = ul * G + gate;
+    unsigned char *dst = img + (size_t)g * wg_stride + layer_off + (size_t)row * KP;
+    for (int k = threadIdx.x; k < K; k += 256) {
+        const float v = src_t[(size_t)(k0 + k) * ld + row0 + unit] * inv;
+        dst[tg8_pos(kdst + k, row, KAP, KP)] = (unsigned char)(__builtin_amdgcn_cvt_pk_fp8_f32(v, 0.0f, 0, false) & 0xff);
+    }
+}
+
+// The abs-max pass of the e4m3 pack: *out = max(*out, bits of |w|) over rows [k0, k0 + K) x columns [c0, c0 + N) of src_t.  The bits of
+// non-negative floats order as the floats do, and those of an infinity or a NaN are at or above 0x7f800000: one word is the maximum
+// and the non-finite flag.  One block per row of src_t, columns across the threads.
+__global__ void __launch_bounds__(256) teamg_absmax_kernel(const float *__restrict__ src_t, int ld, int c0, int k0, int N, unsigned *out) {
+    const float *src = src_t + (size_t)(k0 + blockIdx.x) * ld + c0;
+    unsigned m = 0;
+    for (int j = threadIdx.x; j < N; j += 256) {
+        const unsigned b = __float_as_uint(src[j]) & 0x7fffffffu;
+        m = b > m ? b : m;
+    }
+    if (m) atomicMax(out, m);
+}
+
 }  // namespace
+
+float wrnn_teamg_e4m3_scale(float amax) {
+    if (!(amax > 0.0f)) return 1.0f;
+    int e;
+    const float f = frexpf(amax, &e);   // amax = f 2^e, 0.5 <= f < 1; 448 = 0.875 * 2^9
+    e -= f <= 0.875f ? 9 : 8;
+    return ldexpf(1.0f, e < -126 ? -126 : e);
+}
 
 const char *const wrnn_teamg_layer_names[WRNN_TEAMG_LAYERS] = {"fc3", "fc2", "fc1", "rnn2", "rnn1", "I"};
 
@@ -447,6 +577,7 @@ const char *wrnn_teamg_make_plan(const WrnnDims &d, int64_t budget, WrnnTeamGPla
     auto set = [&](int l, int N, int G, int KA, int KB) {
         WrnnTeamGLayer &L = p.L[l];
         L.N = N; L.G = G; L.KA = KA; L.KB = KB; L.KAP = tg_r64(KA); L.KP = L.KAP + (KB ? tg_r64(KB) : 0); L.U = (N + TEAM_WGS - 1) / TEAM_WGS;
+        L.scale = 1.0f;
     };
     set(WRNN_TEAMG_FC3, d.NC, 1, d.FC, 0);
     set(WRNN_TEAMG_FC2, d.FC, 1, d.FC + d.A, 0);
@@ -471,7 +602,7 @@ const char *wrnn_teamg_make_plan(const WrnnDims &d, int64_t budget, WrnnTeamGPla
     if (budget < 0 || budget > dflt) budget = dflt;
     // Residency in layer order (shortest rows first): whole units, as many as still fit; the first layer that does not fit whole is the
     // last to get any (so a layer's resident share never shrinks when the budget grows).  Every workgroup gets the same count.
-    // Counted in elements of esz bytes; a unit is a multiple of 64 elements, so every offset is a multiple of 16 bytes in either format.
+    // Counted in elements of esz bytes; a unit is a multiple of 64 elements, so every offset is a multiple of 16 bytes in every format.
     int64_t left = budget / esz, img = 0, res = 0;
     for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) {
         WrnnTeamGLayer &L = p.L[l];
@@ -490,25 +621,55 @@ const char *wrnn_teamg_make_plan(const WrnnDims &d, int64_t budget, WrnnTeamGPla
     return nullptr;
 }
 
-hipError_t wrnn_teamg_pack(const wrnn_handle *h, const WrnnTeamGPlan &p, void *img, hipStream_t s, int *bad_layer) {
+hipError_t wrnn_teamg_pack(const wrnn_handle *h, const WrnnTeamGPlan &p, void *img, hipStream_t s, int *bad_layer, float scales[WRNN_TEAMG_LAYERS]) {
     const WrnnDims &d = h->d;
     const WrnnPacked &o = h->off;
     const float *w = h->wdev;
+    const int H = d.H, A = d.A, FC = d.FC;
     *bad_layer = -1;
-    hipError_t e = hipMemsetAsync(img, 0, wrnn_teamg_img_bytes(p), s);   // padding elements and the range flags
+    for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) scales[l] = 1.0f;
+    hipError_t e = hipMemsetAsync(img, 0, wrnn_teamg_img_bytes(p), s);   // padding elements and the words behind the slices
     if (e != hipSuccess) return e;
     (void)hipGetLastError();
     int32_t *flags = (int32_t *)((char *)img + (size_t)TEAM_WGS * p.img_elems_wg * p.esz);   // one word per layer behind the slices
+    if (p.esz == 1) {
+        // the six maxima, all gates and both matrices of a GRU layer together (they share image rows); the only wait of this pack
+        auto amax = [&](int l, const float *src_t, int ld, int c0, int k0, int K, int N) {
+            hipLaunchKernelGGL(teamg_absmax_kernel, dim3(K), dim3(256), 0, s, src_t, ld, c0, k0, N, (unsigned *)flags + l);
+        };
+        amax(WRNN_TEAMG_FC3, w + o.fc3_t, d.NC, 0, 0, FC, d.NC);
+        amax(WRNN_TEAMG_FC2, w + o.fc2_t, FC, 0, 0, FC + A, FC);
+        amax(WRNN_TEAMG_FC1, w + o.fc1_t, FC, 0, 0, H + A, FC);
+        amax(WRNN_TEAMG_RNN2, w + o.r2_wih_t, 3 * H, 0, 0, H + A, 3 * H);
+        amax(WRNN_TEAMG_RNN2, w + o.r2_whh_t, 3 * H, 0, 0, H, 3 * H);
+        amax(WRNN_TEAMG_RNN1, w + o.r1_wih_t, 3 * H, 0, 0, H, 3 * H);
+        amax(WRNN_TEAMG_RNN1, w + o.r1_whh_t, 3 * H, 0, 0, H, 3 * H);
+        amax(WRNN_TEAMG_COND, w + o.I_t, H, 0, 1, d.F + A, H);
+        e = hipGetLastError();
+        uint32_t bits[WRNN_TEAMG_LAYERS];
+        if (e == hipSuccess) e = hipMemcpyAsync(bits, flags, sizeof(bits), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return e;
+        for (int l = WRNN_TEAMG_LAYERS - 1; l >= 0; --l) {
+            if (bits[l] >= 0x7f800000u) { *bad_layer = l; continue; }
+            float m;
+            memcpy(&m, &bits[l], sizeof(m));
+            scales[l] = wrnn_teamg_e4m3_scale(m);
+        }
+        if (*bad_layer >= 0) return hipSuccess;
+    }
     auto put = [&](int l, const float *src_t, int ld, int row0, int k0, int K, int gate, int kdst) {
         const WrnnTeamGLayer &L = p.L[l];
-        if (p.esz == 4)
+        if (p.esz == 1)
+            hipLaunchKernelGGL(teamg_pack8_kernel, dim3(L.N), dim3(256), 0, s, src_t, ld, row0, k0, K, (unsigned char *)img, (size_t)p.img_elems_wg, (size_t)L.img_off,
+                               L.N, L.U, L.G, gate, L.KAP, L.KP, kdst, 1.0f / scales[l]);
+        else if (p.esz == 4)
             hipLaunchKernelGGL(teamg_pack_kernel<float>, dim3(L.N), dim3(256), 0, s, src_t, ld, row0, k0, K, (float *)img, (size_t)p.img_elems_wg, (size_t)L.img_off,
                                L.N, L.U, L.G, gate, L.KAP, L.KP, kdst, flags + l);
         else
             hipLaunchKernelGGL(teamg_pack_kernel<_Float16>, dim3(L.N), dim3(256), 0, s, src_t, ld, row0, k0, K, (_Float16 *)img, (size_t)p.img_elems_wg,
                                (size_t)L.img_off, L.N, L.U, L.G, gate, L.KAP, L.KP, kdst, flags + l);
     };
-    const int H = d.H, A = d.A, FC = d.FC;
     put(WRNN_TEAMG_FC3, w + o.fc3_t, d.NC, 0, 0, FC, 0, 0);
     put(WRNN_TEAMG_FC2, w + o.fc2_t, FC, 0, 0, FC + A, 0, 0);
     put(WRNN_TEAMG_FC1, w + o.fc1_t, FC, 0, 0, H + A, 0, 0);
@@ -520,7 +681,7 @@ hipError_t wrnn_teamg_pack(const wrnn_handle *h, const WrnnTeamGPlan &p, void *i
     }
     put(WRNN_TEAMG_COND, w + o.I_t, H, 0, 1, d.F + A, 0, 0);   // column 0 (the fed-back sample) stays a vector
     e = hipGetLastError();
-    if (e != hipSuccess || p.esz == 4) return e;
+    if (e != hipSuccess || p.esz != 2) return e;
     // the range check of the fp16 image: once per pack, the only wait
     int32_t bad[WRNN_TEAMG_LAYERS];
     e = hipMemcpyAsync(bad, flags, sizeof(bad), hipMemcpyDeviceToHost, s);
@@ -532,7 +693,7 @@ hipError_t wrnn_teamg_pack(const wrnn_handle *h, const WrnnTeamGPlan &p, void *i
 }
 
 static const void *teamg_kernel_fn(const WrnnTeamGPlan &p) {
-    return p.esz == 4 ? (const void *)loop_teamg_kernel<float> : (const void *)loop_teamg_kernel<_Float16>;
+    return p.esz == 4 ? (const void *)loop_teamg_kernel<float> : p.esz == 2 ? (const void *)loop_teamg_kernel<_Float16> : (const void *)loop_teamg_kernel<TgE4m3>;
 }
 
 hipError_t wrnn_teamg_occupancy(const WrnnTeamGPlan &p, int *blocks_per_cu) {
@@ -548,7 +709,8 @@ hipError_t wrnn_launch_loop_teamg(const WrnnTeamGArgs &a, hipStream_t s) {
     hipError_t e = hipFuncSetAttribute(teamg_kernel_fn(a.plan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     if (a.plan.esz == 4) hipLaunchKernelGGL(loop_teamg_kernel<float>, dim3(a.n_teams * TEAM_WGS), dim3(TG_THREADS), lds, s, a);
-    else hipLaunchKernelGGL(loop_teamg_kernel<_Float16>, dim3(a.n_teams * TEAM_WGS), dim3(TG_THREADS), lds, s, a);
+    else if (a.plan.esz == 2) hipLaunchKernelGGL(loop_teamg_kernel<_Float16>, dim3(a.n_teams * TEAM_WGS), dim3(TG_THREADS), lds, s, a);
+    else hipLaunchKernelGGL(loop_teamg_kernel<TgE4m3>, dim3(a.n_teams * TEAM_WGS), dim3(TG_THREADS), lds, s, a);
     return hipGetLastError();
 }
 
@@ -556,8 +718,8 @@ hipError_t wrnn_launch_loop_teamg(const WrnnTeamGArgs &a, hipStream_t s) {
 
 static int teamg_plan_info(const wrnn_config *cfg, int rows_per_team, int fmt, int64_t lds_budget_bytes, wrnn_teamg_plan_info *out) {
     if (!cfg || !out || rows_per_team < 1 || rows_per_team > WRNN_TEAMG_BATCH_MAX_ROWS) return WRNN_ERR_INVALID;
-    if (fmt != WRNN_WEIGHTS_F32 && fmt != WRNN_WEIGHTS_F16) return WRNN_ERR_INVALID;
-    const int64_t esz = fmt == WRNN_WEIGHTS_F16 ? 2 : 4;
+    if (fmt != WRNN_WEIGHTS_F32 && fmt != WRNN_WEIGHTS_F16 && fmt != WRNN_WEIGHTS_E4M3) return WRNN_ERR_INVALID;   // 2 is reserved
+    const int64_t esz = fmt == WRNN_WEIGHTS_E4M3 ? 1 : fmt == WRNN_WEIGHTS_F16 ? 2 : 4;
     WrnnDims d;
     if (wrnn_dims_from_config(cfg, d) || d.FC > (1 << 20) || d.F > (1 << 20)) return WRNN_ERR_INVALID;
     WrnnTeamGPlan p;

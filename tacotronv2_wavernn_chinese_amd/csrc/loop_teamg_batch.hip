@@ -9,7 +9,8 @@
 // row_sum, the cells use the same libm calls, Philox is keyed (seed or row key, step, row, class), the race keeps the lowest class of
 // a tie -- so a row's labels, samples and logits are bit-equal to WRNN_KERNEL_TEAMG's whatever batch the row lands in.
 // The kernel is templated on the element type of the image as loop_teamg.hip is (float, or _Float16 for WRNN_WEIGHTS_F16): the fp16
-// instantiations are bit-equal to the fp16 instantiation of that kernel, and to the fp32 ones on the model rounded to fp16.
+// instantiations are bit-equal to the fp16 instantiation of that kernel, and to the fp32 ones on the model rounded to fp16; likewise
+// TgE4m3 (WRNN_WEIGHTS_E4M3) and the model dequantised from its e4m3 bytes and per-layer scales.
 //
 // Rows.  Batch b = schedule slots [b rpb, (b + 1) rpb) of `order` (longest first in a ragged call, identity otherwise), dealt to the
 // teams round-robin, in snake order when ragged, as loop_batch_cs.hip deals them.  A batch runs for the steps of its longest row; a
@@ -187,11 +188,136 @@ __device__ __forceinline__ void tgb_dot16(const TgHalf8 *__restrict__ rp, int kp
         }
 }
 
-// G rows from row `row0` of a layer's slice at `base` (LDS or device memory), KP elements each, in the image's element type
+// tgb_dot on the e4m3 image (teamg_layout.h), as tg_dot8 is tg_dot's: rp = the unit's first row, rows KP bytes apart, row0 its index in the
+// slice.  One 16-byte load per row and QUAD of steps, UNQ quads issued together (tgb_dot16's weight bytes in flight at 2 rows per team,
+// fewer with more rows), then what is left in halving blocks, and the 8-byte pair and the 4-byte single step of a segment's end loaded together.  Each step's weights are widened
+// exactly right before its multiply-adds; per (row, lane) the chains are tgb_dot's.  The caller applies the layer's scale to the sums.
+template <int G, int RB>
+__device__ __forceinline__ void tgb_dot8(const unsigned char *__restrict__ rp, int KP, int row0, const float4 *lds4, int xi, int xs4, int nA, int nK, int q, float (&sa)[G],
+                                         float (&sb)[G]) {
+    constexpr int UNQ = G == 1 ? (RB <= 2 ? 4 : RB <= 4 ? 2 : 1) : (RB <= 2 ? 2 : 1);   // with 4 rows half, with 8 a quarter: no registers for more
+    asm volatile("" : "+v"(xi));
+    const float4 *xp = lds4 + xi;
+    const unsigned char *row[G];
+    const uint4 *wq[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        row[g] = rp + (size_t)g * KP;
+        wq[g] = (const uint4 *)row[g] + ((q + tg8_rot(row0 + g, KP)) & 15);
+    }
+    float a0[RB][G], a1[RB][G];
+#pragma unroll
+    for (int r = 0; r < RB; ++r)
+#pragma unroll
+        for (int g = 0; g < G; ++g) a0[r][g] = a1[r][g] = 0.0f;
+    auto mac = [&](const float4 (&w)[G], int k) {
+#pragma unroll
+        for (int r = 0; r < RB; ++r) {
+            const float4 x = xp[r * xs4 + k * 16];
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                a0[r][g] = fmaf(w[g].x, x.x, a0[r][g]); a1[r][g] = fmaf(w[g].y, x.y, a1[r][g]);
+                a0[r][g] = fmaf(w[g].z, x.z, a0[r][g]); a1[r][g] = fmaf(w[g].w, x.w, a1[r][g]);
+            }
+        }
+    };
+    // one step from the dwords d[g] of the G rows
+    auto step = [&](const unsigned (&d)[G], int k) {
+        float4 w[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) w[g] = tg8_w4(d[g]);
+        mac(w, k);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto quad = [&](const uint4 (&wv)[G], int k) {
+        unsigned d[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) d[g] = wv[g].x;
+        step(d, k);
+#pragma unroll
+        for (int g = 0; g < G; ++g) d[g] = wv[g].y;
+        step(d, k + 1);
+#pragma unroll
+        for (int g = 0; g < G; ++g) d[g] = wv[g].z;
+        step(d, k + 2);
+#pragma unroll
+        for (int g = 0; g < G; ++g) d[g] = wv[g].w;
+        step(d, k + 3);
+    };
+    // NQ quads of steps from step k: their weight loads are issued together
+    auto block = [&](auto nq, int k) {
+        constexpr int NQ = decltype(nq)::value;
+        uint4 wv[NQ][G];
+#pragma unroll
+        for (int u = 0; u < NQ; ++u)
+#pragma unroll
+            for (int g = 0; g < G; ++g) wv[u][g] = wq[g][(k + 4 * u) * 4];
+#pragma unroll
+        for (int u = 0; u < NQ; ++u) quad(wv[u], k + 4 * u);
+    };
+    auto segment = [&](int k0, int k1) {
+        int k = k0;
+#pragma unroll 1
+        for (; k + 4 * UNQ <= k1; k += 4 * UNQ) block(std::integral_constant<int, UNQ>{}, k);
+        if constexpr (UNQ > 2) {
+            if (k + 8 <= k1) { block(std::integral_constant<int, 2>{}, k); k += 8; }
+        }
+        if constexpr (UNQ > 1) {
+            if (k + 4 <= k1) { block(std::integral_constant<int, 1>{}, k); k += 4; }
+        }
+        const int rem = k1 - k, ks = k + (rem & 2);
+        uint2 wp[G];
+        unsigned ws[G];
+        if (rem & 2) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) wp[g] = ((const uint2 *)(row[g] + 64 * k))[q];
+        }
+        if (rem & 1) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) ws[g] = ((const unsigned *)(row[g] + 64 * ks))[q];
+        }
+        if (rem & 2) {
+            unsigned d[G];
+#pragma unroll
+            for (int g = 0; g < G; ++g) d[g] = wp[g].x;
+            step(d, k);
+#pragma unroll
+            for (int g = 0; g < G; ++g) d[g] = wp[g].y;
+            step(d, k + 1);
+        }
+        if (rem & 1) step(ws, ks);
+    };
+    segment(0, nA);
+#pragma unroll
+    for (int r = 0; r < RB; ++r)
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const float v = row_sum(a0[r][g] + a1[r][g]);
+            sa[g] = (r == 0 || q == r) ? v : sa[g];
+            a0[r][g] = a1[r][g] = 0.0f;
+        }
+    segment(nA, nK);
+#pragma unroll
+    for (int r = 0; r < RB; ++r)
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const float v = row_sum(a0[r][g] + a1[r][g]);
+            sb[g] = (r == 0 || q == r) ? v : sb[g];
+        }
+}
+
+// G rows from row `row0` of a layer's slice at `base` (LDS or device memory), KP elements each, in the image's element type; `scale` is the
+// layer's (e4m3 only, a power of two)
 template <int G, int RB, typename WT>
-__device__ __forceinline__ void tgb_rows(const WT *base, int row0, int KP, const float4 *lds4, int xi, int xs4, int nA, int nK, int q, float (&sa)[G], float (&sb)[G]) {
+__device__ __forceinline__ void tgb_rows(const WT *base, int row0, int KP, float scale, const float4 *lds4, int xi, int xs4, int nA, int nK, int q, float (&sa)[G],
+                                         float (&sb)[G]) {
     if constexpr (sizeof(WT) == 4) tgb_dot<G, RB>((const float4 *)(base + (size_t)row0 * KP) + q, KP / 4, lds4, xi, xs4, nA, nK, q, sa, sb);
-    else tgb_dot16<G, RB>((const TgHalf8 *)(base + (size_t)row0 * KP), KP / 8, row0, lds4, xi, xs4, nA, nK, q, sa, sb);
+    else if constexpr (sizeof(WT) == 2) tgb_dot16<G, RB>((const TgHalf8 *)(base + (size_t)row0 * KP), KP / 8, row0, lds4, xi, xs4, nA, nK, q, sa, sb);
+    else {
+        tgb_dot8<G, RB>((const unsigned char *)(base + (size_t)row0 * KP), KP, row0, lds4, xi, xs4, nA, nK, q, sa, sb);
+#pragma unroll
+        for (int g = 0; g < G; ++g) { sa[g] *= scale; sb[g] *= scale; }
+    }
 }
 
 template <int RB, typename WT>
@@ -278,10 +404,10 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
         const int xi = (ly.v.cb + par * CB) / 4 + q;
         for (int ul = qw; ul < nown; ul += 32) {
             float sa[1], sb[1];
-            if (ul < L.nres) tgb_rows<1, RB>(wres + L.lds_off, ul, L.KP, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
-            else tgb_rows<1, RB>(img + L.img_off, ul, L.KP, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
+            if (ul < L.nres) tgb_rows<1, RB>(wres + L.lds_off, ul, L.KP, L.scale, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
+            else tgb_rows<1, RB>(img + L.img_off, ul, L.KP, L.scale, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
             const int j = g * L.U + ul;
-            if (q < RB) st_granule(mail, q * G1 + M_XC + (tag & 1u) * HP + j, tag, __float_as_uint(sa[0] + w[a.off.I_b + j]));
+            if (q < RB) tg_st_granule<WT>(mail, q * G1 + M_XC + (tag & 1u) * HP + j, tag, __float_as_uint(sa[0] + w[a.off.I_b + j]));
         }
     };
     // one GRU layer (get_gru_cell :273-279, gate rows [r; z; n]): h' of the own units of every row -> mailbox.  A row's input is
@@ -295,14 +421,14 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
             const float zg = 1.0f / (1.0f + expf(-((gi[1] + bi[H + j]) + (gh[1] + bh[H + j]))));
             const float ng = tanhf((gi[2] + bi[2 * H + j]) + rg * (gh[2] + bh[2 * H + j]));
             const float hn = (1.0f - zg) * ng + zg * lds[r * rowf + xoff + L.KAP + j];
-            st_granule(mail, r * G1 + region + (epoch & 1u) * HP + j, epoch, __float_as_uint(hn));
+            tg_st_granule<WT>(mail, r * G1 + region + (epoch & 1u) * HP + j, epoch, __float_as_uint(hn));
         };
         if (L.U <= 16) {
             for (int task = qw; task < 3 * nown; task += 32) {
                 const int ul = task / 3;
                 float sa[1], sb[1];
-                if (ul < L.nres) tgb_rows<1, RB>(wres + L.lds_off, task, L.KP, (const float4 *)lds, xi, xs4, nA, nK, q, sa, sb);
-                else tgb_rows<1, RB>(img + L.img_off, task, L.KP, (const float4 *)lds, xi, xs4, nA, nK, q, sa, sb);
+                if (ul < L.nres) tgb_rows<1, RB>(wres + L.lds_off, task, L.KP, L.scale, (const float4 *)lds, xi, xs4, nA, nK, q, sa, sb);
+                else tgb_rows<1, RB>(img + L.img_off, task, L.KP, L.scale, (const float4 *)lds, xi, xs4, nA, nK, q, sa, sb);
                 if (q < RB) { gsum[q * 128 + 2 * task] = sa[0]; gsum[q * 128 + 2 * task + 1] = sb[0]; }
             }
             __syncthreads();
@@ -316,15 +442,15 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
             for (int ul = qw; ul < nown; ul += 32) {
                 float gi[3] = {0.0f, 0.0f, 0.0f}, gh[3] = {0.0f, 0.0f, 0.0f};
                 if constexpr (RB <= 4) {
-                    if (ul < L.nres) tgb_rows<3, RB>(wres + L.lds_off, ul * 3, L.KP, (const float4 *)lds, xi, xs4, nA, nK, q, gi, gh);
-                    else tgb_rows<3, RB>(img + L.img_off, ul * 3, L.KP, (const float4 *)lds, xi, xs4, nA, nK, q, gi, gh);
+                    if (ul < L.nres) tgb_rows<3, RB>(wres + L.lds_off, ul * 3, L.KP, L.scale, (const float4 *)lds, xi, xs4, nA, nK, q, gi, gh);
+                    else tgb_rows<3, RB>(img + L.img_off, ul * 3, L.KP, L.scale, (const float4 *)lds, xi, xs4, nA, nK, q, gi, gh);
                 } else {
                     // 8 rows x 3 gates x (a0, a1) would not leave room for the loads in flight: gate by gate, the same sums
 #pragma unroll 1
                     for (int gt = 0; gt < 3; ++gt) {
                         float sa[1], sb[1];
-                        if (ul < L.nres) tgb_rows<1, RB>(wres + L.lds_off, ul * 3 + gt, L.KP, (const float4 *)lds, xi, xs4, nA, nK, q, sa, sb);
-                        else tgb_rows<1, RB>(img + L.img_off, ul * 3 + gt, L.KP, (const float4 *)lds, xi, xs4, nA, nK, q, sa, sb);
+                        if (ul < L.nres) tgb_rows<1, RB>(wres + L.lds_off, ul * 3 + gt, L.KP, L.scale, (const float4 *)lds, xi, xs4, nA, nK, q, sa, sb);
+                        else tgb_rows<1, RB>(img + L.img_off, ul * 3 + gt, L.KP, L.scale, (const float4 *)lds, xi, xs4, nA, nK, q, sa, sb);
                         gi[0] = gt == 0 ? sa[0] : gi[0]; gi[1] = gt == 1 ? sa[0] : gi[1]; gi[2] = gt == 2 ? sa[0] : gi[2];
                         gh[0] = gt == 0 ? sb[0] : gh[0]; gh[1] = gt == 1 ? sb[0] : gh[1]; gh[2] = gt == 2 ? sb[0] : gh[2];
                     }
@@ -339,10 +465,10 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
         const int xi = xoff / 4 + q;
         for (int ul = qw; ul < nown; ul += 32) {
             float sa[1], sb[1];
-            if (ul < L.nres) tgb_rows<1, RB>(wres + L.lds_off, ul, L.KP, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
-            else tgb_rows<1, RB>(img + L.img_off, ul, L.KP, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
+            if (ul < L.nres) tgb_rows<1, RB>(wres + L.lds_off, ul, L.KP, L.scale, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
+            else tgb_rows<1, RB>(img + L.img_off, ul, L.KP, L.scale, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
             const int j = g * L.U + ul;
-            if (q < RB) st_granule(mail, q * G1 + region + (epoch & 1u) * FCP + j, epoch, __float_as_uint(fmaxf(sa[0] + w[ob + j], 0.0f)));
+            if (q < RB) tg_st_granule<WT>(mail, q * G1 + region + (epoch & 1u) * FCP + j, epoch, __float_as_uint(fmaxf(sa[0] + w[ob + j], 0.0f)));
         }
     };
     // all N values of an exchanged vector of every row: 64 granules of one row per wave and turn (RB * ceil(N / 64) turns over the 8
@@ -461,8 +587,8 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
                 int bi = 0x7fffffff;
                 for (int ul = qw; ul < nown; ul += 32) {
                     float sa[1], sb[1];
-                    if (ul < L.nres) tgb_rows<1, RB>(wres + L.lds_off, ul, L.KP, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
-                    else tgb_rows<1, RB>(img + L.img_off, ul, L.KP, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
+                    if (ul < L.nres) tgb_rows<1, RB>(wres + L.lds_off, ul, L.KP, L.scale, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
+                    else tgb_rows<1, RB>(img + L.img_off, ul, L.KP, L.scale, (const float4 *)lds, xi, xs4, nK, nK, q, sa, sb);
                     if (q < RB) {
                         const int c = g * L.U + ul;
                         const float lg = sa[0] + w[a.off.fc3_b + c];
@@ -474,7 +600,7 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
                             else if (act && a.noise_mode == WRNN_NOISE_PHILOX) v -= logf(-logf(wrnn_uniform_raw(kseed, (uint64_t)t, krow, (uint32_t)c)));
                             if (v > bv) { bv = v; bi = c; }   // classes ascend: ties keep the lowest
                         } else {
-                            st_granule(mail, q * G1 + M_CAND + par * 64 + c, epoch, __float_as_uint(lg));
+                            tg_st_granule<WT>(mail, q * G1 + M_CAND + par * 64 + c, epoch, __float_as_uint(lg));
                         }
                     }
                 }
@@ -491,8 +617,8 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
                     int k = lane < 32 ? race_i[r * 64 + 32 + lane] : 0x7fffffff;
                     wave_argmax(v, k);
                     if (lane == 0) {   // the workgroup's candidate: granule g = value, 32 + g = class
-                        st_granule(mail, cand + g, epoch, __float_as_uint(v));
-                        st_granule(mail, cand + 32 + g, epoch, (unsigned)k);
+                        tg_st_granule<WT>(mail, cand + g, epoch, __float_as_uint(v));
+                        tg_st_granule<WT>(mail, cand + 32 + g, epoch, (unsigned)k);
                     }
                     const float pv = take_staggered(mail, cand + lane, epoch, dead, a.err, 15u);
                     const int ck = __shfl(__float_as_int(pv), (lane + 32) & 63, 64);
@@ -553,7 +679,8 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
 
 template <int RB>
 const void *tgb_fn(int esz) {
-    return esz == 4 ? (const void *)loop_teamg_batch_kernel<RB, float> : (const void *)loop_teamg_batch_kernel<RB, _Float16>;
+    return esz == 4 ? (const void *)loop_teamg_batch_kernel<RB, float>
+                    : esz == 2 ? (const void *)loop_teamg_batch_kernel<RB, _Float16> : (const void *)loop_teamg_batch_kernel<RB, TgE4m3>;
 }
 const void *tgb_kernel_fn(int rb, int esz) { return rb == 2 ? tgb_fn<2>(esz) : rb == 4 ? tgb_fn<4>(esz) : rb == 8 ? tgb_fn<8>(esz) : nullptr; }
 
@@ -564,7 +691,8 @@ void tgb_launch(const WrnnTeamGBatchArgs &a, size_t lds, hipStream_t s) {
 template <int RB>
 void tgb_launch_fmt(const WrnnTeamGBatchArgs &a, size_t lds, hipStream_t s) {
     if (a.plan.esz == 4) tgb_launch<RB, float>(a, lds, s);
-    else tgb_launch<RB, _Float16>(a, lds, s);
+    else if (a.plan.esz == 2) tgb_launch<RB, _Float16>(a, lds, s);
+    else tgb_launch<RB, TgE4m3>(a, lds, s);
 }
 
 }  // namespace

@@ -83,6 +83,14 @@ __device__ __forceinline__ void st_granule(u64 *base, unsigned idx, unsigned tag
     const unsigned off = idx * 8u;
     asm volatile("global_store_dwordx2 %0, %1, %2" ::"v"(off), "v"(v), "s"(base) : "memory");
 }
+// st_granule for a kernel so short of scalar registers that `base` may come back from a spill: it is then restored with v_readlane
+// right in front of the store, and a VALU write of an SGPR needs five wait states before a VMEM instruction reads it as its address.
+// The compiler inserts them for its own instructions, not for inline assembly, so they are part of the statement here.
+__device__ __forceinline__ void st_granule_ws(u64 *base, unsigned idx, unsigned tag, unsigned payload) {
+    const u64 v = ((u64)tag << 32) | payload;
+    const unsigned off = idx * 8u;
+    asm volatile("s_nop 4\n\tglobal_store_dwordx2 %0, %1, %2" ::"v"(off), "v"(v), "s"(base) : "memory");
+}
 __device__ __forceinline__ u64 peek(const u64 *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // One granule per lane, wave-uniform completion, two staggered first looks, then the bounded re-read loop (loop_dm_team.hip,
 // loop_teamg.hip).  loop_team2.hip measured this form against a single look and keeps its own take_granule.

@@ -2,6 +2,7 @@
 // per team in lock-step).  wrnn_teamg_make_plan sizes the resident weights by what these leave of 160 KiB.  The vectors are fp32 whatever
 // the element type of the weight image.
 #pragma once
+#include "team_common.h"
 #include "wrnn_internal.h"
 
 #define TG_THREADS WRNN_TEAMG_THREADS
@@ -83,6 +84,49 @@ __host__ __device__ inline int tg16_pos(int p, int row, int KAP, int KP) {
     const int rel = k - k0;
     if (((k1 - k0) & 1) && rel == k1 - k0 - 1) return p;   // the unpaired last step of a segment
     return 64 * (k - (rel & 1)) + 8 * (q ^ tg16_swz(row, KP)) + 4 * (rel & 1) + c;
+}
+
+// The e4m3 image (WRNN_WEIGHTS_E4M3).  The same elements as OCP e4m3fn bytes, each layer divided by its power-of-two scale
+// beforehand; a row is KP bytes.  The steps of a segment go in QUADS: quad j of the segment that starts at step k0 is steps k0 + 4 j ..
+// + 3 and takes the 256 bytes from byte 64 (k0 + 4 j) of the row; lane q's 16 bytes are piece (q + rot) & 15 of those 16 pieces: its 4
+// bytes of the first step, then of the second, third and fourth -- ONE 16-byte load for four steps.  What is left of a segment goes as one
+// PAIR (128 bytes, lane q's 8 bytes are piece q: 4 bytes of the first step, 4 of the second; an 8-byte load) and then one SINGLE step
+// stored as in the fp32 image (lane q's bytes at 64 k + 4 q .. + 3; a 4-byte load), so k still ascends.
+//   rot.  Rows are KP = 64 m bytes apart.  One ds_read_b128 serves lanes 0-3 and 12-15 of one 16-lane group together with lanes 4-11 of
+// the next, i.e. pieces {12 .. 15, 0 .. 3} of one row with pieces {4 .. 11} of another, over the 16 pieces (256 bytes) the 64 banks span:
+// two arcs of 8 that are disjoint only when the two rows start a multiple of 256 bytes apart.  Rows r and r' start 64 m (r' - r) bytes
+// apart, any multiple of a quarter span, and an XOR of the piece index can only undo half a span.  So a row's pieces are ROTATED by
+// rot = 4 ((-m row) mod 4), row counted inside the workgroup's slice of the layer: byte 64 m row + 16 rot is a multiple of 256 from the
+// slice's start, every row of the layer has the same bank frame, and any two rows are read conflict-free, whether the groups of a wave
+// take consecutive rows (G = 1) or rows three apart (the gates of consecutive units).  rot = 0 where m is a multiple of 4.  The pair and
+// the single step are not rotated: a ds_read_b64 of two rows 64 m bytes apart is 2-way unless m = 2 (mod 4) -- at most one such read per
+// segment.
+// The permutation only moves bytes (tg8_pos below is what wrnn_teamg_pack writes by and the dot products read by): each lane still gets
+// elements 4 (q + 16 k) .. + 3 at step k, k ascending, and v_cvt_pk_f32_fp8 widens them exactly.
+struct TgE4m3 { unsigned char b; };
+// two dwords of the conversion: bytes 0, 1 (word 0) and 2, 3 (word 1) of d, each an e4m3fn value, exactly
+__device__ __forceinline__ float4 tg8_w4(unsigned d) {
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)d, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)d, true);
+    return make_float4(lo[0], lo[1], hi[0], hi[1]);
+}
+// pieces a row's quads are rotated by
+__host__ __device__ inline int tg8_rot(int row, int KP) { return ((-(row * (KP >> 6))) & 3) << 2; }
+// where element p of row `row` (KAP = elements of segment A, KP = of the row; both multiples of 64) lives in the row of the e4m3 image
+__host__ __device__ inline int tg8_pos(int p, int row, int KAP, int KP) {
+    const int k = p >> 6, q = (p >> 2) & 15, c = p & 3;
+    const int k0 = p < KAP ? 0 : KAP >> 6, k1 = p < KAP ? KAP >> 6 : KP >> 6;
+    const int rel = k - k0, n = k1 - k0, nq = n & ~3;
+    if (rel < nq) return 64 * (k - (rel & 3)) + 16 * ((q + tg8_rot(row, KP)) & 15) + 4 * (rel & 3) + c;   // a quad
+    if ((n & 2) && rel - nq < 2) return 64 * (k - (rel - nq)) + 8 * q + 4 * (rel - nq) + c;              // the pair
+    return p;                                                                                             // the single last step
+}
+
+// a granule of either kernel: the e4m3 instantiations are the ones short of scalar registers (team_common.h, st_granule_ws); the
+// fp32 and fp16 ones keep st_granule
+template <typename WT>
+__device__ __forceinline__ void tg_st_granule(unsigned long long *base, unsigned idx, unsigned tag, unsigned payload) {
+    if constexpr (sizeof(WT) == 1) st_granule_ws(base, idx, tag, payload);
+    else st_granule(base, idx, tag, payload);
 }
 
 constexpr int MB_X = 8, MB_ROW = 16, MB_STEPS = 24, MB_UTT = 32, MB_START = 40, MB_SEED = 56, MB_KROW = 72;

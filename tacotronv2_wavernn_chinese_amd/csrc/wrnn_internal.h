@@ -110,10 +110,11 @@ struct wrnn_handle {
     bool team_dims = false;       // the constructor dims are the reference hparams the team kernels are built for
     bool team_ok = false;         // the 32-workgroup team kernels can be co-resident on this device (checked at create)
     std::string team_why;         // why not, when team_ok is false
-    void *teamg_img = nullptr;    // TEAMG weight image [32 WGs][WrnnTeamGPlan::img_elems_wg] of fp32 or fp16, packed on the device by the first TEAMG call
+    void *teamg_img = nullptr;    // TEAMG weight image [32 WGs][WrnnTeamGPlan::img_elems_wg] of fp32, fp16 or e4m3, packed on the device by the first TEAMG call
                                   // after a load or a change of teamg_fmt
     bool teamg_img_ok = false;
-    int32_t teamg_fmt = 0;        // WRNN_WEIGHTS_F32 / WRNN_WEIGHTS_F16 (wrnn_teamg_set_weight_format): the element type of the image
+    int32_t teamg_fmt = 0;        // WRNN_WEIGHTS_F32 / _F16 / _E4M3 (wrnn_teamg_set_weight_format): the element type of the image
+    float teamg_scale[6] = {1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f};   // per-layer scales of the image last packed (wrnn_teamg_weight_scales)
     int64_t teamg_budget = -1;    // wrnn_debug_teamg_lds_budget: LDS bytes for resident weights, < 0 = the default
     int last_batch_rows = 1;      // rows per team batch of the last generate call's loop kernel (wrnn_last_batch_rows)
     bool force_no_teams = false;  // wrnn_debug_force_no_teams: AUTO behaves as if residency had failed (tests of the slow-path warning)
@@ -281,12 +282,12 @@ struct WrnnBatchArgs {
 // row); a row is [segment A: KA weights, padded to KAP | segment B: KB weights, padded] = KP elements, both paddings multiples of 64
 // (16 lanes x 4 elements).  Workgroup g owns units [g * U, min(N, (g + 1) * U)); its slice of the image is U * G rows of KP elements at
 // img_off, of which the first nres units are copied to LDS (at lds_off elements behind the activation vectors) at the start of a launch.
-// An element is a weight of plan.esz bytes: 4 (fp32) or 2 (IEEE binary16); offsets and counts are in elements either way.
+// An element is a weight of plan.esz bytes: 4 (fp32), 2 (IEEE binary16) or 1 (OCP e4m3fn); offsets and counts are in elements in every format.
 struct WrnnTeamGLayer {
     int32_t N, G, KA, KB, KAP, KP, U, nres;
     int64_t img_off;    // elements, inside a workgroup's image
     int32_t lds_off;    // elements, inside the resident-weight area
-    int32_t pad_;
+    float scale;        // WRNN_WEIGHTS_E4M3: the layer's power-of-two scale, applied to a row's segment sums; 1 in the other formats
 };
 struct WrnnTeamGPlan {
     WrnnTeamGLayer L[WRNN_TEAMG_LAYERS];
@@ -294,7 +295,7 @@ struct WrnnTeamGPlan {
     int32_t act_floats;        // LDS floats of the activation vectors (TgLay, loop_teamg.hip): fp32 in either format
     int32_t res_elems;         // LDS elements of the resident weights
     int32_t mail_granules;     // per team
-    int32_t esz;               // bytes of a weight element: 4 or 2
+    int32_t esz;               // bytes of a weight element: 4, 2 or 1
 };
 inline size_t wrnn_teamg_lds_bytes(const WrnnTeamGPlan &p) { return (size_t)p.act_floats * 4 + (size_t)p.res_elems * p.esz; }
 #define WRNN_TEAMG_THREADS 512
@@ -310,13 +311,20 @@ struct WrnnTeamGArgs {
 // pure host: ownership and placement for dims d with `budget` LDS bytes for resident weights (< 0 or too large: 160 KiB minus the
 // activation vectors); nullptr, or why the kernel cannot serve these dims.  rows_per_team = 1: loop_teamg.hip; 2, 4, 8: the lock-step
 // rows of loop_teamg_batch.hip, whose activation vectors (TgbLay, teamg_layout.h) and mailbox regions are counted that many times --
-// ownership and the weight image do not depend on it.  esz = bytes of a weight element (4: fp32, 2: fp16): only how many units fit.
+// ownership and the weight image do not depend on it.  esz = bytes of a weight element (4: fp32, 2: fp16, 1: e4m3): only how many units fit;
+// every layer's scale is 1 (the caller sets the scales of the packed e4m3 image).
 const char *wrnn_teamg_make_plan(const WrnnDims &d, int64_t budget, WrnnTeamGPlan &p, int rows_per_team = 1, int esz = 4);
-// bytes of the image allocation: the 32 slices and, behind them, one flag word per layer for the fp16 range check
+// bytes of the image allocation: the 32 slices and, behind them, one word per layer: the flag of the fp16 range check, or the bits of
+// the layer's largest |w| of the e4m3 pack
 inline size_t wrnn_teamg_img_bytes(const WrnnTeamGPlan &p) { return (size_t)32 * p.img_elems_wg * p.esz + WRNN_TEAMG_LAYERS * sizeof(int32_t); }
 // Packs the image in the plan's element type.  fp16: round to nearest even on the device, then ONE wait for the range check;
 // *bad_layer = the first layer holding a weight that does not round to a finite fp16, or -1.  fp32: no wait, *bad_layer = -1.
-hipError_t wrnn_teamg_pack(const wrnn_handle *h, const WrnnTeamGPlan &p, void *img, hipStream_t s, int *bad_layer);
+// e4m3: an abs-max pass per layer, ONE wait for the six maxima, the scales on the host (wrnn_teamg_e4m3_scale), then the pack proper;
+// *bad_layer = the first layer holding a weight that is not finite, or -1.  scales[l] = the layer's scale (1 in the other formats).
+hipError_t wrnn_teamg_pack(const wrnn_handle *h, const WrnnTeamGPlan &p, void *img, hipStream_t s, int *bad_layer, float scales[WRNN_TEAMG_LAYERS]);
+// The scale of an e4m3 layer whose largest magnitude is amax (finite): 2^e with e the smallest integer such that amax / 2^e <= 448,
+// clamped to e >= -126 so that the scale is a normal float (amax < 2^128 gives e <= 120, so 2^-e is normal too); 1 for amax = 0.
+float wrnn_teamg_e4m3_scale(float amax);
 extern const char *const wrnn_teamg_layer_names[WRNN_TEAMG_LAYERS];
 hipError_t wrnn_teamg_occupancy(const WrnnTeamGPlan &p, int *blocks_per_cu);
 hipError_t wrnn_launch_loop_teamg(const WrnnTeamGArgs &a, hipStream_t s);

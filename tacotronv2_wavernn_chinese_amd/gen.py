@@ -7,7 +7,7 @@ handed to ``model.generate``; the output file name pattern is the reference's (:
 
 Deliberate differences: the reference hard-overrides ``batched = False`` and
 ``device = cpu`` after parsing its flags (:76-77, :93); here ``--batched`` is honoured and the model
-runs on the MI355X.  Extensions: ``--kernel NAME``, ``--teamg-weights f32|f16``, ``--target auto|per_xcd``, ``--noise reference [--seed N]``, ``--stream-frames N`` (streaming generation)
+runs on the MI355X.  Extensions: ``--kernel NAME``, ``--teamg-weights f32|f16|e4m3``, ``--target auto|per_xcd``, ``--noise reference [--seed N]``, ``--stream-frames N`` (streaming generation)
 (the reference's own noise stream: ``vocoder.reference_noise``).
 
 The ``.wav`` branch (:17-20) does what the reference's intends: ``load_wav``, the input saved as ``__{idx}__{k}k_steps_target.wav`` (the
@@ -193,9 +193,10 @@ def build_parser() -> argparse.ArgumentParser:
                         help="extension: the device loop kernel ('auto': the library's choice; 'teamg': the XCD-team kernel for any model "
                              "dims, the fast path of a model whose dims are not the reference hparams; 'teamg_batch': the same kernel with "
                              "several rows per team in lock-step, for batched (fold) mode and other many-row calls of such a model)")
-    parser.add_argument('--teamg-weights', choices=('f32', 'f16'), default='f32',
+    parser.add_argument('--teamg-weights', choices=('f32', 'f16', 'e4m3'), default='f32',
                         help="extension: element type of the weight image of --kernel teamg / teamg_batch ('f16': the loop matrices as IEEE "
-                             "binary16, half the bytes streamed per step; activations and accumulators stay fp32); ignored by the other kernels")
+                             "binary16, half the bytes streamed per step; 'e4m3': as 8-bit OCP e4m3 with one power-of-two scale per layer, a "
+                             "quarter of the bytes; activations and accumulators stay fp32); ignored by the other kernels")
     parser.set_defaults(batched=None)
     return parser
 

@@ -326,13 +326,17 @@ class WaveRNN(nn.Module):
         halves the bytes a team streams per step and doubles what fits in LDS.  The outputs are bit-equal to the fp32 kernel's on a model
         whose matrices were rounded to fp16 beforehand.  The setting belongs to the model: it survives ``load_state_dict`` and ``.to()``,
         the image is packed again by the next call, and no other kernel reads it (``last_timing['teamg_weights']`` says what ran).  A
-        weight that has no finite fp16 makes that call raise ``WrnnError`` (WRNN_ERR_UNSUPPORTED) naming the layer."""
+        weight that has no finite fp16 makes that call raise ``WrnnError`` (WRNN_ERR_UNSUPPORTED) naming the layer.
+
+        ``'e4m3'``: the same matrices as OCP e4m3fn bytes with one power-of-two scale per image layer (a quarter of fp32's bytes; the
+        scales are found at pack time, ``native().teamg_weight_scales()``).  Bit-equal to the fp32 kernel on the dequantised model; only a
+        weight that is not finite is refused."""
         return self._teamg_weights
 
     @teamg_weights.setter
     def teamg_weights(self, fmt: str):
-        if fmt not in _cabi.WEIGHT_FORMATS:
-            raise ValueError(f"teamg_weights must be 'f32' or 'f16', not {fmt!r}")
+        if not isinstance(fmt, str) or fmt not in _cabi.TEAMG_WEIGHT_FORMATS:
+            raise ValueError(f"teamg_weights must be 'f32', 'f16' or 'e4m3', not {fmt!r}")
         self._teamg_weights = fmt
         if self._native is not None:
             self._native.set_teamg_weights(fmt)

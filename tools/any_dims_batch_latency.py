@@ -15,7 +15,12 @@ default by more than that.
     python tools/any_dims_batch_latency.py --weights f16 [--out FILE]
 
 times WRNN_KERNEL_TEAMG_BATCH with the fp32 weight image against the fp16 image (`teamg_weights='f16'`) at every rows-per-team count both
-plans admit: two handles of one model, the formats alternating call by call."""
+plans admit: two handles of one model, the formats alternating call by call.
+
+    python tools/any_dims_batch_latency.py --weights e4m3 [--out FILE]
+
+adds a third handle with the e4m3 image: fp32, fp16 and e4m3 alternate call by call in one session; the verdict of a shape is e4m3
+against fp16 in that session, the time ratio next to the ratio of the streamed bytes."""
 import argparse
 import os
 import sys
@@ -30,12 +35,14 @@ FRAMES = {'A': 2, 'C': 42, 'D': 1}      # 256, 252 and 275 steps
 
 
 def weights_session(args):
-    """fp32 image against fp16 image, WRNN_KERNEL_TEAMG_BATCH at every admitted rows-per-team count, 8 x n_teams rows."""
+    """fp32 image against fp16 image (and, with --weights e4m3, the e4m3 image), WRNN_KERNEL_TEAMG_BATCH at every admitted rows-per-team
+    count, 8 x n_teams rows."""
+    fmts = ('f32', 'f16') if args.weights == 'f16' else ('f32', 'f16', 'e4m3')
     from tacotronv2_wavernn_chinese_amd import _cabi
     from tacotronv2_wavernn_chinese_amd.synth import make_mels, make_state_dict
     from tacotronv2_wavernn_chinese_amd.vocoder import WaveRNN
     from tests.teamg_cases import DIM_SETS
-    lines = [f'fp16 weight image, many rows on other dims, {torch.cuda.get_device_name(0)}, torch {torch.__version__}', '',
+    lines = [f'{"fp16" if args.weights == "f16" else "fp16 and e4m3"} weight image, many rows on other dims, {torch.cuda.get_device_name(0)}, torch {torch.__version__}', '',
              f'loop_ms of one call (HIP events around the loop kernel), {args.warmup} warm-up + {args.reps} timed calls per format, alternating; RAW, Philox noise',
              'us/step/row = median loop time / (steps x rows); spread = (max - min) of the timed calls in the same unit; streamed = weight bytes a team reads per step', '']
     verdicts = []
@@ -43,7 +50,7 @@ def weights_session(args):
         dims = DIM_SETS[name]
         sd = make_state_dict(7, 'RAW', 'peaky', **dims)
         models = {}
-        for w in ('f32', 'f16'):
+        for w in fmts:
             m = WaveRNN(**dims, mode='RAW')
             m.verbose = False
             m.teamg_weights = w
@@ -56,12 +63,12 @@ def weights_session(args):
         plans = {}
         for R in (2, 4, 8):
             try:
-                plans[R] = {w: _cabi.teamg_plan_fmt(R, w, -1, mode='RAW', **dims) for w in ('f32', 'f16')}
+                plans[R] = {w: _cabi.teamg_plan_fmt(R, w, -1, mode='RAW', **dims) for w in fmts}
             except _cabi.WrnnError:
                 pass
         lines.append(f'set {name}: rnn {dims["rnn_dims"]}, fc {dims["fc_dims"]}, hop {dims["hop_length"]}; {B} rows x {steps} steps on {teams} teams; rows per team admitted: {sorted(plans)}')
         mels = torch.from_numpy(make_mels(5, B, T, feat_dims=dims['feat_dims'])).cuda()
-        ms = {(R, w): [] for R in plans for w in ('f32', 'f16')}
+        ms = {(R, w): [] for R in plans for w in fmts}
         for rep in range(args.warmup + args.reps):
             for R, w in ms:
                 m = models[w]
@@ -73,10 +80,18 @@ def weights_session(args):
         us = {k: float(np.median(v)) * 1e3 / (steps * B) for k, v in ms.items()}
         spread = {k: (max(v) - min(v)) * 1e3 / (steps * B) for k, v in ms.items()}
         for R in sorted(plans):
-            for w in ('f32', 'f16'):
+            for w in fmts:
                 p = plans[R][w]
                 lines.append(f'  R={R} {w}  {us[(R, w)]:8.3f} us/step/row  {1e3 / us[(R, w)]:9.2f} ksamples/s in all  spread {spread[(R, w)]:.3f}   streamed {p["streamed_bytes_step"] / 1e6:6.2f} MB '
                              f'per step, LDS {p["lds_bytes"]}   calls (ms): ' + ' '.join(f'{v:.3f}' for v in ms[(R, w)]))
+            if args.weights == 'e4m3':
+                margin = max(spread[(R, 'f16')], spread[(R, 'e4m3')])
+                d = us[(R, 'e4m3')] - us[(R, 'f16')]
+                verdicts.append(f'set {name} R={R}: e4m3 / f16 time {us[(R, "e4m3")] / us[(R, "f16")]:.3f} (streamed bytes e4m3 / f16 '
+                                f'{plans[R]["e4m3"]["streamed_bytes_step"] / max(plans[R]["f16"]["streamed_bytes_step"], 1):.3f}; e4m3 / f32 time '
+                                f'{us[(R, "e4m3")] / us[(R, "f32")]:.3f}), margin {margin:.3f} -> '
+                                f'{"e4m3 FASTER than f16 beyond the spread" if -d > margin else "e4m3 SLOWER than f16 beyond the spread" if d > margin else "e4m3 equal to f16 within the spread"}')
+                continue
             margin = max(spread[(R, 'f32')], spread[(R, 'f16')])
             verdicts.append(f'set {name} R={R}: f16 / f32 time {us[(R, "f16")] / us[(R, "f32")]:.3f} (streamed bytes f16 / f32 '
                             f'{plans[R]["f16"]["streamed_bytes_step"] / max(plans[R]["f32"]["streamed_bytes_step"], 1):.3f}), margin {margin:.3f} -> '
@@ -98,7 +113,8 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--sets', default='ACD')
     ap.add_argument('--out', default=None)
-    ap.add_argument('--weights', choices=('f32', 'f16'), default='f32', help="f16: time the fp32 image against the fp16 image of TEAMG_BATCH instead")
+    ap.add_argument('--weights', choices=('f32', 'f16', 'e4m3'), default='f32',
+                    help="f16: time the fp32 image against the fp16 image of TEAMG_BATCH instead; e4m3: fp32, fp16 and e4m3 alternating")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise RuntimeError('any_dims_batch_latency.py measures on an MI355X: no GPU, no figures')
@@ -108,7 +124,7 @@ def main():
     from tacotronv2_wavernn_chinese_amd.synth import make_mels, make_state_dict
     from tacotronv2_wavernn_chinese_amd.vocoder import WaveRNN
     from tests.teamg_cases import DIM_SETS
-    if args.weights == 'f16':
+    if args.weights != 'f32':
         return weights_session(args)
     lines = [f'many rows on other dims, {torch.cuda.get_device_name(0)}, torch {torch.__version__}', '',
              f'loop_ms of one call (HIP events around the loop kernel), {args.warmup} warm-up + {args.reps} timed calls per kernel, alternating; RAW, Philox noise',

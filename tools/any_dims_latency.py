@@ -13,7 +13,13 @@ median is what the ratio is made of.  Next to it the bytes TEAMG streams per ste
 times WRNN_KERNEL_TEAMG with the fp32 weight image against the same kernel with the fp16 image (`teamg_weights='f16'`) instead: two
 handles of one model, the two formats alternating call by call, the same shapes, mels and seed; per shape the median, the min-to-max
 spread of either, the bytes streamed per step in either format (`wrnn_teamg_plan_fmt`) and whether f16 is slower than f32 by more than the
-larger spread."""
+larger spread.
+
+    python tools/any_dims_latency.py --weights e4m3 [--out FILE]
+
+adds a third handle with the e4m3 image (`teamg_weights='e4m3'`): fp32, fp16 and e4m3 alternate call by call in one session, same
+protocol; the verdict of a shape is e4m3 against fp16 in that session (faster by more than the spread, equal, or slower), with the time
+ratio next to the ratio of the streamed bytes."""
 import argparse
 import os
 import sys
@@ -28,12 +34,13 @@ FRAMES = {'A': 2, 'C': 42, 'D': 1}      # 256, 252 and 275 steps
 
 
 def weights_session(args):
-    """fp32 image against fp16 image, WRNN_KERNEL_TEAMG, B = 1 and B = 8 rows."""
+    """fp32 image against fp16 image (and, with --weights e4m3, the e4m3 image), WRNN_KERNEL_TEAMG, B = 1 and B = 8 rows."""
+    fmts = ('f32', 'f16') if args.weights == 'f16' else ('f32', 'f16', 'e4m3')
     from tacotronv2_wavernn_chinese_amd import _cabi
     from tacotronv2_wavernn_chinese_amd.synth import make_mels, make_state_dict
     from tacotronv2_wavernn_chinese_amd.vocoder import WaveRNN
     from tests.teamg_cases import DIM_SETS
-    lines = [f'fp16 weight image of the any-dims team kernel, {torch.cuda.get_device_name(0)}, torch {torch.__version__}', '',
+    lines = [f'{"fp16" if args.weights == "f16" else "fp16 and e4m3"} weight image of the any-dims team kernel, {torch.cuda.get_device_name(0)}, torch {torch.__version__}', '',
              f'loop_ms of one call (HIP events around the loop kernel), {args.warmup} warm-up + {args.reps} timed calls per format, alternating; RAW, Philox noise',
              'us/step = median loop time / steps per row; spread = (max - min) of the timed calls per step; GB/s per XCD = bytes streamed per step / us per step', '']
     verdicts = []
@@ -41,7 +48,7 @@ def weights_session(args):
         dims = DIM_SETS[name]
         sd = make_state_dict(7, 'RAW', 'peaky', **dims)
         models, plans = {}, {}
-        for w in ('f32', 'f16'):
+        for w in fmts:
             m = WaveRNN(**dims, mode='RAW')
             m.verbose = False
             m.teamg_weights = w
@@ -51,14 +58,14 @@ def weights_session(args):
             plans[w] = _cabi.teamg_plan_fmt(1, w, -1, mode='RAW', **dims)
         lines.append(f'set {name}: rnn {dims["rnn_dims"]}, fc {dims["fc_dims"]}, feat {dims["feat_dims"]}, res_out {dims["res_out_dims"]}, bits {dims["bits"]}, hop {dims["hop_length"]}; '
                      + '; '.join(f'{w}: weights {sum(L["weight_bytes"] for L in plans[w]["layers"].values()) / 1e6:.2f} MB, streamed {plans[w]["streamed_bytes_step"] / 1e6:.2f} MB '
-                                 f'per step and team, LDS {plans[w]["lds_bytes"]}' for w in ('f32', 'f16')))
+                                 f'per step and team, LDS {plans[w]["lds_bytes"]}' for w in fmts))
         for B in (1, 8):
             T = FRAMES[name]
             steps = T * dims['hop_length']
             mels = torch.from_numpy(make_mels(5, B, T, feat_dims=dims['feat_dims'])).cuda()
-            ms = {'f32': [], 'f16': []}
+            ms = {w: [] for w in fmts}
             for rep in range(args.warmup + args.reps):
-                for w in ('f32', 'f16'):
+                for w in fmts:
                     m = models[w]
                     m.generate_raw(mels, False, 11000, 550, noise_mode='philox', seed=99, kernel='teamg')
                     lt = m.last_timing
@@ -67,9 +74,18 @@ def weights_session(args):
                         ms[w].append(float(lt['loop_ms']))
             us = {w: float(np.median(v)) * 1e3 / steps for w, v in ms.items()}
             spread = {w: (max(v) - min(v)) * 1e3 / steps for w, v in ms.items()}
-            for w in ('f32', 'f16'):
+            for w in fmts:
                 lines.append(f'  B={B} {steps} steps  {w}  {us[w]:8.2f} us/step  spread {spread[w]:.2f}  {1e3 / us[w]:7.2f} ksamples/s per row  '
                              f'{plans[w]["streamed_bytes_step"] / us[w] / 1e3:7.1f} GB/s per XCD   calls (ms): ' + ' '.join(f'{v:.3f}' for v in ms[w]))
+            if args.weights == 'e4m3':
+                margin = max(spread['f16'], spread['e4m3'])
+                ratio_b = plans['e4m3']['streamed_bytes_step'] / max(plans['f16']['streamed_bytes_step'], 1)
+                d = us['e4m3'] - us['f16']
+                verdicts.append(f'set {name} B={B}: e4m3 / f16 time per step {us["e4m3"] / us["f16"]:.3f} (streamed bytes e4m3 / f16 {ratio_b:.3f}; e4m3 / f32 time '
+                                f'{us["e4m3"] / us["f32"]:.3f}), margin {margin:.2f} us -> '
+                                f'{"e4m3 FASTER than f16 beyond the spread" if -d > margin else "e4m3 SLOWER than f16 beyond the spread" if d > margin else "e4m3 equal to f16 within the spread"}; '
+                                f'e4m3 {1e3 / us["e4m3"]:.2f} ksamples/s per row')
+                continue
             margin = max(spread.values())
             ratio_b = plans['f16']['streamed_bytes_step'] / max(plans['f32']['streamed_bytes_step'], 1)
             verdicts.append(f'set {name} B={B}: f16 / f32 time per step {us["f16"] / us["f32"]:.3f} (streamed bytes f16 / f32 {ratio_b:.3f}), margin {margin:.2f} us -> '
@@ -91,7 +107,8 @@ def main():
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--out', default=None)
-    ap.add_argument('--weights', choices=('f32', 'f16'), default='f32', help="f16: time the fp32 image against the fp16 image of TEAMG instead")
+    ap.add_argument('--weights', choices=('f32', 'f16', 'e4m3'), default='f32',
+                    help="f16: time the fp32 image against the fp16 image of TEAMG instead; e4m3: fp32, fp16 and e4m3 alternating")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise RuntimeError('any_dims_latency.py measures on an MI355X: no GPU, no figures')
@@ -101,7 +118,7 @@ def main():
     from tacotronv2_wavernn_chinese_amd.synth import make_mels, make_state_dict
     from tacotronv2_wavernn_chinese_amd.vocoder import WaveRNN
     from tests.teamg_cases import DIM_SETS
-    if args.weights == 'f16':
+    if args.weights != 'f32':
         return weights_session(args)
     lines = [f'generate loop on other dims, {torch.cuda.get_device_name(0)}, torch {torch.__version__}', '',
              f'loop_ms of one call (HIP events around the loop kernel), {args.warmup} warm-up + {args.reps} timed calls per kernel, alternating; RAW, Philox noise',
