@@ -171,19 +171,24 @@ def label_stats(got, ref_labels, first):
     return dict(compared=compared, mismatches=mism, max_abs=max_abs, near_tie_abs=near)
 
 
-def stream_raw(m, mels, sizes, **kw):
+def stream_raw(m, mels, sizes, infos=None, **kw):
     """Push mels (B, n_mels, T) through ``m.stream(raw=True, **kw)`` in chunks of `sizes` frames, then finish: the raw outputs
-    concatenated, (labels, samples) numpy (B, T * hop)."""
+    concatenated, (labels, samples) numpy (B, T * hop).  infos: a list that receives the stream's ``info()`` when it opens, after every
+    push and after the finish."""
     B = mels.shape[0]
     labs, smps = [], []
     with m.stream(batch=B, raw=True, **kw) as st:
+        note = (lambda: infos.append(st.info())) if infos is not None else (lambda: None)
+        note()
         f = 0
         for k in sizes:
             r = st.push(mels[:, :, f:f + k] if B > 1 else mels[0, :, f:f + k])
             f += k
             labs.append(r['labels'].cpu().numpy())
             smps.append(r['samples'].cpu().numpy())
+            note()
         r = st.finish()
         labs.append(r['labels'].cpu().numpy())
         smps.append(r['samples'].cpu().numpy())
+        note()
     return np.concatenate(labs, axis=1), np.concatenate(smps, axis=1)
