@@ -317,14 +317,22 @@ def epilogue(samples_bl: np.ndarray, n_classes: int, mu_law: bool, batched: bool
 
 # ------------------------------------------------ losses on forward()'s output (wavernn_train.py:82,112-121)
 
-def cross_entropy(y_hat: np.ndarray, y: np.ndarray) -> float:
-    """F.cross_entropy(y_hat.transpose(1, 2).unsqueeze(-1), y.unsqueeze(-1)): mean over (B, L) of
-    logsumexp(y_hat[b, t]) - y_hat[b, t, y[b, t]]; float32 per element, float64 mean."""
+def cross_entropy_rows(y_hat: np.ndarray, y: np.ndarray) -> np.ndarray:
+    """-log_softmax(y_hat[b, t])[y[b, t]] of every row, float32, flattened.  Written as torch writes it, log(s) - (p[t] - m) with
+    m the row's maximum and s = sum exp(p - m): both terms are of the size of the loss.  (m + log(s)) - p[t] would round the log-sum-exp at
+    the spacing of m before p[t] comes off, an error that grows with the logits, not with the loss."""
     yh = np.asarray(y_hat, np.float32).reshape(-1, y_hat.shape[-1])
     yy = np.asarray(y).reshape(-1).astype(np.int64)
     m = yh.max(axis=1, keepdims=True)
-    lse = (m[:, 0] + np.log(np.exp(yh - m).sum(axis=1, dtype=np.float32))).astype(np.float32)
-    return float((lse - yh[np.arange(yh.shape[0]), yy]).astype(np.float64).mean())
+    with np.errstate(under='ignore', divide='ignore'):
+        log_s = np.log(np.exp(yh - m).sum(axis=1, dtype=np.float32))
+        return (log_s - (yh[np.arange(yh.shape[0]), yy] - m[:, 0])).astype(np.float32)
+
+
+def cross_entropy(y_hat: np.ndarray, y: np.ndarray) -> float:
+    """F.cross_entropy(y_hat.transpose(1, 2).unsqueeze(-1), y.unsqueeze(-1)): mean over (B, L) of
+    logsumexp(y_hat[b, t]) - y_hat[b, t, y[b, t]]; float32 per element, float64 mean."""
+    return float(cross_entropy_rows(y_hat, y).astype(np.float64).mean())
 
 
 def _softplus(x):

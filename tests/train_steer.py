@@ -147,6 +147,45 @@ def steered(mode, B, L, seed, dims=None, device='cpu'):
     return out
 
 
+PEAKY_SPREAD = 5.0
+# (dims name, B spec, L) of the peaky whole-step cases (tests/test_gpu_raw_ce.py); seeds apart from every case_seed
+PEAKY_CASES = [('default', (4, 1), 7), ('generic', (0, 33), 3)]
+
+
+def peaky_seed(c):
+    return 900001 + 1000 * PEAKY_CASES.index(c)
+
+
+def steered_peaky(B, L, seed, dims=None, device='cpu'):
+    """steered('RAW', ...) with the output layer of a trained model: fc3.bias = a `mixed` row of tests/raw_ce.py (one class 25 above
+    the rest), fc3.weight scaled so that the float64 fc3 products spread by +-PEAKY_SPREAD around it, y on the row's float64 argmax in
+    3 of 4 positions (2 of 3 at L = 3) and on a seeded class elsewhere.  fc3 comes after both ReLUs: the pre-activations, so the two masks and their
+    margins, do not depend on it, and the steering still holds (tests/test_raw_ce_host.py asserts it anyway)."""
+    from tests import raw_ce as rc
+    d = dict(DEFAULT_DIMS)
+    d.update(dims or {})
+    st = steered('RAW', B, L, seed, dims, device)
+    sd = st['sd']
+    with torch.no_grad():
+        t = {k: torch.as_tensor(v).to(device, torch.float64) for k, v in sd.items()}
+        _, _, p2 = tr.loop_forward(t, torch.as_tensor(st['x']).to(device, torch.float64), torch.as_tensor(st['mels_up']).to(device, torch.float64),
+                                   torch.as_tensor(st['aux']).to(device, torch.float64), return_pre=True)
+        z = (torch.relu(p2) @ t['fc3.weight'].t()).cpu().numpy()                    # (B, L, NC): fc3 without its bias
+    sd['fc3.weight'] = (sd['fc3.weight'] * np.float32(PEAKY_SPREAD / np.abs(z).max())).astype(np.float32)
+    sd['fc3.bias'] = rc.group('mixed', d['bits'])['P'][0].copy()
+    logits = z * (PEAKY_SPREAD / np.abs(z).max()) + sd['fc3.bias'].astype(np.float64)
+    rng = np.random.Generator(np.random.PCG64(seed + 2))
+    y = rng.integers(0, logits.shape[-1], size=(B, L)).astype(np.int64)
+    # a miss where (b + t) % 4 == 3; every batch row has one (L = 3: (b + t) % 3 == 2, so 2 of 3 are hits there): a row of hits alone
+    # has gradients of ~1e-8, softmax - 1 at the peak, which float32 cannot hold -- torch's own float32 is 0.24 off on such a row
+    # of d_mels_up, and the per-row bound of the GPU tests would measure that, not the kernels
+    k = min(4, L)
+    hit = (np.arange(B)[:, None] + np.arange(L)[None, :]) % k != k - 1
+    y[hit] = logits.argmax(axis=-1)[hit]
+    st.update(y=y, hit=hit)
+    return st
+
+
 def pre_activations64(st, device='cpu'):
     """The float64 fc1 / fc2 pre-activations of steered inputs: (p1, p2), (B, L, FC) each."""
     return _pre64(st['sd'], st['x'], st['mels_up'], st['aux'], device)
