@@ -121,7 +121,11 @@ typedef struct wrnn_sample_opts {
     int32_t kernel;     /* WRNN_KERNEL_* */
     /* != 0: mels_dev is (B, feat, T + 2*pad), already padded by `pad` frames on both sides with real context like the
      * training collate does and WaveRNN.forward receives it (:143); 0: (B, feat, T), zero padding applied on the fly
-     * like generate() (:183-185).  T is the unpadded frame count either way. */
+     * like generate() (:183-185).  T is the unpadded frame count either way.  It only moves where frame 0 lies in a row of
+     * mels_dev, on every kernel: with batched != 0 the folds are cut from the conditioning of the T middle frames as before,
+     * with frames_dev utterance b still runs frames_dev[b] * hop steps and its frames beyond frames_dev[b] are read as given
+     * (zeros, as documented there).  A call whose 2*pad context frames are zero has the bits of the unpadded call in all three
+     * forms (tests/test_gpu_forward_padded.py). */
     int32_t mels_padded;
     uint64_t seed;      /* WRNN_NOISE_PHILOX */
     /* WRNN_NOISE_INJECTED, device pointers, step-major like the reference's
