@@ -17,7 +17,9 @@
 //                             window 4: conditioning of step t+1 (LDS <- registers <- HBM stream, prefetched two steps
 //                             ahead), window 5: gh1 gather, gh2 = W_hh2.h2, per-frame constants.
 // All 512 threads share phase A (unit j = tid) and the exchange polls (granule tid); behind B5 the race costs one LDS read
-// ({sample value, class}: the value comes from a per-class table built once, not from a division).  No AGPR parking: 2 waves/SIMD x 256 registers hold 160 weights + the working set.  S hands its results to C
+// (the sample value: it comes from a per-class table built once, not from a division), issued together with the coming step's phase-A operands and
+// the critical waves' phase-B operands (ONE LDS round trip between B5 and phase A); the per-step outputs are stored by a shadow wave of workgroup 0 one
+// window and a half later.  No AGPR parking: 2 waves/SIMD x 256 registers hold 160 weights + the working set.  S hands its results to C
 // through small LDS slots between the same 5 barriers.  The phase-A conditioning {cI, v_r, v_z, v_n}[512] of every step
 // is precomputed by cond_stream_kernel (prologue.hip) into an 8 KB/step HBM stream instead of being rebuilt from
 // per-frame records in LDS: 57 KB of LDS and ~70 instructions per step saved for 1.6 GB/s of HBM traffic.
@@ -25,8 +27,10 @@
 // Thread map inside a role (wl = wave & 3, lane l: quarter r4 = l>>4, q = l&15): quarter-wave (wl, r4) owns hidden
 // unit / fc row u = 16 g + 4 wl + r4 and columns 32q..32q+31 of every row it owns.
 //
-// Developer knobs (all -D, see where each is defined): T2_HOIST_LDS (shipped 1), T2_STRAIGHT_POLL (shipped 7), T2_PRESLEEP, T2_DEFER_OUT, T2_RACE_SLEEP
-// work as before or are new; T2_LATE_B and T2_STAGGER (the two-look polls of rounds 1-3, measured slower in round 4) were removed with their dead paths.
+// Developer knobs (all -D, see where each is defined): T2_HOIST_LDS (shipped 1), T2_STRAIGHT_POLL (shipped 7), the step head's T2_HEAD_ONE_TRIP,
+// T2_OUT_SHADOW, T2_PREB1_OPERANDS and T2_PHILOX_OPAQUE (all shipped 1), T2_PRESLEEP (0), T2_RACE_SLEEP (3; re-tuned over 2, 3, 4 on the step-head tree).
+// T2_DEFER_OUT (the outputs carried in registers to a shadow wave one step later: -1.2 %) was replaced by T2_OUT_SHADOW and removed with its dead
+// paths, as T2_LATE_B and T2_STAGGER (the two-look polls of rounds 1-3, measured slower in round 4) were before it.
 #include "team_common.h"
 
 #define T2_THREADS 512
@@ -67,11 +71,31 @@ __device__ __forceinline__ void finish_n(const u64 *base, unsigned idx, unsigned
 // and the retry out of line LOST 2.5 % and is not in the tree (profiles/team2_chain_lds.txt).
 #define T2_STRAIGHT_POLL 7
 #endif
-#ifndef T2_DEFER_OUT
-#define T2_DEFER_OUT 0   // developer knob, see the merge at the end of the step
+// ---- A/B knobs of the step head, B5 .. the first x2 read of phase B (profiles/team2_step_head.txt: all three shipped ON, +2.5 .. +2.7 % together) ----
+#ifndef T2_HEAD_ONE_TRIP
+// behind B5 the fed-back sample and phase A's own operands (L_CSTA, L_COND, three gh1 words: none depends on the winner) are read back to back and
+// waited for once; 0 = the sample is read and waited for, then the branches behind it, then phase A's operands at the loop top: two LDS round trips in series
+#define T2_HEAD_ONE_TRIP 1
+#endif
+#ifndef T2_OUT_SHADOW
+// RAW: labels_out / samples_out of step t are stored by thread 256 of workgroup 0 (a shadow wave) in window B2..B3 of step t + 1, where the shadow waves
+// have next to nothing to do; it re-reads {value, class} from LDS (valid until wave 0 rewrites them in window 4), so no register carries them; a
+// segment's last step is stored behind the loop.  0 = thread 0 of workgroup 0 stores them between B5 and phase A, on the one workgroup whose
+// publish every all-gather then waits for.  (The same store in window B1..B2, in front of the shadow waves' W_hh1 product, measured -0.2 % against 0.)
+#define T2_OUT_SHADOW 1
+#endif
+#ifndef T2_PREB1_OPERANDS
+// the critical waves' phase-B operands that phase A does not produce (hand[0..2], cstQ[8..10], h2o: written in window 4 / at the previous exchange-1
+// landing) are read in front of B1, behind the step head's other reads: window B1..B2 opens with the x2 reads.  0 = two ds_read_b96 and a
+// ds_read2st64_b32 (the slowest LDS forms, returned in order) stand between B1 and the first ds_read_b128.  (The shadow waves' cstQ[0..2] read the
+// same way measured -1.4 %: it stays behind their s_sleep in window B1..B2.)
+#define T2_PREB1_OPERANDS 1
+#endif
+#ifndef T2_PHILOX_OPAQUE
+#define T2_PHILOX_OPAQUE 1   // see s_noise: pays for the registers that the step head's operands hold across the back edge; alone neutral in time
 #endif
 #ifndef T2_PRESLEEP
-#define T2_PRESLEEP 0   // developer knob: s_sleep units in front of the first look
+#define T2_PRESLEEP 0  // developer knob: s_sleep units in front of the first look
 #endif
 
 // T2_HOIST_LDS: every consumer of a hoisted value sits in `if (q == 0)` behind the DPP row sums, and the compiler sinks a plain read into
@@ -250,6 +274,38 @@ constexpr unsigned G_X3 = 0, G_F1 = 1024, G_F2 = 2048, G_PR = 3072, G_GH = 4096;
         }                                                                   \
     } while (0)
 
+// The step head's reads, expanded behind B5 and in front of a segment's first step (macros, not lambdas: a lambda that captures the loop-carried
+// operands changes how this kernel, at its register limit, is laid out even where it expands to nothing).  Phase B's (c2 rzn, gh2 rzn, h2) are the
+// critical waves'; the shadow waves read them too and drop them: a role branch in the head costs registers (scratch 80 -> 120 bytes).
+#define T2_PHASE_A_READS()                                                  \
+    do {                                                                    \
+        hA = ((const float4 *)(lds + L_CSTA))[tid];                         \
+        hD = ((const float4 *)(lds + L_COND))[tid];                         \
+        hgr = gh1s[tid]; hgz = gh1s[512 + tid]; hgn = gh1s[1024 + tid];     \
+    } while (0)
+#if T2_PREB1_OPERANDS
+#define T2_PHASE_B_READS()                                                  \
+    do {                                                                    \
+        pq0 = cstQ[8]; pq1 = cstQ[9]; pq2 = cstQ[10];                       \
+        pg0 = hand[0]; pg1 = hand[1]; pg2 = hand[2];                        \
+        ph2 = xb[XB_H2 * XB_VEC + pu];                                      \
+    } while (0)
+#else
+#define T2_PHASE_B_READS() do { } while (0)
+#endif
+// LDS returns a wave's reads in order: phase A's operands go first and phase A waits for them alone (a counted lgkmcnt); phase B's are served while
+// phase A computes.  The fences keep the compiler from sorting the slow ds_read_b96 forms in front of the fed-back sample.
+#define T2_HEAD_READS() do { __builtin_amdgcn_sched_barrier(0); T2_PHASE_A_READS(); __builtin_amdgcn_sched_barrier(0); T2_PHASE_B_READS(); __builtin_amdgcn_sched_barrier(0); } while (0)
+// T2_OUT_SHADOW, thread 256 of workgroup 0: the outputs of step ts from the race result in LDS.  samples_out takes the SAMPLED value also where
+// x_forced feeds another one (:237)
+#define T2_STORE_OUT(ts)                                                                                    \
+    do {                                                                                                    \
+        const float2 win_ = *(const float2 *)(misc_f + 16);                                                 \
+        if (a.labels_out) a.labels_out[(size_t)row * a.steps + (ts)] = __float_as_int(win_.y);              \
+        a.samples_out[(size_t)row * a.steps + (ts)] = win_.x;                                               \
+    } while (0)
+#define T2_OUT_THREAD (T2_OUT_SHADOW && MODE == WRNN_MODE_RAW && g == 0 && tid == 256)
+
 template <int MODE, bool PROF, bool RAGGED>
 __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -417,7 +473,14 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
                     // evaluate 16 DIFFERENT blocks (the next 32 steps) at once instead of the same one 16 times: one
                     // Philox evaluation per lane every 32 steps; the lane that owns step ts hands its draw over.
                     if ((ts & 31) == 0) {
-                        const Philox4 pz = wrnn_raw_block(kseed, (uint64_t)ts + 2u * (unsigned)q, krow, (uint32_t)c3row0);
+                        // T2_PHILOX_OPAQUE: the lane's class pair and block offset are made opaque HERE.  Otherwise the compiler hoists the first Philox
+                        // round's per-lane products out of the step loop and keeps them in spill slots for the whole launch (scratch 108 -> 80 bytes
+                        // with the step head's operands live across the back edge; the same device as in the logits branch below)
+                        int c3p = c3row0, qp = q;
+#if T2_PHILOX_OPAQUE
+                        asm volatile("" : "+v"(c3p), "+v"(qp));
+#endif
+                        const Philox4 pz = wrnn_raw_block(kseed, (uint64_t)ts + 2u * (unsigned)qp, krow, (uint32_t)c3p);
                         // -log q = -log(-log u): the inner log exactly (q is tiny for u -> 1, where v_log_f32 is not accurate
                         // relative to the result -- and such a draw tends to win the race), the outer one fast
                         nzE0 = -__logf(-logf(u01_from_bits(pz.x)));
@@ -460,8 +523,14 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
         }
         __syncthreads();
 
-        int out_k = 0;
-        float out_x = 0.0f;
+        // The step head: what the coming step reads from LDS that no thread writes between B5 and B1 -- phase A's operands (unit j = tid) and,
+        // T2_PREB1_OPERANDS, phase B's.  Issued behind B5 (the first step: behind the barrier above) in one batch, see T2_HEAD_READS.
+        float4 hA = make_float4(0.f, 0.f, 0.f, 0.f), hD = hA;
+        float hgr = 0.f, hgz = 0.f, hgn = 0.f;
+        float pq0 = 0.f, pq1 = 0.f, pq2 = 0.f, pg0 = 0.f, pg1 = 0.f, pg2 = 0.f, ph2 = 0.f;
+#if T2_HEAD_ONE_TRIP
+        T2_HEAD_READS();
+#endif
         for (int64_t t = a.seg0; t < seg_end; ++t) {
             ++epoch;
             const unsigned par = epoch & 1u;
@@ -470,9 +539,11 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
             // ---- phase A (all 512 threads, unit j = tid): I + GRU1, replicated in every WG (:208-212) ----
             float x2_j;
             {
-                const float4 cA = ((const float4 *)(lds + L_CSTA))[tid];
-                const float4 cd = ((const float4 *)(lds + L_COND))[tid];
-                const float ghr = gh1s[tid], ghz = gh1s[512 + tid], ghn = gh1s[1024 + tid];
+#if !T2_HEAD_ONE_TRIP
+                T2_HEAD_READS();
+#endif
+                const float4 cA = hA, cd = hD;
+                const float ghr = hgr, ghz = hgz, ghn = hgn;
                 const float xprev = xfeed;
                 const float xin = fmaf(cA.x, xprev, cd.x);
                 const float rg = sigmoid_fast(fmaf(cA.y, xprev, cd.y) + ghr);
@@ -489,10 +560,14 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
 
             if (isC) {
                 // ---- phase B: GRU2 unit `unit` (:213-216); rows r,z,n of W_ih2[:, :512] . x2 ----
-                float h2o = xb[XB_H2 * XB_VEC + pu];
                 float x2u = xb[XB_X2 * XB_VEC + pu];
+#if T2_PREB1_OPERANDS
+                float h2o = ph2, g2r = pg0, g2z = pg1, g2n = pg2, c2r = pq0, c2z = pq1, c2n = pq2;   // read in the step head
+#else
+                float h2o = xb[XB_H2 * XB_VEC + pu];
                 float g2r = hand[0], g2z = hand[1], g2n = hand[2];
                 float c2r = cstQ[8], c2z = cstQ[9], c2n = cstQ[10];
+#endif
                 hoist_fence();
                 float gr, gz, gn;
                 dot32x3(wv, xb + XB_X2 * XB_VEC, q, gr, gz, gn);
@@ -504,10 +579,6 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
                 const float x3u = x2u + ((1.0f - zg) * ng + zg * h2o);
                 if (q == 0) st_granule(mail, G_X3 + par * 512 + unit, epoch, __float_as_uint(x3u));
             } else {
-                if (T2_DEFER_OUT && MODE == WRNN_MODE_RAW && g == 0 && tid == 256 && t > a.seg0) {   // outputs of step t - 1 (see the merge at the end of the step)
-                    if (a.labels_out) a.labels_out[(size_t)row * a.steps + t - 1] = out_k;
-                    a.samples_out[(size_t)row * a.steps + t - 1] = out_x;
-                }
                 // ---- S: gh1 for the next step = W_hh1 . h1' + b_hh1, published for everyone ----
                 float sr, sz, sn;
                 __builtin_amdgcn_s_sleep(2);   // let the critical waves' x2 reads go first
@@ -543,6 +614,7 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
                 if (q == 0) st_granule(mail, G_F1 + par * 512 + unit, epoch, __float_as_uint(fmaxf(s, 0.0f)));
             } else {
                 // ---- S: sampling noise of step t+1 (C reads the other parity slot this step) ----
+                if (T2_OUT_THREAD && t > a.seg0) T2_STORE_OUT(t - 1);   // the outputs of step t - 1: this window is the shadow waves' lightest
                 if (t + 1 < seg_end) s_noise(t + 1, epoch + 1);
             }
             P2(5);
@@ -755,9 +827,16 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
             __syncthreads();  // B5
             P2(12);
             if (MODE == WRNN_MODE_RAW) {
+#if T2_OUT_SHADOW
+                const float x_new = misc_f[16];   // the sample value of the race winner; its class is read by the thread that stores it
+#else
                 const float2 win = *(const float2 *)(misc_f + 16);   // {sample value, class} of the race winner
                 const float x_new = win.x;
                 const int bk = __float_as_int(win.y);
+#endif
+#if T2_HEAD_ONE_TRIP
+                T2_HEAD_READS();   // the coming step's operands ride on the same wait
+#endif
                 P2(15);
                 // (:237) The teacher-forced value is waited for INSIDE its branch: with `cond ? load : x_new` the compiler cannot know at
                 // the top of the next step whether a load into xfeed is pending and opens EVERY step with `s_waitcnt vmcnt(0)` -- which also
@@ -765,11 +844,7 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
                 // found in the ISA; the same in loop_batch*.hip).
                 xfeed = x_new;
                 if (a.x_forced) { float v = a.x_forced[(size_t)t * a.n_rows + row]; asm volatile("" : "+v"(v)); xfeed = v; }
-                // T2_DEFER_OUT 1 (developer knob, NOT shipped): the outputs of step t stored one step later by a shadow wave of workgroup 0
-                // instead of by thread 0 here, to keep the store acknowledgements off the critical waves.  Measured: 297 -> 293.5
-                // ksamples/s -- the acknowledgements were never on the serial chain.
-                out_k = bk; out_x = x_new;
-#if !T2_DEFER_OUT
+#if !T2_OUT_SHADOW
                 if (g == 0 && tid == 0) {
                     if (a.labels_out) a.labels_out[(size_t)row * a.steps + t] = bk;
                     a.samples_out[(size_t)row * a.steps + t] = x_new;
@@ -777,18 +852,21 @@ __global__ void __launch_bounds__(T2_THREADS, 2) loop_team2_kernel(WrnnTeamArgs 
 #endif
             } else {
                 xfeed = misc_f[M_XF];
+#if T2_HEAD_ONE_TRIP
+                T2_HEAD_READS();
+#endif
             }
             if ((t & 63) == 63) {   // bounded-spin bail-out, checked workgroup-wide every 64 steps
                 if (dead && lane == 0) misc_i[M_DEAD] = 1;
                 __syncthreads();
-                if (misc_i[M_DEAD]) return;
+                if (misc_i[M_DEAD]) {
+                    if (T2_OUT_THREAD) T2_STORE_OUT(t);   // no later step stores them
+                    return;
+                }
             }
         }
         __syncthreads();
-        if (T2_DEFER_OUT && MODE == WRNN_MODE_RAW && g == 0 && tid == 256 && seg_end > a.seg0) {   // the last step's outputs
-            if (a.labels_out) a.labels_out[(size_t)row * a.steps + seg_end - 1] = out_k;
-            a.samples_out[(size_t)row * a.steps + seg_end - 1] = out_x;
-        }
+        if (T2_OUT_THREAD && seg_end > a.seg0) T2_STORE_OUT(seg_end - 1);   // T2_OUT_SHADOW: the segment's last step has no later window
         if (seg_end < (RAGGED ? (int64_t)a.rows[row].steps : a.steps)) {   // hand the recurrent state to the next segment's launch
             if (g == 0) {
                 st[tid] = h1_j;
