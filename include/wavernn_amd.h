@@ -439,6 +439,30 @@ int wrnn_teamg_plan_fmt(const wrnn_config *cfg, int32_t rows_per_team, int32_t w
 /* The six scales of the image last packed on h, in the order fc3, fc2, fc1, rnn2, rnn1, I; 1.0 each for an fp32 or fp16 image, after a
  * refused pack and before any pack. */
 int wrnn_teamg_weight_scales(const wrnn_handle *h, float out[6]);
+/* Block-sparse weight image for the same two kernels (added to ABI 9: new entry points only).  A block is 64 consecutive
+ * elements of one padded image row -- one gate row, segments A (the input's matrix) and B (W_hh) apart: 64-column chunks of fc3, fc2, fc1,
+ * of every gate row of W_ih and, separately, of W_hh, and of I.weight[:, 1:] counted from column 1.  With the setting on, the pack reads
+ * the pattern off the weights: a block is left out if and only if all its weights compare equal to zero (a NaN or an infinity is kept,
+ * nothing is refused), the kernels walk every row's list of kept blocks in ascending order and feed the multiply-adds of the dense fp32
+ * kernel in the same order.  fmaf(0, x, a) == a for finite x, so the outputs are equal, number for number, to the dense fp32 kernel's
+ * on the same model, for any model.  Two caveats: where an activation is not finite the dense kernel yields NaN and the sparse one may
+ * not, and a sum that is exactly zero may differ in the sign of zero.  The values stay fp32: with WRNN_WEIGHTS_F16 or WRNN_WEIGHTS_E4M3
+ * also set, the generate call that would pack fails with WRNN_ERR_UNSUPPORTED naming both settings, and the handle generates again once
+ * either is reset.  The setting is a property of the handle for both kernels, off by default, and no other kernel reads it; changing it
+ * drops the packed image.  The pack waits once, for its census. */
+int wrnn_teamg_set_sparse(wrnn_handle *h, int32_t on);
+int32_t wrnn_teamg_sparse(const wrnn_handle *h);
+/* Host only: wrnn_teamg_plan_fmt(.., WRNN_WEIGHTS_F32, ..) for the sparse image whose rows hold nb_a[l] blocks of segment A and nb_b[l] of
+ * segment B in layer l (every row of a layer has its layer's longest list; shorter rows are padded with zero blocks).  An image row is
+ * its 16-bit block indices, padded to 16 bytes, and its blocks of 64 floats; weight_bytes, resident_bytes_*, streamed_bytes_step and
+ * lds_bytes count such rows, indices included (resident_bytes_team + streamed_bytes_step == weight_bytes, the image's bytes); k and
+ * k_padded stay the dense row's.  WRNN_ERR_INVALID: also a count above the dense row's k_padded / 64 of its segment. */
+int wrnn_teamg_sparse_plan(const wrnn_config *cfg, int32_t rows_per_team, const int32_t nb_a[6], const int32_t nb_b[6], int64_t lds_budget_bytes,
+                           wrnn_teamg_plan_info *out);
+/* The sparse image last packed on h, per layer in the order fc3, fc2, fc1, rnn2, rnn1, I: blocks kept (non-zero), blocks of the dense rows
+ * (units * rows_per_unit * k_padded / 64), nb_a, nb_b, and the plan of the call that last ran it (its rows per team and LDS budget).
+ * Any out pointer may be null.  WRNN_ERR_STATE: no sparse image has been packed since the setting, the format or the weights changed. */
+int wrnn_teamg_sparse_info(wrnn_handle *h, int64_t kept[6], int64_t dense[6], int32_t nb_a[6], int32_t nb_b[6], wrnn_teamg_plan_info *plan);
 
 /* ---- streaming generation (ABI 7) -------------------------------------------------------------------------------------------
  * Mel frames arrive a few at a time (Tacotron's decoder); audio leaves as soon as the frames it depends on are in.  A stream

@@ -43,7 +43,8 @@ EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wr
                     'wrnn_resample_create', 'wrnn_resample_out_len', 'wrnn_resample_bank', 'wrnn_resample', 'wrnn_resample_last_error',
                     'wrnn_resample_destroy', 'wrnn_condition_frames', 'wrnn_condition', 'wrnn_teamg_plan', 'wrnn_debug_teamg_lds_budget',
                     'wrnn_teamg_batch_plan', 'wrnn_last_batch_rows', 'wrnn_teamg_set_weight_format', 'wrnn_teamg_weight_format',
-                    'wrnn_teamg_plan_fmt', 'wrnn_teamg_weight_scales', 'wrnn_train_last_recurrence', 'wrnn_train_teamg_plan',
+                    'wrnn_teamg_plan_fmt', 'wrnn_teamg_weight_scales', 'wrnn_teamg_set_sparse', 'wrnn_teamg_sparse', 'wrnn_teamg_sparse_plan',
+                    'wrnn_teamg_sparse_info', 'wrnn_train_last_recurrence', 'wrnn_train_teamg_plan',
                     'wrnn_train_set_precision', 'wrnn_train_precision', 'wrnn_train_last_gemms', 'wrnn_debug_train_gemm',
                     'wrnn_griffin_create', 'wrnn_griffin_samples', 'wrnn_griffin_tables', 'wrnn_griffin_lim', 'wrnn_deemphasis',
                     'wrnn_griffin_last_error', 'wrnn_griffin_destroy',
@@ -180,12 +181,12 @@ class TeamgPlanInfo(C.Structure):
 
 
 def teamg_plan(lds_budget_bytes: int = -1, *, rnn_dims, fc_dims, bits, pad, upsample_factors, feat_dims, compute_dims, res_out_dims,
-               res_blocks, hop_length, sample_rate=22050, mode='RAW', rows_per_team=None, weights=None) -> dict:
+               res_blocks, hop_length, sample_rate=22050, mode='RAW', rows_per_team=None, weights=None, sparse_blocks=None) -> dict:
     """Host-only ``wrnn_teamg_plan``: how WRNN_KERNEL_TEAMG splits a model of these constructor dims over the 32 workgroups of a team and
     what it keeps in LDS with ``lds_budget_bytes`` for resident weights (< 0: the default, 160 KiB minus the activation vectors).
     ``layers``: name -> dict of the ``wrnn_teamg_layer_info`` fields (``own_first`` / ``own_count`` as lists of 32).
     ``rows_per_team``: ``wrnn_teamg_batch_plan`` instead (see :func:`teamg_batch_plan`); ``weights``: ``wrnn_teamg_plan_fmt`` instead (see
-    :func:`teamg_plan_fmt`)."""
+    :func:`teamg_plan_fmt`); ``sparse_blocks = (nb_a, nb_b)``: ``wrnn_teamg_sparse_plan`` instead (see :func:`teamg_sparse_plan`)."""
     cfg = Config()
     cfg.rnn_dims, cfg.fc_dims, cfg.bits, cfg.pad = rnn_dims, fc_dims, bits, pad
     cfg.n_upsample = len(upsample_factors)
@@ -195,7 +196,14 @@ def teamg_plan(lds_budget_bytes: int = -1, *, rnn_dims, fc_dims, bits, pad, upsa
     cfg.res_blocks, cfg.hop_length, cfg.sample_rate = res_blocks, hop_length, sample_rate
     cfg.mode = MODE_RAW if mode == 'RAW' else MODE_MOL
     info = TeamgPlanInfo()
-    if weights is not None:
+    if sparse_blocks is not None:
+        nb_a, nb_b = ([int(v) for v in nb] for nb in sparse_blocks)
+        if len(nb_a) != 6 or len(nb_b) != 6:
+            raise ValueError('sparse_blocks: six counts per segment, in the order of TEAMG_LAYER_NAMES')
+        rows = 1 if rows_per_team is None else int(rows_per_team)
+        rc = load_library().wrnn_teamg_sparse_plan(C.byref(cfg), rows, (C.c_int32 * 6)(*nb_a), (C.c_int32 * 6)(*nb_b), int(lds_budget_bytes), C.byref(info))
+        what = f'wrnn_teamg_sparse_plan({rows} rows per team, blocks {nb_a} / {nb_b})'
+    elif weights is not None:
         if not isinstance(weights, str) or weights not in TEAMG_WEIGHT_FORMATS:
             raise ValueError(f'weights must be one of {sorted(TEAMG_WEIGHT_FORMATS)}, not {weights!r}')
         rows = 1 if rows_per_team is None else int(rows_per_team)
@@ -266,6 +274,14 @@ def teamg_plan_fmt(rows_per_team: int, weights: str, lds_budget_bytes: int = -1,
     with 'f16' every byte figure counts 2-byte weights, with 'e4m3' 1-byte weights, and more units fit the same LDS budget; ownership and
     ``k_padded`` are unchanged."""
     return teamg_plan(lds_budget_bytes, rows_per_team=int(rows_per_team), weights=weights, **dims)
+
+
+def teamg_sparse_plan(rows_per_team: int, nb_a, nb_b, lds_budget_bytes: int = -1, **dims) -> dict:
+    """Host-only ``wrnn_teamg_sparse_plan``: :func:`teamg_batch_plan` for the block-sparse fp32 image whose rows hold ``nb_a[l]`` blocks of
+    segment A and ``nb_b[l]`` of segment B in layer ``l`` (order of ``TEAMG_LAYER_NAMES``).  Same dict; the byte figures count the image's
+    rows, 16-bit block indices included; ``k`` and ``k_padded`` stay the dense row's.  ``WrnnError`` (WRNN_ERR_INVALID) for a count above
+    the dense row's."""
+    return teamg_plan(lds_budget_bytes, rows_per_team=int(rows_per_team), sparse_blocks=(nb_a, nb_b), **dims)
 
 
 _lib: Optional[C.CDLL] = None
@@ -379,6 +395,14 @@ def load_library() -> C.CDLL:
     lib.wrnn_teamg_weight_format.restype = C.c_int32
     lib.wrnn_teamg_weight_scales.argtypes = [vp, C.POINTER(C.c_float)]
     lib.wrnn_teamg_weight_scales.restype = C.c_int
+    lib.wrnn_teamg_set_sparse.argtypes = [vp, C.c_int32]
+    lib.wrnn_teamg_set_sparse.restype = C.c_int
+    lib.wrnn_teamg_sparse.argtypes = [vp]
+    lib.wrnn_teamg_sparse.restype = C.c_int32
+    lib.wrnn_teamg_sparse_plan.argtypes = [C.POINTER(Config), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64, C.POINTER(TeamgPlanInfo)]
+    lib.wrnn_teamg_sparse_plan.restype = C.c_int
+    lib.wrnn_teamg_sparse_info.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(TeamgPlanInfo)]
+    lib.wrnn_teamg_sparse_info.restype = C.c_int
     lib.wrnn_train_last_recurrence.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.wrnn_train_last_recurrence.restype = C.c_int
     lib.wrnn_train_teamg_plan.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -744,11 +768,37 @@ class NativeVocoder:
         self._check(self.lib.wrnn_teamg_weight_scales(self._h, out))
         return np.array(out[:], np.float32)
 
+    def set_teamg_sparse(self, on: bool):
+        """Block-sparse fp32 weight image for TEAMG / TEAMG_BATCH (``wrnn_teamg_set_sparse``): the pack leaves out every 64-element block of
+        an image row whose weights are all zero.  A change makes the next call of either kernel pack again.  No other kernel reads it."""
+        if not isinstance(on, (bool, np.bool_)):
+            raise ValueError(f'teamg sparse must be a bool, not {on!r}')
+        self._check(self.lib.wrnn_teamg_set_sparse(self._h, 1 if on else 0))
+
+    @property
+    def teamg_sparse(self) -> bool:
+        return bool(self.lib.wrnn_teamg_sparse(self._h))
+
+    def teamg_sparse_info(self) -> dict:
+        """``wrnn_teamg_sparse_info``: the sparse image last packed.  ``layers``: name -> ``dict(kept, dense, nb_a, nb_b)`` (non-zero blocks,
+        blocks of the dense rows, blocks per image row and segment); ``kept`` / ``dense``: their sums; ``plan``: the plan in force (the
+        dict of :func:`teamg_sparse_plan`).  ``WrnnError`` (WRNN_ERR_STATE) before a call has packed a sparse image."""
+        kept, dense, nb_a, nb_b = (C.c_int64 * 6)(), (C.c_int64 * 6)(), (C.c_int32 * 6)(), (C.c_int32 * 6)()
+        info = TeamgPlanInfo()
+        self._check(self.lib.wrnn_teamg_sparse_info(self._h, kept, dense, nb_a, nb_b, C.byref(info)))
+        layers = {n: dict(kept=int(kept[i]), dense=int(dense[i]), nb_a=int(nb_a[i]), nb_b=int(nb_b[i])) for i, n in enumerate(TEAMG_LAYER_NAMES)}
+        plan = {f: int(getattr(info, f)) for f, _ in TeamgPlanInfo._fields_ if f != 'layer'}
+        plan['layers'] = {}
+        for name, li in zip(TEAMG_LAYER_NAMES, info.layer):
+            plan['layers'][name] = {f: (list(getattr(li, f)) if f.startswith('own_') else int(getattr(li, f))) for f, _ in TeamgLayerInfo._fields_ if f != 'reserved_'}
+        return dict(layers=layers, kept=sum(kept[:]), dense=sum(dense[:]), plan=plan)
+
     def last_timing(self) -> dict:
         t = Timing()
         self._check(self.lib.wrnn_last_timing(self._h, C.byref(t)))
         return dict(prologue_ms=t.prologue_ms, loop_ms=t.loop_ms, kernel=t.kernel, rows=t.rows, steps=t.steps,
-                    launches=t.launches, batch_rows=int(self.lib.wrnn_last_batch_rows(self._h)), teamg_weights=self.teamg_weights)
+                    launches=t.launches, batch_rows=int(self.lib.wrnn_last_batch_rows(self._h)), teamg_weights=self.teamg_weights,
+                    teamg_sparse=self.teamg_sparse)
 
 
 def plan_folded(frames, hop: int, target: int, overlap: int) -> Tuple[np.ndarray, int]:

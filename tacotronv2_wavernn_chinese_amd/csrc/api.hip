@@ -193,6 +193,7 @@ void wrnn_destroy(wrnn_handle *h) {
     if (h->team_w) (void)hipFree(h->team_w);
     if (h->team_fc3) (void)hipFree(h->team_fc3);
     if (h->teamg_img) (void)hipFree(h->teamg_img);
+    if (h->teamg_sp_flags) (void)hipFree(h->teamg_sp_flags);
     if (h->batch_w) (void)hipFree(h->batch_w);
     if (h->batch_fc3) (void)hipFree(h->batch_fc3);
     if (h->batch_wn) (void)hipFree(h->batch_wn);
@@ -237,7 +238,7 @@ int wrnn_teamg_set_weight_format(wrnn_handle *h, int32_t fmt) {
     if (!h) return WRNN_ERR_INVALID;
     if (fmt != WRNN_WEIGHTS_F32 && fmt != WRNN_WEIGHTS_F16 && fmt != WRNN_WEIGHTS_E4M3)   // 2 is reserved
         return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_teamg_set_weight_format: %d is none of WRNN_WEIGHTS_F32, WRNN_WEIGHTS_F16, WRNN_WEIGHTS_E4M3", fmt);
-    if (fmt != h->teamg_fmt) h->teamg_img_ok = false;   // the next TEAMG / TEAMG_BATCH call packs the image in the new element type
+    if (fmt != h->teamg_fmt) { h->teamg_img_ok = false; h->teamg_sp_ok = false; }   // the next TEAMG / TEAMG_BATCH call packs the image in the new element type
     h->teamg_fmt = fmt;
     return WRNN_OK;
 }
@@ -245,6 +246,26 @@ int32_t wrnn_teamg_weight_format(const wrnn_handle *h) { return h ? h->teamg_fmt
 int wrnn_teamg_weight_scales(const wrnn_handle *h, float out[6]) {
     if (!h || !out) return WRNN_ERR_INVALID;
     for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) out[l] = h->teamg_scale[l];
+    return WRNN_OK;
+}
+int wrnn_teamg_set_sparse(wrnn_handle *h, int32_t on) {
+    if (!h) return WRNN_ERR_INVALID;
+    if ((on != 0) != h->teamg_sparse) { h->teamg_img_ok = false; h->teamg_sp_ok = false; }   // the next TEAMG / TEAMG_BATCH call packs the other image
+    h->teamg_sparse = on != 0;
+    return WRNN_OK;
+}
+int32_t wrnn_teamg_sparse(const wrnn_handle *h) { return h && h->teamg_sparse ? 1 : 0; }
+int wrnn_teamg_sparse_info(wrnn_handle *h, int64_t kept[6], int64_t dense[6], int32_t nb_a[6], int32_t nb_b[6], wrnn_teamg_plan_info *plan) {
+    if (!h) return WRNN_ERR_INVALID;
+    if (!h->teamg_sp_ok || !h->teamg_img_ok)
+        return wrnn_fail(h, WRNN_ERR_STATE, "wrnn_teamg_sparse_info: no block-sparse image is packed (wrnn_teamg_set_sparse(h, 1), then a TEAMG / TEAMG_BATCH call)");
+    for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) {
+        if (kept) kept[l] = h->teamg_sp_kept[l];
+        if (dense) dense[l] = h->teamg_sp_dense[l];
+        if (nb_a) nb_a[l] = h->teamg_nb_a[l];
+        if (nb_b) nb_b[l] = h->teamg_nb_b[l];
+    }
+    if (plan) return wrnn_teamg_plan_info_impl(&h->cfg, h->teamg_sp_rows, WRNN_WEIGHTS_F32, h->teamg_sp_budget, plan, h->teamg_nb_a, h->teamg_nb_b);
     return WRNN_OK;
 }
 int32_t wrnn_n_classes(const wrnn_handle *h) { return h ? h->d.NC : 0; }
@@ -474,6 +495,7 @@ int wrnn_load_weights(wrnn_handle *h, const wrnn_tensor_desc *tensors, int32_t n
     WRNN_HIP_TRY(h, hipMalloc(&h->wdev, o.total * sizeof(float)));
     WRNN_HIP_TRY(h, hipMemcpy(h->wdev, pk.data(), o.total * sizeof(float), hipMemcpyHostToDevice));
     h->teamg_img_ok = false;   // the TEAMG image is packed from wdev by the next TEAMG call
+    h->teamg_sp_ok = false;
     h->loaded = true;
     return WRNN_OK;
 }
@@ -599,6 +621,14 @@ static int teamg_image(wrnn_handle *h, const WrnnTeamGPlan &plan, hipStream_t s)
     if (h->teamg_img_ok) return WRNN_OK;
     if (h->teamg_img) { (void)hipFree(h->teamg_img); h->teamg_img = nullptr; }
     WRNN_HIP_TRY(h, hipMalloc(&h->teamg_img, wrnn_teamg_img_bytes(plan)));
+    if (h->teamg_sparse) {
+        // the census has run (teamg_plan): compaction by its flags, no further wait
+        for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) h->teamg_scale[l] = 1.0f;
+        WRNN_HIP_TRY(h, wrnn_teamg_sparse_pack(h, plan, h->teamg_nb_a, h->teamg_nb_b, h->teamg_sp_flags, h->teamg_img, s));
+        h->teamg_img_ok = true;
+        WRNN_HIP_TRY(h, hipEventRecord(h->ev[1], s));
+        return WRNN_OK;
+    }
     int bad = -1;
     WRNN_HIP_TRY(h, wrnn_teamg_pack(h, plan, h->teamg_img, s, &bad, h->teamg_scale));
     if (bad >= 0 && plan.esz == 1) {
@@ -613,6 +643,32 @@ static int teamg_image(wrnn_handle *h, const WrnnTeamGPlan &plan, hipStream_t s)
     WRNN_HIP_TRY(h, hipEventRecord(h->ev[1], s));   // the one-time image is not loop time
     return WRNN_OK;
 }
+// The plan of a TEAMG / TEAMG_BATCH call in the handle's format and setting; nullptr or why not (*rc = the error).  With the sparse setting
+// on and no image packed, the census runs first (one wait): the plan needs each layer's longest list.  `probe`: only whether a plan
+// exists for rb rows, nothing is recorded.
+static const char *teamg_plan(wrnn_handle *h, const WrnnDims &d, int rb, WrnnTeamGPlan &plan, hipStream_t s, int *rc, bool probe = false) {
+    const int esz = h->teamg_fmt == WRNN_WEIGHTS_E4M3 ? 1 : h->teamg_fmt == WRNN_WEIGHTS_F16 ? 2 : 4;
+    *rc = WRNN_ERR_UNSUPPORTED;
+    if (!h->teamg_sparse) return wrnn_teamg_make_plan(d, h->teamg_budget, plan, rb, esz);
+    if (esz != 4)
+        return h->teamg_fmt == WRNN_WEIGHTS_F16 ? "the sparse weight image (wrnn_teamg_set_sparse) holds fp32 values: it cannot be combined with WRNN_WEIGHTS_F16; reset either setting"
+                                                : "the sparse weight image (wrnn_teamg_set_sparse) holds fp32 values: it cannot be combined with WRNN_WEIGHTS_E4M3; reset either setting";
+    if (!h->teamg_img_ok && !h->teamg_sp_ok) {
+        if (h->teamg_sp_flags) { (void)hipFree(h->teamg_sp_flags); h->teamg_sp_flags = nullptr; }
+        hipError_t e = hipMalloc(&h->teamg_sp_flags, wrnn_teamg_sparse_flag_bytes(d));
+        if (e == hipSuccess) e = wrnn_teamg_sparse_census(h, h->teamg_sp_flags, s, h->teamg_nb_a, h->teamg_nb_b, h->teamg_sp_kept, h->teamg_sp_dense);
+        if (e != hipSuccess) { *rc = WRNN_ERR_HIP; return hipGetErrorString(e); }
+        h->teamg_sp_ok = true;
+    }
+    const char *why = wrnn_teamg_make_plan(d, h->teamg_budget, plan, rb, 4, h->teamg_nb_a, h->teamg_nb_b);
+    if (!why && !probe) { h->teamg_sp_budget = h->teamg_budget; h->teamg_sp_rows = rb; }
+    return why;
+}
+static void teamg_sparse_args(const wrnn_handle *h, WrnnTeamGSparse &sp) {
+    sp = WrnnTeamGSparse{};
+    sp.on = h->teamg_sparse ? 1 : 0;
+    for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) { sp.nbA[l] = h->teamg_nb_a[l]; sp.nbB[l] = h->teamg_nb_b[l]; }
+}
 static int teamg_esz(const wrnn_handle *h) { return h->teamg_fmt == WRNN_WEIGHTS_E4M3 ? 1 : h->teamg_fmt == WRNN_WEIGHTS_F16 ? 2 : 4; }
 // the scales of the packed image into a plan made for this call (wrnn_teamg_make_plan leaves them 1)
 static void teamg_plan_scales(const wrnn_handle *h, WrnnTeamGPlan &p) {
@@ -625,9 +681,10 @@ static int run_teamg(wrnn_handle *h, const WrnnLoopArgs &a, int snake, int n_slo
     if (h->force_no_teams) return wrnn_fail(h, WRNN_ERR_INVALID, "team kernels disabled by wrnn_debug_force_no_teams (test hook)");
     if (h->n_teams < 1) return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "WRNN_KERNEL_TEAMG: fewer than 32 CUs visible (one team = the 32 CUs of an XCD)");
     WrnnTeamGArgs ga{};
-    if (const char *why = wrnn_teamg_make_plan(a.d, h->teamg_budget, ga.plan, 1, teamg_esz(h))) return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "%s", why);
+    int prc = 0;
+    if (const char *why = teamg_plan(h, a.d, 1, ga.plan, s, &prc)) return wrnn_fail(h, prc, "%s", why);
     int blocks = 0;
-    const hipError_t oe = wrnn_teamg_occupancy(ga.plan, &blocks);
+    const hipError_t oe = wrnn_teamg_occupancy(ga.plan, &blocks, h->teamg_sparse);
     (void)hipGetLastError();
     if (oe != hipSuccess || blocks < 1)
         return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "WRNN_KERNEL_TEAMG: loop_teamg_kernel cannot be resident on a CU with %zu bytes of LDS (%s)",
@@ -636,6 +693,7 @@ static int run_teamg(wrnn_handle *h, const WrnnLoopArgs &a, int snake, int n_slo
     teamg_plan_scales(h, ga.plan);
     ga.a = a; ga.img = h->teamg_img; ga.sched = h->sched_dev; ga.n_slots = n_slots; ga.ragged = snake; ga.n_teams = h->n_teams;
     ga.mail = h->mail; ga.ctl = h->ctl;
+    teamg_sparse_args(h, ga.sp);
     const size_t mail_bytes = (size_t)h->n_teams * ga.plan.mail_granules * sizeof(unsigned long long);   // sized from the dims; <= WRNN_MAIL_BYTES
     WRNN_HIP_TRY(h, wrnn_gated_launch(h->cfg.device, s, h->mail, mail_bytes, h->ctl, TEAM_CTL_WORDS * sizeof(unsigned), [&] { return wrnn_launch_loop_teamg(ga, s); }));
     return WRNN_OK;
@@ -648,9 +706,10 @@ static int run_teamg_batch(wrnn_handle *h, const WrnnLoopArgs &a, int snake, int
     if (h->n_teams < 1) return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "WRNN_KERNEL_TEAMG_BATCH: fewer than 32 CUs visible (one team = the 32 CUs of an XCD)");
     const int rb = wrnn_teamg_batch_inst(rpb);
     WrnnTeamGBatchArgs ga{};
-    if (const char *why = wrnn_teamg_make_plan(a.d, h->teamg_budget, ga.plan, rb, teamg_esz(h))) return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "%s (batch_rows %d runs as %d)", why, rpb, rb);
+    int prc = 0;
+    if (const char *why = teamg_plan(h, a.d, rb, ga.plan, s, &prc)) return wrnn_fail(h, prc, "%s (batch_rows %d runs as %d)", why, rpb, rb);
     int blocks = 0;
-    const hipError_t oe = wrnn_teamg_batch_occupancy(ga.plan, rb, &blocks);
+    const hipError_t oe = wrnn_teamg_batch_occupancy(ga.plan, rb, &blocks, h->teamg_sparse);
     (void)hipGetLastError();
     if (oe != hipSuccess || blocks < 1)
         return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "WRNN_KERNEL_TEAMG_BATCH: loop_teamg_batch_kernel<%d> cannot be resident on a CU with %zu bytes of LDS (%s)", rb,
@@ -659,6 +718,7 @@ static int run_teamg_batch(wrnn_handle *h, const WrnnLoopArgs &a, int snake, int
     teamg_plan_scales(h, ga.plan);
     ga.a = a; ga.img = h->teamg_img; ga.order = h->order_dev; ga.rpb = rpb; ga.snake = snake; ga.n_teams = h->n_teams;
     ga.mail = h->mail; ga.ctl = h->ctl;
+    teamg_sparse_args(h, ga.sp);
     const size_t mail_bytes = (size_t)h->n_teams * ga.plan.mail_granules * sizeof(unsigned long long);   // <= WRNN_MAIL_BYTES: the plan refuses more
     WRNN_HIP_TRY(h, wrnn_gated_launch(h->cfg.device, s, h->mail, mail_bytes, h->ctl, TEAM_CTL_WORDS * sizeof(unsigned), [&] { return wrnn_launch_loop_teamg_batch(ga, rb, s); }));
     return WRNN_OK;

@@ -215,11 +215,68 @@ __device__ __forceinline__ void tg_dot8(const unsigned char *__restrict__ rp, in
     for (int g = 0; g < G; ++g) sb[g] = row_sum(a0[g] + a1[g]);
 }
 
+// tg_dot on the block-sparse image (WrnnTeamGSparse): rp = the unit's first image row, rows `rs` floats apart, each [nK 16-bit block
+// indices, padded to 16 bytes][nK blocks of 64 floats].  List entry j stands for step idx[j] of the dense row: x = xp[idx * 16], w = block
+// j's float4 q -- the four multiply-adds of that step into the same a0 / a1 chains.  A list ascends inside a segment (entries [0, nA) and
+// [nA, nK)) and leaves out only steps whose 64 weights are zero, which change no chain (fmaf(0, x, a) == a for finite x); the zero blocks
+// that pad a short list change none either.  Every row has its own list.  The indices and the weights of four entries are loaded together,
+// then the activation reads, whose addresses wait for the indices: tg_dot's weight bytes in flight.
+template <int G>
+__device__ __forceinline__ void tg_dots(const float *__restrict__ rp, int rs, int q, const float4 *xp, int nA, int nK, float (&sa)[G], float (&sb)[G]) {
+    const int idxf = (nK + 7) / 8 * 4;   // wrnn_teamg_sparse_idx_elems
+    const unsigned short *ip[G];
+    const float4 *wp[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        ip[g] = (const unsigned short *)(rp + (size_t)g * rs);
+        wp[g] = (const float4 *)(rp + (size_t)g * rs + idxf) + q;
+    }
+    float a0[G], a1[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) a0[g] = a1[g] = 0.0f;
+    auto block = [&](auto nu, int j) {
+        constexpr int NU = decltype(nu)::value;
+        int id[NU][G];
+        float4 w[NU][G];
+#pragma unroll
+        for (int u = 0; u < NU; ++u)
+#pragma unroll
+            for (int g = 0; g < G; ++g) id[u][g] = ip[g][j + u];
+#pragma unroll
+        for (int u = 0; u < NU; ++u)
+#pragma unroll
+            for (int g = 0; g < G; ++g) w[u][g] = wp[g][(j + u) * 16];
+#pragma unroll
+        for (int u = 0; u < NU; ++u)
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const float4 x = xp[id[u][g] * 16];
+                a0[g] = fmaf(w[u][g].x, x.x, a0[g]); a1[g] = fmaf(w[u][g].y, x.y, a1[g]);
+                a0[g] = fmaf(w[u][g].z, x.z, a0[g]); a1[g] = fmaf(w[u][g].w, x.w, a1[g]);
+            }
+    };
+    auto segment = [&](int j0, int j1) {
+        int j = j0;
+#pragma unroll 1
+        for (; j + 4 <= j1; j += 4) block(std::integral_constant<int, 4>{}, j);
+        if (j + 2 <= j1) { block(std::integral_constant<int, 2>{}, j); j += 2; }
+        if (j < j1) block(std::integral_constant<int, 1>{}, j);
+    };
+    segment(0, nA);
+#pragma unroll
+    for (int g = 0; g < G; ++g) { sa[g] = row_sum(a0[g] + a1[g]); a0[g] = a1[g] = 0.0f; }
+    segment(nA, nK);
+#pragma unroll
+    for (int g = 0; g < G; ++g) sb[g] = row_sum(a0[g] + a1[g]);
+}
+
 // G rows from row `row0` of a layer's slice at `base` (LDS or device memory), KP elements each, in the image's element type; `scale` is the
-// layer's (e4m3 only: a power of two, so scaling the two sums equals scaling every weight)
+// layer's (e4m3 only: a power of two, so scaling the two sums equals scaling every weight).  TgSparse: KP = the floats of an image row,
+// nA / nK count list entries
 template <int G, typename WT>
 __device__ __forceinline__ void tg_rows(const WT *base, int row0, int KP, float scale, int q, const float4 *xp, int nA, int nK, float (&sa)[G], float (&sb)[G]) {
-    if constexpr (sizeof(WT) == 4) tg_dot<G>((const float4 *)(base + (size_t)row0 * KP) + q, KP / 4, xp, nA, nK, sa, sb);
+    if constexpr (std::is_same<WT, TgSparse>::value) tg_dots<G>((const float *)base + (size_t)row0 * KP, KP, q, xp, nA, nK, sa, sb);
+    else if constexpr (sizeof(WT) == 4) tg_dot<G>((const float4 *)(base + (size_t)row0 * KP) + q, KP / 4, xp, nA, nK, sa, sb);
     else if constexpr (sizeof(WT) == 2) tg_dot16<G>((const TgHalf8 *)(base + (size_t)row0 * KP), KP / 8, row0, q, xp, nA, nK, sa, sb);
     else {
         tg_dot8<G>((const unsigned char *)(base + (size_t)row0 * KP), KP, row0, q, xp, nA, nK, sa, sb);
@@ -241,6 +298,7 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
     int *misc_i = (int *)misc;
     float *f1 = lds + ly.f1, *f2 = lds + ly.f2, *f3 = lds + ly.f3;
     WT *wres = (WT *)(lds + ly.total);   // resident weights, in the image's element type
+    constexpr bool SP = std::is_same<WT, TgSparse>::value;   // the block-sparse image: a layer's steps are its list entries
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int qw = tid >> 4, q = tid & 15;
@@ -298,7 +356,7 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
     // the own rows of W_I[:, 1:] . [m | a1] + b_I for the step whose conditioning is in cbuf -> mailbox, tagged `tag`
     auto xc_publish = [&](const float *cbuf, unsigned tag) {
         const WrnnTeamGLayer &L = ta.plan.L[WRNN_TEAMG_COND];
-        const int nown = owned(L), nK = L.KP / 64;
+        const int nown = owned(L), nK = SP ? tg_sp_nk(ta.plan, ta.sp, L) : L.KP / 64;
         for (int ul = qw; ul < nown; ul += 32) {
             float sa[1], sb[1];
             if (ul < L.nres) tg_rows<1>(wres + L.lds_off, ul, L.KP, L.scale, q, (const float4 *)cbuf + q, nK, nK, sa, sb);
@@ -311,7 +369,7 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
     // With 16 or fewer units per workgroup (rnn_dims <= 512) a unit per 16-lane group would leave half the groups, and their loads in
     // flight, idle: then a group takes one gate ROW, the sums meet in LDS and one lane per unit finishes the cell.  Same sums either way.
     auto gru_phase = [&](const WrnnTeamGLayer &L, const float *xin, size_t obih, size_t obhh, unsigned region, unsigned epoch) {
-        const int nown = owned(L), nA = L.KAP / 64, nK = L.KP / 64;
+        const int nown = owned(L), nA = SP ? tg_sp_na(ta.plan, ta.sp, L) : L.KAP / 64, nK = SP ? tg_sp_nk(ta.plan, ta.sp, L) : L.KP / 64;
         const bool by_row = L.U <= 16;
         if (by_row) {
             float *gs = lds + ly.gs;
@@ -342,7 +400,7 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
     };
     // relu(W . x + b) of the own rows -> mailbox
     auto fc_phase = [&](const WrnnTeamGLayer &L, const float *xin, size_t ob, unsigned region, unsigned epoch) {
-        const int nown = owned(L), nK = L.KP / 64;
+        const int nown = owned(L), nK = SP ? tg_sp_nk(ta.plan, ta.sp, L) : L.KP / 64;
         for (int ul = qw; ul < nown; ul += 32) {
             float sa[1], sb[1];
             if (ul < L.nres) tg_rows<1>(wres + L.lds_off, ul, L.KP, L.scale, q, (const float4 *)xin + q, nK, nK, sa, sb);
@@ -425,7 +483,7 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_kernel(WrnnTeamGArgs ta
             // ---- 5. logits = fc3(x) :223 of the own classes, and the sampler :225-237 ----
             {
                 const WrnnTeamGLayer &L = ta.plan.L[WRNN_TEAMG_FC3];
-                const int nown = owned(L), nK = L.KP / 64;
+                const int nown = owned(L), nK = SP ? tg_sp_nk(ta.plan, ta.sp, L) : L.KP / 64;
                 float bv = -INFINITY;
                 int bi = 0x7fffffff;
                 for (int ul = qw; ul < nown; ul += 32) {
@@ -557,6 +615,75 @@ __global__ void __launch_bounds__(256) teamg_absmax_kernel(const float *__restri
     if (m) atomicMax(out, m);
 }
 
+// The two sources of an image row of the sparse pack: element p < KAP of the padded row of unit u is a[(ka0 + p) * lda + ca + u] for
+// p < KA, element KAP + p is b[p * ldb + cb + u] for p < KB (b = nullptr: no segment B); everything else is padding.
+struct TgSpSrc {
+    const float *a, *b;
+    int lda, ca, ka0, KA, ldb, cb, KB;
+};
+__device__ __forceinline__ float tg_sp_elem(const TgSpSrc &s, int unit, int KAP, int p) {
+    if (p < KAP) return p < s.KA ? s.a[(size_t)(s.ka0 + p) * s.lda + s.ca + unit] : 0.0f;
+    p -= KAP;
+    return p < s.KB ? s.b[(size_t)p * s.ldb + s.cb + unit] : 0.0f;
+}
+// counters of the census, per layer, behind the flags
+struct TgSpStat { unsigned nbA, nbB; unsigned long long kept; };
+
+// The census: one workgroup per unit and gate, thread t the blocks t, t + 256, ... of the padded row (nKd of them, the first nAd segment
+// A's).  flags[(unit * G + gate) * nKd + block] = 1 where a weight of the block does not compare equal to zero (a NaN does not); the
+// layer's counters take the row's counts.  Blocks of padding only are zero by tg_sp_elem.
+__global__ void __launch_bounds__(256) teamg_sp_census_kernel(TgSpSrc src, int G, int gate, int KAP, int nAd, int nKd, unsigned char *flags, TgSpStat *st) {
+    __shared__ unsigned cnt[2];
+    const int unit = blockIdx.x;
+    if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    unsigned char *f = flags + ((size_t)unit * G + gate) * nKd;
+    for (int b = threadIdx.x; b < nKd; b += 256) {
+        bool nz = false;
+        for (int c = 0; c < 64; ++c) nz |= !(tg_sp_elem(src, unit, KAP, b * 64 + c) == 0.0f);
+        f[b] = nz;
+        if (nz) atomicAdd(&cnt[b < nAd ? 0 : 1], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (cnt[0]) atomicMax(&st->nbA, cnt[0]);
+        if (cnt[1]) atomicMax(&st->nbB, cnt[1]);
+        if (cnt[0] + cnt[1]) atomicAdd(&st->kept, (unsigned long long)(cnt[0] + cnt[1]));
+    }
+}
+
+// The compaction: one workgroup per unit and gate writes its image row -- rs floats: [nbA + nbB 16-bit indices, padded to 16 bytes][the
+// blocks].  Thread 0 lists the flagged blocks in ascending order, segment A's from entry 0 and B's from entry nbA; the entries a short
+// row leaves keep the zero blocks of the memset and get the index of their segment's first block.  Then all threads copy the listed blocks.
+__global__ void __launch_bounds__(256) teamg_sp_pack_kernel(TgSpSrc src, int U, int G, int gate, int KAP, int nAd, int nKd, int nbA, int nbB, int rs,
+                                                            const unsigned char *__restrict__ flags, float *__restrict__ img, size_t wg_stride, size_t layer_off) {
+    __shared__ int n_list[2];
+    const int unit = blockIdx.x;
+    const int g = unit / U, ul = unit - g * U;
+    float *row = img + (size_t)g * wg_stride + layer_off + (size_t)(ul * G + gate) * rs;
+    unsigned short *idx = (unsigned short *)row;
+    const int nb = nbA + nbB;
+    float *blocks = row + (nb + 7) / 8 * 4;
+    const unsigned char *f = flags + ((size_t)unit * G + gate) * nKd;
+    if (threadIdx.x == 0) {
+        int ja = 0, jb = 0;
+        for (int b = 0; b < nAd; ++b)
+            if (f[b] && ja < nbA) idx[ja++] = (unsigned short)b;
+        for (int b = nAd; b < nKd; ++b)
+            if (f[b] && jb < nbB) idx[nbA + jb++] = (unsigned short)b;
+        n_list[0] = ja; n_list[1] = jb;
+        for (int j = ja; j < nbA; ++j) idx[j] = 0;
+        for (int j = jb; j < nbB; ++j) idx[nbA + j] = (unsigned short)nAd;
+    }
+    __syncthreads();   // the list is read back from the image: a workgroup's own global writes are visible to it behind the barrier
+    const int ja = n_list[0], jb = n_list[1];
+    for (int e = threadIdx.x; e < nb * 64; e += 256) {
+        const int j = e >> 6, c = e & 63;
+        if (j < nbA ? j >= ja : j - nbA >= jb) continue;
+        blocks[e] = tg_sp_elem(src, unit, KAP, (int)idx[j] * 64 + c);
+    }
+}
+
 }  // namespace
 
 float wrnn_teamg_e4m3_scale(float amax) {
@@ -569,7 +696,7 @@ float wrnn_teamg_e4m3_scale(float amax) {
 
 const char *const wrnn_teamg_layer_names[WRNN_TEAMG_LAYERS] = {"fc3", "fc2", "fc1", "rnn2", "rnn1", "I"};
 
-const char *wrnn_teamg_make_plan(const WrnnDims &d, int64_t budget, WrnnTeamGPlan &p, int rows_per_team, int esz) {
+const char *wrnn_teamg_make_plan(const WrnnDims &d, int64_t budget, WrnnTeamGPlan &p, int rows_per_team, int esz, const int32_t *nb_a, const int32_t *nb_b) {
     const TgLay ly(d);
     const int RB = rows_per_team;
     p = WrnnTeamGPlan{};
@@ -585,6 +712,15 @@ const char *wrnn_teamg_make_plan(const WrnnDims &d, int64_t budget, WrnnTeamGPla
     set(WRNN_TEAMG_RNN2, d.H, 3, d.H + d.A, d.H);
     set(WRNN_TEAMG_RNN1, d.H, 3, d.H, d.H);
     set(WRNN_TEAMG_COND, d.H, 1, d.F + d.A, 0);
+    if (nb_a && nb_b) {
+        // the block-sparse image: a row is its index list and its blocks (wrnn_internal.h); 16-bit indices
+        for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) {
+            WrnnTeamGLayer &L = p.L[l];
+            if (L.KP / 64 > 65535) return "the block-sparse image: a row of more than 65535 blocks";
+            if (nb_a[l] < 0 || nb_b[l] < 0 || nb_a[l] > L.KAP / 64 || nb_b[l] > (L.KP - L.KAP) / 64) return "the block-sparse image: more blocks than the dense row has";
+            L.KP = wrnn_teamg_sparse_row_elems(nb_a[l] + nb_b[l]);
+        }
+    }
     // one row: TgLay as ever; RB rows in lock-step: TgbLay, and every mailbox region once per row
     const int64_t act_floats = RB == 1 ? ly.total : TgbLay(d, RB).total;
     const int64_t act_bytes = act_floats * 4;
@@ -607,7 +743,7 @@ const char *wrnn_teamg_make_plan(const WrnnDims &d, int64_t budget, WrnnTeamGPla
     for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) {
         WrnnTeamGLayer &L = p.L[l];
         const int64_t unit = (int64_t)L.G * L.KP;
-        int64_t n = left / unit;
+        int64_t n = unit ? left / unit : L.U;   // a layer with no block at all (the sparse image of an all-zero layer) takes no room
         if (n > L.U) n = L.U;
         L.nres = (int32_t)n;
         L.lds_off = (int32_t)res;
@@ -692,23 +828,120 @@ hipError_t wrnn_teamg_pack(const wrnn_handle *h, const WrnnTeamGPlan &p, void *i
     return hipSuccess;
 }
 
-static const void *teamg_kernel_fn(const WrnnTeamGPlan &p) {
+// ---- the block-sparse pack ----
+
+namespace {
+struct TgSpLayer { int l; TgSpSrc src[3]; };
+// the six layers' sources, gate by gate, as wrnn_teamg_pack's `put`s have them
+void tg_sp_sources(const wrnn_handle *h, TgSpLayer (&out)[WRNN_TEAMG_LAYERS]) {
+    const WrnnDims &d = h->d;
+    const WrnnPacked &o = h->off;
+    const float *w = h->wdev;
+    const int H = d.H, A = d.A, FC = d.FC;
+    auto one = [&](int l, const float *a, int lda, int ka0, int KA) {
+        out[l].l = l;
+        for (int gt = 0; gt < 3; ++gt) out[l].src[gt] = TgSpSrc{a, nullptr, lda, 0, ka0, KA, 0, 0, 0};
+    };
+    auto gru = [&](int l, const float *a, int KA, const float *b) {
+        out[l].l = l;
+        for (int gt = 0; gt < 3; ++gt) out[l].src[gt] = TgSpSrc{a, b, 3 * H, gt * H, 0, KA, 3 * H, gt * H, H};
+    };
+    one(WRNN_TEAMG_FC3, w + o.fc3_t, d.NC, 0, FC);
+    one(WRNN_TEAMG_FC2, w + o.fc2_t, FC, 0, FC + A);
+    one(WRNN_TEAMG_FC1, w + o.fc1_t, FC, 0, H + A);
+    gru(WRNN_TEAMG_RNN2, w + o.r2_wih_t, H + A, w + o.r2_whh_t);
+    gru(WRNN_TEAMG_RNN1, w + o.r1_wih_t, H, w + o.r1_whh_t);
+    one(WRNN_TEAMG_COND, w + o.I_t, H, 1, d.F + A);   // column 0 (the fed-back sample) stays a vector
+}
+// offsets of the layers' flags, the counters behind them
+size_t tg_sp_flag_offsets(const WrnnTeamGPlan &dense, size_t (&off)[WRNN_TEAMG_LAYERS]) {
+    size_t n = 0;
+    for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) {
+        off[l] = n;
+        n += (size_t)dense.L[l].N * dense.L[l].G * (dense.L[l].KP / 64);
+    }
+    return (n + 15) & ~(size_t)15;
+}
+// the dense layer table alone (no budget, one row: sizes that cannot fail for dims a handle holds)
+void tg_sp_dense_layers(const WrnnDims &d, WrnnTeamGPlan &p) { (void)wrnn_teamg_make_plan(d, 0, p, 1, 4); }
+}  // namespace
+
+size_t wrnn_teamg_sparse_flag_bytes(const WrnnDims &d) {
+    WrnnTeamGPlan dense;
+    tg_sp_dense_layers(d, dense);
+    size_t off[WRNN_TEAMG_LAYERS];
+    return tg_sp_flag_offsets(dense, off) + WRNN_TEAMG_LAYERS * sizeof(TgSpStat);
+}
+
+hipError_t wrnn_teamg_sparse_census(const wrnn_handle *h, void *flags, hipStream_t s, int32_t nb_a[WRNN_TEAMG_LAYERS], int32_t nb_b[WRNN_TEAMG_LAYERS],
+                                    int64_t kept[WRNN_TEAMG_LAYERS], int64_t dense_blocks[WRNN_TEAMG_LAYERS]) {
+    WrnnTeamGPlan dense;
+    tg_sp_dense_layers(h->d, dense);
+    size_t off[WRNN_TEAMG_LAYERS];
+    const size_t nflags = tg_sp_flag_offsets(dense, off);
+    TgSpStat *st = (TgSpStat *)((char *)flags + nflags);
+    hipError_t e = hipMemsetAsync(st, 0, WRNN_TEAMG_LAYERS * sizeof(TgSpStat), s);
+    if (e != hipSuccess) return e;
+    (void)hipGetLastError();
+    TgSpLayer src[WRNN_TEAMG_LAYERS];
+    tg_sp_sources(h, src);
+    for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) {
+        const WrnnTeamGLayer &L = dense.L[l];
+        for (int gt = 0; gt < L.G; ++gt)
+            hipLaunchKernelGGL(teamg_sp_census_kernel, dim3(L.N), dim3(256), 0, s, src[l].src[gt], L.G, gt, L.KAP, L.KAP / 64, L.KP / 64, (unsigned char *)flags + off[l],
+                               st + l);
+    }
+    e = hipGetLastError();
+    TgSpStat got[WRNN_TEAMG_LAYERS];
+    if (e == hipSuccess) e = hipMemcpyAsync(got, st, sizeof(got), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);   // the only wait of the sparse pack
+    if (e != hipSuccess) return e;
+    for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) {
+        nb_a[l] = (int32_t)got[l].nbA; nb_b[l] = (int32_t)got[l].nbB; kept[l] = (int64_t)got[l].kept;
+        dense_blocks[l] = (int64_t)dense.L[l].N * dense.L[l].G * (dense.L[l].KP / 64);
+    }
+    return hipSuccess;
+}
+
+hipError_t wrnn_teamg_sparse_pack(const wrnn_handle *h, const WrnnTeamGPlan &p, const int32_t *nb_a, const int32_t *nb_b, const void *flags, void *img, hipStream_t s) {
+    WrnnTeamGPlan dense;
+    tg_sp_dense_layers(h->d, dense);
+    size_t off[WRNN_TEAMG_LAYERS];
+    (void)tg_sp_flag_offsets(dense, off);
+    hipError_t e = hipMemsetAsync(img, 0, wrnn_teamg_img_bytes(p), s);   // the zero blocks that pad a short row; units past N
+    if (e != hipSuccess) return e;
+    (void)hipGetLastError();
+    TgSpLayer src[WRNN_TEAMG_LAYERS];
+    tg_sp_sources(h, src);
+    for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) {
+        const WrnnTeamGLayer &L = p.L[l], &D = dense.L[l];
+        if (nb_a[l] + nb_b[l] == 0) continue;
+        for (int gt = 0; gt < L.G; ++gt)
+            hipLaunchKernelGGL(teamg_sp_pack_kernel, dim3(L.N), dim3(256), 0, s, src[l].src[gt], L.U, L.G, gt, D.KAP, D.KAP / 64, D.KP / 64, nb_a[l], nb_b[l], L.KP,
+                               (const unsigned char *)flags + off[l], (float *)img, (size_t)p.img_elems_wg, (size_t)L.img_off);
+    }
+    return hipGetLastError();
+}
+
+static const void *teamg_kernel_fn(const WrnnTeamGPlan &p, bool sparse = false) {
+    if (sparse) return (const void *)loop_teamg_kernel<TgSparse>;
     return p.esz == 4 ? (const void *)loop_teamg_kernel<float> : p.esz == 2 ? (const void *)loop_teamg_kernel<_Float16> : (const void *)loop_teamg_kernel<TgE4m3>;
 }
 
-hipError_t wrnn_teamg_occupancy(const WrnnTeamGPlan &p, int *blocks_per_cu) {
+hipError_t wrnn_teamg_occupancy(const WrnnTeamGPlan &p, int *blocks_per_cu, bool sparse) {
     const size_t lds = wrnn_teamg_lds_bytes(p);
-    hipError_t e = hipFuncSetAttribute(teamg_kernel_fn(p), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute(teamg_kernel_fn(p, sparse), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, teamg_kernel_fn(p), TG_THREADS, lds);
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, teamg_kernel_fn(p, sparse), TG_THREADS, lds);
 }
 
 hipError_t wrnn_launch_loop_teamg(const WrnnTeamGArgs &a, hipStream_t s) {
     (void)hipGetLastError();
     const size_t lds = wrnn_teamg_lds_bytes(a.plan);
-    hipError_t e = hipFuncSetAttribute(teamg_kernel_fn(a.plan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute(teamg_kernel_fn(a.plan, a.sp.on != 0), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    if (a.plan.esz == 4) hipLaunchKernelGGL(loop_teamg_kernel<float>, dim3(a.n_teams * TEAM_WGS), dim3(TG_THREADS), lds, s, a);
+    if (a.sp.on) hipLaunchKernelGGL(loop_teamg_kernel<TgSparse>, dim3(a.n_teams * TEAM_WGS), dim3(TG_THREADS), lds, s, a);
+    else if (a.plan.esz == 4) hipLaunchKernelGGL(loop_teamg_kernel<float>, dim3(a.n_teams * TEAM_WGS), dim3(TG_THREADS), lds, s, a);
     else if (a.plan.esz == 2) hipLaunchKernelGGL(loop_teamg_kernel<_Float16>, dim3(a.n_teams * TEAM_WGS), dim3(TG_THREADS), lds, s, a);
     else hipLaunchKernelGGL(loop_teamg_kernel<TgE4m3>, dim3(a.n_teams * TEAM_WGS), dim3(TG_THREADS), lds, s, a);
     return hipGetLastError();
@@ -716,21 +949,33 @@ hipError_t wrnn_launch_loop_teamg(const WrnnTeamGArgs &a, hipStream_t s) {
 
 // ---- C ABI: the plan, host only ----
 
-static int teamg_plan_info(const wrnn_config *cfg, int rows_per_team, int fmt, int64_t lds_budget_bytes, wrnn_teamg_plan_info *out) {
+// nb_a / nb_b: the plan of the block-sparse image with those blocks per row (fp32 only); the byte figures then count the image's rows,
+// index lists included, so that resident + streamed == image bytes; k and k_padded stay the dense row's
+int wrnn_teamg_plan_info_impl(const wrnn_config *cfg, int rows_per_team, int fmt, int64_t lds_budget_bytes, wrnn_teamg_plan_info *out, const int32_t *nb_a,
+                              const int32_t *nb_b) {
     if (!cfg || !out || rows_per_team < 1 || rows_per_team > WRNN_TEAMG_BATCH_MAX_ROWS) return WRNN_ERR_INVALID;
     if (fmt != WRNN_WEIGHTS_F32 && fmt != WRNN_WEIGHTS_F16 && fmt != WRNN_WEIGHTS_E4M3) return WRNN_ERR_INVALID;   // 2 is reserved
     const int64_t esz = fmt == WRNN_WEIGHTS_E4M3 ? 1 : fmt == WRNN_WEIGHTS_F16 ? 2 : 4;
     WrnnDims d;
     if (wrnn_dims_from_config(cfg, d) || d.FC > (1 << 20) || d.F > (1 << 20)) return WRNN_ERR_INVALID;
     WrnnTeamGPlan p;
-    if (wrnn_teamg_make_plan(d, lds_budget_bytes, p, rows_per_team, (int)esz)) return WRNN_ERR_UNSUPPORTED;
+    const bool sparse = nb_a && nb_b;
+    if (sparse) {
+        if (fmt != WRNN_WEIGHTS_F32) return WRNN_ERR_INVALID;
+        WrnnTeamGPlan dense;
+        (void)wrnn_teamg_make_plan(d, 0, dense, 1, 4);   // the layer table: a count above the dense row's is the caller's mistake
+        for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l)
+            if (nb_a[l] < 0 || nb_b[l] < 0 || nb_a[l] > dense.L[l].KAP / 64 || nb_b[l] > (dense.L[l].KP - dense.L[l].KAP) / 64) return WRNN_ERR_INVALID;
+    }
+    if (wrnn_teamg_make_plan(d, lds_budget_bytes, p, rows_per_team, (int)esz, nb_a, nb_b)) return WRNN_ERR_UNSUPPORTED;
     *out = wrnn_teamg_plan_info{};
     for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) {
         const WrnnTeamGLayer &L = p.L[l];
         wrnn_teamg_layer_info &o = out->layer[l];
         const int K = L.KA + L.KB;
-        o.units = L.N; o.rows_per_unit = L.G; o.k = K; o.k_padded = L.KP; o.resident_units = L.nres;
-        o.weight_bytes = esz * L.N * L.G * K;
+        const int64_t KB_ = sparse ? L.KP : K;   // what a row counts in the byte figures
+        o.units = L.N; o.rows_per_unit = L.G; o.k = K; o.k_padded = sparse ? L.KAP + tg_r64(L.KB) : L.KP; o.resident_units = L.nres;
+        o.weight_bytes = esz * L.N * L.G * KB_;
         o.rows_min = INT32_MAX;
         for (int g = 0; g < TEAM_WGS; ++g) {
             int n = L.N - g * L.U;
@@ -740,7 +985,7 @@ static int teamg_plan_info(const wrnn_config *cfg, int rows_per_team, int fmt, i
             const int rows = n * L.G, res = (n < L.nres ? n : L.nres);
             if (rows < o.rows_min) o.rows_min = rows;
             if (rows > o.rows_max) o.rows_max = rows;
-            const int64_t rb = esz * res * L.G * K;
+            const int64_t rb = esz * res * L.G * KB_;
             if (rb > o.resident_bytes_wg) o.resident_bytes_wg = rb;
             o.resident_bytes_team += rb;
         }
@@ -753,6 +998,16 @@ static int teamg_plan_info(const wrnn_config *cfg, int rows_per_team, int fmt, i
     out->lds_budget_bytes = (lds_budget_bytes < 0 || lds_budget_bytes > TG_LDS_MAX - out->activation_bytes) ? TG_LDS_MAX - out->activation_bytes : lds_budget_bytes;
     out->mail_granules = p.mail_granules;
     return WRNN_OK;
+}
+
+static int teamg_plan_info(const wrnn_config *cfg, int rows_per_team, int fmt, int64_t lds_budget_bytes, wrnn_teamg_plan_info *out) {
+    return wrnn_teamg_plan_info_impl(cfg, rows_per_team, fmt, lds_budget_bytes, out, nullptr, nullptr);
+}
+
+extern "C" int wrnn_teamg_sparse_plan(const wrnn_config *cfg, int32_t rows_per_team, const int32_t nb_a[6], const int32_t nb_b[6], int64_t lds_budget_bytes,
+                                      wrnn_teamg_plan_info *out) {
+    if (!nb_a || !nb_b) return WRNN_ERR_INVALID;
+    return wrnn_teamg_plan_info_impl(cfg, rows_per_team, WRNN_WEIGHTS_F32, lds_budget_bytes, out, nb_a, nb_b);
 }
 
 extern "C" int wrnn_teamg_plan(const wrnn_config *cfg, int64_t lds_budget_bytes, wrnn_teamg_plan_info *out) {

@@ -306,12 +306,94 @@ __device__ __forceinline__ void tgb_dot8(const unsigned char *__restrict__ rp, i
         }
 }
 
+// tgb_dot on the block-sparse image, as tg_dots (loop_teamg.hip) is tg_dot's: rp = the unit's first image row, rows `rs` floats apart.  The
+// index and the weight float4 of a list entry are loaded once and used by the RB rows; UNR entries' loads are issued together, then each
+// entry's RB activation reads at the step its index names.  Per (row, lane) the chains are tgb_dot's without the steps of all-zero weights.
+template <int G, int RB>
+__device__ __forceinline__ void tgb_dots(const float *__restrict__ rp, int rs, const float4 *lds4, int xi, int xs4, int nA, int nK, int q, float (&sa)[G], float (&sb)[G]) {
+    constexpr int UNR = G == 1 ? 4 : 2;
+    asm volatile("" : "+v"(xi));
+    const float4 *xp = lds4 + xi;
+    const int idxf = (nK + 7) / 8 * 4;   // wrnn_teamg_sparse_idx_elems
+    const unsigned short *ip[G];
+    const float4 *wp[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        ip[g] = (const unsigned short *)(rp + (size_t)g * rs);
+        wp[g] = (const float4 *)(rp + (size_t)g * rs + idxf) + q;
+    }
+    float a0[RB][G], a1[RB][G];
+#pragma unroll
+    for (int r = 0; r < RB; ++r)
+#pragma unroll
+        for (int g = 0; g < G; ++g) a0[r][g] = a1[r][g] = 0.0f;
+    // every row has its own list: the activation reads are per (row of the batch, row of the unit)
+    auto mac = [&](const float4 (&w)[G], const int (&id)[G]) {
+#pragma unroll
+        for (int r = 0; r < RB; ++r) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const float4 x = xp[r * xs4 + id[g] * 16];
+                a0[r][g] = fmaf(w[g].x, x.x, a0[r][g]); a1[r][g] = fmaf(w[g].y, x.y, a1[r][g]);
+                a0[r][g] = fmaf(w[g].z, x.z, a0[r][g]); a1[r][g] = fmaf(w[g].w, x.w, a1[r][g]);
+            }
+        }
+    };
+    auto segment = [&](int j0, int j1) {
+        int j = j0;
+#pragma unroll 1
+        for (; j + UNR <= j1; j += UNR) {
+            int id[UNR][G];
+            float4 w[UNR][G];
+#pragma unroll
+            for (int u = 0; u < UNR; ++u)
+#pragma unroll
+                for (int g = 0; g < G; ++g) id[u][g] = ip[g][j + u];
+#pragma unroll
+            for (int u = 0; u < UNR; ++u)
+#pragma unroll
+                for (int g = 0; g < G; ++g) w[u][g] = wp[g][(j + u) * 16];
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) {
+                mac(w[u], id[u]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+#pragma unroll 1
+        for (; j < j1; ++j) {
+            int id[G];
+            float4 w[G];
+#pragma unroll
+            for (int g = 0; g < G; ++g) { id[g] = ip[g][j]; w[g] = wp[g][j * 16]; }
+            mac(w, id);
+        }
+    };
+    segment(0, nA);
+#pragma unroll
+    for (int r = 0; r < RB; ++r)
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const float v = row_sum(a0[r][g] + a1[r][g]);
+            sa[g] = (r == 0 || q == r) ? v : sa[g];
+            a0[r][g] = a1[r][g] = 0.0f;
+        }
+    segment(nA, nK);
+#pragma unroll
+    for (int r = 0; r < RB; ++r)
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const float v = row_sum(a0[r][g] + a1[r][g]);
+            sb[g] = (r == 0 || q == r) ? v : sb[g];
+        }
+}
+
 // G rows from row `row0` of a layer's slice at `base` (LDS or device memory), KP elements each, in the image's element type; `scale` is the
-// layer's (e4m3 only, a power of two)
+// layer's (e4m3 only, a power of two).  TgSparse: KP = the floats of an image row, nA / nK count list entries
 template <int G, int RB, typename WT>
 __device__ __forceinline__ void tgb_rows(const WT *base, int row0, int KP, float scale, const float4 *lds4, int xi, int xs4, int nA, int nK, int q, float (&sa)[G],
                                          float (&sb)[G]) {
-    if constexpr (sizeof(WT) == 4) tgb_dot<G, RB>((const float4 *)(base + (size_t)row0 * KP) + q, KP / 4, lds4, xi, xs4, nA, nK, q, sa, sb);
+    if constexpr (std::is_same<WT, TgSparse>::value) tgb_dots<G, RB>((const float *)base + (size_t)row0 * KP, KP, lds4, xi, xs4, nA, nK, q, sa, sb);
+    else if constexpr (sizeof(WT) == 4) tgb_dot<G, RB>((const float4 *)(base + (size_t)row0 * KP) + q, KP / 4, lds4, xi, xs4, nA, nK, q, sa, sb);
     else if constexpr (sizeof(WT) == 2) tgb_dot16<G, RB>((const TgHalf8 *)(base + (size_t)row0 * KP), KP / 8, row0, lds4, xi, xs4, nA, nK, q, sa, sb);
     else {
         tgb_dot8<G, RB>((const unsigned char *)(base + (size_t)row0 * KP), KP, row0, lds4, xi, xs4, nA, nK, q, sa, sb);
@@ -335,6 +417,7 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
     float *gsum = lds + ly.gs, *race = lds + ly.race;
     int *race_i = (int *)race;
     WT *wres = (WT *)(lds + ly.total);   // resident weights, in the image's element type
+    constexpr bool SP = std::is_same<WT, TgSparse>::value;   // the block-sparse image: a layer's steps are its list entries
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int qw = tid >> 4, q = tid & 15;   // not const: see the top of the step loop
@@ -400,7 +483,7 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
     // the own rows of W_I[:, 1:] . [m | a1] + b_I for the step whose conditioning is in parity `par` -> every row's mailbox, tagged `tag`
     auto xc_publish = [&](unsigned par, unsigned tag) {
         const WrnnTeamGLayer &L = ta.plan.L[WRNN_TEAMG_COND];
-        const int nown = owned(L), nK = L.KP / 64;
+        const int nown = owned(L), nK = SP ? tg_sp_nk(ta.plan, ta.sp, L) : L.KP / 64;
         const int xi = (ly.v.cb + par * CB) / 4 + q;
         for (int ul = qw; ul < nown; ul += 32) {
             float sa[1], sb[1];
@@ -413,7 +496,7 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
     // one GRU layer (get_gru_cell :273-279, gate rows [r; z; n]): h' of the own units of every row -> mailbox.  A row's input is
     // [input (KAP) | h (HP)] at xoff of its vectors.  By gate row or by unit as in loop_teamg.hip.
     auto gru_phase = [&](const WrnnTeamGLayer &L, int xoff, size_t obih, size_t obhh, unsigned region, unsigned epoch) {
-        const int nown = owned(L), nA = L.KAP / 64, nK = L.KP / 64;
+        const int nown = owned(L), nA = SP ? tg_sp_na(ta.plan, ta.sp, L) : L.KAP / 64, nK = SP ? tg_sp_nk(ta.plan, ta.sp, L) : L.KP / 64;
         const int xi = xoff / 4 + q;
         const float *bi = w + obih, *bh = w + obhh;
         auto cell = [&](int r, int j, const float (&gi)[3], const float (&gh)[3]) {
@@ -461,7 +544,7 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
     };
     // relu(W . x + b) of the own rows, every row -> mailbox
     auto fc_phase = [&](const WrnnTeamGLayer &L, int xoff, size_t ob, unsigned region, unsigned epoch) {
-        const int nown = owned(L), nK = L.KP / 64;
+        const int nown = owned(L), nK = SP ? tg_sp_nk(ta.plan, ta.sp, L) : L.KP / 64;
         const int xi = xoff / 4 + q;
         for (int ul = qw; ul < nown; ul += 32) {
             float sa[1], sb[1];
@@ -576,7 +659,7 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
             // ---- 5. logits = fc3(x) :223 of the own classes, and the sampler :225-237.  Lane r of a group: row r ----
             {
                 const WrnnTeamGLayer &L = ta.plan.L[WRNN_TEAMG_FC3];
-                const int nown = owned(L), nK = L.KP / 64;
+                const int nown = owned(L), nK = SP ? tg_sp_nk(ta.plan, ta.sp, L) : L.KP / 64;
                 const int xi = f3 / 4 + q;
                 const int qr = q < RB ? q : 0;
                 const int row = q < RB ? misc_i[MB_ROW + qr] : -1;
@@ -678,11 +761,14 @@ __global__ void __launch_bounds__(TG_THREADS) loop_teamg_batch_kernel(WrnnTeamGB
 }
 
 template <int RB>
-const void *tgb_fn(int esz) {
+const void *tgb_fn(int esz, bool sparse) {
+    if (sparse) return (const void *)loop_teamg_batch_kernel<RB, TgSparse>;
     return esz == 4 ? (const void *)loop_teamg_batch_kernel<RB, float>
                     : esz == 2 ? (const void *)loop_teamg_batch_kernel<RB, _Float16> : (const void *)loop_teamg_batch_kernel<RB, TgE4m3>;
 }
-const void *tgb_kernel_fn(int rb, int esz) { return rb == 2 ? tgb_fn<2>(esz) : rb == 4 ? tgb_fn<4>(esz) : rb == 8 ? tgb_fn<8>(esz) : nullptr; }
+const void *tgb_kernel_fn(int rb, int esz, bool sparse) {
+    return rb == 2 ? tgb_fn<2>(esz, sparse) : rb == 4 ? tgb_fn<4>(esz, sparse) : rb == 8 ? tgb_fn<8>(esz, sparse) : nullptr;
+}
 
 template <int RB, typename WT>
 void tgb_launch(const WrnnTeamGBatchArgs &a, size_t lds, hipStream_t s) {
@@ -690,16 +776,17 @@ void tgb_launch(const WrnnTeamGBatchArgs &a, size_t lds, hipStream_t s) {
 }
 template <int RB>
 void tgb_launch_fmt(const WrnnTeamGBatchArgs &a, size_t lds, hipStream_t s) {
-    if (a.plan.esz == 4) tgb_launch<RB, float>(a, lds, s);
+    if (a.sp.on) tgb_launch<RB, TgSparse>(a, lds, s);
+    else if (a.plan.esz == 4) tgb_launch<RB, float>(a, lds, s);
     else if (a.plan.esz == 2) tgb_launch<RB, _Float16>(a, lds, s);
     else tgb_launch<RB, TgE4m3>(a, lds, s);
 }
 
 }  // namespace
 
-hipError_t wrnn_teamg_batch_occupancy(const WrnnTeamGPlan &p, int rb, int *blocks_per_cu) {
+hipError_t wrnn_teamg_batch_occupancy(const WrnnTeamGPlan &p, int rb, int *blocks_per_cu, bool sparse) {
     const size_t lds = wrnn_teamg_lds_bytes(p);
-    const void *fn = tgb_kernel_fn(rb, p.esz);
+    const void *fn = tgb_kernel_fn(rb, p.esz, sparse);
     if (!fn) return hipErrorInvalidValue;
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
@@ -709,7 +796,7 @@ hipError_t wrnn_teamg_batch_occupancy(const WrnnTeamGPlan &p, int rb, int *block
 hipError_t wrnn_launch_loop_teamg_batch(const WrnnTeamGBatchArgs &a, int rb, hipStream_t s) {
     (void)hipGetLastError();
     const size_t lds = wrnn_teamg_lds_bytes(a.plan);
-    const void *fn = tgb_kernel_fn(rb, a.plan.esz);
+    const void *fn = tgb_kernel_fn(rb, a.plan.esz, a.sp.on != 0);
     if (!fn) return hipErrorInvalidValue;
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;

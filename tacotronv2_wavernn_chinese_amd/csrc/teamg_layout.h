@@ -2,6 +2,8 @@
 // per team in lock-step).  wrnn_teamg_make_plan sizes the resident weights by what these leave of 160 KiB.  The vectors are fp32 whatever
 // the element type of the weight image.
 #pragma once
+#include <type_traits>
+
 #include "team_common.h"
 #include "wrnn_internal.h"
 
@@ -119,6 +121,16 @@ __host__ __device__ inline int tg8_pos(int p, int row, int KAP, int KP) {
     if (rel < nq) return 64 * (k - (rel & 3)) + 16 * ((q + tg8_rot(row, KP)) & 15) + 4 * (rel & 3) + c;   // a quad
     if ((n & 2) && rel - nq < 2) return 64 * (k - (rel - nq)) + 8 * q + 4 * (rel - nq) + c;              // the pair
     return p;                                                                                             // the single last step
+}
+
+// The block-sparse fp32 image (WrnnTeamGSparse): the element is a float, the type only selects the instantiation whose
+// dot products walk a row's index list: in that instantiation segment A = list entries [0, nA), B = [nA, nK) of the
+// layer, where the dense instantiations have the steps of the padded row.
+struct TgSparse { float v; };
+// list entries of a layer's segment A, and of the whole row, in the sparse instantiations
+__device__ __forceinline__ int tg_sp_na(const WrnnTeamGPlan &plan, const WrnnTeamGSparse &sp, const WrnnTeamGLayer &L) { return sp.nbA[&L - plan.L]; }
+__device__ __forceinline__ int tg_sp_nk(const WrnnTeamGPlan &plan, const WrnnTeamGSparse &sp, const WrnnTeamGLayer &L) {
+    return sp.nbA[&L - plan.L] + sp.nbB[&L - plan.L];
 }
 
 // a granule of either kernel: the e4m3 instantiations are the ones short of scalar registers (team_common.h, st_granule_ws); the

@@ -115,6 +115,13 @@ struct wrnn_handle {
     bool teamg_img_ok = false;
     int32_t teamg_fmt = 0;        // WRNN_WEIGHTS_F32 / _F16 / _E4M3 (wrnn_teamg_set_weight_format): the element type of the image
     float teamg_scale[6] = {1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f};   // per-layer scales of the image last packed (wrnn_teamg_weight_scales)
+    bool teamg_sparse = false;    // wrnn_teamg_set_sparse: both kernels run the block-sparse fp32 image
+    bool teamg_sp_ok = false;     // the figures below are those of a packed sparse image (wrnn_teamg_sparse_info)
+    int32_t teamg_nb_a[6] = {}, teamg_nb_b[6] = {};       // blocks per image row and segment: the layer's longest list
+    int64_t teamg_sp_kept[6] = {}, teamg_sp_dense[6] = {};   // non-zero blocks, and blocks of the dense rows, per layer
+    int64_t teamg_sp_budget = -1; // the plan in force: budget and rows per team of the call that last ran sparse
+    int32_t teamg_sp_rows = 1;
+    void *teamg_sp_flags = nullptr;   // census scratch: one byte per block of the dense rows, then the per-layer counters
     int64_t teamg_budget = -1;    // wrnn_debug_teamg_lds_budget: LDS bytes for resident weights, < 0 = the default
     int last_batch_rows = 1;      // rows per team batch of the last generate call's loop kernel (wrnn_last_batch_rows)
     bool force_no_teams = false;  // wrnn_debug_force_no_teams: AUTO behaves as if residency had failed (tests of the slow-path warning)
@@ -297,6 +304,17 @@ struct WrnnTeamGPlan {
     int32_t mail_granules;     // per team
     int32_t esz;               // bytes of a weight element: 4, 2 or 1
 };
+// The block-sparse fp32 image: behind the plan in the kernels' arguments, so that nothing the dense instantiations read
+// moves.  A block = 64 consecutive elements of a padded row (one step of a 16-lane group's dot product).  An image row is
+// [nbA + nbB 16-bit block indices, padded to 16 bytes][nbA + nbB blocks of 64 floats]: segment A's kept blocks in ascending order, padded
+// to nbA with zero blocks of index 0, then segment B's (indices count from the row's start, so >= KAP / 64), padded to nbB with zero blocks
+// of index KAP / 64.  In a sparse plan L.KP is the FLOATS OF AN IMAGE ROW (wrnn_teamg_sparse_row_elems), everything else is the dense plan's.
+struct WrnnTeamGSparse {
+    int32_t on, pad_;
+    int32_t nbA[WRNN_TEAMG_LAYERS], nbB[WRNN_TEAMG_LAYERS];
+};
+inline int wrnn_teamg_sparse_idx_elems(int nb) { return (nb + 7) / 8 * 4; }                           // floats of the index list
+inline int wrnn_teamg_sparse_row_elems(int nb) { return wrnn_teamg_sparse_idx_elems(nb) + 64 * nb; }  // floats of an image row
 inline size_t wrnn_teamg_lds_bytes(const WrnnTeamGPlan &p) { return (size_t)p.act_floats * 4 + (size_t)p.res_elems * p.esz; }
 #define WRNN_TEAMG_THREADS 512
 struct WrnnTeamGArgs {
@@ -307,13 +325,17 @@ struct WrnnTeamGArgs {
     int32_t n_slots, ragged, n_teams, pad_;
     unsigned long long *mail;  // [n_teams][plan.mail_granules]
     unsigned *ctl;
+    WrnnTeamGSparse sp;        // last: the dense instantiations never read it
 };
 // pure host: ownership and placement for dims d with `budget` LDS bytes for resident weights (< 0 or too large: 160 KiB minus the
 // activation vectors); nullptr, or why the kernel cannot serve these dims.  rows_per_team = 1: loop_teamg.hip; 2, 4, 8: the lock-step
 // rows of loop_teamg_batch.hip, whose activation vectors (TgbLay, teamg_layout.h) and mailbox regions are counted that many times --
 // ownership and the weight image do not depend on it.  esz = bytes of a weight element (4: fp32, 2: fp16, 1: e4m3): only how many units fit;
 // every layer's scale is 1 (the caller sets the scales of the packed e4m3 image).
-const char *wrnn_teamg_make_plan(const WrnnDims &d, int64_t budget, WrnnTeamGPlan &p, int rows_per_team = 1, int esz = 4);
+// nb_a / nb_b (both or neither; esz = 4): the plan of the block-sparse image with that many blocks per row and segment of each layer;
+// a count above the dense row's is refused.
+const char *wrnn_teamg_make_plan(const WrnnDims &d, int64_t budget, WrnnTeamGPlan &p, int rows_per_team = 1, int esz = 4, const int32_t *nb_a = nullptr,
+                                 const int32_t *nb_b = nullptr);
 // bytes of the image allocation: the 32 slices and, behind them, one word per layer: the flag of the fp16 range check, or the bits of
 // the layer's largest |w| of the e4m3 pack
 inline size_t wrnn_teamg_img_bytes(const WrnnTeamGPlan &p) { return (size_t)32 * p.img_elems_wg * p.esz + WRNN_TEAMG_LAYERS * sizeof(int32_t); }
@@ -326,8 +348,18 @@ hipError_t wrnn_teamg_pack(const wrnn_handle *h, const WrnnTeamGPlan &p, void *i
 // clamped to e >= -126 so that the scale is a normal float (amax < 2^128 gives e <= 120, so 2^-e is normal too); 1 for amax = 0.
 float wrnn_teamg_e4m3_scale(float amax);
 extern const char *const wrnn_teamg_layer_names[WRNN_TEAMG_LAYERS];
-hipError_t wrnn_teamg_occupancy(const WrnnTeamGPlan &p, int *blocks_per_cu);
+// wrnn_teamg_plan_fmt's figures; with nb_a / nb_b those of the block-sparse plan (wrnn_teamg_sparse_plan)
+int wrnn_teamg_plan_info_impl(const wrnn_config *cfg, int rows_per_team, int fmt, int64_t lds_budget_bytes, wrnn_teamg_plan_info *out, const int32_t *nb_a,
+                              const int32_t *nb_b);
+hipError_t wrnn_teamg_occupancy(const WrnnTeamGPlan &p, int *blocks_per_cu, bool sparse = false);
 hipError_t wrnn_launch_loop_teamg(const WrnnTeamGArgs &a, hipStream_t s);
+// The sparse pack.  Census: per image row and segment, which blocks of the dense row hold a weight that does not compare equal to zero
+// (a NaN does not), into `flags` (wrnn_teamg_sparse_flag_bytes) -- one wait, then nb_a / nb_b = each layer's longest list, kept / dense =
+// its non-zero blocks and the blocks of its dense rows.  Compaction: the image of a plan made from those counts, no wait.
+size_t wrnn_teamg_sparse_flag_bytes(const WrnnDims &d);
+hipError_t wrnn_teamg_sparse_census(const wrnn_handle *h, void *flags, hipStream_t s, int32_t nb_a[WRNN_TEAMG_LAYERS], int32_t nb_b[WRNN_TEAMG_LAYERS],
+                                    int64_t kept[WRNN_TEAMG_LAYERS], int64_t dense[WRNN_TEAMG_LAYERS]);
+hipError_t wrnn_teamg_sparse_pack(const wrnn_handle *h, const WrnnTeamGPlan &p, const int32_t *nb_a, const int32_t *nb_b, const void *flags, void *img, hipStream_t s);
 
 // The same team kernel with RB = 2, 4 or 8 rows per team in lock-step (loop_teamg_batch.hip).  plan = wrnn_teamg_make_plan(.., RB).
 #define WRNN_TEAMG_BATCH_MAX_ROWS 8
@@ -341,9 +373,10 @@ struct WrnnTeamGBatchArgs {
     int32_t n_teams, pad_;
     unsigned long long *mail;  // [n_teams][plan.mail_granules], row r of a team's batch at r * (plan.mail_granules / RB)
     unsigned *ctl;
+    WrnnTeamGSparse sp;        // last, as in WrnnTeamGArgs
 };
 inline int wrnn_teamg_batch_inst(int rpb) { return rpb <= 2 ? 2 : (rpb <= 4 ? 4 : 8); }   // the instantiation that runs rpb rows
-hipError_t wrnn_teamg_batch_occupancy(const WrnnTeamGPlan &p, int rb, int *blocks_per_cu);
+hipError_t wrnn_teamg_batch_occupancy(const WrnnTeamGPlan &p, int rb, int *blocks_per_cu, bool sparse = false);
 hipError_t wrnn_launch_loop_teamg_batch(const WrnnTeamGBatchArgs &a, int rb, hipStream_t s);
 
 // Persistent team kernels of the two GRU recurrences of wrnn_train_step (train_team.hip)

@@ -7,7 +7,7 @@ handed to ``model.generate``; the output file name pattern is the reference's (:
 
 Deliberate differences: the reference hard-overrides ``batched = False`` and
 ``device = cpu`` after parsing its flags (:76-77, :93); here ``--batched`` is honoured and the model
-runs on the MI355X.  Extensions: ``--kernel NAME``, ``--teamg-weights f32|f16|e4m3``, ``--target auto|per_xcd``, ``--noise reference [--seed N]``, ``--stream-frames N`` (streaming generation)
+runs on the MI355X.  Extensions: ``--kernel NAME``, ``--teamg-weights f32|f16|e4m3``, ``--teamg-sparse``, ``--target auto|per_xcd``, ``--noise reference [--seed N]``, ``--stream-frames N`` (streaming generation)
 (the reference's own noise stream: ``vocoder.reference_noise``).
 
 The ``.wav`` branch (:17-20) does what the reference's intends: ``load_wav``, the input saved as ``__{idx}__{k}k_steps_target.wav`` (the
@@ -197,6 +197,9 @@ def build_parser() -> argparse.ArgumentParser:
                         help="extension: element type of the weight image of --kernel teamg / teamg_batch ('f16': the loop matrices as IEEE "
                              "binary16, half the bytes streamed per step; 'e4m3': as 8-bit OCP e4m3 with one power-of-two scale per layer, a "
                              "quarter of the bytes; activations and accumulators stay fp32); ignored by the other kernels")
+    parser.add_argument('--teamg-sparse', dest='teamg_sparse', action='store_true',
+                        help='extension: --kernel teamg / teamg_batch leave out every block of 64 weights of a row that is all zero (a model '
+                             'pruned by wavernn_train.py --sparse-density); same outputs as without; fp32 weights only; ignored by the other kernels')
     parser.set_defaults(batched=None)
     return parser
 
@@ -235,6 +238,7 @@ def main(argv=None):
     from . import _cabi
     model.kernel = _cabi.KERNEL_IDS[args.kernel]
     model.teamg_weights = args.teamg_weights
+    model.teamg_sparse = args.teamg_sparse
     # wavernn_gen.py:112-117: `--voc_weights`, else the latest checkpoint of the training run
     # (Paths.voc_latest_weights = <base>/logs_wavernn/checkpoints/latest_weights.pyt, wavernn/utils/paths.py:11-12; <base> is
     # the directory the script is started from here).  The reference then dies in torch.load when that file is absent; no

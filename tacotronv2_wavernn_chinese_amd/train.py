@@ -122,7 +122,7 @@ def collate_windows(batch: Sequence[Tuple[np.ndarray, np.ndarray]], *, mode: str
 
 def voc_train_loop(paths: VocPaths, model, loss_func: Optional[Callable], optimizer, train_set: Iterable, test_set, lr: float,
                    total_steps: int, *, clip_grad_norm: Optional[float] = 4, checkpoint_every: int = 1000,
-                   at_checkpoint: Optional[Callable] = None, report: Optional[Callable[[str], None]] = None):
+                   at_checkpoint: Optional[Callable] = None, report: Optional[Callable[[str], None]] = None, sparsify=None):
     """``voc_train_loop`` (wavernn_train.py:88-151) on the MI355X.
 
     ``loss_func=None``: each iteration is ``model.training_loss(x, m, y)`` (forward + loss + backward of the loop layers fused
@@ -135,6 +135,9 @@ def voc_train_loop(paths: VocPaths, model, loss_func: Optional[Callable], optimi
     iteration has run on whatever the step produced -- nothing corrupt reaches disk (no checkpoint is written behind a raised error), but the
     in-memory parameters and Adam moments are then poisoned: restore the latest checkpoint (``restore_checkpoint``) before continuing, do
     not just retry the iteration.
+    ``sparsify``: a ``sparsity.SparsitySchedule``.  After ``optimizer.step()`` of a step at which the schedule is due the block masks are
+    recomputed (``sparsity.block_masks`` at the schedule's density, intersected with the masks so far: a pruned block stays pruned), and
+    the masks are re-applied after every step, so the pruned blocks are exactly zero in every checkpoint.  Training itself stays dense.
     """
     device = next(model.parameters()).device
     for g in optimizer.param_groups:
@@ -145,6 +148,9 @@ def voc_train_loop(paths: VocPaths, model, loss_func: Optional[Callable], optimi
     epochs = (total_steps - model.get_step()) // per_epoch + 1
     params = [p for p in model.parameters() if p.requires_grad]
     losses = []
+    masks = None
+    if sparsify is not None:
+        from .sparsity import apply_masks_, block_masks
     model.train()
     # Device-side errors of the training kernels are asked for once per iteration (at the loss.item() below, where the host waits anyway)
     # instead of inside every call, and the NaN message of the clipping waits for the same point: the host queues the upsample network's
@@ -171,6 +177,11 @@ def voc_train_loop(paths: VocPaths, model, loss_func: Optional[Callable], optimi
                 loss.backward()
                 norm = torch.nn.utils.clip_grad_norm_(params, clip_grad_norm) if clip_grad_norm is not None else None
                 optimizer.step()
+                if sparsify is not None:
+                    if sparsify.due(model.get_step()):
+                        masks = block_masks(model, sparsify.density(model.get_step()), sparsify.layers, keep=masks)
+                    if masks is not None:
+                        apply_masks_(model, masks)
                 value = loss.item()                  # the one host sync of an iteration (the reference has it too, :129)
                 if hasattr(model, 'training_status'):
                     model.training_status()
@@ -301,6 +312,14 @@ def build_parser():
     parser.add_argument('--train-precision', dest='train_precision', choices=('f32', 'bf16'), default='f32',
                         help="precision of the loop layers' batched GEMMs: f32 (default), or bf16 operands on the matrix cores with fp32 "
                              'accumulators (WaveRNN.train_precision; parameters, recurrences and losses stay fp32)')
+    parser.add_argument('--sparse-density', dest='sparse_density', type=float, metavar='D', default=None,
+                        help='extension: prune rnn1, rnn2, fc1 and fc2 while training, in blocks of 64 weights of a row, down to the share D '
+                             'of blocks per row (sparsity.SparsitySchedule; needs --sparse-start and --sparse-end).  The checkpoints run on '
+                             'wavernn_gen.py --kernel teamg --teamg-sparse')
+    parser.add_argument('--sparse-start', dest='sparse_start', type=int, metavar='S', default=None, help='step at which pruning begins')
+    parser.add_argument('--sparse-end', dest='sparse_end', type=int, metavar='E', default=None, help='step at which the density reaches D')
+    parser.add_argument('--sparse-every', dest='sparse_every', type=int, metavar='N', default=100,
+                        help='recompute the masks every N steps between S and E (default 100)')
     parser.add_argument('--total_steps', type=int, help='override hp.voc_total_steps')
     parser.add_argument('--score_at_checkpoint', action='store_true',
                         help='extension: at every checkpoint, score each generated held-out clip against its target on the device '
@@ -312,6 +331,18 @@ def build_parser():
     return parser
 
 
+def sparsity_schedule(args):
+    """The ``sparsity.SparsitySchedule`` of the --sparse-* arguments, or ``None`` without --sparse-density (``ValueError`` for half a set)."""
+    if args.sparse_density is None:
+        if args.sparse_start is not None or args.sparse_end is not None:
+            raise ValueError('--sparse-start / --sparse-end need --sparse-density')
+        return None
+    if args.sparse_start is None or args.sparse_end is None:
+        raise ValueError('--sparse-density needs --sparse-start and --sparse-end')
+    from .sparsity import SparsitySchedule
+    return SparsitySchedule(args.sparse_density, args.sparse_start, args.sparse_end, args.sparse_every)
+
+
 def main(argv=None):
     """``python wavernn_train.py`` (wavernn_train.py:20-86) on the MI355X."""
     import torch.nn.functional as F
@@ -320,6 +351,7 @@ def main(argv=None):
     from .hparams import hparams as hp
     args = build_parser().parse_args(argv)
     conditioning = condition_arguments(args)
+    sparsify = sparsity_schedule(args)
     hp.configure(args.hp_file)
     if not args.synthetic and not args.wav_dir:
         from .dataset import check_saved_features
@@ -376,7 +408,7 @@ def main(argv=None):
 
     voc_train_loop(paths, model, loss_func, optimizer, loader, test, hp.voc_lr, total,
                    clip_grad_norm=hp.voc_clip_grad_norm, checkpoint_every=hp.voc_checkpoint_every, at_checkpoint=at_checkpoint,
-                   report=lambda s: print('\r' + s, end='', flush=True))
+                   report=lambda s: print('\r' + s, end='', flush=True), sparsify=sparsify)
     print('\nTraining Complete.')
 
 

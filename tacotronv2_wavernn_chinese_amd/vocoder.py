@@ -283,6 +283,7 @@ class WaveRNN(nn.Module):
         # knobs that are not part of the reference signature
         self.kernel = _cabi.KERNEL_AUTO
         self._teamg_weights = 'f32'       # see the property teamg_weights
+        self._teamg_sparse = False        # see the property teamg_sparse
         self._train_precision = 'f32'     # see the property train_precision
         # True: every training call (training_loss, forward / backward in train() mode) waits for its kernels and raises on a device-side
         # error (a busy GPU, a timed-out team kernel) -- safe, but the host cannot queue the rest of the iteration (the upsample network's
@@ -342,6 +343,25 @@ class WaveRNN(nn.Module):
             self._native.set_teamg_weights(fmt)
 
     @property
+    def teamg_sparse(self) -> bool:
+        """``True``: ``kernel='teamg'`` / ``'teamg_batch'`` run the block-sparse fp32 weight image.  A block is 64 consecutive elements of
+        one padded image row (``sparsity.block_layout``); the pack reads the pattern off the weights and leaves out every block whose
+        weights are all zero, so a model pruned in such blocks (``sparsity.block_masks``, ``voc_train_loop(sparsify=...)``) streams and
+        multiplies only what it kept.  The outputs equal the dense fp32 kernel's on the same model number for number, for any model
+        (``native().teamg_sparse_info()`` says what was kept).  Default ``False``; the setting belongs to the model like ``teamg_weights``
+        and no other kernel reads it (``last_timing['teamg_sparse']``).  With ``teamg_weights`` other than ``'f32'`` the call that packs
+        raises ``WrnnError`` (WRNN_ERR_UNSUPPORTED)."""
+        return self._teamg_sparse
+
+    @teamg_sparse.setter
+    def teamg_sparse(self, on: bool):
+        if not isinstance(on, bool):
+            raise ValueError(f'teamg_sparse must be a bool, not {on!r}')
+        self._teamg_sparse = on
+        if self._native is not None:
+            self._native.set_teamg_sparse(on)
+
+    @property
     def train_precision(self) -> str:
         """Precision of the batched GEMMs of training (``forward`` in ``train()`` mode, ``training_loss``, both autograd functions):
         ``'f32'`` (default) or ``'bf16'``.  With ``'bf16'`` every operand of those GEMMs -- forward, input gradients, weight gradients --
@@ -372,6 +392,7 @@ class WaveRNN(nn.Module):
                 self._native.close()
             self._native = _cabi.NativeVocoder(device=dev, **self._ctor)
             self._native.set_teamg_weights(self._teamg_weights)
+            self._native.set_teamg_sparse(self._teamg_sparse)
             self._native.set_train_precision(self._train_precision)
             self._native_key = None
         return self._native
@@ -385,6 +406,7 @@ class WaveRNN(nn.Module):
                 self._native.close()
             self._native = _cabi.NativeVocoder(device=dev, **self._ctor)
             self._native.set_teamg_weights(self._teamg_weights)
+            self._native.set_teamg_sparse(self._teamg_sparse)
             self._native.set_train_precision(self._train_precision)
             self._native_key = None
         if self._native_key != key:

@@ -20,7 +20,13 @@ plans admit: two handles of one model, the formats alternating call by call.
     python tools/any_dims_batch_latency.py --weights e4m3 [--out FILE]
 
 adds a third handle with the e4m3 image: fp32, fp16 and e4m3 alternate call by call in one session; the verdict of a shape is e4m3
-against fp16 in that session, the time ratio next to the ratio of the streamed bytes."""
+against fp16 in that session, the time ratio next to the ratio of the streamed bytes.
+
+    python tools/any_dims_batch_latency.py --sparse 0.5,0.25,0.125,0.0625 [--sets CDA] [--out FILE]
+
+times the block-sparse image (`teamg_sparse = True`) on WRNN_KERNEL_TEAMG_BATCH, 8 x n_teams rows at the most rows per team the plan admits (up to 8):
+tools/any_dims_latency.py's `sparse_session` (dense fp32, fp16, e4m3 and the pruned copies alternating call by call, kept / total blocks
+and streamed bytes from `teamg_sparse_info`)."""
 import argparse
 import os
 import sys
@@ -115,11 +121,17 @@ def main():
     ap.add_argument('--out', default=None)
     ap.add_argument('--weights', choices=('f32', 'f16', 'e4m3'), default='f32',
                     help="f16: time the fp32 image against the fp16 image of TEAMG_BATCH instead; e4m3: fp32, fp16 and e4m3 alternating")
+    ap.add_argument('--sparse', metavar='DENSITY[,DENSITY..]', default=None,
+                    help='time the block-sparse image at these densities next to the dense fp32, fp16 and e4m3 images, 8 rows per team')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise RuntimeError('any_dims_batch_latency.py measures on an MI355X: no GPU, no figures')
     if args.reps < 5:
         raise ValueError('at least 5 timed calls per kernel')
+    if args.sparse is not None:
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        from any_dims_latency import sparse_session
+        return sparse_session(args, kernel='teamg_batch', rows=0, batch_rows=8)
     from tacotronv2_wavernn_chinese_amd import _cabi
     from tacotronv2_wavernn_chinese_amd.synth import make_mels, make_state_dict
     from tacotronv2_wavernn_chinese_amd.vocoder import WaveRNN

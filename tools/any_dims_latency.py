@@ -19,7 +19,14 @@ larger spread.
 
 adds a third handle with the e4m3 image (`teamg_weights='e4m3'`): fp32, fp16 and e4m3 alternate call by call in one session, same
 protocol; the verdict of a shape is e4m3 against fp16 in that session (faster by more than the spread, equal, or slower), with the time
-ratio next to the ratio of the streamed bytes."""
+ratio next to the ratio of the streamed bytes.
+
+    python tools/any_dims_latency.py --sparse 0.5,0.25,0.125,0.0625 [--sets CDA] [--lib build_variants/libX.so] [--out FILE]
+
+times the block-sparse image (`teamg_sparse = True`): per density a copy of the synthetic model pruned with
+`sparsity.block_masks` on rnn1, rnn2, fc1 and fc2, next to the dense model with the fp32, fp16 and e4m3 images -- all configurations
+alternate call by call in one session, one row per team; kept / total blocks and the bytes streamed per step come from
+`teamg_sparse_info`.  The verdict of a set is each sparse configuration against dense fp32.  `--lib` times another build of the library."""
 import argparse
 import os
 import sys
@@ -102,6 +109,90 @@ def weights_session(args):
             f.write(text)
 
 
+def sparse_session(args, kernel='teamg', rows=1, batch_rows=0):
+    """Dense fp32 / fp16 / e4m3 and the sparse image at every density of --sparse, alternating call by call; `rows` rows on `kernel`."""
+    from tacotronv2_wavernn_chinese_amd import _cabi
+    from tacotronv2_wavernn_chinese_amd.sparsity import apply_masks_, block_masks
+    from tacotronv2_wavernn_chinese_amd.synth import make_mels, make_state_dict
+    from tacotronv2_wavernn_chinese_amd.vocoder import WaveRNN
+    from tests.teamg_cases import DIM_SETS
+    densities = [float(v) for v in args.sparse.split(',')]
+    lines = [f'block-sparse weight image of the any-dims team kernels ({kernel}), {torch.cuda.get_device_name(0)}, torch {torch.__version__}', '',
+             f'loop_ms of one call (HIP events around the loop kernel), {args.warmup} warm-up + {args.reps} timed calls per configuration, alternating; RAW, Philox noise',
+             'us/step = median loop time / steps per row; spread = (max - min) of the timed calls per step; streamed = weight bytes a team reads per step;',
+             'sparse D = rnn1, rnn2, fc1, fc2 pruned to the share D of blocks per row (sparsity.block_masks), fp32 values, teamg_sparse on', '']
+    verdicts = []
+    for name in args.sets:
+        dims = DIM_SETS[name]
+        sd = make_state_dict(7, 'RAW', 'peaky', **dims)
+        configs = [('f32', 'f32', None), ('f16', 'f16', None), ('e4m3', 'e4m3', None)] + [(f'sparse {d:g}', 'f32', d) for d in densities]
+        models = {}
+        for tag, w, density in configs:
+            m = WaveRNN(**dims, mode='RAW')
+            m.verbose = False
+            m.teamg_weights = w
+            m.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in sd.items()})
+            if density is not None:
+                apply_masks_(m, block_masks(m, density))
+                m.teamg_sparse = True
+            m.to('cuda:0')
+            models[tag] = m
+        teams = models['f32'].native().team_info()[1]
+        B = rows if rows > 0 else 8 * teams
+        R = batch_rows   # the most rows per team the plan admits for these dims, up to batch_rows
+        while R > 1:
+            try:
+                _cabi.teamg_batch_plan(R, -1, mode='RAW', **dims)
+                break
+            except _cabi.WrnnError:
+                R //= 2
+        T = FRAMES[name]
+        steps = T * dims['hop_length']
+        lines.append(f'set {name}: rnn {dims["rnn_dims"]}, fc {dims["fc_dims"]}, hop {dims["hop_length"]}; {B} rows x {steps} steps on {teams} teams'
+                     + (f', {R} rows per team' if batch_rows else ''))
+        mels = torch.from_numpy(make_mels(5, B, T, feat_dims=dims['feat_dims'])).cuda()
+        kw = dict(batch_rows=R) if batch_rows else {}
+        ms = {tag: [] for tag, _, _ in configs}
+        for rep in range(args.warmup + args.reps):
+            for tag, w, density in configs:
+                m = models[tag]
+                m.generate_raw(mels, False, 11000, 550, noise_mode='philox', seed=99, kernel=kernel, **kw)
+                lt = m.last_timing
+                assert lt['kernel'] == _cabi.KERNEL_IDS[kernel] and lt['steps'] == steps and lt['teamg_weights'] == w and lt['teamg_sparse'] is (density is not None)
+                assert not batch_rows or lt['batch_rows'] == R
+                if rep >= args.warmup:
+                    ms[tag].append(float(lt['loop_ms']))
+        us = {k: float(np.median(v)) * 1e3 / steps for k, v in ms.items()}
+        spread = {k: (max(v) - min(v)) * 1e3 / steps for k, v in ms.items()}
+        for tag, w, density in configs:
+            if density is None:
+                p = _cabi.teamg_plan_fmt(max(R, 1), w, -1, mode='RAW', **dims)
+                what = f'streamed {p["streamed_bytes_step"] / 1e6:6.2f} MB per step, LDS {p["lds_bytes"]}'
+            else:
+                info = models[tag].native().teamg_sparse_info()
+                p = info['plan']
+                what = (f'streamed {p["streamed_bytes_step"] / 1e6:6.2f} MB per step, LDS {p["lds_bytes"]}, kept {info["kept"]} of {info["dense"]} blocks, image '
+                        f'{sum(L["weight_bytes"] for L in p["layers"].values()) / 1e6:.2f} MB')
+            lines.append(f'  {tag:14s} {us[tag]:8.2f} us/step  spread {spread[tag]:.2f}  {what}   calls (ms): ' + ' '.join(f'{v:.3f}' for v in ms[tag]))
+        for tag, w, density in configs:
+            if density is None:
+                continue
+            margin = max(spread[tag], spread['f32'])
+            d = us[tag] - us['f32']
+            verdicts.append(f'set {name} {tag}: time / dense fp32 {us[tag] / us["f32"]:.3f}, margin {margin:.2f} us -> '
+                            f'{"sparse FASTER than dense fp32 beyond the spread" if -d > margin else "sparse SLOWER than dense fp32 beyond the spread" if d > margin else "equal within the spread"}'
+                            f' (fp16 {us["f16"]:.2f}, e4m3 {us["e4m3"]:.2f} us/step)')
+        lines.append('')
+        del models
+        torch.cuda.empty_cache()
+    lines += verdicts
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=5)
@@ -109,12 +200,20 @@ def main():
     ap.add_argument('--out', default=None)
     ap.add_argument('--weights', choices=('f32', 'f16', 'e4m3'), default='f32',
                     help="f16: time the fp32 image against the fp16 image of TEAMG instead; e4m3: fp32, fp16 and e4m3 alternating")
+    ap.add_argument('--sparse', metavar='DENSITY[,DENSITY..]', default=None,
+                    help='time the block-sparse image at these densities next to the dense fp32, fp16 and e4m3 images (sparse_session)')
+    ap.add_argument('--sets', default='CDA', help='with --sparse: the dim sets of tests/teamg_cases.py to time')
+    ap.add_argument('--lib', default=None, help='another build of libwavernn_amd.so to time')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise RuntimeError('any_dims_latency.py measures on an MI355X: no GPU, no figures')
     if args.reps < 5:
         raise ValueError('at least 5 timed calls per kernel')
     from tacotronv2_wavernn_chinese_amd import _cabi
+    if args.lib:
+        _cabi.LIB_PATH = os.path.abspath(args.lib)
+    if args.sparse is not None:
+        return sparse_session(args)
     from tacotronv2_wavernn_chinese_amd.synth import make_mels, make_state_dict
     from tacotronv2_wavernn_chinese_amd.vocoder import WaveRNN
     from tests.teamg_cases import DIM_SETS
