@@ -880,6 +880,81 @@ int wrnn_score_tables(const wrnn_score_handle *h, int32_t r, float *window, floa
 const char *wrnn_score_last_error(const wrnn_score_handle *h);
 void wrnn_score_destroy(wrnn_score_handle *h);
 
+/* ---- pitch (new entry points in ABI 9 again, and one new struct; nothing existing changes): a YIN F0 track (de Cheveigne & Kawahara
+ * 2002) of float32 clips, and the F0 / voicing error scores of a TEST clip against a TARGET clip of the same length.  Every operation
+ * after reading the float32 samples is float64: a threshold decision on a float32 difference function flips too easily.
+ *   tau_min = ceil(sample_rate / fmax),  tau_max = floor(sample_rate / fmin)
+ * Frames.  A clip of n >= 1 samples has T = 1 + n / hop frames (the mel front end's count at the same hop); frame t is the frame_length
+ * samples from t hop - frame_length / 2, samples outside the clip read as zeros.  With x the frame and W = window:
+ *   d(tau) = sum_{j < W} (x[j] - x[j + tau])^2                        tau = 0 .. tau_max + 1, the direct form
+ *   d'(0) = 1,  d'(tau) = d(tau) tau / sum_{k = 1 .. tau} d(k)        1 wherever that sum is exactly 0 (silence, DC)
+ *   candidate: the first tau in [tau_min, tau_max] with d'(tau) < threshold, then tau + 1 while tau + 1 <= tau_max and
+ *              d'(tau + 1) < d'(tau) (both strict); none: no candidate
+ *   voiced  <=>  a candidate exists and sqrt(mean_{j < W} x[j]^2) >= silence_rms
+ *   a, b, c = d'(tau - 1), d'(tau), d'(tau + 1);  den = a - 2 b + c;  off = 0.5 (a - c) / den if den > 0 else 0, clamped to [-0.5, 0.5]
+ *   f0 = sample_rate / (tau + off)                                     float32, rounded from float64 once; 0: unvoiced
+ *   aperiodicity = min_{tau_min <= tau <= tau_max} d'(tau)             float32, rounded once
+ * Pair scores over the tracks ft (target), fs (test), float64 from the float32 f0; V: the frames voiced in both clips:
+ *   f0_rmse_cents = sqrt(mean_V (1200 log2(fs / ft))^2)
+ *   gpe = #{t in V: |fs / ft - 1| > gpe_ratio} / #V                    gross pitch error
+ *   vde = #{t: voiced_t != voiced_s} / T                               voicing decision error
+ *   ffe = (#gpe frames + #vde frames) / T                              F0 frame error
+ *   f0_corr = Pearson correlation of log2 f0 over V, in two passes: cov / sqrt(var_t var_s); 0 when #V < 2 or a variance is 0
+ *   then the voiced frames of the target, of the test, and of both.
+ * f0_rmse_cents, gpe and f0_corr are 0 when V is empty; a clip with n = 0 has no frames and an all-zero row.  The sums are taken by a
+ * second launch in a fixed order (no floating-point atomics): two calls give the same bits, a clip of a ragged batch equals the call on
+ * it alone bit for bit, and both clips of a pair run the same instructions, so identical clips (and two silences) score exactly 0 on
+ * the first four fields. */
+#define WRNN_PITCH_FIELDS 8        /* doubles per pair in summary_dev, in this order: */
+#define WRNN_PITCH_F0_RMSE_CENTS 0
+#define WRNN_PITCH_GPE 1
+#define WRNN_PITCH_VDE 2
+#define WRNN_PITCH_FFE 3
+#define WRNN_PITCH_F0_CORR 4
+#define WRNN_PITCH_VOICED_TARGET 5
+#define WRNN_PITCH_VOICED_TEST 6
+#define WRNN_PITCH_VOICED_BOTH 7
+typedef struct wrnn_pitch_handle wrnn_pitch_handle;
+typedef struct wrnn_pitch_config {
+    uint32_t struct_size;    /* the size of this struct */
+    int32_t sample_rate;     /* hp.sample_rate */
+    int32_t hop;             /* hp.hop_length */
+    int32_t frame_length;    /* 2048; one of 512, 1024, 2048, 4096 */
+    int32_t window;          /* 1024: W, with window + tau_max + 1 <= frame_length */
+    int32_t device;
+    double fmin;             /* 60 */
+    double fmax;             /* 600 */
+    double threshold;        /* 0.15, inside (0, 1) */
+    double silence_rms;      /* 1e-4 */
+    double gpe_ratio;        /* 0.2 */
+} wrnn_pitch_config;
+/* Host only, touches no device.  A refused handle is still returned, for its error text and the destroy entry.  WRNN_ERR_INVALID: a
+ * struct_size other than the struct's own size, sample_rate or hop < 1, fmin or fmax not finite or fmin >= fmax, tau_min < 1,
+ * tau_min > tau_max, threshold outside (0, 1), silence_rms < 0 (or not finite), gpe_ratio <= 0 (or not finite), window < 1.
+ * WRNN_ERR_UNSUPPORTED: frame_length outside {512, 1024, 2048, 4096}, window + tau_max + 1 > frame_length. */
+int wrnn_pitch_create(const wrnn_pitch_config *cfg, wrnn_pitch_handle **out);
+/* Host only: the frames of a clip of n samples, 1 + n / hop, and 0 for n = 0 (such a clip has no frames).  WRNN_ERR_INVALID (< 0) for
+ * n < 0, n >= 2^31 or a refused handle. */
+int64_t wrnn_pitch_frames(const wrnn_pitch_handle *h, int64_t n);
+/* Host only: the lag range.  Either pointer may be NULL. */
+int wrnn_pitch_lags(const wrnn_pitch_handle *h, int32_t *tau_min, int32_t *tau_max);
+/* wav_dev: B float32 clips, row stride n_max >= 1; n_dev: B int32 on the device, the clips' own lengths (ragged; a value above n_max is
+ * read as n_max, one below 1 as an empty clip).  f0_dev, aperiodicity_dev: (B, frames_stride) float32, frames_stride at least the
+ * frames entry's value for n_max; aperiodicity_dev may be NULL.  Entries at or past a clip's own frame count are written as 0.  One
+ * launch, asynchronous on `stream`; the entry owns no scratch. */
+int wrnn_pitch_track(wrnn_pitch_handle *h, const float *wav_dev, int64_t n_max, const int32_t *n_dev, int32_t B, float *f0_dev,
+                     float *aperiodicity_dev, int64_t frames_stride, void *stream);
+/* target_dev, test_dev, n_dev: as above, pair by pair.  summary_dev (B, WRNN_PITCH_FIELDS) float64.  frames_dev: NULL (the per-frame
+ * values go to the handle's scratch), or (B, frames_stride) float32; with F the frames entry's value for n_max a row holds
+ * f0_t[F] | ap_t[F] | f0_s[F] | ap_s[F] | cents[F] (1200 log2(fs / ft) on the frames of V, 0 elsewhere) and frames_stride >= 5 F.
+ * Three launches (the two tracks in one, the per-frame pair values, the summaries), asynchronous on `stream`.  The handle owns the
+ * scratch and grows it when a call needs more -- the one case in which a call waits for `stream` -- so calls on ONE handle must be
+ * ordered by the caller. */
+int wrnn_pitch_score(wrnn_pitch_handle *h, const float *target_dev, const float *test_dev, int64_t n_max, const int32_t *n_dev, int32_t B,
+                     double *summary_dev, float *frames_dev, int64_t frames_stride, void *stream);
+const char *wrnn_pitch_last_error(const wrnn_pitch_handle *h);
+void wrnn_pitch_destroy(wrnn_pitch_handle *h);
+
 #ifdef __cplusplus
 }
 #endif

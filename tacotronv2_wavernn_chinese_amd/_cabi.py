@@ -49,7 +49,9 @@ EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wr
                     'wrnn_griffin_create', 'wrnn_griffin_samples', 'wrnn_griffin_tables', 'wrnn_griffin_lim', 'wrnn_deemphasis',
                     'wrnn_griffin_last_error', 'wrnn_griffin_destroy',
                     'wrnn_score_create', 'wrnn_score_frames', 'wrnn_score', 'wrnn_score_tables', 'wrnn_score_last_error',
-                    'wrnn_score_destroy')
+                    'wrnn_score_destroy',
+                    'wrnn_pitch_create', 'wrnn_pitch_frames', 'wrnn_pitch_lags', 'wrnn_pitch_track', 'wrnn_pitch_score',
+                    'wrnn_pitch_last_error', 'wrnn_pitch_destroy')
 
 
 def epilogue_tables(n_classes: int, overlap: int, hop: int):
@@ -158,6 +160,32 @@ class ScoreConfig(C.Structure):
         cols = list(zip(*(res + pad)))
         super().__init__(C.sizeof(ScoreConfig), len(res), (C.c_int32 * 4)(*cols[0]), (C.c_int32 * 4)(*cols[1]), (C.c_int32 * 4)(*cols[2]),
                          float(mag_floor), int(mcd_order))
+
+
+PITCH_FIELDS = 8   # WRNN_PITCH_FIELDS
+# the order of the doubles in wrnn_pitch_score's summary: WRNN_PITCH_F0_RMSE_CENTS .. WRNN_PITCH_VOICED_BOTH
+PITCH_FIELD_NAMES = ('f0_rmse_cents', 'gpe', 'vde', 'ffe', 'f0_corr', 'voiced_target', 'voiced_test', 'voiced_both')
+PITCH_FRAME_NAMES = ('f0_target', 'aperiodicity_target', 'f0_test', 'aperiodicity_test', 'cents')   # a row of frames_dev
+PITCH_DEFAULTS = dict(sample_rate=22050, hop=275, frame_length=2048, window=1024, fmin=60.0, fmax=600.0, threshold=0.15, silence_rms=1e-4,
+                      gpe_ratio=0.2)
+
+
+class PitchConfig(C.Structure):
+    """``wrnn_pitch_config``; a fresh one holds the defaults."""
+    _fields_ = [('struct_size', C.c_uint32), ('sample_rate', C.c_int32), ('hop', C.c_int32), ('frame_length', C.c_int32), ('window', C.c_int32),
+                ('device', C.c_int32), ('fmin', C.c_double), ('fmax', C.c_double), ('threshold', C.c_double), ('silence_rms', C.c_double),
+                ('gpe_ratio', C.c_double)]
+
+    def __init__(self, device=0, **settings):
+        unknown = set(settings) - set(PITCH_DEFAULTS)
+        if unknown:
+            raise TypeError(f'unknown pitch settings {sorted(unknown)}')
+        v = dict(PITCH_DEFAULTS, **settings)
+        ints = [int(v[k]) for k in ('sample_rate', 'hop', 'frame_length', 'window')]
+        if any(not -2 ** 31 <= i < 2 ** 31 for i in ints):
+            raise ValueError(f'WRNN_ERR_INVALID: sample_rate, hop, frame_length, window = {ints} do not fit 32 bits')
+        super().__init__(C.sizeof(PitchConfig), *ints, int(device), float(v['fmin']), float(v['fmax']), float(v['threshold']),
+                         float(v['silence_rms']), float(v['gpe_ratio']))
 
 
 WEIGHT_FORMATS = {'f32': 0, 'f16': 1}   # WRNN_WEIGHTS_*: the element type of the TEAMG / TEAMG_BATCH weight image
@@ -493,6 +521,20 @@ def load_library() -> C.CDLL:
     lib.wrnn_score_last_error.restype = C.c_char_p
     lib.wrnn_score_destroy.argtypes = [vp]
     lib.wrnn_score_destroy.restype = None
+    lib.wrnn_pitch_create.argtypes = [C.POINTER(PitchConfig), C.POINTER(vp)]
+    lib.wrnn_pitch_create.restype = C.c_int
+    lib.wrnn_pitch_frames.argtypes = [vp, C.c_int64]
+    lib.wrnn_pitch_frames.restype = C.c_int64
+    lib.wrnn_pitch_lags.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.wrnn_pitch_lags.restype = C.c_int
+    lib.wrnn_pitch_track.argtypes = [vp, vp, C.c_int64, vp, C.c_int32, vp, vp, C.c_int64, vp]
+    lib.wrnn_pitch_track.restype = C.c_int
+    lib.wrnn_pitch_score.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int32, vp, vp, C.c_int64, vp]
+    lib.wrnn_pitch_score.restype = C.c_int
+    lib.wrnn_pitch_last_error.argtypes = [vp]
+    lib.wrnn_pitch_last_error.restype = C.c_char_p
+    lib.wrnn_pitch_destroy.argtypes = [vp]
+    lib.wrnn_pitch_destroy.restype = None
     lib.wrnn_quantise.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp]
     lib.wrnn_quantise.restype = C.c_int
     lib.wrnn_collate_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -1145,6 +1187,55 @@ class NativeScore:
     def close(self):
         if getattr(self, '_h', None):
             self.lib.wrnn_score_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NativePitch:
+    """Owner of one ``wrnn_pitch_handle`` (a YIN F0 track and the F0 / voicing error scores of a pair; no weights, no tables).  Creating
+    it touches no device; a configuration the library refuses raises ``ValueError``.  ``config``: a ``PitchConfig``."""
+
+    def __init__(self, config=None):
+        self.lib = load_library()
+        self.config = config if config is not None else PitchConfig()
+        self.device = int(self.config.device)
+        self._h = C.c_void_p()
+        rc = self.lib.wrnn_pitch_create(C.byref(self.config), C.byref(self._h))
+        if rc != 0:
+            msg = self.lib.wrnn_pitch_last_error(self._h).decode() if self._h else 'wrnn_pitch_create failed'
+            self.close()
+            raise ValueError(f'{ERR_NAMES.get(rc, rc)}: {msg}')
+        lo, hi = C.c_int32(), C.c_int32()
+        self._check(self.lib.wrnn_pitch_lags(self._h, C.byref(lo), C.byref(hi)))
+        self.tau_min, self.tau_max = lo.value, hi.value
+
+    def _check(self, rc: int):
+        if rc != 0:
+            raise WrnnError(rc, self.lib.wrnn_pitch_last_error(self._h).decode())
+
+    def frames(self, n: int) -> int:
+        """Host-only ``wrnn_pitch_frames``: ``1 + n // hop`` frames of ``n >= 1`` samples, none of an empty clip."""
+        t = int(self.lib.wrnn_pitch_frames(self._h, int(n))) if 0 <= int(n) < 2 ** 31 else -1
+        if t < 0:
+            raise ValueError(f'a clip length of {int(n)} samples is outside 0 .. 2**31 - 1')
+        return t
+
+    def track(self, wav_ptr: int, n_max: int, n_ptr: int, B: int, f0_ptr: int, ap_ptr: int, frames_stride: int, stream: int):
+        self._check(self.lib.wrnn_pitch_track(self._h, wav_ptr or None, int(n_max), n_ptr or None, int(B), f0_ptr or None, ap_ptr or None,
+                                              int(frames_stride), stream or None))
+
+    def score(self, target_ptr: int, test_ptr: int, n_max: int, n_ptr: int, B: int, summary_ptr: int, frames_ptr: int, frames_stride: int, stream: int):
+        self._check(self.lib.wrnn_pitch_score(self._h, target_ptr or None, test_ptr or None, int(n_max), n_ptr or None, int(B), summary_ptr or None,
+                                              frames_ptr or None, int(frames_stride), stream or None))
+
+    def close(self):
+        if getattr(self, '_h', None):
+            self.lib.wrnn_pitch_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -622,6 +622,114 @@ class SpectralScore:
         return out
 
 
+class _PitchBase:
+    """The settings and the per-device handles ``PitchTracker`` and ``PitchScore`` share."""
+
+    def __init__(self, hp=None, device=None, **settings):
+        unknown = set(settings) - set(_cabi.PITCH_DEFAULTS)
+        if unknown:
+            raise TypeError(f'unknown pitch settings {sorted(unknown)}')
+        s = dict(_cabi.PITCH_DEFAULTS)
+        if hp is not None:
+            s['sample_rate'], s['hop'] = getattr(hp, 'sample_rate', s['sample_rate']), getattr(hp, 'hop_length', s['hop'])
+        s.update(settings)
+        self.settings = s
+        self.sample_rate, self.hop, self.frame_length, self.window = (int(s[k]) for k in ('sample_rate', 'hop', 'frame_length', 'window'))
+        self._device = device
+        self._index = torch.device(device).index if device is not None and torch.device(device).index is not None else None
+        self._nat = {}
+        nat = self._native(self._index or 0)   # the configuration is checked here, without a device
+        self.tau_min, self.tau_max = nat.tau_min, nat.tau_max
+
+    def _native(self, index: int) -> _cabi.NativePitch:
+        if index not in self._nat:
+            self._nat[index] = _cabi.NativePitch(_cabi.PitchConfig(device=index, **self.settings))
+        return self._nat[index]
+
+    def frames(self, n: int) -> int:
+        """The frames of a clip of ``n`` samples: ``1 + n // hop``, and none of an empty clip."""
+        return next(iter(self._nat.values())).frames(n)
+
+    def _cuda(self, device, what):
+        dev = torch.device(device if device is not None else self._device if self._device is not None else 'cuda')
+        if dev.type != 'cuda':
+            raise ValueError(f'{what} on the GPU only, got device {dev}')
+        return torch.device('cuda', dev.index if dev.index is not None else torch.cuda.current_device())
+
+
+class PitchTracker(_PitchBase):
+    """``PitchTracker(hp, frame_length=2048, window=1024, fmin=60, fmax=600, threshold=0.15, silence_rms=1e-4)``: the YIN F0 track of
+    clips on the device (``csrc/pitch.hip``; the definitions are in ``include/wavernn_amd.h``), one frame per ``hop`` samples, lined up
+    with the mel's frames.  ``sample_rate`` and ``hop`` come from ``hp`` unless given.  ``ValueError`` for a configuration the library
+    refuses, without a device."""
+
+    def track(self, wavs, device=None):
+        """``wavs``: what ``MelFrontEnd.melspectrogram`` accepts (one 1-D array / tensor, a 2-D one, or a list of clips of different
+        lengths, on the host or the device).  One library call for the whole list.  Returns a list of ``(f0, aperiodicity)`` float32
+        arrays over each clip's own ``frames(n)`` frames; ``f0`` is 0 on unvoiced frames."""
+        clips, lens = _clip_list(wavs)
+        T = [self.frames(n) for n in lens]
+        dev = self._cuda(device, 'the pitch tracker runs')
+        B, n_max = len(lens), max(max(lens), 1)
+        wav = _padded_rows(clips, lens, dev) if max(lens) > 0 else torch.zeros((B, 1), dtype=torch.float32, device=dev)
+        nat = self._native(dev.index)
+        stride = nat.frames(n_max)
+        with torch.cuda.device(dev):
+            n_dev = torch.tensor(lens, dtype=torch.int32).to(dev)
+            out = torch.empty((2, B, stride), dtype=torch.float32, device=dev)
+            nat.track(wav.data_ptr(), n_max, n_dev.data_ptr(), B, out[0].data_ptr(), out[1].data_ptr(), stride,
+                      torch.cuda.current_stream(dev).cuda_stream)
+            out = out.cpu().numpy()
+        self.last_buffer = out     # the raw rows as the library wrote them (zeros past a clip's own frames)
+        return [(out[0, b, :t].copy(), out[1, b, :t].copy()) for b, t in enumerate(T)]
+
+
+class PitchScore(_PitchBase):
+    """``PitchScore(hp, gpe_ratio=0.2, ...)``: the F0 and voicing errors of test clips against their targets, on the device, over the
+    tracks of ``PitchTracker`` with the same settings: ``f0_rmse_cents``, ``gpe`` (gross pitch error), ``vde`` (voicing decision
+    error), ``ffe`` (F0 frame error), ``f0_corr`` and the voiced frame counts.  No time alignment: the clips are compared frame for frame."""
+
+    def score(self, targets, tests, device=None, per_frame=False):
+        """``targets`` and ``tests`` as ``SpectralScore.score`` takes them, pair by pair; every pair is cut to its shorter clip.  One
+        library call for the whole list.  Returns a list of dicts, one per pair: the names of ``_cabi.PITCH_FIELD_NAMES`` (the three
+        counts as ints), ``n`` and ``frames``; with ``per_frame=True`` also ``f0_target``, ``aperiodicity_target``, ``f0_test``,
+        ``aperiodicity_test`` and ``cents`` (float32 arrays over the pair's frames).  Reading the results back is the one host wait."""
+        (ca, la), (cb, lb) = _clip_list(targets), _clip_list(tests)
+        if len(ca) != len(cb):
+            raise ValueError(f'{len(ca)} targets for {len(cb)} tests')
+        lens = [min(a, b) for a, b in zip(la, lb)]
+        T = [self.frames(n) for n in lens]
+        dev = self._cuda(device, 'the scores run')
+        B, n_max = len(lens), max(max(lens), 1)
+        if max(lens) > 0:
+            wa = _padded_rows([c[:n] for c, n in zip(ca, lens)], lens, dev)
+            wb = _padded_rows([c[:n] for c, n in zip(cb, lens)], lens, dev)
+        else:
+            wa = wb = torch.zeros((B, 1), dtype=torch.float32, device=dev)
+        nat = self._native(dev.index)
+        F = nat.frames(n_max)
+        with torch.cuda.device(dev):
+            n_dev = torch.tensor(lens, dtype=torch.int32).to(dev)
+            summary = torch.empty((B, _cabi.PITCH_FIELDS), dtype=torch.float64, device=dev)
+            frames = torch.empty((B, 5 * F), dtype=torch.float32, device=dev) if per_frame else None
+            nat.score(wa.data_ptr(), wb.data_ptr(), n_max, n_dev.data_ptr(), B, summary.data_ptr(), frames.data_ptr() if per_frame else 0,
+                      5 * F, torch.cuda.current_stream(dev).cuda_stream)
+            summary = summary.cpu().numpy()
+            frames = frames.cpu().numpy() if per_frame else None
+        self.last_frames_buffer = frames
+        out = []
+        for b, n in enumerate(lens):
+            d = dict(zip(_cabi.PITCH_FIELD_NAMES, (float(v) for v in summary[b])))
+            for k in _cabi.PITCH_FIELD_NAMES[5:]:
+                d[k] = int(d[k])
+            d.update(n=n, frames=T[b])
+            if per_frame:
+                for i, name in enumerate(_cabi.PITCH_FRAME_NAMES):
+                    d[name] = frames[b, i * F:i * F + T[b]].copy()
+            out.append(d)
+        return out
+
+
 def _decode(path, data) -> np.ndarray:
     if data.dtype == np.int16:
         y = data.astype(np.float32) / np.float32(32768.0)

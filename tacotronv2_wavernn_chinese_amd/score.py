@@ -2,12 +2,15 @@
 
     wavernn_score.py --target a.wav --test b.wav [--features vocoder|tacotron] [--resample] [--json] [--per_frame out.npz]
     wavernn_score.py --target_dir DIR --test_dir DIR
+    wavernn_score.py ... --pitch [--fmin HZ] [--fmax HZ] [--pitch_threshold X]
 
 One line per pair (``mel_lsd_db``: the mean per-frame log-mel distance in dB; ``mcd_db``: the mean mel-cepstral distortion in dB, no
 time alignment; ``mr_sc`` / ``mr_logmag``: spectral convergence and log-magnitude distance, averaged over the STFT resolutions) and the
 mean over the pairs.  Directory mode pairs the ``*.wav`` files of the two folders by stem; a file without a partner is an error.  Every
 pair is compared over the shorter of its two clips.  Files at another sample rate than ``hp.sample_rate`` are an error unless
-``--resample``.  The reference has no such tool: its ``gen_testset`` writes the target next to the generated file and stops there."""
+``--resample``.  ``--pitch`` adds the F0 and voicing errors of ``frontend.PitchScore`` (``csrc/pitch.hip``) to every pair and to the
+mean: ``f0_rmse_cents``, ``gpe``, ``vde``, ``ffe``, ``f0_corr`` and the voiced frame counts; without it the output is what it was before
+the flag existed.  The reference has no such tool: its ``gen_testset`` writes the target next to the generated file and stops there."""
 from __future__ import annotations
 
 import argparse
@@ -17,6 +20,7 @@ from pathlib import Path
 import numpy as np
 
 SUMMARY_KEYS = ('mel_lsd_db', 'mcd_db', 'mr_sc', 'mr_logmag')
+PITCH_KEYS = ('f0_rmse_cents', 'gpe', 'vde', 'ffe', 'f0_corr', 'voiced_target', 'voiced_test', 'voiced_both')   # _cabi.PITCH_FIELD_NAMES
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -32,6 +36,11 @@ def build_parser() -> argparse.ArgumentParser:
                                                                 'file is an error)')
     parser.add_argument('--json', action='store_true', help='print one JSON object (pairs, mean) instead of the table')
     parser.add_argument('--per_frame', metavar='NPZ', help='also write the per-frame arrays of every pair to this .npz file')
+    parser.add_argument('--pitch', action='store_true', help='also report the F0 and voicing errors (a YIN track of both clips on the device)')
+    parser.add_argument('--fmin', type=float, default=None, metavar='HZ', help='the lowest pitch the tracker looks for (default 60)')
+    parser.add_argument('--fmax', type=float, default=None, metavar='HZ', help='the highest pitch the tracker looks for (default 600)')
+    parser.add_argument('--pitch_threshold', type=float, default=None, metavar='X', help="YIN's threshold on the normalised difference "
+                                                                                          '(default 0.15)')
     parser.add_argument('--hp_file', metavar='FILE', default=DEFAULT_HPARAMS, help='The file to use for the hyperparameters')
     return parser
 
@@ -52,24 +61,62 @@ def pair_files(args):
     raise ValueError('give --target and --test, or --target_dir and --test_dir')
 
 
+def pitch_settings(args) -> dict:
+    """The ``PitchScore`` settings the arguments name; ``ValueError`` for tracker settings without ``--pitch``."""
+    given = {k: v for k, v in (('fmin', args.fmin), ('fmax', args.fmax), ('threshold', args.pitch_threshold)) if v is not None}
+    if given and not args.pitch:
+        raise ValueError('--fmin, --fmax and --pitch_threshold belong to --pitch')
+    return given
+
+
+def table(names, scores, mean, pitch_hop=None) -> str:
+    """The table the command prints without ``--json``: one line per pair and the mean; with ``pitch_hop`` (the tracker's hop, under
+    ``--pitch``) a second table of the pitch fields after an empty line."""
+    width = max(len(name) for name in list(names) + ['mean'])
+    lines = [f"{'clip':<{width}}  {'samples':>9}  {'mel_lsd_db':>10}  {'mcd_db':>10}  {'mr_sc':>10}  {'mr_logmag':>10}"]
+    for name, s in zip(names, scores):
+        lines.append(f"{name:<{width}}  {s['n']:>9}  {s['mel_lsd_db']:>10.6f}  {s['mcd_db']:>10.6f}  {s['mr_sc']:>10.6f}  {s['mr_logmag']:>10.6f}")
+    lines.append(f"{'mean':<{width}}  {'':>9}  {mean['mel_lsd_db']:>10.6f}  {mean['mcd_db']:>10.6f}  {mean['mr_sc']:>10.6f}  {mean['mr_logmag']:>10.6f}")
+    if pitch_hop is not None:
+        lines += ['', f"{'clip':<{width}}  {'frames':>9}  {'f0_rmse_cents':>13}  {'gpe':>8}  {'vde':>8}  {'ffe':>8}  {'f0_corr':>8}  "
+                      f"{'voiced (target, test, both)':>27}"]
+        for name, frames, s in [(name, str(1 + s['n'] // pitch_hop), s) for name, s in zip(names, scores)] + [('mean', '', mean)]:
+            voiced = f"{s['voiced_target']:g}, {s['voiced_test']:g}, {s['voiced_both']:g}"
+            lines.append(f"{name:<{width}}  {frames:>9}  {s['f0_rmse_cents']:>13.4f}  {s['gpe']:>8.4f}  {s['vde']:>8.4f}  {s['ffe']:>8.4f}  "
+                         f"{s['f0_corr']:>8.4f}  {voiced:>27}")
+    return '\n'.join(lines)
+
+
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     try:
         pairs = pair_files(args)
+        pitch_kw = pitch_settings(args)
     except ValueError as e:
         parser.error(str(e))
     import torch
-    from .frontend import SpectralScore, load_wav
+    from .frontend import PitchScore, SpectralScore, load_wav
     from .hparams import hparams as hp
     hp.configure(args.hp_file)
     if not torch.cuda.is_available():
         raise RuntimeError('the scores run on an MI355X only (no CPU path)')
     scorer = SpectralScore(hp, features=args.features)
+    try:
+        pitch = PitchScore(hp, **pitch_kw) if args.pitch else None
+    except ValueError as e:
+        parser.error(str(e))
     targets = [load_wav(a, scorer.sample_rate, resample=args.resample) for _, a, _ in pairs]
     tests = [load_wav(b, scorer.sample_rate, resample=args.resample) for _, _, b in pairs]
     scores = scorer.score(targets, tests, per_frame=bool(args.per_frame))
-    mean = {k: float(np.mean([s[k] for s in scores])) for k in SUMMARY_KEYS}
+    keys = SUMMARY_KEYS
+    if pitch is not None:
+        keys = SUMMARY_KEYS + PITCH_KEYS
+        for s, p in zip(scores, pitch.score(targets, tests, per_frame=bool(args.per_frame))):
+            s.update({k: p[k] for k in PITCH_KEYS})
+            if args.per_frame:
+                s['pitch_frames'] = {k: p[k] for k in ('f0_target', 'aperiodicity_target', 'f0_test', 'aperiodicity_test', 'cents')}
+    mean = {k: float(np.mean([s[k] for s in scores])) for k in keys}
     if args.per_frame:
         arrays = {}
         for (name, _, _), s in zip(pairs, scores):
@@ -77,15 +124,13 @@ def main(argv=None):
             for r in s['stft']:
                 for q in ('num', 'den', 'lm'):
                     arrays[f"{name}/{q}_{r['n_fft']}_{r['hop']}_{r['win']}"] = r.pop(q)
+            for k, v in s.pop('pitch_frames', {}).items():
+                arrays[f'{name}/{k}'] = v
         np.savez(args.per_frame, **arrays)
     if args.json:
         print(json.dumps(dict(pairs=[dict(s, name=name) for (name, _, _), s in zip(pairs, scores)], mean=mean)))
     else:
-        width = max(len(name) for name, _, _ in pairs + [('mean', None, None)])
-        print(f"{'clip':<{width}}  {'samples':>9}  {'mel_lsd_db':>10}  {'mcd_db':>10}  {'mr_sc':>10}  {'mr_logmag':>10}")
-        for (name, _, _), s in zip(pairs, scores):
-            print(f"{name:<{width}}  {s['n']:>9}  {s['mel_lsd_db']:>10.6f}  {s['mcd_db']:>10.6f}  {s['mr_sc']:>10.6f}  {s['mr_logmag']:>10.6f}")
-        print(f"{'mean':<{width}}  {'':>9}  {mean['mel_lsd_db']:>10.6f}  {mean['mcd_db']:>10.6f}  {mean['mr_sc']:>10.6f}  {mean['mr_logmag']:>10.6f}")
+        print(table([name for name, _, _ in pairs], scores, mean, pitch.hop if pitch is not None else None))
     return scores
 
 

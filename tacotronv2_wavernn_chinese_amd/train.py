@@ -266,10 +266,11 @@ def synthetic_pairs(n: int, frames: int, *, bits: int, n_mels: int, hop_length: 
     return out
 
 
-def checkpoint_generator(hp, paths: VocPaths, scorer=None):
+def checkpoint_generator(hp, paths: VocPaths, scorer=None, pitch=None):
     """The ``at_checkpoint`` of the command line: ``gen_testset`` (dataset.py:18-43), vocode a few held-out mels next to the checkpoint.
     ``scorer``: a ``frontend.SpectralScore``; every generated clip is then scored against its decoded target (both are in memory) and
-    ``step, clip, mel_lsd_db, mcd_db, mr_sc, mr_logmag`` is appended to ``checkpoints/scores.txt``.  ``None``: nothing else is written."""
+    ``step, clip, mel_lsd_db, mcd_db, mr_sc, mr_logmag`` is appended to ``checkpoints/scores.txt``.  ``None``: nothing else is written.
+    ``pitch``: a ``frontend.PitchScore`` (with a scorer only); ``f0_rmse_cents gpe vde`` of the pair then follow on the same line."""
     def at_checkpoint(mod, test_set, step):
         from .dsp import decode_mu_law, label_2_float, save_wav
         k = step // 1000
@@ -286,7 +287,11 @@ def checkpoint_generator(hp, paths: VocPaths, scorer=None):
                                hp.voc_overlap, hp.mu_law)
             if scorer is not None:
                 s = scorer.score(np.asarray(x, np.float32), np.asarray(wav, np.float32), device=next(mod.parameters()).device)[0]
-                rows.append(f"{step} {i} {s['mel_lsd_db']:.6f} {s['mcd_db']:.6f} {s['mr_sc']:.6f} {s['mr_logmag']:.6f}\n")
+                row = f"{step} {i} {s['mel_lsd_db']:.6f} {s['mcd_db']:.6f} {s['mr_sc']:.6f} {s['mr_logmag']:.6f}"
+                if pitch is not None:
+                    p = pitch.score(np.asarray(x, np.float32), np.asarray(wav, np.float32), device=next(mod.parameters()).device)[0]
+                    row += f" {p['f0_rmse_cents']:.6f} {p['gpe']:.6f} {p['vde']:.6f}"
+                rows.append(row + '\n')
         if rows:
             with open(paths.voc_checkpoints / 'scores.txt', 'a') as fh:
                 fh.writelines(rows)
@@ -326,6 +331,9 @@ def build_parser():
                              '(frontend.SpectralScore) and append "step clip mel_lsd_db mcd_db mr_sc mr_logmag" to '
                              'logs_wavernn/checkpoints/scores.txt (default: off; with --synthetic, hp.voc_gen_at_checkpoint more synthetic '
                              'utterances are held out for it)')
+    parser.add_argument('--score_pitch', action='store_true',
+                        help='extension, with --score_at_checkpoint: also append "f0_rmse_cents gpe vde" (frontend.PitchScore, a YIN track of '
+                             'both clips on the device) to each line of scores.txt (default: off)')
     parser.add_argument('--reference_body', action='store_true',
                         help="run the reference's loop body (model(x, m) + torch loss) instead of the fused training_loss")
     return parser
@@ -350,6 +358,8 @@ def main(argv=None):
     from .gen import build_model_from_hparams
     from .hparams import hparams as hp
     args = build_parser().parse_args(argv)
+    if args.score_pitch and not args.score_at_checkpoint:
+        raise ValueError('--score_pitch extends --score_at_checkpoint: give both')
     conditioning = condition_arguments(args)
     sparsify = sparsity_schedule(args)
     hp.configure(args.hp_file)
@@ -404,7 +414,11 @@ def main(argv=None):
     if args.score_at_checkpoint:
         from .frontend import SpectralScore
         scorer = SpectralScore(hp, features=args.features)
-    at_checkpoint = checkpoint_generator(hp, paths, scorer)
+    pitch = None
+    if args.score_pitch:
+        from .frontend import PitchScore
+        pitch = PitchScore(hp)
+    at_checkpoint = checkpoint_generator(hp, paths, scorer, pitch)
 
     voc_train_loop(paths, model, loss_func, optimizer, loader, test, hp.voc_lr, total,
                    clip_grad_norm=hp.voc_clip_grad_norm, checkpoint_every=hp.voc_checkpoint_every, at_checkpoint=at_checkpoint,

@@ -4,8 +4,10 @@ Vocodes one mel unbatched and in the reference's batched mode at three fold dens
 clip becomes 64 folds), ``target='per_xcd'`` (one fold per XCD team) and the reference's own 11000 / 550 -- with the same seed, scores
 every folded output against the unbatched one (``frontend.SpectralScore``), and lists the per-frame log-mel distance ``lsd`` at and away
 from the fold boundaries: a frame is "at a boundary" when its centre ``t hop`` lies inside a crossfade of ``overlap`` samples.
+``--pitch`` adds the F0 and voicing errors of every run against the unbatched output (``frontend.PitchScore``): what a cold-started
+fold does to the pitch track, which the spectral distances hardly see.
 
-    python tools/fold_quality.py --voc_weights CHECKPOINT.pyt --mel MEL.npy [--seed 1] [--overlap 550]
+    python tools/fold_quality.py --voc_weights CHECKPOINT.pyt --mel MEL.npy [--seed 1] [--overlap 550] [--pitch]
     python tools/fold_quality.py --frames 401                      # no checkpoint: the repository's seeded random weights, a synthetic mel
 
 WHAT THIS DOES NOT SHOW.  No trained checkpoint ships with this repository.  Without ``--voc_weights`` the model carries seeded random
@@ -45,10 +47,11 @@ def main(argv=None):
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--baseline_seed', type=int, default=2, help='the unbatched output under this seed is scored too: the distance between two samplings')
     ap.add_argument('--overlap', type=int, default=550)
+    ap.add_argument('--pitch', action='store_true', help='also report f0_rmse_cents, gpe, vde, ffe, f0_corr and the voiced frame counts of every run')
     ap.add_argument('--hp_file', default=None)
     args = ap.parse_args(argv)
     import torch
-    from tacotronv2_wavernn_chinese_amd.frontend import SpectralScore
+    from tacotronv2_wavernn_chinese_amd.frontend import PitchScore, SpectralScore
     from tacotronv2_wavernn_chinese_amd.synth import DEFAULT_DIMS, make_mels, make_state_dict
     from tacotronv2_wavernn_chinese_amd.vocoder import WaveRNN
     if args.voc_weights:
@@ -92,6 +95,13 @@ def main(argv=None):
             at = f"{s['lsd'][mask].mean():.4f} ({int(mask.sum())} frames)" if mask.any() else 'none'
             away = f"{s['lsd'][~mask].mean():.4f} ({int((~mask).sum())} frames)" if (~mask).any() else 'none'
         print(f"{name:<34} {folds:>5} {s['mel_lsd_db']:>10.4f} {s['mcd_db']:>8.4f} {s['mr_sc']:>8.4f} {s['mr_logmag']:>9.4f} | {at:>26} {away:>26}")
+    if args.pitch:
+        pitch = PitchScore(hop=hop, sample_rate=model.sample_rate)
+        print()
+        print(f"{'run':<34} {'f0_rmse_cents':>13} {'gpe':>8} {'vde':>8} {'ffe':>8} {'f0_corr':>8} {'voiced (unbatched, run, both)':>30}")
+        for (name, _, _), p in zip(runs, pitch.score([base] * len(runs), [wav for _, _, wav in runs])):
+            voiced = f"{p['voiced_target']}, {p['voiced_test']}, {p['voiced_both']} of {p['frames']}"
+            print(f"{name:<34} {p['f0_rmse_cents']:>13.4f} {p['gpe']:>8.4f} {p['vde']:>8.4f} {p['ffe']:>8.4f} {p['f0_corr']:>8.4f} {voiced:>30}")
 
 
 if __name__ == '__main__':
