@@ -955,6 +955,99 @@ int wrnn_pitch_score(wrnn_pitch_handle *h, const float *target_dev, const float 
 const char *wrnn_pitch_last_error(const wrnn_pitch_handle *h);
 void wrnn_pitch_destroy(wrnn_pitch_handle *h);
 
+/* ---- time alignment (new entry points in ABI 9 again, and one new struct; nothing existing changes): the dynamic-time-warping path of
+ * a TEST clip b (nb samples) against a TARGET clip a (na samples, need not equal nb) over their mel cepstra, and the scores along it.
+ * The score and pitch sections above compare frame t with frame t; this one is for pairs that are not sample-aligned (trimmed clips, a
+ * rendering of a predicted mel against the recording, two takes of a sentence).
+ * Mels and cepstra.  Both clips go through the mel front end above, in either feature profile, exactly as wrnn_score runs it:
+ * Ma (n_mels, Ta), Mb (n_mels, Tb) in [0, 1], T = 1 + n / hop_length.
+ *   ca[k, i] = (sum_m C[k, m] Ma[m, i]) (-min_level_db) ln 10 / 20,  k = 1 .. K = mcd_order;  C = wrnn_score_tables' dct (the orthonormal
+ *              DCT-II without row 0).  float32, rounded once from a float64 sum over m in ascending order; cb likewise.
+ * Cost.
+ *   d(i, j) = (10 / ln 10) sqrt(2 sum_k (ca[k, i] - cb[k, j])^2)     float32, rounded once from a float64 sum over k in ascending order.
+ * Both clips' cepstra come out of the same instructions, so identical frames give d = 0 exactly.
+ * Accumulated cost, float64.
+ *   D(0, 0) = d(0, 0);  D(i, j) = d(i, j) + min(D(i - 1, j - 1), D(i - 1, j), D(i, j - 1)), leaving out predecessors outside the matrix.
+ * The predecessor is picked in that order: the diagonal first, then (i - 1, j) if it is strictly smaller, then (i, j - 1) if it is
+ * strictly smaller than the one held (so a NaN never displaces a held value).  One byte per cell records the choice.  The symmetric step
+ * pattern with unit weights; no band, no slope constraint.
+ * Path.  Backtracked from (Ta - 1, Tb - 1) to (0, 0) over the recorded choices, returned in ascending order: P pairs (i_p, j_p),
+ * max(Ta, Tb) <= P <= Ta + Tb - 1.  The backtrack takes at most Ta + Tb - 1 steps whatever the matrix holds (NaN included): every step
+ * lowers i + j and stays inside the matrix, and the loop has that bound of its own.
+ * Summaries: WRNN_ALIGN_FIELDS float64 per pair, in a fixed order (no floating-point atomics: two calls give the same bits, and a pair
+ * of a ragged batch equals the call on it alone bit for bit):
+ *   total_cost = D(Ta - 1, Tb - 1),  path_len = P,  frames_target = Ta,  frames_test = Tb,  mcd_dtw_db = total_cost / P,
+ *   mel_lsd_dtw_db = mean_p lsd_p,  lsd_p = sqrt(mean_m ((Ma[m, i_p] - Mb[m, j_p]) (-min_level_db))^2)      float64 from the float32 mels
+ * and, with F0 tracks supplied (float32 as wrnn_pitch_track writes them, 0 = unvoiced; ft the target's, fs the test's; V the path pairs
+ * voiced on both sides), in float64:
+ *   f0_rmse_cents = sqrt(mean_V (1200 log2(fs[j_p] / ft[i_p]))^2),  gpe = #{p in V: |fs / ft - 1| > gpe_ratio} / #V,
+ *   vde = #{p: voiced differs} / P,  ffe = (#gpe pairs + #vde pairs) / P,
+ *   f0_corr = the Pearson correlation of log2 f0 over V in two passes, as wrnn_pitch_score defines it,  voiced_both = #V.
+ * Without tracks these six are 0; f0_rmse_cents, gpe and f0_corr are 0 when V is empty.  A clip with no frames (shorter than the front
+ * end can pad) gives an all-zero row, path_len = 0 and a path of -1.  Identical clips give the pure diagonal (P = T) and exactly 0 in
+ * total_cost, mcd_dtw_db, mel_lsd_dtw_db, f0_rmse_cents, gpe, vde and ffe: equal frames cost exactly 0, every D is then >= 0 with 0 on
+ * the diagonal, and the diagonal wins every tie.
+ * Limits, checked on the host from B and the frames Ta_max, Tb_max of the longest clips (WRNN_ERR_UNSUPPORTED beyond them):
+ *   min(Ta_max, Tb_max) <= 4096   one workgroup runs a pair's DP along the anti-diagonals and keeps three of them (s, s - 1, s - 2) in
+ *                                 LDS as float64, indexed by the pair's shorter side: 3 x 4096 x 8 bytes = 96 KiB of the 160 KiB;
+ *   B Ta_max Tb_max <= 2^28       a cell index fits 32 bits, and the scratch stays at 1 GiB of costs + 256 MiB of choice bytes.
+ * and 1 <= B <= 65535 (WRNN_ERR_INVALID). */
+#define WRNN_ALIGN_FIELDS 12       /* doubles per pair in summary_dev, in this order: */
+#define WRNN_ALIGN_TOTAL_COST 0
+#define WRNN_ALIGN_PATH_LEN 1
+#define WRNN_ALIGN_FRAMES_TARGET 2
+#define WRNN_ALIGN_FRAMES_TEST 3
+#define WRNN_ALIGN_MCD_DTW_DB 4
+#define WRNN_ALIGN_MEL_LSD_DTW_DB 5
+#define WRNN_ALIGN_F0_RMSE_CENTS 6
+#define WRNN_ALIGN_GPE 7
+#define WRNN_ALIGN_VDE 8
+#define WRNN_ALIGN_FFE 9
+#define WRNN_ALIGN_F0_CORR 10
+#define WRNN_ALIGN_VOICED_BOTH 11
+typedef struct wrnn_align_handle wrnn_align_handle;
+typedef struct wrnn_align_config {
+    uint32_t struct_size;    /* the size of this struct */
+    int32_t mcd_order;       /* 13 */
+    double gpe_ratio;        /* 0.2 */
+} wrnn_align_config;
+/* Host only, touches no device.  `features` may be NULL: the default profile.  It refuses what the profile create entry of the front
+ * end refuses (with that entry's status), and with WRNN_ERR_INVALID a struct_size other than the struct's own size, mcd_order outside
+ * 1 .. n_mels - 1 and a gpe_ratio that is not finite and > 0.  A refused handle is still returned, for its error text and the destroy
+ * entry. */
+int wrnn_align_create(const wrnn_mel_config *cfg, const wrnn_mel_features *features, const wrnn_align_config *align, wrnn_align_handle **out);
+/* Host only: the frames of a clip of n samples, 1 + n / hop_length.  WRNN_ERR_INVALID (< 0) for a clip the front end cannot pad (under
+ * reflect padding fewer than n_fft / 2 + 1 samples, under zero padding none), n >= 2^31 or a refused handle. */
+int64_t wrnn_align_frames(const wrnn_align_handle *h, int64_t n);
+/* Host only: the bytes of scratch wrnn_align_score needs for B pairs whose longest clips have na_max and nb_max samples (the other
+ * entries need less), or the negative status with which that call would be refused (the limits above; the text is in last_error). */
+int64_t wrnn_align_workspace_bytes(wrnn_align_handle *h, int32_t B, int64_t na_max, int64_t nb_max);
+/* target_dev: B float32 clips, row stride na_max; na_dev: B int32 on the device, their own lengths; test_dev, nb_max, nb_dev likewise
+ * (ragged; a value above the stride is read as the stride; a clip too short to pad has no frames: the lengths live on the device and
+ * the call never waits, so the HOST side checks them with the frames entry).  With Ta_max, Tb_max the frames entry's values for na_max,
+ * nb_max: cost_dev (B, Ta_max, Tb_max) float32, d(i, j) of pair b at [b][i][j]; cells outside a pair's own Ta x Tb are written as 0.
+ * 2 (+ 2 peak launches under a profile with preemph_rescale) mel launches and 2 of this section, asynchronous on `stream`. */
+int wrnn_align_cost(wrnn_align_handle *h, const float *target_dev, int64_t na_max, const int32_t *na_dev, const float *test_dev, int64_t nb_max,
+                    const int32_t *nb_dev, int32_t B, float *cost_dev, void *stream);
+/* The generic part: the accumulated cost and the path over ANY float32 cost matrices.  cost_dev (B, Ta_max, Tb_max); ta_dev, tb_dev: B
+ * int32 on the device, the pairs' own frame counts (read clamped to 0 .. Ta_max, 0 .. Tb_max).  path_dev (B, Ta_max + Tb_max - 1, 2)
+ * int32, 8-byte aligned: (i_p, j_p) in ascending order, entries past P written as -1; path_len_dev (B) int32; total_dev (B) float64.
+ * One launch, one workgroup per pair, asynchronous on `stream`. */
+int wrnn_align_path(wrnn_align_handle *h, const float *cost_dev, int32_t B, int32_t Ta_max, int32_t Tb_max, const int32_t *ta_dev, const int32_t *tb_dev,
+                    int32_t *path_dev, int32_t *path_len_dev, double *total_dev, void *stream);
+/* The whole chain: mels, cepstra, costs, DP, path, the values along it, the summaries.  The clips as in wrnn_align_cost.
+ * f0_target_dev, f0_test_dev: both NULL, or (B, f0_stride) float32 tracks at the mel's hop, f0_stride >= max(Ta_max, Tb_max).
+ * summary_dev (B, WRNN_ALIGN_FIELDS) float64.  path_dev, path_len_dev: NULL, or as in wrnn_align_path.  per_path_dev: NULL, or
+ * (B, 2, Ta_max + Tb_max - 1) float64: lsd_p, then 1200 log2(fs / ft) of the path pairs in V (0 elsewhere), zeros past P.
+ * The mel launches, then 5 of this section, asynchronous on `stream`.  The handle owns the scratch and grows it when a call needs more
+ * -- the one case in which a call waits for `stream` -- so calls on ONE handle must be ordered by the caller.  The DCT table is uploaded
+ * by the first call (one blocking copy). */
+int wrnn_align_score(wrnn_align_handle *h, const float *target_dev, int64_t na_max, const int32_t *na_dev, const float *test_dev, int64_t nb_max,
+                     const int32_t *nb_dev, int32_t B, const float *f0_target_dev, const float *f0_test_dev, int64_t f0_stride, double *summary_dev,
+                     int32_t *path_dev, int32_t *path_len_dev, double *per_path_dev, void *stream);
+const char *wrnn_align_last_error(const wrnn_align_handle *h);
+void wrnn_align_destroy(wrnn_align_handle *h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,7 +51,9 @@ EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wr
                     'wrnn_score_create', 'wrnn_score_frames', 'wrnn_score', 'wrnn_score_tables', 'wrnn_score_last_error',
                     'wrnn_score_destroy',
                     'wrnn_pitch_create', 'wrnn_pitch_frames', 'wrnn_pitch_lags', 'wrnn_pitch_track', 'wrnn_pitch_score',
-                    'wrnn_pitch_last_error', 'wrnn_pitch_destroy')
+                    'wrnn_pitch_last_error', 'wrnn_pitch_destroy',
+                    'wrnn_align_create', 'wrnn_align_frames', 'wrnn_align_workspace_bytes', 'wrnn_align_cost', 'wrnn_align_path',
+                    'wrnn_align_score', 'wrnn_align_last_error', 'wrnn_align_destroy')
 
 
 def epilogue_tables(n_classes: int, overlap: int, hop: int):
@@ -186,6 +188,23 @@ class PitchConfig(C.Structure):
             raise ValueError(f'WRNN_ERR_INVALID: sample_rate, hop, frame_length, window = {ints} do not fit 32 bits')
         super().__init__(C.sizeof(PitchConfig), *ints, int(device), float(v['fmin']), float(v['fmax']), float(v['threshold']),
                          float(v['silence_rms']), float(v['gpe_ratio']))
+
+
+ALIGN_FIELDS = 12   # WRNN_ALIGN_FIELDS
+# the order of the doubles in wrnn_align_score's summary: WRNN_ALIGN_TOTAL_COST .. WRNN_ALIGN_VOICED_BOTH
+ALIGN_FIELD_NAMES = ('total_cost', 'path_len', 'frames_target', 'frames_test', 'mcd_dtw_db', 'mel_lsd_dtw_db', 'f0_rmse_cents', 'gpe', 'vde', 'ffe',
+                     'f0_corr', 'voiced_both')
+ALIGN_COUNT_NAMES = ('path_len', 'frames_target', 'frames_test', 'voiced_both')   # the fields that are counts
+ALIGN_PATH_NAMES = ('lsd', 'cents')   # the rows of per_path_dev
+ALIGN_MAX_SIDE, ALIGN_MAX_CELLS = 4096, 2 ** 28   # min(Ta_max, Tb_max) and B Ta_max Tb_max of one call
+
+
+class AlignConfig(C.Structure):
+    """``wrnn_align_config``."""
+    _fields_ = [('struct_size', C.c_uint32), ('mcd_order', C.c_int32), ('gpe_ratio', C.c_double)]
+
+    def __init__(self, mcd_order=13, gpe_ratio=0.2):
+        super().__init__(C.sizeof(AlignConfig), int(mcd_order), float(gpe_ratio))
 
 
 WEIGHT_FORMATS = {'f32': 0, 'f16': 1}   # WRNN_WEIGHTS_*: the element type of the TEAMG / TEAMG_BATCH weight image
@@ -535,6 +554,22 @@ def load_library() -> C.CDLL:
     lib.wrnn_pitch_last_error.restype = C.c_char_p
     lib.wrnn_pitch_destroy.argtypes = [vp]
     lib.wrnn_pitch_destroy.restype = None
+    lib.wrnn_align_create.argtypes = [C.POINTER(MelConfig), C.POINTER(MelFeatures), C.POINTER(AlignConfig), C.POINTER(vp)]
+    lib.wrnn_align_create.restype = C.c_int
+    lib.wrnn_align_frames.argtypes = [vp, C.c_int64]
+    lib.wrnn_align_frames.restype = C.c_int64
+    lib.wrnn_align_workspace_bytes.argtypes = [vp, C.c_int32, C.c_int64, C.c_int64]
+    lib.wrnn_align_workspace_bytes.restype = C.c_int64
+    lib.wrnn_align_cost.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int32, vp, vp]
+    lib.wrnn_align_cost.restype = C.c_int
+    lib.wrnn_align_path.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
+    lib.wrnn_align_path.restype = C.c_int
+    lib.wrnn_align_score.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int32, vp, vp, C.c_int64, vp, vp, vp, vp, vp]
+    lib.wrnn_align_score.restype = C.c_int
+    lib.wrnn_align_last_error.argtypes = [vp]
+    lib.wrnn_align_last_error.restype = C.c_char_p
+    lib.wrnn_align_destroy.argtypes = [vp]
+    lib.wrnn_align_destroy.restype = None
     lib.wrnn_quantise.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp]
     lib.wrnn_quantise.restype = C.c_int
     lib.wrnn_collate_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -1236,6 +1271,76 @@ class NativePitch:
     def close(self):
         if getattr(self, '_h', None):
             self.lib.wrnn_pitch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NativeAlign:
+    """Owner of one ``wrnn_align_handle`` (the DTW path of a test clip against a target over their mel cepstra, and the scores along it;
+    no weights).  Creating it touches no device; a configuration the library refuses raises ``ValueError``.  ``features``: a
+    ``MelFeatures`` or ``None`` (the default profile); ``align``: an ``AlignConfig``."""
+
+    def __init__(self, *, sample_rate=22050, n_fft=2048, hop_length=275, win_length=1100, n_mels=80, fmin=95, min_level_db=-100, device: int = 0,
+                 features=None, align=None):
+        self.lib = load_library()
+        cfg = MelConfig(int(sample_rate), int(n_fft), int(hop_length), int(win_length), int(n_mels), float(fmin), float(min_level_db), int(device))
+        self.cfg = cfg
+        self.features = features
+        self.align_config = align if align is not None else AlignConfig()
+        self.device = int(device)
+        self._h = C.c_void_p()
+        rc = self.lib.wrnn_align_create(C.byref(cfg), C.byref(features) if features is not None else None, C.byref(self.align_config),
+                                        C.byref(self._h))
+        if rc != 0:
+            msg = self.lib.wrnn_align_last_error(self._h).decode() if self._h else 'wrnn_align_create failed'
+            self.close()
+            raise ValueError(f'{ERR_NAMES.get(rc, rc)}: {msg}')
+        reflect = features is None or features.pad_mode == MEL_PAD_MODES['reflect']
+        self.min_samples = cfg.n_fft // 2 + 1 if reflect else 1
+
+    def _check(self, rc: int):
+        if rc != 0:
+            raise WrnnError(rc, self.lib.wrnn_align_last_error(self._h).decode())
+
+    def frames(self, n: int) -> int:
+        """Host-only ``wrnn_align_frames``: ``1 + n // hop_length``; ``ValueError`` for a clip shorter than ``min_samples``."""
+        t = int(self.lib.wrnn_align_frames(self._h, int(n))) if 0 <= int(n) < 2 ** 31 else -1
+        if t < 0:
+            raise ValueError(f'a clip of {int(n)} samples cannot be aligned: at least {self.min_samples} samples are needed')
+        return t
+
+    def workspace_bytes(self, B: int, na_max: int, nb_max: int) -> int:
+        """Host-only ``wrnn_align_workspace_bytes``: the scratch of a score call, or ``WrnnError`` with the status of its refusal."""
+        if not (0 <= int(B) < 2 ** 31 and 0 <= int(na_max) < 2 ** 63 and 0 <= int(nb_max) < 2 ** 63):
+            raise WrnnError(ERR_INVALID, f'B = {B}, na_max = {na_max}, nb_max = {nb_max} do not fit the entry')
+        n = int(self.lib.wrnn_align_workspace_bytes(self._h, int(B), int(na_max), int(nb_max)))
+        if n < 0:
+            raise WrnnError(n, self.lib.wrnn_align_last_error(self._h).decode())
+        return n
+
+    def cost(self, target_ptr: int, na_max: int, na_ptr: int, test_ptr: int, nb_max: int, nb_ptr: int, B: int, cost_ptr: int, stream: int):
+        self._check(self.lib.wrnn_align_cost(self._h, target_ptr or None, int(na_max), na_ptr or None, test_ptr or None, int(nb_max), nb_ptr or None,
+                                             int(B), cost_ptr or None, stream or None))
+
+    def path(self, cost_ptr: int, B: int, Ta_max: int, Tb_max: int, ta_ptr: int, tb_ptr: int, path_ptr: int, path_len_ptr: int, total_ptr: int,
+             stream: int):
+        self._check(self.lib.wrnn_align_path(self._h, cost_ptr or None, int(B), int(Ta_max), int(Tb_max), ta_ptr or None, tb_ptr or None,
+                                             path_ptr or None, path_len_ptr or None, total_ptr or None, stream or None))
+
+    def score(self, target_ptr: int, na_max: int, na_ptr: int, test_ptr: int, nb_max: int, nb_ptr: int, B: int, f0_target_ptr: int, f0_test_ptr: int,
+              f0_stride: int, summary_ptr: int, path_ptr: int, path_len_ptr: int, per_path_ptr: int, stream: int):
+        self._check(self.lib.wrnn_align_score(self._h, target_ptr or None, int(na_max), na_ptr or None, test_ptr or None, int(nb_max), nb_ptr or None,
+                                              int(B), f0_target_ptr or None, f0_test_ptr or None, int(f0_stride), summary_ptr or None,
+                                              path_ptr or None, path_len_ptr or None, per_path_ptr or None, stream or None))
+
+    def close(self):
+        if getattr(self, '_h', None):
+            self.lib.wrnn_align_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -8,7 +8,9 @@ opt-in everywhere.  ``MelFrontEnd(features='tacotron')`` is the Tacotron-side me
 into the kernel's tap gather), the features the reference's vocoder is trained on.  ``GriffinLim`` (``csrc/griffin_lim.hip``) is the way back with no trained model:
 ``inv_mel_spectrogram`` of ``tacotron/datasets/audio.py:122-137`` in either profile.  ``SpectralScore`` (``csrc/score.hip``) rates a test clip
 against its target: log-mel distance and mel-cepstral distortion over this front end's mel, spectral convergence and log-magnitude distance at
-several STFT resolutions (the reference compares its ``*_target.wav`` files with nothing).  Linear ``spectrogram`` files and LWS are not here.
+several STFT resolutions (the reference compares its ``*_target.wav`` files with nothing).  ``AlignedScore`` and ``dtw_path``
+(``csrc/align.hip``) rate pairs that are not sample-aligned along the dynamic-time-warping path over their mel cepstra.  Linear ``spectrogram``
+files and LWS are not here.
 """
 from __future__ import annotations
 
@@ -728,6 +730,174 @@ class PitchScore(_PitchBase):
                     d[name] = frames[b, i * F:i * F + T[b]].copy()
             out.append(d)
         return out
+
+
+def _ragged_rows(clips, lens, n_max, dev) -> torch.Tensor:
+    """``_padded_rows`` for a buffer that may be wider than the longest clip (a side whose clips are all empty still needs a legal row)."""
+    if max(lens) == n_max:
+        return _padded_rows(clips, lens, dev)
+    with torch.cuda.device(dev):
+        wav = torch.zeros((len(clips), n_max), dtype=torch.float32, device=dev)
+        for i, c in enumerate(clips):
+            if lens[i]:
+                wav[i, :lens[i]] = torch.as_tensor(c).to(device=dev, dtype=torch.float32)
+    return wav
+
+
+class AlignedScore:
+    """``AlignedScore(hp, features='vocoder', mcd_order=13, pitch=False, gpe_ratio=0.2, **pitch_settings)``: test clips rated against
+    their targets along the dynamic-time-warping path over their mel cepstra, on the device (``csrc/align.hip``; the definitions are in
+    ``include/wavernn_amd.h``): for pairs that are not sample-aligned -- a trimmed clip, a rendering of a predicted mel against the
+    recording, two takes of a sentence -- where ``SpectralScore`` and ``PitchScore`` (frame t against frame t) mean nothing.  The mel is
+    ``MelFrontEnd(hp, features=features)``'s (the same configuration: ``hp``, the ``MEL_DEFAULTS`` names and the profile's fields as
+    keywords).  With ``pitch=True`` both clips also go through ``PitchTracker(hp, **pitch_settings)`` at the mel's hop and the F0 /
+    voicing errors are taken along the path; the tracker's settings go by their own names (``frame_length, window, threshold,
+    silence_rms``) or, where the mel has one of that name, with a prefix (``pitch_fmin, pitch_fmax``).  The clips of a pair may differ in length; batches are ragged; a clip of no samples has no
+    frames and an all-zero row.  ``ValueError`` for a configuration the library refuses, without a device."""
+
+    def __init__(self, hp=None, device=None, features='vocoder', mcd_order=13, pitch=False, gpe_ratio=0.2, **kw):
+        if 'n_mels' in kw:
+            kw['num_mels'] = kw.pop('n_mels')
+        self.feature_config = feature_settings(features, **{k: kw.pop(k) for k in list(kw) if k in FEATURE_PROFILES['vocoder']})
+        self.features = features
+        # the tracker's settings under their own names, or with a `pitch_` prefix where the mel has a setting of that name (fmin, fmax)
+        pitch_kw = {k[6:]: kw.pop(k) for k in list(kw) if k.startswith('pitch_') and k[6:] in _cabi.PITCH_DEFAULTS}
+        pitch_kw.update({k: kw.pop(k) for k in list(kw) if k in _cabi.PITCH_DEFAULTS and k not in MEL_DEFAULTS and k != 'gpe_ratio'})
+        unknown = set(kw) - set(MEL_DEFAULTS)
+        if unknown:
+            raise TypeError(f'unknown alignment parameters {sorted(unknown)}')
+        if pitch_kw and not pitch:
+            raise TypeError(f'the pitch settings {sorted(pitch_kw)} belong to pitch=True')
+        self.config = {k: kw[k] if k in kw else getattr(hp, k, v) if hp is not None else v for k, v in MEL_DEFAULTS.items()}
+        self.mcd_order, self.gpe_ratio = int(mcd_order), float(gpe_ratio)
+        self._align_config = _cabi.AlignConfig(self.mcd_order, self.gpe_ratio)
+        self._device = device
+        self._index = torch.device(device).index if device is not None and torch.device(device).index is not None else None
+        self.n_mels, self.hop_length, self.sample_rate = int(self.config['num_mels']), int(self.config['hop_length']), int(self.config['sample_rate'])
+        self._nat = {}
+        self.min_samples = self._native(self._index or 0).min_samples   # the configuration is checked here, without a device
+        self.pitch = PitchTracker(device=device, **dict(dict(sample_rate=self.sample_rate, hop=self.hop_length), **pitch_kw)) if pitch else None
+
+    def _native(self, index: int) -> _cabi.NativeAlign:
+        if index not in self._nat:
+            c, f = self.config, self.feature_config
+            feat = None if f == FEATURE_PROFILES['vocoder'] else _cabi.MelFeatures(**dict(f, pad_mode=_cabi.MEL_PAD_MODES[f['pad_mode']]))
+            self._nat[index] = _cabi.NativeAlign(sample_rate=c['sample_rate'], n_fft=c['n_fft'], hop_length=c['hop_length'], win_length=c['win_length'],
+                                                 n_mels=c['num_mels'], fmin=c['fmin'], min_level_db=c['min_level_db'], device=index, features=feat,
+                                                 align=self._align_config)
+        return self._nat[index]
+
+    def frames(self, n: int) -> int:
+        """The frames of a clip of ``n`` samples, ``1 + n // hop_length``; ``ValueError`` for a clip shorter than ``min_samples``."""
+        return next(iter(self._nat.values())).frames(n)
+
+    def _stage(self, targets, tests, device):
+        """The two sides as padded device rows: (dev, native handle, B, (wav, n_max, lens, n_dev, frames) per side)."""
+        (ca, la), (cb, lb) = _clip_list(targets), _clip_list(tests)
+        if len(ca) != len(cb):
+            raise ValueError(f'{len(ca)} targets for {len(cb)} tests')
+        T = [[self.frames(n) if n else 0 for n in lens] for lens in (la, lb)]   # refuses a short clip before anything is launched; an empty one has no frames
+        dev = torch.device(device if device is not None else self._device if self._device is not None else 'cuda')
+        if dev.type != 'cuda':
+            raise ValueError(f'the alignment runs on the GPU only, got device {dev}')
+        dev = torch.device('cuda', dev.index if dev.index is not None else torch.cuda.current_device())
+        nat = self._native(dev.index)
+        sides = []
+        for clips, lens, frames in ((ca, la, T[0]), (cb, lb, T[1])):
+            n_max = max(max(lens), self.min_samples)
+            wav = _ragged_rows(clips, lens, n_max, dev)
+            with torch.cuda.device(dev):
+                n_dev = torch.tensor(lens, dtype=torch.int32).to(dev)
+            sides.append((wav, n_max, lens, n_dev, frames))
+        nat.workspace_bytes(len(ca), sides[0][1], sides[1][1])   # the library's limits, as a WrnnError before any launch
+        return dev, nat, len(ca), sides
+
+    def cost(self, targets, tests, device=None):
+        """``targets`` and ``tests``: what ``MelFrontEnd.melspectrogram`` accepts, pair by pair.  A list of ``(Ta, Tb)`` float32 device
+        tensors, one per pair: ``d(i, j)`` in dB between frame ``i`` of the target and frame ``j`` of the test."""
+        dev, nat, B, ((wa, na_max, _, na_dev, Ta), (wb, nb_max, _, nb_dev, Tb)) = self._stage(targets, tests, device)
+        with torch.cuda.device(dev):
+            out = torch.empty((B, nat.frames(na_max), nat.frames(nb_max)), dtype=torch.float32, device=dev)
+            nat.cost(wa.data_ptr(), na_max, na_dev.data_ptr(), wb.data_ptr(), nb_max, nb_dev.data_ptr(), B, out.data_ptr(),
+                     torch.cuda.current_stream(dev).cuda_stream)
+        return [out[b, :Ta[b], :Tb[b]] for b in range(B)]
+
+    def align(self, targets, tests, device=None):
+        """The DTW paths: a list of ``(P, 2)`` int32 tensors of ``(i_p, j_p)`` in ascending order, one per pair."""
+        return self.score(targets, tests, device=device, per_path=True)['path']
+
+    def score(self, targets, tests, device=None, per_path=False):
+        """One library call for the whole list (plus the two pitch tracks under ``pitch=True``).  Returns a dict of float64 tensors of
+        shape ``(B,)`` under the names of ``_cabi.ALIGN_FIELD_NAMES`` (``total_cost, path_len, frames_target, frames_test, mcd_dtw_db,
+        mel_lsd_dtw_db, f0_rmse_cents, gpe, vde, ffe, f0_corr, voiced_both``; the pitch fields are 0 without ``pitch=True``); with
+        ``per_path=True`` also ``path`` (a list of ``(P, 2)`` int32 tensors), ``lsd`` and ``cents`` (lists of ``(P,)`` float64 tensors:
+        the log-mel distance of every path pair, and ``1200 log2(fs / ft)`` where both sides are voiced, 0 elsewhere) and, under
+        ``pitch=True``, ``f0_target`` and ``f0_test`` (the tracks, float32).  Everything comes back on the host: reading the results
+        is the one wait."""
+        dev, nat, B, ((wa, na_max, la, na_dev, Ta), (wb, nb_max, lb, nb_dev, Tb)) = self._stage(targets, tests, device)
+        Ta_max, Tb_max = nat.frames(na_max), nat.frames(nb_max)
+        P_max, stride = Ta_max + Tb_max - 1, max(Ta_max, Tb_max)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            f0 = None
+            if self.pitch is not None:
+                f0 = torch.empty((2, B, stride), dtype=torch.float32, device=dev)
+                pn = self.pitch._native(dev.index)
+                pn.track(wa.data_ptr(), na_max, na_dev.data_ptr(), B, f0[0].data_ptr(), 0, stride, stream)
+                pn.track(wb.data_ptr(), nb_max, nb_dev.data_ptr(), B, f0[1].data_ptr(), 0, stride, stream)
+            summary = torch.empty((B, _cabi.ALIGN_FIELDS), dtype=torch.float64, device=dev)
+            path = torch.empty((B, P_max, 2), dtype=torch.int32, device=dev) if per_path else None
+            plen = torch.empty((B,), dtype=torch.int32, device=dev) if per_path else None
+            pp = torch.empty((B, 2, P_max), dtype=torch.float64, device=dev) if per_path else None
+            nat.score(wa.data_ptr(), na_max, na_dev.data_ptr(), wb.data_ptr(), nb_max, nb_dev.data_ptr(), B, f0[0].data_ptr() if f0 is not None else 0,
+                      f0[1].data_ptr() if f0 is not None else 0, stride, summary.data_ptr(), path.data_ptr() if per_path else 0,
+                      plen.data_ptr() if per_path else 0, pp.data_ptr() if per_path else 0, stream)
+            summary = summary.cpu()
+            out = {name: summary[:, i].clone() for i, name in enumerate(_cabi.ALIGN_FIELD_NAMES)}
+            if per_path:
+                path, plen, pp = path.cpu(), plen.cpu().tolist(), pp.cpu()
+                self.last_path_buffer = path       # the raw rows as the library wrote them (-1 past a pair's own path)
+                out['path'] = [path[b, :plen[b]].clone() for b in range(B)]
+                for i, name in enumerate(_cabi.ALIGN_PATH_NAMES):
+                    out[name] = [pp[b, i, :plen[b]].clone() for b in range(B)]
+                if f0 is not None:
+                    f0 = f0.cpu()
+                    out['f0_target'] = [f0[0, b, :Ta[b]].clone() for b in range(B)]
+                    out['f0_test'] = [f0[1, b, :Tb[b]].clone() for b in range(B)]
+        out['n_target'], out['n_test'] = list(la), list(lb)
+        return out
+
+
+_DTW_HANDLES = {}
+
+
+def dtw_path(cost, lens_a=None, lens_b=None):
+    """The generic entry (``wrnn_align_path``): dynamic time warping over ANY cost matrices, a float32 CUDA tensor ``(B, Ta, Tb)`` or
+    ``(Ta, Tb)``; ``lens_a`` / ``lens_b``: the pairs' own frame counts (default: the whole matrix).  The symmetric step pattern with
+    unit weights, ties to the diagonal first, then ``(i - 1, j)``.  Returns ``(paths, totals)``: a list of ``(P, 2)`` int32 device
+    tensors in ascending order and a ``(B,)`` float64 device tensor of ``D(Ta - 1, Tb - 1)``.  Reading the path lengths is the one wait."""
+    if not (isinstance(cost, torch.Tensor) and cost.is_cuda and cost.dtype == torch.float32 and cost.dim() in (2, 3)):
+        raise ValueError('expected a float32 (B, Ta, Tb) or (Ta, Tb) tensor on the GPU')
+    c = (cost if cost.dim() == 3 else cost.unsqueeze(0)).contiguous()
+    B, Ta, Tb = c.shape
+    la = [Ta] * B if lens_a is None else [int(v) for v in lens_a]
+    lb = [Tb] * B if lens_b is None else [int(v) for v in lens_b]
+    if len(la) != B or len(lb) != B or min(la + lb) < 0 or max(la) > Ta or max(lb) > Tb:
+        raise ValueError(f'{len(la)} and {len(lb)} lengths (max {max(la)}, {max(lb)}) for cost matrices of shape {tuple(c.shape)}')
+    dev = c.device
+    if dev.index not in _DTW_HANDLES:
+        _DTW_HANDLES[dev.index] = _cabi.NativeAlign(device=dev.index)
+    nat = _DTW_HANDLES[dev.index]
+    with torch.cuda.device(dev):
+        ta, tb = torch.tensor(la, dtype=torch.int32).to(dev), torch.tensor(lb, dtype=torch.int32).to(dev)
+        path = torch.empty((B, Ta + Tb - 1, 2), dtype=torch.int32, device=dev)
+        plen = torch.empty((B,), dtype=torch.int32, device=dev)
+        total = torch.empty((B,), dtype=torch.float64, device=dev)
+        nat.path(c.data_ptr(), B, Ta, Tb, ta.data_ptr(), tb.data_ptr(), path.data_ptr(), plen.data_ptr(), total.data_ptr(),
+                 torch.cuda.current_stream(dev).cuda_stream)
+        P = plen.cpu().tolist()
+    dtw_path.last_path_buffer = path
+    return [path[b, :P[b]] for b in range(B)], total
 
 
 def _decode(path, data) -> np.ndarray:
