@@ -1048,6 +1048,76 @@ int wrnn_align_score(wrnn_align_handle *h, const float *target_dev, int64_t na_m
 const char *wrnn_align_last_error(const wrnn_align_handle *h);
 void wrnn_align_destroy(wrnn_align_handle *h);
 
+/* ---- Tacotron-2: symbol ids -> mel ------------------------------------------------------------------------------------------------
+ * Inference of the reference's default feature-prediction model (forward location-sensitive attention), free-running or
+ * teacher-forced on a target (GTA).  Per utterance: embedding -> enc_conv_layers x (conv1d 'same' + bias -> ReLU -> BatchNorm) -> BiLSTM
+ * (the memory) -> the decoder loop (prenet with dropout 0.5 always on, decoder_layers zoneout LSTMs, the attention with its
+ * inference-only window block, the frame and stop projections) -> clip -> postnet -> projection + residual -> clip -> [0, 1].
+ * Kernels: grid kernels for everything that is parallel in time; the encoder recurrences run one workgroup per direction per
+ * utterance; the decoder loop runs ONE persistent workgroup per utterance with its state in LDS and decides the stop on the device
+ * (p > 0.5 for any of a step's r tokens; that step's frames are still emitted), so a call never waits for the host per frame and no
+ * workgroup waits for another.  Every loop is bounded by max_iters or Tx.  An utterance of a ragged batch gives the bits of the call
+ * on it alone.  Prenet dropout: layer l of step s keeps unit k (scaled by 2) when the Philox uniform of the utterance's own seed at
+ * counter (s * prenet_layers + l, row 0, k) is >= 0.5.
+ * Limits (WRNN_ERR_INVALID with the reason in last_error): 1 <= Tx <= WRNN_TACO_MAX_TX symbols per utterance, ids inside
+ * 0 .. n_symbols - 1, 1 <= B <= 65535, 1 <= prenet_layers <= WRNN_TACO_MAX_PRENET, 1 <= decoder_layers <= 4, every size >= 1,
+ * conv kernels <= 64 taps, and a decoder state that fits 64 KiB of LDS. */
+#define WRNN_TACO_MAX_TX 1024
+#define WRNN_TACO_MAX_PRENET 4
+typedef struct wrnn_taco_handle wrnn_taco_handle;
+typedef struct wrnn_taco_dims {
+    uint32_t struct_size;        /* the size of this struct */
+    int32_t device;
+    int32_t n_symbols, num_mels, outputs_per_step, embedding_dim;
+    int32_t enc_conv_layers, enc_conv_channels, enc_conv_kernel, encoder_lstm_units;
+    int32_t attention_dim, attention_filters, attention_kernel;
+    int32_t prenet_layers, prenet_sizes[WRNN_TACO_MAX_PRENET];
+    int32_t decoder_layers, decoder_lstm_units;
+    int32_t postnet_layers, postnet_channels, postnet_kernel;
+    float zoneout;               /* 0.1 */
+    float max_abs_value;         /* 4 */
+    float lower_bound_decay;     /* 0.1 */
+    float bn_epsilon;            /* 1e-3 */
+} wrnn_taco_dims;
+typedef struct wrnn_taco_call {
+    uint32_t struct_size;        /* the size of this struct */
+    int32_t B, Tx_max;           /* utterances; the row stride of ids_host */
+    int32_t max_iters;           /* decoder steps at most (free-running); >= 1 */
+    int32_t prenet_dropout;      /* 0: no masks, no scaling */
+    int32_t steps_max;           /* the step stride of the outputs: >= max_iters, with a target >= every gta_frames_host[b] / r */
+    const int32_t *ids_host;     /* (B, Tx_max) */
+    const int32_t *tx_host;      /* (B) symbols per utterance */
+    const uint64_t *seeds_host;  /* (B) */
+    const float *gta_dev;        /* NULL, or (B, gta_max, num_mels): step s >= 1 reads frame s r - 1 */
+    int32_t gta_max;
+    const int32_t *gta_frames_host; /* (B) multiples of r, 1 .. gta_max frames: the utterance runs gta_frames / r steps */
+    /* caller-allocated, on the device; rows past an utterance's own length are written as 0 */
+    float *encoder_dev;          /* NULL, or (B, Tx_max, 2 encoder_lstm_units) */
+    float *decoder_dev;          /* (B, steps_max r, num_mels): the decoder's frames, clipped to [-max_abs - decay, max_abs] */
+    float *mel_raw_dev;          /* (B, steps_max r, num_mels): after the postnet, the residual and the clip */
+    float *mel_dev;              /* (B, steps_max r, num_mels): clip((clip(raw, -max_abs, max_abs) + max_abs) / (2 max_abs), 0, 1) */
+    float *alignments_dev;       /* (B, steps_max, Tx_max) */
+    float *stop_dev;             /* (B, steps_max r) probabilities */
+    int32_t *max_attentions_dev; /* (B, steps_max) */
+    int32_t *steps_dev;          /* (B) decoder steps run */
+    int32_t *mel_frames_dev;     /* (B) free-running: the index of the first stop token > 0.5, else steps r; with a target: steps r */
+} wrnn_taco_call;
+/* Host only.  A refused handle is still returned, for its error text and the destroy entry. */
+int wrnn_taco_create(const wrnn_taco_dims *dims, wrnn_taco_handle **out);
+/* Host only: the tensors the model takes, named as the reference graph's variables below Tacotron_model/inference/.  The name entry
+ * returns NULL and the shape entry a negative status outside 0 .. count - 1; shape_out takes up to 3 extents, the return is the rank. */
+int wrnn_taco_tensor_count(const wrnn_taco_handle *h);
+const char *wrnn_taco_tensor_name(const wrnn_taco_handle *h, int index);
+int wrnn_taco_tensor_shape(const wrnn_taco_handle *h, int index, int64_t *shape_out);
+/* One float32 tensor from host memory, C-contiguous, in the reference's own layout.  WRNN_ERR_MISSING_KEY: a name outside the table;
+ * WRNN_ERR_INVALID: another shape, or a value that is not finite. */
+int wrnn_taco_load_tensor(wrnn_taco_handle *h, const char *name, const float *data_host, int ndim, const int64_t *shape);
+/* Checks everything on the host first, then uploads the weights (first call after a load), zeroes the outputs and launches; asynchronous
+ * on `stream` but for the copies of ids, lengths and seeds.  WRNN_ERR_STATE: a tensor of the table has not been loaded (named). */
+int wrnn_taco_synthesize(wrnn_taco_handle *h, const wrnn_taco_call *call, void *stream);
+const char *wrnn_taco_last_error(const wrnn_taco_handle *h);
+void wrnn_taco_destroy(wrnn_taco_handle *h);
+
 #ifdef __cplusplus
 }
 #endif

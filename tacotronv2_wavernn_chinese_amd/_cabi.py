@@ -53,7 +53,9 @@ EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wr
                     'wrnn_pitch_create', 'wrnn_pitch_frames', 'wrnn_pitch_lags', 'wrnn_pitch_track', 'wrnn_pitch_score',
                     'wrnn_pitch_last_error', 'wrnn_pitch_destroy',
                     'wrnn_align_create', 'wrnn_align_frames', 'wrnn_align_workspace_bytes', 'wrnn_align_cost', 'wrnn_align_path',
-                    'wrnn_align_score', 'wrnn_align_last_error', 'wrnn_align_destroy')
+                    'wrnn_align_score', 'wrnn_align_last_error', 'wrnn_align_destroy',
+                    'wrnn_taco_create', 'wrnn_taco_tensor_count', 'wrnn_taco_tensor_name', 'wrnn_taco_tensor_shape', 'wrnn_taco_load_tensor',
+                    'wrnn_taco_synthesize', 'wrnn_taco_last_error', 'wrnn_taco_destroy')
 
 
 def epilogue_tables(n_classes: int, overlap: int, hop: int):
@@ -93,6 +95,29 @@ class SampleOpts(C.Structure):
                 ('seed', C.c_uint64), ('noise1_dev', C.c_void_p), ('noise2_dev', C.c_void_p), ('x_forced_dev', C.c_void_p),
                 ('logits_out_dev', C.c_void_p), ('x_init_dev', C.c_void_p), ('frames_dev', C.c_void_p),
                 ('batch_rows', C.c_int32), ('team2_segment', C.c_int32), ('utt_seeds_dev', C.c_void_p)]
+
+
+TACO_MAX_TX, TACO_MAX_PRENET = 1024, 4   # WRNN_TACO_MAX_TX, WRNN_TACO_MAX_PRENET
+
+
+class TacoDims(C.Structure):
+    """``wrnn_taco_dims``."""
+    _fields_ = [('struct_size', C.c_uint32), ('device', C.c_int32), ('n_symbols', C.c_int32), ('num_mels', C.c_int32),
+                ('outputs_per_step', C.c_int32), ('embedding_dim', C.c_int32), ('enc_conv_layers', C.c_int32), ('enc_conv_channels', C.c_int32),
+                ('enc_conv_kernel', C.c_int32), ('encoder_lstm_units', C.c_int32), ('attention_dim', C.c_int32), ('attention_filters', C.c_int32),
+                ('attention_kernel', C.c_int32), ('prenet_layers', C.c_int32), ('prenet_sizes', C.c_int32 * TACO_MAX_PRENET),
+                ('decoder_layers', C.c_int32), ('decoder_lstm_units', C.c_int32), ('postnet_layers', C.c_int32), ('postnet_channels', C.c_int32),
+                ('postnet_kernel', C.c_int32), ('zoneout', C.c_float), ('max_abs_value', C.c_float), ('lower_bound_decay', C.c_float),
+                ('bn_epsilon', C.c_float)]
+
+
+class TacoCall(C.Structure):
+    """``wrnn_taco_call``."""
+    _fields_ = [('struct_size', C.c_uint32), ('B', C.c_int32), ('Tx_max', C.c_int32), ('max_iters', C.c_int32), ('prenet_dropout', C.c_int32),
+                ('steps_max', C.c_int32), ('ids_host', C.c_void_p), ('tx_host', C.c_void_p), ('seeds_host', C.c_void_p), ('gta_dev', C.c_void_p),
+                ('gta_max', C.c_int32), ('gta_frames_host', C.c_void_p), ('encoder_dev', C.c_void_p), ('decoder_dev', C.c_void_p),
+                ('mel_raw_dev', C.c_void_p), ('mel_dev', C.c_void_p), ('alignments_dev', C.c_void_p), ('stop_dev', C.c_void_p),
+                ('max_attentions_dev', C.c_void_p), ('steps_dev', C.c_void_p), ('mel_frames_dev', C.c_void_p)]
 
 
 LOOP_PARAM_FIELDS = ('I_w', 'I_b', 'rnn1_w_ih', 'rnn1_w_hh', 'rnn1_b_ih', 'rnn1_b_hh', 'rnn2_w_ih', 'rnn2_w_hh', 'rnn2_b_ih',
@@ -570,6 +595,22 @@ def load_library() -> C.CDLL:
     lib.wrnn_align_last_error.restype = C.c_char_p
     lib.wrnn_align_destroy.argtypes = [vp]
     lib.wrnn_align_destroy.restype = None
+    lib.wrnn_taco_create.argtypes = [C.POINTER(TacoDims), C.POINTER(vp)]
+    lib.wrnn_taco_create.restype = C.c_int
+    lib.wrnn_taco_tensor_count.argtypes = [vp]
+    lib.wrnn_taco_tensor_count.restype = C.c_int
+    lib.wrnn_taco_tensor_name.argtypes = [vp, C.c_int]
+    lib.wrnn_taco_tensor_name.restype = C.c_char_p
+    lib.wrnn_taco_tensor_shape.argtypes = [vp, C.c_int, C.POINTER(C.c_int64)]
+    lib.wrnn_taco_tensor_shape.restype = C.c_int
+    lib.wrnn_taco_load_tensor.argtypes = [vp, C.c_char_p, vp, C.c_int, C.POINTER(C.c_int64)]
+    lib.wrnn_taco_load_tensor.restype = C.c_int
+    lib.wrnn_taco_synthesize.argtypes = [vp, C.POINTER(TacoCall), vp]
+    lib.wrnn_taco_synthesize.restype = C.c_int
+    lib.wrnn_taco_last_error.argtypes = [vp]
+    lib.wrnn_taco_last_error.restype = C.c_char_p
+    lib.wrnn_taco_destroy.argtypes = [vp]
+    lib.wrnn_taco_destroy.restype = None
     lib.wrnn_quantise.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp]
     lib.wrnn_quantise.restype = C.c_int
     lib.wrnn_collate_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -1399,6 +1440,52 @@ class NativeResampler:
     def close(self):
         if getattr(self, '_h', None):
             self.lib.wrnn_resample_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NativeTacotron:
+    """Owner of one ``wrnn_taco_handle`` (Tacotron-2 inference: symbol ids -> mel).  Creating it touches no device; dims the library
+    refuses raise ``WrnnError`` with its reason."""
+
+    def __init__(self, dims: TacoDims):
+        self.lib = load_library()
+        self.dims = dims
+        self._h = C.c_void_p()
+        rc = self.lib.wrnn_taco_create(C.byref(dims), C.byref(self._h))
+        if rc != 0:
+            msg = self.lib.wrnn_taco_last_error(self._h).decode() if self._h else 'wrnn_taco_create failed'
+            self.close()
+            raise WrnnError(rc, msg)
+
+    def _check(self, rc: int):
+        if rc != 0:
+            raise WrnnError(rc, self.lib.wrnn_taco_last_error(self._h).decode())
+
+    def tensor_shapes(self) -> "Dict[str, Tuple[int, ...]]":
+        """The library's own table: name -> shape, in its order."""
+        out, shape = {}, (C.c_int64 * 3)()
+        for i in range(self.lib.wrnn_taco_tensor_count(self._h)):
+            nd = self.lib.wrnn_taco_tensor_shape(self._h, i, shape)
+            out[self.lib.wrnn_taco_tensor_name(self._h, i).decode()] = tuple(int(shape[k]) for k in range(nd))
+        return out
+
+    def load_tensor(self, name: str, array: np.ndarray):
+        a = np.ascontiguousarray(array, dtype=np.float32)
+        shape = (C.c_int64 * max(a.ndim, 1))(*a.shape)
+        self._check(self.lib.wrnn_taco_load_tensor(self._h, name.encode(), a.ctypes.data, a.ndim, shape))
+
+    def synthesize(self, call: TacoCall, stream: int):
+        self._check(self.lib.wrnn_taco_synthesize(self._h, C.byref(call), stream or None))
+
+    def close(self):
+        if getattr(self, '_h', None):
+            self.lib.wrnn_taco_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

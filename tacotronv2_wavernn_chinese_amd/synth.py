@@ -133,3 +133,66 @@ def make_dm_state_dict(seed: int = 0, hidden_size: int = 896, quantisation: int 
     sd['I_coarse.weight'] = uni((3 * S, 2), 2)
     sd['I_fine.weight'] = uni((3 * S, 3), 3)
     return sd
+
+
+def make_tacotron_state(seed: int = 0, variant: str = 'default', **dims) -> "OrderedDict[str, np.ndarray]":
+    """Seeded synthetic Tacotron-2 weights keyed by the reference graph's variable names (``tacotron.Tacotron.tensor_shapes``), numpy-only
+    (PCG64) like ``make_state_dict``.  variant 'default': fan-in uniform kernels, small random biases, randomised BatchNorm statistics (so
+    the inference-mode BatchNorm is exercised), the frame projection scaled by 12 so that the decoder's frames fill the model's
+    ``[-4, 4]`` range and some of them clip.  variant 'peaked': the same, with the attention's ``v_a`` scaled by 8 so that the softmax
+    over the memory is far from flat."""
+    from .tacotron import DEFAULT_TACOTRON_DIMS
+    if variant not in ('default', 'peaked'):
+        raise ValueError(f'unknown variant {variant!r}')
+    d = dict(DEFAULT_TACOTRON_DIMS)
+    d.update(dims)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    M, r, E, C, K, H = d['num_mels'], d['outputs_per_step'], d['embedding_dim'], d['enc_conv_channels'], d['enc_conv_kernel'], d['encoder_lstm_units']
+    A, F, AK, D, PC, PK = d['attention_dim'], d['attention_filters'], d['attention_kernel'], d['decoder_lstm_units'], d['postnet_channels'], d['postnet_kernel']
+    pre = tuple(d['prenet_layers'])
+    E2 = 2 * H
+    sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
+
+    def uni(shape, fan_in, scale=1.0):
+        k = scale / np.sqrt(fan_in)
+        return rng.uniform(-k, k, size=shape).astype(np.float32)
+
+    def conv_block(p, taps, cin, cout):
+        sd[p + 'conv1d/kernel'] = uni((taps, cin, cout), taps * cin, 2.0)
+        sd[p + 'conv1d/bias'] = (0.1 * rng.standard_normal(cout)).astype(np.float32)
+        sd[p + 'batch_normalization/gamma'] = rng.uniform(0.5, 1.5, size=(cout,)).astype(np.float32)
+        sd[p + 'batch_normalization/beta'] = (0.1 * rng.standard_normal(cout)).astype(np.float32)
+        sd[p + 'batch_normalization/moving_mean'] = (0.1 * rng.standard_normal(cout)).astype(np.float32)
+        sd[p + 'batch_normalization/moving_variance'] = rng.uniform(0.5, 1.5, size=(cout,)).astype(np.float32)
+
+    def dense(p, n_in, n_out, scale=1.0, bias=True):
+        sd[p + 'kernel'] = uni((n_in, n_out), n_in, scale)
+        if bias:
+            sd[p + 'bias'] = (0.1 * rng.standard_normal(n_out)).astype(np.float32)
+
+    sd['inputs_embedding'] = rng.standard_normal((d['n_symbols'], E)).astype(np.float32)
+    for i in range(d['enc_conv_layers']):
+        conv_block(f'encoder_convolutions/conv_layer_{i + 1}_encoder_convolutions/', K, C if i else E, C)
+    for dr in ('fw', 'bw'):
+        dense(f'encoder_LSTM/bidirectional_rnn/{dr}/encoder_{dr}_LSTM/', C + H, 4 * H, 2.0)
+    dense('memory_layer/', E2, A, 1.0, bias=False)
+    n_in = M
+    for l, p in enumerate(pre):
+        dense(f'decoder/decoder_prenet/dense_{l + 1}/', n_in, p, 2.0)
+        n_in = p
+    for l in range(d['decoder_layers']):
+        dense(f'decoder/decoder_LSTM/multi_rnn_cell/cell_{l}/decoder_LSTM_{l + 1}/', (D if l else n_in + E2) + D, 4 * D, 2.0)
+    lsa = 'decoder/Location_Sensitive_Attention/'
+    dense(lsa + 'query_layer/', D, A, 1.0, bias=False)
+    sd[lsa + 'location_features_convolution/kernel'] = uni((AK, 1, F), AK, 2.0)
+    sd[lsa + 'location_features_convolution/bias'] = (0.1 * rng.standard_normal(F)).astype(np.float32)
+    dense(lsa + 'location_features_layer/', F, A, 1.0, bias=False)
+    sd[lsa + 'attention_variable_projection'] = uni((A,), A, 8.0 if variant == 'peaked' else 1.0)
+    sd[lsa + 'attention_bias'] = (0.1 * rng.standard_normal(A)).astype(np.float32)
+    dense('decoder/dense/', E2 + D, 1, 2.0)
+    dense('decoder/linear_transform_projection/projection_linear_transform_projection/', D + E2, r * M, 12.0)
+    dense('decoder/stop_token_projection/projection_stop_token_projection/', D + E2, r, 2.0)
+    for i in range(d['postnet_layers']):
+        conv_block(f'postnet_convolutions/conv_layer_{i + 1}_postnet_convolutions/', PK, PC if i else M, PC)
+    dense('postnet_projection/projection_postnet_projection/', PC, M, 1.0)
+    return sd

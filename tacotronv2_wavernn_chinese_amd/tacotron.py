@@ -1,0 +1,292 @@
+"""Tacotron-2 inference on the device: pinyin symbols -> the (T, num_mels) mel in [0, 1] that ``WaveRNN.generate`` vocodes.
+
+The model is the reference's default one (``tacotron/models/tacotron.py`` with ``ForwardLocationSensitiveAttention``), in synthesis
+mode and in GTA (teacher-forced) mode; the kernels are in ``csrc/tacotron.hip``.  Weights are an ``.npz`` keyed by the reference graph's
+variable names below ``Tacotron_model/inference/`` (``Tacotron.tensor_shapes()`` lists them with their shapes; INTEGRATION.md has the
+table).  Hanzi -> pinyin is not done here: the input is the space-separated pinyin the reference's ``get_pyin`` returns.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+
+from . import _cabi
+
+# the reference's tacotron_hparams.py
+DEFAULT_TACOTRON_DIMS = dict(n_symbols=256, num_mels=80, outputs_per_step=1, embedding_dim=128, enc_conv_layers=3, enc_conv_channels=256,
+                             enc_conv_kernel=5, encoder_lstm_units=256, attention_dim=128, attention_filters=32, attention_kernel=31,
+                             prenet_layers=(256, 256), decoder_layers=2, decoder_lstm_units=256, postnet_layers=5, postnet_channels=256,
+                             postnet_kernel=5, zoneout=0.1, max_abs_value=4.0, lower_bound_decay=0.1, bn_epsilon=1e-3)
+KEY_PREFIX = 'Tacotron_model/inference/'   # a key may carry it, and TensorFlow's ':0'
+
+
+def load_symbols(path: str) -> List[str]:
+    """The reference's ``utils/symbols.py``: ``['_', '~']`` + the sorted set of the tokens after the last ``|`` of every line of the
+    training list."""
+    chars = set()
+    with open(path, 'r', encoding='utf-8') as f:
+        for line in f:
+            for w in line.strip().split('|')[-1].strip().split(' '):
+                chars.add(w)
+    return ['_', '~'] + sorted(chars)
+
+
+def text_to_sequence(pinyin, symbols: Sequence[str]) -> List[int]:
+    """``utils/text.py:18-31``: a string is split at single spaces, tokens outside the table are dropped, ``~`` (EOS) is appended."""
+    table = {s: i for i, s in enumerate(symbols)}
+    words = pinyin.split(' ') if isinstance(pinyin, str) else pinyin
+    return [table[w] for w in words if w in table] + [table['~']]
+
+
+def make_dims(device: int = 0, **dims) -> _cabi.TacoDims:
+    d = dict(DEFAULT_TACOTRON_DIMS)
+    unknown = set(dims) - set(d)
+    if unknown:
+        raise TypeError(f'unknown Tacotron dims: {sorted(unknown)}')
+    d.update(dims)
+    pre = tuple(int(p) for p in d['prenet_layers'])
+    if not 1 <= len(pre) <= _cabi.TACO_MAX_PRENET:
+        raise _cabi.WrnnError(_cabi.ERR_INVALID, f'unsupported dims: {len(pre)} prenet layers, 1 .. {_cabi.TACO_MAX_PRENET} are served')
+    t = _cabi.TacoDims()
+    t.struct_size = C.sizeof(_cabi.TacoDims)
+    t.device = int(device)
+    for k in ('n_symbols', 'num_mels', 'outputs_per_step', 'embedding_dim', 'enc_conv_layers', 'enc_conv_channels', 'enc_conv_kernel',
+              'encoder_lstm_units', 'attention_dim', 'attention_filters', 'attention_kernel', 'decoder_layers', 'decoder_lstm_units',
+              'postnet_layers', 'postnet_channels', 'postnet_kernel'):
+        setattr(t, k, int(d[k]))
+    t.prenet_layers = len(pre)
+    for i, p in enumerate(pre):
+        t.prenet_sizes[i] = p
+    for k in ('zoneout', 'max_abs_value', 'lower_bound_decay', 'bn_epsilon'):
+        setattr(t, k, float(d[k]))
+    return t
+
+
+class Tacotron:
+    """``Tacotron(**dims)`` -> ``load(path)`` or ``load_state(dict)`` -> ``synthesize(sequences, ...)``."""
+
+    def __init__(self, device: int = 0, **dims):
+        self.dims = dict(DEFAULT_TACOTRON_DIMS)
+        self.dims.update(dims)
+        self.device = int(device)
+        self.native = _cabi.NativeTacotron(make_dims(device, **dims))
+        self.r, self.num_mels = int(self.dims['outputs_per_step']), int(self.dims['num_mels'])
+
+    def tensor_shapes(self) -> Dict[str, tuple]:
+        return self.native.tensor_shapes()
+
+    def load_state(self, state: Dict[str, np.ndarray]) -> 'Tacotron':
+        """Every tensor of the table must be there (``WRNN_ERR_MISSING_KEY`` names the first that is not); keys the model does not have
+        (the optimiser's slots of a converted checkpoint) are ignored."""
+        clean = {}
+        for k, v in state.items():
+            k = k[len(KEY_PREFIX):] if k.startswith(KEY_PREFIX) else k
+            clean[k[:-2] if k.endswith(':0') else k] = v
+        for name in self.tensor_shapes():
+            if name not in clean:
+                raise _cabi.WrnnError(-4, f'tensor {name} is missing from the checkpoint')
+            self.native.load_tensor(name, np.asarray(clean[name]))
+        return self
+
+    def load(self, path: str) -> 'Tacotron':
+        with np.load(path, allow_pickle=False) as z:
+            return self.load_state({k: z[k] for k in z.files})
+
+    def synthesize(self, sequences, seeds=None, max_iters: int = 2000, gta_targets=None, prenet_dropout: bool = True, return_device: bool = False):
+        """``sequences``: a list of id lists (a ragged batch; each utterance comes out as the call on it alone).  ``seeds``: one int per
+        utterance for its prenet dropout masks (default 0, 1, ...).  ``gta_targets``: ``None``, or one ``(T, num_mels)`` array per utterance
+        in the model's own range (``[-max_abs_value, max_abs_value]``): teacher forcing, T / r steps whatever the stop token says; a T
+        that is no multiple of r is padded with ``-max_abs_value`` rows first, as the reference's ``padding_targets`` would.
+        Returns one dict per utterance: ``mel`` (T, num_mels) in [0, 1], trimmed at the first stop token above 0.5 when free-running,
+        ``mel_raw``, ``decoder_output`` (all the frames the decoder emitted, the stopping one included), ``alignments`` (steps, Tx),
+        ``stop_tokens``, ``max_attentions``, ``steps``, ``encoder_outputs`` -- numpy arrays, or torch tensors on the device with
+        ``return_device=True`` (``mel`` then feeds ``WaveRNN.generate`` without a copy to the host)."""
+        import torch
+        seqs = [np.asarray(s, dtype=np.int64).reshape(-1) for s in sequences]
+        B = len(seqs)
+        if B < 1:
+            raise _cabi.WrnnError(_cabi.ERR_INVALID, 'no utterances')
+        tx = np.array([len(s) for s in seqs], dtype=np.int32)
+        Tx_max = int(tx.max()) if tx.size else 0
+        ids = np.zeros((B, Tx_max), dtype=np.int32)
+        for b, s in enumerate(seqs):
+            if s.size and (s.min() < -2 ** 31 or s.max() >= 2 ** 31):
+                raise _cabi.WrnnError(_cabi.ERR_INVALID, f'utterance {b}: a symbol id does not fit 32 bits')
+            ids[b, :len(s)] = s
+        seeds_a = np.array(list(range(B)) if seeds is None else [int(x) & (2 ** 64 - 1) for x in seeds], dtype=np.uint64)
+        if seeds_a.shape != (B,):
+            raise _cabi.WrnnError(_cabi.ERR_INVALID, f'{seeds_a.size} seeds for {B} utterances')
+        dev = torch.device('cuda', self.device)
+        r, M = self.r, self.num_mels
+        call = _cabi.TacoCall()
+        call.struct_size = C.sizeof(_cabi.TacoCall)
+        gta_dev = gta_frames = None
+        if gta_targets is not None:
+            if len(gta_targets) != B:
+                raise _cabi.WrnnError(_cabi.ERR_INVALID, f'{len(gta_targets)} targets for {B} utterances')
+            tg = []
+            for b, t in enumerate(gta_targets):
+                t = np.asarray(t, dtype=np.float32)
+                if t.ndim != 2 or t.shape[1] != M or t.shape[0] < 1:
+                    raise _cabi.WrnnError(_cabi.ERR_INVALID, f'target {b}: shape {t.shape}, (T >= 1, {M}) is needed')
+                if t.shape[0] % r:
+                    t = np.pad(t, [(0, r - t.shape[0] % r), (0, 0)], mode='constant', constant_values=-float(self.dims['max_abs_value']))
+                tg.append(t)
+            gta_frames = np.array([t.shape[0] for t in tg], dtype=np.int32)
+            gmax = int(gta_frames.max())
+            packed = np.zeros((B, gmax, M), dtype=np.float32)
+            for b, t in enumerate(tg):
+                packed[b, :t.shape[0]] = t
+            gta_dev = torch.from_numpy(packed).to(dev)
+            S = gmax // r
+            call.gta_dev, call.gta_max, call.gta_frames_host = gta_dev.data_ptr(), gmax, gta_frames.ctypes.data
+        else:
+            S = int(max_iters)
+            if S < 1:
+                raise _cabi.WrnnError(_cabi.ERR_INVALID, f'max_iters {max_iters} < 1')
+        E2 = 2 * int(self.dims['encoder_lstm_units'])
+        with torch.cuda.device(dev):
+            enc = torch.empty((B, Tx_max, E2), dtype=torch.float32, device=dev)
+            dec = torch.empty((B, S * r, M), dtype=torch.float32, device=dev)
+            raw, mel = torch.empty_like(dec), torch.empty_like(dec)
+            ali = torch.empty((B, S, Tx_max), dtype=torch.float32, device=dev)
+            stop = torch.empty((B, S * r), dtype=torch.float32, device=dev)
+            maxatt = torch.empty((B, S), dtype=torch.int32, device=dev)
+            steps = torch.empty((B,), dtype=torch.int32, device=dev)
+            frames = torch.empty((B,), dtype=torch.int32, device=dev)
+            call.B, call.Tx_max, call.max_iters, call.prenet_dropout, call.steps_max = B, Tx_max, max(int(max_iters), 1), int(bool(prenet_dropout)), S
+            call.ids_host, call.tx_host, call.seeds_host = ids.ctypes.data, tx.ctypes.data, seeds_a.ctypes.data
+            call.encoder_dev, call.decoder_dev, call.mel_raw_dev, call.mel_dev = enc.data_ptr(), dec.data_ptr(), raw.data_ptr(), mel.data_ptr()
+            call.alignments_dev, call.stop_dev, call.max_attentions_dev = ali.data_ptr(), stop.data_ptr(), maxatt.data_ptr()
+            call.steps_dev, call.mel_frames_dev = steps.data_ptr(), frames.data_ptr()
+            self.native.synthesize(call, torch.cuda.current_stream(dev).cuda_stream)
+            n_steps, n_frames = steps.cpu().numpy(), frames.cpu().numpy()   # the one wait of the call: the lengths the slices below need
+        out = []
+        for b in range(B):
+            n, f, t = int(n_steps[b]), int(n_frames[b]), int(tx[b])
+            res = {'mel': mel[b, :f], 'mel_raw': raw[b, :n * r], 'decoder_output': dec[b, :n * r], 'alignments': ali[b, :n, :t],
+                   'stop_tokens': stop[b, :n * r], 'max_attentions': maxatt[b, :n], 'encoder_outputs': enc[b, :t]}
+            if not return_device:
+                res = {k: v.cpu().numpy() for k, v in res.items()}
+            res['steps'], res['mel_length'] = n, f
+            out.append(res)
+        return out
+
+
+def dims_from_state(state: Dict[str, np.ndarray]) -> dict:
+    """The model's dims read off a checkpoint's tensor shapes (``zoneout`` and the clip range are not in it: the reference's values)."""
+    s = {}
+    for k, v in state.items():
+        k = k[len(KEY_PREFIX):] if k.startswith(KEY_PREFIX) else k
+        s[k[:-2] if k.endswith(':0') else k] = tuple(np.shape(v))
+
+    def count(fmt):
+        n = 0
+        while fmt.format(n + 1) in s:
+            n += 1
+        return n
+    enc, post = 'encoder_convolutions/conv_layer_{}_encoder_convolutions/conv1d/kernel', 'postnet_convolutions/conv_layer_{}_postnet_convolutions/conv1d/kernel'
+    pre, lstm = 'decoder/decoder_prenet/dense_{}/kernel', 'decoder/decoder_LSTM/multi_rnn_cell/cell_{0}/decoder_LSTM_{1}/bias'
+    n_dec = 0
+    while lstm.format(n_dec, n_dec + 1) in s:
+        n_dec += 1
+    n_pre = count(pre)
+    try:
+        M = s[pre.format(1)][0]
+        loc = s['decoder/Location_Sensitive_Attention/location_features_convolution/kernel']
+        return dict(n_symbols=s['inputs_embedding'][0], embedding_dim=s['inputs_embedding'][1], num_mels=M,
+                    outputs_per_step=s['decoder/stop_token_projection/projection_stop_token_projection/bias'][0],
+                    enc_conv_layers=count(enc), enc_conv_kernel=s[enc.format(1)][0], enc_conv_channels=s[enc.format(1)][2],
+                    encoder_lstm_units=s['encoder_LSTM/bidirectional_rnn/fw/encoder_fw_LSTM/bias'][0] // 4,
+                    attention_dim=s['memory_layer/kernel'][1], attention_kernel=loc[0], attention_filters=loc[2],
+                    prenet_layers=tuple(s[pre.format(i + 1)][1] for i in range(n_pre)), decoder_layers=n_dec,
+                    decoder_lstm_units=s[lstm.format(0, 1)][0] // 4, postnet_layers=count(post), postnet_kernel=s[post.format(1)][0],
+                    postnet_channels=s[post.format(1)][2])
+    except KeyError as e:
+        raise _cabi.WrnnError(-4, f'tensor {e.args[0]} is missing from the checkpoint') from None
+
+
+def checkpoint_step(path: str) -> str:
+    """``tacotron_synthesize.py:192``: what follows the last ``-`` of the checkpoint's name (``tacotron_model.ckpt-150000`` -> ``150000``)."""
+    import os
+    return os.path.splitext(os.path.basename(path))[0].split('-')[-1].strip()
+
+
+def synthesize_to_file(model: Tacotron, pinyin: str, symbols: Sequence[str], out_dir: str, step: str, seed: int = 0, max_iters: int = 2000,
+                       gta_target=None, return_device: bool = False):
+    """``Synthesizer.synthesize`` of ``tacotron_synthesize.py``: writes ``step-{step}-{md5 of the text}-mel-pred.npy``, the (T, num_mels) mel
+    in [0, 1] that ``wavernn_gen.py --file`` reads.  Returns (path, the call's result)."""
+    import hashlib
+    import os
+    seq = text_to_sequence(pinyin.split(' '), symbols)
+    res = model.synthesize([seq], seeds=[seed], max_iters=max_iters, gta_targets=None if gta_target is None else [gta_target],
+                           return_device=return_device)[0]
+    idx = hashlib.md5(pinyin.encode('utf-8')).hexdigest()
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, f'step-{step}-{idx}-mel-pred.npy')
+    mel = res['mel']
+    np.save(path, mel.cpu().numpy() if return_device else mel, allow_pickle=False)
+    return path, res
+
+
+def build_parser():
+    import argparse
+    p = argparse.ArgumentParser(description='Tacotron-2 on the device: pinyin -> the mel wavernn_gen.py vocodes')
+    p.add_argument('--pinyin', required=True, help='space-separated pinyin tokens with tone digits and punctuation, as the reference\'s get_pyin returns them')
+    p.add_argument('--symbols', required=True, metavar='FILE', help='the training list (the tokens after the last | of every line make the symbol table)')
+    p.add_argument('--checkpoint', required=True, metavar='NPZ', help='the weights, keyed by the reference graph\'s variable names (INTEGRATION.md "From text")')
+    p.add_argument('--gta', metavar='MEL.npy', default=None, help='teacher-force on this (T, num_mels) target in [-4, 4]: the GTA mel a WaveRNN is trained on')
+    p.add_argument('--seed', type=int, default=0, help='keys the prenet dropout masks')
+    p.add_argument('--max_iters', type=int, default=2000)
+    p.add_argument('--out_dir', default='./tacotron_inference_output')
+    p.add_argument('--vocode', metavar='WAVERNN.pyt', default=None, help='also vocode the mel with these WaveRNN weights (the mel stays on the device)')
+    p.add_argument('--griffin_lim', type=int, nargs='?', const=60, default=None, metavar='N_ITER', help='also vocode the mel by Griffin-Lim (no model)')
+    return p
+
+
+def main(argv=None):
+    import os
+    import torch
+    args = build_parser().parse_args(argv)
+    if not torch.cuda.is_available():
+        raise RuntimeError('Tacotron runs on an MI355X only (no CPU path)')
+    symbols = load_symbols(args.symbols)
+    with np.load(args.checkpoint, allow_pickle=False) as z:
+        state = {k: z[k] for k in z.files}
+    dims = dims_from_state(state)
+    if dims['n_symbols'] != len(symbols):
+        raise ValueError(f'{args.symbols} makes {len(symbols)} symbols, the checkpoint\'s embedding has {dims["n_symbols"]} rows')
+    model = Tacotron(**dims).load_state(state)
+    target = np.load(args.gta) if args.gta else None
+    path, res = synthesize_to_file(model, args.pinyin, symbols, args.out_dir, checkpoint_step(args.checkpoint), seed=args.seed,
+                                   max_iters=args.max_iters, gta_target=target, return_device=True)
+    print(f'{res["steps"]} decoder steps, {res["mel_length"]} mel frames -> {path}')
+    mel = res['mel']
+    stem = path[:-len('-mel-pred.npy')]
+    if args.vocode:
+        from .gen import build_model_from_hparams
+        from .hparams import hparams as hp
+        if not hp.is_configured():
+            hp.configure()
+        voc = build_model_from_hparams().to(mel.device)
+        voc.load(args.vocode)
+        voc.generate(mel.T[None].contiguous(), stem + '-wavernn.wav', False, hp.voc_target, hp.voc_overlap, hp.mu_law)
+        print(stem + '-wavernn.wav')
+    if args.griffin_lim is not None:
+        from .dsp import save_wav
+        from .frontend import GriffinLim
+        gl = GriffinLim(features='tacotron', n_iter=int(args.griffin_lim), device=mel.device)
+        out = gl.reconstruct(mel.T.contiguous(), seed=args.seed, device=mel.device)
+        wav = out[0, :gl.last_samples[0]].cpu().numpy()
+        peak = float(np.abs(wav).max()) if wav.size else 0.0
+        if peak > 1.0:
+            wav = wav * np.float32(0.999 / peak)
+        save_wav(wav, stem + '-griffin_lim.wav', gl.sample_rate)
+        print(stem + '-griffin_lim.wav')
+    return path
+
+
+if __name__ == '__main__':
+    main()
