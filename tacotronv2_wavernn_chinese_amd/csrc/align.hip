@@ -20,15 +20,13 @@
 // The backtrack is one lane's chain of at most Ta + Tb - 1 dependent byte reads; every step lowers i + j and stays inside the matrix
 // whatever the bytes hold, and the loop has that bound of its own.  It writes the path backwards into scratch; the workgroup reverses it.
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include <hip/hip_runtime.h>
-
-#include "../../include/wavernn_amd.h"
+#include "dsp_device.h"
+#include "dsp_tables.h"
+#include "handle_common.h"
 
 namespace {
 
@@ -290,25 +288,6 @@ __global__ void __launch_bounds__(THREADS) align_along_kernel(AlignAlongArgs g) 
     g.pp[((long)b * 2 + 1) * P_max + p] = cents;
 }
 
-// The sums of N values per thread, to every thread: one fixed pairwise tree over the thread index for all N (acc holds N * THREADS).
-template <int N>
-__device__ inline void block_sums(double (&v)[N], double *acc) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < N; ++k) acc[k * THREADS + tid] = v[k];
-    for (int d = THREADS / 2; d > 0; d >>= 1) {
-        __syncthreads();
-        if (tid < d) {
-#pragma unroll
-            for (int k = 0; k < N; ++k) acc[k * THREADS + tid] += acc[k * THREADS + tid + d];
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = acc[k * THREADS];
-    __syncthreads();
-}
-
 // One workgroup per pair.  Thread i takes path pairs i, i + 256, ... in ascending order, then the threads are added in a fixed tree: the
 // order depends on a pair's place on the path alone.  Two passes, as the pitch summaries: the counts, the squares and the means of
 // log2 f0, then the central moments.
@@ -338,7 +317,7 @@ __global__ void __launch_bounds__(THREADS) align_summary_kernel(AlignAlongArgs g
         }
     }
     double first[7] = {n_v, n_vde, n_gpe, c2, lt, ls, sl};
-    block_sums(first, acc);
+    block_sums<THREADS>(first, acc);
     n_v = first[0]; n_vde = first[1]; n_gpe = first[2]; c2 = first[3]; lt = first[4]; ls = first[5]; sl = first[6];
     const double mt = n_v > 0.0 ? lt / n_v : 0.0, ms = n_v > 0.0 ? ls / n_v : 0.0;
     double cov = 0.0, var_t = 0.0, var_s = 0.0;
@@ -355,7 +334,7 @@ __global__ void __launch_bounds__(THREADS) align_summary_kernel(AlignAlongArgs g
         }
     }
     double second[3] = {cov, var_t, var_s};
-    block_sums(second, acc);
+    block_sums<THREADS>(second, acc);
     cov = second[0]; var_t = second[1]; var_s = second[2];
     if (tid != 0) return;
     double *o = g.summary + (long)b * WRNN_ALIGN_FIELDS;
@@ -389,34 +368,14 @@ struct wrnn_align_handle {
     bool ok = false;                  // false while the configuration is refused
     int min_samples = 0;              // the shortest clip the front end can pad
     wrnn_mel_handle *mel = nullptr;   // the front end the mels come from: its own handle, its own launch path
-    std::vector<float> dct;           // (K, n_mels): wrnn_score_tables' dct
-    float *dct_dev = nullptr;         // its transpose, uploaded by the first call that needs it
+    std::vector<float> dct;           // (K, n_mels): dsp_tables.h's rows rounded to float32, what wrnn_score_tables hands out
+    void *dct_dev = nullptr;          // its transpose, uploaded by the first call that needs it
     bool lds_set = false;             // the DP kernel's dynamic LDS limit is raised once
-    char *ws = nullptr;               // the scratch of a call, grown on demand
-    size_t ws_cap = 0;
+    WrnnScratch ws;                   // the scratch of a call, grown on demand
     std::string err;
 };
 
 namespace {
-int al_fail(wrnn_align_handle *h, int code, const char *fmt, ...) {
-    char buf[400];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (h) h->err = buf;
-    return code;
-}
-#define AL_TRY(h, expr)                                                                                   \
-    do {                                                                                                  \
-        hipError_t e__ = (expr);                                                                          \
-        if (e__ != hipSuccess) return al_fail((h), WRNN_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e__)); \
-    } while (0)
-const int AL_MAX_B = 65535;   // grid.y and grid.z
-const wrnn_mel_features AL_DEFAULT_FEATURES = {(uint32_t)sizeof(wrnn_mel_features), WRNN_MEL_PAD_REFLECT, 1, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // The scratch of a call over (B, Ta_max, Tb_max), region by region; a call takes the regions it needs, in this order.
 struct AlLayout {
     size_t mel_a = 0, mel_b = 0, cep_a = 0, cep_b = 0, frames = 0, cost = 0, choice = 0, rev = 0, path = 0, plen = 0, total = 0, pp = 0, bytes = 0;
@@ -428,7 +387,7 @@ AlLayout al_layout(const wrnn_align_handle *h, int64_t B, int64_t Ta, int64_t Tb
     size_t at = 0;
     auto take = [&at](size_t bytes) {
         const size_t o = at;
-        at += up256(bytes);
+        at += wrnn_up256(bytes);
         return o;
     };
     const size_t n_mels = (size_t)h->cfg.n_mels, K = (size_t)h->acfg.mcd_order, P = (size_t)(Ta + Tb - 1);
@@ -456,28 +415,15 @@ AlLayout al_layout(const wrnn_align_handle *h, int64_t B, int64_t Ta, int64_t Tb
 
 // WRNN_OK, or the status and the text of the refusal of a call over (B, Ta_max, Tb_max) frames.
 int al_check_shape(wrnn_align_handle *h, int64_t B, int64_t Ta, int64_t Tb) {
-    if (B < 1 || B > AL_MAX_B || Ta < 1 || Tb < 1 || Ta > INT32_MAX / 2 || Tb > INT32_MAX / 2)
-        return al_fail(h, WRNN_ERR_INVALID, "bad shape: 1 <= B <= %d, Ta_max and Tb_max at least 1, got B = %lld, Ta_max = %lld, Tb_max = %lld", AL_MAX_B,
+    if (B < 1 || B > WRNN_MAX_GRID_Y || Ta < 1 || Tb < 1 || Ta > INT32_MAX / 2 || Tb > INT32_MAX / 2)
+        return wrnn_failf(h, WRNN_ERR_INVALID, "bad shape: 1 <= B <= %d, Ta_max and Tb_max at least 1, got B = %lld, Ta_max = %lld, Tb_max = %lld", WRNN_MAX_GRID_Y,
                        (long long)B, (long long)Ta, (long long)Tb);
     if ((Ta < Tb ? Ta : Tb) > DP_MAX_SIDE)
-        return al_fail(h, WRNN_ERR_UNSUPPORTED, "min(Ta_max, Tb_max) = %lld frames: three float64 anti-diagonals of the shorter side fit the LDS up to %d frames",
+        return wrnn_failf(h, WRNN_ERR_UNSUPPORTED, "min(Ta_max, Tb_max) = %lld frames: three float64 anti-diagonals of the shorter side fit the LDS up to %d frames",
                        (long long)(Ta < Tb ? Ta : Tb), DP_MAX_SIDE);
     if (Ta * Tb > MAX_CELLS || B * Ta * Tb > MAX_CELLS)
-        return al_fail(h, WRNN_ERR_UNSUPPORTED, "B Ta_max Tb_max = %lld x %lld x %lld cells: a call holds at most 2^28 (32-bit cell indices, 1 GiB of costs)",
+        return wrnn_failf(h, WRNN_ERR_UNSUPPORTED, "B Ta_max Tb_max = %lld x %lld x %lld cells: a call holds at most 2^28 (32-bit cell indices, 1 GiB of costs)",
                        (long long)B, (long long)Ta, (long long)Tb);
-    return WRNN_OK;
-}
-
-int al_grow(wrnn_align_handle *h, size_t need, hipStream_t s) {
-    if (need <= h->ws_cap) return WRNN_OK;
-    if (h->ws) {
-        AL_TRY(h, hipStreamSynchronize(s));   // growing is the one wait: an earlier call may still read the old buffer
-        AL_TRY(h, hipFree(h->ws));
-        h->ws = nullptr;
-        h->ws_cap = 0;
-    }
-    AL_TRY(h, hipMalloc((void **)&h->ws, need));
-    h->ws_cap = need;
     return WRNN_OK;
 }
 
@@ -488,51 +434,46 @@ int al_launch_cost(wrnn_align_handle *h, const AlLayout &l, const float *target_
                    int64_t nb_max, const int32_t *nb_dev, int B, int Ta, int Tb, float *cost, hipStream_t s) {
     const int n_mels = h->cfg.n_mels, K = h->acfg.mcd_order;
     if (!h->dct_dev) {
-        std::vector<float> t((size_t)n_mels * K);
+        WrnnImage img;
+        float *t = img.at<float>(img.take((size_t)n_mels * K * 4));
         for (int k = 0; k < K; ++k)
             for (int m = 0; m < n_mels; ++m) t[(size_t)m * K + k] = h->dct[(size_t)k * n_mels + m];
-        float *d = nullptr;
-        AL_TRY(h, hipMalloc((void **)&d, t.size() * 4));
-        hipError_t e = hipMemcpy(d, t.data(), t.size() * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(d);
-            return al_fail(h, WRNN_ERR_HIP, "uploading the DCT table: %s", hipGetErrorString(e));
-        }
-        h->dct_dev = d;
+        const hipError_t e = img.upload(&h->dct_dev);
+        if (e != hipSuccess) return wrnn_failf(h, WRNN_ERR_HIP, "uploading the DCT table: %s", hipGetErrorString(e));
     }
-    float *mel_a = (float *)(h->ws + l.mel_a), *mel_b = (float *)(h->ws + l.mel_b);
+    float *mel_a = (float *)(h->ws.p + l.mel_a), *mel_b = (float *)(h->ws.p + l.mel_b);
     if (wrnn_melspectrogram(h->mel, target_dev, na_max, na_dev, B, Ta, mel_a, (void *)s) != WRNN_OK ||
         wrnn_melspectrogram(h->mel, test_dev, nb_max, nb_dev, B, Tb, mel_b, (void *)s) != WRNN_OK)
-        return al_fail(h, WRNN_ERR_HIP, "the mel front end: %s", wrnn_mel_last_error(h->mel));
+        return wrnn_failf(h, WRNN_ERR_HIP, "the mel front end: %s", wrnn_mel_last_error(h->mel));
     AlignCepArgs c{};
     c.mel[0] = mel_a; c.mel[1] = mel_b; c.n_samples[0] = na_dev; c.n_samples[1] = nb_dev;
-    c.cep[0] = (float *)(h->ws + l.cep_a); c.cep[1] = (float *)(h->ws + l.cep_b);
-    c.frames[0] = (int32_t *)(h->ws + l.frames); c.frames[1] = c.frames[0] + B;
-    c.dct_t = h->dct_dev; c.n_max[0] = na_max; c.n_max[1] = nb_max; c.T_max[0] = Ta; c.T_max[1] = Tb;
+    c.cep[0] = (float *)(h->ws.p + l.cep_a); c.cep[1] = (float *)(h->ws.p + l.cep_b);
+    c.frames[0] = (int32_t *)(h->ws.p + l.frames); c.frames[1] = c.frames[0] + B;
+    c.dct_t = (const float *)h->dct_dev; c.n_max[0] = na_max; c.n_max[1] = nb_max; c.T_max[0] = Ta; c.T_max[1] = Tb;
     c.n_mels = n_mels; c.hop = h->cfg.hop_length; c.K = K; c.min_samples = h->min_samples;
     c.scale = (double)(-h->cfg.min_level_db) * (2.302585092994046 / 20.0);
     const int T = Ta > Tb ? Ta : Tb;
     hipLaunchKernelGGL(align_cep_kernel, dim3((unsigned)((T + MAX_WAVES - 1) / MAX_WAVES), (unsigned)B, 2u), dim3(THREADS), 0, s, c);
-    AL_TRY(h, hipGetLastError());
+    WRNN_TRY(h, hipGetLastError());
     AlignCostArgs a{};
     a.cep_a = c.cep[0]; a.cep_b = c.cep[1]; a.ta = c.frames[0]; a.tb = c.frames[1]; a.cost = cost; a.Ta_max = Ta; a.Tb_max = Tb; a.K = K;
     const size_t lds = (size_t)2 * TILE * (K | 1) * 4;   // at most 2 x 32 x 127 floats = 32 KiB
     hipLaunchKernelGGL(align_cost_kernel, dim3((unsigned)((Tb + TILE - 1) / TILE), (unsigned)((Ta + TILE - 1) / TILE), (unsigned)B), dim3(THREADS), lds, s, a);
-    AL_TRY(h, hipGetLastError());
+    WRNN_TRY(h, hipGetLastError());
     return WRNN_OK;
 }
 
 int al_launch_dp(wrnn_align_handle *h, const AlLayout &l, const float *cost, const int32_t *ta, const int32_t *tb, int B, int Ta, int Tb, int2 *path,
                  int32_t *path_len, double *total, hipStream_t s) {
     AlignDpArgs d{};
-    d.cost = cost; d.ta = ta; d.tb = tb; d.choice = (uint8_t *)(h->ws + l.choice); d.rev = (int2 *)(h->ws + l.rev);
+    d.cost = cost; d.ta = ta; d.tb = tb; d.choice = (uint8_t *)(h->ws.p + l.choice); d.rev = (int2 *)(h->ws.p + l.rev);
     d.path = path; d.path_len = path_len; d.total = total; d.Ta_max = Ta; d.Tb_max = Tb; d.L = Ta < Tb ? Ta : Tb;
     if (!h->lds_set) {
-        AL_TRY(h, hipFuncSetAttribute((const void *)align_dp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * DP_MAX_SIDE * 8));
+        WRNN_TRY(h, hipFuncSetAttribute((const void *)align_dp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * DP_MAX_SIDE * 8));
         h->lds_set = true;
     }
     hipLaunchKernelGGL(align_dp_kernel, dim3((unsigned)B), dim3(THREADS), (size_t)3 * d.L * 8, s, d);
-    AL_TRY(h, hipGetLastError());
+    WRNN_TRY(h, hipGetLastError());
     return WRNN_OK;
 }
 }  // namespace
@@ -544,31 +485,20 @@ int wrnn_align_create(const wrnn_mel_config *cfg, const wrnn_mel_features *f, co
     wrnn_align_handle *h = new wrnn_align_handle();
     *out = h;
     h->cfg = *cfg;
-    if (!f) f = &AL_DEFAULT_FEATURES;
+    if (!f) f = &WRNN_DEFAULT_MEL_FEATURES;
     if (ac->struct_size != sizeof(wrnn_align_config))
-        return al_fail(h, WRNN_ERR_INVALID, "align.struct_size = %u, this library's wrnn_align_config has %zu bytes", ac->struct_size, sizeof(wrnn_align_config));
+        return wrnn_failf(h, WRNN_ERR_INVALID, "align.struct_size = %u, this library's wrnn_align_config has %zu bytes", ac->struct_size, sizeof(wrnn_align_config));
     h->acfg = *ac;
     // the front end checks its own configuration (struct_size of the features included) and builds its own tables; no device is touched
     const int rc = wrnn_mel_create_features(cfg, f, &h->mel);
-    if (rc != WRNN_OK) return al_fail(h, rc, "%s", h->mel ? wrnn_mel_last_error(h->mel) : "wrnn_mel_create_features failed");
+    if (rc != WRNN_OK) return wrnn_failf(h, rc, "%s", h->mel ? wrnn_mel_last_error(h->mel) : "wrnn_mel_create_features failed");
     h->feat = *f;
     if (ac->mcd_order < 1 || ac->mcd_order > cfg->n_mels - 1)
-        return al_fail(h, WRNN_ERR_INVALID, "mcd_order = %d: 1 <= mcd_order <= n_mels - 1 = %d", ac->mcd_order, cfg->n_mels - 1);
-    if (!(ac->gpe_ratio > 0.0) || !std::isfinite(ac->gpe_ratio)) return al_fail(h, WRNN_ERR_INVALID, "gpe_ratio = %g: finite and above 0", ac->gpe_ratio);
-    // the DCT rows are the score section's own: a score handle of one small resolution builds them and hands them over
-    wrnn_score_config sc{};
-    sc.struct_size = (uint32_t)sizeof(wrnn_score_config);
-    sc.n_res = 1; sc.n_fft[0] = 256; sc.hop[0] = 64; sc.win[0] = 256; sc.mag_floor = 1e-7f; sc.mcd_order = ac->mcd_order;
-    wrnn_score_handle *sh = nullptr;
-    const int rs = wrnn_score_create(cfg, f, &sc, &sh);
-    if (rs == WRNN_OK) {
-        h->dct.resize((size_t)ac->mcd_order * cfg->n_mels);
-        wrnn_score_tables(sh, 0, nullptr, nullptr, h->dct.data());
-    } else {
-        al_fail(h, rs, "the DCT table: %s", sh ? wrnn_score_last_error(sh) : "wrnn_score_create failed");
-    }
-    if (sh) wrnn_score_destroy(sh);
-    if (rs != WRNN_OK) return rs;
+        return wrnn_failf(h, WRNN_ERR_INVALID, "mcd_order = %d: 1 <= mcd_order <= n_mels - 1 = %d", ac->mcd_order, cfg->n_mels - 1);
+    if (!(ac->gpe_ratio > 0.0) || !std::isfinite(ac->gpe_ratio)) return wrnn_failf(h, WRNN_ERR_INVALID, "gpe_ratio = %g: finite and above 0", ac->gpe_ratio);
+    // the DCT rows are the score section's own: the same builder, the same one rounding to float32
+    const std::vector<double> dct = wrnn_dsp::dct_rows(cfg->n_mels, ac->mcd_order);
+    h->dct.assign(dct.begin(), dct.end());
     h->min_samples = f->pad_mode == WRNN_MEL_PAD_REFLECT ? cfg->n_fft / 2 + 1 : 1;
     h->ok = true;
     return WRNN_OK;
@@ -581,9 +511,9 @@ int64_t wrnn_align_frames(const wrnn_align_handle *h, int64_t n) {
 
 int64_t wrnn_align_workspace_bytes(wrnn_align_handle *h, int32_t B, int64_t na_max, int64_t nb_max) {
     if (!h) return WRNN_ERR_INVALID;
-    if (!h->ok) return al_fail(h, WRNN_ERR_STATE, "the handle's configuration was refused by wrnn_align_create");
+    if (!h->ok) return wrnn_failf(h, WRNN_ERR_STATE, "the handle's configuration was refused by wrnn_align_create");
     if (na_max < h->min_samples || nb_max < h->min_samples || na_max > INT32_MAX || nb_max > INT32_MAX)
-        return al_fail(h, WRNN_ERR_INVALID, "bad arguments: %d <= na_max, nb_max < 2^31", h->min_samples);
+        return wrnn_failf(h, WRNN_ERR_INVALID, "bad arguments: %d <= na_max, nb_max < 2^31", h->min_samples);
     const int64_t Ta = al_frames(h, na_max), Tb = al_frames(h, nb_max);
     const int rc = al_check_shape(h, B, Ta, Tb);
     if (rc != WRNN_OK) return rc;
@@ -593,34 +523,32 @@ int64_t wrnn_align_workspace_bytes(wrnn_align_handle *h, int32_t B, int64_t na_m
 int wrnn_align_cost(wrnn_align_handle *h, const float *target_dev, int64_t na_max, const int32_t *na_dev, const float *test_dev, int64_t nb_max,
                     const int32_t *nb_dev, int32_t B, float *cost_dev, void *stream) {
     if (!h) return WRNN_ERR_INVALID;
-    if (!h->ok) return al_fail(h, WRNN_ERR_STATE, "the handle's configuration was refused by wrnn_align_create");
+    if (!h->ok) return wrnn_failf(h, WRNN_ERR_STATE, "the handle's configuration was refused by wrnn_align_create");
     if (!target_dev || !test_dev || !na_dev || !nb_dev || !cost_dev || na_max < h->min_samples || nb_max < h->min_samples || na_max > INT32_MAX ||
         nb_max > INT32_MAX)
-        return al_fail(h, WRNN_ERR_INVALID, "bad arguments: device pointers, %d <= na_max, nb_max < 2^31", h->min_samples);
+        return wrnn_failf(h, WRNN_ERR_INVALID, "bad arguments: device pointers, %d <= na_max, nb_max < 2^31", h->min_samples);
     const int64_t Ta = al_frames(h, na_max), Tb = al_frames(h, nb_max);
     const int rc = al_check_shape(h, B, Ta, Tb);
     if (rc != WRNN_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    AL_TRY(h, hipSetDevice(h->cfg.device));
+    WRNN_TRY(h, hipSetDevice(h->cfg.device));
     const AlLayout l = al_layout(h, B, Ta, Tb, AL_MELS);
-    const int rg = al_grow(h, l.bytes, s);
-    if (rg != WRNN_OK) return rg;
+    WRNN_TRY(h, h->ws.reserve(l.bytes, s));
     return al_launch_cost(h, l, target_dev, na_max, na_dev, test_dev, nb_max, nb_dev, B, (int)Ta, (int)Tb, cost_dev, s);
 }
 
 int wrnn_align_path(wrnn_align_handle *h, const float *cost_dev, int32_t B, int32_t Ta_max, int32_t Tb_max, const int32_t *ta_dev, const int32_t *tb_dev,
                     int32_t *path_dev, int32_t *path_len_dev, double *total_dev, void *stream) {
     if (!h) return WRNN_ERR_INVALID;
-    if (!h->ok) return al_fail(h, WRNN_ERR_STATE, "the handle's configuration was refused by wrnn_align_create");
+    if (!h->ok) return wrnn_failf(h, WRNN_ERR_STATE, "the handle's configuration was refused by wrnn_align_create");
     if (!cost_dev || !ta_dev || !tb_dev || !path_dev || !path_len_dev || !total_dev)
-        return al_fail(h, WRNN_ERR_INVALID, "bad arguments: cost_dev, ta_dev, tb_dev, path_dev, path_len_dev and total_dev are device pointers");
+        return wrnn_failf(h, WRNN_ERR_INVALID, "bad arguments: cost_dev, ta_dev, tb_dev, path_dev, path_len_dev and total_dev are device pointers");
     const int rc = al_check_shape(h, B, Ta_max, Tb_max);
     if (rc != WRNN_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    AL_TRY(h, hipSetDevice(h->cfg.device));
+    WRNN_TRY(h, hipSetDevice(h->cfg.device));
     const AlLayout l = al_layout(h, B, Ta_max, Tb_max, AL_DP);
-    const int rg = al_grow(h, l.bytes, s);
-    if (rg != WRNN_OK) return rg;
+    WRNN_TRY(h, h->ws.reserve(l.bytes, s));
     return al_launch_dp(h, l, cost_dev, ta_dev, tb_dev, B, Ta_max, Tb_max, (int2 *)path_dev, path_len_dev, total_dev, s);
 }
 
@@ -628,52 +556,51 @@ int wrnn_align_score(wrnn_align_handle *h, const float *target_dev, int64_t na_m
                      const int32_t *nb_dev, int32_t B, const float *f0_target_dev, const float *f0_test_dev, int64_t f0_stride, double *summary_dev,
                      int32_t *path_dev, int32_t *path_len_dev, double *per_path_dev, void *stream) {
     if (!h) return WRNN_ERR_INVALID;
-    if (!h->ok) return al_fail(h, WRNN_ERR_STATE, "the handle's configuration was refused by wrnn_align_create");
+    if (!h->ok) return wrnn_failf(h, WRNN_ERR_STATE, "the handle's configuration was refused by wrnn_align_create");
     if (!target_dev || !test_dev || !na_dev || !nb_dev || !summary_dev || na_max < h->min_samples || nb_max < h->min_samples || na_max > INT32_MAX ||
         nb_max > INT32_MAX)
-        return al_fail(h, WRNN_ERR_INVALID, "bad arguments: device pointers, %d <= na_max, nb_max < 2^31", h->min_samples);
+        return wrnn_failf(h, WRNN_ERR_INVALID, "bad arguments: device pointers, %d <= na_max, nb_max < 2^31", h->min_samples);
     if ((f0_target_dev == nullptr) != (f0_test_dev == nullptr))
-        return al_fail(h, WRNN_ERR_INVALID, "f0_target_dev and f0_test_dev are both NULL or both set");
+        return wrnn_failf(h, WRNN_ERR_INVALID, "f0_target_dev and f0_test_dev are both NULL or both set");
     const int64_t Ta = al_frames(h, na_max), Tb = al_frames(h, nb_max);
     if (f0_target_dev && f0_stride < (Ta > Tb ? Ta : Tb))
-        return al_fail(h, WRNN_ERR_INVALID, "f0_stride = %lld: a row of the F0 tracks holds max(Ta_max, Tb_max) = %lld frames", (long long)f0_stride,
+        return wrnn_failf(h, WRNN_ERR_INVALID, "f0_stride = %lld: a row of the F0 tracks holds max(Ta_max, Tb_max) = %lld frames", (long long)f0_stride,
                        (long long)(Ta > Tb ? Ta : Tb));
     const int rc = al_check_shape(h, B, Ta, Tb);
     if (rc != WRNN_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    AL_TRY(h, hipSetDevice(h->cfg.device));
+    WRNN_TRY(h, hipSetDevice(h->cfg.device));
     const AlLayout l = al_layout(h, B, Ta, Tb, AL_MELS | AL_COST | AL_DP | AL_PATH | AL_ALONG);
-    const int rg = al_grow(h, l.bytes, s);
-    if (rg != WRNN_OK) return rg;
-    int r = al_launch_cost(h, l, target_dev, na_max, na_dev, test_dev, nb_max, nb_dev, B, (int)Ta, (int)Tb, (float *)(h->ws + l.cost), s);
+    WRNN_TRY(h, h->ws.reserve(l.bytes, s));
+    int r = al_launch_cost(h, l, target_dev, na_max, na_dev, test_dev, nb_max, nb_dev, B, (int)Ta, (int)Tb, (float *)(h->ws.p + l.cost), s);
     if (r != WRNN_OK) return r;
-    const int32_t *ta = (const int32_t *)(h->ws + l.frames), *tb = ta + B;
-    int2 *path = path_dev ? (int2 *)path_dev : (int2 *)(h->ws + l.path);
-    int32_t *plen = path_len_dev ? path_len_dev : (int32_t *)(h->ws + l.plen);
-    double *total = (double *)(h->ws + l.total);
-    r = al_launch_dp(h, l, (const float *)(h->ws + l.cost), ta, tb, B, (int)Ta, (int)Tb, path, plen, total, s);
+    const int32_t *ta = (const int32_t *)(h->ws.p + l.frames), *tb = ta + B;
+    int2 *path = path_dev ? (int2 *)path_dev : (int2 *)(h->ws.p + l.path);
+    int32_t *plen = path_len_dev ? path_len_dev : (int32_t *)(h->ws.p + l.plen);
+    double *total = (double *)(h->ws.p + l.total);
+    r = al_launch_dp(h, l, (const float *)(h->ws.p + l.cost), ta, tb, B, (int)Ta, (int)Tb, path, plen, total, s);
     if (r != WRNN_OK) return r;
     AlignAlongArgs g{};
-    g.mel_a = (const float *)(h->ws + l.mel_a); g.mel_b = (const float *)(h->ws + l.mel_b); g.path = path; g.path_len = plen;
-    g.f0_a = f0_target_dev; g.f0_b = f0_test_dev; g.pp = per_path_dev ? per_path_dev : (double *)(h->ws + l.pp); g.ta = ta; g.tb = tb; g.total = total;
+    g.mel_a = (const float *)(h->ws.p + l.mel_a); g.mel_b = (const float *)(h->ws.p + l.mel_b); g.path = path; g.path_len = plen;
+    g.f0_a = f0_target_dev; g.f0_b = f0_test_dev; g.pp = per_path_dev ? per_path_dev : (double *)(h->ws.p + l.pp); g.ta = ta; g.tb = tb; g.total = total;
     g.summary = summary_dev; g.f0_stride = f0_stride; g.Ta_max = (int)Ta; g.Tb_max = (int)Tb; g.n_mels = h->cfg.n_mels;
     g.range_db = (double)(-h->cfg.min_level_db); g.gpe_ratio = h->acfg.gpe_ratio;
     const int P_max = (int)(Ta + Tb - 1);
     hipLaunchKernelGGL(align_along_kernel, dim3((unsigned)((P_max + THREADS - 1) / THREADS), (unsigned)B), dim3(THREADS), 0, s, g);
-    AL_TRY(h, hipGetLastError());
+    WRNN_TRY(h, hipGetLastError());
     hipLaunchKernelGGL(align_summary_kernel, dim3((unsigned)B), dim3(THREADS), 0, s, g);
-    AL_TRY(h, hipGetLastError());
+    WRNN_TRY(h, hipGetLastError());
     return WRNN_OK;
 }
 
-const char *wrnn_align_last_error(const wrnn_align_handle *h) { return h ? h->err.c_str() : "null handle"; }
+const char *wrnn_align_last_error(const wrnn_align_handle *h) { return wrnn_last_error_of(h); }
 
 void wrnn_align_destroy(wrnn_align_handle *h) {
     if (!h) return;
-    if (h->dct_dev || h->ws) {
+    if (h->dct_dev || h->ws.p) {
         (void)hipSetDevice(h->cfg.device);
         if (h->dct_dev) (void)hipFree(h->dct_dev);
-        if (h->ws) (void)hipFree(h->ws);
+        h->ws.release();
     }
     if (h->mel) wrnn_mel_destroy(h->mel);
     delete h;

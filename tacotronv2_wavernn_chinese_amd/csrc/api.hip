@@ -4,8 +4,6 @@
 // enqueueing kernels on the caller's stream.
 #include <climits>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -130,18 +128,18 @@ int wrnn_create(const wrnn_config *cfg, wrnn_handle **out) {
     *out = h;  // from here on errors are reported through the handle
     // Any constructor dims (fatchord_version.py:93-129) run on the SIMPLE kernel as long as its activation vectors fit a
     // CU's LDS; the team kernels (TEAM2, BATCH) are built for the reference hparams (wavernn_hparams.py:18-57).
-    if (const char *why = wrnn_dims_from_config(cfg, d)) return wrnn_fail(h, WRNN_ERR_INVALID, "%s", why);
+    if (const char *why = wrnn_dims_from_config(cfg, d)) return wrnn_failf(h, WRNN_ERR_INVALID, "%s", why);
     h->team_dims = d.H == 512 && d.FC == 512 && d.F == 80 && d.R == 128 && d.C == 128 && d.A == 32;
-    if (hop != cfg->hop_length) return wrnn_fail(h, WRNN_ERR_INVALID, "prod(upsample_factors)=%d != hop_length=%d", hop, cfg->hop_length);
+    if (hop != cfg->hop_length) return wrnn_failf(h, WRNN_ERR_INVALID, "prod(upsample_factors)=%d != hop_length=%d", hop, cfg->hop_length);
     if (reach > cfg->pad * hop || d.ND > WRNN_KTAB_MAXD)
-        return wrnn_fail(h, WRNN_ERR_INVALID, "upsample edge reach %d exceeds indent %d: composite FIR not shift-invariant", reach, cfg->pad * hop);
+        return wrnn_failf(h, WRNN_ERR_INVALID, "upsample edge reach %d exceeds indent %d: composite FIR not shift-invariant", reach, cfg->pad * hop);
     if (wrnn_simple_lds_bytes(d) > 160u * 1024u || ((size_t)(8 + d.KS - 1) * d.F + 16u * d.C) * sizeof(float) > 160u * 1024u)
-        return wrnn_fail(h, WRNN_ERR_INVALID, "dims too large: the activation vectors of one row (%zu bytes) must fit 160 KB of LDS", wrnn_simple_lds_bytes(d));
-    WRNN_HIP_TRY(h, hipSetDevice(cfg->device));
+        return wrnn_failf(h, WRNN_ERR_INVALID, "dims too large: the activation vectors of one row (%zu bytes) must fit 160 KB of LDS", wrnn_simple_lds_bytes(d));
+    WRNN_TRY(h, hipSetDevice(cfg->device));
     {
         // team kernels: one team per XCD = 32 CUs (SPX: 256 CUs = 8 teams; a CPX/DPX partition exposes fewer)
         hipDeviceProp_t prop;
-        WRNN_HIP_TRY(h, hipGetDeviceProperties(&prop, cfg->device));
+        WRNN_TRY(h, hipGetDeviceProperties(&prop, cfg->device));
         h->n_teams = prop.multiProcessorCount / 32;
         if (h->n_teams > 8) h->n_teams = 8;
     }
@@ -172,9 +170,9 @@ int wrnn_create(const wrnn_config *cfg, wrnn_handle **out) {
         }
         (void)hipGetLastError();
     }
-    for (int i = 0; i < 3; ++i) WRNN_HIP_TRY(h, hipEventCreate(&h->ev[i]));
-    WRNN_HIP_TRY(h, hipMalloc(&h->err_dev, 64));
-    WRNN_HIP_TRY(h, hipMemset(h->err_dev, 0, 64));
+    for (int i = 0; i < 3; ++i) WRNN_TRY(h, hipEventCreate(&h->ev[i]));
+    WRNN_TRY(h, hipMalloc(&h->err_dev, 64));
+    WRNN_TRY(h, hipMemset(h->err_dev, 0, 64));
     return WRNN_OK;
 }
 
@@ -212,7 +210,7 @@ void wrnn_destroy(wrnn_handle *h) {
     delete h;
 }
 
-const char *wrnn_last_error(const wrnn_handle *h) { return h ? h->err.c_str() : "null handle"; }
+const char *wrnn_last_error(const wrnn_handle *h) { return wrnn_last_error_of(h); }
 
 int32_t wrnn_team_info(const wrnn_handle *h, int32_t *n_teams_out, const char **why_not_out) {
     if (!h) return 0;
@@ -237,7 +235,7 @@ int wrnn_debug_teamg_lds_budget(wrnn_handle *h, int64_t bytes) {
 int wrnn_teamg_set_weight_format(wrnn_handle *h, int32_t fmt) {
     if (!h) return WRNN_ERR_INVALID;
     if (fmt != WRNN_WEIGHTS_F32 && fmt != WRNN_WEIGHTS_F16 && fmt != WRNN_WEIGHTS_E4M3)   // 2 is reserved
-        return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_teamg_set_weight_format: %d is none of WRNN_WEIGHTS_F32, WRNN_WEIGHTS_F16, WRNN_WEIGHTS_E4M3", fmt);
+        return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_teamg_set_weight_format: %d is none of WRNN_WEIGHTS_F32, WRNN_WEIGHTS_F16, WRNN_WEIGHTS_E4M3", fmt);
     if (fmt != h->teamg_fmt) { h->teamg_img_ok = false; h->teamg_sp_ok = false; }   // the next TEAMG / TEAMG_BATCH call packs the image in the new element type
     h->teamg_fmt = fmt;
     return WRNN_OK;
@@ -258,7 +256,7 @@ int32_t wrnn_teamg_sparse(const wrnn_handle *h) { return h && h->teamg_sparse ? 
 int wrnn_teamg_sparse_info(wrnn_handle *h, int64_t kept[6], int64_t dense[6], int32_t nb_a[6], int32_t nb_b[6], wrnn_teamg_plan_info *plan) {
     if (!h) return WRNN_ERR_INVALID;
     if (!h->teamg_sp_ok || !h->teamg_img_ok)
-        return wrnn_fail(h, WRNN_ERR_STATE, "wrnn_teamg_sparse_info: no block-sparse image is packed (wrnn_teamg_set_sparse(h, 1), then a TEAMG / TEAMG_BATCH call)");
+        return wrnn_failf(h, WRNN_ERR_STATE, "wrnn_teamg_sparse_info: no block-sparse image is packed (wrnn_teamg_set_sparse(h, 1), then a TEAMG / TEAMG_BATCH call)");
     for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) {
         if (kept) kept[l] = h->teamg_sp_kept[l];
         if (dense) dense[l] = h->teamg_sp_dense[l];
@@ -279,13 +277,13 @@ int wrnn_load_weights(wrnn_handle *h, const wrnn_tensor_desc *tensors, int32_t n
         if (tensors[i].name && tensors[i].data) tv[tensors[i].name] = TensorView{&tensors[i]};
     auto need = [&](const std::string &name, std::initializer_list<int64_t> shape, const float **out) -> int {
         auto it = tv.find(name);
-        if (it == tv.end()) return wrnn_fail(h, WRNN_ERR_MISSING_KEY, "state_dict key missing: %s", name.c_str());
+        if (it == tv.end()) return wrnn_failf(h, WRNN_ERR_MISSING_KEY, "state_dict key missing: %s", name.c_str());
         const wrnn_tensor_desc *t = it->second.t;
-        if (t->dtype != WRNN_DTYPE_F32) return wrnn_fail(h, WRNN_ERR_INVALID, "%s: expected float32", name.c_str());
-        if ((size_t)t->ndim != shape.size()) return wrnn_fail(h, WRNN_ERR_INVALID, "%s: expected %d dimensions, got %d", name.c_str(), (int)shape.size(), (int)t->ndim);
+        if (t->dtype != WRNN_DTYPE_F32) return wrnn_failf(h, WRNN_ERR_INVALID, "%s: expected float32", name.c_str());
+        if ((size_t)t->ndim != shape.size()) return wrnn_failf(h, WRNN_ERR_INVALID, "%s: expected %d dimensions, got %d", name.c_str(), (int)shape.size(), (int)t->ndim);
         int di = 0;
         for (auto s : shape) {
-            if (t->shape[di] != s) return wrnn_fail(h, WRNN_ERR_INVALID, "%s: dimension %d is %lld, expected %lld", name.c_str(), di, (long long)t->shape[di], (long long)s);
+            if (t->shape[di] != s) return wrnn_failf(h, WRNN_ERR_INVALID, "%s: dimension %d is %lld, expected %lld", name.c_str(), di, (long long)t->shape[di], (long long)s);
             ++di;
         }
         *out = it->second.f();
@@ -476,24 +474,24 @@ int wrnn_load_weights(wrnn_handle *h, const wrnn_tensor_desc *tensors, int32_t n
                     }
                 }
     }
-    WRNN_HIP_TRY(h, hipSetDevice(h->cfg.device));
+    WRNN_TRY(h, hipSetDevice(h->cfg.device));
     auto upload = [&](float *&dst, const std::vector<float> &src) -> int {
         if (dst) { (void)hipFree(dst); dst = nullptr; }
-        WRNN_HIP_TRY(h, hipMalloc(&dst, src.size() * sizeof(float)));
-        WRNN_HIP_TRY(h, hipMemcpy(dst, src.data(), src.size() * sizeof(float), hipMemcpyHostToDevice));
+        WRNN_TRY(h, hipMalloc(&dst, src.size() * sizeof(float)));
+        WRNN_TRY(h, hipMemcpy(dst, src.data(), src.size() * sizeof(float), hipMemcpyHostToDevice));
         return WRNN_OK;
     };
     if ((rc = upload(h->team_w, tw)) || (rc = upload(h->team_fc3, tf3)) || (rc = upload(h->wI0, vwI0)) || (rc = upload(h->u1, vu1)) ||
         (rc = upload(h->batch_w, bw)) || (rc = upload(h->batch_fc3, bf3)) || (rc = upload(h->batch_wn, bwn))) return rc;
     }
-    WRNN_HIP_TRY(h, hipSetDevice(h->cfg.device));
+    WRNN_TRY(h, hipSetDevice(h->cfg.device));
     if (!h->mail) {
-        WRNN_HIP_TRY(h, hipMalloc(&h->mail, WRNN_MAIL_BYTES));
-        WRNN_HIP_TRY(h, hipMalloc(&h->ctl, TEAM_CTL_WORDS * sizeof(unsigned)));
+        WRNN_TRY(h, hipMalloc(&h->mail, WRNN_MAIL_BYTES));
+        WRNN_TRY(h, hipMalloc(&h->ctl, TEAM_CTL_WORDS * sizeof(unsigned)));
     }
     if (h->wdev) { (void)hipFree(h->wdev); h->wdev = nullptr; }
-    WRNN_HIP_TRY(h, hipMalloc(&h->wdev, o.total * sizeof(float)));
-    WRNN_HIP_TRY(h, hipMemcpy(h->wdev, pk.data(), o.total * sizeof(float), hipMemcpyHostToDevice));
+    WRNN_TRY(h, hipMalloc(&h->wdev, o.total * sizeof(float)));
+    WRNN_TRY(h, hipMemcpy(h->wdev, pk.data(), o.total * sizeof(float), hipMemcpyHostToDevice));
     h->teamg_img_ok = false;   // the TEAMG image is packed from wdev by the next TEAMG call
     h->teamg_sp_ok = false;
     h->loaded = true;
@@ -503,19 +501,19 @@ int wrnn_load_weights(wrnn_handle *h, const wrnn_tensor_desc *tensors, int32_t n
 static int ensure_aux(wrnn_handle *h, int B, int T) { return wrnn_grow(h, h->aux_frames, h->aux_cap, (size_t)B * T * h->d.R); }
 
 int wrnn_conditioning(wrnn_handle *h, const float *mels_dev, int32_t B, int32_t T, int32_t mels_padded, float *up_dev, float *aux_dev, void *stream) {
-    if (!h || !mels_dev || B < 1 || T < 1) return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_conditioning: bad arguments");
-    if (!h->loaded) return wrnn_fail(h, WRNN_ERR_STATE, "weights not loaded");
-    WRNN_HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (!h || !mels_dev || B < 1 || T < 1) return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_conditioning: bad arguments");
+    if (!h->loaded) return wrnn_failf(h, WRNN_ERR_STATE, "weights not loaded");
+    WRNN_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     if (int rc = ensure_aux(h, B, T)) return rc;
     const int mel_T = mels_padded ? T + 2 * h->d.P : T, mel_off = mels_padded ? h->d.P : 0;
-    WRNN_HIP_TRY(h, wrnn_launch_resnet(h, mels_dev, B, T, mel_T, mel_off, h->aux_frames, s));
-    if (up_dev || aux_dev) WRNN_HIP_TRY(h, wrnn_launch_materialize(h, mels_dev, h->aux_frames, B, T, mel_T, mel_off, up_dev, aux_dev, s));
+    WRNN_TRY(h, wrnn_launch_resnet(h, mels_dev, B, T, mel_T, mel_off, h->aux_frames, s));
+    if (up_dev || aux_dev) WRNN_TRY(h, wrnn_launch_materialize(h, mels_dev, h->aux_frames, B, T, mel_T, mel_off, up_dev, aux_dev, s));
     return WRNN_OK;
 }
 
 int wrnn_plan(wrnn_handle *h, int32_t B, int32_t T, int32_t batched, int32_t target, int32_t overlap, int32_t *rows_out, int64_t *steps_out) {
-    if (!h || B < 1 || T < 1) return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_plan: bad arguments");
+    if (!h || B < 1 || T < 1) return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_plan: bad arguments");
     const int64_t total = (int64_t)T * h->d.HOP;
     if (!batched) {
         if (rows_out) *rows_out = B;
@@ -524,15 +522,15 @@ int wrnn_plan(wrnn_handle *h, int32_t B, int32_t T, int32_t batched, int32_t tar
     }
     // fold_with_overlap (fatchord_version.py:293-340) indexes folded[i] = x[:, start:end, :] with a
     // batch-1 x; any other batch size raises in the reference.
-    if (B != 1) return wrnn_fail(h, WRNN_ERR_INVALID, "batched generation requires a single utterance (fold_with_overlap)");
-    if (target < 1 || overlap < 0) return wrnn_fail(h, WRNN_ERR_INVALID, "bad target/overlap");
+    if (B != 1) return wrnn_failf(h, WRNN_ERR_INVALID, "batched generation requires a single utterance (fold_with_overlap)");
+    if (target < 1 || overlap < 0) return wrnn_failf(h, WRNN_ERR_INVALID, "bad target/overlap");
     // Python floor division like fatchord_version.py:319 (a clip shorter than `overlap` gives -1 -> 0 folds -> error)
     const int64_t fold_den = (int64_t)target + overlap, fold_num = total - overlap;
     int64_t num_folds = fold_num / fold_den;
     if (fold_num % fold_den != 0 && fold_num < 0) --num_folds;
     const int64_t extended = num_folds * ((int64_t)overlap + target) + overlap;
     if (total - extended != 0) num_folds += 1;
-    if (num_folds < 1) return wrnn_fail(h, WRNN_ERR_INVALID, "sequence shorter than one fold");
+    if (num_folds < 1) return wrnn_failf(h, WRNN_ERR_INVALID, "sequence shorter than one fold");
     if (rows_out) *rows_out = (int32_t)num_folds;
     if (steps_out) *steps_out = (int64_t)target + 2LL * overlap;
     return WRNN_OK;
@@ -553,15 +551,15 @@ static int build_row_table(wrnn_handle *h, int32_t B, int32_t T, int32_t batched
             return rc;
         h->rows_cap = rows;
     }
-    WRNN_HIP_TRY(h, hipMemsetAsync(h->err_dev, 0, 64, s));
+    WRNN_TRY(h, hipMemsetAsync(h->err_dev, 0, 64, s));
     if (!fold_frames) {
-        WRNN_HIP_TRY(h, wrnn_launch_rows(h->rows_dev, h->order_dev, h->sched_dev, rows, sched_teams, batched, (long)target + overlap, (long)steps,
+        WRNN_TRY(h, wrnn_launch_rows(h->rows_dev, h->order_dev, h->sched_dev, rows, sched_teams, batched, (long)target + overlap, (long)steps,
                                          opts->frames_dev, T, h->d.HOP, h->keys_dev, opts->utt_seeds_dev, s));
         return WRNN_OK;
     }
     h->fold_B = 0;   // the fold offsets on the handle are valid once the kernel that writes them is enqueued
     if (int rc = wrnn_grow(h, h->fold0_dev, h->fold0_cap, (size_t)B + 1)) return rc;
-    WRNN_HIP_TRY(h, wrnn_launch_rows_folded(h->rows_dev, h->order_dev, h->sched_dev, h->fold0_dev, h->err_dev, fold_frames, B, rows, sched_teams,
+    WRNN_TRY(h, wrnn_launch_rows_folded(h->rows_dev, h->order_dev, h->sched_dev, h->fold0_dev, h->err_dev, fold_frames, B, rows, sched_teams,
                                             (long)target, (long)overlap, h->d.HOP, T, h->keys_dev, opts->utt_seeds_dev, s));
     h->fold_B = B; h->fold_target = target; h->fold_overlap = overlap; h->fold_rows = rows;
     return WRNN_OK;
@@ -571,7 +569,7 @@ static int build_row_table(wrnn_handle *h, int32_t B, int32_t T, int32_t batched
 // the teams first (rpb rows per batch), a team runs ceil(batches / n_teams) batches one after the other.  a: the call's loop arguments.
 static int run_batch(wrnn_handle *h, const WrnnLoopArgs &a, const WrnnFrameTables &t, int B, bool cs, int batch_rows, int snake, int *rpb_out, hipStream_t s) {
     const int rows = a.n_rows;
-    WRNN_HIP_TRY(h, wrnn_launch_pack_records32(t.CM, t.CA, t.VM, t.VA, t.C2, t.C3, t.C4, t.REC, B, a.T, a.d.P, a.frames, s));
+    WRNN_TRY(h, wrnn_launch_pack_records32(t.CM, t.CA, t.VM, t.VA, t.C2, t.C3, t.C4, t.REC, B, a.T, a.d.P, a.frames, s));
     int rpb = (rows + h->n_teams - 1) / h->n_teams;
     if (rpb > WRNN_BATCH_MAX_ROWS) rpb = WRNN_BATCH_MAX_ROWS;
     if (batch_rows > 0) rpb = batch_rows;
@@ -582,9 +580,9 @@ static int run_batch(wrnn_handle *h, const WrnnLoopArgs &a, const WrnnFrameTable
     ba.T = a.T; ba.total_len = a.total_len; ba.steps = a.steps;
     wrnn_copy_sampling(ba, a);
     ba.mail = h->mail; ba.ctl = h->ctl; ba.err = a.err; ba.prof = h->prof_on ? h->prof : nullptr;
-    if (ba.prof) WRNN_HIP_TRY(h, hipMemsetAsync(h->prof, 0, 8 * WRNN_PROF_SLOTS * sizeof(unsigned long long), s));
-    WRNN_HIP_TRY(h, hipEventRecord(h->ev[1], s));  // tables and records are prologue work
-    WRNN_HIP_TRY(h, wrnn_gated_launch(h->cfg.device, s, h->mail, WRNN_MAIL_BYTES, h->ctl, TEAM_CTL_WORDS * sizeof(unsigned),
+    if (ba.prof) WRNN_TRY(h, hipMemsetAsync(h->prof, 0, 8 * WRNN_PROF_SLOTS * sizeof(unsigned long long), s));
+    WRNN_TRY(h, hipEventRecord(h->ev[1], s));  // tables and records are prologue work
+    WRNN_TRY(h, wrnn_gated_launch(h->cfg.device, s, h->mail, WRNN_MAIL_BYTES, h->ctl, TEAM_CTL_WORDS * sizeof(unsigned),
                                       [&] { return cs ? wrnn_launch_loop_batch_cs(ba, s) : wrnn_launch_loop_batch(ba, s); }));
     h->prof_div = (double)a.steps * ((((rows + rpb - 1) / rpb) + h->n_teams - 1) / h->n_teams);
     *rpb_out = rpb;
@@ -595,8 +593,8 @@ static int run_batch(wrnn_handle *h, const WrnnLoopArgs &a, const WrnnFrameTable
 static int run_team2(wrnn_handle *h, const WrnnLoopArgs &a, const WrnnFrameTables &t, int B, int team2_segment, int snake, int n_slots, int *launches,
                      hipStream_t s) {
     const int rows = a.n_rows;
-    WRNN_HIP_TRY(h, wrnn_launch_pack_records(t.CM, t.CA, t.VM, t.VA, t.REC, B, a.T, a.d.P, a.frames, s));
-    if (a.frames) WRNN_HIP_TRY(h, wrnn_launch_mask_frame_tables(t.C2, t.C3, t.C4, a.frames, B, a.T, s));
+    WRNN_TRY(h, wrnn_launch_pack_records(t.CM, t.CA, t.VM, t.VA, t.REC, B, a.T, a.d.P, a.frames, s));
+    if (a.frames) WRNN_TRY(h, wrnn_launch_mask_frame_tables(t.C2, t.C3, t.C4, a.frames, B, a.T, s));
     const int64_t seg = wrnn_team2_segment_len(rows, a.d.H, a.steps, team2_segment);
     int rc;
     if ((rc = wrnn_grow(h, h->cond, h->cond_cap, (size_t)rows * (size_t)seg * a.d.H * 4)) ||
@@ -609,8 +607,8 @@ static int run_team2(wrnn_handle *h, const WrnnLoopArgs &a, const WrnnFrameTable
     ta.state = h->team_state;
     wrnn_copy_sampling(ta, a);
     ta.mail = h->mail; ta.ctl = h->ctl; ta.err = a.err; ta.prof = h->prof_on ? h->prof : nullptr;
-    WRNN_HIP_TRY(h, hipEventRecord(h->ev[1], s));  // the tables are prologue work; the stream chunks are timed with the loop
-    if (ta.prof) WRNN_HIP_TRY(h, hipMemsetAsync(h->prof, 0, 8 * WRNN_PROF_SLOTS * sizeof(unsigned long long), s));
+    WRNN_TRY(h, hipEventRecord(h->ev[1], s));  // the tables are prologue work; the stream chunks are timed with the loop
+    if (ta.prof) WRNN_TRY(h, hipMemsetAsync(h->prof, 0, 8 * WRNN_PROF_SLOTS * sizeof(unsigned long long), s));
     h->prof_div = (double)a.steps * ((rows + h->n_teams - 1) / h->n_teams);
     return wrnn_run_team2_segments(h, ta, h->cond, 0, a.steps, seg, launches, s);
 }
@@ -620,27 +618,27 @@ static int run_team2(wrnn_handle *h, const WrnnLoopArgs &a, const WrnnFrameTable
 static int teamg_image(wrnn_handle *h, const WrnnTeamGPlan &plan, hipStream_t s) {
     if (h->teamg_img_ok) return WRNN_OK;
     if (h->teamg_img) { (void)hipFree(h->teamg_img); h->teamg_img = nullptr; }
-    WRNN_HIP_TRY(h, hipMalloc(&h->teamg_img, wrnn_teamg_img_bytes(plan)));
+    WRNN_TRY(h, hipMalloc(&h->teamg_img, wrnn_teamg_img_bytes(plan)));
     if (h->teamg_sparse) {
         // the census has run (teamg_plan): compaction by its flags, no further wait
         for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) h->teamg_scale[l] = 1.0f;
-        WRNN_HIP_TRY(h, wrnn_teamg_sparse_pack(h, plan, h->teamg_nb_a, h->teamg_nb_b, h->teamg_sp_flags, h->teamg_img, s));
+        WRNN_TRY(h, wrnn_teamg_sparse_pack(h, plan, h->teamg_nb_a, h->teamg_nb_b, h->teamg_sp_flags, h->teamg_img, s));
         h->teamg_img_ok = true;
-        WRNN_HIP_TRY(h, hipEventRecord(h->ev[1], s));
+        WRNN_TRY(h, hipEventRecord(h->ev[1], s));
         return WRNN_OK;
     }
     int bad = -1;
-    WRNN_HIP_TRY(h, wrnn_teamg_pack(h, plan, h->teamg_img, s, &bad, h->teamg_scale));
+    WRNN_TRY(h, wrnn_teamg_pack(h, plan, h->teamg_img, s, &bad, h->teamg_scale));
     if (bad >= 0 && plan.esz == 1) {
         for (int l = 0; l < WRNN_TEAMG_LAYERS; ++l) h->teamg_scale[l] = 1.0f;
-        return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "WRNN_WEIGHTS_E4M3: a weight of layer %s is not finite, the layer has no scale; the fp32 image runs whatever the weights",
+        return wrnn_failf(h, WRNN_ERR_UNSUPPORTED, "WRNN_WEIGHTS_E4M3: a weight of layer %s is not finite, the layer has no scale; the fp32 image runs whatever the weights",
                          wrnn_teamg_layer_names[bad]);
     }
     if (bad >= 0)
-        return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "WRNN_WEIGHTS_F16: a weight of layer %s does not round to a finite fp16 (|w| >= 65520); use WRNN_WEIGHTS_F32 for this model",
+        return wrnn_failf(h, WRNN_ERR_UNSUPPORTED, "WRNN_WEIGHTS_F16: a weight of layer %s does not round to a finite fp16 (|w| >= 65520); use WRNN_WEIGHTS_F32 for this model",
                          wrnn_teamg_layer_names[bad]);
     h->teamg_img_ok = true;
-    WRNN_HIP_TRY(h, hipEventRecord(h->ev[1], s));   // the one-time image is not loop time
+    WRNN_TRY(h, hipEventRecord(h->ev[1], s));   // the one-time image is not loop time
     return WRNN_OK;
 }
 // The plan of a TEAMG / TEAMG_BATCH call in the handle's format and setting; nullptr or why not (*rc = the error).  With the sparse setting
@@ -678,16 +676,16 @@ static void teamg_plan_scales(const wrnn_handle *h, WrnnTeamGPlan &p) {
 // The team kernel for any dims (loop_teamg.hip): one row per XCD team at a time, one launch.  Placement and residency are settled here,
 // before the launch; whatever keeps the kernel from running is an error with its reason, never another kernel.
 static int run_teamg(wrnn_handle *h, const WrnnLoopArgs &a, int snake, int n_slots, hipStream_t s) {
-    if (h->force_no_teams) return wrnn_fail(h, WRNN_ERR_INVALID, "team kernels disabled by wrnn_debug_force_no_teams (test hook)");
-    if (h->n_teams < 1) return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "WRNN_KERNEL_TEAMG: fewer than 32 CUs visible (one team = the 32 CUs of an XCD)");
+    if (h->force_no_teams) return wrnn_failf(h, WRNN_ERR_INVALID, "team kernels disabled by wrnn_debug_force_no_teams (test hook)");
+    if (h->n_teams < 1) return wrnn_failf(h, WRNN_ERR_UNSUPPORTED, "WRNN_KERNEL_TEAMG: fewer than 32 CUs visible (one team = the 32 CUs of an XCD)");
     WrnnTeamGArgs ga{};
     int prc = 0;
-    if (const char *why = teamg_plan(h, a.d, 1, ga.plan, s, &prc)) return wrnn_fail(h, prc, "%s", why);
+    if (const char *why = teamg_plan(h, a.d, 1, ga.plan, s, &prc)) return wrnn_failf(h, prc, "%s", why);
     int blocks = 0;
     const hipError_t oe = wrnn_teamg_occupancy(ga.plan, &blocks, h->teamg_sparse);
     (void)hipGetLastError();
     if (oe != hipSuccess || blocks < 1)
-        return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "WRNN_KERNEL_TEAMG: loop_teamg_kernel cannot be resident on a CU with %zu bytes of LDS (%s)",
+        return wrnn_failf(h, WRNN_ERR_UNSUPPORTED, "WRNN_KERNEL_TEAMG: loop_teamg_kernel cannot be resident on a CU with %zu bytes of LDS (%s)",
                          wrnn_teamg_lds_bytes(ga.plan), oe != hipSuccess ? hipGetErrorString(oe) : "occupancy 0");
     if (int rc = teamg_image(h, ga.plan, s)) return rc;
     teamg_plan_scales(h, ga.plan);
@@ -695,24 +693,24 @@ static int run_teamg(wrnn_handle *h, const WrnnLoopArgs &a, int snake, int n_slo
     ga.mail = h->mail; ga.ctl = h->ctl;
     teamg_sparse_args(h, ga.sp);
     const size_t mail_bytes = (size_t)h->n_teams * ga.plan.mail_granules * sizeof(unsigned long long);   // sized from the dims; <= WRNN_MAIL_BYTES
-    WRNN_HIP_TRY(h, wrnn_gated_launch(h->cfg.device, s, h->mail, mail_bytes, h->ctl, TEAM_CTL_WORDS * sizeof(unsigned), [&] { return wrnn_launch_loop_teamg(ga, s); }));
+    WRNN_TRY(h, wrnn_gated_launch(h->cfg.device, s, h->mail, mail_bytes, h->ctl, TEAM_CTL_WORDS * sizeof(unsigned), [&] { return wrnn_launch_loop_teamg(ga, s); }));
     return WRNN_OK;
 }
 
 // The same kernel with rpb > 1 rows per team in lock-step (loop_teamg_batch.hip) on its instantiation rb = 2, 4 or 8; the refusals of
 // run_teamg, the weight image of run_teamg.
 static int run_teamg_batch(wrnn_handle *h, const WrnnLoopArgs &a, int snake, int rpb, hipStream_t s) {
-    if (h->force_no_teams) return wrnn_fail(h, WRNN_ERR_INVALID, "team kernels disabled by wrnn_debug_force_no_teams (test hook)");
-    if (h->n_teams < 1) return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "WRNN_KERNEL_TEAMG_BATCH: fewer than 32 CUs visible (one team = the 32 CUs of an XCD)");
+    if (h->force_no_teams) return wrnn_failf(h, WRNN_ERR_INVALID, "team kernels disabled by wrnn_debug_force_no_teams (test hook)");
+    if (h->n_teams < 1) return wrnn_failf(h, WRNN_ERR_UNSUPPORTED, "WRNN_KERNEL_TEAMG_BATCH: fewer than 32 CUs visible (one team = the 32 CUs of an XCD)");
     const int rb = wrnn_teamg_batch_inst(rpb);
     WrnnTeamGBatchArgs ga{};
     int prc = 0;
-    if (const char *why = teamg_plan(h, a.d, rb, ga.plan, s, &prc)) return wrnn_fail(h, prc, "%s (batch_rows %d runs as %d)", why, rpb, rb);
+    if (const char *why = teamg_plan(h, a.d, rb, ga.plan, s, &prc)) return wrnn_failf(h, prc, "%s (batch_rows %d runs as %d)", why, rpb, rb);
     int blocks = 0;
     const hipError_t oe = wrnn_teamg_batch_occupancy(ga.plan, rb, &blocks, h->teamg_sparse);
     (void)hipGetLastError();
     if (oe != hipSuccess || blocks < 1)
-        return wrnn_fail(h, WRNN_ERR_UNSUPPORTED, "WRNN_KERNEL_TEAMG_BATCH: loop_teamg_batch_kernel<%d> cannot be resident on a CU with %zu bytes of LDS (%s)", rb,
+        return wrnn_failf(h, WRNN_ERR_UNSUPPORTED, "WRNN_KERNEL_TEAMG_BATCH: loop_teamg_batch_kernel<%d> cannot be resident on a CU with %zu bytes of LDS (%s)", rb,
                          wrnn_teamg_lds_bytes(ga.plan), oe != hipSuccess ? hipGetErrorString(oe) : "occupancy 0");
     if (int rc = teamg_image(h, ga.plan, s)) return rc;
     teamg_plan_scales(h, ga.plan);
@@ -720,7 +718,7 @@ static int run_teamg_batch(wrnn_handle *h, const WrnnLoopArgs &a, int snake, int
     ga.mail = h->mail; ga.ctl = h->ctl;
     teamg_sparse_args(h, ga.sp);
     const size_t mail_bytes = (size_t)h->n_teams * ga.plan.mail_granules * sizeof(unsigned long long);   // <= WRNN_MAIL_BYTES: the plan refuses more
-    WRNN_HIP_TRY(h, wrnn_gated_launch(h->cfg.device, s, h->mail, mail_bytes, h->ctl, TEAM_CTL_WORDS * sizeof(unsigned), [&] { return wrnn_launch_loop_teamg_batch(ga, rb, s); }));
+    WRNN_TRY(h, wrnn_gated_launch(h->cfg.device, s, h->mail, mail_bytes, h->ctl, TEAM_CTL_WORDS * sizeof(unsigned), [&] { return wrnn_launch_loop_teamg_batch(ga, rb, s); }));
     return WRNN_OK;
 }
 
@@ -729,32 +727,32 @@ static int run_teamg_batch(wrnn_handle *h, const WrnnLoopArgs &a, int snake, int
 static int generate_impl(wrnn_handle *h, const float *mels_dev, int32_t B, int32_t T, int32_t batched, int32_t target, int32_t overlap,
                          const wrnn_sample_opts *opts, int32_t *labels_out_dev, float *samples_out_dev, void *stream,
                          const int32_t *fold_frames, int32_t rows_total) {
-    if (!h || !mels_dev || !opts || !samples_out_dev) return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_generate: bad arguments");
+    if (!h || !mels_dev || !opts || !samples_out_dev) return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_generate: bad arguments");
     if (opts->struct_size != sizeof(wrnn_sample_opts))
-        return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_sample_opts.struct_size is %u, this library (ABI %d) expects %zu: caller built against another revision of wavernn_amd.h",
+        return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_sample_opts.struct_size is %u, this library (ABI %d) expects %zu: caller built against another revision of wavernn_amd.h",
                     opts->struct_size, WRNN_ABI_VERSION, sizeof(wrnn_sample_opts));
-    if (!h->loaded) return wrnn_fail(h, WRNN_ERR_STATE, "weights not loaded");
-    if (opts->frames_dev && batched) return wrnn_fail(h, WRNN_ERR_INVALID, "frames_dev (ragged batch) is for unbatched calls: folds of one utterance have one length");
-    if (opts->batch_rows < 0 || opts->batch_rows > WRNN_BATCH_MAX_ROWS) return wrnn_fail(h, WRNN_ERR_INVALID, "batch_rows must be 0 (default) or 1..%d", WRNN_BATCH_MAX_ROWS);
-    if (opts->team2_segment < 0) return wrnn_fail(h, WRNN_ERR_INVALID, "team2_segment must be >= 0");
+    if (!h->loaded) return wrnn_failf(h, WRNN_ERR_STATE, "weights not loaded");
+    if (opts->frames_dev && batched) return wrnn_failf(h, WRNN_ERR_INVALID, "frames_dev (ragged batch) is for unbatched calls: folds of one utterance have one length");
+    if (opts->batch_rows < 0 || opts->batch_rows > WRNN_BATCH_MAX_ROWS) return wrnn_failf(h, WRNN_ERR_INVALID, "batch_rows must be 0 (default) or 1..%d", WRNN_BATCH_MAX_ROWS);
+    if (opts->team2_segment < 0) return wrnn_failf(h, WRNN_ERR_INVALID, "team2_segment must be >= 0");
     const WrnnDims &d = h->d;
     int32_t rows = 0;
     int64_t steps = 0;
     if (fold_frames) {
-        if (B < 1 || T < 1 || rows_total < 1 || target < 1 || overlap < 0) return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_generate_folded: bad arguments");
+        if (B < 1 || T < 1 || rows_total < 1 || target < 1 || overlap < 0) return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_generate_folded: bad arguments");
         rows = rows_total;
         steps = (int64_t)target + 2LL * overlap;
     } else if (int rc = wrnn_plan(h, B, T, batched, target, overlap, &rows, &steps)) return rc;
     if (opts->noise_mode == WRNN_NOISE_INJECTED && (!opts->noise1_dev || (d.mode == WRNN_MODE_MOL && !opts->noise2_dev)))
-        return wrnn_fail(h, WRNN_ERR_INVALID, "WRNN_NOISE_INJECTED needs noise pointers");
+        return wrnn_failf(h, WRNN_ERR_INVALID, "WRNN_NOISE_INJECTED needs noise pointers");
     if (opts->noise_mode == WRNN_NOISE_ARGMAX && d.mode != WRNN_MODE_RAW)
-        return wrnn_fail(h, WRNN_ERR_INVALID, "WRNN_NOISE_ARGMAX is RAW-only");
-    if (opts->noise_mode < 0 || opts->noise_mode > 2) return wrnn_fail(h, WRNN_ERR_INVALID, "bad noise_mode");
+        return wrnn_failf(h, WRNN_ERR_INVALID, "WRNN_NOISE_ARGMAX is RAW-only");
+    if (opts->noise_mode < 0 || opts->noise_mode > 2) return wrnn_failf(h, WRNN_ERR_INVALID, "bad noise_mode");
     if (opts->utt_seeds_dev && opts->noise_mode != WRNN_NOISE_PHILOX)
-        return wrnn_fail(h, WRNN_ERR_INVALID, "utt_seeds_dev (per-utterance seeds) needs noise_mode WRNN_NOISE_PHILOX");
+        return wrnn_failf(h, WRNN_ERR_INVALID, "utt_seeds_dev (per-utterance seeds) needs noise_mode WRNN_NOISE_PHILOX");
     if (opts->utt_seeds_dev && batched && !fold_frames)
-        return wrnn_fail(h, WRNN_ERR_INVALID, "utt_seeds_dev is for unbatched calls and wrnn_generate_folded: a batched wrnn_generate has one utterance, `seed` is its key");
-    WRNN_HIP_TRY(h, hipSetDevice(h->cfg.device));
+        return wrnn_failf(h, WRNN_ERR_INVALID, "utt_seeds_dev is for unbatched calls and wrnn_generate_folded: a batched wrnn_generate has one utterance, `seed` is its key");
+    WRNN_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
 
     const int sched_teams = h->n_teams < 1 ? 1 : h->n_teams;
@@ -762,10 +760,10 @@ static int generate_impl(wrnn_handle *h, const float *mels_dev, int32_t B, int32
     const int snake = opts->frames_dev ? 1 : 0;
     if (int rc = ensure_aux(h, B, T)) return rc;
 
-    WRNN_HIP_TRY(h, hipEventRecord(h->ev[0], s));
+    WRNN_TRY(h, hipEventRecord(h->ev[0], s));
     const int mel_T = opts->mels_padded ? T + 2 * d.P : T, mel_off = opts->mels_padded ? d.P : 0;
-    WRNN_HIP_TRY(h, wrnn_launch_resnet(h, mels_dev, B, T, mel_T, mel_off, h->aux_frames, s));
-    WRNN_HIP_TRY(h, hipEventRecord(h->ev[1], s));
+    WRNN_TRY(h, wrnn_launch_resnet(h, mels_dev, B, T, mel_T, mel_off, h->aux_frames, s));
+    WRNN_TRY(h, hipEventRecord(h->ev[1], s));
 
     WrnnLoopArgs a{};
     a.w = h->wdev; a.off = h->off; a.d = d; a.mels = mels_dev; a.mel_T = mel_T; a.mel_off = mel_off; a.aux_frames = h->aux_frames; a.rows = h->rows_dev;
@@ -787,10 +785,10 @@ static int generate_impl(wrnn_handle *h, const float *mels_dev, int32_t B, int32
     }
     if (kernel == WRNN_KERNEL_BATCH_CS && !team_no && !h->cs_ok) team_no = "loop_batch_cs_kernel cannot be resident (LDS/registers); WRNN_KERNEL_BATCH can";
     if (kernel == WRNN_KERNEL_SIMPLE) {
-        WRNN_HIP_TRY(h, wrnn_launch_loop_simple(a, s));
+        WRNN_TRY(h, wrnn_launch_loop_simple(a, s));
     } else if (kernel == WRNN_KERNEL_TEAM2 || kernel == WRNN_KERNEL_BATCH || kernel == WRNN_KERNEL_BATCH_CS) {
         const bool batch_family = kernel != WRNN_KERNEL_TEAM2;
-        if (team_no) return wrnn_fail(h, WRNN_ERR_INVALID, "%s", team_no);
+        if (team_no) return wrnn_failf(h, WRNN_ERR_INVALID, "%s", team_no);
         WrnnFrameTables t;
         if (int rc = wrnn_build_frame_tables(h, h->tab, h->tab_cap, mels_dev, mel_T, d.P - mel_off, h->aux_frames, B, T, batch_family ? 32 : 28, t, s)) return rc;
         if (int rc = batch_family ? run_batch(h, a, t, B, kernel == WRNN_KERNEL_BATCH_CS, opts->batch_rows, snake, &batch_rows_run, s)
@@ -814,9 +812,9 @@ static int generate_impl(wrnn_handle *h, const float *mels_dev, int32_t B, int32
         } else if (int rc = run_teamg_batch(h, a, snake, rpb, s)) return rc;
         batch_rows_run = rpb;
     } else {
-        return wrnn_fail(h, WRNN_ERR_INVALID, "kernel %d not available", kernel);
+        return wrnn_failf(h, WRNN_ERR_INVALID, "kernel %d not available", kernel);
     }
-    WRNN_HIP_TRY(h, hipEventRecord(h->ev[2], s));
+    WRNN_TRY(h, hipEventRecord(h->ev[2], s));
     h->timing_valid = true;
     h->last.kernel = kernel; h->last.rows = rows; h->last.steps = steps; h->last.launches = launches;
     h->last_batch_rows = batch_rows_run;
@@ -855,48 +853,48 @@ int wrnn_plan_folded(const int32_t *frames_host, int32_t B, int32_t hop, int32_t
 int wrnn_generate_folded(wrnn_handle *h, const float *mels_dev, int32_t B, int32_t T, const int32_t *frames_dev, int32_t rows_total,
                          int32_t target, int32_t overlap, const wrnn_sample_opts *opts, int32_t *labels_out_dev,
                          float *samples_out_dev, void *stream) {
-    if (!h || !frames_dev) return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_generate_folded: bad arguments");
+    if (!h || !frames_dev) return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_generate_folded: bad arguments");
     if (opts && opts->struct_size == sizeof(wrnn_sample_opts) &&
         (opts->frames_dev || opts->mels_padded || opts->x_forced_dev || opts->x_init_dev || opts->logits_out_dev))
-        return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_generate_folded: opts.frames_dev, mels_padded, x_forced_dev, x_init_dev and logits_out_dev must be unset");
+        return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_generate_folded: opts.frames_dev, mels_padded, x_forced_dev, x_init_dev and logits_out_dev must be unset");
     return generate_impl(h, mels_dev, B, T, 1, target, overlap, opts, labels_out_dev, samples_out_dev, stream, frames_dev, rows_total);
 }
 
 int wrnn_loss(wrnn_handle *h, const float *y_hat_dev, const void *y_dev, int64_t n_rows, float *loss_out_dev, void *stream) {
-    if (!h || !y_hat_dev || !y_dev || !loss_out_dev || n_rows < 1) return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_loss: bad arguments");
-    WRNN_HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (!h || !y_hat_dev || !y_dev || !loss_out_dev || n_rows < 1) return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_loss: bad arguments");
+    WRNN_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     const size_t nblk = (size_t)(h->d.mode == WRNN_MODE_RAW ? (n_rows + 3) / 4 : (n_rows + 255) / 256);
     if (int rc = wrnn_grow(h, h->loss_partial, h->loss_cap, nblk + 1)) return rc;
     int *bad = (int *)(h->loss_partial + nblk);
-    WRNN_HIP_TRY(h, hipMemsetAsync(bad, 0, sizeof(double), s));
-    WRNN_HIP_TRY(h, wrnn_launch_loss(h->d.mode, y_hat_dev, y_dev, h->d.NC, (long)n_rows, h->loss_partial, bad, loss_out_dev, s));
+    WRNN_TRY(h, hipMemsetAsync(bad, 0, sizeof(double), s));
+    WRNN_TRY(h, wrnn_launch_loss(h->d.mode, y_hat_dev, y_dev, h->d.NC, (long)n_rows, h->loss_partial, bad, loss_out_dev, s));
     return WRNN_OK;
 }
 
 int wrnn_last_timing(wrnn_handle *h, wrnn_timing *out) {
     if (!h) return WRNN_ERR_INVALID;
-    if (!h->timing_valid) return wrnn_fail(h, WRNN_ERR_STATE, "no generate call to time");
-    WRNN_HIP_TRY(h, hipSetDevice(h->cfg.device));
-    WRNN_HIP_TRY(h, hipEventSynchronize(h->ev[2]));
-    WRNN_HIP_TRY(h, hipEventElapsedTime(&h->last.prologue_ms, h->ev[0], h->ev[1]));
-    WRNN_HIP_TRY(h, hipEventElapsedTime(&h->last.loop_ms, h->ev[1], h->ev[2]));
+    if (!h->timing_valid) return wrnn_failf(h, WRNN_ERR_STATE, "no generate call to time");
+    WRNN_TRY(h, hipSetDevice(h->cfg.device));
+    WRNN_TRY(h, hipEventSynchronize(h->ev[2]));
+    WRNN_TRY(h, hipEventElapsedTime(&h->last.prologue_ms, h->ev[0], h->ev[1]));
+    WRNN_TRY(h, hipEventElapsedTime(&h->last.loop_ms, h->ev[1], h->ev[2]));
     unsigned errw = 0;
-    WRNN_HIP_TRY(h, hipMemcpy(&errw, h->err_dev, sizeof(errw), hipMemcpyDeviceToHost));
+    WRNN_TRY(h, hipMemcpy(&errw, h->err_dev, sizeof(errw), hipMemcpyDeviceToHost));
     if (out) *out = h->last;
     if (errw == WRNN_DEVERR_ROWS)
-        return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_generate_folded: rows_total differs from the fold count of frames_dev on the device "
+        return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_generate_folded: rows_total differs from the fold count of frames_dev on the device "
                                          "(wrnn_plan_folded gives it for the same frames, target and overlap)");
     if (errw == WRNN_DEVERR_BUSY)
-        return wrnn_fail(h, WRNN_ERR_BUSY, "the team kernel's workgroups did not all become resident within its start-up wait: the GPU is shared with another "
+        return wrnn_failf(h, WRNN_ERR_BUSY, "the team kernel's workgroups did not all become resident within its start-up wait: the GPU is shared with another "
                                       "kernel (another process?).  Retry, or use WRNN_KERNEL_SIMPLE");
-    if (errw) return wrnn_fail(h, WRNN_ERR_TIMEOUT, "device-side bounded spin gave up (code %u)", errw);
+    if (errw) return wrnn_failf(h, WRNN_ERR_TIMEOUT, "device-side bounded spin gave up (code %u)", errw);
     return WRNN_OK;
 }
 
 int wrnn_phase_profile(wrnn_handle *h, int32_t enable) {
     if (!h) return WRNN_ERR_INVALID;
-    WRNN_HIP_TRY(h, hipSetDevice(h->cfg.device));
+    WRNN_TRY(h, hipSetDevice(h->cfg.device));
     if (enable) {
         // the instrumented instantiations have their own register / LDS footprint: check their residency like wrnn_create does
         int blocks = 0;
@@ -906,10 +904,10 @@ int wrnn_phase_profile(wrnn_handle *h, int32_t enable) {
             for (int nq = 1; nq <= 2 && e == hipSuccess && blocks >= 1; ++nq) e = wrnn_batch_occupancy(h->cfg.mode, nq, true, &blocks, &lds);
             for (int nq = 1; nq <= wrnn_batch_cs_max_nq(h->cfg.mode) && e == hipSuccess && blocks >= 1; ++nq) e = wrnn_batch_cs_occupancy(h->cfg.mode, nq, true, &blocks, &lds);
             (void)hipGetLastError();
-            if (e != hipSuccess || blocks < 1) return wrnn_fail(h, WRNN_ERR_INVALID, "the instrumented team kernels cannot be resident on this device");
+            if (e != hipSuccess || blocks < 1) return wrnn_failf(h, WRNN_ERR_INVALID, "the instrumented team kernels cannot be resident on this device");
         }
-        if (!h->prof) WRNN_HIP_TRY(h, hipMalloc(&h->prof, 8 * WRNN_PROF_SLOTS * sizeof(unsigned long long)));
-        WRNN_HIP_TRY(h, hipMemset(h->prof, 0, 8 * WRNN_PROF_SLOTS * sizeof(unsigned long long)));
+        if (!h->prof) WRNN_TRY(h, hipMalloc(&h->prof, 8 * WRNN_PROF_SLOTS * sizeof(unsigned long long)));
+        WRNN_TRY(h, hipMemset(h->prof, 0, 8 * WRNN_PROF_SLOTS * sizeof(unsigned long long)));
     }
     h->prof_on = enable != 0;
     return WRNN_OK;
@@ -917,11 +915,11 @@ int wrnn_phase_profile(wrnn_handle *h, int32_t enable) {
 
 int wrnn_phase_cycles(wrnn_handle *h, double *out) {
     if (!h || !out) return WRNN_ERR_INVALID;
-    if (!h->prof_on || !h->prof || !h->timing_valid) return wrnn_fail(h, WRNN_ERR_STATE, "no instrumented call to report (wrnn_phase_profile(h, 1), then a TEAM2 / BATCH call)");
-    WRNN_HIP_TRY(h, hipSetDevice(h->cfg.device));
-    WRNN_HIP_TRY(h, hipEventSynchronize(h->ev[2]));
+    if (!h->prof_on || !h->prof || !h->timing_valid) return wrnn_failf(h, WRNN_ERR_STATE, "no instrumented call to report (wrnn_phase_profile(h, 1), then a TEAM2 / BATCH call)");
+    WRNN_TRY(h, hipSetDevice(h->cfg.device));
+    WRNN_TRY(h, hipEventSynchronize(h->ev[2]));
     unsigned long long pr[8 * WRNN_PROF_SLOTS];
-    WRNN_HIP_TRY(h, hipMemcpy(pr, h->prof, sizeof(pr), hipMemcpyDeviceToHost));
+    WRNN_TRY(h, hipMemcpy(pr, h->prof, sizeof(pr), hipMemcpyDeviceToHost));
     const double n = h->prof_div > 0 ? h->prof_div : 1.0;   // steps x rows (or batches) team 0 ran
     for (int i = 0; i < 8 * WRNN_PROF_SLOTS; ++i) out[i] = (double)pr[i] / n;
     return WRNN_OK;
@@ -941,29 +939,9 @@ struct wrnn_mel_handle {
     std::string err;
 };
 
-namespace {
-int mel_fail(wrnn_mel_handle *h, int code, const char *fmt, ...) {
-    char buf[400];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (h) h->err = buf;
-    return code;
-}
-#define MEL_TRY(h, expr)                                                                                   \
-    do {                                                                                                   \
-        hipError_t e__ = (expr);                                                                           \
-        if (e__ != hipSuccess) return mel_fail((h), WRNN_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e__)); \
-    } while (0)
-}  // namespace
-
 extern "C" {
 
-static const wrnn_mel_features MEL_DEFAULT_FEATURES = {(uint32_t)sizeof(wrnn_mel_features), WRNN_MEL_PAD_REFLECT, 1, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-static const int MEL_MAX_B = 65535;   // grid.y; also the size of the handle's peak workspace
-
-int wrnn_mel_create(const wrnn_mel_config *cfg, wrnn_mel_handle **out) { return wrnn_mel_create_features(cfg, &MEL_DEFAULT_FEATURES, out); }
+int wrnn_mel_create(const wrnn_mel_config *cfg, wrnn_mel_handle **out) { return wrnn_mel_create_features(cfg, &WRNN_DEFAULT_MEL_FEATURES, out); }
 
 int wrnn_mel_create_features(const wrnn_mel_config *cfg, const wrnn_mel_features *f, wrnn_mel_handle **out) {
     if (!cfg || !f || !out) return WRNN_ERR_INVALID;
@@ -971,20 +949,11 @@ int wrnn_mel_create_features(const wrnn_mel_config *cfg, const wrnn_mel_features
     *out = h;
     h->cfg = *cfg;
     if (f->struct_size != sizeof(wrnn_mel_features))
-        return mel_fail(h, WRNN_ERR_INVALID, "features.struct_size = %u, this library's wrnn_mel_features has %zu bytes", f->struct_size, sizeof(wrnn_mel_features));
+        return wrnn_failf(h, WRNN_ERR_INVALID, "features.struct_size = %u, this library's wrnn_mel_features has %zu bytes", f->struct_size, sizeof(wrnn_mel_features));
     h->feat = *f;
-    if (cfg->n_fft != WRNN_MEL_NFFT) return mel_fail(h, WRNN_ERR_UNSUPPORTED, "n_fft = %d: the front end is built for n_fft = %d only", cfg->n_fft, WRNN_MEL_NFFT);
-    if (cfg->hop_length < 1 || !(cfg->min_level_db < 0.0f) || cfg->device < 0)
-        return mel_fail(h, WRNN_ERR_INVALID, "bad configuration: hop_length >= 1, min_level_db < 0, device >= 0");
-    if ((f->pad_mode != WRNN_MEL_PAD_REFLECT && f->pad_mode != WRNN_MEL_PAD_ZERO) || (f->magnitude_power != 1 && f->magnitude_power != 2))
-        return mel_fail(h, WRNN_ERR_INVALID, "bad features: pad_mode is WRNN_MEL_PAD_REFLECT or WRNN_MEL_PAD_ZERO, magnitude_power 1 or 2");
-    if (!(f->preemphasis >= 0.0f) || !(f->preemph_rescale >= 0.0f) || !(f->max_abs_value >= 0.0f) || !std::isfinite(f->preemphasis) ||
-        !std::isfinite(f->preemph_rescale) || !std::isfinite(f->max_abs_value) || !std::isfinite(f->ref_level_db))
-        return mel_fail(h, WRNN_ERR_INVALID, "bad features: preemphasis, preemph_rescale and max_abs_value are finite and >= 0, ref_level_db is finite");
-    if (f->fmax != 0.0f && !((double)f->fmax > (double)cfg->fmin && (double)f->fmax <= 0.5 * (double)cfg->sample_rate))
-        return mel_fail(h, WRNN_ERR_INVALID, "bad features: fmax = %g is not in (fmin, sample_rate / 2] (0 stands for sample_rate / 2)", (double)f->fmax);
+    if (const int rc = wrnn_mel_check(h, cfg, f, "the front end")) return rc;
     if (!wrnn_mel_build_tables(cfg->sample_rate, cfg->win_length, cfg->n_mels, (double)cfg->fmin, (double)f->fmax, &h->tab))
-        return mel_fail(h, WRNN_ERR_INVALID, "bad configuration: 1 <= win_length <= n_fft, 1 <= n_mels <= %d, 0 <= fmin < sample_rate / 2", WRNN_MEL_MAX_MELS);
+        return wrnn_failf(h, WRNN_ERR_INVALID, "bad configuration: 1 <= win_length <= n_fft, 1 <= n_mels <= %d, 0 <= fmin < sample_rate / 2", WRNN_MEL_MAX_MELS);
     // fmax lives in the filterbank table alone, so it needs no arm of the kernel
     h->profile = f->pad_mode != WRNN_MEL_PAD_REFLECT || f->magnitude_power != 1 || f->ref_level_db != 0.0f || f->preemphasis != 0.0f ||
                  f->preemph_rescale != 0.0f || f->max_abs_value != 0.0f;
@@ -1011,31 +980,21 @@ int wrnn_mel_tables(const wrnn_mel_handle *h, float *window, float *twiddle, int
 int wrnn_melspectrogram(wrnn_mel_handle *h, const float *wav_dev, int64_t n_max, const int32_t *n_samples_dev, int32_t B, int32_t T_max,
                         float *mel_out_dev, void *stream) {
     if (!h) return WRNN_ERR_INVALID;
-    if (h->tab.window.empty()) return mel_fail(h, WRNN_ERR_STATE, "the handle's configuration was refused by wrnn_mel_create");
-    if (!wav_dev || !n_samples_dev || !mel_out_dev || n_max < 1 || B < 1 || B > MEL_MAX_B || T_max < 1)
-        return mel_fail(h, WRNN_ERR_INVALID, "bad arguments: device pointers, n_max >= 1, 1 <= B <= 65535, T_max >= 1");
-    MEL_TRY(h, hipSetDevice(h->cfg.device));
+    if (h->tab.window.empty()) return wrnn_failf(h, WRNN_ERR_STATE, "the handle's configuration was refused by wrnn_mel_create");
+    if (!wav_dev || !n_samples_dev || !mel_out_dev || n_max < 1 || B < 1 || B > WRNN_MAX_GRID_Y || T_max < 1)
+        return wrnn_failf(h, WRNN_ERR_INVALID, "bad arguments: device pointers, n_max >= 1, 1 <= B <= 65535, T_max >= 1");
+    WRNN_TRY(h, hipSetDevice(h->cfg.device));
     const WrnnMelTables &t = h->tab;
     if (!h->dev) {
-        auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        h->o_tw = up(t.window.size() * 4);
-        h->o_rows = h->o_tw + up(t.twiddle.size() * 4);
-        h->o_w = h->o_rows + up(t.rows.size() * 4);
-        h->o_peak = h->o_w + up(t.weights.size() * 4);
-        const size_t total = h->o_peak + (h->feat.preemph_rescale > 0.0f ? up((size_t)MEL_MAX_B * 4) : 0);
-        std::vector<char> img(total, 0);
-        memcpy(img.data(), t.window.data(), t.window.size() * 4);
-        memcpy(img.data() + h->o_tw, t.twiddle.data(), t.twiddle.size() * 4);
-        memcpy(img.data() + h->o_rows, t.rows.data(), t.rows.size() * 4);
-        memcpy(img.data() + h->o_w, t.weights.data(), t.weights.size() * 4);
-        void *d = nullptr;
-        MEL_TRY(h, hipMalloc(&d, total));
-        hipError_t e = hipMemcpy(d, img.data(), total, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(d);
-            return mel_fail(h, WRNN_ERR_HIP, "uploading the front-end tables: %s", hipGetErrorString(e));
-        }
-        h->dev = d;
+        // window | twiddle | rows | weights | the peak workspace: one float per clip of the largest batch
+        WrnnImage img;
+        img.put(t.window.data(), t.window.size() * 4);
+        h->o_tw = img.put(t.twiddle.data(), t.twiddle.size() * 4);
+        h->o_rows = img.put(t.rows.data(), t.rows.size() * 4);
+        h->o_w = img.put(t.weights.data(), t.weights.size() * 4);
+        h->o_peak = h->feat.preemph_rescale > 0.0f ? img.take((size_t)WRNN_MAX_GRID_Y * 4) : img.bytes.size();
+        const hipError_t e = img.upload(&h->dev);
+        if (e != hipSuccess) return wrnn_failf(h, WRNN_ERR_HIP, "uploading the front-end tables: %s", hipGetErrorString(e));
     }
     WrnnMelArgs a{};
     const char *d = (const char *)h->dev;
@@ -1052,14 +1011,14 @@ int wrnn_melspectrogram(wrnn_mel_handle *h, const float *wav_dev, int64_t n_max,
         if (f.preemph_rescale > 0.0f) {
             float *peak = (float *)((char *)h->dev + h->o_peak);
             a.peak = peak;
-            MEL_TRY(h, wrnn_launch_mel_peak(wav_dev, n_max, n_samples_dev, B, f.preemphasis, peak, (hipStream_t)stream));
+            WRNN_TRY(h, wrnn_launch_mel_peak(wav_dev, n_max, n_samples_dev, B, f.preemphasis, peak, (hipStream_t)stream));
         }
     }
-    MEL_TRY(h, wrnn_launch_melspec(a, B, h->profile, (hipStream_t)stream));
+    WRNN_TRY(h, wrnn_launch_melspec(a, B, h->profile, (hipStream_t)stream));
     return WRNN_OK;
 }
 
-const char *wrnn_mel_last_error(const wrnn_mel_handle *h) { return h ? h->err.c_str() : "null handle"; }
+const char *wrnn_mel_last_error(const wrnn_mel_handle *h) { return wrnn_last_error_of(h); }
 
 void wrnn_mel_destroy(wrnn_mel_handle *h) {
     if (!h) return;
@@ -1077,26 +1036,9 @@ void wrnn_mel_destroy(wrnn_mel_handle *h) {
 struct wrnn_resample_handle {
     int32_t src_rate = 0, dst_rate = 0, device = 0;
     WrnnResamplePlan plan;
-    float *bank_dev = nullptr;    // wrnn_resample_device_bank, uploaded by the first wrnn_resample
+    void *bank_dev = nullptr;     // wrnn_resample_device_bank, uploaded by the first wrnn_resample
     std::string err;
 };
-
-namespace {
-int rs_fail(wrnn_resample_handle *h, int code, const char *fmt, ...) {
-    char buf[400];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (h) h->err = buf;
-    return code;
-}
-#define RS_TRY(h, expr)                                                                                   \
-    do {                                                                                                  \
-        hipError_t e__ = (expr);                                                                          \
-        if (e__ != hipSuccess) return rs_fail((h), WRNN_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e__)); \
-    } while (0)
-}  // namespace
 
 extern "C" {
 
@@ -1105,11 +1047,11 @@ int wrnn_resample_create(int32_t src_rate, int32_t dst_rate, int32_t device, wrn
     wrnn_resample_handle *h = new wrnn_resample_handle();
     *out = h;
     h->src_rate = src_rate; h->dst_rate = dst_rate; h->device = device;
-    if (device < 0) return rs_fail(h, WRNN_ERR_INVALID, "bad configuration: device >= 0");
+    if (device < 0) return wrnn_failf(h, WRNN_ERR_INVALID, "bad configuration: device >= 0");
     const int rc = wrnn_resample_build_plan(src_rate, dst_rate, &h->plan);
-    if (rc == WRNN_ERR_INVALID) return rs_fail(h, rc, "bad configuration: %d Hz -> %d Hz, both rates must be positive", src_rate, dst_rate);
+    if (rc == WRNN_ERR_INVALID) return wrnn_failf(h, rc, "bad configuration: %d Hz -> %d Hz, both rates must be positive", src_rate, dst_rate);
     if (rc != WRNN_OK)
-        return rs_fail(h, rc, "%d Hz -> %d Hz is outside what the resampler is built for: a ratio of at least 1/%d and a filter bank of at most "
+        return wrnn_failf(h, rc, "%d Hz -> %d Hz is outside what the resampler is built for: a ratio of at least 1/%d and a filter bank of at most "
                               "%d entries (the bank has one phase per output position of the reduced ratio)",
                        src_rate, dst_rate, WRNN_RS_MIN_SCALE_INV, WRNN_RS_MAX_BANK);
     return WRNN_OK;
@@ -1133,32 +1075,28 @@ int wrnn_resample(wrnn_resample_handle *h, const float *in_dev, int64_t n_in_max
                   float *out_dev, void *stream) {
     if (!h) return WRNN_ERR_INVALID;
     const WrnnResamplePlan &pl = h->plan;
-    if (pl.bank.empty()) return rs_fail(h, WRNN_ERR_STATE, "the handle's rates were refused by wrnn_resample_create");
-    if (pl.p == pl.q) return rs_fail(h, WRNN_ERR_INVALID, "equal rates: there is nothing to resample, and the filter is a low-pass that must not run at ratio 1");
-    if (!in_dev || !n_in_dev || !out_dev || n_in_max < 1 || n_in_max > INT32_MAX || B < 1 || B > 65535 || n_out_max < 1 ||
+    if (pl.bank.empty()) return wrnn_failf(h, WRNN_ERR_STATE, "the handle's rates were refused by wrnn_resample_create");
+    if (pl.p == pl.q) return wrnn_failf(h, WRNN_ERR_INVALID, "equal rates: there is nothing to resample, and the filter is a low-pass that must not run at ratio 1");
+    if (!in_dev || !n_in_dev || !out_dev || n_in_max < 1 || n_in_max > INT32_MAX || B < 1 || B > WRNN_MAX_GRID_Y || n_out_max < 1 ||
         n_out_max > (int64_t)INT32_MAX * WRNN_RS_TILE)
-        return rs_fail(h, WRNN_ERR_INVALID, "bad arguments: device pointers, 1 <= n_in_max < 2^31, 1 <= B <= 65535, n_out_max >= 1");
-    RS_TRY(h, hipSetDevice(h->device));
+        return wrnn_failf(h, WRNN_ERR_INVALID, "bad arguments: device pointers, 1 <= n_in_max < 2^31, 1 <= B <= 65535, n_out_max >= 1");
+    WRNN_TRY(h, hipSetDevice(h->device));
     if (!h->bank_dev) {
         const std::vector<float> bt = wrnn_resample_device_bank(pl);
-        void *d = nullptr;
-        RS_TRY(h, hipMalloc(&d, bt.size() * sizeof(float)));
-        hipError_t e = hipMemcpy(d, bt.data(), bt.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(d);
-            return rs_fail(h, WRNN_ERR_HIP, "uploading the filter bank: %s", hipGetErrorString(e));
-        }
-        h->bank_dev = (float *)d;
+        WrnnImage img;
+        img.put(bt.data(), bt.size() * sizeof(float));
+        const hipError_t e = img.upload(&h->bank_dev);
+        if (e != hipSuccess) return wrnn_failf(h, WRNN_ERR_HIP, "uploading the filter bank: %s", hipGetErrorString(e));
     }
     WrnnResampleArgs a{};
-    a.in = in_dev; a.n_in = n_in_dev; a.out = out_dev; a.bank = h->bank_dev;
+    a.in = in_dev; a.n_in = n_in_dev; a.out = out_dev; a.bank = (const float *)h->bank_dev;
     a.n_in_max = n_in_max; a.n_out_max = n_out_max;
     a.p = pl.p; a.q = pl.q; a.half = pl.half; a.taps = pl.taps;
-    RS_TRY(h, wrnn_launch_resample(a, B, pl.span_max, (hipStream_t)stream));
+    WRNN_TRY(h, wrnn_launch_resample(a, B, pl.span_max, (hipStream_t)stream));
     return WRNN_OK;
 }
 
-const char *wrnn_resample_last_error(const wrnn_resample_handle *h) { return h ? h->err.c_str() : "null handle"; }
+const char *wrnn_resample_last_error(const wrnn_resample_handle *h) { return wrnn_last_error_of(h); }
 
 void wrnn_resample_destroy(wrnn_resample_handle *h) {
     if (!h) return;

@@ -8,24 +8,24 @@
 //                                                           u = X / |X| -> Z = S u -> inverse real FFT -> taps under the window
 //   griffin_ola_kernel        grid (ceil(n / 256), B)       overlap-add of the stored taps over the window-sum-square (librosa.istft)
 //   deemphasis_kernel         grid (B)                      y[i] = x[i] + k y[i-1], a blocked float64 scan
-// The 2048-point real transforms are the 1024-point complex radix-4 transform of melspec.hip with its split pass, restated here (that
-// file stays as it is).
+// The 2048-point real transforms are the 1024-point complex radix-4 transform of melspec.hip (radix4_1024 of dsp_device.h, in float64) with
+// its split pass.
 // Precision: the mel, the injected phases and the wav are float32; everything between them is float64 -- the pseudo-inverse, the window
-// and the twiddles (built here in float64; the float32 tables of mel_internal.h are the test entry's window only), S, the transforms, the
+// and the twiddles (dsp_tables.h, unrounded; the float32 tables of mel_internal.h are the mel front end's), S, the transforms, the
 // stored taps and the wave between rounds.  The rounds are not a contraction: where a bin of the current wave's spectrum comes close to
 // zero, u = X / |X| turns a rounding error into a phase error, and a float32 chain was measured to drift from the float64 one by up to
 // 150 times its one-round error over 60 rounds.  In float64 the drift stays far under the float32 rounding of the output.
 // The C entries of the header's Griffin-Lim section are at the end of this file: a handle of its own like the mel front end's, no weights.
 #include <cfloat>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include "../../include/wavernn_amd.h"
 #include "device_util.h"
+#include "dsp_device.h"
+#include "dsp_tables.h"
+#include "handle_common.h"
 #include "mel_internal.h"
 
 namespace {
@@ -52,39 +52,6 @@ struct GriffinArgs {
 };
 
 __device__ inline int clip_frames(const GriffinArgs &a, int b) { return min(max(a.frames[b], 0), a.T_max); }
-
-__device__ inline double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-
-// base-4 digit reversal of a 10-bit index: bit reversal, then the two bits of every digit swapped back
-__device__ inline int rev4(int k) {
-    const unsigned r = __brev((unsigned)k) >> 22;
-    return (int)(((r & 0x2AAu) >> 1) | ((r & 0x155u) << 1));
-}
-
-// 1024-point complex transform in place, input digit-reversed: five radix-4 passes, one butterfly per thread and pass; W_4 = -i.
-// Starts with a barrier (the caller's stores), ends with one.
-__device__ inline void fft1024(double2 *z, const double2 *twiddle, int tid) {
-#pragma unroll
-    for (int s = 0; s < 5; ++s) {
-        __syncthreads();
-        const int q = 1 << (2 * s);
-        const int pos = tid & (q - 1), base = ((tid >> (2 * s)) << (2 * s + 2)) + pos;
-        double2 a0 = z[base], a1 = z[base + q], a2 = z[base + 2 * q], a3 = z[base + 3 * q];
-        if (s > 0) {
-            const int ts = pos * (512 >> (2 * s));   // W_L^pos as an index into the n_fft-point table, L = 4 q
-            a1 = cmul(a1, twiddle[ts]);
-            a2 = cmul(a2, twiddle[2 * ts]);
-            a3 = cmul(a3, twiddle[3 * ts]);
-        }
-        const double2 s02 = make_double2(a0.x + a2.x, a0.y + a2.y), d02 = make_double2(a0.x - a2.x, a0.y - a2.y);
-        const double2 s13 = make_double2(a1.x + a3.x, a1.y + a3.y), d13 = make_double2(a1.x - a3.x, a1.y - a3.y);
-        z[base] = make_double2(s02.x + s13.x, s02.y + s13.y);
-        z[base + q] = make_double2(d02.x + d13.y, d02.y - d13.x);       // d02 - i d13
-        z[base + 2 * q] = make_double2(s02.x - s13.x, s02.y - s13.y);
-        z[base + 3 * q] = make_double2(d02.x - d13.y, d02.y + d13.x);   // d02 + i d13
-    }
-    __syncthreads();
-}
 
 // ---- a. mel -> magnitude ------------------------------------------------------------------------------------------------------------
 // Steps 7, 6 and 4 of wrnn_mel_features backwards, then the pseudo-inverse of the filterbank (a dense product, P has both signs), the
@@ -178,7 +145,7 @@ __global__ void __launch_bounds__(THREADS) griffin_frame_kernel(GriffinArgs a) {
             }
             z[rev4(k)] = make_double2(v[0], v[1]);
         }
-        fft1024(z, a.twiddle, tid);
+        radix4_1024(z, a.twiddle, tid);
     }
     // Split pass, projection and the inverse split pass, one pair of bins (k, NC - k) per step.  Forward: X[k] = E + W^k O,
     // X[NC - k] = conj(E - W^k O).  Backward, for the spectrum Z: E' = (Z[k] + conj(Z[NC - k])) / 2, O' = conj(W^k) (Z[k] - conj(Z[NC - k])) / 2,
@@ -221,7 +188,7 @@ __global__ void __launch_bounds__(THREADS) griffin_frame_kernel(GriffinArgs a) {
             y[rev4(NC - k)] = make_double2(Ei.x + Oi.y, -(Oi.x - Ei.y));
         }
     }
-    fft1024(y, a.twiddle, tid);
+    radix4_1024(y, a.twiddle, tid);
     // frame sample 2 n = Re conj(y[n]) / NC, sample 2 n + 1 = Im conj(y[n]) / NC
     double *out = a.taps + ((long)b * a.T_max + t) * a.win_length;
     const double scale = 1.0 / (double)NC;
@@ -321,41 +288,7 @@ hipError_t launch_deemphasis(const IN *in, long in_stride, const int32_t *n_dev,
     return hipGetLastError();
 }
 
-// ---- host tables ----------------------------------------------------------------------------------------------------------------------
-// The Slaney filterbank of wrnn_mel_build_tables once more, kept in float64 (that one rounds to float32 and packs the rows): the
-// pseudo-inverse is taken of the unrounded basis.
-std::vector<double> linspace(double start, double stop, int num) {
-    std::vector<double> y(num);
-    const double step = (stop - start) / (double)(num - 1);
-    for (int i = 0; i < num; ++i) y[i] = (double)i * step + start;
-    y[num - 1] = stop;
-    return y;
-}
-const double F_SP = 200.0 / 3.0, MIN_LOG_HZ = 1000.0;
-double hz_to_mel(double f) {
-    const double min_log_mel = MIN_LOG_HZ / F_SP, logstep = std::log(6.4) / 27.0;
-    return f >= MIN_LOG_HZ ? min_log_mel + std::log(f / MIN_LOG_HZ) / logstep : f / F_SP;
-}
-double mel_to_hz(double m) {
-    const double min_log_mel = MIN_LOG_HZ / F_SP, logstep = std::log(6.4) / 27.0;
-    return m >= min_log_mel ? MIN_LOG_HZ * std::exp(logstep * (m - min_log_mel)) : F_SP * m;
-}
-std::vector<double> mel_basis64(int sample_rate, int n_mels, double fmin, double fmax_arg) {
-    const double nyquist = 0.5 * (double)sample_rate, fmax = fmax_arg == 0.0 ? nyquist : fmax_arg;
-    const std::vector<double> fftfreqs = linspace(0.0, nyquist, NB);
-    std::vector<double> mel_f = linspace(hz_to_mel(fmin), hz_to_mel(fmax), n_mels + 2);
-    for (double &m : mel_f) m = mel_to_hz(m);
-    std::vector<double> basis((size_t)n_mels * NB);
-    for (int i = 0; i < n_mels; ++i) {
-        const double fd0 = mel_f[i + 1] - mel_f[i], fd1 = mel_f[i + 2] - mel_f[i + 1], enorm = 2.0 / (mel_f[i + 2] - mel_f[i]);
-        for (int k = 0; k < NB; ++k) {
-            const double lower = -(mel_f[i] - fftfreqs[k]) / fd0, upper = (mel_f[i + 2] - fftfreqs[k]) / fd1;
-            basis[(size_t)i * NB + k] = std::fmax(0.0, std::fmin(lower, upper)) * enorm;
-        }
-    }
-    return basis;
-}
-
+// ---- host tables (the basis, the window and the twiddles are dsp_tables.h's, unrounded) -----------------------------------------------
 // P = B^T (B B^T)^-1 of a basis of full row rank, (NB, n) row-major, by a Cholesky factorisation of the n x n Gram matrix.
 // 0: done; 1: an empty filterbank row; 2: the Gram matrix is not positive definite.
 int pseudo_inverse(const std::vector<double> &basis, int n, std::vector<double> *P) {
@@ -415,28 +348,9 @@ struct wrnn_griffin_handle {
     std::vector<double> pinv;         // (NB, n_mels) the pseudo-inverse, unrounded
     void *dev = nullptr;              // window | twiddle | pinv transposed, all float64, uploaded by the first call
     size_t o_tw = 0, o_p = 0;
-    double *ws = nullptr;             // S | taps | wave, grown on demand
-    size_t ws_cap = 0;                // in doubles
+    WrnnScratch ws;                   // S | taps | wave, grown on demand
     std::string err;
 };
-
-namespace {
-int gl_fail(wrnn_griffin_handle *h, int code, const char *fmt, ...) {
-    char buf[400];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (h) h->err = buf;
-    return code;
-}
-#define GL_TRY(h, expr)                                                                                   \
-    do {                                                                                                  \
-        hipError_t e__ = (expr);                                                                          \
-        if (e__ != hipSuccess) return gl_fail((h), WRNN_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e__)); \
-    } while (0)
-const int GL_MAX_B = 65535;   // grid.y
-}  // namespace
 
 extern "C" {
 
@@ -446,35 +360,23 @@ int wrnn_griffin_create(const wrnn_mel_config *cfg, const wrnn_mel_features *f, 
     *out = h;
     h->cfg = *cfg;
     if (f->struct_size != sizeof(wrnn_mel_features))
-        return gl_fail(h, WRNN_ERR_INVALID, "features.struct_size = %u, this library's wrnn_mel_features has %zu bytes", f->struct_size, sizeof(wrnn_mel_features));
+        return wrnn_failf(h, WRNN_ERR_INVALID, "features.struct_size = %u, this library's wrnn_mel_features has %zu bytes", f->struct_size, sizeof(wrnn_mel_features));
     if (g->struct_size != sizeof(wrnn_griffin_config))
-        return gl_fail(h, WRNN_ERR_INVALID, "griffin.struct_size = %u, this library's wrnn_griffin_config has %zu bytes", g->struct_size, sizeof(wrnn_griffin_config));
+        return wrnn_failf(h, WRNN_ERR_INVALID, "griffin.struct_size = %u, this library's wrnn_griffin_config has %zu bytes", g->struct_size, sizeof(wrnn_griffin_config));
     h->feat = *f;
     h->gcfg = *g;
-    if (cfg->n_fft != WRNN_MEL_NFFT) return gl_fail(h, WRNN_ERR_UNSUPPORTED, "n_fft = %d: Griffin-Lim is built for n_fft = %d only", cfg->n_fft, WRNN_MEL_NFFT);
-    if (cfg->hop_length < 1 || !(cfg->min_level_db < 0.0f) || cfg->device < 0)
-        return gl_fail(h, WRNN_ERR_INVALID, "bad configuration: hop_length >= 1, min_level_db < 0, device >= 0");
-    if ((f->pad_mode != WRNN_MEL_PAD_REFLECT && f->pad_mode != WRNN_MEL_PAD_ZERO) || (f->magnitude_power != 1 && f->magnitude_power != 2))
-        return gl_fail(h, WRNN_ERR_INVALID, "bad features: pad_mode is WRNN_MEL_PAD_REFLECT or WRNN_MEL_PAD_ZERO, magnitude_power 1 or 2");
-    if (!(f->preemphasis >= 0.0f) || !(f->preemph_rescale >= 0.0f) || !(f->max_abs_value >= 0.0f) || !std::isfinite(f->preemphasis) ||
-        !std::isfinite(f->preemph_rescale) || !std::isfinite(f->max_abs_value) || !std::isfinite(f->ref_level_db))
-        return gl_fail(h, WRNN_ERR_INVALID, "bad features: preemphasis, preemph_rescale and max_abs_value are finite and >= 0, ref_level_db is finite");
-    if (f->fmax != 0.0f && !((double)f->fmax > (double)cfg->fmin && (double)f->fmax <= 0.5 * (double)cfg->sample_rate))
-        return gl_fail(h, WRNN_ERR_INVALID, "bad features: fmax = %g is not in (fmin, sample_rate / 2] (0 stands for sample_rate / 2)", (double)f->fmax);
+    if (const int rc = wrnn_mel_check(h, cfg, f, "Griffin-Lim")) return rc;
     if (!(g->power > 0.0f) || !std::isfinite(g->power) || g->n_iter_default < 0)
-        return gl_fail(h, WRNN_ERR_INVALID, "bad griffin configuration: power is finite and > 0, n_iter_default >= 0");
+        return wrnn_failf(h, WRNN_ERR_INVALID, "bad griffin configuration: power is finite and > 0, n_iter_default >= 0");
     WrnnMelTables tab;
     if (!wrnn_mel_build_tables(cfg->sample_rate, cfg->win_length, cfg->n_mels, (double)cfg->fmin, (double)f->fmax, &tab))
-        return gl_fail(h, WRNN_ERR_INVALID, "bad configuration: 1 <= win_length <= n_fft, 1 <= n_mels <= %d, 0 <= fmin < sample_rate / 2", WRNN_MEL_MAX_MELS);
+        return wrnn_failf(h, WRNN_ERR_INVALID, "bad configuration: 1 <= win_length <= n_fft, 1 <= n_mels <= %d, 0 <= fmin < sample_rate / 2", WRNN_MEL_MAX_MELS);
     std::vector<double> P;
-    const int rc = pseudo_inverse(mel_basis64(cfg->sample_rate, cfg->n_mels, (double)cfg->fmin, (double)f->fmax), cfg->n_mels, &P);
-    if (rc == 1) return gl_fail(h, WRNN_ERR_UNSUPPORTED, "a filterbank row is empty (n_mels = %d over this band is finer than the bins): the mel cannot be inverted", cfg->n_mels);
-    if (rc == 2) return gl_fail(h, WRNN_ERR_UNSUPPORTED, "the filterbank has no full row rank (the Cholesky factorisation of its Gram matrix failed)");
+    const int rc = pseudo_inverse(wrnn_dsp::slaney_basis(cfg->sample_rate, WRNN_MEL_NFFT, cfg->n_mels, (double)cfg->fmin, (double)f->fmax), cfg->n_mels, &P);
+    if (rc == 1) return wrnn_failf(h, WRNN_ERR_UNSUPPORTED, "a filterbank row is empty (n_mels = %d over this band is finer than the bins): the mel cannot be inverted", cfg->n_mels);
+    if (rc == 2) return wrnn_failf(h, WRNN_ERR_UNSUPPORTED, "the filterbank has no full row rank (the Cholesky factorisation of its Gram matrix failed)");
     h->pinv = std::move(P);
-    // the window of wrnn_mel_build_tables before its rounding to float32: the symmetric Hann window of win_length + 1 points without its last
-    const double pi = 3.141592653589793, wstep = (pi - (-pi)) / (double)cfg->win_length;
-    h->window.resize(cfg->win_length);
-    for (int i = 0; i < cfg->win_length; ++i) h->window[i] = 0.5 + 0.5 * std::cos((double)i * wstep + (-pi));
+    h->window = wrnn_dsp::hann_periodic(cfg->win_length);   // unrounded, where wrnn_mel_build_tables rounds it to float32
     h->tab = std::move(tab);
     return WRNN_OK;
 }
@@ -507,7 +409,7 @@ int wrnn_griffin_tables(const wrnn_griffin_handle *h, float *pinv, float *window
 }
 
 int wrnn_deemphasis(const float *wav_dev, int64_t n_max, const int32_t *n_dev, int32_t B, double k, float *out_dev, void *stream) {
-    if (!wav_dev || !n_dev || !out_dev || n_max < 1 || B < 1 || B > GL_MAX_B || !std::isfinite(k) || !(std::fabs(k) < 1.0)) return WRNN_ERR_INVALID;
+    if (!wav_dev || !n_dev || !out_dev || n_max < 1 || B < 1 || B > WRNN_MAX_GRID_Y || !std::isfinite(k) || !(std::fabs(k) < 1.0)) return WRNN_ERR_INVALID;
     return launch_deemphasis(wav_dev, (long)n_max, n_dev, 0, B, k, out_dev, (long)n_max, (hipStream_t)stream) == hipSuccess ? WRNN_OK : WRNN_ERR_HIP;
 }
 
@@ -515,63 +417,42 @@ int wrnn_griffin_lim(wrnn_griffin_handle *h, const float *mel_dev, const int32_t
                      int32_t phase_mode, uint64_t seed, const float *phases_dev, float *wav_out_dev, int64_t n_out_max,
                      float *magnitude_out_dev, void *stream) {
     if (!h) return WRNN_ERR_INVALID;
-    if (h->tab.window.empty()) return gl_fail(h, WRNN_ERR_STATE, "the handle's configuration was refused by wrnn_griffin_create");
+    if (h->tab.window.empty()) return wrnn_failf(h, WRNN_ERR_STATE, "the handle's configuration was refused by wrnn_griffin_create");
     if (n_iter < 0) n_iter = h->gcfg.n_iter_default;
     const int64_t n_wave = (int64_t)h->cfg.hop_length * (T_max - 1);
-    if (!mel_dev || !frames_dev || !wav_out_dev || B < 1 || B > GL_MAX_B || T_max < 1 || T_max > 65535 * 32 || n_out_max < 1 || n_out_max < n_wave ||
+    if (!mel_dev || !frames_dev || !wav_out_dev || B < 1 || B > WRNN_MAX_GRID_Y || T_max < 1 || T_max > 65535 * 32 || n_out_max < 1 || n_out_max < n_wave ||
         n_out_max >= ((int64_t)1 << 31) * THREADS)
-        return gl_fail(h, WRNN_ERR_INVALID, "bad arguments: device pointers, 1 <= B <= 65535, T_max >= 1, n_out_max >= max(1, hop (T_max - 1))");
+        return wrnn_failf(h, WRNN_ERR_INVALID, "bad arguments: device pointers, 1 <= B <= 65535, T_max >= 1, n_out_max >= max(1, hop (T_max - 1))");
     if (phase_mode != WRNN_GRIFFIN_PHASE_ZERO && phase_mode != WRNN_GRIFFIN_PHASE_PHILOX && phase_mode != WRNN_GRIFFIN_PHASE_INJECTED)
-        return gl_fail(h, WRNN_ERR_INVALID, "phase_mode %d is none of WRNN_GRIFFIN_PHASE_ZERO, _PHILOX, _INJECTED", phase_mode);
+        return wrnn_failf(h, WRNN_ERR_INVALID, "phase_mode %d is none of WRNN_GRIFFIN_PHASE_ZERO, _PHILOX, _INJECTED", phase_mode);
     if ((phase_mode == WRNN_GRIFFIN_PHASE_INJECTED) != (phases_dev != nullptr))
-        return gl_fail(h, WRNN_ERR_INVALID, "phases_dev goes with WRNN_GRIFFIN_PHASE_INJECTED, and with that mode only");
+        return wrnn_failf(h, WRNN_ERR_INVALID, "phases_dev goes with WRNN_GRIFFIN_PHASE_INJECTED, and with that mode only");
     hipStream_t s = (hipStream_t)stream;
-    GL_TRY(h, hipSetDevice(h->cfg.device));
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    WRNN_TRY(h, hipSetDevice(h->cfg.device));
     const int n_mels = h->cfg.n_mels, win = h->cfg.win_length;
     if (!h->dev) {
-        h->o_tw = up(h->window.size() * 8);
-        h->o_p = h->o_tw + up((size_t)WRNN_MEL_NFFT * 16);
-        const size_t total = h->o_p + up(h->pinv.size() * 8);
-        std::vector<char> img(total, 0);
-        memcpy(img.data(), h->window.data(), h->window.size() * 8);
-        double *tw = (double *)(img.data() + h->o_tw);
-        for (int k = 0; k < WRNN_MEL_NFFT; ++k) {
-            const double ang = 2.0 * 3.141592653589793 * (double)k / (double)WRNN_MEL_NFFT;
-            tw[2 * k] = std::cos(ang);
-            tw[2 * k + 1] = -std::sin(ang);
-        }
-        double *pt = (double *)(img.data() + h->o_p);
+        WrnnImage img;
+        img.put(h->window.data(), h->window.size() * 8);
+        const std::vector<double> tw = wrnn_dsp::twiddles(WRNN_MEL_NFFT);
+        h->o_tw = img.put(tw.data(), tw.size() * 8);
+        h->o_p = img.take(h->pinv.size() * 8);
+        double *pt = img.at<double>(h->o_p);
         for (int k = 0; k < NB; ++k)
             for (int m = 0; m < n_mels; ++m) pt[(size_t)m * NB + k] = h->pinv[(size_t)k * n_mels + m];
-        void *d = nullptr;
-        GL_TRY(h, hipMalloc(&d, total));
-        hipError_t e = hipMemcpy(d, img.data(), total, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(d);
-            return gl_fail(h, WRNN_ERR_HIP, "uploading the Griffin-Lim tables: %s", hipGetErrorString(e));
-        }
-        h->dev = d;
+        const hipError_t e = img.upload(&h->dev);
+        if (e != hipSuccess) return wrnn_failf(h, WRNN_ERR_HIP, "uploading the Griffin-Lim tables: %s", hipGetErrorString(e));
     }
     // S | taps | wave: the calls on one handle share them, so the caller orders those calls (one stream at a time)
-    const size_t n_S = up((size_t)B * T_max * NB * 8) / 8, n_taps = up((size_t)B * T_max * win * 8) / 8;
-    const size_t n_ws = n_S + n_taps + up((size_t)B * (size_t)(n_wave > 0 ? n_wave : 1) * 8) / 8;
-    if (n_ws > h->ws_cap) {
-        if (h->ws) {
-            GL_TRY(h, hipStreamSynchronize(s));   // growing is the one wait: an earlier call may still read the old buffer
-            GL_TRY(h, hipFree(h->ws));
-            h->ws = nullptr;
-            h->ws_cap = 0;
-        }
-        GL_TRY(h, hipMalloc((void **)&h->ws, n_ws * 8));
-        h->ws_cap = n_ws;
-    }
+    const size_t n_S = wrnn_up256((size_t)B * T_max * NB * 8) / 8, n_taps = wrnn_up256((size_t)B * T_max * win * 8) / 8;
+    const size_t n_ws = n_S + n_taps + wrnn_up256((size_t)B * (size_t)(n_wave > 0 ? n_wave : 1) * 8) / 8;
+    WRNN_TRY(h, h->ws.reserve(n_ws * 8, s));
+    double *ws = (double *)h->ws.p;
     GriffinArgs a{};
     const char *d = (const char *)h->dev;
     a.mel = mel_dev; a.frames = frames_dev;
     a.window = (const double *)d; a.twiddle = (const double2 *)(d + h->o_tw); a.pinv_t = (const double *)(d + h->o_p);
-    a.S = h->ws; a.S_out = magnitude_out_dev; a.taps = h->ws + n_S;
-    double *wave = h->ws + n_S + n_taps;
+    a.S = ws; a.S_out = magnitude_out_dev; a.taps = ws + n_S;
+    double *wave = ws + n_S + n_taps;
     a.wave = wave; a.n_wave = n_wave > 0 ? n_wave : 1;
     a.phases = phases_dev; a.seed = seed; a.phase_mode = phase_mode;
     a.T_max = T_max; a.n_mels = n_mels; a.hop = h->cfg.hop_length; a.win_length = win;
@@ -579,32 +460,32 @@ int wrnn_griffin_lim(wrnn_griffin_handle *h, const float *mel_dev, const int32_t
     a.min_level_db = h->cfg.min_level_db; a.ref_level_db = h->feat.ref_level_db; a.max_abs = h->feat.max_abs_value; a.power = h->gcfg.power;
     const dim3 fgrid((unsigned)T_max, (unsigned)B), block(THREADS);
     hipLaunchKernelGGL(griffin_magnitude_kernel, fgrid, block, 0, s, a);
-    GL_TRY(h, hipGetLastError());
+    WRNN_TRY(h, hipGetLastError());
     const double k = (double)h->feat.preemphasis;
     for (int it = 0; it <= n_iter; ++it) {
         if (it == 0) hipLaunchKernelGGL(griffin_frame_kernel<true>, fgrid, block, 0, s, a);
         else hipLaunchKernelGGL(griffin_frame_kernel<false>, fgrid, block, 0, s, a);
-        GL_TRY(h, hipGetLastError());
+        WRNN_TRY(h, hipGetLastError());
         // the last overlap-add writes the caller's buffer itself (zeros past every clip's end) unless the de-emphasis follows
         const bool to_caller = it == n_iter && k == 0.0;
         const long dst_n = to_caller ? (long)n_out_max : (long)a.n_wave;
         const dim3 ogrid((unsigned)((dst_n + THREADS - 1) / THREADS), (unsigned)B);
         if (to_caller) hipLaunchKernelGGL(griffin_ola_kernel<float>, ogrid, block, 0, s, a, wav_out_dev, dst_n);
         else hipLaunchKernelGGL(griffin_ola_kernel<double>, ogrid, block, 0, s, a, wave, dst_n);
-        GL_TRY(h, hipGetLastError());
+        WRNN_TRY(h, hipGetLastError());
     }
-    if (k != 0.0) GL_TRY(h, launch_deemphasis(wave, (long)a.n_wave, frames_dev, h->cfg.hop_length, B, k, wav_out_dev, (long)n_out_max, s));
+    if (k != 0.0) WRNN_TRY(h, launch_deemphasis(wave, (long)a.n_wave, frames_dev, h->cfg.hop_length, B, k, wav_out_dev, (long)n_out_max, s));
     return WRNN_OK;
 }
 
-const char *wrnn_griffin_last_error(const wrnn_griffin_handle *h) { return h ? h->err.c_str() : "null handle"; }
+const char *wrnn_griffin_last_error(const wrnn_griffin_handle *h) { return wrnn_last_error_of(h); }
 
 void wrnn_griffin_destroy(wrnn_griffin_handle *h) {
     if (!h) return;
-    if (h->dev || h->ws) {
+    if (h->dev || h->ws.p) {
         (void)hipSetDevice(h->cfg.device);
         if (h->dev) (void)hipFree(h->dev);
-        if (h->ws) (void)hipFree(h->ws);
+        h->ws.release();
     }
     delete h;
 }

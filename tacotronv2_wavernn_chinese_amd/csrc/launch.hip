@@ -5,7 +5,7 @@
 
 #include "team_common.h"
 
-int wrnn_fail(wrnn_handle *h, int code, const char *fmt, ...) {
+int wrnn_failf(wrnn_handle *h, int code, const char *fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -26,13 +26,13 @@ int wrnn_build_frame_tables(wrnn_handle *h, float *&buf, size_t &cap, const floa
     t.CM = buf; t.CA = t.CM + nCM; t.VM = t.CA + nCA; t.VA = t.VM + nVM; t.C2 = t.VA + nVA; t.C3 = t.C2 + nC2; t.C4 = t.C3 + nC3; t.REC = t.C4 + nC4;
     const float *w = h->wdev;
     const WrnnPacked &o = h->off;
-    WRNN_HIP_TRY(h, wrnn_launch_frame_linear(1, mels, (size_t)F * mel_T, 0, 0, w + o.I_t + (size_t)1 * H, H, nullptr, t.CM, (size_t)TP * H, TP, F, H, B, mel_T, mel_shift, s));
-    WRNN_HIP_TRY(h, wrnn_launch_frame_linear(0, aux, (size_t)T * R, R, T, w + o.I_t + (size_t)(1 + F) * H, H, w + o.I_b, t.CA, (size_t)T1 * H, T1, A, H, B, T, P, s));
-    WRNN_HIP_TRY(h, wrnn_launch_frame_linear(0, t.CM, (size_t)TP * H, H, TP, w + o.r1_wih_t, 3 * H, nullptr, t.VM, (size_t)TP * 3 * H, TP, H, 3 * H, B, T, P, s));
-    WRNN_HIP_TRY(h, wrnn_launch_frame_linear(0, t.CA, (size_t)T1 * H, H, T1, w + o.r1_wih_t, 3 * H, w + o.r1_bih, t.VA, (size_t)T1 * 3 * H, T1, H, 3 * H, B, T, P, s));
-    WRNN_HIP_TRY(h, wrnn_launch_frame_linear(0, aux + A, (size_t)T * R, R, T, w + o.r2_wih_t + (size_t)H * 3 * H, 3 * H, w + o.r2_bih, t.C2, (size_t)T1 * 3 * H, T1, A, 3 * H, B, T, P, s));
-    WRNN_HIP_TRY(h, wrnn_launch_frame_linear(0, aux + 2 * A, (size_t)T * R, R, T, w + o.fc1_t + (size_t)H * FC, FC, w + o.fc1_b, t.C3, (size_t)T1 * FC, T1, A, FC, B, T, P, s));
-    WRNN_HIP_TRY(h, wrnn_launch_frame_linear(0, aux + 3 * A, (size_t)T * R, R, T, w + o.fc2_t + (size_t)FC * FC, FC, w + o.fc2_b, t.C4, (size_t)T1 * FC, T1, A, FC, B, T, P, s));
+    WRNN_TRY(h, wrnn_launch_frame_linear(1, mels, (size_t)F * mel_T, 0, 0, w + o.I_t + (size_t)1 * H, H, nullptr, t.CM, (size_t)TP * H, TP, F, H, B, mel_T, mel_shift, s));
+    WRNN_TRY(h, wrnn_launch_frame_linear(0, aux, (size_t)T * R, R, T, w + o.I_t + (size_t)(1 + F) * H, H, w + o.I_b, t.CA, (size_t)T1 * H, T1, A, H, B, T, P, s));
+    WRNN_TRY(h, wrnn_launch_frame_linear(0, t.CM, (size_t)TP * H, H, TP, w + o.r1_wih_t, 3 * H, nullptr, t.VM, (size_t)TP * 3 * H, TP, H, 3 * H, B, T, P, s));
+    WRNN_TRY(h, wrnn_launch_frame_linear(0, t.CA, (size_t)T1 * H, H, T1, w + o.r1_wih_t, 3 * H, w + o.r1_bih, t.VA, (size_t)T1 * 3 * H, T1, H, 3 * H, B, T, P, s));
+    WRNN_TRY(h, wrnn_launch_frame_linear(0, aux + A, (size_t)T * R, R, T, w + o.r2_wih_t + (size_t)H * 3 * H, 3 * H, w + o.r2_bih, t.C2, (size_t)T1 * 3 * H, T1, A, 3 * H, B, T, P, s));
+    WRNN_TRY(h, wrnn_launch_frame_linear(0, aux + 2 * A, (size_t)T * R, R, T, w + o.fc1_t + (size_t)H * FC, FC, w + o.fc1_b, t.C3, (size_t)T1 * FC, T1, A, FC, B, T, P, s));
+    WRNN_TRY(h, wrnn_launch_frame_linear(0, aux + 3 * A, (size_t)T * R, R, T, w + o.fc2_t + (size_t)FC * FC, FC, w + o.fc2_b, t.C4, (size_t)T1 * FC, T1, A, FC, B, T, P, s));
     return WRNN_OK;
 }
 
@@ -55,9 +55,9 @@ int wrnn_run_team2_segments(wrnn_handle *h, WrnnTeamArgs &ta, float *cond, int64
     int n = 0;
     for (int64_t t0 = t_begin; t0 < t_end; t0 += seg, ++n) {
         const int64_t len = t_end - t0 < seg ? t_end - t0 : seg;
-        WRNN_HIP_TRY(h, wrnn_launch_cond_stream(ta.tabREC, ta.w + ta.off.ktab, ta.rows, cond, ta.n_rows, ta.T, ta.d.HOP, ta.total_len, t0, len, s));
+        WRNN_TRY(h, wrnn_launch_cond_stream(ta.tabREC, ta.w + ta.off.ktab, ta.rows, cond, ta.n_rows, ta.T, ta.d.HOP, ta.total_len, t0, len, s));
         ta.seg0 = t0; ta.seg_len = len;
-        WRNN_HIP_TRY(h, wrnn_gated_launch(h->cfg.device, s, h->mail, WRNN_MAIL_BYTES, h->ctl, TEAM_CTL_WORDS * sizeof(unsigned), [&] { return wrnn_launch_loop_team2(ta, s); }));
+        WRNN_TRY(h, wrnn_gated_launch(h->cfg.device, s, h->mail, WRNN_MAIL_BYTES, h->ctl, TEAM_CTL_WORDS * sizeof(unsigned), [&] { return wrnn_launch_loop_team2(ta, s); }));
     }
     if (launches) *launches = n;
     return WRNN_OK;

@@ -125,22 +125,7 @@ struct wrnn_dm_handle {
     std::string err;
 };
 
-#include <cstdarg>
 #include <map>
-static int dm_fail(wrnn_dm_handle *h, int code, const char *fmt, ...) {
-    char buf[400];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (h) h->err = buf;
-    return code;
-}
-#define DM_TRY(h, expr)                                                                                  \
-    do {                                                                                                 \
-        hipError_t e__ = (expr);                                                                         \
-        if (e__ != hipSuccess) return dm_fail((h), WRNN_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e__)); \
-    } while (0)
 
 extern "C" {
 
@@ -150,7 +135,7 @@ int wrnn_dm_create(int32_t hidden_size, int32_t quantisation, int32_t device, wr
     *out = h;
     h->H = hidden_size; h->Q = quantisation; h->device = device;
     if (hidden_size < 2 || hidden_size > 1024 || (hidden_size & 1) || quantisation < 2 || quantisation > 256)
-        return dm_fail(h, WRNN_ERR_INVALID, "unsupported sizes: hidden_size even and <= 1024, quantisation <= 256");
+        return wrnn_failf(h, WRNN_ERR_INVALID, "unsupported sizes: hidden_size even and <= 1024, quantisation <= 256");
     return WRNN_OK;
 }
 
@@ -165,7 +150,7 @@ void wrnn_dm_destroy(wrnn_dm_handle *h) {
     delete h;
 }
 
-const char *wrnn_dm_last_error(const wrnn_dm_handle *h) { return h ? h->err.c_str() : "null handle"; }
+const char *wrnn_dm_last_error(const wrnn_dm_handle *h) { return wrnn_last_error_of(h); }
 
 int wrnn_dm_load_weights(wrnn_dm_handle *h, const wrnn_tensor_desc *tensors, int32_t n) {
     if (!h || !tensors) return WRNN_ERR_INVALID;
@@ -175,10 +160,10 @@ int wrnn_dm_load_weights(wrnn_dm_handle *h, const wrnn_tensor_desc *tensors, int
         if (tensors[i].name && tensors[i].data) tv[tensors[i].name] = &tensors[i];
     auto get = [&](const char *name, int64_t numel, const float **out) -> int {
         auto it = tv.find(name);
-        if (it == tv.end()) return dm_fail(h, WRNN_ERR_MISSING_KEY, "state_dict key missing: %s", name);
+        if (it == tv.end()) return wrnn_failf(h, WRNN_ERR_MISSING_KEY, "state_dict key missing: %s", name);
         int64_t ne = 1;
         for (int i = 0; i < it->second->ndim; ++i) ne *= it->second->shape[i];
-        if (it->second->dtype != WRNN_DTYPE_F32 || ne != numel) return dm_fail(h, WRNN_ERR_INVALID, "%s: bad dtype/shape", name);
+        if (it->second->dtype != WRNN_DTYPE_F32 || ne != numel) return wrnn_failf(h, WRNN_ERR_INVALID, "%s: bad dtype/shape", name);
         *out = (const float *)it->second->data;
         return WRNN_OK;
     };
@@ -210,10 +195,10 @@ int wrnn_dm_load_weights(wrnn_dm_handle *h, const wrnn_tensor_desc *tensors, int
         (rc = put_v("I_coarse.weight", a.oIc, 3 * S * 2)) || (rc = put_v("I_fine.weight", a.oIf, 3 * S * 3)) ||
         (rc = put_v("bias_u", a.obu, H)) || (rc = put_v("bias_r", a.obr, H)) || (rc = put_v("bias_e", a.obe, H)))
         return rc;
-    DM_TRY(h, hipSetDevice(h->device));
+    WRNN_TRY(h, hipSetDevice(h->device));
     if (h->wdev) { (void)hipFree(h->wdev); h->wdev = nullptr; }
-    DM_TRY(h, hipMalloc(&h->wdev, cur * sizeof(float)));
-    DM_TRY(h, hipMemcpy(h->wdev, pk.data(), cur * sizeof(float), hipMemcpyHostToDevice));
+    WRNN_TRY(h, hipMalloc(&h->wdev, cur * sizeof(float)));
+    WRNN_TRY(h, hipMemcpy(h->wdev, pk.data(), cur * sizeof(float), hipMemcpyHostToDevice));
     // ---- team kernel layouts (loop_dm_team.hip) ----
     if (wrnn_dm_team_supported(H, Q)) {
         const int U = S / 32, QW = Q / 32, CPL = H / 64, PS = CPL / 2, NR = 3 * CPL * 4;
@@ -250,14 +235,14 @@ int wrnn_dm_load_weights(wrnn_dm_handle *h, const wrnn_tensor_desc *tensors, int
         }
         auto upload = [&](float *&dst, const std::vector<float> &src) -> int {
             if (dst) { (void)hipFree(dst); dst = nullptr; }
-            DM_TRY(h, hipMalloc(&dst, src.size() * sizeof(float)));
-            DM_TRY(h, hipMemcpy(dst, src.data(), src.size() * sizeof(float), hipMemcpyHostToDevice));
+            WRNN_TRY(h, hipMalloc(&dst, src.size() * sizeof(float)));
+            WRNN_TRY(h, hipMemcpy(dst, src.data(), src.size() * sizeof(float), hipMemcpyHostToDevice));
             return WRNN_OK;
         };
         if ((rc = upload(h->team_w, tw)) || (rc = upload(h->team_lds, tl))) return rc;
         if (!h->mail) {
-            DM_TRY(h, hipMalloc(&h->mail, (size_t)WRNN_DM_MAIL_GRANULES * sizeof(unsigned long long)));
-            DM_TRY(h, hipMalloc(&h->ctl, 2 * TEAM_CTL_WORDS * sizeof(unsigned)));
+            WRNN_TRY(h, hipMalloc(&h->mail, (size_t)WRNN_DM_MAIL_GRANULES * sizeof(unsigned long long)));
+            WRNN_TRY(h, hipMalloc(&h->ctl, 2 * TEAM_CTL_WORDS * sizeof(unsigned)));
         }
     }
     h->loaded = true;
@@ -266,57 +251,57 @@ int wrnn_dm_load_weights(wrnn_dm_handle *h, const wrnn_tensor_desc *tensors, int
 
 int wrnn_dm_set_kernel(wrnn_dm_handle *h, int32_t kernel) {
     if (!h) return WRNN_ERR_INVALID;
-    if (kernel < 0 || kernel > 2) return dm_fail(h, WRNN_ERR_INVALID, "kernel must be 0 (auto), 1 (single workgroup) or 2 (team)");
+    if (kernel < 0 || kernel > 2) return wrnn_failf(h, WRNN_ERR_INVALID, "kernel must be 0 (auto), 1 (single workgroup) or 2 (team)");
     if (kernel == 2 && !wrnn_dm_team_supported(h->H, h->Q))
-        return dm_fail(h, WRNN_ERR_INVALID, "team kernel needs hidden_size in {512,640,768,896} and quantisation in {64,128,192,256}");
+        return wrnn_failf(h, WRNN_ERR_INVALID, "team kernel needs hidden_size in {512,640,768,896} and quantisation in {64,128,192,256}");
     h->kernel = kernel;
     return WRNN_OK;
 }
 
 int wrnn_dm_generate(wrnn_dm_handle *h, int64_t seq_len, int32_t noise_mode, uint64_t seed, const float *noise_dev,
                      int32_t *coarse_out_dev, int32_t *fine_out_dev, void *stream) {
-    if (!h || seq_len < 0) return dm_fail(h, WRNN_ERR_INVALID, "wrnn_dm_generate: bad arguments");
-    if (!h->loaded) return dm_fail(h, WRNN_ERR_STATE, "weights not loaded");
-    if (noise_mode < 0 || noise_mode > 2) return dm_fail(h, WRNN_ERR_INVALID, "bad noise_mode");
+    if (!h || seq_len < 0) return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_dm_generate: bad arguments");
+    if (!h->loaded) return wrnn_failf(h, WRNN_ERR_STATE, "weights not loaded");
+    if (noise_mode < 0 || noise_mode > 2) return wrnn_failf(h, WRNN_ERR_INVALID, "bad noise_mode");
     if (seq_len == 0) return WRNN_OK;   // nothing to write or to draw: an allocator hands out null for the empty buffers of such a call
-    if (!coarse_out_dev || !fine_out_dev) return dm_fail(h, WRNN_ERR_INVALID, "wrnn_dm_generate: bad arguments");
-    if (noise_mode == WRNN_NOISE_INJECTED && !noise_dev) return dm_fail(h, WRNN_ERR_INVALID, "WRNN_NOISE_INJECTED needs a noise pointer");
-    DM_TRY(h, hipSetDevice(h->device));
+    if (!coarse_out_dev || !fine_out_dev) return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_dm_generate: bad arguments");
+    if (noise_mode == WRNN_NOISE_INJECTED && !noise_dev) return wrnn_failf(h, WRNN_ERR_INVALID, "WRNN_NOISE_INJECTED needs a noise pointer");
+    WRNN_TRY(h, hipSetDevice(h->device));
     WrnnDmArgs a = h->args;
     a.w = h->wdev; a.H = h->H; a.Q = h->Q; a.seq_len = seq_len; a.noise_mode = noise_mode; a.seed = seed; a.noise = noise_dev;
     a.coarse = coarse_out_dev; a.fine = fine_out_dev;
     const bool team = h->kernel == 2 || (h->kernel == 0 && wrnn_dm_team_supported(h->H, h->Q));
     if (team) {
         hipStream_t s = (hipStream_t)stream;
-        DM_TRY(h, hipMemsetAsync(h->mail, 0, (size_t)WRNN_DM_MAIL_GRANULES * sizeof(unsigned long long), s));
-        DM_TRY(h, hipMemsetAsync(h->ctl, 0, 2 * TEAM_CTL_WORDS * sizeof(unsigned), s));
+        WRNN_TRY(h, hipMemsetAsync(h->mail, 0, (size_t)WRNN_DM_MAIL_GRANULES * sizeof(unsigned long long), s));
+        WRNN_TRY(h, hipMemsetAsync(h->ctl, 0, 2 * TEAM_CTL_WORDS * sizeof(unsigned), s));
         WrnnDmTeamArgs ta{};
         ta.base = a; ta.team_w = h->team_w; ta.team_lds = h->team_lds; ta.mail = h->mail; ta.ctl = h->ctl; ta.err = h->ctl + TEAM_CTL_WORDS;
         // team kernels of one device are ordered behind each other, whatever handle / stream launches them (wavernn_amd.h)
-        DM_TRY(h, wrnn_team_gate_enter(h->device, s));
+        WRNN_TRY(h, wrnn_team_gate_enter(h->device, s));
         const hipError_t le = wrnn_launch_dm_team(ta, s);
         const hipError_t ge = wrnn_team_gate_leave(h->device, s);
-        DM_TRY(h, le);
-        DM_TRY(h, ge);
+        WRNN_TRY(h, le);
+        WRNN_TRY(h, ge);
         return WRNN_OK;
     }
     (void)hipGetLastError();
     hipLaunchKernelGGL(dm_loop_kernel, dim3(1), dim3(DM_THREADS), 0, (hipStream_t)stream, a);
-    DM_TRY(h, hipGetLastError());
+    WRNN_TRY(h, hipGetLastError());
     return WRNN_OK;
 }
 
 /* device-side error word of the last team-kernel call (0 = ok); blocks until the stream work is done */
 int wrnn_dm_sync_status(wrnn_dm_handle *h, void *stream) {
     if (!h) return WRNN_ERR_INVALID;
-    DM_TRY(h, hipSetDevice(h->device));
-    DM_TRY(h, hipStreamSynchronize((hipStream_t)stream));
+    WRNN_TRY(h, hipSetDevice(h->device));
+    WRNN_TRY(h, hipStreamSynchronize((hipStream_t)stream));
     if (!h->ctl) return WRNN_OK;
     unsigned errw = 0;
-    DM_TRY(h, hipMemcpy(&errw, h->ctl + TEAM_CTL_WORDS, sizeof(errw), hipMemcpyDeviceToHost));
+    WRNN_TRY(h, hipMemcpy(&errw, h->ctl + TEAM_CTL_WORDS, sizeof(errw), hipMemcpyDeviceToHost));
     if (errw == WRNN_DEVERR_BUSY)
-        return dm_fail(h, WRNN_ERR_BUSY, "the team kernel's 32 workgroups did not all become resident: the GPU is shared with another kernel (retry, or wrnn_dm_set_kernel(h, 1))");
-    if (errw) return dm_fail(h, WRNN_ERR_TIMEOUT, "device-side bounded spin gave up (code %u)", errw);
+        return wrnn_failf(h, WRNN_ERR_BUSY, "the team kernel's 32 workgroups did not all become resident: the GPU is shared with another kernel (retry, or wrnn_dm_set_kernel(h, 1))");
+    if (errw) return wrnn_failf(h, WRNN_ERR_TIMEOUT, "device-side bounded spin gave up (code %u)", errw);
     return WRNN_OK;
 }
 

@@ -10,19 +10,13 @@
 // spectrum, ref_level_db and the symmetric normalisation.  The peak comes from melspec_peak_kernel, one launch in front.
 #include <cmath>
 
+#include "dsp_device.h"
+#include "dsp_tables.h"
 #include "mel_internal.h"
 
 namespace {
 
 constexpr int NC = WRNN_MEL_NFFT / 2;   // complex points
-
-__device__ inline float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-
-// base-4 digit reversal of a 10-bit index: bit reversal, then the two bits of every digit swapped back
-__device__ inline int rev4(int k) {
-    const unsigned r = __brev((unsigned)k) >> 22;
-    return (int)(((r & 0x2AAu) >> 1) | ((r & 0x155u) << 1));
-}
 
 // sample j of the pre-emphasised clip, 0 <= j < n: x[j] - k x[j-1] with x[-1] = 0.  The peak launch and the tap gather share it.
 __device__ inline float preemph_at(const float *x, long j, float k) { return x[j] - k * (j > 0 ? x[j - 1] : 0.0f); }
@@ -100,7 +94,8 @@ __global__ void __launch_bounds__(WRNN_MEL_THREADS) melspec_kernel(WrnnMelArgs a
         }
         z[rev4(k)] = make_float2(v[0], v[1]);
     }
-    // five radix-4 passes, one butterfly per thread and pass; W_4 = -i
+    // five radix-4 passes, one butterfly per thread and pass; W_4 = -i.  (radix4_1024 of dsp_device.h is this loop as a function; called
+    // from here the compiler schedules this kernel differently, so the passes stay inline and the machine code stays what it was.)
 #pragma unroll
     for (int s = 0; s < 5; ++s) {
         __syncthreads();
@@ -178,26 +173,6 @@ __global__ void __launch_bounds__(WRNN_MEL_THREADS) melspec_kernel(WrnnMelArgs a
     }
 }
 
-// np.linspace(start, stop, num): arange * step + start, last point set to stop
-std::vector<double> linspace(double start, double stop, int num) {
-    std::vector<double> y(num);
-    const double step = (stop - start) / (double)(num - 1);
-    for (int i = 0; i < num; ++i) y[i] = (double)i * step + start;
-    y[num - 1] = stop;
-    return y;
-}
-
-// Slaney mel scale (librosa htk=False): linear below 1 kHz, 200/3 Hz per mel; log above, 27 mels per factor 6.4
-const double F_SP = 200.0 / 3.0, MIN_LOG_HZ = 1000.0;
-double hz_to_mel(double f) {
-    const double min_log_mel = MIN_LOG_HZ / F_SP, logstep = std::log(6.4) / 27.0;
-    return f >= MIN_LOG_HZ ? min_log_mel + std::log(f / MIN_LOG_HZ) / logstep : f / F_SP;
-}
-double mel_to_hz(double m) {
-    const double min_log_mel = MIN_LOG_HZ / F_SP, logstep = std::log(6.4) / 27.0;
-    return m >= min_log_mel ? MIN_LOG_HZ * std::exp(logstep * (m - min_log_mel)) : F_SP * m;
-}
-
 }  // namespace
 
 bool wrnn_mel_build_tables(int sample_rate, int win_length, int n_mels, double fmin, double fmax_arg, WrnnMelTables *out) {
@@ -206,31 +181,18 @@ bool wrnn_mel_build_tables(int sample_rate, int win_length, int n_mels, double f
     if (sample_rate < 1 || win_length < 1 || win_length > N || n_mels < 1 || n_mels > WRNN_MEL_MAX_MELS || !(fmin >= 0.0) || !(fmin < fmax) ||
         !(fmax <= nyquist))
         return false;
-    // scipy.signal.get_window('hann', win_length, fftbins=True): the symmetric window of win_length + 1 points without its last one
-    out->window.resize(win_length);
-    const double pi = 3.141592653589793;
-    const double wstep = (pi - (-pi)) / (double)win_length;
-    for (int i = 0; i < win_length; ++i) out->window[i] = (float)(0.5 + 0.5 * std::cos((double)i * wstep + (-pi)));
-    out->twiddle.resize(2 * (size_t)N);
-    for (int k = 0; k < N; ++k) {
-        const double ang = 2.0 * pi * (double)k / (double)N;
-        out->twiddle[2 * k] = (float)std::cos(ang);
-        out->twiddle[2 * k + 1] = (float)-std::sin(ang);
-    }
-    // librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax, htk=False, norm=1); the bin frequencies run to sr / 2 whatever fmax is
-    const std::vector<double> fftfreqs = linspace(0.0, nyquist, 1 + N / 2);
-    std::vector<double> mel_f = linspace(hz_to_mel(fmin), hz_to_mel(fmax), n_mels + 2);
-    for (double &m : mel_f) m = mel_to_hz(m);
+    // the shared float64 tables, rounded to float32 once
+    const std::vector<double> window = wrnn_dsp::hann_periodic(win_length), twiddle = wrnn_dsp::twiddles(N);
+    out->window.assign(window.begin(), window.end());
+    out->twiddle.assign(twiddle.begin(), twiddle.end());
+    const std::vector<double> basis = wrnn_dsp::slaney_basis(sample_rate, N, n_mels, fmin, fmax_arg);
     out->rows.assign(3 * (size_t)n_mels, 0);
     out->weights.clear();
     for (int i = 0; i < n_mels; ++i) {
-        const double fd0 = mel_f[i + 1] - mel_f[i], fd1 = mel_f[i + 2] - mel_f[i + 1], enorm = 2.0 / (mel_f[i + 2] - mel_f[i]);
         int first = -1, last = -1;
         std::vector<float> row(1 + N / 2, 0.0f);
         for (int k = 0; k <= N / 2; ++k) {
-            const double lower = -(mel_f[i] - fftfreqs[k]) / fd0, upper = (mel_f[i + 2] - fftfreqs[k]) / fd1;
-            const double w = std::fmax(0.0, std::fmin(lower, upper)) * enorm;
-            row[k] = (float)w;
+            row[k] = (float)basis[(size_t)i * (1 + N / 2) + k];
             if (row[k] != 0.0f) {
                 if (first < 0) first = k;
                 last = k;

@@ -15,14 +15,11 @@
 // Reading x[j .. j + 3] is one 16-byte broadcast, x[j + tau] is consecutive across the lanes: no bank conflicts.
 #include <climits>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <string>
 
-#include <hip/hip_runtime.h>
-
-#include "../../include/wavernn_amd.h"
+#include "dsp_device.h"
+#include "handle_common.h"
 
 namespace {
 
@@ -179,25 +176,6 @@ __global__ void __launch_bounds__(THREADS) pitch_pair_kernel(PitchPairArgs g) {
     g.cents[(long)b * g.stride + t] = c;
 }
 
-// The sums of N values per thread, to every thread: one fixed pairwise tree over the thread index for all N (acc holds N * THREADS).
-template <int N>
-__device__ inline void block_sums(double (&v)[N], double *acc) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < N; ++k) acc[k * THREADS + tid] = v[k];
-    for (int d = THREADS / 2; d > 0; d >>= 1) {
-        __syncthreads();
-        if (tid < d) {
-#pragma unroll
-            for (int k = 0; k < N; ++k) acc[k * THREADS + tid] += acc[k * THREADS + tid + d];
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = acc[k * THREADS];
-    __syncthreads();
-}
-
 // One workgroup per pair.  Thread i takes frames i, i + 256, ... in ascending order, then the threads are added in a fixed tree: the
 // order depends on a frame's index alone.  Two passes: the counts, the squared cents and the means of log2 f0, then the central moments.
 __global__ void __launch_bounds__(THREADS) pitch_summary_kernel(PitchPairArgs g) {
@@ -223,7 +201,7 @@ __global__ void __launch_bounds__(THREADS) pitch_summary_kernel(PitchPairArgs g)
         }
     }
     double first[8] = {n_t, n_s, n_v, n_vde, n_gpe, c2, lt, ls};
-    block_sums(first, acc);
+    block_sums<THREADS>(first, acc);
     n_t = first[0]; n_s = first[1]; n_v = first[2]; n_vde = first[3]; n_gpe = first[4]; c2 = first[5]; lt = first[6]; ls = first[7];
     const double mt = n_v > 0.0 ? lt / n_v : 0.0, ms = n_v > 0.0 ? ls / n_v : 0.0;
     double cov = 0.0, var_t = 0.0, var_s = 0.0;
@@ -237,7 +215,7 @@ __global__ void __launch_bounds__(THREADS) pitch_summary_kernel(PitchPairArgs g)
         }
     }
     double second[3] = {cov, var_t, var_s};
-    block_sums(second, acc);
+    block_sums<THREADS>(second, acc);
     cov = second[0]; var_t = second[1]; var_s = second[2];
     if (tid != 0) return;
     double *o = g.summary + (long)b * WRNN_PITCH_FIELDS;
@@ -264,28 +242,11 @@ struct wrnn_pitch_handle {
     wrnn_pitch_config cfg{};
     bool ok = false;                  // false while the configuration is refused
     int tau_min = 0, tau_max = 0;
-    float *ws = nullptr;              // the per-frame rows of a score call without frames_dev, grown on demand
-    size_t ws_cap = 0;
+    WrnnScratch ws;                   // the per-frame rows of a score call without frames_dev, grown on demand
     std::string err;
 };
 
 namespace {
-int pt_fail(wrnn_pitch_handle *h, int code, const char *fmt, ...) {
-    char buf[400];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (h) h->err = buf;
-    return code;
-}
-#define PT_TRY(h, expr)                                                                                   \
-    do {                                                                                                  \
-        hipError_t e__ = (expr);                                                                          \
-        if (e__ != hipSuccess) return pt_fail((h), WRNN_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e__)); \
-    } while (0)
-const int PT_MAX_B = 65535;   // grid.y
-
 int64_t pt_frames(const wrnn_pitch_handle *h, int64_t n) { return n > 0 ? 1 + n / h->cfg.hop : 0; }
 
 int pt_launch_track(wrnn_pitch_handle *h, const float *a, const float *b, float *f0_a, float *ap_a, float *f0_b, float *ap_b, int64_t n_max,
@@ -299,7 +260,7 @@ int pt_launch_track(wrnn_pitch_handle *h, const float *a, const float *b, float 
     g.sample_rate = (double)c.sample_rate; g.threshold = c.threshold; g.silence_rms = c.silence_rms;
     const size_t lds = (size_t)(h->tau_max + 3) * 8 + (size_t)c.frame_length * 4;
     hipLaunchKernelGGL(pitch_track_kernel, dim3((unsigned)g.T_max, (unsigned)B, b ? 2u : 1u), dim3(THREADS), lds, s, g);
-    PT_TRY(h, hipGetLastError());
+    WRNN_TRY(h, hipGetLastError());
     return WRNN_OK;
 }
 }  // namespace
@@ -311,26 +272,26 @@ int wrnn_pitch_create(const wrnn_pitch_config *cfg, wrnn_pitch_handle **out) {
     wrnn_pitch_handle *h = new wrnn_pitch_handle();
     *out = h;
     if (cfg->struct_size != sizeof(wrnn_pitch_config))
-        return pt_fail(h, WRNN_ERR_INVALID, "struct_size = %u, this library's wrnn_pitch_config has %zu bytes", cfg->struct_size, sizeof(wrnn_pitch_config));
+        return wrnn_failf(h, WRNN_ERR_INVALID, "struct_size = %u, this library's wrnn_pitch_config has %zu bytes", cfg->struct_size, sizeof(wrnn_pitch_config));
     h->cfg = *cfg;
     if (cfg->sample_rate < 1 || cfg->hop < 1)
-        return pt_fail(h, WRNN_ERR_INVALID, "sample_rate = %d, hop = %d: both are at least 1", cfg->sample_rate, cfg->hop);
+        return wrnn_failf(h, WRNN_ERR_INVALID, "sample_rate = %d, hop = %d: both are at least 1", cfg->sample_rate, cfg->hop);
     if (!std::isfinite(cfg->fmin) || !std::isfinite(cfg->fmax) || !(cfg->fmin < cfg->fmax))
-        return pt_fail(h, WRNN_ERR_INVALID, "fmin = %g, fmax = %g: finite, and fmin < fmax", cfg->fmin, cfg->fmax);
+        return wrnn_failf(h, WRNN_ERR_INVALID, "fmin = %g, fmax = %g: finite, and fmin < fmax", cfg->fmin, cfg->fmax);
     const double lo = std::ceil((double)cfg->sample_rate / cfg->fmax), hi = std::floor((double)cfg->sample_rate / cfg->fmin);
-    if (lo < 1.0) return pt_fail(h, WRNN_ERR_INVALID, "tau_min = ceil(sample_rate / fmax) = %g: a lag is at least 1", lo);
-    if (!(cfg->fmin > 0.0)) return pt_fail(h, WRNN_ERR_INVALID, "fmin = %g: tau_max = floor(sample_rate / fmin) needs fmin > 0", cfg->fmin);
-    if (lo > hi) return pt_fail(h, WRNN_ERR_INVALID, "tau_min = %g > tau_max = %g: no lag lies between sample_rate / fmax and sample_rate / fmin", lo, hi);
-    if (!(cfg->threshold > 0.0 && cfg->threshold < 1.0)) return pt_fail(h, WRNN_ERR_INVALID, "threshold = %g is outside (0, 1)", cfg->threshold);
+    if (lo < 1.0) return wrnn_failf(h, WRNN_ERR_INVALID, "tau_min = ceil(sample_rate / fmax) = %g: a lag is at least 1", lo);
+    if (!(cfg->fmin > 0.0)) return wrnn_failf(h, WRNN_ERR_INVALID, "fmin = %g: tau_max = floor(sample_rate / fmin) needs fmin > 0", cfg->fmin);
+    if (lo > hi) return wrnn_failf(h, WRNN_ERR_INVALID, "tau_min = %g > tau_max = %g: no lag lies between sample_rate / fmax and sample_rate / fmin", lo, hi);
+    if (!(cfg->threshold > 0.0 && cfg->threshold < 1.0)) return wrnn_failf(h, WRNN_ERR_INVALID, "threshold = %g is outside (0, 1)", cfg->threshold);
     if (!(cfg->silence_rms >= 0.0) || !std::isfinite(cfg->silence_rms))
-        return pt_fail(h, WRNN_ERR_INVALID, "silence_rms = %g: finite and at least 0", cfg->silence_rms);
-    if (!(cfg->gpe_ratio > 0.0) || !std::isfinite(cfg->gpe_ratio)) return pt_fail(h, WRNN_ERR_INVALID, "gpe_ratio = %g: finite and above 0", cfg->gpe_ratio);
-    if (cfg->window < 1) return pt_fail(h, WRNN_ERR_INVALID, "window = %d: at least 1", cfg->window);
+        return wrnn_failf(h, WRNN_ERR_INVALID, "silence_rms = %g: finite and at least 0", cfg->silence_rms);
+    if (!(cfg->gpe_ratio > 0.0) || !std::isfinite(cfg->gpe_ratio)) return wrnn_failf(h, WRNN_ERR_INVALID, "gpe_ratio = %g: finite and above 0", cfg->gpe_ratio);
+    if (cfg->window < 1) return wrnn_failf(h, WRNN_ERR_INVALID, "window = %d: at least 1", cfg->window);
     const int fl = cfg->frame_length;
     if (fl != 512 && fl != 1024 && fl != 2048 && fl != 4096)
-        return pt_fail(h, WRNN_ERR_UNSUPPORTED, "frame_length = %d is none of 512, 1024, 2048, 4096", fl);
+        return wrnn_failf(h, WRNN_ERR_UNSUPPORTED, "frame_length = %d is none of 512, 1024, 2048, 4096", fl);
     if ((double)cfg->window + hi + 1.0 > (double)fl)
-        return pt_fail(h, WRNN_ERR_UNSUPPORTED, "window + tau_max + 1 = %d + %g + 1 exceeds frame_length = %d", cfg->window, hi, fl);
+        return wrnn_failf(h, WRNN_ERR_UNSUPPORTED, "window + tau_max + 1 = %d + %g + 1 exceeds frame_length = %d", cfg->window, hi, fl);
     h->tau_min = (int)lo;
     h->tau_max = (int)hi;
     h->ok = true;
@@ -352,62 +313,50 @@ int wrnn_pitch_lags(const wrnn_pitch_handle *h, int32_t *tau_min, int32_t *tau_m
 int wrnn_pitch_track(wrnn_pitch_handle *h, const float *wav_dev, int64_t n_max, const int32_t *n_dev, int32_t B, float *f0_dev,
                      float *aperiodicity_dev, int64_t frames_stride, void *stream) {
     if (!h) return WRNN_ERR_INVALID;
-    if (!h->ok) return pt_fail(h, WRNN_ERR_STATE, "the handle's configuration was refused by wrnn_pitch_create");
-    if (!wav_dev || !n_dev || !f0_dev || B < 1 || B > PT_MAX_B || n_max < 1 || n_max > INT32_MAX)
-        return pt_fail(h, WRNN_ERR_INVALID, "bad arguments: device pointers, 1 <= B <= 65535, 1 <= n_max < 2^31");
+    if (!h->ok) return wrnn_failf(h, WRNN_ERR_STATE, "the handle's configuration was refused by wrnn_pitch_create");
+    if (!wav_dev || !n_dev || !f0_dev || B < 1 || B > WRNN_MAX_GRID_Y || n_max < 1 || n_max > INT32_MAX)
+        return wrnn_failf(h, WRNN_ERR_INVALID, "bad arguments: device pointers, 1 <= B <= 65535, 1 <= n_max < 2^31");
     if (frames_stride < pt_frames(h, n_max))
-        return pt_fail(h, WRNN_ERR_INVALID, "frames_stride = %lld: a row holds %lld frames for n_max = %lld", (long long)frames_stride,
+        return wrnn_failf(h, WRNN_ERR_INVALID, "frames_stride = %lld: a row holds %lld frames for n_max = %lld", (long long)frames_stride,
                        (long long)pt_frames(h, n_max), (long long)n_max);
-    PT_TRY(h, hipSetDevice(h->cfg.device));
+    WRNN_TRY(h, hipSetDevice(h->cfg.device));
     return pt_launch_track(h, wav_dev, nullptr, f0_dev, aperiodicity_dev, nullptr, nullptr, n_max, n_dev, B, frames_stride, (hipStream_t)stream);
 }
 
 int wrnn_pitch_score(wrnn_pitch_handle *h, const float *target_dev, const float *test_dev, int64_t n_max, const int32_t *n_dev, int32_t B,
                      double *summary_dev, float *frames_dev, int64_t frames_stride, void *stream) {
     if (!h) return WRNN_ERR_INVALID;
-    if (!h->ok) return pt_fail(h, WRNN_ERR_STATE, "the handle's configuration was refused by wrnn_pitch_create");
-    if (!target_dev || !test_dev || !n_dev || !summary_dev || B < 1 || B > PT_MAX_B || n_max < 1 || n_max > INT32_MAX)
-        return pt_fail(h, WRNN_ERR_INVALID, "bad arguments: device pointers, 1 <= B <= 65535, 1 <= n_max < 2^31");
+    if (!h->ok) return wrnn_failf(h, WRNN_ERR_STATE, "the handle's configuration was refused by wrnn_pitch_create");
+    if (!target_dev || !test_dev || !n_dev || !summary_dev || B < 1 || B > WRNN_MAX_GRID_Y || n_max < 1 || n_max > INT32_MAX)
+        return wrnn_failf(h, WRNN_ERR_INVALID, "bad arguments: device pointers, 1 <= B <= 65535, 1 <= n_max < 2^31");
     const int64_t T = pt_frames(h, n_max), total = 5 * T;
     if (frames_dev && frames_stride < total)
-        return pt_fail(h, WRNN_ERR_INVALID, "frames_stride = %lld: a row of the per-frame buffer holds %lld values for n_max = %lld", (long long)frames_stride,
+        return wrnn_failf(h, WRNN_ERR_INVALID, "frames_stride = %lld: a row of the per-frame buffer holds %lld values for n_max = %lld", (long long)frames_stride,
                        (long long)total, (long long)n_max);
     hipStream_t s = (hipStream_t)stream;
-    PT_TRY(h, hipSetDevice(h->cfg.device));
+    WRNN_TRY(h, hipSetDevice(h->cfg.device));
     const int64_t stride = frames_dev ? frames_stride : total;
-    if (!frames_dev) {
-        const size_t need = (size_t)B * (size_t)total * 4;
-        if (need > h->ws_cap) {
-            if (h->ws) {
-                PT_TRY(h, hipStreamSynchronize(s));   // growing is the one wait: an earlier call may still read the old buffer
-                PT_TRY(h, hipFree(h->ws));
-                h->ws = nullptr;
-                h->ws_cap = 0;
-            }
-            PT_TRY(h, hipMalloc((void **)&h->ws, need));
-            h->ws_cap = need;
-        }
-    }
-    float *frames = frames_dev ? frames_dev : h->ws;
+    if (!frames_dev) WRNN_TRY(h, h->ws.reserve((size_t)B * (size_t)total * 4, s));
+    float *frames = frames_dev ? frames_dev : (float *)h->ws.p;
     const int rc = pt_launch_track(h, target_dev, test_dev, frames, frames + T, frames + 2 * T, frames + 3 * T, n_max, n_dev, B, stride, s);
     if (rc != WRNN_OK) return rc;
     PitchPairArgs p{};
     p.frames = frames; p.cents = frames + 4 * T; p.n_samples = n_dev; p.summary = summary_dev; p.n_max = n_max; p.stride = stride;
     p.T_max = (int32_t)T; p.hop = h->cfg.hop; p.gpe_ratio = h->cfg.gpe_ratio;
     hipLaunchKernelGGL(pitch_pair_kernel, dim3((unsigned)((T + THREADS - 1) / THREADS), (unsigned)B), dim3(THREADS), 0, s, p);
-    PT_TRY(h, hipGetLastError());
+    WRNN_TRY(h, hipGetLastError());
     hipLaunchKernelGGL(pitch_summary_kernel, dim3((unsigned)B), dim3(THREADS), 0, s, p);
-    PT_TRY(h, hipGetLastError());
+    WRNN_TRY(h, hipGetLastError());
     return WRNN_OK;
 }
 
-const char *wrnn_pitch_last_error(const wrnn_pitch_handle *h) { return h ? h->err.c_str() : "null handle"; }
+const char *wrnn_pitch_last_error(const wrnn_pitch_handle *h) { return wrnn_last_error_of(h); }
 
 void wrnn_pitch_destroy(wrnn_pitch_handle *h) {
     if (!h) return;
-    if (h->ws) {
+    if (h->ws.p) {
         (void)hipSetDevice(h->cfg.device);
-        (void)hipFree(h->ws);
+        h->ws.release();
     }
     delete h;
 }

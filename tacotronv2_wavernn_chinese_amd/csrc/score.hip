@@ -19,15 +19,13 @@
 // LDS per workgroup: 2 clips x FPW frames x (n_fft / 2) double2 = 32 KiB at n_fft 2048, 16 KiB at 1024, 512 and 256, plus 12 doubles for
 // the waves' sums.
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include <hip/hip_runtime.h>
-
-#include "../../include/wavernn_amd.h"
+#include "dsp_device.h"
+#include "dsp_tables.h"
+#include "handle_common.h"
 
 namespace {
 
@@ -46,8 +44,6 @@ struct ScoreStftArgs {
     int32_t T_max, hop, win, min_samples;
     float floor;
 };
-
-__device__ inline double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 
 // The clip's own length as every kernel here reads it: clamped to the buffer, and 0 (no frames anywhere) for a clip too short to pad.
 __device__ inline long clip_len(const int32_t *n_samples, int b, long n_max, int min_samples) {
@@ -309,29 +305,6 @@ void launch_stft(const ScoreStftArgs &a, int B, hipStream_t s) {
     hipLaunchKernelGGL(score_stft_kernel<LOG>, dim3((unsigned)((a.T_max + FPW - 1) / FPW), (unsigned)B), dim3(THREADS), 0, s, a);
 }
 
-// ---- host tables ----------------------------------------------------------------------------------------------------------------------
-// window[win]: the periodic Hann window; twiddle[n_fft][2]: cos, -sin of 2 pi k / n_fft.  Float64: the transform kernel reads them unrounded.
-void build_tables(int n_fft, int win, std::vector<double> *window, std::vector<double> *twiddle) {
-    // the periodic Hann window and the twiddles of wrnn_mel_build_tables, at this resolution's sizes, before that function's rounding
-    const double pi = 3.141592653589793, wstep = (pi - (-pi)) / (double)win;
-    window->resize(win);
-    for (int i = 0; i < win; ++i) (*window)[i] = 0.5 + 0.5 * std::cos((double)i * wstep + (-pi));
-    twiddle->resize(2 * (size_t)n_fft);
-    for (int k = 0; k < n_fft; ++k) {
-        const double ang = 2.0 * pi * (double)k / (double)n_fft;
-        (*twiddle)[2 * k] = std::cos(ang);
-        (*twiddle)[2 * k + 1] = -std::sin(ang);
-    }
-}
-
-// dct (K, n_mels): C[k, m] = sqrt(2 / n_mels) cos(pi k (m + 1/2) / n_mels) for k = 1 .. K, built in float64, rounded once.
-void build_dct(int n_mels, int K, std::vector<float> *dct) {
-    const double pi = 3.141592653589793, scale = std::sqrt(2.0 / (double)n_mels);
-    dct->resize((size_t)K * n_mels);
-    for (int k = 1; k <= K; ++k)
-        for (int m = 0; m < n_mels; ++m) (*dct)[(size_t)(k - 1) * n_mels + m] = (float)(scale * std::cos(pi * (double)k * ((double)m + 0.5) / (double)n_mels));
-}
-
 }  // namespace
 
 // ---- the C entries ----------------------------------------------------------------------------------------------------------------------
@@ -344,32 +317,14 @@ struct wrnn_score_handle {
     int min_samples = 0;              // the shortest clip every transform (and the mel) can pad
     wrnn_mel_handle *mel = nullptr;   // the front end the mels come from: its own handle, its own launch path
     std::vector<double> window[WRNN_SCORE_MAX_RES], twiddle[WRNN_SCORE_MAX_RES];   // float64, as the transform kernel reads them
-    std::vector<float> dct;           // (K, n_mels)
+    std::vector<float> dct;           // (K, n_mels): dsp_tables.h's rows, rounded to float32 once
     void *dev = nullptr;              // per resolution window | twiddle (float64), then the DCT transposed (float32); uploaded by the first call
     size_t o_win[WRNN_SCORE_MAX_RES] = {}, o_tw[WRNN_SCORE_MAX_RES] = {}, o_dct = 0;
-    char *ws = nullptr;               // the two mels | the sums | the per-frame scratch, grown on demand
-    size_t ws_cap = 0;
+    WrnnScratch ws;                   // the two mels | the sums | the per-frame scratch, grown on demand
     std::string err;
 };
 
 namespace {
-int sc_fail(wrnn_score_handle *h, int code, const char *fmt, ...) {
-    char buf[400];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (h) h->err = buf;
-    return code;
-}
-#define SC_TRY(h, expr)                                                                                   \
-    do {                                                                                                  \
-        hipError_t e__ = (expr);                                                                          \
-        if (e__ != hipSuccess) return sc_fail((h), WRNN_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e__)); \
-    } while (0)
-const int SC_MAX_B = 65535;   // grid.y
-const wrnn_mel_features SC_DEFAULT_FEATURES = {(uint32_t)sizeof(wrnn_mel_features), WRNN_MEL_PAD_REFLECT, 1, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-
 int64_t frames_of(const wrnn_score_handle *h, int r, int64_t n) { return 1 + n / (r < 0 ? h->cfg.hop_length : h->scfg.hop[r]); }
 }  // namespace
 
@@ -380,31 +335,36 @@ int wrnn_score_create(const wrnn_mel_config *cfg, const wrnn_mel_features *f, co
     wrnn_score_handle *h = new wrnn_score_handle();
     *out = h;
     h->cfg = *cfg;
-    if (!f) f = &SC_DEFAULT_FEATURES;
+    if (!f) f = &WRNN_DEFAULT_MEL_FEATURES;
     if (sc->struct_size != sizeof(wrnn_score_config))
-        return sc_fail(h, WRNN_ERR_INVALID, "score.struct_size = %u, this library's wrnn_score_config has %zu bytes", sc->struct_size, sizeof(wrnn_score_config));
+        return wrnn_failf(h, WRNN_ERR_INVALID, "score.struct_size = %u, this library's wrnn_score_config has %zu bytes", sc->struct_size, sizeof(wrnn_score_config));
     h->scfg = *sc;
     // the front end checks its own configuration (struct_size of the features included) and builds its own tables; no device is touched
     const int rc = wrnn_mel_create_features(cfg, f, &h->mel);
-    if (rc != WRNN_OK) return sc_fail(h, rc, "%s", h->mel ? wrnn_mel_last_error(h->mel) : "wrnn_mel_create_features failed");
+    if (rc != WRNN_OK) return wrnn_failf(h, rc, "%s", h->mel ? wrnn_mel_last_error(h->mel) : "wrnn_mel_create_features failed");
     h->feat = *f;
     if (sc->n_res < 1 || sc->n_res > WRNN_SCORE_MAX_RES)
-        return sc_fail(h, WRNN_ERR_INVALID, "n_res = %d: a handle holds 1 .. %d resolutions", sc->n_res, WRNN_SCORE_MAX_RES);
+        return wrnn_failf(h, WRNN_ERR_INVALID, "n_res = %d: a handle holds 1 .. %d resolutions", sc->n_res, WRNN_SCORE_MAX_RES);
     int min_samples = f->pad_mode == WRNN_MEL_PAD_REFLECT ? cfg->n_fft / 2 + 1 : 1;
     for (int r = 0; r < sc->n_res; ++r) {
         const int n_fft = sc->n_fft[r];
         if (n_fft != 256 && n_fft != 512 && n_fft != 1024 && n_fft != 2048)
-            return sc_fail(h, WRNN_ERR_INVALID, "resolution %d: n_fft = %d is none of 256, 512, 1024, 2048", r, n_fft);
+            return wrnn_failf(h, WRNN_ERR_INVALID, "resolution %d: n_fft = %d is none of 256, 512, 1024, 2048", r, n_fft);
         if (sc->win[r] < 1 || sc->win[r] > n_fft || sc->hop[r] < 1)
-            return sc_fail(h, WRNN_ERR_INVALID, "resolution %d: 1 <= win <= n_fft and hop >= 1, got win = %d, hop = %d", r, sc->win[r], sc->hop[r]);
+            return wrnn_failf(h, WRNN_ERR_INVALID, "resolution %d: 1 <= win <= n_fft and hop >= 1, got win = %d, hop = %d", r, sc->win[r], sc->hop[r]);
         if (n_fft / 2 + 1 > min_samples) min_samples = n_fft / 2 + 1;
     }
     if (!(sc->mag_floor > 0.0f) || !std::isfinite(sc->mag_floor))
-        return sc_fail(h, WRNN_ERR_INVALID, "mag_floor = %g: the floor under re^2 + im^2 is finite and > 0 (its logarithm is taken)", (double)sc->mag_floor);
+        return wrnn_failf(h, WRNN_ERR_INVALID, "mag_floor = %g: the floor under re^2 + im^2 is finite and > 0 (its logarithm is taken)", (double)sc->mag_floor);
     if (sc->mcd_order < 1 || sc->mcd_order > cfg->n_mels - 1)
-        return sc_fail(h, WRNN_ERR_INVALID, "mcd_order = %d: 1 <= mcd_order <= n_mels - 1 = %d", sc->mcd_order, cfg->n_mels - 1);
-    for (int r = 0; r < sc->n_res; ++r) build_tables(sc->n_fft[r], sc->win[r], &h->window[r], &h->twiddle[r]);
-    build_dct(cfg->n_mels, sc->mcd_order, &h->dct);
+        return wrnn_failf(h, WRNN_ERR_INVALID, "mcd_order = %d: 1 <= mcd_order <= n_mels - 1 = %d", sc->mcd_order, cfg->n_mels - 1);
+    // float64: the transform kernel reads the window and the twiddles unrounded
+    for (int r = 0; r < sc->n_res; ++r) {
+        h->window[r] = wrnn_dsp::hann_periodic(sc->win[r]);
+        h->twiddle[r] = wrnn_dsp::twiddles(sc->n_fft[r]);
+    }
+    const std::vector<double> dct = wrnn_dsp::dct_rows(cfg->n_mels, sc->mcd_order);
+    h->dct.assign(dct.begin(), dct.end());
     h->min_samples = min_samples;
     h->ok = true;
     return WRNN_OK;
@@ -428,9 +388,9 @@ int wrnn_score_tables(const wrnn_score_handle *h, int32_t r, float *window, floa
 int wrnn_score(wrnn_score_handle *h, const float *target_dev, const float *test_dev, int64_t n_max, const int32_t *n_dev, int32_t B,
                double *summary_dev, float *frames_dev, int64_t frames_stride, void *stream) {
     if (!h) return WRNN_ERR_INVALID;
-    if (!h->ok) return sc_fail(h, WRNN_ERR_STATE, "the handle's configuration was refused by wrnn_score_create");
-    if (!target_dev || !test_dev || !n_dev || !summary_dev || B < 1 || B > SC_MAX_B || n_max < h->min_samples || n_max > INT32_MAX)
-        return sc_fail(h, WRNN_ERR_INVALID, "bad arguments: device pointers, 1 <= B <= 65535, %d <= n_max < 2^31", h->min_samples);
+    if (!h->ok) return wrnn_failf(h, WRNN_ERR_STATE, "the handle's configuration was refused by wrnn_score_create");
+    if (!target_dev || !test_dev || !n_dev || !summary_dev || B < 1 || B > WRNN_MAX_GRID_Y || n_max < h->min_samples || n_max > INT32_MAX)
+        return wrnn_failf(h, WRNN_ERR_INVALID, "bad arguments: device pointers, 1 <= B <= 65535, %d <= n_max < 2^31", h->min_samples);
     const wrnn_score_config &sc = h->scfg;
     const int n_res = sc.n_res, Q = 2 + 3 * n_res, n_mels = h->cfg.n_mels, K = sc.mcd_order;
     // the per-frame row: lsd | mcd | (num | den | lm) of every resolution, every segment as long as the frames of n_max samples
@@ -443,67 +403,43 @@ int wrnn_score(wrnn_score_handle *h, const float *target_dev, const float *test_
         total += T;
     }
     if (frames_dev && frames_stride < total)
-        return sc_fail(h, WRNN_ERR_INVALID, "frames_stride = %lld: a row of the per-frame buffer holds %lld values for n_max = %lld", (long long)frames_stride,
+        return wrnn_failf(h, WRNN_ERR_INVALID, "frames_stride = %lld: a row of the per-frame buffer holds %lld values for n_max = %lld", (long long)frames_stride,
                        (long long)total, (long long)n_max);
     hipStream_t s = (hipStream_t)stream;
-    SC_TRY(h, hipSetDevice(h->cfg.device));
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    WRNN_TRY(h, hipSetDevice(h->cfg.device));
     if (!h->dev) {
-        size_t at = 0;
+        WrnnImage img;
         for (int r = 0; r < n_res; ++r) {
-            h->o_win[r] = at;
-            at += up(h->window[r].size() * 8);
-            h->o_tw[r] = at;
-            at += up(h->twiddle[r].size() * 8);
+            h->o_win[r] = img.put(h->window[r].data(), h->window[r].size() * 8);
+            h->o_tw[r] = img.put(h->twiddle[r].data(), h->twiddle[r].size() * 8);
         }
-        h->o_dct = at;
-        at += up(h->dct.size() * 4);
-        std::vector<char> img(at, 0);
-        for (int r = 0; r < n_res; ++r) {
-            memcpy(img.data() + h->o_win[r], h->window[r].data(), h->window[r].size() * 8);
-            memcpy(img.data() + h->o_tw[r], h->twiddle[r].data(), h->twiddle[r].size() * 8);
-        }
-        float *dt = (float *)(img.data() + h->o_dct);
+        h->o_dct = img.take(h->dct.size() * 4);
+        float *dt = img.at<float>(h->o_dct);
         for (int k = 0; k < K; ++k)
             for (int m = 0; m < n_mels; ++m) dt[(size_t)m * K + k] = h->dct[(size_t)k * n_mels + m];
-        void *d = nullptr;
-        SC_TRY(h, hipMalloc(&d, at));
-        hipError_t e = hipMemcpy(d, img.data(), at, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(d);
-            return sc_fail(h, WRNN_ERR_HIP, "uploading the score tables: %s", hipGetErrorString(e));
-        }
-        h->dev = d;
+        const hipError_t e = img.upload(&h->dev);
+        if (e != hipSuccess) return wrnn_failf(h, WRNN_ERR_HIP, "uploading the score tables: %s", hipGetErrorString(e));
     }
     // the two mels | the sums | the per-frame scratch: the calls on one handle share them, so the caller orders those calls
     const int T_mel = seg_len[0];
-    const size_t b_mel = up((size_t)B * n_mels * T_mel * 4), b_sums = up((size_t)B * Q * 8);
+    const size_t b_mel = wrnn_up256((size_t)B * n_mels * T_mel * 4), b_sums = wrnn_up256((size_t)B * Q * 8);
     const int64_t stride = frames_dev ? frames_stride : total;
-    const size_t need = 2 * b_mel + b_sums + (frames_dev ? 0 : up((size_t)B * total * 4));
-    if (need > h->ws_cap) {
-        if (h->ws) {
-            SC_TRY(h, hipStreamSynchronize(s));   // growing is the one wait: an earlier call may still read the old buffer
-            SC_TRY(h, hipFree(h->ws));
-            h->ws = nullptr;
-            h->ws_cap = 0;
-        }
-        SC_TRY(h, hipMalloc((void **)&h->ws, need));
-        h->ws_cap = need;
-    }
-    float *mel_a = (float *)h->ws, *mel_b = (float *)(h->ws + b_mel);
-    double *sums = (double *)(h->ws + 2 * b_mel);
-    float *frames = frames_dev ? frames_dev : (float *)(h->ws + 2 * b_mel + b_sums);
+    WRNN_TRY(h, h->ws.reserve(2 * b_mel + b_sums + (frames_dev ? 0 : wrnn_up256((size_t)B * total * 4)), s));
+    char *ws = h->ws.p;
+    float *mel_a = (float *)ws, *mel_b = (float *)(ws + b_mel);
+    double *sums = (double *)(ws + 2 * b_mel);
+    float *frames = frames_dev ? frames_dev : (float *)(ws + 2 * b_mel + b_sums);
     const char *d = (const char *)h->dev;
     // the mels: the front end's own entry, twice into scratch
     if (wrnn_melspectrogram(h->mel, target_dev, n_max, n_dev, B, T_mel, mel_a, stream) != WRNN_OK ||
         wrnn_melspectrogram(h->mel, test_dev, n_max, n_dev, B, T_mel, mel_b, stream) != WRNN_OK)
-        return sc_fail(h, WRNN_ERR_HIP, "the mel front end: %s", wrnn_mel_last_error(h->mel));
+        return wrnn_failf(h, WRNN_ERR_HIP, "the mel front end: %s", wrnn_mel_last_error(h->mel));
     ScoreMelArgs m{};
     m.mel_a = mel_a; m.mel_b = mel_b; m.n_samples = n_dev; m.dct_t = (const float *)(d + h->o_dct); m.frames = frames;
     m.n_max = n_max; m.stride = stride; m.T_max = T_mel; m.n_mels = n_mels; m.hop = h->cfg.hop_length; m.K = K; m.min_samples = h->min_samples;
     m.range_db = -h->cfg.min_level_db;
     hipLaunchKernelGGL(score_mel_kernel, dim3((unsigned)((T_mel + MAX_WAVES - 1) / MAX_WAVES), (unsigned)B), dim3(THREADS), 0, s, m);
-    SC_TRY(h, hipGetLastError());
+    WRNN_TRY(h, hipGetLastError());
     for (int r = 0; r < n_res; ++r) {
         ScoreStftArgs a{};
         a.a = target_dev; a.b = test_dev; a.n_samples = n_dev;
@@ -516,7 +452,7 @@ int wrnn_score(wrnn_score_handle *h, const float *target_dev, const float *test_
             case 1024: launch_stft<9>(a, B, s); break;
             default: launch_stft<10>(a, B, s); break;
         }
-        SC_TRY(h, hipGetLastError());
+        WRNN_TRY(h, hipGetLastError());
     }
     ScoreReduceArgs ra{};
     ra.frames = frames; ra.sums = sums; ra.stride = stride; ra.Q = Q;
@@ -525,7 +461,7 @@ int wrnn_score(wrnn_score_handle *h, const float *target_dev, const float *test_
         ra.seg_len[q] = seg_len[q];
     }
     hipLaunchKernelGGL(score_reduce_kernel, dim3((unsigned)Q, (unsigned)B), dim3(THREADS), 0, s, ra);
-    SC_TRY(h, hipGetLastError());
+    WRNN_TRY(h, hipGetLastError());
     ScoreFinalArgs fa{};
     fa.sums = sums; fa.n_samples = n_dev; fa.summary = summary_dev; fa.n_max = n_max; fa.B = B; fa.n_res = n_res;
     fa.mel_hop = h->cfg.hop_length; fa.min_samples = h->min_samples;
@@ -534,18 +470,18 @@ int wrnn_score(wrnn_score_handle *h, const float *target_dev, const float *test_
         fa.bins[r] = sc.n_fft[r] / 2 + 1;
     }
     hipLaunchKernelGGL(score_finalize_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, fa);
-    SC_TRY(h, hipGetLastError());
+    WRNN_TRY(h, hipGetLastError());
     return WRNN_OK;
 }
 
-const char *wrnn_score_last_error(const wrnn_score_handle *h) { return h ? h->err.c_str() : "null handle"; }
+const char *wrnn_score_last_error(const wrnn_score_handle *h) { return wrnn_last_error_of(h); }
 
 void wrnn_score_destroy(wrnn_score_handle *h) {
     if (!h) return;
-    if (h->dev || h->ws) {
+    if (h->dev || h->ws.p) {
         (void)hipSetDevice(h->cfg.device);
         if (h->dev) (void)hipFree(h->dev);
-        if (h->ws) (void)hipFree(h->ws);
+        h->ws.release();
     }
     if (h->mel) wrnn_mel_destroy(h->mel);
     delete h;

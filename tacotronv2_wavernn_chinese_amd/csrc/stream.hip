@@ -90,25 +90,25 @@ int64_t wrnn_stream_ready_steps(int64_t frames_in, int32_t hop, int32_t pad, int
 }
 
 int wrnn_stream_open(wrnn_handle *h, int32_t B, const wrnn_sample_opts *opts, wrnn_stream **out) {
-    if (!h || !opts || !out || B < 1) return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_stream_open: bad arguments");
+    if (!h || !opts || !out || B < 1) return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_stream_open: bad arguments");
     *out = nullptr;
     if (opts->struct_size != sizeof(wrnn_sample_opts))
-        return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_sample_opts.struct_size is %u, this library (ABI %d) expects %zu", opts->struct_size,
+        return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_sample_opts.struct_size is %u, this library (ABI %d) expects %zu", opts->struct_size,
                      WRNN_ABI_VERSION, sizeof(wrnn_sample_opts));
-    if (!h->loaded) return wrnn_fail(h, WRNN_ERR_STATE, "weights not loaded");
+    if (!h->loaded) return wrnn_failf(h, WRNN_ERR_STATE, "weights not loaded");
     if (opts->noise_mode != WRNN_NOISE_PHILOX && opts->noise_mode != WRNN_NOISE_ARGMAX)
-        return wrnn_fail(h, WRNN_ERR_INVALID, "a stream draws its noise on the device: noise_mode must be WRNN_NOISE_PHILOX or WRNN_NOISE_ARGMAX");
-    if (opts->noise_mode == WRNN_NOISE_ARGMAX && h->d.mode != WRNN_MODE_RAW) return wrnn_fail(h, WRNN_ERR_INVALID, "WRNN_NOISE_ARGMAX is RAW-only");
+        return wrnn_failf(h, WRNN_ERR_INVALID, "a stream draws its noise on the device: noise_mode must be WRNN_NOISE_PHILOX or WRNN_NOISE_ARGMAX");
+    if (opts->noise_mode == WRNN_NOISE_ARGMAX && h->d.mode != WRNN_MODE_RAW) return wrnn_failf(h, WRNN_ERR_INVALID, "WRNN_NOISE_ARGMAX is RAW-only");
     if (opts->mels_padded || opts->noise1_dev || opts->noise2_dev || opts->x_forced_dev || opts->logits_out_dev || opts->x_init_dev ||
         opts->frames_dev || opts->batch_rows || opts->team2_segment || opts->utt_seeds_dev)
-        return wrnn_fail(h, WRNN_ERR_INVALID, "a stream takes noise_mode, kernel and seed only: mels_padded, the pointers (utt_seeds_dev included) and the tuning fields must be 0");
+        return wrnn_failf(h, WRNN_ERR_INVALID, "a stream takes noise_mode, kernel and seed only: mels_padded, the pointers (utt_seeds_dev included) and the tuning fields must be 0");
     const char *team_no = wrnn_loop_team_obstacle(h);
     int kernel = opts->kernel;
     if (kernel == WRNN_KERNEL_AUTO) kernel = team_no ? WRNN_KERNEL_SIMPLE : WRNN_KERNEL_TEAM2;
-    if (kernel == WRNN_KERNEL_TEAM2 && team_no) return wrnn_fail(h, WRNN_ERR_INVALID, "%s", team_no);
+    if (kernel == WRNN_KERNEL_TEAM2 && team_no) return wrnn_failf(h, WRNN_ERR_INVALID, "%s", team_no);
     if (kernel != WRNN_KERNEL_TEAM2 && kernel != WRNN_KERNEL_SIMPLE)
-        return wrnn_fail(h, WRNN_ERR_INVALID, "a stream runs WRNN_KERNEL_AUTO, TEAM2 or SIMPLE (kernel %d)", opts->kernel);
-    WRNN_HIP_TRY(h, hipSetDevice(h->cfg.device));
+        return wrnn_failf(h, WRNN_ERR_INVALID, "a stream runs WRNN_KERNEL_AUTO, TEAM2 or SIMPLE (kernel %d)", opts->kernel);
+    WRNN_TRY(h, hipSetDevice(h->cfg.device));
     wrnn_stream *st = new wrnn_stream();
     st->h = h; st->device = h->cfg.device; st->B = B; st->kernel = kernel; st->noise_mode = opts->noise_mode; st->seed = opts->seed;
     const int teams = h->n_teams < 1 ? 1 : h->n_teams;
@@ -123,7 +123,7 @@ int wrnn_stream_open(wrnn_handle *h, int32_t B, const wrnn_sample_opts *opts, wr
     }
     if (e != hipSuccess) {
         wrnn_stream_close(st);
-        return wrnn_fail(h, WRNN_ERR_HIP, "wrnn_stream_open: %s", hipGetErrorString(e));
+        return wrnn_failf(h, WRNN_ERR_HIP, "wrnn_stream_open: %s", hipGetErrorString(e));
     }
     *out = st;
     return WRNN_OK;
@@ -134,10 +134,10 @@ int wrnn_stream_push(wrnn_stream *st, const float *mels_dev, int32_t n_frames, i
     if (!st) return WRNN_ERR_INVALID;
     wrnn_handle *h = st->h;
     if (steps_out) *steps_out = 0;
-    if (st->poisoned) return wrnn_fail(h, WRNN_ERR_STATE, "the stream reported a device-side error (wrnn_stream_sync): it cannot continue");
-    if (st->ended) return wrnn_fail(h, WRNN_ERR_STATE, "push after the stream's last push");
-    if (n_frames < 0 || (n_frames > 0 && !mels_dev) || !steps_out) return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_stream_push: bad arguments");
-    if (!h->loaded) return wrnn_fail(h, WRNN_ERR_STATE, "weights not loaded");
+    if (st->poisoned) return wrnn_failf(h, WRNN_ERR_STATE, "the stream reported a device-side error (wrnn_stream_sync): it cannot continue");
+    if (st->ended) return wrnn_failf(h, WRNN_ERR_STATE, "push after the stream's last push");
+    if (n_frames < 0 || (n_frames > 0 && !mels_dev) || !steps_out) return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_stream_push: bad arguments");
+    if (!h->loaded) return wrnn_failf(h, WRNN_ERR_STATE, "weights not loaded");
     const WrnnDims &d = h->d;
     const int B = st->B, F = d.F, P = d.P, HOP = d.HOP;
     const int64_t fin = st->frames_in + n_frames;
@@ -145,10 +145,10 @@ int wrnn_stream_push(wrnn_stream *st, const float *mels_dev, int32_t n_frames, i
     const int64_t s0 = st->steps_done, s1 = ready > s0 ? ready : s0;
     const int64_t n = s1 - s0;
     if (n > 0 && (!samples_out_dev || out_capacity < (int64_t)B * n))
-        return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_stream_push: %lld steps are ready, the outputs must hold B * steps = %lld elements (capacity %lld)",
+        return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_stream_push: %lld steps are ready, the outputs must hold B * steps = %lld elements (capacity %lld)",
                      (long long)n, (long long)B * n, (long long)out_capacity);
-    if (n > INT32_MAX / 2) return wrnn_fail(h, WRNN_ERR_INVALID, "wrnn_stream_push: push too long");
-    WRNN_HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (n > INT32_MAX / 2) return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_stream_push: push too long");
+    WRNN_TRY(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     const int hn = (int)(st->frames_in - st->hist0);
     const float *hist = st->hist[st->cur];
@@ -157,15 +157,15 @@ int wrnn_stream_push(wrnn_stream *st, const float *mels_dev, int32_t n_frames, i
         // window: frames [f0, f1) own the ready steps, their conditioning reads mel frames [f0 - P, f1 + P)
         const int64_t f0 = s0 / HOP, f1 = (s1 + HOP - 1) / HOP;
         const int Tw = (int)(f1 - f0), nW = Tw + 2 * P;
-        if (f0 - P >= 0 && f0 - P < st->hist0) return wrnn_fail(h, WRNN_ERR_STATE, "internal: mel history lost frame %lld", (long long)(f0 - P));
+        if (f0 - P >= 0 && f0 - P < st->hist0) return wrnn_failf(h, WRNN_ERR_STATE, "internal: mel history lost frame %lld", (long long)(f0 - P));
         if (int rc = wrnn_grow(h, st->win, st->win_cap, (size_t)B * F * nW)) return rc;
-        WRNN_HIP_TRY(h, launch_gather(hist, st->hist0, hn, mels_dev, st->frames_in, n_frames, st->win, f0 - P, nW, B, F, fin, s));
+        WRNN_TRY(h, launch_gather(hist, st->hist0, hn, mels_dev, st->frames_in, n_frames, st->win, f0 - P, nW, B, F, fin, s));
         if (int rc = wrnn_grow(h, st->aux, st->aux_cap, (size_t)B * Tw * d.R)) return rc;
-        WRNN_HIP_TRY(h, wrnn_launch_resnet(h, st->win, B, Tw, nW, P, st->aux, s));
+        WRNN_TRY(h, wrnn_launch_resnet(h, st->win, B, Tw, nW, P, st->aux, s));
         const int32_t row_steps = st->kernel == WRNN_KERNEL_SIMPLE ? (int32_t)n : INT32_MAX;
         hipLaunchKernelGGL(stream_rows_kernel, dim3((st->n_slots + 255) / 256), dim3(256), 0, s, st->rows, st->sched, B, st->n_slots,
                            row_steps, -f0 * (int64_t)HOP);
-        WRNN_HIP_TRY(h, hipGetLastError());
+        WRNN_TRY(h, hipGetLastError());
         // the loop arguments of the push; TEAM2 takes its sampling fields from them
         WrnnLoopArgs a{};
         a.w = h->wdev; a.off = h->off; a.d = d; a.mels = st->win; a.mel_T = nW; a.mel_off = P; a.aux_frames = st->aux; a.rows = st->rows;
@@ -174,12 +174,12 @@ int wrnn_stream_push(wrnn_stream *st, const float *mels_dev, int32_t n_frames, i
         a.labels_out = labels_out_dev ? labels_out_dev - s0 : nullptr; a.samples_out = samples_out_dev - s0; a.err = st->err;
         a.seg0 = s0; a.state = st->state;
         if (st->kernel == WRNN_KERNEL_SIMPLE) {
-            WRNN_HIP_TRY(h, wrnn_launch_loop_simple(a, s));
+            WRNN_TRY(h, wrnn_launch_loop_simple(a, s));
         } else {
             // the offline TEAM2 prologue and segment loop (launch.hip) on the window: T = Tw, mels (B, F, Tw + 2P) padded by P
             WrnnFrameTables t;
             if (int rc = wrnn_build_frame_tables(h, st->tab, st->tab_cap, st->win, nW, 0, st->aux, B, Tw, 28, t, s)) return rc;
-            WRNN_HIP_TRY(h, wrnn_launch_pack_records(t.CM, t.CA, t.VM, t.VA, t.REC, B, Tw, P, nullptr, s));
+            WRNN_TRY(h, wrnn_launch_pack_records(t.CM, t.CA, t.VM, t.VA, t.REC, B, Tw, P, nullptr, s));
             // every segment start s0 + k * seg lies on a 32-step boundary because s0 does
             const int64_t seg = wrnn_team2_segment_len(B, d.H, n, 0);
             if (int rc = wrnn_grow(h, st->cond, st->cond_cap, (size_t)B * (size_t)seg * d.H * 4)) return rc;
@@ -204,7 +204,7 @@ int wrnn_stream_push(wrnn_stream *st, const float *mels_dev, int32_t n_frames, i
         const int nk = (int)(fin - keep0);
         const int nxt = 1 - st->cur;
         if (int rc = wrnn_grow(h, st->hist[nxt], st->hist_cap[nxt], (size_t)B * F * (nk > 0 ? nk : 1))) return rc;
-        WRNN_HIP_TRY(h, launch_gather(hist, st->hist0, hn, mels_dev, st->frames_in, n_frames, st->hist[nxt], keep0, nk, B, F, fin, s));
+        WRNN_TRY(h, launch_gather(hist, st->hist0, hn, mels_dev, st->frames_in, n_frames, st->hist[nxt], keep0, nk, B, F, fin, s));
         st->cur = nxt;
         st->hist0 = keep0;
     }
@@ -218,16 +218,16 @@ int wrnn_stream_push(wrnn_stream *st, const float *mels_dev, int32_t n_frames, i
 int wrnn_stream_sync(wrnn_stream *st, void *stream) {
     if (!st) return WRNN_ERR_INVALID;
     wrnn_handle *h = st->h;
-    WRNN_HIP_TRY(h, hipSetDevice(h->cfg.device));
-    WRNN_HIP_TRY(h, hipStreamSynchronize((hipStream_t)stream));
+    WRNN_TRY(h, hipSetDevice(h->cfg.device));
+    WRNN_TRY(h, hipStreamSynchronize((hipStream_t)stream));
     unsigned errw = 0;
-    WRNN_HIP_TRY(h, hipMemcpy(&errw, st->err, sizeof(errw), hipMemcpyDeviceToHost));
+    WRNN_TRY(h, hipMemcpy(&errw, st->err, sizeof(errw), hipMemcpyDeviceToHost));
     if (!errw) return WRNN_OK;
     st->poisoned = true;
     if (errw == WRNN_DEVERR_BUSY)
-        return wrnn_fail(h, WRNN_ERR_BUSY, "the stream's team kernel could not get its workgroups resident (the GPU is shared with another kernel): "
+        return wrnn_failf(h, WRNN_ERR_BUSY, "the stream's team kernel could not get its workgroups resident (the GPU is shared with another kernel): "
                                        "the stream cannot continue; open a new one (WRNN_KERNEL_SIMPLE runs anywhere)");
-    return wrnn_fail(h, WRNN_ERR_TIMEOUT, "device-side bounded spin gave up in a stream push (code %u)", errw);
+    return wrnn_failf(h, WRNN_ERR_TIMEOUT, "device-side bounded spin gave up in a stream push (code %u)", errw);
 }
 
 int wrnn_stream_info(const wrnn_stream *st, int64_t *frames_in, int64_t *steps_done, int64_t *workspace_bytes) {

@@ -13,16 +13,12 @@
 // conv kernels): thread j of a layer owns output column j, and a wave reads 64 neighbouring floats of one weight row.
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include <hip/hip_runtime.h>
-
-#include "../../include/wavernn_amd.h"
 #include "device_util.h"
+#include "handle_common.h"
 
 namespace {
 
@@ -486,27 +482,11 @@ struct wrnn_taco_handle {
     float *img = nullptr;         // the device image: the tensors in table order, then the derived ones
     size_t img_cap = 0;
     size_t off_bn_enc = 0, off_bn_post = 0, off_loc_m = 0, off_att_bias = 0, off_proj_w = 0, off_proj_b = 0;
-    char *ws = nullptr;           // the scratch of a call, grown on demand
-    size_t ws_cap = 0;
+    WrnnScratch ws;               // the scratch of a call, grown on demand
     std::string err;
 };
 
 namespace {
-int tc_fail(wrnn_taco_handle *h, int code, const char *fmt, ...) {
-    char buf[400];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (h) h->err = buf;
-    return code;
-}
-#define TC_TRY(h, expr)                                                                                   \
-    do {                                                                                                  \
-        hipError_t e__ = (expr);                                                                          \
-        if (e__ != hipSuccess) return tc_fail((h), WRNN_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e__)); \
-    } while (0)
-
 size_t up64(size_t floats) { return (floats + 63) & ~(size_t)63; }
 
 void add(wrnn_taco_handle *h, const std::string &name, std::vector<int64_t> shape) {
@@ -589,7 +569,7 @@ size_t decoder_lds_floats(const wrnn_taco_dims &d, int Tx_max, int *Pmax_out, in
 int upload(wrnn_taco_handle *h) {
     const wrnn_taco_dims &d = h->d;
     for (const Tensor &t : h->tensors)
-        if (t.data.empty()) return tc_fail(h, WRNN_ERR_STATE, "tensor %s has not been loaded", t.name.c_str());
+        if (t.data.empty()) return wrnn_failf(h, WRNN_ERR_STATE, "tensor %s has not been loaded", t.name.c_str());
     std::vector<float> img;
     for (Tensor &t : h->tensors) {
         t.off = img.size();
@@ -644,13 +624,13 @@ int upload(wrnn_taco_handle *h) {
     for (int j = 0; j < RM; ++j) img[h->off_proj_b + j] = fb->data[j];
     for (int j = 0; j < r; ++j) img[h->off_proj_b + RM + j] = sb->data[j];
     if (img.size() > h->img_cap) {
-        if (h->img) TC_TRY(h, hipFree(h->img));
+        if (h->img) WRNN_TRY(h, hipFree(h->img));
         h->img = nullptr;
         h->img_cap = 0;
-        TC_TRY(h, hipMalloc((void **)&h->img, img.size() * sizeof(float)));
+        WRNN_TRY(h, hipMalloc((void **)&h->img, img.size() * sizeof(float)));
         h->img_cap = img.size();
     }
-    TC_TRY(h, hipMemcpy(h->img, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
+    WRNN_TRY(h, hipMemcpy(h->img, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
     h->dirty = false;
     return WRNN_OK;
 }
@@ -663,7 +643,7 @@ int launch_conv(wrnn_taco_handle *h, hipStream_t s, const float *in, const float
     const size_t lds = (size_t)(CONV_TT + taps - 1) * Cin * sizeof(float);
     hipLaunchKernelGGL(taco_conv_kernel, dim3((unsigned)((T_max + CONV_TT - 1) / CONV_TT), (unsigned)B, (unsigned)((Cout + 63) / 64)),
                        dim3(CONV_THREADS), lds, s, a);
-    TC_TRY(h, hipGetLastError());
+    WRNN_TRY(h, hipGetLastError());
     return WRNN_OK;
 }
 }  // namespace
@@ -677,33 +657,33 @@ int wrnn_taco_create(const wrnn_taco_dims *dims, wrnn_taco_handle **out) {
     wrnn_taco_handle *h = new wrnn_taco_handle();
     *out = h;
     if (dims->struct_size != sizeof(wrnn_taco_dims))
-        return tc_fail(h, WRNN_ERR_INVALID, "wrnn_taco_dims.struct_size %u, this library's is %zu", dims->struct_size, sizeof(wrnn_taco_dims));
+        return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_taco_dims.struct_size %u, this library's is %zu", dims->struct_size, sizeof(wrnn_taco_dims));
     h->d = *dims;
     const wrnn_taco_dims &d = h->d;
     const int32_t sizes[] = {d.n_symbols, d.num_mels, d.outputs_per_step, d.embedding_dim, d.enc_conv_layers, d.enc_conv_channels, d.enc_conv_kernel,
                              d.encoder_lstm_units, d.attention_dim, d.attention_filters, d.attention_kernel, d.decoder_lstm_units, d.postnet_layers,
                              d.postnet_channels, d.postnet_kernel};
     for (int32_t v : sizes)
-        if (v < 1 || v > 65536) return tc_fail(h, WRNN_ERR_INVALID, "unsupported dims: every size must be in 1 .. 65536 (got %d)", v);
-    if (d.device < 0) return tc_fail(h, WRNN_ERR_INVALID, "device %d", d.device);
+        if (v < 1 || v > 65536) return wrnn_failf(h, WRNN_ERR_INVALID, "unsupported dims: every size must be in 1 .. 65536 (got %d)", v);
+    if (d.device < 0) return wrnn_failf(h, WRNN_ERR_INVALID, "device %d", d.device);
     if (d.prenet_layers < 1 || d.prenet_layers > WRNN_TACO_MAX_PRENET)
-        return tc_fail(h, WRNN_ERR_INVALID, "unsupported dims: prenet_layers %d outside 1 .. %d", d.prenet_layers, WRNN_TACO_MAX_PRENET);
+        return wrnn_failf(h, WRNN_ERR_INVALID, "unsupported dims: prenet_layers %d outside 1 .. %d", d.prenet_layers, WRNN_TACO_MAX_PRENET);
     for (int l = 0; l < d.prenet_layers; ++l)
-        if (d.prenet_sizes[l] < 1 || d.prenet_sizes[l] > 65536) return tc_fail(h, WRNN_ERR_INVALID, "unsupported dims: prenet size %d", d.prenet_sizes[l]);
+        if (d.prenet_sizes[l] < 1 || d.prenet_sizes[l] > 65536) return wrnn_failf(h, WRNN_ERR_INVALID, "unsupported dims: prenet size %d", d.prenet_sizes[l]);
     if (d.decoder_layers < 1 || d.decoder_layers > MAX_DEC_LAYERS)
-        return tc_fail(h, WRNN_ERR_INVALID, "unsupported dims: decoder_layers %d outside 1 .. %d", d.decoder_layers, MAX_DEC_LAYERS);
+        return wrnn_failf(h, WRNN_ERR_INVALID, "unsupported dims: decoder_layers %d outside 1 .. %d", d.decoder_layers, MAX_DEC_LAYERS);
     if (d.enc_conv_kernel > MAX_TAPS || d.attention_kernel > MAX_TAPS || d.postnet_kernel > MAX_TAPS)
-        return tc_fail(h, WRNN_ERR_INVALID, "unsupported dims: a convolution of more than %d taps", MAX_TAPS);
+        return wrnn_failf(h, WRNN_ERR_INVALID, "unsupported dims: a convolution of more than %d taps", MAX_TAPS);
     if (!(d.zoneout >= 0.0f && d.zoneout <= 1.0f) || !(d.max_abs_value > 0.0f) || !(d.lower_bound_decay >= 0.0f) || !(d.bn_epsilon > 0.0f))
-        return tc_fail(h, WRNN_ERR_INVALID, "zoneout outside [0, 1], max_abs_value <= 0, lower_bound_decay < 0 or bn_epsilon <= 0");
+        return wrnn_failf(h, WRNN_ERR_INVALID, "zoneout outside [0, 1], max_abs_value <= 0, lower_bound_decay < 0 or bn_epsilon <= 0");
     const int cin_max = std::max(std::max(d.embedding_dim, d.enc_conv_channels), std::max(d.postnet_channels, std::max(d.num_mels, 2 * d.encoder_lstm_units)));
     const int taps_max = std::max(d.enc_conv_kernel, d.postnet_kernel);
     if ((size_t)(CONV_TT + taps_max - 1) * cin_max * sizeof(float) + sizeof(float) * CONV_THREADS * CONV_TT > LDS_LIMIT)
-        return tc_fail(h, WRNN_ERR_INVALID, "unsupported dims: a convolution's input tile of %d rows x %d channels exceeds 64 KiB of LDS", CONV_TT + taps_max - 1, cin_max);
+        return wrnn_failf(h, WRNN_ERR_INVALID, "unsupported dims: a convolution's input tile of %d rows x %d channels exceeds 64 KiB of LDS", CONV_TT + taps_max - 1, cin_max);
     if ((size_t)(6 * d.encoder_lstm_units + 4 * LOOP_THREADS) * sizeof(float) > LDS_LIMIT)
-        return tc_fail(h, WRNN_ERR_INVALID, "unsupported dims: encoder_lstm_units %d: the recurrence's state exceeds 64 KiB of LDS", d.encoder_lstm_units);
+        return wrnn_failf(h, WRNN_ERR_INVALID, "unsupported dims: encoder_lstm_units %d: the recurrence's state exceeds 64 KiB of LDS", d.encoder_lstm_units);
     if (decoder_lds_floats(d, 1, nullptr, nullptr) * sizeof(float) > LDS_LIMIT)
-        return tc_fail(h, WRNN_ERR_INVALID, "unsupported dims: the decoder's state exceeds 64 KiB of LDS");
+        return wrnn_failf(h, WRNN_ERR_INVALID, "unsupported dims: the decoder's state exceeds 64 KiB of LDS");
     build_table(h);
     h->ok = true;
     return WRNN_OK;
@@ -725,64 +705,64 @@ int wrnn_taco_tensor_shape(const wrnn_taco_handle *h, int index, int64_t *shape_
 
 int wrnn_taco_load_tensor(wrnn_taco_handle *h, const char *name, const float *data_host, int ndim, const int64_t *shape) {
     if (!h) return WRNN_ERR_INVALID;
-    if (!h->ok) return tc_fail(h, WRNN_ERR_INVALID, "the handle was refused at creation");
-    if (!name || !data_host || !shape || ndim < 1 || ndim > 3) return tc_fail(h, WRNN_ERR_INVALID, "wrnn_taco_load_tensor: a NULL argument or a rank outside 1 .. 3");
+    if (!h->ok) return wrnn_failf(h, WRNN_ERR_INVALID, "the handle was refused at creation");
+    if (!name || !data_host || !shape || ndim < 1 || ndim > 3) return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_taco_load_tensor: a NULL argument or a rank outside 1 .. 3");
     for (Tensor &t : h->tensors) {
         if (t.name != name) continue;
         bool same = (int)t.shape.size() == ndim;
         for (int i = 0; same && i < ndim; ++i) same = t.shape[i] == shape[i];
-        if (!same) return tc_fail(h, WRNN_ERR_INVALID, "tensor %s: the shape does not match the model's", name);
+        if (!same) return wrnn_failf(h, WRNN_ERR_INVALID, "tensor %s: the shape does not match the model's", name);
         const size_t n = t.count();
         for (size_t i = 0; i < n; ++i)
-            if (!std::isfinite(data_host[i])) return tc_fail(h, WRNN_ERR_INVALID, "tensor %s: element %zu is not finite", name, i);
+            if (!std::isfinite(data_host[i])) return wrnn_failf(h, WRNN_ERR_INVALID, "tensor %s: element %zu is not finite", name, i);
         t.data.assign(data_host, data_host + n);
         h->dirty = true;
         return WRNN_OK;
     }
-    return tc_fail(h, WRNN_ERR_MISSING_KEY, "no tensor named %s in this model", name);
+    return wrnn_failf(h, WRNN_ERR_MISSING_KEY, "no tensor named %s in this model", name);
 }
 
 int wrnn_taco_synthesize(wrnn_taco_handle *h, const wrnn_taco_call *c, void *stream) {
     if (!h) return WRNN_ERR_INVALID;
-    if (!h->ok) return tc_fail(h, WRNN_ERR_INVALID, "the handle was refused at creation");
-    if (!c) return tc_fail(h, WRNN_ERR_INVALID, "call is NULL");
+    if (!h->ok) return wrnn_failf(h, WRNN_ERR_INVALID, "the handle was refused at creation");
+    if (!c) return wrnn_failf(h, WRNN_ERR_INVALID, "call is NULL");
     if (c->struct_size != sizeof(wrnn_taco_call))
-        return tc_fail(h, WRNN_ERR_INVALID, "wrnn_taco_call.struct_size %u, this library's is %zu", c->struct_size, sizeof(wrnn_taco_call));
+        return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_taco_call.struct_size %u, this library's is %zu", c->struct_size, sizeof(wrnn_taco_call));
     const wrnn_taco_dims &d = h->d;
     const int B = c->B, Tx_max = c->Tx_max, r = d.outputs_per_step, M = d.num_mels;
-    if (B < 1 || B > 65535) return tc_fail(h, WRNN_ERR_INVALID, "B %d outside 1 .. 65535", B);
-    if (Tx_max < 1 || Tx_max > WRNN_TACO_MAX_TX) return tc_fail(h, WRNN_ERR_INVALID, "Tx_max %d outside 1 .. %d symbols", Tx_max, WRNN_TACO_MAX_TX);
-    if (!c->ids_host || !c->tx_host || !c->seeds_host) return tc_fail(h, WRNN_ERR_INVALID, "ids_host, tx_host or seeds_host is NULL");
+    if (B < 1 || B > WRNN_MAX_GRID_Y) return wrnn_failf(h, WRNN_ERR_INVALID, "B %d outside 1 .. 65535", B);
+    if (Tx_max < 1 || Tx_max > WRNN_TACO_MAX_TX) return wrnn_failf(h, WRNN_ERR_INVALID, "Tx_max %d outside 1 .. %d symbols", Tx_max, WRNN_TACO_MAX_TX);
+    if (!c->ids_host || !c->tx_host || !c->seeds_host) return wrnn_failf(h, WRNN_ERR_INVALID, "ids_host, tx_host or seeds_host is NULL");
     if (!c->decoder_dev || !c->mel_raw_dev || !c->mel_dev || !c->alignments_dev || !c->stop_dev || !c->max_attentions_dev || !c->steps_dev || !c->mel_frames_dev)
-        return tc_fail(h, WRNN_ERR_INVALID, "an output pointer is NULL");
-    if (c->max_iters < 1) return tc_fail(h, WRNN_ERR_INVALID, "max_iters %d < 1", c->max_iters);
+        return wrnn_failf(h, WRNN_ERR_INVALID, "an output pointer is NULL");
+    if (c->max_iters < 1) return wrnn_failf(h, WRNN_ERR_INVALID, "max_iters %d < 1", c->max_iters);
     for (int b = 0; b < B; ++b) {
         const int tx = c->tx_host[b];
-        if (tx < 1 || tx > Tx_max) return tc_fail(h, WRNN_ERR_INVALID, "utterance %d: %d symbols outside 1 .. Tx_max = %d (the limit is %d)", b, tx, Tx_max, WRNN_TACO_MAX_TX);
+        if (tx < 1 || tx > Tx_max) return wrnn_failf(h, WRNN_ERR_INVALID, "utterance %d: %d symbols outside 1 .. Tx_max = %d (the limit is %d)", b, tx, Tx_max, WRNN_TACO_MAX_TX);
         for (int t = 0; t < tx; ++t) {
             const int id = c->ids_host[(size_t)b * Tx_max + t];
-            if (id < 0 || id >= d.n_symbols) return tc_fail(h, WRNN_ERR_INVALID, "utterance %d: symbol id %d at %d is outside the table of %d", b, id, t, d.n_symbols);
+            if (id < 0 || id >= d.n_symbols) return wrnn_failf(h, WRNN_ERR_INVALID, "utterance %d: symbol id %d at %d is outside the table of %d", b, id, t, d.n_symbols);
         }
     }
     const bool gta = c->gta_dev != nullptr;
     int need_steps = c->max_iters;
     std::vector<int32_t> gsteps(B, 0);
     if (gta) {
-        if (!c->gta_frames_host || c->gta_max < r) return tc_fail(h, WRNN_ERR_INVALID, "a target needs gta_frames_host and gta_max >= r");
+        if (!c->gta_frames_host || c->gta_max < r) return wrnn_failf(h, WRNN_ERR_INVALID, "a target needs gta_frames_host and gta_max >= r");
         need_steps = 1;
         for (int b = 0; b < B; ++b) {
             const int f = c->gta_frames_host[b];
-            if (f < r || f > c->gta_max || f % r) return tc_fail(h, WRNN_ERR_INVALID, "utterance %d: %d target frames: not a multiple of r = %d in r .. gta_max = %d", b, f, r, c->gta_max);
+            if (f < r || f > c->gta_max || f % r) return wrnn_failf(h, WRNN_ERR_INVALID, "utterance %d: %d target frames: not a multiple of r = %d in r .. gta_max = %d", b, f, r, c->gta_max);
             gsteps[b] = f / r;
             need_steps = std::max(need_steps, f / r);
         }
     }
     const int S = c->steps_max;
-    if (S < need_steps || (int64_t)S * r > (1 << 24)) return tc_fail(h, WRNN_ERR_INVALID, "steps_max %d: below the %d steps this call can run, or above 2^24 / r", S, need_steps);
+    if (S < need_steps || (int64_t)S * r > (1 << 24)) return wrnn_failf(h, WRNN_ERR_INVALID, "steps_max %d: below the %d steps this call can run, or above 2^24 / r", S, need_steps);
     int Pmax = 0, Kmax = 0;
     const size_t dec_lds = decoder_lds_floats(d, Tx_max, &Pmax, &Kmax) * sizeof(float);
-    if (dec_lds > LDS_LIMIT) return tc_fail(h, WRNN_ERR_INVALID, "the decoder's state for Tx_max %d exceeds 64 KiB of LDS", Tx_max);
-    TC_TRY(h, hipSetDevice(d.device));
+    if (dec_lds > LDS_LIMIT) return wrnn_failf(h, WRNN_ERR_INVALID, "the decoder's state for Tx_max %d exceeds 64 KiB of LDS", Tx_max);
+    WRNN_TRY(h, hipSetDevice(d.device));
     hipStream_t s = (hipStream_t)stream;
     if (h->dirty) {
         const int rc = upload(h);
@@ -792,39 +772,33 @@ int wrnn_taco_synthesize(wrnn_taco_handle *h, const wrnn_taco_call *c, void *str
     const int C = d.enc_conv_channels, H = d.encoder_lstm_units, E2 = 2 * H, A = d.attention_dim, PC = d.postnet_channels, T_out = S * r;
     const size_t act_floats = std::max((size_t)B * Tx_max * std::max(C, d.embedding_dim), (size_t)B * T_out * std::max(PC, M));
     size_t at = 0;
-    auto take = [&at](size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; };
+    auto take = [&at](size_t bytes) { const size_t o = at; at += wrnn_up256(bytes); return o; };
     const size_t o_ids = take((size_t)B * Tx_max * 4), o_tx = take((size_t)B * 4), o_gs = take((size_t)B * 4), o_seed = take((size_t)B * 8);
     const size_t o_a0 = take(act_floats * 4), o_a1 = take(act_floats * 4), o_xp0 = take((size_t)B * Tx_max * 4 * H * 4), o_xp1 = take((size_t)B * Tx_max * 4 * H * 4);
     const size_t o_mem = take((size_t)B * Tx_max * E2 * 4), o_keys = take((size_t)B * Tx_max * A * 4);
-    if (at > h->ws_cap) {
-        TC_TRY(h, hipStreamSynchronize(s));
-        if (h->ws) TC_TRY(h, hipFree(h->ws));
-        h->ws = nullptr;
-        h->ws_cap = 0;
-        TC_TRY(h, hipMalloc((void **)&h->ws, at));
-        h->ws_cap = at;
-    }
-    int32_t *ids = (int32_t *)(h->ws + o_ids), *tx = (int32_t *)(h->ws + o_tx), *gs = (int32_t *)(h->ws + o_gs);
-    uint64_t *seeds = (uint64_t *)(h->ws + o_seed);
-    float *a0 = (float *)(h->ws + o_a0), *a1 = (float *)(h->ws + o_a1), *xp[2] = {(float *)(h->ws + o_xp0), (float *)(h->ws + o_xp1)};
-    float *mem = (float *)(h->ws + o_mem), *keys = (float *)(h->ws + o_keys);
+    WRNN_TRY(h, h->ws.reserve(at, s));
+    char *ws = h->ws.p;
+    int32_t *ids = (int32_t *)(ws + o_ids), *tx = (int32_t *)(ws + o_tx), *gs = (int32_t *)(ws + o_gs);
+    uint64_t *seeds = (uint64_t *)(ws + o_seed);
+    float *a0 = (float *)(ws + o_a0), *a1 = (float *)(ws + o_a1), *xp[2] = {(float *)(ws + o_xp0), (float *)(ws + o_xp1)};
+    float *mem = (float *)(ws + o_mem), *keys = (float *)(ws + o_keys);
     // pageable host memory: these copies return once the source has been read
-    TC_TRY(h, hipMemcpyAsync(ids, c->ids_host, (size_t)B * Tx_max * 4, hipMemcpyHostToDevice, s));
-    TC_TRY(h, hipMemcpyAsync(tx, c->tx_host, (size_t)B * 4, hipMemcpyHostToDevice, s));
-    TC_TRY(h, hipMemcpyAsync(gs, gsteps.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
-    TC_TRY(h, hipMemcpyAsync(seeds, c->seeds_host, (size_t)B * 8, hipMemcpyHostToDevice, s));
-    TC_TRY(h, hipStreamSynchronize(s));   // gsteps leaves scope; the caller's arrays may too
-    TC_TRY(h, hipMemsetAsync(mem, 0, (size_t)B * Tx_max * E2 * 4, s));
-    TC_TRY(h, hipMemsetAsync(c->decoder_dev, 0, (size_t)B * T_out * M * 4, s));
-    TC_TRY(h, hipMemsetAsync(c->alignments_dev, 0, (size_t)B * S * Tx_max * 4, s));
-    TC_TRY(h, hipMemsetAsync(c->stop_dev, 0, (size_t)B * T_out * 4, s));
-    TC_TRY(h, hipMemsetAsync(c->max_attentions_dev, 0, (size_t)B * S * 4, s));
+    WRNN_TRY(h, hipMemcpyAsync(ids, c->ids_host, (size_t)B * Tx_max * 4, hipMemcpyHostToDevice, s));
+    WRNN_TRY(h, hipMemcpyAsync(tx, c->tx_host, (size_t)B * 4, hipMemcpyHostToDevice, s));
+    WRNN_TRY(h, hipMemcpyAsync(gs, gsteps.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
+    WRNN_TRY(h, hipMemcpyAsync(seeds, c->seeds_host, (size_t)B * 8, hipMemcpyHostToDevice, s));
+    WRNN_TRY(h, hipStreamSynchronize(s));   // gsteps leaves scope; the caller's arrays may too
+    WRNN_TRY(h, hipMemsetAsync(mem, 0, (size_t)B * Tx_max * E2 * 4, s));
+    WRNN_TRY(h, hipMemsetAsync(c->decoder_dev, 0, (size_t)B * T_out * M * 4, s));
+    WRNN_TRY(h, hipMemsetAsync(c->alignments_dev, 0, (size_t)B * S * Tx_max * 4, s));
+    WRNN_TRY(h, hipMemsetAsync(c->stop_dev, 0, (size_t)B * T_out * 4, s));
+    WRNN_TRY(h, hipMemsetAsync(c->max_attentions_dev, 0, (size_t)B * S * 4, s));
     const float *img = h->img;
     auto T = [&](const std::string &n) { return img + find(h, n)->off; };
     // ---- encoder
     EmbedArgs e{ids, tx, T("inputs_embedding"), a0, Tx_max, d.embedding_dim, d.n_symbols};
     hipLaunchKernelGGL(taco_embed_kernel, dim3((unsigned)Tx_max, (unsigned)B), dim3(CONV_THREADS), 0, s, e);
-    TC_TRY(h, hipGetLastError());
+    WRNN_TRY(h, hipGetLastError());
     float *cur = a0, *nxt = a1;
     int rc;
     for (int i = 0; i < d.enc_conv_layers; ++i) {
@@ -845,8 +819,8 @@ int wrnn_taco_synthesize(wrnn_taco_handle *h, const wrnn_taco_call *c, void *str
     }
     el.tx = tx; el.memory = mem; el.Tx_max = Tx_max; el.H = H; el.zoneout = d.zoneout;
     hipLaunchKernelGGL(taco_enc_lstm_kernel, dim3(2u, (unsigned)B), dim3(LOOP_THREADS), (size_t)(6 * H + 4 * LOOP_THREADS) * sizeof(float), s, el);
-    TC_TRY(h, hipGetLastError());
-    if (c->encoder_dev) TC_TRY(h, hipMemcpyAsync(c->encoder_dev, mem, (size_t)B * Tx_max * E2 * 4, hipMemcpyDeviceToDevice, s));
+    WRNN_TRY(h, hipGetLastError());
+    if (c->encoder_dev) WRNN_TRY(h, hipMemcpyAsync(c->encoder_dev, mem, (size_t)B * Tx_max * E2 * 4, hipMemcpyDeviceToDevice, s));
     rc = launch_conv(h, s, mem, T("memory_layer/kernel"), nullptr, nullptr, 0, keys, tx, 1, B, Tx_max, E2, A, 1, 0);
     if (rc != WRNN_OK) return rc;
     // ---- decoder
@@ -868,7 +842,7 @@ int wrnn_taco_synthesize(wrnn_taco_handle *h, const wrnn_taco_call *c, void *str
     g.taps = d.attention_kernel; g.gta_max = gta ? c->gta_max : 0; g.max_iters = c->max_iters; g.steps_max = S; g.dropout = c->prenet_dropout ? 1 : 0;
     g.Pmax = Pmax; g.Kmax = Kmax; g.zoneout = d.zoneout; g.clip_lo = -d.max_abs_value - d.lower_bound_decay; g.clip_hi = d.max_abs_value;
     hipLaunchKernelGGL(taco_decoder_kernel, dim3((unsigned)B), dim3(LOOP_THREADS), dec_lds, s, g);
-    TC_TRY(h, hipGetLastError());
+    WRNN_TRY(h, hipGetLastError());
     // ---- postnet over steps r rows per utterance, the count read from the device
     const float *pin = c->decoder_dev;
     cur = a0; nxt = a1;
@@ -884,18 +858,18 @@ int wrnn_taco_synthesize(wrnn_taco_handle *h, const wrnn_taco_call *c, void *str
     if (rc != WRNN_OK) return rc;
     FinishArgs f{c->decoder_dev, cur, c->steps_dev, c->mel_raw_dev, c->mel_dev, T_out, M, r, g.clip_lo, g.clip_hi};
     hipLaunchKernelGGL(taco_finish_kernel, dim3((unsigned)(((size_t)T_out * M + CONV_THREADS - 1) / CONV_THREADS), (unsigned)B), dim3(CONV_THREADS), 0, s, f);
-    TC_TRY(h, hipGetLastError());
+    WRNN_TRY(h, hipGetLastError());
     return WRNN_OK;
 }
 
-const char *wrnn_taco_last_error(const wrnn_taco_handle *h) { return h ? h->err.c_str() : "null handle"; }
+const char *wrnn_taco_last_error(const wrnn_taco_handle *h) { return wrnn_last_error_of(h); }
 
 void wrnn_taco_destroy(wrnn_taco_handle *h) {
     if (!h) return;
-    if (h->img || h->ws) {
+    if (h->img || h->ws.p) {
         (void)hipSetDevice(h->d.device);
         if (h->img) (void)hipFree(h->img);
-        if (h->ws) (void)hipFree(h->ws);
+        h->ws.release();
     }
     delete h;
 }

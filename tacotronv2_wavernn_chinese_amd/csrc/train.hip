@@ -27,8 +27,6 @@
 // Entry points: wrnn_train_step (forward + the script's loss + backward in one call), wrnn_train_forward / wrnn_train_backward (the same
 // split where autograd splits it), wrnn_sync_status.
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 
 #include "team_common.h"
 #include "train_teamg_plan.h"
@@ -637,19 +635,11 @@ void wrnn_train_state_free(WrnnTrainState *st) {
 
 namespace {
 
-int tfail(wrnn_handle *h, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    h->err = buf;
-    return code;
-}
+// every HIP failure of a step carries the entry's name (the caller reads it through the model's handle)
 #define T_TRY(expr)                                                                                       \
     do {                                                                                                  \
         hipError_t e__ = (expr);                                                                          \
-        if (e__ != hipSuccess) return tfail(h, WRNN_ERR_HIP, "wrnn_train_step: %s: %s", #expr, hipGetErrorString(e__)); \
+        if (e__ != hipSuccess) return wrnn_failf(h, WRNN_ERR_HIP, "wrnn_train_step: %s: %s", #expr, hipGetErrorString(e__)); \
     } while (0)
 
 struct Gru {   // one recurrence's buffers
@@ -685,15 +675,15 @@ static int train_impl(wrnn_handle *h, int phase, const wrnn_loop_params *w, cons
                       float *d_mels_up_dev, float *d_aux_dev, void *stream) {
     if (!h) return WRNN_ERR_INVALID;
     const bool do_fwd = (phase & 1) != 0, do_bwd = (phase & 2) != 0;
-    if (!w || !x_dev || !mels_up_dev || !aux_dev || B < 1 || L < 1) return tfail(h, WRNN_ERR_INVALID, "wrnn_train_step: bad arguments");
-    if (do_bwd && !g) return tfail(h, WRNN_ERR_INVALID, "wrnn_train_backward: no gradient outputs");
-    if (do_bwd && !dY_ext && (!y_dev || !loss_out_dev)) return tfail(h, WRNN_ERR_INVALID, "wrnn_train_step: gradients need targets and a loss output");
+    if (!w || !x_dev || !mels_up_dev || !aux_dev || B < 1 || L < 1) return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_train_step: bad arguments");
+    if (do_bwd && !g) return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_train_backward: no gradient outputs");
+    if (do_bwd && !dY_ext && (!y_dev || !loss_out_dev)) return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_train_step: gradients need targets and a loss output");
     const WrnnDims &d = h->d;
     const int H = d.H, FC = d.FC, F = d.F, A = d.A, R = d.R, NC = d.NC;
-    if (H % 16 != 0 || FC < 1) return tfail(h, WRNN_ERR_INVALID, "wrnn_train_step: rnn_dims must be a multiple of 16");
+    if (H % 16 != 0 || FC < 1) return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_train_step: rnn_dims must be a multiple of 16");
     const size_t lds_f = (size_t)(44 * GR_HLD(H) + 4 * 512) * sizeof(float), lds_b = (size_t)(32 * (GB_KC + 4) + GR_UW * (3 * H + 4) + 4 * 128) * sizeof(float);
     if (lds_f > 160u * 1024u || lds_b > 160u * 1024u)
-        return tfail(h, WRNN_ERR_INVALID, "wrnn_train_step: rnn_dims too large for the step kernels' LDS tiles");
+        return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_train_step: rnn_dims too large for the step kernels' LDS tiles");
     T_TRY(hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     const long M = (long)B * L;
@@ -718,7 +708,7 @@ static int train_impl(wrnn_handle *h, int phase, const wrnn_loop_params *w, cons
     const size_t oIMG = take((size_t)786432);                                // weight image of the recurrence at hand (team kernels)
     const bool fresh = need > st->ws_floats;
     if (!do_fwd && (fresh || !st->fwd_valid || st->B != B || st->L != L))
-        return tfail(h, WRNN_ERR_STATE, "wrnn_train_backward: no matching wrnn_train_forward before it (same handle, B, L)");
+        return wrnn_failf(h, WRNN_ERR_STATE, "wrnn_train_backward: no matching wrnn_train_forward before it (same handle, B, L)");
     if (fresh) {
         if (st->ws) (void)hipFree(st->ws);
         st->ws = nullptr; st->ws_floats = 0;
@@ -926,14 +916,14 @@ extern "C" int wrnn_train_step(wrnn_handle *h, const wrnn_loop_params *w, const 
 
 extern "C" int wrnn_train_forward(wrnn_handle *h, const wrnn_loop_params *w, const float *x_dev, const float *mels_up_dev, const float *aux_dev,
                                   int32_t B, int64_t L, float *logits_out_dev, void *stream) {
-    if (h && !logits_out_dev) return tfail(h, WRNN_ERR_INVALID, "wrnn_train_forward: logits_out_dev is the result");
+    if (h && !logits_out_dev) return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_train_forward: logits_out_dev is the result");
     return train_impl(h, 1, w, nullptr, x_dev, mels_up_dev, aux_dev, nullptr, nullptr, B, L, nullptr, logits_out_dev, nullptr, nullptr, stream);
 }
 
 extern "C" int wrnn_train_backward(wrnn_handle *h, const wrnn_loop_params *w, const wrnn_loop_params *g, const float *d_logits_dev,
                                    const float *x_dev, const float *mels_up_dev, const float *aux_dev, int32_t B, int64_t L,
                                    float *d_mels_up_dev, float *d_aux_dev, void *stream) {
-    if (h && !d_logits_dev) return tfail(h, WRNN_ERR_INVALID, "wrnn_train_backward: d_logits_dev missing");
+    if (h && !d_logits_dev) return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_train_backward: d_logits_dev missing");
     return train_impl(h, 2, w, g, x_dev, mels_up_dev, aux_dev, nullptr, d_logits_dev, B, L, nullptr, nullptr, d_mels_up_dev, d_aux_dev, stream);
 }
 
@@ -946,8 +936,8 @@ extern "C" int wrnn_sync_status(wrnn_handle *h, void *stream) {
     unsigned errw = 0;
     T_TRY(hipMemcpy(&errw, h->err_dev, sizeof(errw), hipMemcpyDeviceToHost));
     if (errw == WRNN_DEVERR_BUSY)
-        return tfail(h, WRNN_ERR_BUSY, "a team kernel's workgroups did not all become resident: the GPU is shared with another kernel (retry)");
-    if (errw) return tfail(h, WRNN_ERR_TIMEOUT, "device-side bounded spin gave up (code %u)", errw);
+        return wrnn_failf(h, WRNN_ERR_BUSY, "a team kernel's workgroups did not all become resident: the GPU is shared with another kernel (retry)");
+    if (errw) return wrnn_failf(h, WRNN_ERR_TIMEOUT, "device-side bounded spin gave up (code %u)", errw);
     return WRNN_OK;
 }
 
@@ -971,7 +961,7 @@ extern "C" int wrnn_train_last_recurrence(const wrnn_handle *h, int32_t *kernel,
 extern "C" int wrnn_train_set_precision(wrnn_handle *h, int32_t fmt) {
     if (!h) return WRNN_ERR_INVALID;
     if (fmt != WRNN_TRAIN_F32 && fmt != WRNN_TRAIN_BF16)
-        return tfail(h, WRNN_ERR_INVALID, "wrnn_train_set_precision: %d is neither WRNN_TRAIN_F32 nor WRNN_TRAIN_BF16", fmt);
+        return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_train_set_precision: %d is neither WRNN_TRAIN_F32 nor WRNN_TRAIN_BF16", fmt);
     h->train_precision = fmt;
     return WRNN_OK;
 }
@@ -999,12 +989,12 @@ extern "C" int wrnn_debug_train_gemm(wrnn_handle *h, int32_t precision, int32_t 
                                      int64_t ldb, float *C, int64_t ldc, int32_t M, int32_t N, int32_t K, int32_t beta, const float *bias,
                                      int32_t relu, int32_t slices, void *stream) {
     if (!h) return WRNN_ERR_INVALID;
-    if (precision != WRNN_TRAIN_F32 && precision != WRNN_TRAIN_BF16) return tfail(h, WRNN_ERR_INVALID, "wrnn_debug_train_gemm: bad precision %d", precision);
+    if (precision != WRNN_TRAIN_F32 && precision != WRNN_TRAIN_BF16) return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_debug_train_gemm: bad precision %d", precision);
     if (!A || !B || !C || M < 1 || N < 1 || K < 0 || lda < 1 || ldb < 1 || ldc < N || slices < 0 || slices > 64)
-        return tfail(h, WRNN_ERR_INVALID, "wrnn_debug_train_gemm: bad arguments");
-    if ((ta ? lda < M : lda < K) || (tb ? ldb < K : ldb < N)) return tfail(h, WRNN_ERR_INVALID, "wrnn_debug_train_gemm: a leading dimension is shorter than its row");
-    if (slices != 1 && (bias || relu)) return tfail(h, WRNN_ERR_INVALID, "wrnn_debug_train_gemm: a split product takes no bias and no relu");
-    if (precision == WRNN_TRAIN_BF16 && ta && tb) return tfail(h, WRNN_ERR_UNSUPPORTED, "wrnn_debug_train_gemm: the bf16 kernel has no TT form");
+        return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_debug_train_gemm: bad arguments");
+    if ((ta ? lda < M : lda < K) || (tb ? ldb < K : ldb < N)) return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_debug_train_gemm: a leading dimension is shorter than its row");
+    if (slices != 1 && (bias || relu)) return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_debug_train_gemm: a split product takes no bias and no relu");
+    if (precision == WRNN_TRAIN_BF16 && ta && tb) return wrnn_failf(h, WRNN_ERR_UNSUPPORTED, "wrnn_debug_train_gemm: the bf16 kernel has no TT form");
     T_TRY(hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     int32_t n32 = 0, n16 = 0;

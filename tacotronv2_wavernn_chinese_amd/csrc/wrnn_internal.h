@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/wavernn_amd.h"
+#include "handle_common.h"
 
 #define WRNN_MAX_UP 4
 #define WRNN_PROF_SLOTS 32   // phase-cycle counters per wave (WRNN_TEAM_PROF=1)
@@ -459,13 +460,9 @@ hipError_t wrnn_launch_frame_linear(int mode, const float *src, size_t src_bstri
 
 // ---- host launch path of the team kernels, shared by the offline calls (api.hip), the streams (stream.hip) and training (train.hip) ----
 
-// h->err = the formatted message (h may be null); returns `code` (launch.hip)
-int wrnn_fail(wrnn_handle *h, int code, const char *fmt, ...);
-#define WRNN_HIP_TRY(h, expr)                                                                                \
-    do {                                                                                                     \
-        hipError_t e__ = (expr);                                                                             \
-        if (e__ != hipSuccess) return wrnn_fail((h), WRNN_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e__)); \
-    } while (0)
+// The main handle's own formatter (launch.hip): its texts are cut at 511 characters, where handle_common.h's template cuts at 399.  A call
+// of wrnn_failf or WRNN_TRY on a wrnn_handle picks this one (a non-template is preferred to the template).
+int wrnn_failf(wrnn_handle *h, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
 
 // Grow-only device scratch of `need` elements: kept while it is large enough, so a buffer stays at its high-water mark.  A failed
 // allocation leaves p null and cap 0.
@@ -474,7 +471,7 @@ int wrnn_grow(wrnn_handle *h, T *&p, size_t &cap, size_t need) {
     if (need <= cap) return WRNN_OK;
     if (p) (void)hipFree(p);
     p = nullptr; cap = 0;
-    WRNN_HIP_TRY(h, hipMalloc(&p, need * sizeof(T)));
+    WRNN_TRY(h, hipMalloc(&p, need * sizeof(T)));
     cap = need;
     return WRNN_OK;
 }
