@@ -1116,7 +1116,68 @@ int wrnn_taco_load_tensor(wrnn_taco_handle *h, const char *name, const float *da
  * on `stream` but for the copies of ids, lengths and seeds.  WRNN_ERR_STATE: a tensor of the table has not been loaded (named). */
 int wrnn_taco_synthesize(wrnn_taco_handle *h, const wrnn_taco_call *call, void *stream);
 const char *wrnn_taco_last_error(const wrnn_taco_handle *h);
+/* With streams still open the handle lives on until the last of them is closed (they read its weights); from then on
+ * wrnn_taco_load_tensor, wrnn_taco_synthesize and wrnn_taco_stream_open on it are WRNN_ERR_STATE (the table queries and the error text
+ * still answer). */
 void wrnn_taco_destroy(wrnn_taco_handle *h);
+
+/* ---- Tacotron-2, streaming: mel frames while the decoder is still running ---------------------------------------------------------
+ * A stream is a free-running wrnn_taco_synthesize cut into pushes of decoder steps.  The encoder runs at open; every step entry
+ * advances each unfinished utterance by up to n_steps steps from state kept in device memory (the last frame, h and c of every layer,
+ * the context, the alignments and their sum, mu, the attention window's two counters, the first stop, the step count), then runs the
+ * postnet over the rows that have become final, and waits once.  What comes out, concatenated over any partition into pushes, is what
+ * wrnn_taco_synthesize writes for the same text, seeds, max_iters and prenet_dropout, bit for bit.
+ * The release rule: a mel frame reads the decoder's frames up to halo = postnet_layers * ((k - 1) - (k - 1) / 2) rows ahead
+ * (k = postnet_kernel, integer division: the right-hand reach of a 'same' convolution, once per layer; the 1-tap projection adds
+ * nothing).  While an utterance runs, mel frames t < decoded - halo are final; once it has finished (a stop token above 0.5, or
+ * max_iters steps) all mel_frames of them are.  decoder, alignments, stop and max_attentions of a step are final when it has run.
+ * The stream owns all its memory (wrnn_taco_stream_info: workspace_bytes; each postnet layer keeps max_iters r rows per utterance),
+ * the handle's scratch is not touched: offline calls and several streams of one handle may interleave on one HIP stream.  While a
+ * stream is open wrnn_taco_load_tensor is WRNN_ERR_STATE.  Teacher forcing is not streamed. */
+typedef struct wrnn_taco_stream wrnn_taco_stream;
+typedef struct wrnn_taco_stream_opts {
+    uint32_t struct_size;        /* the size of this struct */
+    int32_t B, Tx_max;           /* utterances; the row stride of ids_host */
+    int32_t max_iters;           /* decoder steps at most; >= 1; the step stride of the outputs */
+    int32_t prenet_dropout;      /* 0: no masks, no scaling */
+    const int32_t *ids_host;     /* (B, Tx_max) */
+    const int32_t *tx_host;      /* (B) symbols per utterance */
+    const uint64_t *seeds_host;  /* (B) */
+    const float *gta_dev;        /* must be NULL: a target is WRNN_ERR_INVALID */
+} wrnn_taco_stream_opts;
+typedef struct wrnn_taco_stream_outputs {
+    uint32_t struct_size;        /* the size of this struct, set by the caller */
+    /* on the device, owned by the stream, full length, filled front to back; element strides between utterances */
+    float *encoder_dev;          /* (B, Tx_max, 2 encoder_lstm_units), complete after open */
+    float *decoder_dev;          /* (B, max_iters r, num_mels) */
+    float *mel_raw_dev;          /* (B, max_iters r, num_mels) */
+    float *mel_dev;              /* (B, max_iters r, num_mels) */
+    float *alignments_dev;       /* (B, max_iters, Tx_max) */
+    float *stop_dev;             /* (B, max_iters r) */
+    int32_t *max_attentions_dev; /* (B, max_iters) */
+    int32_t *steps_dev;          /* (B) decoder steps run so far */
+    int32_t *mel_frames_dev;     /* (B) as wrnn_taco_call's once the utterance has finished */
+    int64_t encoder_stride, frames_stride, alignments_stride, stop_stride, max_attentions_stride;
+} wrnn_taco_stream_outputs;
+/* Host only: the halo of the release rule for these dims; WRNN_ERR_INVALID (negative) for NULL, postnet_layers < 0 or
+ * postnet_kernel < 1. */
+int wrnn_taco_stream_halo(const wrnn_taco_dims *dims);
+/* The host-side checks of wrnn_taco_synthesize, with its wording; then uploads the weights if a tensor was loaded since, allocates and
+ * zeroes the stream's workspace and launches the encoder on `stream`.  A refusal leaves *out NULL and its reason in the HANDLE's
+ * wrnn_taco_last_error. */
+int wrnn_taco_stream_open(wrnn_taco_handle *h, const wrnn_taco_stream_opts *opts, void *stream, wrnn_taco_stream **out);
+/* Up to n_steps >= 1 (WRNN_ERR_INVALID otherwise) more decoder steps of every unfinished utterance and the postnet rows they make
+ * final, on `stream`; one wait; then per utterance (B entries each): decoder frames so far (steps r), final mel frames so far (the
+ * release rule), finished (0 / 1).  A finished utterance's workgroups return at once.  WRNN_ERR_STATE once every utterance has
+ * finished.  The pushes of one stream must be ordered on the device (one HIP stream). */
+int wrnn_taco_stream_step(wrnn_taco_stream *st, int32_t n_steps, void *stream, int32_t *decoded_host, int32_t *final_host, int32_t *finished_host);
+int wrnn_taco_stream_view(const wrnn_taco_stream *st, wrnn_taco_stream_outputs *out);
+/* any pointer may be NULL */
+int wrnn_taco_stream_info(const wrnn_taco_stream *st, int32_t *B, int32_t *Tx_max, int32_t *max_iters, int32_t *halo, int64_t *workspace_bytes);
+const char *wrnn_taco_stream_last_error(const wrnn_taco_stream *st);
+/* Frees the stream's memory (the free waits for work that still uses it).  NULL is a no-op.  Close a stream before its handle is destroyed (see
+ * wrnn_taco_destroy for what happens otherwise). */
+void wrnn_taco_stream_close(wrnn_taco_stream *st);
 
 #ifdef __cplusplus
 }

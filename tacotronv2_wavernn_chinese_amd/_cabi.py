@@ -55,7 +55,9 @@ EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wr
                     'wrnn_align_create', 'wrnn_align_frames', 'wrnn_align_workspace_bytes', 'wrnn_align_cost', 'wrnn_align_path',
                     'wrnn_align_score', 'wrnn_align_last_error', 'wrnn_align_destroy',
                     'wrnn_taco_create', 'wrnn_taco_tensor_count', 'wrnn_taco_tensor_name', 'wrnn_taco_tensor_shape', 'wrnn_taco_load_tensor',
-                    'wrnn_taco_synthesize', 'wrnn_taco_last_error', 'wrnn_taco_destroy')
+                    'wrnn_taco_synthesize', 'wrnn_taco_last_error', 'wrnn_taco_destroy',
+                    'wrnn_taco_stream_halo', 'wrnn_taco_stream_open', 'wrnn_taco_stream_step', 'wrnn_taco_stream_view', 'wrnn_taco_stream_info',
+                    'wrnn_taco_stream_last_error', 'wrnn_taco_stream_close')
 
 
 def epilogue_tables(n_classes: int, overlap: int, hop: int):
@@ -118,6 +120,20 @@ class TacoCall(C.Structure):
                 ('gta_max', C.c_int32), ('gta_frames_host', C.c_void_p), ('encoder_dev', C.c_void_p), ('decoder_dev', C.c_void_p),
                 ('mel_raw_dev', C.c_void_p), ('mel_dev', C.c_void_p), ('alignments_dev', C.c_void_p), ('stop_dev', C.c_void_p),
                 ('max_attentions_dev', C.c_void_p), ('steps_dev', C.c_void_p), ('mel_frames_dev', C.c_void_p)]
+
+
+class TacoStreamOpts(C.Structure):
+    """``wrnn_taco_stream_opts``."""
+    _fields_ = [('struct_size', C.c_uint32), ('B', C.c_int32), ('Tx_max', C.c_int32), ('max_iters', C.c_int32), ('prenet_dropout', C.c_int32),
+                ('ids_host', C.c_void_p), ('tx_host', C.c_void_p), ('seeds_host', C.c_void_p), ('gta_dev', C.c_void_p)]
+
+
+class TacoStreamOutputs(C.Structure):
+    """``wrnn_taco_stream_outputs``."""
+    _fields_ = [('struct_size', C.c_uint32), ('encoder_dev', C.c_void_p), ('decoder_dev', C.c_void_p), ('mel_raw_dev', C.c_void_p),
+                ('mel_dev', C.c_void_p), ('alignments_dev', C.c_void_p), ('stop_dev', C.c_void_p), ('max_attentions_dev', C.c_void_p),
+                ('steps_dev', C.c_void_p), ('mel_frames_dev', C.c_void_p), ('encoder_stride', C.c_int64), ('frames_stride', C.c_int64),
+                ('alignments_stride', C.c_int64), ('stop_stride', C.c_int64), ('max_attentions_stride', C.c_int64)]
 
 
 LOOP_PARAM_FIELDS = ('I_w', 'I_b', 'rnn1_w_ih', 'rnn1_w_hh', 'rnn1_b_ih', 'rnn1_b_hh', 'rnn2_w_ih', 'rnn2_w_hh', 'rnn2_b_ih',
@@ -611,6 +627,21 @@ def load_library() -> C.CDLL:
     lib.wrnn_taco_last_error.restype = C.c_char_p
     lib.wrnn_taco_destroy.argtypes = [vp]
     lib.wrnn_taco_destroy.restype = None
+    i32p = C.POINTER(C.c_int32)
+    lib.wrnn_taco_stream_halo.argtypes = [C.POINTER(TacoDims)]
+    lib.wrnn_taco_stream_halo.restype = C.c_int
+    lib.wrnn_taco_stream_open.argtypes = [vp, C.POINTER(TacoStreamOpts), vp, C.POINTER(vp)]
+    lib.wrnn_taco_stream_open.restype = C.c_int
+    lib.wrnn_taco_stream_step.argtypes = [vp, C.c_int32, vp, i32p, i32p, i32p]
+    lib.wrnn_taco_stream_step.restype = C.c_int
+    lib.wrnn_taco_stream_view.argtypes = [vp, C.POINTER(TacoStreamOutputs)]
+    lib.wrnn_taco_stream_view.restype = C.c_int
+    lib.wrnn_taco_stream_info.argtypes = [vp, i32p, i32p, i32p, i32p, C.POINTER(C.c_int64)]
+    lib.wrnn_taco_stream_info.restype = C.c_int
+    lib.wrnn_taco_stream_last_error.argtypes = [vp]
+    lib.wrnn_taco_stream_last_error.restype = C.c_char_p
+    lib.wrnn_taco_stream_close.argtypes = [vp]
+    lib.wrnn_taco_stream_close.restype = None
     lib.wrnn_quantise.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp]
     lib.wrnn_quantise.restype = C.c_int
     lib.wrnn_collate_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -1453,8 +1484,8 @@ class NativeTacotron:
     """Owner of one ``wrnn_taco_handle`` (Tacotron-2 inference: symbol ids -> mel).  Creating it touches no device; dims the library
     refuses raise ``WrnnError`` with its reason."""
 
-    def __init__(self, dims: TacoDims):
-        self.lib = load_library()
+    def __init__(self, dims: TacoDims, lib=None):
+        self.lib = lib if lib is not None else load_library()   # lib: another build of the library with its wrnn_taco_* argtypes set (A/B tools)
         self.dims = dims
         self._h = C.c_void_p()
         rc = self.lib.wrnn_taco_create(C.byref(dims), C.byref(self._h))
@@ -1483,10 +1514,65 @@ class NativeTacotron:
     def synthesize(self, call: TacoCall, stream: int):
         self._check(self.lib.wrnn_taco_synthesize(self._h, C.byref(call), stream or None))
 
+    def stream_open(self, opts: 'TacoStreamOpts', stream: int) -> 'NativeTacotronStream':
+        st = C.c_void_p()
+        self._check(self.lib.wrnn_taco_stream_open(self._h, C.byref(opts), stream or None, C.byref(st)))
+        return NativeTacotronStream(self, st, int(opts.B))
+
     def close(self):
         if getattr(self, '_h', None):
             self.lib.wrnn_taco_destroy(self._h)
             self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def taco_stream_halo(dims: TacoDims) -> int:
+    """Host only: ``wrnn_taco_stream_halo`` -- the decoder frames a mel frame waits for."""
+    return int(load_library().wrnn_taco_stream_halo(C.byref(dims)))
+
+
+class NativeTacotronStream:
+    """Owner of one ``wrnn_taco_stream``; it keeps its ``NativeTacotron`` alive."""
+
+    def __init__(self, owner: NativeTacotron, st, B: int):
+        self.owner, self.lib, self._st, self.B = owner, owner.lib, st, B
+
+    def _live(self):
+        if not self._st:
+            raise WrnnError(ERR_STATE, 'the stream is closed')
+        return self._st
+
+    def _check(self, rc: int):
+        if rc != 0:
+            raise WrnnError(rc, self.lib.wrnn_taco_stream_last_error(self._st).decode())
+
+    def step(self, n: int, stream: int):
+        """(decoder frames so far, final mel frames so far, finished) per utterance, after the one wait of the push."""
+        st = self._live()
+        dec, fin, done = ((C.c_int32 * self.B)() for _ in range(3))
+        self._check(self.lib.wrnn_taco_stream_step(st, int(n), stream or None, dec, fin, done))
+        return list(dec), list(fin), [bool(x) for x in done]
+
+    def view(self) -> TacoStreamOutputs:
+        v = TacoStreamOutputs()
+        v.struct_size = C.sizeof(TacoStreamOutputs)
+        self._check(self.lib.wrnn_taco_stream_view(self._live(), C.byref(v)))
+        return v
+
+    def info(self) -> dict:
+        b, tx, it, halo, ws = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+        self._check(self.lib.wrnn_taco_stream_info(self._live(), C.byref(b), C.byref(tx), C.byref(it), C.byref(halo), C.byref(ws)))
+        return dict(B=b.value, Tx_max=tx.value, max_iters=it.value, halo=halo.value, workspace_bytes=ws.value)
+
+    def close(self):
+        if getattr(self, '_st', None):
+            self.lib.wrnn_taco_stream_close(self._st)
+            self._st = None
 
     def __del__(self):
         try:

@@ -8,6 +8,13 @@
 //   taco_decoder_kernel  grid (B)                                          ONE persistent workgroup per utterance: the whole decoder loop, its
 //                                                                          state in LDS, the weights streamed from L2; the stop is decided here
 //   taco_finish_kernel   grid (ceil(S r M / 256), B)                       residual, clips, the map to [0, 1]
+// A stream (wrnn_taco_stream_*) runs the same step and the same convolution from state kept in device memory between pushes:
+//   taco_decoder_kernel<true>  grid (B)                                up to n more steps of every unfinished utterance: the other
+//                                                                          instantiation of the decoder kernel, with a load at entry and a
+//                                                                          store at exit
+//   taco_conv_kernel<true>     grid (ceil((n r + held back) / 8) + 1, B, ..)  the conv kernel over the rows of a layer that this push made
+//                                                                          final, the range read from the stream's state
+//   taco_finish_window_kernel  grid (ceil((n r + halo) M / 256), B)        taco_finish_kernel's arithmetic over the released rows
 // Nothing crosses workgroups, nothing spins, no atomics; every sum has a fixed order that does not depend on the batch, so an utterance of
 // a ragged batch gives the bits of the call on it alone.  All layouts are the reference's own ([in, out] dense kernels, [tap, in, out]
 // conv kernels): thread j of a layer owns output column j, and a wave reads 64 neighbouring floats of one weight row.
@@ -28,6 +35,8 @@ constexpr int LOOP_THREADS = 1024;  // the recurrences: 16 waves on one CU
 constexpr int MAX_DEC_LAYERS = 4;
 constexpr int MAX_TAPS = 64;
 constexpr size_t LDS_LIMIT = 64 * 1024;
+// A stream's integers per utterance, in device memory between pushes.  WAS: the utterance had finished before this push (nothing is new).
+enum { ST_MAX_ATT = 0, ST_POS_REC, ST_FIRST_STOP, ST_STEP, ST_FINISHED, ST_PREV, ST_WAS, ST_INTS = 8 };
 
 __device__ inline float sigmoid_acc(float x) { return 1.0f / (1.0f + expf(-x)); }
 
@@ -146,15 +155,41 @@ struct ConvArgs {
     const int32_t *len;   // (B): the utterance's rows are len[b] * len_mul, clamped to 0 .. T_max
     int32_t len_mul, T_max, Cin, Cout, taps, act;   // act 0: none, 1: relu, 2: tanh
 };
+struct ConvWindow {       // the windowed variant's own arguments; ConvArgs.len is unused there
+    const int32_t *win;   // the stream's integers (B, ST_INTS)
+    int32_t held;         // rows this layer's output is held back behind the decoder while the utterance runs
+};
 // A workgroup takes CONV_TT time steps of 64 output channels; its 4 waves split the taps x Cin products between them (the chain of
 // dependent weight loads is what a small grid waits for) and add their partial sums in wave order.  Row (q + k) of the tile, channel c,
 // is tile[q Cin + (k Cin + c)]: the products of one output are one flat run of taps x Cin weights against a flat run of the tile.
-__global__ void __launch_bounds__(CONV_THREADS) taco_conv_kernel(ConvArgs g) {
+// WINDOW: the rows [lo, hi) that became final at this layer in the stream's last push.  The tiles start at multiples of CONV_TT, as in
+// the whole-utterance launch: the order of an output's sum does not depend on the tile, but the compiler fuses the multiply-adds of some
+// of a tile's CONV_TT rows and not of others, so a row gives the offline bits only at the offline position in its tile.  Rows of the
+// first tile below lo are computed again and not written.  L is the decoder's row count so far: while the utterance runs every row
+// read lies below it, and once it has finished it is the true length.
+template <bool WINDOW>
+__global__ void __launch_bounds__(CONV_THREADS) taco_conv_kernel(ConvArgs g, ConvWindow cw) {
     extern __shared__ __align__(16) float tile[];         // (CONV_TT + taps - 1, Cin): rows t0 - left .. of the input, zeros outside the utterance
     __shared__ float part[CONV_THREADS / 64][CONV_TT][64];
-    const int b = blockIdx.y, t0 = blockIdx.x * CONV_TT, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, co = blockIdx.z * 64 + lane;
-    const long lraw = (long)g.len[b] * g.len_mul;
+    const int b = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, co = blockIdx.z * 64 + lane;
+    int t0 = blockIdx.x * CONV_TT, lo = 0, hi = g.T_max;
+    long lraw;
+    if constexpr (WINDOW) {
+        const int32_t *si = cw.win + (long)b * ST_INTS;
+        if (si[ST_WAS]) return;
+        lraw = (long)si[ST_STEP] * g.len_mul;
+    } else {
+        lraw = (long)g.len[b] * g.len_mul;
+    }
     const int L = (int)(lraw < 0 ? 0 : lraw > g.T_max ? g.T_max : lraw);
+    if constexpr (WINDOW) {
+        const int32_t *si = cw.win + (long)b * ST_INTS;
+        const long praw = (long)si[ST_PREV] * g.len_mul - cw.held;
+        lo = (int)(praw < 0 ? 0 : praw > L ? L : praw);
+        hi = si[ST_FINISHED] ? L : max(0, L - cw.held);
+        t0 += lo / CONV_TT * CONV_TT;
+        if (t0 >= hi) return;   // the whole workgroup
+    }
     const int left = (g.taps - 1) / 2, rows = CONV_TT + g.taps - 1;
     const float *in = g.in + (long)b * g.T_max * g.Cin;
     for (int x = threadIdx.x; x < rows * g.Cin; x += CONV_THREADS) {
@@ -183,7 +218,12 @@ __global__ void __launch_bounds__(CONV_THREADS) taco_conv_kernel(ConvArgs g) {
     const float s = g.bn_s ? g.bn_s[co] : 1.0f, sh = g.bn_s ? g.bn_b[co] : 0.0f;
     for (int q = wave; q < CONV_TT; q += CONV_THREADS / 64) {
         const int t = t0 + q;
-        if (t >= g.T_max) break;
+        if constexpr (WINDOW) {
+            if (t >= hi) break;
+            if (t < lo) continue;
+        } else {
+            if (t >= g.T_max) break;
+        }
         float v = bias;
         for (int p = 0; p < CONV_THREADS / 64; ++p) v += part[p][q][lane];
         if (g.act == 1) v = fmaxf(v, 0.0f);
@@ -244,9 +284,19 @@ struct DecArgs {
     int32_t Tx_max, E2, A, M, r, D, L, n_prenet, prenet[WRNN_TACO_MAX_PRENET], taps, gta_max, max_iters, steps_max, dropout, Pmax, Kmax;
     float zoneout, clip_lo, clip_hi;
 };
+// The resumable variant's own arguments: the state between pushes, floats (B, st_stride): xin[M] h[L D] c[L D] ctx[E2] al[Tx_max]
+// cum[Tx_max] mu, integers (B, ST_INTS); a launch runs n_steps more steps at most.
+struct DecState {
+    float *st_f;
+    int32_t *st_i;
+    int32_t st_stride, n_steps;
+};
 // LDS (floats): scratch[4 blockDim.x] xin[M] pa[Pmax] pb[Pmax] vec[Kmax] h[L D] c[L D] gates[4D] y[D] ctx[E2] q[A] al[Tx_max] cum[Tx_max]
 //               sm[Tx_max] fw[Tx_max] proj[r M + r] mu1[1] red[16], then int: flags[4]
-__global__ void __launch_bounds__(LOOP_THREADS) taco_decoder_kernel(DecArgs g) {
+// RESUME: steps s0 .. s0 + n_steps - 1 of the same loop, s0 and everything a step hands to the next read from st_f / st_i and written back.
+// The dropout counters and the output rows are keyed by the absolute step, so a partition into launches gives the bits of one launch.
+template <bool RESUME>
+__global__ void __launch_bounds__(LOOP_THREADS) taco_decoder_kernel(DecArgs g, DecState ds) {
     extern __shared__ __align__(16) float lds[];
     const int tid = threadIdx.x, NT = blockDim.x, b = blockIdx.x, wave = tid >> 6, lane = tid & 63, nw = NT >> 6;
     const int M = g.M, D = g.D, E2 = g.E2, A = g.A, r = g.r, L = g.L, RM = g.r * g.M;
@@ -260,6 +310,20 @@ __global__ void __launch_bounds__(LOOP_THREADS) taco_decoder_kernel(DecArgs g) {
     int steps = g.max_iters;
     if (g.gta) steps = g.gta_steps[b];
     steps = min(max(steps, 0), g.steps_max);
+    const int all_steps = steps;
+    int s0 = 0;
+    float *sf = nullptr;
+    int32_t *si = nullptr;
+    if constexpr (RESUME) {
+        sf = ds.st_f + (long)b * ds.st_stride;
+        si = ds.st_i + (long)b * ST_INTS;
+        s0 = min(max(si[ST_STEP], 0), all_steps);
+        if (si[ST_FINISHED]) {   // the whole workgroup: nothing is new for this utterance
+            if (tid == 0) { si[ST_PREV] = s0; si[ST_WAS] = 1; }
+            return;
+        }
+        steps = min(all_steps, s0 + min(max(ds.n_steps, 0), all_steps));
+    }
     for (int j = tid; j < M; j += NT) xin[j] = 0.0f;
     for (int j = tid; j < L * D; j += NT) { h[j] = 0.0f; c[j] = 0.0f; }
     for (int j = tid; j < E2; j += NT) ctx[j] = 0.0f;
@@ -269,6 +333,23 @@ __global__ void __launch_bounds__(LOOP_THREADS) taco_decoder_kernel(DecArgs g) {
     int first_stop = -1, s = 0;
     const float z = g.zoneout, keep = 1.0f - g.zoneout;
     const int left = (g.taps - 1) / 2;
+    if constexpr (RESUME) {
+        float *sh = sf + M, *sc = sh + L * D, *sctx = sc + L * D, *sal = sctx + E2, *scum = sal + g.Tx_max;
+        if (s0 > 0) {
+            for (int j = tid; j < M; j += NT) xin[j] = sf[j];
+            for (int j = tid; j < L * D; j += NT) { h[j] = sh[j]; c[j] = sc[j]; }
+            for (int j = tid; j < E2; j += NT) ctx[j] = sctx[j];
+            for (int j = tid; j < Tx; j += NT) { al[j] = sal[j]; cum[j] = scum[j]; }
+            mu = scum[g.Tx_max];
+            first_stop = si[ST_FIRST_STOP];
+            s = s0;
+        }
+        if (tid == 0) {
+            if (s0 > 0) { flags[0] = si[ST_MAX_ATT]; flags[1] = si[ST_POS_REC]; }
+            si[ST_PREV] = s0;
+            si[ST_WAS] = 0;
+        }
+    }
     __syncthreads();
     for (; s < steps; ++s) {
         // ---- prenet: dense -> relu -> dropout(0.5), always on
@@ -434,6 +515,21 @@ __global__ void __launch_bounds__(LOOP_THREADS) taco_decoder_kernel(DecArgs g) {
         __syncthreads();
         if (!g.gta && flags[2]) { ++s; break; }
     }
+    if constexpr (RESUME) {   // every thread is past the last barrier of the last step
+        float *sh = sf + M, *sc = sh + L * D, *sctx = sc + L * D, *sal = sctx + E2, *scum = sal + g.Tx_max;
+        for (int j = tid; j < M; j += NT) sf[j] = xin[j];
+        for (int j = tid; j < L * D; j += NT) { sh[j] = h[j]; sc[j] = c[j]; }
+        for (int j = tid; j < E2; j += NT) sctx[j] = ctx[j];
+        for (int j = tid; j < Tx; j += NT) { sal[j] = al[j]; scum[j] = cum[j]; }
+        if (tid == 0) {
+            scum[g.Tx_max] = mu;
+            si[ST_MAX_ATT] = flags[0];
+            si[ST_POS_REC] = flags[1];
+            si[ST_FIRST_STOP] = first_stop;
+            si[ST_STEP] = s;
+            si[ST_FINISHED] = (flags[2] || s >= all_steps) ? 1 : 0;
+        }
+    }
     if (tid == 0) {
         g.steps[b] = s;
         g.mel_frames[b] = (!g.gta && first_stop >= 0) ? first_stop : s * r;
@@ -447,6 +543,12 @@ struct FinishArgs {
     int32_t T_max, M, r;
     float clip_lo, clip_hi;
 };
+__device__ inline void finish_element(const FinishArgs &g, long at) {
+    const float raw = fminf(fmaxf(g.decoder[at] + g.residual[at], g.clip_lo), g.clip_hi);
+    g.mel_raw[at] = raw;
+    const float v = fminf(fmaxf(raw, -g.clip_hi), g.clip_hi);
+    g.mel[at] = fminf(fmaxf((v + g.clip_hi) / (2.0f * g.clip_hi), 0.0f), 1.0f);
+}
 __global__ void __launch_bounds__(CONV_THREADS) taco_finish_kernel(FinishArgs g) {
     const int b = blockIdx.y;
     const long x = (long)blockIdx.x * CONV_THREADS + threadIdx.x, n = (long)g.T_max * g.M;
@@ -454,10 +556,19 @@ __global__ void __launch_bounds__(CONV_THREADS) taco_finish_kernel(FinishArgs g)
     const long rows = (long)min(max(g.steps[b], 0), g.T_max / g.r) * g.r;
     const long at = (long)b * n + x;
     if (x / g.M >= rows) { g.mel_raw[at] = 0.0f; g.mel[at] = 0.0f; return; }
-    const float raw = fminf(fmaxf(g.decoder[at] + g.residual[at], g.clip_lo), g.clip_hi);
-    g.mel_raw[at] = raw;
-    const float v = fminf(fmaxf(raw, -g.clip_hi), g.clip_hi);
-    g.mel[at] = fminf(fmaxf((v + g.clip_hi) / (2.0f * g.clip_hi), 0.0f), 1.0f);
+    finish_element(g, at);
+}
+// The rows a stream's last push released: [prev r - halo, steps r - halo), up to the true end once the utterance has finished.  The rows
+// beyond stay the zeros the stream's buffers were opened with.
+__global__ void __launch_bounds__(CONV_THREADS) taco_finish_window_kernel(FinishArgs g, const int32_t *win, int halo) {
+    const int b = blockIdx.y;
+    const int32_t *si = win + (long)b * ST_INTS;
+    if (si[ST_WAS]) return;
+    const long L = (long)min(max(si[ST_STEP], 0), g.T_max / g.r) * g.r;
+    const long lo = min(max((long)si[ST_PREV] * g.r - halo, 0L), L), hi = si[ST_FINISHED] ? L : max(L - halo, 0L);
+    const long x = lo * g.M + (long)blockIdx.x * CONV_THREADS + threadIdx.x;
+    if (x >= hi * g.M) return;
+    finish_element(g, (long)b * g.T_max * g.M + x);
 }
 
 struct Tensor {
@@ -483,6 +594,25 @@ struct wrnn_taco_handle {
     size_t img_cap = 0;
     size_t off_bn_enc = 0, off_bn_post = 0, off_loc_m = 0, off_att_bias = 0, off_proj_w = 0, off_proj_b = 0;
     WrnnScratch ws;               // the scratch of a call, grown on demand
+    int open_streams = 0;         // wrnn_taco_stream objects that read img
+    bool destroyed = false;       // wrnn_taco_destroy came while streams were open: the last close frees the handle
+    std::string err;
+};
+
+struct wrnn_taco_stream {
+    wrnn_taco_handle *h = nullptr;
+    int B = 0, Tx_max = 0, S = 0, dropout = 0;
+    char *ws = nullptr;           // everything the stream owns on the device, one allocation
+    size_t ws_bytes = 0;
+    int32_t *host_i = nullptr;    // pinned, (B, ST_INTS): the state's integers after a push
+    int32_t *ids = nullptr, *tx = nullptr, *st_i = nullptr, *max_attentions = nullptr, *steps = nullptr, *mel_frames = nullptr;
+    uint64_t *seeds = nullptr;
+    float *mem = nullptr, *keys = nullptr, *st_f = nullptr, *decoder = nullptr, *residual = nullptr, *mel_raw = nullptr, *mel = nullptr;
+    float *alignments = nullptr, *stop = nullptr;
+    std::vector<float *> post;    // the postnet layers' activations, (B, S r, postnet_channels) each
+    int st_stride = 0, Pmax = 0, Kmax = 0;
+    size_t dec_lds = 0;
+    bool done = false;            // every utterance has finished
     std::string err;
 };
 
@@ -641,10 +771,97 @@ int launch_conv(wrnn_taco_handle *h, hipStream_t s, const float *in, const float
     a.in = in; a.w = w; a.bias = bias; a.bn_s = bn; a.bn_b = bn ? bn + C_bn_stride : nullptr; a.out = out; a.len = len; a.len_mul = len_mul;
     a.T_max = T_max; a.Cin = Cin; a.Cout = Cout; a.taps = taps; a.act = act;
     const size_t lds = (size_t)(CONV_TT + taps - 1) * Cin * sizeof(float);
-    hipLaunchKernelGGL(taco_conv_kernel, dim3((unsigned)((T_max + CONV_TT - 1) / CONV_TT), (unsigned)B, (unsigned)((Cout + 63) / 64)),
-                       dim3(CONV_THREADS), lds, s, a);
+    hipLaunchKernelGGL(taco_conv_kernel<false>, dim3((unsigned)((T_max + CONV_TT - 1) / CONV_TT), (unsigned)B, (unsigned)((Cout + 63) / 64)),
+                       dim3(CONV_THREADS), lds, s, a, ConvWindow{});
     WRNN_TRY(h, hipGetLastError());
     return WRNN_OK;
+}
+
+// The host-side checks of a call's text, shared by the offline call and a stream's open (the offline call checks its output pointers
+// and max_iters between the two).
+int check_text(wrnn_taco_handle *h, int B, int Tx_max, const int32_t *ids_host, const int32_t *tx_host, const uint64_t *seeds_host) {
+    if (B < 1 || B > WRNN_MAX_GRID_Y) return wrnn_failf(h, WRNN_ERR_INVALID, "B %d outside 1 .. 65535", B);
+    if (Tx_max < 1 || Tx_max > WRNN_TACO_MAX_TX) return wrnn_failf(h, WRNN_ERR_INVALID, "Tx_max %d outside 1 .. %d symbols", Tx_max, WRNN_TACO_MAX_TX);
+    if (!ids_host || !tx_host || !seeds_host) return wrnn_failf(h, WRNN_ERR_INVALID, "ids_host, tx_host or seeds_host is NULL");
+    return WRNN_OK;
+}
+int check_symbols(wrnn_taco_handle *h, int B, int Tx_max, const int32_t *ids_host, const int32_t *tx_host) {
+    for (int b = 0; b < B; ++b) {
+        const int tx = tx_host[b];
+        if (tx < 1 || tx > Tx_max) return wrnn_failf(h, WRNN_ERR_INVALID, "utterance %d: %d symbols outside 1 .. Tx_max = %d (the limit is %d)", b, tx, Tx_max, WRNN_TACO_MAX_TX);
+        for (int t = 0; t < tx; ++t) {
+            const int id = ids_host[(size_t)b * Tx_max + t];
+            if (id < 0 || id >= h->d.n_symbols) return wrnn_failf(h, WRNN_ERR_INVALID, "utterance %d: symbol id %d at %d is outside the table of %d", b, id, t, h->d.n_symbols);
+        }
+    }
+    return WRNN_OK;
+}
+
+const float *tensor_at(const wrnn_taco_handle *h, const std::string &n) { return h->img + find(h, n)->off; }
+
+// ids, tx -> memory and keys.  a0, a1: B Tx_max max(enc_conv_channels, embedding_dim) floats each; xp: B Tx_max 4 H floats each;
+// mem has been zeroed.
+struct EncBufs {
+    const int32_t *ids, *tx;
+    float *a0, *a1, *xp[2], *mem, *keys;
+};
+int run_encoder(wrnn_taco_handle *h, hipStream_t s, const EncBufs &e, int B, int Tx_max) {
+    const wrnn_taco_dims &d = h->d;
+    const int C = d.enc_conv_channels, H = d.encoder_lstm_units, E2 = 2 * H, A = d.attention_dim;
+    const float *img = h->img;
+    EmbedArgs em{e.ids, e.tx, tensor_at(h, "inputs_embedding"), e.a0, Tx_max, d.embedding_dim, d.n_symbols};
+    hipLaunchKernelGGL(taco_embed_kernel, dim3((unsigned)Tx_max, (unsigned)B), dim3(CONV_THREADS), 0, s, em);
+    WRNN_TRY(h, hipGetLastError());
+    float *cur = e.a0, *nxt = e.a1;
+    int rc;
+    for (int i = 0; i < d.enc_conv_layers; ++i) {
+        const std::string p = enc_conv(i + 1);
+        rc = launch_conv(h, s, cur, tensor_at(h, p + "conv1d/kernel"), tensor_at(h, p + "conv1d/bias"), img + h->off_bn_enc + (size_t)i * 2 * up64(C), (int)up64(C), nxt,
+                         e.tx, 1, B, Tx_max, i ? C : d.embedding_dim, C, d.enc_conv_kernel, 1);
+        if (rc != WRNN_OK) return rc;
+        std::swap(cur, nxt);
+    }
+    EncLstmArgs el{};
+    int di = 0;
+    for (const char *dir : {"fw", "bw"}) {
+        rc = launch_conv(h, s, cur, tensor_at(h, enc_lstm(dir) + "kernel"), tensor_at(h, enc_lstm(dir) + "bias"), nullptr, 0, e.xp[di], e.tx, 1, B, Tx_max, C, 4 * H, 1, 0);
+        if (rc != WRNN_OK) return rc;
+        el.xproj[di] = e.xp[di];
+        el.whh[di] = tensor_at(h, enc_lstm(dir) + "kernel") + (size_t)C * 4 * H;
+        ++di;
+    }
+    el.tx = e.tx; el.memory = e.mem; el.Tx_max = Tx_max; el.H = H; el.zoneout = d.zoneout;
+    hipLaunchKernelGGL(taco_enc_lstm_kernel, dim3(2u, (unsigned)B), dim3(LOOP_THREADS), (size_t)(6 * H + 4 * LOOP_THREADS) * sizeof(float), s, el);
+    WRNN_TRY(h, hipGetLastError());
+    return launch_conv(h, s, e.mem, tensor_at(h, "memory_layer/kernel"), nullptr, nullptr, 0, e.keys, e.tx, 1, B, Tx_max, E2, A, 1, 0);
+}
+
+// The decoder's weights and the model's sizes; the caller adds the call's own pointers and counts.
+void decoder_model_args(const wrnn_taco_handle *h, DecArgs &g) {
+    const wrnn_taco_dims &d = h->d;
+    const float *img = h->img;
+    for (int l = 0; l < d.prenet_layers; ++l) {
+        g.prenet_w[l] = tensor_at(h, "decoder/decoder_prenet/dense_" + std::to_string(l + 1) + "/kernel");
+        g.prenet_b[l] = tensor_at(h, "decoder/decoder_prenet/dense_" + std::to_string(l + 1) + "/bias");
+        g.prenet[l] = d.prenet_sizes[l];
+    }
+    for (int l = 0; l < d.decoder_layers; ++l) { g.lstm_w[l] = tensor_at(h, dec_lstm(l) + "kernel"); g.lstm_b[l] = tensor_at(h, dec_lstm(l) + "bias"); }
+    g.query_w = tensor_at(h, std::string(LSA) + "query_layer/kernel");
+    g.loc_m = img + h->off_loc_m; g.att_bias = img + h->off_att_bias; g.att_v = tensor_at(h, std::string(LSA) + "attention_variable_projection");
+    g.mu_w = tensor_at(h, "decoder/dense/kernel"); g.mu_b = tensor_at(h, "decoder/dense/bias");
+    g.proj_w = img + h->off_proj_w; g.proj_b = img + h->off_proj_b;
+    g.E2 = 2 * d.encoder_lstm_units; g.A = d.attention_dim; g.M = d.num_mels; g.r = d.outputs_per_step; g.D = d.decoder_lstm_units; g.L = d.decoder_layers;
+    g.n_prenet = d.prenet_layers; g.taps = d.attention_kernel;
+    g.zoneout = d.zoneout; g.clip_lo = -d.max_abs_value - d.lower_bound_decay; g.clip_hi = d.max_abs_value;
+}
+
+// Rows a mel frame waits for: what the postnet's convolutions reach to the right ('same' padding puts (k - 1) / 2 taps on the left).
+int postnet_reach(const wrnn_taco_dims &d) { return (d.postnet_kernel - 1) - (d.postnet_kernel - 1) / 2; }
+
+void free_stream(wrnn_taco_stream *st) {
+    if (st->ws) (void)hipFree(st->ws);
+    if (st->host_i) (void)hipHostFree(st->host_i);
+    delete st;
 }
 }  // namespace
 
@@ -706,7 +923,9 @@ int wrnn_taco_tensor_shape(const wrnn_taco_handle *h, int index, int64_t *shape_
 int wrnn_taco_load_tensor(wrnn_taco_handle *h, const char *name, const float *data_host, int ndim, const int64_t *shape) {
     if (!h) return WRNN_ERR_INVALID;
     if (!h->ok) return wrnn_failf(h, WRNN_ERR_INVALID, "the handle was refused at creation");
+    if (h->destroyed) return wrnn_failf(h, WRNN_ERR_STATE, "the handle was destroyed: it lives only until its last stream is closed");
     if (!name || !data_host || !shape || ndim < 1 || ndim > 3) return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_taco_load_tensor: a NULL argument or a rank outside 1 .. 3");
+    if (h->open_streams > 0) return wrnn_failf(h, WRNN_ERR_STATE, "%d open streams read the weights: close them before loading a tensor", h->open_streams);
     for (Tensor &t : h->tensors) {
         if (t.name != name) continue;
         bool same = (int)t.shape.size() == ndim;
@@ -725,25 +944,18 @@ int wrnn_taco_load_tensor(wrnn_taco_handle *h, const char *name, const float *da
 int wrnn_taco_synthesize(wrnn_taco_handle *h, const wrnn_taco_call *c, void *stream) {
     if (!h) return WRNN_ERR_INVALID;
     if (!h->ok) return wrnn_failf(h, WRNN_ERR_INVALID, "the handle was refused at creation");
+    if (h->destroyed) return wrnn_failf(h, WRNN_ERR_STATE, "the handle was destroyed: it lives only until its last stream is closed");
     if (!c) return wrnn_failf(h, WRNN_ERR_INVALID, "call is NULL");
     if (c->struct_size != sizeof(wrnn_taco_call))
         return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_taco_call.struct_size %u, this library's is %zu", c->struct_size, sizeof(wrnn_taco_call));
     const wrnn_taco_dims &d = h->d;
     const int B = c->B, Tx_max = c->Tx_max, r = d.outputs_per_step, M = d.num_mels;
-    if (B < 1 || B > WRNN_MAX_GRID_Y) return wrnn_failf(h, WRNN_ERR_INVALID, "B %d outside 1 .. 65535", B);
-    if (Tx_max < 1 || Tx_max > WRNN_TACO_MAX_TX) return wrnn_failf(h, WRNN_ERR_INVALID, "Tx_max %d outside 1 .. %d symbols", Tx_max, WRNN_TACO_MAX_TX);
-    if (!c->ids_host || !c->tx_host || !c->seeds_host) return wrnn_failf(h, WRNN_ERR_INVALID, "ids_host, tx_host or seeds_host is NULL");
+    int rc = check_text(h, B, Tx_max, c->ids_host, c->tx_host, c->seeds_host);
+    if (rc != WRNN_OK) return rc;
     if (!c->decoder_dev || !c->mel_raw_dev || !c->mel_dev || !c->alignments_dev || !c->stop_dev || !c->max_attentions_dev || !c->steps_dev || !c->mel_frames_dev)
         return wrnn_failf(h, WRNN_ERR_INVALID, "an output pointer is NULL");
     if (c->max_iters < 1) return wrnn_failf(h, WRNN_ERR_INVALID, "max_iters %d < 1", c->max_iters);
-    for (int b = 0; b < B; ++b) {
-        const int tx = c->tx_host[b];
-        if (tx < 1 || tx > Tx_max) return wrnn_failf(h, WRNN_ERR_INVALID, "utterance %d: %d symbols outside 1 .. Tx_max = %d (the limit is %d)", b, tx, Tx_max, WRNN_TACO_MAX_TX);
-        for (int t = 0; t < tx; ++t) {
-            const int id = c->ids_host[(size_t)b * Tx_max + t];
-            if (id < 0 || id >= d.n_symbols) return wrnn_failf(h, WRNN_ERR_INVALID, "utterance %d: symbol id %d at %d is outside the table of %d", b, id, t, d.n_symbols);
-        }
-    }
+    if ((rc = check_symbols(h, B, Tx_max, c->ids_host, c->tx_host)) != WRNN_OK) return rc;
     const bool gta = c->gta_dev != nullptr;
     int need_steps = c->max_iters;
     std::vector<int32_t> gsteps(B, 0);
@@ -764,10 +976,7 @@ int wrnn_taco_synthesize(wrnn_taco_handle *h, const wrnn_taco_call *c, void *str
     if (dec_lds > LDS_LIMIT) return wrnn_failf(h, WRNN_ERR_INVALID, "the decoder's state for Tx_max %d exceeds 64 KiB of LDS", Tx_max);
     WRNN_TRY(h, hipSetDevice(d.device));
     hipStream_t s = (hipStream_t)stream;
-    if (h->dirty) {
-        const int rc = upload(h);
-        if (rc != WRNN_OK) return rc;
-    }
+    if (h->dirty && (rc = upload(h)) != WRNN_OK) return rc;
     // the scratch: ids, tx, gta steps, seeds; two ping-pong activations; the LSTM input projections; memory; keys
     const int C = d.enc_conv_channels, H = d.encoder_lstm_units, E2 = 2 * H, A = d.attention_dim, PC = d.postnet_channels, T_out = S * r;
     const size_t act_floats = std::max((size_t)B * Tx_max * std::max(C, d.embedding_dim), (size_t)B * T_out * std::max(PC, M));
@@ -796,56 +1005,22 @@ int wrnn_taco_synthesize(wrnn_taco_handle *h, const wrnn_taco_call *c, void *str
     const float *img = h->img;
     auto T = [&](const std::string &n) { return img + find(h, n)->off; };
     // ---- encoder
-    EmbedArgs e{ids, tx, T("inputs_embedding"), a0, Tx_max, d.embedding_dim, d.n_symbols};
-    hipLaunchKernelGGL(taco_embed_kernel, dim3((unsigned)Tx_max, (unsigned)B), dim3(CONV_THREADS), 0, s, e);
-    WRNN_TRY(h, hipGetLastError());
-    float *cur = a0, *nxt = a1;
-    int rc;
-    for (int i = 0; i < d.enc_conv_layers; ++i) {
-        const std::string p = enc_conv(i + 1);
-        rc = launch_conv(h, s, cur, T(p + "conv1d/kernel"), T(p + "conv1d/bias"), img + h->off_bn_enc + (size_t)i * 2 * up64(C), (int)up64(C), nxt, tx, 1, B, Tx_max,
-                         i ? C : d.embedding_dim, C, d.enc_conv_kernel, 1);
-        if (rc != WRNN_OK) return rc;
-        std::swap(cur, nxt);
-    }
-    EncLstmArgs el{};
-    int di = 0;
-    for (const char *dir : {"fw", "bw"}) {
-        rc = launch_conv(h, s, cur, T(enc_lstm(dir) + "kernel"), T(enc_lstm(dir) + "bias"), nullptr, 0, xp[di], tx, 1, B, Tx_max, C, 4 * H, 1, 0);
-        if (rc != WRNN_OK) return rc;
-        el.xproj[di] = xp[di];
-        el.whh[di] = T(enc_lstm(dir) + "kernel") + (size_t)C * 4 * H;
-        ++di;
-    }
-    el.tx = tx; el.memory = mem; el.Tx_max = Tx_max; el.H = H; el.zoneout = d.zoneout;
-    hipLaunchKernelGGL(taco_enc_lstm_kernel, dim3(2u, (unsigned)B), dim3(LOOP_THREADS), (size_t)(6 * H + 4 * LOOP_THREADS) * sizeof(float), s, el);
-    WRNN_TRY(h, hipGetLastError());
+    const EncBufs eb{ids, tx, a0, a1, {xp[0], xp[1]}, mem, keys};
+    if ((rc = run_encoder(h, s, eb, B, Tx_max)) != WRNN_OK) return rc;
     if (c->encoder_dev) WRNN_TRY(h, hipMemcpyAsync(c->encoder_dev, mem, (size_t)B * Tx_max * E2 * 4, hipMemcpyDeviceToDevice, s));
-    rc = launch_conv(h, s, mem, T("memory_layer/kernel"), nullptr, nullptr, 0, keys, tx, 1, B, Tx_max, E2, A, 1, 0);
-    if (rc != WRNN_OK) return rc;
     // ---- decoder
     DecArgs g{};
     g.memory = mem; g.keys = keys; g.tx = tx; g.seeds = seeds; g.gta = c->gta_dev; g.gta_steps = gs;
-    for (int l = 0; l < d.prenet_layers; ++l) {
-        g.prenet_w[l] = T("decoder/decoder_prenet/dense_" + std::to_string(l + 1) + "/kernel");
-        g.prenet_b[l] = T("decoder/decoder_prenet/dense_" + std::to_string(l + 1) + "/bias");
-        g.prenet[l] = d.prenet_sizes[l];
-    }
-    for (int l = 0; l < d.decoder_layers; ++l) { g.lstm_w[l] = T(dec_lstm(l) + "kernel"); g.lstm_b[l] = T(dec_lstm(l) + "bias"); }
-    g.query_w = T(std::string(LSA) + "query_layer/kernel");
-    g.loc_m = img + h->off_loc_m; g.att_bias = img + h->off_att_bias; g.att_v = T(std::string(LSA) + "attention_variable_projection");
-    g.mu_w = T("decoder/dense/kernel"); g.mu_b = T("decoder/dense/bias");
-    g.proj_w = img + h->off_proj_w; g.proj_b = img + h->off_proj_b;
+    decoder_model_args(h, g);
     g.decoder = c->decoder_dev; g.alignments = c->alignments_dev; g.stop = c->stop_dev;
     g.max_attentions = c->max_attentions_dev; g.steps = c->steps_dev; g.mel_frames = c->mel_frames_dev;
-    g.Tx_max = Tx_max; g.E2 = E2; g.A = A; g.M = M; g.r = r; g.D = d.decoder_lstm_units; g.L = d.decoder_layers; g.n_prenet = d.prenet_layers;
-    g.taps = d.attention_kernel; g.gta_max = gta ? c->gta_max : 0; g.max_iters = c->max_iters; g.steps_max = S; g.dropout = c->prenet_dropout ? 1 : 0;
-    g.Pmax = Pmax; g.Kmax = Kmax; g.zoneout = d.zoneout; g.clip_lo = -d.max_abs_value - d.lower_bound_decay; g.clip_hi = d.max_abs_value;
-    hipLaunchKernelGGL(taco_decoder_kernel, dim3((unsigned)B), dim3(LOOP_THREADS), dec_lds, s, g);
+    g.Tx_max = Tx_max; g.gta_max = gta ? c->gta_max : 0; g.max_iters = c->max_iters; g.steps_max = S; g.dropout = c->prenet_dropout ? 1 : 0;
+    g.Pmax = Pmax; g.Kmax = Kmax;
+    hipLaunchKernelGGL(taco_decoder_kernel<false>, dim3((unsigned)B), dim3(LOOP_THREADS), dec_lds, s, g, DecState{});
     WRNN_TRY(h, hipGetLastError());
     // ---- postnet over steps r rows per utterance, the count read from the device
     const float *pin = c->decoder_dev;
-    cur = a0; nxt = a1;
+    float *cur = a0, *nxt = a1;
     for (int i = 0; i < d.postnet_layers; ++i) {
         const std::string p = post_conv(i + 1);
         rc = launch_conv(h, s, pin, T(p + "conv1d/kernel"), T(p + "conv1d/bias"), img + h->off_bn_post + (size_t)i * 2 * up64(PC), (int)up64(PC), cur, c->steps_dev, r, B,
@@ -864,8 +1039,177 @@ int wrnn_taco_synthesize(wrnn_taco_handle *h, const wrnn_taco_call *c, void *str
 
 const char *wrnn_taco_last_error(const wrnn_taco_handle *h) { return wrnn_last_error_of(h); }
 
+int wrnn_taco_stream_halo(const wrnn_taco_dims *dims) {
+    if (!dims || dims->postnet_layers < 0 || dims->postnet_kernel < 1) return WRNN_ERR_INVALID;
+    return dims->postnet_layers * postnet_reach(*dims);
+}
+
+int wrnn_taco_stream_open(wrnn_taco_handle *h, const wrnn_taco_stream_opts *o, void *stream, wrnn_taco_stream **out) {
+    if (out) *out = nullptr;
+    if (!h) return WRNN_ERR_INVALID;
+    if (!h->ok) return wrnn_failf(h, WRNN_ERR_INVALID, "the handle was refused at creation");
+    if (h->destroyed) return wrnn_failf(h, WRNN_ERR_STATE, "the handle was destroyed: it lives only until its last stream is closed");
+    if (!o || !out) return wrnn_failf(h, WRNN_ERR_INVALID, "opts or out is NULL");
+    if (o->struct_size != sizeof(wrnn_taco_stream_opts))
+        return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_taco_stream_opts.struct_size %u, this library's is %zu", o->struct_size, sizeof(wrnn_taco_stream_opts));
+    if (o->gta_dev) return wrnn_failf(h, WRNN_ERR_INVALID, "a stream is free-running: teacher forcing has the whole target in hand, use wrnn_taco_synthesize");
+    const wrnn_taco_dims &d = h->d;
+    const int B = o->B, Tx_max = o->Tx_max, r = d.outputs_per_step, M = d.num_mels, S = o->max_iters;
+    int rc = check_text(h, B, Tx_max, o->ids_host, o->tx_host, o->seeds_host);
+    if (rc != WRNN_OK) return rc;
+    if (S < 1) return wrnn_failf(h, WRNN_ERR_INVALID, "max_iters %d < 1", S);
+    if ((rc = check_symbols(h, B, Tx_max, o->ids_host, o->tx_host)) != WRNN_OK) return rc;
+    if ((int64_t)S * r > (1 << 24)) return wrnn_failf(h, WRNN_ERR_INVALID, "max_iters %d: above 2^24 / r", S);
+    int Pmax = 0, Kmax = 0;
+    const size_t dec_lds = decoder_lds_floats(d, Tx_max, &Pmax, &Kmax) * sizeof(float);
+    if (dec_lds > LDS_LIMIT) return wrnn_failf(h, WRNN_ERR_INVALID, "the decoder's state for Tx_max %d exceeds 64 KiB of LDS", Tx_max);
+    WRNN_TRY(h, hipSetDevice(d.device));
+    hipStream_t s = (hipStream_t)stream;
+    if (h->dirty && (rc = upload(h)) != WRNN_OK) return rc;
+    const int C = d.enc_conv_channels, H = d.encoder_lstm_units, E2 = 2 * H, A = d.attention_dim, PC = d.postnet_channels, T_out = S * r, LD = d.decoder_layers * d.decoder_lstm_units;
+    const size_t enc_act = (size_t)B * Tx_max * std::max(C, d.embedding_dim), frames = (size_t)B * T_out * M;
+    const int st_stride = (int)up64((size_t)M + 2 * (size_t)LD + E2 + 2 * (size_t)Tx_max + 1);
+    size_t at = 0;
+    auto take = [&at](size_t bytes) { const size_t off = at; at += wrnn_up256(bytes); return off; };
+    const size_t o_ids = take((size_t)B * Tx_max * 4), o_tx = take((size_t)B * 4), o_seed = take((size_t)B * 8);
+    const size_t o_a0 = take(enc_act * 4), o_a1 = take(enc_act * 4), o_xp0 = take((size_t)B * Tx_max * 4 * H * 4), o_xp1 = take((size_t)B * Tx_max * 4 * H * 4);
+    const size_t o_mem = take((size_t)B * Tx_max * E2 * 4), o_keys = take((size_t)B * Tx_max * A * 4);
+    const size_t o_sf = take((size_t)B * st_stride * 4), o_si = take((size_t)B * ST_INTS * 4);
+    const size_t o_dec = take(frames * 4), o_res = take(frames * 4), o_raw = take(frames * 4), o_mel = take(frames * 4);
+    const size_t o_ali = take((size_t)B * S * Tx_max * 4), o_stop = take((size_t)B * T_out * 4), o_ma = take((size_t)B * S * 4);
+    const size_t o_steps = take((size_t)B * 4), o_mf = take((size_t)B * 4);
+    std::vector<size_t> o_post;
+    for (int i = 0; i < d.postnet_layers; ++i) o_post.push_back(take((size_t)B * T_out * PC * 4));
+    wrnn_taco_stream *st = new wrnn_taco_stream();
+    auto fail = [&](int code) { free_stream(st); return code; };
+    hipError_t e = hipMalloc((void **)&st->ws, at);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&st->host_i, (size_t)B * ST_INTS * 4, hipHostMallocDefault);
+    if (e != hipSuccess) return fail(wrnn_failf(h, WRNN_ERR_HIP, "a stream's workspace of %zu bytes: %s", at, hipGetErrorString(e)));
+    char *ws = st->ws;
+    st->h = h; st->B = B; st->Tx_max = Tx_max; st->S = S; st->dropout = o->prenet_dropout ? 1 : 0; st->ws_bytes = at;
+    st->ids = (int32_t *)(ws + o_ids); st->tx = (int32_t *)(ws + o_tx); st->seeds = (uint64_t *)(ws + o_seed);
+    st->mem = (float *)(ws + o_mem); st->keys = (float *)(ws + o_keys); st->st_f = (float *)(ws + o_sf); st->st_i = (int32_t *)(ws + o_si);
+    st->decoder = (float *)(ws + o_dec); st->residual = (float *)(ws + o_res); st->mel_raw = (float *)(ws + o_raw); st->mel = (float *)(ws + o_mel);
+    st->alignments = (float *)(ws + o_ali); st->stop = (float *)(ws + o_stop); st->max_attentions = (int32_t *)(ws + o_ma);
+    st->steps = (int32_t *)(ws + o_steps); st->mel_frames = (int32_t *)(ws + o_mf);
+    for (size_t off : o_post) st->post.push_back((float *)(ws + off));
+    st->st_stride = st_stride; st->Pmax = Pmax; st->Kmax = Kmax; st->dec_lds = dec_lds;
+    // everything starts as zeros: the outputs past an utterance's end stay so, and step 0 of the state means "not begun"
+    if ((e = hipMemsetAsync(ws, 0, at, s)) == hipSuccess) e = hipMemcpyAsync(st->ids, o->ids_host, (size_t)B * Tx_max * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(st->tx, o->tx_host, (size_t)B * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(st->seeds, o->seeds_host, (size_t)B * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);   // the caller's arrays may leave scope
+    if (e != hipSuccess) return fail(wrnn_failf(h, WRNN_ERR_HIP, "a stream's inputs: %s", hipGetErrorString(e)));
+    const EncBufs eb{st->ids, st->tx, (float *)(ws + o_a0), (float *)(ws + o_a1), {(float *)(ws + o_xp0), (float *)(ws + o_xp1)}, st->mem, st->keys};
+    if ((rc = run_encoder(h, s, eb, B, Tx_max)) != WRNN_OK) return fail(rc);
+    ++h->open_streams;
+    *out = st;
+    return WRNN_OK;
+}
+
+int wrnn_taco_stream_step(wrnn_taco_stream *st, int32_t n_steps, void *stream, int32_t *decoded_host, int32_t *final_host, int32_t *finished_host) {
+    if (!st) return WRNN_ERR_INVALID;
+    if (n_steps < 1) return wrnn_failf(st, WRNN_ERR_INVALID, "n_steps %d < 1", n_steps);
+    if (!decoded_host || !final_host || !finished_host) return wrnn_failf(st, WRNN_ERR_INVALID, "decoded_host, final_host or finished_host is NULL");
+    if (st->done) return wrnn_failf(st, WRNN_ERR_STATE, "every utterance of the stream has finished");
+    wrnn_taco_handle *h = st->h;
+    const wrnn_taco_dims &d = h->d;
+    const int B = st->B, S = st->S, r = d.outputs_per_step, M = d.num_mels, PC = d.postnet_channels, T_out = S * r;
+    const int n = std::min(n_steps, S), reach = postnet_reach(d), halo = d.postnet_layers * reach;
+    WRNN_TRY(st, hipSetDevice(d.device));
+    hipStream_t s = (hipStream_t)stream;
+    DecArgs g{};
+    g.memory = st->mem; g.keys = st->keys; g.tx = st->tx; g.seeds = st->seeds;
+    decoder_model_args(h, g);
+    g.decoder = st->decoder; g.alignments = st->alignments; g.stop = st->stop;
+    g.max_attentions = st->max_attentions; g.steps = st->steps; g.mel_frames = st->mel_frames;
+    g.Tx_max = st->Tx_max; g.max_iters = S; g.steps_max = S; g.dropout = st->dropout; g.Pmax = st->Pmax; g.Kmax = st->Kmax;
+    const DecState ds{st->st_f, st->st_i, st->st_stride, n};
+    hipLaunchKernelGGL(taco_decoder_kernel<true>, dim3((unsigned)B), dim3(LOOP_THREADS), st->dec_lds, s, g, ds);
+    WRNN_TRY(st, hipGetLastError());
+    // layer i (1-based) is held i reach rows behind the decoder while the utterance runs; a push adds n r rows at most, and the rows held
+    // back when it ends; one tile more, since the tiles are aligned and the range need not be
+    const float *img = h->img, *pin = st->decoder;
+    for (int i = 0; i <= d.postnet_layers; ++i) {
+        const bool proj = i == d.postnet_layers;
+        const std::string p = post_conv(i + 1);
+        ConvArgs a{};
+        a.in = pin;
+        a.w = tensor_at(h, proj ? std::string(POSTP) + "kernel" : p + "conv1d/kernel");
+        a.bias = tensor_at(h, proj ? std::string(POSTP) + "bias" : p + "conv1d/bias");
+        a.bn_s = proj ? nullptr : img + h->off_bn_post + (size_t)i * 2 * up64(PC);
+        a.bn_b = proj ? nullptr : a.bn_s + up64(PC);
+        a.out = proj ? st->residual : st->post[i];
+        a.len_mul = r; a.T_max = T_out; a.Cin = i ? PC : M; a.Cout = proj ? M : PC; a.taps = proj ? 1 : d.postnet_kernel;
+        a.act = i + 1 < d.postnet_layers ? 2 : 0;
+        const ConvWindow cw{st->st_i, std::min(i + 1, (int)d.postnet_layers) * reach};
+        const long rows = std::min((long)n * r + cw.held, (long)T_out);
+        hipLaunchKernelGGL(taco_conv_kernel<true>, dim3((unsigned)((rows + CONV_TT - 1) / CONV_TT + 1), (unsigned)B, (unsigned)((a.Cout + 63) / 64)), dim3(CONV_THREADS),
+                           (size_t)(CONV_TT + a.taps - 1) * a.Cin * sizeof(float), s, a, cw);
+        WRNN_TRY(st, hipGetLastError());
+        pin = a.out;
+    }
+    FinishArgs f{st->decoder, st->residual, st->steps, st->mel_raw, st->mel, T_out, M, r, g.clip_lo, g.clip_hi};
+    const long frows = std::min((long)n * r + halo, (long)T_out);
+    hipLaunchKernelGGL(taco_finish_window_kernel, dim3((unsigned)((frows * M + CONV_THREADS - 1) / CONV_THREADS), (unsigned)B), dim3(CONV_THREADS), 0, s, f, st->st_i, halo);
+    WRNN_TRY(st, hipGetLastError());
+    WRNN_TRY(st, hipMemcpyAsync(st->host_i, st->st_i, (size_t)B * ST_INTS * 4, hipMemcpyDeviceToHost, s));
+    WRNN_TRY(st, hipStreamSynchronize(s));   // the one wait of a push
+    bool done = true;
+    for (int b = 0; b < B; ++b) {
+        const int32_t *si = st->host_i + (size_t)b * ST_INTS;
+        const int frames = si[ST_STEP] * r, fin = si[ST_FINISHED];
+        decoded_host[b] = frames;
+        finished_host[b] = fin;
+        final_host[b] = fin ? (si[ST_FIRST_STOP] >= 0 ? si[ST_FIRST_STOP] : frames) : std::max(frames - halo, 0);
+        done = done && fin;
+    }
+    st->done = done;
+    return WRNN_OK;
+}
+
+int wrnn_taco_stream_view(const wrnn_taco_stream *st, wrnn_taco_stream_outputs *v) {
+    if (!st || !v) return WRNN_ERR_INVALID;
+    if (v->struct_size != sizeof(wrnn_taco_stream_outputs)) return WRNN_ERR_INVALID;
+    const wrnn_taco_dims &d = st->h->d;
+    const int64_t T_out = (int64_t)st->S * d.outputs_per_step;
+    v->encoder_dev = st->mem; v->decoder_dev = st->decoder; v->mel_raw_dev = st->mel_raw; v->mel_dev = st->mel;
+    v->alignments_dev = st->alignments; v->stop_dev = st->stop; v->max_attentions_dev = st->max_attentions;
+    v->steps_dev = st->steps; v->mel_frames_dev = st->mel_frames;
+    v->encoder_stride = (int64_t)st->Tx_max * 2 * d.encoder_lstm_units;
+    v->frames_stride = T_out * d.num_mels;
+    v->alignments_stride = (int64_t)st->S * st->Tx_max;
+    v->stop_stride = T_out;
+    v->max_attentions_stride = st->S;
+    return WRNN_OK;
+}
+
+int wrnn_taco_stream_info(const wrnn_taco_stream *st, int32_t *B, int32_t *Tx_max, int32_t *max_iters, int32_t *halo, int64_t *workspace_bytes) {
+    if (!st) return WRNN_ERR_INVALID;
+    if (B) *B = st->B;
+    if (Tx_max) *Tx_max = st->Tx_max;
+    if (max_iters) *max_iters = st->S;
+    if (halo) *halo = wrnn_taco_stream_halo(&st->h->d);
+    if (workspace_bytes) *workspace_bytes = (int64_t)st->ws_bytes;
+    return WRNN_OK;
+}
+
+const char *wrnn_taco_stream_last_error(const wrnn_taco_stream *st) { return wrnn_last_error_of(st); }
+
+void wrnn_taco_stream_close(wrnn_taco_stream *st) {
+    if (!st) return;
+    wrnn_taco_handle *h = st->h;
+    (void)hipSetDevice(h->d.device);
+    free_stream(st);   // hipFree waits for the work that still uses the allocation (the encoder of an open that was never stepped)
+    if (--h->open_streams == 0 && h->destroyed) wrnn_taco_destroy(h);
+}
+
 void wrnn_taco_destroy(wrnn_taco_handle *h) {
     if (!h) return;
+    if (h->open_streams > 0) {   // its streams read the weight image: the last wrnn_taco_stream_close frees the handle
+        h->destroyed = true;
+        return;
+    }
     if (h->img || h->ws.p) {
         (void)hipSetDevice(h->d.device);
         if (h->img) (void)hipFree(h->img);

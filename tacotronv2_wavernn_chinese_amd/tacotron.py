@@ -64,6 +64,151 @@ def make_dims(device: int = 0, **dims) -> _cabi.TacoDims:
     return t
 
 
+def pack_text(sequences, seeds):
+    """A ragged list of id lists -> ids (B, Tx_max) int32 padded with 0, tx (B) int32, seeds (B) uint64 (default 0, 1, ...)."""
+    seqs = [np.asarray(s, dtype=np.int64).reshape(-1) for s in sequences]
+    B = len(seqs)
+    if B < 1:
+        raise _cabi.WrnnError(_cabi.ERR_INVALID, 'no utterances')
+    tx = np.array([len(s) for s in seqs], dtype=np.int32)
+    Tx_max = int(tx.max()) if tx.size else 0
+    ids = np.zeros((B, Tx_max), dtype=np.int32)
+    for b, s in enumerate(seqs):
+        if s.size and (s.min() < -2 ** 31 or s.max() >= 2 ** 31):
+            raise _cabi.WrnnError(_cabi.ERR_INVALID, f'utterance {b}: a symbol id does not fit 32 bits')
+        ids[b, :len(s)] = s
+    seeds_a = np.array(list(range(B)) if seeds is None else [int(x) & (2 ** 64 - 1) for x in seeds], dtype=np.uint64)
+    if seeds_a.shape != (B,):
+        raise _cabi.WrnnError(_cabi.ERR_INVALID, f'{seeds_a.size} seeds for {B} utterances')
+    return ids, tx, seeds_a
+
+
+def stream_halo(postnet_layers: int, postnet_kernel: int) -> int:
+    """Decoder frames a mel frame waits for: each postnet layer reaches ``(k - 1) - (k - 1) // 2`` rows to the right ('same' padding
+    puts ``(k - 1) // 2`` of a kernel's taps on the left); the 1-tap projection adds nothing."""
+    k = int(postnet_kernel)
+    return int(postnet_layers) * ((k - 1) - (k - 1) // 2)
+
+
+def stream_release(decoded_frames: int, finished: bool, mel_length: int, postnet_layers: int, postnet_kernel: int) -> int:
+    """Leading mel frames of a stream that are final: ``decoded_frames - halo`` (floored at 0) while the utterance is running, all
+    ``mel_length`` of them once it has finished (a stop token above 0.5, or ``max_iters`` steps).  ``wrnn_taco_stream_step`` reports
+    the same number."""
+    if finished:
+        return int(mel_length)
+    return max(int(decoded_frames) - stream_halo(postnet_layers, postnet_kernel), 0)
+
+
+class _DeviceArray:
+    """A device buffer the library owns, for ``torch.as_tensor`` (no copy)."""
+
+    def __init__(self, ptr: int, shape, typestr: str):
+        self.__cuda_array_interface__ = dict(shape=tuple(int(n) for n in shape), typestr=typestr, data=(int(ptr), False), version=2, strides=None)
+
+
+class TacotronStream:
+    """``Tacotron.stream(...)``: a free-running ``synthesize`` cut into pushes of decoder steps.  ``step(n)`` runs up to ``n`` more
+    steps of every unfinished utterance and returns, per utterance, what became final: ``mel`` and ``mel_raw`` rows by the release
+    rule (:func:`stream_release`), ``decoder_output``, ``stop_tokens``, ``alignments`` and ``max_attentions`` of the steps just run.
+    The pieces of an utterance, concatenated over any partition into pushes, are ``synthesize``'s arrays bit for bit.  With
+    ``return_device=True`` the pieces are views of the stream's own buffers, valid until ``close()``; ``result()`` returns copies."""
+
+    def __init__(self, model: 'Tacotron', sequences, seeds, max_iters: int, prenet_dropout: bool, return_device: bool, gta_targets=None):
+        import torch
+        self._ns = None
+        ids, tx, seeds_a = pack_text(sequences, seeds)
+        self.model, self.return_device = model, bool(return_device)
+        self.B, self.Tx_max, self.S = ids.shape[0], ids.shape[1], int(max_iters)
+        self._tx = [int(t) for t in tx]
+        self._dev = torch.device('cuda', model.device)
+        o = _cabi.TacoStreamOpts()
+        o.struct_size = C.sizeof(_cabi.TacoStreamOpts)
+        o.B, o.Tx_max, o.max_iters, o.prenet_dropout = self.B, self.Tx_max, self.S, int(bool(prenet_dropout))
+        o.ids_host, o.tx_host, o.seeds_host = ids.ctypes.data, tx.ctypes.data, seeds_a.ctypes.data
+        if gta_targets is not None:
+            o.gta_dev = ids.ctypes.data   # any address: the library refuses a target before it looks at it
+        with torch.cuda.device(self._dev):
+            self._ns = model.native.stream_open(o, torch.cuda.current_stream(self._dev).cuda_stream)
+            v = self._ns.view()
+            r, M, S, Tx, E2 = model.r, model.num_mels, self.S, self.Tx_max, 2 * int(model.dims['encoder_lstm_units'])
+            view = lambda ptr, shape, t='<f4': torch.as_tensor(_DeviceArray(ptr, shape, t), device=self._dev)
+            self._buf = dict(encoder_outputs=view(v.encoder_dev, (self.B, Tx, E2)), decoder_output=view(v.decoder_dev, (self.B, S * r, M)),
+                             mel_raw=view(v.mel_raw_dev, (self.B, S * r, M)), mel=view(v.mel_dev, (self.B, S * r, M)),
+                             alignments=view(v.alignments_dev, (self.B, S, Tx)), stop_tokens=view(v.stop_dev, (self.B, S * r)),
+                             max_attentions=view(v.max_attentions_dev, (self.B, S), '<i4'))
+        self.decoded = [0] * self.B        # decoder frames so far
+        self.final = [0] * self.B          # mel frames released so far
+        self.final_raw = [0] * self.B      # mel_raw rows released so far: the stopping step's rows too
+        self.finished = [False] * self.B
+
+    @property
+    def done(self) -> bool:
+        return all(self.finished)
+
+    def info(self) -> dict:
+        return self._live().info()
+
+    def _live(self):
+        if self._ns is None:
+            raise _cabi.WrnnError(_cabi.ERR_STATE, 'the stream is closed')
+        return self._ns
+
+    def _out(self, t):
+        return t if self.return_device else t.cpu().numpy()
+
+    def step(self, n: int):
+        import torch
+        ns = self._live()
+        with torch.cuda.device(self._dev):
+            dec, fin, done = ns.step(int(n), torch.cuda.current_stream(self._dev).cuda_stream)
+        r, halo, out, buf = self.model.r, self.model.halo, [], self._buf
+        for b in range(self.B):
+            d0, f0, w0 = self.decoded[b], self.final[b], self.final_raw[b]
+            d1, f1 = dec[b], fin[b]
+            w1 = d1 if done[b] else max(d1 - halo, 0)
+            res = {'mel': buf['mel'][b, f0:f1], 'mel_raw': buf['mel_raw'][b, w0:w1], 'decoder_output': buf['decoder_output'][b, d0:d1],
+                   'stop_tokens': buf['stop_tokens'][b, d0:d1], 'alignments': buf['alignments'][b, d0 // r:d1 // r, :self._tx[b]],
+                   'max_attentions': buf['max_attentions'][b, d0 // r:d1 // r]}
+            out.append({k: self._out(t) for k, t in res.items()})
+            self.decoded[b], self.final[b], self.final_raw[b], self.finished[b] = d1, f1, w1, done[b]
+        return out
+
+    def result(self):
+        """What ``synthesize`` returns for the same arguments, from the stream's buffers; only once every utterance has finished."""
+        self._live()
+        if not self.done:
+            raise _cabi.WrnnError(_cabi.ERR_STATE, 'result() before every utterance has finished: call step() until .done')
+        r, buf, out = self.model.r, self._buf, []
+        for b in range(self.B):
+            d, f, t = self.decoded[b], self.final[b], self._tx[b]
+            res = {'mel': buf['mel'][b, :f], 'mel_raw': buf['mel_raw'][b, :d], 'decoder_output': buf['decoder_output'][b, :d],
+                   'alignments': buf['alignments'][b, :d // r, :t], 'stop_tokens': buf['stop_tokens'][b, :d],
+                   'max_attentions': buf['max_attentions'][b, :d // r], 'encoder_outputs': buf['encoder_outputs'][b, :t]}
+            res = {k: (v.clone() if self.return_device else v.cpu().numpy()) for k, v in res.items()}
+            res['steps'], res['mel_length'] = d // r, f
+            out.append(res)
+        return out
+
+    def close(self):
+        if self._ns is not None:
+            self._buf = None
+            self._ns.close()
+            self._ns = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Tacotron:
     """``Tacotron(**dims)`` -> ``load(path)`` or ``load_state(dict)`` -> ``synthesize(sequences, ...)``."""
 
@@ -73,6 +218,7 @@ class Tacotron:
         self.device = int(device)
         self.native = _cabi.NativeTacotron(make_dims(device, **dims))
         self.r, self.num_mels = int(self.dims['outputs_per_step']), int(self.dims['num_mels'])
+        self.halo = stream_halo(self.dims['postnet_layers'], self.dims['postnet_kernel'])
 
     def tensor_shapes(self) -> Dict[str, tuple]:
         return self.native.tensor_shapes()
@@ -104,20 +250,8 @@ class Tacotron:
         ``stop_tokens``, ``max_attentions``, ``steps``, ``encoder_outputs`` -- numpy arrays, or torch tensors on the device with
         ``return_device=True`` (``mel`` then feeds ``WaveRNN.generate`` without a copy to the host)."""
         import torch
-        seqs = [np.asarray(s, dtype=np.int64).reshape(-1) for s in sequences]
-        B = len(seqs)
-        if B < 1:
-            raise _cabi.WrnnError(_cabi.ERR_INVALID, 'no utterances')
-        tx = np.array([len(s) for s in seqs], dtype=np.int32)
-        Tx_max = int(tx.max()) if tx.size else 0
-        ids = np.zeros((B, Tx_max), dtype=np.int32)
-        for b, s in enumerate(seqs):
-            if s.size and (s.min() < -2 ** 31 or s.max() >= 2 ** 31):
-                raise _cabi.WrnnError(_cabi.ERR_INVALID, f'utterance {b}: a symbol id does not fit 32 bits')
-            ids[b, :len(s)] = s
-        seeds_a = np.array(list(range(B)) if seeds is None else [int(x) & (2 ** 64 - 1) for x in seeds], dtype=np.uint64)
-        if seeds_a.shape != (B,):
-            raise _cabi.WrnnError(_cabi.ERR_INVALID, f'{seeds_a.size} seeds for {B} utterances')
+        ids, tx, seeds_a = pack_text(sequences, seeds)
+        B, Tx_max = ids.shape
         dev = torch.device('cuda', self.device)
         r, M = self.r, self.num_mels
         call = _cabi.TacoCall()
@@ -174,6 +308,58 @@ class Tacotron:
             out.append(res)
         return out
 
+    def stream(self, sequences, seeds=None, max_iters: int = 2000, prenet_dropout: bool = True, return_device: bool = False,
+               gta_targets=None) -> TacotronStream:
+        """A :class:`TacotronStream` over a free-running ``synthesize(sequences, seeds, max_iters, prenet_dropout=...)``: the encoder
+        runs here, the decoder and the postnet in ``step(n)``.  A context manager.  ``gta_targets`` is refused (``WRNN_ERR_INVALID``):
+        teacher forcing has the whole target in hand and is not streamed."""
+        return TacotronStream(self, sequences, seeds, max_iters, prenet_dropout, return_device, gta_targets)
+
+    def synthesize_stream(self, sequence, chunk_steps: int = 8, **kw):
+        """Generator over one utterance: the non-empty ``mel`` pieces of ``stream([sequence], **kw)`` stepped ``chunk_steps`` at a time
+        (``seeds=[seed]``, ``max_iters``, ``prenet_dropout``, ``return_device`` as for :meth:`stream`).  Concatenated they are
+        ``synthesize([sequence], ...)[0]['mel']``.  The stream is closed when the generator ends, so with ``return_device=True`` the
+        pieces are copies on the device, not views of the stream's buffers: a piece the consumer keeps stays valid."""
+        with self.stream([sequence], **kw) as st:
+            while not st.done:
+                mel = st.step(chunk_steps)[0]['mel']
+                if mel.shape[0]:
+                    yield mel.clone() if st.return_device else mel
+
+
+def synthesize_stream_to_wav(model: Tacotron, voc, seq, path, chunk_steps: int = 8, seed: int = 0, tail: str = 'reference', max_iters: int = 2000,
+                             mu_law: bool = True, return_result: bool = False, **voc_kw):
+    """Text to audio with both halves streaming: every ``mel`` piece of ``model.stream([seq], seeds=[seed])`` goes, transposed to
+    ``(num_mels, k)`` and still on the device, into ``voc.stream(tail=tail, mu_law=mu_law, **voc_kw).push``; then ``finish()``.  The two
+    models take turns on one HIP stream.  Writes the wav to ``path`` (``None``: no file) and returns (audio float64, seconds from the
+    call to the first mel piece, seconds to the first audio samples; ``None`` for a time whose event never came).  With
+    ``tail='reference'`` the audio is what ``voc.generate(mel.T[None], path, False, ..., mu_law)`` makes of ``synthesize``'s mel after the
+    same ``torch.manual_seed``.  ``return_result=True`` appends the Tacotron stream's ``result()[0]`` (device copies): the text is
+    decoded once for the mel and the audio."""
+    import time
+    from .dsp import save_wav
+    t0 = time.perf_counter()
+    t_mel = t_audio = None
+    pieces = []
+    with model.stream([seq], seeds=[seed], max_iters=max_iters, return_device=True) as ts, voc.stream(tail=tail, mu_law=mu_law, **voc_kw) as vs:
+        while not ts.done:
+            mel = ts.step(chunk_steps)[0]['mel']
+            if not mel.shape[0]:
+                continue
+            if t_mel is None:
+                t_mel = time.perf_counter() - t0
+            pieces.append(vs.push(mel.T.contiguous()))
+            if t_audio is None and pieces[-1].size:
+                t_audio = time.perf_counter() - t0
+        pieces.append(vs.finish())
+        if t_audio is None and pieces[-1].size:
+            t_audio = time.perf_counter() - t0
+        res = ts.result()[0] if return_result else None
+    audio = np.concatenate(pieces)
+    if path is not None:
+        save_wav(audio, path, voc.sample_rate)
+    return (audio, t_mel, t_audio, res) if return_result else (audio, t_mel, t_audio)
+
 
 def dims_from_state(state: Dict[str, np.ndarray]) -> dict:
     """The model's dims read off a checkpoint's tensor shapes (``zoneout`` and the clip range are not in it: the reference's values)."""
@@ -215,20 +401,32 @@ def checkpoint_step(path: str) -> str:
 
 
 def synthesize_to_file(model: Tacotron, pinyin: str, symbols: Sequence[str], out_dir: str, step: str, seed: int = 0, max_iters: int = 2000,
-                       gta_target=None, return_device: bool = False):
+                       gta_target=None, return_device: bool = False, stream_steps: Optional[int] = None):
     """``Synthesizer.synthesize`` of ``tacotron_synthesize.py``: writes ``step-{step}-{md5 of the text}-mel-pred.npy``, the (T, num_mels) mel
-    in [0, 1] that ``wavernn_gen.py --file`` reads.  Returns (path, the call's result)."""
+    in [0, 1] that ``wavernn_gen.py --file`` reads.  Returns (path, the call's result).  ``stream_steps``: decode through
+    ``Tacotron.stream`` in pushes of that many steps (the same bytes)."""
+    seq = text_to_sequence(pinyin.split(' '), symbols)
+    if stream_steps is not None:
+        with model.stream([seq], seeds=[seed], max_iters=max_iters, return_device=return_device,
+                          gta_targets=None if gta_target is None else [gta_target]) as st:
+            while not st.done:
+                st.step(stream_steps)
+            res = st.result()[0]
+    else:
+        res = model.synthesize([seq], seeds=[seed], max_iters=max_iters, gta_targets=None if gta_target is None else [gta_target],
+                               return_device=return_device)[0]
+    return write_mel_file(res['mel'], pinyin, out_dir, step), res
+
+
+def write_mel_file(mel, pinyin: str, out_dir: str, step: str) -> str:
+    """``step-{step}-{md5 of the text}-mel-pred.npy`` in ``out_dir``; ``mel``: numpy, or a torch tensor on any device."""
     import hashlib
     import os
-    seq = text_to_sequence(pinyin.split(' '), symbols)
-    res = model.synthesize([seq], seeds=[seed], max_iters=max_iters, gta_targets=None if gta_target is None else [gta_target],
-                           return_device=return_device)[0]
     idx = hashlib.md5(pinyin.encode('utf-8')).hexdigest()
     os.makedirs(out_dir, exist_ok=True)
     path = os.path.join(out_dir, f'step-{step}-{idx}-mel-pred.npy')
-    mel = res['mel']
-    np.save(path, mel.cpu().numpy() if return_device else mel, allow_pickle=False)
-    return path, res
+    np.save(path, mel if isinstance(mel, np.ndarray) else mel.cpu().numpy(), allow_pickle=False)
+    return path
 
 
 def build_parser():
@@ -241,6 +439,8 @@ def build_parser():
     p.add_argument('--seed', type=int, default=0, help='keys the prenet dropout masks')
     p.add_argument('--max_iters', type=int, default=2000)
     p.add_argument('--out_dir', default='./tacotron_inference_output')
+    p.add_argument('--stream-steps', dest='stream_steps', type=int, default=None, metavar='N',
+                   help='decode in pushes of N steps (Tacotron.stream): the same mel; with --vocode the vocoder streams too and the time to the first audio is printed')
     p.add_argument('--vocode', metavar='WAVERNN.pyt', default=None, help='also vocode the mel with these WaveRNN weights (the mel stays on the device)')
     p.add_argument('--griffin_lim', type=int, nargs='?', const=60, default=None, metavar='N_ITER', help='also vocode the mel by Griffin-Lim (no model)')
     return p
@@ -260,19 +460,35 @@ def main(argv=None):
         raise ValueError(f'{args.symbols} makes {len(symbols)} symbols, the checkpoint\'s embedding has {dims["n_symbols"]} rows')
     model = Tacotron(**dims).load_state(state)
     target = np.load(args.gta) if args.gta else None
-    path, res = synthesize_to_file(model, args.pinyin, symbols, args.out_dir, checkpoint_step(args.checkpoint), seed=args.seed,
-                                   max_iters=args.max_iters, gta_target=target, return_device=True)
-    print(f'{res["steps"]} decoder steps, {res["mel_length"]} mel frames -> {path}')
-    mel = res['mel']
-    stem = path[:-len('-mel-pred.npy')]
+    voc = hp = None
     if args.vocode:
         from .gen import build_model_from_hparams
         from .hparams import hparams as hp
         if not hp.is_configured():
             hp.configure()
-        voc = build_model_from_hparams().to(mel.device)
+        voc = build_model_from_hparams().to(torch.device('cuda', model.device))
         voc.load(args.vocode)
-        voc.generate(mel.T[None].contiguous(), stem + '-wavernn.wav', False, hp.voc_target, hp.voc_overlap, hp.mu_law)
+    step = checkpoint_step(args.checkpoint)
+    both_stream = voc is not None and args.stream_steps is not None and target is None
+    if both_stream:   # one Tacotron stream feeds the mel file and the vocoder's stream
+        from .dsp import save_wav
+        seq = text_to_sequence(args.pinyin.split(' '), symbols)
+        audio, t_mel, t_audio, res = synthesize_stream_to_wav(model, voc, seq, None, chunk_steps=args.stream_steps, seed=args.seed,
+                                                              max_iters=args.max_iters, mu_law=hp.mu_law, return_result=True)
+        path = write_mel_file(res['mel'], args.pinyin, args.out_dir, step)
+    else:
+        path, res = synthesize_to_file(model, args.pinyin, symbols, args.out_dir, step, seed=args.seed, max_iters=args.max_iters,
+                                       gta_target=target, return_device=True, stream_steps=args.stream_steps)
+    print(f'{res["steps"]} decoder steps, {res["mel_length"]} mel frames -> {path}')
+    mel = res['mel']
+    stem = path[:-len('-mel-pred.npy')]
+    if voc is not None:
+        if both_stream:
+            save_wav(audio, stem + '-wavernn.wav', voc.sample_rate)
+            ms = lambda t: 'never' if t is None else f'after {1e3 * t:.1f} ms'
+            print(f'first mel frames {ms(t_mel)}, first audio {ms(t_audio)}')
+        else:
+            voc.generate(mel.T[None].contiguous(), stem + '-wavernn.wav', False, hp.voc_target, hp.voc_overlap, hp.mu_law)
         print(stem + '-wavernn.wav')
     if args.griffin_lim is not None:
         from .dsp import save_wav
