@@ -1179,6 +1179,56 @@ const char *wrnn_taco_stream_last_error(const wrnn_taco_stream *st);
  * wrnn_taco_destroy for what happens otherwise). */
 void wrnn_taco_stream_close(wrnn_taco_stream *st);
 
+/* ---- Tacotron-2, the GTA corpus: a corpus's ground-truth mels -> the mels the model predicts under teacher forcing -------------------
+ * What the reference's wavernn_preprocess.py does per utterance (feed the recording's own frames to the decoder, keep
+ * mel[:target_length], map to [0, 1]), for a group of B utterances of a mel table that lives on the device, written into a table of the
+ * same layout.  Utterance b is (frames_host[b], num_mels) float32 in [0, 1], frames-major, from element mel_off_host[b] of mels_dev;
+ * its GTA mel goes to element out_off_host[b] of gta_mels_dev.
+ * The target: the pack kernel builds the (B, gta_max, num_mels) target wrnn_taco_synthesize reads from the [0, 1] mel m, with
+ * A = max_abs_value, gta_max = r ceil(max frames / r): row t < frames is clip(fl(fl(2A m) - A), -A, A) in float32 (fl: one rounding
+ * each, no fused multiply-add); rows from frames up to the next multiple of r are -A (the reference's padding_targets); rows past that
+ * are 0.  This formula IS the definition of the target.  The mel front end computes m = clip((sym + A) / 2A, 0, 1) from its internal
+ * sym = clip(2A n - A, -A, A); the target equals that sym wherever sym <= -A / 2 and lies within one float32 spacing of 2A (ulp(2A))
+ * of it elsewhere.  A corpus loaded from files has only m, which is why the target is defined from it.
+ * Then encoder, decoder, postnet and finish run exactly as wrnn_taco_synthesize launches them with that target, gta_frames
+ * r ceil(frames / r) and steps_max = gta_max / r, every intermediate output in scratch this entry owns (not the scratch of
+ * wrnn_taco_synthesize).  The unpack kernel (one workgroup per utterance) copies the first frames[b] rows of that call's [0, 1] mel
+ * to the output table and writes l1[b] = mean |gta - ground truth| over them; the alignment kernel (one workgroup per utterance)
+ * writes focus[b] = the mean over the utterance's steps of max_t alignments[s, t], and last_attention[b] = max_attentions of the last
+ * step.  Both sums are float64 with a fixed assignment of elements to threads and a fixed tree: a second call gives the same bits.
+ * Waiting: the call never waits for the device.  Every host array is read by a copy queued on `stream`, so the arrays must stay
+ * unchanged until the stream has passed the call; give page-locked memory, so that the copies are asynchronous.  The scratch grows on
+ * demand, and growing it waits for `stream`: a group whose need exceeds what is reserved waits once.  The need grows with B, Tx_max and
+ * the longest utterance, so wrnn_taco_gta_reserve for the largest B, Tx_max and frame count of a corpus, before its first group, leaves
+ * no group a wait (wrnn_taco_gta_workspace_bytes reports what is reserved; it never shrinks).  The first call after a load uploads the
+ * weights (one blocking copy).  Calls on one handle must be ordered by the caller (one HIP stream).
+ * Refusals (WRNN_ERR_INVALID): those of wrnn_taco_synthesize in its wording; frames < 1; frames above 2^24; an offset or extent
+ * outside mels_elems / out_elems; a NULL input table or output. */
+typedef struct wrnn_taco_gta_call {
+    uint32_t struct_size;        /* the size of this struct */
+    int32_t B, Tx_max;           /* utterances; the row stride of ids_host */
+    int32_t prenet_dropout;      /* 0: no masks, no scaling */
+    const int32_t *ids_host;     /* (B, Tx_max) */
+    const int32_t *tx_host;      /* (B) symbols per utterance */
+    const uint64_t *seeds_host;  /* (B) */
+    const int32_t *frames_host;  /* (B) mel frames per utterance, >= 1 */
+    const int64_t *mel_off_host; /* (B) the utterance's first element in mels_dev */
+    const int64_t *out_off_host; /* (B) the utterance's first element in gta_mels_dev */
+    const float *mels_dev;       /* the ground-truth table, mels_elems float32 */
+    int64_t mels_elems;
+    float *gta_mels_dev;         /* the output table, out_elems float32; only the B utterances' own elements are written */
+    int64_t out_elems;
+    double *l1_dev;              /* (B) */
+    double *focus_dev;           /* (B) */
+    int32_t *last_attention_dev; /* (B) */
+} wrnn_taco_gta_call;
+int wrnn_taco_gta_corpus(wrnn_taco_handle *h, const wrnn_taco_gta_call *call, void *stream);
+/* Grows the scratch of wrnn_taco_gta_corpus to what a group of B utterances of up to Tx_max symbols and frames_max mel frames needs
+ * (the one wait, and only when it grows).  WRNN_ERR_INVALID: B, Tx_max or frames_max outside what wrnn_taco_gta_corpus serves. */
+int wrnn_taco_gta_reserve(wrnn_taco_handle *h, int32_t B, int32_t Tx_max, int32_t frames_max, void *stream);
+/* Host only: bytes of that scratch now (0 before the first reserve or call, and for NULL). */
+int64_t wrnn_taco_gta_workspace_bytes(const wrnn_taco_handle *h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,7 +57,8 @@ EXPORTED_SYMBOLS = ('wrnn_create', 'wrnn_load_weights', 'wrnn_conditioning', 'wr
                     'wrnn_taco_create', 'wrnn_taco_tensor_count', 'wrnn_taco_tensor_name', 'wrnn_taco_tensor_shape', 'wrnn_taco_load_tensor',
                     'wrnn_taco_synthesize', 'wrnn_taco_last_error', 'wrnn_taco_destroy',
                     'wrnn_taco_stream_halo', 'wrnn_taco_stream_open', 'wrnn_taco_stream_step', 'wrnn_taco_stream_view', 'wrnn_taco_stream_info',
-                    'wrnn_taco_stream_last_error', 'wrnn_taco_stream_close')
+                    'wrnn_taco_stream_last_error', 'wrnn_taco_stream_close', 'wrnn_taco_gta_corpus',
+                    'wrnn_taco_gta_reserve', 'wrnn_taco_gta_workspace_bytes')
 
 
 def epilogue_tables(n_classes: int, overlap: int, hop: int):
@@ -134,6 +135,14 @@ class TacoStreamOutputs(C.Structure):
                 ('mel_dev', C.c_void_p), ('alignments_dev', C.c_void_p), ('stop_dev', C.c_void_p), ('max_attentions_dev', C.c_void_p),
                 ('steps_dev', C.c_void_p), ('mel_frames_dev', C.c_void_p), ('encoder_stride', C.c_int64), ('frames_stride', C.c_int64),
                 ('alignments_stride', C.c_int64), ('stop_stride', C.c_int64), ('max_attentions_stride', C.c_int64)]
+
+
+class TacoGtaCall(C.Structure):
+    """``wrnn_taco_gta_call``."""
+    _fields_ = [('struct_size', C.c_uint32), ('B', C.c_int32), ('Tx_max', C.c_int32), ('prenet_dropout', C.c_int32), ('ids_host', C.c_void_p),
+                ('tx_host', C.c_void_p), ('seeds_host', C.c_void_p), ('frames_host', C.c_void_p), ('mel_off_host', C.c_void_p),
+                ('out_off_host', C.c_void_p), ('mels_dev', C.c_void_p), ('mels_elems', C.c_int64), ('gta_mels_dev', C.c_void_p),
+                ('out_elems', C.c_int64), ('l1_dev', C.c_void_p), ('focus_dev', C.c_void_p), ('last_attention_dev', C.c_void_p)]
 
 
 LOOP_PARAM_FIELDS = ('I_w', 'I_b', 'rnn1_w_ih', 'rnn1_w_hh', 'rnn1_b_ih', 'rnn1_b_hh', 'rnn2_w_ih', 'rnn2_w_hh', 'rnn2_b_ih',
@@ -642,6 +651,12 @@ def load_library() -> C.CDLL:
     lib.wrnn_taco_stream_last_error.restype = C.c_char_p
     lib.wrnn_taco_stream_close.argtypes = [vp]
     lib.wrnn_taco_stream_close.restype = None
+    lib.wrnn_taco_gta_corpus.argtypes = [vp, C.POINTER(TacoGtaCall), vp]
+    lib.wrnn_taco_gta_corpus.restype = C.c_int
+    lib.wrnn_taco_gta_reserve.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp]
+    lib.wrnn_taco_gta_reserve.restype = C.c_int
+    lib.wrnn_taco_gta_workspace_bytes.argtypes = [vp]
+    lib.wrnn_taco_gta_workspace_bytes.restype = C.c_int64
     lib.wrnn_quantise.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp]
     lib.wrnn_quantise.restype = C.c_int
     lib.wrnn_collate_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -1513,6 +1528,18 @@ class NativeTacotron:
 
     def synthesize(self, call: TacoCall, stream: int):
         self._check(self.lib.wrnn_taco_synthesize(self._h, C.byref(call), stream or None))
+
+    def gta_corpus(self, call: TacoGtaCall, stream: int = 0) -> None:
+        """``wrnn_taco_gta_corpus``: one group of a corpus; waits only if its scratch has to grow (``gta_reserve``)."""
+        self._check(self.lib.wrnn_taco_gta_corpus(self._h, C.byref(call), stream or None))
+
+    def gta_reserve(self, B: int, Tx_max: int, frames_max: int, stream: int = 0) -> int:
+        """``wrnn_taco_gta_reserve``: the scratch for groups of up to this shape, grown now; returns ``gta_workspace_bytes()``."""
+        self._check(self.lib.wrnn_taco_gta_reserve(self._h, int(B), int(Tx_max), int(frames_max), stream or None))
+        return self.gta_workspace_bytes()
+
+    def gta_workspace_bytes(self) -> int:
+        return int(self.lib.wrnn_taco_gta_workspace_bytes(self._h))
 
     def stream_open(self, opts: 'TacoStreamOpts', stream: int) -> 'NativeTacotronStream':
         st = C.c_void_p()

@@ -26,6 +26,7 @@
 
 #include "device_util.h"
 #include "handle_common.h"
+#include "taco_internal.h"
 
 namespace {
 
@@ -571,33 +572,9 @@ __global__ void __launch_bounds__(CONV_THREADS) taco_finish_window_kernel(Finish
     finish_element(g, (long)b * g.T_max * g.M + x);
 }
 
-struct Tensor {
-    std::string name;
-    std::vector<int64_t> shape;
-    std::vector<float> data;   // empty until loaded
-    size_t off = 0;            // floats, in the device image
-    size_t count() const {
-        size_t n = 1;
-        for (int64_t e : shape) n *= (size_t)e;
-        return n;
-    }
-};
+using Tensor = TacoTensor;   // taco_internal.h
 
 }  // namespace
-
-struct wrnn_taco_handle {
-    wrnn_taco_dims d{};
-    bool ok = false;
-    std::vector<Tensor> tensors;
-    bool dirty = true;            // a tensor was loaded since the last upload
-    float *img = nullptr;         // the device image: the tensors in table order, then the derived ones
-    size_t img_cap = 0;
-    size_t off_bn_enc = 0, off_bn_post = 0, off_loc_m = 0, off_att_bias = 0, off_proj_w = 0, off_proj_b = 0;
-    WrnnScratch ws;               // the scratch of a call, grown on demand
-    int open_streams = 0;         // wrnn_taco_stream objects that read img
-    bool destroyed = false;       // wrnn_taco_destroy came while streams were open: the last close frees the handle
-    std::string err;
-};
 
 struct wrnn_taco_stream {
     wrnn_taco_handle *h = nullptr;
@@ -785,10 +762,15 @@ int check_text(wrnn_taco_handle *h, int B, int Tx_max, const int32_t *ids_host, 
     if (!ids_host || !tx_host || !seeds_host) return wrnn_failf(h, WRNN_ERR_INVALID, "ids_host, tx_host or seeds_host is NULL");
     return WRNN_OK;
 }
+}  // namespace
+int taco_refuse_length(wrnn_taco_handle *h, int b, int tx, int Tx_max) {
+    return wrnn_failf(h, WRNN_ERR_INVALID, "utterance %d: %d symbols outside 1 .. Tx_max = %d (the limit is %d)", b, tx, Tx_max, WRNN_TACO_MAX_TX);
+}
+namespace {
 int check_symbols(wrnn_taco_handle *h, int B, int Tx_max, const int32_t *ids_host, const int32_t *tx_host) {
     for (int b = 0; b < B; ++b) {
         const int tx = tx_host[b];
-        if (tx < 1 || tx > Tx_max) return wrnn_failf(h, WRNN_ERR_INVALID, "utterance %d: %d symbols outside 1 .. Tx_max = %d (the limit is %d)", b, tx, Tx_max, WRNN_TACO_MAX_TX);
+        if (tx < 1 || tx > Tx_max) return taco_refuse_length(h, b, tx, Tx_max);
         for (int t = 0; t < tx; ++t) {
             const int id = ids_host[(size_t)b * Tx_max + t];
             if (id < 0 || id >= h->d.n_symbols) return wrnn_failf(h, WRNN_ERR_INVALID, "utterance %d: symbol id %d at %d is outside the table of %d", b, id, t, h->d.n_symbols);
@@ -864,6 +846,86 @@ void free_stream(wrnn_taco_stream *st) {
     delete st;
 }
 }  // namespace
+
+// ---- taco_internal.h: what wrnn_taco_gta_corpus (taco_gta.hip) shares with wrnn_taco_synthesize
+int taco_check_text(wrnn_taco_handle *h, int B, int Tx_max, const int32_t *ids_host, const int32_t *tx_host, const uint64_t *seeds_host) {
+    return check_text(h, B, Tx_max, ids_host, tx_host, seeds_host);
+}
+int taco_check_symbols(wrnn_taco_handle *h, int B, int Tx_max, const int32_t *ids_host, const int32_t *tx_host) {
+    return check_symbols(h, B, Tx_max, ids_host, tx_host);
+}
+int taco_check_decoder_lds(wrnn_taco_handle *h, int Tx_max) {
+    if (decoder_lds_floats(h->d, Tx_max, nullptr, nullptr) * sizeof(float) > LDS_LIMIT)
+        return wrnn_failf(h, WRNN_ERR_INVALID, "the decoder's state for Tx_max %d exceeds 64 KiB of LDS", Tx_max);
+    return WRNN_OK;
+}
+int taco_upload_if_dirty(wrnn_taco_handle *h) { return h->dirty ? upload(h) : WRNN_OK; }
+
+TacoBufs taco_layout(const wrnn_taco_dims &d, int B, int Tx_max, int S) {
+    const int C = d.enc_conv_channels, H = d.encoder_lstm_units, E2 = 2 * H, A = d.attention_dim, PC = d.postnet_channels, M = d.num_mels;
+    const size_t T_out = (size_t)S * d.outputs_per_step;
+    const size_t act_floats = std::max((size_t)B * Tx_max * std::max(C, d.embedding_dim), (size_t)B * T_out * std::max(PC, M));
+    size_t at = 0;
+    auto take = [&at](size_t bytes) { const size_t o = at; at += wrnn_up256(bytes); return o; };
+    TacoBufs o{};
+    o.ids = take((size_t)B * Tx_max * 4); o.tx = take((size_t)B * 4); o.gs = take((size_t)B * 4); o.seeds = take((size_t)B * 8);
+    o.a0 = take(act_floats * 4); o.a1 = take(act_floats * 4);
+    o.xp0 = take((size_t)B * Tx_max * 4 * H * 4); o.xp1 = take((size_t)B * Tx_max * 4 * H * 4);
+    o.mem = take((size_t)B * Tx_max * E2 * 4); o.keys = take((size_t)B * Tx_max * A * 4);
+    o.end = at;
+    return o;
+}
+
+int taco_run(wrnn_taco_handle *h, hipStream_t s, const TacoRun &c) {
+    const wrnn_taco_dims &d = h->d;
+    const int B = c.B, Tx_max = c.Tx_max, S = c.S, r = d.outputs_per_step, M = d.num_mels;
+    const int E2 = 2 * d.encoder_lstm_units, PC = d.postnet_channels, T_out = S * r;
+    int Pmax = 0, Kmax = 0, rc;
+    const size_t dec_lds = decoder_lds_floats(d, Tx_max, &Pmax, &Kmax) * sizeof(float);
+    char *ws = c.ws;
+    const int32_t *ids = (const int32_t *)(ws + c.o.ids), *tx = (const int32_t *)(ws + c.o.tx), *gs = (const int32_t *)(ws + c.o.gs);
+    const uint64_t *seeds = (const uint64_t *)(ws + c.o.seeds);
+    float *a0 = (float *)(ws + c.o.a0), *a1 = (float *)(ws + c.o.a1), *xp[2] = {(float *)(ws + c.o.xp0), (float *)(ws + c.o.xp1)};
+    float *mem = (float *)(ws + c.o.mem), *keys = (float *)(ws + c.o.keys);
+    WRNN_TRY(h, hipMemsetAsync(mem, 0, (size_t)B * Tx_max * E2 * 4, s));
+    WRNN_TRY(h, hipMemsetAsync(c.decoder, 0, (size_t)B * T_out * M * 4, s));
+    WRNN_TRY(h, hipMemsetAsync(c.alignments, 0, (size_t)B * S * Tx_max * 4, s));
+    WRNN_TRY(h, hipMemsetAsync(c.stop, 0, (size_t)B * T_out * 4, s));
+    WRNN_TRY(h, hipMemsetAsync(c.max_attentions, 0, (size_t)B * S * 4, s));
+    const float *img = h->img;
+    auto T = [&](const std::string &n) { return img + find(h, n)->off; };
+    // ---- encoder
+    const EncBufs eb{ids, tx, a0, a1, {xp[0], xp[1]}, mem, keys};
+    if ((rc = run_encoder(h, s, eb, B, Tx_max)) != WRNN_OK) return rc;
+    if (c.encoder) WRNN_TRY(h, hipMemcpyAsync(c.encoder, mem, (size_t)B * Tx_max * E2 * 4, hipMemcpyDeviceToDevice, s));
+    // ---- decoder
+    DecArgs g{};
+    g.memory = mem; g.keys = keys; g.tx = tx; g.seeds = seeds; g.gta = c.gta; g.gta_steps = gs;
+    decoder_model_args(h, g);
+    g.decoder = c.decoder; g.alignments = c.alignments; g.stop = c.stop;
+    g.max_attentions = c.max_attentions; g.steps = c.steps; g.mel_frames = c.mel_frames;
+    g.Tx_max = Tx_max; g.gta_max = c.gta ? c.gta_max : 0; g.max_iters = c.max_iters; g.steps_max = S; g.dropout = c.dropout;
+    g.Pmax = Pmax; g.Kmax = Kmax;
+    hipLaunchKernelGGL(taco_decoder_kernel<false>, dim3((unsigned)B), dim3(LOOP_THREADS), dec_lds, s, g, DecState{});
+    WRNN_TRY(h, hipGetLastError());
+    // ---- postnet over steps r rows per utterance, the count read from the device
+    const float *pin = c.decoder;
+    float *cur = a0, *nxt = a1;
+    for (int i = 0; i < d.postnet_layers; ++i) {
+        const std::string p = post_conv(i + 1);
+        rc = launch_conv(h, s, pin, T(p + "conv1d/kernel"), T(p + "conv1d/bias"), img + h->off_bn_post + (size_t)i * 2 * up64(PC), (int)up64(PC), cur, c.steps, r, B,
+                         T_out, i ? PC : M, PC, d.postnet_kernel, i + 1 < d.postnet_layers ? 2 : 0);
+        if (rc != WRNN_OK) return rc;
+        pin = cur;
+        std::swap(cur, nxt);
+    }
+    rc = launch_conv(h, s, pin, T(std::string(POSTP) + "kernel"), T(std::string(POSTP) + "bias"), nullptr, 0, cur, c.steps, r, B, T_out, PC, M, 1, 0);
+    if (rc != WRNN_OK) return rc;
+    FinishArgs f{c.decoder, cur, c.steps, c.mel_raw, c.mel, T_out, M, r, g.clip_lo, g.clip_hi};
+    hipLaunchKernelGGL(taco_finish_kernel, dim3((unsigned)(((size_t)T_out * M + CONV_THREADS - 1) / CONV_THREADS), (unsigned)B), dim3(CONV_THREADS), 0, s, f);
+    WRNN_TRY(h, hipGetLastError());
+    return WRNN_OK;
+}
 
 extern "C" {
 
@@ -949,7 +1011,7 @@ int wrnn_taco_synthesize(wrnn_taco_handle *h, const wrnn_taco_call *c, void *str
     if (c->struct_size != sizeof(wrnn_taco_call))
         return wrnn_failf(h, WRNN_ERR_INVALID, "wrnn_taco_call.struct_size %u, this library's is %zu", c->struct_size, sizeof(wrnn_taco_call));
     const wrnn_taco_dims &d = h->d;
-    const int B = c->B, Tx_max = c->Tx_max, r = d.outputs_per_step, M = d.num_mels;
+    const int B = c->B, Tx_max = c->Tx_max, r = d.outputs_per_step;
     int rc = check_text(h, B, Tx_max, c->ids_host, c->tx_host, c->seeds_host);
     if (rc != WRNN_OK) return rc;
     if (!c->decoder_dev || !c->mel_raw_dev || !c->mel_dev || !c->alignments_dev || !c->stop_dev || !c->max_attentions_dev || !c->steps_dev || !c->mel_frames_dev)
@@ -971,70 +1033,26 @@ int wrnn_taco_synthesize(wrnn_taco_handle *h, const wrnn_taco_call *c, void *str
     }
     const int S = c->steps_max;
     if (S < need_steps || (int64_t)S * r > (1 << 24)) return wrnn_failf(h, WRNN_ERR_INVALID, "steps_max %d: below the %d steps this call can run, or above 2^24 / r", S, need_steps);
-    int Pmax = 0, Kmax = 0;
-    const size_t dec_lds = decoder_lds_floats(d, Tx_max, &Pmax, &Kmax) * sizeof(float);
-    if (dec_lds > LDS_LIMIT) return wrnn_failf(h, WRNN_ERR_INVALID, "the decoder's state for Tx_max %d exceeds 64 KiB of LDS", Tx_max);
+    if ((rc = taco_check_decoder_lds(h, Tx_max)) != WRNN_OK) return rc;
     WRNN_TRY(h, hipSetDevice(d.device));
     hipStream_t s = (hipStream_t)stream;
-    if (h->dirty && (rc = upload(h)) != WRNN_OK) return rc;
-    // the scratch: ids, tx, gta steps, seeds; two ping-pong activations; the LSTM input projections; memory; keys
-    const int C = d.enc_conv_channels, H = d.encoder_lstm_units, E2 = 2 * H, A = d.attention_dim, PC = d.postnet_channels, T_out = S * r;
-    const size_t act_floats = std::max((size_t)B * Tx_max * std::max(C, d.embedding_dim), (size_t)B * T_out * std::max(PC, M));
-    size_t at = 0;
-    auto take = [&at](size_t bytes) { const size_t o = at; at += wrnn_up256(bytes); return o; };
-    const size_t o_ids = take((size_t)B * Tx_max * 4), o_tx = take((size_t)B * 4), o_gs = take((size_t)B * 4), o_seed = take((size_t)B * 8);
-    const size_t o_a0 = take(act_floats * 4), o_a1 = take(act_floats * 4), o_xp0 = take((size_t)B * Tx_max * 4 * H * 4), o_xp1 = take((size_t)B * Tx_max * 4 * H * 4);
-    const size_t o_mem = take((size_t)B * Tx_max * E2 * 4), o_keys = take((size_t)B * Tx_max * A * 4);
-    WRNN_TRY(h, h->ws.reserve(at, s));
+    if ((rc = taco_upload_if_dirty(h)) != WRNN_OK) return rc;
+    const TacoBufs o = taco_layout(d, B, Tx_max, S);
+    WRNN_TRY(h, h->ws.reserve(o.end, s));
     char *ws = h->ws.p;
-    int32_t *ids = (int32_t *)(ws + o_ids), *tx = (int32_t *)(ws + o_tx), *gs = (int32_t *)(ws + o_gs);
-    uint64_t *seeds = (uint64_t *)(ws + o_seed);
-    float *a0 = (float *)(ws + o_a0), *a1 = (float *)(ws + o_a1), *xp[2] = {(float *)(ws + o_xp0), (float *)(ws + o_xp1)};
-    float *mem = (float *)(ws + o_mem), *keys = (float *)(ws + o_keys);
     // pageable host memory: these copies return once the source has been read
-    WRNN_TRY(h, hipMemcpyAsync(ids, c->ids_host, (size_t)B * Tx_max * 4, hipMemcpyHostToDevice, s));
-    WRNN_TRY(h, hipMemcpyAsync(tx, c->tx_host, (size_t)B * 4, hipMemcpyHostToDevice, s));
-    WRNN_TRY(h, hipMemcpyAsync(gs, gsteps.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
-    WRNN_TRY(h, hipMemcpyAsync(seeds, c->seeds_host, (size_t)B * 8, hipMemcpyHostToDevice, s));
+    WRNN_TRY(h, hipMemcpyAsync(ws + o.ids, c->ids_host, (size_t)B * Tx_max * 4, hipMemcpyHostToDevice, s));
+    WRNN_TRY(h, hipMemcpyAsync(ws + o.tx, c->tx_host, (size_t)B * 4, hipMemcpyHostToDevice, s));
+    WRNN_TRY(h, hipMemcpyAsync(ws + o.gs, gsteps.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
+    WRNN_TRY(h, hipMemcpyAsync(ws + o.seeds, c->seeds_host, (size_t)B * 8, hipMemcpyHostToDevice, s));
     WRNN_TRY(h, hipStreamSynchronize(s));   // gsteps leaves scope; the caller's arrays may too
-    WRNN_TRY(h, hipMemsetAsync(mem, 0, (size_t)B * Tx_max * E2 * 4, s));
-    WRNN_TRY(h, hipMemsetAsync(c->decoder_dev, 0, (size_t)B * T_out * M * 4, s));
-    WRNN_TRY(h, hipMemsetAsync(c->alignments_dev, 0, (size_t)B * S * Tx_max * 4, s));
-    WRNN_TRY(h, hipMemsetAsync(c->stop_dev, 0, (size_t)B * T_out * 4, s));
-    WRNN_TRY(h, hipMemsetAsync(c->max_attentions_dev, 0, (size_t)B * S * 4, s));
-    const float *img = h->img;
-    auto T = [&](const std::string &n) { return img + find(h, n)->off; };
-    // ---- encoder
-    const EncBufs eb{ids, tx, a0, a1, {xp[0], xp[1]}, mem, keys};
-    if ((rc = run_encoder(h, s, eb, B, Tx_max)) != WRNN_OK) return rc;
-    if (c->encoder_dev) WRNN_TRY(h, hipMemcpyAsync(c->encoder_dev, mem, (size_t)B * Tx_max * E2 * 4, hipMemcpyDeviceToDevice, s));
-    // ---- decoder
-    DecArgs g{};
-    g.memory = mem; g.keys = keys; g.tx = tx; g.seeds = seeds; g.gta = c->gta_dev; g.gta_steps = gs;
-    decoder_model_args(h, g);
-    g.decoder = c->decoder_dev; g.alignments = c->alignments_dev; g.stop = c->stop_dev;
-    g.max_attentions = c->max_attentions_dev; g.steps = c->steps_dev; g.mel_frames = c->mel_frames_dev;
-    g.Tx_max = Tx_max; g.gta_max = gta ? c->gta_max : 0; g.max_iters = c->max_iters; g.steps_max = S; g.dropout = c->prenet_dropout ? 1 : 0;
-    g.Pmax = Pmax; g.Kmax = Kmax;
-    hipLaunchKernelGGL(taco_decoder_kernel<false>, dim3((unsigned)B), dim3(LOOP_THREADS), dec_lds, s, g, DecState{});
-    WRNN_TRY(h, hipGetLastError());
-    // ---- postnet over steps r rows per utterance, the count read from the device
-    const float *pin = c->decoder_dev;
-    float *cur = a0, *nxt = a1;
-    for (int i = 0; i < d.postnet_layers; ++i) {
-        const std::string p = post_conv(i + 1);
-        rc = launch_conv(h, s, pin, T(p + "conv1d/kernel"), T(p + "conv1d/bias"), img + h->off_bn_post + (size_t)i * 2 * up64(PC), (int)up64(PC), cur, c->steps_dev, r, B,
-                         T_out, i ? PC : M, PC, d.postnet_kernel, i + 1 < d.postnet_layers ? 2 : 0);
-        if (rc != WRNN_OK) return rc;
-        pin = cur;
-        std::swap(cur, nxt);
-    }
-    rc = launch_conv(h, s, pin, T(std::string(POSTP) + "kernel"), T(std::string(POSTP) + "bias"), nullptr, 0, cur, c->steps_dev, r, B, T_out, PC, M, 1, 0);
-    if (rc != WRNN_OK) return rc;
-    FinishArgs f{c->decoder_dev, cur, c->steps_dev, c->mel_raw_dev, c->mel_dev, T_out, M, r, g.clip_lo, g.clip_hi};
-    hipLaunchKernelGGL(taco_finish_kernel, dim3((unsigned)(((size_t)T_out * M + CONV_THREADS - 1) / CONV_THREADS), (unsigned)B), dim3(CONV_THREADS), 0, s, f);
-    WRNN_TRY(h, hipGetLastError());
-    return WRNN_OK;
+    TacoRun run{};
+    run.B = B; run.Tx_max = Tx_max; run.S = S; run.gta_max = gta ? c->gta_max : 0; run.max_iters = c->max_iters; run.dropout = c->prenet_dropout ? 1 : 0;
+    run.ws = ws; run.o = o; run.gta = c->gta_dev;
+    run.encoder = c->encoder_dev; run.decoder = c->decoder_dev; run.mel_raw = c->mel_raw_dev; run.mel = c->mel_dev;
+    run.alignments = c->alignments_dev; run.stop = c->stop_dev;
+    run.max_attentions = c->max_attentions_dev; run.steps = c->steps_dev; run.mel_frames = c->mel_frames_dev;
+    return taco_run(h, s, run);
 }
 
 const char *wrnn_taco_last_error(const wrnn_taco_handle *h) { return wrnn_last_error_of(h); }
@@ -1210,10 +1228,11 @@ void wrnn_taco_destroy(wrnn_taco_handle *h) {
         h->destroyed = true;
         return;
     }
-    if (h->img || h->ws.p) {
+    if (h->img || h->ws.p || h->gta_ws.p) {
         (void)hipSetDevice(h->d.device);
         if (h->img) (void)hipFree(h->img);
         h->ws.release();
+        h->gta_ws.release();
     }
     delete h;
 }

@@ -24,6 +24,7 @@ from .train import draw_window_offsets
 
 LIST_NAME = 'wavernn_training_data.txt'
 FEATURES_NAME = 'wavernn_training_features.txt'   # next to the list file: the feature profile of the saved mels, one word
+GTA_NAME = 'wavernn_training_gta.txt'             # next to the list file of a GTA corpus: the checkpoint's name and the seed base
 
 
 def saved_features(list_file: Union[str, Path]) -> str:
@@ -61,6 +62,27 @@ def _device(device) -> torch.device:
     return torch.device('cuda', dev.index if dev.index is not None else torch.cuda.current_device())
 
 
+class _GtaMade:
+    """``corpus.gta`` of a GTA corpus: equal to ``True`` and true, where every other corpus has the method ``gta``.  Calling it is a
+    ``ValueError`` that says so (``gta_made`` is the plain flag every corpus has)."""
+
+    def __eq__(self, other):
+        return other is True or isinstance(other, _GtaMade)
+
+    def __hash__(self):
+        return hash(True)
+
+    def __bool__(self):
+        return True
+
+    def __repr__(self):
+        return 'True'
+
+    def __call__(self, *args, **kw):
+        raise ValueError('this corpus already holds GTA mels (gta_made): teacher-force the corpus it was made from, whose mels it keeps as '
+                         'source_mels, not this one')
+
+
 class DeviceCorpus:
     """Utterances as ``labels`` (int32, all utterances back to back) and ``mels`` (float32, utterance u as ``(frames[u], n_mels)``
     from element ``mel_off[u]``) on one device.  ``label_off / label_len / mel_off / frames`` are host arrays with one entry per
@@ -68,8 +90,16 @@ class DeviceCorpus:
 
     def __init__(self, labels: torch.Tensor, mels: torch.Tensor, label_off, label_len, mel_off, frames, n_mels: int, stems: Sequence[str],
                  *, hop_length: int, sample_rate: Optional[int] = None, bits: Optional[int] = None, mu_law: Optional[bool] = None,
-                 n_clipped: int = 0, trim_top_db: Optional[float] = None, peak_norm: Optional[float] = None, features: str = 'vocoder'):
+                 n_clipped: int = 0, trim_top_db: Optional[float] = None, peak_norm: Optional[float] = None, features: str = 'vocoder',
+                 source_mels: Optional[torch.Tensor] = None, gta: bool = False, gta_note: Optional[dict] = None):
         self.labels, self.mels = labels, mels
+        # a GTA corpus (``gta()``): ``mels`` are the Tacotron's teacher-forced predictions, ``source_mels`` the ground truth they were made
+        # from, a table of the same offsets; ``gta_note`` is what ``save`` writes about their making
+        self.source_mels, self.gta_made, self.gta_note = source_mels, bool(gta), dict(gta_note or {})
+        if self.gta_made:
+            self.gta = _GtaMade()   # on a GTA corpus the name is the flag, == True; called, it says why there is no second pass
+        if source_mels is not None and source_mels.numel() != mels.numel():
+            raise ValueError('source_mels and mels are tables of one layout: they differ in size')
         self.features = features   # the feature profile of the mels (frontend.FEATURE_PROFILES)
         self.trim_top_db, self.peak_norm = trim_top_db, peak_norm   # how from_wavs conditioned the clips (None: it did not)
         self.label_off, self.label_len = np.asarray(label_off, np.int64), np.asarray(label_len, np.int64)
@@ -117,13 +147,16 @@ class DeviceCorpus:
             out.append((mel.T, self.labels[int(lo):int(lo) + int(ln)].cpu().numpy()))
         return out
 
+    def _meta(self) -> dict:
+        return dict(hop_length=self.hop_length, sample_rate=self.sample_rate, bits=self.bits, mu_law=self.mu_law, n_clipped=self.n_clipped,
+                    trim_top_db=self.trim_top_db, peak_norm=self.peak_norm, features=self.features)
+
     def subset(self, ids: Sequence[int]) -> 'DeviceCorpus':
-        """The utterances ``ids`` as a corpus of their own that shares the device buffers (nothing is copied)."""
+        """The utterances ``ids`` as a corpus of their own that shares the device buffers (nothing is copied); of a GTA corpus, a GTA
+        corpus."""
         ids = np.asarray(list(ids), np.int64)
         return DeviceCorpus(self.labels, self.mels, self.label_off[ids], self.label_len[ids], self.mel_off[ids], self.frames[ids], self.n_mels,
-                            [self.stems[i] for i in ids], hop_length=self.hop_length, sample_rate=self.sample_rate, bits=self.bits,
-                            mu_law=self.mu_law, n_clipped=self.n_clipped, trim_top_db=self.trim_top_db, peak_norm=self.peak_norm,
-                            features=self.features)
+                            [self.stems[i] for i in ids], source_mels=self.source_mels, gta=self.gta_made, gta_note=self.gta_note, **self._meta())
 
     def split(self, test_samples: int) -> Tuple['DeviceCorpus', 'DeviceCorpus']:
         """(train, test) the way ``read_feature_list`` / ``get_vocoder_datasets`` (dataset.py:79-85) split: ids shuffled with seed
@@ -133,6 +166,101 @@ class DeviceCorpus:
         if test_samples:
             return self.subset(ids[:-test_samples]), self.subset(ids[-test_samples:])
         return self.subset(ids), self.subset([])
+
+    # ------------------------------------------------------------------ the Tacotron's own mels
+    def gta(self, model, sequences, *, seeds=None, seed_base: int = 0, batch_utts: int = 64, prenet_dropout: bool = True):
+        """``(corpus, report)``: this corpus with every mel replaced by the one ``model`` (a ``tacotron.Tacotron``) predicts when its
+        decoder is fed the utterance's own frames -- the GTA mels the reference's ``wavernn_preprocess.py`` trains its vocoder on.
+        ``sequences[u]`` is the symbol id list of utterance u.  Utterance u's dropout masks are keyed by ``seeds[u]``, or
+        ``seed_base + u``: by its position in the corpus and not by its group, so its GTA mel does not depend on ``batch_utts``.  The
+        utterances go through ``wrnn_taco_gta_corpus`` in groups of ``batch_utts`` formed by frame count, back to back on the current
+        stream; the mels never leave the device.  The library's scratch is grown once, before the first group, to the need of the largest
+        (that waits for the stream when it grows at all); no group waits, and the host waits once at the end, for the report.
+
+        The new corpus shares ``labels`` and the label tables, owns a new ``mels`` table with the same offsets and frame counts, has
+        ``gta_made == True`` and keeps this corpus's table as ``source_mels``.  ``report``: host arrays with one entry per utterance --
+        ``l1`` (mean |GTA - ground truth| in [0, 1] units), ``focus`` (the mean over the decoder's steps of the largest alignment),
+        ``last_attention`` (``max_attentions`` of the last step), ``tx``, ``frames``, ``steps``.
+        ``ValueError``: the mels are not Tacotron's (``features``), ``n_mels`` is not the model's, or the sequences do not match the
+        utterances in number.  A group the library refuses raises ``_cabi.WrnnError`` with its reason and the utterance's stem."""
+        import ctypes as C
+        import re
+        if self.features != 'tacotron':
+            raise ValueError(f'this corpus holds {self.features!r} mel features: a Tacotron is teacher-forced on its own kind, make the '
+                             f'corpus with features=\'tacotron\'')
+        if self.n_mels != int(model.num_mels):
+            raise ValueError(f'the corpus has {self.n_mels} mel bands, the Tacotron predicts {int(model.num_mels)}')
+        N = len(self)
+        if len(sequences) != N:
+            raise ValueError(f'{len(sequences)} symbol sequences for {N} utterances')
+        dev = self.device
+        if dev.index != int(model.device):
+            raise ValueError(f'the corpus lives on {dev}, the Tacotron on device {model.device}')
+        if seeds is not None and len(seeds) != N:
+            raise ValueError(f'{len(seeds)} seeds for {N} utterances')
+        seqs = [np.asarray(s, dtype=np.int64).reshape(-1) for s in sequences]
+        for u, q in enumerate(seqs):
+            if q.size and (q.min() < -2 ** 31 or q.max() >= 2 ** 31):
+                raise ValueError(f'utterance {self.stems[u]!r}: a symbol id does not fit 32 bits')
+        tx = np.array([len(q) for q in seqs], np.int32)
+        seed_of = [(int(seeds[u]) if seeds is not None else int(seed_base) + u) & (2 ** 64 - 1) for u in range(N)]
+        r, M = int(model.r), self.n_mels
+        frames = self.frames.astype(np.int32)
+        report = dict(l1=np.zeros(N, np.float64), focus=np.zeros(N, np.float64), last_attention=np.zeros(N, np.int32), tx=tx.copy(),
+                      frames=frames.copy(), steps=((frames.astype(np.int64) + r - 1) // r).astype(np.int32))
+        note = dict(checkpoint=getattr(model, 'checkpoint', None), seed_base=int(seed_base))
+        step = max(1, int(batch_utts))
+        order = np.argsort(frames, kind='stable')
+        groups = [order[g:g + step] for g in range(0, N, step)]
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            out = torch.zeros_like(self.mels)
+            made = DeviceCorpus(self.labels, out, self.label_off, self.label_len, self.mel_off, self.frames, M, self.stems,
+                                source_mels=self.mels, gta=True, gta_note=note, **self._meta())
+            made._tables = self.device_tables()
+            if not N:
+                return made, report
+            widths = [max(int(tx[ids].max()), 1) for ids in groups]
+            if max(widths) <= _cabi.TACO_MAX_TX:   # the scratch for the largest group now, so that no group waits for it to grow (an
+                model.native.gta_reserve(min(step, N), max(widths), max(int(frames.max()), 1), stream)   # over-long text is refused below, by name)
+            l1, focus = torch.zeros(N, dtype=torch.float64, device=dev), torch.zeros(N, dtype=torch.float64, device=dev)
+            last = torch.zeros(N, dtype=torch.int32, device=dev)
+            # page-locked host arrays for every group: the library's copies are queued, nothing waits for them
+            pin32 = torch.zeros(sum(len(ids) * w for ids, w in zip(groups, widths)) + 2 * N, dtype=torch.int32).pin_memory()
+            pin64 = torch.zeros(3 * N, dtype=torch.int64).pin_memory()
+            h32, h64 = pin32.numpy(), pin64.numpy()
+            at32 = at = 0
+            for ids, w in zip(groups, widths):
+                B = len(ids)
+                ids_h, at32 = h32[at32:at32 + B * w].reshape(B, w), at32 + B * w
+                tx_h, fr_h, at32 = h32[at32:at32 + B], h32[at32 + B:at32 + 2 * B], at32 + 2 * B
+                seeds_h, off_h = h64[3 * at:3 * at + B].view(np.uint64), h64[3 * at + B:3 * at + 2 * B]
+                for b, u in enumerate(ids):
+                    ids_h[b, :len(seqs[u])] = seqs[u][:w]
+                    seeds_h[b] = seed_of[u]
+                tx_h[:], fr_h[:], off_h[:] = tx[ids], frames[ids], self.mel_off[ids]
+                call = _cabi.TacoGtaCall()
+                call.struct_size = C.sizeof(_cabi.TacoGtaCall)
+                call.B, call.Tx_max, call.prenet_dropout = B, w, int(bool(prenet_dropout))
+                call.ids_host, call.tx_host, call.seeds_host = ids_h.ctypes.data, tx_h.ctypes.data, seeds_h.ctypes.data
+                call.frames_host, call.mel_off_host, call.out_off_host = fr_h.ctypes.data, off_h.ctypes.data, off_h.ctypes.data
+                call.mels_dev, call.mels_elems = self.mels.data_ptr(), self.mels.numel()
+                call.gta_mels_dev, call.out_elems = out.data_ptr(), out.numel()
+                call.l1_dev, call.focus_dev, call.last_attention_dev = l1[at:].data_ptr(), focus[at:].data_ptr(), last[at:].data_ptr()
+                try:
+                    model.native.gta_corpus(call, stream)
+                except _cabi.WrnnError as e:
+                    torch.cuda.current_stream(dev).synchronize()   # the groups already queued read the page-locked arrays
+                    reason = str(e).split(': ', 1)[-1]
+                    named = re.search(r'utterance (\d+)', reason)
+                    if named and int(named.group(1)) < B:
+                        reason += f' (utterance {named.group(1)} of its group is {self.stems[int(ids[int(named.group(1))])]!r})'
+                    raise _cabi.WrnnError(e.code, reason) from None
+                at += B
+            torch.cuda.current_stream(dev).synchronize()           # the one wait: the report, and the page-locked arrays may go
+            report['l1'][order], report['focus'][order] = l1.cpu().numpy(), focus.cpu().numpy()
+            report['last_attention'][order] = last.cpu().numpy()
+        return made, report
 
     # ------------------------------------------------------------------ constructors
     @classmethod
@@ -332,6 +460,8 @@ class DeviceCorpus:
         (out / 'mel').mkdir(parents=True, exist_ok=True)
         if len(set(self.stems)) != len(self.stems):
             raise ValueError('two utterances share a name: their files would overwrite each other')
+        if self.gta_made:
+            return self._save_gta(out)
         lines = []
         for (mel, lab), stem in zip(self.pairs(), self.stems):
             q, m = out / 'quant' / f'{stem}.npy', out / 'mel' / f'{stem}.npy'
@@ -341,6 +471,26 @@ class DeviceCorpus:
         listing = out / LIST_NAME
         listing.write_text(''.join(lines), encoding='utf-8')
         (out / FEATURES_NAME).write_text(self.features + '\n', encoding='utf-8')
+        return listing
+
+    def _save_gta(self, out: Path) -> Path:
+        """``save`` of a GTA corpus: ``mel/<stem>.npy`` is the ground truth (``source_mels``), ``mel_gta/<stem>.npy`` the GTA mel, and
+        the lines are ``quant|mel|mel_gta|stem`` -- the reference's own ``quant | mel | predicted mel | text``, of which
+        ``read_feature_list``, ``load`` and the reference's ``get_vocoder_datasets`` read fields 0 and 2.  ``wavernn_training_gta.txt``
+        notes the checkpoint's name and the seed base."""
+        (out / 'mel_gta').mkdir(parents=True, exist_ok=True)
+        lines = []
+        for (gta, lab), stem, mo, t in zip(self.pairs(), self.stems, self.mel_off, self.frames):
+            q, m, g = out / 'quant' / f'{stem}.npy', out / 'mel' / f'{stem}.npy', out / 'mel_gta' / f'{stem}.npy'
+            truth = self.source_mels[int(mo):int(mo) + int(t) * self.n_mels].cpu().numpy().reshape(int(t), self.n_mels)
+            np.save(q, lab.astype(np.int32), allow_pickle=False)
+            np.save(m, np.ascontiguousarray(truth, dtype=np.float32), allow_pickle=False)
+            np.save(g, np.ascontiguousarray(gta.T, dtype=np.float32), allow_pickle=False)
+            lines.append(f'{q}|{m}|{g}|{stem}\n')
+        listing = out / LIST_NAME
+        listing.write_text(''.join(lines), encoding='utf-8')
+        (out / FEATURES_NAME).write_text(self.features + '\n', encoding='utf-8')
+        (out / GTA_NAME).write_text(f'checkpoint {self.gta_note.get("checkpoint")}\nseed_base {self.gta_note.get("seed_base")}\n', encoding='utf-8')
         return listing
 
     @classmethod
@@ -413,6 +563,70 @@ class DeviceWindowLoader:
             yield x, y, mels
 
 
+def add_gta_arguments(parser) -> None:
+    """The ``--gta_*`` options of ``wavernn_preprocess.py`` and ``wavernn_train.py`` (with ``--wav_dir DIR --features tacotron``)."""
+    parser.add_argument('--gta_checkpoint', metavar='TACO.npz', default=None,
+                        help='replace the mels of the --wav_dir corpus by the ones this Tacotron predicts under teacher forcing (GTA): '
+                             'the vocoder then learns from the mels it is given at synthesis time.  Needs --features tacotron and --gta_metadata')
+    parser.add_argument('--gta_metadata', metavar='train.txt', default=None,
+                        help='the Tacotron\'s training list (audio-NAME.npy|mel-NAME.npy|samples|frames|text|pinyin): the pinyin of clip NAME.wav, '
+                             'and the symbol table')
+    parser.add_argument('--gta_seed', type=int, default=0, metavar='N', help='utterance u draws its prenet dropout masks from seed N + u')
+    parser.add_argument('--gta_batch', type=int, default=64, metavar='N', help='utterances per call of the teacher-forced decoder')
+    parser.add_argument('--gta_report', metavar='FILE.tsv', default=None,
+                        help='write one line per utterance: stem, frames, tx, l1, focus, last_attention')
+    parser.add_argument('--gta_min_focus', type=float, default=None, metavar='F',
+                        help='keep only the utterances whose attention focus is at least F (default: keep all)')
+
+
+def gta_arguments(args) -> bool:
+    """Whether the arguments ask for a GTA corpus; ``ValueError`` for a combination that cannot be served."""
+    if args.gta_checkpoint is None:
+        given = [n for n in ('gta_metadata', 'gta_report', 'gta_min_focus') if getattr(args, n) is not None]
+        if given:
+            raise ValueError(f'--{given[0]} belongs to --gta_checkpoint: without a Tacotron there are no GTA mels')
+        return False
+    if getattr(args, 'wav_dir', None) is None:
+        raise ValueError('--gta_checkpoint teacher-forces the Tacotron on the corpus made from --wav_dir: give --wav_dir')
+    if args.features != 'tacotron':
+        raise ValueError(f'--gta_checkpoint needs --features tacotron: the decoder is fed the corpus\'s own mels, and those must be the '
+                         f'features the Tacotron was trained on, not the {args.features!r} ones')
+    if args.gta_metadata is None:
+        raise ValueError('--gta_checkpoint needs --gta_metadata: the Tacotron reads each clip\'s pinyin, and the list also makes the symbol table')
+    if args.gta_batch < 1:
+        raise ValueError(f'--gta_batch {args.gta_batch} < 1')
+    return True
+
+
+def gta_from_arguments(corpus: 'DeviceCorpus', args) -> 'DeviceCorpus':
+    """``corpus.gta`` as the ``--gta_*`` arguments ask for it: the checkpoint's dims are read off its tensors, a clip's stem looks up its
+    line of the metadata, the report goes to ``--gta_report`` and ``--gta_min_focus`` drops the utterances below it."""
+    import os
+    from . import tacotron as taco
+    symbols, metadata = taco.load_symbols(args.gta_metadata), taco.read_metadata(args.gta_metadata)
+    with np.load(args.gta_checkpoint, allow_pickle=False) as z:
+        state = {k: z[k] for k in z.files}
+    dims = taco.dims_from_state(state)
+    if dims['n_symbols'] != len(symbols):
+        raise ValueError(f'{args.gta_metadata} makes {len(symbols)} symbols, the checkpoint\'s embedding has {dims["n_symbols"]} rows')
+    seqs = taco.metadata_sequences(metadata, corpus.stems, symbols, args.gta_metadata)
+    model = taco.Tacotron(device=corpus.device.index, **dims).load_state(state)
+    model.checkpoint = os.path.basename(args.gta_checkpoint)
+    made, report = corpus.gta(model, seqs, seed_base=args.gta_seed, batch_utts=args.gta_batch)
+    if args.gta_report:
+        with open(args.gta_report, 'w', encoding='utf-8') as f:
+            f.write('stem\tframes\ttx\tl1\tfocus\tlast_attention\n')
+            for u, stem in enumerate(made.stems):
+                f.write(f'{stem}\t{report["frames"][u]}\t{report["tx"][u]}\t{report["l1"][u]:.6f}\t{report["focus"][u]:.6f}\t{report["last_attention"][u]}\n')
+    print(f'GTA mels of {len(made)} utterances from {model.checkpoint} | mean l1 {float(report["l1"].mean()):.4f} | '
+          f'mean focus {float(report["focus"].mean()):.4f}')
+    if args.gta_min_focus is not None:
+        keep = np.flatnonzero(report['focus'] >= args.gta_min_focus)
+        print(f'--gta_min_focus {args.gta_min_focus}: {len(made) - len(keep)} of {len(made)} utterances dropped')
+        made = made.subset(keep)
+    return made
+
+
 def build_parser():
     import argparse
     from .hparams import DEFAULT_HPARAMS
@@ -426,6 +640,7 @@ def build_parser():
     from .frontend import add_condition_arguments, add_features_argument
     add_condition_arguments(parser, 'the files')
     add_features_argument(parser, 'the files')
+    add_gta_arguments(parser)
     return parser
 
 
@@ -436,6 +651,7 @@ def main(argv=None):
     from .hparams import hparams as hp
     args = build_parser().parse_args(argv)
     conditioning = condition_arguments(args)
+    want_gta = gta_arguments(args)
     hp.configure(args.hp_file)
     if not torch.cuda.is_available():
         raise RuntimeError('the preprocessing runs on an MI355X only (no CPU path)')
@@ -444,9 +660,13 @@ def main(argv=None):
         raise FileNotFoundError(f'no *.wav files in {args.wav_dir}')
     corpus = DeviceCorpus.from_wavs(wavs, hp, 'cuda', batch_clips=args.batch_clips, resample=args.resample, features=args.features,
                                     **conditioning)
+    if want_gta:
+        corpus = gta_from_arguments(corpus, args)
     listing = corpus.save(args.out_dir)
     print(f'{len(corpus)} utterances of {len(wavs)} files | {corpus.hours:.3f} hours | {corpus.n_clipped} clipped samples | '
-          f'{corpus.bits} bits {"mu-law" if corpus.mu_law else "linear"} | {corpus.features} features | {listing}')
+          f'{corpus.bits} bits {"mu-law" if corpus.mu_law else "linear"} | {corpus.features} features'
+          f'{" | GTA mels in mel_gta/" if corpus.gta_made else ""} | {listing}')
+    return listing
 
 
 if __name__ == "__main__":

@@ -33,6 +33,34 @@ def load_symbols(path: str) -> List[str]:
     return ['_', '~'] + sorted(chars)
 
 
+def read_metadata(path: str) -> Dict[str, str]:
+    """The reference's training list (``audio-000001.npy|mel-000001.npy|46200|168|text|pinyin``) as ``{key: pinyin}``: the key is the
+    stem of field 0 with a leading ``audio-`` removed (the clip ``000001.wav`` the preprocessor made it from), the pinyin the last
+    field.  ``load_symbols`` on the same file gives the symbol table."""
+    import os
+    out = {}
+    with open(path, 'r', encoding='utf-8') as f:
+        for line in f:
+            parts = line.strip().split('|')
+            if len(parts) < 2 or not parts[0].strip():
+                continue
+            key = os.path.splitext(os.path.basename(parts[0].strip()))[0]
+            out[key[len('audio-'):] if key.startswith('audio-') else key] = parts[-1].strip()
+    return out
+
+
+def metadata_sequences(metadata: Dict[str, str], stems: Sequence[str], symbols: Sequence[str], source: str = 'the metadata') -> List[List[int]]:
+    """The id sequence of every clip of ``stems`` (a clip's stem looks up its line of ``read_metadata``); a stem without a line is a
+    ``ValueError`` that names it."""
+    seqs = []
+    for stem in stems:
+        key = stem[len('audio-'):] if stem.startswith('audio-') else stem
+        if key not in metadata:
+            raise ValueError(f'clip {stem!r} has no line in {source}')
+        seqs.append(text_to_sequence(metadata[key], symbols))
+    return seqs
+
+
 def text_to_sequence(pinyin, symbols: Sequence[str]) -> List[int]:
     """``utils/text.py:18-31``: a string is split at single spaces, tokens outside the table are dropped, ``~`` (EOS) is appended."""
     table = {s: i for i, s in enumerate(symbols)}
@@ -81,6 +109,14 @@ def pack_text(sequences, seeds):
     if seeds_a.shape != (B,):
         raise _cabi.WrnnError(_cabi.ERR_INVALID, f'{seeds_a.size} seeds for {B} utterances')
     return ids, tx, seeds_a
+
+
+def pad_gta_target(target: np.ndarray, r: int, max_abs_value: float) -> np.ndarray:
+    """A (T, num_mels) target with T brought up to a multiple of ``r`` by rows of ``-max_abs_value``: the reference's
+    ``padding_targets`` (``tacotron/feeder.py``), what ``synthesize(gta_targets=...)`` feeds the decoder."""
+    if target.shape[0] % r:
+        target = np.pad(target, [(0, r - target.shape[0] % r), (0, 0)], mode='constant', constant_values=-float(max_abs_value))
+    return target
 
 
 def stream_halo(postnet_layers: int, postnet_kernel: int) -> int:
@@ -219,6 +255,7 @@ class Tacotron:
         self.native = _cabi.NativeTacotron(make_dims(device, **dims))
         self.r, self.num_mels = int(self.dims['outputs_per_step']), int(self.dims['num_mels'])
         self.halo = stream_halo(self.dims['postnet_layers'], self.dims['postnet_kernel'])
+        self.checkpoint = None   # the file ``load`` read, by name (a GTA corpus notes it)
 
     def tensor_shapes(self) -> Dict[str, tuple]:
         return self.native.tensor_shapes()
@@ -237,8 +274,11 @@ class Tacotron:
         return self
 
     def load(self, path: str) -> 'Tacotron':
+        import os
         with np.load(path, allow_pickle=False) as z:
-            return self.load_state({k: z[k] for k in z.files})
+            self.load_state({k: z[k] for k in z.files})
+        self.checkpoint = os.path.basename(str(path))
+        return self
 
     def synthesize(self, sequences, seeds=None, max_iters: int = 2000, gta_targets=None, prenet_dropout: bool = True, return_device: bool = False):
         """``sequences``: a list of id lists (a ragged batch; each utterance comes out as the call on it alone).  ``seeds``: one int per
@@ -265,9 +305,7 @@ class Tacotron:
                 t = np.asarray(t, dtype=np.float32)
                 if t.ndim != 2 or t.shape[1] != M or t.shape[0] < 1:
                     raise _cabi.WrnnError(_cabi.ERR_INVALID, f'target {b}: shape {t.shape}, (T >= 1, {M}) is needed')
-                if t.shape[0] % r:
-                    t = np.pad(t, [(0, r - t.shape[0] % r), (0, 0)], mode='constant', constant_values=-float(self.dims['max_abs_value']))
-                tg.append(t)
+                tg.append(pad_gta_target(t, r, float(self.dims['max_abs_value'])))
             gta_frames = np.array([t.shape[0] for t in tg], dtype=np.int32)
             gmax = int(gta_frames.max())
             packed = np.zeros((B, gmax, M), dtype=np.float32)

@@ -312,6 +312,8 @@ def build_parser():
     from .frontend import add_condition_arguments, add_features_argument
     add_condition_arguments(parser, 'the --wav_dir files')
     add_features_argument(parser, 'the --wav_dir files; a saved corpus (hp.feature_path) must hold the same ones')
+    from .dataset import add_gta_arguments
+    add_gta_arguments(parser)   # --gta_checkpoint ...: GTA mels for the --wav_dir corpus; --gta / -g above stays what it is
     parser.add_argument('--resident', action='store_true', help='load the corpus of hp.feature_path onto the device once instead of reading '
                                                                 '.npy files every iteration')
     parser.add_argument('--train-precision', dest='train_precision', choices=('f32', 'bf16'), default='f32',
@@ -362,6 +364,8 @@ def main(argv=None):
         raise ValueError('--score_pitch extends --score_at_checkpoint: give both')
     conditioning = condition_arguments(args)
     sparsify = sparsity_schedule(args)
+    from .dataset import gta_arguments
+    want_gta = gta_arguments(args)
     hp.configure(args.hp_file)
     if not args.synthetic and not args.wav_dir:
         from .dataset import check_saved_features
@@ -388,6 +392,9 @@ def main(argv=None):
             raise FileNotFoundError(f'no *.wav files in {args.wav_dir}')
         corpus = DeviceCorpus.from_wavs(wavs, hp, 'cuda', resample=args.resample, features=args.features, **conditioning)
         print(f'{len(corpus)} utterances of {len(wavs)} files | {corpus.hours:.3f} hours | {corpus.n_clipped} clipped samples')
+        if want_gta:   # train on the mels the Tacotron will hand the vocoder; nothing is written
+            from .dataset import gta_from_arguments
+            corpus = gta_from_arguments(corpus, args)
         train, held_out = corpus.split(hp.voc_test_samples)
         test = held_out.pairs()
     else:
